@@ -26,6 +26,8 @@ GEMM — the rate at which MI values, not decisions, are produced) and `job` (th
 on the HOST -> both tsv files on disk: `h2d_ms`, Hamming weights, cold MI pass, `tsv_write_s`, short-range model + ARACNE), the
 `adversarial` workload; last, `cpu_baseline` on the host cores (rank 0, N = 1 only).
 With N > 1 the line carries `per_rank` (compute_ms, exposed_gather_ms, bytes_sent of every rank).
+`--dump-outputs DIR` writes the link tables of the LAST timed step as .npy files right after the timed region (dump_outputs), so that
+two builds can be compared output for output on the same seeded workload.
 """
 import argparse
 import json
@@ -91,7 +93,42 @@ def parse():
     ap.add_argument("--strict-exit", action="store_true", help="N > 1: exit code 3 when the sr_tail leg is abandoned or fails AFTER rank 0 has printed the line (default 0: the line of "
                                                                 "the timed region is complete and says in `sr_tail.note` what happened to the leg; a launcher that drops the line of a non-zero exit would lose the measurement)")
     ap.add_argument("--sustain-s", type=float, default=10.0, help="N = 1: keep stepping after the timed region until this many seconds of steps have run")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed region, write the link tables of the last timed step (what a caller "
+                    "of the timed path receives on rank 0) as DIR/<table>_<column>.npy: see dump_outputs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.L > 1 << 24:
+        ap.error("--dump-outputs stores SNP indices as float32, exact up to --L 2^24")
+    return args
+
+
+DUMP_ROWS = 1_250_000   # rows kept per table by --dump-outputs: 24 bytes a row (a, b: float32, MI, row: float64), 60 MB for both tables at most
+DUMP_SEED = 1988
+
+
+def dump_outputs(outdir, tables):
+    """--dump-outputs: `tables` = {"sr": (a, b, MI), "lr": (a, b, MI)}, the device tensors the timed path hands its caller on rank 0
+    (0-based SNP indices, fp64 MI; on one rank views of the engine's own tables, valid until its next pass), written as
+    DIR/{sr,lr}_{a,b,mi,row}.npy + DIR/n_rows.npy ([n_sr, n_lr]).  A table of more than DUMP_ROWS rows is represented by a fixed seeded
+    sample of its rows, in table order; `row` holds their positions in the table (all of them when it is not sampled)."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    n_rows = []
+    for name in ("sr", "lr"):
+        a, b, mi = tables[name]
+        n = int(mi.numel())
+        n_rows.append(n)
+        rows = np.arange(n)
+        if n > DUMP_ROWS:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+            idx = torch.from_numpy(rows).to(mi.device)
+            a, b, mi = (t.index_select(0, idx) for t in (a, b, mi))
+        cols = dict(a=a.cpu().numpy().astype(np.float32), b=b.cpu().numpy().astype(np.float32), mi=mi.cpu().numpy().astype(np.float64),
+                    row=rows.astype(np.float64))
+        for col, v in cols.items():
+            np.save(os.path.join(outdir, f"{name}_{col}.npy"), v)
+    np.save(os.path.join(outdir, "n_rows.npy"), np.array(n_rows, dtype=np.float64))
 
 
 def cpu_baseline(states_np, hdw, r, uqe, N, sample):
@@ -513,6 +550,8 @@ def inproc_main(args):
             acc["per_engine_ms"] += np.asarray(info["per_engine_ms"])
         sync()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"sr": engs[0].links_view(0), "lr": engs[0].links_view(1)})
         K = args.steps
         out = dict(metric="MI SNP-pairs/sec", value=pairs * K / dt, unit="pairs/s", n_gpus=len(set(devs)), steps=K, warmup=args.warmup, ms_per_step=dt / K * 1e3,
                    higher_is_better=True, scaling="strong", vs_baseline=None, dtype="i8", data="synthetic",
@@ -665,6 +704,7 @@ def main():
 
     rk_acc = dict(compute_ms=0.0, gather_begin_ms=0.0, exposed_gather_ms=0.0, bytes_sent=0, steps=0)
     cold = not args.warm
+    last = {}   # --dump-outputs: the tables of the latest step (rank 0)
 
     def step(accumulate_timing, reset=None):
         if cold if reset is None else reset:
@@ -694,6 +734,8 @@ def main():
         if out is not None:
             result["n_sr"] = int(out["sr"][2].numel())
             result["n_lr"] = int(out["lr"][2].numel())
+            if args.dump_outputs:
+                last["tables"] = out
 
     def fence():
         if world > 1:
@@ -719,6 +761,8 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:   # (before any later pass overwrites the engine's tables)
+        dump_outputs(args.dump_outputs, last.pop("tables"))
     counters_timed = eng.counters()
     links_timed = dict(result)
     per_rank = None

@@ -71,6 +71,34 @@ def test_bench_multi_rank_rehearsal():
     assert sent < 0.6 * 16 * (one["links"]["n_sr"] + one["links"]["n_lr"]) * 3 / 4 + 16 * one["links"]["n_lr"]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR`: the link tables of the last timed step as float32 / float64 .npy files, 64 MB at most, the short-range table
+    (~14 M rows at this shape) as a seeded sample of its rows; the same arguments dump the same files, and two ranks (phased gather to
+    rank 0) the same tables as one."""
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = ["--steps", "2", "--warmup", "1", "--no-extra-legs", "--no-cpu-baseline", "--L", "40000", "--N", "2000", "--max-blk-sz", "5000"]
+    runs = {}
+    for tag, gpus in (("one", ["--gpus", "1"]), ("again", ["--gpus", "1"]), ("two", ["--gpus", "2", "--backend", "gloo"])):
+        line = _bench_line([sys.executable, os.path.join(root, "bench.py")] + gpus + base + ["--dump-outputs", str(tmp_path / tag)], 600)
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        runs[tag] = (line, {f[:-4]: np.load(tmp_path / tag / f) for f in os.listdir(tmp_path / tag)})
+    line, d = runs["one"]
+    assert sorted(d) == sorted(["n_rows"] + [f"{t}_{c}" for t in ("sr", "lr") for c in ("a", "b", "mi", "row")])
+    assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+    assert sum(os.path.getsize(tmp_path / "one" / f) for f in os.listdir(tmp_path / "one")) <= 64e6
+    assert d["n_rows"].tolist() == [line["links"]["n_sr"], line["links"]["n_lr"]]
+    for t, n in zip(("sr", "lr"), d["n_rows"]):
+        rows = d[f"{t}_row"]
+        assert all(len(d[f"{t}_{c}"]) == len(rows) for c in ("a", "b", "mi"))
+        assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < n
+        assert np.isfinite(d[f"{t}_mi"]).all() and (d[f"{t}_a"] != d[f"{t}_b"]).all()
+    assert len(d["sr_row"]) < d["n_rows"][0] and len(d["lr_row"]) == d["n_rows"][1]
+    for tag in ("again", "two"):
+        o = runs[tag][1]
+        assert sorted(o) == sorted(d) and all(np.array_equal(o[k], d[k]) for k in d), tag
+
+
 def test_bench_line_carries_roofline_hamming_and_the_scaling_model():
     """r06: `roofline_hamming` (the Hamming stage priced: its GEMM against the int8 peak on executed operations, the kernels around it against HBM, the
     rest of the call as host time) and `scaling_model` (every share of the N = 1, 2, 4, 8 deals run alone on this GPU + a modelled gather; marked as a model)."""

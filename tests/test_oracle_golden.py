@@ -4,6 +4,11 @@ import numpy as np
 import c_oracle
 import ldw_oracle as orc
 
+# MI values of the numpy oracle against the committed ones: the last bits follow the host CPU (OpenBLAS picks its dgemm kernel, and with it
+# the summation order of the joint sums, by CPU model; numpy's log has AVX-512 and generic paths).  Across those kernels the values of
+# these fixtures move by at most 8.8e-16 (MI <= 0.69); counts, positions and row order do not move at all and are compared exactly.
+MI_ATOL = 5e-15
+
 
 def test_encoding_and_counts(sample):
     st = sample["states"]
@@ -30,7 +35,7 @@ def test_hamming_weights_golden(sample):
 def test_mi_single_block_golden(sample):
     st, idx = sample["states"], np.arange(1268)
     MI = orc.mi_block_faithful(st, sample["hdw"], sample["r"], sample["uqe"], idx, idx)
-    assert np.array_equal(MI[np.ix_(sample["sub_r"], sample["sub_c"])], sample["MI_single_sub"])
+    np.testing.assert_allclose(MI[np.ix_(sample["sub_r"], sample["sub_c"])], sample["MI_single_sub"], rtol=0, atol=MI_ATOL)
     np.testing.assert_allclose(MI.sum(axis=0), sample["MI_single_colsum"], rtol=0, atol=1e-12)
     off = MI[~np.eye(1268, dtype=bool)]
     assert 1.7e-13 < off.min() < 1.9e-13 and abs(off.max() - 0.682443935150819) < 1e-12
@@ -78,12 +83,13 @@ def test_link_digests_golden(sample):
                                      lr_retain_links=1e5, max_blk_sz=1000, do_srp=False)
     assert abs(res.lr_links_approx - float(sample["multi_lr_approx"])) < 1e-9
     assert len(res.lr_rows["MI"]) == int(sample["multi_lr_n"])
-    for k in ("pos1", "pos2", "len", "MI"):
+    for k in ("pos1", "pos2", "len"):
         assert np.array_equal(np.asarray(res.lr_rows[k], dtype=float)[:200], sample[f"multi_lr_{k}_head"])
+    np.testing.assert_allclose(np.asarray(res.lr_rows["MI"])[:200], sample["multi_lr_MI_head"], rtol=0, atol=MI_ATOL)
     for ci in (1, 2, 3):
         d = res.sr_links_by_clust[ci - 1]
         assert len(d["MI"]) == int(sample[f"multi_sr{ci}_n"])
-        assert np.array_equal(np.asarray(d["MI"])[-200:], sample[f"multi_sr{ci}_MI_tail"])
+        np.testing.assert_allclose(np.asarray(d["MI"])[-200:], sample[f"multi_sr{ci}_MI_tail"], rtol=0, atol=MI_ATOL)
 
 
 def test_kat_elementwise(kat):
