@@ -109,6 +109,27 @@ int ldw_encode_alignment(ldw_ctx *ctx, const char *chars, int64_t N, int64_t L_t
  * "everything else" per column: allele_counts_out is 5 x L_total int32, column-major like `allele_counts`.
  * The SNP filter itself (:104-166) is O(L_total) host logic on these counts. */
 int ldw_alignment_scan(ldw_ctx *ctx, const char *chars, int64_t N, int64_t L_total, int32_t *allele_counts_out);
+/* ---- the native FASTA feeder: a FASTA file (plain or gzip, read with zlib) streamed into the device scan and encoder without the
+ * whole N x L_total character matrix ever existing, on the host or on the device (src/getACGTNsites.cpp:13-291).  Records: a header
+ * line starts with '>', the name is its first whitespace-delimited token ("" if none); other lines are sequence with trailing '\r' /
+ * '\n' stripped, blank lines skipped, every other byte kept; lines before the first header are skipped.  Errors (LDW_ERR_ARG):
+ * "File does not contain any sequences!" and "sequences are of different lengths" (an empty record counts as one of length 0).
+ * Names come NUL-separated (each followed by '\0'); names may be NULL, names_bytes receives the size needed (LDW_ERR_SIZE if
+ * names_cap is smaller).  chunk_rows / io_bytes 0: the defaults (rows of about 32 MiB, 4 MiB reads). */
+/* host only, no context and no GPU: parse the whole file and return its shape and names — for callers sizing buffers, and CPU tests */
+int ldw_fasta_probe(const char *path, int64_t io_bytes, int64_t *N, int64_t *L_total, char *names, int64_t names_cap,
+                    int64_t *names_bytes);
+/* pass 1: stream the file, accumulate per-column allele counts on the device; keep the 4-bit packed states resident if they fit in
+ * keep_bytes (0: never, < 0: automatic — at most 8 GiB and a quarter of the free device memory).  A new scan discards the last one. */
+int ldw_fasta_scan(ldw_ctx *ctx, const char *path, int64_t chunk_rows, int64_t io_bytes, int64_t keep_bytes, int64_t *N_out,
+                   int64_t *L_total_out);
+/* the scan's A/C/G/T/other counts: 5 x L_total int32, column-major like `allele_counts` (ldw_alignment_scan) */
+int ldw_fasta_counts(ldw_ctx *ctx, int32_t *allele_counts_out);
+int ldw_fasta_names(ldw_ctx *ctx, char *names, int64_t cap, int64_t *names_bytes);
+/* pass 2: encode the 1-based retained columns pos[n_pos] into the context's alignment (states [n_pos][N]); from the packed copy if the
+ * scan kept one (released here), else by reading the file again (LDW_ERR_STATE if its size, modification time, N or L_total changed);
+ * LDW_ERR_STATE without a scan.  acgtn_table_out as in ldw_encode_alignment (may be NULL). */
+int ldw_fasta_encode(ldw_ctx *ctx, const int32_t *pos, int64_t n_pos, int32_t *acgtn_table_out);
 /* per-SNP state counts (5 x L, column-major like ACGTN_table) of the resident alignment */
 int ldw_state_counts(ldw_ctx *ctx, int32_t *counts_out);
 /* copy the resident states back (tests) */

@@ -54,6 +54,11 @@ _SIGS = {
     "ldw_encode_alignment": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p]),
     "ldw_alignment_scan": (C.c_int, [_p, _p, _i64, _i64, _p]),
     "ldw_state_counts": (C.c_int, [_p, _p]),
+    "ldw_fasta_probe": (C.c_int, [C.c_char_p, _i64, C.POINTER(_i64), C.POINTER(_i64), C.c_char_p, _i64, C.POINTER(_i64)]),
+    "ldw_fasta_scan": (C.c_int, [_p, C.c_char_p, _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "ldw_fasta_counts": (C.c_int, [_p, _p]),
+    "ldw_fasta_names": (C.c_int, [_p, C.c_char_p, _i64, C.POINTER(_i64)]),
+    "ldw_fasta_encode": (C.c_int, [_p, _p, _i64, _p]),
     "ldw_get_alignment": (C.c_int, [_p, _p]),
     "ldw_hamming_weights": (C.c_int, [_p, C.c_int32, _p, _p]),
     "ldw_hamming_counts": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, _p]),

@@ -10,6 +10,8 @@
 
 #include <thread>
 #include "ldw_internal.h"
+#include "ldw_dev.h"
+#include "ldw_fasta.h"
 
 // ------------------------------------------------------------------------------------------------
 // error plumbing
@@ -279,17 +281,7 @@ __global__ void k_unpad_states(const uint8_t *__restrict__ src, uint8_t *__restr
         dst[a * N + s] = src[a * Npad + s];
 }
 
-// 5-state encoder (src/getACGTNsites.cpp:229-265): chars [N][L_total] -> states [n_pos][Npad]
-__device__ __forceinline__ uint8_t encode_char(unsigned char c) {
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return 4;
-    }
-}
-
+// 5-state encoder (src/getACGTNsites.cpp:229-265, encode_char in ldw_dev.h): chars [N][L_total] -> states [n_pos][Npad]
 __global__ void k_encode(const char *__restrict__ chars, int64_t N, int64_t L_total, const int32_t *__restrict__ pos,
                          int64_t n_pos, uint8_t *__restrict__ states, int64_t Npad) {
     // tile transpose through LDS: 64 positions x 64 sequences per workgroup, coalesced on both sides
@@ -324,6 +316,79 @@ __global__ __launch_bounds__(256) void k_column_counts(const char *__restrict__ 
     }
 #pragma unroll
     for (int x = 0; x < 5; ++x) counts[j * 5 + x] = c[x];
+}
+
+// ---- the native FASTA feeder's kernels (host side: ldw_fasta.cpp) ----
+// k_fasta_count_pack: one launch per chunk of rows [rows][Lp] (rows padded to Lp = L rounded up to 16 bytes by the reader).  A lane owns 16
+// consecutive columns — one 16-byte load per row — for the whole launch, so the counts [Lp][5] are read, added to and written back without
+// atomics (launches on one stream do not overlap).  A/C/G/T are counted, the fifth state is what is left.  With packed non-null the chunk's
+// states also go out 4 bits each (8 bytes per lane and row), the device copy ldw_fasta_encode reads instead of the file.
+constexpr int FA_COLS = 16;
+__global__ __launch_bounds__(256) void k_fasta_count_pack(const uint8_t *__restrict__ chunk, int64_t rows, int64_t L, int64_t Lp,
+                                                          int32_t *__restrict__ counts, uint8_t *__restrict__ packed) {
+    const int64_t j0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * FA_COLS;
+    if (j0 >= L) return;
+    int c[FA_COLS][4] = {};
+    for (int64_t r = 0; r < rows; ++r) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(chunk + r * Lp + j0);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        uint32_t pk[2] = {0, 0};
+#pragma unroll
+        for (int k = 0; k < FA_COLS; ++k) {
+            const uint32_t st = encode_char((unsigned char)(w[k >> 2] >> (8 * (k & 3))));
+#pragma unroll
+            for (int x = 0; x < 4; ++x) c[k][x] += st == (uint32_t)x;
+            pk[k >> 3] |= st << (4 * (k & 7));
+        }
+        if (packed) *reinterpret_cast<uint2 *>(packed + r * (Lp / 2) + j0 / 2) = make_uint2(pk[0], pk[1]);
+    }
+    // the lane's 16 columns are 80 consecutive int32 of the counts (320 bytes, 64-byte aligned; the buffer is padded to Lp columns): 20
+    // 16-byte read-modify-writes instead of 80 scattered dwords (a 1-row chunk of 2.2 M columns: 54 -> 36 us)
+    int add[FA_COLS * 5];
+#pragma unroll
+    for (int k = 0; k < FA_COLS; ++k) {
+#pragma unroll
+        for (int x = 0; x < 4; ++x) add[k * 5 + x] = c[k][x];
+        add[k * 5 + 4] = (int)rows - (c[k][0] + c[k][1] + c[k][2] + c[k][3]);
+    }
+    int4 *o = reinterpret_cast<int4 *>(counts + j0 * 5);
+#pragma unroll
+    for (int q = 0; q < FA_COLS * 5 / 4; ++q) {
+        int4 v = o[q];
+        v.x += add[4 * q];
+        v.y += add[4 * q + 1];
+        v.z += add[4 * q + 2];
+        v.w += add[4 * q + 3];
+        o[q] = v;
+    }
+}
+
+// k_fasta_encode_rows: the retained columns of the sequences s0 .. s_end (one chunk of rows, or all of them from the packed copy) into
+// states [n_pos][Npad], transposed through LDS in tiles of 64 positions x 64 sequences as k_encode; sequences from N on are the 255 padding
+// (the launch of the last chunk runs to Npad, so the padding is written once).
+template <bool Packed>
+__global__ __launch_bounds__(256) void k_fasta_encode_rows(const uint8_t *__restrict__ src, int64_t stride, int64_t src_s0, int64_t s0,
+                                                           int64_t s_end, int64_t N, const int32_t *__restrict__ pos, int64_t n_pos,
+                                                           uint8_t *__restrict__ states, int64_t Npad) {
+    __shared__ uint8_t tile[64][65];
+    const int64_t p0 = (int64_t)blockIdx.x * 64, sb = s0 + (int64_t)blockIdx.y * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int64_t p = p0 + tx;
+    const int64_t col = p < n_pos ? (int64_t)pos[p] - 1 : 0;
+    for (int i = ty; i < 64; i += 4) {   // i: sequence within the tile, tx: position
+        const int64_t s = sb + i;
+        uint8_t v = 255;
+        if (s < N && s < s_end && p < n_pos) {
+            const uint8_t *row = src + (s - src_s0) * stride;
+            v = Packed ? (uint8_t)((row[col >> 1] >> (4 * (col & 1))) & 15) : encode_char(row[col]);
+        }
+        tile[i][tx] = v;
+    }
+    __syncthreads();
+    for (int i = ty; i < 64; i += 4) {   // i: position within the tile, tx: sequence
+        const int64_t q = p0 + i, s = sb + tx;
+        if (q < n_pos && s < s_end) states[q * Npad + s] = tile[tx][i];
+    }
 }
 
 // per-SNP state counts and fixed-point weighted marginals.  One wave per SNP; each lane reads 4
@@ -398,6 +463,24 @@ int launch_state_counts(ldw_ctx *c) {
     if (int rc = c->counts.reserve((size_t)c->L * 5 * 4)) return rc;
     hipLaunchKernelGGL(k_counts_marginals, dim3((unsigned)((c->L + 3) / 4)), dim3(256), 0, c->stream, c->states.as<uint8_t>(), c->L, c->Npad, (const int64_t *)nullptr,
                        c->counts.as<int32_t>(), (int64_t *)nullptr);
+    LDW_HIP(hipGetLastError());
+    return LDW_OK;
+}
+
+int launch_fasta_count_pack(const uint8_t *chunk, int64_t rows, int64_t L, int64_t Lp, int32_t *counts, uint8_t *packed, hipStream_t s) {
+    const int64_t lanes = (L + FA_COLS - 1) / FA_COLS;
+    hipLaunchKernelGGL(k_fasta_count_pack, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, chunk, rows, L, Lp, counts, packed);
+    LDW_HIP(hipGetLastError());
+    return LDW_OK;
+}
+
+int launch_fasta_encode_rows(bool packed, const uint8_t *src, int64_t stride, int64_t src_s0, int64_t s0, int64_t s_end, int64_t N,
+                             const int32_t *pos, int64_t n_pos, uint8_t *states, int64_t Npad, hipStream_t s) {
+    const dim3 grid((unsigned)((n_pos + 63) / 64), (unsigned)((s_end - s0 + 63) / 64));
+    if (packed)
+        hipLaunchKernelGGL(k_fasta_encode_rows<true>, grid, dim3(256), 0, s, src, stride, src_s0, s0, s_end, N, pos, n_pos, states, Npad);
+    else
+        hipLaunchKernelGGL(k_fasta_encode_rows<false>, grid, dim3(256), 0, s, src, stride, src_s0, s0, s_end, N, pos, n_pos, states, Npad);
     LDW_HIP(hipGetLastError());
     return LDW_OK;
 }
@@ -530,6 +613,7 @@ int ldw_ctx_destroy(ldw_ctx *c) {
     if (c->lr_st) (void)hipStreamSynchronize(c->lr_st);
     {
     ldw::DrainedScope drained;   // every stream that could touch this context's blocks is idle: no device-wide synchronisation per released block
+    ldw::fasta_release(c);
     ldw::DevBuf *bufs[] = {&c->srm_tmp, &c->chars, &c->states, &c->digits, &c->vfixed, &c->r, &c->uqe, &c->POS, &c->paint, &c->Mbits, &c->row0,
                            &c->slot_meta, &c->slot_pfix, &c->apx_skip, &c->snp_sup, &c->counts, &c->pfix_state, &c->G, &c->MIblk, &c->rowlist_f, &c->rowlist_t,
                            &c->idx_f, &c->idx_t, &c->lrow_f, &c->lrow_t, &c->perm_f, &c->perm_t, &c->scr_units, &c->epi_rest, &c->slot_pfix_hi, &c->glo, &c->lo_rows, &c->packs, &c->colcnt,
@@ -774,7 +858,8 @@ int ldw_fast_hadamard(ldw_ctx *c, double *MI, const double *den, const double *u
 }
 
 // ---- alignment residency ------------------------------------------------------------------------
-static int set_dims(ldw_ctx *c, int64_t L, int64_t N) {
+extern "C++" {   // (ldw_fasta.cpp sets the shape too)
+int ldw::set_dims(ldw_ctx *c, int64_t L, int64_t N) {
     LDW_REQUIRE(L > 0 && N > 0, LDW_ERR_ARG, "alignment must be non-empty (L=%lld N=%lld)", (long long)L, (long long)N);
     LDW_REQUIRE(L < (int64_t)1 << 27, LDW_ERR_ARG, "L too large (%lld)", (long long)L);
     c->L = L;
@@ -785,6 +870,7 @@ static int set_dims(ldw_ctx *c, int64_t L, int64_t N) {
     c->have_weights = false;
     c->have_meta = false;
     return c->states.reserve((size_t)L * c->Npad);
+}
 }
 
 int ldw_set_alignment(ldw_ctx *c, const uint8_t *states, int64_t L, int64_t N, int on_device) {

@@ -54,4 +54,15 @@ __host__ __device__ __forceinline__ double key_f64(uint64_t k) {
     return v;
 }
 
+// the 5-state rule of src/getACGTNsites.cpp:229-265: A/a, C/c, G/g, T/t -> 0..3, every other byte -> 4
+__host__ __device__ __forceinline__ uint8_t encode_char(unsigned char c) {
+    switch (c) {
+        case 'A': case 'a': return 0;
+        case 'C': case 'c': return 1;
+        case 'G': case 'g': return 2;
+        case 'T': case 't': return 3;
+        default: return 4;
+    }
+}
+
 }  // namespace ldw

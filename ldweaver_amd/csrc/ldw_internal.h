@@ -95,6 +95,7 @@ struct ldw_ctx {
     ldw::DevBuf states;              // uint8 [L][N]
     ldw::DevBuf chars;               // raw alignment characters [cN][cL] kept by ldw_alignment_scan
     int64_t cN = 0, cL = 0;
+    void *fasta = nullptr;           // scan state of the native FASTA feeder (ldw_fasta.hip: FastaScan), made by ldw_fasta_scan
 
     // ---- weights ----
     bool have_weights = false;
@@ -290,6 +291,7 @@ struct ldw_ctx {
 namespace ldw {
 // launchers implemented in the .hip files (all asynchronous on ctx->stream)
 int ensure_rows(ldw_ctx *ctx);
+int set_dims(ldw_ctx *ctx, int64_t L, int64_t N);   // ldw_api.hip: the shape of the resident alignment; reserves states [L][Npad]
 int launch_hist(ldw_ctx *ctx, const int32_t *idx_f, int nf, const int32_t *idx_t, int nt, const int64_t *pfix_state,
                 int quirk, int lower_only, double *MI);
 // G[t][f] = sum_k [row t has bit k][row f has bit k] * sum_j digits[j][k] 256^j over the bit matrix Mbits[rows][KW words]

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "ldw_internal.h"
+#include "ldw_fasta.h"
 
 namespace {
 
@@ -749,6 +750,7 @@ int ldw_host_trim(ldw_ctx *c, int64_t *bytes_out) {
     n += (int64_t)ldw::device_pool_trim();   // r05: + the released DEVICE blocks kept for the next context (ldw_api.hip)
     if (c) {
         if (int rc = tsv_async_join(c, nullptr, nullptr)) return rc;
+        n += ldw::fasta_trim(c);   // the FASTA feeder's pinned chunk buffers
         if (c->lr_stream == nullptr && c->pin_fetch) {
             (void)hipSetDevice(c->device);
             (void)hipHostFree(c->pin_fetch);

@@ -2,10 +2,27 @@
 from __future__ import annotations
 
 import ctypes as C
+import errno
+import os
 
 import numpy as np
 
 from . import _lib as L
+
+
+def fasta_check(code: int, path):
+    """L.check for the FASTA feeder's entries: its two input errors become the ValueErrors ``snpdat.read_fasta`` raises, an unreadable
+    path the OSError ``open`` would raise."""
+    if code == L.LDW_OK:
+        return
+    msg = L.lib().ldw_last_error().decode("utf-8", "replace")
+    if "does not contain any sequences" in msg:
+        raise ValueError("File does not contain any sequences!")
+    if "sequences are of different lengths" in msg:
+        raise ValueError("Error! sequences are of different lengths!")
+    if "cannot open" in msg:
+        raise FileNotFoundError(errno.ENOENT, msg, str(path)) if not os.path.exists(path) else OSError(msg)
+    raise L.LdwError(code, msg)
 
 
 def _is_torch(x):
@@ -289,6 +306,32 @@ class Engine:
         L.check(L.lib().ldw_alignment_scan(self._ctx, L.ptr(ch), ch.shape[0], ch.shape[1], L.ptr(out)))
         self._scanned = ch.shape
         return np.ascontiguousarray(out.T)
+
+    def fasta_scan(self, path, chunk_rows: int = 0, io_bytes: int = 0, keep_bytes: int = -1):
+        """Pass 1 of the native FASTA feeder: stream the (gz) FASTA file through the device counts, one chunk of rows at a time.  Returns
+        (names, L_total, 5 x L_total allele counts).  keep_bytes: device bytes the 4-bit packed states may take so that ``fasta_encode``
+        does not read the file again (0 never, < 0 automatic)."""
+        p = os.fsencode(path)
+        n, lt = C.c_int64(), C.c_int64()
+        fasta_check(L.lib().ldw_fasta_scan(self._ctx, p, int(chunk_rows), int(io_bytes), int(keep_bytes), C.byref(n), C.byref(lt)), path)
+        nb = C.c_int64()
+        L.check(L.lib().ldw_fasta_names(self._ctx, None, 0, C.byref(nb)))
+        buf = C.create_string_buffer(max(nb.value, 1))
+        L.check(L.lib().ldw_fasta_names(self._ctx, buf, nb.value, C.byref(nb)))
+        names = [x.decode() for x in buf.raw[:nb.value].split(b"\0")[:-1]]
+        self._fasta_n = int(n.value)
+        out = np.empty((lt.value, 5), dtype=np.int32)
+        L.check(L.lib().ldw_fasta_counts(self._ctx, L.ptr(out)))
+        return names, int(lt.value), out.T          # (a view: no second O(L_total) copy on the host)
+
+    def fasta_encode(self, pos: np.ndarray, want_table=True):
+        """Pass 2: the 1-based retained columns ``pos`` of the scanned file become the engine's alignment (from the packed copy, or the file
+        read again); returns ACGTN_table (5, n_pos)."""
+        ps = L.as_c(pos, np.int32)
+        tab = np.zeros((len(ps), 5), dtype=np.int32) if want_table else None
+        L.check(L.lib().ldw_fasta_encode(self._ctx, L.ptr(ps), len(ps), L.ptr(tab)))
+        self.L, self.N = len(ps), self._fasta_n
+        return None if tab is None else np.ascontiguousarray(tab.T)
 
     def encode_alignment(self, chars, pos: np.ndarray, want_table=True, shape=None):
         """chars: (N, L_total) bytes, or None to reuse the alignment kept by ``alignment_scan``; pos: 1-based retained
