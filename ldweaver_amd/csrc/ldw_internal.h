@@ -188,6 +188,9 @@ struct ldw_ctx {
     std::vector<int32_t> h_POS, h_paint;
     int32_t paint_min = 0, paint_max = 0;
     bool pos_sorted = true;      // POS ascends over the whole alignment (the reference's parser emits it so; any order is accepted)
+    bool pos_strict = true;      // ... strictly: the SNP index is the rank among the distinct positions (no slot array needed)
+    ldw::DevBuf pos_slot;        // otherwise int32[L]: rank of a SNP's position among the sorted distinct positions (ldw::pos_slots, built on first use)
+    int64_t n_slots = 0;         // number of distinct positions; 0 = pos_slot not built for the current meta data
     double sr_total_dist = -1;   // number of SNP pairs within sr_total_dist on the circle (sizes the short-range table once; reset with the meta data)
     int64_t sr_total = -1;
     uint64_t sr_share_key = 0;   // r05: the last SHARE of the block list a pass was sized for (hash of blocks + sr_dist) and its exact short-range row count
@@ -324,4 +327,7 @@ void warm_srp();
 int reduced_import_full(ldw_ctx *ctx, int64_t n_red, const int32_t *a, const int32_t *b, const double *MI, const uint32_t *meta, const double *srp, int64_t n_pool,
                         const int32_t *pool_a, const int32_t *pool_b, const double *pool_MI);
 void warm_post();
+// ldw_post.hip: the graph node of every SNP for consumers that work on positions (LD map, ARACNE): *slot = null and *n_nodes = L when POS
+// ascends strictly, else the device array ctx->pos_slot (SNPs sharing a position share a node) and the number of distinct positions
+int pos_slots(ldw_ctx *ctx, const int32_t **slot, int64_t *n_nodes);
 }  // namespace ldw

@@ -126,6 +126,33 @@ __global__ __launch_bounds__(256) void k_ldmap_rescale(double *__restrict__ red,
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) red[i] = (red[i] - mn) * inv_rn;
 }
 
+// Graph nodes of the position-based consumers: the rank of each SNP's position among the sorted DISTINCT positions (stable sort of h_POS, then a
+// running rank), so that SNPs sharing a position are one node like in the reference, which works on positions.  Strictly ascending POS needs
+// none (the SNP index is that rank); otherwise it is built once per ldw_set_snp_meta.
+int pos_slots(ldw_ctx *c, const int32_t **slot, int64_t *n_nodes) {
+    const int64_t L = c->L;
+    *slot = nullptr;
+    *n_nodes = L;
+    if (c->pos_strict) return LDW_OK;
+    if (c->n_slots == 0) {
+        std::vector<int32_t> ord((size_t)L), h((size_t)L);
+        for (int64_t i = 0; i < L; ++i) ord[(size_t)i] = (int32_t)i;
+        std::stable_sort(ord.begin(), ord.end(), [&](int32_t u, int32_t v) { return c->h_POS[(size_t)u] < c->h_POS[(size_t)v]; });
+        int32_t k = -1;
+        for (int64_t i = 0; i < L; ++i) {
+            if (i == 0 || c->h_POS[(size_t)ord[(size_t)i]] != c->h_POS[(size_t)ord[(size_t)i - 1]]) ++k;
+            h[(size_t)ord[(size_t)i]] = k;
+        }
+        if (int rc = c->pos_slot.reserve((size_t)L * 4)) return rc;
+        LDW_HIP(hipMemcpyAsync(c->pos_slot.p, h.data(), (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
+        LDW_HIP(hipStreamSynchronize(c->stream));   // (`h` goes out of scope)
+        c->n_slots = (int64_t)k + 1;
+    }
+    *slot = c->pos_slot.as<int32_t>();
+    *n_nodes = c->n_slots;
+    return LDW_OK;
+}
+
 static int links_ready(ldw_ctx *c, const char *who) {
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(c->have_meta, LDW_ERR_STATE, "%s: ldw_set_snp_meta has not been called", who);
@@ -282,45 +309,29 @@ int ldw_ldmap(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t *n_
     const int windowed = (from != 0 || to != 0) ? 1 : 0;
     LDW_REQUIRE(!windowed || (to > from && from >= 0), LDW_ERR_ARG, "ldw_ldmap: <to> must be greater than <from> and both positive");
     LDW_REQUIRE(reducer >= 0, LDW_ERR_ARG, "ldw_ldmap: reducer must be >= 0 (0 = default)");
-    const int64_t L = c->L, nl = c->n_lr, ns = c->n_sr;
+    const int64_t nl = c->n_lr, ns = c->n_sr;
     LDW_REQUIRE(nl + ns > 0, LDW_ERR_STATE, "ldw_ldmap: no links");
     // r05: the rank of a position in pos_vec is its rank among the sorted distinct positions.  With POS strictly ascending (what the reference's parser
-    // emits) that is the SNP order; otherwise (any order, repeated positions) through a slot per SNP, built once per call on the host.
+    // emits) that is the SNP order; otherwise (any order, repeated positions) through a slot per SNP (ldw::pos_slots).
     const int32_t *d_slot = nullptr;
-    {
-        bool strict = c->pos_sorted;
-        for (int64_t i = 1; i < L && strict; ++i) strict = c->h_POS[(size_t)i] > c->h_POS[(size_t)i - 1];
-        if (!strict) {
-            std::vector<int32_t> ord((size_t)L), slot((size_t)L);
-            for (int64_t i = 0; i < L; ++i) ord[(size_t)i] = (int32_t)i;
-            std::stable_sort(ord.begin(), ord.end(), [&](int32_t u, int32_t v) { return c->h_POS[(size_t)u] < c->h_POS[(size_t)v]; });
-            int32_t k = -1;
-            for (int64_t i = 0; i < L; ++i) {
-                if (i == 0 || c->h_POS[(size_t)ord[(size_t)i]] != c->h_POS[(size_t)ord[(size_t)i - 1]]) ++k;
-                slot[(size_t)ord[(size_t)i]] = k;
-            }
-            if (int rc = c->srd_lower.reserve((size_t)L * 4)) return rc;
-            LDW_HIP(hipMemcpyAsync(c->srd_lower.p, slot.data(), (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
-            LDW_HIP(hipStreamSynchronize(c->stream));   // (`slot` goes out of scope)
-            d_slot = c->srd_lower.as<int32_t>();
-        }
-    }
+    int64_t n_nodes = 0;
+    if (int rc = pos_slots(c, &d_slot, &n_nodes)) return rc;
     // ---- pos_vec: which SNPs occur in a link, and their rank ----
-    if (int rc = c->srm_cnt.reserve((size_t)(L + 1) * 4 * 2)) return rc;
-    int32_t *used = c->srm_cnt.as<int32_t>(), *rank = used + L + 1;
-    LDW_HIP(hipMemsetAsync(used, 0, (size_t)(L + 1) * 4, c->stream));
+    if (int rc = c->srm_cnt.reserve((size_t)(n_nodes + 1) * 4 * 2)) return rc;
+    int32_t *used = c->srm_cnt.as<int32_t>(), *rank = used + n_nodes + 1;
+    LDW_HIP(hipMemsetAsync(used, 0, (size_t)(n_nodes + 1) * 4, c->stream));
     const int32_t *POS = c->POS.as<int32_t>();
     auto grid_of = [](int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 16384)); };
     if (nl > 0) hipLaunchKernelGGL(k_mark_used, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), nl, POS, from, to, windowed, used, d_slot);
     if (ns > 0) hipLaunchKernelGGL(k_mark_used, grid_of(ns), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), ns, POS, from, to, windowed, used, d_slot);
     LDW_HIP(hipGetLastError());
     size_t sb = 0;
-    LDW_HIP(prim_exclusive_sum(nullptr, sb, used, rank, (int)(L + 1), c->stream));
+    LDW_HIP(prim_exclusive_sum(nullptr, sb, used, rank, (int)(n_nodes + 1), c->stream));
     if (int rc = c->scratch.reserve(sb)) return rc;
     sb = c->scratch.cap;
-    LDW_HIP(prim_exclusive_sum(c->scratch.p, sb, used, rank, (int)(L + 1), c->stream));
+    LDW_HIP(prim_exclusive_sum(c->scratch.p, sb, used, rank, (int)(n_nodes + 1), c->stream));
     int32_t n_pos = 0;
-    LDW_HIP(hipMemcpyAsync(&n_pos, rank + L, 4, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(&n_pos, rank + n_nodes, 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     // reducer = round(length(pos_vec) / 1e3) by default (:83-87); R's round() is half-to-even
     int32_t r = reducer > 0 ? reducer : (int32_t)std::nearbyint((double)n_pos / 1e3);

@@ -740,11 +740,12 @@ __global__ __launch_bounds__(256) void k_sr_pool(const int32_t *__restrict__ sa,
 // ------------------------------------------------------------------------------------------------
 // ARACNE
 // ------------------------------------------------------------------------------------------------
+// Nodes are positions (runARACNE works on pos1 / pos2): slot (null: the SNP index itself) maps a SNP to its distinct-position node (ldw::pos_slots)
 __global__ __launch_bounds__(256) void k_ar_edges(const int32_t *__restrict__ pa, const int32_t *__restrict__ pb,
                                                   const double *__restrict__ pmi, int64_t n, uint64_t *__restrict__ key,
-                                                  double *__restrict__ val) {
+                                                  double *__restrict__ val, const int32_t *__restrict__ slot) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const uint64_t a = (uint32_t)pa[i], b = (uint32_t)pb[i];
+        const uint64_t a = (uint32_t)(slot ? slot[pa[i]] : pa[i]), b = (uint32_t)(slot ? slot[pb[i]] : pb[i]);
         const double m = pmi[i];
         key[2 * i] = (a << 32) | b;
         val[2 * i] = m;
@@ -753,10 +754,10 @@ __global__ __launch_bounds__(256) void k_ar_edges(const int32_t *__restrict__ pa
     }
 }
 
-// off[v] = first directed edge whose node is >= v, v = 0..L
-__global__ void k_ar_offsets(const uint64_t *__restrict__ key, int64_t n2, int64_t L, int64_t *__restrict__ off) {
+// off[v] = first directed edge whose node is >= v, v = 0..n_nodes
+__global__ void k_ar_offsets(const uint64_t *__restrict__ key, int64_t n2, int64_t n_nodes, int64_t *__restrict__ off) {
     const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v > L) return;
+    if (v > n_nodes) return;
     int64_t lo = 0, hi = n2;
     while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
@@ -768,16 +769,19 @@ __global__ void k_ar_offsets(const uint64_t *__restrict__ key, int64_t n2, int64
 
 // One wave per link (X,Z) = (to side, from side): lanes stride over the shorter neighbour list and binary-search the
 // longer one.  flag = 0 iff some common neighbour Y has MI(X,Z) < MI(X,Y) and MI(X,Z) < MI(Z,Y)  (src/computeMI.cpp:63-77).
+// A (node, neighbour) pair joined by several pool rows takes the MI of the first of them in pool order, like the reference's match() of a
+// common neighbour in matX / matZ: the stable sort keeps such entries in pool order, so the iterated list skips all but the first of a run of
+// equal keys and the lower bound in the searched list lands on the first.
 __global__ __launch_bounds__(256) void k_ar_check(const int64_t *__restrict__ red_row, int64_t n_red,
                                                   const int32_t *__restrict__ sa, const int32_t *__restrict__ sb,
                                                   const double *__restrict__ smi, const uint64_t *__restrict__ key,
                                                   const double *__restrict__ val, const int64_t *__restrict__ off,
-                                                  uint8_t *__restrict__ flags) {
+                                                  uint8_t *__restrict__ flags, const int32_t *__restrict__ slot) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= n_red) return;
     const int64_t row = red_row[w];
-    const int32_t X = sb[row], Z = sa[row];
+    const int32_t X = slot ? slot[sb[row]] : sb[row], Z = slot ? slot[sa[row]] : sa[row];
     const double mi0 = smi[row];
     int64_t xs = off[X], xe = off[X + 1], zs = off[Z], ze = off[Z + 1];
     if (xe - xs > ze - zs) {   // iterate over the shorter list
@@ -787,6 +791,7 @@ __global__ __launch_bounds__(256) void k_ar_check(const int64_t *__restrict__ re
     bool indirect = false;
     for (int64_t i = xs + lane; i < xe && !indirect; i += 64) {
         const uint32_t y = (uint32_t)key[i];
+        if (i > xs && key[i] == key[i - 1]) continue;   // not the first pool row of this (node, neighbour)
         if (!(mi0 < val[i])) continue;
         int64_t lo = zs, hi = ze;
         while (lo < hi) {
@@ -1251,16 +1256,20 @@ int ldw_aracne_device(ldw_ctx *c, int64_t capacity, uint8_t *flags_out) {
     if (nr == 0) return LDW_OK;
     LDW_REQUIRE(flags_out, LDW_ERR_ARG, "ldw_aracne_device: null output");
     LDW_REQUIRE(np > 0, LDW_ERR_STATE, "ldw_aracne_device: no pool (call ldw_sr_pvalues or ldw_lr_tukey first)");
-    const int64_t n2 = 2 * np, L = c->L;
+    const int64_t n2 = 2 * np;
+    // nodes: SNP indices while POS ascends strictly, else distinct positions (SNPs sharing a position are one node, as in the reference)
+    const int32_t *d_slot = nullptr;
+    int64_t n_nodes = 0;
+    if (int rc = pos_slots(c, &d_slot, &n_nodes)) return rc;
     if (int rc = c->ar_key.reserve((size_t)n2 * 8)) return rc;
     if (int rc = c->ar_key2.reserve((size_t)n2 * 8)) return rc;
     if (int rc = c->ar_val.reserve((size_t)n2 * 8)) return rc;
     if (int rc = c->ar_val2.reserve((size_t)n2 * 8)) return rc;
-    if (int rc = c->ar_off.reserve((size_t)(L + 2) * 8)) return rc;
+    if (int rc = c->ar_off.reserve((size_t)(n_nodes + 2) * 8)) return rc;
     if (int rc = c->ar_flags.reserve((size_t)nr)) return rc;
     const int grid = (int)std::min<int64_t>((np + 255) / 256, 16384);
     hipLaunchKernelGGL(k_ar_edges, dim3(grid), dim3(256), 0, c->stream, c->pool_a.as<int32_t>(), c->pool_b.as<int32_t>(),
-                       c->pool_mi.as<double>(), np, c->ar_key.as<uint64_t>(), c->ar_val.as<double>());
+                       c->pool_mi.as<double>(), np, c->ar_key.as<uint64_t>(), c->ar_val.as<double>(), d_slot);
     size_t tb = 0;
     LDW_HIP(prim_sort_pairs(nullptr, tb, c->ar_key.as<uint64_t>(), c->ar_key2.as<uint64_t>(), c->ar_val.as<double>(),
                                                c->ar_val2.as<double>(), n2, 0, 64, c->stream));
@@ -1268,14 +1277,14 @@ int ldw_aracne_device(ldw_ctx *c, int64_t capacity, uint8_t *flags_out) {
     tb = c->scratch.cap;
     LDW_HIP(prim_sort_pairs(c->scratch.p, tb, c->ar_key.as<uint64_t>(), c->ar_key2.as<uint64_t>(),
                                                c->ar_val.as<double>(), c->ar_val2.as<double>(), n2, 0, 64, c->stream));
-    hipLaunchKernelGGL(k_ar_offsets, dim3((unsigned)((L + 1 + 255) / 256)), dim3(256), 0, c->stream, c->ar_key2.as<uint64_t>(), n2, L,
+    hipLaunchKernelGGL(k_ar_offsets, dim3((unsigned)((n_nodes + 1 + 255) / 256)), dim3(256), 0, c->stream, c->ar_key2.as<uint64_t>(), n2, n_nodes,
                        c->ar_off.as<int64_t>());
     // the links to check are rows of the short-range table (after ldw_sr_pvalues) or of the long-range one (after ldw_lr_tukey)
     const int32_t *ta = (c->red_from_lr ? c->lr_a : c->sr_a).as<int32_t>(), *tb2 = (c->red_from_lr ? c->lr_b : c->sr_b).as<int32_t>();
     const double *tmi = (c->red_from_lr ? c->lr_mi : c->sr_mi).as<double>();
     hipLaunchKernelGGL(k_ar_check, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), nr,
                        ta, tb2, tmi, c->ar_key2.as<uint64_t>(),
-                       c->ar_val2.as<double>(), c->ar_off.as<int64_t>(), c->ar_flags.as<uint8_t>());
+                       c->ar_val2.as<double>(), c->ar_off.as<int64_t>(), c->ar_flags.as<uint8_t>(), d_slot);
     LDW_HIP(hipGetLastError());
     LDW_HIP(hipMemcpyAsync(flags_out, c->ar_flags.p, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
