@@ -122,8 +122,11 @@ __global__ __launch_bounds__(256) void k_ldmap_log(const double *__restrict__ re
     }
 }
 
-__global__ __launch_bounds__(256) void k_ldmap_rescale(double *__restrict__ red, int64_t n, double mn, double inv_rn) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) red[i] = (red[i] - mn) * inv_rn;
+// (v - min) / (max - min), a division like .rescale01 (R/LDSummaryPlot.R:157-163): the largest cell is exactly 1 and the smallest exactly 0.  A product
+// with 1 / rn is not: (mx - mn) * (1 / (mx - mn)) rounds to 1 - 2^-53 for some rn, and which rn a map meets depends on the order the atomics of
+// k_ldmap_add land in.
+__global__ __launch_bounds__(256) void k_ldmap_rescale(double *__restrict__ red, int64_t n, double mn, double rn) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) red[i] = (red[i] - mn) / rn;
 }
 
 // Graph nodes of the position-based consumers: the rank of each SNP's position among the sorted DISTINCT positions (stable sort of h_POS, then a
@@ -362,7 +365,7 @@ int ldw_ldmap(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t *n_
         mx = std::max(mx, hmm[2 * i + 1]);
     }
     const double rn = mx - mn;   // 0 -> NaN everywhere, like .rescale01
-    hipLaunchKernelGGL(k_ldmap_rescale, dim3(rgrid), dim3(256), 0, c->stream, htm, nb, mn, 1.0 / rn);
+    hipLaunchKernelGGL(k_ldmap_rescale, dim3(rgrid), dim3(256), 0, c->stream, htm, nb, mn, rn);
     LDW_HIP(hipGetLastError());
     LDW_HIP(hipMemcpyAsync(htm_out, htm, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));

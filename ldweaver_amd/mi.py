@@ -20,7 +20,7 @@ from . import _lib as L
 from . import rcompat
 from .engine import Engine, aracne, write_table_tsv
 from .snpdat import CdsVar, SnpDat
-from .srp import COLS, merge_n_sort_sr_links, merge_n_sort_sr_links_device
+from .srp import COLS, merge_n_sort_sr_links, merge_n_sort_sr_links_device, merged_key_rows, repeats_positions
 
 
 # ---------------------------------------------------------------------------------------------
@@ -406,6 +406,8 @@ def perform_MI_computation(snp_dat: SnpDat, hdw, cds_var: CdsVar, ncores: int = 
         red = sr
         red.insert(0, "clust_c", redd["clust_c"].astype(np.int64))
         red["srp_max"] = redd["srp_max"]
+        if pool is not None and repeats_positions(POS):   # (the check set holds one row per cross-cluster key, like the reduced rows)
+            pool = tuple(x[merged_key_rows(POS, paint, *pool, paint[pool[0]] != paint[pool[1]])] for x in pool)
         chk = links_frame(*pool, POS, paint, g) if pool is not None else None
         if runARACNE:
             say(f"Running ARACNE on {len(red)} links... ")

@@ -175,6 +175,35 @@ def stable_argsort_desc(v: np.ndarray) -> np.ndarray:
     return idx
 
 
+def merged_key_rows(POS, paint, a, b, mi, dup) -> np.ndarray:
+    """Keep-mask of link rows given in the reference's row order: False for a cross-cluster row (``dup``) whose whole key (pos1, pos2,
+    clust1, clust2, len, MI) an earlier cross-cluster row holds.  data.table groups such rows into ONE reduced row (R/computePairwiseMI.R:
+    478-485), the first of the group; the device keeps one row per table row.  Two table rows share a key when two SNPs at one position
+    (same cluster) have the same MI towards a third SNP (len follows from the positions)."""
+    keep = np.ones(len(a), dtype=bool)
+    d = np.nonzero(np.asarray(dup, dtype=bool))[0]
+    if len(d) < 2:
+        return keep
+    ka, kb = np.asarray(a)[d], np.asarray(b)[d]
+    POS, paint = np.asarray(POS), np.asarray(paint)
+    cols = (np.ascontiguousarray(np.asarray(mi, dtype=np.float64)[d]).view(np.int64), paint[ka], paint[kb], POS[ka], POS[kb])
+    o = np.lexsort((d,) + cols)
+    same = np.ones(len(o) - 1, dtype=bool)
+    for c in cols:
+        cs = c[o]
+        same &= cs[1:] == cs[:-1]
+    keep[d[o[1:][same]]] = False
+    return keep
+
+
+def repeats_positions(POS) -> bool:
+    """Some position is held by more than one SNP (ascending positions: an O(L) check)."""
+    POS = np.asarray(POS)
+    if len(POS) < 2 or bool(np.all(POS[1:] > POS[:-1])):
+        return False
+    return len(np.unique(POS)) < len(POS)
+
+
 def merge_n_sort_sr_links_device(eng, nclust: int, sr_dist: float, srp_cutoff: float, POS, paint, g, run_aracne=True, order_links=False,
                                  block_rows=None):
     """mergeNsort_sr_links + runARACNE with the link table left on the device by ``eng.mi_all_pairs``: the O(#links)
@@ -225,6 +254,10 @@ def merge_n_sort_sr_links_device(eng, nclust: int, sr_dist: float, srp_cutoff: f
         order = np.argsort((np.asarray(red["dup"], dtype=np.int64) << 62) | (key_cl.astype(np.int64) << 48) | row)   # (keys are unique: rows are)
     else:
         order = np.lexsort((row, key_cl, red["dup"]))
+    if n_red and repeats_positions(POS):
+        # one reduced row per cross-cluster key (R/computePairwiseMI.R:478-485): only SNPs sharing a position give two table rows one key
+        # (the pass never writes one SNP pair twice).  The ARACNE flags of such rows are equal: same positions, same MI
+        order = order[merged_key_rows(POS, paint, red["a"][order], red["b"][order], red["MI"][order], red["dup"][order])]
     if order_links:
         # sr_links_red[order(-srp_max)] (R/computePairwiseMI.R:126; order() is stable) folded into the same gather: the columns are
         # permuted once, as arrays, instead of once here and once more as a DataFrame

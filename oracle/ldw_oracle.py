@@ -572,10 +572,11 @@ def neg_log_beta_sf(x, a: float, b: float) -> np.ndarray:
     return out
 
 
-def merge_n_sort_sr_links(sr_links_by_clust, nclust: int, sr_dist: float, srp_cutoff: float, fit_data=None):
+def merge_n_sort_sr_links(sr_links_by_clust, nclust: int, sr_dist: float, srp_cutoff: float, fit_data=None, shapes=None):
     """Returns (sr_links_red, sr_links_ARACNE_check) as dicts of columns
     clust_c,pos1,pos2,clust1,clust2,len,MI,srp_max.  The plot (:440) is not produced; the table saved as
-    c<i>_fit_data.rds (maxvls: len, max, fit; :422-439) is appended per cluster to ``fit_data`` when a list is given.
+    c<i>_fit_data.rds (maxvls: len, max, fit; :422-439) is appended per cluster to ``fit_data`` when a list is given, and
+    the fitted beta shapes (shape1, shape2; :452) to ``shapes``.
     Reproduces Q5 (``mean_dist[len]`` positional indexing, :448) and Q6 (natural-log srp, :453)."""
     from scipy import stats
     cols = ["pos1", "pos2", "clust1", "clust2", "len", "MI"]
@@ -604,6 +605,8 @@ def merge_n_sort_sr_links(sr_links_by_clust, nclust: int, sr_dist: float, srp_cu
         diff = t["MI"] - md
         idx = np.nonzero(diff > 0)[0]                                 # NA > 0 is dropped by which()
         a_, b_ = _beta_mle(diff[idx])                                 # (:452)
+        if shapes is not None:
+            shapes.append((a_, b_))
         srp = neg_log_beta_sf(diff[idx], a_, b_)                      # (:453)
         t = {k: v[idx] for k, v in t.items()}
         t["srp_max"] = srp

@@ -588,3 +588,18 @@ def test_ldmap_windows(engine):
         assert _ldmap_case(engine, POS, lr, sr, reducer=red, win=(int(POS[20]) + 1, int(POS[21]) - 1)) is None
         with pytest.raises(RuntimeError):
             engine.ldmap(red, int(POS[20]) + 1, int(POS[21]) - 1)
+
+
+@pytest.mark.gpu
+def test_ldmap_rescale_is_a_division(engine):
+    """.rescale01 divides by max - min (R/LDSummaryPlot.R:157-163): the largest cell is exactly 1.  One link per cell (no order of atomics to
+    depend on) and a largest MI for which a product with 1 / (max - min) rounds to 1 - 2^-53."""
+    L = 40
+    POS = _ascending(L, 10)
+    lo = np.log10(1e-5)
+    top = next(v for v in 0.25 + np.arange(1, 4096) / 4096
+               if (np.log10((v + v) / 4 + 1e-5) - lo) * (1.0 / (np.log10((v + v) / 4 + 1e-5) - lo)) != 1.0)
+    a = np.arange(0, L, 2)
+    mi = np.r_[np.linspace(0.01, 0.2, len(a) - 1), top]
+    htm, _, _ = _ldmap_case(engine, POS, (a, a + 1, mi), (E32, E32, E64), reducer=2)
+    assert htm.shape == (20, 20) and htm[19, 19] == 1.0 and htm.max() == 1.0 and htm.min() == 0.0
