@@ -44,15 +44,13 @@ extern "C" {
 
 #define LDW_ENGINE_MFMA 0 /* i8 MFMA fixed-point co-occurrence GEMM + fp64 epilogue (default) */
 #define LDW_ENGINE_HIST 1 /* joint histograms on bit planes: LDS-tiled class-wise popcounts (VALU), exact int64 sums, same fp64 epilogue and results */
-#define LDW_ENGINE_HIST_STATES 2 /* the first histogram kernel: byte states in LDS, 25 sums per pair updated sequence by sequence (independent cross-check; ~200x slower) */
+#define LDW_ENGINE_HIST_STATES 2 /* removed (byte-state histogram kernel, measured ~200x slower): ldw_set_engine answers LDW_ERR_STATE */
 
 typedef struct ldw_ctx ldw_ctx;
 
 /* ---- library / device ------------------------------------------------------------------ */
 int ldw_version(void);
-/* bit 0: built with -DLDW_EXPERIMENTS (make EXPERIMENTS=1): the measured-slower kernel variants and their environment switches are in the
- * library (the fused GEMM + epilogue kernel, LDW_ENGINE_HIST_STATES, corner spans / split diagonal blocks of ldw_set_span, the alternative
- * approximate GEMMs, the list-driven screen).  The default library returns 0, holds none of them and answers LDW_ERR_STATE where one is asked for. */
+/* build flags; always 0 (bit 0 once marked a build with the measured-slower variants, which have been removed) */
 int ldw_build_info(void);
 const char *ldw_last_error(void);
 /* number of visible HIP devices (0 when none); never initialises a context */
@@ -68,7 +66,7 @@ int ldw_ctx_sync(ldw_ctx *ctx);
 int ldw_ctx_last_timing(ldw_ctx *ctx, double ms_out[4]);
 
 /* diagnostics since the context was created: out[0] = blocks whose speculative long-range gather had to fall back to
- * the dense pass, out[1] = blocks run by the fused GEMM + epilogue kernel, out[2] = blocks run by the two-kernel path,
+ * the dense pass, out[1] = 0 (was: blocks run by the removed fused kernel), out[2] = blocks run by the two-kernel path,
  * out[3] = pairs the fp32 screen would have lost (counted in ldw_set_screen mode 2 only; must stay 0) */
 int ldw_ctx_counters(ldw_ctx *ctx, int64_t out[4]);
 /* the same four, then out[4] = blocks run in the mixed-precision path (ldw_set_mixed), out[5] = blocks run in the
@@ -228,11 +226,8 @@ int ldw_links_end(ldw_ctx *ctx);
  * that the per-stage times of ldw_ctx_last_timing are exclusive kernel times (what bench.py's roofline uses).
  * Results are identical either way. */
 int ldw_set_overlap(ldw_ctx *ctx, int on);
-/* on: blocks for which a histogram-bucket guess exists (every block but the first of a call sequence) run the
- * co-occurrence GEMM and the MI epilogue as ONE kernel: the joint sums stay in LDS.  off (default): GEMM -> G in HBM ->
- * k_mi_screen -> k_mi_units; measured faster on C4 (122 vs 132 ms per step) because the epilogue hides its latencies
- * with occupancy the fused kernel cannot have.  Link tables are identical either way up to the rounding of MI (<= 1e-15:
- * on diagonal blocks the fused kernel may meet a pair in mirrored roles). */
+/* 0: GEMM -> G in HBM -> k_mi_screen -> k_mi_units, the only path.  1 (the fused GEMM + MI epilogue kernel: 132 against 122 ms per
+ * C4 step) has been removed and answers LDW_ERR_STATE. */
 int ldw_set_fused(ldw_ctx *ctx, int on);
 /* Mixed precision (default on; 5 weight limbs, two-kernel path, speculative blocks): the block-wide co-occurrence GEMM runs
  * with the 3 HIGH limbs of the fixed-point weights only — all the fp32 screen needs; its margin is widened by a rigorous
@@ -259,7 +254,7 @@ int ldw_reset_speculation(ldw_ctx *ctx);
 /* Which execution path the blocks of this context took since it was created (a real data set may fail a gate silently):
  * out[0] blocks through the approximate-GEMM path, out[1] through the mixed-precision limb path, out[2] through the plain path
  * (5-limb GEMM + fp64 MI of every pair: blocks without a bucket guess and every block when neither fast path applies),
- * out[3] through the fused kernel, out[4] speculation misses (blocks redone non-speculatively), out[5] blocks whose guess came from
+ * out[3] = 0 (was: the removed fused kernel), out[4] speculation misses (blocks redone non-speculatively), out[5] blocks whose guess came from
  * the sampled probe of the block itself (cold starts), out[6] pairs listed for exact evaluation, out[7] units listed.
  * gate (capacity bytes, may be NULL) receives a short text: "ok" ("ok (block exponents per 32 positions)" when the weights'
  * dynamic range needs the finer exponents) or which gate keeps the approximate path off
@@ -278,10 +273,9 @@ int ldw_prune_report(ldw_ctx *ctx, int64_t out[4]);
 /* r04 — spans.  The reference's loop visits the block pairs of a block row one at a time (R/computePairwiseMI.R:103-116); consecutive
  * LONG-RANGE-ONLY block pairs of one row (same from range, to ranges ascending, no pair within sr_dist) are run as ONE launch sequence
  * over their concatenated to side, every reference block keeping its own histogram, threshold, candidate list and place in the append
- * order (the lr filter is per block: :352-358).  Results never depend on it.  ldw_set_span: on != 0 (default; on = 3 also lets CORNER
- * block pairs — the neighbouring pair of the row, the pair that closes the circle: a few short-range pairs — join the spans, their
- * short-range pairs evaluated by an SR sub-pass: correct, measured slower on MI355X, so not the default), at most max_blocks
- * (2..8; 0 keeps the current value) reference blocks per span.  ldw_span_report: out[0] spans run, out[1] reference blocks they covered,
+ * order (the lr filter is per block: :352-358).  Results never depend on it.  ldw_set_span: on != 0 (default), at most max_blocks
+ * (2..8; 0 keeps the current value) reference blocks per span; bits 1 and 2 of on (corner spans, split diagonal blocks: measured
+ * slower, removed) answer LDW_ERR_STATE.  ldw_span_report: out[0] spans run, out[1] reference blocks they covered,
  * out[2] segments redone on their own after a wrong guess, out[3] on.
  * ldw_set_pair_cap (tests only): a fixed capacity for the pair lists of the approximate path (0: automatic) — a list that overflows makes
  * its block fall back like a wrong guess; process-wide. */

@@ -171,7 +171,7 @@ def lib():
 
 
 def has_experiments() -> bool:
-    """The loaded library was built with -DLDW_EXPERIMENTS (make EXPERIMENTS=1; LDW_AMD_LIB selects it)."""
+    """Always False: bit 0 of ldw_build_info marked the LDW_EXPERIMENTS build, whose measured-slower variants have been removed."""
     return bool(lib().ldw_build_info() & 1)
 
 

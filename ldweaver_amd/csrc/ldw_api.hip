@@ -496,7 +496,7 @@ int ldw_version(void) { return 100; }
 
 const char *ldw_last_error(void) { return ldw::g_err; }
 
-int ldw_build_info(void) { return LDW_HAS_EXPERIMENTS ? 1 : 0; }
+int ldw_build_info(void) { return 0; }
 
 int ldw_device_count(void) {
     int n = 0;
@@ -625,7 +625,7 @@ int ldw_ctx_destroy(ldw_ctx *c) {
                            &c->pair_sums, &c->tab11[0], &c->tab11[1], &c->G2, &c->G3, &c->miss_key, &c->miss_val, &c->srd_lower, &c->srd_cur, &c->srd_out, &c->srd_seg, &c->pos_slot};
     for (auto *b : bufs) b->release();
     for (int k = 0; k < LDW_NSLOT; ++k)
-        for (ldw::DevBuf *b : {&c->panel[k][0], &c->panel[k][1], &c->Gapx[k], &c->pairs[k], &c->apx_mini[k], &c->apx_units[k], &c->apx_packs[k], &c->apx_bins[k], &c->apx_clean[k], &c->scr_live[k], &c->sub_units[k], &c->sub_packs[k], &c->sub_bins[k], &c->sub_live[k],
+        for (ldw::DevBuf *b : {&c->panel[k][0], &c->panel[k][1], &c->Gapx[k], &c->pairs[k], &c->apx_mini[k], &c->apx_units[k], &c->apx_packs[k], &c->apx_bins[k], &c->apx_clean[k],
                                &c->hist[k], &c->cand_key[k], &c->cand_val[k]})
             b->release();
     for (auto &e : c->ev)
@@ -691,8 +691,8 @@ int ldw_ctx_last_timing(ldw_ctx *c, double ms_out[4]) {
 int ldw_ctx_counters2(ldw_ctx *c, int64_t out[8]) {
     LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_ctx_counters2: null argument");
     out[0] = c->spec_misses;
-    out[1] = c->fused_blocks;
-    out[2] = c->unfused_blocks;
+    out[1] = 0;   // (the removed fused kernel's blocks)
+    out[2] = c->blocks_run;
     out[3] = c->screen_violations;
     out[4] = c->mixed_blocks;
     out[5] = c->apx_blocks;
@@ -704,8 +704,8 @@ int ldw_ctx_counters2(ldw_ctx *c, int64_t out[8]) {
 int ldw_ctx_counters(ldw_ctx *c, int64_t out[4]) {
     LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_ctx_counters: null argument");
     out[0] = c->spec_misses;
-    out[1] = c->fused_blocks;
-    out[2] = c->unfused_blocks;
+    out[1] = 0;   // (the removed fused kernel's blocks)
+    out[2] = c->blocks_run;
     out[3] = c->screen_violations;
     return LDW_OK;
 }
@@ -725,8 +725,8 @@ int ldw_path_report(ldw_ctx *c, int64_t out[8], char *gate, int capacity) {
     LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_path_report: null argument");
     out[0] = c->apx_blocks;
     out[1] = c->mixed_blocks;
-    out[2] = c->unfused_blocks - c->apx_blocks - c->mixed_blocks + c->spec_misses + c->generic_blocks;   // (blocks in generic POS order always take the plain path)
-    out[3] = c->fused_blocks;
+    out[2] = c->blocks_run - c->apx_blocks - c->mixed_blocks + c->spec_misses + c->generic_blocks;   // (blocks in generic POS order always take the plain path)
+    out[3] = 0;   // (the removed fused kernel's blocks)
     out[4] = c->spec_misses;
     out[5] = c->probe_blocks;
     out[6] = c->apx_pairs_listed;
@@ -795,8 +795,8 @@ int ldw_gemm_stats(ldw_ctx *c, double out[6], int reset) {
 int ldw_set_engine(ldw_ctx *c, int engine) {
     LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
     LDW_REQUIRE(engine == LDW_ENGINE_MFMA || engine == LDW_ENGINE_HIST || engine == LDW_ENGINE_HIST_STATES, LDW_ERR_ARG, "unknown engine %d", engine);
-    LDW_REQUIRE(engine != LDW_ENGINE_HIST_STATES || LDW_HAS_EXPERIMENTS, LDW_ERR_STATE,
-                "LDW_ENGINE_HIST_STATES (the first, byte-state histogram kernel: ~200x slower, kept as a cross-check) is only in the LDW_EXPERIMENTS build");
+    LDW_REQUIRE(engine != LDW_ENGINE_HIST_STATES, LDW_ERR_STATE,
+                "LDW_ENGINE_HIST_STATES: the byte-state histogram kernel (formerly the LDW_EXPERIMENTS build's) was measured ~200x slower and has been removed");
     c->engine = engine;
     return LDW_OK;
 }
@@ -978,11 +978,10 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
             for (int k = 0; k < LDW_NSLOT; ++k) g.insert(g.end(), {&c->panel[k][0], &c->panel[k][1], &c->Gapx[k]});
         if (mask & 8)
             for (int k = 0; k < LDW_NSLOT; ++k)
-                g.insert(g.end(), {&c->apx_bins[k], &c->apx_clean[k], &c->apx_mini[k], &c->apx_units[k], &c->apx_packs[k], &c->scr_live[k], &c->pairs[k], &c->sub_units[k], &c->sub_packs[k],
-                                   &c->sub_bins[k], &c->sub_live[k]});
+                g.insert(g.end(), {&c->apx_bins[k], &c->apx_clean[k], &c->apx_mini[k], &c->apx_units[k], &c->apx_packs[k], &c->pairs[k]});
         for (int k = 0; k < LDW_NSLOT; ++k) {
-            ldw::DevBuf *one[8] = {&c->apx_bins[k], &c->apx_clean[k], &c->apx_mini[k], &c->apx_units[k], &c->apx_packs[k], &c->scr_live[k], &c->pairs[k], &c->sub_units[k]};
-            for (int q = 0; q < 8; ++q)
+            ldw::DevBuf *one[6] = {&c->apx_bins[k], &c->apx_clean[k], &c->apx_mini[k], &c->apx_units[k], &c->apx_packs[k], &c->pairs[k]};
+            for (int q = 0; q < 6; ++q)
                 if (mask & (64 << q)) g.push_back(one[q]);
         }
         if (mask & 16)
@@ -1076,7 +1075,6 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
     c->have_weights = true;
     c->rows_ready = false;
     c->tab11_lo[0] = c->tab11_lo[1] = 0;   // the threshold tables belong to the old weights
-    c->tab11_on = ldw::exp_env("LDW_NO_TAB11") == nullptr;
     return LDW_OK;
 }
 

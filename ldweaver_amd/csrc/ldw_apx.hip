@@ -96,10 +96,9 @@ int prepare_apx_weights(ldw_ctx *c) {
             delta = std::max(delta, std::fabs((double)(Va - V)) / (double)V);
         }
     };
-    static const int force_gran = [] { const char *e = exp_env("LDW_APX_GRAN"); return e ? atoi(e) : 0; }();   // 1 / 4: force fine / coarse (A/B)
-    assign(force_gran == 1 ? 1 : 4);
-    c->apx_fine = force_gran == 1;
-    if (force_gran == 0 && delta > 1.5e-3) {
+    assign(4);
+    c->apx_fine = false;
+    if (delta > 1.5e-3) {
         assign(1);
         c->apx_fine = true;
     }
@@ -110,12 +109,6 @@ int prepare_apx_weights(ldw_ctx *c) {
     c->apx_lost_units = 0;
     for (int k = 1; k < S4; ++k)
         if (sh[(size_t)k] > 0) c->apx_lost_units += std::ldexp(1.0, em[(size_t)k] - c->apx_e_last);
-    // (experiments build, a PRICING switch: LDW_APX_EXTRA_UNITS=x treats every GEMM entry as up to x WEIGHT units low on top of that — what an absolute
-    // slack per entry, e.g. of a contraction over compressed clone groups (docs/HISTORY.md 10), would cost the screen in listed pairs; results stay exact)
-    if (const char *xs = exp_env("LDW_APX_EXTRA_UNITS")) {
-        const double x = atof(xs);
-        if (x > 0) c->apx_lost_units += x / std::ldexp(1.0, c->apx_e_last - c->frac_bits);
-    }
     // weight classes = runs of equal V along the positions; segments = (32-bit word, class) intersections
     std::vector<PopSeg> segs;
     std::vector<int32_t> wbeg((size_t)(Npad / 32) + 1, 0);
@@ -184,14 +177,14 @@ int prepare_apx_weights(ldw_ctx *c) {
 // consecutive pieces: the GEMM's loads are contiguous runs).  interleave != 0 (gemm_apx_kernel, one block exponent per k-step): the eight
 // 16-bit groups g of the macro step are stored as word 0 = groups (0, 2, 4, 6), word 1 = groups (1, 3, 5, 7), so that the lane half fh of an
 // MFMA k-step kk finds ITS sixteen positions 32 kk + 16 fh .. + 15 — a k-step covers 32 CONSECUTIVE positions, one block exponent —
-// at bits 16 kk of word fh.  interleave == 0 (gemm_apx_lds_kernel; gemm_apx_kernel with one exponent per macro step): the words as they are.
-// scaled != 0 (r06, gemm_apx_kernel): every word goes out as FOUR dwords, dword kk = the word's bytes 2 kk and 2 kk + 1 each multiplied by 8 in
-// a 16-bit field — the byte offsets of the two entries of the kernel's 8-byte expansion table that k-step kk looks up: the kernel gets an offset
-// with ONE VALU instruction (and / shift) instead of two (extract, then scale); piece ((m Rpad + r) 2 + word) of 16 bytes, a panel twice the size.
+// at bits 16 kk of word fh.  interleave == 0 (one exponent per macro step): the words as they are.
+// Every word then goes out SCALED (r06) as FOUR dwords, dword kk = the word's bytes 2 kk and 2 kk + 1 each multiplied by 8 in a 16-bit field —
+// the byte offsets of the two entries of the kernel's 8-byte expansion table that k-step kk looks up: the kernel gets an offset with ONE VALU
+// instruction (and / shift) instead of two (extract, then scale); piece ((m Rpad + r) 2 + word) of 16 bytes, a panel twice the size.
 // ------------------------------------------------------------------------------------------------
 // blockIdx.y = 1: the second row list of the launch (rowlist2 / Rpad2 / panel2: the to side of an off-diagonal block — both panels in ONE launch).
 __global__ __launch_bounds__(256) void k_pack_panel(const uint64_t *__restrict__ Mbits, int64_t KW, const int32_t *__restrict__ rowlist,
-                                                    int Rpad, int M2, uint64_t *__restrict__ panel, int interleave, int scaled,
+                                                    int Rpad, int M2, uint64_t *__restrict__ panel, int interleave,
                                                     const int32_t *__restrict__ rowlist2 = nullptr, int Rpad2 = 0, uint64_t *__restrict__ panel2 = nullptr) {
     typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -203,7 +196,6 @@ __global__ __launch_bounds__(256) void k_pack_panel(const uint64_t *__restrict__
     const int r = blockIdx.x * 64 + (threadIdx.x & 63);
     if (r >= Rpad) return;
     const u64x2 *src = reinterpret_cast<const u64x2 *>(Mbits + (int64_t)rowlist[r] * KW);
-    u64x2 *dst = reinterpret_cast<u64x2 *>(panel);
     u32x4 *dst4 = reinterpret_cast<u32x4 *>(panel);
     for (int m = threadIdx.x >> 6; m < M2; m += 4) {
         u64x2 v = src[m];
@@ -215,45 +207,22 @@ __global__ __launch_bounds__(256) void k_pack_panel(const uint64_t *__restrict__
             v[0] = ex;   // g0 g2 g4 g6
             v[1] = ox;   // g1 g3 g5 g7
         }
-        if (scaled) {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const unsigned long long w = v[h];
-                u32x4 o;
+        for (int h = 0; h < 2; ++h) {
+            const unsigned long long w = v[h];
+            u32x4 o;
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk)
-                    o[kk] = (((unsigned int)(w >> (16 * kk)) & 0xFFu) << 3) | (((unsigned int)(w >> (16 * kk + 8)) & 0xFFu) << 19);
-                dst4[((int64_t)m * Rpad + r) * 2 + h] = o;
-            }
-        } else {
-            dst[(int64_t)m * Rpad + r] = v;
+            for (int kk = 0; kk < 4; ++kk)
+                o[kk] = (((unsigned int)(w >> (16 * kk)) & 0xFFu) << 3) | (((unsigned int)(w >> (16 * kk + 8)) & 0xFFu) << 19);
+            dst4[((int64_t)m * Rpad + r) * 2 + h] = o;
         }
     }
-}
-
-static bool apx_kernel_is_lds() {
-    // "reg" (default): operands expanded in registers per wave; "lds": expansion shared through LDS (r03 experiment: correct, and
-    // 28 % slower — 0.659 vs 0.515 ms per C4 launch — because the fragment reads + table reads + tile writes make it LDS-bound)
-    static const bool lds = [] {
-        const char *e = exp_env("LDW_APX_KERNEL");
-        return e && e[0] == 'l';
-    }();
-    return lds;
-}
-
-// the register-expansion kernel (gemm_apx_kernel: the production one) reads the SCALED panel, the experiment kernels the plain words
-static bool apx_kernel_is_reg() {
-    static const bool reg = [] {
-        const char *e = exp_env("LDW_APX_KERNEL");
-        return !(e && (e[0] == 'l' || e[0] == 'p'));
-    }();
-    return reg;
 }
 
 int launch_pack_panel(ldw_ctx *c, const int32_t *rowlist, int Rpad, uint64_t *panel, hipStream_t st, const int32_t *rowlist2, int Rpad2, uint64_t *panel2) {
     const int rmax = (rowlist2 && Rpad2 > Rpad) ? Rpad2 : Rpad;
     hipLaunchKernelGGL(k_pack_panel, dim3((unsigned)((rmax + 63) / 64), rowlist2 ? 2u : 1u), dim3(256), 0, st, c->Mbits.as<uint64_t>(), c->KW, rowlist, Rpad,
-                       (int)(c->KW / 2), panel, (c->apx_fine && !apx_kernel_is_lds()) ? 1 : 0, apx_kernel_is_reg() ? 1 : 0, rowlist2, Rpad2, panel2);
+                       (int)(c->KW / 2), panel, c->apx_fine ? 1 : 0, rowlist2, Rpad2, panel2);
     LDW_HIP(hipGetLastError());
     return LDW_OK;
 }
@@ -276,14 +245,8 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 // index as one SDWA instruction; the table reads one k-step ahead; a 16-way replicated table.  Their code left this file in r06: git history has it.)
 constexpr int APX_MT = 4, APX_WPS = 2;
 
-// the 16 expanded bytes (0xFF / 0x00) of the 16 bits of k-step KK of a 64-bit panel word: two look-ups in the 256-entry byte -> 8 x 0xFF table (LDS)
-template <int KK>
-__device__ __forceinline__ v4i expand16(const uint64_t *lutFF, uint64_t w) {
-    typedef unsigned long long u64x2v __attribute__((ext_vector_type(2)));
-    const u64x2v q = {lutFF[(w >> (16 * KK)) & 0xFFu], lutFF[(w >> (16 * KK + 8)) & 0xFFu]};
-    return __builtin_bit_cast(v4i, q);
-}
-// the same from a piece of the SCALED panel (k_pack_panel): dword KK holds the two table offsets, in bytes, as 16-bit fields
+// the 16 expanded bytes (0xFF / 0x00) of the 16 bits of k-step KK: two look-ups in the 256-entry byte -> 8 x 0xFF table (LDS).  From a piece
+// of the scaled panel (k_pack_panel): dword KK holds the two table offsets, in bytes, as 16-bit fields
 typedef unsigned int apx_u32x4 __attribute__((ext_vector_type(4)));
 template <int KK>
 __device__ __forceinline__ v4i expand16s(const uint8_t *lut_bytes, const apx_u32x4 &w) {
@@ -394,7 +357,7 @@ __device__ __forceinline__ void apx_gemm_epilogue(const ApxGemmArgs &P, v16i (&a
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int trow = ty * TH + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * fh;
-                    if ((128 % TH == 0 || trow < P.RTpad) && (64 % TWd == 0 || fcol < P.RFpad)) P.G[(int64_t)trow * P.RFpad + fcol] = acc[i][j][e];
+                    P.G[(int64_t)trow * P.RFpad + fcol] = acc[i][j][e];
                 }
             }
         }
@@ -540,14 +503,12 @@ __global__ __launch_bounds__(256, WPS) void gemm_apx_kernel(ApxGemmArgs P) {
         const apx_u32x4 *pa[MT], *pb[NT];   // (pieces of the scaled panel: k_pack_panel)
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
-            int rt = ty * TH + 32 * i + frow;
-            if (128 % TH != 0 && rt >= P.RTpad) rt = P.RTpad - 1;   // (only the 96-row tiles of the r05 experiment can run past RTpad, a multiple of 128)
+            const int rt = ty * TH + 32 * i + frow;
             pa[i] = reinterpret_cast<const apx_u32x4 *>(P.panel_t) + ((int64_t)rt * 2 + fh);
         }
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-            int rf = tx * TWd + 32 * i + frow;
-            if (64 % TWd != 0 && rf >= P.RFpad) rf = P.RFpad - 1;   // (only the 96-column tiles of the r05 experiments can run past RFpad, a multiple of 64)
+            const int rf = tx * TWd + 32 * i + frow;
             pb[i] = reinterpret_cast<const apx_u32x4 *>(P.panel_f) + ((int64_t)rf * 2 + fh);
         }
         v16i acc[MT][NT];
@@ -611,287 +572,6 @@ __global__ __launch_bounds__(256, WPS) void gemm_apx_kernel(ApxGemmArgs P) {
         apx_gemm_epilogue<MT, NT>(P, acc, ty, tx, lane, s_tab, reinterpret_cast<uint8_t *>(s_tab + 64 * 64) + wave * 256);
     }
 }
-#ifdef LDW_EXPERIMENTS
-// ------------------------------------------------------------------------------------------------
-// gemm_apx_pipe_kernel (r03 experiment, LDW_APX_KERNEL=pipe; coarse exponents only): the register-expansion kernel with the expansion
-// of k-step s + 1 SOFTWARE-PIPELINED under the MFMAs of k-step s, at a dependency distance of three MFMA slots: slot k of a step
-// issues MFMA k, the index arithmetic and the two table reads of fragment k of the NEXT step (k < 6), and the four ANDs of the
-// fragment whose reads were issued three slots earlier.  Two fragment sets alternate (4 k-steps per macro step: no copies).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 2) void gemm_apx_pipe_kernel(ApxGemmArgs P) {
-    constexpr int MT = 4, NT = 2;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint64_t *lutFF = reinterpret_cast<uint64_t *>(smem);
-    uint8_t *sA = smem + 2048, *sB = sA + (size_t)P.M2 * 128;
-    int2 *s_tab = reinterpret_cast<int2 *>(sB + (size_t)P.M2 * 128);
-    const int tid = threadIdx.x;
-    if (P.fuse)
-        for (int i = tid; i < P.tab_nb * P.tab_nb; i += 256) s_tab[i] = P.tab[i];
-    {
-        uint64_t e = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) e |= ((tid >> k) & 1) ? (0xFFull << (8 * k)) : 0ull;
-        lutFF[tid] = e;
-        const int n16 = P.M2 * 8;
-        for (int i = tid; i < n16; i += 256) {
-            reinterpret_cast<uint4 *>(sA)[i] = reinterpret_cast<const uint4 *>(P.dig_a)[i];
-            reinterpret_cast<uint4 *>(sB)[i] = reinterpret_cast<const uint4 *>(P.dig_b)[i];
-        }
-    }
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6;
-    const int ty = 2 * blockIdx.y + (wave >> 1), tx = 2 * blockIdx.x + (wave & 1);
-    constexpr int TH = 32 * MT, TWd = 32 * NT;
-    if (ty * TH >= P.RTpad || tx * TWd >= P.RFpad) return;
-    if (P.lower_only && tx * TWd + TWd - 1 < ty * TH) return;
-    const int frow = lane & 31, fh = lane >> 5;
-    const uint64_t *pw[6];   // rows of this lane: 0..3 to side, 4..5 from side
-#pragma unroll
-    for (int i = 0; i < MT; ++i) pw[i] = P.panel_t + ((int64_t)(ty * TH + 32 * i + frow) * 2 + fh);
-#pragma unroll
-    for (int i = 0; i < NT; ++i) pw[MT + i] = P.panel_f + ((int64_t)(tx * TWd + 32 * i + frow) * 2 + fh);
-    const int64_t st6[6] = {(int64_t)P.RTpad * 2, (int64_t)P.RTpad * 2, (int64_t)P.RTpad * 2, (int64_t)P.RTpad * 2, (int64_t)P.RFpad * 2, (int64_t)P.RFpad * 2};
-    v16i acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
-    typedef unsigned long long u64x2v __attribute__((ext_vector_type(2)));
-    uint64_t wcur[6], wnxt[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        wcur[r] = pw[r][0];
-        wnxt[r] = P.M2 > 1 ? pw[r][st6[r]] : 0ull;
-    }
-    // fragment sets X (even k-steps) and Y (odd k-steps); index 0..3 to side, 4..5 from side
-    v4i fX[6], fY[6];
-    auto lut2 = [&](uint64_t w, int kk) -> v4i {
-        const u64x2v q = {lutFF[(w >> (16 * kk)) & 0xFFu], lutFF[(w >> (16 * kk + 8)) & 0xFFu]};
-        return __builtin_bit_cast(v4i, q);
-    };
-    const uint8_t *dAl = sA + fh * 64, *dBl = sB + fh * 64;
-    {   // prologue: fragments of k-step 0 into X
-        const v4i da = *reinterpret_cast<const v4i *>(dAl), db = *reinterpret_cast<const v4i *>(dBl);
-#pragma unroll
-        for (int r = 0; r < 6; ++r) fX[r] = lut2(wcur[r], 0) & (r < MT ? da : db);
-    }
-    // fragment order of the expansion = the order in which the MFMAs of a step first need them
-    constexpr int ORD[6] = {4, 0, 1, 5, 2, 3};                    // B0 A0 A1 B1 A2 A3
-    constexpr int MI_[8] = {0, 1, 0, 1, 2, 2, 3, 3}, MJ_[8] = {0, 0, 1, 1, 0, 1, 0, 1};
-    for (int m = 0; m < P.M2; ++m) {
-        const int sh = P.shift[4 * m];
-        if (sh) {
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[i][j][e] = (int)((unsigned)acc[i][j][e] >> sh);
-        }
-        const bool more = m + 1 < P.M2;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            v4i(&cur)[6] = (kk & 1) ? fY : fX;
-            v4i(&nxt)[6] = (kk & 1) ? fX : fY;
-            const int kn = (kk + 1) & 3;                            // k-step within its macro step of the NEXT step
-            const bool wrap = kk == 3;                              // the next step belongs to macro step m + 1
-            const int mo = wrap ? (m + 1) * 128 : m * 128;
-            const bool have_next = !wrap || more;
-            v4i dna = {0, 0, 0, 0}, dnb = {0, 0, 0, 0};
-            if (have_next) {
-                dna = *reinterpret_cast<const v4i *>(dAl + mo + 16 * kn);
-                dnb = *reinterpret_cast<const v4i *>(dBl + mo + 16 * kn);
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                acc[MI_[k]][MJ_[k]] = __builtin_amdgcn_mfma_i32_32x32x32_i8(cur[MI_[k]], cur[MT + MJ_[k]], acc[MI_[k]][MJ_[k]], 0, 0, 0);
-                if (k < 6) {
-                    const int r = ORD[k];
-                    nxt[r] = lut2(wrap ? wnxt[r] : wcur[r], kn);
-                }
-                if (k >= 3 && k < 7) {
-                    const int r = ORD[k - 3];
-                    nxt[r] = nxt[r] & (r < MT ? dna : dnb);
-                }
-                if (k == 7) {
-                    nxt[ORD[4]] = nxt[ORD[4]] & dna;
-                    nxt[ORD[5]] = nxt[ORD[5]] & dna;
-                }
-#ifdef LDW_PIPE_SGB   // pinning the interleave (MFMA, 2 table reads, 8 VALU per slot): 0.572 ms; without it (the compiler's own order): see docs/HISTORY.md 5.1c
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 8, 0);
-#endif
-            }
-        }
-        // panel words: the next macro step's become current, the one after that is requested
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            wcur[r] = wnxt[r];
-            if (m + 2 < P.M2) wnxt[r] = pw[r][(int64_t)(m + 2) * st6[r]];
-        }
-    }
-    apx_gemm_epilogue<MT, NT>(P, acc, ty, tx, lane, s_tab, reinterpret_cast<uint8_t *>(s_tab + 64 * 64) + wave * 256);
-}
-
-// ------------------------------------------------------------------------------------------------
-// gemm_apx_lds_kernel: the same contraction with the operand expansion SHARED through LDS (r03).
-//
-// gemm_apx_kernel expands every fragment in the wave that consumes it: 6 expansions (48 VALU, 12 table reads) per 8 MFMAs, which
-// keeps the VALU issue port ~88 % busy at the full MFMA rate even on paper — it runs at 0.51 of the int8 peak.  Here a
-// workgroup of 8 waves (2 along the to side x 4 along the from side, 256 x 256 rows, wave tile 128 x 64 as before) expands
-// each operand row ONCE per 64 positions: thread t owns row t & 255 of side t >> 8, reads the row's 64-bit panel word, turns it
-// into four digit-masked 16-byte fragments (table look-ups as before) and writes them to an LDS byte tile; every wave then feeds
-// its MFMAs with ds_read_b128.  Per 64 positions a wave does 4 expansions (32 VALU, 8 table reads, 4 ds_write_b128) and
-// 12 ds_read_b128 for 16 MFMAs: 2 VALU per MFMA instead of 6.  Two LDS buffers, one workgroup barrier per 64 positions (512
-// MFMA cycles).  The byte tile is [row][64 B] with the 16-byte slot XOR-swizzled by (row >> 2) & 3: the 16 lanes that share
-// an LDS pass (rows r .. r + 15, same slot) then cover all 64 banks once, for the writes and for the fragment reads.
-// LDS: 2 x 32 KB tiles + 2 KB table + the digit arrays (+ 33 KB threshold table when the epilogue applies it): one workgroup
-// of 8 waves per CU, two waves per SIMD as before.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512, 1) void gemm_apx_lds_kernel(ApxGemmArgs P) {
-    constexpr int MT = 4, NT = 2;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint64_t *lutFF = reinterpret_cast<uint64_t *>(smem);                       // [256]
-    uint8_t *sA = smem + 2048, *sB = sA + (size_t)P.M2 * 128;                   // digits by position
-    uint8_t *tile0 = sB + (size_t)P.M2 * 128;                                   // 2 buffers x (256 to-rows + 256 from-rows) x 64 B
-    int2 *s_tab = reinterpret_cast<int2 *>(tile0 + 2 * 32768);                  // threshold table (P.fuse)
-    const int tid = threadIdx.x;
-    if (P.fuse)
-        for (int i = tid; i < P.tab_nb * P.tab_nb; i += 512) s_tab[i] = P.tab[i];
-    if (tid < 256) {
-        uint64_t e = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) e |= ((tid >> k) & 1) ? (0xFFull << (8 * k)) : 0ull;
-        lutFF[tid] = e;
-    }
-    {
-        const int n16 = P.M2 * 8;
-        for (int i = tid; i < n16; i += 512) {
-            reinterpret_cast<uint4 *>(sA)[i] = reinterpret_cast<const uint4 *>(P.dig_a)[i];
-            reinterpret_cast<uint4 *>(sB)[i] = reinterpret_cast<const uint4 *>(P.dig_b)[i];
-        }
-    }
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wy = wave >> 2, wx = wave & 3;
-    const int ty = 2 * blockIdx.y + wy, tx = 4 * blockIdx.x + wx;      // wave-tile coordinates (128 to-rows, 64 from-rows)
-    constexpr int TH = 128, TWd = 64;
-    // the whole 256 x 256 tile above the diagonal: nothing to do (uniform over the workgroup: no barrier is skipped by a part of it)
-    if (P.lower_only && (int)(4 * blockIdx.x + 3) * TWd + TWd - 1 < (int)(2 * blockIdx.y) * TH) return;
-    const bool wave_live = ty * TH < P.RTpad && tx * TWd < P.RFpad && !(P.lower_only && tx * TWd + TWd - 1 < ty * TH);
-    // ---- expansion role: row er of side eside ----
-    const int eside = tid >> 8, er = tid & 255;
-    const int grow = eside == 0 ? (int)(2 * blockIdx.y) * TH + er : (int)(4 * blockIdx.x) * TWd + er;   // row in the side's row list
-    const int gmax = eside == 0 ? P.RTpad : P.RFpad;
-    const bool erow_ok = grow < gmax;
-    const uint64_t *prow = (eside == 0 ? P.panel_t : P.panel_f) + (int64_t)(erow_ok ? grow : 0) * 2;
-    const int64_t pst = (int64_t)gmax * 2;     // words per macro step in this side's panel
-    const uint8_t *dig = eside == 0 ? sA : sB;
-    const int wsw = (er >> 2) & 3;             // the row's slot swizzle
-    uint8_t *wdst = tile0 + eside * 16384 + er * 64;
-    typedef unsigned long long u64x2v __attribute__((ext_vector_type(2)));
-    // The expansion of a chunk is split around the MFMAs of the chunk being computed: the eight table reads and the digits are
-    // REQUESTED before the first k-step (exp_issue), masked and written behind it (exp_finish), so that the LDS round trip and
-    // the write pass run under MFMAs instead of in a phase of their own (all eight waves leave a barrier together: a phase
-    // without MFMAs is a phase in which the matrix pipe of every SIMD idles).
-    u64x2v xq[4];
-    v4i xdg[4];
-    auto exp_issue = [&](uint64_t w, int chunk) {
-        const uint8_t *d = dig + chunk * 64;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            xq[g][0] = lutFF[(w >> (16 * g)) & 0xFFu];
-            xq[g][1] = lutFF[(w >> (16 * g + 8)) & 0xFFu];
-            xdg[g] = *reinterpret_cast<const v4i *>(d + 16 * g);
-        }
-    };
-    auto exp_finish = [&](uint8_t *buf_base) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) *reinterpret_cast<v4i *>(buf_base + 16 * (g ^ wsw)) = __builtin_bit_cast(v4i, xq[g]) & xdg[g];
-    };
-    // ---- consumer role ----
-    const int frow = lane & 31, fh = lane >> 5;
-    int offA[MT], offB[NT];      // byte offset of this lane's row in the A / B half of a buffer, and its swizzle
-    int swA[MT], swB[NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int r = wy * TH + 32 * i + frow;
-        offA[i] = r * 64;
-        swA[i] = (r >> 2) & 3;
-    }
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int r = wx * TWd + 32 * j + frow;
-        offB[j] = 16384 + r * 64;
-        swB[j] = (r >> 2) & 3;
-    }
-    v16i acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
-    // one macro step (128 positions = two chunks) per iteration; the panel words of macro step m + 2 are requested at the top of
-    // iteration m and first touched at its bottom, two chunks of MFMAs later
-    u64x2v wcur = {0ull, 0ull}, wnext = {0ull, 0ull}, wfar = {0ull, 0ull};
-    if (erow_ok) wcur = *reinterpret_cast<const u64x2v *>(prow);
-    if (erow_ok && P.M2 > 1) wnext = *reinterpret_cast<const u64x2v *>(prow + pst);
-    __syncthreads();            // table, digits
-    exp_issue(wcur[0], 0);
-    exp_finish(wdst);
-    __syncthreads();
-    auto kstep = [&](const uint8_t *cur, int ks) {
-        v4i fa[MT], fb[NT];
-        const int slot = 2 * ks + fh;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) fa[i] = *reinterpret_cast<const v4i *>(cur + offA[i] + 16 * (slot ^ swA[i]));
-#pragma unroll
-        for (int j = 0; j < NT; ++j) fb[j] = *reinterpret_cast<const v4i *>(cur + offB[j] + 16 * (slot ^ swB[j]));
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    };
-    for (int m = 0; m < P.M2; ++m) {
-        if (erow_ok && m + 2 < P.M2) wfar = *reinterpret_cast<const u64x2v *>(prow + (int64_t)(m + 2) * pst);
-        // ---- chunk 2m (buffer 0); chunk 2m + 1 is expanded into buffer 1 meanwhile ----
-        const int4 sh4 = reinterpret_cast<const int4 *>(P.shift)[m];   // one exponent per k-step of 32 positions
-        auto rescale = [&](int sh) {
-            if (sh && wave_live) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[i][j][e] = (int)((unsigned)acc[i][j][e] >> sh);
-            }
-        };
-        exp_issue(wcur[1], 2 * m + 1);
-        rescale(sh4.x);
-        if (wave_live) kstep(tile0, 0);
-        exp_finish(wdst + 32768);
-        rescale(sh4.y);
-        if (wave_live) kstep(tile0, 1);
-        __syncthreads();
-        // ---- chunk 2m + 1 (buffer 1); the first chunk of the next macro step goes into buffer 0 ----
-        if (m + 1 < P.M2) exp_issue(wnext[0], 2 * m + 2);
-        rescale(sh4.z);
-        if (wave_live) kstep(tile0 + 32768, 0);
-        if (m + 1 < P.M2) exp_finish(wdst);
-        rescale(sh4.w);
-        if (wave_live) kstep(tile0 + 32768, 1);
-        __syncthreads();
-        wcur = wnext;
-        wnext = wfar;
-    }
-    if (!wave_live) return;
-    apx_gemm_epilogue<MT, NT>(P, acc, ty, tx, lane, s_tab, reinterpret_cast<uint8_t *>(s_tab + 64 * 64) + wave * 256);
-}
-
-#endif   // LDW_EXPERIMENTS
 
 int launch_apx_live_tiles(ldw_ctx *c, const ApxGemmArgs &P, hipStream_t st) {
     LDW_REQUIRE(P.fuse && P.skip_ctr && P.tile_list && P.n_live && P.RTpad % 128 == 0 && P.RFpad % 64 == 0 && P.tab && P.tab_nb == 64,
@@ -907,85 +587,20 @@ int launch_gemm_apx(ldw_ctx *c, const ApxGemmArgs &P, hipStream_t st) {
     const size_t lds = APX_LUT_BYTES + (size_t)P.M2 * 256 + (P.fuse ? (size_t)P.tab_nb * P.tab_nb * 8 + 1024 : 0);
     LDW_REQUIRE(lds <= 65536, LDW_ERR_ARG, "launch_gemm_apx: %d positions do not fit the LDS digit arrays", P.M2 * 128);
     LDW_REQUIRE(!P.fuse || (P.tab_nb == 64 && P.bin_t && P.bin_f && P.tab && P.clean), LDW_ERR_ARG, "launch_gemm_apx: bad table arguments");
-    static const int tile = [] {
-        const char *e = exp_env("LDW_APX_TILE");   // tuning: wave tile in MFMA tiles, to side x from side (default 4 x 2)
-        return e ? atoi(e) : 42;
-    }();
-#ifdef LDW_EXPERIMENTS
-    const int kern = apx_kernel_is_lds() ? 1 : 0;
-    static const bool pipe = [] { const char *e = exp_env("LDW_APX_KERNEL"); return e && e[0] == 'p'; }();
-    if (pipe && !P.fine && tile == 42) {
-        const int ntx = P.RFpad / 64, nty = P.RTpad / 128;
-        hipLaunchKernelGGL(gemm_apx_pipe_kernel, dim3((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2)), dim3(256), lds, st, P);
-        LDW_HIP(hipGetLastError());
-        int64_t waves = 0;
-        for (int ty = 0; ty < nty; ++ty) {
-            if (!P.lower_only) waves += ntx;
-            else for (int tx = 0; tx < ntx; ++tx) waves += (tx * 64 + 63 < ty * 128) ? 0 : 1;
-        }
-        c->gemm_stat[0] += 1;
-        if (P.fuse) c->gemm_stat[5] += 1;
-        c->gemm_stat[1] += 2.0 * (double)waves * 128 * 64 * ((double)P.M2 * 128.0);
-        return LDW_OK;
-    }
-    const size_t lds2 = 2048 + (size_t)P.M2 * 256 + 2 * 32768 + (P.fuse ? (size_t)P.tab_nb * P.tab_nb * 8 + 8 * 256 : 0);
-    if (kern == 1 && lds2 <= 160 * 1024 && tile == 42) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            LDW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_apx_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set = true;
-        }
-        const int ntx = P.RFpad / 64, nty = P.RTpad / 128;
-        hipLaunchKernelGGL(gemm_apx_lds_kernel, dim3((unsigned)((ntx + 3) / 4), (unsigned)((nty + 1) / 2)), dim3(512), lds2, st, P);
-        LDW_HIP(hipGetLastError());
-        int64_t waves = 0;
-        for (int ty = 0; ty < nty; ++ty) {
-            if (!P.lower_only) waves += ntx;
-            else for (int tx = 0; tx < ntx; ++tx) waves += (tx * 64 + 63 < ty * 128) ? 0 : 1;
-        }
-        c->gemm_stat[0] += 1;
-        if (P.fuse) c->gemm_stat[5] += 1;
-        c->gemm_stat[1] += 2.0 * (double)waves * 128 * 64 * ((double)P.M2 * 128.0);
-        return LDW_OK;
-    }
-#endif   // LDW_EXPERIMENTS
-#define LDW_APX_LAUNCH(MTv, NTv)                                                                                              \
-    {                                                                                                                         \
-        const int ntx = P.RFpad / (32 * NTv), nty = P.RTpad / (32 * MTv);                                                     \
-        if (P.fine) hipLaunchKernelGGL((gemm_apx_kernel<MTv, NTv, true>), dim3((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2)), dim3(256), lds, st, P); \
-        else hipLaunchKernelGGL((gemm_apx_kernel<MTv, NTv, false>), dim3((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2)), dim3(256), lds, st, P); \
-    }
     if (P.skip_ctr) {
         LDW_REQUIRE(P.fuse && P.tile_list && P.n_live && P.RFpad % 64 == 0, LDW_ERR_ARG, "launch_gemm_apx: bad pruning arguments");
         const int tiles = (P.RTpad / (32 * APX_MT)) * (P.RFpad / 64), g = (tiles + 3) / 4;   // (the list is made by launch_apx_live_tiles)
         if (P.fine) hipLaunchKernelGGL((gemm_apx_kernel<APX_MT, 2, true, APX_WPS>), dim3((unsigned)g), dim3(256), lds, st, P);
         else hipLaunchKernelGGL((gemm_apx_kernel<APX_MT, 2, false, APX_WPS>), dim3((unsigned)g), dim3(256), lds, st, P);
+    } else {
+        const int ntx = P.RFpad / 64, nty = P.RTpad / 128;
+        const dim3 grid((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2));
+        if (P.fine) hipLaunchKernelGGL((gemm_apx_kernel<4, 2, true>), grid, dim3(256), lds, st, P);
+        else hipLaunchKernelGGL((gemm_apx_kernel<4, 2, false>), grid, dim3(256), lds, st, P);
     }
-#ifdef LDW_EXPERIMENTS
-    else if (tile == 22 && !P.fuse) LDW_APX_LAUNCH(2, 2)          // (the table epilogue assumes 64 from-rows per wave: NT = 2)
-    else if (tile == 33 && !P.fuse) {   // r05: 3 x 3 MFMA tiles per wave (96 x 96: 6 fragments per 9 MFMAs instead of 6 per 8), two waves per SIMD
-        const int ntx = (P.RFpad + 95) / 96, nty = (P.RTpad + 95) / 96;
-        if (P.fine) hipLaunchKernelGGL((gemm_apx_kernel<3, 3, true, 2>), dim3((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2)), dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((gemm_apx_kernel<3, 3, false, 2>), dim3((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2)), dim3(256), lds, st, P);
-    }
-    else if (tile == 224 && !P.fuse) {   // r05: 2 x 2 tiles built for FOUR waves per SIMD (<= 128 VGPRs)
-        const int ntx = P.RFpad / 64, nty = P.RTpad / 64;
-        if (P.fine) hipLaunchKernelGGL((gemm_apx_kernel<2, 2, true, 4>), dim3((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2)), dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((gemm_apx_kernel<2, 2, false, 4>), dim3((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2)), dim3(256), lds, st, P);
-    }
-    else if (tile == 24 && !P.fuse) LDW_APX_LAUNCH(2, 4)
-    else if (tile == 32 && !P.fuse) {   // r05: 3 x 2 MFMA tiles per wave = 96 accumulators, built for THREE waves per SIMD (<= 170 VGPRs)
-        const int ntx = P.RFpad / 64, nty = (P.RTpad + 95) / 96;
-        if (P.fine) hipLaunchKernelGGL((gemm_apx_kernel<3, 2, true, 3>), dim3((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2)), dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((gemm_apx_kernel<3, 2, false, 3>), dim3((unsigned)((ntx + 1) / 2), (unsigned)((nty + 1) / 2)), dim3(256), lds, st, P);
-    }
-#endif
-    else LDW_APX_LAUNCH(4, 2)
-#undef LDW_APX_LAUNCH
     LDW_HIP(hipGetLastError());
     {   // executed work (ldw_gemm_stats): waves that do not leave at once, each 2 * rows_t * rows_f * K int8 operations
-        const int tl = P.fuse ? 42 : tile;
-        const int MTv = (P.fuse && P.skip_ctr) ? APX_MT : (tl == 22 || tl == 24 || tl == 224 ? 2 : (tl == 32 || tl == 33 ? 3 : 4)), NTv = tl == 24 ? 4 : (tl == 33 ? 3 : 2), TH = 32 * MTv, TWd = 32 * NTv;
+        constexpr int TH = 128, TWd = 64;
         int64_t waves = 0;
         for (int ty = 0; ty * TH < P.RTpad; ++ty) {
             const int ntx = P.RFpad / TWd;

@@ -1,6 +1,5 @@
-// Device-side pieces of the MI epilogue shared by k_mi_epilogue (ldw_mi.hip) and the fused GEMM + epilogue kernel
-// (ldw_fused.hip): histogram buckets, short-range interval tests, the fp64 log helpers, the per-pair MI
-// (src/computeMI.cpp:19 cell by cell) and the emission of one finished pair.
+// Device-side pieces of the MI epilogue and the screens (ldw_mi.hip): histogram buckets, short-range interval tests, the fp64 log
+// helpers, the per-pair MI (src/computeMI.cpp:19 cell by cell) and the emission of one finished pair.
 #pragma once
 #include <cmath>
 #include "ldw_internal.h"
@@ -132,15 +131,15 @@ struct EmitArgs {
 // screen reads int32 sums of the approximate weights V' in units of 2^e_last; its bound of the exact MI carries the relative error delta of the
 // weights and the units lost to truncation.  One place for the engine (make_emit_args, ldw_mi_items.inc) and the test hook (ldw_debug_apx_params):
 // BOUNDS.md 3 states what each constant has to cover.
-inline void apx_screen_params(const ldw_ctx *c, EmitArgs &E, bool r02_bound = false) {
+inline void apx_screen_params(const ldw_ctx *c, EmitArgs &E) {
     const double den = c->neff > 1.0 ? c->neff : 1.0;
     E.apx = 1;
     E.apx_EG = (float)(c->apx_lost_units * 1.001);
     E.apx_dfac = (float)(1.01 * c->apx_delta / (1.0 - c->apx_delta));
     E.apx_unit = std::ldexp(1.0, c->apx_e_last - c->frac_bits);
-    E.apx_s1 = (float)(E.apx_unit * (2.0 * std::log(den + 12.5) + (r02_bound ? 3.1 : 2.1)) / (1.0 - c->apx_delta) * 1.01);
-    E.apx_c1 = r02_bound ? 1.02f : 0.02f;
-    E.apx_W = r02_bound ? 0.0 : std::ldexp((double)c->total_fixed, -c->frac_bits);
+    E.apx_s1 = (float)(E.apx_unit * (2.0 * std::log(den + 12.5) + 2.1) / (1.0 - c->apx_delta) * 1.01);
+    E.apx_c1 = 0.02f;
+    E.apx_W = std::ldexp((double)c->total_fixed, -c->frac_bits);
     E.scr_shift = 0;
     E.scr_scale = (float)std::ldexp(1.0, c->apx_e_last - c->frac_bits);
     E.scr_eps = 2e-4f;   // SCREEN_EPS (below)
@@ -186,7 +185,7 @@ __device__ __forceinline__ void emit_pair(const EmitArgs &E, const ColInfo &c, i
     }
 }
 
-// emission in the speculative selection mode without a dense block or an LDS histogram (fused kernel, k_mi_units):
+// emission in the speculative selection mode without a dense block or an LDS histogram (k_mi_units):
 // candidates are rare, their bucket counts go straight to the global histogram
 __device__ __forceinline__ void emit_pair_spec(const EmitArgs &E, const ColInfo &c, int a_loc, int b_loc, int sa, int sb, double mi,
                                            unsigned long long *__restrict__ ghist) {
@@ -308,8 +307,8 @@ struct EpiArgs {
     // sflag_f[64 * tile + lane], sflag_t[column slot]
     const uint8_t *sflag_f, *sflag_t;
     const double *snp_sup;    // [L][4] (k_snp_sup)
-    int sr_excl;              // 1: the block's short-range pairs are evaluated elsewhere (an SR sub-pass over the same block in list order): the
-                              // screens only keep them out of the long-range candidates and never list a unit for them (E.any_sr is 0 then)
+    int sr_excl;              // always 0 (its SR sub-pass is gone); removing the field and its reads changes the screens' SGPR and scratch
+                              // allocation, so it stays until a change to the screens can be measured against that
     const MiniCol *mini_c;    // [nt] / [64 * from-tiles] (k_screen_maybe); null: not built
     const MiniRow *mini_r;
     int span;                 // > 0: the to side is the concatenation of `span` reference blocks (segments), nt of each = nf
@@ -334,18 +333,6 @@ struct PairEnt {
 constexpr int PAIR_PATHS = 5;    // (NA, NB) = (1,1) (2,1) (1,2) (2,2) straight-line code, 4 = predicated
 constexpr int PAIR_SHARDS = 8;
 
-// arguments of the fused GEMM + epilogue kernel (ldw_fused.hip); A.G is unused there
-struct FusedArgs {
-    const uint64_t *Mbits;
-    int64_t KW, Kpad;
-    const int32_t *rowlist_t, *rowlist_f;
-    const int8_t *digits;
-    const int32_t *pos_f, *pos_t;   // local SNP index starting at each row position of the padded row lists, -1 elsewhere
-    const uint8_t *cls_f, *cls_t;   // slot-count class (1, 2, 4) of every 32-row group of the row lists
-    unsigned long long *ghist;      // NBINS counters of the long-range candidates
-    EpiArgs A;
-};
-int launch_fused(ldw_ctx *ctx, const FusedArgs &F, int RFpad, int RTpad, int nlimbs, hipStream_t stream);
 // arguments of the gathered low-limb GEMM (ldw_gemm_bits.hip)
 struct LoGemmArgs {
     const uint64_t *Mbits;
@@ -398,7 +385,7 @@ struct RowPack {
 // the run-time slot counts still mask the individual cells.
 // Where the joint sums of one pair live.  g points at G(slot 0 of a, slot 0 of b); slot i of the from-side SNP and slot j of
 // the to-side SNP are at g[i * si + j * sj] (global G block: si = 1, sj = RFpad, or transposed on the mirrored half of a
-// diagonal block; LDS tile of the fused kernel: si = 1, sj = its padded row stride).  In the mixed-precision path the
+// diagonal block).  In the mixed-precision path the
 // block-wide GEMM only carries the HIGH limbs of the weights (g, to be shifted left by `shift` bits) and the low limbs of
 // the listed units come from the gathered GEMM (l, int32, own strides): sum = (g << shift) + l.
 struct GAcc {

@@ -1,5 +1,5 @@
 // K loop of one 128 (to side) x 64 (from side) workgroup tile of the bit-packed co-occurrence GEMM.  Textually
-// included in the body of gemm_bits_kernel (ldw_gemm_bits.hip) and gemm_mi_fused_kernel (ldw_fused.hip): as an inlined
+// included in the body of gemm_bits_kernel (ldw_gemm_bits.hip): as an inlined
 // function taking the accumulators by reference the same code needs ~70 more VGPRs and spills (hipcc 7.2).
 // Expects in scope: template int J; GemmSmem<J> S (shared); Mbits, KW, rowlist_t, rowlist_f, digits, Kpad; bx, by.
 // Defines: tid, lane, wave, wm, wn, frow, fh and acc[J][2]: acc[j][m][e] of lane (frow, fh) of wave (wm, wn) is limb j

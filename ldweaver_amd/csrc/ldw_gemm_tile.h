@@ -1,6 +1,5 @@
-// K loop of the bit-packed fixed-point co-occurrence GEMM for one 128 (to side) x 64 (from side) workgroup tile,
-// shared by gemm_bits_kernel (ldw_gemm_bits.hip: G goes to HBM) and the fused GEMM + MI epilogue kernel
-// (ldw_fused.hip: G stays on chip).  See ldw_gemm_bits.hip for the formulation.
+// K loop of the bit-packed fixed-point co-occurrence GEMM for one 128 (to side) x 64 (from side) workgroup tile of
+// gemm_bits_kernel (ldw_gemm_bits.hip).  See ldw_gemm_bits.hip for the formulation.
 #pragma once
 #include "ldw_internal.h"
 

@@ -16,27 +16,9 @@
 // lists the main stream is evaluating; every per-block buffer exists once per slot (block b uses slot b % LDW_NSLOT).
 #define LDW_NSLOT 3
 
-// LDW_EXPERIMENTS (make EXPERIMENTS=1 -> libldweaver_amd_exp.so): the measured-slower variants kept as the record of what was tried — the
-// pipelined and LDS-shared approximate GEMMs, the fused GEMM + epilogue kernel, the byte-state histogram kernel, corner spans, the split
-// diagonal blocks, the list-driven screen — and the environment switches that select them.  The DEFAULT library holds none of it: the
-// entry points that would select a variant return LDW_ERR_STATE, the switches are not read (ldw::exp_env).
-#ifdef LDW_EXPERIMENTS
-#define LDW_HAS_EXPERIMENTS 1
-#else
-#define LDW_HAS_EXPERIMENTS 0
-#endif
+// Variants measured slower than this code (fused GEMM + epilogue, corner spans, ...) are recorded in docs/HISTORY.md, not kept here.
 
 namespace ldw {
-
-// an environment switch of the experiments build (null in the default library, whatever the environment says)
-inline const char *exp_env(const char *name) {
-#ifdef LDW_EXPERIMENTS
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
 
 void set_error(const char *fmt, ...);
 int hip_fail(hipError_t e, const char *what, const char *file, int line);
@@ -75,7 +57,7 @@ struct BlockStat {
 };
 // what the host knew / learnt about a block (LDW_BLOCK_TRACE=1 prints one line per block at ldw_links_end)
 struct BlockTrace {
-    int diag = 0, guess = -1, B_true = -1, margin = 0, path = 0 /* 0 plain, 1 mixed, 2 apx, 3 fused */, missed = 0, probed = 0;
+    int diag = 0, guess = -1, B_true = -1, margin = 0, path = 0 /* 0 plain, 1 mixed, 2 apx, 4 span */, missed = 0, probed = 0;
     long long n_cand = 0;
 };
 
@@ -143,11 +125,8 @@ struct ldw_ctx {
     int64_t tab11_builds = 0;
     float tab11_c = 0;
     int tab11_nb = 0;
-    bool tab11_on = true;              // LDW_NO_TAB11 switches the table off (A/B measurements)
     ldw::DevBuf pair_sums;             // exact joint sums of the listed pairs (16 per pair)
     ldw::DevBuf pairs[LDW_NSLOT];              // per pipeline slot: pair lists of the approximate screen (counters + PAIR_PATHS x PAIR_SHARDS lists)
-    ldw::DevBuf sub_units[LDW_NSLOT], sub_packs[LDW_NSLOT], sub_bins[LDW_NSLOT], sub_live[LDW_NSLOT];   // the same four for an item's SR sub-pass
-    ldw::DevBuf scr_live[LDW_NSLOT];           // per slot: counter, per-tile summaries and the list of the (tile, column group) combinations the screen has work for
     ldw::DevBuf apx_bins[LDW_NSLOT], apx_clean[LDW_NSLOT];    // per slot: threshold-table bin of every row of the two row lists; clean-region flags of the GEMM epilogue
     ldw::DevBuf apx_mini[LDW_NSLOT];           // per slot: the 32-byte per-SNP extracts k_screen_maybe reads (MiniCol [nt], MiniRow [64 * from-tiles])
     ldw::DevBuf apx_units[LDW_NSLOT], apx_packs[LDW_NSLOT];   // per slot: per-(tile, class) unit lists + counters; per-block SNP constants
@@ -161,14 +140,11 @@ struct ldw_ctx {
     int64_t apx_waves_skipped = 0, apx_waves_total = 0;
     // Spans (r04, docs/HISTORY.md 6b): consecutive long-range-only blocks of one block row run as ONE launch sequence over their concatenated to side
     bool span_on = true;               // ldw_set_span / LDW_NO_SPAN
-    bool diag_split = false;           // ldw_set_span(on | 4) / LDW_DIAG_SPLIT: diagonal blocks as SR sub-pass + weight-ordered long-range pass
-    bool span_corners = false;         // ldw_set_span(on | 2) / LDW_SPAN_CORNERS: corner blocks join the spans (SR sub-passes); measured slower, off by default
     int span_max = 8;                  // most reference blocks per span (LDW_SPAN_MAX env, <= ldw::LDW_SPAN_MAX)
     int64_t maybe_entries = 0;           // entries handed to the maybe list since the context was created (ldw_overflow_report out[3])
     int64_t pair_list_overflows = 0, maybe_overflows = 0;   // blocks / segments redone because a pair list / the maybe list overflowed (ldw_overflow_report)
     bool maybe_off = false;              // the maybe list overflowed in this pass: off until ldw_reset_speculation / new weights
     int64_t span_items = 0, span_blocks = 0, span_fallbacks = 0;   // spans run, reference blocks they covered, segments redone non-speculatively
-    int64_t span_sr_subs = 0;          // SR sub-passes run for corner segments of spans
     bool early_sr = false;             // this pass assigns an item's short-range rows when the item is SUBMITTED (submit order = block order), not in its second phase
     std::atomic<int64_t> sorted_blocks{0};   // (prep_block runs on the helper thread and, for the cold-start probes, on the calling thread at once)
     std::mutex order_mtx;                    // guards order_cache
@@ -269,8 +245,6 @@ struct ldw_ctx {
     void *pin_lrc = nullptr;             // pinned copy of the running long-range row count
     hipEvent_t ev_lrc = nullptr;
     bool lrc_recorded = false;
-    bool fused = false;                  // GEMM + epilogue in one kernel whenever a bucket guess exists (ldw_fused.hip); off:
-                                         // GEMM -> k_mi_screen -> k_mi_units, which measures 7 % faster on C4 (docs/HISTORY.md 5.2)
     bool spec_seen[2] = {false, false};  // a block of this kind (off-diagonal, diagonal) has set its own guess
     bool spec_probed[2] = {false, false};   // the kind's current guess came from a cold-start probe of the kind itself
     std::vector<hipEvent_t> ev_pool;     // 4 timing events per block
@@ -278,7 +252,7 @@ struct ldw_ctx {
     int spec_hist_n[2] = {0, 0};
     bool spec_small[2] = {false, false};   // the kind's blocks keep few rows (< 5000): noisier thresholds, wider margins
     int spec_B_next[2] = {-1, -1};       // bucket guess for the speculative long-range gather: [off-diagonal, diagonal]
-    int64_t spec_misses = 0, fused_blocks = 0, unfused_blocks = 0, screen_violations = 0, mixed_blocks = 0;
+    int64_t spec_misses = 0, blocks_run = 0, screen_violations = 0, mixed_blocks = 0;
     int screen = 1;                      // fp32 screen in front of the fp64 MI evaluation (0 off, 1 on, 2 verify)
     std::vector<ldw::BlockStat> stats;
     std::vector<int32_t> multi_owner;    // r05: ctx[0] of ldw_mi_all_pairs_multi(.., LDW_MI_SR_ROWS_STAY): the deal (owner of every block); empty otherwise
@@ -295,8 +269,6 @@ namespace ldw {
 // launchers implemented in the .hip files (all asynchronous on ctx->stream)
 int ensure_rows(ldw_ctx *ctx);
 int set_dims(ldw_ctx *ctx, int64_t L, int64_t N);   // ldw_api.hip: the shape of the resident alignment; reserves states [L][Npad]
-int launch_hist(ldw_ctx *ctx, const int32_t *idx_f, int nf, const int32_t *idx_t, int nt, const int64_t *pfix_state,
-                int quirk, int lower_only, double *MI);
 // G[t][f] = sum_k [row t has bit k][row f has bit k] * sum_j digits[j][k] 256^j over the bit matrix Mbits[rows][KW words]
 int launch_gemm_bits(ldw_ctx *ctx, const uint64_t *Mbits, int64_t KW, const int32_t *rowlist_t, int RTpad, const int32_t *rowlist_f,
                      int RFpad, int64_t *G, int nlimbs, const int8_t *digits, int lower_only, hipStream_t stream = nullptr, int by0 = 0,

@@ -24,7 +24,6 @@
 // between -> k_lr_append.
 // The short-range test needs no arithmetic per pair: POS is ascending, so the partners of a to-side SNP within sr_dist
 // (circularly) are at most three index intervals of the from-side list, found on the host by binary search (ColInfo).
-// The fused alternative (GEMM + epilogue in one kernel, ldw_set_fused) lives in ldw_fused.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -80,20 +79,7 @@ int ensure_streams(ldw_ctx *c) {
             // small latency-bound kernels that should be dispatched as soon as they are ready: lowest priority for this stream
             int lo_p = 0, hi_p = 0;
             LDW_HIP(hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
-            static const bool prio = exp_env("LDW_NO_STREAM_PRIO") == nullptr;
-            // LDW_CU_RESERVE=m (odd, experiment): the GEMM stream may not use every m-th CU, so that the main stream's chain of small
-            // kernels always finds free CUs while a block-wide kernel runs (an odd modulus spreads the reserved CUs over the XCDs
-            // whether the mask bits run XCD by XCD or interleave them)
-            static const int cu_mod = [] { const char *e = exp_env("LDW_CU_RESERVE"); return e ? atoi(e) : 0; }();
-            if (cu_mod >= 3 && (cu_mod & 1)) {
-                int cus = 256;
-                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-                std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
-                for (int i = 0; i < cus; ++i)
-                    if (i % cu_mod != cu_mod - 1) mask[(size_t)i / 32] |= 1u << (i % 32);
-                LDW_HIP(hipExtStreamCreateWithCUMask(&c->gemm_stream, (uint32_t)mask.size(), mask.data()));
-            } else if (prio) LDW_HIP(hipStreamCreateWithPriority(&c->gemm_stream, hipStreamNonBlocking, lo_p));
-            else LDW_HIP(hipStreamCreateWithFlags(&c->gemm_stream, hipStreamNonBlocking));
+            LDW_HIP(hipStreamCreateWithPriority(&c->gemm_stream, hipStreamNonBlocking, lo_p));
         }
         for (int k = 0; k < LDW_NSLOT; ++k) LDW_HIP(hipEventCreateWithFlags(&c->ev_gemm[k], hipEventDisableTiming));
         // r05: what the streaming lr_links.tsv writer needs on the device side (ldw_lr_stream_begin): made here, not inside a job
@@ -347,7 +333,7 @@ int ldw_links_end(ldw_ctx *c) {
         if (b < (int64_t)c->ev_valid.size() && !c->ev_valid[(size_t)b]) continue;   // a later segment of a span: its time is in the span's first block
         LDW_HIP(hipEventElapsedTime(&t01, ev[0], ev[1]));
         LDW_HIP(hipEventElapsedTime(&t12, ev[c->engine == LDW_ENGINE_MFMA ? 4 : 1], ev[2]));
-        if (c->engine == LDW_ENGINE_MFMA && !c->fused) {   // the screens of the approximate path run behind the GEMM on its stream
+        if (c->engine == LDW_ENGINE_MFMA) {   // the screens of the approximate path run behind the GEMM on its stream
             float t15 = 0;
             if (hipEventElapsedTime(&t15, ev[1], ev[5]) == hipSuccess) t12 += t15;
             else (void)hipGetLastError();   // (an event this block never recorded: the failed query must not surface at the next launch check)
@@ -376,53 +362,29 @@ int ldw_links_end(ldw_ctx *c) {
 // A block can be part of a span when its to side lies strictly AFTER its from side (make_blocks order: i < j), it is square, far enough
 // from its from side that no pair is short-range (POS ascends over the alignment: the test of build_cols on the four end positions), and
 // neither side holds a SNP the fused table test cannot place (no indicator row, or unflagged slots: h_span_bad).
-// Returns 0 (no), 1 (long-range-only) or 2 (a CORNER block: its few short-range pairs — the facing ends of two neighbouring blocks, or the two
-// ends of the circle — go to an SR sub-pass, the rest joins the span).
-static int span_candidate(const ldw_ctx *c, const int32_t *b, const ldw_mi_params *p) {
+// Corner blocks (a few short-range pairs at the facing ends) stay items of their own: docs/HISTORY.md 6b.
+static bool span_candidate(const ldw_ctx *c, const int32_t *b, const ldw_mi_params *p) {
     const int64_t fs = b[0], fe = b[1], ts = b[2], te = b[3];
-    if (!(fs >= 1 && fe >= fs && ts > fe && te >= ts && te <= c->L)) return 0;
+    if (!(fs >= 1 && fe >= fs && ts > fe && te >= ts && te <= c->L)) return false;
     const int64_t nf = fe - fs + 1, nt = te - ts + 1;
-    if (nf != nt || nf < 2048) return 0;
-    if ((int64_t)c->h_span_bad.size() != c->L + 1) return 0;
-    if (c->h_span_bad[(size_t)fe] - c->h_span_bad[(size_t)fs - 1] != 0 || c->h_span_bad[(size_t)te] - c->h_span_bad[(size_t)ts - 1] != 0) return 0;
-    if (!(2 * p->sr_dist < c->g)) return 0;
+    if (nf != nt || nf < 2048) return false;
+    if ((int64_t)c->h_span_bad.size() != c->L + 1) return false;
+    if (c->h_span_bad[(size_t)fe] - c->h_span_bad[(size_t)fs - 1] != 0 || c->h_span_bad[(size_t)te] - c->h_span_bad[(size_t)ts - 1] != 0) return false;
+    if (!(2 * p->sr_dist < c->g)) return false;
     const std::vector<int32_t> &P = c->h_POS;
     const double pf_min = P[(size_t)fs - 1], pf_max = P[(size_t)fe - 1], pt_min = P[(size_t)ts - 1], pt_max = P[(size_t)te - 1];
-    if (pt_min - pf_max > p->sr_dist && pf_min + c->g - pt_max > p->sr_dist) return 1;
-    // Measured (C4, same box, 20 cold steps): spans of long-range-only blocks 36.0 ms per pass; with the corner blocks inside them 39.8 ms although the
-    // serialized kernel time fell from 36.6 to 35.2 ms — 20 large items instead of 28 alternate "diagonal block, span of eight" and the two queues no
-    // longer fill each other's gaps (profiles/r04_timeline_corner_spans.txt) — so corner blocks stay items of their own unless LDW_SPAN_CORNERS=1 /
-    // ldw_set_span(.., corners) asks for them (kept, tested: test_spans_equal_block_by_block runs both)
-    static const bool corners_env = exp_env("LDW_SPAN_CORNERS") != nullptr;
-    if (!corners_env && !c->span_corners) return 0;
-    // short-range pairs of the block: POS ascends, so they sit where the two ranges face each other (directly, or across the origin)
-    auto count_le = [&](int64_t lo, int64_t hi, double v) { return (int64_t)(std::upper_bound(P.begin() + (lo - 1), P.begin() + hi, (int32_t)std::floor(v)) - (P.begin() + (lo - 1))); };
-    const int64_t f_tail = nf - count_le(fs, fe, pt_min - p->sr_dist - 1.0), t_head = count_le(ts, te, pf_max + p->sr_dist);      // from SNPs within sr_dist of the to side's first / to SNPs of the from side's last
-    const int64_t f_head = count_le(fs, fe, pt_max + p->sr_dist - c->g), t_tail = nt - count_le(ts, te, pf_min - p->sr_dist + c->g - 1.0);
-    const int64_t est = f_tail * t_head + f_head * t_tail;   // (an upper bound of the pair count; a quarter of a block's side at most per corner)
-    return (est > 0 && est <= 4000000 && f_tail <= nf / 4 && t_head <= nt / 4 && f_head <= nf / 4 && t_tail <= nt / 4) ? 2 : 0;
+    return pt_min - pf_max > p->sr_dist && pf_min + c->g - pt_max > p->sr_dist;
 }
 // what the whole pass must offer (checked once, after the cold-start probes: a positive guess for off-diagonal blocks exists)
 static bool spans_possible(const ldw_ctx *c, const ldw_mi_params *p) {
     static const bool env_off = getenv("LDW_NO_SPAN") != nullptr;
-    return c->span_on && !env_off && c->span_max >= 2 && c->prune && c->engine == LDW_ENGINE_MFMA && c->apx_ok && !c->fused && c->path_mode != 1 && c->screen == 1 &&
-           !p->sr_only && speculation_pays(c, p) && c->pos_sorted && c->spec_B_next[0] > 0 && c->tab11_on &&
+    return c->span_on && !env_off && c->span_max >= 2 && c->prune && c->engine == LDW_ENGINE_MFMA && c->apx_ok && c->path_mode != 1 && c->screen == 1 &&
+           !p->sr_only && speculation_pays(c, p) && c->pos_sorted && c->spec_B_next[0] > 0 &&
            (p->quirk_mode != LDW_QUIRK_REFERENCE || c->r_min >= 2.0);
-}
-// r04c: a DIAGONAL block can run as SR sub-pass (list order: band GEMM + whole units) + long-range pass with its rows ordered by weight like any
-// long-range-only block (tile pruning, clean regions), the short-range pairs kept out of its candidates: LDW_DIAG_SPLIT=1 / ldw_set_span(on | 4)
-static bool diag_split_ok(const ldw_ctx *c, const int32_t *b) {
-    static const bool env_on = exp_env("LDW_DIAG_SPLIT") != nullptr;
-    if (!env_on && !c->diag_split) return false;
-    const int64_t fs = b[0], fe = b[1];
-    if (!(b[2] == fs && b[3] == fe) || fe - fs + 1 < 2048) return false;
-    if ((int64_t)c->h_span_bad.size() != c->L + 1) return false;
-    return c->h_span_bad[(size_t)fe] - c->h_span_bad[(size_t)fs - 1] == 0;
 }
 struct WorkItem {
     int64_t b0;
     int nseg;           // 1: an ordinary block
-    uint32_t sr_mask;   // segments of a span that are corner blocks (SR sub-pass)
 };
 
 int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const ldw_mi_params *p, int reset) {
@@ -530,8 +492,8 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
     std::vector<uint8_t> cand((size_t)nblocks, 0);
     for (int64_t b = 0; b < nblocks; ++b) cand[(size_t)b] = (uint8_t)span_candidate(c, blocks + b * 4, p);
     int64_t lead = 0;
-    while (lead < nblocks && !cand[(size_t)lead] && !diag_split_ok(c, blocks + lead * 4)) ++lead;   // (a block that may be split is planned after the probes)
-    for (int64_t b = 0; b < lead; ++b) items.push_back(WorkItem{b, 1, 0u});
+    while (lead < nblocks && !cand[(size_t)lead]) ++lead;
+    for (int64_t b = 0; b < lead; ++b) items.push_back(WorkItem{b, 1});
     struct Shared {
         std::mutex m;
         std::condition_variable cv;
@@ -546,13 +508,13 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
     sh.n_planned = (int64_t)items.size();
     sh.plan_final = lead == nblocks;
     sh.prepped.assign((size_t)nblocks + 1, 0);
-    // r04: TWO helpers (a span of eight blocks with a corner segment takes ~3 ms of list building, a diagonal block in front of it gives the
+    // r04: TWO helpers (a span of eight blocks took ~3 ms of list building, a diagonal block in front of it gives the
     // GPU 1.3 ms of work: one helper left the GEMM stream waiting).  Each takes the next item; items k, k+1, k+2 use different slots.
     auto worker = [&]() {
         (void)hipSetDevice(c->device);
         std::vector<int32_t> wfi, wti;   // this helper's own index lists
         for (;;) {
-            WorkItem it{0, 0, 0u};
+            WorkItem it{0, 0};
             int64_t k = 0;
             {
                 std::unique_lock<std::mutex> lk(sh.m);
@@ -592,45 +554,10 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
                         rc = LDW_ERR_HIP;
                     }
                     HostBlock &h = hb[k % RING];
-                    const bool split1 = it.nseg == 1 && (it.sr_mask & 1u);   // a diagonal block: SR sub-pass + weight-ordered long-range pass
-                    if (rc == LDW_OK) rc = prep_block(c, wfi.data(), (int64_t)wfi.size(), wti.data(), (int64_t)wti.size(), p, slot, it.b0, h, it.nseg > 1 ? &spn : nullptr, -1, false, 0, split1);
-                    if (rc == LDW_OK && split1) {
-                        if (h.n_sr_blk > 0 && !h.lo.band_full && !h.generic && h.lo.ordered) {
-                            const size_t base = (h.total + 255) / 256 * 256;
-                            HostBlock sub;
-                            rc = prep_block(c, wfi.data(), (int64_t)wfi.size(), wti.data(), (int64_t)wti.size(), p, slot, it.b0, sub, nullptr, -1, true, base);
-                            if (rc == LDW_OK) {
-                                h.stage_total = (base + sub.total + 255) / 256 * 256;
-                                h.subs.push_back(std::move(sub));
-                                h.subs_seg.push_back(0);
-                            }
-                        } else {   // nothing to split after all: the ordinary form of the block
-                            rc = prep_block(c, wfi.data(), (int64_t)wfi.size(), wti.data(), (int64_t)wti.size(), p, slot, it.b0, h);
-                        }
-                    }
+                    if (rc == LDW_OK) rc = prep_block(c, wfi.data(), (int64_t)wfi.size(), wti.data(), (int64_t)wti.size(), p, slot, it.b0, h, it.nseg > 1 ? &spn : nullptr);
                     if (rc == LDW_OK && it.nseg > 1) {
                         h.span_from = wfi;
                         h.span_to = wti;
-                        // the SR sub-passes of its corner segments: the block alone, in list order, behind the span's own image
-                        size_t base = (h.total + 255) / 256 * 256;
-                        for (int q = 0; q < it.nseg && rc == LDW_OK; ++q) {
-                            if (!((it.sr_mask >> q) & 1u)) continue;
-                            HostBlock sub;
-                            rc = prep_block(c, wfi.data(), (int64_t)wfi.size(), wti.data() + spn.start[q], spn.nt[q], p, slot, it.b0 + q, sub, nullptr, -1, true, base);
-                            if (rc != LDW_OK) break;
-                            if (sub.n_sr_blk <= 0) continue;   // (no pair within sr_dist after all)
-                            if (sub.lo.band_full || sub.generic) {
-                                set_error("corner block %lld cannot take an SR sub-pass", (long long)(it.b0 + q));
-                                rc = LDW_ERR_STATE;
-                                break;
-                            }
-                            h.seg_n_sr[q] = sub.n_sr_blk;
-                            h.seg_lr_total[q] -= sub.n_sr_blk;
-                            base = (base + sub.total + 255) / 256 * 256;
-                            h.subs.push_back(std::move(sub));
-                            h.subs_seg.push_back(q);
-                        }
-                        h.stage_total = base;
                     }
                 }
             } catch (const std::exception &e) {
@@ -655,8 +582,8 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
             if (rc != LDW_OK) return;
         }
     };
-    static const int n_helpers = [] { const char *e = exp_env("LDW_HELPERS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 3 ? 3 : v); }();
-    std::thread helpers[3];
+    constexpr int n_helpers = 2;
+    std::thread helpers[n_helpers];
     for (int i = 0; i < n_helpers; ++i) helpers[i] = std::thread(worker);
     struct Joiner {   // every way out of this function stops and joins the helpers
         Shared &sh;
@@ -676,7 +603,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
     // (the helper is already building the first blocks' lists while the probes run; it stays out of the last slot until they are done)
     // cold start: a sampled guess for each block kind that has none yet (probe_kind_guess), taken from the first block of the kind
     static const bool probe_on = getenv("LDW_NO_PROBE") == nullptr;
-    if (probe_on && !p->sr_only && c->engine != LDW_ENGINE_HIST_STATES && !c->fused && c->pos_sorted && speculation_pays(c, p)) {
+    if (probe_on && !p->sr_only && c->pos_sorted && speculation_pays(c, p)) {
         bool done_kind[2] = {false, false};
         Probe probes[2];
         int n_probe = 0;
@@ -721,11 +648,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
                     ++n;
                 }
             }
-            uint32_t srm = 0;
-            for (int k = 0; k < n; ++k)
-                if (n > 1 && cand[(size_t)(b + k)] == 2) srm |= 1u << k;
-            if (n == 1 && spans && diag_split_ok(c, blocks + b * 4)) srm = 1u;
-            rest.push_back(WorkItem{b, n, srm});
+            rest.push_back(WorkItem{b, n});
             b += n;
         }
         c->early_sr = spans;
@@ -783,7 +706,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
     for (int64_t b = 0; b < nitems && fail_rc == LDW_OK; ++b) {
         HostBlock &cur = hb[b % RING];
         double t0 = now();
-        if (int rc = submit_b(c, cur, p, sl)) { failed(rc, b, false, false); break; }   // unfused: epilogue + pick of item b (main stream)
+        if (int rc = submit_b(c, cur, p, sl)) { failed(rc, b, false, false); break; }   // epilogue + pick of item b (main stream)
         th[0] += now() - t0;
         t0 = now();
         // items b+1 .. b+ahead (GEMM stream) run beside them: b+1 is waited for, the ones after it are taken if they are ready
@@ -993,9 +916,7 @@ int ldw_debug_tab11(ldw_ctx *c, double W, double lo, double delta, double eta, d
 
 int ldw_set_span(ldw_ctx *c, int on, int max_blocks) {
     LDW_REQUIRE(c && (max_blocks == 0 || (max_blocks >= 2 && max_blocks <= LDW_SPAN_MAX)), LDW_ERR_ARG, "ldw_set_span: max_blocks must be 0 or 2..%d", LDW_SPAN_MAX);
-    LDW_REQUIRE(!(on & 6) || LDW_HAS_EXPERIMENTS, LDW_ERR_STATE, "ldw_set_span: corner spans / split diagonal blocks (measured slower, r04) are only in the LDW_EXPERIMENTS build");
-    c->diag_split = (on & 4) != 0;     // bit 2: diagonal blocks as SR sub-pass + weight-ordered long-range pass
-    c->span_corners = (on & 2) != 0;   // bit 1: corner blocks (few short-range pairs) join the spans, their short-range pairs go to SR sub-passes (off by default: slower)
+    LDW_REQUIRE(!(on & 6), LDW_ERR_STATE, "ldw_set_span: corner spans / split diagonal blocks (bits 1, 2; formerly the LDW_EXPERIMENTS build's) were measured slower and have been removed");
     c->span_on = on != 0;
     if (max_blocks) c->span_max = max_blocks;
     return LDW_OK;
@@ -1044,9 +965,8 @@ int ldw_set_mixed(ldw_ctx *c, int on) {
 }
 
 int ldw_set_fused(ldw_ctx *c, int on) {
-    LDW_REQUIRE(!on || LDW_HAS_EXPERIMENTS, LDW_ERR_STATE, "ldw_set_fused(1): the fused GEMM + epilogue kernel (measured slower since r01) is only in the LDW_EXPERIMENTS build");
+    LDW_REQUIRE(!on, LDW_ERR_STATE, "ldw_set_fused(1): the fused GEMM + epilogue kernel (formerly the LDW_EXPERIMENTS build's) was measured slower and has been removed");
     LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
-    c->fused = on != 0;
     return LDW_OK;
 }
 

@@ -11,7 +11,7 @@ int upload_i32(ldw_ctx *c, ldw::DevBuf &buf, const std::vector<int32_t> &v) {
 // Row list of one side of a block.  SNPs are grouped by slot-count CLASS — 1, 2 or 4 indicator rows after padding
 // (0 -> 1, 3 -> 4 with rows of zeros) — in their list order within a class, and every class starts on a 32-row
 // boundary: a 32 x 32 MFMA tile then holds whole SNPs of one class on either side and no SNP straddles the 64 x 32
-// sub-tile of a wave, which is what lets the fused kernel (ldw_fused.hip) run the epilogue on chip.  lrow[k] = row
+// sub-tile of a wave.  lrow[k] = row
 // position of SNP k's first row; pos[p] = k at that position, -1 elsewhere; cls[g] = class of 32-row group g.
 struct SideLists {
     std::vector<int32_t> rowlist, lrow, pos;
@@ -188,8 +188,6 @@ struct LoHost {
     int ordered = 0;                     // rows of the one-row SNPs in order of the minor state's weight (prep_block: tile pruning)
     int fuse_ok = 0;                     // rows of one-row SNPs sit at their slot index in both row lists (no SNP without a row): the
                                          // GEMM's epilogue may apply the threshold table by row (ApxGemmArgs::fuse)
-    int sr_sub = 0;                      // an SR sub-pass (short-range pairs of a span's corner segment): see HostBlock::sr_sub
-    int sr_excl = 0;                     // the block's short-range pairs are evaluated by an SR sub-pass: keep them out of the candidates, list no unit for them
     int span = 0;                        // reference blocks on the to side (0: an ordinary block); sseg: their candidate lists / histograms
     const SpanSeg *sseg = nullptr;
     // r04: the threshold table this item's FIRST phase chose (null: none applies) — its second phase, queued after the first phases of later
@@ -307,23 +305,6 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
     E.nf = (int)nf;
     dim3 egrid((unsigned)(D.nf_tiles > 0 ? D.nf_tiles : (nf + 63) / 64), (unsigned)((nt + EPI_COLS - 1) / EPI_COLS));
     LDW_REQUIRE(egrid.y <= 65535u, LDW_ERR_ARG, "nt too large for the epilogue grid");
-    if (c->engine == LDW_ENGINE_HIST_STATES) {
-        LDW_HIP(hipEventRecord(ev[0], c->stream));
-        LDW_HIP(hipEventRecord(ev[1], c->stream));
-#ifdef LDW_EXPERIMENTS
-        if (int rc = launch_hist(c, D.idx_f, (int)nf, D.idx_t, (int)nt, c->pfix_state.as<int64_t>(), quirk, E.lower_only,
-                                 c->MIblk.as<double>()))
-            return rc;
-#else
-        LDW_REQUIRE(false, LDW_ERR_STATE, "LDW_ENGINE_HIST_STATES is not part of this build (LDW_EXPERIMENTS)");   // (unreachable: ldw_set_engine refuses)
-#endif
-        if (E.cols) {
-            hipLaunchKernelGGL(k_post_mi, egrid, dim3(256), 0, c->stream, E, D.idx_f, D.idx_t, (int)nt, ghist);
-            LDW_HIP(hipGetLastError());
-        }
-        LDW_HIP(hipEventRecord(ev[2], c->stream));
-        return LDW_OK;
-    }
     if (!epilogue_only) {
         if (int rc = Gbuf.reserve((size_t)RFpad * RTpad * 8)) return rc;
         LDW_HIP(hipEventRecord(ev[0], c->stream));
@@ -488,13 +469,9 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
 // ------------------------------------------------------------------------------------------------
 int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RFpad, int RTpad, int quirk, EmitArgs E, hipEvent_t *ev, int phase,
                      hipStream_t gs, unsigned long long *ghist, const LoHost *lo_h, void *zero_hist = nullptr, void *zero_pick = nullptr,
-                     size_t zero_pick_bytes = 0, hipStream_t s2 = nullptr) {
+                     size_t zero_pick_bytes = 0) {
     const int s = lo_h->slot;
-    if (!s2) s2 = c->stream;   // stream of phase 2 (an SR sub-pass runs both of its phases on one stream)
-    // an SR sub-pass has the slot's second set of list / constant buffers: it runs on the main stream while the item's long-range pass, whose
-    // first phase filled the first set on the GEMM stream, still needs them for its second phase
-    ldw::DevBuf &B_units = lo_h->sr_sub ? c->sub_units[s] : c->apx_units[s], &B_packs = lo_h->sr_sub ? c->sub_packs[s] : c->apx_packs[s],
-                &B_bins = lo_h->sr_sub ? c->sub_bins[s] : c->apx_bins[s], &B_live = lo_h->sr_sub ? c->sub_live[s] : c->scr_live[s];
+    hipStream_t s2 = c->stream;   // stream of phase 2
     E.nf = (int)nf;
     E.MI = nullptr;
     dim3 egrid((unsigned)(D.nf_tiles > 0 ? D.nf_tiles : (nf + 63) / 64), (unsigned)((nt + EPI_COLS - 1) / EPI_COLS));
@@ -511,13 +488,11 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     const bool use_pairs = E.scr_mode == 1 && E.do_lr;   // verify mode keeps whole units: it must see the dismissed ones
     // units are evaluated from EXACT sums: the 5-limb GEMM of the tiles they live in (all tiles when any unit can be listed)
     const bool need_exact = E.any_sr || !use_pairs || lo_h->band_full;
-    // (an SR sub-pass only ever lists units that hold a short-range pair: the band's tiles are all the exact GEMM has to cover)
-    const uint8_t *band = ((use_pairs || lo_h->sr_sub) && !lo_h->band_full) ? D.band_mask : nullptr;
-    static const bool band_early_env = exp_env("LDW_BAND_LATE") == nullptr;
-    // r04: the exact band GEMM in phase 1, on the GEMM stream (an SR sub-pass runs both phases on one stream anyway) — for alignments of at
-    // least 4096 sequences, where the GEMMs are long: see screen_main below
+    const uint8_t *band = (use_pairs && !lo_h->band_full) ? D.band_mask : nullptr;
+    // r04: the exact band GEMM in phase 1, on the GEMM stream — for alignments of at least 4096 sequences, where the GEMMs are long: see
+    // screen_main below
     const int64_t swap_kw = [] { const char *e = getenv("LDW_QUEUE_SWAP_KW"); return e ? (int64_t)atol(e) : (int64_t)64; }();   // (per call: the tests lower it)
-    const bool band_early = band_early_env && !lo_h->sr_sub && c->KW >= swap_kw;
+    const bool band_early = c->KW >= swap_kw;
     ldw::DevBuf &Gx = gx(c, s);
     if (phase == 1) {
         if (int rc = c->panel[s][0].reserve((size_t)RFpad * c->KW * 16)) return rc;   // (the scaled panel of k_pack_panel: 16 bytes per word)
@@ -525,15 +500,15 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
             if (int rc = c->panel[s][1].reserve((size_t)RTpad * c->KW * 16)) return rc;
         if (E.do_lr)
             if (int rc = c->Gapx[s].reserve((size_t)RFpad * RTpad * 4)) return rc;
-        if (int rc = B_units.reserve(o_flat + 2 * n_units_max * 8 + 64)) return rc;
-        if (int rc = B_packs.reserve(o_rt + (size_t)nt * 4 + 256)) return rc;
+        if (int rc = c->apx_units[s].reserve(o_flat + 2 * n_units_max * 8 + 64)) return rc;
+        if (int rc = c->apx_packs[s].reserve(o_rt + (size_t)nt * 4 + 256)) return rc;
         if (use_pairs)
             if (int rc = c->pairs[s].reserve(o_pairs + (size_t)PAIR_PATHS * PAIR_SHARDS * pair_cap_for(nf, nt, lo_h->span) * sizeof(PairEnt) +
                                              (size_t)maybe_cap_for(RTpad, RFpad) * sizeof(ApxMaybe) + 64))
                 return rc;
         if (need_exact)
             if (int rc = Gx.reserve((size_t)RFpad * RTpad * 8)) return rc;
-        if (int rc = B_bins.reserve(2 * ((size_t)RTpad + (size_t)RFpad) + (size_t)nt + (size_t)nf_slots + 256 + (size_t)(RTpad / 64) * (size_t)(RFpad / 64) * 4)) return rc;   // (the tile list at its finest: 64 x 64 wave tiles)
+        if (int rc = c->apx_bins[s].reserve(2 * ((size_t)RTpad + (size_t)RFpad) + (size_t)nt + (size_t)nf_slots + 256 + (size_t)(RTpad / 64) * (size_t)(RFpad / 64) * 4)) return rc;   // (the tile list at its finest: 64 x 64 wave tiles)
         if (int rc = c->apx_clean[s].reserve((size_t)(RTpad / 32) * (size_t)(RFpad / 64) + 64)) return rc;
         if (!c->apx_skip.p) {
             if (int rc = c->apx_skip.reserve(64)) return rc;
@@ -541,7 +516,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
         }
     }
     if (phase == 1) {
-        if (E.do_lr && c->tab11_on) {
+        if (E.do_lr) {
             // threshold table of the biallelic pairs, one per block kind (diagonal blocks sit ~8 % below the others): valid for every
             // block whose level is at least the level it was built for — a higher level only widens the true interval, i.e. the
             // table gets looser, and how tight it is decides how many regions the GEMM's epilogue finds clean — so it is rebuilt as
@@ -568,7 +543,6 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     EpiArgs A;
     fill_epi_args(c, D, nf, nt, RFpad, quirk, E, reinterpret_cast<const int64_t *>(c->Gapx[s].p), A);
     A.lo.slot_pfix_hi = c->slot_papx.as<int64_t>();   // the screen derives its cells from the marginals of the approximate weights
-    A.sr_excl = lo_h->sr_excl;
     if (lo_h->span) {
         LDW_REQUIRE(E.scr_mode == 1 && E.do_lr && !E.any_sr && !lo_h->band_full && lo_h->fuse_ok && lo_h->sseg, LDW_ERR_STATE, "a span needs long-range-only blocks and pair lists");
         A.span = lo_h->span;
@@ -578,7 +552,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     // (the table is built for RXY = 1, the floor of the reference's scrambled RXY = r r' / 4 as long as no SNP has r < 2)
     if (phase == 1 || !lo_h->tab_set) {
         lo_h->tab_p = nullptr;
-        if (E.do_lr && c->tab11_on && c->tab11[kd_tab].p && c->tab11_lo[kd_tab] > 0 && E.spec_lo - (double)E.scr_eps >= c->tab11_lo[kd_tab] &&
+        if (E.do_lr && c->tab11[kd_tab].p && c->tab11_lo[kd_tab] > 0 && E.spec_lo - (double)E.scr_eps >= c->tab11_lo[kd_tab] &&
             (quirk != LDW_QUIRK_REFERENCE || c->r_min >= 2.0))
             lo_h->tab_p = c->tab11[kd_tab].as<int2>() + (size_t)c->tab11_cur[kd_tab] * 64 * 64;
         lo_h->tab_set = true;
@@ -589,10 +563,9 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
         A.tab_c = c->tab11_c;
     }
     // long-range-only blocks: the GEMM applies the table itself and neither stores nor lets the screen read the regions that pass
-    static const bool fuse_on = exp_env("LDW_NO_FUSE_TAB") == nullptr;
-    const bool fuse = fuse_on && lo_h->fuse_ok && A.tab11 && A.tab_nb == 64 && (use_pairs || c->screen == 2) && E.do_lr && (!E.any_sr || (D.band_mask && !lo_h->band_full)) && RFpad % 64 == 0 &&   // (verify mode: the clean regions' units are listed as dismissed and checked in fp64)
+    const bool fuse = lo_h->fuse_ok && A.tab11 && A.tab_nb == 64 && (use_pairs || c->screen == 2) && E.do_lr && (!E.any_sr || (D.band_mask && !lo_h->band_full)) && RFpad % 64 == 0 &&   // (verify mode: the clean regions' units are listed as dismissed and checked in fp64)
                       2048 + (size_t)(c->KW / 2) * 256 + 64 * 64 * 8 + 1024 <= 65536;   // (the table shares the GEMM's LDS with the digit arrays)
-    uint8_t *bin_t = B_bins.as<uint8_t>(), *bin_f = bin_t + RTpad;
+    uint8_t *bin_t = c->apx_bins[s].as<uint8_t>(), *bin_f = bin_t + RTpad;
     // pruning flags by row (zeroed per block: padding rows) and by epilogue slot
     // ... and, zeroed with the row flags, the count of the wave tiles the pruning leaves (k_apx_live_tiles), whose list ends the buffer
     uint8_t *rflag_t = bin_f + RFpad, *rflag_f = rflag_t + RTpad;
@@ -609,10 +582,10 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
         A.clean = c->apx_clean[s].as<uint8_t>();
         A.clean_stride = RFpad / 64;
     }
-    char *ub = B_units.as<char>();
+    char *ub = c->apx_units[s].as<char>();
     unsigned int *n_units = reinterpret_cast<unsigned int *>(ub);
     uint64_t *units = reinterpret_cast<uint64_t *>(ub + o_flat);
-    char *pb = B_packs.as<char>();
+    char *pb = c->apx_packs[s].as<char>();
     ColMeta *cp = reinterpret_cast<ColMeta *>(pb), *cph = reinterpret_cast<ColMeta *>(pb + o_cph);
     RowPack *rp = reinterpret_cast<RowPack *>(pb + o_rp), *rph = reinterpret_cast<RowPack *>(pb + o_rph);
     float *rlf = reinterpret_cast<float *>(pb + o_rf), *rlt = reinterpret_cast<float *>(pb + o_rt);
@@ -697,8 +670,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
             P.lower_only = E.lower_only;
             if (fuse) {
                 P.fuse = 1;
-                static const bool std_kernel = getenv("LDW_APX_KERNEL") == nullptr && getenv("LDW_APX_TILE") == nullptr;   // (the experimental GEMM variants know no tile list)
-                P.skip_ctr = (c->prune && lo_h->ordered && std_kernel) ? c->apx_skip.as<unsigned long long>() : nullptr;   // (list order: a tile spans every bin)
+                P.skip_ctr = (c->prune && lo_h->ordered) ? c->apx_skip.as<unsigned long long>() : nullptr;   // (list order: a tile spans every bin)
                 if (P.skip_ctr) {
                     P.tile_list = tile_list;
                     P.n_live = n_live;
@@ -733,8 +705,8 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     A.colpack_hi = cph;
     A.rowpack = rp;
     A.rowpack_hi = rph;
-    // LDW_SCREEN_MAIN=1 (experiment): the block's screen at the head of phase 2 on the main stream — beside the NEXT block's GEMM on the GEMM
-    // stream — instead of behind its own GEMM
+    // The block's screen at the head of phase 2 on the main stream — beside the NEXT block's GEMM on the GEMM stream — instead of behind
+    // its own GEMM.
     // (r04, first attempt: a span's screen at the head of phase 2 went WRONG — phase 2 is queued after the first phase of LATER items, which may
     // rebuild the threshold table for their level; the screen then either found no table it might use and, with it, no clean flags — it read the
     // regions the GEMM's epilogue had not stored: 20-60 million pairs listed per span at C5, overflowing lists, 43 segments redone per pass — or
@@ -745,39 +717,10 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     // ms; the band GEMM alone on the GEMM stream: 35.3 / 34.9; three more alternating pairs at the end: 33.6 / 33.2 / 33.4 against 34.0 / 33.8 /
     // 34.0; C5 819 against 824 ms, 3 misses per pass either way).  Only where the GEMMs are long (N >= 4096): at 85k x 616 the approximate GEMM
     // is 2.7 ms of a 19-ms pass, the GEMM queue would idle and the main queue carry everything — 20.9 / 21.1 against 19.3 / 19.1 ms — so short
-    // alignments keep the old places.  LDW_SCREEN_GEMMQ=1 / LDW_BAND_LATE=1 restore them for any size.
-    static const bool screen_main_env = exp_env("LDW_SCREEN_GEMMQ") == nullptr;
-    const bool screen_main = screen_main_env && !lo_h->sr_sub && c->KW >= swap_kw;
+    // alignments keep the old places.
+    const bool screen_main = c->KW >= swap_kw;
     const int rm_s = quirk == LDW_QUIRK_REFERENCE ? (lo_h->span ? 3 : (nf == nt ? 1 : 2)) : 0;
-#ifdef LDW_EXPERIMENTS
-    // r04 experiment: list-driven screen (k_screen_tiles -> k_screen_live -> k_mi_screen_list) instead of one workgroup per (tile, column group)
-    // (measured r04, C4, 10 cold steps per setting on one box: full grid 36.9 ms per pass, list-driven with 1536 / 4096 / 12288 / 32768 striding
-    // workgroups 38.2 / 37.0 / 36.0 / 37.0: no gain — the dispatcher balances 86k short workgroups better than a strided list does, and the
-    // two list kernels cost what the empty workgroups did; kept behind LDW_SCREEN_LIST=1 in the experiments build)
-    static const bool screen_list = exp_env("LDW_SCREEN_LIST") != nullptr;
-    const size_t o_ts = 64, o_live = o_ts + ((size_t)egrid.x * sizeof(TileState) + 63) / 64 * 64;
-    if (screen_list)
-        if (int rc = B_live.reserve(o_live + (size_t)egrid.x * egrid.y * 4 + 64)) return rc;
-    unsigned int *n_live_scr = screen_list ? B_live.as<unsigned int>() : nullptr;
-    TileState *ts_scr = screen_list ? reinterpret_cast<TileState *>(B_live.as<char>() + o_ts) : nullptr;
-    uint32_t *live_scr = screen_list ? reinterpret_cast<uint32_t *>(B_live.as<char>() + o_live) : nullptr;
-    static const size_t lgrid_max = [] { const char *e = exp_env("LDW_SCREEN_GRID"); return e ? (size_t)atol(e) : (size_t)1536; }();
-    const unsigned lgrid = (unsigned)std::min<size_t>((size_t)egrid.x * egrid.y, lgrid_max);
-#define LDW_SCREEN(RMv, ST)                                                                                                                       \
-    do {                                                                                                                                          \
-        if (screen_list) {                                                                                                                        \
-            hipLaunchKernelGGL(k_screen_tiles, dim3(egrid.x), dim3(64), 0, ST, A, D.perm, (int)egrid.x, ts_scr, n_live_scr);                        \
-            hipLaunchKernelGGL(k_screen_live<true>, dim3(egrid.y), dim3(256), 0, ST, A, D.perm_t, ts_scr, (int)egrid.x, live_scr, n_live_scr);    \
-            hipLaunchKernelGGL((k_mi_screen_list<RMv, true>), dim3(lgrid), dim3(256), 0, ST, A, D.perm, D.perm_t, units, n_units, list_stride,    \
-                               live_scr, n_live_scr);                                                                                             \
-        } else {                                                                                                                                  \
-            hipLaunchKernelGGL((k_mi_screen<RMv, true>), egrid, dim3(256), 0, ST, A, D.perm, D.perm_t, units, n_units, list_stride);                \
-        }                                                                                                                                         \
-    } while (0)
-#else
-    (void)B_live;
 #define LDW_SCREEN(RMv, ST) hipLaunchKernelGGL((k_mi_screen<RMv, true>), egrid, dim3(256), 0, ST, A, D.perm, D.perm_t, units, n_units, list_stride)
-#endif
     if (phase == 1) {
         if (!screen_main) {
             if (rm_s == 0) LDW_SCREEN(0, gs);
@@ -945,8 +888,8 @@ int run_block_mi(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t 
 }
 
 int ensure_links_capacity(ldw_ctx *c, int64_t sr_rows, int64_t lr_rows) {
-    // the fused kernels of earlier blocks write the short-range table on the GEMM stream: a reallocation (rare: the
-    // all-pairs driver sizes the table up front) waits for them and is complete before anything else is queued
+    // a reallocation (rare: the all-pairs driver sizes the table up front) waits for the GEMM stream and is complete before
+    // anything else is queued
     const bool grow_sr = (size_t)sr_rows * 8 > c->sr_mi.cap || (size_t)sr_rows * 4 > c->sr_a.cap || (size_t)sr_rows * 4 > c->sr_b.cap;
     if (grow_sr && c->gemm_stream) LDW_HIP(hipStreamSynchronize(c->gemm_stream));
     if (int rc = c->sr_a.reserve_keep((size_t)sr_rows * 4, (size_t)c->n_sr * 4, c->stream)) return rc;

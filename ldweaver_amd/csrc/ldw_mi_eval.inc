@@ -438,31 +438,6 @@ __global__ void k_apx_stats(const unsigned int *__restrict__ n_units, const unsi
     if (pl_n) acc[2] += (unsigned long long)pl_n[48];   // r05: entries the GEMM's epilogue handed to the maybe list (word 48 of the zeroed list header; 0 when the list is off)
 }
 
-// the same emission for an MI block produced elsewhere (LDW_ENGINE_HIST)
-__global__ __launch_bounds__(256) void k_post_mi(EmitArgs E, const int32_t *__restrict__ idx_f,
-                                                 const int32_t *__restrict__ idx_t, int nt,
-                                                 unsigned long long *__restrict__ ghist) {
-    __shared__ unsigned int sh_hist[NBINS];
-    for (int i = threadIdx.x; i < NBINS; i += 256) sh_hist[i] = 0;
-    __syncthreads();
-    const int a_loc = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int wave = threadIdx.x >> 6;
-    const int b_first = blockIdx.y * EPI_COLS + wave * (EPI_COLS / 4);
-    if (a_loc < E.nf) {
-        const int sa = idx_f[a_loc];
-        for (int it = 0; it < EPI_COLS / 4; ++it) {
-            const int b_loc = b_first + it;
-            if (b_loc >= nt) break;
-            if (E.lower_only && a_loc <= b_loc) continue;
-            const ColInfo c = E.cols[b_loc];
-            emit_pair(E, c, a_loc, b_loc, sa, idx_t[b_loc], E.MI[(int64_t)a_loc + (int64_t)b_loc * E.nf], sh_hist);
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NBINS; i += 256)
-        if (sh_hist[i]) atomicAdd(&ghist[i], (unsigned long long)sh_hist[i]);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Blocks whose SNP lists are NOT ascending in POS (the reference imposes no order on snp.dat$POS: R/computePairwiseMI.R:176-177,
 // :306-333 work on whatever order the lists have).  The short-range partners of a column are then no index interval, so the

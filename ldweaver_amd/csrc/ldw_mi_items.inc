@@ -1,15 +1,14 @@
 // Part of ldw_mi.hip (inside its anonymous namespace): the ITEM pipeline of the all-pairs loop — HostBlock, prep_block (pure host, run by the
 // helper threads), submit_a / submit_b / finish_block / finish_span (the phases of an item), the redo of a span's segment, the cold-start probes.
-// ---- one block of the link loop in phases so that the host work of block i+1 and (fused path) its whole kernel
-// ---- overlap the selection of block i:
+// ---- one block of the link loop in phases so that the host work and the GEMM of block i+1 overlap the selection of block i:
 // ----   prep     pure host, into pinned memory
-// ----   submit_a upload; unfused: the GEMM on the GEMM stream | fused: GEMM + epilogue + bucket pick + copy-back of the pick
-// ----   submit_b unfused: epilogue + bucket pick + copy-back on the main stream | fused: nothing
+// ----   submit_a upload, then the GEMM on the GEMM stream
+// ----   submit_b epilogue + bucket pick + copy-back on the main stream
 // ----   finish   the one host round trip (candidate count), then sorts / threshold / append on the main stream
 struct HostBlock {
     int64_t nf = 0, nt = 0, n_sr_blk = 0, n_lr_total = 0, blk_no = 0;
     int RFpad = 0, RTpad = 0, slot = 0;
-    bool diag = false, fused = false, submitted = false;
+    bool diag = false, submitted = false;
     int nf_tiles = 0;          // tiles of 64 in the padded from-side order
     int gen_t0 = 0, gen_q0 = 0;
     bool mixed = false;        // high-limb GEMM + gathered low limbs (decided with the bucket guess at submit_a)
@@ -33,19 +32,8 @@ struct HostBlock {
     int pin_slot = -1;                 // staging buffer the lists were built in (-1: the slot's own)
     bool force_plain = false;          // never speculate: a span's segment that is redone after a wrong guess
     bool span_alone = false;           // the span could not be submitted as one (no positive guess): its blocks run one by one in finish_span
-    // r04b: short-range pairs of a span's CORNER segments (the neighbouring block pair of the row, the pair that closes the circle) are evaluated by an SR
-    // sub-pass over that block alone, in list order (band GEMM + whole units: the r03 machinery in its SR-only form), queued in front of the span's
-    // own kernels; the span treats the segment as long-range-only and keeps the short-range pairs out of its candidates (EpiArgs::sr_excl)
-    bool sr_sub = false;               // this HostBlock IS such a sub-pass (list order, no ordering of its rows)
-    bool lr_split = false;             // a single block (diagonal) whose short-range pairs go to an SR sub-pass: its own rows are ordered by weight like a
-                                       // long-range-only block's, its screens keep the short-range pairs out (sr_excl), no band, no units
-    size_t stage_base = 0;             // offset of its image in the item's staging buffer
+    size_t stage_base = 0;             // offset of its image in the staging buffer
     int64_t sr_base = 0;               // first row of the item's short-range rows (set when the item is submitted: submit order = block order)
-    int64_t seg_n_sr[LDW_SPAN_MAX] = {};
-    std::vector<HostBlock> subs;       // the SR sub-passes of a span (at most one per segment), subs_seg[i] = its segment
-    std::vector<int> subs_seg;
-    size_t stage_total = 0;            // bytes of the item's whole staging image (its own lists + those of its sub-passes); 0: total
-    bool sr_base_fixed = false;        // sr_base was assigned by the caller (a span's segment that runs alone): do not touch the running row count
     std::vector<int32_t> span_from, span_to;   // the span's SNP lists (host): what a segment that runs on its own is prepared from
 };
 
@@ -60,15 +48,14 @@ struct SpanPlan {
 // 1e6: 5000 SNPs keep 8 % — nearly every unit has to be listed and the lists cost more than evaluating everything: measured on 30k x 2k
 // (tools/keep_frac_probe.py, warm passes, default against plain): 6.5 / 11.2 ms at 0.02 %, 21.2 / 21.6 at 0.5 %, 24.1 / 22.8 at 1 %, 84.7 / 24.9 at
 // 5 %.  Above 0.7 % every block takes the plain path (5-limb GEMM, fp64 MI of every pair, full histogram), cold start included.
-// Only the automatic choice is gated: ldw_set_fused(1) and ldw_set_path(1 | 2) are honoured as given.
+// Only the automatic choice is gated: ldw_set_path(1 | 2) is honoured as given.
 static inline bool speculation_pays(const ldw_ctx *c, const ldw_mi_params *p) {
-    if (c->fused || c->path_mode != 0) return true;
+    if (c->path_mode != 0) return true;
     return !(p->lr_links_approx > 0.0) || p->lr_retain_links < 0.007 * p->lr_links_approx;
 }
 
 int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *to_idx, int64_t nt, const ldw_mi_params *p,
-               int slot, int64_t blk_no, HostBlock &hb, const SpanPlan *sp = nullptr, int pin_slot = -1, bool sr_sub = false, size_t stage_base = 0,
-               bool lr_split = false) {
+               int slot, int64_t blk_no, HostBlock &hb, const SpanPlan *sp = nullptr, int pin_slot = -1, size_t stage_base = 0) {
     LDW_REQUIRE(nf > 0 && nt > 0, LDW_ERR_ARG, "empty block (nf=%lld nt=%lld)", (long long)nf, (long long)nt);
     LDW_REQUIRE(nf <= 1000000 && nt <= 1000000 && nf * nt < 2147483647LL, LDW_ERR_ARG, "block too large (%lld x %lld)",
                 (long long)nf, (long long)nt);
@@ -82,8 +69,6 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     hb.slot = slot;
     hb.blk_no = blk_no;
     hb.pin_slot = pin_slot;
-    hb.sr_sub = sr_sub;
-    hb.lr_split = lr_split;
     hb.stage_base = stage_base;
     hb.diag = same_list(from_idx, nf, to_idx, nt);
     SideLists SF, ST;
@@ -100,8 +85,7 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
         cols.assign((size_t)nt, z);
         hb.n_sr_blk = 0;
     } else if (sp) {
-        // a span: the intervals segment by segment (the long-range-only ones leave build_cols at its range test; one pass over the
-        // concatenated list would take the slow path for all of them as soon as ONE segment is a corner block)
+        // a span: the intervals segment by segment (every segment is long-range-only: build_cols leaves at its range test)
         cols.resize((size_t)nt);
         std::vector<ColInfo> ck;
         for (int k = 0; k < sp->nseg; ++k) {
@@ -114,7 +98,6 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     if (sp) {   // a span: every column learns its reference block and where that block starts in the concatenated to side
         LDW_REQUIRE(!hb.generic && !hb.diag && sp->nseg >= 1 && sp->nseg <= LDW_SPAN_MAX, LDW_ERR_STATE,
                     "span of %d blocks at block %lld cannot be formed", sp->nseg, (long long)blk_no);
-        hb.n_sr_blk = 0;   // (the span itself emits no short-range row: its corner segments' pairs belong to their SR sub-passes; the intervals stay: sr_excl)
         hb.span = sp->nseg;
         for (int k = 0; k < sp->nseg; ++k) {
             hb.seg_start[k] = sp->start[k];
@@ -136,14 +119,14 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     // every SNP has short-range partners there.
     const std::vector<int32_t> *ord_f = nullptr, *ord_t = nullptr;
     std::vector<int32_t> ord_f_own, ord_t_own, ord_f_full, ord_t_full;
-    if (c->prune && !hb.generic && (!hb.diag || lr_split) && !sr_sub && c->engine == LDW_ENGINE_MFMA && c->apx_ok && !c->fused) {
+    if (c->prune && !hb.generic && !hb.diag && c->engine == LDW_ENGINE_MFMA && c->apx_ok) {
         bool rowless = false;
         for (int64_t k = 0; k < nf && !rowless; ++k) rowless = c->h_row0[from_idx[k] + 1] == c->h_row0[from_idx[k]];
         for (int64_t k = 0; k < nt && !rowless; ++k) rowless = c->h_row0[to_idx[k] + 1] == c->h_row0[to_idx[k]];
         if (!rowless) {
             ord_f = minor_weight_order(c, from_idx, nf, ord_f_full);
             ord_t = minor_weight_order(c, to_idx, nt, ord_t_full);
-            if (hb.n_sr_blk > 0 && !lr_split) {
+            if (hb.n_sr_blk > 0) {
                 std::vector<int32_t> df((size_t)nf + 1, 0);
                 std::vector<uint8_t> in_f((size_t)nf, 0), in_t((size_t)nt, 0);
                 for (int64_t b = 0; b < nt; ++b)
@@ -296,13 +279,13 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
                 for (int64_t tx = f0 / 64; tx <= (f1 - 1) / 64; ++tx) band[(size_t)ty * ntx + tx] = 1;
         };
         std::vector<int32_t> nxt1, prv1;   // first one-row SNP at or after / last one before a list position (ordered rows only)
-        if (hb.n_sr_blk > 0 && !hb.lo.band_full && ord_f && !lr_split) {
+        if (hb.n_sr_blk > 0 && !hb.lo.band_full && ord_f) {
             nxt1.assign((size_t)nf + 1, (int32_t)nf);
             prv1.assign((size_t)nf + 1, -1);
             for (int64_t a = nf - 1; a >= 0; --a) nxt1[(size_t)a] = cls_of(from_idx[a]) == 0 ? (int32_t)a : nxt1[(size_t)a + 1];
             for (int64_t a = 0; a < nf; ++a) prv1[(size_t)a + 1] = cls_of(from_idx[a]) == 0 ? (int32_t)a : prv1[(size_t)a];
         }
-        if (hb.n_sr_blk > 0 && !hb.lo.band_full && !lr_split)
+        if (hb.n_sr_blk > 0 && !hb.lo.band_full)
             for (int64_t b2 = 0; b2 < nt; ++b2) {
                 const ColInfo &ci = cols[(size_t)b2];
                 const int64_t rb0 = ST.lrow[(size_t)b2], rb1 = rb0 + (1 << cls_of(to_idx[b2]));
@@ -358,7 +341,7 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     if (c->pin_cap[ps] < stage_base + o) {
         void *np = nullptr;
         LDW_HIP(hipHostMalloc(&np, (stage_base + o) * 2, hipHostMallocDefault));
-        if (c->pin[ps] && stage_base) memcpy(np, c->pin[ps], stage_base);   // (the images of the item's earlier parts)
+        if (c->pin[ps] && stage_base) memcpy(np, c->pin[ps], stage_base);   // (the images in front of it: the first cold-start probe's)
         if (c->pin[ps]) LDW_HIP(hipHostFree(c->pin[ps]));
         c->pin[ps] = np;
         c->pin_cap[ps] = (stage_base + o) * 2;
@@ -422,7 +405,7 @@ int make_emit_args(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
     E.lower_only = hb.diag ? 1 : 0;
     E.keep_sr = p->keep_sr ? 1 : 0;
     E.do_lr = do_lr ? 1 : 0;
-    E.sr_base = (c->early_sr || hb.sr_base_fixed) ? hb.sr_base : c->n_sr;   // (early_sr: the rows were assigned when the item was submitted)
+    E.sr_base = c->early_sr ? hb.sr_base : c->n_sr;   // (early_sr: the rows were assigned when the item was submitted)
     E.sr_a = c->sr_a.as<int32_t>();
     E.sr_b = c->sr_b.as<int32_t>();
     E.sr_mi = c->sr_mi.as<double>();
@@ -456,7 +439,7 @@ int make_emit_args(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
     E.write_dense = (do_lr && hb.spec_B < 0) ? 1 : 0;   // the dense block only feeds k_lr_gather; SR-only passes take the screen path
     E.spec_B = hb.spec_B;
     E.spec_lo = hb.spec_B > 0 ? bucket_lo(hb.spec_B) : -1e300;
-    E.any_sr = (hb.n_sr_blk > 0 && !hb.span && !hb.lr_split) ? 1 : 0;   // (a span / a split block never emits a short-range row itself: sr_excl)
+    E.any_sr = hb.n_sr_blk > 0 ? 1 : 0;
     E.n_cand = &sl.pick[s]->n_cand;
     E.ckey = c->cand_key[s].as<uint64_t>();
     E.cval = c->cand_val[s].as<uint64_t>();
@@ -478,8 +461,7 @@ int make_emit_args(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
     E.scr_scale = (float)std::ldexp(1.0, E.scr_shift - c->frac_bits + (hb.mixed ? 8 * LO_LIMBS : 0));
     E.scr_eps = SCREEN_EPS + (hb.mixed ? (float)lo_bound(c) : 0.0f);
     if (hb.apx) {
-        static const bool r02_bound = exp_env("LDW_SCREEN_R02_BOUND") != nullptr;   // A/B: the bound without the totals argument
-        apx_screen_params(c, E, r02_bound);   // (ldw_epi.h: shared with the test hook ldw_debug_apx_params, so that the brute-force tests price the engine's own constants)
+        apx_screen_params(c, E);   // (ldw_epi.h: shared with the test hook ldw_debug_apx_params, so that the brute-force tests price the engine's own constants)
     }
     E.scr_viol = reinterpret_cast<unsigned long long *>(sl.lr_count + 1);
     hb.E = E;
@@ -509,11 +491,8 @@ int launch_pick(ldw_ctx *c, const HostBlock &hb, const ldw_mi_params *p, const S
     return LDW_OK;
 }
 
-// First phase: upload the block's index structures, then
-//   unfused: the co-occurrence GEMM into this slot's G buffer on the GEMM stream.  Nothing there touches what the
-//            previous block's epilogue / selection still uses, so it overlaps the tail of block b;
-//   fused:   GEMM + epilogue in one kernel, the bucket pick and the copy-back of the pick, all on the GEMM stream:
-//            the whole block overlaps the selection (sorts, host round trip) of the previous one.
+// First phase: upload the block's index structures, then the co-occurrence GEMM into this slot's G buffer on the GEMM stream.
+// Nothing there touches what the previous block's epilogue / selection still uses, so it overlaps the tail of block b.
 static void fill_dev_ptrs(ldw_ctx *c, HostBlock &hb) {
     const char *d = stage_ptr(c, hb);
     auto I = [&](size_t off) { return reinterpret_cast<const int32_t *>(d + off); };
@@ -525,36 +504,13 @@ static void fill_dev_ptrs(ldw_ctx *c, HostBlock &hb) {
                    hb.gen_q0};
 }
 
-// The short-range pairs of one corner segment of a span: the block alone, in list order, through the SR-only form of the approximate path —
-// per-SNP constants, k_mi_screen (lists the units that hold a short-range pair: no MI needed for that), the exact 5-limb GEMM of the band's
-// tiles, k_mi_units (fp64 MI of the listed units; only the short-range pairs are emitted, to their final rows) — both phases on the GEMM
-// given stream (the main one, in front of the item's second phase), with the slot's second set of list / constant buffers.
-int launch_sr_sub(ldw_ctx *c, HostBlock &sub, const ldw_mi_params *p, const SmallLayout &sl, hipStream_t gs, int64_t sr_base) {
-    fill_dev_ptrs(c, sub);
-    ldw_mi_params q = *p;
-    q.sr_only = 1;
-    sub.sr_base = sr_base;
-    sub.sr_base_fixed = true;
-    sub.apx = true;
-    sub.lo.apx = 1;
-    sub.lo.sr_sub = 1;
-    LDW_REQUIRE(!sub.lo.band_full && !sub.generic && sub.n_sr_blk > 0, LDW_ERR_STATE, "SR sub-pass of block %lld: unexpected block structure", (long long)sub.blk_no);
-    if (int rc = make_emit_args(c, sub, &q, sl, -1)) return rc;
-    hipEvent_t dummy[6] = {c->ev[3], c->ev[3], c->ev[3], c->ev[3], c->ev[3], c->ev[3]};
-    if (int rc = launch_block_apx(c, sub.D, sub.nf, sub.nt, sub.RFpad, sub.RTpad, p->quirk_mode, sub.E, dummy, 1, gs, nullptr, &sub.lo)) return rc;
-    if (int rc = launch_block_apx(c, sub.D, sub.nf, sub.nt, sub.RFpad, sub.RTpad, p->quirk_mode, sub.E, dummy, 2, gs, nullptr, &sub.lo, nullptr, nullptr, 0, gs)) return rc;
-    ++c->span_sr_subs;
-    return LDW_OK;
-}
-
 int submit_a(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayout &sl) {
     const int s = hb.slot;
     const int stg = hb.pin_slot >= 0 ? hb.pin_slot : s;   // (a span's segment that runs on its own is staged through the extra buffer)
-    const size_t img = hb.stage_total ? hb.stage_total : hb.total;   // (a span's image includes the lists of its SR sub-passes)
-    if (int rc = c->dstage[stg].reserve(img)) return rc;
+    if (int rc = c->dstage[stg].reserve(hb.total)) return rc;
     // the device image and the per-slot buffers (G, histogram, pick, candidates) were last used by the block two steps back
     if (c->done_recorded[s]) LDW_HIP(hipStreamWaitEvent(c->copy_stream, c->ev_done[s], 0));
-    LDW_HIP(hipMemcpyAsync(c->dstage[stg].p, c->pin[stg], img, hipMemcpyHostToDevice, c->copy_stream));
+    LDW_HIP(hipMemcpyAsync(c->dstage[stg].p, c->pin[stg], hb.total, hipMemcpyHostToDevice, c->copy_stream));
     LDW_HIP(hipEventRecord(c->ev_up[s], c->copy_stream));
     c->up_recorded[s] = true;
     fill_dev_ptrs(c, hb);
@@ -565,34 +521,14 @@ int submit_a(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayou
     if (c->done_recorded[s]) LDW_HIP(hipStreamWaitEvent(gs, c->ev_done[s], 0));
     hipEvent_t *ev = &c->ev_pool[(size_t)hb.blk_no * EVB];
     const bool do_lr = !p->sr_only;
-    int guess = do_lr ? ((speculation_pays(c, p) && !hb.force_plain) ? c->spec_B_next[hb.diag ? 1 : 0] : -1) : 0;
-    if (hb.span > 1 && guess > 0) {
-        // one guess serves every reference block of the span, and the next guess only arrives after all of them: LDW_SPAN_MARGIN=k lowers it by k
-        // more buckets.  Not needed: at C5 (800 kept rows per block, the noisiest thresholds) 3 of 1275 blocks miss per pass with k = 0, as many
-        // as block by block, and k = 4 lists 40 % more pairs (858 against 846 ms per pass)
-        static const int extra_env = [] { const char *e = exp_env("LDW_SPAN_MARGIN"); return e ? atoi(e) : -1; }();
-        const int extra = extra_env >= 0 ? extra_env : 0;
-        guess = guess > extra ? guess - extra : 1;
-    }
-    if (hb.lr_split && !(guess > 0 && c->path_mode != 1 && c->apx_ok && c->screen == 1 && do_lr && !c->fused)) {
-        // prepared for the split, but no positive guess for its kind (no probe for blocks this small, say): the plain path does the whole
-        // block — short-range rows included — on the ordered rows (it reads every position through the row maps)
-        hb.lr_split = false;
-        hb.subs.clear();
-        hb.subs_seg.clear();
-        guess = do_lr ? -1 : 0;
-    }
+    // (a span: one guess serves every reference block, and the next guess only arrives after all of them.  No wider margin is needed: at C5
+    // (800 kept rows per block, the noisiest thresholds) 3 of 1275 blocks miss per pass, as many as block by block)
+    const int guess = do_lr ? ((speculation_pays(c, p) && !hb.force_plain) ? c->spec_B_next[hb.diag ? 1 : 0] : -1) : 0;
     if ((int64_t)c->ev_valid.size() < hb.blk_no + std::max(1, hb.span)) c->ev_valid.resize((size_t)(hb.blk_no + std::max(1, hb.span)), 1);
     c->ev_valid[(size_t)hb.blk_no] = 1;
     for (int k = 1; k < hb.span; ++k) c->ev_valid[(size_t)hb.blk_no + k] = 0;   // (the span's stage events are its first block's; a segment that runs alone records its own)
-    if (c->early_sr && !hb.sr_base_fixed) {
-        // this pass assigns short-range rows in SUBMIT order (= block order): the SR sub-passes of a span write theirs from the GEMM stream, ahead
-        // of the second phase of the items before it
-        int64_t sr_add = 0;
-        if (p->keep_sr) {
-            if (hb.span) for (int k = 0; k < hb.span; ++k) sr_add += hb.seg_n_sr[k];
-            else sr_add = hb.n_sr_blk;
-        }
+    if (c->early_sr) {   // this pass assigns short-range rows in SUBMIT order (= block order)
+        const int64_t sr_add = p->keep_sr ? hb.n_sr_blk : 0;
         if (int rc = ensure_links_capacity(c, c->n_sr + sr_add, c->n_lr)) return rc;
         hb.sr_base = c->n_sr;
         c->n_sr += sr_add;
@@ -600,100 +536,59 @@ int submit_a(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayou
     if (hb.span) {
         // a span runs the approximate path or not at all: should the state it was planned on have gone (no positive guess any more),
         // its reference blocks take the ordinary chain one after the other (finish_span)
-        const bool can = c->path_mode != 1 && c->apx_ok && c->screen == 1 && do_lr && guess > 0 && !c->fused && c->engine == LDW_ENGINE_MFMA;
+        const bool can = c->path_mode != 1 && c->apx_ok && c->screen == 1 && do_lr && guess > 0;
         if (!can) {
             hb.span_alone = true;
             return LDW_OK;
         }
     }
-    hb.fused = c->fused && c->nlimbs <= 5 && (!do_lr || guess >= 0);
-    if (hb.span) c->unfused_blocks += hb.span;
-    else ++(hb.fused ? c->fused_blocks : c->unfused_blocks);
+    c->blocks_run += hb.span ? hb.span : 1;
     hb.guess = guess;
-    if (!hb.fused) {
-        // mixed precision: with a bucket guess the block will run the screen, which only needs the high limbs; the low
-        // limbs follow for the listed units only.  The guess is frozen here because the GEMM commits to it.
-        hb.mixed = c->mixed && c->screen && c->nlimbs == HI_LIMBS + LO_LIMBS && do_lr && guess > 0 && lo_bound(c) < 1e-3 &&
-                   c->N <= 60000;   // the low-limb sums are int32: |sum| <= N * 2^15
-        // approximate GEMM + class-wise popcounts: any block that takes the screen path (a bucket guess exists, or the pass
-        // is SR-only and needs no MI to screen at all)
-        hb.apx = c->path_mode != 1 && c->apx_ok && c->screen && (do_lr ? guess > 0 : true) && hb.nt < (1 << 29);
-        LDW_REQUIRE(c->path_mode != 2 || hb.apx || (do_lr && guess <= 0), LDW_ERR_STATE,
-                    "ldw_set_path(2): the approximate path is not available (delta %.3g, %d weight classes, %lld sequences, screen %d)", c->apx_delta,
-                    c->n_classes, (long long)c->N, c->screen);
-        LDW_REQUIRE(!hb.lr_split || hb.apx, LDW_ERR_STATE, "block %lld was prepared for the split (SR sub-pass + ordered long-range pass) but cannot take the approximate path",
-                    (long long)hb.blk_no);
-        if (hb.apx) {
-            hb.mixed = false;
-            hb.lo.apx = 1;
-            c->apx_blocks += hb.span ? hb.span : 1;
-        }
-        if (hb.span) {
-            ++c->span_items;
-            c->span_blocks += hb.span;
-        }
-        if (hb.mixed) ++c->mixed_blocks;
-        if (hb.apx) {
-            // phase 1 of the approximate path: panels, GEMM, SNP constants and the screens, all beside the previous block's tail.
-            // The emission constants of phase 2 (table pointers, row base) are refreshed in submit_b.
-            if (int rc = make_emit_args(c, hb, p, sl, do_lr ? guess : -1)) return rc;
-            if (int rc = c->hist[s].reserve((size_t)NBINS * 8 * (size_t)(hb.span ? hb.span : 1))) return rc;
-            hb.lo.span = hb.span;
-            hb.lo.sseg = hb.sseg;
-            hb.lo.sr_excl = ((hb.span && !hb.subs.empty()) || hb.lr_split) ? 1 : 0;
-            if (int rc = launch_block_apx(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, hb.E, ev, 1, gs, nullptr, &hb.lo, c->hist[s].p, sl.pick[s],
-                                          PICK_STRIDE * (size_t)(hb.span ? hb.span : 1)))
-                return rc;
-            LDW_HIP(hipEventRecord(c->ev_gemm[s], gs));
-            return LDW_OK;
-        }
-        EmitArgs E;
-        memset(&E, 0, sizeof(E));
-        E.lower_only = hb.diag ? 1 : 0;
-        E.do_lr = do_lr ? 1 : 0;
-        if (int rc = launch_block_mi(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, E, ev, 1, &gx(c, s), gs, nullptr,
-                                     hb.mixed ? &hb.lo : nullptr))
+    // mixed precision: with a bucket guess the block will run the screen, which only needs the high limbs; the low
+    // limbs follow for the listed units only.  The guess is frozen here because the GEMM commits to it.
+    hb.mixed = c->mixed && c->screen && c->nlimbs == HI_LIMBS + LO_LIMBS && do_lr && guess > 0 && lo_bound(c) < 1e-3 &&
+               c->N <= 60000;   // the low-limb sums are int32: |sum| <= N * 2^15
+    // approximate GEMM + class-wise popcounts: any block that takes the screen path (a bucket guess exists, or the pass
+    // is SR-only and needs no MI to screen at all)
+    hb.apx = c->path_mode != 1 && c->apx_ok && c->screen && (do_lr ? guess > 0 : true) && hb.nt < (1 << 29);
+    LDW_REQUIRE(c->path_mode != 2 || hb.apx || (do_lr && guess <= 0), LDW_ERR_STATE,
+                "ldw_set_path(2): the approximate path is not available (delta %.3g, %d weight classes, %lld sequences, screen %d)", c->apx_delta,
+                c->n_classes, (long long)c->N, c->screen);
+    if (hb.apx) {
+        hb.mixed = false;
+        hb.lo.apx = 1;
+        c->apx_blocks += hb.span ? hb.span : 1;
+    }
+    if (hb.span) {
+        ++c->span_items;
+        c->span_blocks += hb.span;
+    }
+    if (hb.mixed) ++c->mixed_blocks;
+    if (hb.apx) {
+        // phase 1 of the approximate path: panels, GEMM, SNP constants and the screens, all beside the previous block's tail.
+        // The emission constants of phase 2 (table pointers, row base) are refreshed in submit_b.
+        if (int rc = make_emit_args(c, hb, p, sl, do_lr ? guess : -1)) return rc;
+        if (int rc = c->hist[s].reserve((size_t)NBINS * 8 * (size_t)(hb.span ? hb.span : 1))) return rc;
+        hb.lo.span = hb.span;
+        hb.lo.sseg = hb.sseg;
+        if (int rc = launch_block_apx(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, hb.E, ev, 1, gs, nullptr, &hb.lo, c->hist[s].p, sl.pick[s],
+                                      PICK_STRIDE * (size_t)(hb.span ? hb.span : 1)))
             return rc;
         LDW_HIP(hipEventRecord(c->ev_gemm[s], gs));
         return LDW_OK;
     }
-    const int64_t sr_add = p->keep_sr ? hb.n_sr_blk : 0;
-    if (int rc = ensure_links_capacity(c, c->n_sr + sr_add, c->n_lr)) return rc;
-    if (int rc = c->hist[s].reserve((size_t)NBINS * 8)) return rc;
-    if (int rc = make_emit_args(c, hb, p, sl, do_lr ? guess : -1)) return rc;
-    c->n_sr += sr_add;
-    LDW_HIP(hipMemsetAsync(c->hist[s].p, 0, (size_t)NBINS * 8, gs));
-    LDW_HIP(hipMemsetAsync(sl.pick[s], 0, sizeof(ldw::PickOut), gs));
-    FusedArgs F;
-    F.Mbits = c->Mbits.as<uint64_t>();
-    F.KW = c->KW;
-    F.Kpad = c->KW * 64;
-    F.rowlist_t = hb.D.rl_t;
-    F.rowlist_f = hb.D.rl_f;
-    F.digits = c->digits.as<int8_t>();
-    F.pos_f = hb.D.pos_f;
-    F.pos_t = hb.D.pos_t;
-    F.cls_f = hb.D.cls_f;
-    F.cls_t = hb.D.cls_t;
-    F.ghist = c->hist[s].as<unsigned long long>();
-    fill_epi_args(c, hb.D, hb.nf, hb.nt, hb.RFpad, p->quirk_mode, hb.E, nullptr, F.A);
-    LDW_HIP(hipEventRecord(ev[0], gs));
-#ifdef LDW_EXPERIMENTS
-    if (int rc = launch_fused(c, F, hb.RFpad, hb.RTpad, c->nlimbs, gs)) return rc;
-#else
-    LDW_REQUIRE(false, LDW_ERR_STATE, "the fused kernel is not part of this build (LDW_EXPERIMENTS)");   // (unreachable: ldw_set_fused refuses)
-#endif
-    LDW_HIP(hipEventRecord(ev[1], gs));
-    LDW_HIP(hipEventRecord(ev[4], gs));
-    LDW_HIP(hipEventRecord(ev[2], gs));
-    if (int rc = launch_pick(c, hb, p, sl, gs)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->pin_pick[s], sl.pick[s], sizeof(ldw::PickOut), hipMemcpyDeviceToHost, gs));
-    LDW_HIP(hipEventRecord(c->ev_pick[s], gs));
+    EmitArgs E;
+    memset(&E, 0, sizeof(E));
+    E.lower_only = hb.diag ? 1 : 0;
+    E.do_lr = do_lr ? 1 : 0;
+    if (int rc = launch_block_mi(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, E, ev, 1, &gx(c, s), gs, nullptr,
+                                 hb.mixed ? &hb.lo : nullptr))
+        return rc;
     LDW_HIP(hipEventRecord(c->ev_gemm[s], gs));
     return LDW_OK;
 }
 
-// Second phase (unfused path only): epilogue, histogram pick and the copy-back of the pick on the main stream.
+// Second phase: epilogue, histogram pick and the copy-back of the pick on the main stream.
 // A block in generic order (HostBlock::generic): dense MI of every pair by the plain path, then the reference's pair list from the
 // dense block with the len predicate (k_gen_count -> host scan of the 2 nt column counts -> k_gen_emit_sr, k_pick_bucket,
 // k_gen_gather).  Synchronous where it needs the counts; such blocks are the exception (the reference's own parser emits ascending
@@ -775,41 +670,23 @@ int submit_generic(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
 }
 
 int submit_b(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayout &sl) {
-    if (hb.fused || hb.span_alone) return LDW_OK;
+    if (hb.span_alone) return LDW_OK;
     if (hb.generic) return submit_generic(c, hb, p, sl);
     const int s = hb.slot;
     LDW_HIP(hipStreamWaitEvent(c->stream, c->ev_up[s], 0));
     if (c->engine == LDW_ENGINE_MFMA) LDW_HIP(hipStreamWaitEvent(c->stream, c->ev_gemm[s], 0));
     const bool do_lr = !p->sr_only;
-    const int64_t sr_add = (p->keep_sr && !c->early_sr && !hb.sr_base_fixed) ? hb.n_sr_blk : 0;   // (early_sr: assigned in submit_a)
+    const int64_t sr_add = (p->keep_sr && !c->early_sr) ? hb.n_sr_blk : 0;   // (early_sr: assigned in submit_a)
     if (int rc = ensure_links_capacity(c, c->n_sr + sr_add, c->n_lr)) return rc;
     if (int rc = c->hist[s].reserve((size_t)NBINS * 8)) return rc;
     if (!hb.apx) LDW_HIP(hipMemsetAsync(c->hist[s].p, 0, (size_t)NBINS * 8, c->stream));   // (the approximate path zeroed both in its first phase: k_zero4)
-    if (int rc = make_emit_args(c, hb, p, sl, (hb.mixed || hb.apx) ? (do_lr ? hb.guess : -1) : ((do_lr && c->engine != LDW_ENGINE_HIST_STATES) ? c->spec_B_next[hb.diag ? 1 : 0] : -1)))   // (the bit-plane histogram engine shares the epilogue: it speculates like the MFMA engine)
+    if (int rc = make_emit_args(c, hb, p, sl, (hb.mixed || hb.apx) ? (do_lr ? hb.guess : -1) : (do_lr ? c->spec_B_next[hb.diag ? 1 : 0] : -1)))   // (the bit-plane histogram engine shares the epilogue: it speculates like the MFMA engine)
         return rc;
     if (!hb.apx) LDW_HIP(hipMemsetAsync(sl.pick[s], 0, sizeof(ldw::PickOut), c->stream));
     hipEvent_t *ev = &c->ev_pool[(size_t)hb.blk_no * EVB];
-    // the SR sub-passes of the item (a split diagonal block; the corner segments of a span) — on the MAIN stream, in front of the item's own second
-    // phase: on the GEMM stream (r04b) they lengthened the longer of the two queues (39.8 against 36.0 ms per C4 pass with the corner blocks)
-    if (hb.apx && !hb.subs.empty() && p->keep_sr) {
-        if (!hb.span) {
-            if (int rc = launch_sr_sub(c, hb.subs[0], p, sl, c->stream, hb.sr_base)) return rc;
-        } else {
-            int64_t base = hb.sr_base;
-            size_t si = 0;
-            for (int k = 0; k < hb.span; ++k) {
-                if (si < hb.subs.size() && hb.subs_seg[si] == k) {
-                    if (int rc = launch_sr_sub(c, hb.subs[si], p, sl, c->stream, base)) return rc;
-                    ++si;
-                }
-                base += hb.seg_n_sr[k];
-            }
-        }
-    }
     if (hb.apx) {
         hb.lo.span = hb.span;
         hb.lo.sseg = hb.sseg;
-        hb.lo.sr_excl = ((hb.span && !hb.subs.empty()) || hb.lr_split) ? 1 : 0;
         if (int rc = launch_block_apx(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, hb.E, ev, 2, nullptr, c->hist[s].as<unsigned long long>(), &hb.lo))
             return rc;
     } else if (int rc = launch_block_mi(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, hb.E, ev, c->engine == LDW_ENGINE_MFMA ? 2 : 3,
@@ -937,25 +814,23 @@ int finish_block(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallL
     const int s = hb.slot;
     // ---- the one host round trip of the block: the candidate count sizes the sorts ----
     LDW_HIP(hipEventSynchronize(c->ev_pick[s]));
-    if (hb.fused) LDW_HIP(hipStreamWaitEvent(c->stream, c->ev_gemm[s], 0));   // selection runs on the main stream
     ldw::PickOut *hp = static_cast<ldw::PickOut *>(c->pin_pick[s]);
     bool missed = false;
     if (do_lr && hb.spec_B >= 0 && hp->n > 0 && !hp->spec_ok) {
         // the bucket guess was above the true bucket: redo the epilogue non-speculatively (the short-range rows are
         // already final): full histogram, dense store, then pick and gather with the true bucket.  The plain two-kernel
-        // path still has G; the fused and the mixed-precision ones have to run the (full) GEMM again.
+        // path still has G; the mixed-precision and the approximate ones have to run the (full) GEMM again.
         EmitArgs E = hb.E;
         E.write_dense = 1;
         E.spec_B = -1;
         E.keep_sr = 0;
-        E.any_sr = hb.n_sr_blk > 0 ? 1 : 0;   // (a split block's speculative pass had it off — sr_excl —: the plain epilogue must keep its short-range pairs out of the histogram itself)
         E.scr_mode = 0;   // every pair goes into the histogram
         hb.spec_B = -1;
         LDW_HIP(hipMemsetAsync(c->hist[s].p, 0, (size_t)NBINS * 8, c->stream));
         LDW_HIP(hipMemsetAsync(sl.pick[s], 0, sizeof(ldw::PickOut), c->stream));
         hipEvent_t dummy[6] = {c->ev[3], c->ev[3], c->ev[4], c->ev[3], c->ev[5], c->ev[3]};   // keep the block's stage events as they are
         E.apx = 0;
-        if (int rc = launch_block_mi(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, E, dummy, (hb.fused || hb.mixed || hb.apx) ? 3 : 2,
+        if (int rc = launch_block_mi(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, E, dummy, (hb.mixed || hb.apx) ? 3 : 2,
                                      &gx(c, s), nullptr, c->hist[s].as<unsigned long long>()))
             return rc;
         if (int rc = launch_pick(c, hb, p, sl, c->stream)) return rc;
@@ -973,7 +848,7 @@ int finish_block(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallL
         tr.diag = hb.diag ? 1 : 0;
         tr.guess = hb.guess;
         tr.B_true = do_lr ? hp->B_true : -1;
-        tr.path = hb.fused ? 3 : (hb.apx ? 2 : (hb.mixed ? 1 : 0));
+        tr.path = hb.apx ? 2 : (hb.mixed ? 1 : 0);
         tr.missed = (missed || hb.force_plain) ? 1 : 0;
         tr.n_cand = do_lr ? (long long)hp->n_cand : 0;
     }
@@ -1013,14 +888,6 @@ int run_block_alone(ldw_ctx *c, const HostBlock &span, int k, const ldw_mi_param
     if (c->gemm_stream) LDW_HIP(hipStreamSynchronize(c->gemm_stream));
     if (int rc = prep_block(c, span.span_from.data(), span.nf, ti, span.seg_nt[k], p, span.slot, span.blk_no + k, hb, nullptr, LDW_NSLOT)) return rc;
     hb.force_plain = force_plain;
-    // the segment's short-range rows: their place was assigned with the span; after a wrong guess (force_plain) the span's SR sub-pass has
-    // already written them
-    ldw_mi_params q = *p;
-    if (force_plain) q.keep_sr = 0;
-    hb.sr_base = span.sr_base;
-    for (int j = 0; j < k; ++j) hb.sr_base += span.seg_n_sr[j];
-    hb.sr_base_fixed = true;
-    p = &q;
     if (int rc = submit_a(c, hb, p, sl)) return rc;
     if (int rc = submit_b(c, hb, p, sl)) return rc;
     if (int rc = finish_block(c, hb, p, sl)) return rc;
@@ -1068,7 +935,7 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
         }
     }
     // the common case — every guess held, every candidate set fits the sort-free selection — takes ONE launch per stage for all segments
-    static const bool sel_fast_on = getenv("LDW_NO_FAST_SELECT") == nullptr && exp_env("LDW_NO_SPAN_SELECT") == nullptr;
+    static const bool sel_fast_on = getenv("LDW_NO_FAST_SELECT") == nullptr;
     bool batched = sel_fast_on && c->select_mode == 0;
     long long m_max = 0, m_sum = 0;
     for (int k = 0; k < hb.span && batched; ++k) {
@@ -1123,7 +990,6 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
             S.bitmap[k] = c->sel_bitmap.as<uint32_t>() + woff[k];
             S.chunks[k] = c->sel_chunks.as<uint32_t>() + coff[k];
             S.supers[k] = c->sel_prefix.as<uint32_t>() + (size_t)k * SEL_MAX_SUPER;
-            DA.n_sr[k] = hb.seg_n_sr[k];
         }
         const unsigned gridm = (unsigned)std::max<long long>(1, (m_max + 255) / 256);
         hipLaunchKernelGGL(k_sel_thresh_span, dim3(1, (unsigned)hb.span), dim3(1024), 0, c->stream, S);
@@ -1164,7 +1030,7 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
         S.nf = hb.nf;
         S.nt = hb.seg_nt[k];
         S.blk_no = hb.blk_no + k;
-        S.n_sr_blk = hb.seg_n_sr[k];
+        S.n_sr_blk = 0;   // (every segment is long-range-only)
         S.ck = hb.sseg[k].ckey;
         S.cv = hb.sseg[k].cval;
         S.pick = reinterpret_cast<ldw::PickOut *>(reinterpret_cast<char *>(sl.pick[s]) + (size_t)k * PICK_STRIDE);
@@ -1215,7 +1081,7 @@ int probe_enqueue(ldw_ctx *c, const int32_t *fi, int64_t nf, const int32_t *ti, 
     P.queued = false;
     // (host staging of the LAST slot: the helper threads of ldw_mi_all_pairs are already building the first blocks' lists in the others)
     constexpr int PS = LDW_NSLOT - 1;
-    if (int rc = prep_block(c, sf.data(), (int64_t)sf.size(), st.data(), (int64_t)st.size(), &q, PS, 0, hb, nullptr, -1, false, pin_base)) return rc;
+    if (int rc = prep_block(c, sf.data(), (int64_t)sf.size(), st.data(), (int64_t)st.size(), &q, PS, 0, hb, nullptr, -1, pin_base)) return rc;
     hb.slot = which;      // the DEVICE side of the probe is slot `which`'s (the blocks are submitted after the probes)
     hb.lo.slot = which;
     hb.stage_base = 0;    // (its device image starts its slot's staging buffer)
@@ -1256,14 +1122,12 @@ void probe_collect(ldw_ctx *c, const Probe &P) {
     }
 }
 
-// whether the next block can be submitted before the current one is finished: the fused path needs a bucket guess
+// whether the next block can be submitted before the current one is finished
 bool can_submit_early(ldw_ctx *c, const HostBlock &hb, const ldw_mi_params *p) {
     if (!c->overlap) return false;
     if (!p->sr_only && !speculation_pays(c, p)) return true;   // (plain blocks need no guess)
     // no bucket guess for this kind of block yet (the first blocks of a cold pass): the block in flight is about to provide one —
     // submitted now, this block would take the non-speculative path (full 5-limb GEMM, fp64 for every pair: ~4 ms more)
-    if (c->engine == LDW_ENGINE_MFMA && !p->sr_only && c->screen && c->spec_B_next[hb.diag ? 1 : 0] < 0) return false;
-    if (c->engine != LDW_ENGINE_MFMA || !c->fused || c->nlimbs > 5 || p->sr_only) return true;
-    return c->spec_B_next[hb.diag ? 1 : 0] >= 0;
+    return !(c->engine == LDW_ENGINE_MFMA && !p->sr_only && c->screen && c->spec_B_next[hb.diag ? 1 : 0] < 0);
 }
 

@@ -787,112 +787,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LDW_SCREEN_
     screen_wg<RM, APX>(A, perm_f, perm_t, units, n_units, list_stride, cm, (int)blockIdx.x, (int)blockIdx.y);
 }
 
-#ifdef LDW_EXPERIMENTS
-// r04: LIST-DRIVEN.  Three quarters of the (tile, column group) combinations of a long-range block have nothing to screen — all four of their
-// regions flagged clean by the GEMM's epilogue or pruned with their tile, or every column dead against the tile's kind — and each of them still
-// cost a workgroup dispatch (~4 ns: the floor of the full-grid kernel was 47 us per 10k x 10k block, 0.33 ms per span of seven, with every
-// column dropped).  k_screen_live lists the combinations that are left; a fixed grid of workgroups strides over the list.
-template <int RM, bool APX>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_mi_screen_list(EpiArgs A, const int32_t *__restrict__ perm_f,
-                                                                                                 const int32_t *__restrict__ perm_t,
-                                                                                                 uint64_t *__restrict__ units,
-                                                                                                 unsigned int *__restrict__ n_units, int64_t list_stride,
-                                                                                                 const uint32_t *__restrict__ live,
-                                                                                                 const unsigned int *__restrict__ n_live) {
-    __shared__ ColMeta cm[EPI_COLS];
-    const unsigned int n = *n_live;
-    for (unsigned int i = blockIdx.x; i < n; i += gridDim.x) {
-        const uint32_t e = live[i];
-        screen_wg<RM, APX>(A, perm_f, perm_t, units, n_units, list_stride, cm, (int)(e & 0xFFFFu), (int)(e >> 16));
-        __syncthreads();   // (cm is staged again for the next entry)
-    }
-}
-
-// Which (from-tile, column group) combinations does k_mi_screen have something to do for?  Its own workgroup-wide exits, from flags alone:
-// outside its domain (tiles / columns of the generic screen); all four 32-column regions clean; every column dead against the tile's kind
-// (long-range-only blocks); on a diagonal block every column's SNP behind every SNP of the tile.  One workgroup per column group, its
-// threads stride over the tiles; entries = tile | column group << 16, appended per wave.
-struct TileState {
-    int amax;            // largest list index among the tile's SNPs (-1: none)
-    unsigned kind;       // bit 0: all real SNPs of kind 2, bit 1: all of kind 3, bit 2: all dead versus kind 2, bit 3: all dead versus kind 3, bit 4: some real SNP
-};
-__global__ __launch_bounds__(64) void k_screen_tiles(EpiArgs A, const int32_t *__restrict__ perm_f, int ntiles, TileState *__restrict__ ts,
-                                                     unsigned int *__restrict__ n_live) {
-    const int tile = blockIdx.x, lane = threadIdx.x;
-    int a = perm_f[tile * 64 + lane];
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_xor(a, off);
-        a = o > a ? o : a;
-    }
-    unsigned kind = 0;
-    if (A.sflag_f) {
-        const unsigned fa = A.sflag_f[tile * 64 + lane];
-        const bool real = (fa & PF_PAD) == 0u;
-        const unsigned ka = fa & PF_KIND;
-        kind = (__ballot(real && ka != 2u) == 0ull ? 1u : 0u) | (__ballot(real && ka != 3u) == 0ull ? 2u : 0u) | (__ballot(real && !(fa & PF_DEAD2)) == 0ull ? 4u : 0u) |
-               (__ballot(real && !(fa & PF_DEAD3)) == 0ull ? 8u : 0u) | (__ballot(real) != 0ull ? 16u : 0u);
-    }
-    if (lane == 0) ts[tile] = TileState{a, kind};
-    if (n_live && tile == 0 && lane == 0) *n_live = 0u;   // (k_screen_live, next on the stream, counts from zero)
-}
-template <bool APX>
-__global__ __launch_bounds__(256) void k_screen_live(EpiArgs A, const int32_t *__restrict__ perm_t, const TileState *__restrict__ ts, int ntiles,
-                                                     uint32_t *__restrict__ live, unsigned int *__restrict__ n_live) {
-    __shared__ unsigned int s_dead[8];   // [tile state: (k2 | k3) x all_dead2 x all_dead3]: every column of the group dead for such a tile
-    __shared__ int s_minb;
-    const int cgy = blockIdx.x, t = threadIdx.x;
-    const int q0 = cgy * EPI_COLS;
-    if (t < 8) s_dead[t] = 1u;
-    if (t == 0) s_minb = 0x7FFFFFFF;
-    __syncthreads();
-    const bool prune_on = APX && A.sflag_f && A.E.do_lr && !A.E.any_sr && A.E.scr_mode != 2;
-    if (t < EPI_COLS) {
-        const int q = q0 + t;
-        if (q < A.nt) {
-            if (A.E.lower_only) atomicMin(&s_minb, perm_t[q]);
-            if (prune_on) {
-                const unsigned fb = A.sflag_t[q], kb = fb & PF_KIND;
-                for (int s = 0; s < 8; ++s) {
-                    const bool all_k2 = (s & 4) == 0, ad2 = (s & 1) != 0, ad3 = (s & 2) != 0;   // s: bit 2 = tile of kind 3 (else kind 2)
-                    const bool dead = kb >= 2u && ((kb == 2u ? ad2 : ad3) || (fb & (all_k2 ? PF_DEAD2 : PF_DEAD3)) != 0u);
-                    if (!dead) s_dead[s] = 0u;   // (benign race: every writer stores 0)
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const bool whole = q0 + EPI_COLS <= A.nt;
-    for (int tile0 = 0; tile0 < ntiles; tile0 += 256) {
-        const int tile = tile0 + t;
-        bool keep = tile < ntiles && tile < A.gen_t0 && q0 < A.gen_q0;
-        if (keep && APX && A.clean && A.E.scr_mode != 2 && tile < A.clean_stride && whole && q0 + EPI_COLS <= A.gen_q0) {
-            bool all_clean = true;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) all_clean = all_clean && A.clean[(int64_t)((q0 + w * (EPI_COLS / 4)) / 32) * A.clean_stride + tile] != 0;
-            keep = !all_clean;
-        }
-        if (keep) {
-            const TileState T = ts[tile];
-            if (A.E.lower_only && whole && A.E.scr_mode != 2 && s_minb >= T.amax) keep = false;   // no pair: every column's SNP behind every SNP of the tile
-            if (keep && prune_on && whole && (T.kind & 16u) && (T.kind & 3u)) {
-                const int s = ((T.kind & 1u) ? 0 : 4) | ((T.kind >> 2) & 3u);
-                if (s_dead[s]) keep = false;
-            }
-        }
-        const unsigned long long mk = __ballot(keep);
-        if (mk != 0ull) {
-            unsigned int base = 0;
-            const int lane = t & 63;
-            if (lane == __builtin_ctzll(mk)) base = atomicAdd(n_live, (unsigned int)__popcll(mk));
-            base = (unsigned int)__shfl((int)base, __builtin_ctzll(mk));
-            if (keep) live[base + (unsigned int)__popcll(mk & ((1ull << lane) - 1ull))] = (uint32_t)tile | ((uint32_t)cgy << 16);
-        }
-    }
-}
-
-#endif   // LDW_EXPERIMENTS
-
 // ------------------------------------------------------------------------------------------------
 // k_mi_screen_generic: the fp32 screen for the units k_mi_screen leaves out — a from-tile or a column whose SNPs have >= 3
 // minor states (or none).  Those are 1-2 % of the units, but unscreened they were a quarter of the fp64 kernel's list,

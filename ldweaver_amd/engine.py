@@ -134,8 +134,7 @@ class Engine:
 
     def set_span(self, on: bool, max_blocks: int = 0, corners: bool = False, diag_split: bool = False):
         """Spans (default on): consecutive long-range-only block pairs of one block row run as one launch sequence; results never depend on it.
-        corners: corner block pairs join them too (their short-range pairs through SR sub-passes; slower, off by default).
-        diag_split: diagonal blocks run as SR sub-pass + weight-ordered long-range pass (off by default)."""
+        corners / diag_split: the corner-span and split-diagonal-block variants, measured slower and removed: LdwError (LDW_ERR_STATE)."""
         L.check(L.lib().ldw_set_span(self._ctx, (1 if on else 0) | (2 if (on and corners) else 0) | (4 if (on and diag_split) else 0), int(max_blocks)))
 
     def span_report(self):
@@ -244,7 +243,7 @@ class Engine:
         L.check(L.lib().ldw_set_overlap(self._ctx, int(bool(on))))
 
     def set_fused(self, on: bool):
-        """GEMM + MI epilogue as one kernel for every block with a bucket guess (default on); off = the two-kernel path."""
+        """Only off is accepted: the fused GEMM + MI epilogue kernel was measured slower and removed (on raises LDW_ERR_STATE)."""
         L.check(L.lib().ldw_set_fused(self._ctx, int(bool(on))))
 
     def set_mixed(self, on: bool):

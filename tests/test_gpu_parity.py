@@ -23,19 +23,6 @@ MI_TOL = 1e-6          # tolerance stated by BASELINE.json's north_star
 MI_TIGHT = 1e-10       # what the 40-bit fixed-point weights actually deliver
 
 
-EXP = None
-
-
-def _need_exp(what=""):
-    """Skip unless the loaded library is the experiments build (make EXPERIMENTS=1, LDW_AMD_LIB=.../libldweaver_amd_exp.so): the default
-    library ships without the measured-slower variants; the builder's loop runs these cases against the experiments build."""
-    global EXP
-    if EXP is None:
-        EXP = L.has_experiments()
-    if not EXP:
-        pytest.skip(f"{what or 'this variant'} is only in the LDW_EXPERIMENTS build of the library")
-
-
 def _setup(eng, d, nlimbs=0):
     eng.set_engine(L.ENGINE_MFMA)
     eng.set_alignment(d["states"])
@@ -90,10 +77,8 @@ def test_joint_counts_bit_exact(engine, sample, synth):
     assert np.array_equal(cnt[:4], synth["joint_counts"])                       # golden
 
 
-@pytest.mark.parametrize("eng_kind", [L.ENGINE_MFMA, L.ENGINE_HIST, L.ENGINE_HIST_STATES])
+@pytest.mark.parametrize("eng_kind", [L.ENGINE_MFMA, L.ENGINE_HIST])
 def test_mi_blocks_match_oracle_and_golden(engine, sample, eng_kind):
-    if eng_kind == L.ENGINE_HIST_STATES:
-        _need_exp("LDW_ENGINE_HIST_STATES")
     _setup(engine, sample)
     engine.set_engine(eng_kind)
     idx = np.arange(1268)
@@ -164,7 +149,7 @@ def test_edge_cases_ragged_and_degenerate(engine):
     hdw = rng.choice([1.0, 0.5, 1 / 3, 1 / 7, 1 / 131], Ns)
     POS = np.sort(rng.choice(5000, Ls, replace=False) + 1).astype(np.int32)
     d = dict(states=st, hdw=hdw, r=r, uqe=uqe, POS=POS, paint=np.ones(Ls, dtype=np.int32), g=5001.0)
-    for kind in (L.ENGINE_MFMA, L.ENGINE_HIST) + ((L.ENGINE_HIST_STATES,) if L.has_experiments() else ()):
+    for kind in (L.ENGINE_MFMA, L.ENGINE_HIST):
         _setup(engine, d)
         engine.set_engine(kind)
         for fi, ti in ((np.arange(Ls), np.arange(Ls)), (np.arange(0, 40), np.arange(40, 77)), (np.array([5]), np.array([6])),
@@ -242,7 +227,7 @@ def test_lr_quantile_filter_exact(engine, synth):
         assert off == len(mi)
 
 
-@pytest.mark.parametrize("variant", ["default", "plain", "limb_paths", "fused", "sort_select"])
+@pytest.mark.parametrize("variant", ["default", "plain", "limb_paths", "sort_select"])
 def test_threshold_ties_match_oracle_exactly(engine, sample, variant):
     """Ties at a block's long-range threshold (R/computePairwiseMI.R:352-358: `MI >= quantile(MI, prob)`): the reference's
     sample alignment is clonal — a third of its links sit in groups of pairs with identical joint tables, and several blocks'
@@ -250,29 +235,24 @@ def test_threshold_ties_match_oracle_exactly(engine, sample, variant):
     the emitted fp64 MI is a pure function of the slot-ordered joint table (same cell order and arithmetic in every kernel
     variant), hence the retained (a, b) set of every block equals the oracle's EXACTLY — no tolerance for threshold ties —
     on every execution path, cold and warm."""
-    if variant == "fused":
-        _need_exp("the fused GEMM + epilogue kernel")
     _setup(engine, sample)
     POS, g = sample["POS"], sample["g"]
     approx = orc.lr_links_approx(POS, g, 20000.0)
     blocks = np.array(orc.make_blocks(1268, 300), dtype=np.int32)      # 5 x 5 grid, 15 block pairs, ragged last column
-    cfg = dict(default=(True, 1, 0, False), plain=(False, 0, 1, False), limb_paths=(True, 1, 1, False), fused=(True, 1, 1, True),
-               sort_select=(True, 1, 0, False))[variant]
+    cfg = dict(default=(True, 1, 0), plain=(False, 0, 1), limb_paths=(True, 1, 1), sort_select=(True, 1, 0))[variant]
     engine.set_select(1 if variant == "sort_select" else 0)     # the general selection path (two radix sorts) against the sort-free one
     engine.set_mixed(cfg[0])
     engine.set_screen(cfg[1])
     engine.set_path(cfg[2])
-    engine.set_fused(cfg[3])
     try:
         runs = []
-        for _ in range(2):      # cold (no bucket guesses), then warm (speculative blocks: screen / approximate / fused paths)
+        for _ in range(2):      # cold (no bucket guesses), then warm (speculative blocks: screen / approximate paths)
             engine.mi_all_pairs(blocks, 20000.0, 40000.0, approx)
             runs.append((engine.links(1), engine.block_stats()))
     finally:
         engine.set_mixed(True)
         engine.set_screen(1)
         engine.set_path(0)
-        engine.set_fused(False)
         engine.set_select(0)
     tied_blocks = 0
     for (a, b, mi), st in runs:
@@ -841,57 +821,11 @@ def _same_up_to_threshold_ties(d0, d1, thr, tol):
         assert abs(d0[k] - d1[k]) < tol, (k, d0[k], d1[k])
 
 
-@pytest.mark.parametrize("nlimbs", [0, 1, 3])
-def test_fused_kernel_matches_two_kernel_path(engine, synth, nlimbs):
-    """The fused GEMM + epilogue kernel (ldw_fused.hip) against the GEMM -> G -> epilogue pair on the same blocks:
-    diagonal, square off-diagonal and ragged (non-square, Q1-scrambled) blocks, SNPs of every slot-count class.
-    The sr tables must hold the same rows in the same order, the lr tables the same rows up to ties AT the block's
-    threshold; MI may differ by rounding only (a diagonal block can meet a pair in mirrored roles)."""
-    _need_exp("the fused GEMM + epilogue kernel")
-    d = dict(synth)
-    if nlimbs == 1:
-        d["hdw"] = np.ones_like(synth["hdw"])
-    _setup(engine, d, nlimbs)
-    POS, g = synth["POS"], synth["g"]
-    approx = orc.lr_links_approx(POS, g, 20000.0)
-    blocks = np.array(orc.make_blocks(512, 150), dtype=np.int32)     # 4 x 4 grid: 150, 150, 150, 62 -> 10 block pairs
-    out = {}
-    for fused in (False, True):
-        engine.set_fused(fused)
-        c0 = engine.counters()
-        for _ in range(2):     # the second pass starts with bucket guesses: every block of it can run fused
-            engine.mi_all_pairs(blocks, 20000.0, 3000.0, approx)
-        c1 = engine.counters()
-        out[fused] = (engine.links(0), engine.links(1), engine.block_stats(), c1["fused_blocks"] - c0["fused_blocks"])
-    engine.set_fused(False)
-    assert out[False][3] == 0 and out[True][3] >= len(blocks) + len(blocks) - 2, (out[False][3], out[True][3])
-    (a0, b0, m0), (a1, b1, m1) = out[False][0], out[True][0]
-    assert len(m0) == len(m1) > 0 and np.array_equal(a0, a1) and np.array_equal(b0, b1)
-    assert np.abs(m0 - m1).max() < 1e-13
-    for k in ("n_lr_total", "n_sr"):
-        assert np.array_equal(out[False][2][k], out[True][2][k])
-    lr0, lr1 = _lr_blocks(out[False][1], out[False][2]), _lr_blocks(out[True][1], out[True][2])
-    for bi in range(len(blocks)):
-        _same_up_to_threshold_ties(lr0[bi], lr1[bi], out[True][2]["disc_thresh"][bi], 1e-13)
-    if nlimbs == 3:      # 24-bit weights: MI is only good to 1e-4, the selection near the threshold may differ from the oracle's
-        return
-    # and against the oracle, block by block (lr part)
-    for bi, (fs, fe, ts, te) in enumerate(blocks.tolist()):
-        fi, ti = np.arange(fs - 1, fe), np.arange(ts - 1, te)
-        Mb = c_oracle.mi_block(d["states"], d["hdw"], d["r"], d["uqe"], fi, ti)
-        bl = orc.block_links(Mb, fi, ti, POS, d["paint"], g, 20000.0, 3000.0, approx)
-        ref = dict(zip(zip(bl.lr["a"].tolist(), bl.lr["b"].tolist()), bl.lr["MI"].tolist()))
-        assert abs(out[True][2]["disc_thresh"][bi] - bl.disc_thresh) < MI_TIGHT
-        _same_up_to_threshold_ties(ref, lr1[bi], bl.disc_thresh, MI_TIGHT)
-
-
-@pytest.mark.parametrize("fused", [False, True])
+@pytest.mark.parametrize("fused", [False])   # (ldw_set_fused(0), what bench.py calls, is still accepted; 1 was removed)
 def test_fp32_screen_loses_nothing(engine, synth, fused):
     """The fp32 screen in front of the fp64 MI evaluation (speculative blocks) must never dismiss a pair that the exact
     value would have emitted: mode 2 evaluates every pair both ways and counts such pairs; and since every emitted MI
     is the exact one, the link tables with the screen on are bit-identical to those with the screen off."""
-    if fused:
-        _need_exp("the fused GEMM + epilogue kernel")
     syn = synth_alignment(3000, 700, seed=11)
     st = syn["states"]
     uqe, r = orc.uqe_r(st)
@@ -912,7 +846,6 @@ def test_fp32_screen_loses_nothing(engine, synth, fused):
         out[mode] = (engine.links(0), engine.links(1), c1["screen_violations"] - c0["screen_violations"],
                      c1["spec_misses"] - c0["spec_misses"])
     engine.set_screen(1)
-    engine.set_fused(False)
     assert out[2][2] == 0, f"the screen would have lost {out[2][2]} pairs"
     assert out[1][3] == 0 and out[0][3] == 0     # the second pass runs speculatively, i.e. with the screen
     for which in (0, 1):
@@ -2060,24 +1993,9 @@ def test_spans_equal_block_by_block(engine):
             # shorter spans give the same tables
             engine.set_span(True, 2)
             same(plain, run(quirk, True), (quirk, "spans of 2"))
-            if L.has_experiments():   # (the two measured-slower span variants are not in the default library: DESIGN.md 14)
-                # corner block pairs inside the spans (their short-range pairs through SR sub-passes): the same tables, short-range rows included
+            with pytest.raises(L.LdwError) as ei:   # (corner spans were measured slower and removed)
                 engine.set_span(True, 8, corners=True)
-                s2 = engine.span_report()
-                same(plain, run(quirk, True), (quirk, "spans with corner blocks, cold"))
-                same(plain, run(quirk, False), (quirk, "spans with corner blocks, warm"))
-                s3 = engine.span_report()
-                # diagonal blocks as SR sub-pass (list order) + long-range pass with rows ordered by weight (tile pruning on the lower triangle)
-                engine.set_span(True, 8, corners=False, diag_split=True)
-                same(plain, run(quirk, True), (quirk, "diagonal blocks split, cold"))
-                same(plain, run(quirk, False), (quirk, "diagonal blocks split, warm"))
-                engine.set_span(True, 8, corners=True, diag_split=True)
-                same(plain, run(quirk, True), (quirk, "corners + diagonal split"))
-                assert s3["blocks"] - s2["blocks"] >= 50, (s2, s3)    # (rows 0..5: every off-diagonal pair of the row in one span: 7 + 6 + 5 + 4 + 3 + 2, twice)
-            else:
-                with pytest.raises(L.LdwError) as ei:
-                    engine.set_span(True, 8, corners=True)
-                assert ei.value.code == L.LDW_ERR_STATE
+            assert ei.value.code == L.LDW_ERR_STATE
             engine.set_span(True, 8)
         # r04 (end): the queue assignment of long alignments — screens at the head of phase 2 on the main stream, exact band GEMM on the GEMM
         # stream, every item keeping the threshold table of its first phase — forced on this short one, through the same variants
@@ -2093,11 +2011,6 @@ def test_spans_equal_block_by_block(engine):
                 same(plain_q, run(quirk, False), (quirk, "queues swapped, spans, warm"))
                 engine.set_span(False, 8)
                 same(plain_q, run(quirk, True), (quirk, "queues swapped, no spans"))
-                if L.has_experiments():
-                    engine.set_span(True, 8, corners=True)
-                    same(plain_q, run(quirk, True), (quirk, "queues swapped, corner spans"))
-                    engine.set_span(True, 8, corners=False, diag_split=True)
-                    same(plain_q, run(quirk, True), (quirk, "queues swapped, diagonal split"))
                 engine.set_span(True, 8)
         finally:
             os.environ.pop("LDW_QUEUE_SWAP_KW")
@@ -2612,14 +2525,13 @@ def test_consumers_of_a_reused_context_equal_a_fresh_one():
 
 
 def test_default_library_refuses_experiment_variants(engine):
-    """The default library holds none of the measured-slower variants: asking for one is an error (LDW_ERR_STATE), not a silent fallback."""
-    if L.has_experiments():
-        pytest.skip("experiments build loaded")
+    """The measured-slower variants have been removed: asking for one is an error (LDW_ERR_STATE) that says so, not a silent fallback."""
+    assert not L.has_experiments()
     for call in (lambda: engine.set_fused(True), lambda: engine.set_engine(L.ENGINE_HIST_STATES), lambda: engine.set_span(True, 8, corners=True),
                  lambda: engine.set_span(True, 8, diag_split=True)):
         with pytest.raises(L.LdwError) as ei:
             call()
-        assert ei.value.code == L.LDW_ERR_STATE and "LDW_EXPERIMENTS" in str(ei.value)
+        assert ei.value.code == L.LDW_ERR_STATE and "LDW_EXPERIMENTS" in str(ei.value) and "removed" in str(ei.value)
     engine.set_fused(False)
     engine.set_engine(L.ENGINE_MFMA)
     engine.set_span(True, 8)
