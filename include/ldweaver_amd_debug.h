@@ -1,0 +1,177 @@
+/*
+ * ldweaver_amd_debug.h — diagnostics, test hooks and execution options of libldweaver_amd.so.
+ *
+ * Nothing here is needed to integrate the engine: the integration surface is ldweaver_amd.h, which this
+ * header includes.  What is declared here falls into four groups:
+ *   - counters, timings and reports of what a context did (measurement, the benchmark's roofline);
+ *   - execution options: which path, stream overlap or screen the all-pairs loop uses.  Every MI that is
+ *     emitted is computed from the exact fixed-point sums on every path, so the link tables do not depend
+ *     on any of them;
+ *   - inspection entry points that return intermediate values the reference never materialises;
+ *   - test hooks that expose the engine's bounds and kernels as functions (BOUNDS.md, tests/test_bounds.py).
+ * The same conventions hold as in ldweaver_amd.h: int status, ldw_last_error(), caller-allocated outputs.
+ * Past measurements behind these switches are recorded in DESIGN.md and docs/HISTORY.md.
+ */
+#ifndef LDWEAVER_AMD_DEBUG_H
+#define LDWEAVER_AMD_DEBUG_H
+
+#include "ldweaver_amd.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define LDW_ENGINE_MFMA 0 /* i8 MFMA fixed-point co-occurrence GEMM + fp64 epilogue (default) */
+#define LDW_ENGINE_HIST 1 /* joint histograms on bit planes: LDS-tiled class-wise popcounts (VALU), exact int64 sums, same fp64 epilogue and results */
+#define LDW_ENGINE_HIST_STATES 2 /* removed (byte-state histogram kernel, measured ~200x slower): ldw_set_engine answers LDW_ERR_STATE */
+
+/* ---- library / context -------------------------------------------------------------------------------------------------------- */
+/* build flags; always 0 (bit 0 once marked a build with the measured-slower variants, which have been removed) */
+int ldw_build_info(void);
+/* elapsed ms of the kernels of the last ldw_mi_block / ldw_mi_all_pairs call, by stage, measured with
+ * HIP events on the context's stream: [0] gemm, [1] epilogue, [2] selection, [3] total */
+int ldw_ctx_last_timing(ldw_ctx *ctx, double ms_out[4]);
+/* diagnostics since the context was created: out[0] = blocks whose speculative long-range gather had to fall back to
+ * the dense pass, out[1] = 0 (was: blocks run by the removed fused kernel), out[2] = blocks run by the two-kernel path,
+ * out[3] = pairs the fp32 screen would have lost (counted in ldw_set_screen mode 2 only; must stay 0) */
+int ldw_ctx_counters(ldw_ctx *ctx, int64_t out[4]);
+/* the same four, then out[4] = blocks run in the mixed-precision path (ldw_set_mixed), out[5] = blocks run in the
+ * approximate-GEMM path (ldw_set_path), out[6] = units its screen listed (they hold a short-range pair), out[7] = long-range candidate
+ * pairs its screen listed */
+int ldw_ctx_counters2(ldw_ctx *ctx, int64_t out[8]);
+/* Work the block-wide GEMMs of this context EXECUTED since the last reset (for the roofline: executed int8 operations /
+ * kernel time / peak): out[0] launches and out[1] int8 operations (2 x rows x rows x positions of the wave tiles that do not exit
+ * at once) of the approximate GEMM (gemm_apx_kernel), out[2] / out[3] the same for the unmasked limb GEMM (gemm_bits_kernel<J>,
+ * all J limbs), out[4] launches of the band-masked limb GEMM, out[5] launches of the approximate GEMM that applied the threshold
+ * table in their epilogue (long-range-only blocks).  reset != 0 clears the counts. */
+int ldw_gemm_stats(ldw_ctx *ctx, double out[6], int reset);
+/* diagnostics of the approximate path after ldw_set_weights: out[0] = usable (0/1), out[1] = max relative error delta of the
+ * dual-digit weights, out[2] = weight classes, out[3] = popcount segments, out[4] = exponent transitions, out[5] = e_last */
+int ldw_apx_info(ldw_ctx *ctx, double out[6]);
+
+/* ---- Hamming weights and joint tables --------------------------------------------------------------------------------------- */
+/* What the last ldw_hamming_weights of this context did, for its roofline (bench.py `roofline_hamming`): out[0] = bit columns K (one per
+ * minor state + one "not the major state" column per multi-allelic SNP: ~1.3 L), [1] = K padded to the GEMM's word pairs, [2] = ms of the
+ * kernels in front of the GEMM (column bits, bit transpose, per-sequence counts; HIP events), [3] = ms of the lower-triangular int8 GEMM,
+ * [4] = ms of the N x N neighbour count, [5] / [6] = algorithmic bytes of the kernels in front of / behind the GEMM, [7] = wall ms of the
+ * whole call on the host (allocations, state counts, column list, uploads included).  The GEMM's executed int8 operations are in
+ * ldw_gemm_stats (bits_ops). */
+int ldw_hamming_stats(ldw_ctx *ctx, double out[8]);
+/* inspection: exact weighted joint tables in fixed point and plain integer joint counts for a list of SNP pairs:
+ * counts_out[p][25] (row X of SNP a, column Y of SNP b), fixed_out[p][25] (sum of quantised weights,
+ * value = fixed * 2^-frac_bits).  Either output may be NULL. */
+int ldw_joint_tables(ldw_ctx *ctx, const int32_t *pair_a, const int32_t *pair_b, int64_t npairs,
+                     int64_t *counts_out, int64_t *fixed_out, int *frac_bits_out);
+
+/* ---- execution options of the all-pairs loop: results do not depend on them ----------------------------------------------- */
+/* LDW_ENGINE_MFMA (default) or LDW_ENGINE_HIST; LDW_ENGINE_HIST_STATES answers LDW_ERR_STATE */
+int ldw_set_engine(ldw_ctx *ctx, int engine);
+/* on (default): the co-occurrence GEMM of block b+1 runs on a second stream beside the epilogue and link selection
+ * of block b (~5 % faster end to end).  off: all kernels of all blocks run back to back on the context's stream, so
+ * that the per-stage times of ldw_ctx_last_timing are exclusive kernel times (what bench.py's roofline uses). */
+int ldw_set_overlap(ldw_ctx *ctx, int on);
+/* 0: GEMM -> G in HBM -> k_mi_screen -> k_mi_units, the only path.  1 (the fused GEMM + MI epilogue kernel: 132 against 122 ms per
+ * C4 step) has been removed and answers LDW_ERR_STATE. */
+int ldw_set_fused(ldw_ctx *ctx, int on);
+/* Mixed precision (default on; 5 weight limbs, two-kernel path, speculative blocks): the block-wide co-occurrence GEMM runs
+ * with the 3 HIGH limbs of the fixed-point weights only — all the fp32 screen needs; its margin is widened by a rigorous
+ * bound of what the low limbs can add — and the exact joint sums of the units the screen lists (3-4 % of an off-diagonal
+ * block, the short-range band of a diagonal one) get their 2 low limbs from a gathered GEMM over just those rows:
+ * sum = (high << 16) + low, the same integers as the 5-limb GEMM. */
+int ldw_set_mixed(ldw_ctx *ctx, int on);
+/* Which block-wide pass feeds the screen of the speculative blocks (every block but the first of a call sequence):
+ * 0 (default) = the approximate-GEMM path when the weights allow it — ONE int8 MFMA pass with dual-digit block-floating-
+ *     point weights (V ~ a b 2^e, rigorous relative error bound in the screen's margin), exact joint sums of the listed
+ *     units by class-wise popcounts over the weight classes (sequences of equal weight are contiguous in the bit rows),
+ *     exact re-screen, fp64 — else the limb paths; 1 = the limb paths of ldw_set_mixed only; 2 = the approximate path or
+ *     LDW_ERR_STATE at block time when the weights do not allow it (too many distinct weights, > 30k sequences). */
+int ldw_set_path(ldw_ctx *ctx, int mode);
+/* Long-range selection of the speculative blocks: 0 (default) = without a sort where it applies (radix select of the threshold,
+ * bitmap ranks over the row-order key space: ldw_mi.hip k_sel_*), 1 = always the general path (two radix sorts). */
+int ldw_set_select(ldw_ctx *ctx, int mode);
+/* fp32 screen in front of the fp64 MI evaluation, in blocks that run the speculative selection: a long-range pair
+ * only matters if its MI reaches the guessed histogram bucket, so MI is first bounded in fp32 (v_log_f32, proven
+ * error < 1.3e-5 nats, margin 2e-4) and the exact value is computed for the waves that hold a pair which may pass, or a
+ * short-range pair.  0 = off, 1 = on (default), 2 = verify: evaluate everything both ways and count lost pairs in
+ * ldw_ctx_counters[3]. */
+int ldw_set_screen(ldw_ctx *ctx, int mode);
+/* Tile pruning of the approximate path (default on; LDW_NO_PRUNE in the environment = off).  In a block pair without a short-range
+ * pair the order of the rows within a slot class is free, so the biallelic SNPs are ordered by the weight of their minor state;
+ * a 128 x 64 wave tile of the approximate GEMM whose rectangle of threshold-table bins holds only unconditional entries — no joint
+ * count can lift a pair of such marginals to the block's level; real alignments are full of near-singleton sites — is then
+ * flagged clean without being computed or screened.  The same table entries dismiss the same pairs either way; verify mode
+ * (ldw_set_screen 2) checks the pruned tiles' pairs in fp64 like every other dismissal. */
+int ldw_set_prune(ldw_ctx *ctx, int on);
+/* (test hook) a fixed capacity for the pair lists of the approximate path (0: automatic) — a list that overflows makes its block fall
+ * back like a wrong guess; process-wide. */
+int ldw_set_pair_cap(uint32_t cap);
+/* Forget what earlier passes of this context learnt about the workload — the per-kind histogram-bucket guesses of the long-range
+ * threshold, their spread history and the biallelic threshold table — without touching the alignment, the weights or any
+ * buffer.  The next ldw_mi_all_pairs then runs as the FIRST pass of a job does (the reference visits every block pair once,
+ * R/computePairwiseMI.R:103-116); bench.py calls it before every timed step.  Results never depend on this state. */
+int ldw_reset_speculation(ldw_ctx *ctx);
+
+/* ---- reports of the all-pairs loop ----------------------------------------------------------------------------------------- */
+/* Which execution path the blocks of this context took since it was created (a real data set may fail a gate silently):
+ * out[0] blocks through the approximate-GEMM path, out[1] through the mixed-precision limb path, out[2] through the plain path
+ * (5-limb GEMM + fp64 MI of every pair: blocks without a bucket guess and every block when neither fast path applies),
+ * out[3] = 0 (was: the removed fused kernel), out[4] speculation misses (blocks redone non-speculatively), out[5] blocks whose guess came from
+ * the sampled probe of the block itself (cold starts), out[6] pairs listed for exact evaluation, out[7] units listed.
+ * gate (capacity bytes, may be NULL) receives a short text: "ok" ("ok (block exponents per 32 positions)" when the weights'
+ * dynamic range needs the finer exponents) or which gate keeps the approximate path off
+ * ("delta 5.1e-03 > 4e-03", "Npad 40960 > 30720", "popcount segment tables 70000 B > 60000 B of LDS", "weights not set"). */
+int ldw_path_report(ldw_ctx *ctx, int64_t out[8], char *gate, int capacity);
+/* tile pruning (ldw_set_prune): out[0] blocks whose rows were ordered, out[1] wave tiles pruned, out[2] wave tiles of the GEMMs that
+ * could prune (both since the context was created; pruned tiles are not counted as executed work by ldw_gemm_stats), out[3] = on. */
+int ldw_prune_report(ldw_ctx *ctx, int64_t out[4]);
+/* spans (ldw_set_span): out[0] spans run, out[1] reference blocks they covered, out[2] segments redone on their own after a wrong guess,
+ * out[3] on. */
+int ldw_span_report(ldw_ctx *ctx, int64_t out[4]);
+/* List overflows.  The default path lists its candidates in fixed-capacity device lists; a list that overflows makes its block (or
+ * its segment of a span) be redone on the plain path (counted in spec_misses like a wrong bucket guess), so results never depend on a
+ * capacity.  out[0] blocks / segments redone because a PAIR list overflowed, out[1] because the MAYBE list of the approximate GEMM's
+ * epilogue did (sized for the worst case: non-zero only under the test override LDW_MAYBE_CAP), out[2] = 1 while the maybe list
+ * is switched off for the rest of the pass after such an overflow (ldw_reset_speculation switches it on again), out[3] entries handed to the
+ * maybe list since the context was created. */
+int ldw_overflow_report(ldw_ctx *ctx, int64_t out[4]);
+
+/* ---- inspection and test hooks (BOUNDS.md; tests/test_bounds.py brute-forces every bound of the default path through them;
+ *      ldweaver_amd/csrc/ldw_debug.hip) ------------------------------------------------------------------------------------------- */
+/* the per-SNP bounds behind the pruning of the 2 x 3 / 3 x 3 tables.  out[a * 4 + 2 * m + (k - 2)] = the largest MI
+ * SNP a (2 or 3 states, all flagged in uqe, r = its number of states) can reach with ANY partner that has k = 2 or 3 flagged states
+ * and r = k — the maximum of the MI over the joint tables with a's marginals, which is convex there and sits at a vertex: every
+ * state of a sends all its weight to one state of the partner — under the intended (m = 0) and the reference (m = 1: RXY at its
+ * floor min(r)^2 / 4) reading of RXY; 1e300 for other SNPs and for SNPs with a sizeable minor state (not evaluated).  Needs the
+ * alignment, the weights and the SNP meta data; capacity in doubles (>= 4 L). */
+int ldw_snp_bounds(ldw_ctx *ctx, double *out, int64_t capacity);
+/* out[0] = pairs that verify mode (ldw_set_screen 2) counted as "the screen would have lost this one" since the last call, out[1 + 4 k ..]
+ * = (from SNP, to SNP, exact MI, level) of the first 16 of them.  65 doubles. */
+int ldw_debug_violations(ldw_ctx *ctx, double *out);
+/* the threshold table of the biallelic pairs (k_build_tab11) for a total weight W, an MI level lo, the approximate sums' relative
+ * error delta, their absolute slack eta and the unit sprime of the int32 sums: out[64 * 64 * 2] = (Lq, Hq) of entry [bin of the to side][bin of the
+ * from side], bin = min(63, floor(sqrtf(p) * cbin)); a sum n' with Lq < n' < Hq is dismissed.  tests/test_gpu_parity.py checks the table against
+ * the MI formula on a grid of joint tables. */
+int ldw_debug_tab11(ldw_ctx *ctx, double W, double lo, double delta, double eta, double sprime, int32_t *out, double *cbin_out);
+/* ldw_debug_apx_params: the constants the approximate screen's bound is built from for the CURRENT weights, as the engine derives them:
+ *   out[0] F (fraction bits of the fixed-point weights), [1] e_last, [2] delta = max |V'/V - 1|, [3] lost units of a GEMM entry, [4] sum of the fixed-point weights,
+ *   [5] neff, [6] apx_EG, [7] apx_dfac, [8] apx_s1, [9] apx_c1, [10] apx_W, [11] apx_unit = 2^(e_last - F), [12] scr_scale of the approximate screen,
+ *   [13] scr_shift and [14] scr_scale of the exact-limb screen, [15] bit 0: the path is usable, bit 1: block exponents per 32 positions,
+ *   [16] lo_abs_sum = sum |V_lo| 2^-F and [17] lo_bound, the margin the mixed-precision screen adds for the two low limbs, [18] apx_MU (units a floor marginal can be low: 1, or 0 at e_last = 0), [19] limbs;
+ *   vfixed_out / vapx_out (may be NULL; capacity >= N): the exact fixed-point weight V_s and its dual-digit approximation V'_s = a b 2^e of every SEQUENCE.
+ * ldw_debug_rows: row0_out[L + 1] = first indicator row of every SNP, slot_meta_out[L] = rows (3 bits) | uqe flag of slot i << (3 + i) | state of slot i << (8 + 3 i).
+ * ldw_debug_apx_gemm: gemm_apx_kernel over the given indicator rows (indices 0..R; R = the all-zero padding row): out[nrt][nrf] = the int32 sums G' in units of 2^e_last.
+ * ldw_debug_screen_bound: the engine's own device functions on n caller-made joint tables (arrays by case: g[16] = sums of the indicator rows, g[j * 4 + i] = slot i of the
+ *   from-side SNP x slot j of the to-side SNP; pa / pb[5] integer marginals by slot; pX / pY[5] weighted marginals; rr[3] = r_a, r_b, RXY; masks[2] = slot meta of both SNPs,
+ *   kinds 1 / 3 only; params = the 20 numbers of ldw_debug_apx_params, which the caller may alter).  kind 0: full_cells_screen<na, nb, APX> — the approximate path's upper
+ *   bound of MI; 1: pair_screen_generic<APX>; 2: full_cells_screen<na, nb> on exact sums (an fp32 MI); 3: pair_screen_generic on exact sums; 4: full_cells_mi<na, nb>, the
+ *   fp64 value the engine emits (out64).  na, nb in {1, 2} for kinds 0 / 2 / 4. */
+int ldw_debug_apx_params(ldw_ctx *ctx, double out[20], int64_t *vfixed_out, int64_t *vapx_out, int64_t capacity);
+int ldw_debug_rows(ldw_ctx *ctx, int32_t *row0_out, uint32_t *slot_meta_out, int64_t capacity);
+int ldw_debug_apx_gemm(ldw_ctx *ctx, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int32_t *out);
+int ldw_debug_screen_bound(ldw_ctx *ctx, int kind, int na, int nb, int64_t n, const int64_t *g, const int64_t *pa, const int64_t *pb, const float *pX, const float *pY,
+                           const double *rr, const uint32_t *masks, const double params[20], float *out, double *out64);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* LDWEAVER_AMD_DEBUG_H */

@@ -1,4 +1,4 @@
-"""ctypes binding of libldweaver_amd.so (the C ABI declared in include/ldweaver_amd.h).
+"""ctypes binding of libldweaver_amd.so (the C ABI declared in include/ldweaver_amd.h and include/ldweaver_amd_debug.h).
 
 There is NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  Nothing in this package computes MI, Hamming weights or
@@ -37,58 +37,49 @@ _lib = None
 
 _p = C.c_void_p
 _i64 = C.c_int64
-_SIGS = {
+# include/ldweaver_amd.h: the integration surface
+_SIGS_API = {
     "ldw_version": (C.c_int, []),
     "ldw_last_error": (C.c_char_p, []),
     "ldw_device_count": (C.c_int, []),
     "ldw_ctx_create": (C.c_int, [C.c_int, C.POINTER(_p)]),
     "ldw_ctx_destroy": (C.c_int, [_p]),
+    "ldw_ctx_reserve": (C.c_int, [_p, C.c_int64, C.c_int64, C.c_int64]),
     "ldw_ctx_set_stream": (C.c_int, [_p, _p]),
     "ldw_ctx_sync": (C.c_int, [_p]),
-    "ldw_ctx_last_timing": (C.c_int, [_p, _p]),
-    "ldw_ctx_counters": (C.c_int, [_p, _p]),
+    "ldw_host_trim": (C.c_int, [_p, C.POINTER(_i64)]),
     "ldw_acgtn2num": (C.c_int, [_p, _p, _p, _i64, C.c_int]),
     "ldw_acgtn2num_dev": (C.c_int, [_p, _p, _p, _i64]),
     "ldw_fast_hadamard": (C.c_int, [_p] + [_p] * 8 + [_i64, C.c_int]),
     "ldw_set_alignment": (C.c_int, [_p, _p, _i64, _i64, C.c_int]),
     "ldw_encode_alignment": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p]),
     "ldw_alignment_scan": (C.c_int, [_p, _p, _i64, _i64, _p]),
-    "ldw_state_counts": (C.c_int, [_p, _p]),
     "ldw_fasta_probe": (C.c_int, [C.c_char_p, _i64, C.POINTER(_i64), C.POINTER(_i64), C.c_char_p, _i64, C.POINTER(_i64)]),
     "ldw_fasta_scan": (C.c_int, [_p, C.c_char_p, _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "ldw_fasta_counts": (C.c_int, [_p, _p]),
     "ldw_fasta_names": (C.c_int, [_p, C.c_char_p, _i64, C.POINTER(_i64)]),
     "ldw_fasta_encode": (C.c_int, [_p, _p, _i64, _p]),
+    "ldw_state_counts": (C.c_int, [_p, _p]),
     "ldw_get_alignment": (C.c_int, [_p, _p]),
     "ldw_hamming_weights": (C.c_int, [_p, C.c_int32, _p, _p]),
     "ldw_hamming_counts": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, _p]),
-    "ldw_hamming_stats": (C.c_int, [_p, _p]),
+    "ldw_hamming_weights_multi": (C.c_int, [_p, C.c_int, C.c_int32, _p]),
     "ldw_set_weights": (C.c_int, [_p, _p, _i64, C.c_int]),
     "ldw_set_snp_meta": (C.c_int, [_p, _p, _p, _p, _p, C.c_double]),
-    "ldw_set_engine": (C.c_int, [_p, C.c_int]),
     "ldw_mi_block": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_int, _p, C.c_int]),
-    "ldw_joint_tables": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p]),
     "ldw_mi_all_pairs": (C.c_int, [_p, _p, _i64, C.POINTER(MIParams), C.c_int]),
-    "ldw_build_info": (C.c_int, []),
     "ldw_mi_all_pairs_multi": (C.c_int, [_p, C.c_int, _p, _i64, C.POINTER(MIParams), _p, _p]),
     "ldw_deal_blocks": (C.c_int, [_p, _i64, C.c_int, _p]),
-    "ldw_hamming_weights_multi": (C.c_int, [_p, C.c_int, C.c_int32, _p]),
+    "ldw_set_span": (C.c_int, [_p, C.c_int, C.c_int]),
     "ldw_links_begin": (C.c_int, [_p, _i64]),
     "ldw_mi_block_links": (C.c_int, [_p, _p, _i64, _p, _i64, C.POINTER(MIParams)]),
     "ldw_links_end": (C.c_int, [_p]),
-    "ldw_set_overlap": (C.c_int, [_p, C.c_int]),
-    "ldw_set_fused": (C.c_int, [_p, C.c_int]),
-    "ldw_set_mixed": (C.c_int, [_p, C.c_int]),
-    "ldw_ctx_counters2": (C.c_int, [_p, _p]),
-    "ldw_set_screen": (C.c_int, [_p, C.c_int]),
-    "ldw_set_path": (C.c_int, [_p, C.c_int]),
-    "ldw_set_select": (C.c_int, [_p, C.c_int]),
-    "ldw_links_device_ptrs": (C.c_int, [_p, C.c_int, _p, _p, _p, _p]),
-    "ldw_apx_info": (C.c_int, [_p, _p]),
     "ldw_links_count": (C.c_int, [_p, C.c_int, C.POINTER(_i64)]),
     "ldw_links_fetch": (C.c_int, [_p, C.c_int, _p, _p, _p, _i64, C.c_int]),
-    "ldw_block_stats": (C.c_int, [_p, _i64, _p, _p, _p, _p]),
+    "ldw_links_device_ptrs": (C.c_int, [_p, C.c_int, _p, _p, _p, _p]),
     "ldw_links_import": (C.c_int, [_p, C.c_int, _p, _p, _p, _i64, C.c_int]),
+    "ldw_block_stats": (C.c_int, [_p, _i64, _p, _p, _p, _p]),
+    "ldw_sr_pairs_fill": (C.c_int, [_p, _p, C.c_int64, C.c_double, _p, _p, C.c_int64, _p]),
     "ldw_aracne": (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _p, _i64, _p]),
     "ldw_sr_len_quantiles": (C.c_int, [_p, C.c_int, C.c_double, C.c_double, C.c_int32, _p, _p, _p]),
     "ldw_sr_excess_stats": (C.c_int, [_p, C.c_int, C.c_int32, _p, _p]),
@@ -104,27 +95,9 @@ _SIGS = {
     "ldw_sr_len_quantiles_multi": (C.c_int, [_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int32, _p, _p, _p]),
     "ldw_sr_excess_stats_multi": (C.c_int, [_p, C.c_int, C.c_int, C.c_int32, _p, _p]),
     "ldw_sr_pvalues_multi": (C.c_int, [_p, C.c_int, C.c_int, C.c_int32, _p, _p, C.c_double, _p, _p, _p]),
-    "ldw_gemm_stats": (C.c_int, [_p, _p, C.c_int]),
     "ldw_lr_tukey": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "ldw_lr_reduced_fetch": (C.c_int, [_p, _i64, _p, _p, _p, _p]),
     "ldw_ldmap": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, _p, _p, _p, _p, _i64]),
-    "ldw_reset_speculation": (C.c_int, [_p]),
-    "ldw_path_report": (C.c_int, [_p, _p, C.c_char_p, C.c_int]),
-    "ldw_set_prune": (C.c_int, [_p, C.c_int]),
-    "ldw_prune_report": (C.c_int, [_p, _p]),
-    "ldw_ctx_reserve": (C.c_int, [_p, C.c_int64, C.c_int64, C.c_int64]),
-    "ldw_sr_pairs_fill": (C.c_int, [_p, _p, C.c_int64, C.c_double, _p, _p, C.c_int64, _p]),
-    "ldw_set_span": (C.c_int, [_p, C.c_int, C.c_int]),
-    "ldw_span_report": (C.c_int, [_p, _p]),
-    "ldw_overflow_report": (C.c_int, [_p, _p]),
-    "ldw_set_pair_cap": (C.c_int, [C.c_uint32]),
-    "ldw_snp_bounds": (C.c_int, [_p, _p, C.c_int64]),
-    "ldw_debug_violations": (C.c_int, [_p, _p]),
-    "ldw_debug_tab11": (C.c_int, [_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
-    "ldw_debug_apx_params": (C.c_int, [_p, _p, _p, _p, _i64]),
-    "ldw_debug_rows": (C.c_int, [_p, _p, _p, _i64]),
-    "ldw_debug_apx_gemm": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p]),
-    "ldw_debug_screen_bound": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ldw_format_number": (C.c_int, [C.c_double, C.c_char_p, C.c_int]),
     "ldw_r_sample": (C.c_int, [C.c_uint32, C.c_int64, C.c_int64, _p]),
     "ldw_write_table_tsv": (C.c_int, [C.c_char_p, C.c_int, _i64, C.c_int, _p, _p, C.c_int, C.POINTER(_i64)]),
@@ -132,7 +105,6 @@ _SIGS = {
     "ldw_write_links_tsv_begin": (C.c_int, [_p, C.c_int, C.c_char_p, C.c_int, C.c_int]),
     "ldw_write_links_tsv_end": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
     "ldw_tsv_join": (C.c_int, [_p]),
-    "ldw_host_trim": (C.c_int, [_p, C.POINTER(_i64)]),
     "ldw_lr_stream_begin": (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int]),
     "ldw_lr_stream_end": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "ldw_compare_to_row": (C.c_int, [_p, _i64, _i64, _p, _i64, _p]),
@@ -140,10 +112,45 @@ _SIGS = {
     "ldw_compare_triplet": (C.c_int, [_p, _p, _i64, C.c_double, C.POINTER(C.c_int)]),
     "ldw_fast_intersect": (C.c_int, [_p, _i64, _p, _i64, _p, C.POINTER(_i64)]),
 }
+# include/ldweaver_amd_debug.h: diagnostics, test hooks and execution options that change no result
+_SIGS_DEBUG = {
+    "ldw_build_info": (C.c_int, []),
+    "ldw_ctx_last_timing": (C.c_int, [_p, _p]),
+    "ldw_ctx_counters": (C.c_int, [_p, _p]),
+    "ldw_ctx_counters2": (C.c_int, [_p, _p]),
+    "ldw_gemm_stats": (C.c_int, [_p, _p, C.c_int]),
+    "ldw_apx_info": (C.c_int, [_p, _p]),
+    "ldw_hamming_stats": (C.c_int, [_p, _p]),
+    "ldw_joint_tables": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p]),
+    "ldw_set_engine": (C.c_int, [_p, C.c_int]),
+    "ldw_set_overlap": (C.c_int, [_p, C.c_int]),
+    "ldw_set_fused": (C.c_int, [_p, C.c_int]),
+    "ldw_set_mixed": (C.c_int, [_p, C.c_int]),
+    "ldw_set_path": (C.c_int, [_p, C.c_int]),
+    "ldw_set_select": (C.c_int, [_p, C.c_int]),
+    "ldw_set_screen": (C.c_int, [_p, C.c_int]),
+    "ldw_set_prune": (C.c_int, [_p, C.c_int]),
+    "ldw_set_pair_cap": (C.c_int, [C.c_uint32]),
+    "ldw_reset_speculation": (C.c_int, [_p]),
+    "ldw_path_report": (C.c_int, [_p, _p, C.c_char_p, C.c_int]),
+    "ldw_prune_report": (C.c_int, [_p, _p]),
+    "ldw_span_report": (C.c_int, [_p, _p]),
+    "ldw_overflow_report": (C.c_int, [_p, _p]),
+    "ldw_snp_bounds": (C.c_int, [_p, _p, C.c_int64]),
+    "ldw_debug_violations": (C.c_int, [_p, _p]),
+    "ldw_debug_tab11": (C.c_int, [_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
+    "ldw_debug_apx_params": (C.c_int, [_p, _p, _p, _p, _i64]),
+    "ldw_debug_rows": (C.c_int, [_p, _p, _p, _i64]),
+    "ldw_debug_apx_gemm": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p]),
+    "ldw_debug_screen_bound": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+}
+_SIGS = {**_SIGS_API, **_SIGS_DEBUG}
+_SIGS_BY_HEADER = {"ldweaver_amd.h": _SIGS_API, "ldweaver_amd_debug.h": _SIGS_DEBUG}
 
 
-def declared_symbols():
-    return sorted(_SIGS)
+def declared_symbols(header: str | None = None):
+    """Names of the bound functions: all of them, or those of one header under include/ ("ldweaver_amd.h" or "ldweaver_amd_debug.h")."""
+    return sorted(_SIGS if header is None else _SIGS_BY_HEADER[header])
 
 
 def lib():

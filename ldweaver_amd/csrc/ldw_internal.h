@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ldweaver_amd.h"
+#include "../../include/ldweaver_amd_debug.h"
 
 // Pipeline slots of the all-pairs loop: the block-wide kernels (GEMM stream) may run LDW_NSLOT - 1 blocks ahead of the block whose
 // lists the main stream is evaluating; every per-block buffer exists once per slot (block b uses slot b % LDW_NSLOT).

@@ -42,7 +42,11 @@ class Engine:
     def close(self, trim: bool = False):
         """Destroy the context.  Its large device blocks go to the process-wide free list for the next engine (capped; trimmed to LDW_DEVPOOL_IDLE_GB when the
         process's last context goes); trim=True gives everything back to the runtime at once — for a process that shares the GPU with other allocators
-        (torch, RCCL buffers, other ranks on the same device)."""
+        (torch, RCCL buffers, other ranks on the same device).
+
+        Device views this engine handed out (``links_view``, ``sr_tail_extract(on_device=True)``) stay valid only until the context is
+        destroyed, and destroying it waits for the engine's own streams only: synchronise every stream that reads them (a torch or RCCL
+        stream) before calling close()."""
         if self._ctx:
             L.lib().ldw_ctx_destroy(self._ctx)
             self._ctx = C.c_void_p()

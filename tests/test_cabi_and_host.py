@@ -1,4 +1,4 @@
-"""CPU: the C-ABI library loads and exports what include/ldweaver_amd.h declares; host logic (blocks, RNG-driven
+"""CPU: the C-ABI library loads and exports what include/ldweaver_amd.h and include/ldweaver_amd_debug.h declare; host logic (blocks, RNG-driven
 lr_links_approx, srp model, ARACNE and the small native helpers) against the oracle.  No GPU compute calls."""
 import ctypes as C
 import os
@@ -19,17 +19,53 @@ from ldweaver_amd.snpdat import SnpDat, encode_chars
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_exports_every_declared_symbol():
-    hdr = open(os.path.join(ROOT, "include", "ldweaver_amd.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+HEADERS = ("ldweaver_amd.h", "ldweaver_amd_debug.h")     # the integration surface; diagnostics, test hooks and execution options
+
+
+def _header_functions(name):
+    """Names of the functions include/<name> declares (comments stripped)."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
     declared = set(re.findall(r"\b(ldw_[a-z0-9_]+)\s*\(", hdr))
     declared.discard("ldw_ctx")
-    assert len(declared) >= 30
+    return declared
+
+
+def test_headers_declare_exactly_what_the_library_exports():
+    """Both headers together declare the library's C ABI, each function in exactly one of them: each header's set is its _lib table,
+    every declared name is exported, and every unmangled ldw_* function the default library exports is declared."""
+    api, debug = (_header_functions(h) for h in HEADERS)
+    assert len(api) >= 30 and len(debug) >= 20
+    assert not api & debug, sorted(api & debug)
+    assert api == set(L.declared_symbols("ldweaver_amd.h")), api ^ set(L.declared_symbols("ldweaver_amd.h"))
+    assert debug == set(L.declared_symbols("ldweaver_amd_debug.h")), debug ^ set(L.declared_symbols("ldweaver_amd_debug.h"))
+    declared = api | debug
     lib = L.lib()
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
     assert declared == set(L.declared_symbols()), declared ^ set(L.declared_symbols())
     assert lib.ldw_version() >= 100
+    if os.environ.get("LDW_AMD_LIB"):
+        return      # (another build: its measurement-only exports are not declared)
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {f[2] for f in (ln.split() for ln in out.splitlines()) if len(f) == 3 and f[1] == "T" and f[2].startswith("ldw_")}
+    assert exported == declared, sorted(exported ^ declared)
+
+
+def test_each_header_compiles_on_its_own(tmp_path):
+    """Each public header is self-contained: a translation unit that includes it and nothing else compiles as C11 and C++17 with every
+    warning an error."""
+    import shutil
+    import subprocess
+    if shutil.which("gcc") is None or shutil.which("g++") is None:
+        pytest.skip("no gcc / g++")
+    for h in HEADERS:
+        for comp, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
+            src = tmp_path / f"only_{h.replace('.', '_')}.{ext}"
+            src.write_text(f'#include "{h}"\n')
+            r = subprocess.run([comp, std, "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), str(src)],
+                               capture_output=True, text=True)
+            assert r.returncode == 0, (h, comp, r.stderr[-3000:])
 
 
 def test_default_library_is_lean():
@@ -301,8 +337,8 @@ def test_r_shim_is_consistent_with_itself_and_the_header():
     """The R shim cannot be compiled here (no R headers in the image), so it is checked statically: every `.Call("ldwamd_*", ...)` of
     r_shim/ldweaver_amd.R names a routine registered in the shim's R_CallMethodDef table with the number of arguments the call passes; every
     registered routine is defined with that many SEXP parameters; every `ldw_*` function the shim calls is declared in include/ldweaver_amd.h
-    and called with the declared number of arguments; the reference's own six `.Call` symbols are registered with the reference's arities
-    (src/RcppExports.cpp:154-160)."""
+    (the integration header alone: a call into include/ldweaver_amd_debug.h fails) and called with the declared number of arguments; the
+    reference's own six `.Call` symbols are registered with the reference's arities (src/RcppExports.cpp:154-160)."""
     c_src = open(os.path.join(ROOT, "r_shim", "ldweaver_amd_shim.c")).read()
     r_src = open(os.path.join(ROOT, "r_shim", "ldweaver_amd.R")).read()
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ldweaver_amd.h")).read(), flags=re.S)
