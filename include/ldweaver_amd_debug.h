@@ -121,6 +121,13 @@ int ldw_reset_speculation(ldw_ctx *ctx);
  * dynamic range needs the finer exponents) or which gate keeps the approximate path off
  * ("delta 5.1e-03 > 4e-03", "Npad 40960 > 30720", "popcount segment tables 70000 B > 60000 B of LDS", "weights not set"). */
 int ldw_path_report(ldw_ctx *ctx, int64_t out[8], char *gate, int capacity);
+/* Kernel launches by form since the context was created, so that a test can tell which form of a size-dependent stage ran (results do not
+ * depend on the form): the exact pair sums of the approximate path's listed pairs, two launches per block, out[0] walking the set bits against
+ * a per-position weight table within the default 64 KB of LDS (k_pair_sums_bits), out[1] the same with the 160-KB dynamic-LDS attribute
+ * (more than 8 192 padded sequences), out[2] class-wise popcounts with the segment tables in LDS (k_pair_sums), out[3] the same with the tables
+ * in global memory (many weight classes beyond the bit walk's 160 KB, or LDW_NO_PAIR_BITS set); out[4] launches of the bit-row fill that
+ * reads the states from global memory instead of staging a row in LDS (more than 61 440 padded sequences). */
+int ldw_pair_form_report(ldw_ctx *ctx, int64_t out[5]);
 /* tile pruning (ldw_set_prune): out[0] blocks whose rows were ordered, out[1] wave tiles pruned, out[2] wave tiles of the GEMMs that
  * could prune (both since the context was created; pruned tiles are not counted as executed work by ldw_gemm_stats), out[3] = on. */
 int ldw_prune_report(ldw_ctx *ctx, int64_t out[4]);

@@ -735,6 +735,12 @@ int ldw_path_report(ldw_ctx *c, int64_t out[8], char *gate, int capacity) {
     return LDW_OK;
 }
 
+int ldw_pair_form_report(ldw_ctx *c, int64_t out[5]) {
+    LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_pair_form_report: null argument");
+    for (int i = 0; i < 5; ++i) out[i] = c->form_launches[i];
+    return LDW_OK;
+}
+
 int ldw_set_prune(ldw_ctx *c, int on) {
     LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
     c->prune = on != 0;

@@ -247,6 +247,7 @@ int fill_rows_bits(ldw_ctx *c, const int32_t *d_rowinfo, int64_t R) {
     const int use_lds = c->Npad <= 61440 ? 1 : 0;   // the default dynamic-LDS limit is 64 KB
     hipLaunchKernelGGL(k_fill_rows_bits, dim3((unsigned)R), dim3(256), use_lds ? (size_t)c->Npad : 0, c->stream, c->states.as<uint8_t>(), c->Npad,
                        d_rowinfo, c->KW, c->seq_perm.as<int32_t>(), use_lds, c->Mbits.as<uint64_t>());
+    if (!use_lds) ++c->form_launches[4];
     LDW_HIP(hipGetLastError());
     return LDW_OK;
 }

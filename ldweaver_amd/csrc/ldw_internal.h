@@ -132,6 +132,9 @@ struct ldw_ctx {
     ldw::DevBuf apx_mini[LDW_NSLOT];           // per slot: the 32-byte per-SNP extracts k_screen_maybe reads (MiniCol [nt], MiniRow [64 * from-tiles])
     ldw::DevBuf apx_units[LDW_NSLOT], apx_packs[LDW_NSLOT];   // per slot: per-(tile, class) unit lists + counters; per-block SNP constants
     int64_t apx_blocks = 0, apx_units_listed = 0, apx_pairs_listed = 0, probe_blocks = 0, generic_blocks = 0;
+    // launches by form (ldw_pair_form_report): [0] k_pair_sums_bits within the default 64 KB of LDS, [1] k_pair_sums_bits with the 160-KB attribute,
+    // [2] k_pair_sums with its segment tables in LDS, [3] k_pair_sums with them in global memory, [4] k_fill_rows_bits in its global-memory form
+    int64_t form_launches[5] = {0, 0, 0, 0, 0};
     // Tile pruning (docs/HISTORY.md 5.1d): in blocks without a short-range pair the one-row SNPs are ordered by the weight of their minor
     // state, so that a wave tile of the approximate GEMM spans few bins of the threshold table; a tile whose whole bin rectangle is
     // unconditionally below the level (no joint count can lift such a pair to it) is flagged clean without being computed.

@@ -110,6 +110,13 @@ class Engine:
         return dict(apx_blocks=int(v[0]), mixed_blocks=int(v[1]), plain_blocks=int(v[2]), fused_blocks=int(v[3]), spec_misses=int(v[4]),
                     probe_blocks=int(v[5]), pairs_listed=int(v[6]), units_listed=int(v[7]), apx_gate=buf.value.decode())
 
+    def form_report(self):
+        """Kernel launches by form since the context was created (ldw_pair_form_report): the exact pair sums of the listed pairs walking set bits
+        within 64 KB of LDS / with the 160-KB attribute, class-wise with LDS / global segment tables, and bit-row fills from global memory."""
+        v = np.zeros(5, dtype=np.int64)
+        L.check(L.lib().ldw_pair_form_report(self._ctx, L.ptr(v)))
+        return dict(bits_lds64=int(v[0]), bits_lds160=int(v[1]), classwise_lds=int(v[2]), classwise_global=int(v[3]), fill_rows_global=int(v[4]))
+
     def set_prune(self, on: bool):
         """Tile pruning of the approximate path (default on): rows ordered by minor-state weight, rare x rare tiles never computed."""
         L.check(L.lib().ldw_set_prune(self._ctx, int(bool(on))))

@@ -136,12 +136,15 @@ def _pack(n, ka, kb, G, mrg_a, mrg_b, pXf, pYf):
 
 
 WEIGHTINGS = [("hamming", 2000, 11), ("few", 600, 12), ("distinct", 616, 13), ("wide", 400, 14), ("unit", 300, 15)]
+# the approximate path accepts up to Npad 30 720, and the bounds' constants depend on N (apx_s1 grows with log(den + 12.5), ldw_epi.h): large N,
+# on both sides of the pair-sum forms' switch at Npad 20 480 and at the path's own gate (fewer random tables per shape: the numpy sums are O(n N))
+WEIGHTINGS_LARGE = [("distinct", 20481, 16), ("distinct", 30720, 17), ("wide", 30720, 18)]
 
 
 # ------------------------------------------------------------------------------------------------
 # BOUNDS.md 1-2: dual-digit weights and the truncation of the approximate GEMM
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind,N,seed", WEIGHTINGS)
+@pytest.mark.parametrize("kind,N,seed", WEIGHTINGS + WEIGHTINGS_LARGE)
 def test_dual_digit_weights_and_gemm_truncation_are_inside_their_bounds(engine, kind, N, seed):
     """(1) |V'_s / V_s - 1| <= delta for every sequence; (2) every entry of gemm_apx_kernel's output lies in (S' / 2^e_last - lost_units, S' / 2^e_last],
     S' = the exact integer sum of the dual-digit weights over the co-occurring sequences (R/computePairwiseMI.R:391's sum with V' for V) — for all rows
@@ -201,7 +204,7 @@ def _apx_inputs(rng, a, b, ka, kb, V, Va, P, adversarial_loss):
     return Sx, scale, _pack(n, ka, kb, G, mrg_a, mrg_b, pXf, pYf)
 
 
-@pytest.mark.parametrize("kind,N,seed", WEIGHTINGS)
+@pytest.mark.parametrize("kind,N,seed", WEIGHTINGS + WEIGHTINGS_LARGE)
 def test_approximate_screen_bound_is_an_upper_bound_of_the_exact_mi(engine, kind, N, seed):
     """full_cells_screen<NA, NB, APX> (the four straight-line variants of k_mi_screen / k_screen_maybe) and pair_screen_generic<APX> (k_mi_screen_generic):
     for joint tables built from the engine's own V and V', GEMM entries anywhere in their truncation interval and floor marginals, the fp32 value the
@@ -211,7 +214,7 @@ def test_approximate_screen_bound_is_an_upper_bound_of_the_exact_mi(engine, kind
     P = dict(zip(Engine.APX_PARAM_NAMES, par))
     assert int(P["flags"]) & 1
     rng = np.random.default_rng(seed + 100)
-    n = 4000
+    n = 4000 if N <= 2000 else 600
     worst, slack = 0.0, []
     for (ka, kb), adv in itertools.product([(2, 2), (2, 3), (3, 2), (3, 3)], [False, True]):
         a, b = _random_state_pairs(rng, n, N, ka, kb)
@@ -226,7 +229,7 @@ def test_approximate_screen_bound_is_an_upper_bound_of_the_exact_mi(engine, kind
         slack.append(float(np.median(gap)))
     # the predicated screen: 0..4 indicator rows per side, unflagged slots (cells masked by uq = uqX (x) uqY), r free
     for (ka, kb), adv in itertools.product([(1, 2), (2, 4), (4, 3), (5, 5), (3, 1), (4, 4)], [False, True]):
-        m = 2500
+        m = 2500 if N <= 2000 else 400
         a, b = _random_state_pairs(rng, m, N, ka, kb)
         Sx, scale, (g, pa, pb, pX, pY) = _apx_inputs(rng, a, b, ka, kb, V, Va, P, adv)
         ra, rb, rxy = _r_and_rxy(rng, m, ka, kb)

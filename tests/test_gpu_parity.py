@@ -2251,8 +2251,9 @@ def test_gates_of_the_approximate_path_fall_back_to_the_limb_paths(engine, case)
     """the gates of the approximate path that no test reached (prepare_apx_weights, ldw_apx.hip).  (i) more than
     30 720 padded sequences — the two digit arrays no longer fit the GEMM's LDS beside its tables: N = 30 848: ldw_path_report names the
     gate, the blocks run the limb paths (mixed precision: 3 high limbs + gathered low limbs) with the screen.  (ii) r03's third gate —
-    so many weight classes that the popcount segment tables of k_pair_sums exceed 60 000 bytes of LDS: 4000 DISTINCT weights — is GONE
-    (r04: the kernel reads such tables from global memory): the approximate path runs.  Either way the link tables equal the plain
+    so many weight classes that the popcount segment tables of k_pair_sums exceed 60 000 bytes of LDS: 4000 DISTINCT weights — is GONE:
+    the approximate path runs, and its pair sums walk the set bits against a per-position weight table in 32 KB of LDS (k_pair_sums_bits;
+    the class-wise form with global tables is reached above Npad 20 480 or with LDW_NO_PAIR_BITS: tests/test_sequence_count_edges.py).  Either way the link tables equal the plain
     path's bit for bit.  (The remaining fallback — a pair list that overflows — is forced in test_spans_equal_block_by_block with
     ldw_set_pair_cap.)"""
     if case == "npad_gate":
@@ -2288,11 +2289,11 @@ def test_gates_of_the_approximate_path_fall_back_to_the_limb_paths(engine, case)
             engine.set_path(path)
             if key != "verify":
                 engine.reset_speculation()
-            c0 = engine.counters()
+            c0, f0 = engine.counters(), engine.form_report()
             for _ in range(2):
                 engine.mi_all_pairs(blocks, 20000.0, lr_retain, approx)
-            c1 = engine.counters()
-            out[key] = (engine.links(0), engine.links(1), engine.block_stats(), {k: c1[k] - c0[k] for k in c1})
+            c1, f1 = engine.counters(), engine.form_report()
+            out[key] = (engine.links(0), engine.links(1), engine.block_stats(), {k: c1[k] - c0[k] for k in c1}, {k: f1[k] - f0[k] for k in f1})
     finally:
         engine.set_mixed(True)
         engine.set_screen(1)
@@ -2301,7 +2302,9 @@ def test_gates_of_the_approximate_path_fall_back_to_the_limb_paths(engine, case)
     if case == "npad_gate":
         assert d["apx_blocks"] == 0 and d["mixed_blocks"] >= len(blocks), d     # the gate sent every speculative block to the limb paths
     else:
-        assert d["apx_blocks"] >= len(blocks) and d["apx_pairs_listed"] > 0, d   # ... and here the approximate path ran, its pair sums from global tables
+        assert d["apx_blocks"] >= len(blocks) and d["apx_pairs_listed"] > 0, d   # ... and here the approximate path ran, its pair sums by the bit walk
+        f = out["default"][4]
+        assert f["bits_lds64"] > 0 and f["bits_lds160"] == f["classwise_lds"] == f["classwise_global"] == 0, f
     assert out["verify"][3]["screen_violations"] == 0
     for key in ("default", "verify"):
         for which in (0, 1):
