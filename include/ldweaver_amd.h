@@ -5,6 +5,7 @@
  *   perform_MI_computation()            R/computePairwiseMI.R:46-145
  *   estimate_Hamming_distance_weights() R/performPopulationStuctureCorrection.R:20-81
  *   .ACGTN2num()                        src/ACGTN2num_parallel.cpp:10-43
+ *   estimate_variation_in_CDS()         R/estimateCDSDiversity.R:27-210
  * and the native helpers they call through `.Call` (src/RcppExports.cpp:154-167).
  *
  * Every entry point is `extern "C"`, takes plain pointers and sizes (no R, Rcpp or
@@ -361,6 +362,33 @@ int ldw_lr_reduced_fetch(ldw_ctx *ctx, int64_t capacity, int64_t *row_out, int32
  * refused with LDW_ERR_ARG. */
 int ldw_ldmap(ldw_ctx *ctx, int32_t reducer, int32_t from, int32_t to, int64_t *n_pos_out, int32_t *reducer_out, int32_t *B_out,
               double *htm_out, int64_t capacity);
+
+/* ---- (8b) CDS variation and SNP paint: estimate_variation_in_CDS (R/estimateCDSDiversity.R:27-123), perform_clustering (:127-148),
+ *           painter (:151-210) ------------------------------------------------------------------------------------------------------
+ * Variation of every CDS from the resident alignment (ldw_set_alignment or the FASTA route; LDW_ERR_STATE without one).  POS: L (the
+ * resident alignment's SNP count) 1-based positions in any order, repeats allowed, each within 1..g; ref_seq: the g characters of the
+ * reference (case preserved).  Per SNP the ACGTN_table column is masked by .ACGTN2num's rule (case-sensitive: A/C/G/T rows 0..3, N and '-'
+ * row 4, other characters mask nothing).  var_out[j] = sum(snp_var : cds_start[j] <= POS <= cds_end[j]) / (cds_end[j] - cds_start[j] + 1),
+ * exact integer sum and one fp64 division (bit-identical to R), NaN when no SNP falls inside (R's NA; a CDS with end < start holds none).
+ * Optional outputs (NULL: not written): snp_var_out int64 [L] masked sums; alt_mask_out uint8 [L], bit x set when the masked count of
+ * state x (A,C,G,T,N) is > 0; ref_out [L] the reference character of each SNP.  The sorted positions stay on the context for ldw_cds_paint. */
+int ldw_cds_variation(ldw_ctx *ctx, const int32_t *POS, int64_t L, const char *ref_seq, int64_t g, const int32_t *cds_start,
+                      const int32_t *cds_end, int64_t ncds, double *var_out, int64_t *snp_var_out, uint8_t *alt_mask_out, char *ref_out);
+/* painter over the SNPs of the last ldw_cds_variation: paint_out int32 [L] in SNP index order.  label[j] in 1..nclust (nclust <= 255) for the
+ * nkept kept CDSs; a SNP takes the largest label of any CDS with cds_start < POS < cds_end (strict), then the 0 runs are filled as painter
+ * does from its run table (first run from the right, last recorded run from the left, interior runs split at round((e - b) / 2), half to
+ * even).  LDW_QUIRK_REFERENCE leaves a last run of one SNP that differs from its predecessor unrecorded, as the reference's loop does (such
+ * a SNP keeps 0 when it is unpainted); LDW_QUIRK_INTENDED records it.  *n_unpainted_out (may be NULL): SNPs left at 0.  LDW_ERR_ARG when no
+ * recorded run is painted (no SNP lies strictly inside a kept CDS).  Where the reference stops with an R error — L = 1, no interior 0 run —
+ * the paint is returned as it stands. */
+int ldw_cds_paint(ldw_ctx *ctx, const int32_t *cds_start, const int32_t *cds_end, const int32_t *label, int64_t nkept, int nclust,
+                  int quirk_mode, int32_t *paint_out, int64_t *n_unpainted_out);
+/* Host only.  k-means of n values into k clusters at the EXACT optimum of the within-cluster sum of squares (1-D clusters are contiguous in
+ * sorted order: a DP over the distinct values with divide-and-conquer rows, O(k n log n)), in place of stats::kmeans(x, k, nstart = 10), which
+ * draws from R's unseeded RNG.  Equal values share a cluster; exact cost ties go to the smallest split point.  label_out [n] in 1..k by cluster
+ * size, descending (ties: ascending cluster mean), as perform_clustering relabels; *cutoff_out = max(x[label == 1]).  LDW_ERR_ARG for
+ * non-finite values, k < 1 or fewer than k distinct values (n = 0 included) ("more cluster centers than distinct data points."). */
+int ldw_kmeans_1d(const double *x, int64_t n, int32_t k, int32_t *label_out, double *cutoff_out);
 
 /* ---- (9) the tsv files — write.table(x, file, append = T, quote = F, row.names = F, col.names = F, sep = '\t'),
  *          R/computePairwiseMI.R:140 (sr_links.tsv) and :362 (lr_links.tsv); readers R/io_functions.R:32-66 ------------

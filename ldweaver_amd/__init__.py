@@ -1,0 +1,17 @@
+"""MI355X-native LDWeaver: the entry points with the reference's names resolve lazily, so importing the package loads nothing."""
+
+_EXPORTS = {
+    "Engine": "engine", "kmeans_1d": "engine",
+    "SnpDat": "snpdat", "CdsVar": "snpdat",
+    "Annotation": "cds", "parse_gff_file": "cds", "estimate_variation_in_CDS": "cds",
+    "parse_fasta_alignment": "extract", "parse_fasta_SNP_alignment": "extract",
+    "estimate_Hamming_distance_weights": "mi", "perform_MI_computation": "mi",
+}
+__all__ = sorted(_EXPORTS)
+
+
+def __getattr__(name):
+    if name in _EXPORTS:
+        import importlib
+        return getattr(importlib.import_module(f".{_EXPORTS[name]}", __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

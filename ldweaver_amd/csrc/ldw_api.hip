@@ -437,13 +437,7 @@ __global__ __launch_bounds__(256) void k_counts_marginals(const uint8_t *__restr
 __global__ void k_acgtn2num(double *__restrict__ nv, const char *__restrict__ ref, int64_t L) {
     const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (c >= L) return;
-    const char cc = ref[c];
-    int rowi = -1;
-    if (cc == 'A') rowi = 0;
-    else if (cc == 'C') rowi = 1;
-    else if (cc == 'G') rowi = 2;
-    else if (cc == 'T') rowi = 3;
-    else if (cc == 'N' || cc == '-') rowi = 4;
+    const int rowi = acgtn_row(ref[c]);
     if (rowi >= 0) nv[c * 5 + rowi] = 0.0;
 }
 
@@ -622,7 +616,8 @@ int ldw_ctx_destroy(ldw_ctx *c) {
                            &c->srm_q, &c->srm_n, &c->srm_md, &c->srm_part, &c->srm_shape, &c->srm_cnt, &c->red_row, &c->red_meta,
                            &c->red_srp, &c->pool_a, &c->pool_b, &c->pool_mi, &c->ar_key, &c->ar_val, &c->ar_key2, &c->ar_val2,
                            &c->ar_off, &c->ar_flags, &c->seq_perm, &c->dig_a, &c->dig_b, &c->apx_shift, &c->slot_papx, &c->pop_segs, &c->pop_wbeg, &c->pop_vpos,
-                           &c->pair_sums, &c->tab11[0], &c->tab11[1], &c->G2, &c->G3, &c->miss_key, &c->miss_val, &c->srd_lower, &c->srd_cur, &c->srd_out, &c->srd_seg, &c->pos_slot};
+                           &c->pair_sums, &c->tab11[0], &c->tab11[1], &c->G2, &c->G3, &c->miss_key, &c->miss_val, &c->srd_lower, &c->srd_cur, &c->srd_out, &c->srd_seg, &c->pos_slot,
+                           &c->cds_keep, &c->cds_work};
     for (auto *b : bufs) b->release();
     for (int k = 0; k < LDW_NSLOT; ++k)
         for (ldw::DevBuf *b : {&c->panel[k][0], &c->panel[k][1], &c->Gapx[k], &c->pairs[k], &c->apx_mini[k], &c->apx_units[k], &c->apx_packs[k], &c->apx_bins[k], &c->apx_clean[k],

@@ -65,4 +65,17 @@ __host__ __device__ __forceinline__ uint8_t encode_char(unsigned char c) {
     }
 }
 
+// the reference-allele row of .ACGTN2num (src/ACGTN2num_parallel.cpp:10-43): case-sensitive, A/C/G/T -> 0..3, N and '-' -> 4, any other byte
+// (lower case, IUPAC) -> -1 (no row is masked)
+__host__ __device__ __forceinline__ int acgtn_row(char c) {
+    switch (c) {
+        case 'A': return 0;
+        case 'C': return 1;
+        case 'G': return 2;
+        case 'T': return 3;
+        case 'N': case '-': return 4;
+        default: return -1;
+    }
+}
+
 }  // namespace ldw

@@ -1,6 +1,6 @@
 // Host-side natives of the path: ARACNE (R/io_functions.R:101-164) and the four small helpers it is
-// built from in the reference (src/computeMI.cpp:25-77, src/fintersect.cpp:6-32).  Exact comparisons
-// only; no floating-point arithmetic.
+// built from in the reference (src/computeMI.cpp:25-77, src/fintersect.cpp:6-32), exact comparisons only;
+// R's sample(); and the 1-D k-means of perform_clustering (R/estimateCDSDiversity.R:127-148).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -69,9 +69,106 @@ struct RMersenne {
         }
     }
 };
+
+// ------------------------------------------------------------------------------------------------
+// 1-D k-means at the exact optimum (perform_clustering, R/estimateCDSDiversity.R:127-148).  Over the d distinct values u (ascending, with
+// multiplicities w) the clusters of an optimum are contiguous: D[c][j] = min_i D[c-1][i] + cost(i, j), cost of the values [i, j) from
+// prefix sums of the centred values in long double.  The argmin is monotone in j (the cost is Monge), so each row is filled by divide and
+// conquer.  Scanning i upwards with a strict < keeps the smallest argmin, which is what makes exact ties deterministic.
+// ------------------------------------------------------------------------------------------------
+struct KMeans1D {
+    std::vector<long double> S1, S2, W;   // prefix sums over distinct values
+    std::vector<long double> prev, cur;
+    std::vector<int32_t> arg;             // [c][j]: split of the best c-cluster partition of [0, j)
+    int64_t d = 0;
+    long double cost(int64_t i, int64_t j) const {
+        const long double s1 = S1[j] - S1[i], s2 = S2[j] - S2[i], w = W[j] - W[i];
+        const long double v = s2 - s1 * s1 / w;
+        return v > 0 ? v : 0;
+    }
+    void row(int c, int64_t jlo, int64_t jhi, int64_t ilo, int64_t ihi) {   // D[c][j] for j in [jlo, jhi], argmin within [ilo, ihi]
+        if (jlo > jhi) return;
+        const int64_t j = (jlo + jhi) / 2;
+        int64_t best_i = -1;
+        long double best = 0;
+        for (int64_t i = std::max<int64_t>(ilo, c - 1); i <= std::min<int64_t>(ihi, j - 1); ++i) {
+            const long double v = prev[(size_t)i] + cost(i, j);
+            if (best_i < 0 || v < best) {
+                best = v;
+                best_i = i;
+            }
+        }
+        cur[(size_t)j] = best;
+        arg[(size_t)c * (d + 1) + j] = (int32_t)best_i;
+        row(c, jlo, j - 1, ilo, best_i);
+        row(c, j + 1, jhi, best_i, ihi);
+    }
+};
 }  // namespace
 
 extern "C" {
+
+int ldw_kmeans_1d(const double *x, int64_t n, int32_t k, int32_t *label_out, double *cutoff_out) {
+    LDW_REQUIRE(cutoff_out && n >= 0 && (n == 0 || (x && label_out)), LDW_ERR_ARG, "ldw_kmeans_1d: bad argument");
+    LDW_REQUIRE(k >= 1, LDW_ERR_ARG, "ldw_kmeans_1d: k = %d must be positive", k);
+    for (int64_t i = 0; i < n; ++i) LDW_REQUIRE(std::isfinite(x[i]), LDW_ERR_ARG, "ldw_kmeans_1d: NA/NaN/Inf in x[%lld]", (long long)i);
+    std::vector<int64_t> ord((size_t)n);
+    for (int64_t i = 0; i < n; ++i) ord[(size_t)i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return x[a] < x[b]; });
+    std::vector<double> u;
+    std::vector<int64_t> w, slot((size_t)n);
+    for (int64_t r = 0; r < n; ++r) {
+        const double v = x[ord[(size_t)r]];
+        if (u.empty() || v != u.back()) {
+            u.push_back(v);
+            w.push_back(0);
+        }
+        ++w.back();
+        slot[(size_t)ord[(size_t)r]] = (int64_t)u.size() - 1;
+    }
+    const int64_t d = (int64_t)u.size();
+    LDW_REQUIRE(d >= k, LDW_ERR_ARG, "more cluster centers than distinct data points.");
+    KMeans1D km;
+    km.d = d;
+    const long double shift = u[(size_t)(d / 2)];
+    km.S1.assign((size_t)d + 1, 0);
+    km.S2.assign((size_t)d + 1, 0);
+    km.W.assign((size_t)d + 1, 0);
+    for (int64_t i = 0; i < d; ++i) {
+        const long double y = (long double)u[(size_t)i] - shift, wi = (long double)w[(size_t)i];
+        km.S1[(size_t)i + 1] = km.S1[(size_t)i] + wi * y;
+        km.S2[(size_t)i + 1] = km.S2[(size_t)i] + wi * y * y;
+        km.W[(size_t)i + 1] = km.W[(size_t)i] + wi;
+    }
+    km.arg.assign((size_t)(k + 1) * (size_t)(d + 1), 0);
+    km.prev.assign((size_t)d + 1, 0);
+    km.cur.assign((size_t)d + 1, 0);
+    for (int64_t j = 1; j <= d; ++j) km.prev[(size_t)j] = km.cost(0, j);
+    for (int c = 2; c <= k; ++c) {
+        km.row(c, c, d, c - 1, d - 1);
+        std::swap(km.prev, km.cur);
+    }
+    // clusters in ascending order of their values: [bnd[q], bnd[q + 1]) over the distinct values
+    std::vector<int64_t> bnd((size_t)k + 1);
+    bnd[(size_t)k] = d;
+    for (int c = k; c >= 2; --c) bnd[(size_t)c - 1] = km.arg[(size_t)c * (d + 1) + bnd[(size_t)c]];
+    bnd[0] = 0;
+    std::vector<int64_t> size((size_t)k, 0);
+    for (int q = 0; q < k; ++q)
+        for (int64_t i = bnd[(size_t)q]; i < bnd[(size_t)q + 1]; ++i) size[(size_t)q] += w[(size_t)i];
+    // relabel by size, descending; equal sizes by ascending mean (= ascending q)
+    std::vector<int> byq((size_t)k);
+    for (int q = 0; q < k; ++q) byq[(size_t)q] = q;
+    std::stable_sort(byq.begin(), byq.end(), [&](int a, int b) { return size[(size_t)a] > size[(size_t)b]; });
+    std::vector<int32_t> lab((size_t)k);
+    for (int r = 0; r < k; ++r) lab[(size_t)byq[(size_t)r]] = r + 1;
+    std::vector<int32_t> lab_of_value((size_t)d);
+    for (int q = 0; q < k; ++q)
+        for (int64_t i = bnd[(size_t)q]; i < bnd[(size_t)q + 1]; ++i) lab_of_value[(size_t)i] = lab[(size_t)q];
+    for (int64_t i = 0; i < n; ++i) label_out[i] = lab_of_value[(size_t)slot[(size_t)i]];
+    *cutoff_out = u[(size_t)bnd[(size_t)byq[0] + 1] - 1];
+    return LDW_OK;
+}
 
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret) {
     LDW_REQUIRE(x && y && ret && nr >= 0 && nc >= 0 && ny >= 0, LDW_ERR_ARG, "ldw_compare_to_row: bad argument");

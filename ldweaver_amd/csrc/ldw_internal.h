@@ -189,6 +189,10 @@ struct ldw_ctx {
     ldw::DevBuf lo_rows;         // int32 row lists of the gathered GEMM's workgroups
     ldw::DevBuf packs;           // per-block SNP constants in epilogue order (ColMeta / RowPack arrays, k_build_packs)
     ldw::DevBuf counts;          // int32 [L][5] per-SNP state counts
+    // ---- CDS variation / paint (ldw_cds.hip) ----
+    ldw::DevBuf cds_keep;        // uint32 [cds_L] positions in ascending order, int32 [cds_L] their SNP index: left by ldw_cds_variation for ldw_cds_paint
+    ldw::DevBuf cds_work;        // per-call working memory of both
+    int64_t cds_L = 0;           // SNPs of the last ldw_cds_variation (0: none yet)
     ldw::DevBuf pfix_state;      // int64 [L][5]: fixed-point marginal of each state (histogram engine)
     std::vector<int32_t> h_row0;
     std::vector<uint32_t> h_slot_meta;

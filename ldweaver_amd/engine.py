@@ -368,6 +368,41 @@ class Engine:
         L.check(L.lib().ldw_state_counts(self._ctx, L.ptr(out)))
         return np.ascontiguousarray(out.T)  # 5 x L like ACGTN_table
 
+    # -- CDS variation and paint (R/estimateCDSDiversity.R) ----------------------------------------------------
+    def cds_variation(self, POS, ref_seq, starts, ends):
+        """Per CDS the masked SNP variation per base of the resident alignment (ldw_cds_variation): (var float64 [ncds], NaN where no SNP falls
+        inside; snp_var int64 [L]; alt_mask uint8 [L], bit x = state x (A,C,G,T,N) present beside the reference; ref uint8 [L])."""
+        ps = L.as_c(POS, np.int32)
+        ref = L.as_c(np.frombuffer(ref_seq, dtype=np.uint8) if isinstance(ref_seq, (bytes, bytearray)) else ref_seq, np.uint8)
+        st, en = L.as_c(starts, np.int32), L.as_c(ends, np.int32)
+        if st.shape != en.shape:
+            raise ValueError("starts and ends differ in length")
+        var = np.empty(len(st), dtype=np.float64)
+        snp_var = np.empty(len(ps), dtype=np.int64)
+        alt = np.empty(len(ps), dtype=np.uint8)
+        refc = np.empty(len(ps), dtype=np.uint8)
+        L.check(L.lib().ldw_cds_variation(self._ctx, L.ptr(ps), len(ps), L.ptr(ref), len(ref), L.ptr(st), L.ptr(en), len(st), L.ptr(var),
+                                          L.ptr(snp_var), L.ptr(alt), L.ptr(refc)))
+        self._cds_L = len(ps)
+        return var, snp_var, alt, refc
+
+    def cds_paint(self, starts, ends, labels, nclust: int, quirk_mode: int = L.QUIRK_REFERENCE):
+        """painter over the SNPs of the last ``cds_variation`` (ldw_cds_paint): (paint int32 [L], SNPs left at 0).  ValueError when no SNP lies
+        strictly inside a kept CDS."""
+        st, en, lb = L.as_c(starts, np.int32), L.as_c(ends, np.int32), L.as_c(labels, np.int32)
+        if not (st.shape == en.shape == lb.shape):
+            raise ValueError("starts, ends and labels differ in length")
+        n0 = C.c_int64(0)
+        out = np.empty(getattr(self, "_cds_L", 0), dtype=np.int32)   # (one entry per SNP of the last cds_variation)
+        rc = L.lib().ldw_cds_paint(self._ctx, L.ptr(st), L.ptr(en), L.ptr(lb), len(st), int(nclust), int(quirk_mode),
+                                   L.ptr(out) if len(out) else None, C.byref(n0))
+        if rc == L.LDW_ERR_ARG:
+            msg = L.lib().ldw_last_error().decode("utf-8", "replace")
+            if "no SNP lies strictly inside" in msg:
+                raise ValueError(msg)
+        L.check(rc)
+        return out, int(n0.value)
+
     # -- Hamming weights -------------------------------------------------------
     def hamming_weights(self, thresh: int, want_shared=False):
         hdw = np.empty(self.N, dtype=np.float64)
@@ -738,6 +773,20 @@ def format_number(x: float) -> str:
     buf = C.create_string_buffer(64)
     L.check(L.lib().ldw_format_number(float(x), buf, 64))
     return buf.value.decode()
+
+
+def kmeans_1d(x, k: int):
+    """k-means of the values x into k clusters at the exact optimum of the within-cluster sum of squares (ldw_kmeans_1d, host only):
+    (labels int32 [n] in 1..k by cluster size, descending, cutoff = max(x[labels == 1])).  ValueError as R's kmeans for fewer than k
+    distinct values."""
+    xs = L.as_c(x, np.float64).ravel()
+    lab = np.empty(len(xs), dtype=np.int32)
+    cut = C.c_double(0)
+    rc = L.lib().ldw_kmeans_1d(L.ptr(xs), len(xs), int(k), L.ptr(lab), C.byref(cut))
+    if rc == L.LDW_ERR_ARG:
+        raise ValueError(L.lib().ldw_last_error().decode("utf-8", "replace"))
+    L.check(rc)
+    return lab, float(cut.value)
 
 
 def write_table_tsv(path: str, columns, append: bool = True, nthreads: int = 0) -> int:

@@ -71,9 +71,17 @@ class SnpDat:
 
 @dataclass
 class CdsVar:
-    """The two fields of ``cds_var`` the path reads (R/estimateCDSDiversity.R; R/computePairwiseMI.R:74,194)."""
+    """``cds_var`` (R/estimateCDSDiversity.R:114-116).  The path reads ``paint`` and ``nclust`` (R/computePairwiseMI.R:74,194); the other
+    fields are what ``cds.estimate_variation_in_CDS`` also returns, None when the object is built by hand."""
     paint: np.ndarray   # int [L] cluster id (1..nclust) per SNP
     nclust: int
+    var_estimate: np.ndarray | None = None   # float64 [kept CDSs]: masked SNP variation per base of every CDS that holds a SNP
+    cds_start: np.ndarray | None = None      # [kept CDSs]
+    cds_end: np.ndarray | None = None        # [kept CDSs]
+    clusts: dict | None = None               # {"km_clst_ord": int32 [kept CDSs] labels 1..nclust by size, "cutoff": max var_estimate of label 1}
+    ref: np.ndarray | None = None            # '<U1' [L] reference character at each SNP (case preserved)
+    alt: list | None = None                  # [L] str: the non-reference states present, "A,C,G,T,*" letters joined with ","
+    allele_table: np.ndarray | None = None   # int32 (5, L) A,C,G,T,N counts (ACGTN_table)
 
 
 def read_fasta(path: str):

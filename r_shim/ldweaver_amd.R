@@ -179,3 +179,36 @@ genomewide_LDMap_device <- function(reducer = NULL, from = NULL, to = NULL) {
   .Call("ldwamd_ldmap", if (is.null(reducer)) 0L else as.integer(round(reducer)), if (is.null(from)) 0L else as.integer(round(from)),
         if (is.null(to)) 0L else as.integer(round(to)))
 }
+
+# estimate_variation_in_CDS (R/estimateCDSDiversity.R:27-123) with a gff3 annotation from parse_gff_file: masked SNP variation, per-CDS
+# variation per base and the SNP paint on the device, the clustering at the exact k-means optimum (the reference's kmeans(nstart = 10) draws
+# from an unseeded RNG).  quirk_mode = 0 reproduces painter's unrecorded single-SNP last run (that SNP may keep paint 0); 1 paints it from the
+# left.  GenBank input and the cluster plot are not implemented.
+ldwamd_estimate_variation_in_CDS <- function(snp.dat, ncores, gbk = NULL, gff = NULL, num_clusts_CDS = 3, clust_plt_path = NULL, mega_dset = FALSE,
+                                             quirk_mode = 0L) {
+  t0 <- Sys.time()
+  if ((is.null(gbk) & is.null(gff)) | (!is.null(gbk) & !is.null(gff))) stop("Provide either one of gbk or gff")
+  if (!is.null(gbk)) stop("ldweaver_amd: GenBank input is not implemented; use parse_gff_file")
+  gff_cds <- gff$gff[tolower(gff$gff$type) == "cds", ]
+  starts <- as.integer(gff_cds$start); ends <- as.integer(gff_cds$end)
+  .ldwamd_use_devices()
+  .Call("ldwamd_set_alignment", .ldwamd_states_from_snpdat(snp.dat), snp.dat$nsnp, snp.dat$nseq)
+  v <- .Call("ldwamd_cds_variation", as.integer(snp.dat$POS), as.character(gff$ref), starts, ends)
+  var_estimate <- v[[1]]; var_estimate[is.nan(var_estimate)] <- NA
+  cds_idx <- !is.na(var_estimate)
+  var_estimate <- var_estimate[cds_idx]; cds_start <- starts[cds_idx]; cds_end <- ends[cds_idx]
+  km <- .Call("ldwamd_kmeans_1d", as.numeric(var_estimate), as.integer(num_clusts_CDS))
+  clusts <- list(km_clst_ord = km[[1]], cutoff = km[[2]])
+  p <- .Call("ldwamd_cds_paint", cds_start, cds_end, km[[1]], as.integer(num_clusts_CDS), as.integer(quirk_mode))
+  paint <- p[[1]]
+  if (p[[2]] > 0) warning(sprintf("SNP at POS %d keeps paint 0 (painter's unrecorded last run); quirk_mode = 1 paints it from the left",
+                                  snp.dat$POS[which(paint == 0)[1]]))
+  alpha <- c("A", "C", "G", "T", "*")
+  alt <- vapply(v[[3]], function(m) paste(alpha[bitwAnd(m, c(1L, 2L, 4L, 8L, 16L)) > 0], collapse = ","), "")
+  variation <- matrix(c(Matrix::rowSums(snp.dat$snp.matrix_A), Matrix::rowSums(snp.dat$snp.matrix_C), Matrix::rowSums(snp.dat$snp.matrix_G),
+                        Matrix::rowSums(snp.dat$snp.matrix_T), Matrix::rowSums(snp.dat$snp.matrix_N)), ncol = snp.dat$nsnp, byrow = T)
+  rownames(variation) <- c("A", "C", "G", "T", "N")
+  cat(paste("Done in", round(difftime(Sys.time(), t0, units = "secs"), 2), "s\n"))
+  list(var_estimate = var_estimate, cds_start = cds_start, cds_end = cds_end, clusts = clusts, paint = paint,
+       ref = gff$ref[snp.dat$POS], alt = alt, allele_table = variation, nclust = num_clusts_CDS)
+}

@@ -267,6 +267,66 @@ SEXP ldwamd_ldmap(SEXP reducer, SEXP from, SEXP to) {
     return htm;
 }
 
+/* estimate_variation_in_CDS (R/estimateCDSDiversity.R:27-105) on the resident alignment.  pos INTSXP [L] 1-based; ref STRSXP: the reference
+ * one character per element (gff$ref); starts / ends INTSXP.  Returns list(var_estimate with NaN where the reference has NA, snp_var, alt mask
+ * (bit x: state x of A,C,G,T,N present beside the reference)).  The SNP count is kept for ldwamd_cds_paint. */
+static R_xlen_t g_cds_L = -1;
+SEXP ldwamd_cds_variation(SEXP pos, SEXP ref, SEXP starts, SEXP ends) {
+    ldw_ctx *c = ctx_or_stop();
+    const R_xlen_t L = XLENGTH(pos), g = XLENGTH(ref), n = XLENGTH(starts);
+    if (XLENGTH(ends) != n) error("ldweaver_amd: starts and ends differ in length");
+    char *rs = (char *)R_alloc((size_t)g + 1, 1);
+    for (R_xlen_t i = 0; i < g; ++i) rs[i] = CHAR(STRING_ELT(ref, i))[0];
+    int64_t *sv = (int64_t *)R_alloc((size_t)L + 1, sizeof(int64_t));
+    uint8_t *am = (uint8_t *)R_alloc((size_t)L + 1, 1);
+    SEXP res = PROTECT(allocVector(VECSXP, 3));
+    SEXP var = PROTECT(allocVector(REALSXP, n)), snp_var = PROTECT(allocVector(REALSXP, L)), alt = PROTECT(allocVector(INTSXP, L));
+    g_cds_L = -1;
+    CHK(ldw_cds_variation(c, (const int32_t *)INTEGER(pos), (int64_t)L, rs, (int64_t)g, (const int32_t *)INTEGER(starts), (const int32_t *)INTEGER(ends),
+                          (int64_t)n, REAL(var), sv, am, NULL));
+    g_cds_L = L;
+    for (R_xlen_t i = 0; i < L; ++i) {
+        REAL(snp_var)[i] = (double)sv[i];
+        INTEGER(alt)[i] = am[i];
+    }
+    SET_VECTOR_ELT(res, 0, var);
+    SET_VECTOR_ELT(res, 1, snp_var);
+    SET_VECTOR_ELT(res, 2, alt);
+    UNPROTECT(4);
+    return res;
+}
+
+/* painter (R/estimateCDSDiversity.R:151-210) over the SNPs of the last ldwamd_cds_variation: list(paint, number of SNPs left at 0).
+ * quirk: 0 the reference's loop, 1 the unrecorded last run filled from the left. */
+SEXP ldwamd_cds_paint(SEXP starts, SEXP ends, SEXP labels, SEXP nclust, SEXP quirk) {
+    ldw_ctx *c = ctx_or_stop();
+    const R_xlen_t n = XLENGTH(starts);
+    if (g_cds_L < 0) error("ldweaver_amd: call ldwamd_cds_variation first");
+    if (XLENGTH(ends) != n || XLENGTH(labels) != n) error("ldweaver_amd: starts, ends and labels differ in length");
+    int64_t n0 = 0;
+    SEXP res = PROTECT(allocVector(VECSXP, 2));
+    SEXP paint = PROTECT(allocVector(INTSXP, g_cds_L));
+    CHK(ldw_cds_paint(c, (const int32_t *)INTEGER(starts), (const int32_t *)INTEGER(ends), (const int32_t *)INTEGER(labels), (int64_t)n,
+                      asInteger(nclust), asInteger(quirk), (int32_t *)INTEGER(paint), &n0));
+    SET_VECTOR_ELT(res, 0, paint);
+    SET_VECTOR_ELT(res, 1, ScalarReal((double)n0));
+    UNPROTECT(2);
+    return res;
+}
+
+/* perform_clustering (R/estimateCDSDiversity.R:127-148) at the exact optimum of the k-means objective: list(km_clst_ord, cutoff) */
+SEXP ldwamd_kmeans_1d(SEXP x, SEXP k) {
+    const R_xlen_t n = XLENGTH(x);
+    double cutoff = 0;
+    SEXP res = PROTECT(allocVector(VECSXP, 2));
+    SEXP lab = PROTECT(allocVector(INTSXP, n));
+    CHK(ldw_kmeans_1d(REAL(x), (int64_t)n, asInteger(k), (int32_t *)INTEGER(lab), &cutoff));
+    SET_VECTOR_ELT(res, 0, lab);
+    SET_VECTOR_ELT(res, 1, ScalarReal(cutoff));
+    UNPROTECT(2);
+    return res;
+}
+
 /* ---- native-level twins of the reference's own .Call table (src/RcppExports.cpp:154-160): same symbol names, arity, argument
  * types and return values, so that LDWeaver's UNCHANGED R code (.fastHadamard R/computePairwiseMI.R:396, .compareToRow :374,
  * .vecPosMatch / .compareTriplet / .fast_intersect R/io_functions.R:125-155, .ACGTN2num R/computePairwiseMI.R:256-259) binds to
@@ -402,6 +462,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"_LDWeaver_fast_intersect", (DL_FUNC)&_LDWeaver_fast_intersect, 2},
     {"ldwamd_lr_tukey_aracne", (DL_FUNC)&ldwamd_lr_tukey_aracne, 4},
     {"ldwamd_ldmap", (DL_FUNC)&ldwamd_ldmap, 3},
+    {"ldwamd_cds_variation", (DL_FUNC)&ldwamd_cds_variation, 4},
+    {"ldwamd_cds_paint", (DL_FUNC)&ldwamd_cds_paint, 5},
+    {"ldwamd_kmeans_1d", (DL_FUNC)&ldwamd_kmeans_1d, 2},
     {"ldwamd_set_sr_rows_stay", (DL_FUNC)&ldwamd_set_sr_rows_stay, 1},
     {"ldwamd_sr_len_quantiles", (DL_FUNC)&ldwamd_sr_len_quantiles, 3},
     {"ldwamd_sr_excess_stats", (DL_FUNC)&ldwamd_sr_excess_stats, 2},
