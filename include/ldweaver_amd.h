@@ -389,6 +389,19 @@ int ldw_cds_paint(ldw_ctx *ctx, const int32_t *cds_start, const int32_t *cds_end
  * size, descending (ties: ascending cluster mean), as perform_clustering relabels; *cutoff_out = max(x[label == 1]).  LDW_ERR_ARG for
  * non-finite values, k < 1 or fewer than k distinct values (n = 0 included) ("more cluster centers than distinct data points."). */
 int ldw_kmeans_1d(const double *x, int64_t n, int32_t k, int32_t *label_out, double *cutoff_out);
+/* Host only, no context and no GPU: the GenBank reader behind parse_genbank_file (R/parseGBK.R), the annotation route the reference's
+ * estimate_variation_in_CDS takes (R/estimateCDSDiversity.R:39-47).  One record, plain or gzip, LF / CRLF / CR lines; '<' and '>' are deleted
+ * from the whole text first.  Every segment of every feature whose key is exactly "CDS" is one row, in file order: start / end int64,
+ * 1-based inclusive (a..b, a, a^b -> [a, b-1]), strand +1 / -1 (complement), feature the 0-based index of its CDS feature.  seq: the ORIGIN
+ * sequence (whitespace, digits and "//" removed; IUPAC DNA letters and -+. only; stored UPPER CASE) cut to the range of the single source
+ * feature, g bytes.  meta: NUL-terminated strings: the sequence name (/chromosome, /strain or /organism of source), the LOCUS name, the first
+ * ACCESSION and the VERSION, then locus_tag, gene and product of each CDS feature ("" when absent).  Errors (LDW_ERR_ARG) name the line:
+ * a segment of negative width, a location outside the grammar (remote accession, gap(), one-of(), nested join), no ORIGIN or not exactly one
+ * source range ("The GBK file should contain the reference sequence!"), more than one record.  Grammar and divergences: DESIGN.md 17.
+ * _probe gives the sizes; _read parses the file again into buffers of at least those sizes (LDW_ERR_SIZE otherwise). */
+int ldw_gbk_probe(const char *path, int64_t *n_rows, int64_t *n_features, int64_t *g, int64_t *meta_bytes);
+int ldw_gbk_read(const char *path, int64_t rows_cap, int64_t *start, int64_t *end, int8_t *strand, int64_t *feature, int64_t g_cap, char *seq,
+                 int64_t meta_cap, char *meta);
 
 /* ---- (9) the tsv files — write.table(x, file, append = T, quote = F, row.names = F, col.names = F, sep = '\t'),
  *          R/computePairwiseMI.R:140 (sr_links.tsv) and :362 (lr_links.tsv); readers R/io_functions.R:32-66 ------------

@@ -4,6 +4,7 @@ _EXPORTS = {
     "Engine": "engine", "kmeans_1d": "engine",
     "SnpDat": "snpdat", "CdsVar": "snpdat",
     "Annotation": "cds", "parse_gff_file": "cds", "estimate_variation_in_CDS": "cds",
+    "GenBankRecord": "gbk", "parse_genbank_file": "gbk",
     "parse_fasta_alignment": "extract", "parse_fasta_SNP_alignment": "extract",
     "estimate_Hamming_distance_weights": "mi", "perform_MI_computation": "mi",
 }

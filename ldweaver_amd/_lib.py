@@ -101,6 +101,8 @@ _SIGS_API = {
     "ldw_cds_variation": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p]),
     "ldw_cds_paint": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, C.c_int, _p, C.POINTER(_i64)]),
     "ldw_kmeans_1d": (C.c_int, [_p, _i64, C.c_int32, _p, C.POINTER(C.c_double)]),
+    "ldw_gbk_probe": (C.c_int, [C.c_char_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "ldw_gbk_read": (C.c_int, [C.c_char_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p]),
     "ldw_format_number": (C.c_int, [C.c_double, C.c_char_p, C.c_int]),
     "ldw_r_sample": (C.c_int, [C.c_uint32, C.c_int64, C.c_int64, _p]),
     "ldw_write_table_tsv": (C.c_int, [C.c_char_p, C.c_int, _i64, C.c_int, _p, _p, C.c_int, C.POINTER(_i64)]),

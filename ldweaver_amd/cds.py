@@ -2,8 +2,10 @@
 
 The annotation (CDS intervals + reference sequence) and the resident alignment give ``cds_var``, the argument ``perform_MI_computation``
 takes: per SNP the non-reference state counts, per CDS the variation per base, a k-means clustering of the CDSs and the paint of every SNP.
-The per-SNP and per-CDS work runs on the device (``Engine.cds_variation`` / ``Engine.cds_paint``, csrc/ldw_cds.hip); the clustering of the
-kept CDSs is the exact 1-D optimum on the host (``kmeans_1d``).  GenBank input and the cluster plot are not implemented.
+The annotation comes from GFF3 plus a reference FASTA (``parse_gff_file``, the FASTA's case kept) or from a GenBank file
+(``parse_genbank_file`` in gbk.py, native parser csrc/ldw_gbk.cpp, sequence upper case).  The per-SNP and per-CDS work runs on the device
+(``Engine.cds_variation`` / ``Engine.cds_paint``, csrc/ldw_cds.hip); the clustering of the kept CDSs is the exact 1-D optimum on the host
+(``kmeans_1d``).  The cluster plot is not drawn.
 """
 from __future__ import annotations
 
@@ -133,7 +135,8 @@ def parse_gff_file(gff3_path, ref_fasta_path, perform_length_check=True) -> Anno
 def estimate_variation_in_CDS(snp_dat: SnpDat, ncores=1, gbk=None, gff: Annotation | None = None, num_clusts_CDS=3, clust_plt_path=None,
                               mega_dset=False, *, engine: Engine | None = None, alignment_resident: bool = False,
                               quirk_mode: int = L.QUIRK_REFERENCE) -> CdsVar:
-    """Mirror of ``estimate_variation_in_CDS`` with an annotation from ``parse_gff_file`` or ``Annotation.from_arrays``.
+    """Mirror of ``estimate_variation_in_CDS`` with an annotation from ``parse_gff_file`` or ``Annotation.from_arrays`` (``gff``), or from
+    ``parse_genbank_file`` (``gbk``: the dict it returns or its GenBankRecord; starts and ends of every CDS row, the upper-case sequence).
 
     ``engine`` with ``alignment_resident=True``: the engine already holds ``snp_dat``'s alignment (e.g. ``parse_fasta_alignment(...,
     keep_on_device=True)``).  The clustering is the exact optimum of the k-means objective (``kmeans_1d``) where the reference draws
@@ -143,15 +146,23 @@ def estimate_variation_in_CDS(snp_dat: SnpDat, ncores=1, gbk=None, gff: Annotati
     if (gbk is None) == (gff is None):
         raise ValueError("Provide either one of gbk or gff")
     if gbk is not None:
-        raise NotImplementedError("GenBank input is not supported: build the annotation with parse_gff_file or Annotation.from_arrays")
-    typ = np.asarray(gff.gff["type"]).astype(str)
-    is_cds = np.char.lower(typ) == "cds"
-    starts = np.asarray(gff.gff["start"])[is_cds].astype(np.int64)
-    ends = np.asarray(gff.gff["end"])[is_cds].astype(np.int64)
+        from .gbk import GenBankRecord
+        rec = gbk.get("gbk") if isinstance(gbk, dict) else gbk
+        if not isinstance(rec, GenBankRecord):
+            raise NotImplementedError("gbk must be what parse_genbank_file returns (or its GenBankRecord); other GenBank objects are not supported")
+        starts = np.asarray(rec.cds["start"]).astype(np.int64)      # gbk@cds: every CDS row (R/estimateCDSDiversity.R:40-43)
+        ends = np.asarray(rec.cds["end"]).astype(np.int64)
+        ref = rec.sequence
+    else:
+        typ = np.asarray(gff.gff["type"]).astype(str)
+        is_cds = np.char.lower(typ) == "cds"
+        starts = np.asarray(gff.gff["start"])[is_cds].astype(np.int64)
+        ends = np.asarray(gff.gff["end"])[is_cds].astype(np.int64)
+        ref = gff.ref
     lim = np.iinfo(np.int32)
     if len(starts) and (min(starts.min(), ends.min()) < lim.min or max(starts.max(), ends.max()) > lim.max):
         raise ValueError("CDS bounds must fit in 32 bits")
-    ref_seq = _as_chars(gff.ref)
+    ref_seq = _as_chars(ref)
     own = engine is None
     eng = engine or Engine(0)
     try:
