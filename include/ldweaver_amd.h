@@ -447,6 +447,18 @@ int ldw_tsv_join(ldw_ctx *ctx);
 int ldw_lr_stream_begin(ldw_ctx *ctx, const char *path, int append, int nthreads);
 int ldw_lr_stream_end(ldw_ctx *ctx, int64_t *rows_out, int64_t *bytes_out, int64_t *blocks_out);
 
+/* ---- (10) the SNP alignment as text — snpdat_to_fa (R/io_functions.R:363-417), generate_Links_SNPS_fasta (:432-460), snps.aln of
+ *           write_output_for_gwes_explorer (R/createGWESExplorerOutput.R:23-76) -------------------------------------------------------
+ * The k SNP rows snp_idx (0-based, any order, repeats allowed, each in [0, L)) of the resident alignment, every sequence in its original
+ * order, states 0..4 printed as A C G T N.  format 0: FASTA records ">name\n" + k characters + "\n"; format 1: the body of write.table's tsv,
+ * name + k x ("\t" character) + "\n" (the header line is the caller's).  names: N names, each followed by a NUL (names_bytes in total); a
+ * name may not hold '\n'.  The file is appended to (append != 0) or truncated.  The text is rendered on the device and written in chunks of
+ * whole records of at most chunk_bytes (<= 0: 64 MiB; a larger record is a chunk of its own) through two pinned buffers that ldw_host_trim
+ * gives back.  LDW_ERR_STATE without a resident alignment; LDW_ERR_ARG for an index outside [0, L), k < 1, a name count other than N, a
+ * name with a newline, or a path that cannot be opened (the message names the path).  *bytes_out (may be NULL): bytes written. */
+int ldw_write_alignment(ldw_ctx *ctx, const char *path, int append, int format, const int32_t *snp_idx, int64_t k, const char *names,
+                        int64_t names_bytes, int64_t chunk_bytes, int64_t *bytes_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

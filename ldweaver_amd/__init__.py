@@ -7,6 +7,8 @@ _EXPORTS = {
     "GenBankRecord": "gbk", "parse_genbank_file": "gbk",
     "parse_fasta_alignment": "extract", "parse_fasta_SNP_alignment": "extract",
     "estimate_Hamming_distance_weights": "mi", "perform_MI_computation": "mi",
+    "snpdat_to_fa": "output", "generate_Links_SNPS_fasta": "output", "write_output_for_gwes_explorer": "output",
+    "read_TopHits": "output", "read_AnnotatedLinks": "output",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -112,6 +112,7 @@ _SIGS_API = {
     "ldw_tsv_join": (C.c_int, [_p]),
     "ldw_lr_stream_begin": (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int]),
     "ldw_lr_stream_end": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "ldw_write_alignment": (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int, _p, _i64, C.c_char_p, _i64, _i64, C.POINTER(_i64)]),
     "ldw_compare_to_row": (C.c_int, [_p, _i64, _i64, _p, _i64, _p]),
     "ldw_vec_pos_match": (C.c_int, [_p, _i64, _p, _i64, _p]),
     "ldw_compare_triplet": (C.c_int, [_p, _p, _i64, C.c_double, C.POINTER(C.c_int)]),

@@ -79,6 +79,7 @@ struct ldw_ctx {
     ldw::DevBuf chars;               // raw alignment characters [cN][cL] kept by ldw_alignment_scan
     int64_t cN = 0, cL = 0;
     void *fasta = nullptr;           // scan state of the native FASTA feeder (ldw_fasta.hip: FastaScan), made by ldw_fasta_scan
+    void *out = nullptr;             // staging of the alignment writer (ldw_out.hip: OutState), made by ldw_write_alignment
 
     // ---- weights ----
     bool have_weights = false;
@@ -310,4 +311,6 @@ void warm_post();
 // ldw_post.hip: the graph node of every SNP for consumers that work on positions (LD map, ARACNE): *slot = null and *n_nodes = L when POS
 // ascends strictly, else the device array ctx->pos_slot (SNPs sharing a position share a node) and the number of distinct positions
 int pos_slots(ldw_ctx *ctx, const int32_t **slot, int64_t *n_nodes);
+void out_release(ldw_ctx *ctx);      // ldw_out.hip: the alignment writer's staging (ldw_ctx_destroy)
+int64_t out_trim(ldw_ctx *ctx);      // ... its pinned buffers and device image only (ldw_host_trim); bytes released
 }  // namespace ldw

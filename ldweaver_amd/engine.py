@@ -363,6 +363,17 @@ class Engine:
         L.check(L.lib().ldw_get_alignment(self._ctx, L.ptr(out)))
         return out
 
+    def write_alignment(self, path, snp_idx, names, format: int = 0, append: bool = False, chunk_bytes: int = 0) -> int:
+        """The SNP rows ``snp_idx`` (0-based, output column order) of the resident alignment as text, rendered on the device
+        (ldw_write_alignment): format 0 FASTA records, 1 the body of write.table's tsv (name, then tab + character per SNP).  ``names``: one
+        str per sequence.  Appended or truncating; written in chunks of ``chunk_bytes`` (0: 64 MiB).  Returns the bytes written."""
+        idx = L.as_c(snp_idx, np.int32).ravel()
+        blob = b"".join(str(n).encode("utf-8") + b"\0" for n in names)
+        nb = C.c_int64(0)
+        L.check(L.lib().ldw_write_alignment(self._ctx, os.fsencode(path), int(bool(append)), int(format), L.ptr(idx), len(idx), blob, len(blob),
+                                            int(chunk_bytes), C.byref(nb)))
+        return int(nb.value)
+
     def state_counts(self) -> np.ndarray:
         out = np.empty((self.L, 5), dtype=np.int32)
         L.check(L.lib().ldw_state_counts(self._ctx, L.ptr(out)))

@@ -174,6 +174,18 @@ analyse_long_range_links_device <- function(snp.dat, cds_var, sr_links, are_lrli
   list(lr_links_red = df, thresholds = r[[7]])
 }
 
+# The text of snpdat_to_fa (R/io_functions.R:363-417) from the resident alignment: snps_idx (1-based rows of snp.dat, output column
+# order) as FASTA appended to aln_path, or as the tsv of write.table(fasta, sep = "\t", quote = F) (header = the positions, no leading field).
+# Host memory stays O(chunk): no dense character matrix is built in R.
+ldwamd_write_alignment <- function(snp.dat, aln_path, snps_idx, pos, format = "fasta") {
+  if (format == "tsv") {
+    writeLines(paste(as.integer(pos), collapse = "\t"), aln_path)
+    .Call("ldwamd_write_alignment", aln_path, TRUE, 1L, as.integer(snps_idx - 1L), as.character(snp.dat$seq.names))
+  } else {
+    .Call("ldwamd_write_alignment", aln_path, TRUE, 0L, as.integer(snps_idx - 1L), as.character(snp.dat$seq.names))
+  }
+}
+
 # Numeric core of genomewide_LDMap (R/LDSummaryPlot.R:55-109): the matrix heatmap3 is given.
 genomewide_LDMap_device <- function(reducer = NULL, from = NULL, to = NULL) {
   .Call("ldwamd_ldmap", if (is.null(reducer)) 0L else as.integer(round(reducer)), if (is.null(from)) 0L else as.integer(round(from)),

@@ -434,6 +434,28 @@ SEXP ldwamd_lr_stream_end(void) {
     return out;
 }
 
+/* snpdat_to_fa / generate_Links_SNPS_fasta / snps.aln (R/io_functions.R:363-460, R/createGWESExplorerOutput.R:23-76) from the resident
+ * alignment: the SNP rows idx (INTSXP, 0-based, output column order) as FASTA (format 0) or as the body of the tsv (format 1, the header line
+ * is R's), names STRSXP one per sequence (snp.dat$seq.names).  Rendered on the device and written in chunks; returns the bytes written. */
+SEXP ldwamd_write_alignment(SEXP path, SEXP append, SEXP format, SEXP idx, SEXP names) {
+    ldw_ctx *c = ctx_or_stop();
+    const R_xlen_t n = XLENGTH(names);
+    size_t nb = 0;
+    for (R_xlen_t i = 0; i < n; ++i) nb += strlen(CHAR(STRING_ELT(names, i))) + 1;
+    char *blob = (char *)R_alloc(nb + 1, 1);
+    size_t at = 0;
+    for (R_xlen_t i = 0; i < n; ++i) {
+        const char *s = CHAR(STRING_ELT(names, i));
+        const size_t l = strlen(s);
+        memcpy(blob + at, s, l + 1);
+        at += l + 1;
+    }
+    int64_t bytes = 0;
+    CHK(ldw_write_alignment(c, CHAR(STRING_ELT(path, 0)), asLogical(append), asInteger(format), (const int32_t *)INTEGER(idx), (int64_t)XLENGTH(idx),
+                            blob, (int64_t)nb, 0, &bytes));
+    return ScalarReal((double)bytes);
+}
+
 /* any numeric data.frame's columns (INTSXP / REALSXP / LGLSXP-as-int) by the same writer; cols: a list of equally long vectors */
 SEXP ldwamd_write_table_tsv(SEXP cols, SEXP path) {
     const int nc = (int)XLENGTH(cols);
@@ -486,6 +508,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"ldwamd_lr_stream_begin", (DL_FUNC)&ldwamd_lr_stream_begin, 1},
     {"ldwamd_lr_stream_end", (DL_FUNC)&ldwamd_lr_stream_end, 0},
     {"ldwamd_write_table_tsv", (DL_FUNC)&ldwamd_write_table_tsv, 2},
+    {"ldwamd_write_alignment", (DL_FUNC)&ldwamd_write_alignment, 5},
     {NULL, NULL, 0}};
 
 void R_init_ldweaver_amd_shim(DllInfo *dll) {
