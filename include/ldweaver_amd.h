@@ -423,6 +423,12 @@ int ldw_r_sample(uint32_t seed, int64_t n, int64_t size, int64_t *out);
  * truncating; rows are formatted by nthreads host threads (0 = all cores) and written in order.  bytes_out may be NULL. */
 int ldw_write_table_tsv(const char *path, int append, int64_t nrows, int ncols, const int32_t *col_kind, const void *const *cols,
                         int nthreads, int64_t *bytes_out);
+/* The same with string-table columns as well: a column of kind LDW_COL_STR holds int32 indices; row i prints string
+ * col_base[k] + index[i] of the table (strings j at blob[offs[j] .. offs[j + 1]), nstr of them, no NUL needed); an index outside the table
+ * is LDW_ERR_ARG.  col_base is read for LDW_COL_STR columns only. */
+#define LDW_COL_STR 3
+int ldw_write_table_tsv_str(const char *path, int append, int64_t nrows, int ncols, const int32_t *col_kind, const void *const *cols,
+                            const int64_t *col_base, const char *blob, const int64_t *offs, int64_t nstr, int nthreads, int64_t *bytes_out);
 /* The context's short-range (which = 0) or long-range (1) link table as the reference's MI_df rows `pos1 pos2 clust1 clust2 len MI`
  * (R/computePairwiseMI.R:319-331: pos1 = POS of the to-side SNP, integer columns; clust, len, MI doubles), fetched from the
  * device and formatted by host threads.  An empty table writes nothing, like the reference (:360). */
@@ -458,6 +464,28 @@ int ldw_lr_stream_end(ldw_ctx *ctx, int64_t *rows_out, int64_t *bytes_out, int64
  * name with a newline, or a path that cannot be opened (the message names the path).  *bytes_out (may be NULL): bytes written. */
 int ldw_write_alignment(ldw_ctx *ctx, const char *path, int append, int format, const int32_t *snp_idx, int64_t k, const char *names,
                         int64_t names_bytes, int64_t chunk_bytes, int64_t *bytes_out);
+
+/* ---- (11) the SnpEff step — perform_snpEff_annotations (R/SnpEffAnnotations.R:29-103): a coding-effect predictor and the link join ------
+ * ldw_annot_snps: the effect of every SNP pos[i] (1-based) with the A/C/G/T alleles of alt_mask[i] (bit x: state x of A C G T; bit 4, the
+ * N / gap state, is ignored) on the CDS features of the reference ref (g characters, any case): seg = nseg x (lo, hi, feature) 1-based inclusive
+ * segments, each feature's segments contiguous and in coding order (ascending on +, descending on -), features 0..nfeat-1 in file order;
+ * strand[f] = +1 / -1.  rec_out: n x LDW_ANNOT_REC int32 records (effect, impact, feature, right feature, c or distance, codon, ref base, alt
+ * base, ref amino acid, alt amino acid, allele, 0); the rule table and the effect codes are DESIGN.md 19.  No alignment is needed.
+ * ldw_annot_map: every end of the n links (pos1, pos2) to the one SNP of POS (L positions, any order) at that position; *bad_out = the first end
+ * (index e < n: pos1[e], else pos2[e - n]) that matches no SNP or several, or -1.  snp_out (capacity L): the SNP index of every annotation row
+ * (the distinct link positions, ascending), *rows_out of them.  The row of every link end stays on the device for ldw_annot_links.
+ * ldw_annot_links: the links of the last ldw_annot_map in R's order(key, decreasing = TRUE) (stable, NaN last): perm_out the source row of
+ * every sorted link, r1_out / r2_out its annotation rows, pair_out 3 code[r1] + code[r2] (codes per row: 0 sy, 1 ns, 2 ig); top_out the sorted
+ * indices of the first max_tophits links that pass detect_top_hits (aracne == 1, pair != syXsy, cds_id[r1] != cds_id[r2], both >= 0),
+ * *n_top_out of them. */
+#define LDW_ANNOT_REC 12
+int ldw_annot_snps(ldw_ctx *ctx, const char *ref, int64_t g, const int32_t *seg, int64_t nseg, const int8_t *strand, int64_t nfeat,
+                   const int32_t *pos, const uint8_t *alt_mask, int64_t n, int32_t *rec_out);
+int ldw_annot_map(ldw_ctx *ctx, const double *pos1, const double *pos2, int64_t n, const int32_t *POS, int64_t L, int32_t *snp_out,
+                  int64_t *rows_out, int64_t *bad_out);
+int ldw_annot_links(ldw_ctx *ctx, const double *key, const double *aracne, int64_t n, const int8_t *code, const int32_t *cds_id, int64_t rows,
+                    int64_t max_tophits, int64_t *perm_out, int32_t *r1_out, int32_t *r2_out, int8_t *pair_out, int64_t *top_out,
+                    int64_t *n_top_out);
 
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */

@@ -9,6 +9,7 @@ _EXPORTS = {
     "estimate_Hamming_distance_weights": "mi", "perform_MI_computation": "mi",
     "snpdat_to_fa": "output", "generate_Links_SNPS_fasta": "output", "write_output_for_gwes_explorer": "output",
     "read_TopHits": "output", "read_AnnotatedLinks": "output",
+    "perform_snpEff_annotations": "annotate",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -19,7 +19,7 @@ LDW_ERR_ARG, LDW_ERR_HIP, LDW_ERR_STATE, LDW_ERR_NOGPU, LDW_ERR_SIZE = 1, 2, 3, 
 QUIRK_REFERENCE, QUIRK_INTENDED = 0, 1
 MI_SR_ROWS_STAY = 1
 ENGINE_MFMA, ENGINE_HIST, ENGINE_HIST_STATES = 0, 1, 2
-COL_INT32, COL_INT64, COL_DOUBLE = 0, 1, 2
+COL_INT32, COL_INT64, COL_DOUBLE, COL_STR = 0, 1, 2, 3
 
 
 class LdwError(RuntimeError):
@@ -113,6 +113,10 @@ _SIGS_API = {
     "ldw_lr_stream_begin": (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int]),
     "ldw_lr_stream_end": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "ldw_write_alignment": (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int, _p, _i64, C.c_char_p, _i64, _i64, C.POINTER(_i64)]),
+    "ldw_write_table_tsv_str": (C.c_int, [C.c_char_p, C.c_int, _i64, C.c_int, _p, _p, _p, _p, _p, _i64, C.c_int, C.POINTER(_i64)]),
+    "ldw_annot_snps": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p]),
+    "ldw_annot_map": (C.c_int, [_p, _p, _p, _i64, _p, _i64, _p, C.POINTER(_i64), C.POINTER(_i64)]),
+    "ldw_annot_links": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, C.POINTER(_i64)]),
     "ldw_compare_to_row": (C.c_int, [_p, _i64, _i64, _p, _i64, _p]),
     "ldw_vec_pos_match": (C.c_int, [_p, _i64, _p, _i64, _p]),
     "ldw_compare_triplet": (C.c_int, [_p, _p, _i64, C.c_double, C.POINTER(C.c_int)]),

@@ -194,6 +194,9 @@ struct ldw_ctx {
     ldw::DevBuf cds_keep;        // uint32 [cds_L] positions in ascending order, int32 [cds_L] their SNP index: left by ldw_cds_variation for ldw_cds_paint
     ldw::DevBuf cds_work;        // per-call working memory of both
     int64_t cds_L = 0;           // SNPs of the last ldw_cds_variation (0: none yet)
+    ldw::DevBuf annot_keep;      // int32 [2][annot_n] annotation row of every link end: left by ldw_annot_map for ldw_annot_links
+    ldw::DevBuf annot_work;      // per-call working memory of ldw_annot_map / ldw_annot_links / ldw_annot_snps
+    int64_t annot_n = -1, annot_rows = 0;   // links and annotation rows of the last ldw_annot_map (-1: none yet)
     ldw::DevBuf pfix_state;      // int64 [L][5]: fixed-point marginal of each state (histogram engine)
     std::vector<int32_t> h_row0;
     std::vector<uint32_t> h_slot_meta;

@@ -162,8 +162,11 @@ inline char *fmt_int(char *p, long long v) {
 }
 
 struct Col {
-    int kind;          // LDW_COL_INT32 / INT64 / DOUBLE
+    int kind;          // LDW_COL_INT32 / INT64 / DOUBLE / STR
     const void *data;
+    const char *blob = nullptr;     // LDW_COL_STR: row i prints blob[offs[data[i]] .. offs[data[i] + 1]) (offs: this column's slice of the table)
+    const int64_t *offs = nullptr;
+    size_t maxlen = 0;              // ... and no string of that slice is longer
 };
 
 // default worker count: the machine's hardware threads, at most 16 (a container's CPU share is usually far below the host's count,
@@ -276,7 +279,9 @@ int write_rows(const char *path, int append, int64_t nrows, const std::vector<Co
     if (nrows > 0) {
         // one chunk per worker and round: the whole share of a worker when its buffer stays below 64 MB (one barrier for a table of a
         // million rows instead of eight: the barrier waits were 3 of the 13 ms), at least 8192 rows
-        const size_t row_max = cols.size() * 41 + 2;
+        size_t row_max = cols.size() * 41 + 2;
+        for (const Col &cl : cols)   // (a string column: room for its table's longest string)
+            if (cl.kind == LDW_COL_STR) row_max += cl.maxlen;
         int nt = default_threads(nthreads);
         nt = (int)std::min<int64_t>(nt, (nrows + 8191) / 8192);
         if (nt < 1) nt = 1;
@@ -315,6 +320,12 @@ int write_rows(const char *path, int append, int64_t nrows, const std::vector<Co
                             const Col &cl = cols[k];
                             if (cl.kind == LDW_COL_DOUBLE) p = fmt_double(p, static_cast<const double *>(cl.data)[i]);
                             else if (cl.kind == LDW_COL_INT32) p = fmt_int(p, static_cast<const int32_t *>(cl.data)[i]);
+                            else if (cl.kind == LDW_COL_STR) {
+                                const int32_t j = static_cast<const int32_t *>(cl.data)[i];
+                                const size_t nb = (size_t)(cl.offs[j + 1] - cl.offs[j]);
+                                memcpy(p, cl.blob + cl.offs[j], nb);
+                                p += nb;
+                            }
                             else p = fmt_int(p, static_cast<const int64_t *>(cl.data)[i]);
                         }
                         *p++ = '\n';
@@ -399,6 +410,37 @@ int ldw_write_table_tsv(const char *path, int append, int64_t nrows, int ncols, 
                     col_kind[k]);
         LDW_REQUIRE(cols[k] || nrows == 0, LDW_ERR_ARG, "ldw_write_table_tsv: column %d is null", k);
         cc[(size_t)k] = Col{col_kind[k], cols[k]};
+    }
+    return write_rows(path, append, nrows, cc, nthreads, bytes_out);
+}
+
+int ldw_write_table_tsv_str(const char *path, int append, int64_t nrows, int ncols, const int32_t *col_kind, const void *const *cols,
+                            const int64_t *col_base, const char *blob, const int64_t *offs, int64_t nstr, int nthreads, int64_t *bytes_out) {
+    LDW_REQUIRE(path && nrows >= 0 && ncols > 0 && ncols <= 64 && col_kind && cols && nstr >= 0 && (nstr == 0 || (blob && offs && col_base)),
+                LDW_ERR_ARG, "ldw_write_table_tsv_str: bad argument");
+    for (int64_t j = 0; j < nstr; ++j)
+        LDW_REQUIRE(offs[j] >= 0 && offs[j + 1] >= offs[j], LDW_ERR_ARG, "ldw_write_table_tsv_str: string offsets decrease at %lld", (long long)j);
+    std::vector<Col> cc((size_t)ncols);
+    for (int k = 0; k < ncols; ++k) {
+        LDW_REQUIRE(col_kind[k] >= LDW_COL_INT32 && col_kind[k] <= LDW_COL_STR, LDW_ERR_ARG, "ldw_write_table_tsv_str: column %d has kind %d", k,
+                    col_kind[k]);
+        LDW_REQUIRE(cols[k] || nrows == 0, LDW_ERR_ARG, "ldw_write_table_tsv_str: column %d is null", k);
+        cc[(size_t)k] = Col{col_kind[k], cols[k]};
+        if (col_kind[k] != LDW_COL_STR) continue;
+        const int64_t b = col_base[k];
+        LDW_REQUIRE(b >= 0 && b <= nstr, LDW_ERR_ARG, "ldw_write_table_tsv_str: column %d has base %lld outside 0..%lld", k, (long long)b, (long long)nstr);
+        const int32_t *ix = static_cast<const int32_t *>(cols[k]);
+        int64_t hi = -1;
+        for (int64_t i = 0; i < nrows; ++i) {
+            LDW_REQUIRE(ix[i] >= 0 && b + ix[i] < nstr, LDW_ERR_ARG, "ldw_write_table_tsv_str: column %d row %lld names string %lld of %lld", k,
+                        (long long)i, (long long)(b + ix[i]), (long long)nstr);
+            hi = std::max<int64_t>(hi, ix[i]);
+        }
+        size_t mx = 0;
+        for (int64_t j = b; j <= b + hi; ++j) mx = std::max(mx, (size_t)(offs[j + 1] - offs[j]));
+        cc[(size_t)k].blob = blob;
+        cc[(size_t)k].offs = offs + b;
+        cc[(size_t)k].maxlen = mx;
     }
     return write_rows(path, append, nrows, cc, nthreads, bytes_out);
 }

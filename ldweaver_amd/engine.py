@@ -9,6 +9,8 @@ import numpy as np
 
 from . import _lib as L
 
+ANNOT_REC = 12   # LDW_ANNOT_REC: int32 words of one k_annot_snp record
+
 
 def fasta_check(code: int, path):
     """L.check for the FASTA feeder's entries: its two input errors become the ValueErrors ``snpdat.read_fasta`` raises, an unreadable
@@ -373,6 +375,48 @@ class Engine:
         L.check(L.lib().ldw_write_alignment(self._ctx, os.fsencode(path), int(bool(append)), int(format), L.ptr(idx), len(idx), blob, len(blob),
                                             int(chunk_bytes), C.byref(nb)))
         return int(nb.value)
+
+    def annot_snps(self, ref, seg, strand, pos, alt_mask) -> np.ndarray:
+        """The coding-effect record of every SNP ``pos`` (1-based) with the A/C/G/T alleles of ``alt_mask`` on the CDS features ``seg`` (nseg x 3:
+        lo, hi, feature; each feature's segments contiguous, in coding order) of strands ``strand`` (+1 / -1) over the reference ``ref``
+        (uint8 characters), by k_annot_snp (ldw_annot_snps): int32 [n, LDW_ANNOT_REC]."""
+        r = L.as_c(ref, np.uint8).ravel()
+        sg = L.as_c(seg, np.int32).reshape(-1, 3)
+        sd = L.as_c(strand, np.int8).ravel()
+        p = L.as_c(pos, np.int32).ravel()
+        am = L.as_c(alt_mask, np.uint8).ravel()
+        if p.shape != am.shape:
+            raise ValueError("pos and alt_mask differ in length")
+        out = np.empty((len(p), ANNOT_REC), dtype=np.int32)
+        L.check(L.lib().ldw_annot_snps(self._ctx, L.ptr(r), len(r), L.ptr(sg) if len(sg) else None, len(sg), L.ptr(sd) if len(sd) else None, len(sd),
+                                       L.ptr(p), L.ptr(am), len(p), L.ptr(out)))
+        return out
+
+    def annot_map(self, pos1, pos2, POS):
+        """Every link end to its SNP (ldw_annot_map): (SNP index of every annotation row = the distinct link positions ascending, the first
+        link end that matches no SNP or several: index into concat(pos1, pos2), or -1).  The rows of the link ends stay on the device."""
+        a, b = L.as_c(pos1, np.float64).ravel(), L.as_c(pos2, np.float64).ravel()
+        P = L.as_c(POS, np.int32).ravel()
+        if a.shape != b.shape:
+            raise ValueError("pos1 and pos2 differ in length")
+        snp = np.empty(max(len(P), 1), dtype=np.int32)
+        rows, bad = C.c_int64(0), C.c_int64(-1)
+        L.check(L.lib().ldw_annot_map(self._ctx, L.ptr(a), L.ptr(b), len(a), L.ptr(P), len(P), L.ptr(snp), C.byref(rows), C.byref(bad)))
+        return snp[:rows.value].copy(), int(bad.value)
+
+    def annot_links(self, key, aracne, code, cds_id, max_tophits: int):
+        """The links of the last ``annot_map`` in order(key, decreasing = TRUE) with the join and detect_top_hits on the device
+        (ldw_annot_links): (perm int64, r1 int32, r2 int32, pair int8 = 3 code1 + code2, top int64: sorted indices of the first max_tophits
+        top hits)."""
+        k, ar = L.as_c(key, np.float64).ravel(), L.as_c(aracne, np.float64).ravel()
+        cd, ci = L.as_c(code, np.int8).ravel(), L.as_c(cds_id, np.int32).ravel()
+        n = len(k)
+        perm, r1, r2 = np.empty(n, np.int64), np.empty(n, np.int32), np.empty(n, np.int32)
+        pair, top = np.empty(n, np.int8), np.empty(max(min(int(max_tophits), n), 1), np.int64)
+        nt = C.c_int64(0)
+        L.check(L.lib().ldw_annot_links(self._ctx, L.ptr(k), L.ptr(ar), n, L.ptr(cd) if len(cd) else None, L.ptr(ci) if len(ci) else None, len(cd),
+                                        int(max_tophits), L.ptr(perm), L.ptr(r1), L.ptr(r2), L.ptr(pair), L.ptr(top), C.byref(nt)))
+        return perm, r1, r2, pair, top[:nt.value].copy()
 
     def state_counts(self) -> np.ndarray:
         out = np.empty((self.L, 5), dtype=np.int32)

@@ -27,6 +27,7 @@ class GenBankRecord:
     accession: str = ""
     version: str = ""
     gbk_path: str | None = None
+    feature: np.ndarray | None = None   # int64 per cds row: its feature (rows of one join() / order() share it); None: every row its own
 
 
 def read_genbank(gbk_path) -> GenBankRecord:
@@ -58,7 +59,7 @@ def read_genbank(gbk_path) -> GenBankRecord:
     cds = pd.DataFrame({"seqnames": [seqname] * n, "start": start, "end": end, "strand": np.where(strand < 0, "-", "+").astype(object),
                         "type": ["CDS"] * n, "locus_tag": tags[feat, 0], "gene": tags[feat, 1], "product": tags[feat, 2]})
     return GenBankRecord(cds=cds, sequence=seq, seqname=seqname, g=int(g.value), locus=locus, accession=accession, version=version,
-                         gbk_path=str(gbk_path))
+                         gbk_path=str(gbk_path), feature=feat)
 
 
 def parse_genbank_file(gbk_path, g=None, length_check=True) -> dict:

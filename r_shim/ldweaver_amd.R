@@ -186,6 +186,26 @@ ldwamd_write_alignment <- function(snp.dat, aln_path, snps_idx, pos, format = "f
   }
 }
 
+# The device halves of perform_snpEff_annotations (R/SnpEffAnnotations.R:29-103; rule table DESIGN.md 19).  ldwamd_annot_snps: one 12-word
+# k_annot_snp record per SNP (columns) from the CDS segments (lo, hi, 1-based feature, each feature's segments in coding order) and the
+# reference string.  ldwamd_annot_links: links_df ordered as add_annotations_to_links orders it, the annotation rows of both ends and the
+# top hits of detect_top_hits (code per annotation row: "sy" "ns" "ig"; genreg: the cds strings, NA allowed).
+ldwamd_annot_snps <- function(ref_string, seg_lo, seg_hi, seg_feature, strand, pos, alt_mask) {
+  .Call("ldwamd_annot_snps", ref_string, as.integer(seg_lo), as.integer(seg_hi), as.integer(seg_feature - 1L), as.integer(strand),
+        as.integer(pos), as.integer(alt_mask))
+}
+ldwamd_annot_links <- function(links_df, snp.dat, code, genreg, links_type = "SR", max_tophits = 250) {
+  m <- .Call("ldwamd_annot_map", as.numeric(links_df$pos1), as.numeric(links_df$pos2), as.integer(snp.dat$POS))
+  if (m[[2]] >= 0) stop(paste("a link position matches no SNP or several:", m[[2]] + 1))
+  key <- if (links_type == "SR") links_df$srp_max else links_df$MI
+  cds_id <- match(genreg, unique(genreg[!is.na(genreg)])) - 1L
+  cds_id[is.na(cds_id)] <- -1L
+  r <- .Call("ldwamd_annot_links", as.numeric(key), as.numeric(links_df$ARACNE), match(code, c("sy", "ns", "ig")) - 1L, as.integer(cds_id),
+             as.numeric(max_tophits))
+  list(snps = m[[1]] + 1L, order = r[[1]], row1 = r[[2]] + 1L, row2 = r[[3]] + 1L,
+       links = c("syXsy", "syXns", "syXig", "nsXsy", "nsXns", "nsXig", "igXsy", "igXns", "igXig")[r[[4]] + 1L], top = r[[5]])
+}
+
 # Numeric core of genomewide_LDMap (R/LDSummaryPlot.R:55-109): the matrix heatmap3 is given.
 genomewide_LDMap_device <- function(reducer = NULL, from = NULL, to = NULL) {
   .Call("ldwamd_ldmap", if (is.null(reducer)) 0L else as.integer(round(reducer)), if (is.null(from)) 0L else as.integer(round(from)),

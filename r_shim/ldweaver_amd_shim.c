@@ -456,6 +456,79 @@ SEXP ldwamd_write_alignment(SEXP path, SEXP append, SEXP format, SEXP idx, SEXP 
     return ScalarReal((double)bytes);
 }
 
+/* perform_snpEff_annotations (R/SnpEffAnnotations.R:29-103), native predictor: ref a one-string reference, segments lo / hi / feature
+ * (INTSXP; feature 0-based, each feature's segments contiguous in coding order), strand INTSXP +1 / -1 per feature, pos / alt_mask INTSXP per
+ * SNP.  Returns an INTSXP 12 x n matrix of k_annot_snp records. */
+SEXP ldwamd_annot_snps(SEXP ref, SEXP lo, SEXP hi, SEXP feat, SEXP strand, SEXP pos, SEXP alt_mask) {
+    ldw_ctx *c = ctx_or_stop();
+    const char *r = CHAR(STRING_ELT(ref, 0));
+    const R_xlen_t nseg = XLENGTH(lo), nf = XLENGTH(strand), n = XLENGTH(pos);
+    int32_t *seg = (int32_t *)R_alloc((size_t)(3 * nseg + 1), sizeof(int32_t));
+    int8_t *sd = (int8_t *)R_alloc((size_t)(nf + 1), 1);
+    uint8_t *am = (uint8_t *)R_alloc((size_t)(n + 1), 1);
+    for (R_xlen_t s = 0; s < nseg; ++s) {
+        seg[3 * s] = INTEGER(lo)[s];
+        seg[3 * s + 1] = INTEGER(hi)[s];
+        seg[3 * s + 2] = INTEGER(feat)[s];
+    }
+    for (R_xlen_t f = 0; f < nf; ++f) sd[f] = (int8_t)INTEGER(strand)[f];
+    for (R_xlen_t i = 0; i < n; ++i) am[i] = (uint8_t)INTEGER(alt_mask)[i];
+    SEXP out = PROTECT(allocMatrix(INTSXP, LDW_ANNOT_REC, (int)n));
+    CHK(ldw_annot_snps(c, r, (int64_t)strlen(r), seg, (int64_t)nseg, sd, (int64_t)nf, (const int32_t *)INTEGER(pos), am, (int64_t)n,
+                       (int32_t *)INTEGER(out)));
+    UNPROTECT(1);
+    return out;
+}
+
+/* add_annotations_to_links' lookups (R/SnpEffAnnotations.R:336-347): the links' pos1 / pos2 (REALSXP) against snp.dat$POS (INTSXP).
+ * Returns list(snp = 0-based SNP of every annotation row, the sorted distinct link positions; bad = the first 0-based end with no or several
+ * SNPs, or -1). */
+SEXP ldwamd_annot_map(SEXP pos1, SEXP pos2, SEXP POS) {
+    ldw_ctx *c = ctx_or_stop();
+    const R_xlen_t L = XLENGTH(POS);
+    int32_t *snp = (int32_t *)R_alloc((size_t)L + 1, sizeof(int32_t));
+    int64_t rows = 0, bad = -1;
+    CHK(ldw_annot_map(c, REAL(pos1), REAL(pos2), (int64_t)XLENGTH(pos1), (const int32_t *)INTEGER(POS), (int64_t)L, snp, &rows, &bad));
+    SEXP out = PROTECT(allocVector(VECSXP, 2));
+    SEXP s = PROTECT(allocVector(INTSXP, (R_xlen_t)rows));
+    memcpy(INTEGER(s), snp, (size_t)rows * sizeof(int32_t));
+    SET_VECTOR_ELT(out, 0, s);
+    SET_VECTOR_ELT(out, 1, ScalarReal((double)bad));
+    UNPROTECT(2);
+    return out;
+}
+
+/* the order, join and detect_top_hits (R/SnpEffAnnotations.R:366, :384, :393-403) of the links of the last ldwamd_annot_map: key = srp_max (SR)
+ * or MI (LR), aracne REALSXP, code (0 sy, 1 ns, 2 ig) and cds_id (-1 for NA) INTSXP per annotation row.  Returns list(perm (1-based source
+ * rows, REALSXP), r1, r2 (0-based rows), pair (3 code1 + code2), top (1-based sorted rows of the top hits)). */
+SEXP ldwamd_annot_links(SEXP key, SEXP aracne, SEXP code, SEXP cds_id, SEXP max_tophits) {
+    ldw_ctx *c = ctx_or_stop();
+    const R_xlen_t n = XLENGTH(key), rows = XLENGTH(code);
+    const int64_t kmax = (int64_t)asReal(max_tophits);
+    int8_t *cd = (int8_t *)R_alloc((size_t)rows + 1, 1);
+    for (R_xlen_t r = 0; r < rows; ++r) cd[r] = (int8_t)INTEGER(code)[r];
+    int64_t *perm = (int64_t *)R_alloc((size_t)n + 1, sizeof(int64_t)), *top = (int64_t *)R_alloc((size_t)(kmax < n ? kmax : n) + 1, sizeof(int64_t));
+    int8_t *pair = (int8_t *)R_alloc((size_t)n + 1, 1);
+    SEXP out = PROTECT(allocVector(VECSXP, 5));
+    SEXP r1 = PROTECT(allocVector(INTSXP, n)), r2 = PROTECT(allocVector(INTSXP, n));
+    int64_t nt = 0;
+    CHK(ldw_annot_links(c, REAL(key), REAL(aracne), (int64_t)n, cd, (const int32_t *)INTEGER(cds_id), (int64_t)rows, kmax, perm,
+                        (int32_t *)INTEGER(r1), (int32_t *)INTEGER(r2), pair, top, &nt));
+    SEXP p = PROTECT(allocVector(REALSXP, n)), pr = PROTECT(allocVector(INTSXP, n)), tp = PROTECT(allocVector(REALSXP, (R_xlen_t)nt));
+    for (R_xlen_t i = 0; i < n; ++i) {
+        REAL(p)[i] = (double)perm[i] + 1;
+        INTEGER(pr)[i] = pair[i];
+    }
+    for (int64_t i = 0; i < nt; ++i) REAL(tp)[i] = (double)top[i] + 1;
+    SET_VECTOR_ELT(out, 0, p);
+    SET_VECTOR_ELT(out, 1, r1);
+    SET_VECTOR_ELT(out, 2, r2);
+    SET_VECTOR_ELT(out, 3, pr);
+    SET_VECTOR_ELT(out, 4, tp);
+    UNPROTECT(6);
+    return out;
+}
+
 /* any numeric data.frame's columns (INTSXP / REALSXP / LGLSXP-as-int) by the same writer; cols: a list of equally long vectors */
 SEXP ldwamd_write_table_tsv(SEXP cols, SEXP path) {
     const int nc = (int)XLENGTH(cols);
@@ -509,6 +582,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"ldwamd_lr_stream_end", (DL_FUNC)&ldwamd_lr_stream_end, 0},
     {"ldwamd_write_table_tsv", (DL_FUNC)&ldwamd_write_table_tsv, 2},
     {"ldwamd_write_alignment", (DL_FUNC)&ldwamd_write_alignment, 5},
+    {"ldwamd_annot_snps", (DL_FUNC)&ldwamd_annot_snps, 7},
+    {"ldwamd_annot_map", (DL_FUNC)&ldwamd_annot_map, 3},
+    {"ldwamd_annot_links", (DL_FUNC)&ldwamd_annot_links, 5},
     {NULL, NULL, 0}};
 
 void R_init_ldweaver_amd_shim(DllInfo *dll) {
