@@ -642,6 +642,8 @@ int ldw_ctx_destroy(ldw_ctx *c) {
     if (c->pin_fetch) (void)hipHostFree(c->pin_fetch);
     if (c->pin_lrc) (void)hipHostFree(c->pin_lrc);
     if (c->ev_lrc) (void)hipEventDestroy(c->ev_lrc);
+    for (auto &e : c->ev_probe)
+        if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_pool) (void)hipEventDestroy(e);
     for (auto &e : c->lr_ev)
         if (e) (void)hipEventDestroy(e);

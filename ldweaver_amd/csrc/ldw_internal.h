@@ -254,6 +254,7 @@ struct ldw_ctx {
     bool up_recorded[LDW_NSLOT] = {};    // ev_up[slot] has been recorded at least once
     void *pin_pick[LDW_NSLOT] = {};   // pinned landing zone of the per-block PickOut, one per slot
     hipEvent_t ev_pick[LDW_NSLOT] = {};
+    hipEvent_t ev_probe[2] = {};      // one per cold-start probe of a pass: the calling thread waits for the probe it needs, not for the stream
     void *pin_lrc = nullptr;             // pinned copy of the running long-range row count
     hipEvent_t ev_lrc = nullptr;
     bool lrc_recorded = false;

@@ -41,6 +41,7 @@
 #include "ldw_epi.h"
 #include <condition_variable>
 #include <mutex>
+#include <future>
 #include <thread>
 
 #include "ldw_apx.h"
@@ -74,6 +75,7 @@ int ensure_streams(ldw_ctx *c) {
             LDW_HIP(hipHostMalloc(&c->pin_pick[k], (size_t)LDW_SPAN_MAX * PICK_STRIDE + 64, hipHostMallocDefault));
         }
         LDW_HIP(hipEventCreateWithFlags(&c->ev_lrc, hipEventDisableTiming));
+        for (auto &e : c->ev_probe) LDW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         LDW_HIP(hipHostMalloc(&c->pin_lrc, 64, hipHostMallocDefault));
         {   // the block-wide kernels (GEMM, screens) fill the chip; the tail of the previous block on the main stream is a chain of
             // small latency-bound kernels that should be dispatched as soon as they are ready: lowest priority for this stream
@@ -375,11 +377,12 @@ static bool span_candidate(const ldw_ctx *c, const int32_t *b, const ldw_mi_para
     const double pf_min = P[(size_t)fs - 1], pf_max = P[(size_t)fe - 1], pt_min = P[(size_t)ts - 1], pt_max = P[(size_t)te - 1];
     return pt_min - pf_max > p->sr_dist && pf_min + c->g - pt_max > p->sr_dist;
 }
-// what the whole pass must offer (checked once, after the cold-start probes: a positive guess for off-diagonal blocks exists)
-static bool spans_possible(const ldw_ctx *c, const ldw_mi_params *p) {
+// what the whole pass must offer (checked once, when the pass is planned: a positive guess for off-diagonal blocks exists, or — guess_expected —
+// the cold-start probe of the pass is about to sample one)
+static bool spans_possible(const ldw_ctx *c, const ldw_mi_params *p, bool guess_expected) {
     static const bool env_off = getenv("LDW_NO_SPAN") != nullptr;
     return c->span_on && !env_off && c->span_max >= 2 && c->prune && c->engine == LDW_ENGINE_MFMA && c->apx_ok && c->path_mode != 1 && c->screen == 1 &&
-           !p->sr_only && speculation_pays(c, p) && c->pos_sorted && c->spec_B_next[0] > 0 &&
+           !p->sr_only && speculation_pays(c, p) && c->pos_sorted && (c->spec_B_next[0] > 0 || guess_expected) &&
            (p->quirk_mode != LDW_QUIRK_REFERENCE || c->r_min >= 2.0);
 }
 struct WorkItem {
@@ -412,6 +415,164 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
         for (int32_t k = ts; k <= te; ++k) ti[k - ts] = k - 1;
         return LDW_OK;
     };
+    // Software pipeline, three ITEMS deep on the host (an item = one block, or a span of consecutive long-range-only blocks of one block
+    // row: r04): item i's epilogue chain is submitted (main stream), then at once the block-wide pass of item i+1 (GEMM stream; prepared
+    // earlier), and only then the host waits for item i's pick(s).
+    // r03: the lists of an item are built by a HELPER THREAD that runs ahead of the submitting thread (prep_block is pure host work into the
+    // slot's pinned staging buffer: 0.45 ms per 10k x 10k block — once the GPU side of a block had come down to 0.5 ms it was the loop's
+    // critical path).  Hand-over through counters under one mutex: item k may be prepared once item k - RING is finished (its ring entry
+    // is free) and item k - LDW_NSLOT has been submitted (the slot's staging buffer then belongs to an upload the helper waits for: ev_up).
+    // The plan is complete before the helpers start (below); the GEMM stream runs up to LDW_NSLOT - 1 = 2 items ahead of the item the main
+    // stream evaluates.
+    constexpr int RING = 8;
+    HostBlock hb[RING];
+    static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
+    double th[5] = {0, 0, 0, 0, 0};
+    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    // The plan: items in block order, made BEFORE the helpers start and before the cold-start probes are queued, so that the list building of
+    // the first span (~3 ms for eight blocks, against 1.3 ms of GPU work in the diagonal block in front of it) runs beside the probes and
+    // the first item instead of after them.  Whether spans may form depends on a positive guess for off-diagonal blocks: on a cold pass the
+    // plan ASSUMES the off-diagonal probe below will deliver one (it is known here whether that probe will be attempted).  A probe that then
+    // yields no guess costs time, never a row: the spans planned on it fall back as any span whose guess has gone does (submit_a: span_alone).
+    static const bool probe_on = getenv("LDW_NO_PROBE") == nullptr;
+    const bool probes_wanted = probe_on && !p->sr_only && c->pos_sorted && speculation_pays(c, p);
+    bool probe_expected = false;   // an off-diagonal guess is missing and the first off-diagonal block is large enough to be sampled
+    if (probes_wanted && c->spec_B_next[0] < 0)
+        for (int64_t b = 0; b < nblocks; ++b) {
+            if (blocks[b * 4 + 0] == blocks[b * 4 + 2] && blocks[b * 4 + 1] == blocks[b * 4 + 3]) continue;
+            probe_expected = (int64_t)(blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1) * (int64_t)(blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1) >= PROBE_MIN_PAIRS;
+            break;
+        }
+    std::vector<WorkItem> items;
+    {   // consecutive candidates of one block row, to sides ascending, form a span (at most span_max blocks,
+        // nf x nt below the 32-bit index limit of the unit lists, the int32 block below ~6 GB)
+        const bool spans = spans_possible(c, p, probe_expected);
+        for (int64_t b = 0; b < nblocks;) {
+            int n = 1;
+            if (spans && span_candidate(c, blocks + b * 4, p)) {
+                const int64_t nf = blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1;
+                int64_t nt_tot = blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1;
+                static const int env_max = [] { const char *e = getenv("LDW_SPAN_MAX"); return e ? atoi(e) : 0; }();   // (A/B measurements)
+                const int nmax = std::min<int>(env_max >= 1 ? env_max : c->span_max, LDW_SPAN_MAX);
+                while (n < nmax && b + n < nblocks && span_candidate(c, blocks + (b + n) * 4, p) && blocks[(b + n) * 4 + 0] == blocks[b * 4 + 0] &&
+                       blocks[(b + n) * 4 + 1] == blocks[b * 4 + 1] && blocks[(b + n) * 4 + 2] > blocks[(b + n - 1) * 4 + 3]) {
+                    const int64_t nt_k = blocks[(b + n) * 4 + 3] - blocks[(b + n) * 4 + 2] + 1;
+                    if (nf * (nt_tot + nt_k) >= 1500000000LL || (nt_tot + nt_k) > 900000) break;
+                    nt_tot += nt_k;
+                    ++n;
+                }
+            }
+            items.push_back(WorkItem{b, n});
+            b += n;
+        }
+        c->early_sr = spans;
+    }
+    const int64_t nitems = (int64_t)items.size();
+    struct Shared {
+        std::mutex m;
+        std::condition_variable cv;
+        int64_t n_sub = 0, n_done = 0, next = 0;   // next: the item the next free helper takes
+        std::vector<uint8_t> prepped;               // per item (helpers finish out of order)
+        int rc = LDW_OK;
+        int64_t bad = INT64_MAX;             // the first item whose preparation failed (items before it are still good: r05)
+        bool stop = false;
+        std::string err;
+    } sh;
+    sh.prepped.assign((size_t)nblocks + 1, 0);
+    // r04: TWO helpers (a span of eight blocks took ~3 ms of list building, a diagonal block in front of it gives the
+    // GPU 1.3 ms of work: one helper left the GEMM stream waiting).  Each takes the next item; items k, k+1, k+2 use different slots.
+    // Now one helper per slot: with the whole plan known at the start, the first three items — the diagonal block, the corner block next
+    // to it and the first span (1.2, 0.9 and 2 ms of list building) — are prepared side by side, where the span used to start behind the
+    // corner block and the GEMM stream stood idle for 0.4-0.9 ms in front of it (profiles/cold_start_timeline.txt).
+    auto worker = [&]() {
+        (void)hipSetDevice(c->device);
+        std::vector<int32_t> wfi, wti;   // this helper's own index lists
+        for (;;) {
+            WorkItem it{0, 0};
+            int64_t k = 0;
+            {
+                std::unique_lock<std::mutex> lk(sh.m);
+                sh.cv.wait(lk, [&] {
+                    if (sh.stop || sh.next >= nitems) return true;   // (nothing left: leave)
+                    return sh.next < sh.n_done + RING && sh.next < sh.n_sub + LDW_NSLOT;
+                });
+                if (sh.stop || sh.next >= nitems) return;
+                k = sh.next++;
+                it = items[(size_t)k];
+            }
+            int rc = LDW_OK;
+            try {   // (prep_block allocates a dozen std::vectors: an exception on this thread must come back as an error code, not std::terminate)
+                const int32_t fs = blocks[it.b0 * 4 + 0], fe = blocks[it.b0 * 4 + 1];
+                bool ok = fs >= 1 && fe >= fs && fe <= c->L;
+                SpanPlan spn;
+                wti.clear();
+                for (int q = 0; q < it.nseg && ok; ++q) {
+                    const int32_t ts = blocks[(it.b0 + q) * 4 + 2], te = blocks[(it.b0 + q) * 4 + 3];
+                    ok = ts >= 1 && te >= ts && te <= c->L;
+                    if (!ok) break;
+                    spn.start[q] = (int32_t)wti.size();
+                    spn.nt[q] = te - ts + 1;
+                    for (int32_t x = ts; x <= te; ++x) wti.push_back(x - 1);
+                }
+                spn.nseg = it.nseg;
+                if (!ok) {
+                    set_error("block %lld = (%d,%d,%d,%d) outside 1..%lld", (long long)it.b0, fs, fe, blocks[it.b0 * 4 + 2], blocks[it.b0 * 4 + 3], (long long)c->L);
+                    rc = LDW_ERR_ARG;
+                } else {
+                    wfi.resize((size_t)(fe - fs + 1));
+                    for (int32_t q = fs; q <= fe; ++q) wfi[q - fs] = q - 1;
+                    const int slot = (int)(k % LDW_NSLOT);
+                    if (c->up_recorded[slot] && hipEventSynchronize(c->ev_up[slot]) != hipSuccess) {   // the staging buffer of this slot has been uploaded
+                        set_error("prep: hipEventSynchronize failed");
+                        rc = LDW_ERR_HIP;
+                    }
+                    HostBlock &h = hb[k % RING];
+                    if (rc == LDW_OK) rc = prep_block(c, wfi.data(), (int64_t)wfi.size(), wti.data(), (int64_t)wti.size(), p, slot, it.b0, h, it.nseg > 1 ? &spn : nullptr);
+                    if (rc == LDW_OK && it.nseg > 1) {
+                        h.span_from = wfi;
+                        h.span_to = wti;
+                    }
+                }
+            } catch (const std::exception &e) {
+                set_error("preparing block %lld: %s", (long long)it.b0, e.what());
+                rc = LDW_ERR_HIP;
+            } catch (...) {
+                set_error("preparing block %lld: unknown exception", (long long)it.b0);
+                rc = LDW_ERR_HIP;
+            }
+            std::lock_guard<std::mutex> lk(sh.m);
+            if (rc != LDW_OK) {
+                if (sh.rc == LDW_OK || k < sh.bad) {
+                    sh.rc = rc;
+                    sh.err = ldw_last_error();
+                }
+                sh.bad = std::min(sh.bad, k);
+                sh.stop = true;
+            } else {
+                sh.prepped[(size_t)k] = 1;
+            }
+            sh.cv.notify_all();
+            if (rc != LDW_OK) return;
+        }
+    };
+    constexpr int n_helpers = LDW_NSLOT;
+    std::thread helpers[n_helpers];
+    for (int i = 0; i < n_helpers; ++i) helpers[i] = std::thread(worker);
+    struct Joiner {   // every way out of this function stops and joins the helpers
+        Shared &sh;
+        std::thread *t;
+        int n;
+        ~Joiner() {
+            {
+                std::lock_guard<std::mutex> lk(sh.m);
+                sh.stop = true;
+            }
+            sh.cv.notify_all();
+            for (int i = 0; i < n; ++i)
+                if (t[i].joinable()) t[i].join();
+        }
+    } joiner{sh, helpers, n_helpers};
+    // (the helpers are at work: the table sizing below runs beside the list building of the first items, which is what the GPU waits for)
     if (p->keep_sr && c->pos_sorted && 2 * p->sr_dist < c->g) {
         // Size the short-range table ONCE: geometric growth re-copies up to a gigabyte and synchronises both streams every time (ten times in
         // the first pass of C4), and would double-buffer tens of GB at C5.  The blocks of a pass hold every unordered SNP pair at most once,
@@ -473,197 +634,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
         if (want < 4e9)
             if (int rc = ensure_links_capacity(c, c->n_sr, (int64_t)want)) return rc;
     }
-    // Software pipeline, three ITEMS deep on the host (an item = one block, or a span of consecutive long-range-only blocks of one block
-    // row: r04): item i's epilogue chain is submitted (main stream), then at once the block-wide pass of item i+1 (GEMM stream; prepared
-    // earlier), and only then the host waits for item i's pick(s).
-    // r03: the lists of an item are built by a HELPER THREAD that runs ahead of the submitting thread (prep_block is pure host work into the
-    // slot's pinned staging buffer: 0.45 ms per 10k x 10k block — once the GPU side of a block had come down to 0.5 ms it was the loop's
-    // critical path).  Hand-over through counters under one mutex: item k may be prepared once item k - RING is finished (its ring entry
-    // is free), item k - LDW_NSLOT has been submitted (the slot's staging buffer then belongs to an upload the helper waits for: ev_up) and
-    // the plan covers it (n_planned: the items behind the leading blocks are only known after the cold-start probes — whether spans may
-    // form depends on a guess existing); the GEMM stream runs up to LDW_NSLOT - 1 = 2 items ahead of the item the main stream evaluates.
-    constexpr int RING = 8;
-    HostBlock hb[RING];
-    static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
-    double th[5] = {0, 0, 0, 0, 0};
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    // the plan: items in block order.  Before the probes only the leading run of blocks that can never be part of a span is planned.
-    std::vector<WorkItem> items;
-    std::vector<uint8_t> cand((size_t)nblocks, 0);
-    for (int64_t b = 0; b < nblocks; ++b) cand[(size_t)b] = (uint8_t)span_candidate(c, blocks + b * 4, p);
-    int64_t lead = 0;
-    while (lead < nblocks && !cand[(size_t)lead]) ++lead;
-    for (int64_t b = 0; b < lead; ++b) items.push_back(WorkItem{b, 1});
-    struct Shared {
-        std::mutex m;
-        std::condition_variable cv;
-        int64_t n_sub = 0, n_done = 0, n_planned = 0, next = 0;   // next: the item the next free helper takes
-        std::vector<uint8_t> prepped;                              // per item (helpers finish out of order)
-        bool plan_final = false;
-        int rc = LDW_OK;
-        int64_t bad = INT64_MAX;             // the first item whose preparation failed (items before it are still good: r05)
-        bool stop = false, probing = true;   // probing: the cold-start probes (calling thread) still use the last slot's staging buffer
-        std::string err;
-    } sh;
-    sh.n_planned = (int64_t)items.size();
-    sh.plan_final = lead == nblocks;
-    sh.prepped.assign((size_t)nblocks + 1, 0);
-    // r04: TWO helpers (a span of eight blocks took ~3 ms of list building, a diagonal block in front of it gives the
-    // GPU 1.3 ms of work: one helper left the GEMM stream waiting).  Each takes the next item; items k, k+1, k+2 use different slots.
-    auto worker = [&]() {
-        (void)hipSetDevice(c->device);
-        std::vector<int32_t> wfi, wti;   // this helper's own index lists
-        for (;;) {
-            WorkItem it{0, 0};
-            int64_t k = 0;
-            {
-                std::unique_lock<std::mutex> lk(sh.m);
-                sh.cv.wait(lk, [&] {
-                    if (sh.stop) return true;
-                    if (sh.next >= sh.n_planned) return sh.plan_final;   // (plan complete and nothing left: leave)
-                    return sh.next < sh.n_done + RING && sh.next < sh.n_sub + LDW_NSLOT - (sh.probing ? 1 : 0);
-                });
-                if (sh.stop || sh.next >= sh.n_planned) return;
-                k = sh.next++;
-                it = items[(size_t)k];
-            }
-            int rc = LDW_OK;
-            try {   // (prep_block allocates a dozen std::vectors: an exception on this thread must come back as an error code, not std::terminate)
-                const int32_t fs = blocks[it.b0 * 4 + 0], fe = blocks[it.b0 * 4 + 1];
-                bool ok = fs >= 1 && fe >= fs && fe <= c->L;
-                SpanPlan spn;
-                wti.clear();
-                for (int q = 0; q < it.nseg && ok; ++q) {
-                    const int32_t ts = blocks[(it.b0 + q) * 4 + 2], te = blocks[(it.b0 + q) * 4 + 3];
-                    ok = ts >= 1 && te >= ts && te <= c->L;
-                    if (!ok) break;
-                    spn.start[q] = (int32_t)wti.size();
-                    spn.nt[q] = te - ts + 1;
-                    for (int32_t x = ts; x <= te; ++x) wti.push_back(x - 1);
-                }
-                spn.nseg = it.nseg;
-                if (!ok) {
-                    set_error("block %lld = (%d,%d,%d,%d) outside 1..%lld", (long long)it.b0, fs, fe, blocks[it.b0 * 4 + 2], blocks[it.b0 * 4 + 3], (long long)c->L);
-                    rc = LDW_ERR_ARG;
-                } else {
-                    wfi.resize((size_t)(fe - fs + 1));
-                    for (int32_t q = fs; q <= fe; ++q) wfi[q - fs] = q - 1;
-                    const int slot = (int)(k % LDW_NSLOT);
-                    if (c->up_recorded[slot] && hipEventSynchronize(c->ev_up[slot]) != hipSuccess) {   // the staging buffer of this slot has been uploaded
-                        set_error("prep: hipEventSynchronize failed");
-                        rc = LDW_ERR_HIP;
-                    }
-                    HostBlock &h = hb[k % RING];
-                    if (rc == LDW_OK) rc = prep_block(c, wfi.data(), (int64_t)wfi.size(), wti.data(), (int64_t)wti.size(), p, slot, it.b0, h, it.nseg > 1 ? &spn : nullptr);
-                    if (rc == LDW_OK && it.nseg > 1) {
-                        h.span_from = wfi;
-                        h.span_to = wti;
-                    }
-                }
-            } catch (const std::exception &e) {
-                set_error("preparing block %lld: %s", (long long)it.b0, e.what());
-                rc = LDW_ERR_HIP;
-            } catch (...) {
-                set_error("preparing block %lld: unknown exception", (long long)it.b0);
-                rc = LDW_ERR_HIP;
-            }
-            std::lock_guard<std::mutex> lk(sh.m);
-            if (rc != LDW_OK) {
-                if (sh.rc == LDW_OK || k < sh.bad) {
-                    sh.rc = rc;
-                    sh.err = ldw_last_error();
-                }
-                sh.bad = std::min(sh.bad, k);
-                sh.stop = true;
-            } else {
-                sh.prepped[(size_t)k] = 1;
-            }
-            sh.cv.notify_all();
-            if (rc != LDW_OK) return;
-        }
-    };
-    constexpr int n_helpers = 2;
-    std::thread helpers[n_helpers];
-    for (int i = 0; i < n_helpers; ++i) helpers[i] = std::thread(worker);
-    struct Joiner {   // every way out of this function stops and joins the helpers
-        Shared &sh;
-        std::thread *t;
-        int n;
-        ~Joiner() {
-            {
-                std::lock_guard<std::mutex> lk(sh.m);
-                sh.stop = true;
-            }
-            sh.cv.notify_all();
-            for (int i = 0; i < n; ++i)
-                if (t[i].joinable()) t[i].join();
-        }
-    } joiner{sh, helpers, n_helpers};
     const double t_sized = now0();
-    // (the helper is already building the first blocks' lists while the probes run; it stays out of the last slot until they are done)
-    // cold start: a sampled guess for each block kind that has none yet (probe_kind_guess), taken from the first block of the kind
-    static const bool probe_on = getenv("LDW_NO_PROBE") == nullptr;
-    if (probe_on && !p->sr_only && c->pos_sorted && speculation_pays(c, p)) {
-        bool done_kind[2] = {false, false};
-        Probe probes[2];
-        int n_probe = 0;
-        size_t pin_base = 0;
-        for (int64_t b = 0; b < nblocks && !(done_kind[0] && done_kind[1]); ++b) {
-            const bool diag = blocks[b * 4 + 0] == blocks[b * 4 + 2] && blocks[b * 4 + 1] == blocks[b * 4 + 3];
-            const int kind = diag ? 1 : 0;
-            if (done_kind[kind]) continue;
-            done_kind[kind] = true;
-            if (c->spec_B_next[kind] >= 0) continue;
-            if (int rc = fill(b)) return rc;
-            const int64_t npairs = diag ? (int64_t)fi.size() * ((int64_t)fi.size() - 1) / 2 : (int64_t)fi.size() * (int64_t)ti.size();
-            if (npairs < PROBE_MIN_PAIRS) continue;
-            // (a staging buffer that has to grow for the second sample is reallocated: the first sample's upload must have left it)
-            if (n_probe > 0 && c->pin_cap[LDW_NSLOT - 1] < pin_base + 2 * probes[0].hb.total + 65536) LDW_HIP(hipStreamSynchronize(c->stream));
-            if (int rc = probe_enqueue(c, fi.data(), (int64_t)fi.size(), ti.data(), (int64_t)ti.size(), p, sl, kind, n_probe, pin_base, probes[n_probe])) return rc;
-            pin_base = (pin_base + probes[n_probe].hb.total + 255) / 256 * 256;
-            ++n_probe;
-        }
-        if (n_probe > 0) {
-            LDW_HIP(hipStreamSynchronize(c->stream));
-            for (int k = 0; k < n_probe; ++k) probe_collect(c, probes[k]);
-        }
-    }
-    const double t_probed = now0();
-    {   // the rest of the plan: consecutive candidates of one block row, to sides ascending, form a span (at most span_max blocks,
-        // nf x nt below the 32-bit index limit of the unit lists, the int32 block below ~6 GB)
-        const bool spans = spans_possible(c, p);
-        std::vector<WorkItem> rest;
-        for (int64_t b = lead; b < nblocks;) {
-            int n = 1;
-            if (spans && cand[(size_t)b]) {
-                const int64_t nf = blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1;
-                int64_t nt_tot = blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1;
-                static const int env_max = [] { const char *e = getenv("LDW_SPAN_MAX"); return e ? atoi(e) : 0; }();   // (A/B measurements)
-                const int nmax = std::min<int>(env_max >= 1 ? env_max : c->span_max, LDW_SPAN_MAX);
-                while (n < nmax && b + n < nblocks && cand[(size_t)(b + n)] && blocks[(b + n) * 4 + 0] == blocks[b * 4 + 0] && blocks[(b + n) * 4 + 1] == blocks[b * 4 + 1] &&
-                       blocks[(b + n) * 4 + 2] > blocks[(b + n - 1) * 4 + 3]) {
-                    const int64_t nt_k = blocks[(b + n) * 4 + 3] - blocks[(b + n) * 4 + 2] + 1;
-                    if (nf * (nt_tot + nt_k) >= 1500000000LL || (nt_tot + nt_k) > 900000) break;
-                    nt_tot += nt_k;
-                    ++n;
-                }
-            }
-            rest.push_back(WorkItem{b, n});
-            b += n;
-        }
-        c->early_sr = spans;
-        std::lock_guard<std::mutex> lk(sh.m);
-        items.insert(items.end(), rest.begin(), rest.end());
-        sh.n_planned = (int64_t)items.size();
-        sh.plan_final = true;
-        sh.probing = false;
-    }
-    sh.cv.notify_all();
-    const int64_t nitems = (int64_t)items.size();
-    const double t_planned = now0();
-    if (host_timing0)
-        fprintf(stderr, "[ldw host us] waiting for the side threads %.0f  links_begin (row map if stale, bookkeeping) %.0f  table sizing + helper start %.0f  cold-start probes %.0f  plan %.0f\n",
-                t_joined - t_enter, t_begun - t_joined, t_sized - t_begun, t_probed - t_sized, t_planned - t_probed);
     // blocks until item k is prepared (true) — or, with wait = false, says whether it is
     auto prepped = [&](int64_t k, bool wait, int &rc) -> bool {
         std::unique_lock<std::mutex> lk(sh.m);
@@ -686,12 +657,56 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
         return LDW_OK;
     };
     const int64_t ahead = c->overlap ? LDW_NSLOT - 1 : 1;
+    // (the helpers are already building the first items' lists while the probes run)
+    // cold start: a sampled guess for each block kind that has none yet (probe_kind_guess), taken from the first block of the kind
+    Probe probes[2];
+    int n_probe = 0;
+    if (probes_wanted) {
+        bool done_kind[2] = {false, false};
+        size_t pin_base = 0;
+        for (int64_t b = 0; b < nblocks && !(done_kind[0] && done_kind[1]); ++b) {
+            const bool diag = blocks[b * 4 + 0] == blocks[b * 4 + 2] && blocks[b * 4 + 1] == blocks[b * 4 + 3];
+            const int kind = diag ? 1 : 0;
+            if (done_kind[kind]) continue;
+            done_kind[kind] = true;
+            if (c->spec_B_next[kind] >= 0) continue;
+            if (int rc = fill(b)) return rc;
+            const int64_t npairs = diag ? (int64_t)fi.size() * ((int64_t)fi.size() - 1) / 2 : (int64_t)fi.size() * (int64_t)ti.size();
+            if (npairs < PROBE_MIN_PAIRS) continue;
+            // (a staging buffer that has to grow for the second sample is reallocated: the first sample's upload must have left it)
+            if (n_probe > 0 && c->pin_cap[LDW_NSLOT] < pin_base + 2 * probes[0].hb.total + 65536) LDW_HIP(hipStreamSynchronize(c->stream));
+            if (int rc = probe_enqueue(c, fi.data(), (int64_t)fi.size(), ti.data(), (int64_t)ti.size(), p, sl, kind, n_probe, pin_base, probes[n_probe])) return rc;
+            pin_base = (pin_base + probes[n_probe].hb.total + 255) / 256 * 256;
+            ++n_probe;
+        }
+    }
+    const double t_queued = now0();
+    // The first item's lists go up while the probes run (the upload needs no guess).  Then the host waits for the probes that item needs — the
+    // one that ran on slot 0's buffers, the one of the item's own kind — and NOT for a second probe of the other kind: that one finishes on
+    // the main stream beside the item's block-wide pass and is collected behind the item's second phase, before anything else is submitted.
+    int deferred = -1;   // the probe still to collect
     {
         int rc = LDW_OK;
         prepped(0, true, rc);
         if (rc) return rc;
-        if ((rc = submit_next())) return rc;
+        if ((rc = submit_upload(c, hb[0]))) return rc;
+        const int kind0 = hb[0].diag ? 1 : 0;
+        for (int k = 0; k < n_probe; ++k) {
+            if (!probes[k].queued) continue;
+            if (probes[k].which != 0 && probes[k].kind != kind0) {
+                deferred = k;
+                continue;
+            }
+            LDW_HIP(hipEventSynchronize(c->ev_probe[probes[k].which]));
+            probe_collect(c, probes[k]);
+        }
     }
+    const double t_probed = now0();
+    if (int rc = submit_next()) return rc;
+    const double t_planned = now0();
+    if (host_timing0)
+        fprintf(stderr, "[ldw host us] waiting for the side threads %.0f  links_begin (row map if stale, bookkeeping) %.0f  table sizing + plan + helper start %.0f  cold-start probes queued %.0f  first upload + wait for its probe %.0f  first item submitted %.0f\n",
+                t_joined - t_enter, t_begun - t_joined, t_sized - t_begun, t_queued - t_sized, t_probed - t_queued, t_planned - t_probed);
     int fail_rc = LDW_OK;
     std::string fail_msg;
     int64_t b_fail = -1;          // the item the loop was at when it failed
@@ -708,6 +723,15 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
         double t0 = now();
         if (int rc = submit_b(c, cur, p, sl)) { failed(rc, b, false, false); break; }   // epilogue + pick of item b (main stream)
         th[0] += now() - t0;
+        if (deferred >= 0) {   // (b == 0) the probe of the other kind ran in front of this second phase: its guess is there before any item of its kind is submitted
+            if (hipEventSynchronize(c->ev_probe[probes[deferred].which]) != hipSuccess) {
+                set_error("cold-start probe: hipEventSynchronize failed");
+                failed(LDW_ERR_HIP, b, true, false);
+                break;
+            }
+            probe_collect(c, probes[deferred]);
+            deferred = -1;
+        }
         t0 = now();
         // items b+1 .. b+ahead (GEMM stream) run beside them: b+1 is waited for, the ones after it are taken if they are ready
         while (n_sub < nitems && n_sub <= b + ahead) {

@@ -94,18 +94,36 @@ int build_cols(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     }
     int64_t total_u = 0, total_l = 0;
     std::vector<int32_t> cu((size_t)nt), cl((size_t)nt);
+    // The four window bounds of a column are those of std::lower_bound / std::upper_bound over pf.  POS ascends along the to side of every block
+    // the item pipeline prepares, so each bound only moves forward from the previous column's: a walk, O(nf + nt) for the block instead of four
+    // binary searches per column (0.4 of the 1.2 ms a 10k x 10k diagonal block took to prepare — the first item of a pass, which the GPU waits
+    // for).  A column whose position steps back searches afresh; the results are the same either way.
+    int64_t hint[4] = {0, 0, 0, 0};
+    double p_prev = 0;
     for (int64_t b = 0; b < nt; ++b) {
         const double p1 = (double)c->h_POS[to_idx[b]];
+        const bool fwd = b > 0 && p1 >= p_prev;
+        p_prev = p1;
+        auto lower = [&](int64_t &h, double v) -> int64_t {   // first index with pf >= v
+            if (!fwd) h = std::lower_bound(pf.begin(), pf.end(), v) - pf.begin();
+            else while (h < nf && pf[(size_t)h] < v) ++h;
+            return h;
+        };
+        auto upper = [&](int64_t &h, double v) -> int64_t {   // first index with pf > v
+            if (!fwd) h = std::upper_bound(pf.begin(), pf.end(), v) - pf.begin();
+            else while (h < nf && pf[(size_t)h] <= v) ++h;
+            return h;
+        };
         auto P = [&](int64_t a) { return circ_len(p1, pf[a], g) <= sr_dist; };
         ColInfo ci;
         memset(&ci, 0, sizeof(ci));
         // candidate intervals from the three position windows
         int64_t iv[3][2];
         iv[0][0] = 0;                                                                                // wrap-low: x <= p1 + sr - g
-        iv[0][1] = std::upper_bound(pf.begin(), pf.end(), p1 + sr_dist - g) - pf.begin();
-        iv[1][0] = std::lower_bound(pf.begin(), pf.end(), p1 - sr_dist) - pf.begin();               // centre
-        iv[1][1] = std::upper_bound(pf.begin(), pf.end(), p1 + sr_dist) - pf.begin();
-        iv[2][0] = std::lower_bound(pf.begin(), pf.end(), p1 - sr_dist + g) - pf.begin();           // wrap-high
+        iv[0][1] = upper(hint[0], p1 + sr_dist - g);
+        iv[1][0] = lower(hint[1], p1 - sr_dist);               // centre
+        iv[1][1] = upper(hint[2], p1 + sr_dist);
+        iv[2][0] = lower(hint[3], p1 - sr_dist + g);           // wrap-high
         iv[2][1] = nf;
         // merge overlapping / touching intervals, keep ascending order
         int n = 0;

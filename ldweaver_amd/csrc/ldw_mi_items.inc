@@ -9,6 +9,7 @@ struct HostBlock {
     int64_t nf = 0, nt = 0, n_sr_blk = 0, n_lr_total = 0, blk_no = 0;
     int RFpad = 0, RTpad = 0, slot = 0;
     bool diag = false, submitted = false;
+    bool uploaded = false;     // submit_upload has queued the upload of its lists (submit_a then skips it)
     int nf_tiles = 0;          // tiles of 64 in the padded from-side order
     int gen_t0 = 0, gen_q0 = 0;
     bool mixed = false;        // high-limb GEMM + gathered low limbs (decided with the bucket guess at submit_a)
@@ -63,6 +64,9 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
         LDW_REQUIRE(from_idx[k] >= 0 && from_idx[k] < c->L, LDW_ERR_ARG, "SNP index %d out of range", from_idx[k]);
     for (int64_t k = 0; k < nt; ++k)
         LDW_REQUIRE(to_idx[k] >= 0 && to_idx[k] < c->L, LDW_ERR_ARG, "SNP index %d out of range", to_idx[k]);
+    static const bool prep_timing = getenv("LDW_HOST_TIMING") != nullptr;
+    auto pnow = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double tp[8] = {pnow(), 0, 0, 0, 0, 0, 0, 0};
     hb = HostBlock();
     hb.nf = nf;
     hb.nt = nt;
@@ -73,6 +77,8 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     hb.diag = same_list(from_idx, nf, to_idx, nt);
     SideLists SF, ST;
     std::vector<ColInfo> cols;
+    std::string cols_err;
+    std::future<int> cols_job;   // (declared behind what it writes: an early return waits for it before those go away)
     auto ascending = [&](const int32_t *idx, int64_t n) {
         for (int64_t k = 1; k < n; ++k)
             if (c->h_POS[idx[k]] < c->h_POS[idx[k - 1]]) return false;
@@ -94,6 +100,16 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
             std::copy(ck.begin(), ck.end(), cols.begin() + sp->start[k]);
         }
         hb.n_sr_blk = 0;
+    } else if (hb.diag) {
+        // A diagonal block is the first item of a pass — the GPU has nothing to do until its lists are there — and neither its row lists nor
+        // its tiles depend on the intervals (no row ordering on the diagonal): the intervals are built on a thread of their own beside them
+        // and joined in front of the band, their first reader (0.36 of 1.1 ms at 10k x 10k).
+        cols.resize((size_t)nt);
+        cols_job = std::async(std::launch::async, [&]() -> int {
+            const int rc = build_cols(c, from_idx, nf, to_idx, nt, true, p->sr_dist, cols, hb.n_sr_blk);
+            if (rc != LDW_OK) cols_err = ldw_last_error();
+            return rc;
+        });
     } else if (int rc = build_cols(c, from_idx, nf, to_idx, nt, hb.diag, p->sr_dist, cols, hb.n_sr_blk)) return rc;
     if (sp) {   // a span: every column learns its reference block and where that block starts in the concatenated to side
         LDW_REQUIRE(!hb.generic && !hb.diag && sp->nseg >= 1 && sp->nseg <= LDW_SPAN_MAX, LDW_ERR_STATE,
@@ -109,6 +125,7 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
             }
         }
     }
+    tp[1] = pnow();
     // Blocks without a short-range pair (most off-diagonal ones): nothing depends on the order of the rows within a class, so the
     // one-row SNPs are ordered by the weight of their minor state on both sides — rows and epilogue slots alike, which the table
     // test of the GEMM's epilogue requires anyway.  The wave tiles of the approximate GEMM then span few bins of the threshold
@@ -160,11 +177,12 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
         }
     }
     LDW_REQUIRE(!sp || (ord_f && ord_t), LDW_ERR_STATE, "span at block %lld cannot be ordered", (long long)blk_no);
+    tp[2] = pnow();
     if (int rc = build_side(c, from_idx, nf, SF, ord_f)) return rc;
     if (int rc = build_side(c, to_idx, nt, ST, ord_t)) return rc;
+    tp[3] = pnow();
     hb.RFpad = SF.Rpad;
     hb.RTpad = ST.Rpad;
-    hb.n_lr_total = (hb.diag ? nf * (nf - 1) / 2 : nf * nt - std::min(nf, nt)) - hb.n_sr_blk;
     auto al = [](size_t x) { return (x + 63) / 64 * 64; };
     size_t o = 0;
     hb.o_idx_f = o; o = al(o + (size_t)nf * 4);
@@ -194,7 +212,7 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     }
     hb.o_perm = o; o = al(o + pf.size() * 4);
     hb.o_perm_t = o; o = al(o + (size_t)nt * 4);
-    hb.o_cols = o; o = al(o + cols.size() * sizeof(ColInfo));
+    hb.o_cols = o; o = al(o + (size_t)nt * sizeof(ColInfo));   // (one entry per to-side SNP; a diagonal block's are still being built)
     hb.o_pos_f = o; o = al(o + SF.pos.size() * 4);
     hb.o_pos_t = o; o = al(o + ST.pos.size() * 4);
     hb.o_cls_f = o; o = al(o + SF.cls.size());
@@ -243,6 +261,13 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     // approximate path: tiles of the exact GEMM (128 to-side x 64 from-side rows) that hold a short-range pair.  POS ascends along
     // both lists and the row lists keep the list order within a slot-count class, so the partners of a to-side SNP are a
     // contiguous row range per class
+    if (cols_job.valid())
+        if (int rc = cols_job.get()) {
+            set_error("%s", cols_err.c_str());
+            return rc;
+        }
+    hb.n_lr_total = (hb.diag ? nf * (nf - 1) / 2 : nf * nt - std::min(nf, nt)) - hb.n_sr_blk;
+    tp[4] = pnow();
     std::vector<uint8_t> band((size_t)(hb.RTpad / TILE) * (hb.RFpad / 64), 0);
     bool no_rowless = true;   // no SNP without an indicator row: a one-row SNP's row-list position is its slot (ApxGemmArgs::fuse)
     {
@@ -316,6 +341,7 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
                 }
             }
     }
+    tp[5] = pnow();
     hb.lo.fuse_ok = no_rowless ? 1 : 0;
     hb.lo.ordered = ord_f != nullptr ? 1 : 0;
     hb.o_cmax = o; o = al(o + cmax.size() * 4);
@@ -346,6 +372,7 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
         c->pin[ps] = np;
         c->pin_cap[ps] = (stage_base + o) * 2;
     }
+    tp[6] = pnow();
     char *b = static_cast<char *>(c->pin[ps]) + stage_base;
     memcpy(b + hb.o_idx_f, from_idx, (size_t)nf * 4);
     memcpy(b + hb.o_idx_t, to_idx, (size_t)nt * 4);
@@ -365,6 +392,9 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     memcpy(b + hb.o_tf, tf.data(), tf.size() * 4);
     memcpy(b + hb.o_band, band.data(), band.size());
     if (!bandl.empty()) memcpy(b + hb.o_bandl, bandl.data(), bandl.size() * 4);
+    if (prep_timing && blk_no < 12)
+        fprintf(stderr, "[ldw prep us] block %lld%s %lld x %lld span %d: checks + intervals %.0f  row order %.0f  sides %.0f  tiles + classes %.0f  band %.0f  band list %.0f  copy to staging %.0f  (%zu bytes)\n",
+                (long long)blk_no, hb.diag ? " diag" : "", (long long)nf, (long long)nt, hb.span, tp[1] - tp[0], tp[2] - tp[1], tp[3] - tp[2], tp[4] - tp[3], tp[5] - tp[4], tp[6] - tp[5], pnow() - tp[6], hb.total);
     return LDW_OK;
 }
 
@@ -504,7 +534,10 @@ static void fill_dev_ptrs(ldw_ctx *c, HostBlock &hb) {
                    hb.gen_q0};
 }
 
-int submit_a(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayout &sl) {
+// The upload alone (copy stream): it needs no bucket guess, so the first item of a cold pass sends its lists while the cold-start probe of its
+// kind is still running (ldw_mi_all_pairs); every other item uploads as the first step of submit_a.
+int submit_upload(ldw_ctx *c, HostBlock &hb) {
+    if (hb.uploaded) return LDW_OK;
     const int s = hb.slot;
     const int stg = hb.pin_slot >= 0 ? hb.pin_slot : s;   // (a span's segment that runs on its own is staged through the extra buffer)
     if (int rc = c->dstage[stg].reserve(hb.total)) return rc;
@@ -514,6 +547,13 @@ int submit_a(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayou
     LDW_HIP(hipEventRecord(c->ev_up[s], c->copy_stream));
     c->up_recorded[s] = true;
     fill_dev_ptrs(c, hb);
+    hb.uploaded = true;
+    return LDW_OK;
+}
+
+int submit_a(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayout &sl) {
+    const int s = hb.slot;
+    if (int rc = submit_upload(c, hb)) return rc;
     hb.submitted = true;
     if (c->engine != LDW_ENGINE_MFMA || hb.generic) return LDW_OK;
     hipStream_t gs = c->overlap ? c->gemm_stream : c->stream;   // overlap off: the stages of all blocks run back to back
@@ -1059,9 +1099,12 @@ constexpr int64_t PROBE_SIDE = 2048;          // sampled SNPs per side
 constexpr int64_t PROBE_MIN_PAIRS = 16000000; // smaller blocks are cheap enough without a guess
 constexpr int PROBE_MARGIN = 6;
 
-// r04: in two halves, so that the probes of both kinds are queued back to back and waited for ONCE (1.25 ms of a cold pass went into two
-// prep / upload / run / wait round trips): probe `which` (0, 1) uses the device buffers of pipeline slot `which` and its own part of
-// the last slot's pinned staging buffer.
+// r04: in two halves, so that the probes of both kinds are queued back to back (1.25 ms of a cold pass went into two prep / upload / run /
+// wait round trips).  Probe `which` (0, 1) uses the G buffer, histogram and pick record of pipeline slot `which`, and its own part of the
+// EXTRA staging pair (pin / dstage [LDW_NSLOT], otherwise used by a span's segment that is redone on its own, which first drains the
+// streams): the three slots' staging buffers belong to the helper threads and to item 0's upload from the start of the pass.
+// Each probe records its own event (ev_probe[which]); the caller waits for the probes of slot 0 and of the first item's kind before it
+// submits that item and collects the other one behind it (ldw_mi_all_pairs).
 struct Probe {
     HostBlock hb;
     int kind = 0, which = 0;
@@ -1079,15 +1122,15 @@ int probe_enqueue(ldw_ctx *c, const int32_t *fi, int64_t nf, const int32_t *ti, 
     P.kind = kind;
     P.which = which;
     P.queued = false;
-    // (host staging of the LAST slot: the helper threads of ldw_mi_all_pairs are already building the first blocks' lists in the others)
-    constexpr int PS = LDW_NSLOT - 1;
-    if (int rc = prep_block(c, sf.data(), (int64_t)sf.size(), st.data(), (int64_t)st.size(), &q, PS, 0, hb, nullptr, -1, pin_base)) return rc;
-    hb.slot = which;      // the DEVICE side of the probe is slot `which`'s (the blocks are submitted after the probes)
-    hb.lo.slot = which;
-    hb.stage_base = 0;    // (its device image starts its slot's staging buffer)
+    constexpr int PS = LDW_NSLOT;
+    if (int rc = prep_block(c, sf.data(), (int64_t)sf.size(), st.data(), (int64_t)st.size(), &q, which, 0, hb, nullptr, PS, pin_base)) return rc;
     if (hb.n_lr_total < 100000) return LDW_OK;   // too few long-range pairs in the sample to say anything
-    if (int rc = c->dstage[which].reserve(hb.total)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->dstage[which].p, static_cast<const char *>(c->pin[PS]) + pin_base, hb.total, hipMemcpyHostToDevice, c->stream));
+    if (c->dstage[PS].cap < pin_base + hb.total) {
+        // (the first sample reserves room for both; should the second still not fit, the first one's kernels leave the buffer before it goes)
+        if (which > 0) LDW_HIP(hipStreamSynchronize(c->stream));
+        if (int rc = c->dstage[PS].reserve(which == 0 ? 2 * hb.total + 65536 + 256 : pin_base + hb.total)) return rc;
+    }
+    LDW_HIP(hipMemcpyAsync(c->dstage[PS].as<char>() + pin_base, static_cast<const char *>(c->pin[PS]) + pin_base, hb.total, hipMemcpyHostToDevice, c->stream));
     fill_dev_ptrs(c, hb);
     if (int rc = c->hist[which].reserve((size_t)NBINS * 8)) return rc;
     if (int rc = make_emit_args(c, hb, &q, sl, -1)) return rc;
@@ -1103,10 +1146,11 @@ int probe_enqueue(ldw_ctx *c, const int32_t *fi, int64_t nf, const int32_t *ti, 
     LDW_HIP(hipGetLastError());
     LDW_HIP(hipMemcpyAsync(c->pin_pick[which], sl.pick[which], sizeof(ldw::PickOut), hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemsetAsync(sl.pick[which], 0, sizeof(ldw::PickOut), c->stream));
+    LDW_HIP(hipEventRecord(c->ev_probe[which], c->stream));
     P.queued = true;
     return LDW_OK;
 }
-// after hipStreamSynchronize(c->stream)
+// after hipEventSynchronize(c->ev_probe[P.which])
 void probe_collect(ldw_ctx *c, const Probe &P) {
     if (!P.queued) return;
     const ldw::PickOut *hp = static_cast<const ldw::PickOut *>(c->pin_pick[P.which]);
