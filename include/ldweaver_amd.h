@@ -487,6 +487,75 @@ int ldw_annot_links(ldw_ctx *ctx, const double *key, const double *aracne, int64
                     int64_t max_tophits, int64_t *perm_out, int32_t *r1_out, int32_t *r2_out, int8_t *pair_out, int64_t *top_out,
                     int64_t *n_top_out);
 
+/* ---- (12) the plots — make_gwes_plots (R/prepareGWESplots.R:25-126), the lr_gwes.png of analyse_long_range_links (R/lr_analyser.R:113-125),
+ *           LD_plot.png of genomewide_LDMap (R/LDSummaryPlot.R:108-127) — rendered on the device, framed and written as PNG by the host.
+ * Rules.  Axis range = range of the kept rows widened by 5 % on both sides (a zero-width range by +-0.5 first), shared by all
+ * panels; px = min(W-1, (int)floor((x - x0) / (x1 - x0) * W)), py = H-1 - min(H-1, (int)floor((y - y0) / (y1 - y0) * H)), fp64, no fused
+ * multiply-add.  A point is the opaque disc of the offsets 4 (dx^2 + dy^2) <= D^2 round its centre pixel, clipped at the panel.  Draw order:
+ * layer 0 under layer 1, inside a layer ascending srp_max (ordered = 0) or descending row (ordered != 0: the first row is on top), so a pixel
+ * shows the maximum key of the discs that cover it.  Rows with a non-finite x, y or srp_max, or a negative srp_max, are dropped and counted.
+ * Colours: srp == NULL: layer_rgb[layer]; else layer 0 = 0xC0C0C0 and layer 1 = the six-stop gradient of t = (srp - lo) / (hi - lo), lo / hi
+ * the range of srp over the kept layer-1 rows (hi == lo: t = 0.5). */
+#define LDW_PLOT_SR_CLUST 0 /* sr_gwes_clust.png: 2200 x 1200, 1..10 facets with strips, colour bar */
+#define LDW_PLOT_SR_COMBI 1 /* sr_gwes_combi.png: 2200 x 1200, one panel, colour bar */
+#define LDW_PLOT_LR 2       /* lr_gwes.png: 4800 x 1200, one panel */
+#define LDW_PLOT_LDMAP 3    /* LD_plot.png: 5000 x 5250, one square panel under a title */
+#define LDW_PLOT_MAX_PANELS 10
+#define LDW_PLOT_MAX_TICKS 16
+#define LDW_PLOT_MAX_D 41
+typedef struct ldw_plot_layout {
+    int32_t width, height;                       /* canvas */
+    int32_t n_panels, rows, cols;                /* facets laid out like ggplot2::wrap_dims, row-major */
+    int32_t panel_w, panel_h;                    /* every panel has this size */
+    int32_t panel[LDW_PLOT_MAX_PANELS][4];       /* x, y, w, h of every panel (top-left origin) */
+    int32_t strip[LDW_PLOT_MAX_PANELS][4];       /* facet strips (w = 0: none) */
+    int32_t cbar[4];                             /* colour bar (w = 0: none) */
+    int32_t n_xticks, n_yticks;
+    int32_t xtick_px[LDW_PLOT_MAX_TICKS];        /* column of every x tick inside a panel (pixel rule) */
+    int32_t ytick_px[LDW_PLOT_MAX_TICKS];        /* row of every y tick inside a panel */
+    double xlim[2], ylim[2];                     /* axis range (after the 5 %) */
+    double xtick[LDW_PLOT_MAX_TICKS], ytick[LDW_PLOT_MAX_TICKS];   /* 1-2-5 positions, ascending */
+} ldw_plot_layout;
+typedef struct ldw_plot_opts {
+    int32_t kind;             /* LDW_PLOT_* (not LDW_PLOT_LDMAP) */
+    int32_t D;                /* disc diameter in pixels, odd, 1..LDW_PLOT_MAX_D; 0 = 11 */
+    int32_t ordered;          /* are_srlinks_ordered: row order is the draw order, first row on top (needs srp) */
+    int32_t flags;            /* LDW_PLOT_NO_PRECHECK (measurement only: same picture) */
+    uint32_t layer_rgb[2];    /* 0xRRGGBB of layer 0 / 1 when srp == NULL */
+    int32_t has_hline;        /* one-pixel horizontal line at y = hline_y over the points (widens the y range like a row) */
+    uint32_t hline_rgb;
+    double hline_y;
+} ldw_plot_opts;
+#define LDW_PLOT_NO_PRECHECK 1
+/* Host only, no context and no GPU.  The figure of `kind` with n_panels facets (1 unless LDW_PLOT_SR_CLUST) for the DATA ranges
+ * [x_min, x_max] x [y_min, y_max] (ignored by LDW_PLOT_LDMAP, which has no ticks). */
+int ldw_plot_layout_get(int kind, int n_panels, double x_min, double x_max, double y_min, double y_max, ldw_plot_layout *out);
+/* Host only: ticks of one axis of `npx` pixels for the data range [lo, hi]: lim_out = the axis range, tick_out / px_out (capacity
+ * LDW_PLOT_MAX_TICKS) the 1-2-5 positions inside it and their pixel offset by the pixel rule (flip != 0: the y axis, row 0 on top). */
+int ldw_plot_ticks(double lo, double hi, int npx, int flip, double lim_out[2], double *tick_out, int32_t *px_out, int32_t *n_out);
+/* Host only: 8-bit RGB, non-interlaced PNG of rgb[height][width][3]; level 0..9 is zlib's (-1: 1). */
+int ldw_png_write(const char *path, const uint8_t *rgb, int32_t width, int32_t height, int level, int64_t *bytes_out);
+/* The scatter figure of n rows: x, y doubles, srp doubles (NULL: fixed colours), layer uint8 0 / 1 (NULL: all 1), panel uint8 in
+ * [0, n_panels) (NULL: all 0), host or device memory (host columns pass through a device buffer of constant size in chunks of 2^20 rows; the
+ * row-order key also keeps a device copy of the srp column, which the colour pass reads by row).  panel_label[n_panels] (may be NULL) is
+ * printed on the strips.  The figure goes to png_path (may be NULL) and / or rgb_out (may be NULL: height x width x 3 bytes of the layout's
+ * canvas).  *dropped_out (may be NULL): rows dropped.  n = 0 gives the frame over the unit ranges. */
+int ldw_plot_scatter(ldw_ctx *ctx, const double *x, const double *y, const double *srp, const uint8_t *layer, const uint8_t *panel, int64_t n,
+                     int on_device, const ldw_plot_opts *opts, int n_panels, const int32_t *panel_label, const char *png_path, uint8_t *rgb_out,
+                     int64_t *dropped_out);
+/* The same from the context's own state, nothing copied to the host: the kept links of ldw_sr_pvalues (which = 0: x = len from POS and g of
+ * ldw_set_snp_meta by the circ_len rule, y = MI, srp = srp_max, panel = rank of clust_c among the clust_c present, LDW_PLOT_SR_CLUST or
+ * _COMBI) or of ldw_lr_tukey (which = 1: LDW_PLOT_LR, fixed colours).  use_aracne != 0: layer = the flags of the last ldw_aracne_device
+ * (LDW_ERR_STATE if it has not run since the kept links last changed: the context keeps track); 0: every row in layer 1.  LDW_ERR_STATE also
+ * without SNP meta data and when the kept links are those of the other table. */
+int ldw_plot_links(ldw_ctx *ctx, int which, int use_aracne, const ldw_plot_opts *opts, const char *png_path, uint8_t *rgb_out, int64_t *dropped_out);
+/* LD_plot.png: htm (B x B doubles in [0, 1], host or device) through the 2056-colour ramp white, #E1B9B4, #AE452C, #802418 (index
+ * min(floor(v * 2056), 2055); non-finite: 0), nearest neighbour, row 0 at the bottom; title (may be NULL) above it. */
+int ldw_plot_heatmap(ldw_ctx *ctx, const double *htm, int32_t B, int on_device, const char *title, const char *png_path, uint8_t *rgb_out);
+/* ldw_ldmap and its picture in one call: the map is rendered from the device copy; htm_out (may be NULL) as in ldw_ldmap. */
+int ldw_plot_ldmap(ldw_ctx *ctx, int32_t reducer, int32_t from, int32_t to, const char *title, const char *png_path, int64_t *n_pos_out,
+                   int32_t *reducer_out, int32_t *B_out, double *htm_out, int64_t capacity);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

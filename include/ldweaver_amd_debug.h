@@ -178,6 +178,19 @@ int ldw_debug_apx_gemm(ldw_ctx *ctx, const int32_t *rows_t, int nrt, const int32
 int ldw_debug_screen_bound(ldw_ctx *ctx, int kind, int na, int nb, int64_t n, const int64_t *g, const int64_t *pa, const int64_t *pb, const float *pX, const float *pY,
                            const double *rr, const uint32_t *masks, const double params[20], float *out, double *out64);
 
+/* ---- the plots (ldweaver_amd.h 12) ------------------------------------------------------------------------------------------------ */
+/* The rasters of ldw_plot_scatter without the frame, for panels of W x H pixels each (any size >= 1): rgb_out[n_panels][H][W][3] (host).  Grid
+ * lines lie at the ticks of ldw_plot_ticks for the data range and W / H.  stats_out (may be NULL, 8 doubles): x min, x max, y min, y max of
+ * the kept rows (the hline included), srp lo, hi over the kept layer-1 rows (NaN: none), rows kept, rows dropped.  *scratch_bytes_out (may be
+ * NULL): device memory the render needs beyond the caller's columns (and, when on_device = 0, beyond the chunk buffer of at most 26 MiB and
+ * the row-order key's copy of the srp column).  ms_out (may be
+ * NULL, 4 doubles): hip-event times of the statistics pass, the key-image clear, the centre pass and the disc + colour pass. */
+int ldw_debug_plot_panels(ldw_ctx *ctx, const double *x, const double *y, const double *srp, const uint8_t *layer, const uint8_t *panel, int64_t n,
+                          int on_device, const ldw_plot_opts *opts, int n_panels, int32_t W, int32_t H, uint8_t *rgb_out, double *stats_out,
+                          int64_t *scratch_bytes_out, double *ms_out);
+/* Host only: the 2056 colours of the LD map's ramp (kind 0, rgb_out 2056 x 3) or the scatter gradient at t[n] (kind 1, rgb_out n x 3). */
+int ldw_debug_plot_colours(int kind, const double *t, int64_t n, uint8_t *rgb_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ _EXPORTS = {
     "snpdat_to_fa": "output", "generate_Links_SNPS_fasta": "output", "write_output_for_gwes_explorer": "output",
     "read_TopHits": "output", "read_AnnotatedLinks": "output",
     "perform_snpEff_annotations": "annotate",
+    "make_gwes_plots": "plots", "read_ShortRangeLinks": "plots", "read_LongRangeLinks": "plots",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -28,6 +28,25 @@ class LdwError(RuntimeError):
         self.code = code
 
 
+PLOT_SR_CLUST, PLOT_SR_COMBI, PLOT_LR, PLOT_LDMAP = 0, 1, 2, 3
+PLOT_MAX_PANELS, PLOT_MAX_TICKS, PLOT_MAX_D, PLOT_NO_PRECHECK = 10, 16, 41, 1
+
+
+class PlotLayout(C.Structure):
+    """ldw_plot_layout (include/ldweaver_amd.h 12)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_panels", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("panel_w", C.c_int32), ("panel_h", C.c_int32), ("panel", (C.c_int32 * 4) * 10), ("strip", (C.c_int32 * 4) * 10),
+                ("cbar", C.c_int32 * 4), ("n_xticks", C.c_int32), ("n_yticks", C.c_int32), ("xtick_px", C.c_int32 * 16),
+                ("ytick_px", C.c_int32 * 16), ("xlim", C.c_double * 2), ("ylim", C.c_double * 2), ("xtick", C.c_double * 16),
+                ("ytick", C.c_double * 16)]
+
+
+class PlotOpts(C.Structure):
+    """ldw_plot_opts (include/ldweaver_amd.h 12)."""
+    _fields_ = [("kind", C.c_int32), ("D", C.c_int32), ("ordered", C.c_int32), ("flags", C.c_int32), ("layer_rgb", C.c_uint32 * 2),
+                ("has_hline", C.c_int32), ("hline_rgb", C.c_uint32), ("hline_y", C.c_double)]
+
+
 class MIParams(C.Structure):
     _fields_ = [("sr_dist", C.c_double), ("lr_retain_links", C.c_double), ("lr_links_approx", C.c_double),
                 ("sr_only", C.c_int32), ("quirk_mode", C.c_int32), ("keep_sr", C.c_int32), ("flags", C.c_int32)]
@@ -117,6 +136,13 @@ _SIGS_API = {
     "ldw_annot_snps": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p]),
     "ldw_annot_map": (C.c_int, [_p, _p, _p, _i64, _p, _i64, _p, C.POINTER(_i64), C.POINTER(_i64)]),
     "ldw_annot_links": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, C.POINTER(_i64)]),
+    "ldw_plot_layout_get": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _p]),
+    "ldw_plot_ticks": (C.c_int, [C.c_double, C.c_double, C.c_int, C.c_int, _p, _p, _p, _p]),
+    "ldw_png_write": (C.c_int, [C.c_char_p, _p, C.c_int32, C.c_int32, C.c_int, C.POINTER(_i64)]),
+    "ldw_plot_scatter": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, C.c_int, _p, C.c_int, _p, C.c_char_p, _p, C.POINTER(_i64)]),
+    "ldw_plot_links": (C.c_int, [_p, C.c_int, C.c_int, _p, C.c_char_p, _p, C.POINTER(_i64)]),
+    "ldw_plot_heatmap": (C.c_int, [_p, _p, C.c_int32, C.c_int, C.c_char_p, C.c_char_p, _p]),
+    "ldw_plot_ldmap": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_char_p, _p, _p, _p, _p, _i64]),
     "ldw_compare_to_row": (C.c_int, [_p, _i64, _i64, _p, _i64, _p]),
     "ldw_vec_pos_match": (C.c_int, [_p, _i64, _p, _i64, _p]),
     "ldw_compare_triplet": (C.c_int, [_p, _p, _i64, C.c_double, C.POINTER(C.c_int)]),
@@ -154,6 +180,8 @@ _SIGS_DEBUG = {
     "ldw_debug_rows": (C.c_int, [_p, _p, _p, _i64]),
     "ldw_debug_apx_gemm": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p]),
     "ldw_debug_screen_bound": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ldw_debug_plot_panels": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, C.c_int, _p, C.c_int, C.c_int32, C.c_int32, _p, _p, C.POINTER(_i64), _p]),
+    "ldw_debug_plot_colours": (C.c_int, [C.c_int, _p, _i64, _p]),
 }
 _SIGS = {**_SIGS_API, **_SIGS_DEBUG}
 _SIGS_BY_HEADER = {"ldweaver_amd.h": _SIGS_API, "ldweaver_amd_debug.h": _SIGS_DEBUG}

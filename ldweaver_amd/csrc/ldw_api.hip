@@ -618,7 +618,7 @@ int ldw_ctx_destroy(ldw_ctx *c) {
                            &c->red_srp, &c->pool_a, &c->pool_b, &c->pool_mi, &c->ar_key, &c->ar_val, &c->ar_key2, &c->ar_val2,
                            &c->ar_off, &c->ar_flags, &c->seq_perm, &c->dig_a, &c->dig_b, &c->apx_shift, &c->slot_papx, &c->pop_segs, &c->pop_wbeg, &c->pop_vpos,
                            &c->pair_sums, &c->tab11[0], &c->tab11[1], &c->G2, &c->G3, &c->miss_key, &c->miss_val, &c->srd_lower, &c->srd_cur, &c->srd_out, &c->srd_seg, &c->pos_slot,
-                           &c->cds_keep, &c->cds_work, &c->annot_keep, &c->annot_work};
+                           &c->cds_keep, &c->cds_work, &c->annot_keep, &c->annot_work, &c->plot_work, &c->plot_cols};
     for (auto *b : bufs) b->release();
     for (int k = 0; k < LDW_NSLOT; ++k)
         for (ldw::DevBuf *b : {&c->panel[k][0], &c->panel[k][1], &c->Gapx[k], &c->pairs[k], &c->apx_mini[k], &c->apx_units[k], &c->apx_packs[k], &c->apx_bins[k], &c->apx_clean[k],

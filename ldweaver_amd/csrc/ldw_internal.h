@@ -239,6 +239,9 @@ struct ldw_ctx {
     ldw::DevBuf red_row, red_meta, red_srp, pool_a, pool_b, pool_mi, ar_key, ar_val, ar_key2, ar_val2, ar_off, ar_flags;
     int64_t n_red = 0, n_pool = 0;
     bool red_from_lr = false;    // red_row indexes the long-range table (ldw_lr_tukey) instead of the short-range one
+    bool ar_valid = false;       // ar_flags holds the ARACNE flags of the CURRENT kept links: set by ldw_aracne_device, cleared wherever the kept set changes
+                                 // or ar_flags is borrowed as working memory (ldw_lr_tukey)
+    ldw::DevBuf plot_work, plot_cols;   // the plots (ldw_plot.hip): key image + rasters + partials; device copy of a chunk of host columns
     int srm_S = 0, srm_nclust = 0;   // geometry of the last ldw_sr_len_quantiles call
     double srm_sr_dist = 0;
 

@@ -1056,6 +1056,7 @@ int ldw_links_import(ldw_ctx *c, int which, const int32_t *a, const int32_t *b, 
     }
     (which == 0 ? c->n_sr : c->n_lr) = n;
     c->n_red = c->n_pool = 0;   // whatever was derived from the old table is stale:
+    c->ar_valid = false;
     c->stats.clear();           // the per-block records of the pass that made it (ldw_block_stats answers LDW_ERR_ARG until the next pass) ...
     c->multi_owner.clear();     // ... and the deal of an in-process pass whose shares these rows replace
     return LDW_OK;

@@ -252,6 +252,7 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
     if (!rows_stay) c0->n_sr = tot[0];   // (rows_stay: ctx[0] keeps the short-range rows of its own share, like every other context)
     c0->n_lr = tot[1];
     c0->n_red = c0->n_pool = 0;
+    c0->ar_valid = false;
     c0->stats = stats;                    // the records of ALL blocks, in the caller's order (ldw_block_stats)
     if (rows_stay) c0->multi_owner = owner;
     if (ms_out) ms_out[1] = now_ms() - t_1;

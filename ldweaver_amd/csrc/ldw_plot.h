@@ -1,0 +1,51 @@
+// The plots (include/ldweaver_amd.h 12): what the device render (ldw_plot.hip) and the host frame / PNG writer (ldw_png.cpp) share.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/ldweaver_amd.h"
+
+namespace ldw {
+
+constexpr uint32_t PLOT_BG = 0xFFFFFF, PLOT_GRID = 0xEBEBEB, PLOT_BORDER = 0xB3B3B3, PLOT_TEXT = 0x4D4D4D, PLOT_TITLE = 0x000000,
+                   PLOT_GREY = 0xC0C0C0;
+constexpr int PLOT_RAMP_N = 2056;
+
+// rev(brewer.pal(6, "RdYlBu")), piecewise linear in sRGB: s = min(floor(5 t), 4), f = 5 t - s, channel = floor(c[s] + (c[s+1] - c[s]) f + 0.5).
+// One IEEE operation at a time (the tests compare with numpy), on the host and on the device.
+__host__ __device__ __forceinline__ uint32_t plot_gradient(double t) {
+#pragma clang fp contract(off)
+    constexpr int c[6][3] = {{0x45, 0x75, 0xB4}, {0x91, 0xBF, 0xDB}, {0xE0, 0xF3, 0xF8}, {0xFE, 0xE0, 0x90}, {0xFC, 0x8D, 0x59}, {0xD7, 0x30, 0x27}};
+    const double t5 = 5.0 * t;
+    int s = (int)floor(t5);
+    s = s > 4 ? 4 : (s < 0 ? 0 : s);
+    const double f = t5 - (double)s;
+    uint32_t rgb = 0;
+    for (int k = 0; k < 3; ++k) {
+        const double d = (double)(c[s + 1][k] - c[s][k]);
+        const double m = d * f;
+        const double v = ((double)c[s][k] + m) + 0.5;
+        rgb = (rgb << 8) | (uint32_t)(int)floor(v);
+    }
+    return rgb;
+}
+
+// the pixel rule of one axis: min(n - 1, (int)floor((v - v0) / (v1 - v0) * n))
+__host__ __device__ __forceinline__ int plot_pixel(double v, double v0, double v1, int n) {
+#pragma clang fp contract(off)
+    const double a = v - v0;
+    const double q = a / (v1 - v0);
+    const double p = floor(q * (double)n);
+    if (!(p >= 0.0)) return 0;   // (not reached by a kept row: its value lies inside the axis range)
+    return p >= (double)n ? n - 1 : (int)p;
+}
+
+// host side (ldw_png.cpp)
+void plot_ramp_table(uint8_t *rgb);   // PLOT_RAMP_N x 3
+int plot_axis(double lo, double hi, int npx, int flip, double lim[2], double *tick, int32_t *px, int32_t *n);
+// the frame round the panels, drawn into canvas[height][width][3]; rasters: [n_panels][panel_h][panel_w][3]
+void plot_frame(uint8_t *canvas, const ldw_plot_layout &lay, int kind, const uint8_t *rasters, const int32_t *panel_label, const char *title,
+                bool cbar_valid, double cb_lo, double cb_hi);
+
+}  // namespace ldw

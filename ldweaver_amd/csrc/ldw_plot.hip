@@ -1,0 +1,671 @@
+// The plots on the device (include/ldweaver_amd.h 12): a scatter rasteriser that draws no point twice and sorts nothing, and
+// the LD map's heat map.
+//
+// ggplot draws opaque points in row order, so the colour of a pixel is the colour of the LAST point whose disc covers it: the maximum of the
+// draw-order key over those points.  k_plot_centre takes that maximum per CENTRE pixel (one 64-bit atomicMax per row into the key image),
+// k_plot_disc takes the maximum of the key image over the disc of offsets round every output pixel — the disc is symmetric, so that is the
+// maximum over the points whose disc covers the pixel — and turns the winning key into a colour.  Both maxima are order independent: the
+// picture is a function of the set of rows.
+//
+// Bounds: a kept row's pixel lies in [0, W) x [0, H) by the clamps of plot_pixel, its panel in [0, n_panels) by the test in the kernel (the
+// statistics pass has already refused the call if any row's panel is out of range); the disc pass reads the key image only at in-panel
+// coordinates and writes one RGB triple per in-panel pixel.
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "ldw_dev.h"
+#include "ldw_internal.h"
+#include "ldw_plot.h"
+
+#pragma clang fp contract(off)
+
+namespace ldw {
+int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t *n_pos_out, int32_t *reducer_out, int32_t *B_out, bool want,
+                 int64_t capacity, const double **d_htm);   // ldw_post.hip
+
+namespace {
+
+constexpr int PLOT_TX = 32, PLOT_TY = 32, PLOT_NPART = 10, PLOT_MAX_BLOCKS = 1024;
+constexpr uint64_t KEY_LAYER = 1ull << 63;
+
+struct PlotRow {
+    double x, y, srp;
+    int layer, panel;
+};
+
+// the caller's columns
+struct ColSrc {
+    const double *x, *y, *srp;
+    const uint8_t *layer, *panel;
+    __device__ __forceinline__ bool has_srp() const { return srp != nullptr; }
+    __device__ __forceinline__ double srp_at(int64_t i) const { return srp[i]; }
+    __device__ __forceinline__ void get(int64_t i, PlotRow &r) const {
+        r.x = x[i];
+        r.y = y[i];
+        r.srp = srp ? srp[i] : 0.0;
+        r.layer = layer ? (layer[i] != 0) : 1;
+        r.panel = panel ? panel[i] : 0;
+    }
+};
+
+// the context's kept links (ldw_sr_pvalues / ldw_lr_tukey): row of the link table, its SNPs' positions, srp_max, clust_c, ARACNE flags
+struct CtxSrc {
+    const int64_t *row;
+    const int32_t *a, *b, *POS;
+    const double *mi, *srp;
+    const uint32_t *meta;
+    const uint8_t *flags;
+    double g;
+    uint8_t lut[256];   // clust_c -> panel
+    int facets;
+    __device__ __forceinline__ bool has_srp() const { return srp != nullptr; }
+    __device__ __forceinline__ double srp_at(int64_t i) const { return srp[i]; }
+    __device__ __forceinline__ void get(int64_t i, PlotRow &r) const {
+        const int64_t t = row[i];
+        r.x = circ_len((double)POS[b[t]], (double)POS[a[t]], g);   // pos1 = to side, pos2 = from side (R/computePairwiseMI.R:319-330)
+        r.y = mi[t];
+        r.srp = srp ? srp[i] : 0.0;
+        r.layer = flags ? (flags[i] != 0) : 1;
+        r.panel = facets ? lut[meta[i] & 0xFF] : 0;
+    }
+};
+
+__device__ __forceinline__ bool plot_keep(const PlotRow &r, bool has_srp) {
+    return isfinite(r.x) && isfinite(r.y) && (!has_srp || (isfinite(r.srp) && r.srp >= 0.0));
+}
+
+// ---- statistics: ranges of the kept rows, range of srp over the kept layer-1 rows, counts; [block][PLOT_NPART] partials ----------------------
+template <class Src>
+__global__ void __launch_bounds__(256) k_plot_stats(const Src s, int64_t n, int n_panels, double *__restrict__ part) {
+    double v[PLOT_NPART] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY, 0, 0, 0, 0};   // x, y, srp (min, max), kept, dropped, bad panel
+    const bool hs = s.has_srp();
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        PlotRow r;
+        s.get(i, r);
+        if (r.panel < 0 || r.panel >= n_panels) v[8] = 1;
+        if (!plot_keep(r, hs)) {
+            v[7] += 1;
+            continue;
+        }
+        v[6] += 1;
+        v[0] = fmin(v[0], r.x);
+        v[1] = fmax(v[1], r.x);
+        v[2] = fmin(v[2], r.y);
+        v[3] = fmax(v[3], r.y);
+        if (hs && r.layer) {
+            v[4] = fmin(v[4], r.srp);
+            v[5] = fmax(v[5], r.srp);
+        }
+    }
+    __shared__ double sh[256];
+    for (int k = 0; k < PLOT_NPART; ++k) {
+        sh[threadIdx.x] = v[k];
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) {
+                const double p = sh[threadIdx.x], q = sh[threadIdx.x + w];
+                sh[threadIdx.x] = k >= 6 ? p + q : ((k & 1) ? fmax(p, q) : fmin(p, q));   // (counts below 2^53: exact)
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) part[(size_t)blockIdx.x * PLOT_NPART + k] = sh[0];
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) k_plot_present(const uint32_t *__restrict__ meta, int64_t n, uint32_t *__restrict__ present) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) present[meta[i] & 0xFF] = 1u;
+}
+
+struct PlotGeom {
+    double x0, x1, y0, y1;
+    int W, H, n_panels;
+};
+
+// ---- centre pass: one atomicMax per kept row -------------------------------------------------------------------------------------------------
+// key, srp order:  ((layer << 63) | bits(srp)) + 1   (srp >= 0: its bit pattern orders like its value; -0.0 counts as 0)
+// key, row order:  (layer << 63) | (n - row)         (the first row is on top)
+template <class Src, int ORDERED, int PRECHECK>
+__global__ void __launch_bounds__(256) k_plot_centre(const Src s, int64_t n, int64_t row0, int64_t n_total, const PlotGeom G,
+                                                     unsigned long long *__restrict__ img) {   // rows row0 .. row0 + n - 1 of a table of n_total
+    const bool hs = s.has_srp();
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        PlotRow r;
+        s.get(i, r);
+        if (!plot_keep(r, hs) || r.panel < 0 || r.panel >= G.n_panels) continue;
+        const int px = plot_pixel(r.x, G.x0, G.x1, G.W), py = G.H - 1 - plot_pixel(r.y, G.y0, G.y1, G.H);
+        const size_t at = ((size_t)r.panel * G.H + py) * G.W + px;
+        unsigned long long key = r.layer ? KEY_LAYER : 0ull;
+        if (ORDERED)
+            key |= (unsigned long long)(n_total - (row0 + i));
+        else
+            key = (key | (r.srp == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(r.srp))) + 1ull;
+        // The image only grows, so a dominated point needs no atomic.  The plain load races with other lanes' atomicMax on the same address:
+        // an aligned 8-byte global load is one access (never torn), and a stale value is never larger than the current one, so the test can
+        // only fail to skip, never skip wrongly.
+        if (PRECHECK && img[at] >= key) continue;
+        atomicMax(&img[at], key);
+    }
+}
+
+struct PlotPaint {
+    int D, h;                  // diameter, halo = D / 2
+    int8_t hw[LDW_PLOT_MAX_D]; // hw[dy + h] = largest dx with 4 (dx^2 + dy^2) <= D^2
+    int nx, ny, xt[LDW_PLOT_MAX_TICKS], yt[LDW_PLOT_MAX_TICKS];   // grid lines
+    int fixed;                 // fixed-colour mode
+    uint32_t layer_rgb[2];
+    double lo, hi;             // range of srp over the kept layer-1 rows
+    int hline_py;              // -1: none
+    uint32_t hline_rgb;
+};
+
+// ---- disc + colour pass: one thread per output pixel, the key image read through an LDS tile with a halo of D / 2 ------------------------------
+// (one kernel: a second 8-byte image between the two steps would double the scratch memory)
+template <class Src, int ORDERED>
+__global__ void __launch_bounds__(256) k_plot_disc(const Src s, int64_t n, const PlotGeom G, const PlotPaint P, const unsigned long long *__restrict__ img,
+                                                   uint8_t *__restrict__ rast) {
+    extern __shared__ unsigned long long tile[];
+    const int h = P.h, tw = PLOT_TX + 2 * h, th = PLOT_TY + 2 * h;
+    const int bx = blockIdx.x * PLOT_TX, by = blockIdx.y * PLOT_TY, panel = blockIdx.z;
+    const unsigned long long *pimg = img + (size_t)panel * G.H * G.W;
+    for (int t = threadIdx.x; t < tw * th; t += 256) {
+        const int gx = bx - h + t % tw, gy = by - h + t / tw;
+        tile[t] = (gx >= 0 && gx < G.W && gy >= 0 && gy < G.H) ? pimg[(size_t)gy * G.W + gx] : 0ull;   // discs are clipped at the panel
+    }
+    __syncthreads();
+    const int lx = threadIdx.x % PLOT_TX;
+    for (int ly = threadIdx.x / PLOT_TX; ly < PLOT_TY; ly += 256 / PLOT_TX) {
+        const int gx = bx + lx, gy = by + ly;
+        if (gx >= G.W || gy >= G.H) continue;
+        unsigned long long m = 0;
+        for (int dy = -h; dy <= h; ++dy) {
+            const int w = P.hw[dy + h];
+            const unsigned long long *rowp = tile + (ly + h + dy) * tw + lx + h;
+            for (int dx = -w; dx <= w; ++dx) m = max(m, rowp[dx]);
+        }
+        uint32_t rgb;
+        if (m == 0) {
+            bool grid = false;
+            for (int k = 0; k < P.nx; ++k) grid |= P.xt[k] == gx;
+            for (int k = 0; k < P.ny; ++k) grid |= P.yt[k] == gy;
+            rgb = grid ? PLOT_GRID : PLOT_BG;
+        } else {
+            const int layer = (int)(m >> 63);
+            const unsigned long long low = m & ~KEY_LAYER;
+            if (P.fixed) {
+                rgb = P.layer_rgb[layer];
+            } else if (!layer) {
+                rgb = PLOT_GREY;
+            } else {
+                double v;
+                if (ORDERED) {
+                    v = s.srp_at(n - (int64_t)low);
+                    v = v == 0.0 ? 0.0 : v;
+                } else {
+                    v = __longlong_as_double((long long)(low - 1ull));
+                }
+                const double t = P.hi == P.lo ? 0.5 : (v - P.lo) / (P.hi - P.lo);
+                rgb = plot_gradient(t);
+            }
+        }
+        if (gy == P.hline_py) rgb = P.hline_rgb;
+        uint8_t *o = rast + (((size_t)panel * G.H + gy) * G.W + gx) * 3;
+        o[0] = (uint8_t)(rgb >> 16);
+        o[1] = (uint8_t)(rgb >> 8);
+        o[2] = (uint8_t)rgb;
+    }
+}
+
+// ---- heat map: nearest neighbour, row 0 at the bottom -------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_plot_heat(const double *__restrict__ htm, int B, int W, int H, const uint8_t *__restrict__ ramp, uint8_t *__restrict__ rast) {
+    const int64_t total = (int64_t)W * H;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int px = (int)(i % W), py = (int)(i / W);
+        const int r = (int)(((int64_t)(H - 1 - py) * B) / H), c = (int)(((int64_t)px * B) / W);
+        const double v = htm[(size_t)r * B + c];
+        int k = 0;
+        if (isfinite(v)) {
+            const double f = floor(v * (double)PLOT_RAMP_N);
+            k = f >= (double)(PLOT_RAMP_N - 1) ? PLOT_RAMP_N - 1 : (f > 0.0 ? (int)f : 0);
+        }
+        rast[i * 3] = ramp[k * 3];
+        rast[i * 3 + 1] = ramp[k * 3 + 1];
+        rast[i * 3 + 2] = ramp[k * 3 + 2];
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------------------
+
+// Device memory: ctx->plot_work (key image, rasters, partials) and ctx->plot_cols (host columns in chunks), the context's grow-only buffers.
+
+// host columns travel in chunks of PLOT_CHUNK rows through one device buffer of constant size: statistics pass, then centre pass, per chunk
+struct HostCols {
+    const double *x, *y, *srp;
+    const uint8_t *layer, *panel;
+};
+constexpr int64_t PLOT_CHUNK = 1 << 20;   // 26 MiB of columns
+size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+size_t chunk_bytes(int64_t n) {
+    const int64_t m = std::min<int64_t>(n, PLOT_CHUNK);
+    return round256((size_t)m * 8) * 3 + round256((size_t)m) * 2;
+}
+// rows [i0, i0 + m) into ctx->plot_cols (reserved by the caller), queued on the context's stream behind the kernels that read the last chunk
+int upload_chunk(ldw_ctx *c, const HostCols &h, int64_t n, int64_t i0, int64_t m, ColSrc &out) {
+    const int64_t m0 = std::min<int64_t>(n, PLOT_CHUNK);
+    const size_t nd = round256((size_t)m0 * 8), nb = round256((size_t)m0);
+    uint8_t *p = c->plot_cols.as<uint8_t>();
+    out = ColSrc{nullptr, nullptr, nullptr, nullptr, nullptr};
+    LDW_HIP(hipMemcpyAsync(p, h.x + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(p + nd, h.y + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+    out.x = (const double *)p;
+    out.y = (const double *)(p + nd);
+    if (h.srp) {
+        LDW_HIP(hipMemcpyAsync(p + 2 * nd, h.srp + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+        out.srp = (const double *)(p + 2 * nd);
+    }
+    if (h.layer) {
+        LDW_HIP(hipMemcpyAsync(p + 3 * nd, h.layer + i0, (size_t)m, hipMemcpyHostToDevice, c->stream));
+        out.layer = p + 3 * nd;
+    }
+    if (h.panel) {
+        LDW_HIP(hipMemcpyAsync(p + 3 * nd + nb, h.panel + i0, (size_t)m, hipMemcpyHostToDevice, c->stream));
+        out.panel = p + 3 * nd + nb;
+    }
+    return LDW_OK;
+}
+
+struct PlotStats {
+    double xr[2] = {0, 1}, yr[2] = {0, 1}, lo = NAN, hi = NAN;
+    int64_t kept = 0, dropped = 0;
+};
+
+constexpr size_t PLOT_CONST_BYTES = (size_t)PLOT_MAX_BLOCKS * PLOT_NPART * 8 + 1024;   // statistics partials + the cluster marks
+
+int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, PLOT_MAX_BLOCKS)); }
+
+int check_opts(const ldw_plot_opts *o, const char *who, int &D) {
+    LDW_REQUIRE(o, LDW_ERR_ARG, "%s: null options", who);
+    LDW_REQUIRE(o->kind >= LDW_PLOT_SR_CLUST && o->kind <= LDW_PLOT_LR, LDW_ERR_ARG, "%s: figure kind %d is no scatter figure", who, o->kind);
+    D = o->D == 0 ? 11 : o->D;
+    LDW_REQUIRE(D >= 1 && D <= LDW_PLOT_MAX_D && (D & 1), LDW_ERR_ARG, "%s: the disc diameter D = %d must be odd and in 1..%d", who, D, LDW_PLOT_MAX_D);
+    LDW_REQUIRE(!o->has_hline || std::isfinite(o->hline_y), LDW_ERR_ARG, "%s: the line's y is not finite", who);
+    return LDW_OK;
+}
+
+// one launch of the statistics pass over m rows, its partials merged into v
+template <class Src>
+int stats_accum(ldw_ctx *c, const Src &s, int64_t m, int n_panels, double *d_part, double *v) {
+    const int grid = grid_for(m);
+    hipLaunchKernelGGL(k_plot_stats<Src>, dim3(grid), dim3(256), 0, c->stream, s, m, n_panels, d_part);
+    LDW_HIP(hipGetLastError());
+    std::vector<double> part((size_t)grid * PLOT_NPART);
+    LDW_HIP(hipMemcpyAsync(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < grid; ++b)
+        for (int k = 0; k < PLOT_NPART; ++k) {
+            const double q = part[(size_t)b * PLOT_NPART + k];
+            v[k] = k >= 6 ? v[k] + q : ((k & 1) ? std::max(v[k], q) : std::min(v[k], q));
+        }
+    return LDW_OK;
+}
+
+// hc != NULL: the rows are host columns, fed in chunks (s is then only the colour pass's view)
+template <class Src>
+int plot_stats(ldw_ctx *c, const Src &s, const HostCols *hc, int64_t n, int n_panels, const ldw_plot_opts *o, double *d_part, PlotStats &st, const char *who) {
+    if (n > 0) {
+        double v[PLOT_NPART] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY, 0, 0, 0, 0};
+        if (hc) {
+            for (int64_t i0 = 0; i0 < n; i0 += PLOT_CHUNK) {
+                const int64_t m = std::min<int64_t>(PLOT_CHUNK, n - i0);
+                ColSrc cs;
+                if (int rc = upload_chunk(c, *hc, n, i0, m, cs)) return rc;
+                if (int rc = stats_accum(c, cs, m, n_panels, d_part, v)) return rc;
+            }
+        } else if (int rc = stats_accum(c, s, n, n_panels, d_part, v)) {
+            return rc;
+        }
+        LDW_REQUIRE(v[8] == 0, LDW_ERR_ARG, "%s: a panel id lies outside 0..%d", who, n_panels - 1);
+        st.kept = (int64_t)v[6];
+        st.dropped = (int64_t)v[7];
+        if (st.kept > 0) {
+            st.xr[0] = v[0] == 0 ? 0.0 : v[0];
+            st.xr[1] = v[1] == 0 ? 0.0 : v[1];
+            st.yr[0] = v[2] == 0 ? 0.0 : v[2];
+            st.yr[1] = v[3] == 0 ? 0.0 : v[3];
+        }
+        if (v[4] <= v[5]) {
+            st.lo = v[4];
+            st.hi = v[5];
+        }
+    }
+    if (o->has_hline) {
+        if (st.kept == 0) st.yr[0] = st.yr[1] = o->hline_y;
+        st.yr[0] = std::min(st.yr[0], o->hline_y);
+        st.yr[1] = std::max(st.yr[1], o->hline_y);
+    }
+    return LDW_OK;
+}
+
+// key image + rasters of n_panels panels of W x H pixels; ev (may be NULL): 4 events recorded after the clear, the centre pass, the disc pass
+template <class Src>
+int plot_raster(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int64_t n, const ldw_plot_opts *o, int D, int n_panels, int W, int H, const double xlim[2], const double ylim[2],
+                int nxt, const int32_t *xt, int nyt, const int32_t *yt, const PlotStats &st, unsigned long long *d_keys, uint8_t *d_rast, hipEvent_t *ev) {
+    const PlotGeom G{xlim[0], xlim[1], ylim[0], ylim[1], W, H, n_panels};
+    PlotPaint P;
+    memset(&P, 0, sizeof(P));
+    P.D = D;
+    P.h = D / 2;
+    for (int dy = -P.h; dy <= P.h; ++dy) {
+        int w = 0;
+        while (4 * ((w + 1) * (w + 1) + dy * dy) <= D * D) ++w;
+        P.hw[dy + P.h] = (int8_t)w;
+    }
+    P.nx = nxt;
+    P.ny = nyt;
+    for (int k = 0; k < nxt; ++k) P.xt[k] = xt[k];
+    for (int k = 0; k < nyt; ++k) P.yt[k] = yt[k];
+    P.lo = st.lo;
+    P.hi = st.hi;
+    P.hline_py = o->has_hline ? H - 1 - plot_pixel(o->hline_y, ylim[0], ylim[1], H) : -1;
+    P.hline_rgb = o->hline_rgb;
+    P.layer_rgb[0] = o->layer_rgb[0];
+    P.layer_rgb[1] = o->layer_rgb[1];
+    P.fixed = has_srp ? 0 : 1;
+    const size_t pixels = (size_t)n_panels * W * H;
+    if (ev) LDW_HIP(hipEventRecord(ev[0], c->stream));
+    LDW_HIP(hipMemsetAsync(d_keys, 0, pixels * 8, c->stream));
+    if (ev) LDW_HIP(hipEventRecord(ev[1], c->stream));
+    const int pre = (o->flags & LDW_PLOT_NO_PRECHECK) ? 0 : 1;
+    const dim3 dgrid((W + PLOT_TX - 1) / PLOT_TX, (H + PLOT_TY - 1) / PLOT_TY, n_panels);
+    const size_t lds = (size_t)(PLOT_TX + 2 * P.h) * (PLOT_TY + 2 * P.h) * 8;
+    int rc_up = LDW_OK;
+    auto run = [&](auto ordered_tag) {
+        constexpr int ORD = decltype(ordered_tag)::value;
+        if (n > 0 && hc) {
+            for (int64_t i0 = 0; i0 < n && rc_up == LDW_OK; i0 += PLOT_CHUNK) {
+                const int64_t m = std::min<int64_t>(PLOT_CHUNK, n - i0);
+                ColSrc cs;
+                rc_up = upload_chunk(c, *hc, n, i0, m, cs);
+                if (rc_up != LDW_OK) break;
+                if (pre)
+                    hipLaunchKernelGGL((k_plot_centre<ColSrc, ORD, 1>), dim3(grid_for(m)), dim3(256), 0, c->stream, cs, m, i0, n, G, d_keys);
+                else
+                    hipLaunchKernelGGL((k_plot_centre<ColSrc, ORD, 0>), dim3(grid_for(m)), dim3(256), 0, c->stream, cs, m, i0, n, G, d_keys);
+            }
+        } else if (n > 0) {
+            if (pre)
+                hipLaunchKernelGGL((k_plot_centre<Src, ORD, 1>), dim3(grid_for(n)), dim3(256), 0, c->stream, s, n, (int64_t)0, n, G, d_keys);
+            else
+                hipLaunchKernelGGL((k_plot_centre<Src, ORD, 0>), dim3(grid_for(n)), dim3(256), 0, c->stream, s, n, (int64_t)0, n, G, d_keys);
+        }
+        if (ev) (void)hipEventRecord(ev[2], c->stream);
+        hipLaunchKernelGGL((k_plot_disc<Src, ORD>), dgrid, dim3(256), lds, c->stream, s, n, G, P, d_keys, d_rast);
+        if (ev) (void)hipEventRecord(ev[3], c->stream);
+    };
+    return [&]() {
+        if (o->ordered)
+            run(std::integral_constant<int, 1>());
+        else
+            run(std::integral_constant<int, 0>());
+        if (rc_up != LDW_OK) return rc_up;
+        LDW_HIP(hipGetLastError());
+        return LDW_OK;
+    }();
+}
+
+template <class Src>
+int plot_panels(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int64_t n, const ldw_plot_opts *o, int n_panels, int W, int H, uint8_t *rgb_out, double *stats_out,
+                int64_t *scratch_out, double *ms_out, const char *who) {
+    int D = 0;
+    if (int rc = check_opts(o, who, D)) return rc;
+    LDW_REQUIRE(!o->ordered || has_srp || n == 0, LDW_ERR_ARG, "%s: the row-order key needs the srp column", who);
+    LDW_REQUIRE(n_panels >= 1 && n_panels <= LDW_PLOT_MAX_PANELS, LDW_ERR_ARG, "%s: %d panels outside 1..%d", who, n_panels, LDW_PLOT_MAX_PANELS);
+    LDW_REQUIRE(W >= 1 && H >= 1 && (int64_t)W * H * n_panels <= (1ll << 28), LDW_ERR_ARG, "%s: panels of %d x %d pixels", who, W, H);
+    LDW_REQUIRE(rgb_out, LDW_ERR_ARG, "%s: null output", who);
+    const size_t pixels = (size_t)n_panels * W * H;
+    const size_t kb = round256(pixels * 8), rb = round256(pixels * 3);
+    if (int rc = c->plot_work.reserve(kb + rb + PLOT_CONST_BYTES)) return rc;
+    unsigned long long *d_keys = c->plot_work.as<unsigned long long>();
+    uint8_t *d_rast = c->plot_work.as<uint8_t>() + kb;
+    double *d_part = (double *)(c->plot_work.as<uint8_t>() + kb + rb);
+    if (scratch_out) *scratch_out = (int64_t)(kb + rb + PLOT_CONST_BYTES);
+    hipEvent_t ev[6] = {};
+    struct EvGuard {
+        hipEvent_t *e;
+        ~EvGuard() {
+            for (int k = 0; k < 6; ++k)
+                if (e[k]) (void)hipEventDestroy(e[k]);
+        }
+    } guard{ev};
+    if (ms_out)
+        for (int k = 0; k < 6; ++k) LDW_HIP(hipEventCreate(&ev[k]));
+    PlotStats st;
+    if (ms_out) LDW_HIP(hipEventRecord(ev[4], c->stream));
+    if (int rc = plot_stats(c, s, hc, n, n_panels, o, d_part, st, who)) return rc;
+    if (ms_out) LDW_HIP(hipEventRecord(ev[5], c->stream));
+    double xlim[2], ylim[2], tick[LDW_PLOT_MAX_TICKS];
+    int32_t xt[LDW_PLOT_MAX_TICKS], yt[LDW_PLOT_MAX_TICKS], nxt = 0, nyt = 0;
+    LDW_REQUIRE(plot_axis(st.xr[0], st.xr[1], W, 0, xlim, tick, xt, &nxt) == LDW_OK && plot_axis(st.yr[0], st.yr[1], H, 1, ylim, tick, yt, &nyt) == LDW_OK,
+                LDW_ERR_ARG, "%s: the data ranges are not finite intervals", who);
+    if (int rc = plot_raster(c, s, hc, has_srp, n, o, D, n_panels, W, H, xlim, ylim, nxt, xt, nyt, yt, st, d_keys, d_rast, ms_out ? ev : nullptr)) return rc;
+    LDW_HIP(hipMemcpyAsync(rgb_out, d_rast, pixels * 3, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    if (ms_out) {
+        float f = 0;
+        LDW_HIP(hipEventElapsedTime(&f, ev[4], ev[5]));
+        ms_out[0] = f;
+        for (int k = 0; k < 3; ++k) {
+            LDW_HIP(hipEventElapsedTime(&f, ev[k], ev[k + 1]));
+            ms_out[k + 1] = f;
+        }
+    }
+    if (stats_out) {
+        const double v[8] = {st.xr[0], st.xr[1], st.yr[0], st.yr[1], st.lo, st.hi, (double)st.kept, (double)st.dropped};
+        memcpy(stats_out, v, sizeof(v));
+    }
+    return LDW_OK;
+}
+
+int emit_figure(const ldw_plot_layout &lay, int kind, const std::vector<uint8_t> &rasters, const int32_t *panel_label, const char *title, bool cb_valid,
+                double cb_lo, double cb_hi, const char *png_path, uint8_t *rgb_out) {
+    std::vector<uint8_t> own;
+    uint8_t *canvas = rgb_out;
+    if (!canvas) {
+        own.resize((size_t)lay.width * lay.height * 3);
+        canvas = own.data();
+    }
+    plot_frame(canvas, lay, kind, rasters.data(), panel_label, title, cb_valid, cb_lo, cb_hi);
+    if (png_path) return ldw_png_write(png_path, canvas, lay.width, lay.height, -1, nullptr);
+    return LDW_OK;
+}
+
+// the whole figure: statistics -> layout -> rasters -> frame -> PNG / canvas
+template <class Src>
+int plot_figure(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int64_t n, const ldw_plot_opts *o, int n_panels, const int32_t *panel_label, const char *png_path,
+                uint8_t *rgb_out, int64_t *dropped_out, const char *who) {
+    int D = 0;
+    if (int rc = check_opts(o, who, D)) return rc;
+    LDW_REQUIRE(!o->ordered || has_srp || n == 0, LDW_ERR_ARG, "%s: the row-order key needs the srp column", who);
+    LDW_REQUIRE(n_panels >= 1 && n_panels <= LDW_PLOT_MAX_PANELS && (o->kind == LDW_PLOT_SR_CLUST || n_panels == 1), LDW_ERR_ARG,
+                "%s: %d panels (1..%d for the facet figure, 1 otherwise)", who, n_panels, LDW_PLOT_MAX_PANELS);
+    LDW_REQUIRE(png_path || rgb_out, LDW_ERR_ARG, "%s: neither a path nor a canvas to write to", who);
+    ldw_plot_layout lay;
+    if (int rc = ldw_plot_layout_get(o->kind, n_panels, 0, 1, 0, 1, &lay)) return rc;   // (panel size: independent of the ranges)
+    const int W = lay.panel_w, H = lay.panel_h;
+    const size_t pixels = (size_t)n_panels * W * H;
+    const size_t kb = round256(pixels * 8), rb = round256(pixels * 3);
+    if (int rc = c->plot_work.reserve(kb + rb + PLOT_CONST_BYTES)) return rc;
+    uint8_t *work = c->plot_work.as<uint8_t>();
+    PlotStats st;
+    if (int rc = plot_stats(c, s, hc, n, n_panels, o, (double *)(work + kb + rb), st, who)) return rc;
+    if (int rc = ldw_plot_layout_get(o->kind, n_panels, st.xr[0], st.xr[1], st.yr[0], st.yr[1], &lay)) return rc;
+    if (int rc = plot_raster(c, s, hc, has_srp, n, o, D, n_panels, W, H, lay.xlim, lay.ylim, lay.n_xticks, lay.xtick_px, lay.n_yticks, lay.ytick_px, st,
+                             (unsigned long long *)work, work + kb, nullptr))
+        return rc;
+    std::vector<uint8_t> rasters(pixels * 3);
+    LDW_HIP(hipMemcpyAsync(rasters.data(), work + kb, pixels * 3, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    if (dropped_out) *dropped_out = st.dropped;
+    return emit_figure(lay, o->kind, rasters, panel_label, nullptr, has_srp && st.lo <= st.hi, st.lo, st.hi, png_path, rgb_out);
+}
+
+// The caller's columns as the passes see them.  Device columns: read where they lie.  Host columns: fed in chunks (HostCols), so the device holds
+// one chunk at a time — and, for the row-order key alone, the whole srp column (8 B per row), which the colour pass reads by row.
+struct Cols {
+    ColSrc src{};
+    HostCols host{};
+    const HostCols *hc = nullptr;
+    int make(ldw_ctx *c, const double *x, const double *y, const double *srp, const uint8_t *layer, const uint8_t *panel, int64_t n, int on_device,
+             int ordered) {
+        src = ColSrc{x, y, srp, layer, panel};
+        if (on_device || n == 0) return LDW_OK;
+        host = HostCols{x, y, srp, layer, panel};
+        hc = &host;
+        const size_t cb = chunk_bytes(n);
+        const bool whole_srp = ordered && srp;
+        if (int rc = c->plot_cols.reserve(cb + (whole_srp ? (size_t)n * 8 : 0))) return rc;
+        src = ColSrc{nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (whole_srp) {
+            double *d = (double *)(c->plot_cols.as<uint8_t>() + cb);
+            LDW_HIP(hipMemcpyAsync(d, srp, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+            src.srp = d;
+        }
+        return LDW_OK;
+    }
+};
+
+int check_cols(const double *x, const double *y, int64_t n, const char *who) {
+    LDW_REQUIRE(n >= 0, LDW_ERR_ARG, "%s: n = %lld < 0", who, (long long)n);
+    LDW_REQUIRE(n == 0 || (x && y), LDW_ERR_ARG, "%s: null x or y column", who);
+    return LDW_OK;
+}
+
+int heat_figure(ldw_ctx *c, const double *d_htm, int32_t B, const char *title, const char *png_path, uint8_t *rgb_out) {
+    ldw_plot_layout lay;
+    if (int rc = ldw_plot_layout_get(LDW_PLOT_LDMAP, 1, 0, 1, 0, 1, &lay)) return rc;
+    const int W = lay.panel_w, H = lay.panel_h;
+    const size_t pixels = (size_t)W * H;
+    if (int rc = c->plot_work.reserve(round256(pixels * 3) + PLOT_RAMP_N * 3)) return rc;
+    uint8_t *d_rast = c->plot_work.as<uint8_t>(), *d_ramp = d_rast + round256(pixels * 3);
+    std::vector<uint8_t> ramp(PLOT_RAMP_N * 3);
+    plot_ramp_table(ramp.data());
+    LDW_HIP(hipMemcpyAsync(d_ramp, ramp.data(), ramp.size(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_plot_heat, dim3(2048), dim3(256), 0, c->stream, d_htm, (int)B, W, H, d_ramp, d_rast);
+    LDW_HIP(hipGetLastError());
+    std::vector<uint8_t> rasters(pixels * 3);
+    LDW_HIP(hipMemcpyAsync(rasters.data(), d_rast, pixels * 3, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    return emit_figure(lay, LDW_PLOT_LDMAP, rasters, nullptr, title, false, 0, 0, png_path, rgb_out);
+}
+
+}  // namespace
+}  // namespace ldw
+
+using namespace ldw;
+
+extern "C" {
+
+int ldw_plot_scatter(ldw_ctx *c, const double *x, const double *y, const double *srp, const uint8_t *layer, const uint8_t *panel, int64_t n, int on_device,
+                     const ldw_plot_opts *opts, int n_panels, const int32_t *panel_label, const char *png_path, uint8_t *rgb_out, int64_t *dropped_out) {
+    LDW_REQUIRE(c != nullptr, LDW_ERR_ARG, "ldw_plot_scatter: null context");
+    if (int rc = check_cols(x, y, n, "ldw_plot_scatter")) return rc;
+    int D = 0;
+    if (int rc = check_opts(opts, "ldw_plot_scatter", D)) return rc;
+    LDW_REQUIRE(n_panels >= 1 && n_panels <= LDW_PLOT_MAX_PANELS && (opts->kind == LDW_PLOT_SR_CLUST || n_panels == 1), LDW_ERR_ARG,
+                "ldw_plot_scatter: %d panels (1..%d for the facet figure, 1 otherwise)", n_panels, LDW_PLOT_MAX_PANELS);
+    LDW_REQUIRE(png_path || rgb_out, LDW_ERR_ARG, "ldw_plot_scatter: neither a path nor a canvas to write to");
+    if (int rc = check_gpu(c)) return rc;
+    Cols cols;
+    if (int rc = cols.make(c, x, y, srp, layer, panel, n, on_device, opts->ordered)) return rc;
+    return plot_figure(c, cols.src, cols.hc, srp != nullptr, n, opts, n_panels, panel_label, png_path, rgb_out, dropped_out, "ldw_plot_scatter");
+}
+
+int ldw_debug_plot_panels(ldw_ctx *c, const double *x, const double *y, const double *srp, const uint8_t *layer, const uint8_t *panel, int64_t n, int on_device,
+                          const ldw_plot_opts *opts, int n_panels, int32_t W, int32_t H, uint8_t *rgb_out, double *stats_out, int64_t *scratch_bytes_out,
+                          double *ms_out) {
+    LDW_REQUIRE(c != nullptr, LDW_ERR_ARG, "ldw_debug_plot_panels: null context");
+    if (int rc = check_cols(x, y, n, "ldw_debug_plot_panels")) return rc;
+    int D = 0;
+    if (int rc = check_opts(opts, "ldw_debug_plot_panels", D)) return rc;
+    if (int rc = check_gpu(c)) return rc;
+    Cols cols;
+    if (int rc = cols.make(c, x, y, srp, layer, panel, n, on_device, opts->ordered)) return rc;
+    return plot_panels(c, cols.src, cols.hc, srp != nullptr, n, opts, n_panels, W, H, rgb_out, stats_out, scratch_bytes_out, ms_out, "ldw_debug_plot_panels");
+}
+
+int ldw_plot_links(ldw_ctx *c, int which, int use_aracne, const ldw_plot_opts *opts, const char *png_path, uint8_t *rgb_out, int64_t *dropped_out) {
+    LDW_REQUIRE(c != nullptr, LDW_ERR_ARG, "ldw_plot_links: null context");
+    LDW_REQUIRE(which == 0 || which == 1, LDW_ERR_ARG, "ldw_plot_links: which = %d (0 short-range, 1 long-range)", which);
+    int D = 0;
+    if (int rc = check_opts(opts, "ldw_plot_links", D)) return rc;
+    LDW_REQUIRE(which == 0 ? opts->kind != LDW_PLOT_LR : opts->kind == LDW_PLOT_LR, LDW_ERR_ARG, "ldw_plot_links: figure kind %d does not fit table %d",
+                opts->kind, which);
+    LDW_REQUIRE(png_path || rgb_out, LDW_ERR_ARG, "ldw_plot_links: neither a path nor a canvas to write to");
+    if (int rc = check_gpu(c)) return rc;
+    LDW_REQUIRE(c->POS.p != nullptr, LDW_ERR_STATE, "ldw_plot_links: no SNP meta data (ldw_set_snp_meta)");
+    LDW_REQUIRE((which == 1) == c->red_from_lr, LDW_ERR_STATE, "ldw_plot_links: the kept links are those of the %s table", c->red_from_lr ? "long-range" : "short-range");
+    const int64_t n = c->n_red;
+    LDW_REQUIRE(!use_aracne || n == 0 || (c->ar_valid && c->ar_flags.cap >= (size_t)n), LDW_ERR_STATE,
+                "ldw_plot_links: ldw_aracne_device has not run for the kept links (use_aracne = 0 draws every link as direct)");
+    CtxSrc s;
+    memset(&s, 0, sizeof(s));
+    s.row = c->red_row.as<int64_t>();
+    s.a = (which ? c->lr_a : c->sr_a).as<int32_t>();
+    s.b = (which ? c->lr_b : c->sr_b).as<int32_t>();
+    s.mi = (which ? c->lr_mi : c->sr_mi).as<double>();
+    s.POS = c->POS.as<int32_t>();
+    s.g = c->g;
+    s.srp = which ? nullptr : c->red_srp.as<double>();
+    s.meta = which ? nullptr : c->red_meta.as<uint32_t>();
+    s.flags = use_aracne && n > 0 ? c->ar_flags.as<uint8_t>() : nullptr;
+    int n_panels = 1;
+    int32_t labels[LDW_PLOT_MAX_PANELS] = {1};
+    if (opts->kind == LDW_PLOT_SR_CLUST && n > 0) {
+        // the facets: the clust_c values present, ascending
+        if (int rc = c->plot_work.reserve(1024)) return rc;
+        void *marks = c->plot_work.p;
+        LDW_HIP(hipMemsetAsync(marks, 0, 1024, c->stream));
+        hipLaunchKernelGGL(k_plot_present, dim3(grid_for(n)), dim3(256), 0, c->stream, s.meta, n, (uint32_t *)marks);
+        LDW_HIP(hipGetLastError());
+        uint32_t present[256];
+        LDW_HIP(hipMemcpyAsync(present, marks, 1024, hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipStreamSynchronize(c->stream));
+        n_panels = 0;
+        for (int k = 0; k < 256; ++k)
+            if (present[k]) {
+                LDW_REQUIRE(n_panels < LDW_PLOT_MAX_PANELS, LDW_ERR_ARG, "ldw_plot_links: more than %d clusters hold links", LDW_PLOT_MAX_PANELS);
+                s.lut[k] = (uint8_t)n_panels;
+                labels[n_panels++] = k;
+            }
+        s.facets = 1;
+    }
+    return plot_figure(c, s, nullptr, s.srp != nullptr, n, opts, n_panels, labels, png_path, rgb_out, dropped_out, "ldw_plot_links");
+}
+
+int ldw_plot_heatmap(ldw_ctx *c, const double *htm, int32_t B, int on_device, const char *title, const char *png_path, uint8_t *rgb_out) {
+    LDW_REQUIRE(c != nullptr, LDW_ERR_ARG, "ldw_plot_heatmap: null context");
+    LDW_REQUIRE(htm && B >= 1 && B <= 32768, LDW_ERR_ARG, "ldw_plot_heatmap: null map or B = %d outside 1..32768", B);
+    LDW_REQUIRE(png_path || rgb_out, LDW_ERR_ARG, "ldw_plot_heatmap: neither a path nor a canvas to write to");
+    if (int rc = check_gpu(c)) return rc;
+    const double *d = htm;
+    if (!on_device) {
+        if (int rc = c->plot_cols.reserve((size_t)B * B * 8)) return rc;
+        LDW_HIP(hipMemcpyAsync(c->plot_cols.p, htm, (size_t)B * B * 8, hipMemcpyHostToDevice, c->stream));
+        d = c->plot_cols.as<double>();
+    }
+    return heat_figure(c, d, B, title, png_path, rgb_out);
+}
+
+int ldw_plot_ldmap(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, const char *title, const char *png_path, int64_t *n_pos_out, int32_t *reducer_out,
+                   int32_t *B_out, double *htm_out, int64_t capacity) {
+    LDW_REQUIRE(c != nullptr, LDW_ERR_ARG, "ldw_plot_ldmap: null context");
+    LDW_REQUIRE(png_path, LDW_ERR_ARG, "ldw_plot_ldmap: null path");
+    const double *d_htm = nullptr;
+    if (int rc = ldmap_device(c, reducer, from, to, n_pos_out, reducer_out, B_out, true, htm_out ? capacity : -1, &d_htm)) return rc;
+    const int32_t B = *B_out;
+    if (htm_out) LDW_HIP(hipMemcpyAsync(htm_out, d_htm, (size_t)B * B * 8, hipMemcpyDeviceToHost, c->stream));
+    return heat_figure(c, d_htm, B, title, png_path, nullptr);
+}
+
+}  // extern "C"

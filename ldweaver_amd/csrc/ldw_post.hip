@@ -201,6 +201,7 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
         LDW_REQUIRE(sr_a[i] >= 0 && sr_a[i] < c->L && sr_b[i] >= 0 && sr_b[i] < c->L, LDW_ERR_ARG,
                     "ldw_lr_tukey: short-range row %lld has SNP indices (%d, %d) outside 0..%lld (a position that is not in POS?)", (long long)i, sr_a[i], sr_b[i],
                     (long long)c->L - 1);
+    c->ar_valid = false;   // the kept set changes, and ar_flags is working memory below
     if (ns > 0) {
         if (int rc = c->ar_val.reserve((size_t)ns * 4)) return rc;
         if (int rc = c->ar_val2.reserve((size_t)ns * 4)) return rc;
@@ -305,8 +306,13 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     return LDW_OK;
 }
 
-int ldw_ldmap(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t *n_pos_out, int32_t *reducer_out, int32_t *B_out,
-              double *htm_out, int64_t capacity) {
+}  // extern "C"
+
+namespace ldw {
+// ldw_ldmap up to the map on the device: *d_htm = the B x B map in the context's working memory, valid until the next call that uses the
+// short-range model's buffers.  want = false: the sizes only; capacity >= 0: refused (LDW_ERR_SIZE) when smaller than B x B.
+int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t *n_pos_out, int32_t *reducer_out, int32_t *B_out, bool want,
+                 int64_t capacity, const double **d_htm) {
     if (int rc = links_ready(c, "ldw_ldmap")) return rc;
     LDW_REQUIRE(n_pos_out && reducer_out && B_out, LDW_ERR_ARG, "ldw_ldmap: null argument");
     const int windowed = (from != 0 || to != 0) ? 1 : 0;
@@ -345,8 +351,8 @@ int ldw_ldmap(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t *n_
     const int32_t B = n_pos / r;
     *B_out = B;
     LDW_REQUIRE(B > 0, LDW_ERR_ARG, "ldw_ldmap: reducer %d larger than the %d positions", r, n_pos);
-    if (!htm_out) return LDW_OK;   // size query
-    LDW_REQUIRE(capacity >= (int64_t)B * B, LDW_ERR_SIZE, "ldw_ldmap: capacity %lld < %lld", (long long)capacity, (long long)B * B);
+    if (!want) return LDW_OK;   // size query
+    LDW_REQUIRE(capacity < 0 || capacity >= (int64_t)B * B, LDW_ERR_SIZE, "ldw_ldmap: capacity %lld < %lld", (long long)capacity, (long long)B * B);
     const int64_t nb = (int64_t)B * B;
     const int rgrid = (int)std::min<int64_t>((nb + 255) / 256, 1024);
     if (int rc = c->srm_q.reserve((size_t)nb * 16 + (size_t)rgrid * 16)) return rc;
@@ -367,7 +373,19 @@ int ldw_ldmap(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t *n_
     const double rn = mx - mn;   // 0 -> NaN everywhere, like .rescale01
     hipLaunchKernelGGL(k_ldmap_rescale, dim3(rgrid), dim3(256), 0, c->stream, htm, nb, mn, rn);
     LDW_HIP(hipGetLastError());
-    LDW_HIP(hipMemcpyAsync(htm_out, htm, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
+    *d_htm = htm;
+    return LDW_OK;
+}
+}  // namespace ldw
+
+extern "C" {
+
+int ldw_ldmap(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t *n_pos_out, int32_t *reducer_out, int32_t *B_out,
+              double *htm_out, int64_t capacity) {
+    const double *htm = nullptr;
+    if (int rc = ldmap_device(c, reducer, from, to, n_pos_out, reducer_out, B_out, htm_out != nullptr, capacity < 0 ? 0 : capacity, &htm)) return rc;
+    if (!htm_out) return LDW_OK;
+    LDW_HIP(hipMemcpyAsync(htm_out, htm, (size_t)*B_out * *B_out * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     return LDW_OK;
 }

@@ -1122,6 +1122,7 @@ int ldw_sr_pvalues(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, c
     const int64_t n = c->n_sr;
     c->n_red = c->n_pool = 0;
     c->red_from_lr = false;
+    c->ar_valid = false;
     *n_red_out = 0;
     if (n_pool_out) *n_pool_out = 0;
     if (min_mi_out) *min_mi_out = std::nan("");
@@ -1288,6 +1289,7 @@ int ldw_aracne_device(ldw_ctx *c, int64_t capacity, uint8_t *flags_out) {
     LDW_HIP(hipGetLastError());
     LDW_HIP(hipMemcpyAsync(flags_out, c->ar_flags.p, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
+    c->ar_valid = true;   // (ldw_plot_links may read the flags where they lie)
     return LDW_OK;
 }
 
@@ -1508,6 +1510,7 @@ int reduced_import_full(ldw_ctx *c, int64_t n_red, const int32_t *a, const int32
     LDW_HIP(hipStreamSynchronize(c->stream));
     c->n_red = n_red;
     c->n_pool = n_pool;
+    c->ar_valid = false;
     return LDW_OK;
 }
 

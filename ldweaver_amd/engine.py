@@ -785,13 +785,17 @@ class Engine:
         L.check(L.lib().ldw_lr_reduced_fetch(self._ctx, n, L.ptr(row), L.ptr(a), L.ptr(b), L.ptr(mi)))
         return dict(row=row, a=a, b=b, MI=mi)
 
-    def ldmap(self, reducer: int = 0, from_: int = 0, to: int = 0):
+    def ldmap(self, reducer: int = 0, from_: int = 0, to: int = 0, plot_save_path=None, plot_title=None):
         """Block-summed, log-scaled, 0..1-rescaled LD map of all links (genomewide_LDMap, R/LDSummaryPlot.R:55-106).
-        Returns (htm [B, B], n_pos, reducer)."""
+        Returns (htm [B, B], n_pos, reducer).  ``plot_save_path``: LD_plot.png is written there from the map's device copy (ldw_plot_ldmap)."""
         n_pos, r, B = C.c_int64(0), C.c_int32(0), C.c_int32(0)
         L.check(L.lib().ldw_ldmap(self._ctx, int(reducer), int(from_), int(to), C.byref(n_pos), C.byref(r), C.byref(B), None, 0))
         htm = np.empty((B.value, B.value), dtype=np.float64)
-        L.check(L.lib().ldw_ldmap(self._ctx, int(reducer), int(from_), int(to), C.byref(n_pos), C.byref(r), C.byref(B), L.ptr(htm), htm.size))
+        if plot_save_path is None:
+            L.check(L.lib().ldw_ldmap(self._ctx, int(reducer), int(from_), int(to), C.byref(n_pos), C.byref(r), C.byref(B), L.ptr(htm), htm.size))
+        else:
+            L.check(L.lib().ldw_plot_ldmap(self._ctx, int(reducer), int(from_), int(to), None if plot_title is None else str(plot_title).encode(),
+                                           os.fsencode(plot_save_path), C.byref(n_pos), C.byref(r), C.byref(B), L.ptr(htm), htm.size))
         return htm, n_pos.value, r.value
 
     # -- element-wise twins ------------------------------------------------------

@@ -27,13 +27,16 @@ def positions_to_snp_index(POS, p) -> np.ndarray:
     return order[np.minimum(k, len(srt) - 1)] if len(p) else np.zeros(0, dtype=np.int64)
 
 
-def analyse_long_range_links(eng, snp_dat, sr_links, cds_var=None, are_lrlinks_ordered: bool = False, min_links: int = 5000) -> dict:
+def analyse_long_range_links(eng, snp_dat, sr_links, cds_var=None, are_lrlinks_ordered: bool = False, min_links: int = 5000,
+                             lr_plt_path=None) -> dict:
     """Tukey outlier analysis + ARACNE of the long-range links the engine holds after ``perform_MI_computation`` /
     ``mi_all_pairs`` (the reference reads them back from lr_links.tsv).  ``sr_links`` is the short-range part of the ARACNE
     pool exactly as the reference has it: the contents of sr_links.tsv (R/lr_analyser.R:67), i.e. the REDUCED frame
     ``perform_MI_computation`` returned (srp_max > srp_cutoff) — pass that frame (pos1, pos2, MI columns) or the path of the
     tsv.  Returns the reference's ``lr_links_red`` (pos1 pos2 [clust1 clust2] len MI ARACNE, descending MI unless
-    ``are_lrlinks_ordered``) plus the thresholds.  Everything O(#links) runs on the device (ldw_lr_tukey, ldw_aracne_device)."""
+    ``are_lrlinks_ordered``) plus the thresholds.  Everything O(#links) runs on the device (ldw_lr_tukey, ldw_aracne_device).
+    ``lr_plt_path``: also write the reference's ``lr_gwes.png`` there (R/lr_analyser.R:117-127: indirect links grey under the direct ones, a
+    line at max(thresholds)), rendered from the outlier links while they are resident (ldw_plot_links)."""
     if isinstance(sr_links, (str, bytes)) or hasattr(sr_links, "__fspath__"):
         sr_links = pd.read_csv(sr_links, sep="\t", header=None, names=SR_TSV_COLS)
     POS_ = np.asarray(snp_dat.POS)
@@ -44,6 +47,10 @@ def analyse_long_range_links(eng, snp_dat, sr_links, cds_var=None, are_lrlinks_o
         warnings.warn("Not enough lr links pass the Tukey criteria, ~5000 top links were retained instead")
     red = eng.lr_reduced()
     flags = eng.aracne_device()
+    if lr_plt_path is not None:
+        from . import plots
+        plots.render_links(eng, 1, opts=plots.plot_opts(plots.L.PLOT_LR, layer_rgb=(plots.GREY, plots.LR_DIRECT), hline=float(np.max(info["thresholds"]))),
+                           use_aracne=len(flags) > 0, path=lr_plt_path)
     POS = np.asarray(snp_dat.POS)
     a, b = red["a"], red["b"]
     pos1, pos2 = POS[b].astype(np.int64), POS[a].astype(np.int64)     # to side = pos1, from side = pos2 (R/computePairwiseMI.R:319-320)
@@ -58,9 +65,11 @@ def analyse_long_range_links(eng, snp_dat, sr_links, cds_var=None, are_lrlinks_o
     return dict(lr_links_red=df, q13=info["q13"], thresholds=info["thresholds"], fallback=info["fallback"], n_pool=info["n_pool"])
 
 
-def genomewide_LDMap(eng, snp_dat, reducer=None, from_=None, to=None) -> dict:
+def genomewide_LDMap(eng, snp_dat, reducer=None, from_=None, to=None, plot_save_path=None, plot_title=None) -> dict:
     """Numeric core of ``genomewide_LDMap``: the reduced, log10-scaled, 0..1-rescaled LD matrix ``htm`` with its row /
-    column labels (the reference's ``nms``: pos_vec[seq(1, n, by = reducer - 1)][1:B], R/LDSummaryPlot.R:95-96)."""
+    column labels (the reference's ``nms``: pos_vec[seq(1, n, by = reducer - 1)][1:B], R/LDSummaryPlot.R:95-96).
+    ``plot_save_path``: also write the reference's ``LD_plot.png`` there (R/LDSummaryPlot.R:121-128), rendered from the map's device copy
+    (ldw_plot_ldmap), under ``plot_title``."""
     if reducer is not None and reducer < 0:     # :30-35
         warnings.warn("<reducer> for genomewide_LDMap should be >0, set to default")
         reducer = None
@@ -74,5 +83,8 @@ def genomewide_LDMap(eng, snp_dat, reducer=None, from_=None, to=None) -> dict:
             raise ValueError("<from> and <to> must be positive values")
         from_, to = int(round(from_)), int(round(to))
     r = 0 if reducer is None else int(np.round(reducer))
-    htm, n_pos, r = eng.ldmap(r, from_ or 0, to or 0)
+    if plot_save_path is None:
+        htm, n_pos, r = eng.ldmap(r, from_ or 0, to or 0)
+    else:
+        htm, n_pos, r = eng.ldmap(r, from_ or 0, to or 0, plot_save_path=plot_save_path, plot_title=plot_title)
     return dict(htm=htm, n_pos=n_pos, reducer=r)
