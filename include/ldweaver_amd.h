@@ -556,6 +556,45 @@ int ldw_plot_heatmap(ldw_ctx *ctx, const double *htm, int32_t B, int on_device, 
 int ldw_plot_ldmap(ldw_ctx *ctx, int32_t reducer, int32_t from, int32_t to, const char *title, const char *png_path, int64_t *n_pos_out,
                    int32_t *reducer_out, int32_t *B_out, double *htm_out, int64_t capacity);
 
+/* ---- (13) numeric link tables read on the device — the readers of R/io_functions.R:32-66 (read_LongRangeLinks, read_ShortRangeLinks), and through them
+ *           the file inputs of genomewide_LDMap (R/LDSummaryPlot.R), analyse_long_range_links (R/lr_analyser.R) and make_gwes_plots -----------------------
+ * A text file, plain or gzip (read with zlib), no header, ONE separator byte ('\t' or ' '), every cell a number.  Lines end at '\n'; one '\r' before it is
+ * stripped; empty lines are skipped; the last line need not end in a newline; a line may hold at most 2^20 bytes.  A number is: an optional sign, digits
+ * with an optional '.' and more digits (at least one digit in all), an optional exponent (e or E, optional sign, digits) — or one of the tokens NA NaN nan
+ * (NaN) Inf inf -Inf -inf.  No hex, no separators of thousands, no quotes, no blanks round a cell.  The value of a cell is the correctly rounded double of
+ * its decimal text (Python's float()): cells with at most 19 significant digits, a mantissa <= 2^53 and a decimal exponent in [-22, 22] are converted on
+ * the device by one fp64 operation, all others ("slow cells") by the host's strtod from the chunk it still holds — they cost time, never a bit.
+ * Refusals (LDW_ERR_ARG, ldw_last_error() names the file, the 1-based physical line and the 1-based column; the earliest bad line of the file wins, and
+ * inside it the leftmost fault): a cell that is not a number, a line that ends before its ncols-th field (column = the first missing field), a line with
+ * more fields (column = ncols + 1), a line that is too long.  A file without rows is no error.  Row order is file order.  Host memory is O(chunk). */
+/* Host only, no context: the fields of the first non-empty line (0 for a file without one) and whether the file is gzip (gz_out may be NULL). */
+int ldw_tsv_probe(const char *path, int sep, int32_t *ncols_out, int32_t *gz_out);
+/* Parses the file into the context's columns (ncols in 1..16), replacing those of the last call, in chunks of chunk_bytes (0: 64 MiB; at most 2^30) read
+ * through two pinned buffers that ldw_host_trim gives back.  *rows_out rows; *slow_cells_out cells the host converted; bit k of *int_cols_mask_out: every
+ * cell of column k was a plain integer literal [+-]?[0-9]+ (0 for a file without rows).  Any output may be NULL.  After a refusal the context holds no
+ * table (rows = 0) and works on. */
+int ldw_tsv_read(ldw_ctx *ctx, const char *path, int sep, int32_t ncols, int64_t chunk_bytes, int64_t *rows_out, int64_t *slow_cells_out,
+                 uint32_t *int_cols_mask_out);
+/* The table itself, without a copy: a DEVICE pointer to the context's own columns, doubles, column k at device_ptr + k * stride (NULL when rows = 0);
+ * read-only.  Valid until the next ldw_tsv_read and never past ldw_ctx_destroy: synchronise every stream that reads them before either, as for
+ * ldw_links_device_ptrs.  LDW_ERR_STATE before the first ldw_tsv_read. */
+int ldw_tsv_columns(ldw_ctx *ctx, const double **device_ptr_out, int64_t *rows_out, int32_t *ncols_out, int64_t *stride_out);
+/* one column (0-based) copied out: dst holds `capacity` >= rows doubles, host or device memory */
+int ldw_tsv_fetch(ldw_ctx *ctx, int32_t col, double *dst, int64_t capacity, int on_device);
+/* Positions for a context WITHOUT an alignment — a directory that holds the link files of an earlier job and nothing else: POS[L] (any order, repeats
+ * allowed, like snp.dat$POS) and the genome length g (0: not known; ldw_plot_links(which = 1), which takes len from POS and g, then answers LDW_ERR_STATE).
+ * What the context held of an alignment — states, weights, r, uqe, paint — and both link tables are dropped.  Enough for ldw_links_load, ldw_links_import,
+ * ldw_ldmap / ldw_plot_ldmap, ldw_lr_tukey, ldw_lr_reduced_fetch, ldw_aracne_device and ldw_plot_links(which = 1); entry points that need the alignment,
+ * the weights, uqe or the paint (the MI pass, the short-range model, the tsv writers, ...) keep answering LDW_ERR_STATE until ldw_set_alignment. */
+int ldw_set_positions(ldw_ctx *ctx, const int32_t *POS, int64_t L, double g);
+/* The columns of the last ldw_tsv_read become the context's short-range (which = 0) or long-range (1) table, exactly as ldw_links_import(on_device = 1)
+ * would install it, all on the device: rows whose min_len_col value is below min_len are dropped (min_len_col = -1: none; the reference's `len < sr_dist`
+ * drop of long-range files; a NaN stays, as in R); pos1_col maps to the to-side SNP index and pos2_col to the from-side one by the positions of
+ * ldw_set_snp_meta or ldw_set_positions, the FIRST SNP at a position; mi_col is the MI column.  Refused (LDW_ERR_ARG, with the file, line and column of the
+ * first such row that stays): a position that is not an integer, does not fit in 32 bits, or is no SNP's.  flags: 0.  *n_out (may be NULL): rows installed. */
+int ldw_links_load(ldw_ctx *ctx, int which, int32_t pos1_col, int32_t pos2_col, int32_t mi_col, int32_t min_len_col, double min_len, int32_t flags,
+                   int64_t *n_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

@@ -11,6 +11,7 @@ _EXPORTS = {
     "read_TopHits": "output", "read_AnnotatedLinks": "output",
     "perform_snpEff_annotations": "annotate",
     "make_gwes_plots": "plots", "read_ShortRangeLinks": "plots", "read_LongRangeLinks": "plots",
+    "read_links_native": "links_io",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -12,6 +12,7 @@
 #include "ldw_internal.h"
 #include "ldw_dev.h"
 #include "ldw_fasta.h"
+#include "ldw_links_read.h"
 
 // ------------------------------------------------------------------------------------------------
 // error plumbing
@@ -453,7 +454,7 @@ __global__ void k_fast_hadamard(double *__restrict__ MI, const double *__restric
 }
 
 int launch_state_counts(ldw_ctx *c) {
-    LDW_REQUIRE(c->L > 0, LDW_ERR_STATE, "state counts: no alignment resident");
+    LDW_REQUIRE(ldw::have_alignment(c), LDW_ERR_STATE, "state counts: no alignment resident");
     if (int rc = c->counts.reserve((size_t)c->L * 5 * 4)) return rc;
     hipLaunchKernelGGL(k_counts_marginals, dim3((unsigned)((c->L + 3) / 4)), dim3(256), 0, c->stream, c->states.as<uint8_t>(), c->L, c->Npad, (const int64_t *)nullptr,
                        c->counts.as<int32_t>(), (int64_t *)nullptr);
@@ -609,6 +610,7 @@ int ldw_ctx_destroy(ldw_ctx *c) {
     ldw::DrainedScope drained;   // every stream that could touch this context's blocks is idle: no device-wide synchronisation per released block
     ldw::fasta_release(c);
     ldw::out_release(c);
+    ldw::tsv_release(c);
     ldw::DevBuf *bufs[] = {&c->srm_tmp, &c->chars, &c->states, &c->digits, &c->vfixed, &c->r, &c->uqe, &c->POS, &c->paint, &c->Mbits, &c->row0,
                            &c->slot_meta, &c->slot_pfix, &c->apx_skip, &c->snp_sup, &c->counts, &c->pfix_state, &c->G, &c->MIblk, &c->rowlist_f, &c->rowlist_t,
                            &c->idx_f, &c->idx_t, &c->lrow_f, &c->lrow_t, &c->perm_f, &c->perm_t, &c->scr_units, &c->epi_rest, &c->slot_pfix_hi, &c->glo, &c->lo_rows, &c->packs, &c->colcnt,
@@ -873,6 +875,7 @@ int ldw::set_dims(ldw_ctx *c, int64_t L, int64_t N) {
     c->rows_ready = false;
     c->have_weights = false;
     c->have_meta = false;
+    c->pos_only = false;
     return c->states.reserve((size_t)L * c->Npad);
 }
 }
@@ -895,7 +898,7 @@ int ldw_set_alignment(ldw_ctx *c, const uint8_t *states, int64_t L, int64_t N, i
 
 int ldw_get_alignment(ldw_ctx *c, uint8_t *out) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(out && c->L > 0, LDW_ERR_STATE, "ldw_get_alignment: no alignment resident");
+    LDW_REQUIRE(out && ldw::have_alignment(c), LDW_ERR_STATE, "ldw_get_alignment: no alignment resident");
     if (int rc = c->scratch.reserve((size_t)c->L * c->N)) return rc;
     hipLaunchKernelGGL(k_unpad_states, dim3((unsigned)c->L), dim3(256), 0, c->stream, c->states.as<uint8_t>(), c->scratch.as<uint8_t>(),
                        c->L, c->N, c->Npad);
@@ -907,7 +910,7 @@ int ldw_get_alignment(ldw_ctx *c, uint8_t *out) {
 
 int ldw_state_counts(ldw_ctx *c, int32_t *counts_out) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(counts_out && c->L > 0, LDW_ERR_STATE, "ldw_state_counts: no alignment resident");
+    LDW_REQUIRE(counts_out && ldw::have_alignment(c), LDW_ERR_STATE, "ldw_state_counts: no alignment resident");
     if (int rc = ldw::launch_state_counts(c)) return rc;
     // stored [L][5] row-major == 5 x L column-major (ACGTN_table layout)
     LDW_HIP(hipMemcpyAsync(counts_out, c->counts.p, (size_t)c->L * 20, hipMemcpyDeviceToHost, c->stream));
@@ -966,7 +969,7 @@ int ldw_encode_alignment(ldw_ctx *c, const char *chars, int64_t N, int64_t L_tot
 // ---- weights / meta -------------------------------------------------------------------------------
 int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->L > 0, LDW_ERR_STATE, "ldw_set_weights: set the alignment first");
+    LDW_REQUIRE(ldw::have_alignment(c), LDW_ERR_STATE, "ldw_set_weights: set the alignment first");
     LDW_REQUIRE(hdw && N == c->N, LDW_ERR_ARG, "ldw_set_weights: hdw has %lld entries, alignment has %lld sequences",
                 (long long)N, (long long)c->N);
     if (nlimbs == 0) nlimbs = 5;
@@ -1084,7 +1087,7 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
 
 int ldw_set_snp_meta(ldw_ctx *c, const double *r, const uint8_t *uqe, const int32_t *POS, const int32_t *paint, double g) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->L > 0, LDW_ERR_STATE, "ldw_set_snp_meta: set the alignment first");
+    LDW_REQUIRE(ldw::have_alignment(c), LDW_ERR_STATE, "ldw_set_snp_meta: set the alignment first");
     if (int rc = ldw_tsv_join(c)) return rc;   // (a pending asynchronous table reads the positions this call replaces)
     LDW_REQUIRE(r && uqe && POS, LDW_ERR_ARG, "ldw_set_snp_meta: null argument");
     LDW_REQUIRE(g > 0, LDW_ERR_ARG, "ldw_set_snp_meta: genome length g must be positive (snp.dat$g)");
@@ -1250,7 +1253,7 @@ int ensure_rows(ldw_ctx *c) {
         (void)hipStreamSynchronize(c->stream);
         fprintf(stderr, "[ldw] ensure_rows: %.2f ms at %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_rows0).count(), what);
     };
-    LDW_REQUIRE(c->L > 0 && c->have_weights && c->have_meta, LDW_ERR_STATE,
+    LDW_REQUIRE(ldw::have_alignment(c) && c->have_weights && c->have_meta, LDW_ERR_STATE,
                 "MI needs the alignment, the weights and the SNP meta data to be set first");
     const int64_t L = c->L, Npad = c->Npad;
     if (int rc = c->counts.reserve((size_t)L * 20)) return rc;

@@ -198,7 +198,7 @@ extern "C" {
 int ldw_cds_variation(ldw_ctx *c, const int32_t *POS, int64_t L, const char *ref_seq, int64_t g, const int32_t *cds_start, const int32_t *cds_end,
                       int64_t ncds, double *var_out, int64_t *snp_var_out, uint8_t *alt_mask_out, char *ref_out) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->L > 0, LDW_ERR_STATE, "ldw_cds_variation: no alignment resident");
+    LDW_REQUIRE(ldw::have_alignment(c), LDW_ERR_STATE, "ldw_cds_variation: no alignment resident");
     LDW_REQUIRE(POS && ref_seq, LDW_ERR_ARG, "ldw_cds_variation: null argument");
     LDW_REQUIRE(L == c->L, LDW_ERR_ARG, "ldw_cds_variation: L = %lld but the resident alignment has %lld SNPs", (long long)L, (long long)c->L);
     LDW_REQUIRE(g >= 1 && g < ((int64_t)1 << 31), LDW_ERR_ARG, "ldw_cds_variation: reference length %lld outside 1..2^31-1", (long long)g);

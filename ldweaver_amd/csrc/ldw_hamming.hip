@@ -202,7 +202,7 @@ static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sh
         fprintf(stderr, "[ldw host] hamming: %-28s %7.3f ms (+%.3f)\n", what, t, t - t_last);
         t_last = t;
     };
-    LDW_REQUIRE(c->L > 0, LDW_ERR_STATE, "ldw_hamming_weights: set the alignment first");
+    LDW_REQUIRE(ldw::have_alignment(c), LDW_ERR_STATE, "ldw_hamming_weights: set the alignment first");
     const bool strip = tile0 >= 0;
     LDW_REQUIRE(strip ? counts_out != nullptr : hdw_out != nullptr, LDW_ERR_ARG, "ldw_hamming_weights: output is null");
     const int64_t L = c->L, N = c->N, Npad = c->Npad, KW = c->KW;

@@ -80,6 +80,7 @@ struct ldw_ctx {
     int64_t cN = 0, cL = 0;
     void *fasta = nullptr;           // scan state of the native FASTA feeder (ldw_fasta.hip: FastaScan), made by ldw_fasta_scan
     void *out = nullptr;             // staging of the alignment writer (ldw_out.hip: OutState), made by ldw_write_alignment
+    void *tsv = nullptr;             // the link-table reader (ldw_links_read.hip: TsvState), made by ldw_tsv_read
 
     // ---- weights ----
     bool have_weights = false;
@@ -163,6 +164,7 @@ struct ldw_ctx {
 
     // ---- per-SNP meta ----
     bool have_meta = false;
+    bool pos_only = false;       // ldw_set_positions: L, POS and g stand for a job whose alignment is not here (no states, weights, r, uqe or paint)
     double g = 0;
     ldw::DevBuf r, uqe, POS, paint;  // double[L], uint8[L][5], int32[L], int32[L]
     std::vector<double> h_r;
@@ -297,6 +299,7 @@ int launch_cooc_popc(ldw_ctx *ctx, const int32_t *rowlist_t, int RTpad, const in
 int fill_rows_bits(ldw_ctx *ctx, const int32_t *d_rowinfo, int64_t R);
 int prepare_apx_weights(ldw_ctx *ctx);   // ldw_apx.hip: dual digits, exponents, popcount segments from h_vfixed / h_seq_perm
 int check_gpu(ldw_ctx *ctx);
+inline bool have_alignment(const ldw_ctx *ctx) { return ctx->L > 0 && !ctx->pos_only; }   // (ldw_set_positions sets L without one)
 int ensure_hi_marginals(ldw_ctx *ctx);   // slot_pfix_hi on demand (mixed-precision path)
 void lr_stream_push(ldw_ctx *ctx, hipStream_t s, const int64_t *d_lr_count, int64_t blocks_done);   // ldw_tsv.cpp: no-ops without an open stream
 void lr_stream_drain(ldw_ctx *ctx);

@@ -1,0 +1,825 @@
+// The native reader of numeric link tables on the device (include/ldweaver_amd.h 13): a chunk of the file's bytes goes to the device
+// through one of two pinned buffers; k_tsv_count / k_tsv_starts find the first byte of every non-empty line, k_tsv_parse turns every row into doubles
+// (Clinger's fast path: a decimal mantissa of at most 2^53 times or over an exact power of ten is ONE correctly rounded fp64 operation; every other
+// cell goes to a list the host converts with strtod), and ldw_links_load maps a parsed table's positions to SNP indices and installs it as the
+// context's short-range or long-range table.
+// No contraction in this file: m * 1e^k must be rounded once, as a product.
+#pragma clang fp contract(off)
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "ldw_internal.h"
+#include "ldw_fasta.h"
+#include "ldw_links_read.h"
+#include "ldw_prim.h"
+
+using namespace ldw;
+
+namespace {
+
+constexpr int TSV_BLOCK = 256;
+constexpr int TSV_TILE = TSV_BLOCK * 16;   // bytes of a chunk one block of the line kernels scans: 16 per thread, one 128-bit load
+constexpr int TSV_STAGE = 32768;           // bytes of LDS a block of the staged parse kernel may fill with its rows' text
+// reasons a row is refused (the low byte of the bad-row key)
+enum { BAD_CELL = 1, BAD_MISSING = 2, BAD_EXTRA = 3, BAD_LONG = 4 };
+// ... and a position of ldw_links_load
+enum { POS_FRACTION = 1, POS_RANGE = 2, POS_UNKNOWN = 3 };
+
+struct TsvResult {   // what a chunk's kernels report (device, copied to a pinned twin)
+    unsigned long long bad;      // min over the refused rows of row << 16 | column (1-based) << 8 | reason; ~0: none
+    uint32_t rows, slow, not_int, pad;
+};
+
+__device__ const double kPow10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
+                                      1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+
+// bit j: byte base + j is the first byte of a non-empty line (the byte before it is '\n', it is neither '\n' nor the '\r' of a "\r\n").  buf[-1] and
+// the bytes behind the data are '\n' (TSV_FRONT, TSV_TAIL).
+__device__ __forceinline__ uint32_t start_mask16(const uint8_t *__restrict__ buf, uint32_t base) {
+    const uint4 w = *reinterpret_cast<const uint4 *>(buf + base);
+    const uint32_t v[4] = {w.x, w.y, w.z, w.w};
+    uint8_t prev = buf[(int64_t)base - 1];
+    const uint8_t after = buf[base + 16];
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const uint8_t cur = (uint8_t)(v[j >> 2] >> (8 * (j & 3)));
+        const uint8_t next = j < 15 ? (uint8_t)(v[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) : after;
+        if (prev == '\n' && cur != '\n' && !(cur == '\r' && next == '\n')) m |= 1u << j;
+        prev = cur;
+    }
+    return m;
+}
+
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *sh) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// cnt[block] = rows that start in the block's TSV_TILE bytes
+__global__ __launch_bounds__(TSV_BLOCK) void k_tsv_count(const uint8_t *__restrict__ buf, uint32_t n, uint32_t *__restrict__ cnt) {
+    __shared__ uint32_t sh[4];
+    const uint32_t base = blockIdx.x * TSV_TILE + threadIdx.x * 16;
+    const uint32_t c = base < n ? __popc(start_mask16(buf, base)) : 0;
+    const uint32_t s = block_sum(c, sh);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = s;
+}
+
+// starts[off[block] + k] = byte offset of the block's k-th row, in file order
+__global__ __launch_bounds__(TSV_BLOCK) void k_tsv_starts(const uint8_t *__restrict__ buf, uint32_t n, const uint32_t *__restrict__ off, uint32_t *__restrict__ starts) {
+    __shared__ uint32_t wsum[4];
+    const uint32_t base = blockIdx.x * TSV_TILE + threadIdx.x * 16;
+    uint32_t m = base < n ? start_mask16(buf, base) : 0;
+    const uint32_t c = __popc(m);
+    // exclusive prefix of c over the block: inside the wave by shuffles, over the four waves through LDS
+    uint32_t incl = c;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t before = off[blockIdx.x] + incl - c;
+    for (int w = 0; w < wave; ++w) before += wsum[w];
+    while (m) {
+        const int j = __ffs(m) - 1;
+        m &= m - 1;
+        starts[before++] = base + (uint32_t)j;
+    }
+}
+
+__device__ __forceinline__ bool is_digit(uint8_t c) { return (uint8_t)(c - '0') <= 9; }
+
+// One row: ncols cells from p[0 ..] into cols[c * stride + row].  Returns 0, or column << 8 | reason of the first thing that is wrong, left to right.
+// *not_int gets a bit for every column whose cell is not a plain integer literal [+-]?[0-9]+; a cell outside the fast path is appended to slow[].
+template <class P>
+__device__ __forceinline__ uint32_t parse_row(P p, int ncols, uint8_t sep, double *__restrict__ cols, int64_t stride, int64_t row, uint32_t row_in_chunk,
+                                              uint32_t row_off, uint32_t *__restrict__ slow_n, uint2 *__restrict__ slow, uint32_t *not_int) {
+    uint32_t i = 0;
+    for (int col = 0; col < ncols; ++col) {
+        const uint32_t cell = i;
+        uint8_t c = p[i];
+        bool neg = false, sgn = false;
+        if (c == '-' || c == '+') {
+            neg = c == '-';
+            sgn = true;
+            c = p[++i];
+        }
+        double v;
+        bool plain = true;
+        if (is_digit(c) || c == '.') {
+            uint64_t m = 0;
+            int nd = 0, dexp = 0;
+            bool any = false, dropped = false;
+            while (is_digit(c)) {
+                any = true;
+                const uint32_t d = c - '0';
+                if (m != 0 || d != 0) {
+                    if (nd < 19) {
+                        m = m * 10 + d;
+                        ++nd;
+                    } else {
+                        dropped = true;
+                        if (dexp < 100000) ++dexp;
+                    }
+                }
+                c = p[++i];
+            }
+            if (c == '.') {
+                plain = false;
+                c = p[++i];
+                while (is_digit(c)) {
+                    any = true;
+                    const uint32_t d = c - '0';
+                    if (m != 0 || d != 0) {
+                        if (nd < 19) {
+                            m = m * 10 + d;
+                            ++nd;
+                            --dexp;
+                        } else {
+                            dropped = true;
+                        }
+                    } else if (dexp > -100000) {
+                        --dexp;
+                    }
+                    c = p[++i];
+                }
+            }
+            if (!any) return (uint32_t)(col + 1) << 8 | BAD_CELL;
+            if (c == 'e' || c == 'E') {
+                plain = false;
+                c = p[++i];
+                bool eneg = false;
+                if (c == '-' || c == '+') {
+                    eneg = c == '-';
+                    c = p[++i];
+                }
+                if (!is_digit(c)) return (uint32_t)(col + 1) << 8 | BAD_CELL;
+                int e = 0;
+                while (is_digit(c)) {
+                    if (e < 100000) e = e * 10 + (c - '0');
+                    c = p[++i];
+                }
+                dexp += eneg ? -e : e;
+            }
+            if (m == 0) {
+                v = 0.0;
+            } else if (!dropped && m <= (1ull << 53) && dexp >= -22 && dexp <= 22) {
+                const double dm = (double)m;   // exact
+                v = dexp < 0 ? dm / kPow10[-dexp] : dm * kPow10[dexp];
+            } else {
+                const uint32_t k = atomicAdd(slow_n, 1u);
+                slow[k] = make_uint2(row_in_chunk * (uint32_t)ncols + (uint32_t)col, row_off + cell);
+                v = 0.0;
+                neg = false;
+            }
+            if (neg) v = -v;
+        } else {
+            plain = false;
+            if (!sgn && c == 'N' && p[i + 1] == 'A') {
+                v = __longlong_as_double(0x7ff8000000000000ll);
+                i += 2;
+            } else if (!sgn && ((c == 'N' && p[i + 1] == 'a' && p[i + 2] == 'N') || (c == 'n' && p[i + 1] == 'a' && p[i + 2] == 'n'))) {
+                v = __longlong_as_double(0x7ff8000000000000ll);
+                i += 3;
+            } else if ((!sgn || neg) && (c == 'I' || c == 'i') && p[i + 1] == 'n' && p[i + 2] == 'f') {
+                v = __longlong_as_double(neg ? 0xfff0000000000000ll : 0x7ff0000000000000ll);
+                i += 3;
+            } else {
+                return (uint32_t)(col + 1) << 8 | BAD_CELL;
+            }
+            c = p[i];
+        }
+        if (!plain) *not_int |= 1u << col;
+        const bool eol = c == '\n' || (c == '\r' && p[i + 1] == '\n');
+        if (col + 1 < ncols) {
+            if (eol) return (uint32_t)(col + 2) << 8 | BAD_MISSING;
+            if (c != sep) return (uint32_t)(col + 1) << 8 | BAD_CELL;
+            ++i;
+        } else if (!eol) {
+            return c == sep ? (uint32_t)(ncols + 1) << 8 | BAD_EXTRA : (uint32_t)(col + 1) << 8 | BAD_CELL;
+        }
+        cols[(int64_t)col * stride + row] = v;
+    }
+    return 0;
+}
+
+// One row per thread, adjacent lanes adjacent rows.  STAGED: the block first copies the text of its 256 rows into LDS with 128-bit loads (adjacent lanes
+// adjacent 16 bytes) and the threads walk their rows there; a block whose rows span more than TSV_STAGE bytes reads global memory like the other form.
+template <bool STAGED>
+__global__ __launch_bounds__(TSV_BLOCK) void k_tsv_parse(const uint8_t *__restrict__ buf, uint32_t n, const uint32_t *__restrict__ starts, uint32_t nrows, int ncols,
+                                                         uint8_t sep, double *__restrict__ cols, int64_t stride, int64_t row0, TsvResult *__restrict__ res,
+                                                         uint2 *__restrict__ slow) {
+    __shared__ uint32_t sh_not_int;
+    __shared__ uint4 tile[STAGED ? TSV_STAGE / 16 + 1 : 1];
+    if (threadIdx.x == 0) sh_not_int = 0;
+    const uint32_t r0 = blockIdx.x * TSV_BLOCK, r = r0 + threadIdx.x;
+    uint32_t lo = 0;
+    bool staged = false;
+    if (STAGED) {
+        const uint32_t r1 = min(r0 + TSV_BLOCK, nrows);
+        lo = starts[r0] & ~15u;
+        const uint32_t hi = r1 < nrows ? starts[r1] : n;   // (the byte before the next block's first row is a '\n': every row of this one ends below hi)
+        staged = hi - lo <= TSV_STAGE;
+        if (staged)
+            for (uint32_t k = threadIdx.x; k < (hi - lo + 15) / 16 + 1; k += TSV_BLOCK) tile[k] = *reinterpret_cast<const uint4 *>(buf + lo + 16 * k);
+    }
+    __syncthreads();
+    uint32_t not_int = 0;
+    if (r < nrows) {
+        const uint32_t s = starts[r];
+        const uint32_t nxt = r + 1 < nrows ? starts[r + 1] : n;
+        uint32_t bad = 0;
+        if (nxt - s > (uint32_t)TSV_LINE_MAX) {   // (rare: a long line, or a run of empty lines behind this one)
+            uint32_t e = s;
+            while (buf[e] != '\n') ++e;
+            if (e - s > (uint32_t)TSV_LINE_MAX) bad = 1u << 8 | BAD_LONG;
+        }
+        if (!bad) {
+            if (STAGED && staged)
+                bad = parse_row(reinterpret_cast<const uint8_t *>(tile) + (s - lo), ncols, sep, cols, stride, row0 + r, r, s, &res->slow, slow, &not_int);
+            else
+                bad = parse_row(buf + s, ncols, sep, cols, stride, row0 + r, r, s, &res->slow, slow, &not_int);
+        }
+        if (bad) atomicMin(&res->bad, (unsigned long long)r << 16 | bad);
+    }
+    if (not_int) atomicOr(&sh_not_int, not_int);
+    __syncthreads();
+    if (threadIdx.x == 0 && sh_not_int) atomicOr(&res->not_int, sh_not_int);
+}
+
+__global__ __launch_bounds__(256) void k_tsv_init(TsvResult *res, uint32_t keep_not_int, const uint32_t *__restrict__ off, uint32_t nblocks) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        res->bad = ~0ull;
+        res->slow = 0;
+        if (!keep_not_int) res->not_int = 0;
+        res->rows = off[nblocks];   // the exclusive sums end with the total
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tsv_patch(const uint32_t *__restrict__ cell, const double *__restrict__ val, uint32_t n, int ncols, double *__restrict__ cols,
+                                                   int64_t stride, int64_t row0) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k < n) cols[(int64_t)(cell[k] % (uint32_t)ncols) * stride + row0 + cell[k] / (uint32_t)ncols] = val[k];
+}
+
+// ---- ldw_links_load ---------------------------------------------------------------------------------------------------------------------------
+
+// first index k with srt[k] >= v
+__device__ __forceinline__ int32_t lower_bound_i32(const int32_t *__restrict__ srt, int32_t L, int32_t v) {
+    int32_t lo = 0, hi = L;
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (srt[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// keep[i] = the row stays (its min_len_col value is not below min_len); for those: idx1 / idx2 = SNP index of pos1 / pos2 (the first SNP at that position:
+// srt = positions ascending, order = the SNP of every sorted position, null when POS itself ascends).  bad = min of row << 8 | file column << 4 | reason:
+// the leftmost fault of the earliest bad row.
+__global__ __launch_bounds__(256) void k_links_map(const double *__restrict__ p1, const double *__restrict__ p2, const double *__restrict__ len, double min_len, int64_t n,
+                                                   const int32_t *__restrict__ srt, const int32_t *__restrict__ order, int32_t L, uint32_t col1, uint32_t col2, uint32_t *__restrict__ keep,
+                                                   int32_t *__restrict__ idx1, int32_t *__restrict__ idx2, unsigned long long *__restrict__ bad) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const bool k = len == nullptr || !(len[i] < min_len);
+        keep[i] = k;
+        if (!k) continue;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const double v = e ? p2[i] : p1[i];
+            uint32_t why = 0;
+            int32_t at = 0;
+            if (!(v == floor(v)) || isinf(v)) {
+                why = POS_FRACTION;
+            } else if (v < -2147483648.0 || v > 2147483647.0) {
+                why = POS_RANGE;
+            } else {
+                const int32_t q = (int32_t)v;
+                at = lower_bound_i32(srt, L, q);
+                if (at >= L || srt[at] != q) why = POS_UNKNOWN;
+                else if (order) at = order[at];
+            }
+            if (why) atomicMin(bad, (unsigned long long)i << 8 | (e ? col2 : col1) << 4 | why);
+            (e ? idx2 : idx1)[i] = at;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_links_compact(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ off, const int32_t *__restrict__ idx1,
+                                                       const int32_t *__restrict__ idx2, const double *__restrict__ mi, int64_t n, int32_t *__restrict__ a,
+                                                       int32_t *__restrict__ b, double *__restrict__ out_mi) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        if (keep[i]) {
+            const uint32_t j = off[i];
+            a[j] = idx2[i];   // from side = pos2
+            b[j] = idx1[i];   // to side = pos1 (R/computePairwiseMI.R:319-320)
+            out_mi[j] = mi[i];
+        }
+}
+
+// ---- the reader's state -----------------------------------------------------------------------------------------------------------------------
+
+struct TsvState {
+    void *pin[2] = {nullptr, nullptr};   // pinned chunk buffers: TSV_FRONT '\n', the data, TSV_TAIL '\n'
+    size_t pin_cap = 0;
+    TsvResult *pin_res = nullptr;        // pinned twin of res, one per chunk buffer
+    DevBuf img, cnt, off, starts, slow, res, patch, scan_tmp;
+    DevBuf cols;                         // double [ncols][stride], column-major: the parsed table
+    int64_t rows = 0, stride = 0;
+    int ncols = 0;
+    int64_t grows = 0;                   // times the columns were moved to a larger buffer (since the context was made)
+    hipEvent_t ev[2][6] = {};            // per chunk buffer: before / after the copy, after the line kernels, before / after the parse kernel, after the patch
+    std::string path;                    // of the last read, for the line numbers of ldw_links_load's refusals
+    int variant = 0;                     // 0: rows parsed from cached global loads, 1: from an LDS-staged tile
+    double ms[8] = {};                   // last read: total, read (host), copy, line kernels, parse kernel, slow-cell patch, chunks, bytes
+    DevBuf keep, koff, idx1, idx2, bad, srt, order;   // ldw_links_load
+};
+
+TsvState *tsv_state(ldw_ctx *c) {
+    if (!c->tsv) c->tsv = new TsvState();
+    return static_cast<TsvState *>(c->tsv);
+}
+
+int64_t free_pins(TsvState *t) {
+    int64_t n = 0;
+    for (auto &p : t->pin) {
+        if (p) {
+            (void)hipHostFree(p);
+            n += (int64_t)t->pin_cap;
+        }
+        p = nullptr;
+    }
+    t->pin_cap = 0;
+    return n;
+}
+
+int ensure_pins(TsvState *t, size_t bytes) {
+    for (auto &row : t->ev)
+        for (auto &e : row)
+            if (!e) LDW_HIP(hipEventCreate(&e));
+    if (!t->pin_res) LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->pin_res), 2 * sizeof(TsvResult), hipHostMallocDefault));
+    if (t->pin_cap < bytes) {
+        free_pins(t);
+        for (auto &p : t->pin)
+            if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                p = nullptr;
+                free_pins(t);
+                set_error("ldw_tsv_read: hipHostMalloc of %zu bytes failed", bytes);
+                return LDW_ERR_HIP;
+            }
+        t->pin_cap = bytes;
+    }
+    return LDW_OK;
+}
+
+// room for `rows` rows: the columns move to a buffer of a larger stride (every column by one device-to-device copy)
+int grow_columns(ldw_ctx *c, TsvState *t, int64_t rows) {
+    if (rows <= t->stride && t->cols.p) return LDW_OK;
+    int64_t stride = std::max<int64_t>(rows, t->stride + t->stride / 2);
+    stride = (stride + 1023) / 1024 * 1024;
+    if ((size_t)stride * 8 * (size_t)t->ncols <= t->cols.cap && t->rows == 0) {   // (an empty table has nothing to move: the buffer it has is re-cut)
+        t->stride = (int64_t)(t->cols.cap / 8 / (size_t)t->ncols);
+        return LDW_OK;
+    }
+    DevBuf nb;
+    if (int rc = nb.reserve((size_t)stride * 8 * (size_t)t->ncols)) return rc;
+    if (t->rows > 0) {
+        LDW_HIP(hipMemcpy2DAsync(nb.p, (size_t)stride * 8, t->cols.p, (size_t)t->stride * 8, (size_t)t->rows * 8, (size_t)t->ncols, hipMemcpyDeviceToDevice, c->stream));
+        LDW_HIP(hipStreamSynchronize(c->stream));
+    }
+    t->cols.release();
+    t->cols = nb;
+    t->stride = stride;
+    ++t->grows;
+    return LDW_OK;
+}
+
+int refuse_row(const char *path, int64_t row, uint32_t col, uint32_t reason, int ncols) {
+    int64_t line = 0;
+    (void)tsv_line_of_row(path, row, &line);
+    switch (reason) {
+    case BAD_MISSING: set_error("ldw_tsv_read: %s: line %lld, column %u: the line ends after %u of %d fields", path, (long long)line, col, col - 1, ncols); break;
+    case BAD_EXTRA: set_error("ldw_tsv_read: %s: line %lld, column %u: more than %d fields", path, (long long)line, col, ncols); break;
+    case BAD_LONG: set_error("ldw_tsv_read: %s: line %lld, column %u: the line is longer than %lld bytes", path, (long long)line, col, (long long)TSV_LINE_MAX); break;
+    default: set_error("ldw_tsv_read: %s: line %lld, column %u: not a number", path, (long long)line, col); break;
+    }
+    return LDW_ERR_ARG;
+}
+
+}  // namespace
+
+namespace ldw {
+void tsv_release(ldw_ctx *c) {
+    auto *t = static_cast<TsvState *>(c->tsv);
+    if (!t) return;
+    (void)hipStreamSynchronize(c->stream);
+    free_pins(t);
+    if (t->pin_res) (void)hipHostFree(t->pin_res);
+    for (DevBuf *b : {&t->img, &t->cnt, &t->off, &t->starts, &t->slow, &t->res, &t->patch, &t->scan_tmp, &t->cols, &t->keep, &t->koff, &t->idx1, &t->idx2, &t->bad, &t->srt, &t->order})
+        b->release();
+    for (auto &row : t->ev)
+        for (auto &e : row)
+            if (e) (void)hipEventDestroy(e);
+    delete t;
+    c->tsv = nullptr;
+}
+
+int64_t tsv_trim(ldw_ctx *c) {
+    auto *t = static_cast<TsvState *>(c->tsv);
+    if (!t) return 0;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    const int64_t n = free_pins(t) + (int64_t)t->img.cap;
+    t->img.release();
+    return n;
+}
+}  // namespace ldw
+
+extern "C" {
+
+int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t chunk_bytes, int64_t *rows_out, int64_t *slow_cells_out, uint32_t *int_cols_mask_out) {
+    if (rows_out) *rows_out = 0;
+    if (slow_cells_out) *slow_cells_out = 0;
+    if (int_cols_mask_out) *int_cols_mask_out = 0;
+    if (int rc = check_gpu(c)) return rc;
+    LDW_REQUIRE(path != nullptr, LDW_ERR_ARG, "ldw_tsv_read: null path");
+    LDW_REQUIRE(sep == '\t' || sep == ' ', LDW_ERR_ARG, "ldw_tsv_read: the separator must be a tab or a space (got %d)", sep);
+    LDW_REQUIRE(ncols >= 1 && ncols <= TSV_MAX_COLS, LDW_ERR_ARG, "ldw_tsv_read: ncols = %d outside 1..%d", (int)ncols, TSV_MAX_COLS);
+    LDW_REQUIRE(chunk_bytes >= 0 && chunk_bytes <= ((int64_t)1 << 30), LDW_ERR_ARG, "ldw_tsv_read: chunk_bytes = %lld outside 0..2^30 (0: 64 MiB)", (long long)chunk_bytes);
+    const int64_t chunk = chunk_bytes > 0 ? chunk_bytes : TSV_DEFAULT_CHUNK;
+    TsvFeeder feed;
+    if (int rc = feed.open(path)) return rc;
+    TsvState *t = tsv_state(c);
+    t->rows = 0;
+    t->path = path;
+    if (t->ncols != ncols) t->stride = 0;   // (the buffer is cut anew: grow_columns)
+    t->ncols = ncols;
+    memset(t->ms, 0, sizeof(t->ms));
+    const auto t_begin = std::chrono::steady_clock::now();
+    const int64_t cap = chunk + TSV_LINE_MAX + 64;   // data bytes of a pinned buffer: a carried line and a chunk
+    const size_t buf_bytes = (size_t)(TSV_FRONT + cap + TSV_TAIL);
+    if (int rc = ensure_pins(t, buf_bytes)) return rc;
+    if (int rc = t->img.reserve(buf_bytes)) return rc;
+    if (int rc = t->res.reserve(sizeof(TsvResult))) return rc;
+    const int64_t max_blocks = (cap + TSV_TILE - 1) / TSV_TILE + 1;
+    if (int rc = t->cnt.reserve((size_t)(max_blocks + 1) * 4)) return rc;
+    if (int rc = t->off.reserve((size_t)(max_blocks + 1) * 4)) return rc;
+    size_t scan_bytes = 0;
+    LDW_HIP(prim_exclusive_sum(nullptr, scan_bytes, t->cnt.as<uint32_t>(), t->off.as<uint32_t>(), (size_t)max_blocks + 1, c->stream));
+    if (int rc = t->scan_tmp.reserve(scan_bytes)) return rc;
+    for (auto &p : t->pin) memset(p, '\n', (size_t)TSV_FRONT);
+
+    int rc = LDW_OK;
+    int64_t slow_total = 0, consumed = 0, nchunks = 0, file_bytes = 0;
+    uint32_t bad_reason = 0, bad_col = 0;
+    int64_t bad_row = -1;
+    struct Chunk {
+        int64_t size = 0, row0 = 0, rows = 0;
+        bool queued = false;
+    } ch[2];
+    const uint8_t *d_buf = t->img.as<uint8_t>() + TSV_FRONT;
+    TsvResult *d_res = t->res.as<TsvResult>();
+
+    // waits for a chunk's kernels; converts and patches its slow cells from the pinned text; notes its first refused row
+    auto finish = [&](int b) -> int {
+        Chunk &k = ch[b];
+        if (!k.queued) return LDW_OK;
+        k.queued = false;
+        hipError_t e = hipEventSynchronize(t->ev[b][4]);
+        if (e != hipSuccess) return hip_fail(e, "ldw_tsv_read: chunk", __FILE__, __LINE__);
+        const TsvResult r = t->pin_res[b];
+        float f = 0;
+        if (hipEventElapsedTime(&f, t->ev[b][0], t->ev[b][1]) == hipSuccess) t->ms[2] += f;
+        if (hipEventElapsedTime(&f, t->ev[b][1], t->ev[b][2]) == hipSuccess) t->ms[3] += f;
+        if (hipEventElapsedTime(&f, t->ev[b][3], t->ev[b][4]) == hipSuccess) t->ms[4] += f;
+        if (r.bad != ~0ull) {
+            bad_row = k.row0 + (int64_t)(r.bad >> 16);
+            bad_col = (uint32_t)(r.bad >> 8) & 0xff;
+            bad_reason = (uint32_t)r.bad & 0xff;
+            return LDW_ERR_ARG;
+        }
+        if (r.slow > 0) {
+            const auto p0 = std::chrono::steady_clock::now();
+            std::vector<uint2> list(r.slow);
+            LDW_HIP(hipMemcpyAsync(list.data(), t->slow.p, (size_t)r.slow * 8, hipMemcpyDeviceToHost, c->stream));
+            LDW_HIP(hipStreamSynchronize(c->stream));
+            // [cells (uint32) | values (double)] in one buffer, one copy
+            const size_t voff = ((size_t)r.slow * 4 + 7) / 8 * 8;
+            std::vector<unsigned char> host(voff + (size_t)r.slow * 8);
+            uint32_t *cell = reinterpret_cast<uint32_t *>(host.data());
+            double *val = reinterpret_cast<double *>(host.data() + voff);
+            const char *text = static_cast<const char *>(t->pin[b]) + TSV_FRONT;
+            for (uint32_t i = 0; i < r.slow; ++i) {
+                cell[i] = list[i].x;
+                val[i] = tsv_strtod(text + list[i].y);
+            }
+            if (int rc2 = t->patch.reserve(host.size())) return rc2;
+            LDW_HIP(hipMemcpyAsync(t->patch.p, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_tsv_patch, dim3((r.slow + 255) / 256), dim3(256), 0, c->stream, t->patch.as<uint32_t>(),
+                               reinterpret_cast<const double *>(t->patch.as<unsigned char>() + voff), r.slow, t->ncols, t->cols.as<double>(), t->stride, k.row0);
+            LDW_HIP(hipGetLastError());
+            LDW_HIP(hipStreamSynchronize(c->stream));   // (`host` goes out of scope)
+            t->ms[5] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p0).count();
+            slow_total += r.slow;
+        }
+        return LDW_OK;
+    };
+
+    int64_t cut = 0, total = 0;
+    std::string fill_err;
+    int fill_rc = feed.fill(static_cast<char *>(t->pin[0]) + TSV_FRONT, 0, chunk, cap, &cut, &total);
+    if (fill_rc != LDW_OK) {
+        fill_err = ldw_last_error();
+        cut = 0;
+    } else if (!feed.gzip()) {
+        FileStamp st;
+        if (file_stamp(path, &st) == LDW_OK) file_bytes = st.size;
+    }
+    for (int64_t k = 0; rc == LDW_OK && cut > 0; ++k) {
+        const int b = (int)(k & 1);
+        char *data = static_cast<char *>(t->pin[b]) + TSV_FRONT;
+        const int64_t carry = total - cut;
+        // the chunk before this one: the other buffer still holds the text of its slow cells
+        if ((rc = finish(1 - b))) break;
+        // the other buffer takes the carried line now: this one's tail becomes '\n' padding
+        memcpy(static_cast<char *>(t->pin[1 - b]) + TSV_FRONT, data + cut, (size_t)carry);
+        memset(data + cut, '\n', (size_t)TSV_TAIL);
+        const int64_t padded = (cut + 15) / 16 * 16;
+        const uint32_t nblocks = (uint32_t)((cut + TSV_TILE - 1) / TSV_TILE);
+        hipError_t e = hipEventRecord(t->ev[b][0], c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(t->img.p, t->pin[b], (size_t)(TSV_FRONT + padded + TSV_TAIL - 16), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(t->ev[b][1], c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(t->cnt.as<uint32_t>() + nblocks, 0, 4, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_tsv_count, dim3(nblocks), dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->cnt.as<uint32_t>());
+            size_t sb = t->scan_tmp.cap;
+            e = prim_exclusive_sum(t->scan_tmp.p, sb, t->cnt.as<uint32_t>(), t->off.as<uint32_t>(), (size_t)nblocks + 1, c->stream);
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_tsv_init, dim3(1), dim3(256), 0, c->stream, d_res, (uint32_t)(k > 0), t->off.as<uint32_t>(), nblocks);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&t->pin_res[b], d_res, sizeof(TsvResult), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(t->ev[b][2], c->stream);
+        if (e != hipSuccess) {
+            rc = hip_fail(e, "ldw_tsv_read: line kernels", __FILE__, __LINE__);
+            break;
+        }
+        ch[b].size = cut;
+        consumed += cut;
+        ++nchunks;
+        // the next chunk is read while this one is copied and its lines are counted
+        int64_t ncut = 0, ntotal = 0;
+        fill_rc = feed.fill(static_cast<char *>(t->pin[1 - b]) + TSV_FRONT, carry, chunk, cap, &ncut, &ntotal);
+        if (fill_rc != LDW_OK) fill_err = ldw_last_error();
+        e = hipEventSynchronize(t->ev[b][2]);
+        if (e != hipSuccess) {
+            rc = hip_fail(e, "ldw_tsv_read: line kernels", __FILE__, __LINE__);
+            break;
+        }
+        const uint32_t nrows = t->pin_res[b].rows;
+        ch[b].row0 = t->rows;
+        ch[b].rows = nrows;
+        if (nrows > 0) {
+            int64_t want = t->rows + nrows;
+            if (k == 0 && file_bytes > cut) want = std::max<int64_t>(want, (int64_t)((double)nrows * ((double)file_bytes / (double)cut) * 1.02) + 1024);   // a plain file: sized once from its first chunk
+            if ((rc = grow_columns(c, t, want))) break;
+            if ((rc = t->starts.reserve((size_t)nrows * 4))) break;
+            if ((rc = t->slow.reserve((size_t)nrows * (size_t)ncols * 8))) break;
+            e = hipEventRecord(t->ev[b][3], c->stream);
+            hipLaunchKernelGGL(k_tsv_starts, dim3(nblocks), dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->off.as<uint32_t>(), t->starts.as<uint32_t>());
+            const dim3 grid((nrows + TSV_BLOCK - 1) / TSV_BLOCK);
+            if (t->variant == 1)
+                hipLaunchKernelGGL(k_tsv_parse<true>, grid, dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->starts.as<uint32_t>(), nrows, (int)ncols, (uint8_t)sep,
+                                   t->cols.as<double>(), t->stride, t->rows, d_res, t->slow.as<uint2>());
+            else
+                hipLaunchKernelGGL(k_tsv_parse<false>, grid, dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->starts.as<uint32_t>(), nrows, (int)ncols, (uint8_t)sep,
+                                   t->cols.as<double>(), t->stride, t->rows, d_res, t->slow.as<uint2>());
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(&t->pin_res[b], d_res, sizeof(TsvResult), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipEventRecord(t->ev[b][4], c->stream);
+            if (e != hipSuccess) {
+                rc = hip_fail(e, "ldw_tsv_read: parse kernel", __FILE__, __LINE__);
+                break;
+            }
+            ch[b].queued = true;
+            t->rows += nrows;
+        }
+        if (fill_rc != LDW_OK) break;
+        cut = ncut;
+        total = ntotal;
+    }
+    for (int b = 0; b < 2 && rc == LDW_OK; ++b) rc = finish(b);
+    (void)hipStreamSynchronize(c->stream);   // (on an error path too: no copy may still read a pinned buffer)
+    uint32_t not_int = 0;
+    if (rc == LDW_OK && fill_rc == LDW_OK && nchunks > 0) {
+        const hipError_t e = hipMemcpy(&not_int, &d_res->not_int, 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "ldw_tsv_read: result", __FILE__, __LINE__);
+    }
+    if (rc == LDW_OK && bad_row < 0 && fill_rc != LDW_OK) {   // the feeder's own refusal comes after every row before it
+        rc = fill_rc;
+        if (cut < 0 || fill_err.find("longer than") != std::string::npos) {
+            int64_t line = 0;
+            (void)tsv_line_of_offset(path, consumed, &line);
+            set_error("ldw_tsv_read: %s: line %lld, column 1: the line is longer than %lld bytes", path, (long long)line, (long long)TSV_LINE_MAX);
+        } else {
+            set_error("%s", fill_err.c_str());
+        }
+    }
+    if (bad_row >= 0) rc = refuse_row(path, bad_row, bad_col, bad_reason, ncols);
+    if (rc != LDW_OK) {
+        t->rows = 0;
+        return rc;
+    }
+    t->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    t->ms[1] = feed.read_ms;
+    t->ms[6] = (double)nchunks;
+    t->ms[7] = (double)consumed;
+    if (rows_out) *rows_out = t->rows;
+    if (slow_cells_out) *slow_cells_out = slow_total;
+    if (int_cols_mask_out) *int_cols_mask_out = t->rows > 0 ? ~not_int & ((1u << ncols) - 1) : 0;
+    return LDW_OK;
+}
+
+int ldw_tsv_columns(ldw_ctx *c, const double **device_ptr_out, int64_t *rows_out, int32_t *ncols_out, int64_t *stride_out) {
+    if (int rc = check_gpu(c)) return rc;
+    LDW_REQUIRE(device_ptr_out && rows_out && ncols_out && stride_out, LDW_ERR_ARG, "ldw_tsv_columns: null argument");
+    auto *t = static_cast<TsvState *>(c->tsv);
+    LDW_REQUIRE(t && t->ncols > 0, LDW_ERR_STATE, "ldw_tsv_columns: no table has been read (ldw_tsv_read)");
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    *device_ptr_out = t->rows > 0 ? t->cols.as<double>() : nullptr;
+    *rows_out = t->rows;
+    *ncols_out = t->ncols;
+    *stride_out = t->stride;
+    return LDW_OK;
+}
+
+int ldw_tsv_fetch(ldw_ctx *c, int32_t col, double *dst, int64_t capacity, int on_device) {
+    if (int rc = check_gpu(c)) return rc;
+    auto *t = static_cast<TsvState *>(c->tsv);
+    LDW_REQUIRE(t && t->ncols > 0, LDW_ERR_STATE, "ldw_tsv_fetch: no table has been read (ldw_tsv_read)");
+    LDW_REQUIRE(col >= 0 && col < t->ncols, LDW_ERR_ARG, "ldw_tsv_fetch: column %d outside 0..%d", (int)col, t->ncols - 1);
+    LDW_REQUIRE(capacity >= t->rows, LDW_ERR_SIZE, "ldw_tsv_fetch: capacity %lld < %lld rows", (long long)capacity, (long long)t->rows);
+    if (t->rows == 0) return LDW_OK;
+    LDW_REQUIRE(dst != nullptr, LDW_ERR_ARG, "ldw_tsv_fetch: null output");
+    LDW_HIP(hipMemcpyAsync(dst, t->cols.as<double>() + (int64_t)col * t->stride, (size_t)t->rows * 8, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    return LDW_OK;
+}
+
+int ldw_set_positions(ldw_ctx *c, const int32_t *POS, int64_t L, double g) {
+    if (int rc = check_gpu(c)) return rc;
+    if (int rc = join_prepare(c)) return rc;
+    if (int rc = ldw_tsv_join(c)) return rc;   // (a pending asynchronous table reads the positions this call replaces)
+    LDW_REQUIRE(POS != nullptr && L > 0 && L < ((int64_t)1 << 27), LDW_ERR_ARG, "ldw_set_positions: null positions or L = %lld outside 1..2^27", (long long)L);
+    LDW_REQUIRE(g >= 0 && !std::isnan(g), LDW_ERR_ARG, "ldw_set_positions: genome length g must be positive, or 0 when it is not known");
+    LDW_REQUIRE(c->blk_capacity == 0 && c->lr_stream == nullptr, LDW_ERR_STATE, "ldw_set_positions: a link pass or an lr_links stream is still open");
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    if (int rc = c->POS.reserve((size_t)L * 4)) return rc;
+    LDW_HIP(hipMemcpyAsync(c->POS.p, POS, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    // what an alignment would have brought is gone: states, weights, r, uqe and paint; the tables index the old SNPs
+    c->L = L;
+    c->N = c->Npad = c->KW = 0;
+    c->pos_only = true;
+    c->have_weights = false;
+    c->rows_ready = false;
+    c->h_r.clear();
+    c->h_paint.clear();
+    c->paint_min = c->paint_max = 0;
+    c->h_POS.assign(POS, POS + L);
+    c->pos_sorted = true;
+    for (int64_t i = 1; i < L && c->pos_sorted; ++i) c->pos_sorted = POS[i] >= POS[i - 1];
+    c->pos_strict = c->pos_sorted;
+    for (int64_t i = 1; i < L && c->pos_strict; ++i) c->pos_strict = POS[i] > POS[i - 1];
+    c->n_slots = 0;
+    c->g = g;
+    c->have_meta = true;
+    c->sr_total = c->sr_share_rows = -1;
+    c->sr_total_dist = -1;
+    c->n_sr = c->n_lr = 0;
+    c->n_red = c->n_pool = 0;
+    c->ar_valid = false;
+    c->stats.clear();
+    c->multi_owner.clear();
+    return LDW_OK;
+}
+
+int ldw_links_load(ldw_ctx *c, int which, int32_t pos1_col, int32_t pos2_col, int32_t mi_col, int32_t min_len_col, double min_len, int32_t flags, int64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (int rc = check_gpu(c)) return rc;
+    if (int rc = join_prepare(c)) return rc;
+    LDW_REQUIRE(which == 0 || which == 1, LDW_ERR_ARG, "ldw_links_load: which must be 0 (sr) or 1 (lr)");
+    LDW_REQUIRE(flags == 0, LDW_ERR_ARG, "ldw_links_load: flags must be 0");
+    auto *t = static_cast<TsvState *>(c->tsv);
+    LDW_REQUIRE(t && t->ncols > 0, LDW_ERR_STATE, "ldw_links_load: no table has been read (ldw_tsv_read)");
+    const int nc = t->ncols;
+    LDW_REQUIRE(pos1_col >= 0 && pos1_col < nc && pos2_col >= 0 && pos2_col < nc && mi_col >= 0 && mi_col < nc && min_len_col >= -1 && min_len_col < nc, LDW_ERR_ARG,
+                "ldw_links_load: a column index lies outside the %d columns read (min_len_col: -1 for none)", nc);
+    LDW_REQUIRE(c->have_meta && c->POS.p && (int64_t)c->h_POS.size() == c->L, LDW_ERR_STATE, "ldw_links_load: no positions (ldw_set_snp_meta or ldw_set_positions)");
+    LDW_REQUIRE(c->blk_capacity == 0, LDW_ERR_STATE, "ldw_links_load: a link pass is still open (ldw_links_end)");
+    const int64_t n = t->rows, L = c->L;
+    LDW_REQUIRE(n < 2147483647LL, LDW_ERR_SIZE, "ldw_links_load: too many rows");
+    if (c->gemm_stream) LDW_HIP(hipStreamSynchronize(c->gemm_stream));
+    DevBuf &A = which == 0 ? c->sr_a : c->lr_a, &B = which == 0 ? c->sr_b : c->lr_b, &M = which == 0 ? c->sr_mi : c->lr_mi;
+    int64_t kept = 0;
+    if (n > 0) {
+        // the positions in ascending order: POS itself, or a sorted copy with the SNP of every entry (the first SNP of a position first: a stable sort)
+        const int32_t *d_srt = c->POS.as<int32_t>(), *d_order = nullptr;
+        if (!c->pos_sorted) {
+            std::vector<int32_t> ord((size_t)L), srt((size_t)L);
+            for (int64_t i = 0; i < L; ++i) ord[(size_t)i] = (int32_t)i;
+            std::stable_sort(ord.begin(), ord.end(), [&](int32_t u, int32_t v) { return c->h_POS[(size_t)u] < c->h_POS[(size_t)v]; });
+            for (int64_t i = 0; i < L; ++i) srt[(size_t)i] = c->h_POS[(size_t)ord[(size_t)i]];
+            if (int rc = t->srt.reserve((size_t)L * 4)) return rc;
+            if (int rc = t->order.reserve((size_t)L * 4)) return rc;
+            LDW_HIP(hipMemcpyAsync(t->srt.p, srt.data(), (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
+            LDW_HIP(hipMemcpyAsync(t->order.p, ord.data(), (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
+            LDW_HIP(hipStreamSynchronize(c->stream));   // (the vectors go out of scope)
+            d_srt = t->srt.as<int32_t>();
+            d_order = t->order.as<int32_t>();
+        }
+        if (int rc = t->keep.reserve((size_t)(n + 1) * 4)) return rc;
+        if (int rc = t->koff.reserve((size_t)(n + 1) * 4)) return rc;
+        if (int rc = t->idx1.reserve((size_t)n * 4)) return rc;
+        if (int rc = t->idx2.reserve((size_t)n * 4)) return rc;
+        if (int rc = t->bad.reserve(8)) return rc;
+        size_t sb = 0;
+        LDW_HIP(prim_exclusive_sum(nullptr, sb, t->keep.as<uint32_t>(), t->koff.as<uint32_t>(), (size_t)n + 1, c->stream));
+        if (int rc = t->scan_tmp.reserve(sb)) return rc;
+        sb = t->scan_tmp.cap;
+        const double *cols = t->cols.as<double>();
+        const int grid = (int)std::min<int64_t>((n + 255) / 256, 16384);
+        LDW_HIP(hipMemsetAsync(t->bad.p, 0xff, 8, c->stream));
+        LDW_HIP(hipMemsetAsync(t->keep.as<uint32_t>() + n, 0, 4, c->stream));
+        hipLaunchKernelGGL(k_links_map, dim3(grid), dim3(256), 0, c->stream, cols + (int64_t)pos1_col * t->stride, cols + (int64_t)pos2_col * t->stride,
+                           min_len_col >= 0 ? cols + (int64_t)min_len_col * t->stride : nullptr, min_len, n, d_srt, d_order, (int32_t)L, (uint32_t)pos1_col, (uint32_t)pos2_col, t->keep.as<uint32_t>(),
+                           t->idx1.as<int32_t>(), t->idx2.as<int32_t>(), t->bad.as<unsigned long long>());
+        LDW_HIP(hipGetLastError());
+        LDW_HIP(prim_exclusive_sum(t->scan_tmp.p, sb, t->keep.as<uint32_t>(), t->koff.as<uint32_t>(), (size_t)n + 1, c->stream));
+        unsigned long long bad = 0;
+        uint32_t total = 0;
+        LDW_HIP(hipMemcpyAsync(&bad, t->bad.p, 8, hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipMemcpyAsync(&total, t->koff.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipStreamSynchronize(c->stream));
+        if (bad != ~0ull) {
+            const int64_t row = (int64_t)(bad >> 8);
+            const int bad_col = (int)(bad >> 4) & 15, why = (int)bad & 15;
+            double v = 0;
+            LDW_HIP(hipMemcpy(&v, cols + (int64_t)bad_col * t->stride + row, 8, hipMemcpyDeviceToHost));
+            int64_t line = 0;
+            (void)tsv_line_of_row(t->path.c_str(), row, &line);
+            const int col = bad_col + 1;
+            if (why == POS_FRACTION) set_error("ldw_links_load: %s: line %lld, column %d: the position %.17g is not an integer", t->path.c_str(), (long long)line, col, v);
+            else if (why == POS_RANGE) set_error("ldw_links_load: %s: line %lld, column %d: the position %.17g does not fit in 32 bits", t->path.c_str(), (long long)line, col, v);
+            else set_error("ldw_links_load: %s: line %lld, column %d: the position %.17g is no SNP's", t->path.c_str(), (long long)line, col, v);
+            return LDW_ERR_ARG;
+        }
+        kept = total;
+        if (int rc = A.reserve((size_t)std::max<int64_t>(kept, 1) * 4)) return rc;
+        if (int rc = B.reserve((size_t)std::max<int64_t>(kept, 1) * 4)) return rc;
+        if (int rc = M.reserve((size_t)std::max<int64_t>(kept, 1) * 8)) return rc;
+        hipLaunchKernelGGL(k_links_compact, dim3(grid), dim3(256), 0, c->stream, t->keep.as<uint32_t>(), t->koff.as<uint32_t>(), t->idx1.as<int32_t>(), t->idx2.as<int32_t>(),
+                           cols + (int64_t)mi_col * t->stride, n, A.as<int32_t>(), B.as<int32_t>(), M.as<double>());
+        LDW_HIP(hipGetLastError());
+        LDW_HIP(hipStreamSynchronize(c->stream));
+    }
+    (which == 0 ? c->n_sr : c->n_lr) = kept;
+    c->n_red = c->n_pool = 0;   // as ldw_links_import leaves the context: whatever was derived from the old table is stale
+    c->ar_valid = false;
+    c->stats.clear();
+    c->multi_owner.clear();
+    if (n_out) *n_out = kept;
+    return LDW_OK;
+}
+
+// ---- include/ldweaver_amd_debug.h ---------------------------------------------------------------------------------------------------------------
+
+int ldw_tsv_stats(ldw_ctx *c, double *out10) {
+    LDW_REQUIRE(c && out10, LDW_ERR_ARG, "ldw_tsv_stats: null argument");
+    auto *t = static_cast<TsvState *>(c->tsv);
+    for (int k = 0; k < 10; ++k) out10[k] = 0;
+    if (!t) return LDW_OK;
+    for (int k = 0; k < 8; ++k) out10[k] = t->ms[k];
+    out10[8] = (double)t->grows;
+    out10[9] = (double)(t->pin_cap * 2);
+    return LDW_OK;
+}
+
+int ldw_tsv_set_variant(ldw_ctx *c, int variant) {
+    LDW_REQUIRE(c != nullptr, LDW_ERR_ARG, "null context");
+    LDW_REQUIRE(variant == 0 || variant == 1, LDW_ERR_ARG, "ldw_tsv_set_variant: 0 (rows from cached global loads) or 1 (from an LDS-staged tile)");
+    tsv_state(c)->variant = variant;
+    return LDW_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,190 @@
+// Host side of the native reader of numeric link tables (include/ldweaver_amd.h 13): ldw_tsv_probe, the chunk feeder, the physical
+// line of a row (error paths) and the conversion of the cells the device leaves to the host.
+#include <errno.h>
+#include <locale.h>
+#include <string.h>
+#include <zlib.h>
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#include "ldw_internal.h"
+#include "ldw_links_read.h"
+
+namespace ldw {
+
+int TsvFeeder::open(const char *path) {
+    close();
+    errno = 0;
+    gzFile f = gzopen(path, "rb");
+    LDW_REQUIRE(f != nullptr, LDW_ERR_ARG, "ldw_tsv: cannot open %s: %s", path, errno ? strerror(errno) : "out of memory");
+    gzbuffer(f, 1u << 20);
+    gz_ = f;
+    gzip_ = gzdirect(f) == 0;
+    eof_ = false;
+    path_ = path;
+    read_ms = 0;
+    return LDW_OK;
+}
+
+void TsvFeeder::close() {
+    if (gz_) gzclose(static_cast<gzFile>(gz_));
+    gz_ = nullptr;
+}
+
+int TsvFeeder::fill(char *data, int64_t carry, int64_t chunk_bytes, int64_t cap, int64_t *cut, int64_t *total) {
+    int64_t size = carry;
+    *cut = 0;
+    *total = size;
+    for (;;) {
+        if (eof_) {   // what is left is the last line, without its newline
+            if (size > 0) {
+                if (size > TSV_LINE_MAX) {
+                    *cut = -1;
+                    set_error("ldw_tsv_read: %s: a line is longer than %lld bytes", path_.c_str(), (long long)TSV_LINE_MAX);
+                    return LDW_ERR_ARG;
+                }
+                data[size++] = '\n';
+            }
+            *cut = *total = size;
+            return LDW_OK;
+        }
+        const int64_t want = std::min<int64_t>(std::min<int64_t>(chunk_bytes, cap - 1 - size), 1 << 30);
+        const auto t0 = std::chrono::steady_clock::now();
+        const int got = gzread(static_cast<gzFile>(gz_), data + size, (unsigned)want);
+        read_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (got < 0) {
+            int errnum = 0;
+            const char *msg = gzerror(static_cast<gzFile>(gz_), &errnum);
+            set_error("ldw_tsv_read: reading %s: %s", path_.c_str(), errnum == Z_ERRNO ? strerror(errno) : msg);
+            return LDW_ERR_ARG;
+        }
+        if (got < want) eof_ = true;
+        // the carry holds no newline, so the last newline of the buffer, if any, is among the new bytes
+        const void *nl = got > 0 ? memrchr(data + size, '\n', (size_t)got) : nullptr;
+        size += got;
+        *total = size;
+        if (nl) {
+            *cut = (int64_t)(static_cast<const char *>(nl) - data) + 1;
+            return LDW_OK;
+        }
+        if (size > TSV_LINE_MAX) {
+            *cut = -1;
+            set_error("ldw_tsv_read: %s: a line is longer than %lld bytes", path_.c_str(), (long long)TSV_LINE_MAX);
+            return LDW_ERR_ARG;
+        }
+    }
+}
+
+namespace {
+// walks the file line by line: fn(line number (1-based), first byte offset, empty) until it returns true
+template <class F>
+int walk_lines(const char *path, F fn) {
+    errno = 0;
+    gzFile f = gzopen(path, "rb");
+    LDW_REQUIRE(f != nullptr, LDW_ERR_ARG, "ldw_tsv: cannot open %s: %s", path, errno ? strerror(errno) : "out of memory");
+    gzbuffer(f, 1u << 20);
+    std::vector<char> buf(1 << 20);
+    int64_t line = 1, off = 0, line_off = 0, len = 0;
+    char last = 0;
+    bool done = false;
+    for (int n; !done && (n = gzread(f, buf.data(), (unsigned)buf.size())) > 0;) {
+        for (int i = 0; i < n && !done; ++i, ++off) {
+            const char ch = buf[(size_t)i];
+            if (ch == '\n') {
+                const bool empty = len == 0 || (len == 1 && last == '\r');
+                done = fn(line, line_off, off, empty);
+                ++line;
+                line_off = off + 1;
+                len = 0;
+            } else {
+                ++len;
+                last = ch;
+            }
+        }
+    }
+    if (!done && len > 0) fn(line, line_off, off, len == 1 && last == '\r');
+    gzclose(f);
+    return LDW_OK;
+}
+}  // namespace
+
+int tsv_line_of_row(const char *path, int64_t row, int64_t *line_out) {
+    int64_t seen = 0;
+    *line_out = 0;
+    return walk_lines(path, [&](int64_t line, int64_t, int64_t, bool empty) {
+        if (empty) return false;
+        if (seen++ == row) {
+            *line_out = line;
+            return true;
+        }
+        return false;
+    });
+}
+
+int tsv_line_of_offset(const char *path, int64_t off, int64_t *line_out) {
+    *line_out = 0;
+    return walk_lines(path, [&](int64_t line, int64_t first, int64_t nl, bool) {
+        *line_out = line;
+        return off >= first && off <= nl;
+    });
+}
+
+double tsv_strtod(const char *p) {
+    static locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+    return strtod_l(p, nullptr, c_locale);
+}
+
+}  // namespace ldw
+
+extern "C" {
+
+int ldw_tsv_probe(const char *path, int sep, int32_t *ncols_out, int32_t *gz_out) {
+    LDW_REQUIRE(path && ncols_out, LDW_ERR_ARG, "ldw_tsv_probe: null argument");
+    LDW_REQUIRE(sep == '\t' || sep == ' ', LDW_ERR_ARG, "ldw_tsv_probe: the separator must be a tab or a space (got %d)", sep);
+    errno = 0;
+    gzFile f = gzopen(path, "rb");
+    LDW_REQUIRE(f != nullptr, LDW_ERR_ARG, "ldw_tsv: cannot open %s: %s", path, errno ? strerror(errno) : "out of memory");
+    if (gz_out) *gz_out = gzdirect(f) == 0;
+    // the fields of the first non-empty line
+    char buf[65536];
+    int32_t fields = 0;
+    int64_t len = 0;
+    char last = 0;
+    bool done = false, failed = false;
+    for (int n; !done && (n = gzread(f, buf, sizeof(buf))) != 0;) {
+        if (n < 0) {
+            failed = true;
+            break;
+        }
+        for (int i = 0; i < n && !done; ++i) {
+            const char ch = buf[i];
+            if (ch == '\n') {
+                if (len == 0 || (len == 1 && last == '\r')) {
+                    len = 0;
+                    fields = 0;
+                    continue;
+                }
+                done = true;
+            } else {
+                if (len == 0) fields = 1;
+                if (ch == (char)sep) ++fields;
+                ++len;
+                last = ch;
+                if (len > ldw::TSV_LINE_MAX) {
+                    gzclose(f);
+                    ldw::set_error("ldw_tsv_probe: %s: a line is longer than %lld bytes", path, (long long)ldw::TSV_LINE_MAX);
+                    return LDW_ERR_ARG;
+                }
+            }
+        }
+    }
+    gzclose(f);
+    LDW_REQUIRE(!failed, LDW_ERR_ARG, "ldw_tsv_probe: reading %s failed", path);
+    if (!done && (len == 0 || (len == 1 && last == '\r'))) fields = 0;   // (a last line without a newline counts; a lone '\r' is empty)
+    *ncols_out = fields;
+    return LDW_OK;
+}
+
+}  // extern "C"

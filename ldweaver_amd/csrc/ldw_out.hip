@@ -184,7 +184,7 @@ int ldw_write_alignment(ldw_ctx *c, const char *path, int append, int format, co
                         int64_t names_bytes, int64_t chunk_bytes, int64_t *bytes_out) {
     if (bytes_out) *bytes_out = 0;
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->L > 0 && c->states.p, LDW_ERR_STATE, "ldw_write_alignment: no alignment resident");
+    LDW_REQUIRE(ldw::have_alignment(c) && c->states.p, LDW_ERR_STATE, "ldw_write_alignment: no alignment resident");
     LDW_REQUIRE(path != nullptr, LDW_ERR_ARG, "ldw_write_alignment: null path");
     LDW_REQUIRE(format == 0 || format == 1, LDW_ERR_ARG, "ldw_write_alignment: format %d (0 FASTA, 1 tsv body)", format);
     LDW_REQUIRE(k >= 1 && snp_idx != nullptr, LDW_ERR_ARG, "ldw_write_alignment: k = %lld SNPs (at least 1)", (long long)k);

@@ -604,6 +604,7 @@ int ldw_plot_links(ldw_ctx *c, int which, int use_aracne, const ldw_plot_opts *o
     LDW_REQUIRE(png_path || rgb_out, LDW_ERR_ARG, "ldw_plot_links: neither a path nor a canvas to write to");
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(c->POS.p != nullptr, LDW_ERR_STATE, "ldw_plot_links: no SNP meta data (ldw_set_snp_meta)");
+    LDW_REQUIRE(c->g > 0, LDW_ERR_STATE, "ldw_plot_links: the genome length is not known (ldw_set_positions with g = 0): len cannot be taken from the positions");
     LDW_REQUIRE((which == 1) == c->red_from_lr, LDW_ERR_STATE, "ldw_plot_links: the kept links are those of the %s table", c->red_from_lr ? "long-range" : "short-range");
     const int64_t n = c->n_red;
     LDW_REQUIRE(!use_aracne || n == 0 || (c->ar_valid && c->ar_flags.cap >= (size_t)n), LDW_ERR_STATE,

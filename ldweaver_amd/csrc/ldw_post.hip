@@ -74,10 +74,44 @@ __global__ __launch_bounds__(256) void k_mark_used(const int32_t *__restrict__ a
     }
 }
 
+// A cell's sum must not depend on the order its links arrive in: two contexts holding the same tables give the same map, bit for bit.  fp64 atomic
+// adds do not do that, integer ones do: a value goes into a 128-bit fixed-point accumulator in units of 2^-90 (two 64-bit atomic adds, the carry of
+// the low word added to the high one: every carry is counted once whatever the order).  A double below 64 in magnitude — an MI is below 2 — is
+// placed to within 2^-91, far below the 1e-5 the map adds before its logarithm, and the accumulator's 37 integer bits hold the sum of 2^31 of them.
+// Everything else (a larger value, an infinity, a NaN) takes the fp64 atomic add of `odd`, as every value did before.
+constexpr int LDMAP_FRAC = 90;
+__device__ __forceinline__ void ldmap_acc(double v, unsigned long long *__restrict__ lo, unsigned long long *__restrict__ hi, double *__restrict__ odd) {
+    if (!(fabs(v) < 64.0)) {   // (false for NaN too)
+        atomicAdd(odd, v);
+        return;
+    }
+    int e;
+    const double f = frexp(fabs(v), &e);                              // |v| = f 2^e, f in [0.5, 1)
+    const unsigned long long m = (unsigned long long)ldexp(f, 53);    // |v| = m 2^(e - 53), exact
+    const int sh = e - 53 + LDMAP_FRAC;
+    unsigned __int128 q = 0;
+    if (sh >= 0) q = (unsigned __int128)m << sh;                      // (sh <= 43: |v| < 2^6)
+    else if (sh > -55) q = (unsigned __int128)((m + (1ull << (-sh - 1))) >> -sh);
+    if (q == 0) return;
+    if (v < 0) q = (unsigned __int128)0 - q;
+    const unsigned long long ql = (unsigned long long)q, qh = (unsigned long long)(q >> 64);
+    const unsigned long long old = atomicAdd(lo, ql);
+    const unsigned long long carry = old + ql < old ? 1ull : 0ull;
+    if (qh + carry != 0) atomicAdd(hi, qh + carry);
+}
+// The accumulated sum as a double (two's complement over both words), plus what went past the accumulator.  The read-out rounds: (double)lo keeps 53 of
+// the low word's 64 bits and the two halves are added in fp64, so the result is the exact sum to within about one ulp of itself (and 2^-79 absolute) —
+// the same for the same accumulator, which is all the map needs.
+__device__ __forceinline__ double ldmap_sum(unsigned long long lo, unsigned long long hi, double odd) {
+    const double s = ldexp((double)(long long)hi, 64 - LDMAP_FRAC) + ldexp((double)lo, -LDMAP_FRAC);
+    return odd == 0.0 ? s : s + odd;
+}
+
 __global__ __launch_bounds__(256) void k_ldmap_add(const int32_t *__restrict__ a, const int32_t *__restrict__ b, const double *__restrict__ mi,
                                                    int64_t n, const int32_t *__restrict__ POS, int from, int to, int windowed,
                                                    const int32_t *__restrict__ used, const int32_t *__restrict__ rank, int r, int B,
-                                                   double *__restrict__ red, const int32_t *__restrict__ slot) {
+                                                   double *__restrict__ red, unsigned long long *__restrict__ acc_lo, unsigned long long *__restrict__ acc_hi,
+                                                   const int32_t *__restrict__ slot) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int32_t x = a[i], y = b[i];
         if (windowed && !(POS[x] >= from && POS[x] <= to && POS[y] >= from && POS[y] <= to)) continue;   // :66-67
@@ -89,18 +123,21 @@ __global__ __launch_bounds__(256) void k_ldmap_add(const int32_t *__restrict__ a
         // mirror cell gets the same value afterwards), so the map is exactly symmetric whatever order the atomics land in.
         const double v = mi[i];
         const int lo = bi < bj ? bi : bj, hi = bi < bj ? bj : bi;
-        atomicAdd(&red[(int64_t)lo * B + hi], lo == hi ? v + v : v);
+        const int64_t cell = (int64_t)lo * B + hi;
+        ldmap_acc(lo == hi ? v + v : v, acc_lo + cell, acc_hi + cell, red + cell);
     }
 }
 
-__global__ __launch_bounds__(256) void k_ldmap_log(const double *__restrict__ red, int B, double inv_r2, double *__restrict__ out,
+__global__ __launch_bounds__(256) void k_ldmap_log(const double *__restrict__ red, const unsigned long long *__restrict__ acc_lo,
+                                                   const unsigned long long *__restrict__ acc_hi, int B, double inv_r2, double *__restrict__ out,
                                                    double *__restrict__ mm) {
     __shared__ double smin[256], smax[256];
     double lo = 1e300, hi = -1e300;
     const int64_t n = (int64_t)B * B;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / B, col = i - row * B;
-        const double s = red[row <= col ? row * B + col : col * B + row];
+        const int64_t cell = row <= col ? row * B + col : col * B + row;
+        const double s = ldmap_sum(acc_lo[cell], acc_hi[cell], red[cell]);
         const double v = log10(s * inv_r2 + 1e-5);
         out[i] = v;
         lo = v < lo ? v : lo;
@@ -355,12 +392,14 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
     LDW_REQUIRE(capacity < 0 || capacity >= (int64_t)B * B, LDW_ERR_SIZE, "ldw_ldmap: capacity %lld < %lld", (long long)capacity, (long long)B * B);
     const int64_t nb = (int64_t)B * B;
     const int rgrid = (int)std::min<int64_t>((nb + 255) / 256, 1024);
-    if (int rc = c->srm_q.reserve((size_t)nb * 16 + (size_t)rgrid * 16)) return rc;
-    double *red = c->srm_q.as<double>(), *htm = red + nb, *mm = htm + nb;
-    LDW_HIP(hipMemsetAsync(red, 0, (size_t)nb * 8, c->stream));
-    if (nl > 0) hipLaunchKernelGGL(k_ldmap_add, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>(), nl, POS, from, to, windowed, used, rank, r, B, red, d_slot);
-    if (ns > 0) hipLaunchKernelGGL(k_ldmap_add, grid_of(ns), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), ns, POS, from, to, windowed, used, rank, r, B, red, d_slot);
-    hipLaunchKernelGGL(k_ldmap_log, dim3(rgrid), dim3(256), 0, c->stream, red, (int)B, 1.0 / ((double)r * (double)r), htm, mm);
+    if (int rc = c->srm_q.reserve((size_t)nb * 32 + (size_t)rgrid * 16)) return rc;
+    // red: what went past the fixed-point accumulators (k_ldmap_add); acc_lo / acc_hi: their two words
+    double *red = c->srm_q.as<double>(), *htm = red + 3 * nb, *mm = htm + nb;
+    unsigned long long *acc_lo = reinterpret_cast<unsigned long long *>(red + nb), *acc_hi = acc_lo + nb;
+    LDW_HIP(hipMemsetAsync(red, 0, (size_t)nb * 24, c->stream));
+    if (nl > 0) hipLaunchKernelGGL(k_ldmap_add, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>(), nl, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
+    if (ns > 0) hipLaunchKernelGGL(k_ldmap_add, grid_of(ns), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), ns, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
+    hipLaunchKernelGGL(k_ldmap_log, dim3(rgrid), dim3(256), 0, c->stream, red, acc_lo, acc_hi, (int)B, 1.0 / ((double)r * (double)r), htm, mm);
     LDW_HIP(hipGetLastError());
     std::vector<double> hmm((size_t)rgrid * 2);
     LDW_HIP(hipMemcpyAsync(hmm.data(), mm, hmm.size() * 8, hipMemcpyDeviceToHost, c->stream));

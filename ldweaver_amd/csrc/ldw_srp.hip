@@ -930,6 +930,7 @@ static int quant_two_sorts(ldw_ctx *c, int64_t n, int32_t S, int nclust, double 
 static int sr_ready(ldw_ctx *c, const char *who) {
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(c->have_meta, LDW_ERR_STATE, "%s: ldw_set_snp_meta has not been called", who);
+    LDW_REQUIRE(!c->pos_only, LDW_ERR_STATE, "%s: the context holds positions only (ldw_set_positions): the short-range model needs the paint of ldw_set_snp_meta", who);
     return LDW_OK;
 }
 

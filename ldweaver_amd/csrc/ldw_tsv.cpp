@@ -27,6 +27,7 @@
 
 #include "ldw_internal.h"
 #include "ldw_fasta.h"
+#include "ldw_links_read.h"
 
 namespace {
 
@@ -794,6 +795,7 @@ int ldw_host_trim(ldw_ctx *c, int64_t *bytes_out) {
         if (int rc = tsv_async_join(c, nullptr, nullptr)) return rc;
         n += ldw::fasta_trim(c);   // the FASTA feeder's pinned chunk buffers
         n += ldw::out_trim(c);     // the alignment writer's pinned chunk buffers (ldw_out.hip)
+        n += ldw::tsv_trim(c);     // the link-table reader's pinned chunk buffers (ldw_links_read.hip)
         if (c->lr_stream == nullptr && c->pin_fetch) {
             (void)hipSetDevice(c->device);
             (void)hipHostFree(c->pin_fetch);

@@ -307,6 +307,7 @@ class Engine:
             Ls, Ns = st.shape
             L.check(L.lib().ldw_set_alignment(self._ctx, L.ptr(st), Ls, Ns, 0))
         self.L, self.N = int(Ls), int(Ns)
+        self._positions = None
         if not getattr(self, "_reserved", False):
             self._reserved = True
             self.reserve(self.L, self.N, max_blk_sz)   # (a side thread: the pinned staging buffers, while the caller goes on to the Hamming weights)
@@ -483,6 +484,7 @@ class Engine:
         pt = None if paint is None else L.as_c(paint, np.int32)
         assert r_.shape == (self.L,) and uq.shape == (self.L, 5) and ps.shape == (self.L,)
         L.check(L.lib().ldw_set_snp_meta(self._ctx, L.ptr(r_), L.ptr(uq), L.ptr(ps), L.ptr(pt), float(g)))
+        self._positions = ps
 
     def mi_block(self, from_idx, to_idx, quirk=L.QUIRK_REFERENCE, out=None) -> np.ndarray:
         """MI of one block as the reference's nf x nt matrix (Fortran order)."""
@@ -613,6 +615,56 @@ class Engine:
             a, b, mi = np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(b, dtype=np.int32), np.ascontiguousarray(mi, dtype=np.float64)
             on_dev = 0
         L.check(L.lib().ldw_links_import(self._ctx, int(which), L.ptr(a), L.ptr(b), L.ptr(mi), len(mi), on_dev))
+
+    # -- link tables from files (include/ldweaver_amd.h 13) ------------------------
+    def tsv_read(self, path, sep: str, ncols: int, chunk_bytes: int = 0):
+        """Parse a numeric table (plain or gzip, no header, one separator byte) into the context's device columns (ldw_tsv_read).
+        Returns (rows, slow cells, tuple of per-column "every cell was a plain integer literal")."""
+        rows, slow, mask = C.c_int64(0), C.c_int64(0), C.c_uint32(0)
+        fasta_check(L.lib().ldw_tsv_read(self._ctx, os.fsencode(path), ord(sep), int(ncols), int(chunk_bytes), C.byref(rows), C.byref(slow), C.byref(mask)), path)
+        return rows.value, slow.value, tuple(bool(mask.value >> k & 1) for k in range(int(ncols)))
+
+    def tsv_columns(self):
+        """The columns of the last tsv_read as float64 torch tensors that ALIAS the context's buffer (no copy): valid until the next tsv_read or
+        close(); read-only.  The stream order of ``links_view`` applies."""
+        import torch
+        p, rows, ncols, stride = C.c_void_p(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        L.check(L.lib().ldw_tsv_columns(self._ctx, C.byref(p), C.byref(rows), C.byref(ncols), C.byref(stride)))
+        dev = torch.device("cuda", self.device)
+        if rows.value == 0:
+            return [torch.empty(0, dtype=torch.float64, device=dev) for _ in range(ncols.value)]
+
+        class _View:
+            def __init__(self, ptr, n):
+                self.__cuda_array_interface__ = dict(shape=(n,), typestr="<f8", data=(ptr, False), version=2)
+
+        return [torch.as_tensor(_View(p.value + 8 * stride.value * k, rows.value), device=dev) for k in range(ncols.value)]
+
+    def tsv_fetch(self, col: int, rows: int) -> np.ndarray:
+        out = np.empty(int(rows), dtype=np.float64)
+        L.check(L.lib().ldw_tsv_fetch(self._ctx, int(col), L.ptr(out), len(out), 0))
+        return out
+
+    def tsv_stats(self) -> dict:
+        v = np.zeros(10)
+        L.check(L.lib().ldw_tsv_stats(self._ctx, L.ptr(v)))
+        return dict(total_ms=v[0], read_ms=v[1], copy_ms=v[2], line_ms=v[3], parse_ms=v[4], patch_ms=v[5], chunks=int(v[6]), bytes=int(v[7]), grows=int(v[8]),
+                    pinned_bytes=int(v[9]))
+
+    def set_positions(self, POS, g: float = 0.0):
+        """Positions for an engine WITHOUT an alignment (ldw_set_positions): enough for links_load / links_import, ldmap, lr_tukey, lr_reduced,
+        aracne_device and the long-range figure; g = 0: genome length not known."""
+        ps = L.as_c(POS, np.int32)
+        assert ps.ndim == 1
+        L.check(L.lib().ldw_set_positions(self._ctx, L.ptr(ps), len(ps), float(g)))
+        self.L, self.N = len(ps), 0
+        self._positions = ps
+
+    def links_load(self, which: int, pos1_col: int, pos2_col: int, mi_col: int, min_len_col: int = -1, min_len: float = 0.0) -> int:
+        """The columns of the last tsv_read become the sr (0) / lr (1) table, on the device (ldw_links_load).  Returns the rows installed."""
+        n = C.c_int64(0)
+        L.check(L.lib().ldw_links_load(self._ctx, int(which), int(pos1_col), int(pos2_col), int(mi_col), int(min_len_col), float(min_len), 0, C.byref(n)))
+        return n.value
 
     def block_stats(self):
         nb = self._nblocks

@@ -150,15 +150,22 @@ def render_heatmap(eng, htm, path, title=None):
 
 # ---- the readers of R/io_functions.R:32-66 ---------------------------------------------------------------------------------------------------
 
-def read_ShortRangeLinks(sr_links_path):
-    """sr_links.tsv as a frame with the reference's column names."""
+def read_ShortRangeLinks(sr_links_path, reader: str = "pandas"):
+    """sr_links.tsv as a frame with the reference's column names.  ``reader="native"``: parsed on the device (links_io.read_links_native), every value
+    the correctly rounded double of its text — pandas' default parser, which ``"pandas"`` keeps, can be one ulp off."""
+    from .links_io import check_reader, read_links_native
+    if check_reader(reader):
+        return read_links_native(sr_links_path, "sr")
     import pandas as pd
     return pd.read_csv(sr_links_path, sep="\t", header=None, names=SR_COLS, quoting=3, comment=None)
 
 
-def read_LongRangeLinks(lr_links_path, links_from_spydrpick: bool = False, sr_dist=20000):
+def read_LongRangeLinks(lr_links_path, links_from_spydrpick: bool = False, sr_dist=20000, reader: str = "pandas"):
     """lr_links.tsv (tab separated, six columns) or a SpydrPick file (space separated: pos1 pos2 len [ARACNE] MI); links with
-    len < sr_dist are dropped."""
+    len < sr_dist are dropped.  ``reader``: as in ``read_ShortRangeLinks``."""
+    from .links_io import check_reader, read_links_native
+    if check_reader(reader):
+        return read_links_native(lr_links_path, "spydrpick" if links_from_spydrpick else "lr", sr_dist=sr_dist)
     import pandas as pd
     if not links_from_spydrpick:
         df = pd.read_csv(lr_links_path, sep="\t", header=None, names=LR_COLS, quoting=3, comment=None)
@@ -197,20 +204,48 @@ def sr_facets(clust_c):
     return panel.astype(np.uint8), labels.astype(np.int32)
 
 
+def _is_path(links):
+    return isinstance(links, (str, bytes)) or hasattr(links, "__fspath__")
+
+
+def _device_columns(eng, links, kind: str, ncol: int, err: str):
+    """The columns of a link file on the engine's GPU (reader="native"): the checks of ``_frame``, no frame."""
+    from .links_io import read_links_native, tsv_probe
+    if not os.path.exists(links) or tsv_probe(links, "\t")[0] not in (0, ncol):
+        raise ValueError(err)
+    return read_links_native(links, kind, engine=eng, to="device")
+
+
+def sr_facets_device(clust_c):
+    """``sr_facets`` for a device column: (panel uint8 tensor, labels int32 array)."""
+    import torch
+    labels, panel = torch.unique(clust_c, sorted=True, return_inverse=True)
+    if len(labels) > L.PLOT_MAX_PANELS:
+        raise ValueError(f"sr_links hold {len(labels)} clusters: the facet figure takes at most {L.PLOT_MAX_PANELS}")
+    return panel.to(torch.uint8), labels.cpu().numpy().astype(np.int32)
+
+
 def make_gwes_plots(lr_links=None, sr_links=None, plt_folder=None, are_srlinks_ordered: bool = False, *, engine=None, D: int = 11,
-                    aracne: bool = True) -> dict:
+                    aracne: bool = True, reader: str = "pandas") -> dict:
     """``make_gwes_plots`` of the reference: ``lr_gwes.png`` from ``lr_links`` (frame or tsv path, six columns) and ``sr_gwes_clust.png`` /
     ``sr_gwes_combi.png`` from ``sr_links`` (frame or tsv path, nine columns) in ``plt_folder`` (default ``PLOTS`` in the working directory).
     Grey ARACNE == 0 points lie under the direct ones, which are drawn by ascending ``srp_max`` (``are_srlinks_ordered``: in reverse row order).
     With ``engine`` and no ``sr_links`` the short-range figures are rendered from the engine's resident reduced table (after
     ``perform_MI_computation``), without a copy to the host; ``aracne=False`` for a table whose ARACNE step was skipped (``runARACNE=False``: every
     link is drawn as direct, like the frame's ARACNE column of ones) — with the default the library refuses such a table instead of guessing.
+    ``reader="native"``: links given as paths are parsed on the device and never become a frame — the columns stay there, the facets come from
+    ``torch.unique`` on the device, and the figures are rendered from the device columns.
     Returns the paths written."""
     from .engine import Engine
+    from .links_io import check_reader
+    native = check_reader(reader)
     if plt_folder is None:
         plt_folder = os.path.join(os.getcwd(), "PLOTS")
-    lr = None if lr_links is None else _frame(lr_links, read_LongRangeLinks, 6, LR_COLS, LR_ERR)
-    sr = None if sr_links is None else _frame(sr_links, read_ShortRangeLinks, 9, SR_COLS, SR_ERR)
+    lr_dev, sr_dev = native and lr_links is not None and _is_path(lr_links), native and sr_links is not None and _is_path(sr_links)
+    lr = None if lr_links is None or lr_dev else _frame(lr_links, read_LongRangeLinks, 6, LR_COLS, LR_ERR)
+    sr = None if sr_links is None or sr_dev else _frame(sr_links, read_ShortRangeLinks, 9, SR_COLS, SR_ERR)
+    if lr_dev or sr_dev:
+        return _make_gwes_plots_native(lr_links if lr_dev else None, lr, sr_links if sr_dev else None, sr, plt_folder, are_srlinks_ordered, engine, D)
     from_engine = sr is None and engine is not None
     if from_engine and are_srlinks_ordered:
         raise ValueError("are_srlinks_ordered needs the sr_links frame: the engine's resident table has no row order of its own")
@@ -234,6 +269,46 @@ def make_gwes_plots(lr_links=None, sr_links=None, plt_folder=None, are_srlinks_o
         elif from_engine:
             render_links(eng, 0, opts=plot_opts(L.PLOT_SR_CLUST, D), use_aracne=bool(aracne), path=out["sr_gwes_clust"])
             render_links(eng, 0, opts=plot_opts(L.PLOT_SR_COMBI, D), use_aracne=bool(aracne), path=out["sr_gwes_combi"])
+    finally:
+        if own:
+            eng.close()
+    return out
+
+
+def _sr_figures(eng, cols, panel, labels, D, ordered, out):
+    render_scatter(eng, *cols, panel, opts=plot_opts(L.PLOT_SR_CLUST, D, ordered), n_panels=max(len(labels), 1), labels=labels, path=out["sr_gwes_clust"])
+    render_scatter(eng, *cols, None, opts=plot_opts(L.PLOT_SR_COMBI, D, ordered), path=out["sr_gwes_combi"])
+
+
+def _make_gwes_plots_native(lr_path, lr, sr_path, sr, plt_folder, ordered, engine, D) -> dict:
+    """make_gwes_plots with at least one table read on the device.  A table's figures are rendered before the next file is read: the device
+    columns alias the engine's one buffer."""
+    from .engine import Engine
+    os.makedirs(plt_folder, exist_ok=True)
+    own = engine is None
+    eng = Engine(0) if own else engine
+    out = {}
+    try:
+        if lr_path is not None or lr is not None:
+            out["lr_gwes"] = os.path.join(plt_folder, "lr_gwes.png")
+            if lr_path is not None:
+                c = _device_columns(eng, lr_path, "lr", 6, LR_ERR)
+                x, y = c["len"], c["MI"]
+            else:
+                x, y = lr["len"].to_numpy(), lr["MI"].to_numpy()
+            render_scatter(eng, x, y, opts=plot_opts(L.PLOT_LR, D, layer_rgb=(0, 0)), path=out["lr_gwes"])
+        if sr_path is not None or sr is not None:
+            out["sr_gwes_clust"] = os.path.join(plt_folder, "sr_gwes_clust.png")
+            out["sr_gwes_combi"] = os.path.join(plt_folder, "sr_gwes_combi.png")
+            if sr_path is not None:
+                import torch
+                c = _device_columns(eng, sr_path, "sr", 9, SR_ERR)
+                panel, labels = sr_facets_device(c["clust_c"])
+                cols = (c["len"], c["MI"], c["srp_max"], (c["ARACNE"] != 0).to(torch.uint8))
+            else:
+                panel, labels = sr_facets(sr["clust_c"].to_numpy())
+                cols = (sr["len"].to_numpy(), sr["MI"].to_numpy(), sr["srp_max"].to_numpy(), (sr["ARACNE"].to_numpy() != 0).astype(np.uint8))
+            _sr_figures(eng, cols, panel, labels, D, ordered, out)
     finally:
         if own:
             eng.close()
