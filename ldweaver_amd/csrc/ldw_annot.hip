@@ -17,14 +17,12 @@
 #include <numeric>
 #include <vector>
 
-#include "ldw_prim.h"
-#include "ldw_internal.h"
+#include "ldw_work.h"
+#include "ldw_dev.h"
 
 using namespace ldw;
 
 namespace {
-
-dim3 grid_of(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384))); }
 
 constexpr int64_t UPDOWN = 5000;   // snpEff's default up/downstream length
 
@@ -53,27 +51,6 @@ __device__ __forceinline__ bool is_start(const char *k) {
 __device__ __forceinline__ char translate(const char *k) {
     const int a = tcag(k[0]), b = tcag(k[1]), d = tcag(k[2]);
     return (a < 0 || b < 0 || d < 0) ? 0 : AA_TCAG[a * 16 + b * 4 + d];
-}
-
-// first index in [0, n) with a[i] > v (n if none)
-__device__ __forceinline__ int64_t upper_bound_i32(const int32_t *__restrict__ a, int64_t n, int64_t v) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)a[mid] <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-// first index in [0, n) with a[i] >= v (n if none)
-__device__ __forceinline__ int64_t lower_bound_i32(const int32_t *__restrict__ a, int64_t n, int64_t v) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // The device image of the feature table (one int32 array, built by the host half of ldw_annot_snps):
@@ -112,7 +89,7 @@ __global__ __launch_bounds__(256) void k_annot_snp(Tables t, const char *__restr
         int best_imp = -1, best_a = 99, best_rank = 0x7fffffff;
         int64_t best_c = 0;
         int32_t cov_f = -1, cov_rank = 0x7fffffff;
-        for (int64_t j = upper_bound_i32(t.stl, t.nseg, p) - 1; j >= 0 && t.stm[j] >= p; --j) {
+        for (int64_t j = upper_bound_dev<int64_t>(t.stl, t.nseg, p) - 1; j >= 0 && t.stm[j] >= p; --j) {
             const int32_t s = t.sti[j];
             if (t.S[s * 4 + 1] < p) continue;
             const int32_t f = t.S[s * 4 + 3];
@@ -158,8 +135,8 @@ __global__ __launch_bounds__(256) void k_annot_snp(Tables t, const char *__restr
         }
         if (cov_f < 0) {
             // ---- non-coding: the nearest feature end on each side (features whose extent holds p are on neither side)
-            const int64_t jr = upper_bound_i32(t.bsl, t.nfeat, p);              // first feature (by lo) that starts after p
-            const int64_t jl = lower_bound_i32(t.beh, t.nfeat, p) - 1;          // last feature (by hi) that ends before p
+            const int64_t jr = upper_bound_dev<int64_t>(t.bsl, t.nfeat, p);              // first feature (by lo) that starts after p
+            const int64_t jl = lower_bound_dev<int64_t>(t.beh, t.nfeat, p) - 1;          // last feature (by hi) that ends before p
             const int64_t dr = jr < t.nfeat ? t.bsl[jr] - p : INT64_MAX, dl = jl >= 0 ? p - t.beh[jl] : INT64_MAX;
             const int64_t d = dr < dl ? dr : dl;
             int a0 = -1;
@@ -209,12 +186,7 @@ __global__ __launch_bounds__(256) void k_map_ends(const double *__restrict__ pos
                                                   int64_t L, int32_t *__restrict__ used, int32_t *__restrict__ slot, unsigned long long *__restrict__ bad) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < 2 * n; e += (int64_t)gridDim.x * 256) {
         const double v = e < n ? pos1[e] : pos2[e - n];
-        int64_t lo = 0, hi = L;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((double)spos[mid] < v) lo = mid + 1;
-            else hi = mid;
-        }
+        const int64_t lo = lower_bound_dev<double>(spos, L, v);
         const bool one = lo < L && (double)spos[lo] == v && (lo + 1 == L || (double)spos[lo + 1] != v);
         if (!one) {
             atomicMin(bad, (unsigned long long)e);
@@ -234,10 +206,6 @@ __global__ __launch_bounds__(256) void k_map_rows(const int32_t *__restrict__ sl
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n2; e += stride) row[e] = ex[slot[e]];
     for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s < L; s += stride)
         if (used[s]) snp_of_row[ex[s]] = sidx[s];
-}
-
-__global__ __launch_bounds__(256) void k_iota32(int32_t *__restrict__ a, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) a[i] = (int32_t)i;
 }
 
 // ascending in the returned key = decreasing in x, NaN last (R's order(decreasing = TRUE), na.last = TRUE); -0 == 0
@@ -286,15 +254,6 @@ __global__ __launch_bounds__(256) void k_links_top(const int64_t *__restrict__ f
     for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256)
         if (flag[j] && ex[j] < kmax) top[ex[j]] = j;
 }
-
-struct Carve {
-    size_t off = 0;
-    template <class T> size_t take(int64_t n) {
-        const size_t o = off;
-        off += ((size_t)std::max<int64_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
-        return o;
-    }
-};
 
 }  // namespace
 
@@ -362,20 +321,20 @@ int ldw_annot_snps(ldw_ctx *c, const char *ref, int64_t g, const int32_t *seg, i
         beh[j] = F[(size_t)be[(size_t)j] * 8 + 1], bef[j] = be[(size_t)j];
     }
     Carve cv;
-    const size_t o_img = cv.take<int32_t>(nimg), o_ref = cv.take<char>(g), o_pos = cv.take<int32_t>(n), o_alt = cv.take<uint8_t>(n),
-                 o_rec = cv.take<int32_t>(n * LDW_ANNOT_REC);
-    if (int rc = c->annot_work.reserve(cv.off)) return rc;
-    char *wb = c->annot_work.as<char>();
-    int32_t *d_img = reinterpret_cast<int32_t *>(wb + o_img), *d_pos = reinterpret_cast<int32_t *>(wb + o_pos), *d_rec = reinterpret_cast<int32_t *>(wb + o_rec);
+    auto d_img = cv.take<int32_t>(nimg);
+    auto d_ref = cv.take<char>(g);
+    auto d_pos = cv.take<int32_t>(n);
+    auto d_alt = cv.take<uint8_t>(n);
+    auto d_rec = cv.take<int32_t>(n * LDW_ANNOT_REC);
+    if (int rc = cv.reserve(c->annot_work)) return rc;
     LDW_HIP(hipMemcpyAsync(d_img, img.data(), (size_t)nimg * 4, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(wb + o_ref, ref, (size_t)g, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(d_ref, ref, (size_t)g, hipMemcpyHostToDevice, c->stream));
     if (n > 0) {
         LDW_HIP(hipMemcpyAsync(d_pos, pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(wb + o_alt, alt_mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        LDW_HIP(hipMemcpyAsync(d_alt, alt_mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
         const int32_t *di = d_img;
         Tables t{di, di + nfeat * 8, di + (stl - w), di + (stm - w), di + (sti - w), di + (bsl - w), di + (bsf - w), di + (beh - w), di + (bef - w), nfeat, nseg};
-        hipLaunchKernelGGL(k_annot_snp, grid_of(n), dim3(256), 0, c->stream, t, wb + o_ref, g, d_pos, reinterpret_cast<const uint8_t *>(wb + o_alt), n, d_rec);
-        LDW_HIP(hipGetLastError());
+        LDW_LAUNCH(k_annot_snp, grid_of(n), dim3(256), 0, c->stream, t, d_ref, g, d_pos, d_alt, n, d_rec);
         LDW_HIP(hipMemcpyAsync(rec_out, d_rec, (size_t)n * LDW_ANNOT_REC * 4, hipMemcpyDeviceToHost, c->stream));
     }
     LDW_HIP(hipStreamSynchronize(c->stream));
@@ -391,40 +350,30 @@ int ldw_annot_map(ldw_ctx *c, const double *pos1, const double *pos2, int64_t n,
     for (int64_t i = 0; i < L; ++i) LDW_REQUIRE(POS[i] >= 1, LDW_ERR_ARG, "ldw_annot_map: POS[%lld] = %d is not positive", (long long)i, POS[i]);
     c->annot_n = -1;
     size_t sort_bytes = 0, scan_bytes = 0;
-    LDW_HIP((prim_sort_pairs<uint32_t, int32_t>(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)L, 0, 32, c->stream)));
-    LDW_HIP((prim_exclusive_sum<int32_t>(nullptr, scan_bytes, nullptr, nullptr, (size_t)L + 1, c->stream)));
+    LDW_HIP((prim_sort_pairs_bytes<uint32_t, int32_t>((size_t)L, 0, 32, c->stream, &sort_bytes)));
+    LDW_HIP(prim_scan_bytes<int32_t>((size_t)L + 1, c->stream, &scan_bytes));
     Carve cv;
-    const size_t o_pos = cv.take<uint32_t>(L), o_spos = cv.take<uint32_t>(L), o_iota = cv.take<int32_t>(L), o_sidx = cv.take<int32_t>(L),
-                 o_p1 = cv.take<double>(n), o_p2 = cv.take<double>(n), o_used = cv.take<int32_t>(L + 1), o_ex = cv.take<int32_t>(L + 1),
-                 o_slot = cv.take<int32_t>(2 * n), o_snp = cv.take<int32_t>(L), o_bad = cv.take<unsigned long long>(1),
-                 o_tmp = cv.take<char>((int64_t)std::max(sort_bytes, scan_bytes));
-    if (int rc = c->annot_work.reserve(cv.off)) return rc;
+    auto d_pos = cv.take<uint32_t>(L), spos = cv.take<uint32_t>(L);
+    auto iota = cv.take<int32_t>(L), sidx = cv.take<int32_t>(L);
+    auto p1 = cv.take<double>(n), p2 = cv.take<double>(n);
+    auto used = cv.take<int32_t>(L + 1), ex = cv.take<int32_t>(L + 1), slot = cv.take<int32_t>(2 * n), snp = cv.take<int32_t>(L);
+    auto bad = cv.take<unsigned long long>(1);
+    auto tmp = cv.take<char>((int64_t)std::max(sort_bytes, scan_bytes));
+    if (int rc = cv.reserve(c->annot_work)) return rc;
     if (int rc = c->annot_keep.reserve((size_t)std::max<int64_t>(2 * n, 1) * 4)) return rc;
-    char *w = c->annot_work.as<char>();
-    auto at = [&](size_t o) { return reinterpret_cast<void *>(w + o); };
-    uint32_t *d_pos = (uint32_t *)at(o_pos), *spos = (uint32_t *)at(o_spos);
-    int32_t *iota = (int32_t *)at(o_iota), *sidx = (int32_t *)at(o_sidx), *used = (int32_t *)at(o_used), *ex = (int32_t *)at(o_ex),
-            *slot = (int32_t *)at(o_slot), *snp = (int32_t *)at(o_snp);
-    double *p1 = (double *)at(o_p1), *p2 = (double *)at(o_p2);
-    unsigned long long *bad = (unsigned long long *)at(o_bad);
-    LDW_HIP(hipMemcpyAsync(d_pos, POS, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
     if (n > 0) {
         LDW_HIP(hipMemcpyAsync(p1, pos1, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemcpyAsync(p2, pos2, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     }
     LDW_HIP(hipMemsetAsync(used, 0, (size_t)(L + 1) * 4, c->stream));
     LDW_HIP(hipMemsetAsync(bad, 0xff, 8, c->stream));
-    hipLaunchKernelGGL(k_iota32, grid_of(L), dim3(256), 0, c->stream, iota, L);
-    LDW_HIP(hipGetLastError());
-    LDW_HIP((prim_sort_pairs<uint32_t, int32_t>(at(o_tmp), sort_bytes, d_pos, spos, iota, sidx, (size_t)L, 0, 32, c->stream)));
+    if (int rc = sort_positions(c, POS, L, 32, d_pos, iota, spos, sidx, tmp, sort_bytes)) return rc;
     if (n > 0) {
-        hipLaunchKernelGGL(k_map_ends, grid_of(2 * n), dim3(256), 0, c->stream, p1, p2, n, spos, L, used, slot, bad);
-        LDW_HIP(hipGetLastError());
+        LDW_LAUNCH(k_map_ends, grid_of(2 * n), dim3(256), 0, c->stream, p1, p2, n, spos, L, used, slot, bad);
     }
-    LDW_HIP((prim_exclusive_sum<int32_t>(at(o_tmp), scan_bytes, used, ex, (size_t)L + 1, c->stream)));
-    hipLaunchKernelGGL(k_map_rows, grid_of(std::max<int64_t>(2 * n, L)), dim3(256), 0, c->stream, slot, 2 * n, used, ex, sidx, L,
+    LDW_HIP((prim_exclusive_sum<int32_t>(tmp, scan_bytes, used, ex, (size_t)L + 1, c->stream)));
+    LDW_LAUNCH(k_map_rows, grid_of(std::max<int64_t>(2 * n, L)), dim3(256), 0, c->stream, slot, 2 * n, used, ex, sidx, L,
                        c->annot_keep.as<int32_t>(), snp);
-    LDW_HIP(hipGetLastError());
     unsigned long long h_bad = 0;
     int32_t h_rows = 0;
     LDW_HIP(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, c->stream));
@@ -456,37 +405,32 @@ int ldw_annot_links(ldw_ctx *c, const double *key, const double *aracne, int64_t
     *n_top_out = 0;
     if (n == 0) return LDW_OK;
     size_t sort_bytes = 0, scan_bytes = 0;
-    LDW_HIP((prim_sort_pairs<uint64_t, int64_t>(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)n, 0, 64, c->stream)));
-    LDW_HIP((prim_exclusive_sum<int64_t>(nullptr, scan_bytes, nullptr, nullptr, (size_t)n + 1, c->stream)));
+    LDW_HIP((prim_sort_pairs_bytes<uint64_t, int64_t>((size_t)n, 0, 64, c->stream, &sort_bytes)));
+    LDW_HIP(prim_scan_bytes<int64_t>((size_t)n + 1, c->stream, &scan_bytes));
     const int64_t kmax = std::min(max_tophits, n);
     Carve cv;
-    const size_t o_key = cv.take<double>(n), o_ar = cv.take<double>(n), o_code = cv.take<int8_t>(rows), o_cds = cv.take<int32_t>(rows),
-                 o_k = cv.take<uint64_t>(n), o_k2 = cv.take<uint64_t>(n), o_i = cv.take<int64_t>(n), o_perm = cv.take<int64_t>(n),
-                 o_r1 = cv.take<int32_t>(n), o_r2 = cv.take<int32_t>(n), o_pair = cv.take<int8_t>(n), o_flag = cv.take<int64_t>(n + 1),
-                 o_ex = cv.take<int64_t>(n + 1), o_top = cv.take<int64_t>(kmax), o_tmp = cv.take<char>((int64_t)std::max(sort_bytes, scan_bytes));
-    if (int rc = c->annot_work.reserve(cv.off)) return rc;
-    char *w = c->annot_work.as<char>();
-    auto at = [&](size_t o) { return reinterpret_cast<void *>(w + o); };
-    double *d_key = (double *)at(o_key), *d_ar = (double *)at(o_ar);
-    uint64_t *k1 = (uint64_t *)at(o_k), *k2 = (uint64_t *)at(o_k2);
-    int64_t *iv = (int64_t *)at(o_i), *perm = (int64_t *)at(o_perm), *flag = (int64_t *)at(o_flag), *ex = (int64_t *)at(o_ex), *top = (int64_t *)at(o_top);
-    int32_t *r1 = (int32_t *)at(o_r1), *r2 = (int32_t *)at(o_r2), *d_cds = (int32_t *)at(o_cds);
-    int8_t *d_code = (int8_t *)at(o_code), *pair = (int8_t *)at(o_pair);
+    auto d_key = cv.take<double>(n), d_ar = cv.take<double>(n);
+    auto d_code = cv.take<int8_t>(rows);
+    auto d_cds = cv.take<int32_t>(rows);
+    auto k1 = cv.take<uint64_t>(n), k2 = cv.take<uint64_t>(n);
+    auto iv = cv.take<int64_t>(n), perm = cv.take<int64_t>(n);
+    auto r1 = cv.take<int32_t>(n), r2 = cv.take<int32_t>(n);
+    auto pair = cv.take<int8_t>(n);
+    auto flag = cv.take<int64_t>(n + 1), ex = cv.take<int64_t>(n + 1), top = cv.take<int64_t>(kmax);
+    auto tmp = cv.take<char>((int64_t)std::max(sort_bytes, scan_bytes));
+    if (int rc = cv.reserve(c->annot_work)) return rc;
     LDW_HIP(hipMemcpyAsync(d_key, key, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     LDW_HIP(hipMemcpyAsync(d_ar, aracne, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     if (rows > 0) {
         LDW_HIP(hipMemcpyAsync(d_code, code, (size_t)rows, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemcpyAsync(d_cds, cds_id, (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
     }
-    hipLaunchKernelGGL(k_links_key, grid_of(n), dim3(256), 0, c->stream, d_key, n, k1, iv);
-    LDW_HIP(hipGetLastError());
-    LDW_HIP((prim_sort_pairs<uint64_t, int64_t>(at(o_tmp), sort_bytes, k1, k2, iv, perm, (size_t)n, 0, 64, c->stream)));
-    hipLaunchKernelGGL(k_links_join, grid_of(n + 1), dim3(256), 0, c->stream, perm, n, c->annot_keep.as<int32_t>(), d_ar, d_code, d_cds, r1, r2, pair, flag);
-    LDW_HIP(hipGetLastError());
-    LDW_HIP((prim_exclusive_sum<int64_t>(at(o_tmp), scan_bytes, flag, ex, (size_t)n + 1, c->stream)));
+    LDW_LAUNCH(k_links_key, grid_of(n), dim3(256), 0, c->stream, d_key, n, k1, iv);
+    LDW_HIP((prim_sort_pairs<uint64_t, int64_t>(tmp, sort_bytes, k1, k2, iv, perm, (size_t)n, 0, 64, c->stream)));
+    LDW_LAUNCH(k_links_join, grid_of(n + 1), dim3(256), 0, c->stream, perm, n, c->annot_keep.as<int32_t>(), d_ar, d_code, d_cds, r1, r2, pair, flag);
+    LDW_HIP((prim_exclusive_sum<int64_t>(tmp, scan_bytes, flag, ex, (size_t)n + 1, c->stream)));
     if (kmax > 0) {
-        hipLaunchKernelGGL(k_links_top, grid_of(n), dim3(256), 0, c->stream, flag, ex, n, kmax, top);
-        LDW_HIP(hipGetLastError());
+        LDW_LAUNCH(k_links_top, grid_of(n), dim3(256), 0, c->stream, flag, ex, n, kmax, top);
     }
     int64_t total = 0;
     LDW_HIP(hipMemcpyAsync(&total, ex + n, 8, hipMemcpyDeviceToHost, c->stream));

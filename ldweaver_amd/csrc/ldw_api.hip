@@ -619,7 +619,7 @@ int ldw_ctx_destroy(ldw_ctx *c) {
                            &c->srm_q, &c->srm_n, &c->srm_md, &c->srm_part, &c->srm_shape, &c->srm_cnt, &c->red_row, &c->red_meta,
                            &c->red_srp, &c->pool_a, &c->pool_b, &c->pool_mi, &c->ar_key, &c->ar_val, &c->ar_key2, &c->ar_val2,
                            &c->ar_off, &c->ar_flags, &c->seq_perm, &c->dig_a, &c->dig_b, &c->apx_shift, &c->slot_papx, &c->pop_segs, &c->pop_wbeg, &c->pop_vpos,
-                           &c->pair_sums, &c->tab11[0], &c->tab11[1], &c->G2, &c->G3, &c->miss_key, &c->miss_val, &c->srd_lower, &c->srd_cur, &c->srd_out, &c->srd_seg, &c->pos_slot,
+                           &c->pair_sums, &c->tab11[0], &c->tab11[1], &c->G2, &c->G3, &c->miss_key, &c->miss_val, &c->srd_lower, &c->srd_cur, &c->srd_out, &c->srd_seg, &c->pos_ord.order, &c->pos_ord.srt, &c->pos_ord.slot,
                            &c->cds_keep, &c->cds_work, &c->annot_keep, &c->annot_work, &c->plot_work, &c->plot_cols};
     for (auto *b : bufs) b->release();
     for (int k = 0; k < LDW_NSLOT; ++k)
@@ -1085,6 +1085,20 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
     return LDW_OK;
 }
 
+}  // extern "C"
+
+// the host copy of new positions and what is known of their order; the order built from the old ones (ldw::pos_order) is dropped
+void ldw::set_pos_meta(ldw_ctx *c, const int32_t *POS, int64_t L) {
+    c->h_POS.assign(POS, POS + L);
+    c->pos_sorted = true;
+    for (int64_t i = 1; i < L && c->pos_sorted; ++i) c->pos_sorted = POS[i] >= POS[i - 1];
+    c->pos_strict = c->pos_sorted;
+    for (int64_t i = 1; i < L && c->pos_strict; ++i) c->pos_strict = POS[i] > POS[i - 1];
+    c->pos_ord.n_slots = 0;
+}
+
+extern "C" {
+
 int ldw_set_snp_meta(ldw_ctx *c, const double *r, const uint8_t *uqe, const int32_t *POS, const int32_t *paint, double g) {
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(ldw::have_alignment(c), LDW_ERR_STATE, "ldw_set_snp_meta: set the alignment first");
@@ -1106,12 +1120,7 @@ int ldw_set_snp_meta(ldw_ctx *c, const double *r, const uint8_t *uqe, const int3
     c->h_r.assign(r, r + L);
     c->r_min = r[0];
     for (int64_t i = 1; i < L; ++i) c->r_min = r[i] < c->r_min ? r[i] : c->r_min;
-    c->h_POS.assign(POS, POS + L);
-    c->pos_sorted = true;
-    for (int64_t i = 1; i < L && c->pos_sorted; ++i) c->pos_sorted = POS[i] >= POS[i - 1];
-    c->pos_strict = c->pos_sorted;
-    for (int64_t i = 1; i < L && c->pos_strict; ++i) c->pos_strict = POS[i] > POS[i - 1];
-    c->n_slots = 0;
+    ldw::set_pos_meta(c, POS, L);
     if (paint) c->h_paint.assign(paint, paint + L);
     else c->h_paint.assign((size_t)L, 0);
     c->paint_min = c->paint_max = 0;

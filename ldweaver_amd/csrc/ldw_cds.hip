@@ -15,44 +15,16 @@
 #include <cstring>
 #include <vector>
 
-#include "ldw_prim.h"
-#include "ldw_internal.h"
+#include "ldw_work.h"
 #include "ldw_dev.h"
 
 using namespace ldw;
 
 namespace {
 
-dim3 grid_of(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384))); }
-
-// first index i in [0, n) with a[i] >= v (n if none)
-template <class T>
-__device__ __forceinline__ int64_t lower_bound_dev(const T *__restrict__ a, int64_t n, int64_t v) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-// first index i in [0, n) with a[i] > v (n if none)
-template <class T>
-__device__ __forceinline__ int64_t upper_bound_dev(const T *__restrict__ a, int64_t n, int64_t v) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)a[mid] <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // per SNP: ref = ref_seq[POS - 1]; the ACGTN_table column with the reference row zeroed (.ACGTN2num); its sum and the states left > 0.
-// Also the identity permutation the sort carries along.
 __global__ __launch_bounds__(256) void k_cds_snp(const int32_t *__restrict__ counts, const uint32_t *__restrict__ pos, const char *__restrict__ ref,
-                                                 int64_t L, int64_t *__restrict__ snp_var, uint8_t *__restrict__ alt, char *__restrict__ refc,
-                                                 int32_t *__restrict__ iota) {
+                                                 int64_t L, int64_t *__restrict__ snp_var, uint8_t *__restrict__ alt, char *__restrict__ refc) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < L; i += (int64_t)gridDim.x * 256) {
         const char ch = ref[pos[i] - 1];
         const int row = acgtn_row(ch);
@@ -67,7 +39,6 @@ __global__ __launch_bounds__(256) void k_cds_snp(const int32_t *__restrict__ cou
         snp_var[i] = v;
         alt[i] = (uint8_t)m;
         refc[i] = ch;
-        iota[i] = (int32_t)i;
     }
 }
 
@@ -83,7 +54,7 @@ __global__ __launch_bounds__(256) void k_cds_var(const uint32_t *__restrict__ sp
                                                  double *__restrict__ var) {
     for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < ncds; j += (int64_t)gridDim.x * 256) {
         const int64_t s = starts[j], e = ends[j];
-        const int64_t lo = lower_bound_dev(spos, L, s), hi = upper_bound_dev(spos, L, e);
+        const int64_t lo = lower_bound_dev<int64_t>(spos, L, s), hi = upper_bound_dev<int64_t>(spos, L, e);
         var[j] = (e < s || hi <= lo) ? __builtin_nan("") : (double)(P[hi] - P[lo]) / (double)(e - s + 1);
     }
 }
@@ -97,7 +68,7 @@ __global__ __launch_bounds__(256) void k_cds_span(const uint32_t *__restrict__ s
             n_out[j] = 0;
             continue;
         }
-        const int64_t lo = upper_bound_dev(spos, L, (int64_t)starts[j]), hi = lower_bound_dev(spos, L, (int64_t)ends[j]);
+        const int64_t lo = upper_bound_dev<int64_t>(spos, L, starts[j]), hi = lower_bound_dev<int64_t>(spos, L, ends[j]);
         lo_out[j] = lo;
         n_out[j] = hi > lo ? hi - lo : 0;
     }
@@ -108,7 +79,7 @@ __global__ __launch_bounds__(256) void k_cds_stab(const int64_t *__restrict__ of
                                                   const int32_t *__restrict__ label, int32_t *__restrict__ ps) {
     const int64_t total = off[nkept];
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int64_t j = upper_bound_dev(off, nkept + 1, t) - 1;   // the CDS whose span holds t (empty spans share an offset and are skipped)
+        const int64_t j = upper_bound_dev<int64_t>(off, nkept + 1, t) - 1;   // the CDS whose span holds t (empty spans share an offset and are skipped)
         atomicMax(ps + lo[j] + (t - off[j]), label[j]);
     }
 }
@@ -181,16 +152,6 @@ __global__ __launch_bounds__(256) void k_run_fill(const int32_t *__restrict__ p,
     }
 }
 
-// bump allocation of one working buffer in 256-byte steps
-struct Carve {
-    size_t off = 0;
-    template <class T> size_t take(int64_t n) {
-        const size_t o = off;
-        off += ((size_t)std::max<int64_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -211,38 +172,36 @@ int ldw_cds_variation(ldw_ctx *c, const int32_t *POS, int64_t L, const char *ref
     unsigned end_bit = 1;
     while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)g) ++end_bit;
     size_t sort_bytes = 0, scan_bytes = 0;
-    LDW_HIP((prim_sort_pairs<uint32_t, int32_t>(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)L, 0, end_bit, c->stream)));
-    LDW_HIP((prim_exclusive_sum<int64_t>(nullptr, scan_bytes, nullptr, nullptr, (size_t)L + 1, c->stream)));
+    LDW_HIP((prim_sort_pairs_bytes<uint32_t, int32_t>((size_t)L, 0, end_bit, c->stream, &sort_bytes)));
+    LDW_HIP(prim_scan_bytes<int64_t>((size_t)L + 1, c->stream, &scan_bytes));
     Carve cv;
-    const size_t o_pos = cv.take<uint32_t>(L), o_ref = cv.take<char>(g), o_se = cv.take<int32_t>(2 * ncds), o_var = cv.take<double>(ncds),
-                 o_sv = cv.take<int64_t>(L), o_alt = cv.take<uint8_t>(L), o_rc = cv.take<char>(L), o_iota = cv.take<int32_t>(L),
-                 o_vs = cv.take<int64_t>(L + 1), o_P = cv.take<int64_t>(L + 1), o_tmp = cv.take<char>((int64_t)std::max(sort_bytes, scan_bytes));
-    if (int rc = c->cds_work.reserve(cv.off)) return rc;
+    auto d_pos = cv.take<uint32_t>(L);
+    auto d_ref = cv.take<char>(g);
+    auto d_se = cv.take<int32_t>(2 * ncds);
+    auto d_var = cv.take<double>(ncds);
+    auto d_sv = cv.take<int64_t>(L);
+    auto d_alt = cv.take<uint8_t>(L);
+    auto d_rc = cv.take<char>(L);
+    auto d_iota = cv.take<int32_t>(L);
+    auto d_vs = cv.take<int64_t>(L + 1), d_P = cv.take<int64_t>(L + 1);
+    auto tmp = cv.take<char>((int64_t)std::max(sort_bytes, scan_bytes));
+    if (int rc = cv.reserve(c->cds_work)) return rc;
     if (int rc = c->cds_keep.reserve((size_t)L * 8)) return rc;
-    char *w = c->cds_work.as<char>();
-    uint32_t *d_pos = reinterpret_cast<uint32_t *>(w + o_pos), *spos = c->cds_keep.as<uint32_t>();
-    int32_t *d_se = reinterpret_cast<int32_t *>(w + o_se), *d_iota = reinterpret_cast<int32_t *>(w + o_iota), *sidx = c->cds_keep.as<int32_t>() + L;
-    char *d_ref = w + o_ref, *d_rc = w + o_rc;
-    double *d_var = reinterpret_cast<double *>(w + o_var);
-    int64_t *d_sv = reinterpret_cast<int64_t *>(w + o_sv), *d_vs = reinterpret_cast<int64_t *>(w + o_vs), *d_P = reinterpret_cast<int64_t *>(w + o_P);
-    uint8_t *d_alt = reinterpret_cast<uint8_t *>(w + o_alt);
+    uint32_t *spos = c->cds_keep.as<uint32_t>();
+    int32_t *sidx = c->cds_keep.as<int32_t>() + L;
     c->cds_L = 0;
 
-    LDW_HIP(hipMemcpyAsync(d_pos, POS, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
     LDW_HIP(hipMemcpyAsync(d_ref, ref_seq, (size_t)g, hipMemcpyHostToDevice, c->stream));
     if (ncds > 0) {
         LDW_HIP(hipMemcpyAsync(d_se, cds_start, (size_t)ncds * 4, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemcpyAsync(d_se + ncds, cds_end, (size_t)ncds * 4, hipMemcpyHostToDevice, c->stream));
     }
-    hipLaunchKernelGGL(k_cds_snp, grid_of(L), dim3(256), 0, c->stream, c->counts.as<int32_t>(), d_pos, d_ref, L, d_sv, d_alt, d_rc, d_iota);
-    LDW_HIP(hipGetLastError());
-    LDW_HIP((prim_sort_pairs<uint32_t, int32_t>(w + o_tmp, sort_bytes, d_pos, spos, d_iota, sidx, (size_t)L, 0, end_bit, c->stream)));
-    hipLaunchKernelGGL(k_cds_gather, grid_of(L + 1), dim3(256), 0, c->stream, sidx, d_sv, L, d_vs);
-    LDW_HIP(hipGetLastError());
-    LDW_HIP((prim_exclusive_sum<int64_t>(w + o_tmp, scan_bytes, d_vs, d_P, (size_t)L + 1, c->stream)));
+    if (int rc = sort_positions(c, POS, L, end_bit, d_pos, d_iota, spos, sidx, tmp, sort_bytes)) return rc;
+    LDW_LAUNCH(k_cds_snp, grid_of(L), dim3(256), 0, c->stream, c->counts.as<int32_t>(), d_pos, d_ref, L, d_sv, d_alt, d_rc);
+    LDW_LAUNCH(k_cds_gather, grid_of(L + 1), dim3(256), 0, c->stream, sidx, d_sv, L, d_vs);
+    LDW_HIP((prim_exclusive_sum<int64_t>(tmp, scan_bytes, d_vs, d_P, (size_t)L + 1, c->stream)));
     if (ncds > 0) {
-        hipLaunchKernelGGL(k_cds_var, grid_of(ncds), dim3(256), 0, c->stream, spos, L, d_P, d_se, d_se + ncds, ncds, d_var);
-        LDW_HIP(hipGetLastError());
+        LDW_LAUNCH(k_cds_var, grid_of(ncds), dim3(256), 0, c->stream, spos, L, d_P, d_se, d_se + ncds, ncds, d_var);
         LDW_HIP(hipMemcpyAsync(var_out, d_var, (size_t)ncds * 8, hipMemcpyDeviceToHost, c->stream));
     }
     if (snp_var_out) LDW_HIP(hipMemcpyAsync(snp_var_out, d_sv, (size_t)L * 8, hipMemcpyDeviceToHost, c->stream));
@@ -269,19 +228,15 @@ int ldw_cds_paint(ldw_ctx *c, const int32_t *cds_start, const int32_t *cds_end, 
     const int32_t *sidx = c->cds_keep.as<int32_t>() + L;
 
     size_t scan64 = 0, scan32 = 0;
-    LDW_HIP((prim_exclusive_sum<int64_t>(nullptr, scan64, nullptr, nullptr, (size_t)nkept + 1, c->stream)));
-    LDW_HIP((prim_exclusive_sum<int32_t>(nullptr, scan32, nullptr, nullptr, (size_t)L + 1, c->stream)));
+    LDW_HIP(prim_scan_bytes<int64_t>((size_t)nkept + 1, c->stream, &scan64));
+    LDW_HIP(prim_scan_bytes<int32_t>((size_t)L + 1, c->stream, &scan32));
     Carve cv;
-    const size_t o_se = cv.take<int32_t>(3 * nkept), o_lo = cv.take<int64_t>(nkept), o_n = cv.take<int64_t>(nkept + 1), o_off = cv.take<int64_t>(nkept + 1),
-                 o_ps = cv.take<int32_t>(L), o_p = cv.take<int32_t>(L), o_f = cv.take<int32_t>(L + 1), o_ex = cv.take<int32_t>(L + 1),
-                 o_rbeg = cv.take<int32_t>(L + 1), o_rval = cv.take<int32_t>(L + 1), o_out = cv.take<int32_t>(L), o_st = cv.take<int32_t>(4),
-                 o_tmp = cv.take<char>((int64_t)std::max(scan64, scan32));
-    if (int rc = c->cds_work.reserve(cv.off)) return rc;
-    char *w = c->cds_work.as<char>();
-    int32_t *d_se = reinterpret_cast<int32_t *>(w + o_se), *ps = reinterpret_cast<int32_t *>(w + o_ps), *p = reinterpret_cast<int32_t *>(w + o_p),
-            *f = reinterpret_cast<int32_t *>(w + o_f), *ex = reinterpret_cast<int32_t *>(w + o_ex), *rbeg = reinterpret_cast<int32_t *>(w + o_rbeg),
-            *rval = reinterpret_cast<int32_t *>(w + o_rval), *out = reinterpret_cast<int32_t *>(w + o_out), *st = reinterpret_cast<int32_t *>(w + o_st);
-    int64_t *lo = reinterpret_cast<int64_t *>(w + o_lo), *n = reinterpret_cast<int64_t *>(w + o_n), *off = reinterpret_cast<int64_t *>(w + o_off);
+    auto d_se = cv.take<int32_t>(3 * nkept);
+    auto lo = cv.take<int64_t>(nkept), n = cv.take<int64_t>(nkept + 1), off = cv.take<int64_t>(nkept + 1);
+    auto ps = cv.take<int32_t>(L), p = cv.take<int32_t>(L), f = cv.take<int32_t>(L + 1), ex = cv.take<int32_t>(L + 1);
+    auto rbeg = cv.take<int32_t>(L + 1), rval = cv.take<int32_t>(L + 1), out = cv.take<int32_t>(L), st = cv.take<int32_t>(4);
+    auto tmp = cv.take<char>((int64_t)std::max(scan64, scan32));
+    if (int rc = cv.reserve(c->cds_work)) return rc;
 
     LDW_HIP(hipMemsetAsync(ps, 0, (size_t)L * 4, c->stream));
     LDW_HIP(hipMemsetAsync(st, 0, 16, c->stream));
@@ -290,22 +245,15 @@ int ldw_cds_paint(ldw_ctx *c, const int32_t *cds_start, const int32_t *cds_end, 
         LDW_HIP(hipMemcpyAsync(d_se + nkept, cds_end, (size_t)nkept * 4, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemcpyAsync(d_se + 2 * nkept, label, (size_t)nkept * 4, hipMemcpyHostToDevice, c->stream));
     }
-    hipLaunchKernelGGL(k_cds_span, grid_of(nkept + 1), dim3(256), 0, c->stream, spos, L, d_se, d_se + nkept, nkept, lo, n);
-    LDW_HIP(hipGetLastError());
-    LDW_HIP((prim_exclusive_sum<int64_t>(w + o_tmp, scan64, n, off, (size_t)nkept + 1, c->stream)));
-    hipLaunchKernelGGL(k_cds_stab, grid_of(L), dim3(256), 0, c->stream, off, nkept, lo, d_se + 2 * nkept, ps);
-    LDW_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cds_scatter, grid_of(L), dim3(256), 0, c->stream, sidx, ps, L, p);
-    LDW_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_run_flags, grid_of(L + 1), dim3(256), 0, c->stream, p, L, f);
-    LDW_HIP(hipGetLastError());
-    LDW_HIP((prim_exclusive_sum<int32_t>(w + o_tmp, scan32, f, ex, (size_t)L + 1, c->stream)));
-    hipLaunchKernelGGL(k_run_compact, grid_of(L + 1), dim3(256), 0, c->stream, p, f, ex, L, rbeg, rval, st);
-    LDW_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_run_fix, dim3(1), dim3(64), 0, c->stream, ex, L, rbeg, rval, quirk_mode, st);
-    LDW_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_run_fill, grid_of(L), dim3(256), 0, c->stream, p, L, f, ex, rbeg, rval, st, out);
-    LDW_HIP(hipGetLastError());
+    LDW_LAUNCH(k_cds_span, grid_of(nkept + 1), dim3(256), 0, c->stream, spos, L, d_se, d_se + nkept, nkept, lo, n);
+    LDW_HIP((prim_exclusive_sum<int64_t>(tmp, scan64, n, off, (size_t)nkept + 1, c->stream)));
+    LDW_LAUNCH(k_cds_stab, grid_of(L), dim3(256), 0, c->stream, off, nkept, lo, d_se + 2 * nkept, ps);
+    LDW_LAUNCH(k_cds_scatter, grid_of(L), dim3(256), 0, c->stream, sidx, ps, L, p);
+    LDW_LAUNCH(k_run_flags, grid_of(L + 1), dim3(256), 0, c->stream, p, L, f);
+    LDW_HIP((prim_exclusive_sum<int32_t>(tmp, scan32, f, ex, (size_t)L + 1, c->stream)));
+    LDW_LAUNCH(k_run_compact, grid_of(L + 1), dim3(256), 0, c->stream, p, f, ex, L, rbeg, rval, st);
+    LDW_LAUNCH(k_run_fix, dim3(1), dim3(64), 0, c->stream, ex, L, rbeg, rval, quirk_mode, st);
+    LDW_LAUNCH(k_run_fill, grid_of(L), dim3(256), 0, c->stream, p, L, f, ex, rbeg, rval, st, out);
     int32_t h_st[4] = {0, 0, 0, 0};
     LDW_HIP(hipMemcpyAsync(h_st, st, 16, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(paint_out, out, (size_t)L * 4, hipMemcpyDeviceToHost, c->stream));

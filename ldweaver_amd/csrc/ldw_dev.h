@@ -78,4 +78,29 @@ __host__ __device__ __forceinline__ int acgtn_row(char c) {
     }
 }
 
+// Binary searches over an ascending array a[0 .. n): the elements are compared as C (int64_t for positions against CDS bounds, int32_t for a
+// parsed position, double for a link end that may be fractional).
+// first index i with a[i] >= v (n if none)
+template <class C, class T>
+__device__ __forceinline__ int64_t lower_bound_dev(const T *__restrict__ a, int64_t n, C v) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((C)a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// first index i with a[i] > v (n if none)
+template <class C, class T>
+__device__ __forceinline__ int64_t upper_bound_dev(const T *__restrict__ a, int64_t n, C v) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((C)a[mid] <= v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 }  // namespace ldw

@@ -231,7 +231,7 @@ static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sh
     auto done2 = [&](int code) { return done(code); };
     if ((rc = ldw::launch_state_counts(c))) return done(rc);
     size_t scan_bytes = 0;
-    HC(ldw::prim_exclusive_sum<int32_t>(nullptr, scan_bytes, (const int32_t *)nullptr, (int32_t *)nullptr, (size_t)L + 1, c->stream));
+    HC(ldw::prim_scan_bytes<int32_t>((size_t)L + 1, c->stream, &scan_bytes));
     const size_t o_off = ((size_t)(L + 1) * 4 + 255) / 256 * 256, o_scan = 2 * o_off;
     if ((rc = tmp.reserve(o_scan + scan_bytes + 256))) return done(rc);
     int32_t *d_ncol = tmp.as<int32_t>(), *d_off = reinterpret_cast<int32_t *>(tmp.as<char>() + o_off);

@@ -172,8 +172,13 @@ struct ldw_ctx {
     int32_t paint_min = 0, paint_max = 0;
     bool pos_sorted = true;      // POS ascends over the whole alignment (the reference's parser emits it so; any order is accepted)
     bool pos_strict = true;      // ... strictly: the SNP index is the rank among the distinct positions (no slot array needed)
-    ldw::DevBuf pos_slot;        // otherwise int32[L]: rank of a SNP's position among the sorted distinct positions (ldw::pos_slots, built on first use)
-    int64_t n_slots = 0;         // number of distinct positions; 0 = pos_slot not built for the current meta data
+    // The ascending order of the positions (ldw::pos_order builds it on first use; ldw::set_pos_meta drops it), int32[L] each on the device:
+    struct PosOrder {
+        ldw::DevBuf order;       // the SNP of every sorted entry, SNPs of one position in index order  (not built when pos_sorted: it is the identity)
+        ldw::DevBuf srt;         // the sorted positions                                               (not built when pos_sorted: POS itself)
+        ldw::DevBuf slot;        // per SNP the rank of its position among the distinct positions      (not built when pos_strict: the SNP index)
+        int64_t n_slots = 0;     // number of distinct positions; 0 = not built for the current positions
+    } pos_ord;
     double sr_total_dist = -1;   // number of SNP pairs within sr_total_dist on the circle (sizes the short-range table once; reset with the meta data)
     int64_t sr_total = -1;
     uint64_t sr_share_key = 0;   // r05: the last SHARE of the block list a pass was sized for (hash of blocks + sr_dist) and its exact short-range row count
@@ -311,6 +316,7 @@ void warm_apx();
 void warm_gemm_bits();
 void ctx_count(int d);               // ldw_api.hip: live contexts of the process (the last one to go trims the device free list to its idle cap)
 struct DrainedScope { DrainedScope(); ~DrainedScope(); };   // releases inside: the caller has drained every stream that could touch the blocks
+void set_pos_meta(ldw_ctx *ctx, const int32_t *POS, int64_t L);   // ldw_api.hip: h_POS, pos_sorted, pos_strict; drops pos_ord
 int launch_state_counts(ldw_ctx *ctx);   // ldw_api.hip: per-SNP state counts into ctx->counts on the context's stream (no copy, no synchronisation)
 size_t device_pool_trim();          // ldw_api.hip: give the released device blocks kept for re-use back to the runtime (ldw_host_trim); bytes
 void warm_srp();
@@ -319,7 +325,7 @@ int reduced_import_full(ldw_ctx *ctx, int64_t n_red, const int32_t *a, const int
                         const int32_t *pool_a, const int32_t *pool_b, const double *pool_MI);
 void warm_post();
 // ldw_post.hip: the graph node of every SNP for consumers that work on positions (LD map, ARACNE): *slot = null and *n_nodes = L when POS
-// ascends strictly, else the device array ctx->pos_slot (SNPs sharing a position share a node) and the number of distinct positions
+// ascends strictly, else the device array ctx->pos_ord.slot (SNPs sharing a position share a node) and the number of distinct positions
 int pos_slots(ldw_ctx *ctx, const int32_t **slot, int64_t *n_nodes);
 void out_release(ldw_ctx *ctx);      // ldw_out.hip: the alignment writer's staging (ldw_ctx_destroy)
 int64_t out_trim(ldw_ctx *ctx);      // ... its pinned buffers and device image only (ldw_host_trim); bytes released

@@ -11,10 +11,10 @@
 #include <cstring>
 #include <vector>
 
-#include "ldw_internal.h"
+#include "ldw_work.h"
+#include "ldw_dev.h"
 #include "ldw_fasta.h"
 #include "ldw_links_read.h"
-#include "ldw_prim.h"
 
 using namespace ldw;
 
@@ -271,17 +271,6 @@ __global__ __launch_bounds__(256) void k_tsv_patch(const uint32_t *__restrict__ 
 
 // ---- ldw_links_load ---------------------------------------------------------------------------------------------------------------------------
 
-// first index k with srt[k] >= v
-__device__ __forceinline__ int32_t lower_bound_i32(const int32_t *__restrict__ srt, int32_t L, int32_t v) {
-    int32_t lo = 0, hi = L;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (srt[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // keep[i] = the row stays (its min_len_col value is not below min_len); for those: idx1 / idx2 = SNP index of pos1 / pos2 (the first SNP at that position:
 // srt = positions ascending, order = the SNP of every sorted position, null when POS itself ascends).  bad = min of row << 8 | file column << 4 | reason:
 // the leftmost fault of the earliest bad row.
@@ -303,7 +292,7 @@ __global__ __launch_bounds__(256) void k_links_map(const double *__restrict__ p1
                 why = POS_RANGE;
             } else {
                 const int32_t q = (int32_t)v;
-                at = lower_bound_i32(srt, L, q);
+                at = (int32_t)lower_bound_dev<int32_t>(srt, L, q);
                 if (at >= L || srt[at] != q) why = POS_UNKNOWN;
                 else if (order) at = order[at];
             }
@@ -340,7 +329,7 @@ struct TsvState {
     std::string path;                    // of the last read, for the line numbers of ldw_links_load's refusals
     int variant = 0;                     // 0: rows parsed from cached global loads, 1: from an LDS-staged tile
     double ms[8] = {};                   // last read: total, read (host), copy, line kernels, parse kernel, slow-cell patch, chunks, bytes
-    DevBuf keep, koff, idx1, idx2, bad, srt, order;   // ldw_links_load
+    DevBuf keep, koff, idx1, idx2, bad;   // ldw_links_load
 };
 
 TsvState *tsv_state(ldw_ctx *c) {
@@ -424,7 +413,7 @@ void tsv_release(ldw_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     free_pins(t);
     if (t->pin_res) (void)hipHostFree(t->pin_res);
-    for (DevBuf *b : {&t->img, &t->cnt, &t->off, &t->starts, &t->slow, &t->res, &t->patch, &t->scan_tmp, &t->cols, &t->keep, &t->koff, &t->idx1, &t->idx2, &t->bad, &t->srt, &t->order})
+    for (DevBuf *b : {&t->img, &t->cnt, &t->off, &t->starts, &t->slow, &t->res, &t->patch, &t->scan_tmp, &t->cols, &t->keep, &t->koff, &t->idx1, &t->idx2, &t->bad})
         b->release();
     for (auto &row : t->ev)
         for (auto &e : row)
@@ -474,7 +463,7 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
     if (int rc = t->cnt.reserve((size_t)(max_blocks + 1) * 4)) return rc;
     if (int rc = t->off.reserve((size_t)(max_blocks + 1) * 4)) return rc;
     size_t scan_bytes = 0;
-    LDW_HIP(prim_exclusive_sum(nullptr, scan_bytes, t->cnt.as<uint32_t>(), t->off.as<uint32_t>(), (size_t)max_blocks + 1, c->stream));
+    LDW_HIP(prim_scan_bytes<uint32_t>((size_t)max_blocks + 1, c->stream, &scan_bytes));
     if (int rc = t->scan_tmp.reserve(scan_bytes)) return rc;
     for (auto &p : t->pin) memset(p, '\n', (size_t)TSV_FRONT);
 
@@ -524,9 +513,8 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
             }
             if (int rc2 = t->patch.reserve(host.size())) return rc2;
             LDW_HIP(hipMemcpyAsync(t->patch.p, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_tsv_patch, dim3((r.slow + 255) / 256), dim3(256), 0, c->stream, t->patch.as<uint32_t>(),
+            LDW_LAUNCH(k_tsv_patch, dim3((r.slow + 255) / 256), dim3(256), 0, c->stream, t->patch.as<uint32_t>(),
                                reinterpret_cast<const double *>(t->patch.as<unsigned char>() + voff), r.slow, t->ncols, t->cols.as<double>(), t->stride, k.row0);
-            LDW_HIP(hipGetLastError());
             LDW_HIP(hipStreamSynchronize(c->stream));   // (`host` goes out of scope)
             t->ms[5] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p0).count();
             slow_total += r.slow;
@@ -696,12 +684,7 @@ int ldw_set_positions(ldw_ctx *c, const int32_t *POS, int64_t L, double g) {
     c->h_r.clear();
     c->h_paint.clear();
     c->paint_min = c->paint_max = 0;
-    c->h_POS.assign(POS, POS + L);
-    c->pos_sorted = true;
-    for (int64_t i = 1; i < L && c->pos_sorted; ++i) c->pos_sorted = POS[i] >= POS[i - 1];
-    c->pos_strict = c->pos_sorted;
-    for (int64_t i = 1; i < L && c->pos_strict; ++i) c->pos_strict = POS[i] > POS[i - 1];
-    c->n_slots = 0;
+    set_pos_meta(c, POS, L);
     c->g = g;
     c->have_meta = true;
     c->sr_total = c->sr_share_rows = -1;
@@ -733,20 +716,12 @@ int ldw_links_load(ldw_ctx *c, int which, int32_t pos1_col, int32_t pos2_col, in
     DevBuf &A = which == 0 ? c->sr_a : c->lr_a, &B = which == 0 ? c->sr_b : c->lr_b, &M = which == 0 ? c->sr_mi : c->lr_mi;
     int64_t kept = 0;
     if (n > 0) {
-        // the positions in ascending order: POS itself, or a sorted copy with the SNP of every entry (the first SNP of a position first: a stable sort)
+        // the positions in ascending order: POS itself, or the context's sorted copy with the SNP of every entry (the first SNP of a position first)
         const int32_t *d_srt = c->POS.as<int32_t>(), *d_order = nullptr;
         if (!c->pos_sorted) {
-            std::vector<int32_t> ord((size_t)L), srt((size_t)L);
-            for (int64_t i = 0; i < L; ++i) ord[(size_t)i] = (int32_t)i;
-            std::stable_sort(ord.begin(), ord.end(), [&](int32_t u, int32_t v) { return c->h_POS[(size_t)u] < c->h_POS[(size_t)v]; });
-            for (int64_t i = 0; i < L; ++i) srt[(size_t)i] = c->h_POS[(size_t)ord[(size_t)i]];
-            if (int rc = t->srt.reserve((size_t)L * 4)) return rc;
-            if (int rc = t->order.reserve((size_t)L * 4)) return rc;
-            LDW_HIP(hipMemcpyAsync(t->srt.p, srt.data(), (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
-            LDW_HIP(hipMemcpyAsync(t->order.p, ord.data(), (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
-            LDW_HIP(hipStreamSynchronize(c->stream));   // (the vectors go out of scope)
-            d_srt = t->srt.as<int32_t>();
-            d_order = t->order.as<int32_t>();
+            if (int rc = pos_order(c)) return rc;
+            d_srt = c->pos_ord.srt.as<int32_t>();
+            d_order = c->pos_ord.order.as<int32_t>();
         }
         if (int rc = t->keep.reserve((size_t)(n + 1) * 4)) return rc;
         if (int rc = t->koff.reserve((size_t)(n + 1) * 4)) return rc;
@@ -754,17 +729,15 @@ int ldw_links_load(ldw_ctx *c, int which, int32_t pos1_col, int32_t pos2_col, in
         if (int rc = t->idx2.reserve((size_t)n * 4)) return rc;
         if (int rc = t->bad.reserve(8)) return rc;
         size_t sb = 0;
-        LDW_HIP(prim_exclusive_sum(nullptr, sb, t->keep.as<uint32_t>(), t->koff.as<uint32_t>(), (size_t)n + 1, c->stream));
+        LDW_HIP(prim_scan_bytes<uint32_t>((size_t)n + 1, c->stream, &sb));
         if (int rc = t->scan_tmp.reserve(sb)) return rc;
         sb = t->scan_tmp.cap;
         const double *cols = t->cols.as<double>();
-        const int grid = (int)std::min<int64_t>((n + 255) / 256, 16384);
         LDW_HIP(hipMemsetAsync(t->bad.p, 0xff, 8, c->stream));
         LDW_HIP(hipMemsetAsync(t->keep.as<uint32_t>() + n, 0, 4, c->stream));
-        hipLaunchKernelGGL(k_links_map, dim3(grid), dim3(256), 0, c->stream, cols + (int64_t)pos1_col * t->stride, cols + (int64_t)pos2_col * t->stride,
+        LDW_LAUNCH(k_links_map, grid_of(n), dim3(256), 0, c->stream, cols + (int64_t)pos1_col * t->stride, cols + (int64_t)pos2_col * t->stride,
                            min_len_col >= 0 ? cols + (int64_t)min_len_col * t->stride : nullptr, min_len, n, d_srt, d_order, (int32_t)L, (uint32_t)pos1_col, (uint32_t)pos2_col, t->keep.as<uint32_t>(),
                            t->idx1.as<int32_t>(), t->idx2.as<int32_t>(), t->bad.as<unsigned long long>());
-        LDW_HIP(hipGetLastError());
         LDW_HIP(prim_exclusive_sum(t->scan_tmp.p, sb, t->keep.as<uint32_t>(), t->koff.as<uint32_t>(), (size_t)n + 1, c->stream));
         unsigned long long bad = 0;
         uint32_t total = 0;
@@ -788,9 +761,8 @@ int ldw_links_load(ldw_ctx *c, int which, int32_t pos1_col, int32_t pos2_col, in
         if (int rc = A.reserve((size_t)std::max<int64_t>(kept, 1) * 4)) return rc;
         if (int rc = B.reserve((size_t)std::max<int64_t>(kept, 1) * 4)) return rc;
         if (int rc = M.reserve((size_t)std::max<int64_t>(kept, 1) * 8)) return rc;
-        hipLaunchKernelGGL(k_links_compact, dim3(grid), dim3(256), 0, c->stream, t->keep.as<uint32_t>(), t->koff.as<uint32_t>(), t->idx1.as<int32_t>(), t->idx2.as<int32_t>(),
+        LDW_LAUNCH(k_links_compact, grid_of(n), dim3(256), 0, c->stream, t->keep.as<uint32_t>(), t->koff.as<uint32_t>(), t->idx1.as<int32_t>(), t->idx2.as<int32_t>(),
                            cols + (int64_t)mi_col * t->stride, n, A.as<int32_t>(), B.as<int32_t>(), M.as<double>());
-        LDW_HIP(hipGetLastError());
         LDW_HIP(hipStreamSynchronize(c->stream));
     }
     (which == 0 ? c->n_sr : c->n_lr) = kept;

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "ldw_dev.h"
-#include "ldw_internal.h"
+#include "ldw_work.h"
 #include "ldw_plot.h"
 
 #pragma clang fp contract(off)
@@ -281,6 +281,7 @@ struct PlotStats {
 };
 
 constexpr size_t PLOT_CONST_BYTES = (size_t)PLOT_MAX_BLOCKS * PLOT_NPART * 8 + 1024;   // statistics partials + the cluster marks
+static_assert(PLOT_CONST_BYTES % 256 == 0, "the carved plot_work keeps its byte count");
 
 int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, PLOT_MAX_BLOCKS)); }
 
@@ -297,8 +298,7 @@ int check_opts(const ldw_plot_opts *o, const char *who, int &D) {
 template <class Src>
 int stats_accum(ldw_ctx *c, const Src &s, int64_t m, int n_panels, double *d_part, double *v) {
     const int grid = grid_for(m);
-    hipLaunchKernelGGL(k_plot_stats<Src>, dim3(grid), dim3(256), 0, c->stream, s, m, n_panels, d_part);
-    LDW_HIP(hipGetLastError());
+    LDW_LAUNCH(k_plot_stats<Src>, dim3(grid), dim3(256), 0, c->stream, s, m, n_panels, d_part);
     std::vector<double> part((size_t)grid * PLOT_NPART);
     LDW_HIP(hipMemcpyAsync(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
@@ -424,12 +424,12 @@ int plot_panels(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int6
     LDW_REQUIRE(W >= 1 && H >= 1 && (int64_t)W * H * n_panels <= (1ll << 28), LDW_ERR_ARG, "%s: panels of %d x %d pixels", who, W, H);
     LDW_REQUIRE(rgb_out, LDW_ERR_ARG, "%s: null output", who);
     const size_t pixels = (size_t)n_panels * W * H;
-    const size_t kb = round256(pixels * 8), rb = round256(pixels * 3);
-    if (int rc = c->plot_work.reserve(kb + rb + PLOT_CONST_BYTES)) return rc;
-    unsigned long long *d_keys = c->plot_work.as<unsigned long long>();
-    uint8_t *d_rast = c->plot_work.as<uint8_t>() + kb;
-    double *d_part = (double *)(c->plot_work.as<uint8_t>() + kb + rb);
-    if (scratch_out) *scratch_out = (int64_t)(kb + rb + PLOT_CONST_BYTES);
+    Carve cv;
+    auto d_keys = cv.take<unsigned long long>((int64_t)pixels);
+    auto d_rast = cv.take<uint8_t>((int64_t)pixels * 3);
+    auto d_part = cv.take<double>(PLOT_CONST_BYTES / 8);
+    if (int rc = cv.reserve(c->plot_work)) return rc;
+    if (scratch_out) *scratch_out = (int64_t)cv.bytes;
     hipEvent_t ev[6] = {};
     struct EvGuard {
         hipEvent_t *e;
@@ -494,17 +494,19 @@ int plot_figure(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int6
     if (int rc = ldw_plot_layout_get(o->kind, n_panels, 0, 1, 0, 1, &lay)) return rc;   // (panel size: independent of the ranges)
     const int W = lay.panel_w, H = lay.panel_h;
     const size_t pixels = (size_t)n_panels * W * H;
-    const size_t kb = round256(pixels * 8), rb = round256(pixels * 3);
-    if (int rc = c->plot_work.reserve(kb + rb + PLOT_CONST_BYTES)) return rc;
-    uint8_t *work = c->plot_work.as<uint8_t>();
+    Carve cv;
+    auto d_keys = cv.take<unsigned long long>((int64_t)pixels);
+    auto d_rast = cv.take<uint8_t>((int64_t)pixels * 3);
+    auto d_part = cv.take<double>(PLOT_CONST_BYTES / 8);
+    if (int rc = cv.reserve(c->plot_work)) return rc;
     PlotStats st;
-    if (int rc = plot_stats(c, s, hc, n, n_panels, o, (double *)(work + kb + rb), st, who)) return rc;
+    if (int rc = plot_stats(c, s, hc, n, n_panels, o, d_part, st, who)) return rc;
     if (int rc = ldw_plot_layout_get(o->kind, n_panels, st.xr[0], st.xr[1], st.yr[0], st.yr[1], &lay)) return rc;
     if (int rc = plot_raster(c, s, hc, has_srp, n, o, D, n_panels, W, H, lay.xlim, lay.ylim, lay.n_xticks, lay.xtick_px, lay.n_yticks, lay.ytick_px, st,
-                             (unsigned long long *)work, work + kb, nullptr))
+                             d_keys, d_rast, nullptr))
         return rc;
     std::vector<uint8_t> rasters(pixels * 3);
-    LDW_HIP(hipMemcpyAsync(rasters.data(), work + kb, pixels * 3, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(rasters.data(), d_rast, pixels * 3, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     if (dropped_out) *dropped_out = st.dropped;
     return emit_figure(lay, o->kind, rasters, panel_label, nullptr, has_srp && st.lo <= st.hi, st.lo, st.hi, png_path, rgb_out);
@@ -551,8 +553,7 @@ int heat_figure(ldw_ctx *c, const double *d_htm, int32_t B, const char *title, c
     std::vector<uint8_t> ramp(PLOT_RAMP_N * 3);
     plot_ramp_table(ramp.data());
     LDW_HIP(hipMemcpyAsync(d_ramp, ramp.data(), ramp.size(), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_plot_heat, dim3(2048), dim3(256), 0, c->stream, d_htm, (int)B, W, H, d_ramp, d_rast);
-    LDW_HIP(hipGetLastError());
+    LDW_LAUNCH(k_plot_heat, dim3(2048), dim3(256), 0, c->stream, d_htm, (int)B, W, H, d_ramp, d_rast);
     std::vector<uint8_t> rasters(pixels * 3);
     LDW_HIP(hipMemcpyAsync(rasters.data(), d_rast, pixels * 3, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
@@ -627,8 +628,7 @@ int ldw_plot_links(ldw_ctx *c, int which, int use_aracne, const ldw_plot_opts *o
         if (int rc = c->plot_work.reserve(1024)) return rc;
         void *marks = c->plot_work.p;
         LDW_HIP(hipMemsetAsync(marks, 0, 1024, c->stream));
-        hipLaunchKernelGGL(k_plot_present, dim3(grid_for(n)), dim3(256), 0, c->stream, s.meta, n, (uint32_t *)marks);
-        LDW_HIP(hipGetLastError());
+        LDW_LAUNCH(k_plot_present, dim3(grid_for(n)), dim3(256), 0, c->stream, s.meta, n, (uint32_t *)marks);
         uint32_t present[256];
         LDW_HIP(hipMemcpyAsync(present, marks, 1024, hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));

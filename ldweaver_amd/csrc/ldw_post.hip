@@ -13,10 +13,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include "ldw_prim.h"
 #include <vector>
 
-#include "ldw_internal.h"
+#include "ldw_work.h"
 #include "ldw_dev.h"
 
 using namespace ldw;
@@ -166,30 +165,51 @@ __global__ __launch_bounds__(256) void k_ldmap_rescale(double *__restrict__ red,
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) red[i] = (red[i] - mn) / rn;
 }
 
-// Graph nodes of the position-based consumers: the rank of each SNP's position among the sorted DISTINCT positions (stable sort of h_POS, then a
-// running rank), so that SNPs sharing a position are one node like in the reference, which works on positions.  Strictly ascending POS needs
-// none (the SNP index is that rank); otherwise it is built once per ldw_set_snp_meta.
-int pos_slots(ldw_ctx *c, const int32_t **slot, int64_t *n_nodes) {
-    const int64_t L = c->L;
-    *slot = nullptr;
-    *n_nodes = L;
-    if (c->pos_strict) return LDW_OK;
-    if (c->n_slots == 0) {
-        std::vector<int32_t> ord((size_t)L), h((size_t)L);
-        for (int64_t i = 0; i < L; ++i) ord[(size_t)i] = (int32_t)i;
-        std::stable_sort(ord.begin(), ord.end(), [&](int32_t u, int32_t v) { return c->h_POS[(size_t)u] < c->h_POS[(size_t)v]; });
-        int32_t k = -1;
-        for (int64_t i = 0; i < L; ++i) {
-            if (i == 0 || c->h_POS[(size_t)ord[(size_t)i]] != c->h_POS[(size_t)ord[(size_t)i - 1]]) ++k;
-            h[(size_t)ord[(size_t)i]] = k;
-        }
-        if (int rc = c->pos_slot.reserve((size_t)L * 4)) return rc;
-        LDW_HIP(hipMemcpyAsync(c->pos_slot.p, h.data(), (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipStreamSynchronize(c->stream));   // (`h` goes out of scope)
-        c->n_slots = (int64_t)k + 1;
+// One stable sort of h_POS gives everything the position-based stages look up: the sorted positions with the SNP of every entry (ldw_links_load:
+// the first SNP of a position is the first of its run) and a running rank over the distinct positions (the graph nodes of the LD map and ARACNE, which
+// like the reference work on positions: SNPs sharing one are one node).  What the order of POS makes trivial is not built.
+int pos_order(ldw_ctx *c) {
+    auto &po = c->pos_ord;
+    if (c->pos_strict || po.n_slots > 0) return LDW_OK;
+    const size_t L = (size_t)c->L;
+    std::vector<int32_t> ord(L), srt(L), slot(L);
+    for (size_t i = 0; i < L; ++i) ord[i] = (int32_t)i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t u, int32_t v) { return c->h_POS[(size_t)u] < c->h_POS[(size_t)v]; });
+    int32_t k = -1;
+    for (size_t i = 0; i < L; ++i) {
+        srt[i] = c->h_POS[(size_t)ord[i]];
+        if (i == 0 || srt[i] != srt[i - 1]) ++k;
+        slot[(size_t)ord[i]] = k;
     }
-    *slot = c->pos_slot.as<int32_t>();
-    *n_nodes = c->n_slots;
+    if (int rc = po.slot.reserve(L * 4)) return rc;
+    LDW_HIP(hipMemcpyAsync(po.slot.p, slot.data(), L * 4, hipMemcpyHostToDevice, c->stream));
+    if (!c->pos_sorted) {
+        if (int rc = po.srt.reserve(L * 4)) return rc;
+        if (int rc = po.order.reserve(L * 4)) return rc;
+        LDW_HIP(hipMemcpyAsync(po.srt.p, srt.data(), L * 4, hipMemcpyHostToDevice, c->stream));
+        LDW_HIP(hipMemcpyAsync(po.order.p, ord.data(), L * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    LDW_HIP(hipStreamSynchronize(c->stream));   // (the vectors go out of scope)
+    po.n_slots = (int64_t)k + 1;
+    return LDW_OK;
+}
+
+int pos_slots(ldw_ctx *c, const int32_t **slot, int64_t *n_nodes) {
+    if (int rc = pos_order(c)) return rc;
+    *slot = c->pos_strict ? nullptr : c->pos_ord.slot.as<int32_t>();
+    *n_nodes = c->pos_strict ? c->L : c->pos_ord.n_slots;
+    return LDW_OK;
+}
+
+__global__ __launch_bounds__(256) void k_iota32(int32_t *__restrict__ a, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) a[i] = (int32_t)i;
+}
+
+int sort_positions(ldw_ctx *c, const int32_t *POS, int64_t L, unsigned end_bit, uint32_t *d_pos, int32_t *iota, uint32_t *spos, int32_t *sidx, void *tmp,
+                   size_t tmp_bytes) {
+    LDW_HIP(hipMemcpyAsync(d_pos, POS, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
+    LDW_LAUNCH(k_iota32, grid_of(L), dim3(256), 0, c->stream, iota, L);
+    LDW_HIP((prim_sort_pairs<uint32_t, int32_t>(tmp, tmp_bytes, d_pos, spos, iota, sidx, (size_t)L, 0, end_bit, c->stream)));
     return LDW_OK;
 }
 
@@ -255,10 +275,9 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     // ---- sorted MI keys -> order statistics ----
     if (int rc = c->ar_key.reserve((size_t)n * 8)) return rc;
     if (int rc = c->ar_key2.reserve((size_t)n * 8)) return rc;
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, 16384);
-    hipLaunchKernelGGL(k_mi_keys, dim3(grid), dim3(256), 0, c->stream, c->lr_mi.as<double>(), n, c->ar_key.as<uint64_t>());
+    LDW_LAUNCH(k_mi_keys, grid_of(n), dim3(256), 0, c->stream, c->lr_mi.as<double>(), n, c->ar_key.as<uint64_t>());
     size_t tb = 0;
-    LDW_HIP(prim_sort_keys(nullptr, tb, c->ar_key.as<uint64_t>(), c->ar_key2.as<uint64_t>(), (int)n, 0, 64, c->stream));
+    LDW_HIP(prim_sort_keys_bytes<uint64_t>((size_t)n, 0, 64, c->stream, &tb));
     if (int rc = c->scratch.reserve(tb)) return rc;
     tb = c->scratch.cap;
     LDW_HIP(prim_sort_keys(c->scratch.p, tb, c->ar_key.as<uint64_t>(), c->ar_key2.as<uint64_t>(), (int)n, 0, 64, c->stream));
@@ -283,11 +302,10 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     if (int rc = c->ar_off.reserve((size_t)(nseg_l + nseg_s + 2) * 8 * 2)) return rc;
     int64_t *cnt_l = c->ar_off.as<int64_t>(), *off_l = cnt_l + nseg_l + 1, *cnt_s = off_l + nseg_l + 1, *off_s = cnt_s + nseg_s + 1;
     auto count_pass = [&](double t, int64_t &n_red, int64_t &n_srp) -> int {
-        hipLaunchKernelGGL(k_count_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->lr_mi.as<double>(), n, t, cnt_l);
-        if (ns > 0) hipLaunchKernelGGL(k_count_gt, dim3((unsigned)nseg_s), dim3(256), 0, c->stream, d_smi, ns, t, cnt_s);
-        LDW_HIP(hipGetLastError());
+        LDW_LAUNCH(k_count_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->lr_mi.as<double>(), n, t, cnt_l);
+        if (ns > 0) LDW_LAUNCH(k_count_gt, dim3((unsigned)nseg_s), dim3(256), 0, c->stream, d_smi, ns, t, cnt_s);
         size_t sb = 0;
-        LDW_HIP(prim_exclusive_sum(nullptr, sb, cnt_l, off_l, (int)nseg_l, c->stream));
+        LDW_HIP(prim_scan_bytes<int64_t>((size_t)nseg_l, c->stream, &sb));
         if (int rc = c->scratch.reserve(sb)) return rc;
         sb = c->scratch.cap;
         LDW_HIP(prim_exclusive_sum(c->scratch.p, sb, cnt_l, off_l, (int)nseg_l, c->stream));
@@ -323,14 +341,13 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     if (int rc = c->pool_a.reserve((size_t)std::max<int64_t>(n_pool, 1) * 4)) return rc;
     if (int rc = c->pool_b.reserve((size_t)std::max<int64_t>(n_pool, 1) * 4)) return rc;
     if (int rc = c->pool_mi.reserve((size_t)std::max<int64_t>(n_pool, 1) * 8)) return rc;
-    hipLaunchKernelGGL(k_select_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(),
+    LDW_LAUNCH(k_select_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(),
                        c->lr_mi.as<double>(), n, tmin, off_l, (int64_t)0, c->red_row.as<int64_t>(), c->pool_a.as<int32_t>(),
                        c->pool_b.as<int32_t>(), c->pool_mi.as<double>());
     if (ns > 0)
-        hipLaunchKernelGGL(k_select_gt, dim3((unsigned)nseg_s), dim3(256), 0, c->stream, d_sa, d_sb,
+        LDW_LAUNCH(k_select_gt, dim3((unsigned)nseg_s), dim3(256), 0, c->stream, d_sa, d_sb,
                            d_smi, ns, tmin, off_s, n_red, (int64_t *)nullptr, c->pool_a.as<int32_t>(),
                            c->pool_b.as<int32_t>(), c->pool_mi.as<double>());
-    LDW_HIP(hipGetLastError());
     LDW_HIP(hipStreamSynchronize(c->stream));
     c->n_red = n_red;
     c->n_pool = n_pool;
@@ -367,12 +384,10 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
     int32_t *used = c->srm_cnt.as<int32_t>(), *rank = used + n_nodes + 1;
     LDW_HIP(hipMemsetAsync(used, 0, (size_t)(n_nodes + 1) * 4, c->stream));
     const int32_t *POS = c->POS.as<int32_t>();
-    auto grid_of = [](int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 16384)); };
-    if (nl > 0) hipLaunchKernelGGL(k_mark_used, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), nl, POS, from, to, windowed, used, d_slot);
-    if (ns > 0) hipLaunchKernelGGL(k_mark_used, grid_of(ns), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), ns, POS, from, to, windowed, used, d_slot);
-    LDW_HIP(hipGetLastError());
+    if (nl > 0) LDW_LAUNCH(k_mark_used, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), nl, POS, from, to, windowed, used, d_slot);
+    if (ns > 0) LDW_LAUNCH(k_mark_used, grid_of(ns), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), ns, POS, from, to, windowed, used, d_slot);
     size_t sb = 0;
-    LDW_HIP(prim_exclusive_sum(nullptr, sb, used, rank, (int)(n_nodes + 1), c->stream));
+    LDW_HIP(prim_scan_bytes<int32_t>((size_t)n_nodes + 1, c->stream, &sb));
     if (int rc = c->scratch.reserve(sb)) return rc;
     sb = c->scratch.cap;
     LDW_HIP(prim_exclusive_sum(c->scratch.p, sb, used, rank, (int)(n_nodes + 1), c->stream));
@@ -397,10 +412,9 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
     double *red = c->srm_q.as<double>(), *htm = red + 3 * nb, *mm = htm + nb;
     unsigned long long *acc_lo = reinterpret_cast<unsigned long long *>(red + nb), *acc_hi = acc_lo + nb;
     LDW_HIP(hipMemsetAsync(red, 0, (size_t)nb * 24, c->stream));
-    if (nl > 0) hipLaunchKernelGGL(k_ldmap_add, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>(), nl, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
-    if (ns > 0) hipLaunchKernelGGL(k_ldmap_add, grid_of(ns), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), ns, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
-    hipLaunchKernelGGL(k_ldmap_log, dim3(rgrid), dim3(256), 0, c->stream, red, acc_lo, acc_hi, (int)B, 1.0 / ((double)r * (double)r), htm, mm);
-    LDW_HIP(hipGetLastError());
+    if (nl > 0) LDW_LAUNCH(k_ldmap_add, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>(), nl, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
+    if (ns > 0) LDW_LAUNCH(k_ldmap_add, grid_of(ns), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), ns, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
+    LDW_LAUNCH(k_ldmap_log, dim3(rgrid), dim3(256), 0, c->stream, red, acc_lo, acc_hi, (int)B, 1.0 / ((double)r * (double)r), htm, mm);
     std::vector<double> hmm((size_t)rgrid * 2);
     LDW_HIP(hipMemcpyAsync(hmm.data(), mm, hmm.size() * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
@@ -410,8 +424,7 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
         mx = std::max(mx, hmm[2 * i + 1]);
     }
     const double rn = mx - mn;   // 0 -> NaN everywhere, like .rescale01
-    hipLaunchKernelGGL(k_ldmap_rescale, dim3(rgrid), dim3(256), 0, c->stream, htm, nb, mn, rn);
-    LDW_HIP(hipGetLastError());
+    LDW_LAUNCH(k_ldmap_rescale, dim3(rgrid), dim3(256), 0, c->stream, htm, nb, mn, rn);
     *d_htm = htm;
     return LDW_OK;
 }

@@ -22,5 +22,18 @@ template <class T>
 inline hipError_t prim_exclusive_sum(void *storage, size_t &bytes, const T *in, T *out, size_t n, hipStream_t st) {
     return rocprim::exclusive_scan(storage, bytes, in, out, T(0), n, rocprim::plus<T>(), st);
 }
+// the storage each of them needs for n items (the size query of the same instantiation)
+template <class K, class V>
+inline hipError_t prim_sort_pairs_bytes(size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t st, size_t *bytes) {
+    return prim_sort_pairs<K, V>(nullptr, *bytes, nullptr, nullptr, nullptr, nullptr, n, begin_bit, end_bit, st);
+}
+template <class K>
+inline hipError_t prim_sort_keys_bytes(size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t st, size_t *bytes) {
+    return prim_sort_keys<K>(nullptr, *bytes, nullptr, nullptr, n, begin_bit, end_bit, st);
+}
+template <class T>
+inline hipError_t prim_scan_bytes(size_t n, hipStream_t st, size_t *bytes) {
+    return prim_exclusive_sum<T>(nullptr, *bytes, nullptr, nullptr, n, st);
+}
 
 }  // namespace ldw

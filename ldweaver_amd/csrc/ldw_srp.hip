@@ -23,11 +23,10 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
-#include "ldw_prim.h"
 #include <thread>
 #include <vector>
 
-#include "ldw_internal.h"
+#include "ldw_work.h"
 #include "ldw_dev.h"
 
 using namespace ldw;
@@ -906,21 +905,20 @@ static int quant_two_sorts(ldw_ctx *c, int64_t n, int32_t S, int nclust, double 
     uint16_t *len16 = reinterpret_cast<uint16_t *>(pack), *len16b = len16 + n;   // pack is free after the first sort
     SrPay *pay = c->srm_pay.as<SrPay>(), *pay2 = c->srm_pay2.as<SrPay>();
     size_t t1 = 0, t2 = 0;
-    LDW_HIP(prim_sort_pairs(nullptr, t1, key, key2, pack, pack2, n, 0, 64, c->stream));
-    LDW_HIP(prim_sort_pairs(nullptr, t2, len16, len16b, pay, pay2, n, 0, 16, c->stream));
+    LDW_HIP((prim_sort_pairs_bytes<uint64_t, uint32_t>((size_t)n, 0, 64, c->stream, &t1)));
+    LDW_HIP((prim_sort_pairs_bytes<uint16_t, SrPay>((size_t)n, 0, 16, c->stream, &t2)));
     if (int rc = c->scratch.reserve(std::max(t1, t2))) return rc;
     size_t tb = c->scratch.cap;
     LDW_HIP(prim_sort_pairs(c->scratch.p, tb, key, key2, pack, pack2, n, 0, 64, c->stream));
-    hipLaunchKernelGGL(k_sr_split, dim3(grid), dim3(256), 0, c->stream, pack2, key2, n, len16, pay);
+    LDW_LAUNCH(k_sr_split, dim3(grid), dim3(256), 0, c->stream, pack2, key2, n, len16, pay);
     tb = c->scratch.cap;
     LDW_HIP(prim_sort_pairs(c->scratch.p, tb, len16, len16b, pay, pay2, n, 0, 16, c->stream));
-    hipLaunchKernelGGL(k_sr_seg_offsets, dim3((S + 2 + 255) / 256), dim3(256), 0, c->stream, len16b, n, S, c->srm_off.as<int64_t>());
+    LDW_LAUNCH(k_sr_seg_offsets, dim3((S + 2 + 255) / 256), dim3(256), 0, c->stream, len16b, n, S, c->srm_off.as<int64_t>());
     LDW_HIP(hipMemcpyAsync(c->srm_q.p, q.data(), cells * 16, hipMemcpyHostToDevice, c->stream));
     unsigned int *d_viol = reinterpret_cast<unsigned int *>(c->srm_n.as<char>() + cells * 8);   // (the 64 spare bytes behind the counts)
     if (viol_out) LDW_HIP(hipMemsetAsync(d_viol, 0, 4, c->stream));
-    hipLaunchKernelGGL(k_sr_quant, dim3(S), dim3(256), 0, c->stream, pay2, c->srm_off.as<int64_t>(), S, nclust, prob,
+    LDW_LAUNCH(k_sr_quant, dim3(S), dim3(256), 0, c->stream, pay2, c->srm_off.as<int64_t>(), S, nclust, prob,
                        c->srm_q.as<double>(), c->srm_n.as<int64_t>(), d_gtot, viol_out ? d_viol : (unsigned int *)nullptr);
-    LDW_HIP(hipGetLastError());
     LDW_HIP(hipMemcpyAsync(q.data(), c->srm_q.p, cells * 16, hipMemcpyDeviceToHost, c->stream));
     if (n_out) LDW_HIP(hipMemcpyAsync(n_out, c->srm_n.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
     if (viol_out) LDW_HIP(hipMemcpyAsync(viol_out, d_viol, 4, hipMemcpyDeviceToHost, c->stream));
@@ -1015,11 +1013,10 @@ int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, in
             fprintf(stderr, "[ldw] sr quantiles%s: reserve %.2f ms (scratch %.1f MB), stream drain %.2f, sort enqueue %.2f + wait %.2f\n", borrow ? " (memory borrowed from the pass)" : "", ms(t_0, t_1), (double)tb / 1e6,
                     ms(t_1, t_1b), ms(t_1b, t_2), ms(t_2, now()));
         }
-        hipLaunchKernelGGL(k_sr_seg_offsets, dim3((S + 2 + 255) / 256), dim3(256), 0, c->stream, len_sorted, n, S, c->srm_off.as<int64_t>());
+        LDW_LAUNCH(k_sr_seg_offsets, dim3((S + 2 + 255) / 256), dim3(256), 0, c->stream, len_sorted, n, S, c->srm_off.as<int64_t>());
         LDW_HIP(hipMemcpyAsync(c->srm_q.p, q.data(), cells * 16, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_sr_select, dim3(S), dim3(SEL_NT), 0, c->stream, pay_sorted, c->srm_off.as<int64_t>(), S, nclust, prob, c->srm_q.as<double>(),
+        LDW_LAUNCH(k_sr_select, dim3(S), dim3(SEL_NT), 0, c->stream, pay_sorted, c->srm_off.as<int64_t>(), S, nclust, prob, c->srm_q.as<double>(),
                            c->srm_n.as<int64_t>());
-        LDW_HIP(hipGetLastError());
         LDW_HIP(hipMemcpyAsync(q.data(), c->srm_q.p, cells * 16, hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipMemcpyAsync(n_out, c->srm_n.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
@@ -1031,7 +1028,7 @@ int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, in
     }
     if (int rc = quant_reserve_sorts(c, n, S, cells)) return rc;
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 65536);
-    hipLaunchKernelGGL(k_sr_tag, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(),
+    LDW_LAUNCH(k_sr_tag, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(),
                        c->sr_mi.as<double>(), n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, sr_dist, c->srm_pack.as<uint32_t>(), c->srm_key.as<uint64_t>());
     if (int rc = quant_two_sorts(c, n, S, nclust, prob, nullptr, q, n_out, nullptr)) return rc;
     for (size_t k = 0; k < cells; ++k) {
@@ -1060,10 +1057,9 @@ static int build_pool(ldw_ctx *c, unsigned long long min_key) {
         const int64_t cap = std::min<int64_t>((int64_t)(c->pool_a.cap / 4), std::min<int64_t>((int64_t)(c->pool_b.cap / 4), (int64_t)(c->pool_mi.cap / 8)));
         SrCounters h2 = {0, 0, min_key};
         LDW_HIP(hipMemcpyAsync(d, &h2, sizeof(h2), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_sr_pool<1>, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n,
+        LDW_LAUNCH(k_sr_pool<1>, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n,
                            c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist, c->srm_md.as<double>(), c->srm_S, d, c->pool_a.as<int32_t>(),
                            c->pool_b.as<int32_t>(), c->pool_mi.as<double>(), cap);
-        LDW_HIP(hipGetLastError());
         SrCounters got;
         LDW_HIP(hipMemcpyAsync(&got, d, sizeof(got), hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
@@ -1096,14 +1092,13 @@ int ldw_sr_excess_stats(ldw_ctx *c, int nclust, int32_t S, const double *mean_di
     const size_t pbytes = (size_t)grid * nclust * 5 * 8;
     if (int rc = c->srm_part.reserve(pbytes)) return rc;
     if (nclust <= 4 && getenv("LDW_SR_STATS_PEEL") == nullptr)
-        hipLaunchKernelGGL(k_sr_stats_small<4>, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n,
+        LDW_LAUNCH(k_sr_stats_small<4>, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n,
                            c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist, c->srm_md.as<double>(), S, nclust, c->srm_part.as<double>(),
                            (const int64_t *)nullptr, 0);
     else
-    hipLaunchKernelGGL(k_sr_stats, dim3(grid), dim3(256), (size_t)4 * nclust * 5 * 8, c->stream, c->sr_a.as<int32_t>(),
+        LDW_LAUNCH(k_sr_stats, dim3(grid), dim3(256), (size_t)4 * nclust * 5 * 8, c->stream, c->sr_a.as<int32_t>(),
                        c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g,
                        c->srm_sr_dist, c->srm_md.as<double>(), S, nclust, c->srm_part.as<double>(), (const int64_t *)nullptr, 0);
-    LDW_HIP(hipGetLastError());
     std::vector<double> part((size_t)grid * nclust * 5);
     LDW_HIP(hipMemcpyAsync(part.data(), c->srm_part.p, pbytes, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
@@ -1152,17 +1147,15 @@ int ldw_sr_pvalues(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, c
     double *d_dstar = nullptr;
     if (getenv("LDW_SR_PVAL_ALL") == nullptr) {
         d_dstar = c->srm_shape.as<double>() + (size_t)nclust * 3;
-        hipLaunchKernelGGL(k_sr_dstar, dim3((nclust + 63) / 64), dim3(64), 0, c->stream, c->srm_shape.as<double>(), nclust, srp_cutoff, d_dstar);
-        LDW_HIP(hipGetLastError());
+        LDW_LAUNCH(k_sr_dstar, dim3((nclust + 63) / 64), dim3(64), 0, c->stream, c->srm_shape.as<double>(), nclust, srp_cutoff, d_dstar);
     }
     for (int pass = 0; pass < 2; ++pass) {
         const int64_t cap = (int64_t)(c->red_row.cap / 8);
         LDW_HIP(hipMemcpyAsync(d, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_sr_pval<1>, dim3(grid), dim3(256), 0, c->stream, sa, sb, smi, n, POS, paint, c->g, c->srm_sr_dist,
+        LDW_LAUNCH(k_sr_pval<1>, dim3(grid), dim3(256), 0, c->stream, sa, sb, smi, n, POS, paint, c->g, c->srm_sr_dist,
                            c->srm_md.as<double>(), S, c->srm_shape.as<double>(), srp_cutoff, d, c->red_row.as<int64_t>(),
                            c->red_meta.as<uint32_t>(), c->red_srp.as<double>(),
                            std::min<int64_t>(cap, std::min<int64_t>((int64_t)(c->red_meta.cap / 4), (int64_t)(c->red_srp.cap / 8))), d_dstar);
-        LDW_HIP(hipGetLastError());
         SrCounters got;
         LDW_HIP(hipMemcpyAsync(&got, d, sizeof(got), hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
@@ -1198,9 +1191,8 @@ int ldw_sr_reduced_fetch(ldw_ctx *c, int64_t capacity, int64_t *row_out, int32_t
     if (int rc = c->scratch.reserve((size_t)n * 16)) return rc;
     double *gmi = c->scratch.as<double>();
     int32_t *ga = reinterpret_cast<int32_t *>(gmi + n), *gb = ga + n;
-    hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), n,
+    LDW_LAUNCH(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), n,
                        c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), ga, gb, gmi);
-    LDW_HIP(hipGetLastError());
     LDW_HIP(hipMemcpyAsync(a_out, ga, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(b_out, gb, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(MI_out, gmi, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1240,9 +1232,8 @@ int ldw_lr_reduced_fetch(ldw_ctx *c, int64_t capacity, int64_t *row_out, int32_t
     if (int rc = c->scratch.reserve((size_t)n * 16)) return rc;
     double *gmi = c->scratch.as<double>();
     int32_t *ga = reinterpret_cast<int32_t *>(gmi + n), *gb = ga + n;
-    hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), n,
+    LDW_LAUNCH(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), n,
                        c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>(), ga, gb, gmi);
-    LDW_HIP(hipGetLastError());
     LDW_HIP(hipMemcpyAsync(a_out, ga, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(b_out, gb, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(MI_out, gmi, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1269,25 +1260,22 @@ int ldw_aracne_device(ldw_ctx *c, int64_t capacity, uint8_t *flags_out) {
     if (int rc = c->ar_val2.reserve((size_t)n2 * 8)) return rc;
     if (int rc = c->ar_off.reserve((size_t)(n_nodes + 2) * 8)) return rc;
     if (int rc = c->ar_flags.reserve((size_t)nr)) return rc;
-    const int grid = (int)std::min<int64_t>((np + 255) / 256, 16384);
-    hipLaunchKernelGGL(k_ar_edges, dim3(grid), dim3(256), 0, c->stream, c->pool_a.as<int32_t>(), c->pool_b.as<int32_t>(),
+    LDW_LAUNCH(k_ar_edges, grid_of(np), dim3(256), 0, c->stream, c->pool_a.as<int32_t>(), c->pool_b.as<int32_t>(),
                        c->pool_mi.as<double>(), np, c->ar_key.as<uint64_t>(), c->ar_val.as<double>(), d_slot);
     size_t tb = 0;
-    LDW_HIP(prim_sort_pairs(nullptr, tb, c->ar_key.as<uint64_t>(), c->ar_key2.as<uint64_t>(), c->ar_val.as<double>(),
-                                               c->ar_val2.as<double>(), n2, 0, 64, c->stream));
+    LDW_HIP((prim_sort_pairs_bytes<uint64_t, double>((size_t)n2, 0, 64, c->stream, &tb)));
     if (int rc = c->scratch.reserve(tb)) return rc;
     tb = c->scratch.cap;
     LDW_HIP(prim_sort_pairs(c->scratch.p, tb, c->ar_key.as<uint64_t>(), c->ar_key2.as<uint64_t>(),
                                                c->ar_val.as<double>(), c->ar_val2.as<double>(), n2, 0, 64, c->stream));
-    hipLaunchKernelGGL(k_ar_offsets, dim3((unsigned)((n_nodes + 1 + 255) / 256)), dim3(256), 0, c->stream, c->ar_key2.as<uint64_t>(), n2, n_nodes,
+    LDW_LAUNCH(k_ar_offsets, dim3((unsigned)((n_nodes + 1 + 255) / 256)), dim3(256), 0, c->stream, c->ar_key2.as<uint64_t>(), n2, n_nodes,
                        c->ar_off.as<int64_t>());
     // the links to check are rows of the short-range table (after ldw_sr_pvalues) or of the long-range one (after ldw_lr_tukey)
     const int32_t *ta = (c->red_from_lr ? c->lr_a : c->sr_a).as<int32_t>(), *tb2 = (c->red_from_lr ? c->lr_b : c->sr_b).as<int32_t>();
     const double *tmi = (c->red_from_lr ? c->lr_mi : c->sr_mi).as<double>();
-    hipLaunchKernelGGL(k_ar_check, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), nr,
+    LDW_LAUNCH(k_ar_check, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), nr,
                        ta, tb2, tmi, c->ar_key2.as<uint64_t>(),
                        c->ar_val2.as<double>(), c->ar_off.as<int64_t>(), c->ar_flags.as<uint8_t>(), d_slot);
-    LDW_HIP(hipGetLastError());
     LDW_HIP(hipMemcpyAsync(flags_out, c->ar_flags.p, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     c->ar_valid = true;   // (ldw_plot_links may read the flags where they lie)
@@ -1313,9 +1301,8 @@ int ldw_sr_tail_extract(ldw_ctx *c, int nclust, int32_t S, const double *lower, 
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 16384);
     const int32_t *sa = c->sr_a.as<int32_t>(), *sb = c->sr_b.as<int32_t>();
     const double *smi = c->sr_mi.as<double>();
-    hipLaunchKernelGGL(k_sr_tail<0>, dim3(grid), dim3(256), 0, c->stream, sa, sb, smi, n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist,
+    LDW_LAUNCH(k_sr_tail<0>, dim3(grid), dim3(256), 0, c->stream, sa, sb, smi, n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist,
                        c->srd_lower.as<double>(), S, nclust, c->srd_cur.as<unsigned long long>(), (double *)nullptr);
-    LDW_HIP(hipGetLastError());
     LDW_HIP(hipMemcpyAsync(cnt_out, c->srd_cur.p, (size_t)G * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     int64_t total = 0;
@@ -1335,9 +1322,8 @@ int ldw_sr_tail_extract(ldw_ctx *c, int nclust, int32_t S, const double *lower, 
         if (int rc = c->srd_out.reserve((size_t)total * 8)) return rc;
         d_out = c->srd_out.as<double>();
     }
-    hipLaunchKernelGGL(k_sr_tail<1>, dim3(grid), dim3(256), 0, c->stream, sa, sb, smi, n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist,
+    LDW_LAUNCH(k_sr_tail<1>, dim3(grid), dim3(256), 0, c->stream, sa, sb, smi, n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist,
                        c->srd_lower.as<double>(), S, nclust, c->srd_cur.as<unsigned long long>(), d_out);
-    LDW_HIP(hipGetLastError());
     if (!on_device) LDW_HIP(hipMemcpyAsync(mi_out, d_out, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));   // (`first` is read by the copy above)
     return LDW_OK;
@@ -1390,9 +1376,8 @@ int ldw_sr_quantiles_merge(ldw_ctx *c, int nclust, int32_t S, double prob, int n
                 LDW_HIP(hipMemcpyAsync(c->srd_out.as<double>() + base, mi_src[r], (size_t)mr * 8, hipMemcpyHostToDevice, c->stream));
                 d_mi = c->srd_out.as<double>() + base;
             }
-            hipLaunchKernelGGL(k_tail_unpack, dim3((unsigned)std::min<int64_t>((mr + 255) / 256, 16384)), dim3(256), 0, c->stream, d_mi, mr, d_go, (int)G, nclust,
+            LDW_LAUNCH(k_tail_unpack, dim3((unsigned)std::min<int64_t>((mr + 255) / 256, 16384)), dim3(256), 0, c->stream, d_mi, mr, d_go, (int)G, nclust,
                                base, c->srm_pack.as<uint32_t>(), c->srm_key.as<uint64_t>());
-            LDW_HIP(hipGetLastError());
             base += mr;
         }
         if (int rc = quant_two_sorts(c, m, S, nclust, prob, c->srd_lower.as<int64_t>(), q, nullptr, &viol)) return rc;   // (synchronises: goff may go)
@@ -1437,14 +1422,13 @@ int ldw_sr_excess_stats_blocks(ldw_ctx *c, int nclust, int32_t S, const double *
     LDW_HIP(hipMemcpyAsync(c->srd_seg.p, seg.data(), seg.size() * 8, hipMemcpyHostToDevice, c->stream));
     const int64_t n = c->n_sr;
     if (nclust <= 4 && getenv("LDW_SR_STATS_PEEL") == nullptr)
-        hipLaunchKernelGGL(k_sr_stats_small<4>, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n,
+        LDW_LAUNCH(k_sr_stats_small<4>, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n,
                            c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist, c->srm_md.as<double>(), S, nclust, c->srm_part.as<double>(),
                            c->srd_seg.as<int64_t>(), STRIPS);
     else
-        hipLaunchKernelGGL(k_sr_stats, dim3(grid), dim3(256), (size_t)4 * nclust * 5 * 8, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(),
+        LDW_LAUNCH(k_sr_stats, dim3(grid), dim3(256), (size_t)4 * nclust * 5 * 8, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(),
                            c->sr_mi.as<double>(), n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist, c->srm_md.as<double>(), S, nclust,
                            c->srm_part.as<double>(), c->srd_seg.as<int64_t>(), STRIPS);
-    LDW_HIP(hipGetLastError());
     std::vector<double> part((size_t)grid * per);
     LDW_HIP(hipMemcpyAsync(part.data(), c->srm_part.p, pbytes, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
@@ -1500,8 +1484,7 @@ int reduced_import_full(ldw_ctx *c, int64_t n_red, const int32_t *a, const int32
     if (srp && n_red > 0) LDW_HIP(hipMemcpyAsync(c->red_srp.p, srp, (size_t)n_red * 8, hipMemcpyHostToDevice, c->stream));
     else LDW_HIP(hipMemsetAsync(c->red_srp.p, 0, nr * 8, c->stream));
     if (n_red > 0) {
-        hipLaunchKernelGGL(k_iota64, dim3((unsigned)((n_red + 255) / 256)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), n_red);
-        LDW_HIP(hipGetLastError());
+        LDW_LAUNCH(k_iota64, dim3((unsigned)((n_red + 255) / 256)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), n_red);
     }
     if (n_pool > 0) {
         LDW_HIP(hipMemcpyAsync(c->pool_a.p, pool_a, (size_t)n_pool * 4, hipMemcpyHostToDevice, c->stream));

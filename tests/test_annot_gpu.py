@@ -307,6 +307,28 @@ def test_single_snp_and_gff_route(eng, tmp_path):
                                            "C:0.75, T:0.25\tC:0.75, T:0.25"
 
 
+# ---- ldw_annot_map with the positions in any order ------------------------------------------------------------------------------------------------
+
+def test_annot_map_with_positions_in_any_order(eng):
+    POS = np.array([40, 10, 30, 70, 50, 20], dtype=np.int32)
+    pos1, pos2 = np.array([10.0, 70.0, 10.0]), np.array([40.0, 20.0, 70.0])
+    ends = np.unique(np.r_[pos1, pos2])                                     # the annotation rows: the distinct link positions, ascending
+    order = np.argsort(POS, kind="stable")
+    want = order[np.searchsorted(POS[order], ends)]
+    snp, bad = eng.annot_map(pos1, pos2, POS)
+    assert len(ends) == 4 and snp.tolist() == want.tolist() == [1, 5, 0, 3] and bad == -1
+    # a position two SNPs hold is nobody's: the first such end, e < n in pos1 and n + i in pos2
+    TWICE = np.array([40, 10, 30, 10], dtype=np.int32)
+    assert eng.annot_map([40.0, 30.0], [30.0, 10.0], TWICE)[1] == 2 + 1
+    assert eng.annot_map([40.0, 10.0], [30.0, 10.0], TWICE)[1] == 1
+    # a fractional end lies between two positions: compared as a double, never rounded onto a SNP
+    assert eng.annot_map([10.5], [40.0], POS)[1] == 0
+    assert eng.annot_map([40.0], [10.5], POS)[1] == 1
+    # one SNP, linked to itself
+    snp, bad = eng.annot_map([5.0], [5.0], np.array([5], dtype=np.int32))
+    assert snp.tolist() == [0] and bad == -1
+
+
 # ---- 10^6 links ---------------------------------------------------------------------------------------------------------------------------
 
 def test_million_links_sha256(eng, tmp_path):

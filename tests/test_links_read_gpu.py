@@ -219,6 +219,65 @@ def test_links_load_refusals(engine, tmp_path):
     assert a.tolist() == [1, 0] and b.tolist() == [0, 3]
 
 
+# ---- positions in any order: the ascending order ldw_links_load searches, shared with the position-based consumers ----------------------------------------
+
+POS_ANY = np.array([40, 10, 30, 10, 70, 50, 20], dtype=np.int32)        # unsorted, one position held twice
+POS_TIED = np.array([10, 10, 20, 30, 40, 50, 70], dtype=np.int32)       # ascending but not strictly: the path without an order array
+POS_OTHER = np.array([20, 70, 10, 50, 10, 30, 40], dtype=np.int32)      # the same positions, another permutation
+ANY_P1, ANY_P2, ANY_MI = [10, 70, 20, 40], [70, 20, 40, 10], [0.125, 0.25, 0.5, 0.75]
+
+
+def _first_snp(POS, q):
+    """The first SNP (lowest index) at every position of q, from plain numpy."""
+    order = np.argsort(POS, kind="stable")
+    at = np.searchsorted(POS[order], q, side="left")
+    assert (POS[order][at] == q).all()
+    return order[at]
+
+
+def _any_table(path, extra=""):
+    path.write_text("".join(f"{p1}\t{p2}\t{mi}\n" for p1, p2, mi in zip(ANY_P1, ANY_P2, ANY_MI)) + extra)
+    return path
+
+
+def _load_any(eng, path):
+    assert eng.tsv_read(path, "\t", 3)[0] == 4
+    assert eng.links_load(1, 0, 1, 2) == 4
+    return eng.links(1)
+
+
+@pytest.mark.parametrize("POS", [POS_ANY, POS_TIED], ids=["unsorted", "ascending_with_a_tie"])
+def test_links_load_with_positions_in_any_order(tmp_path, POS):
+    with E.Engine(0) as eng:
+        eng.set_positions(POS, 1000.0)
+        a, b, mi = _load_any(eng, _any_table(tmp_path / "any.tsv"))
+        # pos2 is the from side (a), pos1 the to side (b); a position held twice is its first SNP
+        assert a.tolist() == _first_snp(POS, ANY_P2).tolist() and b.tolist() == _first_snp(POS, ANY_P1).tolist() and mi.tolist() == ANY_MI
+        assert b[0] == (1 if POS is POS_ANY else 0) and POS[b[0]] == 10
+        bad = _any_table(tmp_path / "bad.tsv", "15\t10\t0.5\n")
+        assert eng.tsv_read(bad, "\t", 3)[0] == 5
+        with pytest.raises(L.LdwError) as e:
+            eng.links_load(1, 0, 1, 2)
+        assert e.value.code == L.LDW_ERR_ARG and "line 5, column 1: the position 15 is no SNP's" in str(e.value), str(e.value)
+
+
+def test_the_position_order_survives_reuse_and_follows_new_positions(tmp_path):
+    path = _any_table(tmp_path / "any.tsv")
+    with E.Engine(0) as eng:
+        eng.set_positions(POS_ANY, 1000.0)
+        first = _load_any(eng, path)
+        assert eng.ldmap(2)[1] == len(np.unique(np.r_[ANY_P1, ANY_P2]))      # (through ldw::pos_slots: four distinct positions hold links)
+        again = _load_any(eng, path)
+        for x, y in zip(first, again):
+            assert np.array_equal(x, y)
+        assert first[0].tolist() == _first_snp(POS_ANY, ANY_P2).tolist() and first[1].tolist() == _first_snp(POS_ANY, ANY_P1).tolist()
+        eng.set_positions(POS_OTHER, 1000.0)
+        a, b, _ = _load_any(eng, path)
+        assert a.tolist() == _first_snp(POS_OTHER, ANY_P2).tolist() and b.tolist() == _first_snp(POS_OTHER, ANY_P1).tolist()
+        assert a.tolist() != first[0].tolist() and b.tolist() != first[1].tolist()
+        assert eng.ldmap(2)[1] == 4
+
+
 # ---- row order ------------------------------------------------------------------------------------------------------------------------------------
 
 def test_ordered_figures_equal_the_frame_route(engine, tmp_path):
