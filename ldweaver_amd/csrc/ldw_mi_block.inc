@@ -184,6 +184,7 @@ bool same_list(const int32_t *a, int64_t na, const int32_t *b, int64_t nb) {
 // device pointers of one block's index structures
 struct DevPtrs {
     const int32_t *idx_f, *idx_t, *rl_f, *rl_t, *lrow_f, *lrow_t, *perm, *perm_t, *pos_f, *pos_t;
+    const ColInfo *cols;        // short-range intervals of every to-side SNP (build_cols)
     const uint8_t *cls_f, *cls_t;
     const int32_t *cmax_f;      // mixed-precision path: per from-tile widest row-slot class, offsets of the low-limb blocks
     const int64_t *tile_base;
@@ -896,9 +897,17 @@ int run_block_mi(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t 
     if (int rc = upload_i32(c, c->perm_f, perm)) return rc;
     if (int rc = c->hist[0].reserve((size_t)NBINS * 8)) return rc;
     LDW_HIP(hipStreamSynchronize(c->stream));  // pageable H2D copies are complete only after a sync
-    DevPtrs D{c->idx_f.as<int32_t>(), c->idx_t.as<int32_t>(), c->rowlist_f.as<int32_t>(), c->rowlist_t.as<int32_t>(),
-              c->lrow_f.as<int32_t>(), c->lrow_t.as<int32_t>(), c->perm_f.as<int32_t>(), c->perm_t.as<int32_t>(), nullptr, nullptr,
-              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, (int)(perm.size() / 64), 0x7FFFFFFF, 0x7FFFFFFF};
+    DevPtrs D{};   // (no intervals, row positions, classes, low-limb geometry or band: the dense path reads none of them)
+    D.idx_f = c->idx_f.as<int32_t>();
+    D.idx_t = c->idx_t.as<int32_t>();
+    D.rl_f = c->rowlist_f.as<int32_t>();
+    D.rl_t = c->rowlist_t.as<int32_t>();
+    D.lrow_f = c->lrow_f.as<int32_t>();
+    D.lrow_t = c->lrow_t.as<int32_t>();
+    D.perm = c->perm_f.as<int32_t>();
+    D.perm_t = c->perm_t.as<int32_t>();
+    D.nf_tiles = (int)(perm.size() / 64);
+    D.gen_t0 = D.gen_q0 = 0x7FFFFFFF;
     E.write_dense = 1;
     E.spec_B = -1;
     // a symmetric block (same list on both sides) may be asked for in full: the GEMM then computes every tile

@@ -5,23 +5,50 @@
 // ----   submit_a upload, then the GEMM on the GEMM stream
 // ----   submit_b epilogue + bucket pick + copy-back on the main stream
 // ----   finish   the one host round trip (candidate count), then sorts / threshold / append on the main stream
+
+// The staging image of a block: the index structures of both sides, one behind the other (64-byte aligned: the kernels read them with wide loads) in
+// the item's pinned buffer, sent to the device as one copy.  array<&DevPtrs::x>(src, count) names an array ONCE — its element type is that of the
+// DevPtrs field, src its host source (null: built in place), count its elements — and from that statement come its offset (returned), its copy into
+// the pinned buffer (copy_to) and its typed device pointer (bind, once the device base is known; an array that is not named keeps its null).
+// The parts live in the HostBlock and nothing is allocated; src is good until prep_block returns.
+struct StageImage {
+    struct Part {
+        size_t off, bytes;
+        const void *src;
+        void (*point)(DevPtrs &, const char *);
+    };
+    Part part[18] = {};   // (the array<> statements of prep_block)
+    int n = 0;
+    size_t bytes = 0;     // of the whole image
+    template <class T> static T elem_of(const T *DevPtrs::*);
+    template <auto F> using Elem = decltype(elem_of(F));
+    template <auto F> size_t array(const Elem<F> *src, size_t count) {
+        part[n] = Part{bytes, count * sizeof(Elem<F>), src, [](DevPtrs &D, const char *p) { D.*F = reinterpret_cast<const Elem<F> *>(p); }};
+        bytes = (bytes + part[n].bytes + 63) / 64 * 64;
+        return part[n++].off;
+    }
+    void copy_to(char *image) const {
+        for (int k = 0; k < n; ++k)
+            if (part[k].src && part[k].bytes) memcpy(image + part[k].off, part[k].src, part[k].bytes);
+    }
+    void bind(DevPtrs &D, const char *image) const {
+        for (int k = 0; k < n; ++k) part[k].point(D, image + part[k].off);
+    }
+};
+
 struct HostBlock {
     int64_t nf = 0, nt = 0, n_sr_blk = 0, n_lr_total = 0, blk_no = 0;
     int RFpad = 0, RTpad = 0, slot = 0;
     bool diag = false, submitted = false;
     bool uploaded = false;     // submit_upload has queued the upload of its lists (submit_a then skips it)
-    int nf_tiles = 0;          // tiles of 64 in the padded from-side order
-    int gen_t0 = 0, gen_q0 = 0;
     bool mixed = false;        // high-limb GEMM + gathered low limbs (decided with the bucket guess at submit_a)
     bool apx = false;          // approximate GEMM + exact popcount sums of the listed units (ldw_apx.h); implies the lo geometry
     bool generic = false;      // a SNP list of the block is not ascending in POS: plain path + the k_gen_* pair list
     int guess = -1;            // bucket guess the block was submitted with
     LoHost lo;
-    size_t o_cmax = 0, o_tbase = 0, o_tf = 0, o_band = 0, o_bandl = 0;
-    int n_band = -1;           // tiles of the band list (r06; -1: no list, the mask alone)
-    size_t o_idx_f = 0, o_idx_t = 0, o_rl_f = 0, o_rl_t = 0, o_lrow_f = 0, o_lrow_t = 0, o_perm = 0, o_perm_t = 0, o_cols = 0, o_pos_f = 0,
-           o_pos_t = 0, o_cls_f = 0, o_cls_t = 0, total = 0;
-    DevPtrs D{};
+    StageImage img;            // where each array sits in the staging image, and the image's bytes
+    size_t total = 0;
+    DevPtrs D{};               // prep_block sets the counts, fill_dev_ptrs the pointers
     EmitArgs E{};
     int spec_B = -1;
     // r04 span (ldw_epi.h): the to side is the concatenation of `span` reference blocks (0: an ordinary block)
@@ -55,30 +82,40 @@ static inline bool speculation_pays(const ldw_ctx *c, const ldw_mi_params *p) {
     return !(p->lr_links_approx > 0.0) || p->lr_retain_links < 0.007 * p->lr_links_approx;
 }
 
-int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *to_idx, int64_t nt, const ldw_mi_params *p,
-               int slot, int64_t blk_no, HostBlock &hb, const SpanPlan *sp = nullptr, int pin_slot = -1, size_t stage_base = 0) {
-    LDW_REQUIRE(nf > 0 && nt > 0, LDW_ERR_ARG, "empty block (nf=%lld nt=%lld)", (long long)nf, (long long)nt);
-    LDW_REQUIRE(nf <= 1000000 && nt <= 1000000 && nf * nt < 2147483647LL, LDW_ERR_ARG, "block too large (%lld x %lld)",
-                (long long)nf, (long long)nt);
-    for (int64_t k = 0; k < nf; ++k)
-        LDW_REQUIRE(from_idx[k] >= 0 && from_idx[k] < c->L, LDW_ERR_ARG, "SNP index %d out of range", from_idx[k]);
-    for (int64_t k = 0; k < nt; ++k)
-        LDW_REQUIRE(to_idx[k] >= 0 && to_idx[k] < c->L, LDW_ERR_ARG, "SNP index %d out of range", to_idx[k]);
-    static const bool prep_timing = getenv("LDW_HOST_TIMING") != nullptr;
-    auto pnow = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tp[8] = {pnow(), 0, 0, 0, 0, 0, 0, 0};
-    hb = HostBlock();
-    hb.nf = nf;
-    hb.nt = nt;
-    hb.slot = slot;
-    hb.blk_no = blk_no;
-    hb.pin_slot = pin_slot;
-    hb.stage_base = stage_base;
-    hb.diag = same_list(from_idx, nf, to_idx, nt);
-    SideLists SF, ST;
+// One call of prep_block: its lists, and what its stages hand to each other.  A diagonal block's intervals are built by a thread of their own
+// (intervals) that writes cols, cols_err and hb.n_sr_blk: join_cols waits for it in front of their first reader, and the destructor before any
+// of them goes away, by whichever return prep_block is left.
+struct PrepWork {
+    ldw_ctx *c;
+    const int32_t *from_idx, *to_idx;
+    int64_t nf, nt;
+    HostBlock &hb;
     std::vector<ColInfo> cols;
     std::string cols_err;
-    std::future<int> cols_job;   // (declared behind what it writes: an early return waits for it before those go away)
+    std::future<int> cols_job;
+    const std::vector<int32_t> *ord_f = nullptr, *ord_t = nullptr;        // row order of the one-row SNPs of either side (null: list order)
+    std::vector<int32_t> ord_f_own, ord_t_own, ord_f_full, ord_t_full;    // what they point to, unless it is minor_weight_order's cache
+    SideLists SF, ST;
+    std::vector<int32_t> pf, cmax, tf;   // from-side tiles; widest row-slot class per from-tile; (tile, fs) pairs of the gathered GEMM's grid
+    std::vector<int64_t> tbase;          // low-limb block offset per from-tile
+    std::vector<uint8_t> band;
+    std::vector<uint32_t> bandl;
+    // the stages, in the words of the [ldw prep us] line
+    int intervals(const ldw_mi_params *p, const SpanPlan *sp);   // hb.generic, cols, hb.n_sr_blk; a span: hb.span / seg_*
+    int row_order(const SpanPlan *sp);                           // ord_f / ord_t
+    void tiles(int slot);                                        // pf, the counts of hb.D, the low-limb geometry hb.lo, cmax / tbase / tf
+    void band_mask();                                            // band, hb.lo.band_full / fuse_ok / ordered (BOUNDS.md)
+    bool band_list();                                            // bandl, hb.D.n_band; false: no list, the mask alone
+    int join_cols() {
+        const int rc = cols_job.valid() ? cols_job.get() : LDW_OK;
+        if (rc != LDW_OK) set_error("%s", cols_err.c_str());
+        return rc;
+    }
+    ~PrepWork() { if (cols_job.valid()) cols_job.wait(); }
+};
+
+int PrepWork::intervals(const ldw_mi_params *p, const SpanPlan *sp) {
+    const int64_t blk_no = hb.blk_no;
     auto ascending = [&](const int32_t *idx, int64_t n) {
         for (int64_t k = 1; k < n; ++k)
             if (c->h_POS[idx[k]] < c->h_POS[idx[k - 1]]) return false;
@@ -105,8 +142,9 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
         // its tiles depend on the intervals (no row ordering on the diagonal): the intervals are built on a thread of their own beside them
         // and joined in front of the band, their first reader (0.36 of 1.1 ms at 10k x 10k).
         cols.resize((size_t)nt);
-        cols_job = std::async(std::launch::async, [&]() -> int {
-            const int rc = build_cols(c, from_idx, nf, to_idx, nt, true, p->sr_dist, cols, hb.n_sr_blk);
+        const double sr_dist = p->sr_dist;
+        cols_job = std::async(std::launch::async, [this, sr_dist]() -> int {
+            const int rc = build_cols(c, from_idx, nf, to_idx, nt, true, sr_dist, cols, hb.n_sr_blk);
             if (rc != LDW_OK) cols_err = ldw_last_error();
             return rc;
         });
@@ -125,17 +163,18 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
             }
         }
     }
-    tp[1] = pnow();
-    // Blocks without a short-range pair (most off-diagonal ones): nothing depends on the order of the rows within a class, so the
-    // one-row SNPs are ordered by the weight of their minor state on both sides — rows and epilogue slots alike, which the table
-    // test of the GEMM's epilogue requires anyway.  The wave tiles of the approximate GEMM then span few bins of the threshold
-    // table and the tiles of the rare x rare corner are pruned whole (apx_tile_prunable).
-    // An off-diagonal block WITH a short-range corner (neighbouring blocks, and the pair that closes the circle): the SNPs that have a
-    // short-range partner in the block are a few hundred at the facing ends of the two lists.  They keep the list order — the band
-    // of tiles the exact GEMM covers needs their partners contiguous — behind the ordered rest.  Diagonal blocks stay as they are:
-    // every SNP has short-range partners there.
-    const std::vector<int32_t> *ord_f = nullptr, *ord_t = nullptr;
-    std::vector<int32_t> ord_f_own, ord_t_own, ord_f_full, ord_t_full;
+    return LDW_OK;
+}
+
+// Blocks without a short-range pair (most off-diagonal ones): nothing depends on the order of the rows within a class, so the
+// one-row SNPs are ordered by the weight of their minor state on both sides — rows and epilogue slots alike, which the table
+// test of the GEMM's epilogue requires anyway.  The wave tiles of the approximate GEMM then span few bins of the threshold
+// table and the tiles of the rare x rare corner are pruned whole (apx_tile_prunable).
+// An off-diagonal block WITH a short-range corner (neighbouring blocks, and the pair that closes the circle): the SNPs that have a
+// short-range partner in the block are a few hundred at the facing ends of the two lists.  They keep the list order — the band
+// of tiles the exact GEMM covers needs their partners contiguous — behind the ordered rest.  Diagonal blocks stay as they are:
+// every SNP has short-range partners there.
+int PrepWork::row_order(const SpanPlan *sp) {
     if (c->prune && !hb.generic && !hb.diag && c->engine == LDW_ENGINE_MFMA && c->apx_ok) {
         bool rowless = false;
         for (int64_t k = 0; k < nf && !rowless; ++k) rowless = c->h_row0[from_idx[k] + 1] == c->h_row0[from_idx[k]];
@@ -176,24 +215,13 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
             c->sorted_blocks += sp ? sp->nseg : 1;
         }
     }
-    LDW_REQUIRE(!sp || (ord_f && ord_t), LDW_ERR_STATE, "span at block %lld cannot be ordered", (long long)blk_no);
-    tp[2] = pnow();
-    if (int rc = build_side(c, from_idx, nf, SF, ord_f)) return rc;
-    if (int rc = build_side(c, to_idx, nt, ST, ord_t)) return rc;
-    tp[3] = pnow();
-    hb.RFpad = SF.Rpad;
-    hb.RTpad = ST.Rpad;
-    auto al = [](size_t x) { return (x + 63) / 64 * 64; };
-    size_t o = 0;
-    hb.o_idx_f = o; o = al(o + (size_t)nf * 4);
-    hb.o_idx_t = o; o = al(o + (size_t)nt * 4);
-    hb.o_rl_f = o; o = al(o + SF.rowlist.size() * 4);
-    hb.o_rl_t = o; o = al(o + ST.rowlist.size() * 4);
-    hb.o_lrow_f = o; o = al(o + (size_t)nf * 4);
-    hb.o_lrow_t = o; o = al(o + (size_t)nt * 4);
-    std::vector<int32_t> pf;
+    LDW_REQUIRE(!sp || (ord_f && ord_t), LDW_ERR_STATE, "span at block %lld cannot be ordered", (long long)hb.blk_no);
+    return LDW_OK;
+}
+
+void PrepWork::tiles(int slot) {
     build_perm_tiles(c, from_idx, nf, pf, ord_f);
-    hb.nf_tiles = (int)(pf.size() / 64);
+    hb.D.nf_tiles = (int)(pf.size() / 64);
     {   // where the SNPs with 1 or 2 indicator rows end in either order
         int64_t n12f = 0, n1 = 0, n2 = 0;
         for (int64_t k = 0; k < nf; ++k) {
@@ -202,24 +230,17 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
             n2 += nr == 2;
         }
         n12f = (n1 + 63) / 64 + (n2 + 63) / 64;   // build_perm_tiles pads each of the two classes to whole tiles
-        hb.gen_t0 = (int)n12f;
+        hb.D.gen_t0 = (int)n12f;
         int64_t q12 = 0;
         for (int64_t k = 0; k < nt; ++k) {
             const int nr = c->h_row0[to_idx[k] + 1] - c->h_row0[to_idx[k]];
             q12 += nr == 1 || nr == 2;
         }
-        hb.gen_q0 = (int)q12;
+        hb.D.gen_q0 = (int)q12;
     }
-    hb.o_perm = o; o = al(o + pf.size() * 4);
-    hb.o_perm_t = o; o = al(o + (size_t)nt * 4);
-    hb.o_cols = o; o = al(o + (size_t)nt * sizeof(ColInfo));   // (one entry per to-side SNP; a diagonal block's are still being built)
-    hb.o_pos_f = o; o = al(o + SF.pos.size() * 4);
-    hb.o_pos_t = o; o = al(o + ST.pos.size() * 4);
-    hb.o_cls_f = o; o = al(o + SF.cls.size());
-    hb.o_cls_t = o; o = al(o + ST.cls.size());
     // mixed-precision path: row-slot classes of the to side, widest class per from-tile, low-limb block offsets
-    std::vector<int32_t> cmax((size_t)hb.nf_tiles, 1);
-    std::vector<int64_t> tbase(cmax.size(), 0);
+    cmax.assign((size_t)hb.D.nf_tiles, 1);
+    tbase.assign(cmax.size(), 0);
     {
         LoHost &lo = hb.lo;
         lo = LoHost();
@@ -249,7 +270,6 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
         lo.diag = hb.diag ? 1 : 0;
         lo.glo_total = tb;
     }
-    std::vector<int32_t> tf;
     // last tiles first: the tile of the SNPs with >= 3 minor states (generic code, every unit listed, cmax 4) is the
     // critical path of the gathered GEMM and must not start last
     for (size_t t = cmax.size(); t-- > 0;)
@@ -258,17 +278,13 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
             tf.push_back(fs);
         }
     hb.lo.n_tf = (int32_t)(tf.size() / 2);
-    // approximate path: tiles of the exact GEMM (128 to-side x 64 from-side rows) that hold a short-range pair.  POS ascends along
-    // both lists and the row lists keep the list order within a slot-count class, so the partners of a to-side SNP are a
-    // contiguous row range per class
-    if (cols_job.valid())
-        if (int rc = cols_job.get()) {
-            set_error("%s", cols_err.c_str());
-            return rc;
-        }
-    hb.n_lr_total = (hb.diag ? nf * (nf - 1) / 2 : nf * nt - std::min(nf, nt)) - hb.n_sr_blk;
-    tp[4] = pnow();
-    std::vector<uint8_t> band((size_t)(hb.RTpad / TILE) * (hb.RFpad / 64), 0);
+}
+
+// approximate path: tiles of the exact GEMM (128 to-side x 64 from-side rows) that hold a short-range pair.  POS ascends along
+// both lists and the row lists keep the list order within a slot-count class, so the partners of a to-side SNP are a
+// contiguous row range per class
+void PrepWork::band_mask() {
+    band.assign((size_t)(hb.RTpad / TILE) * (hb.RFpad / 64), 0);
     bool no_rowless = true;   // no SNP without an indicator row: a one-row SNP's row-list position is its slot (ApxGemmArgs::fuse)
     {
         const int ntx = hb.RFpad / 64;
@@ -341,57 +357,97 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
                 }
             }
     }
-    tp[5] = pnow();
     hb.lo.fuse_ok = no_rowless ? 1 : 0;
     hb.lo.ordered = ord_f != nullptr ? 1 : 0;
-    hb.o_cmax = o; o = al(o + cmax.size() * 4);
-    hb.o_tbase = o; o = al(o + tbase.size() * 8);
-    hb.o_tf = o; o = al(o + tf.size() * 4);
-    hb.o_band = o; o = al(o + band.size());
-    // r06: the band's tiles as a LIST for the exact GEMM's launch (gemm_bits_kernel: a 1-D grid of the live tiles instead of the whole grid behind a mask);
-    // tiles above the diagonal of a diagonal block are left out as the kernel leaves them out; a band that covers most of the grid keeps the mask alone
-    std::vector<uint32_t> bandl;
-    hb.n_band = -1;
+}
+
+// r06: the band's tiles as a LIST for the exact GEMM's launch (gemm_bits_kernel: a 1-D grid of the live tiles instead of the whole grid behind a mask);
+// tiles above the diagonal of a diagonal block are left out as the kernel leaves them out; a band that covers most of the grid keeps the mask alone
+bool PrepWork::band_list() {
+    bool listed = false;
     const int64_t ntx = hb.RFpad / 64;
     if (hb.n_sr_blk > 0 && !hb.lo.band_full && hb.RTpad / TILE < 65536 && ntx < 65536) {
         const int64_t nty = hb.RTpad / TILE;
         for (int64_t ty = 0; ty < nty; ++ty)
             for (int64_t tx = 0; tx < ntx; ++tx)
                 if (band[(size_t)ty * ntx + tx] && !(hb.diag && tx * 64 + 63 < ty * TILE)) bandl.push_back((uint32_t)(ty << 16 | tx));
-        if (bandl.size() * 2 <= band.size()) hb.n_band = (int)bandl.size();
-        else bandl.clear();
+        listed = bandl.size() * 2 <= band.size();
+        if (!listed) bandl.clear();
     }
-    hb.o_bandl = o; o = al(o + bandl.size() * 4);
-    hb.total = o;
+    hb.D.n_band = (int)bandl.size();
+    return listed;
+}
+
+int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *to_idx, int64_t nt, const ldw_mi_params *p,
+               int slot, int64_t blk_no, HostBlock &hb, const SpanPlan *sp = nullptr, int pin_slot = -1, size_t stage_base = 0) {
+    LDW_REQUIRE(nf > 0 && nt > 0, LDW_ERR_ARG, "empty block (nf=%lld nt=%lld)", (long long)nf, (long long)nt);
+    LDW_REQUIRE(nf <= 1000000 && nt <= 1000000 && nf * nt < 2147483647LL, LDW_ERR_ARG, "block too large (%lld x %lld)",
+                (long long)nf, (long long)nt);
+    for (int64_t k = 0; k < nf; ++k)
+        LDW_REQUIRE(from_idx[k] >= 0 && from_idx[k] < c->L, LDW_ERR_ARG, "SNP index %d out of range", from_idx[k]);
+    for (int64_t k = 0; k < nt; ++k)
+        LDW_REQUIRE(to_idx[k] >= 0 && to_idx[k] < c->L, LDW_ERR_ARG, "SNP index %d out of range", to_idx[k]);
+    static const bool prep_timing = getenv("LDW_HOST_TIMING") != nullptr;
+    auto pnow = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double tp[8] = {pnow(), 0, 0, 0, 0, 0, 0, 0};
+    hb = HostBlock();
+    hb.nf = nf;
+    hb.nt = nt;
+    hb.slot = slot;
+    hb.blk_no = blk_no;
+    hb.pin_slot = pin_slot;
+    hb.stage_base = stage_base;
+    hb.diag = same_list(from_idx, nf, to_idx, nt);
+    PrepWork W{c, from_idx, to_idx, nf, nt, hb};
+    if (int rc = W.intervals(p, sp)) return rc;
+    tp[1] = pnow();
+    if (int rc = W.row_order(sp)) return rc;
+    tp[2] = pnow();
+    if (int rc = build_side(c, from_idx, nf, W.SF, W.ord_f)) return rc;
+    if (int rc = build_side(c, to_idx, nt, W.ST, W.ord_t)) return rc;
+    tp[3] = pnow();
+    hb.RFpad = W.SF.Rpad;
+    hb.RTpad = W.ST.Rpad;
+    W.tiles(slot);
+    if (int rc = W.join_cols()) return rc;   // (a diagonal block's intervals: n_lr_total and the band are their first readers)
+    hb.n_lr_total = (hb.diag ? nf * (nf - 1) / 2 : nf * nt - std::min(nf, nt)) - hb.n_sr_blk;
+    tp[4] = pnow();
+    W.band_mask();
+    tp[5] = pnow();
+    const bool band_listed = W.band_list();
+    StageImage &im = hb.img;
+    im.array<&DevPtrs::idx_f>(from_idx, (size_t)nf);
+    im.array<&DevPtrs::idx_t>(to_idx, (size_t)nt);
+    im.array<&DevPtrs::rl_f>(W.SF.rowlist.data(), W.SF.rowlist.size());
+    im.array<&DevPtrs::rl_t>(W.ST.rowlist.data(), W.ST.rowlist.size());
+    im.array<&DevPtrs::lrow_f>(W.SF.lrow.data(), (size_t)nf);
+    im.array<&DevPtrs::lrow_t>(W.ST.lrow.data(), (size_t)nt);
+    im.array<&DevPtrs::perm>(W.pf.data(), W.pf.size());
+    const size_t at_perm_t = im.array<&DevPtrs::perm_t>(nullptr, (size_t)nt);   // (build_perm writes it straight into the pinned buffer)
+    im.array<&DevPtrs::cols>(W.cols.data(), W.cols.size());
+    im.array<&DevPtrs::pos_f>(W.SF.pos.data(), W.SF.pos.size());
+    im.array<&DevPtrs::pos_t>(W.ST.pos.data(), W.ST.pos.size());
+    im.array<&DevPtrs::cls_f>(W.SF.cls.data(), W.SF.cls.size());
+    im.array<&DevPtrs::cls_t>(W.ST.cls.data(), W.ST.cls.size());
+    im.array<&DevPtrs::cmax_f>(W.cmax.data(), W.cmax.size());
+    im.array<&DevPtrs::tile_base>(W.tbase.data(), W.tbase.size());
+    im.array<&DevPtrs::tf_list>(W.tf.data(), W.tf.size());
+    im.array<&DevPtrs::band_mask>(W.band.data(), W.band.size());
+    if (band_listed) im.array<&DevPtrs::band_list>(W.bandl.data(), W.bandl.size());
+    hb.total = im.bytes;
     const int ps = pin_slot >= 0 ? pin_slot : slot;
-    if (c->pin_cap[ps] < stage_base + o) {
+    if (c->pin_cap[ps] < stage_base + hb.total) {
         void *np = nullptr;
-        LDW_HIP(hipHostMalloc(&np, (stage_base + o) * 2, hipHostMallocDefault));
+        LDW_HIP(hipHostMalloc(&np, (stage_base + hb.total) * 2, hipHostMallocDefault));
         if (c->pin[ps] && stage_base) memcpy(np, c->pin[ps], stage_base);   // (the images in front of it: the first cold-start probe's)
         if (c->pin[ps]) LDW_HIP(hipHostFree(c->pin[ps]));
         c->pin[ps] = np;
-        c->pin_cap[ps] = (stage_base + o) * 2;
+        c->pin_cap[ps] = (stage_base + hb.total) * 2;
     }
     tp[6] = pnow();
     char *b = static_cast<char *>(c->pin[ps]) + stage_base;
-    memcpy(b + hb.o_idx_f, from_idx, (size_t)nf * 4);
-    memcpy(b + hb.o_idx_t, to_idx, (size_t)nt * 4);
-    memcpy(b + hb.o_rl_f, SF.rowlist.data(), SF.rowlist.size() * 4);
-    memcpy(b + hb.o_rl_t, ST.rowlist.data(), ST.rowlist.size() * 4);
-    memcpy(b + hb.o_lrow_f, SF.lrow.data(), (size_t)nf * 4);
-    memcpy(b + hb.o_lrow_t, ST.lrow.data(), (size_t)nt * 4);
-    memcpy(b + hb.o_perm, pf.data(), pf.size() * 4);
-    build_perm(c, to_idx, nt, reinterpret_cast<int32_t *>(b + hb.o_perm_t), ord_t);
-    memcpy(b + hb.o_cols, cols.data(), cols.size() * sizeof(ColInfo));
-    memcpy(b + hb.o_pos_f, SF.pos.data(), SF.pos.size() * 4);
-    memcpy(b + hb.o_pos_t, ST.pos.data(), ST.pos.size() * 4);
-    memcpy(b + hb.o_cls_f, SF.cls.data(), SF.cls.size());
-    memcpy(b + hb.o_cls_t, ST.cls.data(), ST.cls.size());
-    memcpy(b + hb.o_cmax, cmax.data(), cmax.size() * 4);
-    memcpy(b + hb.o_tbase, tbase.data(), tbase.size() * 8);
-    memcpy(b + hb.o_tf, tf.data(), tf.size() * 4);
-    memcpy(b + hb.o_band, band.data(), band.size());
-    if (!bandl.empty()) memcpy(b + hb.o_bandl, bandl.data(), bandl.size() * 4);
+    im.copy_to(b);
+    build_perm(c, to_idx, nt, reinterpret_cast<int32_t *>(b + at_perm_t), W.ord_t);
     if (prep_timing && blk_no < 12)
         fprintf(stderr, "[ldw prep us] block %lld%s %lld x %lld span %d: checks + intervals %.0f  row order %.0f  sides %.0f  tiles + classes %.0f  band %.0f  band list %.0f  copy to staging %.0f  (%zu bytes)\n",
                 (long long)blk_no, hb.diag ? " diag" : "", (long long)nf, (long long)nt, hb.span, tp[1] - tp[0], tp[2] - tp[1], tp[3] - tp[2], tp[4] - tp[3], tp[5] - tp[4], tp[6] - tp[5], pnow() - tp[6], hb.total);
@@ -418,19 +474,13 @@ double lo_bound(const ldw_ctx *c) {
     return c->lo_abs_sum * (2.0 * std::log(den + 12.5) + 3.0) / den;
 }
 
-// device image of a block's index structures (its part of the item's staging buffer)
-static inline const char *stage_ptr(ldw_ctx *c, const HostBlock &hb) {
-    return c->dstage[hb.pin_slot >= 0 ? hb.pin_slot : hb.slot].as<char>() + hb.stage_base;
-}
-
 // what the emission of a block's pairs needs (short-range table, candidate list of this slot)
 int make_emit_args(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayout &sl, int spec_B) {
     const int s = hb.slot;
     const bool do_lr = !p->sr_only;
-    const char *d = stage_ptr(c, hb);
     EmitArgs E;
     memset(&E, 0, sizeof(E));
-    E.cols = reinterpret_cast<const ColInfo *>(d + hb.o_cols);
+    E.cols = hb.D.cols;
     E.nf = (int)hb.nf;
     E.lower_only = hb.diag ? 1 : 0;
     E.keep_sr = p->keep_sr ? 1 : 0;
@@ -521,17 +571,9 @@ int launch_pick(ldw_ctx *c, const HostBlock &hb, const ldw_mi_params *p, const S
     return LDW_OK;
 }
 
-// First phase: upload the block's index structures, then the co-occurrence GEMM into this slot's G buffer on the GEMM stream.
-// Nothing there touches what the previous block's epilogue / selection still uses, so it overlaps the tail of block b.
+// the device image of a block's index structures is its part of the item's staging buffer: after that buffer's reserve, which may move it
 static void fill_dev_ptrs(ldw_ctx *c, HostBlock &hb) {
-    const char *d = stage_ptr(c, hb);
-    auto I = [&](size_t off) { return reinterpret_cast<const int32_t *>(d + off); };
-    auto B = [&](size_t off) { return reinterpret_cast<const uint8_t *>(d + off); };
-    hb.D = DevPtrs{I(hb.o_idx_f), I(hb.o_idx_t), I(hb.o_rl_f), I(hb.o_rl_t), I(hb.o_lrow_f), I(hb.o_lrow_t), I(hb.o_perm), I(hb.o_perm_t),
-                   I(hb.o_pos_f), I(hb.o_pos_t), B(hb.o_cls_f), B(hb.o_cls_t), I(hb.o_cmax),
-                   reinterpret_cast<const int64_t *>(d + hb.o_tbase), I(hb.o_tf), B(hb.o_band),
-                   hb.n_band >= 0 ? reinterpret_cast<const uint32_t *>(d + hb.o_bandl) : nullptr, hb.n_band >= 0 ? hb.n_band : 0, hb.nf_tiles, hb.gen_t0,
-                   hb.gen_q0};
+    hb.img.bind(hb.D, c->dstage[hb.pin_slot >= 0 ? hb.pin_slot : hb.slot].as<char>() + hb.stage_base);
 }
 
 // The upload alone (copy stream): it needs no bucket guess, so the first item of a cold pass sends its lists while the cold-start probe of its
@@ -551,6 +593,8 @@ int submit_upload(ldw_ctx *c, HostBlock &hb) {
     return LDW_OK;
 }
 
+// First phase: upload the block's index structures, then the co-occurrence GEMM into this slot's G buffer on the GEMM stream.
+// Nothing there touches what the previous block's epilogue / selection still uses, so it overlaps the tail of block b.
 int submit_a(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayout &sl) {
     const int s = hb.slot;
     if (int rc = submit_upload(c, hb)) return rc;
@@ -784,6 +828,37 @@ struct SelIn {
     ldw::PickOut *pick;                 // device
     const int32_t *idx_f, *idx_t;       // device: the block's own index lists
 };
+// the selection's input for block k of an item (an ordinary block: k = 0) with m candidates
+SelIn sel_in(ldw_ctx *c, const HostBlock &hb, const SmallLayout &sl, int k, int64_t m) {
+    const int s = hb.slot;
+    const bool sp = hb.span > 0;   // (every segment of a span is long-range-only)
+    SelIn S;
+    S.m = m;
+    S.nf = hb.nf;
+    S.nt = sp ? hb.seg_nt[k] : hb.nt;
+    S.blk_no = hb.blk_no + k;
+    S.n_sr_blk = sp ? 0 : hb.n_sr_blk;
+    S.ck = sp ? hb.sseg[k].ckey : (hb.E.ckey ? hb.E.ckey : c->cand_key[s].as<uint64_t>());
+    S.cv = sp ? hb.sseg[k].cval : (hb.E.cval ? hb.E.cval : c->cand_val[s].as<uint64_t>());
+    S.pick = reinterpret_cast<ldw::PickOut *>(reinterpret_cast<char *>(sl.pick[s]) + (size_t)k * PICK_STRIDE);
+    S.idx_f = hb.D.idx_f;
+    S.idx_t = hb.D.idx_t + (sp ? hb.seg_start[k] : 0);
+    return S;
+}
+
+// The three arrays of the sort-free selection (k_sel_thresh) stay all-zero between uses (k_sel_clear): first use, or a larger block or span
+// than any before, reserves them and zeroes them afresh
+int reserve_sel_scratch(ldw_ctx *c, size_t bitmap_bytes, size_t chunk_bytes, size_t prefix_bytes) {
+    if (bitmap_bytes <= c->sel_bitmap.cap && chunk_bytes <= c->sel_chunks.cap && prefix_bytes <= c->sel_prefix.cap) return LDW_OK;
+    if (int rc = c->sel_bitmap.reserve(bitmap_bytes)) return rc;
+    if (int rc = c->sel_chunks.reserve(chunk_bytes)) return rc;
+    if (int rc = c->sel_prefix.reserve(prefix_bytes)) return rc;
+    LDW_HIP(hipMemsetAsync(c->sel_bitmap.p, 0, c->sel_bitmap.cap, c->stream));
+    LDW_HIP(hipMemsetAsync(c->sel_chunks.p, 0, c->sel_chunks.cap, c->stream));
+    LDW_HIP(hipMemsetAsync(c->sel_prefix.p, 0, c->sel_prefix.cap, c->stream));
+    return LDW_OK;
+}
+
 int select_rows(ldw_ctx *c, const SelIn &S, bool do_lr, const SmallLayout &sl) {
     const int64_t m = do_lr ? S.m : 0;
     uint64_t *ck = S.ck, *cv = S.cv;
@@ -795,15 +870,7 @@ int select_rows(ldw_ctx *c, const SelIn &S, bool do_lr, const SmallLayout &sl) {
         // the common case: radix select + bitmap ranks, four small launches, no sort (k_sel_thresh)
         if (int rc = ensure_links_capacity(c, c->n_sr, c->n_lr + m)) return rc;
         const int n_super = (int)n_super_ll;
-        if ((size_t)n_words * 4 > c->sel_bitmap.cap || (size_t)n_chunks * 4 > c->sel_chunks.cap || (size_t)n_super * 4 > c->sel_prefix.cap) {
-            // first use / a larger block: fresh zeroes
-            if (int rc = c->sel_bitmap.reserve((size_t)n_words * 4)) return rc;
-            if (int rc = c->sel_chunks.reserve((size_t)n_chunks * 4)) return rc;
-            if (int rc = c->sel_prefix.reserve((size_t)SEL_MAX_SUPER * 4)) return rc;
-            LDW_HIP(hipMemsetAsync(c->sel_bitmap.p, 0, c->sel_bitmap.cap, c->stream));
-            LDW_HIP(hipMemsetAsync(c->sel_chunks.p, 0, c->sel_chunks.cap, c->stream));
-            LDW_HIP(hipMemsetAsync(c->sel_prefix.p, 0, c->sel_prefix.cap, c->stream));
-        }
+        if (int rc = reserve_sel_scratch(c, (size_t)n_words * 4, (size_t)n_chunks * 4, (size_t)SEL_MAX_SUPER * 4)) return rc;
         uint32_t *bm = c->sel_bitmap.as<uint32_t>(), *cc = c->sel_chunks.as<uint32_t>(), *sc = c->sel_prefix.as<uint32_t>();
         const unsigned gridm = (unsigned)((m + 255) / 256);
         hipLaunchKernelGGL(k_sel_thresh, dim3(1), dim3(1024), 0, c->stream, ck, S.pick);
@@ -846,6 +913,41 @@ int select_rows(ldw_ctx *c, const SelIn &S, bool do_lr, const SmallLayout &sl) {
     return LDW_OK;
 }
 
+// the exact number of long-range rows kept by everything selected before (the copy-back the last queue_lr_count left)
+int read_lr_count(ldw_ctx *c) {
+    if (!c->lrc_recorded) return LDW_OK;
+    LDW_HIP(hipEventSynchronize(c->ev_lrc));
+    memcpy(&c->n_lr, c->pin_lrc, 8);
+    return LDW_OK;
+}
+int queue_lr_count(ldw_ctx *c, const SmallLayout &sl) {
+    LDW_HIP(hipMemcpyAsync(c->pin_lrc, sl.lr_count, 8, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipEventRecord(c->ev_lrc, c->stream));
+    c->lrc_recorded = true;
+    return LDW_OK;
+}
+// the end of an item on the main stream: the row count goes back, its last stage event, its slot is free
+int end_item(ldw_ctx *c, const HostBlock &hb, const SmallLayout &sl) {
+    if (int rc = queue_lr_count(c, sl)) return rc;
+    LDW_HIP(hipEventRecord(c->ev_pool[(size_t)hb.blk_no * EVB + 3], c->stream));
+    LDW_HIP(hipEventRecord(c->ev_done[hb.slot], c->stream));
+    c->done_recorded[hb.slot] = true;
+    return LDW_OK;
+}
+// what block k of an item taught the host: the guess for later blocks of its kind, and its trace record
+void note_block(ldw_ctx *c, const HostBlock &hb, int k, const ldw::PickOut *hp, bool do_lr, bool missed) {
+    if (do_lr && hp->n > 0) update_guess(c, hb.diag, hp, missed);
+    if ((int64_t)c->trace.size() <= hb.blk_no + k) c->trace.resize((size_t)(hb.blk_no + k) + 1);
+    ldw::BlockTrace &tr = c->trace[(size_t)(hb.blk_no + k)];
+    tr = ldw::BlockTrace();
+    tr.diag = hb.diag ? 1 : 0;
+    tr.guess = hb.guess;
+    tr.B_true = do_lr ? hp->B_true : -1;
+    tr.path = hb.span ? 4 : (hb.apx ? 2 : (hb.mixed ? 1 : 0));
+    tr.missed = missed ? 1 : 0;
+    tr.n_cand = do_lr ? (long long)hp->n_cand : 0;
+}
+
 int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayout &sl);
 
 int finish_block(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayout &sl) {
@@ -881,41 +983,10 @@ int finish_block(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallL
         note_overflow(c, hp->over);
         missed = true;
     }
-    if (do_lr && hp->n > 0) update_guess(c, hb.diag, hp, missed || hb.force_plain);   // (force_plain: the redo of a span's segment whose guess was wrong)
-    if ((int64_t)c->trace.size() <= hb.blk_no) c->trace.resize((size_t)hb.blk_no + 1);
-    {
-        ldw::BlockTrace &tr = c->trace[(size_t)hb.blk_no];
-        tr.diag = hb.diag ? 1 : 0;
-        tr.guess = hb.guess;
-        tr.B_true = do_lr ? hp->B_true : -1;
-        tr.path = hb.apx ? 2 : (hb.mixed ? 1 : 0);
-        tr.missed = (missed || hb.force_plain) ? 1 : 0;
-        tr.n_cand = do_lr ? (long long)hp->n_cand : 0;
-    }
-    if (c->lrc_recorded) {   // exact number of long-range rows kept by all EARLIER blocks
-        LDW_HIP(hipEventSynchronize(c->ev_lrc));
-        memcpy(&c->n_lr, c->pin_lrc, 8);
-    }
-    const char *d = stage_ptr(c, hb);
-    SelIn S;
-    S.m = do_lr ? (int64_t)hp->n_cand : 0;
-    S.nf = hb.nf;
-    S.nt = hb.nt;
-    S.blk_no = hb.blk_no;
-    S.n_sr_blk = hb.n_sr_blk;
-    S.ck = hb.E.ckey ? hb.E.ckey : c->cand_key[s].as<uint64_t>();
-    S.cv = hb.E.cval ? hb.E.cval : c->cand_val[s].as<uint64_t>();
-    S.pick = sl.pick[s];
-    S.idx_f = reinterpret_cast<const int32_t *>(d + hb.o_idx_f);
-    S.idx_t = reinterpret_cast<const int32_t *>(d + hb.o_idx_t);
-    if (int rc = select_rows(c, S, do_lr, sl)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->pin_lrc, sl.lr_count, 8, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipEventRecord(c->ev_lrc, c->stream));
-    c->lrc_recorded = true;
-    LDW_HIP(hipEventRecord(c->ev_pool[(size_t)hb.blk_no * EVB + 3], c->stream));
-    LDW_HIP(hipEventRecord(c->ev_done[s], c->stream));
-    c->done_recorded[s] = true;
-    return LDW_OK;
+    note_block(c, hb, 0, hp, do_lr, missed || hb.force_plain);   // (force_plain: the redo of a span's segment whose guess was wrong)
+    if (int rc = read_lr_count(c)) return rc;   // (all EARLIER blocks)
+    if (int rc = select_rows(c, sel_in(c, hb, sl, 0, do_lr ? (int64_t)hp->n_cand : 0), do_lr, sl)) return rc;
+    return end_item(c, hb, sl);
 }
 
 // One reference block of a span through the ordinary per-block chain (prep -> submit_a -> submit_b -> finish_block), synchronously, on the
@@ -951,12 +1022,7 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
     LDW_HIP(hipEventSynchronize(c->ev_pick[s]));
     ldw::PickOut picks[LDW_SPAN_MAX];
     for (int k = 0; k < hb.span; ++k) memcpy(&picks[k], static_cast<const char *>(c->pin_pick[s]) + (size_t)k * PICK_STRIDE, sizeof(ldw::PickOut));
-    if (c->lrc_recorded) {   // exact number of long-range rows kept by all EARLIER blocks (within the span: upper bounds add up)
-        LDW_HIP(hipEventSynchronize(c->ev_lrc));
-        memcpy(&c->n_lr, c->pin_lrc, 8);
-    }
-    const char *d = stage_ptr(c, hb);
-    if ((int64_t)c->trace.size() < hb.blk_no + hb.span) c->trace.resize((size_t)(hb.blk_no + hb.span));
+    if (int rc = read_lr_count(c)) return rc;   // (all EARLIER blocks; within the span: upper bounds add up)
     {
         static const bool trace_on = getenv("LDW_BLOCK_TRACE") != nullptr;
         if (trace_on && picks[0].n > 0 && !picks[0].spec_ok) {   // a span that missed: its pair-list counters (an overflowing list fails every segment)
@@ -1004,29 +1070,16 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
             S.space[k] = space;
             S.n_super[k] = (int)((n_chunks + SEL_SUPER - 1) / SEL_SUPER);
         }
-        if (w_off * 4 > c->sel_bitmap.cap || c_off * 4 > c->sel_chunks.cap || (size_t)LDW_SPAN_MAX * SEL_MAX_SUPER * 4 > c->sel_prefix.cap) {
-            // first use / a larger span: fresh zeroes (all three arrays stay all-zero between uses: k_sel_clear)
-            if (int rc = c->sel_bitmap.reserve(w_off * 4)) return rc;
-            if (int rc = c->sel_chunks.reserve(c_off * 4)) return rc;
-            if (int rc = c->sel_prefix.reserve((size_t)LDW_SPAN_MAX * SEL_MAX_SUPER * 4)) return rc;
-            LDW_HIP(hipMemsetAsync(c->sel_bitmap.p, 0, c->sel_bitmap.cap, c->stream));
-            LDW_HIP(hipMemsetAsync(c->sel_chunks.p, 0, c->sel_chunks.cap, c->stream));
-            LDW_HIP(hipMemsetAsync(c->sel_prefix.p, 0, c->sel_prefix.cap, c->stream));
-        }
+        if (int rc = reserve_sel_scratch(c, w_off * 4, c_off * 4, (size_t)LDW_SPAN_MAX * SEL_MAX_SUPER * 4)) return rc;
         if (int rc = ensure_links_capacity(c, c->n_sr, c->n_lr + m_sum)) return rc;
         for (int k = 0; k < hb.span; ++k) {
             const ldw::PickOut *hp = &picks[k];
-            if (hp->n > 0) update_guess(c, false, hp, false);
-            ldw::BlockTrace &tr = c->trace[(size_t)hb.blk_no + k];
-            tr = ldw::BlockTrace();
-            tr.guess = hb.guess;
-            tr.B_true = hp->B_true;
-            tr.path = 4;   // span
-            tr.n_cand = (long long)hp->n_cand;
-            S.ck[k] = hb.sseg[k].ckey;
-            S.cv[k] = hb.sseg[k].cval;
-            S.pick[k] = reinterpret_cast<ldw::PickOut *>(reinterpret_cast<char *>(sl.pick[s]) + (size_t)k * PICK_STRIDE);
-            S.idx_t[k] = reinterpret_cast<const int32_t *>(d + hb.o_idx_t) + hb.seg_start[k];
+            note_block(c, hb, k, hp, true, false);
+            const SelIn B = sel_in(c, hb, sl, k, (int64_t)hp->n_cand);
+            S.ck[k] = B.ck;
+            S.cv[k] = B.cv;
+            S.pick[k] = B.pick;
+            S.idx_t[k] = B.idx_t;
             S.bitmap[k] = c->sel_bitmap.as<uint32_t>() + woff[k];
             S.chunks[k] = c->sel_chunks.as<uint32_t>() + coff[k];
             S.supers[k] = c->sel_prefix.as<uint32_t>() + (size_t)k * SEL_MAX_SUPER;
@@ -1034,7 +1087,7 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
         const unsigned gridm = (unsigned)std::max<long long>(1, (m_max + 255) / 256);
         hipLaunchKernelGGL(k_sel_thresh_span, dim3(1, (unsigned)hb.span), dim3(1024), 0, c->stream, S);
         hipLaunchKernelGGL(k_sel_mark_span, dim3(gridm, (unsigned)hb.span), dim3(256), 0, c->stream, S);
-        hipLaunchKernelGGL(k_sel_scatter_span, dim3(gridm, (unsigned)hb.span), dim3(256), 0, c->stream, S, reinterpret_cast<const int32_t *>(d + hb.o_idx_f), (int)hb.nf,
+        hipLaunchKernelGGL(k_sel_scatter_span, dim3(gridm, (unsigned)hb.span), dim3(256), 0, c->stream, S, hb.D.idx_f, (int)hb.nf,
                            sl.lr_count, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>());
         hipLaunchKernelGGL(k_sel_clear_span, dim3(gridm, (unsigned)hb.span), dim3(256), 0, c->stream, S);
         hipLaunchKernelGGL(k_span_done, dim3(1), dim3(64), 0, c->stream, S, DA, sl.lr_count, sl.stats_i + hb.blk_no * 3, sl.stats_d + hb.blk_no);
@@ -1049,42 +1102,15 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
             ++c->span_fallbacks;
             note_overflow(c, hp->over);
             // (the redo reads the exact row count of everything before it: the selections of the span's earlier segments are queued, not counted yet)
-            LDW_HIP(hipMemcpyAsync(c->pin_lrc, sl.lr_count, 8, hipMemcpyDeviceToHost, c->stream));
-            LDW_HIP(hipEventRecord(c->ev_lrc, c->stream));
-            c->lrc_recorded = true;
+            if (int rc = queue_lr_count(c, sl)) return rc;
             if (int rc = run_block_alone(c, hb, k, p, sl, true)) return rc;
             continue;
         }
-        if (hp->n > 0) update_guess(c, false, hp, false);
-        {
-            ldw::BlockTrace &tr = c->trace[(size_t)hb.blk_no + k];
-            tr = ldw::BlockTrace();
-            tr.guess = hb.guess;
-            tr.B_true = hp->B_true;
-            tr.path = 4;   // span
-            tr.n_cand = (long long)hp->n_cand;
-        }
+        note_block(c, hb, k, hp, true, false);
         LDW_REQUIRE((size_t)hp->n_cand <= hb.cand_cap, LDW_ERR_STATE, "span segment %d lists %llu candidates, capacity %zu", k, (unsigned long long)hp->n_cand, hb.cand_cap);
-        SelIn S;
-        S.m = (int64_t)hp->n_cand;
-        S.nf = hb.nf;
-        S.nt = hb.seg_nt[k];
-        S.blk_no = hb.blk_no + k;
-        S.n_sr_blk = 0;   // (every segment is long-range-only)
-        S.ck = hb.sseg[k].ckey;
-        S.cv = hb.sseg[k].cval;
-        S.pick = reinterpret_cast<ldw::PickOut *>(reinterpret_cast<char *>(sl.pick[s]) + (size_t)k * PICK_STRIDE);
-        S.idx_f = reinterpret_cast<const int32_t *>(d + hb.o_idx_f);
-        S.idx_t = reinterpret_cast<const int32_t *>(d + hb.o_idx_t) + hb.seg_start[k];
-        if (int rc = select_rows(c, S, true, sl)) return rc;
+        if (int rc = select_rows(c, sel_in(c, hb, sl, k, (int64_t)hp->n_cand), true, sl)) return rc;
     }
-    LDW_HIP(hipMemcpyAsync(c->pin_lrc, sl.lr_count, 8, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipEventRecord(c->ev_lrc, c->stream));
-    c->lrc_recorded = true;
-    LDW_HIP(hipEventRecord(c->ev_pool[(size_t)hb.blk_no * EVB + 3], c->stream));
-    LDW_HIP(hipEventRecord(c->ev_done[s], c->stream));
-    c->done_recorded[s] = true;
-    return LDW_OK;
+    return end_item(c, hb, sl);
 }
 
 // Cold start: a bucket guess for a block kind from a LATTICE SAMPLE of one of its blocks.  Every PROBE_STRIDE-th SNP of both sides
