@@ -556,6 +556,27 @@ int ldw_plot_heatmap(ldw_ctx *ctx, const double *htm, int32_t B, int on_device, 
 int ldw_plot_ldmap(ldw_ctx *ctx, int32_t reducer, int32_t from, int32_t to, const char *title, const char *png_path, int64_t *n_pos_out,
                    int32_t *reducer_out, int32_t *B_out, double *htm_out, int64_t capacity);
 
+/* The network plot of create_network (R/createNetworkPlot.R:120-139).  Its edges are CAPSULES — the pixels within w / 2 of a segment — blended
+ * over a white canvas in list order.  Pixels and endpoints are integer points; with D2 the squared distance from a pixel to the segment (to the nearer end
+ * where the projection falls outside it), the pixel is covered iff 4 D2 <= w^2, evaluated exactly in 64-bit integers; a covered pixel takes, per channel,
+ * c = (c (255 - alpha) + colour alpha + 127) / 255.  Limits (LDW_ERR_ARG beyond them): canvas 1..8192 each way, endpoint coordinates in -8192..16383 (they
+ * may lie outside the canvas and may coincide: a disc), w in 1..1024, alpha in 1..255, at most 2^17 capsules (8192 edges of 16 segments: the binning
+ * tests every capsule against every 32 x 32 tile, so its work is tiles x capsules). */
+typedef struct ldw_capsule {
+    int32_t x0, y0, x1, y1;   /* the segment's ends */
+    int32_t w;                /* width in pixels */
+    uint32_t rgb;             /* 0xRRGGBB */
+    int32_t alpha;            /* 1..255 */
+} ldw_capsule;
+/* The figure: the capsules rendered on the device; then, by the host, a white bordered box with node_names[k] centred on (node_xy[2k], node_xy[2k + 1]) for
+ * every node, the title (may be NULL) centred at the top and, for n_legend > 0, the legend "Num_Links" at the bottom with one swatch legend_rgb[k] and value
+ * legend_value[k] each, in the 5 x 7 font at text_scale (1..64).  The figure goes to png_path (may be NULL) and / or rgb_out (may be NULL: H x W x 3 bytes).
+ * boxes_out (may be NULL, (n_nodes + 2) x 4 int32): x, y, w, h of what the host drew over the raster — the node boxes, the title, the legend (w = 0: none);
+ * a box may reach past the canvas. */
+int ldw_plot_network(ldw_ctx *ctx, const ldw_capsule *caps, int64_t n_caps, int32_t W, int32_t H, const int32_t *node_xy, const char *const *node_names,
+                     int32_t n_nodes, const char *title, const int32_t *legend_value, const uint32_t *legend_rgb, int32_t n_legend, int32_t text_scale,
+                     const char *png_path, uint8_t *rgb_out, int32_t *boxes_out);
+
 /* ---- (13) numeric link tables read on the device — the readers of R/io_functions.R:32-66 (read_LongRangeLinks, read_ShortRangeLinks), and through them
  *           the file inputs of genomewide_LDMap (R/LDSummaryPlot.R), analyse_long_range_links (R/lr_analyser.R) and make_gwes_plots -----------------------
  * A text file, plain or gzip (read with zlib), no header, ONE separator byte ('\t' or ' '), every cell a number.  Lines end at '\n'; one '\r' before it is
@@ -594,6 +615,35 @@ int ldw_set_positions(ldw_ctx *ctx, const int32_t *POS, int64_t L, double g);
  * first such row that stays): a position that is not an integer, does not fit in 32 bits, or is no SNP's.  flags: 0.  *n_out (may be NULL): rows installed. */
 int ldw_links_load(ldw_ctx *ctx, int which, int32_t pos1_col, int32_t pos2_col, int32_t mi_col, int32_t min_len_col, double min_len, int32_t flags,
                    int64_t *n_out);
+
+/* ---- (14) annotated link files searched on the device — grep(gene, pos1_ann / pos2_ann) of create_network_for_gene (R/createNetworkPlot.R:169-290) over
+ *           sr_links_annotated.tsv / lr_links_annotated.tsv of perform_snpEff_annotations ------------------------------------------------------
+ * The file: a tab-separated table with ONE header line, plain or gzip, at most 16 columns, its lines under the rules of (13).  The columns pos1, pos2, len,
+ * ARACNE, MI (numbers under the grammar and the value rule of (13)) and pos1_ann, pos2_ann, links (byte strings, possibly empty, without a tab) are found BY
+ * NAME in the header; every other column is neither parsed nor searched.  An ARACNE cell may also be TRUE or FALSE, read as 1 and 0: the long-range file
+ * holds a logical column.  The needles: n in 1..1024 byte strings of 1..255 bytes, needle j = needles[needle_off[j] .. needle_off[j + 1]).  A row is KEPT
+ * iff some needle occurs, byte for byte and case sensitive (grep(fixed = TRUE): no regular expressions), inside the field pos1_ann or inside the field
+ * pos2_ann — never across a tab — and, with LDW_GREP_DROP_SYXSY, its links field is not exactly "syXsy", and, with LDW_GREP_DROP_INDIRECT, its ARACNE
+ * value equals 1.
+ * Refused (LDW_ERR_ARG; the message names the file, the 1-based physical line and the 1-based column; the earliest bad line wins, inside it the leftmost
+ * fault): a header without one of the eight names (column = fields + 1) or with one of them twice, or with more than 16 fields; a row with fewer (column = the
+ * first missing field) or more (column = fields + 1) fields than the header; a cell of the five numeric columns that is not a number; a line over 2^20 bytes;
+ * a file without a header line; n or a needle's length out of range.
+ * Host memory is O(chunk + kept rows).  Device memory is O(chunk + kept rows of a chunk): the chunk's image, 4 bytes per row of the chunk (its row starts),
+ * and one record of 96 + 8 ceil(n / 64) bytes per kept row — room for 16384 at first; a chunk that keeps more is searched once more with room for all its rows —
+ * in grow-only buffers that ldw_ctx_destroy frees (ldw_host_trim releases the records and the last result). */
+#define LDW_GREP_DROP_SYXSY 1
+#define LDW_GREP_DROP_INDIRECT 2
+/* Searches the file in chunks of chunk_bytes (0: 64 MiB; at most 2^30) through the pinned buffers of ldw_tsv_read.  The kept rows stay with the context until
+ * the next call: *rows_out their count, *text_bytes_out the bytes of their three strings together, *data_rows_out the data rows of the file (any may be NULL). */
+int ldw_links_grep(ldw_ctx *ctx, const char *path, const uint8_t *needles, const int32_t *needle_off, int32_t n_needles, int32_t flags, int64_t chunk_bytes,
+                   int64_t *rows_out, int64_t *text_bytes_out, int64_t *data_rows_out);
+/* The kept rows of the last ldw_links_grep, in file order, into host arrays: row_out[rows] the 0-based index among the data rows; num_out[rows][5] = pos1, pos2,
+ * len, ARACNE, MI; mask_out[rows][ceil(n / 64)]: bit j & 63 of word j / 64 set iff needle j occurs in either field; text_out / text_off_out[3 rows + 1]: string
+ * 3 i + k of row i (k = 0 pos1_ann, 1 pos2_ann, 2 links) = text_out[text_off_out[3 i + k] .. text_off_out[3 i + k + 1]).  LDW_ERR_SIZE when capacity < rows or
+ * text_capacity < the text bytes; LDW_ERR_STATE without a result. */
+int ldw_links_grep_fetch(ldw_ctx *ctx, int64_t capacity, int64_t text_capacity, int64_t *row_out, double *num_out, uint64_t *mask_out, uint8_t *text_out,
+                         int64_t *text_off_out);
 
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */

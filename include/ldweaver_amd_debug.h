@@ -190,6 +190,12 @@ int ldw_debug_plot_panels(ldw_ctx *ctx, const double *x, const double *y, const 
                           int64_t *scratch_bytes_out, double *ms_out);
 /* Host only: the 2056 colours of the LD map's ramp (kind 0, rgb_out 2056 x 3) or the scatter gradient at t[n] (kind 1, rgb_out n x 3). */
 int ldw_debug_plot_colours(int kind, const double *t, int64_t n, uint8_t *rgb_out);
+/* The raw raster of ldw_plot_network, before the host draws over it: rgb_out[H][W][3] (host).  ms_out (may be NULL, 2 doubles): hip-event times of the binning
+ * (boxes, counts, sums, lists) and of the shading. */
+int ldw_debug_plot_capsules(ldw_ctx *ctx, const ldw_capsule *caps, int64_t n_caps, int32_t W, int32_t H, uint8_t *rgb_out, double *ms_out);
+/* The last ldw_links_grep of the context, out8: [0] the whole call, ms (host clock); [1] inside gzread, ms (host clock); [2] chunk copies, [3] line kernels
+ * (k_tsv_count, scan), [4] k_tsv_starts + k_links_grep, ms (hip events, summed over the chunks); [5] chunks; [6] bytes searched; [7] rows kept. */
+int ldw_links_grep_stats(ldw_ctx *ctx, double *out8);
 /* The last ldw_tsv_read of the context, out10: [0] the whole call, ms (host clock); [1] inside gzread, ms (host clock); [2] chunk copies, [3] line kernels
  * (k_tsv_count, scan), [4] k_tsv_starts + k_tsv_parse, ms (hip events, summed over the chunks); [5] slow-cell conversion and patch, ms (host clock round its
  * copies and kernel); [6] chunks; [7] bytes parsed; [8] times the columns moved to a larger buffer since the context was made; [9] bytes of the two pinned

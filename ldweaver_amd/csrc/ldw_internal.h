@@ -81,6 +81,7 @@ struct ldw_ctx {
     void *fasta = nullptr;           // scan state of the native FASTA feeder (ldw_fasta.hip: FastaScan), made by ldw_fasta_scan
     void *out = nullptr;             // staging of the alignment writer (ldw_out.hip: OutState), made by ldw_write_alignment
     void *tsv = nullptr;             // the link-table reader (ldw_links_read.hip: TsvState), made by ldw_tsv_read
+    void *grep = nullptr;            // the search of annotated link files (ldw_links_grep.hip: GrepState), made by ldw_links_grep
 
     // ---- weights ----
     bool have_weights = false;

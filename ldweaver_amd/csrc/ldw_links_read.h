@@ -42,7 +42,23 @@ int tsv_line_of_offset(const char *path, int64_t off, int64_t *line_out);
 // correctly rounded double of the decimal text at p (strtod_l in the "C" locale); the text ends at the first byte strtod does not take
 double tsv_strtod(const char *p);
 
+// The header line text[0 .. len) (no '\n'; a '\r' at its end is dropped) of a tab-separated table: col_out[k] = 0-based column named names[k], *ncols_out = its
+// fields.  LDW_ERR_ARG, the message naming path, `line` and a 1-based column: a name that is missing (column = fields + 1) or there twice (column = the second
+// one), more than max_cols fields.
+int tsv_header_columns(const char *path, int64_t line, const char *text, int64_t len, const char *const *names, int n_names, int max_cols, int32_t *col_out,
+                       int32_t *ncols_out);
+// ldw_links_read.hip, for another pass over a text file (ldw_links_grep.hip).  The reader's two pinned chunk buffers (their TSV_FRONT bytes set to '\n') and
+// the device image, with room for chunks of `chunk` bytes: *cap_out = data bytes a buffer holds (TsvFeeder::fill's cap).  They are the reader's own: a
+// pass that uses them must finish before the next ldw_tsv_read starts (both run on the context's stream, from the caller's thread).
+int tsv_chunk_buffers(ldw_ctx *ctx, int64_t chunk, void *pin[2], uint8_t **d_img, int64_t *cap_out);
+// The non-empty lines of the `cut` bytes at d_buf (device; '\n' in front and behind as TSV_FRONT / TSV_TAIL have it), queued on the context's stream:
+// k_tsv_count and the exclusive sums, *d_total = device address of the line count; then, the count known, k_tsv_starts: (*d_starts)[k] = first byte of line k.
+int tsv_rows_count(ldw_ctx *ctx, const uint8_t *d_buf, int64_t cut, const uint32_t **d_total);
+int tsv_rows_starts(ldw_ctx *ctx, const uint8_t *d_buf, int64_t cut, uint32_t nrows, const uint32_t **d_starts);
+
 void tsv_release(ldw_ctx *ctx);      // ldw_links_read.hip: the reader's state (ldw_ctx_destroy)
 int64_t tsv_trim(ldw_ctx *ctx);      // ... its pinned chunk buffers and the chunk's device image only (ldw_host_trim); bytes released
+void grep_release(ldw_ctx *ctx);     // ldw_links_grep.hip: the search's state (ldw_ctx_destroy)
+int64_t grep_trim(ldw_ctx *ctx);     // ... its device records and the host copy of the last result (ldw_host_trim); bytes released
 
 }  // namespace ldw

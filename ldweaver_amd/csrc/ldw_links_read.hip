@@ -15,6 +15,7 @@
 #include "ldw_dev.h"
 #include "ldw_fasta.h"
 #include "ldw_links_read.h"
+#include "ldw_tsv_cell.h"
 
 using namespace ldw;
 
@@ -32,9 +33,6 @@ struct TsvResult {   // what a chunk's kernels report (device, copied to a pinne
     unsigned long long bad;      // min over the refused rows of row << 16 | column (1-based) << 8 | reason; ~0: none
     uint32_t rows, slow, not_int, pad;
 };
-
-__device__ const double kPow10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
-                                      1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
 
 // bit j: byte base + j is the first byte of a non-empty line (the byte before it is '\n', it is neither '\n' nor the '\r' of a "\r\n").  buf[-1] and
 // the bytes behind the data are '\n' (TSV_FRONT, TSV_TAIL).
@@ -94,8 +92,6 @@ __global__ __launch_bounds__(TSV_BLOCK) void k_tsv_starts(const uint8_t *__restr
     }
 }
 
-__device__ __forceinline__ bool is_digit(uint8_t c) { return (uint8_t)(c - '0') <= 9; }
-
 // One row: ncols cells from p[0 ..] into cols[c * stride + row].  Returns 0, or column << 8 | reason of the first thing that is wrong, left to right.
 // *not_int gets a bit for every column whose cell is not a plain integer literal [+-]?[0-9]+; a cell outside the fast path is appended to slow[].
 template <class P>
@@ -104,98 +100,15 @@ __device__ __forceinline__ uint32_t parse_row(P p, int ncols, uint8_t sep, doubl
     uint32_t i = 0;
     for (int col = 0; col < ncols; ++col) {
         const uint32_t cell = i;
-        uint8_t c = p[i];
-        bool neg = false, sgn = false;
-        if (c == '-' || c == '+') {
-            neg = c == '-';
-            sgn = true;
-            c = p[++i];
-        }
         double v;
-        bool plain = true;
-        if (is_digit(c) || c == '.') {
-            uint64_t m = 0;
-            int nd = 0, dexp = 0;
-            bool any = false, dropped = false;
-            while (is_digit(c)) {
-                any = true;
-                const uint32_t d = c - '0';
-                if (m != 0 || d != 0) {
-                    if (nd < 19) {
-                        m = m * 10 + d;
-                        ++nd;
-                    } else {
-                        dropped = true;
-                        if (dexp < 100000) ++dexp;
-                    }
-                }
-                c = p[++i];
-            }
-            if (c == '.') {
-                plain = false;
-                c = p[++i];
-                while (is_digit(c)) {
-                    any = true;
-                    const uint32_t d = c - '0';
-                    if (m != 0 || d != 0) {
-                        if (nd < 19) {
-                            m = m * 10 + d;
-                            ++nd;
-                            --dexp;
-                        } else {
-                            dropped = true;
-                        }
-                    } else if (dexp > -100000) {
-                        --dexp;
-                    }
-                    c = p[++i];
-                }
-            }
-            if (!any) return (uint32_t)(col + 1) << 8 | BAD_CELL;
-            if (c == 'e' || c == 'E') {
-                plain = false;
-                c = p[++i];
-                bool eneg = false;
-                if (c == '-' || c == '+') {
-                    eneg = c == '-';
-                    c = p[++i];
-                }
-                if (!is_digit(c)) return (uint32_t)(col + 1) << 8 | BAD_CELL;
-                int e = 0;
-                while (is_digit(c)) {
-                    if (e < 100000) e = e * 10 + (c - '0');
-                    c = p[++i];
-                }
-                dexp += eneg ? -e : e;
-            }
-            if (m == 0) {
-                v = 0.0;
-            } else if (!dropped && m <= (1ull << 53) && dexp >= -22 && dexp <= 22) {
-                const double dm = (double)m;   // exact
-                v = dexp < 0 ? dm / kPow10[-dexp] : dm * kPow10[dexp];
-            } else {
-                const uint32_t k = atomicAdd(slow_n, 1u);
-                slow[k] = make_uint2(row_in_chunk * (uint32_t)ncols + (uint32_t)col, row_off + cell);
-                v = 0.0;
-                neg = false;
-            }
-            if (neg) v = -v;
-        } else {
-            plain = false;
-            if (!sgn && c == 'N' && p[i + 1] == 'A') {
-                v = __longlong_as_double(0x7ff8000000000000ll);
-                i += 2;
-            } else if (!sgn && ((c == 'N' && p[i + 1] == 'a' && p[i + 2] == 'N') || (c == 'n' && p[i + 1] == 'a' && p[i + 2] == 'n'))) {
-                v = __longlong_as_double(0x7ff8000000000000ll);
-                i += 3;
-            } else if ((!sgn || neg) && (c == 'I' || c == 'i') && p[i + 1] == 'n' && p[i + 2] == 'f') {
-                v = __longlong_as_double(neg ? 0xfff0000000000000ll : 0x7ff0000000000000ll);
-                i += 3;
-            } else {
-                return (uint32_t)(col + 1) << 8 | BAD_CELL;
-            }
-            c = p[i];
+        bool plain;
+        const int kind = parse_cell(p, i, v, plain);
+        if (kind == CELL_BAD) return (uint32_t)(col + 1) << 8 | BAD_CELL;
+        if (kind == CELL_SLOW) {
+            const uint32_t k = atomicAdd(slow_n, 1u);
+            slow[k] = make_uint2(row_in_chunk * (uint32_t)ncols + (uint32_t)col, row_off + cell);
         }
+        const uint8_t c = p[i];
         if (!plain) *not_int |= 1u << col;
         const bool eol = c == '\n' || (c == '\r' && p[i + 1] == '\n');
         if (col + 1 < ncols) {
@@ -422,6 +335,47 @@ void tsv_release(ldw_ctx *c) {
     c->tsv = nullptr;
 }
 
+int tsv_chunk_buffers(ldw_ctx *c, int64_t chunk, void *pin[2], uint8_t **d_img, int64_t *cap_out) {
+    TsvState *t = tsv_state(c);
+    const int64_t cap = chunk + TSV_LINE_MAX + 64;   // data bytes of a pinned buffer: a carried line and a chunk
+    const size_t buf_bytes = (size_t)(TSV_FRONT + cap + TSV_TAIL);
+    if (int rc = ensure_pins(t, buf_bytes)) return rc;
+    if (int rc = t->img.reserve(buf_bytes)) return rc;
+    const int64_t max_blocks = (cap + TSV_TILE - 1) / TSV_TILE + 1;
+    if (int rc = t->cnt.reserve((size_t)(max_blocks + 1) * 4)) return rc;
+    if (int rc = t->off.reserve((size_t)(max_blocks + 1) * 4)) return rc;
+    size_t scan_bytes = 0;
+    LDW_HIP(prim_scan_bytes<uint32_t>((size_t)max_blocks + 1, c->stream, &scan_bytes));
+    if (int rc = t->scan_tmp.reserve(scan_bytes)) return rc;
+    for (int b = 0; b < 2; ++b) {
+        memset(t->pin[b], '\n', (size_t)TSV_FRONT);
+        pin[b] = t->pin[b];
+    }
+    *d_img = t->img.as<uint8_t>();
+    *cap_out = cap;
+    return LDW_OK;
+}
+
+int tsv_rows_count(ldw_ctx *c, const uint8_t *d_buf, int64_t cut, const uint32_t **d_total) {
+    TsvState *t = tsv_state(c);
+    const uint32_t nblocks = (uint32_t)((cut + TSV_TILE - 1) / TSV_TILE);
+    LDW_HIP(hipMemsetAsync(t->cnt.as<uint32_t>() + nblocks, 0, 4, c->stream));
+    LDW_LAUNCH(k_tsv_count, dim3(nblocks), dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->cnt.as<uint32_t>());
+    size_t sb = t->scan_tmp.cap;
+    LDW_HIP(prim_exclusive_sum(t->scan_tmp.p, sb, t->cnt.as<uint32_t>(), t->off.as<uint32_t>(), (size_t)nblocks + 1, c->stream));
+    *d_total = t->off.as<uint32_t>() + nblocks;   // the exclusive sums end with the total
+    return LDW_OK;
+}
+
+int tsv_rows_starts(ldw_ctx *c, const uint8_t *d_buf, int64_t cut, uint32_t nrows, const uint32_t **d_starts) {
+    TsvState *t = tsv_state(c);
+    const uint32_t nblocks = (uint32_t)((cut + TSV_TILE - 1) / TSV_TILE);
+    if (int rc = t->starts.reserve((size_t)std::max<uint32_t>(nrows, 1) * 4)) return rc;
+    LDW_LAUNCH(k_tsv_starts, dim3(nblocks), dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->off.as<uint32_t>(), t->starts.as<uint32_t>());
+    *d_starts = t->starts.as<uint32_t>();
+    return LDW_OK;
+}
+
 int64_t tsv_trim(ldw_ctx *c) {
     auto *t = static_cast<TsvState *>(c->tsv);
     if (!t) return 0;
@@ -454,18 +408,11 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
     t->ncols = ncols;
     memset(t->ms, 0, sizeof(t->ms));
     const auto t_begin = std::chrono::steady_clock::now();
-    const int64_t cap = chunk + TSV_LINE_MAX + 64;   // data bytes of a pinned buffer: a carried line and a chunk
-    const size_t buf_bytes = (size_t)(TSV_FRONT + cap + TSV_TAIL);
-    if (int rc = ensure_pins(t, buf_bytes)) return rc;
-    if (int rc = t->img.reserve(buf_bytes)) return rc;
+    void *pins[2];
+    uint8_t *d_img = nullptr;
+    int64_t cap = 0;   // data bytes of a pinned buffer
+    if (int rc = tsv_chunk_buffers(c, chunk, pins, &d_img, &cap)) return rc;
     if (int rc = t->res.reserve(sizeof(TsvResult))) return rc;
-    const int64_t max_blocks = (cap + TSV_TILE - 1) / TSV_TILE + 1;
-    if (int rc = t->cnt.reserve((size_t)(max_blocks + 1) * 4)) return rc;
-    if (int rc = t->off.reserve((size_t)(max_blocks + 1) * 4)) return rc;
-    size_t scan_bytes = 0;
-    LDW_HIP(prim_scan_bytes<uint32_t>((size_t)max_blocks + 1, c->stream, &scan_bytes));
-    if (int rc = t->scan_tmp.reserve(scan_bytes)) return rc;
-    for (auto &p : t->pin) memset(p, '\n', (size_t)TSV_FRONT);
 
     int rc = LDW_OK;
     int64_t slow_total = 0, consumed = 0, nchunks = 0, file_bytes = 0;
@@ -546,11 +493,9 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
         hipError_t e = hipEventRecord(t->ev[b][0], c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(t->img.p, t->pin[b], (size_t)(TSV_FRONT + padded + TSV_TAIL - 16), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipEventRecord(t->ev[b][1], c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(t->cnt.as<uint32_t>() + nblocks, 0, 4, c->stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_tsv_count, dim3(nblocks), dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->cnt.as<uint32_t>());
-            size_t sb = t->scan_tmp.cap;
-            e = prim_exclusive_sum(t->scan_tmp.p, sb, t->cnt.as<uint32_t>(), t->off.as<uint32_t>(), (size_t)nblocks + 1, c->stream);
+            const uint32_t *d_total = nullptr;
+            if ((rc = tsv_rows_count(c, d_buf, cut, &d_total))) break;
         }
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_tsv_init, dim3(1), dim3(256), 0, c->stream, d_res, (uint32_t)(k > 0), t->off.as<uint32_t>(), nblocks);
@@ -581,10 +526,10 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
             int64_t want = t->rows + nrows;
             if (k == 0 && file_bytes > cut) want = std::max<int64_t>(want, (int64_t)((double)nrows * ((double)file_bytes / (double)cut) * 1.02) + 1024);   // a plain file: sized once from its first chunk
             if ((rc = grow_columns(c, t, want))) break;
-            if ((rc = t->starts.reserve((size_t)nrows * 4))) break;
             if ((rc = t->slow.reserve((size_t)nrows * (size_t)ncols * 8))) break;
             e = hipEventRecord(t->ev[b][3], c->stream);
-            hipLaunchKernelGGL(k_tsv_starts, dim3(nblocks), dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->off.as<uint32_t>(), t->starts.as<uint32_t>());
+            const uint32_t *d_starts = nullptr;
+            if ((rc = tsv_rows_starts(c, d_buf, cut, nrows, &d_starts))) break;
             const dim3 grid((nrows + TSV_BLOCK - 1) / TSV_BLOCK);
             if (t->variant == 1)
                 hipLaunchKernelGGL(k_tsv_parse<true>, grid, dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->starts.as<uint32_t>(), nrows, (int)ncols, (uint8_t)sep,

@@ -131,6 +131,32 @@ int tsv_line_of_offset(const char *path, int64_t off, int64_t *line_out) {
     });
 }
 
+int tsv_header_columns(const char *path, int64_t line, const char *text, int64_t len, const char *const *names, int n_names, int max_cols, int32_t *col_out,
+                       int32_t *ncols_out) {
+    if (len > 0 && text[len - 1] == '\r') --len;
+    for (int k = 0; k < n_names; ++k) col_out[k] = -1;
+    int32_t ncols = 0;
+    for (int64_t at = 0; at <= len;) {
+        const void *tab = at < len ? memchr(text + at, '\t', (size_t)(len - at)) : nullptr;
+        const int64_t end = tab ? (int64_t)(static_cast<const char *>(tab) - text) : len;
+        for (int k = 0; k < n_names; ++k)
+            if ((int64_t)strlen(names[k]) == end - at && memcmp(names[k], text + at, (size_t)(end - at)) == 0) {
+                LDW_REQUIRE(col_out[k] < 0, LDW_ERR_ARG, "ldw_links_grep: %s: line %lld, column %d: the header names \"%s\" twice", path, (long long)line, (int)ncols + 1,
+                            names[k]);
+                col_out[k] = ncols;
+            }
+        ++ncols;
+        at = end + 1;
+    }
+    LDW_REQUIRE(ncols <= max_cols, LDW_ERR_ARG, "ldw_links_grep: %s: line %lld, column %d: the header has more than %d columns", path, (long long)line, max_cols + 1,
+                max_cols);
+    for (int k = 0; k < n_names; ++k)
+        LDW_REQUIRE(col_out[k] >= 0, LDW_ERR_ARG, "ldw_links_grep: %s: line %lld, column %d: the header has no column \"%s\"", path, (long long)line, (int)ncols + 1,
+                    names[k]);
+    *ncols_out = ncols;
+    return LDW_OK;
+}
+
 double tsv_strtod(const char *p) {
     static locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
     return strtod_l(p, nullptr, c_locale);

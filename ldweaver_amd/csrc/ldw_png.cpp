@@ -218,6 +218,64 @@ void plot_frame(uint8_t *canvas, const ldw_plot_layout &lay, int kind, const uin
     }
 }
 
+// The network plot's text over the edge raster (ldw_plot_net.hip): a white, bordered box with the node's name centred on every node, the title
+// centred at the top, and at the bottom the legend "Num_Links" with one swatch and value per colour.  boxes (may be NULL): x, y, w, h of the node
+// boxes in node order, then of the title and of the legend (w = 0: not drawn).
+void plot_net_overlay(uint8_t *canvas, int W, int H, const int32_t *node_xy, const char *const *node_names, int n_nodes, const char *title,
+                      const int32_t *legend_value, const uint32_t *legend_rgb, int n_legend, int sc, int32_t *boxes) {
+    Canvas cv{canvas, W, H};
+    const int pad = 2 * sc, th = 7 * sc, line = std::max(1, sc / 2);
+    auto note = [&](int k, int x, int y, int w, int h) {
+        if (!boxes) return;
+        boxes[4 * k] = x;
+        boxes[4 * k + 1] = y;
+        boxes[4 * k + 2] = w;
+        boxes[4 * k + 3] = h;
+    };
+    for (int k = 0; k < n_nodes; ++k) {
+        const int tw = text_width(node_names[k], sc), bw = tw + 2 * pad, bh = th + 2 * pad;
+        const int x = node_xy[2 * k] - bw / 2, y = node_xy[2 * k + 1] - bh / 2;
+        cv.rect(x, y, bw, bh, PLOT_TEXT);
+        cv.rect(x + line, y + line, bw - 2 * line, bh - 2 * line, PLOT_BG);
+        draw_text(cv, x + pad, y + pad, node_names[k], sc, PLOT_TITLE);
+        note(k, x, y, bw, bh);
+    }
+    if (title && title[0]) {
+        const int st = sc + sc / 2, tw = text_width(title, st);
+        const int x = (W - tw) / 2, y = 2 * sc;
+        cv.rect(x - pad, y - pad, tw + 2 * pad, 7 * st + 2 * pad, PLOT_BG);
+        draw_text(cv, x, y, title, st, PLOT_TITLE);
+        note(n_nodes, x - pad, y - pad, tw + 2 * pad, 7 * st + 2 * pad);
+    } else {
+        note(n_nodes, 0, 0, 0, 0);
+    }
+    if (n_legend > 0) {
+        const char *name = "Num_Links";
+        const int sw = 4 * th, gap = 2 * sc;
+        std::vector<std::string> val((size_t)n_legend);
+        int total = text_width(name, sc);
+        for (int k = 0; k < n_legend; ++k) {
+            val[(size_t)k] = std::to_string(legend_value[k]);
+            total += 2 * gap + sw + gap + text_width(val[(size_t)k].c_str(), sc);
+        }
+        int x = (W - total) / 2;
+        const int y = H - 2 * sc - th - pad;
+        cv.rect(x - pad, y - pad, total + 2 * pad, th + 2 * pad, PLOT_BG);
+        note(n_nodes + 1, x - pad, y - pad, total + 2 * pad, th + 2 * pad);
+        draw_text(cv, x, y, name, sc, PLOT_TITLE);
+        x += text_width(name, sc);
+        for (int k = 0; k < n_legend; ++k) {
+            x += 2 * gap;
+            cv.rect(x, y + th / 2 - sc, sw, 2 * sc, legend_rgb[k]);
+            x += sw + gap;
+            draw_text(cv, x, y, val[(size_t)k].c_str(), sc, PLOT_TEXT);
+            x += text_width(val[(size_t)k].c_str(), sc);
+        }
+    } else {
+        note(n_nodes + 1, 0, 0, 0, 0);
+    }
+}
+
 }  // namespace ldw
 
 using namespace ldw;

@@ -796,6 +796,7 @@ int ldw_host_trim(ldw_ctx *c, int64_t *bytes_out) {
         n += ldw::fasta_trim(c);   // the FASTA feeder's pinned chunk buffers
         n += ldw::out_trim(c);     // the alignment writer's pinned chunk buffers (ldw_out.hip)
         n += ldw::tsv_trim(c);     // the link-table reader's pinned chunk buffers (ldw_links_read.hip)
+        n += ldw::grep_trim(c);    // the annotated-link search's chunk records and the host copy of its last result (ldw_links_grep.hip)
         if (c->lr_stream == nullptr && c->pin_fetch) {
             (void)hipSetDevice(c->device);
             (void)hipHostFree(c->pin_fetch);

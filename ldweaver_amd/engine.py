@@ -651,6 +651,63 @@ class Engine:
         return dict(total_ms=v[0], read_ms=v[1], copy_ms=v[2], line_ms=v[3], parse_ms=v[4], patch_ms=v[5], chunks=int(v[6]), bytes=int(v[7]), grows=int(v[8]),
                     pinned_bytes=int(v[9]))
 
+    # -- annotated link files searched on the device (include/ldweaver_amd.h 14) ---
+    def links_grep(self, path, needles, drop_syXsy: bool = False, drop_indirect: bool = False, chunk_bytes: int = 0) -> dict:
+        """The rows of an annotated link file (sr_links_annotated.tsv / lr_links_annotated.tsv) whose pos1_ann or pos2_ann field holds one of
+        ``needles`` (bytes or str, literal and case sensitive), in file order (ldw_links_grep + ldw_links_grep_fetch).  Returns a dict: ``row``
+        (int64, 0-based data row), ``num`` (float64 [rows, 5]: pos1 pos2 len ARACNE MI), ``mask`` (uint64 [rows, ceil(n / 64)]), ``pos1_ann`` /
+        ``pos2_ann`` / ``links`` (lists of bytes), ``data_rows`` (rows of the file)."""
+        nd = [x.encode("utf-8", "surrogateescape") if isinstance(x, str) else bytes(x) for x in needles]
+        off = np.zeros(len(nd) + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(x) for x in nd])
+        blob = np.frombuffer(b"".join(nd) or b"\0", dtype=np.uint8)
+        flags = (1 if drop_syXsy else 0) | (2 if drop_indirect else 0)
+        rows, tbytes, drows = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        fasta_check(L.lib().ldw_links_grep(self._ctx, os.fsencode(path), L.ptr(blob), L.ptr(off), len(nd), flags, int(chunk_bytes), C.byref(rows), C.byref(tbytes),
+                                           C.byref(drows)), path)
+        n, nw = rows.value, (len(nd) + 63) // 64
+        row = np.empty(n, dtype=np.int64)
+        num = np.empty((n, 5), dtype=np.float64)
+        mask = np.empty((n, nw), dtype=np.uint64)
+        text = np.empty(max(tbytes.value, 1), dtype=np.uint8)
+        toff = np.empty(3 * n + 1, dtype=np.int64)
+        L.check(L.lib().ldw_links_grep_fetch(self._ctx, n, tbytes.value, L.ptr(row), L.ptr(num), L.ptr(mask), L.ptr(text), L.ptr(toff)))
+        tb = text.tobytes()
+        strs = [tb[toff[k]:toff[k + 1]] for k in range(3 * n)]
+        return dict(row=row, num=num, mask=mask, pos1_ann=strs[0::3], pos2_ann=strs[1::3], links=strs[2::3], data_rows=drows.value)
+
+    def links_grep_stats(self) -> dict:
+        v = np.zeros(8)
+        L.check(L.lib().ldw_links_grep_stats(self._ctx, L.ptr(v)))
+        return dict(total_ms=v[0], read_ms=v[1], copy_ms=v[2], line_ms=v[3], grep_ms=v[4], chunks=int(v[5]), bytes=int(v[6]), kept=int(v[7]))
+
+    # -- the network plot (include/ldweaver_amd.h 12) --------------------------------
+    CAPSULE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("w", "<i4"), ("rgb", "<u4"), ("alpha", "<i4")])
+
+    def plot_capsules(self, caps, W: int, H: int, timings: bool = False):
+        """The raw raster of a capsule list (ldw_debug_plot_capsules): uint8 [H, W, 3]; with ``timings`` also (binning ms, shading ms)."""
+        caps = np.ascontiguousarray(caps, dtype=self.CAPSULE)
+        out = np.empty((int(H), int(W), 3), dtype=np.uint8)
+        ms = np.zeros(2)
+        L.check(L.lib().ldw_debug_plot_capsules(self._ctx, L.ptr(caps) if len(caps) else None, len(caps), int(W), int(H), L.ptr(out), L.ptr(ms) if timings else None))
+        return (out, tuple(ms)) if timings else out
+
+    def plot_network(self, caps, W: int, H: int, node_xy, node_names, title, legend_value, legend_rgb, text_scale: int, png_path=None, want_canvas: bool = False):
+        """The network figure (ldw_plot_network).  Returns (canvas uint8 [H, W, 3] or None, boxes int32 [nodes + 2, 4])."""
+        caps = np.ascontiguousarray(caps, dtype=self.CAPSULE)
+        xy = np.ascontiguousarray(node_xy, dtype=np.int32).reshape(-1, 2)
+        names = [x.encode("utf-8", "replace") if isinstance(x, str) else bytes(x) for x in node_names]
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        lv = np.ascontiguousarray(legend_value, dtype=np.int32)
+        lc = np.ascontiguousarray(legend_rgb, dtype=np.uint32)
+        boxes = np.zeros((len(names) + 2, 4), dtype=np.int32)
+        canvas = np.empty((int(H), int(W), 3), dtype=np.uint8) if want_canvas else None
+        L.check(L.lib().ldw_plot_network(self._ctx, L.ptr(caps) if len(caps) else None, len(caps), int(W), int(H), L.ptr(xy) if len(names) else None,
+                                         C.cast(arr, C.c_void_p) if len(names) else None, len(names), (title or "").encode("utf-8", "replace"),
+                                         L.ptr(lv) if len(lv) else None, L.ptr(lc) if len(lc) else None, len(lv), int(text_scale),
+                                         os.fsencode(png_path) if png_path is not None else None, L.ptr(canvas), L.ptr(boxes)))
+        return canvas, boxes
+
     def set_positions(self, POS, g: float = 0.0):
         """Positions for an engine WITHOUT an alignment (ldw_set_positions): enough for links_load / links_import, ldmap, lr_tukey, lr_reduced,
         aracne_device and the long-range figure; g = 0: genome length not known."""
