@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: MI SNP-pairs/sec of the all-pairs weighted-MI path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--L 100000] [--N 5000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--L 100000] [--N 5000] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,16 +16,20 @@ Every step is a COLD pass, as a job runs it: `ldw_reset_speculation` forgets the
 and the biallelic threshold table before each step (warm-up steps included), so a step visits every block pair once without
 anything learnt from an earlier pass over the same data (R/computePairwiseMI.R:103-116).  Buffers stay allocated.
 
-Order of work (the GPU section is one stretch, the CPU baseline follows it: r04 — a GPU left idle for the baseline's 20-30 s made the first pass
-after it 30 ms slower than the first pass of a job, which follows the set-up at once): setup ->
-W warm-up steps -> EXACTLY K timed steps -> (N = 1 only) the extra
-legs reported on the same line: `warm_replay` (K steps WITHOUT the reset: every pass inherits its predecessor's guesses — the
+A plain run does what the headline figure needs and no more: setup -> W warm-up steps -> EXACTLY K timed steps -> (`--dump-outputs`) the
+link tables -> the line: `value`, `ms_per_step`, the workload, link counts, counters and the brackets taken inside the timed region.
+
+`--full` adds every other measurement to the same line, in this order (the GPU section is one stretch, the CPU baseline follows it: r04 — a
+GPU left idle for the baseline's 20-30 s made the first pass after it 30 ms slower than the first pass of a job, which follows the set-up at
+once): after the K timed steps, (N = 1 only) the extra legs: `warm_replay` (K steps WITHOUT the reset: every pass inherits its predecessor's guesses — the
 r02 headline, kept for comparison), `sustained` (cold steps until >= 10 s of GPU work have run), the kernel-exclusive replay
 behind `roofline`, `mi_values_produced` (5-limb GEMM + fp64 MI of EVERY pair: no screen, no mixed precision, no approximate
 GEMM — the rate at which MI values, not decisions, are produced) and `job` (the product entry points end to end, state matrix
 on the HOST -> both tsv files on disk: `h2d_ms`, Hamming weights, cold MI pass, `tsv_write_s`, short-range model + ARACNE), the
 `adversarial` workload; last, `cpu_baseline` on the host cores (rank 0, N = 1 only).
-With N > 1 the line carries `per_rank` (compute_ms, exposed_gather_ms, bytes_sent of every rank).
+With N > 1 the line carries `per_rank` (compute_ms, exposed_gather_ms, bytes_sent of every rank) and, under `--full`, the `sr_tail` leg.
+The switches that trim these legs (`--no-extra-legs`, `--no-cpu-baseline`, `--no-job`, `--no-adversarial`, `--no-sr-tail-leg`, `--sustain-s`,
+`--cpu-baseline-full`, `--cpu-sample`) act under `--full` only: without it there is nothing to trim.
 `--dump-outputs DIR` writes the link tables of the LAST timed step as .npy files right after the timed region (dump_outputs), so that
 two builds can be compared output for output on the same seeded workload.
 """
@@ -59,7 +63,11 @@ def parse():
     ap.add_argument("--engine", choices=["mfma", "hist", "hist_states"], default="mfma",
                     help="mfma: the default path; hist: joint histograms on bit planes (class-wise popcounts, k_cooc_popc) + the same fp64 epilogue; "
                          "hist_states: the first histogram kernel (byte states in LDS, k_mi_hist)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run everything else the benchmark measures and put it on the same line: the warm / sustained / "
+                         "mi_values_produced / job / adversarial legs, the serialized replay behind `roofline`, the scaling model, the CPU baseline, "
+                         "for N > 1 the sr_tail leg.  Off by default: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for "
                                                       "smoke-testing the N > 1 path on a single GPU)")
     ap.add_argument("--no-prune", action="store_true", help="A/B: no row ordering / tile pruning in the approximate GEMM")
@@ -79,20 +87,20 @@ def parse():
     ap.add_argument("--cpu-baseline-full", action="store_true", help="CPU baseline on the sample BASELINE.md 3 states: one diagonal + one off-diagonal 10 000 x 10 000 "
                                                                      "block at the config's N (minutes on 16 cores; the default times a 2 000 x 2 000 sub-block pair)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="SNPs per side of the CPU-baseline sample block (0 = auto)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the warm / sustained / mi_values_produced / job legs after the timed region")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip the warm / sustained / mi_values_produced / job legs after the timed region")
     ap.add_argument("--warm", action="store_true", help="do NOT reset the speculation state before every step (the r02 behaviour: each step inherits "
                                                         "the previous step's bucket guesses); the default is a cold pass per step")
-    ap.add_argument("--no-job", action="store_true", help="skip the end-to-end job leg (host states -> tsv files)")
-    ap.add_argument("--no-adversarial", action="store_true", help="skip the adversarial-data leg (MAF uniform in [0.2, 0.5], no clonal groups)")
+    ap.add_argument("--no-job", action="store_true", help="--full: skip the end-to-end job leg (host states -> tsv files)")
+    ap.add_argument("--no-adversarial", action="store_true", help="--full: skip the adversarial-data leg (MAF uniform in [0.2, 0.5], no clonal groups)")
     ap.add_argument("--inproc", action="store_true", help="N > 1 WITHOUT one process per GPU: this one process creates one context per device and runs "
                                                           "ldw_mi_all_pairs_multi (worker threads + peer-to-peer gather inside the library) — the route the R shim takes")
     ap.add_argument("--inproc-devices", default="", help="comma-separated device ids for --inproc (default 0..gpus-1; '0,0' = two contexts on one GPU)")
-    ap.add_argument("--no-sr-tail-leg", action="store_true", help="N > 1: skip the leg that runs the short-range model + ARACNE behind the pass both ways "
+    ap.add_argument("--no-sr-tail-leg", action="store_true", help="--full, N > 1: skip the leg that runs the short-range model + ARACNE behind the pass both ways "
                     "(table gathered to rank 0 / rows left on their ranks: ldweaver_amd/dist_srp.py)")
     ap.add_argument("--sr-tail-timeout", type=float, default=240.0, help="N > 1: seconds the sr_tail leg may take before every rank abandons it and rank 0 prints the line without it")
     ap.add_argument("--strict-exit", action="store_true", help="N > 1: exit code 3 when the sr_tail leg is abandoned or fails AFTER rank 0 has printed the line (default 0: the line of "
                                                                 "the timed region is complete and says in `sr_tail.note` what happened to the leg; a launcher that drops the line of a non-zero exit would lose the measurement)")
-    ap.add_argument("--sustain-s", type=float, default=10.0, help="N = 1: keep stepping after the timed region until this many seconds of steps have run")
+    ap.add_argument("--sustain-s", type=float, default=10.0, help="--full, N = 1: keep stepping after the timed region until this many seconds of steps have run")
     ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed region, write the link tables of the last timed step (what a caller "
                     "of the timed path receives on rank 0) as DIR/<table>_<column>.npy: see dump_outputs")
     args = ap.parse_args()
@@ -566,7 +574,7 @@ def inproc_main(args):
                    spec_misses=sum(e.counters()["spec_misses"] for e in engs))
         # r05, after the timed region: pass + short-range model + ARACNE both ways — tables gathered into context 0 and the model there, or the short-range
         # rows left on their contexts (LDW_MI_SR_ROWS_STAY) and the model's reductions over the contexts (ldw_sr_*_multi)
-        if len(engs) > 1 and not args.no_sr_tail_leg:
+        if args.full and len(engs) > 1 and not args.no_sr_tail_leg:
             from ldweaver_amd.engine import EngineGroup
             from ldweaver_amd.srp import merge_n_sort_sr_links_device
             nclust, leg = int(np.max(paint)), {}
@@ -772,9 +780,9 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine_rec)
 
-    run_sr_tail = world > 1 and not args.no_extra_legs and not args.no_sr_tail_leg and args.engine == "mfma"   # (after the line is assembled: see the end of main)
+    run_sr_tail = args.full and world > 1 and not args.no_extra_legs and not args.no_sr_tail_leg and args.engine == "mfma"   # (after the line is assembled: see the end of main)
 
-    extra = rank == 0 and world == 1 and len(my_blocks) and not args.no_extra_legs
+    extra = args.full and rank == 0 and world == 1 and len(my_blocks) and not args.no_extra_legs
     legs = {}
     # ---- warm replay: K steps that inherit their predecessor's bucket guesses, spread history and threshold table (what r02
     # reported as its headline; a real job never sees this state) ----
@@ -802,7 +810,7 @@ def main():
     # the same step with the overlap off (same kernels, same inputs, back to back on one stream) and bracket there. ----
     tim_overlapped = dict(tim)
     n_replay, gst, serial_ms_per_step, cnt_replay, unpruned = 0, None, None, None, None
-    if rank == 0 and len(my_blocks):
+    if args.full and rank == 0 and len(my_blocks):
         eng.set_overlap(False)
         for k in tim:
             tim[k] = 0.0
@@ -898,7 +906,7 @@ def main():
         legs["adversarial"] = adversarial_leg(L, N, local_rank, args)
 
     # ---- a predicted strong-scaling curve on every line (rank 0 runs every share of the N = 1, 2, 4, 8 deals alone; the other ranks wait at the next fence) ----
-    if rank == 0 and not args.no_extra_legs and args.engine == "mfma" and nblocks >= 8:
+    if args.full and rank == 0 and not args.no_extra_legs and args.engine == "mfma" and nblocks >= 8:
         legs["scaling_model"] = scaling_model_leg(eng, blocks, sr_dist, lr_retain, approx, pairs, args.gather_phases, world, dt / args.steps * 1e3, args.min_blocks_per_phase)
 
     if rank == 0:
@@ -969,6 +977,9 @@ def main():
         roof["dominant_stage"] = stage
         roof["hbm_alg_GBps_whole_step"] = (L * N + 8.0 * pairs) / (dt / K) / 1e9
         roof["hbm_frac_whole_step"] = roof["hbm_alg_GBps_whole_step"] / 8000.0
+        if not args.full:   # (no replay has run: only what the timed region itself says)
+            roof = dict(hbm_alg_GBps_whole_step=roof["hbm_alg_GBps_whole_step"], hbm_frac_whole_step=roof["hbm_frac_whole_step"],
+                        note="the dominant kernel's figures come from a serialized replay after the timed region: --full")
         mixed = (J == 5) and not args.no_mixed and not args.fused and args.screen > 0
         out = dict(metric="MI SNP-pairs/sec", value=value, unit="pairs/s", n_gpus=world, steps=K, warmup=args.warmup,
                    ms_per_step=ms_per_step, higher_is_better=True, scaling="strong", vs_baseline=None, dtype="i8",
@@ -990,7 +1001,7 @@ def main():
                                approximate_gemm=eng.apx_info(),
                                parallelism=f"pair-space blocks over {world} GPU(s)"),
                    roofline=roof)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             sample = args.cpu_sample or (min(10_000, L // 2) if args.cpu_baseline_full else max(200, min(2000, L // 2)))   # default: ~10-30 s of host work at N = 5000
             st_np = states[: 2 * sample].cpu().numpy()
             cpu_base = cpu_baseline(st_np, hdw, r[: 2 * sample], uqe[: 2 * sample], N, sample)
@@ -1025,6 +1036,8 @@ def main():
                    stages_ms_per_step_overlapped={k: v / K for k, v in tim_overlapped.items()},
                    links=links_timed, counters=counters_timed, counters_replay=cnt_replay, hamming_weights_s=hamming_s,
                    hamming_gemm_ms=hamming_kernel_ms, roofline_hamming=roof_hamming, setup_s=setup_s)
+        if not args.full:   # (kernel-exclusive stage times and counters of the serialized replay, which has not run)
+            del out["stages_ms_per_step"], out["counters_replay"]
     # ---- N > 1, LAST: the short-range model behind the pass, table gathered / rows left on their ranks (sr_tail_leg).  Everything the line holds is
     # assembled by now, and a watchdog on every rank bounds the leg: its exchanges have only run under gloo and on ONE GPU under RCCL (tests/rccl_worker.py), and
     # a rank stuck in a collective must not cost the line of the timed region — after --sr-tail-timeout seconds rank 0 prints the line without the leg and
@@ -1068,7 +1081,7 @@ def main():
             os._exit(3 if args.strict_exit else 0)
         print_line_once()
     elif world > 1 and rank == 0:
-        out["sr_tail"] = dict(note="not run on this line (--no-extra-legs / --no-sr-tail-leg)")
+        out["sr_tail"] = dict(note="not run on this line (it runs under --full, unless --no-extra-legs / --no-sr-tail-leg)")
     if rank == 0 and not run_sr_tail:
         print(json.dumps(out), flush=True)
     eng.close()

@@ -1,5 +1,5 @@
 """GPU: bench.py under every switch combination that changes the code path (tools/flag_matrix.py) on a small workload: each
-run exits 0 and all runs report the same link counts — the switches change HOW the links are found, never WHICH.  The big
+run (`--full --no-extra-legs`: the timed steps + the serialized replay behind `roofline`) exits 0 and all runs report the same link counts — the switches change HOW the links are found, never WHICH.  The big
 shapes (85k x 616, 500k x 10k) run through the same script by hand; their records are kept under profiles/."""
 import os
 import sys
@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_flag_matrix_small():
-    out, bad, counts = flag_matrix.run_matrix("--L 12000 --N 1200 --steps 1 --warmup 1 --no-cpu-baseline --no-extra-legs", timeout=600, log=lambda *_: None)
+    out, bad, counts = flag_matrix.run_matrix("--L 12000 --N 1200 --steps 1 --warmup 1 --full --no-cpu-baseline --no-extra-legs", timeout=600, log=lambda *_: None)
     assert not bad, [(r["flags"], r.get("stderr_tail", "")[-600:]) for r in bad]
     assert len(counts) == 1 and all(c is not None and c > 0 for c in next(iter(counts))), counts
     assert len(out) == len(flag_matrix.COMBOS)
@@ -31,22 +31,33 @@ def _bench_line(cmd, timeout):
     return json.loads(lines[0])
 
 
+# what only `--full` puts on the line: the legs after the timed region, the figures of the serialized replay, the CPU baseline
+FULL_ONLY = ("warm_replay", "sustained", "mi_values_produced", "value_mi_produced", "ms_per_step_mi_produced", "roofline_mi_produced",
+             "first_pass_incl_allocations_ms", "job", "adversarial", "scaling_model", "cpu_baseline", "stages_ms_per_step", "counters_replay")
+
+
 def test_bench_multi_rank_rehearsal():
     """`python bench.py --gpus 4` (self-launching) = the command the driver's scaling run uses (torch.distributed.run, one rank per process, phased gather to rank 0), rehearsed on
     the ONE GPU of the test box with backend gloo: 4 ranks — the box's process guard allows at most 6 processes on its card, and the
     launcher and this pytest process may count among them (a 6-rank run was killed by it), so the 8-rank deal + gather is covered
     on the CPU instead (tests/test_dist_gloo.py::test_gather_gloo[8]).  Exit code 0, link counts
-    identical to the 1-rank line, and the per-rank record the N > 1 line carries (compute / exposed gather / bytes sent)."""
+    identical to the 1-rank line, and the per-rank record the N > 1 line carries (compute / exposed gather / bytes sent).
+    The 1-rank line is a plain run (no `--full`, no switch that trims a leg): the headline fields and nothing that takes a run of its own."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = ["--steps", "1", "--warmup", "1", "--no-extra-legs", "--no-cpu-baseline", "--L", "40000", "--N", "2000", "--max-blk-sz", "5000"]
+    base = ["--steps", "1", "--warmup", "1", "--L", "40000", "--N", "2000", "--max-blk-sz", "5000"]
     one = _bench_line([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + base, 600)
+    assert not [k for k in FULL_ONLY if k in one], sorted(one)
+    assert (one["metric"], one["unit"], one["higher_is_better"], one["dtype"]) == ("MI SNP-pairs/sec", "pairs/s", True, "i8")
+    assert one["steps"] == 1 and one["ms_per_step"] > 0 and abs(one["value"] * one["ms_per_step"] * 1e-3 / one["config"]["pairs"] - 1) < 1e-9
+    assert "kernel" not in one["roofline"] and one["roofline"]["hbm_alg_GBps_whole_step"] > 0
+    base = ["--full", "--no-cpu-baseline"] + base
     world = 4
     # r04: no launcher around it — `python bench.py --gpus 4` starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node 4
     # --master-addr 127.0.0.1 --master-port P bench.py <same arguments>` itself (a child process, before this one touches the GPU),
     # relays rank 0's line and the exit code
-    # (the 4-rank line runs its extra leg: `sr_tail`, the short-range model + ARACNE behind the pass with the table gathered / the rows left on their ranks)
+    # (`--full`: the 4-rank line runs its extra leg: `sr_tail`, the short-range model + ARACNE behind the pass with the table gathered / the rows left on their ranks)
     # (--min-blocks-per-phase 3: the rehearsal keeps the three-phase gather in it — at 9 block pairs per rank the default, 12, would run one phase)
-    many = _bench_line([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--min-blocks-per-phase", "3"] + [a for a in base if a != "--no-extra-legs"], 900)
+    many = _bench_line([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--min-blocks-per-phase", "3"] + base, 900)
     assert many["ranks_seen"] == world and many["backend"] == "gloo" and many["self_launched"] is True
     assert one["ranks_seen"] == 1 and one["self_launched"] is False
     assert many["n_gpus"] == world and one["n_gpus"] == 1
@@ -64,7 +75,7 @@ def test_bench_multi_rank_rehearsal():
     assert tail["max_bytes_sent_per_peer"]["dist"] < 0.4 * tail["max_bytes_sent_per_peer"]["gather"], tail["max_bytes_sent_per_peer"]
     assert all(r["candidates"] < 0.25 * r["sr_rows"] for r in tail["per_rank"] if r["sr_rows"] > 0)
     # ... and the leg can never cost the line: with a watchdog of 50 ms every rank abandons it, rank 0 prints the line without it, exit code 0
-    cut = _bench_line([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--sr-tail-timeout", "0.05"] + [a for a in base if a != "--no-extra-legs"], 600)
+    cut = _bench_line([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--sr-tail-timeout", "0.05"] + base, 600)
     assert cut["n_gpus"] == 2 and cut["links"] == one["links"] and "abandoned" in cut["sr_tail"]["note"]
     sent = sum(r["bytes_sent"] for r in pr)
     assert sent <= 8 * one["links"]["n_sr"] + 16 * one["links"]["n_lr"]
@@ -100,11 +111,11 @@ def test_bench_dump_outputs(tmp_path):
 
 
 def test_bench_line_carries_roofline_hamming_and_the_scaling_model():
-    """r06: `roofline_hamming` (the Hamming stage priced: its GEMM against the int8 peak on executed operations, the kernels around it against HBM, the
+    """r06, under `--full`: `roofline_hamming` (the Hamming stage priced: its GEMM against the int8 peak on executed operations, the kernels around it against HBM, the
     rest of the call as host time) and `scaling_model` (every share of the N = 1, 2, 4, 8 deals run alone on this GPU + a modelled gather; marked as a model)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     d = _bench_line([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--L", "30000", "--N", "1500", "--max-blk-sz", "5000", "--steps", "2", "--warmup", "1",
-                     "--no-cpu-baseline", "--no-adversarial", "--no-job", "--sustain-s", "0"], 600)
+                     "--full", "--no-cpu-baseline", "--no-adversarial", "--no-job", "--sustain-s", "0"], 600)
     rh = d["roofline_hamming"]
     assert rh["columns"] > 30000 and 0 < rh["gemm"]["frac"] < 1 and rh["gemm"]["executed_ops"] > 0 and rh["gemm"]["bound"] == "mfma"
     assert rh["pre"]["bound"] == "hbm" and 0 < rh["pre"]["frac"] < 1 and 0 < rh["post"]["frac"] < 1

@@ -278,6 +278,20 @@ def test_bench_gpus_n_launches_n_ranks_itself():
         assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_full_option_is_off_by_default():
+    """`bench.py --full` exists (everything but the set-up, the warm-up and timed steps and the line sits behind it) and a plain run does not
+    set it.  No GPU: `parse` is all that runs."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys, runpy; m = runpy.run_path(sys.argv[1]); sys.argv[1:] = sys.argv[2:]; a = m['parse'](); "
+            "print(int(a.full), a.gpus, a.steps, a.warmup)")
+    for extra, want in (([], "0 1 7 2"), (["--full"], "1 1 7 2")):
+        p = subprocess.run([sys.executable, "-c", code, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2"] + extra,
+                           capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0 and p.stdout.split("\n")[-2] == want, (p.stdout[-500:], p.stderr[-1500:])
+
+
 def test_positions_to_snp_index_any_order():
     """lr.analyse_long_range_links maps the positions of sr_links.tsv back to SNP indices with POS in any order."""
     from ldweaver_amd.lr import positions_to_snp_index

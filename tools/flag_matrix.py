@@ -2,7 +2,7 @@
 """bench.py under every switch combination that changes the code path: each run must exit 0 and all runs of one
 workload must report the same link counts (the switches change HOW the links are found, never WHICH).
 
-    python tools/flag_matrix.py [--L 30000] [--N 2000] [--extra "--L 85000 --N 616"] [--out gpurun_out/flags.json]
+    python tools/flag_matrix.py [--only 0,3] [--base "--L 85000 --N 616 --steps 2 --full --no-cpu-baseline --no-extra-legs"] [--out flags.json]
 
 Used by tests/test_bench_flags.py (small workload) and by hand for the big shapes (C3-like 85k x 616, C5 500k x 10k).
 """
@@ -60,7 +60,8 @@ def run_matrix(base: str, combos=COMBOS, timeout: int = 900, log=print):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--base", default="--L 30000 --N 2000 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs")
+    ap.add_argument("--base", default="--L 30000 --N 2000 --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra-legs",
+                    help="arguments of every run (--full --no-extra-legs: the timed steps and the serialized replay behind `roofline`, no other leg)")
     ap.add_argument("--only", default=None, help="comma-separated indices into the combination list")
     ap.add_argument("--out", default=None)
     ap.add_argument("--timeout", type=int, default=900)

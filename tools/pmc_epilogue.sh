@@ -18,7 +18,7 @@ for k, e in d.items():
     e["derived"] = dict(valu_issue_frac=e["SQ_INSTS_VALU"] / cu, valu_busy_frac=e["SQ_ACTIVE_INST_VALU"] / cu, salu_per_valu=e["SQ_INSTS_SALU"] / e["SQ_INSTS_VALU"],
                         lanes_active_per_valu=e.get("SQ_THREAD_CYCLES_VALU", 0) / e["SQ_INSTS_VALU"], wait_inst_any_frac=e["SQ_WAIT_INST_ANY"] / e["SQ_WAVE_CYCLES"],
                         wait_any_frac=e.get("SQ_WAIT_ANY", 0) / e["SQ_WAVE_CYCLES"], waves=e["SQ_WAVES"], cu_busy_ms_at_2p4GHz=cu / 256 / 2.4e9 * 1e3)
-d["_how"] = "tools/pmc_epilogue.sh: per-launch averages, bench.py --steps 1 --warmup 1 --no-overlap --no-mixed --screen 0 --path 1 (C4), two --pmc passes"
+d["_how"] = "tools/pmc_epilogue.sh: per-launch averages, bench.py --steps 1 --warmup 1 --full --no-extra-legs --no-overlap --no-mixed --screen 0 --path 1 (C4), two --pmc passes"
 json.dump(d, open(sys.argv[1], "w"), indent=1)
 for k, e in d.items():
     if isinstance(e, dict) and "derived" in e:

@@ -1,19 +1,22 @@
 #!/bin/bash
 # PMC counter sets (one rocprofv3 pass each: --pmc with --kernel-trace only) of the kernels matching a regex over a short serial bench run.
+# (--full --no-extra-legs: the timed step and the serialized replay behind `roofline`, in which every block launches the dominant kernel)
 # usage (GPU box): tools/pmc_run.sh <regex> <out.json> "<bench args>" "<counters of pass 1>" ["<counters of pass 2>" ...]
 pat=$1; out=$2; bargs=$3; shift 3
+root=$(cd "$(dirname "$0")/.." && pwd)
+work=$(mktemp -d)   # the passes' raw counter files: read below, then removed
 cd /tmp && export TMPDIR=/tmp
 i=0
 for set in "$@"; do
   i=$((i+1))
-  rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$GRAFT_REPO_ROOT/gpurun_out/pmc_r$i" -o p -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-overlap --no-extra-legs $bargs > "$GRAFT_REPO_ROOT/gpurun_out/pmc_r$i.log" 2>&1 || { echo "pass $i failed"; tail -3 "$GRAFT_REPO_ROOT/gpurun_out/pmc_r$i.log"; }
+  rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$work/pmc_r$i" -o p -- python3 "$root/bench.py" --steps 1 --warmup 1 --full --no-cpu-baseline --no-overlap --no-extra-legs $bargs > "$work/pmc_r$i.log" 2>&1 || { echo "pass $i failed"; tail -3 "$work/pmc_r$i.log"; }
 done
-cd "$GRAFT_REPO_ROOT"
-python3 - "$pat" "$out" <<'PY'
+cd "$root"
+python3 - "$pat" "$out" "$work" <<'PY'
 import csv, glob, collections, json, re, sys
-pat, out = sys.argv[1], sys.argv[2]
+pat, out, work = sys.argv[1], sys.argv[2], sys.argv[3]
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
-for f in glob.glob("gpurun_out/pmc_r*/**/*counter_collection.csv", recursive=True):
+for f in glob.glob(work + "/pmc_r*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         if re.search(pat, r["Kernel_Name"]):
             key = re.sub(r"\(.*", "", r["Kernel_Name"])[:90]
@@ -23,4 +26,4 @@ json.dump(res, open(out, "w"), indent=1)
 for k, d in res.items():
     print(k); print("   ", {c: round(v) for c, v in sorted(d.items())})
 PY
-rm -rf gpurun_out/pmc_r[0-9]*
+rm -rf "$work"

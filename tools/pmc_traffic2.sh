@@ -2,17 +2,18 @@
 # HBM traffic per launch of every ldw:: kernel from PMC counters, as MI355X_MICROARCH.md prescribes: separate --pmc passes
 # (FETCH_SIZE, WRITE_SIZE), kernel-trace only.   usage (on the GPU box): tools/pmc_traffic2.sh <out.json> <bench args...>
 out=$1; shift
+root=$(cd "$(dirname "$0")/.." && pwd)
+work=$(mktemp -d)   # the passes' raw counter files: read below, then removed
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf "$GRAFT_REPO_ROOT/gpurun_out/pmc_$c"
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$GRAFT_REPO_ROOT/gpurun_out/pmc_$c" -o p -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --no-extra-legs "$@" > "$GRAFT_REPO_ROOT/gpurun_out/pmc_$c.log" 2>&1 || { echo "pmc pass $c failed"; tail -5 "$GRAFT_REPO_ROOT/gpurun_out/pmc_$c.log"; exit 1; }
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$work/pmc_$c" -o p -- python3 "$root/bench.py" --full --no-cpu-baseline --no-extra-legs "$@" > "$work/pmc_$c.log" 2>&1 || { echo "pmc pass $c failed"; tail -5 "$work/pmc_$c.log"; exit 1; }
 done
-cd "$GRAFT_REPO_ROOT"
-python3 - "$out" "$*" <<'PY'
+cd "$root"
+python3 - "$out" "$*" "$work" <<'PY'
 import csv, glob, collections, json, re, sys
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    for f in glob.glob(f"gpurun_out/pmc_{c}/**/*counter_collection.csv", recursive=True):
+    for f in glob.glob(f"{sys.argv[3]}/pmc_{c}/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
             m = re.search(r"ldw::(\w+(?:<[^>]*>)?)", r["Kernel_Name"])
             if m and r["Counter_Name"] == c:
@@ -33,9 +34,9 @@ for k, d in sorted(agg.items()):
                    "reads narrower than 16 B per lane / gathered: uncalibrated on gfx950 — true bytes lie in hbm_bytes_per_launch_range; "
                    "hbm_bytes_per_launch is its upper end"))
     res[k] = e
-res["_how"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE (one pass) and --pmc WRITE_SIZE (another pass) -- python3 bench.py --no-cpu-baseline "
+res["_how"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE (one pass) and --pmc WRITE_SIZE (another pass) -- python3 bench.py --full --no-cpu-baseline "
                "--no-extra-legs " + sys.argv[2] + "; means over all launches of each kernel (warm-up, timed and replay steps alike)")
 json.dump(res, open(sys.argv[1], "w"), indent=1)
 print(json.dumps({k: {kk: vv for kk, vv in v.items() if kk in ("launches", "FETCH_SIZE_KB_mean_per_launch", "WRITE_SIZE_KB_mean_per_launch")} for k, v in res.items() if k != "_how"}, indent=0))
 PY
-rm -rf gpurun_out/pmc_FETCH_SIZE gpurun_out/pmc_WRITE_SIZE
+rm -rf "$work"

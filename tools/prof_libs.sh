@@ -5,7 +5,7 @@ pat=$1; libs=$2; shift 2
 for lib in $libs; do
   export LDW_AMD_LIB="$GRAFT_REPO_ROOT/$lib"
   tag=$(basename "$lib" .so)
-  bash "$GRAFT_REPO_ROOT/tools/prof_run.sh" "plib_$tag" --steps 4 --warmup 2 --no-cpu-baseline --no-extra-legs --no-overlap "$@" > /dev/null 2>&1
+  bash "$(dirname "$0")/prof_run.sh" "plib_$tag" --steps 4 --warmup 2 --full --no-cpu-baseline --no-extra-legs --no-overlap "$@" > /dev/null 2>&1
   echo "== $lib"
   python3 - "$pat" "$GRAFT_REPO_ROOT/gpurun_out/plib_${tag}_kernel_stats.csv" <<'PY'
 import re, sys
