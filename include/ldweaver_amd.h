@@ -645,6 +645,32 @@ int ldw_links_grep(ldw_ctx *ctx, const char *path, const uint8_t *needles, const
 int ldw_links_grep_fetch(ldw_ctx *ctx, int64_t capacity, int64_t text_capacity, int64_t *row_out, double *num_out, uint64_t *mask_out, uint8_t *text_out,
                          int64_t *text_off_out);
 
+/* ---- (15) the tree view — view_tree (R/preptrees.R): a tree over bands of alleles and metadata, rendered on the device ----------------------
+ * The tree is a list of BARS: axis-aligned, half-open rectangles [x0, x1) x [y0, y1) in 1/16 pixel relative to the panel's top-left corner, x1 > x0 and
+ * y1 > y0, one per branch and one per connector.  A bar adds to every panel pixel its overlap area with that pixel in units of 1/256 pixel (0..256); a
+ * pixel's ink is min(sum, 256) and every channel (255 (256 - ink) + colour ink + 128) >> 8 over white.  Bars are clipped to the panel.  The sums are
+ * integers: the picture does not depend on the order of the bars or of the adds.
+ * The BANDS: levels[n_bands][n_tips] (uint8), band r drawn into band_rect[4 r ..] = x, y, w, h (canvas pixels) with the colours palette[256 r + level]
+ * (0xRRGGBB).  In units where tip i spans [i w, (i + 1) w) and pixel column p spans [p n_tips, (p + 1) n_tips), the overlaps ov of a column with the tips
+ * sum to n_tips and every channel is (sum of ov c[level] + n_tips / 2) / n_tips in 64-bit integers; all rows of a band repeat that line.
+ * Limits (LDW_ERR_ARG beyond them, before anything runs on the device): at most 2^23 bars (checked first), coordinates within +-2^20; canvas 1..8192 each
+ * way; the panel and every band non-empty and inside the canvas, no band overlapping the panel or another band; at most 1024 bands, 2^24 tips and 2^31
+ * levels in all. */
+typedef struct ldw_bar {
+    int32_t x0, y0, x1, y1;
+} ldw_bar;
+/* The figure: a white canvas W x H, the bars in bar_rgb inside panel = x, y, w, h, the bands; then, by the host in the 5 x 7 font at text_scale (1..64):
+ * band_label[r] (may be NULL, entries may be NULL or empty) right-aligned 2 text_scale pixels left of band r and centred on its height; title (may be NULL)
+ * centred at the top; two legends, legend k with its top-left corner at legend_xy[2 k], legend_xy[2 k + 1]: legend_title[k] over legend_n[k] (0..256; 0: no
+ * legend) rows of a square swatch and a label, the entries of legend 1 following those of legend 0 in legend_label / legend_rgb.  The figure goes to
+ * png_path (may be NULL) and / or rgb_out (may be NULL: H x W x 3 bytes).  boxes_out (may be NULL, (n_bands + 3) x 4 int32): x, y, w, h of what the host
+ * drew — the band labels, the title, the two legends (w = 0: none); a box may reach past the canvas.  The host does not keep its text off the panel or the
+ * bands: the caller's layout does. */
+int ldw_plot_tree(ldw_ctx *ctx, int32_t W, int32_t H, const int32_t *panel, const ldw_bar *bars, int64_t n_bars, uint32_t bar_rgb, const uint8_t *levels,
+                  int64_t n_tips, const uint32_t *palette, const int32_t *band_rect, int32_t n_bands, const char *const *band_label, const char *title,
+                  const char *const *legend_title, const int32_t *legend_n, const char *const *legend_label, const uint32_t *legend_rgb,
+                  const int32_t *legend_xy, int32_t text_scale, const char *png_path, uint8_t *rgb_out, int32_t *boxes_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

@@ -52,4 +52,9 @@ void plot_frame(uint8_t *canvas, const ldw_plot_layout &lay, int kind, const uin
 void plot_net_overlay(uint8_t *canvas, int W, int H, const int32_t *node_xy, const char *const *node_names, int n_nodes, const char *title,
                       const int32_t *legend_value, const uint32_t *legend_rgb, int n_legend, int scale, int32_t *boxes);
 
+// the tree view's band labels, title and two legends over the device canvas[H][W][3] (ldw_plot_tree.hip); boxes (may be NULL): (n_bands + 3) x 4
+void plot_tree_overlay(uint8_t *canvas, int W, int H, const int32_t *band_rect, const char *const *band_label, int n_bands, const char *title,
+                       const char *const *legend_title, const int32_t *legend_n, const char *const *legend_label, const uint32_t *legend_rgb,
+                       const int32_t *legend_xy, int scale, int32_t *boxes);
+
 }  // namespace ldw

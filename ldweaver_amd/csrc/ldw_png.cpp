@@ -276,6 +276,63 @@ void plot_net_overlay(uint8_t *canvas, int W, int H, const int32_t *node_xy, con
     }
 }
 
+// The tree view's text over the device canvas (ldw_plot_tree.hip): left of every band its label, right-aligned 2 scale pixels before the band and
+// centred on its height; the title centred at the top; two legends, each its title over one square swatch and label per entry, with the top-left
+// corner at legend_xy[2 k], legend_xy[2 k + 1] (entries of legend 1 follow those of legend 0 in legend_label / legend_rgb).  boxes (may be NULL):
+// x, y, w, h of the band labels in band order, then of the title and of the two legends (w = 0: not drawn); a box may reach past the canvas.
+void plot_tree_overlay(uint8_t *canvas, int W, int H, const int32_t *band_rect, const char *const *band_label, int n_bands, const char *title,
+                       const char *const *legend_title, const int32_t *legend_n, const char *const *legend_label, const uint32_t *legend_rgb,
+                       const int32_t *legend_xy, int sc, int32_t *boxes) {
+    Canvas cv{canvas, W, H};
+    const int th = 7 * sc, gap = 2 * sc;
+    auto note = [&](int k, int x, int y, int w, int h) {
+        if (!boxes) return;
+        boxes[4 * k] = x;
+        boxes[4 * k + 1] = y;
+        boxes[4 * k + 2] = w;
+        boxes[4 * k + 3] = h;
+    };
+    for (int r = 0; r < n_bands; ++r) {
+        const char *s = band_label ? band_label[r] : nullptr;
+        if (!s || !s[0]) {
+            note(r, 0, 0, 0, 0);
+            continue;
+        }
+        const int tw = text_width(s, sc);
+        const int x = band_rect[4 * r] - gap - tw, y = band_rect[4 * r + 1] + (band_rect[4 * r + 3] - th) / 2;
+        draw_text(cv, x, y, s, sc, PLOT_TEXT);
+        note(r, x, y, tw, th);
+    }
+    if (title && title[0]) {
+        const int st = sc + sc / 2, tw = text_width(title, st);
+        const int x = (W - tw) / 2, y = 2 * sc;
+        draw_text(cv, x, y, title, st, PLOT_TITLE);
+        note(n_bands, x, y, tw, 7 * st);
+    } else {
+        note(n_bands, 0, 0, 0, 0);
+    }
+    int first = 0;
+    for (int k = 0; k < 2; ++k) {
+        const int n = legend_n[k];
+        if (n <= 0) {
+            note(n_bands + 1 + k, 0, 0, 0, 0);
+            continue;
+        }
+        const char *name = legend_title[k] ? legend_title[k] : "";
+        const int x = legend_xy[2 * k], y = legend_xy[2 * k + 1];
+        int w = text_width(name, sc);
+        draw_text(cv, x, y, name, sc, PLOT_TITLE);
+        for (int j = 0; j < n; ++j) {
+            const int yj = y + (j + 1) * (th + gap);
+            cv.rect(x, yj, th, th, legend_rgb[first + j]);
+            draw_text(cv, x + th + gap, yj, legend_label[first + j], sc, PLOT_TEXT);
+            w = std::max(w, th + gap + text_width(legend_label[first + j], sc));
+        }
+        note(n_bands + 1 + k, x, y, w, (n + 1) * (th + gap) - gap);
+        first += n;
+    }
+}
+
 }  // namespace ldw
 
 using namespace ldw;

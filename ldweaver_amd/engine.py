@@ -708,6 +708,63 @@ class Engine:
                                          os.fsencode(png_path) if png_path is not None else None, L.ptr(canvas), L.ptr(boxes)))
         return canvas, boxes
 
+    # -- the tree view (include/ldweaver_amd.h 15) ------------------------------------
+    BAR = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4")])
+
+    def _tree_args(self, W, H, panel, bars, bar_rgb, levels, palette, band_rect):
+        bars = np.ascontiguousarray(bars, dtype=self.BAR)
+        panel = np.ascontiguousarray(panel, dtype=np.int32).reshape(4)
+        rect = np.ascontiguousarray(band_rect if band_rect is not None else np.zeros((0, 4)), dtype=np.int32).reshape(-1, 4)
+        R = len(rect)
+        lev = np.ascontiguousarray(levels if levels is not None else np.zeros((0, 1)), dtype=np.uint8).reshape(R, -1) if R else np.zeros((0, 0), dtype=np.uint8)
+        pal = np.ascontiguousarray(palette if palette is not None else np.zeros((0, 256)), dtype=np.uint32).reshape(R, 256) if R else np.zeros((0, 256), dtype=np.uint32)
+        keep = (bars, panel, rect, lev, pal)
+        args = (int(W), int(H), L.ptr(panel), L.ptr(bars) if len(bars) else None, len(bars), int(bar_rgb), L.ptr(lev) if R else None, lev.shape[1] if R else 0,
+                L.ptr(pal) if R else None, L.ptr(rect) if R else None, R)
+        return keep, args
+
+    def plot_tree_raster(self, W: int, H: int, panel, bars, bar_rgb: int = 0, levels=None, palette=None, band_rect=None, timings: bool = False):
+        """The raw canvas of the tree view (ldw_debug_plot_tree): uint8 [H, W, 3]: white, the bars (structured ``Engine.BAR`` array, 1/16 pixel relative
+        to ``panel`` = x, y, w, h) and the bands (``levels`` uint8 [bands, tips], ``palette`` uint32 [bands, 256], ``band_rect`` int32 [bands, 4]);
+        with ``timings`` also (clear, bars, bands, colour) in ms."""
+        keep, args = self._tree_args(W, H, panel, bars, bar_rgb, levels, palette, band_rect)
+        out = np.empty((int(H), int(W), 3), dtype=np.uint8)
+        ms = np.zeros(4)
+        L.check(L.lib().ldw_debug_plot_tree(self._ctx, *args, L.ptr(out), L.ptr(ms) if timings else None))
+        return (out, tuple(ms)) if timings else out
+
+    def plot_tree(self, W: int, H: int, panel, bars, bar_rgb: int = 0, levels=None, palette=None, band_rect=None, band_labels=None, title=None, legends=(),
+                  text_scale: int = 1, png_path=None, want_canvas: bool = False):
+        """The tree figure (ldw_plot_tree).  ``legends``: up to two of (title, labels, colours 0xRRGGBB, (x, y)).  Returns (canvas uint8 [H, W, 3] or
+        None, boxes int32 [bands + 3, 4]: the band labels, the title, the two legends)."""
+        keep, args = self._tree_args(W, H, panel, bars, bar_rgb, levels, palette, band_rect)
+        R = args[-1]
+
+        def enc(s):
+            return s.encode("utf-8", "replace") if isinstance(s, str) else bytes(s)
+
+        labels = [enc(s) for s in (band_labels if band_labels is not None else [""] * R)]
+        if len(labels) != R:
+            raise ValueError(f"{len(labels)} band labels for {R} bands")
+        lab_arr = (C.c_char_p * max(R, 1))(*labels)
+        legends = list(legends) + [("", [], [], (0, 0))] * (2 - len(legends))
+        if len(legends) != 2:
+            raise ValueError("at most two legends")
+        lt = (C.c_char_p * 2)(*[enc(g[0]) for g in legends])
+        ln = np.asarray([len(g[1]) for g in legends], dtype=np.int32)
+        entries = [enc(s) for g in legends for s in g[1]]
+        le = (C.c_char_p * max(len(entries), 1))(*entries)
+        lc = np.ascontiguousarray([int(v) for g in legends for v in g[2]], dtype=np.uint32)
+        if len(lc) != len(entries):
+            raise ValueError("a legend needs one colour per label")
+        lxy = np.ascontiguousarray([v for g in legends for v in g[3]], dtype=np.int32).reshape(4)
+        boxes = np.zeros((R + 3, 4), dtype=np.int32)
+        canvas = np.empty((int(H), int(W), 3), dtype=np.uint8) if want_canvas else None
+        L.check(L.lib().ldw_plot_tree(self._ctx, *args, C.cast(lab_arr, C.c_void_p) if R else None, enc(title or ""), C.cast(lt, C.c_void_p), L.ptr(ln),
+                                      C.cast(le, C.c_void_p) if entries else None, L.ptr(lc) if entries else None, L.ptr(lxy), int(text_scale),
+                                      os.fsencode(png_path) if png_path is not None else None, L.ptr(canvas), L.ptr(boxes)))
+        return canvas, boxes
+
     def set_positions(self, POS, g: float = 0.0):
         """Positions for an engine WITHOUT an alignment (ldw_set_positions): enough for links_load / links_import, ldmap, lr_tukey, lr_reduced,
         aracne_device and the long-range figure; g = 0: genome length not known."""
