@@ -253,6 +253,34 @@ void DevBuf::release() {
     cap = 0;
 }
 
+int PinnedPair::reserve(size_t bytes, const char *who) {
+    if (bytes <= cap) return LDW_OK;
+    release();
+    for (auto &q : p)
+        if (hipHostMalloc(&q, bytes, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();   // (the error is sticky; the slot may hold anything)
+            q = nullptr;
+            release();
+            set_error("%s: hipHostMalloc of %zu bytes failed", who, bytes);
+            return LDW_ERR_HIP;
+        }
+    cap = bytes;
+    return LDW_OK;
+}
+
+int64_t PinnedPair::release() {
+    int64_t n = 0;
+    for (auto &q : p) {
+        if (q) {
+            (void)hipHostFree(q);
+            n += (int64_t)cap;
+        }
+        q = nullptr;
+    }
+    cap = 0;
+    return n;
+}
+
 int check_gpu(ldw_ctx *ctx) {
     LDW_REQUIRE(ctx != nullptr, LDW_ERR_ARG, "null context");
     LDW_HIP(hipSetDevice(ctx->device));

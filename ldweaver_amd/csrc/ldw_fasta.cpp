@@ -206,8 +206,7 @@ struct FastaScan {
     DevBuf counts;                     // int32 [Lp][5] (the first L columns are the file's)
     DevBuf packed;                     // uint8 [N][Lp / 2]: 4-bit states, while `kept`
     bool kept = false;
-    void *pin[2] = {nullptr, nullptr}; // pinned chunks [rows][Lp]
-    size_t pin_cap = 0;
+    PinnedPair pin;                    // pinned chunks [rows][Lp]
     DevBuf dchunk[2];                  // their device images
     hipEvent_t ev[2] = {nullptr, nullptr};   // recorded after the copy of a chunk out of pin[k] (and the kernel behind it)
     bool ev_live[2] = {false, false};
@@ -218,19 +217,14 @@ static FastaScan *scan_state(ldw_ctx *c) {
     return static_cast<FastaScan *>(c->fasta);
 }
 
-static int64_t free_pins(FastaScan *f) {
-    int64_t n = 0;
+// the chunk ring goes: the pinned pair and its device images; bytes released
+static int64_t free_chunks(FastaScan *f) {
+    int64_t n = f->pin.release();
     for (int k = 0; k < 2; ++k) {
-        if (f->pin[k]) {
-            (void)hipHostFree(f->pin[k]);
-            n += (int64_t)f->pin_cap;
-        }
-        f->pin[k] = nullptr;
         n += (int64_t)f->dchunk[k].cap;
         f->dchunk[k].release();
         f->ev_live[k] = false;
     }
-    f->pin_cap = 0;
     return n;
 }
 
@@ -238,7 +232,7 @@ void fasta_release(ldw_ctx *c) {
     auto *f = static_cast<FastaScan *>(c->fasta);
     if (!f) return;
     (void)hipStreamSynchronize(c->stream);
-    free_pins(f);
+    free_chunks(f);
     f->counts.release();
     f->packed.release();
     for (auto &e : f->ev)
@@ -252,25 +246,14 @@ int64_t fasta_trim(ldw_ctx *c) {
     if (!f) return 0;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    return free_pins(f);
+    return free_chunks(f);
 }
 
 // two pinned chunks of `bytes` each and their device images; events once
-static int ensure_pins(FastaScan *f, size_t bytes) {
+static int ensure_chunks(FastaScan *f, size_t bytes) {
     for (auto &e : f->ev)
         if (!e) LDW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (f->pin_cap < bytes) {
-        free_pins(f);
-        for (int k = 0; k < 2; ++k)
-            if (hipHostMalloc(&f->pin[k], bytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                f->pin[k] = nullptr;
-                free_pins(f);
-                set_error("ldw_fasta: hipHostMalloc of %zu bytes failed", bytes);
-                return LDW_ERR_HIP;
-            }
-        f->pin_cap = bytes;
-    }
+    if (int rc = f->pin.reserve(bytes, "ldw_fasta")) return rc;
     for (int k = 0; k < 2; ++k)
         if (int rc = f->dchunk[k].reserve(bytes)) return rc;
     return LDW_OK;
@@ -284,7 +267,7 @@ static int wait_chunk(FastaScan *f, int k) {
 }
 
 static int upload_chunk(ldw_ctx *c, FastaScan *f, int k, int64_t rows) {
-    LDW_HIP(hipMemcpyAsync(f->dchunk[k].p, f->pin[k], (size_t)(rows * f->Lp), hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(f->dchunk[k].p, f->pin.p[k], (size_t)(rows * f->Lp), hipMemcpyHostToDevice, c->stream));
     return LDW_OK;
 }
 
@@ -296,7 +279,7 @@ static int chunk_done(ldw_ctx *c, FastaScan *f, int k) {
 
 // the row r of pin[k]: its padding bytes L .. Lp are zeroed (the kernels read whole 16-byte groups)
 static inline char *pin_row(FastaScan *f, int k, int64_t r) {
-    char *row = static_cast<char *>(f->pin[k]) + r * f->Lp;
+    char *row = static_cast<char *>(f->pin.p[k]) + r * f->Lp;
     if (f->Lp > f->L) memset(row + f->L, 0, (size_t)(f->Lp - f->L));
     return row;
 }
@@ -355,7 +338,7 @@ int ldw_fasta_scan(ldw_ctx *c, const char *path, int64_t chunk_rows, int64_t io_
     }
     const int64_t L = len, Lp = (L + 15) / 16 * 16;
     const int64_t rows = chunk_rows > 0 ? chunk_rows : std::max<int64_t>(1, CHUNK_BYTES / L);
-    if (int rc = ensure_pins(f, (size_t)(rows * Lp))) return rc;
+    if (int rc = ensure_chunks(f, (size_t)(rows * Lp))) return rc;
     if (int rc = f->counts.reserve((size_t)Lp * 20)) return rc;
     LDW_HIP(hipMemsetAsync(f->counts.p, 0, (size_t)Lp * 20, c->stream));
     int64_t budget = keep_bytes;   // bytes the packed copy may take
@@ -488,7 +471,7 @@ int ldw_fasta_encode(ldw_ctx *c, const int32_t *pos, int64_t n_pos, int32_t *acg
         FastaReader rd;
         if (int rc = rd.open(f->path.c_str(), f->io_bytes)) return fail(rc);
         const int64_t rows = f->chunk_rows;
-        if (int rc = ensure_pins(f, (size_t)(rows * Lp))) return fail(rc);
+        if (int rc = ensure_chunks(f, (size_t)(rows * Lp))) return fail(rc);
         std::string nm;
         int64_t len = 0, s0 = 0;
         for (int k = 0; s0 < N; k ^= 1) {

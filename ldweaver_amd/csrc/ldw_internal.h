@@ -48,6 +48,14 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// two pinned host buffers of one size, grow-only: the double buffer of a streaming stage (FASTA feeder, alignment writer, text-file pass)
+struct PinnedPair {
+    void *p[2] = {nullptr, nullptr};
+    size_t cap = 0;                               // bytes of each
+    int reserve(size_t bytes, const char *who);   // contents NOT preserved on growth; LDW_ERR_HIP "<who>: hipHostMalloc of <bytes> bytes failed" leaves no buffer
+    int64_t release();                            // bytes freed; nothing may still be copying to or from the buffers
+};
+
 constexpr int TILE = 128;     // GEMM block tile (rows on both sides)
 constexpr int KSTEP = 128;    // bytes of K (sequences) per pipeline stage
 constexpr int NBINS = 4096;   // level-1 histogram bins of the lr quantile search

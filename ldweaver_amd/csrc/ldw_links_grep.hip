@@ -1,6 +1,6 @@
 // The search of annotated link files on the device (include/ldweaver_amd.h 14): grep(gene, pos1_ann / pos2_ann) of
 // create_network_for_gene (R/createNetworkPlot.R:180, :196, :244, :259) over sr_links_annotated.tsv / lr_links_annotated.tsv, with literal needles.
-// The file goes through the reader's chunk plumbing (TsvFeeder, its pinned double buffer and '\n' padding, k_tsv_count / k_tsv_starts: ldw_links_read.h);
+// The file goes through the reader's chunk pass (TsvPass: the feeder, the pinned double buffer and its '\n' padding, k_tsv_count / k_tsv_starts: ldw_links_read.h);
 // k_links_grep then gives every row to one wave: the lanes find the row's tabs by ballots, five of them parse the numeric cells (ldw_tsv_cell.h), all of
 // them walk the text positions of the two annotation fields against the needles, bucketed by first byte in LDS, and a kept row is appended by one atomic.
 // The host queues a chunk's search, reads the next chunk meanwhile, then sorts the few kept rows of the chunk back into file order and cuts their three
@@ -30,7 +30,6 @@ constexpr int GREP_BLOCK = 256, GREP_WAVES = GREP_BLOCK / 64;
 constexpr int GREP_MAX_NEEDLES = 1024, GREP_MAX_WORDS = GREP_MAX_NEEDLES / 64, GREP_MAX_LEN = 255;
 constexpr uint32_t GREP_FIRST_RECORDS = 16384;   // records a chunk gets room for at first; a chunk that keeps more rows is searched again with room for all
 constexpr int GREP_NUM = 5, GREP_STR = 3;   // pos1 pos2 len ARACNE MI; pos1_ann pos2_ann links
-enum { BAD_CELL = 1, BAD_MISSING = 2, BAD_EXTRA = 3, BAD_LONG = 4 };   // as the reader's
 
 struct GrepResult {   // what a chunk's kernel reports
     unsigned long long bad;   // min over the refused rows of row << 16 | column (1-based) << 8 | reason; ~0: none
@@ -210,7 +209,7 @@ __global__ void k_grep_init(GrepResult *res) {
 struct GrepState {
     DevBuf tables, work;                 // the needle tables and the result word; a chunk's records and mask words
     GrepResult *pin_res = nullptr;       // pinned twin of the result word
-    hipEvent_t ev[5] = {};               // before / after the copy, after the line kernels, after the search kernel, before k_tsv_starts
+    hipEvent_t ev[2] = {};               // before k_tsv_starts, after the search kernel
     // the last result (host)
     int nw = 0;
     std::vector<int64_t> row;
@@ -229,18 +228,6 @@ GrepState *grep_state(ldw_ctx *c) {
 }
 
 const char *const GREP_NAMES[GREP_NUM + GREP_STR] = {"pos1", "pos2", "len", "ARACNE", "MI", "pos1_ann", "pos2_ann", "links"};
-
-int refuse_row(const char *path, int64_t row, uint32_t col, uint32_t reason, int ncols) {
-    int64_t line = 0;
-    (void)tsv_line_of_row(path, row, &line);
-    switch (reason) {
-    case BAD_MISSING: set_error("ldw_links_grep: %s: line %lld, column %u: the line ends after %u of %d fields", path, (long long)line, col, col - 1, ncols); break;
-    case BAD_EXTRA: set_error("ldw_links_grep: %s: line %lld, column %u: more than %d fields", path, (long long)line, col, ncols); break;
-    case BAD_LONG: set_error("ldw_links_grep: %s: line %lld, column %u: the line is longer than %lld bytes", path, (long long)line, col, (long long)TSV_LINE_MAX); break;
-    default: set_error("ldw_links_grep: %s: line %lld, column %u: not a number", path, (long long)line, col); break;
-    }
-    return LDW_ERR_ARG;
-}
 
 }  // namespace
 
@@ -292,10 +279,11 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
         LDW_REQUIRE(len >= 1 && len <= GREP_MAX_LEN, LDW_ERR_ARG, "ldw_links_grep: needle %d has %lld bytes, outside 1..%d", j, (long long)len, GREP_MAX_LEN);
     }
     LDW_REQUIRE((flags & ~(LDW_GREP_DROP_SYXSY | LDW_GREP_DROP_INDIRECT)) == 0, LDW_ERR_ARG, "ldw_links_grep: unknown flags %d", (int)flags);
-    LDW_REQUIRE(chunk_bytes >= 0 && chunk_bytes <= ((int64_t)1 << 30), LDW_ERR_ARG, "ldw_links_grep: chunk_bytes = %lld outside 0..2^30 (0: 64 MiB)", (long long)chunk_bytes);
-    const int64_t chunk = chunk_bytes > 0 ? chunk_bytes : TSV_DEFAULT_CHUNK;
-    TsvFeeder feed;
-    if (int rc = feed.open(path)) return rc;
+    std::vector<GrepRec> recs;   // (in front of the pass: it waits for the stream before they go)
+    std::vector<unsigned long long> rmask;
+    std::vector<uint32_t> idx;
+    TsvPass pass("ldw_links_grep", path);
+    if (int rc = pass.open(chunk_bytes)) return rc;
     GrepState *g = grep_state(c);
     g->valid = false;
     g->row.clear();
@@ -310,8 +298,7 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
     const auto t_begin = std::chrono::steady_clock::now();
     for (auto &e : g->ev)
         if (!e) LDW_HIP(hipEventCreate(&e));
-    if (!g->pin_res) LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->pin_res), sizeof(GrepResult) + 8, hipHostMallocDefault));
-    uint32_t *pin_rows = reinterpret_cast<uint32_t *>(g->pin_res + 1);
+    if (!g->pin_res) LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->pin_res), sizeof(GrepResult), hipHostMallocDefault));
 
     // the needles by first byte (a stable order inside a bucket: the caller's)
     const int32_t blob_bytes = needle_off[n_needles];
@@ -343,11 +330,8 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
     LDW_HIP(hipStreamSynchronize(c->stream));   // (the host vectors may go)
     const NeedleTables T{d_bstart, d_noff, d_orig, d_nlen, d_blob};
 
-    void *pin[2] = {nullptr, nullptr};
-    uint8_t *d_img = nullptr;
-    int64_t cap = 0;
-    if (int rc = tsv_chunk_buffers(c, chunk, pin, &d_img, &cap)) return rc;
-    const uint8_t *d_buf = d_img + TSV_FRONT;
+    if (int rc = pass.attach(c)) return rc;
+    const uint8_t *d_buf = pass.d_text();
 
     GrepParams P;
     memset(&P, 0, sizeof(P));
@@ -358,13 +342,9 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
     bool have_header = false;
     int64_t lines_before_header = 0;   // empty physical lines in front of the header
     int64_t rows_seen = 0;             // non-empty lines of the chunks done (the header among them)
-    int64_t consumed = 0, nchunks = 0;
     int rc = LDW_OK;
     int64_t bad_row = -1;
     uint32_t bad_col = 0, bad_reason = 0;
-    std::vector<GrepRec> recs;
-    std::vector<unsigned long long> rmask;
-    std::vector<uint32_t> idx;
 
     Carve cv;   // a chunk's records and mask words
     Carve::Slot<GrepRec> d_rec{};
@@ -372,7 +352,7 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
     uint32_t rec_cap = 0;
     bool searched = false;
     const uint32_t *d_starts = nullptr;
-    // copies a chunk, finds its rows (the host waits for their count: the copy and two short kernels) and queues the search, which it does not wait for
+    // a chunk's search, queued and not waited for
     auto search = [&](int64_t cut, uint32_t skip, uint32_t nrows, uint32_t want) -> int {
         rec_cap = std::min(nrows, want);
         cv = Carve();
@@ -387,41 +367,29 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
         LDW_HIP(hipMemcpyAsync(g->pin_res, d_res, sizeof(GrepResult), hipMemcpyDeviceToHost, c->stream));
         return LDW_OK;
     };
-    auto queue = [&](int b, int64_t cut, uint32_t skip, uint32_t *nrows_out) -> int {
-        const int64_t padded = (cut + 15) / 16 * 16;
-        LDW_HIP(hipEventRecord(g->ev[0], c->stream));
-        LDW_HIP(hipMemcpyAsync(d_img, pin[b], (size_t)(TSV_FRONT + padded + TSV_TAIL - 16), hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipEventRecord(g->ev[1], c->stream));
-        const uint32_t *d_total = nullptr;
-        if (int rc2 = tsv_rows_count(c, d_buf, cut, &d_total)) return rc2;
-        LDW_HIP(hipMemcpyAsync(pin_rows, d_total, 4, hipMemcpyDeviceToHost, c->stream));
-        LDW_HIP(hipEventRecord(g->ev[2], c->stream));
-        LDW_HIP(hipEventSynchronize(g->ev[2]));
-        const uint32_t nrows = *pin_rows;
-        *nrows_out = nrows;
+    // the rows' count known: their starts and the first search
+    auto queue = [&](int64_t cut, uint32_t skip, uint32_t nrows) -> int {
         searched = have_header && nrows > skip;
         if (!searched) return LDW_OK;
-        LDW_HIP(hipEventRecord(g->ev[4], c->stream));   // (behind the wait: the queue has been idle since ev[2])
-        if (int rc2 = tsv_rows_starts(c, d_buf, cut, nrows, &d_starts)) return rc2;
+        LDW_HIP(hipEventRecord(g->ev[0], c->stream));   // (behind the wait for the count: the queue has been idle since)
+        if (int rc2 = pass.starts(nrows, &d_starts)) return rc2;
         if (int rc2 = search(cut, skip, nrows, GREP_FIRST_RECORDS)) return rc2;
-        LDW_HIP(hipEventRecord(g->ev[3], c->stream));
+        LDW_HIP(hipEventRecord(g->ev[1], c->stream));
         return LDW_OK;
     };
     // waits for a chunk's search; its kept rows, in file order, join the result: slow cells and strings come from the pinned text `data`
     auto finish = [&](const char *data, int64_t cut, uint32_t skip, uint32_t nrows) -> int {
         float fms = 0;
-        if (hipEventElapsedTime(&fms, g->ev[0], g->ev[1]) == hipSuccess) g->ms[2] += fms;
-        if (hipEventElapsedTime(&fms, g->ev[1], g->ev[2]) == hipSuccess) g->ms[3] += fms;
         if (searched) {
-            LDW_HIP(hipEventSynchronize(g->ev[3]));
-            if (hipEventElapsedTime(&fms, g->ev[4], g->ev[3]) == hipSuccess) g->ms[4] += fms;
+            LDW_HIP(hipEventSynchronize(g->ev[1]));
+            if (hipEventElapsedTime(&fms, g->ev[0], g->ev[1]) == hipSuccess) g->ms[4] += fms;
             GrepResult r = *g->pin_res;
             if (r.bad == ~0ull && r.kept > rec_cap) {   // more rows kept than the first guess holds: once more with room for every row
-                LDW_HIP(hipEventRecord(g->ev[4], c->stream));
+                LDW_HIP(hipEventRecord(g->ev[0], c->stream));
                 if (int rc2 = search(cut, skip, nrows, nrows)) return rc2;
-                LDW_HIP(hipEventRecord(g->ev[3], c->stream));
-                LDW_HIP(hipEventSynchronize(g->ev[3]));
-                if (hipEventElapsedTime(&fms, g->ev[4], g->ev[3]) == hipSuccess) g->ms[4] += fms;
+                LDW_HIP(hipEventRecord(g->ev[1], c->stream));
+                LDW_HIP(hipEventSynchronize(g->ev[1]));
+                if (hipEventElapsedTime(&fms, g->ev[0], g->ev[1]) == hipSuccess) g->ms[4] += fms;
                 r = *g->pin_res;
             }
             if (r.bad != ~0ull) {
@@ -459,20 +427,9 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
         return LDW_OK;
     };
 
-    int64_t cut = 0, total = 0;
-    std::string fill_err;
-    int fill_rc = feed.fill(static_cast<char *>(pin[0]) + TSV_FRONT, 0, chunk, cap, &cut, &total);
-    if (fill_rc != LDW_OK) {
-        fill_err = ldw_last_error();
-        cut = cut < 0 ? -1 : 0;
-    }
-    const int64_t first_cut = cut;
-    for (int64_t k = 0; rc == LDW_OK && cut > 0; ++k) {
-        const int b = (int)(k & 1);
-        char *data = static_cast<char *>(pin[b]) + TSV_FRONT;
-        const int64_t carry = total - cut;
-        memcpy(static_cast<char *>(pin[1 - b]) + TSV_FRONT, data + cut, (size_t)carry);
-        memset(data + cut, '\n', (size_t)TSV_TAIL);
+    for (; rc == LDW_OK && pass.more(); pass.advance()) {
+        const char *data = pass.begin();
+        const int64_t cut = pass.cut();
         uint32_t skip = 0;
         if (!have_header) {   // the first non-empty line of the file
             int64_t at = 0;
@@ -495,34 +452,16 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
             }
             if (rc != LDW_OK) break;
         }
+        // the copy and the two short line kernels are waited for: the search needs the rows' count; the next chunk is read while it runs
         uint32_t nrows = 0;
-        if ((rc = queue(b, cut, skip, &nrows))) break;
-        consumed += cut;
-        ++nchunks;
-        // the next chunk is read while this one is searched
-        int64_t ncut = 0, ntotal = 0;
-        fill_rc = feed.fill(static_cast<char *>(pin[1 - b]) + TSV_FRONT, carry, chunk, cap, &ncut, &ntotal);
-        if (fill_rc != LDW_OK) fill_err = ldw_last_error();
-        if ((rc = finish(data, cut, skip, nrows))) break;
-        if (fill_rc != LDW_OK) {
-            cut = ncut;
-            break;
-        }
-        cut = ncut;
-        total = ntotal;
+        if ((rc = pass.queue())) break;
+        if ((rc = pass.wait(&nrows))) break;
+        if ((rc = queue(cut, skip, nrows))) break;
+        pass.prefetch();
+        rc = finish(data, cut, skip, nrows);
     }
-    (void)hipStreamSynchronize(c->stream);   // (on an error path too: no copy may still read a pinned buffer)
-    if (rc == LDW_OK && bad_row < 0 && fill_rc != LDW_OK) {   // the feeder's own refusal comes after every row before it
-        rc = fill_rc;
-        if (cut < 0 || first_cut < 0 || fill_err.find("longer than") != std::string::npos) {
-            int64_t line = 0;
-            (void)tsv_line_of_offset(path, consumed, &line);
-            set_error("ldw_links_grep: %s: line %lld, column 1: the line is longer than %lld bytes", path, (long long)line, (long long)TSV_LINE_MAX);
-        } else {
-            set_error("%s", fill_err.c_str());
-        }
-    }
-    if (bad_row >= 0) rc = refuse_row(path, bad_row, bad_col, bad_reason, P.ncols);
+    if (rc == LDW_OK) rc = pass.feeder_refusal();   // the feeder's own refusal comes after every row before it
+    if (bad_row >= 0) rc = pass.refuse_row(bad_row, bad_col, bad_reason, P.ncols);
     if (rc == LDW_OK && !have_header) {
         set_error("ldw_links_grep: %s: line 1, column 1: the file holds no header line", path);
         rc = LDW_ERR_ARG;
@@ -538,9 +477,11 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
     g->data_rows = rows_seen - 1;
     g->valid = true;
     g->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    g->ms[1] = feed.read_ms;
-    g->ms[5] = (double)nchunks;
-    g->ms[6] = (double)consumed;
+    g->ms[1] = pass.read_ms();
+    g->ms[2] = pass.copy_ms;
+    g->ms[3] = pass.line_ms;
+    g->ms[5] = (double)pass.nchunks;
+    g->ms[6] = (double)pass.consumed;
     g->ms[7] = (double)g->row.size();
     if (rows_out) *rows_out = (int64_t)g->row.size();
     if (text_bytes_out) *text_bytes_out = (int64_t)g->text.size();

@@ -24,9 +24,7 @@ namespace {
 constexpr int TSV_BLOCK = 256;
 constexpr int TSV_TILE = TSV_BLOCK * 16;   // bytes of a chunk one block of the line kernels scans: 16 per thread, one 128-bit load
 constexpr int TSV_STAGE = 32768;           // bytes of LDS a block of the staged parse kernel may fill with its rows' text
-// reasons a row is refused (the low byte of the bad-row key)
-enum { BAD_CELL = 1, BAD_MISSING = 2, BAD_EXTRA = 3, BAD_LONG = 4 };
-// ... and a position of ldw_links_load
+// reasons ldw_links_load refuses a position
 enum { POS_FRACTION = 1, POS_RANGE = 2, POS_UNKNOWN = 3 };
 
 struct TsvResult {   // what a chunk's kernels report (device, copied to a pinned twin)
@@ -230,15 +228,19 @@ __global__ __launch_bounds__(256) void k_links_compact(const uint32_t *__restric
 // ---- the reader's state -----------------------------------------------------------------------------------------------------------------------
 
 struct TsvState {
-    void *pin[2] = {nullptr, nullptr};   // pinned chunk buffers: TSV_FRONT '\n', the data, TSV_TAIL '\n'
-    size_t pin_cap = 0;
+    // what a pass over a text file borrows (TsvPass)
+    PinnedPair pin;                      // pinned chunk buffers: TSV_FRONT '\n', the data, TSV_TAIL '\n'
+    DevBuf img, cnt, off, starts, scan_tmp;
+    uint32_t *pin_rows = nullptr;        // pinned: the line count of the chunk in flight
+    hipEvent_t pass_ev[3] = {};          // before / after a chunk's copy, after its line count
+    // the reader's own
     TsvResult *pin_res = nullptr;        // pinned twin of res, one per chunk buffer
-    DevBuf img, cnt, off, starts, slow, res, patch, scan_tmp;
+    DevBuf slow, res, patch;
     DevBuf cols;                         // double [ncols][stride], column-major: the parsed table
     int64_t rows = 0, stride = 0;
     int ncols = 0;
     int64_t grows = 0;                   // times the columns were moved to a larger buffer (since the context was made)
-    hipEvent_t ev[2][6] = {};            // per chunk buffer: before / after the copy, after the line kernels, before / after the parse kernel, after the patch
+    hipEvent_t ev[2][2] = {};            // per chunk buffer: before / after the parse kernel
     std::string path;                    // of the last read, for the line numbers of ldw_links_load's refusals
     int variant = 0;                     // 0: rows parsed from cached global loads, 1: from an LDS-staged tile
     double ms[8] = {};                   // last read: total, read (host), copy, line kernels, parse kernel, slow-cell patch, chunks, bytes
@@ -248,39 +250,6 @@ struct TsvState {
 TsvState *tsv_state(ldw_ctx *c) {
     if (!c->tsv) c->tsv = new TsvState();
     return static_cast<TsvState *>(c->tsv);
-}
-
-int64_t free_pins(TsvState *t) {
-    int64_t n = 0;
-    for (auto &p : t->pin) {
-        if (p) {
-            (void)hipHostFree(p);
-            n += (int64_t)t->pin_cap;
-        }
-        p = nullptr;
-    }
-    t->pin_cap = 0;
-    return n;
-}
-
-int ensure_pins(TsvState *t, size_t bytes) {
-    for (auto &row : t->ev)
-        for (auto &e : row)
-            if (!e) LDW_HIP(hipEventCreate(&e));
-    if (!t->pin_res) LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->pin_res), 2 * sizeof(TsvResult), hipHostMallocDefault));
-    if (t->pin_cap < bytes) {
-        free_pins(t);
-        for (auto &p : t->pin)
-            if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                p = nullptr;
-                free_pins(t);
-                set_error("ldw_tsv_read: hipHostMalloc of %zu bytes failed", bytes);
-                return LDW_ERR_HIP;
-            }
-        t->pin_cap = bytes;
-    }
-    return LDW_OK;
 }
 
 // room for `rows` rows: the columns move to a buffer of a larger stride (every column by one device-to-device copy)
@@ -305,18 +274,6 @@ int grow_columns(ldw_ctx *c, TsvState *t, int64_t rows) {
     return LDW_OK;
 }
 
-int refuse_row(const char *path, int64_t row, uint32_t col, uint32_t reason, int ncols) {
-    int64_t line = 0;
-    (void)tsv_line_of_row(path, row, &line);
-    switch (reason) {
-    case BAD_MISSING: set_error("ldw_tsv_read: %s: line %lld, column %u: the line ends after %u of %d fields", path, (long long)line, col, col - 1, ncols); break;
-    case BAD_EXTRA: set_error("ldw_tsv_read: %s: line %lld, column %u: more than %d fields", path, (long long)line, col, ncols); break;
-    case BAD_LONG: set_error("ldw_tsv_read: %s: line %lld, column %u: the line is longer than %lld bytes", path, (long long)line, col, (long long)TSV_LINE_MAX); break;
-    default: set_error("ldw_tsv_read: %s: line %lld, column %u: not a number", path, (long long)line, col); break;
-    }
-    return LDW_ERR_ARG;
-}
-
 }  // namespace
 
 namespace ldw {
@@ -324,10 +281,13 @@ void tsv_release(ldw_ctx *c) {
     auto *t = static_cast<TsvState *>(c->tsv);
     if (!t) return;
     (void)hipStreamSynchronize(c->stream);
-    free_pins(t);
+    t->pin.release();
+    if (t->pin_rows) (void)hipHostFree(t->pin_rows);
     if (t->pin_res) (void)hipHostFree(t->pin_res);
     for (DevBuf *b : {&t->img, &t->cnt, &t->off, &t->starts, &t->slow, &t->res, &t->patch, &t->scan_tmp, &t->cols, &t->keep, &t->koff, &t->idx1, &t->idx2, &t->bad})
         b->release();
+    for (auto &e : t->pass_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto &row : t->ev)
         for (auto &e : row)
             if (e) (void)hipEventDestroy(e);
@@ -335,53 +295,73 @@ void tsv_release(ldw_ctx *c) {
     c->tsv = nullptr;
 }
 
-int tsv_chunk_buffers(ldw_ctx *c, int64_t chunk, void *pin[2], uint8_t **d_img, int64_t *cap_out) {
+// ---- TsvPass, the stream half (the host half: ldw_links_read_host.cpp) --------------------------------------------------------------------------
+
+int TsvPass::attach(ldw_ctx *c) {
+    ctx_ = c;
     TsvState *t = tsv_state(c);
-    const int64_t cap = chunk + TSV_LINE_MAX + 64;   // data bytes of a pinned buffer: a carried line and a chunk
-    const size_t buf_bytes = (size_t)(TSV_FRONT + cap + TSV_TAIL);
-    if (int rc = ensure_pins(t, buf_bytes)) return rc;
+    for (auto &e : t->pass_ev)
+        if (!e) LDW_HIP(hipEventCreate(&e));
+    if (!t->pin_rows) LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->pin_rows), 4, hipHostMallocDefault));
+    const size_t buf_bytes = (size_t)buffer_bytes();
+    if (int rc = t->pin.reserve(buf_bytes, "ldw_tsv_read")) return rc;   // (the pair is the reader's, whoever asks)
     if (int rc = t->img.reserve(buf_bytes)) return rc;
-    const int64_t max_blocks = (cap + TSV_TILE - 1) / TSV_TILE + 1;
+    const int64_t max_blocks = (cap_ + TSV_TILE - 1) / TSV_TILE + 1;
     if (int rc = t->cnt.reserve((size_t)(max_blocks + 1) * 4)) return rc;
     if (int rc = t->off.reserve((size_t)(max_blocks + 1) * 4)) return rc;
     size_t scan_bytes = 0;
     LDW_HIP(prim_scan_bytes<uint32_t>((size_t)max_blocks + 1, c->stream, &scan_bytes));
     if (int rc = t->scan_tmp.reserve(scan_bytes)) return rc;
-    for (int b = 0; b < 2; ++b) {
-        memset(t->pin[b], '\n', (size_t)TSV_FRONT);
-        pin[b] = t->pin[b];
-    }
-    *d_img = t->img.as<uint8_t>();
-    *cap_out = cap;
+    d_text_ = t->img.as<uint8_t>() + TSV_FRONT;
+    use(t->pin.p[0], t->pin.p[1]);
     return LDW_OK;
 }
 
-int tsv_rows_count(ldw_ctx *c, const uint8_t *d_buf, int64_t cut, const uint32_t **d_total) {
-    TsvState *t = tsv_state(c);
+int TsvPass::queue() {
+    TsvState *t = tsv_state(ctx_);
+    hipStream_t s = ctx_->stream;
+    const int64_t cut = cut_, padded = (cut + 15) / 16 * 16;   // (the kernels load 16 bytes at a time)
     const uint32_t nblocks = (uint32_t)((cut + TSV_TILE - 1) / TSV_TILE);
-    LDW_HIP(hipMemsetAsync(t->cnt.as<uint32_t>() + nblocks, 0, 4, c->stream));
-    LDW_LAUNCH(k_tsv_count, dim3(nblocks), dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->cnt.as<uint32_t>());
+    LDW_HIP(hipEventRecord(t->pass_ev[0], s));
+    LDW_HIP(hipMemcpyAsync(t->img.p, buf_[buffer()], (size_t)(TSV_FRONT + padded + TSV_TAIL - 16), hipMemcpyHostToDevice, s));
+    LDW_HIP(hipEventRecord(t->pass_ev[1], s));
+    LDW_HIP(hipMemsetAsync(t->cnt.as<uint32_t>() + nblocks, 0, 4, s));
+    LDW_LAUNCH(k_tsv_count, dim3(nblocks), dim3(TSV_BLOCK), 0, s, d_text_, (uint32_t)cut, t->cnt.as<uint32_t>());
     size_t sb = t->scan_tmp.cap;
-    LDW_HIP(prim_exclusive_sum(t->scan_tmp.p, sb, t->cnt.as<uint32_t>(), t->off.as<uint32_t>(), (size_t)nblocks + 1, c->stream));
-    *d_total = t->off.as<uint32_t>() + nblocks;   // the exclusive sums end with the total
+    LDW_HIP(prim_exclusive_sum(t->scan_tmp.p, sb, t->cnt.as<uint32_t>(), t->off.as<uint32_t>(), (size_t)nblocks + 1, s));
+    d_rows_ = t->off.as<uint32_t>() + nblocks;   // the exclusive sums end with the total
+    LDW_HIP(hipMemcpyAsync(t->pin_rows, d_rows_, 4, hipMemcpyDeviceToHost, s));
+    LDW_HIP(hipEventRecord(t->pass_ev[2], s));
     return LDW_OK;
 }
 
-int tsv_rows_starts(ldw_ctx *c, const uint8_t *d_buf, int64_t cut, uint32_t nrows, const uint32_t **d_starts) {
-    TsvState *t = tsv_state(c);
-    const uint32_t nblocks = (uint32_t)((cut + TSV_TILE - 1) / TSV_TILE);
-    if (int rc = t->starts.reserve((size_t)std::max<uint32_t>(nrows, 1) * 4)) return rc;
-    LDW_LAUNCH(k_tsv_starts, dim3(nblocks), dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->off.as<uint32_t>(), t->starts.as<uint32_t>());
+int TsvPass::wait(uint32_t *rows) {
+    TsvState *t = tsv_state(ctx_);
+    LDW_HIP(hipEventSynchronize(t->pass_ev[2]));
+    float f = 0;
+    if (hipEventElapsedTime(&f, t->pass_ev[0], t->pass_ev[1]) == hipSuccess) copy_ms += f;
+    if (hipEventElapsedTime(&f, t->pass_ev[1], t->pass_ev[2]) == hipSuccess) line_ms += f;
+    *rows = *t->pin_rows;
+    return LDW_OK;
+}
+
+int TsvPass::starts(uint32_t rows, const uint32_t **d_starts) {
+    TsvState *t = tsv_state(ctx_);
+    const uint32_t nblocks = (uint32_t)((cut_ + TSV_TILE - 1) / TSV_TILE);
+    if (int rc = t->starts.reserve((size_t)std::max<uint32_t>(rows, 1) * 4)) return rc;
+    LDW_LAUNCH(k_tsv_starts, dim3(nblocks), dim3(TSV_BLOCK), 0, ctx_->stream, d_text_, (uint32_t)cut_, t->off.as<uint32_t>(), t->starts.as<uint32_t>());
     *d_starts = t->starts.as<uint32_t>();
     return LDW_OK;
 }
+
+void TsvPass::drain() { (void)hipStreamSynchronize(ctx_->stream); }
 
 int64_t tsv_trim(ldw_ctx *c) {
     auto *t = static_cast<TsvState *>(c->tsv);
     if (!t) return 0;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    const int64_t n = free_pins(t) + (int64_t)t->img.cap;
+    const int64_t n = t->pin.release() + (int64_t)t->img.cap;
     t->img.release();
     return n;
 }
@@ -397,10 +377,8 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
     LDW_REQUIRE(path != nullptr, LDW_ERR_ARG, "ldw_tsv_read: null path");
     LDW_REQUIRE(sep == '\t' || sep == ' ', LDW_ERR_ARG, "ldw_tsv_read: the separator must be a tab or a space (got %d)", sep);
     LDW_REQUIRE(ncols >= 1 && ncols <= TSV_MAX_COLS, LDW_ERR_ARG, "ldw_tsv_read: ncols = %d outside 1..%d", (int)ncols, TSV_MAX_COLS);
-    LDW_REQUIRE(chunk_bytes >= 0 && chunk_bytes <= ((int64_t)1 << 30), LDW_ERR_ARG, "ldw_tsv_read: chunk_bytes = %lld outside 0..2^30 (0: 64 MiB)", (long long)chunk_bytes);
-    const int64_t chunk = chunk_bytes > 0 ? chunk_bytes : TSV_DEFAULT_CHUNK;
-    TsvFeeder feed;
-    if (int rc = feed.open(path)) return rc;
+    TsvPass pass("ldw_tsv_read", path);
+    if (int rc = pass.open(chunk_bytes)) return rc;
     TsvState *t = tsv_state(c);
     t->rows = 0;
     t->path = path;
@@ -408,21 +386,21 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
     t->ncols = ncols;
     memset(t->ms, 0, sizeof(t->ms));
     const auto t_begin = std::chrono::steady_clock::now();
-    void *pins[2];
-    uint8_t *d_img = nullptr;
-    int64_t cap = 0;   // data bytes of a pinned buffer
-    if (int rc = tsv_chunk_buffers(c, chunk, pins, &d_img, &cap)) return rc;
+    for (auto &row : t->ev)
+        for (auto &e : row)
+            if (!e) LDW_HIP(hipEventCreate(&e));
+    if (!t->pin_res) LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->pin_res), 2 * sizeof(TsvResult), hipHostMallocDefault));
     if (int rc = t->res.reserve(sizeof(TsvResult))) return rc;
+    if (int rc = pass.attach(c)) return rc;
 
     int rc = LDW_OK;
-    int64_t slow_total = 0, consumed = 0, nchunks = 0, file_bytes = 0;
+    int64_t slow_total = 0, file_bytes = 0;
     uint32_t bad_reason = 0, bad_col = 0;
     int64_t bad_row = -1;
     struct Chunk {
-        int64_t size = 0, row0 = 0, rows = 0;
+        int64_t row0 = 0;
         bool queued = false;
     } ch[2];
-    const uint8_t *d_buf = t->img.as<uint8_t>() + TSV_FRONT;
     TsvResult *d_res = t->res.as<TsvResult>();
 
     // waits for a chunk's kernels; converts and patches its slow cells from the pinned text; notes its first refused row
@@ -430,13 +408,11 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
         Chunk &k = ch[b];
         if (!k.queued) return LDW_OK;
         k.queued = false;
-        hipError_t e = hipEventSynchronize(t->ev[b][4]);
+        hipError_t e = hipEventSynchronize(t->ev[b][1]);
         if (e != hipSuccess) return hip_fail(e, "ldw_tsv_read: chunk", __FILE__, __LINE__);
         const TsvResult r = t->pin_res[b];
         float f = 0;
-        if (hipEventElapsedTime(&f, t->ev[b][0], t->ev[b][1]) == hipSuccess) t->ms[2] += f;
-        if (hipEventElapsedTime(&f, t->ev[b][1], t->ev[b][2]) == hipSuccess) t->ms[3] += f;
-        if (hipEventElapsedTime(&f, t->ev[b][3], t->ev[b][4]) == hipSuccess) t->ms[4] += f;
+        if (hipEventElapsedTime(&f, t->ev[b][0], t->ev[b][1]) == hipSuccess) t->ms[4] += f;
         if (r.bad != ~0ull) {
             bad_row = k.row0 + (int64_t)(r.bad >> 16);
             bad_col = (uint32_t)(r.bad >> 8) & 0xff;
@@ -453,7 +429,7 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
             std::vector<unsigned char> host(voff + (size_t)r.slow * 8);
             uint32_t *cell = reinterpret_cast<uint32_t *>(host.data());
             double *val = reinterpret_cast<double *>(host.data() + voff);
-            const char *text = static_cast<const char *>(t->pin[b]) + TSV_FRONT;
+            const char *text = pass.text(b);
             for (uint32_t i = 0; i < r.slow; ++i) {
                 cell[i] = list[i].x;
                 val[i] = tsv_strtod(text + list[i].y);
@@ -468,115 +444,71 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
         }
         return LDW_OK;
     };
+    // a chunk's rows, counted, into the columns: k_tsv_starts and the parse kernel, not waited for
+    auto parse = [&](int b, uint32_t nrows) -> int {
+        int64_t want = t->rows + nrows;
+        if (pass.nchunks == 1 && file_bytes > pass.cut())   // a plain file: sized once from its first chunk
+            want = std::max<int64_t>(want, (int64_t)((double)nrows * ((double)file_bytes / (double)pass.cut()) * 1.02) + 1024);
+        if (int rc2 = grow_columns(c, t, want)) return rc2;
+        if (int rc2 = t->slow.reserve((size_t)nrows * (size_t)ncols * 8)) return rc2;
+        LDW_HIP(hipEventRecord(t->ev[b][0], c->stream));
+        const uint32_t *d_starts = nullptr;
+        if (int rc2 = pass.starts(nrows, &d_starts)) return rc2;
+        const dim3 grid((nrows + TSV_BLOCK - 1) / TSV_BLOCK);
+        if (t->variant == 1)
+            LDW_LAUNCH(k_tsv_parse<true>, grid, dim3(TSV_BLOCK), 0, c->stream, pass.d_text(), (uint32_t)pass.cut(), d_starts, nrows, (int)ncols, (uint8_t)sep,
+                       t->cols.as<double>(), t->stride, t->rows, d_res, t->slow.as<uint2>());
+        else
+            LDW_LAUNCH(k_tsv_parse<false>, grid, dim3(TSV_BLOCK), 0, c->stream, pass.d_text(), (uint32_t)pass.cut(), d_starts, nrows, (int)ncols, (uint8_t)sep,
+                       t->cols.as<double>(), t->stride, t->rows, d_res, t->slow.as<uint2>());
+        LDW_HIP(hipMemcpyAsync(&t->pin_res[b], d_res, sizeof(TsvResult), hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipEventRecord(t->ev[b][1], c->stream));
+        ch[b].row0 = t->rows;
+        ch[b].queued = true;
+        t->rows += nrows;
+        return LDW_OK;
+    };
 
-    int64_t cut = 0, total = 0;
-    std::string fill_err;
-    int fill_rc = feed.fill(static_cast<char *>(t->pin[0]) + TSV_FRONT, 0, chunk, cap, &cut, &total);
-    if (fill_rc != LDW_OK) {
-        fill_err = ldw_last_error();
-        cut = 0;
-    } else if (!feed.gzip()) {
+    if (pass.more() && !pass.gzip()) {
         FileStamp st;
         if (file_stamp(path, &st) == LDW_OK) file_bytes = st.size;
     }
-    for (int64_t k = 0; rc == LDW_OK && cut > 0; ++k) {
-        const int b = (int)(k & 1);
-        char *data = static_cast<char *>(t->pin[b]) + TSV_FRONT;
-        const int64_t carry = total - cut;
-        // the chunk before this one: the other buffer still holds the text of its slow cells
+    for (; rc == LDW_OK && pass.more(); pass.advance()) {
+        const int b = pass.buffer();
+        // the chunk before this one: the other buffer still holds the text of its slow cells, and takes this one's carried line next
         if ((rc = finish(1 - b))) break;
-        // the other buffer takes the carried line now: this one's tail becomes '\n' padding
-        memcpy(static_cast<char *>(t->pin[1 - b]) + TSV_FRONT, data + cut, (size_t)carry);
-        memset(data + cut, '\n', (size_t)TSV_TAIL);
-        const int64_t padded = (cut + 15) / 16 * 16;
-        const uint32_t nblocks = (uint32_t)((cut + TSV_TILE - 1) / TSV_TILE);
-        hipError_t e = hipEventRecord(t->ev[b][0], c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(t->img.p, t->pin[b], (size_t)(TSV_FRONT + padded + TSV_TAIL - 16), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipEventRecord(t->ev[b][1], c->stream);
-        if (e == hipSuccess) {
-            const uint32_t *d_total = nullptr;
-            if ((rc = tsv_rows_count(c, d_buf, cut, &d_total))) break;
-        }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_tsv_init, dim3(1), dim3(256), 0, c->stream, d_res, (uint32_t)(k > 0), t->off.as<uint32_t>(), nblocks);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&t->pin_res[b], d_res, sizeof(TsvResult), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipEventRecord(t->ev[b][2], c->stream);
-        if (e != hipSuccess) {
-            rc = hip_fail(e, "ldw_tsv_read: line kernels", __FILE__, __LINE__);
+        pass.begin();
+        if ((rc = pass.queue())) break;
+        hipLaunchKernelGGL(k_tsv_init, dim3(1), dim3(256), 0, c->stream, d_res, (uint32_t)(pass.nchunks > 1), pass.d_rows(), 0u);
+        if (hipError_t e = hipGetLastError()) {
+            rc = hip_fail(e, "ldw_tsv_read: k_tsv_init", __FILE__, __LINE__);
             break;
         }
-        ch[b].size = cut;
-        consumed += cut;
-        ++nchunks;
         // the next chunk is read while this one is copied and its lines are counted
-        int64_t ncut = 0, ntotal = 0;
-        fill_rc = feed.fill(static_cast<char *>(t->pin[1 - b]) + TSV_FRONT, carry, chunk, cap, &ncut, &ntotal);
-        if (fill_rc != LDW_OK) fill_err = ldw_last_error();
-        e = hipEventSynchronize(t->ev[b][2]);
-        if (e != hipSuccess) {
-            rc = hip_fail(e, "ldw_tsv_read: line kernels", __FILE__, __LINE__);
-            break;
-        }
-        const uint32_t nrows = t->pin_res[b].rows;
-        ch[b].row0 = t->rows;
-        ch[b].rows = nrows;
-        if (nrows > 0) {
-            int64_t want = t->rows + nrows;
-            if (k == 0 && file_bytes > cut) want = std::max<int64_t>(want, (int64_t)((double)nrows * ((double)file_bytes / (double)cut) * 1.02) + 1024);   // a plain file: sized once from its first chunk
-            if ((rc = grow_columns(c, t, want))) break;
-            if ((rc = t->slow.reserve((size_t)nrows * (size_t)ncols * 8))) break;
-            e = hipEventRecord(t->ev[b][3], c->stream);
-            const uint32_t *d_starts = nullptr;
-            if ((rc = tsv_rows_starts(c, d_buf, cut, nrows, &d_starts))) break;
-            const dim3 grid((nrows + TSV_BLOCK - 1) / TSV_BLOCK);
-            if (t->variant == 1)
-                hipLaunchKernelGGL(k_tsv_parse<true>, grid, dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->starts.as<uint32_t>(), nrows, (int)ncols, (uint8_t)sep,
-                                   t->cols.as<double>(), t->stride, t->rows, d_res, t->slow.as<uint2>());
-            else
-                hipLaunchKernelGGL(k_tsv_parse<false>, grid, dim3(TSV_BLOCK), 0, c->stream, d_buf, (uint32_t)cut, t->starts.as<uint32_t>(), nrows, (int)ncols, (uint8_t)sep,
-                                   t->cols.as<double>(), t->stride, t->rows, d_res, t->slow.as<uint2>());
-            if (e == hipSuccess) e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(&t->pin_res[b], d_res, sizeof(TsvResult), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipEventRecord(t->ev[b][4], c->stream);
-            if (e != hipSuccess) {
-                rc = hip_fail(e, "ldw_tsv_read: parse kernel", __FILE__, __LINE__);
-                break;
-            }
-            ch[b].queued = true;
-            t->rows += nrows;
-        }
-        if (fill_rc != LDW_OK) break;
-        cut = ncut;
-        total = ntotal;
+        pass.prefetch();
+        uint32_t nrows = 0;
+        if ((rc = pass.wait(&nrows))) break;
+        if (nrows > 0) rc = parse(b, nrows);
     }
     for (int b = 0; b < 2 && rc == LDW_OK; ++b) rc = finish(b);
-    (void)hipStreamSynchronize(c->stream);   // (on an error path too: no copy may still read a pinned buffer)
+    if (rc == LDW_OK) rc = pass.feeder_refusal();   // the feeder's own refusal comes after every row before it
+    if (bad_row >= 0) rc = pass.refuse_row(bad_row, bad_col, bad_reason, ncols);
     uint32_t not_int = 0;
-    if (rc == LDW_OK && fill_rc == LDW_OK && nchunks > 0) {
-        const hipError_t e = hipMemcpy(&not_int, &d_res->not_int, 4, hipMemcpyDeviceToHost);
+    if (rc == LDW_OK && pass.nchunks > 0) {
+        hipError_t e = hipMemcpyAsync(&not_int, &d_res->not_int, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = hip_fail(e, "ldw_tsv_read: result", __FILE__, __LINE__);
     }
-    if (rc == LDW_OK && bad_row < 0 && fill_rc != LDW_OK) {   // the feeder's own refusal comes after every row before it
-        rc = fill_rc;
-        if (cut < 0 || fill_err.find("longer than") != std::string::npos) {
-            int64_t line = 0;
-            (void)tsv_line_of_offset(path, consumed, &line);
-            set_error("ldw_tsv_read: %s: line %lld, column 1: the line is longer than %lld bytes", path, (long long)line, (long long)TSV_LINE_MAX);
-        } else {
-            set_error("%s", fill_err.c_str());
-        }
-    }
-    if (bad_row >= 0) rc = refuse_row(path, bad_row, bad_col, bad_reason, ncols);
+    t->ms[2] = pass.copy_ms;
+    t->ms[3] = pass.line_ms;
     if (rc != LDW_OK) {
         t->rows = 0;
         return rc;
     }
     t->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    t->ms[1] = feed.read_ms;
-    t->ms[6] = (double)nchunks;
-    t->ms[7] = (double)consumed;
+    t->ms[1] = pass.read_ms();
+    t->ms[6] = (double)pass.nchunks;
+    t->ms[7] = (double)pass.consumed;
     if (rows_out) *rows_out = t->rows;
     if (slow_cells_out) *slow_cells_out = slow_total;
     if (int_cols_mask_out) *int_cols_mask_out = t->rows > 0 ? ~not_int & ((1u << ncols) - 1) : 0;
@@ -728,7 +660,7 @@ int ldw_tsv_stats(ldw_ctx *c, double *out10) {
     if (!t) return LDW_OK;
     for (int k = 0; k < 8; ++k) out10[k] = t->ms[k];
     out10[8] = (double)t->grows;
-    out10[9] = (double)(t->pin_cap * 2);
+    out10[9] = (double)(t->pin.cap * 2);
     return LDW_OK;
 }
 

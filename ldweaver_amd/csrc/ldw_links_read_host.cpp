@@ -1,5 +1,5 @@
-// Host side of the native reader of numeric link tables (include/ldweaver_amd.h 13): ldw_tsv_probe, the chunk feeder, the physical
-// line of a row (error paths) and the conversion of the cells the device leaves to the host.
+// Host side of the native reader of numeric link tables (include/ldweaver_amd.h 13): ldw_tsv_probe, the chunk feeder, the host half of
+// the chunk pass, the physical line of a row (error paths) and the conversion of the cells the device leaves to the host.
 #include <errno.h>
 #include <locale.h>
 #include <string.h>
@@ -75,6 +75,74 @@ int TsvFeeder::fill(char *data, int64_t carry, int64_t chunk_bytes, int64_t cap,
             return LDW_ERR_ARG;
         }
     }
+}
+
+// ---- TsvPass, the host half -----------------------------------------------------------------------------------------------------------------------
+
+int TsvPass::open(int64_t chunk_bytes) {
+    LDW_REQUIRE(chunk_bytes >= 0 && chunk_bytes <= ((int64_t)1 << 30), LDW_ERR_ARG, "%s: chunk_bytes = %lld outside 0..2^30 (0: 64 MiB)", who_, (long long)chunk_bytes);
+    chunk_ = chunk_bytes > 0 ? chunk_bytes : TSV_DEFAULT_CHUNK;
+    cap_ = chunk_ + TSV_LINE_MAX + 64;
+    return feed_.open(path_);
+}
+
+void TsvPass::use(void *b0, void *b1) {
+    buf_[0] = b0;
+    buf_[1] = b1;
+    for (void *b : buf_) memset(b, '\n', (size_t)TSV_FRONT);
+    k_ = -1;             // the first chunk is "prefetched" into buffer 0 behind an empty carry
+    total_ = cut_ = 0;
+    prefetch();
+    advance();
+}
+
+char *TsvPass::begin() {
+    const int b = buffer();
+    char *data = static_cast<char *>(buf_[b]) + TSV_FRONT;
+    // the other buffer takes the carried line now: this one's tail becomes '\n' padding
+    memcpy(static_cast<char *>(buf_[1 - b]) + TSV_FRONT, data + cut_, (size_t)(total_ - cut_));
+    memset(data + cut_, '\n', (size_t)TSV_TAIL);
+    consumed += cut_;
+    ++nchunks;
+    return data;
+}
+
+void TsvPass::prefetch() {
+    fill_rc_ = feed_.fill(static_cast<char *>(buf_[1 - buffer()]) + TSV_FRONT, total_ - cut_, chunk_, cap_, &next_cut_, &next_total_);
+    if (fill_rc_ != LDW_OK) fill_err_ = ldw_last_error();   // (the feeder left next_cut_ at 0 or -1: more() is false once the pass advances)
+}
+
+void TsvPass::advance() {
+    ++k_;
+    cut_ = next_cut_;
+    total_ = next_total_;
+}
+
+int TsvPass::feeder_refusal() const {
+    if (fill_rc_ == LDW_OK) return LDW_OK;
+    // A line over TSV_LINE_MAX or a read error.  The feeder words the first the same way wherever it meets it (the first chunk, a later one, the last line
+    // without its newline), so the saved message alone tells them apart: the cut of -1 it also leaves, in the first chunk or a later one, need not be kept.
+    // The line begins where the chunks before it end, at byte `consumed`.
+    if (fill_err_.find("longer than") != std::string::npos) {
+        int64_t line = 0;
+        (void)tsv_line_of_offset(path_, consumed, &line);
+        set_error("%s: %s: line %lld, column 1: the line is longer than %lld bytes", who_, path_, (long long)line, (long long)TSV_LINE_MAX);
+    } else {
+        set_error("%s", fill_err_.c_str());
+    }
+    return fill_rc_;
+}
+
+int TsvPass::refuse_row(int64_t row, uint32_t col, uint32_t reason, int ncols) const {
+    int64_t line = 0;
+    (void)tsv_line_of_row(path_, row, &line);
+    switch (reason) {
+    case BAD_MISSING: set_error("%s: %s: line %lld, column %u: the line ends after %u of %d fields", who_, path_, (long long)line, col, col - 1, ncols); break;
+    case BAD_EXTRA: set_error("%s: %s: line %lld, column %u: more than %d fields", who_, path_, (long long)line, col, ncols); break;
+    case BAD_LONG: set_error("%s: %s: line %lld, column %u: the line is longer than %lld bytes", who_, path_, (long long)line, col, (long long)TSV_LINE_MAX); break;
+    default: set_error("%s: %s: line %lld, column %u: not a number", who_, path_, (long long)line, col); break;
+    }
+    return LDW_ERR_ARG;
 }
 
 namespace {

@@ -94,8 +94,7 @@ __global__ __launch_bounds__(256) void k_states_to_text(const uint8_t *__restric
 
 // per context: the staging of the writer (made on first use, kept for the next call; ldw_host_trim / ldw_ctx_destroy give it back)
 struct OutState {
-    void *pin[2] = {nullptr, nullptr};
-    size_t pin_cap = 0;
+    PinnedPair pin;
     DevBuf img, rec_off, name_off, names, idx;
     hipEvent_t ev[2][3] = {};   // per pinned buffer: before the kernels, after them, after the copy
 };
@@ -105,35 +104,10 @@ OutState *out_state(ldw_ctx *c) {
     return static_cast<OutState *>(c->out);
 }
 
-int64_t free_pins(OutState *o) {
-    int64_t n = 0;
-    for (auto &p : o->pin) {
-        if (p) {
-            (void)hipHostFree(p);
-            n += (int64_t)o->pin_cap;
-        }
-        p = nullptr;
-    }
-    o->pin_cap = 0;
-    return n;
-}
-
-int ensure_pins(OutState *o, size_t bytes) {
+int make_events(OutState *o) {
     for (auto &row : o->ev)
         for (auto &e : row)
             if (!e) LDW_HIP(hipEventCreate(&e));
-    if (o->pin_cap < bytes) {
-        free_pins(o);
-        for (auto &p : o->pin)
-            if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                p = nullptr;
-                free_pins(o);
-                set_error("ldw_write_alignment: hipHostMalloc of %zu bytes failed", bytes);
-                return LDW_ERR_HIP;
-            }
-        o->pin_cap = bytes;
-    }
     return LDW_OK;
 }
 
@@ -158,7 +132,7 @@ void out_release(ldw_ctx *c) {
     auto *o = static_cast<OutState *>(c->out);
     if (!o) return;
     (void)hipStreamSynchronize(c->stream);
-    free_pins(o);
+    o->pin.release();
     for (DevBuf *b : {&o->img, &o->rec_off, &o->name_off, &o->names, &o->idx}) b->release();
     for (auto &row : o->ev)
         for (auto &e : row)
@@ -172,7 +146,7 @@ int64_t out_trim(ldw_ctx *c) {
     if (!o) return 0;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    const int64_t n = free_pins(o) + (int64_t)o->img.cap;
+    const int64_t n = o->pin.release() + (int64_t)o->img.cap;
     o->img.release();
     return n;
 }
@@ -228,7 +202,8 @@ int ldw_write_alignment(ldw_ctx *c, const char *path, int append, int format, co
     int rc = LDW_OK;
     OutState *o = out_state(c);
     do {
-        if ((rc = ensure_pins(o, (size_t)cap))) break;
+        if ((rc = make_events(o))) break;
+        if ((rc = o->pin.reserve((size_t)cap, "ldw_write_alignment"))) break;
         if ((rc = o->img.reserve((size_t)cap))) break;
         if ((rc = o->rec_off.reserve((size_t)(N + 1) * 8))) break;
         if ((rc = o->name_off.reserve((size_t)(N + 1) * 8))) break;
@@ -261,7 +236,7 @@ int ldw_write_alignment(ldw_ctx *c, const char *path, int append, int format, co
         }
         const int64_t bytes = rec_off[(size_t)cuts[(size_t)i + 1]] - rec_off[(size_t)cuts[(size_t)i]];
         const auto w0 = std::chrono::steady_clock::now();
-        if (int r = write_all(fd, static_cast<const char *>(o->pin[b]), (size_t)bytes, path)) return r;
+        if (int r = write_all(fd, static_cast<const char *>(o->pin.p[b]), (size_t)bytes, path)) return r;
         t_write += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
         total += bytes;
         return LDW_OK;
@@ -285,7 +260,7 @@ int ldw_write_alignment(ldw_ctx *c, const char *path, int append, int format, co
         }
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(o->ev[b][1], c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(o->pin[b], o->img.p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(o->pin.p[b], o->img.p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipEventRecord(o->ev[b][2], c->stream);
         if (e != hipSuccess) {
             rc = hip_fail(e, "ldw_write_alignment: chunk", __FILE__, __LINE__);
