@@ -1,7 +1,7 @@
 """Randomised parity against the oracle on ONE re-used context (r05).  The fixed-input parity tests of test_gpu_parity.py each start from a fresh problem; a
 sequence of random small problems — shapes, weightings, block sizes, short-range distances, retention targets, index lists in any order — run one after the other
 on the same engine also covers state that survives between problems (tools/fuzz_paths.py found such a bug in r05).  Checked per case, through the C ABI:
-Hamming weights (bit-exact), unweighted joint counts of random pairs (bit-exact), the dense MI of a random index-list pair in the reference's quirk mode against
+Hamming weights and shared counts (bit-exact), unweighted joint counts of random pairs (bit-exact), the dense MI of a random index-list pair in the reference's quirk mode against
 the block-faithful oracle and in the intended mode against the per-pair direct oracle (1e-10), and the link tables of every block pair against the oracle's
 selection rule (R/computePairwiseMI.R:306-364) applied to the device's own dense MI: short-range rows in the reference's order with the dense block's bits,
 long-range rows equal as a set with the same threshold.  Part of the cases rewrite a share of the alignment first (tools/fuzz_paths.py mutate():
@@ -51,7 +51,8 @@ def test_random_problems_on_one_context_against_the_oracle(engine, seed):
         engine.set_engine(L.ENGINE_MFMA)
         engine.set_alignment(st)
         # Hamming weights: bit-exact
-        hd = engine.hamming_weights(int(p["L"] * p["thr"]))
+        hd, shared = engine.hamming_weights(int(p["L"] * p["thr"]), want_shared=True)
+        assert np.array_equal(shared, orc.shared_counts(st)), tag
         assert np.array_equal(hd, orc.hamming_weights(st, p["thr"])), tag
         hdw = {"hamming": hd, "unit": np.ones(p["N"]), "few": r2.choice([0.5, 0.25, 1.0 / 3, 0.02], size=p["N"]),
                "distinct": 1.0 / (1.0 + r2.permutation(p["N"])), "wide": 10.0 ** r2.uniform(-5.0, 0.0, p["N"]),
