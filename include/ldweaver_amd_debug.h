@@ -141,6 +141,10 @@ int ldw_span_report(ldw_ctx *ctx, int64_t out[4]);
  * is switched off for the rest of the pass after such an overflow (ldw_reset_speculation switches it on again), out[3] entries handed to the
  * maybe list since the context was created. */
 int ldw_overflow_report(ldw_ctx *ctx, int64_t out[4]);
+/* The per-slot device buffers of a block's launch chain (csrc/ldw_slots.h): out[0] reallocations since the context was created — a buffer that
+ * had to grow where it is used, or that ldw_ctx_reserve had not made —, out[1..5] bytes held now, summed over the pipeline slots, by the unit
+ * lists, the per-block SNP constants, the pair lists, the row bins / flags and the maybe list's extracts. */
+int ldw_slot_report(ldw_ctx *ctx, int64_t out[6]);
 
 /* ---- inspection and test hooks (BOUNDS.md; tests/test_bounds.py brute-forces every bound of the default path through them;
  *      ldweaver_amd/csrc/ldw_debug.hip) ------------------------------------------------------------------------------------------- */

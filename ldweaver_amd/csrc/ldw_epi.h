@@ -5,6 +5,7 @@
 #include "ldw_internal.h"
 #include "ldw_dev.h"
 #include "ldw_log.h"
+#include "ldw_slots.h"   // the records of the per-slot buffers (ColInfo, ColMeta, RowPack, PairEnt, ...) and the buffers' layouts
 
 namespace ldw {
 
@@ -30,15 +31,6 @@ __host__ __device__ __forceinline__ double bucket_lo(int B) {
     return v;
 }
 
-// Short-range partners of one to-side SNP: up to three disjoint, ascending index intervals [s,e) of the
-// from-side list, plus the first row of its upper (a_loc < b_loc) and lower (a_loc > b_loc) segment in
-// the short-range table (relative to the block's base row).
-struct ColInfo {
-    int32_t s[3], e[3];
-    int32_t pad[2];
-    int64_t off_u, off_l;
-};
-
 // (bitwise on purpose: with && / || the compiler branches per interval under a divergent exec mask — three s_and_saveexec chains per pair in the screens of
 // the blocks with short-range pairs)
 __host__ __device__ __forceinline__ bool col_is_sr(const ColInfo &c, int a) {
@@ -53,6 +45,11 @@ __host__ __device__ __forceinline__ int col_count(const ColInfo &c, int lo, int 
         n += b > a ? b - a : 0;
     }
     return n;
+}
+
+// How a kernel reads RXY (quirk Q1): 0 = as intended, r r'; the reference's linear index on 1 = a square block, 2 = a ragged one, 3 = a span's segment
+__host__ __device__ __forceinline__ int rxy_read_mode(int quirk, int span, bool square) {
+    return quirk == LDW_QUIRK_REFERENCE ? (span ? 3 : (square ? 1 : 2)) : 0;
 }
 
 // which segment a pair belongs to: 0 = upper (a<b, off-diagonal blocks only), 1 = lower (a>b), -1 = not a pair
@@ -241,31 +238,12 @@ __host__ __device__ __forceinline__ int lo_class(int nrows) { return nrows <= 1 
 // the upper / lower triangle, the row-order key a + b nf of the selection), RXY as the reference's linear index reads it (Q1), the histogram,
 // candidate list and pick of the long-range filter (per block: R/computePairwiseMI.R:352-358).  A column carries its segment in
 // ColMeta::ci.pad[0] and its segment's first to-side index in ci.pad[1] (k_build_packs).
-constexpr int LDW_SPAN_MAX = 8;
 struct SpanSeg {
     unsigned long long *n_cand;     // candidate counter of the segment (PickOut::n_cand)
     uint64_t *ckey, *cval;          // its candidate list
     unsigned long long *ghist;      // its NBINS histogram counters
 };
 
-// r05: what k_screen_maybe needs of a biallelic SNP, in 32 bytes instead of the ~200-byte ColMeta / RowPack (its entries arrive from the GEMM's
-// epilogue in region order, ~17 M per span on data without rare states, and the kernel was bound by the gathers of the two full records:
-// 1.32 ms per span).  Built by k_build_packs from the _hi packs (marginals of the APPROXIMATE weights: < 2^31 units); 0 / -1 for other SNPs.
-struct MiniCol {
-    int32_t pb0;        // approximate minor marginal (units of 2^e_last)
-    float pY0, pY1;     // weighted marginals of the two states (ColMeta::pYf)
-    float rb, rq;       // r of the SNP; Q1 on square blocks / spans: r[idx_f[b_loc]]
-    int32_t bl, seg0;   // local index in its reference block; first to-side index of its segment (a span's ColInfo::pad[1])
-    int32_t sb;
-};
-struct MiniRow {
-    int32_t pa0, pa1;
-    float pX0, pX1;
-    float ra, rta;
-    int32_t a_loc, sa;
-};
-
-struct PairEnt;
 struct EpiArgs {
     const int64_t *G;
     int RFpad, RTpad;
@@ -326,13 +304,6 @@ __host__ __device__ __forceinline__ int tab_bin(float p, float c, int nb) {
     const int b = (int)(sqrtf(p > 0.0f ? p : 0.0f) * c);
     return b < nb - 1 ? b : nb - 1;
 }
-// a listed candidate pair: from-slot index (64 * tile + lane), column slot, first bit row | row count << 29 of both SNPs
-struct PairEnt {
-    uint32_t t, q, ra, rb;
-};
-constexpr int PAIR_PATHS = 5;    // (NA, NB) = (1,1) (2,1) (1,2) (2,2) straight-line code, 4 = predicated
-constexpr int PAIR_SHARDS = 8;
-
 // arguments of the gathered low-limb GEMM (ldw_gemm_bits.hip)
 struct LoGemmArgs {
     const uint64_t *Mbits;
@@ -345,41 +316,6 @@ struct LoGemmArgs {
 };
 
 int launch_gemm_lo_units(ldw_ctx *ctx, const LoGemmArgs &P, int n_tf, hipStream_t stream);
-
-// everything the epilogue needs about one to-side SNP, staged in LDS once per workgroup so that the
-// per-pair loop has no dependent global loads except its G entries
-struct ColMeta {
-    int32_t sb;
-    uint32_t mb;
-    int32_t rb0, bl;   // first row position in the to-side row list; local index of the SNP in the to-side list
-    double rb;      // r of the to-side SNP
-    double rq;      // Q1 on square blocks: r[idx_f[b_loc]]
-    double pYd[5];
-    int64_t pb[5];
-    float pYf[5];
-    int32_t pad2;
-#ifdef LDW_COLMETA_PAD   // measurement only: how sensitive are the screens to the size of the staged column?
-    char padx[LDW_COLMETA_PAD];
-#endif
-    ColInfo ci;
-};
-
-// per-lane constants of the from-side SNP
-struct RowSide {
-    int sa, na;
-    uint32_t ma;
-    int64_t ra0;
-    double ra, rta;  // rta: Q1 on square blocks, r[idx_t[a_loc]]
-    int64_t pa[5];
-    double pXd[5];
-    float pXf[5];
-};
-
-struct RowPack {
-    RowSide R;
-    int32_t a_loc;   // local index in the from-side list, -1: padding slot of the tile
-    int32_t pad;
-};
 
 // MI of one pair.  NAM / NB bound the unrolled slot loops (na <= NAM for every lane of the wave, nb <= NB);
 // the run-time slot counts still mask the individual cells.

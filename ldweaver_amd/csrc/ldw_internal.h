@@ -156,6 +156,7 @@ struct ldw_ctx {
     // Spans (r04, docs/HISTORY.md 6b): consecutive long-range-only blocks of one block row run as ONE launch sequence over their concatenated to side
     bool span_on = true;               // ldw_set_span / LDW_NO_SPAN
     int span_max = 8;                  // most reference blocks per span (LDW_SPAN_MAX env, <= ldw::LDW_SPAN_MAX)
+    int64_t slot_grown = 0;              // reallocations of a slot buffer where it is used (launch_block_apx; ldw_slot_report out[0])
     int64_t maybe_entries = 0;           // entries handed to the maybe list since the context was created (ldw_overflow_report out[3])
     int64_t pair_list_overflows = 0, maybe_overflows = 0;   // blocks / segments redone because a pair list / the maybe list overflowed (ldw_overflow_report)
     bool maybe_off = false;              // the maybe list overflowed in this pass: off until ldw_reset_speculation / new weights

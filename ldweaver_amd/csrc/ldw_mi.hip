@@ -113,26 +113,23 @@ int join_prepare(ldw_ctx *c) {
     return rc;
 }
 
-// ldw_ctx_reserve's side thread: the per-slot device buffers of a pass of blocks of `blk` SNPs (spans of up to nseg of them), from estimates
-// of the row counts (1.25 rows per SNP + padding; a C4 block has 1.16) — whatever turns out too small grows where it is used, as before.
+// ldw_ctx_reserve's side thread: the per-slot device buffers of a pass of blocks of `blk` SNPs (spans of up to nseg of them), from the estimated
+// geometry of its largest item (slot_geom_estimate, ldw_slots.h) — whatever turns out too small grows where it is used, as before.
 int reserve_slot_buffers(ldw_ctx *c, int64_t Npad, int64_t blk, int64_t nseg) {
     const int64_t KW = Npad / 64;
-    const int64_t nt = blk * nseg;
-    const size_t RF = (size_t)((blk * 5 / 4 + 512 + 127) / 128 * 128), RT = (size_t)((nt * 5 / 4 + 512 + 127) / 128 * 128);
-    const size_t nf_tiles = (size_t)(blk / 64 + 6), nf_slots = nf_tiles * 64;
-    const size_t n_units = nf_tiles * (size_t)nt;
-    const size_t cap = pair_cap_for(blk, nt, (int)nseg);
-    const size_t o_cph = ((size_t)nt * sizeof(ColMeta) + 255) / 256 * 256, o_rph = ((size_t)nf_slots * sizeof(RowPack) + 255) / 256 * 256;
+    const SlotGeom g = slot_geom_estimate(blk, nseg);
+    const size_t RF = (size_t)g.RFpad, RT = (size_t)g.RTpad;
+    const size_t cap = pair_cap_for(g.nf, g.nt, g.nseg);
     const size_t one = (size_t)blk * (size_t)blk;
     for (int s = 0; s < LDW_NSLOT; ++s) {
         if (int rc = c->panel[s][0].reserve(RF * (size_t)KW * 16)) return rc;   // (the scaled panel of k_pack_panel: 16 bytes per word)
         if (int rc = c->panel[s][1].reserve(RT * (size_t)KW * 16)) return rc;
         if (int rc = c->Gapx[s].reserve(RF * RT * 4)) return rc;
-        if (int rc = c->apx_units[s].reserve(64 + 2 * n_units * 8 + 64)) return rc;
-        if (int rc = c->apx_packs[s].reserve(2 * o_cph + 2 * o_rph + ((size_t)blk + (size_t)nt) * 4 + 1024)) return rc;
-        if (int rc = c->apx_mini[s].reserve(((size_t)nt + nf_slots) * 32 + 512)) return rc;
-        if (int rc = c->pairs[s].reserve(256 + (size_t)PAIR_PATHS * PAIR_SHARDS * cap * sizeof(PairEnt) + (size_t)maybe_cap_for((int64_t)RT, (int64_t)RF) * sizeof(ApxMaybe) + 64)) return rc;
-        if (int rc = c->apx_bins[s].reserve(2 * (RT + RF) + (size_t)nt + nf_slots + 256 + (RT / 128) * (RF / 64) * 4)) return rc;
+        if (int rc = UnitsLayout(g).reserve(c->apx_units[s])) return rc;
+        if (int rc = PacksLayout(g).reserve(c->apx_packs[s])) return rc;
+        if (int rc = MiniLayout(g).reserve(c->apx_mini[s])) return rc;
+        if (int rc = PairsLayout((uint32_t)cap, maybe_cap_for(g.RTpad, g.RFpad)).reserve(c->pairs[s])) return rc;
+        if (int rc = BinsLayout(g).reserve(c->apx_bins[s])) return rc;
         if (int rc = c->apx_clean[s].reserve((RT / 32) * (RF / 64) + 64)) return rc;
         if (int rc = c->hist[s].reserve((size_t)nseg * NBINS * 8)) return rc;
         const size_t cand = std::max<size_t>(one, (size_t)nseg * std::min<size_t>(one, (size_t)PAIR_PATHS * PAIR_SHARDS * cap));
@@ -817,15 +814,13 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
         }
         if (hb.empty()) return LDW_OK;
         const size_t nb = hb.size();
-        const size_t o_cu = nb * sizeof(SrBlkDev), o_cl = o_cu + (size_t)ncols * 4, o_rows = (o_cl + (size_t)ncols * 4 + 7) / 8 * 8, o_base = o_rows + nb * 8,
-                     o_bad = o_base + (nb + 1) * 8;
-        if (int rc = c->srd_seg.reserve(o_bad + 8)) return rc;
+        Carve cv;   // the blocks, their columns' upper / lower counts, the blocks' rows and first rows, the flag of a column that needs the host
+        auto d_blk = cv.take<SrBlkDev>((int64_t)nb);
+        auto d_cu = cv.take<int32_t>(ncols), d_cl = cv.take<int32_t>(ncols);
+        auto d_rows = cv.take<int64_t>((int64_t)nb), d_base = cv.take<int64_t>((int64_t)nb + 1);
+        auto d_bad = cv.take<int>(2);
+        if (int rc = cv.reserve(c->srd_seg)) return rc;
         if (int rc = c->srd_out.reserve((size_t)ncols * sizeof(ColInfo))) return rc;
-        char *aux = c->srd_seg.as<char>();
-        SrBlkDev *d_blk = reinterpret_cast<SrBlkDev *>(aux);
-        int32_t *d_cu = reinterpret_cast<int32_t *>(aux + o_cu), *d_cl = reinterpret_cast<int32_t *>(aux + o_cl);
-        int64_t *d_rows = reinterpret_cast<int64_t *>(aux + o_rows), *d_base = reinterpret_cast<int64_t *>(aux + o_base);
-        int *d_bad = reinterpret_cast<int *>(aux + o_bad);
         ColInfo *d_cols = c->srd_out.as<ColInfo>();
         LDW_HIP(hipMemcpyAsync(d_blk, hb.data(), nb * sizeof(SrBlkDev), hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemsetAsync(d_bad, 0, 8, c->stream));
@@ -943,6 +938,21 @@ int ldw_set_span(ldw_ctx *c, int on, int max_blocks) {
     LDW_REQUIRE(!(on & 6), LDW_ERR_STATE, "ldw_set_span: corner spans / split diagonal blocks (bits 1, 2; formerly the LDW_EXPERIMENTS build's) were measured slower and have been removed");
     c->span_on = on != 0;
     if (max_blocks) c->span_max = max_blocks;
+    return LDW_OK;
+}
+
+int ldw_slot_report(ldw_ctx *c, int64_t out[6]) {
+    LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_slot_report: null argument");
+    if (int rc = join_prepare(c)) return rc;   // (ldw_ctx_reserve's side thread may still be sizing the buffers)
+    for (int k = 1; k < 6; ++k) out[k] = 0;
+    out[0] = c->slot_grown;
+    for (int s = 0; s < LDW_NSLOT; ++s) {
+        out[1] += (int64_t)c->apx_units[s].cap;
+        out[2] += (int64_t)c->apx_packs[s].cap;
+        out[3] += (int64_t)c->pairs[s].cap;
+        out[4] += (int64_t)c->apx_bins[s].cap;
+        out[5] += (int64_t)c->apx_mini[s].cap;
+    }
     return LDW_OK;
 }
 

@@ -264,24 +264,15 @@ void fill_epi_args(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RFp
 constexpr int EVB = 6;
 // which: 1 = GEMM only (on gstream, into Gbuf), 2 = epilogue only, 3 = both
 constexpr int HI_LIMBS = 3, LO_LIMBS = 2;   // mixed-precision split of the 5 weight limbs
-constexpr size_t PAIR_CAP = 1u << 18;       // most entries per pair list of the approximate path (PAIR_PATHS x PAIR_SHARDS lists)
-// capacity of the pair lists of one block: an eighth of the block's pairs (a shard's fair share of ALL of them), between 2^12 and
-// PAIR_CAP.  Small blocks (tests, several engines on one GPU) then take megabytes instead of the fixed 1.4 GB; a list that
-// overflows makes the block fall back like a wrong guess (k_pick_bucket: spec_ok = 0), so results never depend on it.
-// nseg > 4: the lists of a span of that many reference blocks (about 4e4 listed pairs per 10k x 10k block, most of them in ONE of the five
-// paths: 3-state x 3-state SNP pairs) get twice the room.  g_pair_cap_override (ldw_set_pair_cap, tests only): a fixed small capacity, so
+// capacity of the pair lists of one block: pair_cap_of (ldw_slots.h), or g_pair_cap_override (ldw_set_pair_cap, tests only): a fixed small capacity, so
 // that the overflow fallback can be exercised.
 static std::atomic<uint32_t> g_pair_cap_override{0};
 inline uint32_t pair_cap_for(int64_t nf, int64_t nt, int nseg = 0) {
     const uint32_t ovr = g_pair_cap_override.load();
     if (ovr) return ovr;
-    const uint64_t top = nseg > 4 ? 2 * PAIR_CAP : PAIR_CAP;
-    uint64_t want = (uint64_t)nf * (uint64_t)nt / PAIR_SHARDS + 1, cap = 1u << 12;
-    while (cap < want && cap < top) cap <<= 1;
-    return (uint32_t)cap;
+    return pair_cap_of(nf, nt, nseg);
 }
-// entries of the maybe list of an item (ApxGemmArgs::maybe).  r05: the WORST case — every region of 32 to-rows x 64 from-rows of the row
-// rectangle hands over APX_MAYBE_MAX entries (0.56 B per entry of G', a seventh of G' itself) — so the list cannot overflow whatever the data
+// entries of the maybe list of an item (ApxGemmArgs::maybe): maybe_cap_of (ldw_slots.h), the worst case, so the list cannot overflow whatever the data
 // look like.  r04 sized it for "one pair in a few thousand fails its table thresholds" (nf nt / 256 + 65 536), which holds on alignments full
 // of rare states; on an alignment without them (MAF 0.2-0.5: the bench's adversarial leg) most regions hand over tens of entries, the list
 // overflowed on nearly every block and each of them was redone on the plain path — 216 ms per pass against 155 ms for the plain path itself.
@@ -290,7 +281,7 @@ inline uint32_t maybe_cap_for(int64_t RTpad, int64_t RFpad) {
         const long k = atol(e);
         if (k > 0) return (uint32_t)k;
     }
-    return (uint32_t)std::min<int64_t>(((RTpad + 31) / 32) * ((RFpad + 63) / 64) * (int64_t)APX_MAYBE_MAX + 64, (int64_t)1 << 30);
+    return maybe_cap_of(RTpad, RFpad);
 }
 // a block (or a span's segment) redone because a list overflowed (PickOut::over): counted, and a maybe list that overflowed — impossible at its
 // worst-case capacity, so only under LDW_MAYBE_CAP — is switched off for the rest of the pass instead of overflowing item after item
@@ -300,6 +291,50 @@ inline void note_overflow(ldw_ctx *c, int over) {
         ++c->maybe_overflows;
         c->maybe_off = true;
     }
+}
+// The run-time RXY read mode (rxy_read_mode, ldw_epi.h) as a template argument: f(std::integral_constant<int, RM>).  SPAN = false leaves mode 3 out:
+// the chain of launch_block_mi runs no span, and its screen is not instantiated for one.
+template <bool SPAN = true, class F> void with_rxy_mode(int rm, F &&f) {
+    if (rm == 0) f(std::integral_constant<int, 0>{});
+    else if (rm == 1) f(std::integral_constant<int, 1>{});
+    else if (rm == 2 || !SPAN) f(std::integral_constant<int, 2>{});
+    else if constexpr (SPAN) f(std::integral_constant<int, 3>{});
+}
+// the units outside k_mi_screen's domain, in one launch over both regions: generic from-tiles x all columns, the other tiles x the generic columns
+template <bool APX> void launch_screen_generic(const EpiArgs &A, const DevPtrs &D, int n_tiles, const UnitsLayout &U, hipStream_t st) {
+    const int gt0 = std::min<int>(A.gen_t0, n_tiles);
+    GenRegions Rg;
+    Rg.tile0_a = gt0;
+    Rg.nt_a = n_tiles - gt0;
+    Rg.ncg_a = Rg.nt_a > 0 ? (A.nt + GEN_COLS - 1) / GEN_COLS : 0;
+    Rg.nt_b = (gt0 > 0 && A.gen_q0 < A.nt) ? gt0 : 0;
+    Rg.q0_b = std::min<int>(A.gen_q0, A.nt) / GEN_COLS * GEN_COLS;
+    Rg.ncg_b = Rg.nt_b > 0 ? (A.nt - Rg.q0_b + GEN_COLS - 1) / GEN_COLS : 0;
+    const long long nblk = (long long)Rg.nt_a * Rg.ncg_a + (long long)Rg.nt_b * Rg.ncg_b;
+    if (nblk > 0)
+        hipLaunchKernelGGL(k_mi_screen_generic<APX>, dim3((unsigned)nblk), dim3(256), 0, st, A, D.perm, D.perm_t, U.flat, U.counters, U.list_stride, Rg);
+}
+// the fp64 MI of the listed units: the straight-line code over the first flat list, the predicated code over the second
+void launch_units(const EpiArgs &A, const DevPtrs &D, const UnitsLayout &U, unsigned long long *ghist, hipStream_t st) {
+    UnitLists UL;
+    memset(&UL, 0, sizeof(UL));
+    UL.units[0] = U.flat;
+    UL.n[0] = U.counters;
+    hipLaunchKernelGGL(k_mi_units<true>, dim3(2048, 1), dim3(256), 0, st, A, D.perm, D.perm_t, UL, ghist);
+    UnitLists UG;
+    memset(&UG, 0, sizeof(UG));
+    UG.units[0] = U.flat + U.list_stride;
+    UG.n[0] = U.counters + 1;
+    hipLaunchKernelGGL(k_mi_units<false>, dim3(512, 1), dim3(256), 0, st, A, D.perm, D.perm_t, UG, ghist);
+}
+// the per-block SNP constants k_build_packs wrote (it runs with none set: it derives what the packs then hold); hi: the screen reads the _hi copies
+void bind_packs(EpiArgs &A, const PacksLayout &K, bool hi) {
+    A.rloc_f = K.rloc_f;
+    A.rloc_t = K.rloc_t;
+    A.colpack = K.cp;
+    A.colpack_hi = hi ? K.cp_hi : K.cp;
+    A.rowpack = K.rp;
+    A.rowpack_hi = hi ? K.rp_hi : K.rp;
 }
 int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RFpad, int RTpad, int quirk, EmitArgs E,
                     hipEvent_t *ev, int which, ldw::DevBuf *Gb, hipStream_t gstream, unsigned long long *ghist,
@@ -339,14 +374,10 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
     if (which == 2) LDW_HIP(hipEventRecord(ev[4], c->stream));
     if (A.E.scr_mode && A.E.cols && !A.E.write_dense) {
         // speculative mode: the lean fp32 screen lists the units that need the exact value, k_mi_units evaluates those
-        const size_t n_units_max = (size_t)egrid.x * (size_t)nt;
-        const size_t o_cnt = 64, o_flat = o_cnt + ((size_t)egrid.x * 12 + 63) / 64 * 64, o_tl = o_flat + 2 * n_units_max * 8;
-        const int64_t list_stride = (int64_t)n_units_max;   // two flat lists: straight-line units, the others
-        if (int rc = c->scr_units.reserve(o_tl + n_units_max * 4 + 64)) return rc;
-        char *ub = c->scr_units.as<char>();
-        unsigned int *n_units = reinterpret_cast<unsigned int *>(ub);
-        uint64_t *units = reinterpret_cast<uint64_t *>(ub + o_flat);
-        LDW_HIP(hipMemsetAsync(ub, 0, o_flat, c->stream));   // the unit counter and the per-(tile, class) counters
+        const SlotGeom g{nf, nt, RFpad, RTpad, (int64_t)egrid.x, 0, mixed != nullptr};
+        UnitsLayout U(g);
+        if (int rc = U.reserve(c->scr_units)) return rc;
+        LDW_HIP(hipMemsetAsync(U.zeroed().p, 0, U.zeroed().bytes, c->stream));
         if (mixed) {
             LDW_REQUIRE(mixed->ntiles == (int)egrid.x, LDW_ERR_STATE, "mixed-precision geometry does not match the epilogue grid");
             if (int rc = ensure_hi_marginals(c)) return rc;
@@ -362,55 +393,27 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
             lo.on = 1;
             lo.cmax_f = D.cmax_f;
             lo.tile_base = D.tile_base;
-            lo.cnt = reinterpret_cast<unsigned int *>(ub + o_cnt);
-            lo.tl = reinterpret_cast<uint32_t *>(ub + o_tl);
+            lo.cnt = U.tile_cnt();
+            lo.tl = U.tl;
             lo.glo = c->glo.as<int32_t>();
             lo.slot_pfix_hi = c->slot_pfix_hi.as<int64_t>();
             lo.hi_shift = 8 * LO_LIMBS;
         }
         {   // per-block SNP constants in epilogue order (A.lo is final by now: the high-limb marginals are reachable)
-            const int nf_slots = (int)egrid.x * 64;
-            const size_t o_cph = ((size_t)nt * sizeof(ColMeta) + 255) / 256 * 256, o_rp = 2 * o_cph;
-            const size_t o_rph = o_rp + ((size_t)nf_slots * sizeof(RowPack) + 255) / 256 * 256;
-            const size_t o_rf = o_rph + ((size_t)nf_slots * sizeof(RowPack) + 255) / 256 * 256, o_rt = o_rf + ((size_t)nf * 4 + 255) / 256 * 256;
-            if (int rc = c->packs.reserve(o_rt + (size_t)nt * 4 + 256)) return rc;
-            char *pb = c->packs.as<char>();
-            ColMeta *cp = reinterpret_cast<ColMeta *>(pb), *cph = reinterpret_cast<ColMeta *>(pb + o_cph);
-            RowPack *rp = reinterpret_cast<RowPack *>(pb + o_rp), *rph = reinterpret_cast<RowPack *>(pb + o_rph);
-            float *rlf = reinterpret_cast<float *>(pb + o_rf), *rlt = reinterpret_cast<float *>(pb + o_rt);
-            const int nthr = std::max<int>((int)nt, nf_slots);
-            hipLaunchKernelGGL(k_build_packs, dim3((unsigned)((nthr + 255) / 256), 2), dim3(256), 0, c->stream, A, D.perm, D.perm_t, nf_slots,
-                               mixed ? 1 : 0, cp, cph, rp, rph, rlf, rlt);
-            A.rloc_f = rlf;
-            A.rloc_t = rlt;
+            PacksLayout K(g);
+            if (int rc = K.reserve(c->packs)) return rc;
+            const int nthr = std::max<int>((int)nt, (int)g.nf_slots());
+            hipLaunchKernelGGL(k_build_packs, dim3((unsigned)((nthr + 255) / 256), 2), dim3(256), 0, c->stream, A, D.perm, D.perm_t, (int)g.nf_slots(),
+                               mixed ? 1 : 0, K.cp, K.cp_hi, K.rp, K.rp_hi, K.rloc_f, K.rloc_t);
             LDW_HIP(hipGetLastError());
-            A.colpack = cp;
-            A.colpack_hi = mixed ? cph : cp;
-            A.rowpack = rp;
-            A.rowpack_hi = mixed ? rph : rp;
+            bind_packs(A, K, mixed != nullptr);
         }
-        const int rm = quirk == LDW_QUIRK_REFERENCE ? (nf == nt ? 1 : 2) : 0;
-        if (rm == 0) hipLaunchKernelGGL((k_mi_screen<0, false>), egrid, dim3(256), 0, c->stream, A, D.perm, D.perm_t, units, n_units, list_stride);
-        else if (rm == 1) hipLaunchKernelGGL((k_mi_screen<1, false>), egrid, dim3(256), 0, c->stream, A, D.perm, D.perm_t, units, n_units, list_stride);
-        else hipLaunchKernelGGL((k_mi_screen<2, false>), egrid, dim3(256), 0, c->stream, A, D.perm, D.perm_t, units, n_units, list_stride);
+        with_rxy_mode<false>(rxy_read_mode(quirk, 0, nf == nt), [&](auto RM) {
+            hipLaunchKernelGGL((k_mi_screen<decltype(RM)::value, false>), egrid, dim3(256), 0, c->stream, A, D.perm, D.perm_t, U.flat, U.counters, U.list_stride);
+        });
         LDW_HIP(hipGetLastError());
-        {   // the units outside k_mi_screen's domain: generic from-tiles x all columns, the other tiles x the generic columns
-            const int gt0 = std::min<int>(A.gen_t0, (int)egrid.x);
-            const int q0 = std::min<int>(A.gen_q0, (int)nt) / GEN_COLS * GEN_COLS;
-            {
-                GenRegions Rg;
-                Rg.tile0_a = gt0;
-                Rg.nt_a = (int)egrid.x - gt0;
-                Rg.ncg_a = Rg.nt_a > 0 ? (int)((nt + GEN_COLS - 1) / GEN_COLS) : 0;
-                Rg.nt_b = (gt0 > 0 && A.gen_q0 < (int)nt) ? gt0 : 0;
-                Rg.q0_b = q0;
-                Rg.ncg_b = Rg.nt_b > 0 ? (int)((nt - q0 + GEN_COLS - 1) / GEN_COLS) : 0;
-                const long long nblk = (long long)Rg.nt_a * Rg.ncg_a + (long long)Rg.nt_b * Rg.ncg_b;
-                if (nblk > 0)
-                    hipLaunchKernelGGL(k_mi_screen_generic<false>, dim3((unsigned)nblk), dim3(256), 0, c->stream, A, D.perm, D.perm_t, units, n_units, list_stride, Rg);
-            }
-            LDW_HIP(hipGetLastError());
-        }
+        launch_screen_generic<false>(A, D, (int)egrid.x, U, c->stream);
+        LDW_HIP(hipGetLastError());
         if (mixed) {   // low limbs of the listed units
             LoGemmArgs P;
             P.Mbits = c->Mbits.as<uint64_t>();
@@ -429,16 +432,7 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
             P.lo = A.lo;
             if (int rc = launch_gemm_lo_units(c, P, mixed->n_tf, c->stream)) return rc;
         }
-        UnitLists UL;
-        memset(&UL, 0, sizeof(UL));
-        UL.units[0] = units;
-        UL.n[0] = n_units;
-        hipLaunchKernelGGL(k_mi_units<true>, dim3(2048, 1), dim3(256), 0, c->stream, A, D.perm, D.perm_t, UL, ghist);
-        UnitLists UG;
-        memset(&UG, 0, sizeof(UG));
-        UG.units[0] = units + list_stride;
-        UG.n[0] = n_units + 1;
-        hipLaunchKernelGGL(k_mi_units<false>, dim3(512, 1), dim3(256), 0, c->stream, A, D.perm, D.perm_t, UG, ghist);
+        launch_units(A, D, U, ghist, c->stream);
         LDW_HIP(hipGetLastError());
     } else {
         // the straight-line units first (k_mi_epilogue_fast: 5 waves per SIMD), then the predicated code over the units it listed (ldw_mi_eval.inc)
@@ -449,19 +443,13 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
             unsigned int *n_rest = c->epi_rest.as<unsigned int>();
             uint64_t *rest = reinterpret_cast<uint64_t *>(c->epi_rest.as<char>() + 64);
             LDW_HIP(hipMemsetAsync(n_rest, 0, 64, c->stream));
-            const int rm = quirk != LDW_QUIRK_REFERENCE ? 0 : (A.span ? 3 : (nf == nt ? 1 : 2));
             const int mode = !A.E.cols ? 0 : (A.E.spec_B >= 0 ? 2 : 1);
-#define LDW_EPI_FAST_LAUNCH(RM, MODE) hipLaunchKernelGGL((k_mi_epilogue_fast<RM, MODE>), egrid, dim3(256), 0, c->stream, A, D.perm, D.perm_t, ghist, rest, n_rest)
-#define LDW_EPI_FAST_MODES(RM)              \
-    if (mode == 0) LDW_EPI_FAST_LAUNCH(RM, 0); \
-    else if (mode == 1) LDW_EPI_FAST_LAUNCH(RM, 1); \
-    else LDW_EPI_FAST_LAUNCH(RM, 2)
-            if (rm == 0) { LDW_EPI_FAST_MODES(0); }
-            else if (rm == 1) { LDW_EPI_FAST_MODES(1); }
-            else if (rm == 2) { LDW_EPI_FAST_MODES(2); }
-            else { LDW_EPI_FAST_MODES(3); }
-#undef LDW_EPI_FAST_MODES
-#undef LDW_EPI_FAST_LAUNCH
+            with_rxy_mode(rxy_read_mode(quirk, A.span, nf == nt), [&](auto RM) {
+                constexpr int rm = decltype(RM)::value;
+                if (mode == 0) hipLaunchKernelGGL((k_mi_epilogue_fast<rm, 0>), egrid, dim3(256), 0, c->stream, A, D.perm, D.perm_t, ghist, rest, n_rest);
+                else if (mode == 1) hipLaunchKernelGGL((k_mi_epilogue_fast<rm, 1>), egrid, dim3(256), 0, c->stream, A, D.perm, D.perm_t, ghist, rest, n_rest);
+                else hipLaunchKernelGGL((k_mi_epilogue_fast<rm, 2>), egrid, dim3(256), 0, c->stream, A, D.perm, D.perm_t, ghist, rest, n_rest);
+            });
             LDW_HIP(hipGetLastError());
             hipLaunchKernelGGL(k_mi_epilogue_rest, dim3(1024), dim3(256), 0, c->stream, A, D.perm, D.perm_t, ghist, (const uint64_t *)rest, (const unsigned int *)n_rest);
         } else {
@@ -482,7 +470,7 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
 //            the tiles that hold a short-range pair (band_mask: the short-range band is dense, a fifth of a diagonal block);
 //   phase 2 (main stream): exact sums + fp64 MI + emission of the listed pairs (k_pair_sums, k_pair_mi) and the fp64
 //            evaluation of the listed units from the exact tiles (k_mi_units).
-// Everything phase 1 writes is per pipeline slot; both phases derive the same pointers from the slot's buffers.
+// Everything phase 1 writes is per pipeline slot; both phases take their pointers from ONE description of each of the slot's buffers (ldw_slots.h).
 // Events: ev[0] / ev[1] around the packing + approximate GEMM, ev[5] after the screens and the band GEMM (gs); ev[4] / ev[2]
 // around phase 2.
 // ------------------------------------------------------------------------------------------------
@@ -496,14 +484,22 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     dim3 egrid((unsigned)(D.nf_tiles > 0 ? D.nf_tiles : (nf + 63) / 64), (unsigned)((nt + EPI_COLS - 1) / EPI_COLS));
     LDW_REQUIRE(egrid.y <= 65535u, LDW_ERR_ARG, "nt too large for the epilogue grid");
     LDW_REQUIRE(E.scr_mode && E.cols && !E.write_dense, LDW_ERR_STATE, "the approximate path needs the screen");
-    const size_t n_units_max = (size_t)egrid.x * (size_t)nt;
-    const size_t o_flat = 64;
-    const int64_t list_stride = (int64_t)n_units_max;   // two flat lists: straight-line units, the others
-    const int nf_slots = (int)egrid.x * 64;
-    const size_t o_cph = ((size_t)nt * sizeof(ColMeta) + 255) / 256 * 256, o_rp = 2 * o_cph;
-    const size_t o_rph = o_rp + ((size_t)nf_slots * sizeof(RowPack) + 255) / 256 * 256;
-    const size_t o_rf = o_rph + ((size_t)nf_slots * sizeof(RowPack) + 255) / 256 * 256, o_rt = o_rf + ((size_t)nf * 4 + 255) / 256 * 256;
-    const size_t o_pairs = 256;
+    // the slot's buffers: phase 1 reserves them, phase 2 finds them where phase 1 left them
+    const SlotGeom g{nf, nt, RFpad, RTpad, (int64_t)egrid.x, lo_h->span, false};
+    UnitsLayout U(g);
+    PacksLayout K(g);
+    BinsLayout B(g);
+    MiniLayout M(g);
+    const uint32_t pl_cap = pair_cap_for(nf, nt, lo_h->span), maybe_cap = maybe_cap_for(RTpad, RFpad);
+    PairsLayout PL(pl_cap, maybe_cap);
+    auto place = [c, phase](Carve &cv, ldw::DevBuf &b) {
+        if (phase == 1) {
+            c->slot_grown += cv.bytes > b.cap || !b.p ? 1 : 0;
+            return cv.reserve(b);
+        }
+        cv.bind(b);
+        return (int)LDW_OK;
+    };
     const bool use_pairs = E.scr_mode == 1 && E.do_lr;   // verify mode keeps whole units: it must see the dismissed ones
     // units are evaluated from EXACT sums: the 5-limb GEMM of the tiles they live in (all tiles when any unit can be listed)
     const bool need_exact = E.any_sr || !use_pairs || lo_h->band_full;
@@ -519,21 +515,19 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
             if (int rc = c->panel[s][1].reserve((size_t)RTpad * c->KW * 16)) return rc;
         if (E.do_lr)
             if (int rc = c->Gapx[s].reserve((size_t)RFpad * RTpad * 4)) return rc;
-        if (int rc = c->apx_units[s].reserve(o_flat + 2 * n_units_max * 8 + 64)) return rc;
-        if (int rc = c->apx_packs[s].reserve(o_rt + (size_t)nt * 4 + 256)) return rc;
-        if (use_pairs)
-            if (int rc = c->pairs[s].reserve(o_pairs + (size_t)PAIR_PATHS * PAIR_SHARDS * pair_cap_for(nf, nt, lo_h->span) * sizeof(PairEnt) +
-                                             (size_t)maybe_cap_for(RTpad, RFpad) * sizeof(ApxMaybe) + 64))
-                return rc;
         if (need_exact)
             if (int rc = Gx.reserve((size_t)RFpad * RTpad * 8)) return rc;
-        if (int rc = c->apx_bins[s].reserve(2 * ((size_t)RTpad + (size_t)RFpad) + (size_t)nt + (size_t)nf_slots + 256 + (size_t)(RTpad / 64) * (size_t)(RFpad / 64) * 4)) return rc;   // (the tile list at its finest: 64 x 64 wave tiles)
         if (int rc = c->apx_clean[s].reserve((size_t)(RTpad / 32) * (size_t)(RFpad / 64) + 64)) return rc;
         if (!c->apx_skip.p) {
             if (int rc = c->apx_skip.reserve(64)) return rc;
             LDW_HIP(hipMemsetAsync(c->apx_skip.p, 0, 64, gs));
         }
     }
+    if (int rc = place(U, c->apx_units[s])) return rc;
+    if (int rc = place(K, c->apx_packs[s])) return rc;
+    if (int rc = place(B, c->apx_bins[s])) return rc;
+    if (use_pairs)
+        if (int rc = place(PL, c->pairs[s])) return rc;
     if (phase == 1) {
         if (E.do_lr) {
             // threshold table of the biallelic pairs, one per block kind (diagonal blocks sit ~8 % below the others): valid for every
@@ -584,15 +578,14 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     // long-range-only blocks: the GEMM applies the table itself and neither stores nor lets the screen read the regions that pass
     const bool fuse = lo_h->fuse_ok && A.tab11 && A.tab_nb == 64 && (use_pairs || c->screen == 2) && E.do_lr && (!E.any_sr || (D.band_mask && !lo_h->band_full)) && RFpad % 64 == 0 &&   // (verify mode: the clean regions' units are listed as dismissed and checked in fp64)
                       2048 + (size_t)(c->KW / 2) * 256 + 64 * 64 * 8 + 1024 <= 65536;   // (the table shares the GEMM's LDS with the digit arrays)
-    uint8_t *bin_t = c->apx_bins[s].as<uint8_t>(), *bin_f = bin_t + RTpad;
-    // pruning flags by row (zeroed per block: padding rows) and by epilogue slot
-    // ... and, zeroed with the row flags, the count of the wave tiles the pruning leaves (k_apx_live_tiles), whose list ends the buffer
-    uint8_t *rflag_t = bin_f + RFpad, *rflag_f = rflag_t + RTpad;
-    unsigned int *n_live = reinterpret_cast<unsigned int *>(rflag_f + RFpad);
-    uint8_t *sflag_t = rflag_f + RFpad + 16, *sflag_f = sflag_t + ((size_t)nt + 15) / 16 * 16;
-    uint32_t *tile_list = reinterpret_cast<uint32_t *>(sflag_f + ((size_t)nf_slots + 15) / 16 * 16);
+    // pruning flags by row and by epilogue slot
     const bool wide_prune = c->prune && c->snp_sup.p && E.do_lr && (use_pairs || c->screen == 2);
+    uint8_t *sflag_f = nullptr, *sflag_t = nullptr, *rflag_f = nullptr, *rflag_t = nullptr;
     if (wide_prune) {
+        sflag_f = B.sflag_f;
+        sflag_t = B.sflag_t;
+        rflag_f = B.rflag_f;
+        rflag_t = B.rflag_t;
         A.snp_sup = c->snp_sup.as<double>();
         A.sflag_f = sflag_f;
         A.sflag_t = sflag_t;
@@ -601,17 +594,10 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
         A.clean = c->apx_clean[s].as<uint8_t>();
         A.clean_stride = RFpad / 64;
     }
-    char *ub = c->apx_units[s].as<char>();
-    unsigned int *n_units = reinterpret_cast<unsigned int *>(ub);
-    uint64_t *units = reinterpret_cast<uint64_t *>(ub + o_flat);
-    char *pb = c->apx_packs[s].as<char>();
-    ColMeta *cp = reinterpret_cast<ColMeta *>(pb), *cph = reinterpret_cast<ColMeta *>(pb + o_cph);
-    RowPack *rp = reinterpret_cast<RowPack *>(pb + o_rp), *rph = reinterpret_cast<RowPack *>(pb + o_rph);
-    float *rlf = reinterpret_cast<float *>(pb + o_rf), *rlt = reinterpret_cast<float *>(pb + o_rt);
     if (use_pairs) {
-        A.pl_n = c->pairs[s].as<unsigned int>();
-        A.pl_pairs = reinterpret_cast<PairEnt *>(c->pairs[s].as<char>() + o_pairs);
-        A.pl_cap = pair_cap_for(nf, nt, lo_h->span);
+        A.pl_n = PL.hdr;
+        A.pl_pairs = PL.lists;
+        A.pl_cap = pl_cap;
     }
     // r04: table-eligible regions with a few failing entries hand those entries over instead of being stored and screened (k_screen_maybe);
     // the counter lives in the zeroed header of the pair lists, the entries behind the lists
@@ -620,19 +606,16 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     // region: at N = 616 the GEMM's launch went from 0.091 to 0.107 ms and the pass from 19.4 to 20.1 ms with it, at N = 5000 the launch does
     // not move and the pass gains 0.3-0.4 ms; building the mask only in failing regions was slower at both sizes)
     const bool use_maybe = maybe_on && !c->maybe_off && fuse && use_pairs && c->screen == 1 && !E.lower_only && c->KW >= 32;
-    unsigned int *maybe_n = use_maybe ? c->pairs[s].as<unsigned int>() + 48 : nullptr;
-    const unsigned int maybe_cap = maybe_cap_for(RTpad, RFpad);
-    ApxMaybe *maybe_list = use_maybe ? reinterpret_cast<ApxMaybe *>(c->pairs[s].as<char>() + o_pairs + (size_t)PAIR_PATHS * PAIR_SHARDS * A.pl_cap * sizeof(PairEnt)) : nullptr;
+    unsigned int *maybe_n = nullptr;
+    ApxMaybe *maybe_list = nullptr;
     MiniCol *mini_c = nullptr;
     MiniRow *mini_r = nullptr;
-    if (use_maybe) {   // r05: the 32-byte extracts of the _hi packs k_screen_maybe reads (both phases derive the same pointers)
-        const size_t o_mr = ((size_t)nt * sizeof(MiniCol) + 255) / 256 * 256;
-        if (phase == 1)
-            if (int rc = c->apx_mini[s].reserve(o_mr + (size_t)nf_slots * sizeof(MiniRow) + 64)) return rc;
-        mini_c = c->apx_mini[s].as<MiniCol>();
-        mini_r = reinterpret_cast<MiniRow *>(c->apx_mini[s].as<char>() + o_mr);
-        A.mini_c = mini_c;
-        A.mini_r = mini_r;
+    if (use_maybe) {
+        maybe_n = PL.hdr + PH_MAYBE_N;
+        maybe_list = PL.maybe;
+        if (int rc = place(M, c->apx_mini[s])) return rc;
+        A.mini_c = mini_c = M.col;
+        A.mini_r = mini_r = M.row;
     }
     if (phase == 1) {
         if (E.do_lr) {
@@ -643,12 +626,12 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
         {   // the unit counters, the pair-list counters, this slot's histogram and pick record (submit_b skips its own memsets)
             ZeroArgs Z;
             memset(&Z, 0, sizeof(Z));
-            Z.p[0] = reinterpret_cast<uint4 *>(ub);
-            Z.n16[0] = (unsigned int)((o_flat + 15) / 16);
-            if (use_pairs) {
-                Z.p[1] = reinterpret_cast<uint4 *>(c->pairs[s].p);
-                Z.n16[1] = (unsigned int)((o_pairs + 15) / 16);
-            }
+            auto zero = [&Z](int k, const Carve::Range &r) {
+                Z.p[k] = reinterpret_cast<uint4 *>(r.p);
+                Z.n16[k] = r.n16();
+            };
+            zero(0, U.zeroed());
+            if (use_pairs) zero(1, PL.zeroed());
             if (fuse) {
                 // Every region must read "not clean" unless THIS block's GEMM (or its live-tile pass) says otherwise.  r01-r05 zeroed the flags of diagonal
                 // blocks only (the GEMM skips their tiles above the diagonal) and relied on every other region being rewritten by every launch — which holds
@@ -657,8 +640,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
                 Z.p[4] = reinterpret_cast<uint4 *>(c->apx_clean[s].p);
                 Z.n16[4] = (unsigned int)(((size_t)(RTpad / 32) * (size_t)(RFpad / 64) + 15) / 16);
             }
-            Z.p[5] = reinterpret_cast<uint4 *>(rflag_t);
-            Z.n16[5] = (unsigned int)(((size_t)RTpad + (size_t)RFpad) / 16 + 1);
+            zero(5, B.zeroed());
             if (zero_hist) {
                 Z.p[2] = reinterpret_cast<uint4 *>(zero_hist);
                 Z.n16[2] = (unsigned int)((size_t)NBINS * 8 / 16 * (size_t)(lo_h->span ? lo_h->span : 1));   // (a span: one histogram per reference block)
@@ -668,10 +650,9 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
             hipLaunchKernelGGL(k_zero4, dim3(16), dim3(256), 0, gs, Z);
         }
         // the per-SNP constants in epilogue order — before the GEMM: its epilogue reads the table bins by row
-        const int nthr = std::max<int>(std::max<int>((int)nt, nf_slots), std::max<int>(RTpad, RFpad));
-        hipLaunchKernelGGL(k_build_packs, dim3((unsigned)((nthr + 255) / 256), 2), dim3(256), 0, gs, A, D.perm, D.perm_t, nf_slots, 1, cp, cph, rp, rph,
-                           rlf, rlt, bin_t, bin_f, RTpad, RFpad, wide_prune ? sflag_f : nullptr, wide_prune ? sflag_t : nullptr, wide_prune ? rflag_f : nullptr,
-                           wide_prune ? rflag_t : nullptr, mini_c, mini_r);
+        const int nthr = std::max<int>(std::max<int>((int)nt, (int)g.nf_slots()), std::max<int>(RTpad, RFpad));
+        hipLaunchKernelGGL(k_build_packs, dim3((unsigned)((nthr + 255) / 256), 2), dim3(256), 0, gs, A, D.perm, D.perm_t, (int)g.nf_slots(), 1, K.cp, K.cp_hi, K.rp,
+                           K.rp_hi, K.rloc_f, K.rloc_t, B.bin_t, B.bin_f, RTpad, RFpad, sflag_f, sflag_t, rflag_f, rflag_t, mini_c, mini_r);
         LDW_HIP(hipGetLastError());
         ApxGemmArgs P;
         if (E.do_lr) {
@@ -691,15 +672,13 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
                 P.fuse = 1;
                 P.skip_ctr = (c->prune && lo_h->ordered) ? c->apx_skip.as<unsigned long long>() : nullptr;   // (list order: a tile spans every bin)
                 if (P.skip_ctr) {
-                    P.tile_list = tile_list;
-                    P.n_live = n_live;
-                }
-                if (P.skip_ctr && wide_prune) {
+                    P.tile_list = B.tile_list;
+                    P.n_live = B.n_live;
                     P.rflag_t = rflag_t;
                     P.rflag_f = rflag_f;
                 }
-                P.bin_t = bin_t;
-                P.bin_f = bin_f;
+                P.bin_t = B.bin_t;
+                P.bin_f = B.bin_f;
                 P.tab = A.tab11;
                 P.tab_nb = A.tab_nb;
                 P.clean = c->apx_clean[s].as<uint8_t>();
@@ -718,12 +697,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
             if (int rc = launch_gemm_apx(c, P, gs)) return rc;
         LDW_HIP(hipEventRecord(ev[1], gs));
     }
-    A.rloc_f = rlf;
-    A.rloc_t = rlt;
-    A.colpack = cp;
-    A.colpack_hi = cph;
-    A.rowpack = rp;
-    A.rowpack_hi = rph;
+    bind_packs(A, K, true);
     // The block's screen at the head of phase 2 on the main stream — beside the NEXT block's GEMM on the GEMM stream — instead of behind
     // its own GEMM.
     // (r04, first attempt: a span's screen at the head of phase 2 went WRONG — phase 2 is queued after the first phase of LATER items, which may
@@ -738,14 +712,15 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     // is 2.7 ms of a 19-ms pass, the GEMM queue would idle and the main queue carry everything — 20.9 / 21.1 against 19.3 / 19.1 ms — so short
     // alignments keep the old places.
     const bool screen_main = c->KW >= swap_kw;
-    const int rm_s = quirk == LDW_QUIRK_REFERENCE ? (lo_h->span ? 3 : (nf == nt ? 1 : 2)) : 0;
-#define LDW_SCREEN(RMv, ST) hipLaunchKernelGGL((k_mi_screen<RMv, true>), egrid, dim3(256), 0, ST, A, D.perm, D.perm_t, units, n_units, list_stride)
+    const int rm = rxy_read_mode(quirk, lo_h->span, nf == nt);
+    auto screen = [&](hipStream_t st) {
+        with_rxy_mode(rm, [&](auto RM) {
+            hipLaunchKernelGGL((k_mi_screen<decltype(RM)::value, true>), egrid, dim3(256), 0, st, A, D.perm, D.perm_t, U.flat, U.counters, U.list_stride);
+        });
+    };
     if (phase == 1) {
         if (!screen_main) {
-            if (rm_s == 0) LDW_SCREEN(0, gs);
-            else if (rm_s == 1) LDW_SCREEN(1, gs);
-            else if (rm_s == 3) LDW_SCREEN(3, gs);
-            else LDW_SCREEN(2, gs);
+            screen(gs);
             LDW_HIP(hipGetLastError());
         }
         if (band_early && need_exact)
@@ -754,10 +729,9 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
                 return rc;
         if (use_maybe && E.do_lr) {
             constexpr unsigned MAYBE_GRID = 512u;   // (r05: 512 / 2048 / 8192 / 32768 workgroups measured on the adversarial alignment — no difference: the kernel was bound by its atomics)
-            if (rm_s == 0) hipLaunchKernelGGL((k_screen_maybe<0>), dim3(MAYBE_GRID), dim3(256), 0, gs, A, maybe_list, maybe_n, maybe_cap);
-            else if (rm_s == 1) hipLaunchKernelGGL((k_screen_maybe<1>), dim3(MAYBE_GRID), dim3(256), 0, gs, A, maybe_list, maybe_n, maybe_cap);
-            else if (rm_s == 3) hipLaunchKernelGGL((k_screen_maybe<3>), dim3(MAYBE_GRID), dim3(256), 0, gs, A, maybe_list, maybe_n, maybe_cap);
-            else hipLaunchKernelGGL((k_screen_maybe<2>), dim3(MAYBE_GRID), dim3(256), 0, gs, A, maybe_list, maybe_n, maybe_cap);
+            with_rxy_mode(rm, [&](auto RM) {
+                hipLaunchKernelGGL((k_screen_maybe<decltype(RM)::value>), dim3(MAYBE_GRID), dim3(256), 0, gs, A, maybe_list, maybe_n, maybe_cap);
+            });
             LDW_HIP(hipGetLastError());
         }
         LDW_HIP(hipEventRecord(ev[5], gs));
@@ -766,28 +740,10 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     // ---- phase 2 ----
     LDW_HIP(hipEventRecord(ev[4], s2));
     if (screen_main) {
-        if (rm_s == 0) LDW_SCREEN(0, s2);
-        else if (rm_s == 1) LDW_SCREEN(1, s2);
-        else if (rm_s == 3) LDW_SCREEN(3, s2);
-        else LDW_SCREEN(2, s2);
+        screen(s2);
         LDW_HIP(hipGetLastError());
     }
-#undef LDW_SCREEN
-    // the units outside k_mi_screen's domain: generic from-tiles x all columns, the other tiles x the generic columns
-    const int gt0 = std::min<int>(A.gen_t0, (int)egrid.x);
-    const int q0 = std::min<int>(A.gen_q0, (int)nt) / GEN_COLS * GEN_COLS;
-    {
-        GenRegions Rg;
-        Rg.tile0_a = gt0;
-        Rg.nt_a = (int)egrid.x - gt0;
-        Rg.ncg_a = Rg.nt_a > 0 ? (int)((nt + GEN_COLS - 1) / GEN_COLS) : 0;
-        Rg.nt_b = (gt0 > 0 && A.gen_q0 < (int)nt) ? gt0 : 0;
-        Rg.q0_b = q0;
-        Rg.ncg_b = Rg.nt_b > 0 ? (int)((nt - q0 + GEN_COLS - 1) / GEN_COLS) : 0;
-        const long long nblk = (long long)Rg.nt_a * Rg.ncg_a + (long long)Rg.nt_b * Rg.ncg_b;
-        if (nblk > 0)
-            hipLaunchKernelGGL(k_mi_screen_generic<true>, dim3((unsigned)nblk), dim3(256), 0, s2, A, D.perm, D.perm_t, units, n_units, list_stride, Rg);
-    }
+    launch_screen_generic<true>(A, D, (int)egrid.x, U, s2);
     LDW_HIP(hipGetLastError());
     if (need_exact && !band_early)
         if (int rc = launch_gemm_bits(c, c->Mbits.as<uint64_t>(), c->KW, D.rl_t, RTpad, D.rl_f, RFpad, Gx.as<int64_t>(), c->nlimbs, c->digits.as<int8_t>(),
@@ -802,18 +758,9 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
         Ax.G = Gx.as<int64_t>();
         Ax.E.apx = 0;
         Ax.pl_pairs = nullptr;
-        UnitLists UL;
-        memset(&UL, 0, sizeof(UL));
-        UL.units[0] = units;
-        UL.n[0] = n_units;
-        hipLaunchKernelGGL(k_mi_units<true>, dim3(2048, 1), dim3(256), 0, s2, Ax, D.perm, D.perm_t, UL, ghist);
-        UnitLists UG;
-        memset(&UG, 0, sizeof(UG));
-        UG.units[0] = units + list_stride;
-        UG.n[0] = n_units + 1;
-        hipLaunchKernelGGL(k_mi_units<false>, dim3(512, 1), dim3(256), 0, s2, Ax, D.perm, D.perm_t, UG, ghist);
+        launch_units(Ax, D, U, ghist, s2);
     }
-    hipLaunchKernelGGL(k_apx_stats, dim3(1), dim3(64), 0, s2, n_units, A.pl_n, A.pl_cap, A.E.scr_viol + 1);
+    hipLaunchKernelGGL(k_apx_stats, dim3(1), dim3(64), 0, s2, U.counters, A.pl_n, A.pl_cap, A.E.scr_viol + 1);
     LDW_HIP(hipGetLastError());
     LDW_HIP(hipEventRecord(ev[2], s2));
     return LDW_OK;

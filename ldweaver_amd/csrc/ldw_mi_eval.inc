@@ -435,7 +435,7 @@ __global__ void k_apx_stats(const unsigned int *__restrict__ n_units, const unsi
     if (pl_n)
         for (int i = 0; i < PAIR_PATHS * PAIR_SHARDS; ++i) k += pl_n[i] > pl_cap ? pl_cap : pl_n[i];
     acc[1] += k;
-    if (pl_n) acc[2] += (unsigned long long)pl_n[48];   // r05: entries the GEMM's epilogue handed to the maybe list (word 48 of the zeroed list header; 0 when the list is off)
+    if (pl_n) acc[2] += (unsigned long long)pl_n[PH_MAYBE_N];   // r05: entries the GEMM's epilogue handed to the maybe list (0 when the list is off)
 }
 
 // ------------------------------------------------------------------------------------------------

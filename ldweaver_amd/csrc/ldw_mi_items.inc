@@ -551,13 +551,14 @@ int make_emit_args(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
 // bucket pick + copy-back of the pick of slot s on `st`
 int launch_pick(ldw_ctx *c, const HostBlock &hb, const ldw_mi_params *p, const SmallLayout &sl, hipStream_t st) {
     const int s = hb.slot;
+    const unsigned int *pl_hdr = c->pairs[s].as<unsigned int>();   // (PairsLayout::hdr opens the buffer)
     if (hb.span) {
         PickSpanArgs S;
         memset(&S, 0, sizeof(S));
         for (int k = 0; k < hb.span; ++k) S.n_total[k] = (long long)hb.seg_lr_total[k];
         hipLaunchKernelGGL(k_pick_bucket_span, dim3((unsigned)hb.span), dim3(256), 0, st, c->hist[s].as<unsigned long long>(), p->lr_retain_links,
                            p->lr_links_approx, hb.spec_B, S, reinterpret_cast<char *>(sl.pick[s]), PICK_STRIDE,
-                           reinterpret_cast<const unsigned int *>(c->pairs[s].p), pair_cap_for(hb.nf, hb.nt, hb.span));
+                           pl_hdr, pair_cap_for(hb.nf, hb.nt, hb.span));
         LDW_HIP(hipGetLastError());
         return LDW_OK;
     }
@@ -565,7 +566,7 @@ int launch_pick(ldw_ctx *c, const HostBlock &hb, const ldw_mi_params *p, const S
         const bool pl = hb.apx && c->screen == 1;
         hipLaunchKernelGGL(k_pick_bucket, dim3(1), dim3(256), 0, st, c->hist[s].as<unsigned long long>(), p->lr_retain_links,
                            p->lr_links_approx, hb.spec_B, (long long)hb.n_lr_total, sl.pick[s],
-                           pl ? reinterpret_cast<const unsigned int *>(c->pairs[s].p) : nullptr, pair_cap_for(hb.nf, hb.nt));
+                           pl ? pl_hdr : nullptr, pair_cap_for(hb.nf, hb.nt));
         LDW_HIP(hipGetLastError());
     }
     return LDW_OK;
@@ -1027,7 +1028,7 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
         static const bool trace_on = getenv("LDW_BLOCK_TRACE") != nullptr;
         if (trace_on && picks[0].n > 0 && !picks[0].spec_ok) {   // a span that missed: its pair-list counters (an overflowing list fails every segment)
             unsigned int pl[PAIR_PATHS * PAIR_SHARDS];
-            LDW_HIP(hipMemcpy(pl, c->pairs[s].p, sizeof(pl), hipMemcpyDeviceToHost));
+            LDW_HIP(hipMemcpy(pl, c->pairs[s].as<unsigned int>() + PH_COUNT, sizeof(pl), hipMemcpyDeviceToHost));   // (PairsLayout::hdr opens the buffer)
             fprintf(stderr, "[ldw span at block %lld] guess %d, %d segments, pair-list capacity %u, counters by path:", (long long)hb.blk_no, hb.guess, hb.span, pair_cap_for(hb.nf, hb.nt, hb.span));
             for (int pth = 0; pth < PAIR_PATHS; ++pth) {
                 unsigned long long tot = 0, mx = 0;

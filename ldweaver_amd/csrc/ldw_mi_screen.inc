@@ -698,9 +698,9 @@ template <int RM>
 __global__ __launch_bounds__(256) void k_screen_maybe(EpiArgs A, const ApxMaybe *__restrict__ maybe, const unsigned int *__restrict__ maybe_n,
                                                       unsigned int maybe_cap) {
     const unsigned int n_all = *maybe_n;
-    if (n_all > maybe_cap) {   // the list overflowed: the block takes the pair lists' overflow path — through a word of its own behind the 40 list
+    if (n_all > maybe_cap) {   // the list overflowed: the block takes the pair lists' overflow path — through a word of its own behind the list
         // counters, which k_pick_bucket reads with them (bumping a real counter would make its consumers read entries that were never written)
-        if (blockIdx.x == 0 && threadIdx.x == 0) A.pl_n[PAIR_PATHS * PAIR_SHARDS] = 0xFFFFFFFFu;
+        if (blockIdx.x == 0 && threadIdx.x == 0) A.pl_n[PH_MAYBE_OVER] = 0xFFFFFFFFu;
         return;
     }
     const float lo = (float)A.E.spec_lo - A.E.scr_eps;
@@ -834,7 +834,7 @@ __global__ __launch_bounds__(256) void k_mi_screen_generic(EpiArgs A, const int3
     int n_it = A.nt - q_base;
     n_it = n_it > GEN_COLS / 4 ? GEN_COLS / 4 : n_it;
     if (n_it <= 0) return;
-    const int rxy_mode = A.quirk == LDW_QUIRK_REFERENCE ? (A.span ? 3 : (square ? 1 : 2)) : 0;
+    const int rxy_mode = rxy_read_mode(A.quirk, A.span, square);
     const float lo = (float)A.E.spec_lo - A.E.scr_eps;
     const bool test_sr = A.E.any_sr != 0 || A.sr_excl != 0, keep_sr = A.E.keep_sr != 0 && !A.sr_excl, do_lr = A.E.do_lr != 0;
     unsigned int wanted = 0, mine = 0;   // mine: the units of this wave that belong to this kernel

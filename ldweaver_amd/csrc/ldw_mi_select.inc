@@ -96,7 +96,7 @@ __device__ __forceinline__ void pick_bucket_body(const unsigned long long *__res
                 int over = 0;
                 if (pl_n) {
                     for (int i = 0; i < PAIR_PATHS * PAIR_SHARDS; ++i) over |= pl_n[i] > pl_cap ? 1 : 0;
-                    over |= pl_n[PAIR_PATHS * PAIR_SHARDS] > pl_cap ? 2 : 0;   // (word 40: the maybe list's overflow, k_screen_maybe)
+                    over |= pl_n[PH_MAYBE_OVER] > pl_cap ? 2 : 0;   // (the maybe list's overflow, k_screen_maybe)
                 }
                 out->over = over;
                 out->spec_ok = over ? 0 : 1;

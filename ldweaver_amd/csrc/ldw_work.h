@@ -3,6 +3,7 @@
 #pragma once
 #include <algorithm>
 
+#include "ldw_carve.h"   // Carve: the carving of one working buffer into typed arrays
 #include "ldw_internal.h"
 #include "ldw_prim.h"
 
@@ -17,28 +18,6 @@ inline dim3 grid_of(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std:
         hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);  \
         LDW_HIP(hipGetLastError());                                         \
     } while (0)
-
-// Bump allocation of one working buffer in 256-byte steps: take<T>(n) names an array of max(n, 1) elements and its element type once; after
-// reserve() the Slot it returned converts to the array's T * (pointer arithmetic and calls take it as one).
-struct Carve {
-    template <class T> struct Slot {
-        const Carve *cv;
-        size_t off;
-        operator T *() const { return reinterpret_cast<T *>(cv->base + off); }
-    };
-    size_t bytes = 0;
-    char *base = nullptr;
-    template <class T> Slot<T> take(int64_t n) {
-        const size_t o = bytes;
-        bytes += ((size_t)std::max<int64_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
-        return Slot<T>{this, o};
-    }
-    int reserve(DevBuf &b) {
-        const int rc = b.reserve(bytes);
-        base = b.as<char>();
-        return rc;
-    }
-};
 
 // ldw_post.hip.  The ascending order of the context's positions, built on first use after they change (one stable sort of h_POS: SNPs of one
 // position stay in index order) and kept on the device in ctx->pos_ord: slot / n_slots unless POS ascends strictly, srt / order unless it ascends.

@@ -162,6 +162,12 @@ class Engine:
         L.check(L.lib().ldw_overflow_report(self._ctx, L.ptr(v)))
         return dict(pair_list=int(v[0]), maybe_list=int(v[1]), maybe_off=bool(v[2]), maybe_entries=int(v[3]))
 
+    def slot_report(self):
+        """The per-slot device buffers of a block's launch chain: reallocations since the context was created and the bytes held now."""
+        v = np.zeros(6, dtype=np.int64)
+        L.check(L.lib().ldw_slot_report(self._ctx, L.ptr(v)))
+        return dict(grown=int(v[0]), units=int(v[1]), packs=int(v[2]), pairs=int(v[3]), bins=int(v[4]), mini=int(v[5]))
+
     @staticmethod
     def set_pair_cap(cap: int):
         """Tests only: a fixed capacity of the approximate path's pair lists (0: automatic), process-wide."""

@@ -444,6 +444,7 @@ def test_new_entry_points_refuse_bad_arguments_without_a_gpu():
     assert lib.ldw_lr_stream_end(None, None, None, None) == L.LDW_ERR_ARG
     assert lib.ldw_tsv_join(None) == L.LDW_ERR_ARG
     assert lib.ldw_overflow_report(None, L.ptr(np.zeros(4, dtype=np.int64))) == L.LDW_ERR_ARG
+    assert lib.ldw_slot_report(None, L.ptr(np.zeros(6, dtype=np.int64))) == L.LDW_ERR_ARG
     assert lib.ldw_build_info() == 0
     # r05, the short-range model over ranks: no context -> LDW_ERR_ARG, never a crash
     z8, zi = np.zeros(8), np.zeros(8, dtype=np.int64)
