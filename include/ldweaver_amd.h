@@ -576,6 +576,23 @@ typedef struct ldw_capsule {
 int ldw_plot_network(ldw_ctx *ctx, const ldw_capsule *caps, int64_t n_caps, int32_t W, int32_t H, const int32_t *node_xy, const char *const *node_names,
                      int32_t n_nodes, const char *title, const int32_t *legend_value, const uint32_t *legend_rgb, int32_t n_legend, int32_t text_scale,
                      const char *png_path, uint8_t *rgb_out, int32_t *boxes_out);
+/* The tanglegram of create_tanglegram (R/createTanglegram.R): gene-pair links between two genome bars.  The links are capsules, drawn over white
+ * exactly as ldw_plot_network draws them (same coverage test, same blend, list order).  Then every RECTANGLE — the half-open pixel box [x0, x1) x [y0, y1),
+ * clipped to the canvas — is painted OPAQUE over that raster in list order: a pixel takes the colour of the last rectangle that covers it.  An empty rectangle
+ * (x0 = x1 or y0 = y1) paints nothing.  Limits (LDW_ERR_ARG beyond them, before anything runs on the device): those of the capsules; at most 2^16 rectangles,
+ * their coordinates in -8192..16383, x1 >= x0 and y1 >= y0, rgb <= 0xFFFFFF. */
+typedef struct ldw_rect {
+    int32_t x0, y0, x1, y1;   /* half-open */
+    uint32_t rgb;             /* 0xRRGGBB, opaque */
+} ldw_rect;
+/* The figure: capsules and rectangles rendered on the device; then, by the host in the 5 x 7 font at text_scale (1..64), labels[k] read UPWARDS from its
+ * anchor (label_xy[2k], label_xy[2k + 1]) = the bottom-left corner of the turned text (7 text_scale wide, as high as the text is long), and the title (may be
+ * NULL) centred at the top.  The host makes no layout decisions: an empty label draws nothing.  The figure goes to png_path (may be NULL) and / or rgb_out (may
+ * be NULL: H x W x 3 bytes).  boxes_out (may be NULL, (n_labels + 1) x 4 int32): x, y, w, h of what the host drew — the labels, then the title (w = 0: none; an
+ * empty label reports its anchor); a box may reach past the canvas. */
+int ldw_plot_tanglegram(ldw_ctx *ctx, const ldw_capsule *caps, int64_t n_caps, const ldw_rect *rects, int64_t n_rects, int32_t W, int32_t H,
+                        const int32_t *label_xy, const char *const *labels, int32_t n_labels, const char *title, int32_t text_scale, const char *png_path,
+                        uint8_t *rgb_out, int32_t *boxes_out);
 
 /* ---- (13) numeric link tables read on the device — the readers of R/io_functions.R:32-66 (read_LongRangeLinks, read_ShortRangeLinks), and through them
  *           the file inputs of genomewide_LDMap (R/LDSummaryPlot.R), analyse_long_range_links (R/lr_analyser.R) and make_gwes_plots -----------------------

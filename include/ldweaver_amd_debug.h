@@ -197,6 +197,10 @@ int ldw_debug_plot_colours(int kind, const double *t, int64_t n, uint8_t *rgb_ou
 /* The raw raster of ldw_plot_network, before the host draws over it: rgb_out[H][W][3] (host).  ms_out (may be NULL, 2 doubles): hip-event times of the binning
  * (boxes, counts, sums, lists) and of the shading. */
 int ldw_debug_plot_capsules(ldw_ctx *ctx, const ldw_capsule *caps, int64_t n_caps, int32_t W, int32_t H, uint8_t *rgb_out, double *ms_out);
+/* The raw raster of ldw_plot_tanglegram, before the host draws over it: the capsules, then the rectangles: rgb_out[H][W][3] (host).  ms_out (may be NULL, 3
+ * doubles): hip-event times of the binning and the shading of the capsules and of the rectangle pass (copy of the list, owner image, colours). */
+int ldw_debug_plot_marks(ldw_ctx *ctx, const ldw_capsule *caps, int64_t n_caps, const ldw_rect *rects, int64_t n_rects, int32_t W, int32_t H, uint8_t *rgb_out,
+                         double *ms_out);
 /* The raw canvas of ldw_plot_tree (ldweaver_amd.h 15), before the host draws over it: rgb_out[H][W][3] (host).  ms_out (may be NULL, 4 doubles): hip-event
  * times of the clear (coverage image and canvas), the bars (counts, sums, adds), the bands (lines, fill) and the colour pass over the panel. */
 int ldw_debug_plot_tree(ldw_ctx *ctx, int32_t W, int32_t H, const int32_t *panel, const ldw_bar *bars, int64_t n_bars, uint32_t bar_rgb, const uint8_t *levels,

@@ -144,6 +144,7 @@ _SIGS_API = {
     "ldw_plot_heatmap": (C.c_int, [_p, _p, C.c_int32, C.c_int, C.c_char_p, C.c_char_p, _p]),
     "ldw_plot_ldmap": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_char_p, _p, _p, _p, _p, _i64]),
     "ldw_plot_network": (C.c_int, [_p, _p, _i64, C.c_int32, C.c_int32, _p, _p, C.c_int32, C.c_char_p, _p, _p, C.c_int32, C.c_int32, C.c_char_p, _p, _p]),
+    "ldw_plot_tanglegram": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_int32, C.c_int32, _p, _p, C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, _p, _p]),
     "ldw_plot_tree": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p, _i64, C.c_uint32, _p, _i64, _p, _p, C.c_int32, _p, C.c_char_p, _p, _p, _p, _p, _p, C.c_int32,
                                 C.c_char_p, _p, _p]),
     "ldw_tsv_probe": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -195,6 +196,7 @@ _SIGS_DEBUG = {
     "ldw_debug_plot_panels": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, C.c_int, _p, C.c_int, C.c_int32, C.c_int32, _p, _p, C.POINTER(_i64), _p]),
     "ldw_debug_plot_colours": (C.c_int, [C.c_int, _p, _i64, _p]),
     "ldw_debug_plot_capsules": (C.c_int, [_p, _p, _i64, C.c_int32, C.c_int32, _p, _p]),
+    "ldw_debug_plot_marks": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_int32, C.c_int32, _p, _p]),
     "ldw_debug_plot_tree": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p, _i64, C.c_uint32, _p, _i64, _p, _p, C.c_int32, _p, _p]),
     "ldw_links_grep_stats": (C.c_int, [_p, _p]),
     "ldw_tsv_stats": (C.c_int, [_p, _p]),

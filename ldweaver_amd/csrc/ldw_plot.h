@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/ldweaver_amd.h"
+#include "ldw_carve.h"
 
 namespace ldw {
 
@@ -51,6 +52,38 @@ void plot_frame(uint8_t *canvas, const ldw_plot_layout &lay, int kind, const uin
 // the network plot's node labels, title and legend over the edge raster canvas[H][W][3]; boxes (may be NULL): (n_nodes + 2) x 4
 void plot_net_overlay(uint8_t *canvas, int W, int H, const int32_t *node_xy, const char *const *node_names, int n_nodes, const char *title,
                       const int32_t *legend_value, const uint32_t *legend_rgb, int n_legend, int scale, int32_t *boxes);
+
+// N hip events of a timed render: created on demand, destroyed with the object
+template <int N> struct PlotEvents {
+    hipEvent_t e[N] = {};
+    ~PlotEvents() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    hipError_t create() {
+        for (hipEvent_t &x : e)
+            if (hipError_t rc = hipEventCreate(&x)) return rc;
+        return hipSuccess;
+    }
+    // ms[k] = the time from event k to event k + 1 (all recorded, the stream idle)
+    hipError_t elapsed(double *ms) const {
+        for (int k = 0; k + 1 < N; ++k) {
+            float f = 0;
+            if (hipError_t rc = hipEventElapsedTime(&f, e[k], e[k + 1])) return rc;
+            ms[k] = f;
+        }
+        return hipSuccess;
+    }
+};
+
+// ldw_plot_net.hip, shared with the tanglegram (ldw_plot_tng.hip): the capsule checks, and the capsule raster left on the device (see there)
+int check_capsules(const ldw_capsule *caps, int64_t n, int W, int H, const char *who);
+int net_raster_device(ldw_ctx *c, Carve &cv, const ldw_capsule *caps, int64_t n, int W, int H, uint8_t **d_rast_out, hipEvent_t *ev, const char *who);
+
+// the tanglegram's labels (read upwards from their anchors label_xy[2 k], label_xy[2 k + 1]) and title over the device canvas[H][W][3]
+// (ldw_plot_tng.hip); boxes (may be NULL): (n_labels + 1) x 4
+void plot_tng_overlay(uint8_t *canvas, int W, int H, const int32_t *label_xy, const char *const *labels, int n_labels, const char *title, int scale,
+                      int32_t *boxes);
 
 // the tree view's band labels, title and two legends over the device canvas[H][W][3] (ldw_plot_tree.hip); boxes (may be NULL): (n_bands + 3) x 4
 void plot_tree_overlay(uint8_t *canvas, int W, int H, const int32_t *band_rect, const char *const *band_label, int n_bands, const char *title,

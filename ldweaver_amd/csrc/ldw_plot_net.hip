@@ -121,6 +121,8 @@ __global__ __launch_bounds__(256) void k_net_shade(const ldw_capsule *__restrict
     }
 }
 
+}  // namespace
+
 int check_capsules(const ldw_capsule *caps, int64_t n, int W, int H, const char *who) {
     LDW_REQUIRE(W >= 1 && H >= 1 && W <= NET_MAX_DIM && H <= NET_MAX_DIM, LDW_ERR_ARG, "%s: a canvas of %d x %d pixels (1..%d each way)", who, W, H, NET_MAX_DIM);
     LDW_REQUIRE(n >= 0 && n <= NET_MAX_CAPS && (n == 0 || caps), LDW_ERR_ARG, "%s: %lld capsules (0..%lld), or a null list", who, (long long)n, (long long)NET_MAX_CAPS);
@@ -135,16 +137,14 @@ int check_capsules(const ldw_capsule *caps, int64_t n, int W, int H, const char 
     return LDW_OK;
 }
 
-}  // namespace
-
-// the raster of the capsules, rgb_out[H][W][3] (host); ms_out (may be NULL, 2 doubles): hip-event times of the binning and of the shading
-int net_raster(ldw_ctx *c, const ldw_capsule *caps, int64_t n, int W, int H, uint8_t *rgb_out, double *ms_out, const char *who) {
+// The raster of the capsules, left ON THE DEVICE: *d_rast_out[H][W][3] inside ctx->plot_work, valid until that buffer's next use; the work is queued on the
+// context's stream and not waited for.  cv: arrays the caller took for itself beforehand — they are carved from the same buffer, behind which this call
+// puts its own, and are bound when it returns.  ev (may be NULL, 3 created events): recorded before the binning, between binning and shading, after it.
+int net_raster_device(ldw_ctx *c, Carve &cv, const ldw_capsule *caps, int64_t n, int W, int H, uint8_t **d_rast_out, hipEvent_t *ev, const char *who) {
     if (int rc = check_capsules(caps, n, W, H, who)) return rc;
-    LDW_REQUIRE(rgb_out, LDW_ERR_ARG, "%s: null output", who);
     const int ntx = (W + NET_T - 1) / NET_T, nty = (H + NET_T - 1) / NET_T, ntiles = ntx * nty;
     size_t scan_bytes = 0;
     LDW_HIP(prim_scan_bytes<uint32_t>((size_t)ntiles + 1, c->stream, &scan_bytes));
-    Carve cv;
     auto d_caps = cv.take<ldw_capsule>(n);
     auto d_box = cv.take<TileBox>(n);
     auto d_cnt = cv.take<uint32_t>(ntiles + 1);
@@ -152,18 +152,8 @@ int net_raster(ldw_ctx *c, const ldw_capsule *caps, int64_t n, int W, int H, uin
     auto d_tmp = cv.take<uint8_t>((int64_t)scan_bytes);
     auto d_rast = cv.take<uint8_t>((int64_t)W * H * 3);
     if (int rc = cv.reserve(c->plot_work)) return rc;
-    hipEvent_t ev[3] = {};
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() {
-            for (int k = 0; k < 3; ++k)
-                if (e[k]) (void)hipEventDestroy(e[k]);
-        }
-    } guard{ev};
-    if (ms_out)
-        for (auto &e : ev) LDW_HIP(hipEventCreate(&e));
     if (n > 0) LDW_HIP(hipMemcpyAsync(d_caps, caps, (size_t)n * sizeof(ldw_capsule), hipMemcpyHostToDevice, c->stream));
-    if (ms_out) LDW_HIP(hipEventRecord(ev[0], c->stream));
+    if (ev) LDW_HIP(hipEventRecord(ev[0], c->stream));
     LDW_HIP(hipMemsetAsync(d_cnt, 0, (size_t)(ntiles + 1) * 4, c->stream));
     const dim3 bin_grid((ntiles + 255) / 256);
     if (n > 0) {
@@ -178,18 +168,25 @@ int net_raster(ldw_ctx *c, const ldw_capsule *caps, int64_t n, int W, int H, uin
     if (int rc = c->plot_cols.reserve((size_t)std::max<uint32_t>(entries, 1) * 4)) return rc;
     uint32_t *d_list = c->plot_cols.as<uint32_t>();
     if (n > 0) LDW_LAUNCH(k_net_bin<1>, bin_grid, dim3(256), 0, c->stream, (const TileBox *)d_box, n, ntx, ntiles, (uint32_t *)nullptr, (const uint32_t *)d_off, d_list);
-    if (ms_out) LDW_HIP(hipEventRecord(ev[1], c->stream));
+    if (ev) LDW_HIP(hipEventRecord(ev[1], c->stream));
     LDW_LAUNCH(k_net_shade, dim3(ntx, nty), dim3(256), 0, c->stream, (const ldw_capsule *)d_caps, (const uint32_t *)d_off, (const uint32_t *)d_list, W, H, (uint8_t *)d_rast);
-    if (ms_out) LDW_HIP(hipEventRecord(ev[2], c->stream));
+    if (ev) LDW_HIP(hipEventRecord(ev[2], c->stream));
+    *d_rast_out = d_rast;
+    return LDW_OK;
+}
+
+// the raster of the capsules, rgb_out[H][W][3] (host); ms_out (may be NULL, 2 doubles): hip-event times of the binning and of the shading
+int net_raster(ldw_ctx *c, const ldw_capsule *caps, int64_t n, int W, int H, uint8_t *rgb_out, double *ms_out, const char *who) {
+    if (int rc = check_capsules(caps, n, W, H, who)) return rc;
+    LDW_REQUIRE(rgb_out, LDW_ERR_ARG, "%s: null output", who);
+    PlotEvents<3> ev;
+    if (ms_out) LDW_HIP(ev.create());
+    Carve cv;
+    uint8_t *d_rast = nullptr;
+    if (int rc = net_raster_device(c, cv, caps, n, W, H, &d_rast, ms_out ? ev.e : nullptr, who)) return rc;
     LDW_HIP(hipMemcpyAsync(rgb_out, d_rast, (size_t)W * H * 3, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
-    if (ms_out) {
-        float f = 0;
-        LDW_HIP(hipEventElapsedTime(&f, ev[0], ev[1]));
-        ms_out[0] = f;
-        LDW_HIP(hipEventElapsedTime(&f, ev[1], ev[2]));
-        ms_out[1] = f;
-    }
+    if (ms_out) LDW_HIP(ev.elapsed(ms_out));
     return LDW_OK;
 }
 

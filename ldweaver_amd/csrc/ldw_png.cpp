@@ -333,6 +333,38 @@ void plot_tree_overlay(uint8_t *canvas, int W, int H, const int32_t *band_rect, 
     }
 }
 
+// The tanglegram's text over the device canvas (ldw_plot_tng.hip): label k read UPWARDS from its anchor — the bottom-left corner of the turned text, 7
+// scale pixels wide and text_width high — and the title centred at the top.  The anchors are the caller's layout; nothing is moved or left out here.
+// boxes (may be NULL): x, y, w, h of the labels in their order, then of the title (w = 0: an empty string, nothing drawn); a box may reach past the canvas.
+void plot_tng_overlay(uint8_t *canvas, int W, int H, const int32_t *label_xy, const char *const *labels, int n_labels, const char *title, int sc,
+                      int32_t *boxes) {
+    Canvas cv{canvas, W, H};
+    auto note = [&](int k, int x, int y, int w, int h) {
+        if (!boxes) return;
+        boxes[4 * k] = x;
+        boxes[4 * k + 1] = y;
+        boxes[4 * k + 2] = w;
+        boxes[4 * k + 3] = h;
+    };
+    for (int k = 0; k < n_labels; ++k) {
+        const int x = label_xy[2 * k], y = label_xy[2 * k + 1], tw = text_width(labels[k], sc);
+        if (tw == 0) {
+            note(k, x, y, 0, 0);
+            continue;
+        }
+        draw_text(cv, x, y, labels[k], sc, PLOT_TEXT, 1);
+        note(k, x, y - tw + 1, 7 * sc, tw);
+    }
+    if (title && title[0]) {
+        const int st = sc + sc / 2, tw = text_width(title, st);
+        const int x = (W - tw) / 2, y = 2 * sc;
+        draw_text(cv, x, y, title, st, PLOT_TITLE);
+        note(n_labels, x, y, tw, 7 * st);
+    } else {
+        note(n_labels, 0, 0, 0, 0);
+    }
+}
+
 }  // namespace ldw
 
 using namespace ldw;

@@ -714,6 +714,38 @@ class Engine:
                                          os.fsencode(png_path) if png_path is not None else None, L.ptr(canvas), L.ptr(boxes)))
         return canvas, boxes
 
+    # -- the tanglegram (include/ldweaver_amd.h 12) ------------------------------------
+    RECT = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("rgb", "<u4")])
+
+    def debug_plot_marks(self, caps, rects, W: int, H: int, timings: bool = False):
+        """The raw raster of a tanglegram's marks (ldw_debug_plot_marks): the capsules, then the opaque half-open rectangles (structured ``Engine.RECT``
+        array) in list order: uint8 [H, W, 3]; with ``timings`` also (binning, shading, rectangles) in ms."""
+        caps = np.ascontiguousarray(caps, dtype=self.CAPSULE)
+        rects = np.ascontiguousarray(rects, dtype=self.RECT)
+        out = np.empty((int(H), int(W), 3), dtype=np.uint8)
+        ms = np.zeros(3)
+        L.check(L.lib().ldw_debug_plot_marks(self._ctx, L.ptr(caps) if len(caps) else None, len(caps), L.ptr(rects) if len(rects) else None, len(rects), int(W),
+                                             int(H), L.ptr(out), L.ptr(ms) if timings else None))
+        return (out, tuple(ms)) if timings else out
+
+    def plot_tanglegram(self, caps, rects, W: int, H: int, label_xy, labels, title, text_scale: int, png_path=None, want_canvas: bool = False):
+        """The tanglegram figure (ldw_plot_tanglegram): labels read upwards from their anchors.  Returns (canvas uint8 [H, W, 3] or None, boxes int32
+        [labels + 1, 4]: the labels, the title)."""
+        caps = np.ascontiguousarray(caps, dtype=self.CAPSULE)
+        rects = np.ascontiguousarray(rects, dtype=self.RECT)
+        xy = np.ascontiguousarray(label_xy, dtype=np.int32).reshape(-1, 2)
+        names = [x.encode("utf-8", "replace") if isinstance(x, str) else bytes(x) for x in labels]
+        if len(names) != len(xy):
+            raise ValueError(f"{len(names)} labels for {len(xy)} anchors")
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        boxes = np.zeros((len(names) + 1, 4), dtype=np.int32)
+        canvas = np.empty((int(H), int(W), 3), dtype=np.uint8) if want_canvas else None
+        L.check(L.lib().ldw_plot_tanglegram(self._ctx, L.ptr(caps) if len(caps) else None, len(caps), L.ptr(rects) if len(rects) else None, len(rects), int(W),
+                                            int(H), L.ptr(xy) if len(names) else None, C.cast(arr, C.c_void_p) if len(names) else None, len(names),
+                                            (title or "").encode("utf-8", "replace"), int(text_scale), os.fsencode(png_path) if png_path is not None else None,
+                                            L.ptr(canvas), L.ptr(boxes)))
+        return canvas, boxes
+
     # -- the tree view (include/ldweaver_amd.h 15) ------------------------------------
     BAR = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4")])
 
