@@ -556,6 +556,36 @@ int ldw_plot_heatmap(ldw_ctx *ctx, const double *htm, int32_t B, int on_device, 
 int ldw_plot_ldmap(ldw_ctx *ctx, int32_t reducer, int32_t from, int32_t to, const char *title, const char *png_path, int64_t *n_pos_out,
                    int32_t *reducer_out, int32_t *B_out, double *htm_out, int64_t capacity);
 
+/* The "xy" figures: c<i>_fit.png of perform_MI_computation (R/computePairwiseMI.R:430-440) — black points, a red polyline over them — and
+ * CDS_clustering.png of estimate_variation_in_CDS (R/estimateCDSDiversity.R:212-220) — points coloured by class.  The rules are those of the scatter
+ * figures where they apply (axis range, pixel rule, opaque disc, grid lines, font).  Kept points: x, y finite (the others are dropped and counted); cls ==
+ * NULL: class 0; a row, kept or dropped, with cls >= n_classes refuses the call (LDW_ERR_ARG) before anything is drawn.  Draw order = row order, the LATER
+ * row on top: a pixel shows the class of the largest row whose disc covers it.  Line: segment i joins vertices i and i + 1 and exists iff both are finite
+ * (x and y); a finite vertex with no finite neighbour is a disc of diameter line_w; every segment is the opaque capsule of width line_w between the two
+ * vertices' centre pixels by the network plot's integer rule 4 D2 <= w^2 (below), drawn over the points and clipped at the panel.  Axis range: that of the
+ * kept points and the finite vertices together, widened by 5 % (nothing kept: [0, 1]).  line_x / line_y are HOST arrays of at most 2^17 vertices in
+ * drawing order (n_line may be 0); x, y, cls are host or device memory (on_device), host columns passing through the chunk buffer of ldw_plot_scatter. */
+#define LDW_PLOT_FIT 4   /* c<i>_fit.png: 2200 x 1200, one panel under a title; black points, a red line over them */
+#define LDW_PLOT_CDS 5   /* CDS_clustering.png: 2200 x 1200, one panel, points coloured by class, a legend on the right */
+#define LDW_PLOT_MAX_CLASSES 10
+typedef struct ldw_plot_xy_opts {
+    int32_t kind;            /* LDW_PLOT_FIT or LDW_PLOT_CDS */
+    int32_t D;               /* disc diameter, odd, 1..LDW_PLOT_MAX_D; 0 = 11 */
+    int32_t n_classes;       /* 1..LDW_PLOT_MAX_CLASSES */
+    uint32_t class_rgb[LDW_PLOT_MAX_CLASSES];
+    int32_t line_w;          /* polyline width in pixels, 1..1024; 0 = 5 (nominal, like D) */
+    uint32_t line_rgb;
+} ldw_plot_xy_opts;
+/* Host only: ldw_plot_layout_get for the xy figures (kind LDW_PLOT_FIT or LDW_PLOT_CDS; n_panels must be 1).  ldw_plot_layout_get itself keeps to the
+ * kinds 0..3. */
+int ldw_plot_xy_layout_get(int kind, int n_panels, double x_min, double x_max, double y_min, double y_max, ldw_plot_layout *out);
+/* The figure: the panel rendered on the device; then, by the host, the frame, the tick labels, xlab under and ylab beside the panel, for LDW_PLOT_FIT the
+ * title above it and for LDW_PLOT_CDS the legend "Cluster" with one swatch per class (title, xlab, ylab may be NULL).  The figure goes to png_path (may be
+ * NULL) and / or rgb_out (may be NULL: 1200 x 2200 x 3 bytes).  *dropped_out (may be NULL): rows dropped. */
+int ldw_plot_xy(ldw_ctx *ctx, const double *x, const double *y, const uint8_t *cls, int64_t n, int on_device, const double *line_x, const double *line_y,
+                int64_t n_line, const ldw_plot_xy_opts *opts, const char *title, const char *xlab, const char *ylab, const char *png_path, uint8_t *rgb_out,
+                int64_t *dropped_out);
+
 /* The network plot of create_network (R/createNetworkPlot.R:120-139).  Its edges are CAPSULES — the pixels within w / 2 of a segment — blended
  * over a white canvas in list order.  Pixels and endpoints are integer points; with D2 the squared distance from a pixel to the segment (to the nearer end
  * where the projection falls outside it), the pixel is covered iff 4 D2 <= w^2, evaluated exactly in 64-bit integers; a covered pixel takes, per channel,

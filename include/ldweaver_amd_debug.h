@@ -192,6 +192,12 @@ int ldw_debug_screen_bound(ldw_ctx *ctx, int kind, int na, int nb, int64_t n, co
 int ldw_debug_plot_panels(ldw_ctx *ctx, const double *x, const double *y, const double *srp, const uint8_t *layer, const uint8_t *panel, int64_t n,
                           int on_device, const ldw_plot_opts *opts, int n_panels, int32_t W, int32_t H, uint8_t *rgb_out, double *stats_out,
                           int64_t *scratch_bytes_out, double *ms_out);
+/* The panel of ldw_plot_xy without the frame, W x H pixels (1..8192 each way): rgb_out[H][W][3] (host).  Grid lines lie at the ticks of ldw_plot_ticks for the
+ * data range and W / H.  stats_out (may be NULL, 6 doubles): x min, x max, y min, y max of the kept rows and finite line vertices, rows kept, rows dropped.
+ * ms_out (may be NULL, 4 doubles): hip-event times of the statistics pass, the key-image clear, the centre + segment passes and the paint pass. */
+int ldw_debug_plot_xy_panel(ldw_ctx *ctx, const double *x, const double *y, const uint8_t *cls, int64_t n, int on_device, const double *line_x,
+                            const double *line_y, int64_t n_line, const ldw_plot_xy_opts *opts, int32_t W, int32_t H, uint8_t *rgb_out, double *stats_out,
+                            double *ms_out);
 /* Host only: the 2056 colours of the LD map's ramp (kind 0, rgb_out 2056 x 3) or the scatter gradient at t[n] (kind 1, rgb_out n x 3). */
 int ldw_debug_plot_colours(int kind, const double *t, int64_t n, uint8_t *rgb_out);
 /* The raw raster of ldw_plot_network, before the host draws over it: rgb_out[H][W][3] (host).  ms_out (may be NULL, 2 doubles): hip-event times of the binning

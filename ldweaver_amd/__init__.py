@@ -13,6 +13,7 @@ _EXPORTS = {
     "make_gwes_plots": "plots", "read_ShortRangeLinks": "plots", "read_LongRangeLinks": "plots",
     "read_links_native": "links_io",
     "create_tanglegram": "tanglegram",
+    "LDWeaver": "driver", "cleanup": "driver",
     "view_tree": "tree", "read_newick": "tree", "midpoint_root": "tree", "ladderize": "tree",
 }
 __all__ = sorted(_EXPORTS)

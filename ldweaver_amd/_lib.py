@@ -30,6 +30,7 @@ class LdwError(RuntimeError):
 
 PLOT_SR_CLUST, PLOT_SR_COMBI, PLOT_LR, PLOT_LDMAP = 0, 1, 2, 3
 PLOT_MAX_PANELS, PLOT_MAX_TICKS, PLOT_MAX_D, PLOT_NO_PRECHECK = 10, 16, 41, 1
+PLOT_FIT, PLOT_CDS, PLOT_MAX_CLASSES = 4, 5, 10
 
 
 class PlotLayout(C.Structure):
@@ -45,6 +46,12 @@ class PlotOpts(C.Structure):
     """ldw_plot_opts (include/ldweaver_amd.h 12)."""
     _fields_ = [("kind", C.c_int32), ("D", C.c_int32), ("ordered", C.c_int32), ("flags", C.c_int32), ("layer_rgb", C.c_uint32 * 2),
                 ("has_hline", C.c_int32), ("hline_rgb", C.c_uint32), ("hline_y", C.c_double)]
+
+
+class PlotXYOpts(C.Structure):
+    """ldw_plot_xy_opts (include/ldweaver_amd.h 12)."""
+    _fields_ = [("kind", C.c_int32), ("D", C.c_int32), ("n_classes", C.c_int32), ("class_rgb", C.c_uint32 * 10), ("line_w", C.c_int32),
+                ("line_rgb", C.c_uint32)]
 
 
 class MIParams(C.Structure):
@@ -143,6 +150,8 @@ _SIGS_API = {
     "ldw_plot_links": (C.c_int, [_p, C.c_int, C.c_int, _p, C.c_char_p, _p, C.POINTER(_i64)]),
     "ldw_plot_heatmap": (C.c_int, [_p, _p, C.c_int32, C.c_int, C.c_char_p, C.c_char_p, _p]),
     "ldw_plot_ldmap": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_char_p, _p, _p, _p, _p, _i64]),
+    "ldw_plot_xy_layout_get": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _p]),
+    "ldw_plot_xy": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, _p, _p, _i64, _p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _p, C.POINTER(_i64)]),
     "ldw_plot_network": (C.c_int, [_p, _p, _i64, C.c_int32, C.c_int32, _p, _p, C.c_int32, C.c_char_p, _p, _p, C.c_int32, C.c_int32, C.c_char_p, _p, _p]),
     "ldw_plot_tanglegram": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_int32, C.c_int32, _p, _p, C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, _p, _p]),
     "ldw_plot_tree": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p, _i64, C.c_uint32, _p, _i64, _p, _p, C.c_int32, _p, C.c_char_p, _p, _p, _p, _p, _p, C.c_int32,
@@ -194,6 +203,7 @@ _SIGS_DEBUG = {
     "ldw_debug_apx_gemm": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p]),
     "ldw_debug_screen_bound": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ldw_debug_plot_panels": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, C.c_int, _p, C.c_int, C.c_int32, C.c_int32, _p, _p, C.POINTER(_i64), _p]),
+    "ldw_debug_plot_xy_panel": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, _p, _p, _i64, _p, C.c_int32, C.c_int32, _p, _p, _p]),
     "ldw_debug_plot_colours": (C.c_int, [C.c_int, _p, _i64, _p]),
     "ldw_debug_plot_capsules": (C.c_int, [_p, _p, _i64, C.c_int32, C.c_int32, _p, _p]),
     "ldw_debug_plot_marks": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_int32, C.c_int32, _p, _p]),

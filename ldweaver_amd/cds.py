@@ -141,8 +141,9 @@ def estimate_variation_in_CDS(snp_dat: SnpDat, ncores=1, gbk=None, gff: Annotati
     ``engine`` with ``alignment_resident=True``: the engine already holds ``snp_dat``'s alignment (e.g. ``parse_fasta_alignment(...,
     keep_on_device=True)``).  The clustering is the exact optimum of the k-means objective (``kmeans_1d``) where the reference draws
     ``stats::kmeans(nstart = 10)`` from an unseeded RNG.  ``quirk_mode``: QUIRK_REFERENCE reproduces painter's loop, which leaves a last run
-    of one SNP unrecorded (an unpainted such SNP keeps 0, and a UserWarning names it); QUIRK_INTENDED fills it from the left.  No plot is
-    drawn (``clust_plt_path`` is accepted and ignored, like ``ncores`` and ``mega_dset``)."""
+    of one SNP unrecorded (an unpainted such SNP keeps 0, and a UserWarning names it); QUIRK_INTENDED fills it from the left.
+    ``clust_plt_path``: where ``CDS_clustering.png`` is drawn (``plots.cds_cluster_plot``); None draws nothing — the reference's default file
+    ``clust_plt.png`` in the working directory is deliberately not reproduced.  ``ncores`` and ``mega_dset`` are accepted and ignored."""
     if (gbk is None) == (gff is None):
         raise ValueError("Provide either one of gbk or gff")
     if gbk is not None:
@@ -182,6 +183,10 @@ def estimate_variation_in_CDS(snp_dat: SnpDat, ncores=1, gbk=None, gff: Annotati
         warnings.warn(f"SNP {int(idx[0])} (POS {int(np.asarray(snp_dat.POS)[idx[0]])}) keeps paint 0: it is the last SNP, alone in its run, and "
                       "painter does not record that run (R/estimateCDSDiversity.R:166-178); perform_MI_computation's short-range model "
                       "rejects paint 0.  quirk_mode=QUIRK_INTENDED paints it from the left.", UserWarning, stacklevel=2)
-    return CdsVar(paint=paint, nclust=int(num_clusts_CDS), var_estimate=var_estimate, cds_start=cds_start, cds_end=cds_end,
-                  clusts={"km_clst_ord": labels, "cutoff": cutoff}, ref=refc.view("S1").astype("U1"),
-                  alt=[_ALT_OF_MASK[m] for m in alt_mask.tolist()], allele_table=allele_table)
+    cv = CdsVar(paint=paint, nclust=int(num_clusts_CDS), var_estimate=var_estimate, cds_start=cds_start, cds_end=cds_end,
+                clusts={"km_clst_ord": labels, "cutoff": cutoff}, ref=refc.view("S1").astype("U1"),
+                alt=[_ALT_OF_MASK[m] for m in alt_mask.tolist()], allele_table=allele_table)
+    if clust_plt_path is not None:
+        from .plots import cds_cluster_plot
+        cds_cluster_plot(cv, clust_plt_path, engine=engine)
+    return cv

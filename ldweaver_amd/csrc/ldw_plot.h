@@ -49,6 +49,10 @@ int plot_axis(double lo, double hi, int npx, int flip, double lim[2], double *ti
 void plot_frame(uint8_t *canvas, const ldw_plot_layout &lay, int kind, const uint8_t *rasters, const int32_t *panel_label, const char *title,
                 bool cbar_valid, double cb_lo, double cb_hi);
 
+// the frame of an xy figure (ldw_plot_xy.hip) round its one panel: ticks, title, axis labels and, for LDW_PLOT_CDS, the legend "Cluster"
+void plot_xy_frame(uint8_t *canvas, const ldw_plot_layout &lay, int kind, const uint8_t *raster, const char *title, const char *xlab, const char *ylab,
+                   const uint32_t *class_rgb, int n_classes);
+
 // the network plot's node labels, title and legend over the edge raster canvas[H][W][3]; boxes (may be NULL): (n_nodes + 2) x 4
 void plot_net_overlay(uint8_t *canvas, int W, int H, const int32_t *node_xy, const char *const *node_names, int n_nodes, const char *title,
                       const int32_t *legend_value, const uint32_t *legend_rgb, int n_legend, int scale, int32_t *boxes);

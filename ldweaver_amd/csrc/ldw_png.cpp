@@ -218,6 +218,44 @@ void plot_frame(uint8_t *canvas, const ldw_plot_layout &lay, int kind, const uin
     }
 }
 
+// The frame of an xy figure (ldw_plot_xy.hip): the panel's border, ticks and tick labels as in plot_frame; xlab centred under the panel and ylab
+// read upwards beside it; the title (LDW_PLOT_FIT) centred above the panel; for LDW_PLOT_CDS the legend "Cluster" right of the panel, one square
+// swatch and the class number (from 1) per class.  NULL or empty strings draw nothing.
+void plot_xy_frame(uint8_t *canvas, const ldw_plot_layout &lay, int kind, const uint8_t *raster, const char *title, const char *xlab, const char *ylab,
+                   const uint32_t *class_rgb, int n_classes) {
+    Canvas cv{canvas, lay.width, lay.height};
+    memset(canvas, 0xFF, (size_t)lay.width * lay.height * 3);
+    const int pw = lay.panel_w, ph = lay.panel_h, x = lay.panel[0][0], y = lay.panel[0][1];
+    const int sc = 3, st = 4, tick_len = 8;
+    cv.rect(x - 1, y - 1, pw + 2, ph + 2, PLOT_BORDER);
+    for (int j = 0; j < ph; ++j) memcpy(canvas + ((size_t)(y + j) * lay.width + x) * 3, raster + (size_t)j * pw * 3, (size_t)pw * 3);
+    for (int t = 0; t < lay.n_yticks; ++t) {
+        const int ty = y + lay.ytick_px[t];
+        cv.rect(x - 1 - tick_len, ty, tick_len, 1, PLOT_BORDER);
+        const std::string s = fmt_tick(lay.ytick[t]);
+        draw_text(cv, x - 1 - tick_len - 6 - text_width(s.c_str(), sc), ty - (7 * sc) / 2, s.c_str(), sc, PLOT_TEXT);
+    }
+    for (int t = 0; t < lay.n_xticks; ++t) {
+        const int tx = x + lay.xtick_px[t];
+        cv.rect(tx, y + ph + 1, 1, tick_len, PLOT_BORDER);
+        const std::string s = fmt_tick(lay.xtick[t]);
+        draw_text(cv, tx - text_width(s.c_str(), sc) / 2, y + ph + 1 + tick_len + 6, s.c_str(), sc, PLOT_TEXT);
+    }
+    if (xlab && xlab[0]) draw_text(cv, x + (pw - text_width(xlab, st)) / 2, lay.height - 12 - 7 * st, xlab, st, PLOT_TITLE);
+    if (ylab && ylab[0]) draw_text(cv, 12, y + (ph + text_width(ylab, st)) / 2, ylab, st, PLOT_TITLE, 1);
+    if (kind == LDW_PLOT_FIT && title && title[0]) draw_text(cv, x + (pw - text_width(title, st)) / 2, (y - 7 * st) / 2, title, st, PLOT_TITLE);
+    if (kind == LDW_PLOT_CDS) {
+        const int th = 7 * sc, gap = 2 * sc, lx = x + pw + 50;
+        const int ly = y + (ph - (n_classes + 1) * (th + gap)) / 2;
+        draw_text(cv, lx, ly, "Cluster", sc, PLOT_TITLE);
+        for (int k = 0; k < n_classes; ++k) {
+            const int yk = ly + (k + 1) * (th + gap);
+            cv.rect(lx, yk, th, th, class_rgb[k]);
+            draw_text(cv, lx + th + gap, yk, std::to_string(k + 1).c_str(), sc, PLOT_TEXT);
+        }
+    }
+}
+
 // The network plot's text over the edge raster (ldw_plot_net.hip): a white, bordered box with the node's name centred on every node, the title
 // centred at the top, and at the bottom the legend "Num_Links" with one swatch and value per colour.  boxes (may be NULL): x, y, w, h of the node
 // boxes in node order, then of the title and of the legend (w = 0: not drawn).
@@ -434,6 +472,30 @@ int ldw_plot_layout_get(int kind, int n_panels, double x_min, double x_max, doub
     LDW_REQUIRE(plot_axis(x_min, x_max, L.panel_w, 0, L.xlim, L.xtick, L.xtick_px, &L.n_xticks) == LDW_OK &&
                     plot_axis(y_min, y_max, L.panel_h, 1, L.ylim, L.ytick, L.ytick_px, &L.n_yticks) == LDW_OK,
                 LDW_ERR_ARG, "ldw_plot_layout_get: the axis range of the data is not finite");
+    return LDW_OK;
+}
+
+int ldw_plot_xy_layout_get(int kind, int n_panels, double x_min, double x_max, double y_min, double y_max, ldw_plot_layout *out) {
+    LDW_REQUIRE(out, LDW_ERR_ARG, "ldw_plot_xy_layout_get: null output");
+    LDW_REQUIRE(kind == LDW_PLOT_FIT || kind == LDW_PLOT_CDS, LDW_ERR_ARG, "ldw_plot_xy_layout_get: figure kind %d is no xy figure", kind);
+    LDW_REQUIRE(n_panels == 1, LDW_ERR_ARG, "ldw_plot_xy_layout_get: %d panels (an xy figure has one)", n_panels);
+    LDW_REQUIRE(std::isfinite(x_min) && std::isfinite(x_max) && x_min <= x_max && std::isfinite(y_min) && std::isfinite(y_max) && y_min <= y_max,
+                LDW_ERR_ARG, "ldw_plot_xy_layout_get: the data ranges are not finite intervals");
+    ldw_plot_layout &L = *out;
+    memset(&L, 0, sizeof(L));
+    L.n_panels = L.rows = L.cols = 1;
+    L.width = 2200;
+    L.height = 1200;
+    const int left = 190, bottom = 130, top = kind == LDW_PLOT_FIT ? 70 : 30, right = kind == LDW_PLOT_CDS ? 270 : 40;
+    L.panel_w = L.width - left - right;
+    L.panel_h = L.height - top - bottom;
+    L.panel[0][0] = left;
+    L.panel[0][1] = top;
+    L.panel[0][2] = L.panel_w;
+    L.panel[0][3] = L.panel_h;
+    LDW_REQUIRE(plot_axis(x_min, x_max, L.panel_w, 0, L.xlim, L.xtick, L.xtick_px, &L.n_xticks) == LDW_OK &&
+                    plot_axis(y_min, y_max, L.panel_h, 1, L.ylim, L.ytick, L.ytick_px, &L.n_yticks) == LDW_OK,
+                LDW_ERR_ARG, "ldw_plot_xy_layout_get: the axis range of the data is not finite");
     return LDW_OK;
 }
 

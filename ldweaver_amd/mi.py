@@ -198,7 +198,7 @@ def perform_MI_computation(snp_dat: SnpDat, hdw, cds_var: CdsVar, ncores: int = 
                            engine: Engine | None = None, alignment_resident: bool = False,
                            quirk_mode: int = L.QUIRK_REFERENCE, nlimbs: int = 0, verbose: bool = True,
                            return_aux: bool = False, sr_model: str = "device", group=None, engines=None, stream_lr: bool = True,
-                           sr_tail: str = "gather"):
+                           sr_tail: str = "gather", fit_plots: bool = False):
     """Returns the short-range link data.frame (clust_c,pos1,pos2,clust1,clust2,len,MI,srp_max,ARACNE);
     long-range links are appended to ``lr_save_path`` and the returned frame to ``sr_save_path``.
 
@@ -220,7 +220,10 @@ def perform_MI_computation(snp_dat: SnpDat, hdw, cds_var: CdsVar, ncores: int = 
     filters, :179-189) run on ``engines[0]`` alone.
 
     ``stream_lr`` (r05, default): on one engine ``lr_links.tsv`` is appended while the block loop runs (``ldw_lr_stream_begin`` / ``_end``) like the
-    reference's per-block ``write.table(append = T)`` (:362); ``False`` writes the table after the pass, beside the short-range model (r04)."""
+    reference's per-block ``write.table(append = T)`` (:362); ``False`` writes the table after the pass, beside the short-range model (r04).
+
+    ``fit_plots``: also write ``c<i>_fit.png`` (``plots.fit_plot``, R/computePairwiseMI.R:430-440) beside every ``c<i>_fit_data.tsv`` in
+    ``plt_folder``; the default leaves the folder as it was."""
     t000 = time.time()
     say = print if verbose else (lambda *a, **k: None)
     if lr_save_path is None:
@@ -419,11 +422,14 @@ def perform_MI_computation(snp_dat: SnpDat, hdw, cds_var: CdsVar, ncores: int = 
         if runARACNE:
             say(f"Running ARACNE on {len(red)} links... ")
             red["ARACNE"] = aracne(red["pos1"], red["pos2"], red["MI"], chk["pos1"], chk["pos2"], chk["MI"]).astype(np.float64)
-    # the data of c<i>_fit_data.rds (saveRDS(maxvls), R/computePairwiseMI.R:439) as a tsv with a header; the png is out of scope
+    # the data of c<i>_fit_data.rds (saveRDS(maxvls), R/computePairwiseMI.R:439) as a tsv with a header; the png on request
     for ci, fd in enumerate(fit_data):
         with open(os.path.join(plt_folder, f"c{ci + 1}_fit_data.tsv"), "w") as fh:
             fh.write("len\tmax\tfit\n")
         append_table(os.path.join(plt_folder, f"c{ci + 1}_fit_data.tsv"), [fd["len"].to_numpy(), fd["max"].to_numpy(), fd["fit"].to_numpy()])
+        if fit_plots:
+            from .plots import fit_plot
+            fit_plot(fd, ci + 1, os.path.join(plt_folder, f"c{ci + 1}_fit.png"), engine=None if own else eng)
     if not runARACNE:
         warnings.warn("ARACNE not run, all values will be set to 1")
         red["ARACNE"] = 1.0

@@ -17,7 +17,11 @@ LR_COLS = ["pos1", "pos2", "c1", "c2", "len", "MI"]                             
 # every colour the frame uses outside the panels, the strips and the colour bar: background, lines / strips, tick labels, titles
 FRAME_COLOURS = ((0xFF, 0xFF, 0xFF), (0xB3, 0xB3, 0xB3), (0x4D, 0x4D, 0x4D), (0x00, 0x00, 0x00))
 GREY, LR_DIRECT, LR_LINE = 0xC0C0C0, 0x0868AC, 0xDB4325     # R/lr_analyser.R:120-122
-CANVAS = {L.PLOT_SR_CLUST: (2200, 1200), L.PLOT_SR_COMBI: (2200, 1200), L.PLOT_LR: (4800, 1200), L.PLOT_LDMAP: (5000, 5250)}
+CANVAS = {L.PLOT_SR_CLUST: (2200, 1200), L.PLOT_SR_COMBI: (2200, 1200), L.PLOT_LR: (4800, 1200), L.PLOT_LDMAP: (5000, 5250),
+          L.PLOT_FIT: (2200, 1200), L.PLOT_CDS: (2200, 1200)}
+FIT_LINE = 0xFF0000                                           # R/computePairwiseMI.R:434
+FIT_LABELS = ("Basepair separation", "MI (95th percentile)")  # R/computePairwiseMI.R:435-436
+CDS_LABELS = ("Genomic starting position of CDS", "Diversity within CDS")   # R/estimateCDSDiversity.R:216-217
 SR_ERR = "sr_links must either be (1) a data.frame with sr_links or (2) the path to the saved tsv file from perform_MI_computation()"
 LR_ERR = "lr_links must either be (1) a data.frame with lr_links or (2) the path to the saved tsv file from perform_MI_computation()"
 
@@ -26,7 +30,8 @@ def layout(kind: int, n_panels: int = 1, xr=(0.0, 1.0), yr=(0.0, 1.0)) -> dict:
     """The figure of ``kind`` (``_lib.PLOT_*``) with ``n_panels`` facets for the DATA ranges xr, yr: canvas size, facet grid, panel /
     strip / colour-bar rectangles (x, y, w, h; top-left origin), axis ranges and ticks in data and panel-pixel coordinates.  Host only."""
     lay = L.PlotLayout()
-    L.check(L.lib().ldw_plot_layout_get(int(kind), int(n_panels), float(xr[0]), float(xr[1]), float(yr[0]), float(yr[1]), C.byref(lay)))
+    get = L.lib().ldw_plot_xy_layout_get if int(kind) in (L.PLOT_FIT, L.PLOT_CDS) else L.lib().ldw_plot_layout_get
+    L.check(get(int(kind), int(n_panels), float(xr[0]), float(xr[1]), float(yr[0]), float(yr[1]), C.byref(lay)))
     n = lay.n_panels
     return dict(width=lay.width, height=lay.height, n_panels=n, rows=lay.rows, cols=lay.cols, panel_w=lay.panel_w, panel_h=lay.panel_h,
                 panels=[tuple(lay.panel[p]) for p in range(n)], strips=[tuple(lay.strip[p]) for p in range(n) if lay.strip[p][2] > 0],
@@ -133,6 +138,103 @@ def debug_panels(eng, x, y, srp=None, layer=None, panel=None, *, opts: L.PlotOpt
                                           L.ptr(out), L.ptr(st), C.byref(scratch), L.ptr(ms) if timing else None))
     stats = dict(xr=(st[0], st[1]), yr=(st[2], st[3]), lo=st[4], hi=st[5], kept=int(st[6]), dropped=int(st[7]))
     return out, stats, scratch.value, (dict(stats=ms[0], clear=ms[1], centre=ms[2], disc=ms[3]) if timing else None)
+
+
+def xy_opts(kind: int, D: int = 11, class_rgb=(0,), line_w: int = 5, line_rgb: int = FIT_LINE) -> L.PlotXYOpts:
+    o = L.PlotXYOpts()
+    o.kind, o.D, o.n_classes, o.line_w, o.line_rgb = int(kind), int(D), len(class_rgb), int(line_w), int(line_rgb)
+    for k, v in enumerate(class_rgb[:L.PLOT_MAX_CLASSES]):
+        o.class_rgb[k] = int(v)
+    return o
+
+
+def _xy_columns(x, y, cls, line):
+    """x, y, cls as arrays of the C ABI's types (numpy: host; torch tensors on the GPU: device) and the line's vertices as host arrays."""
+    dev = hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
+    cols = []
+    for a, dt in ((x, "float64"), (y, "float64"), (cls, "uint8")):
+        if a is None:
+            cols.append(None)
+        elif dev:
+            import torch
+            cols.append(a.to(getattr(torch, dt)).contiguous())
+        else:
+            cols.append(np.ascontiguousarray(a, dtype=dt))
+    if dev:
+        import torch
+        torch.cuda.current_stream().synchronize()   # the library reads the columns on the engine's stream
+    n = len(cols[0])
+    if any(c is not None and len(c) != n for c in cols):
+        raise ValueError("the columns differ in length")
+    lx, ly = (None, None) if line is None else (np.ascontiguousarray(line[0], dtype=np.float64), np.ascontiguousarray(line[1], dtype=np.float64))
+    if lx is not None and len(lx) != len(ly):
+        raise ValueError("the line's vertex arrays differ in length")
+    return cols, n, dev, lx, ly
+
+
+def _text(s):
+    return None if s is None else str(s).encode()
+
+
+def render_xy(eng, x, y, cls=None, line=None, *, opts: L.PlotXYOpts, title=None, xlab=None, ylab=None, path=None, want_canvas: bool = False):
+    """One xy figure (ldw_plot_xy): points in row order, the later row on top, coloured by class; ``line`` = (x, y) vertices of a polyline drawn
+    over them.  Returns (canvas or None, rows dropped)."""
+    cols, n, dev, lx, ly = _xy_columns(x, y, cls, line)
+    W, H = CANVAS[opts.kind]
+    canvas = np.zeros((H, W, 3), dtype=np.uint8) if want_canvas else None
+    dropped = C.c_int64(0)
+    L.check(L.lib().ldw_plot_xy(eng._ctx, *[L.ptr(c) for c in cols], n, int(dev), L.ptr(lx), L.ptr(ly), 0 if lx is None else len(lx), C.byref(opts),
+                                _text(title), _text(xlab), _text(ylab), None if path is None else os.fsencode(path), L.ptr(canvas), C.byref(dropped)))
+    return canvas, dropped.value
+
+
+def debug_xy_panel(eng, x, y, cls=None, line=None, *, opts: L.PlotXYOpts, W: int, H: int, timing: bool = False):
+    """The panel without the frame (ldw_debug_plot_xy_panel): (rgb (H, W, 3), stats dict, ms or None)."""
+    cols, n, dev, lx, ly = _xy_columns(x, y, cls, line)
+    out = np.zeros((H, W, 3), dtype=np.uint8)
+    st, ms = np.zeros(6), np.zeros(4)
+    L.check(L.lib().ldw_debug_plot_xy_panel(eng._ctx, *[L.ptr(c) for c in cols], n, int(dev), L.ptr(lx), L.ptr(ly), 0 if lx is None else len(lx),
+                                            C.byref(opts), int(W), int(H), L.ptr(out), L.ptr(st), L.ptr(ms) if timing else None))
+    stats = dict(xr=(st[0], st[1]), yr=(st[2], st[3]), kept=int(st[4]), dropped=int(st[5]))
+    return out, stats, (dict(stats=ms[0], clear=ms[1], centre=ms[2], paint=ms[3]) if timing else None)
+
+
+def _with_engine(engine, fn):
+    from .engine import Engine
+    own = engine is None
+    eng = Engine(0) if own else engine
+    try:
+        return fn(eng)
+    finally:
+        if own:
+            eng.close()
+
+
+def fit_plot(fit_data_i, i: int, path, *, engine=None) -> str:
+    """``c<i>_fit.png`` (R/computePairwiseMI.R:430-440): the per-distance 95th percentile ``max`` against ``len`` as black points, the fitted
+    curve (``len``, ``fit``) as a red line over them, titled ``Clust i``.  ``fit_data_i``: a frame with the columns len, max, fit, ascending in
+    len (what ``perform_MI_computation`` writes to ``c<i>_fit_data.tsv``).  Returns the path."""
+    ln = np.asarray(fit_data_i["len"], dtype=np.float64)
+    mx = np.asarray(fit_data_i["max"], dtype=np.float64)
+    ft = np.asarray(fit_data_i["fit"], dtype=np.float64)
+    _with_engine(engine, lambda eng: render_xy(eng, ln, mx, None, (ln, ft), opts=xy_opts(L.PLOT_FIT), title=f"Clust {int(i)}", xlab=FIT_LABELS[0],
+                                               ylab=FIT_LABELS[1], path=path))
+    return str(path)
+
+
+def cds_cluster_plot(cds_var, path, *, engine=None) -> str:
+    """``CDS_clustering.png`` (R/estimateCDSDiversity.R:212-220): ``var_estimate`` against ``cds_start``, coloured by the cluster
+    ``km_clst_ord`` in ggplot's default hues, in row order.  Returns the path."""
+    from .network import hue_palette
+    nclust = int(cds_var.nclust)
+    if not 1 <= nclust <= L.PLOT_MAX_CLASSES:
+        raise ValueError(f"{nclust} clusters: the figure takes 1..{L.PLOT_MAX_CLASSES}")
+    x = np.asarray(cds_var.cds_start, dtype=np.float64)
+    y = np.asarray(cds_var.var_estimate, dtype=np.float64)
+    cls = (np.asarray(cds_var.clusts["km_clst_ord"]).astype(np.int64) - 1).astype(np.uint8)
+    _with_engine(engine, lambda eng: render_xy(eng, x, y, cls, None, opts=xy_opts(L.PLOT_CDS, class_rgb=[int(c) for c in hue_palette(nclust)]),
+                                               xlab=CDS_LABELS[0], ylab=CDS_LABELS[1], path=path))
+    return str(path)
 
 
 def render_heatmap(eng, htm, path, title=None):

@@ -35,11 +35,11 @@ class SnpDat:
 
     @property
     def nsnp(self) -> int:
-        return int(self.states.shape[0])
+        return len(self.POS) if self.states is None else int(self.states.shape[0])      # (None: the alignment stayed on the device)
 
     @property
     def nseq(self) -> int:
-        return int(self.states.shape[1])
+        return len(self.seq_names) if self.states is None else int(self.states.shape[1])
 
     @classmethod
     def from_states(cls, states, POS, g, counts=None, seq_names=None):
