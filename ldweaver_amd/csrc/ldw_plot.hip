@@ -14,9 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "ldw_dev.h"
-#include "ldw_work.h"
-#include "ldw_plot.h"
+#include "ldw_plot_prim.h"
 
 #pragma clang fp contract(off)
 
@@ -26,28 +24,8 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
 
 namespace {
 
-constexpr int PLOT_TX = 32, PLOT_TY = 32, PLOT_NPART = 10, PLOT_MAX_BLOCKS = 1024;
 constexpr uint64_t KEY_LAYER = 1ull << 63;
-
-struct PlotRow {
-    double x, y, srp;
-    int layer, panel;
-};
-
-// the caller's columns
-struct ColSrc {
-    const double *x, *y, *srp;
-    const uint8_t *layer, *panel;
-    __device__ __forceinline__ bool has_srp() const { return srp != nullptr; }
-    __device__ __forceinline__ double srp_at(int64_t i) const { return srp[i]; }
-    __device__ __forceinline__ void get(int64_t i, PlotRow &r) const {
-        r.x = x[i];
-        r.y = y[i];
-        r.srp = srp ? srp[i] : 0.0;
-        r.layer = layer ? (layer[i] != 0) : 1;
-        r.panel = panel ? panel[i] : 0;
-    }
-};
+enum { KEY_SRP = 0, KEY_FIRST_ROW = 1, KEY_CLASS = 2 };   // the draw orders of the centre pass (see there)
 
 // the context's kept links (ldw_sr_pvalues / ldw_lr_tukey): row of the link table, its SNPs' positions, srp_max, clust_c, ARACNE flags
 struct CtxSrc {
@@ -98,35 +76,18 @@ __global__ void __launch_bounds__(256) k_plot_stats(const Src s, int64_t n, int 
             v[5] = fmax(v[5], r.srp);
         }
     }
-    __shared__ double sh[256];
-    for (int k = 0; k < PLOT_NPART; ++k) {
-        sh[threadIdx.x] = v[k];
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if ((int)threadIdx.x < w) {
-                const double p = sh[threadIdx.x], q = sh[threadIdx.x + w];
-                sh[threadIdx.x] = k >= 6 ? p + q : ((k & 1) ? fmax(p, q) : fmin(p, q));   // (counts below 2^53: exact)
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) part[(size_t)blockIdx.x * PLOT_NPART + k] = sh[0];
-        __syncthreads();
-    }
+    plot_partials_reduce<3, 4>(v, part);
 }
 
 __global__ void __launch_bounds__(256) k_plot_present(const uint32_t *__restrict__ meta, int64_t n, uint32_t *__restrict__ present) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) present[meta[i] & 0xFF] = 1u;
 }
 
-struct PlotGeom {
-    double x0, x1, y0, y1;
-    int W, H, n_panels;
-};
-
 // ---- centre pass: one atomicMax per kept row -------------------------------------------------------------------------------------------------
 // key, srp order:  ((layer << 63) | bits(srp)) + 1   (srp >= 0: its bit pattern orders like its value; -0.0 counts as 0)
 // key, row order:  (layer << 63) | (n - row)         (the first row is on top)
-template <class Src, int ORDERED, int PRECHECK>
+// key, classes:    (row + 1) << 8 | panel            (the xy figures: the LAST row is on top, the panel slot holds the class, one panel)
+template <class Src, int KEY, int PRECHECK>
 __global__ void __launch_bounds__(256) k_plot_centre(const Src s, int64_t n, int64_t row0, int64_t n_total, const PlotGeom G,
                                                      unsigned long long *__restrict__ img) {   // rows row0 .. row0 + n - 1 of a table of n_total
     const bool hs = s.has_srp();
@@ -135,9 +96,11 @@ __global__ void __launch_bounds__(256) k_plot_centre(const Src s, int64_t n, int
         s.get(i, r);
         if (!plot_keep(r, hs) || r.panel < 0 || r.panel >= G.n_panels) continue;
         const int px = plot_pixel(r.x, G.x0, G.x1, G.W), py = G.H - 1 - plot_pixel(r.y, G.y0, G.y1, G.H);
-        const size_t at = ((size_t)r.panel * G.H + py) * G.W + px;
+        const size_t at = ((size_t)(KEY == KEY_CLASS ? 0 : r.panel) * G.H + py) * G.W + px;
         unsigned long long key = r.layer ? KEY_LAYER : 0ull;
-        if (ORDERED)
+        if (KEY == KEY_CLASS)
+            key = ((unsigned long long)(row0 + i + 1) << 8) | (unsigned long long)r.panel;
+        else if (KEY == KEY_FIRST_ROW)
             key |= (unsigned long long)(n_total - (row0 + i));
         else
             key = (key | (r.srp == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(r.srp))) + 1ull;
@@ -150,9 +113,8 @@ __global__ void __launch_bounds__(256) k_plot_centre(const Src s, int64_t n, int
 }
 
 struct PlotPaint {
-    int D, h;                  // diameter, halo = D / 2
-    int8_t hw[LDW_PLOT_MAX_D]; // hw[dy + h] = largest dx with 4 (dx^2 + dy^2) <= D^2
-    int nx, ny, xt[LDW_PLOT_MAX_TICKS], yt[LDW_PLOT_MAX_TICKS];   // grid lines
+    PlotDisc disc;
+    PlotTicks ticks;
     int fixed;                 // fixed-colour mode
     uint32_t layer_rgb[2];
     double lo, hi;             // range of srp over the kept layer-1 rows
@@ -166,30 +128,17 @@ template <class Src, int ORDERED>
 __global__ void __launch_bounds__(256) k_plot_disc(const Src s, int64_t n, const PlotGeom G, const PlotPaint P, const unsigned long long *__restrict__ img,
                                                    uint8_t *__restrict__ rast) {
     extern __shared__ unsigned long long tile[];
-    const int h = P.h, tw = PLOT_TX + 2 * h, th = PLOT_TY + 2 * h;
-    const int bx = blockIdx.x * PLOT_TX, by = blockIdx.y * PLOT_TY, panel = blockIdx.z;
-    const unsigned long long *pimg = img + (size_t)panel * G.H * G.W;
-    for (int t = threadIdx.x; t < tw * th; t += 256) {
-        const int gx = bx - h + t % tw, gy = by - h + t / tw;
-        tile[t] = (gx >= 0 && gx < G.W && gy >= 0 && gy < G.H) ? pimg[(size_t)gy * G.W + gx] : 0ull;   // discs are clipped at the panel
-    }
+    const int bx = blockIdx.x * PLOT_T, by = blockIdx.y * PLOT_T, panel = blockIdx.z;
+    plot_tile_load(tile, img + (size_t)panel * G.H * G.W, G.W, G.H, bx, by, P.disc.h);
     __syncthreads();
-    const int lx = threadIdx.x % PLOT_TX;
-    for (int ly = threadIdx.x / PLOT_TX; ly < PLOT_TY; ly += 256 / PLOT_TX) {
+    const int lx = threadIdx.x % PLOT_T;
+    for (int ly = threadIdx.x / PLOT_T; ly < PLOT_T; ly += 256 / PLOT_T) {
         const int gx = bx + lx, gy = by + ly;
         if (gx >= G.W || gy >= G.H) continue;
-        unsigned long long m = 0;
-        for (int dy = -h; dy <= h; ++dy) {
-            const int w = P.hw[dy + h];
-            const unsigned long long *rowp = tile + (ly + h + dy) * tw + lx + h;
-            for (int dx = -w; dx <= w; ++dx) m = max(m, rowp[dx]);
-        }
+        const unsigned long long m = plot_disc_max(tile, P.disc, lx, ly);
         uint32_t rgb;
         if (m == 0) {
-            bool grid = false;
-            for (int k = 0; k < P.nx; ++k) grid |= P.xt[k] == gx;
-            for (int k = 0; k < P.ny; ++k) grid |= P.yt[k] == gy;
-            rgb = grid ? PLOT_GRID : PLOT_BG;
+            rgb = P.ticks.grid_or_background(gx, gy);
         } else {
             const int layer = (int)(m >> 63);
             const unsigned long long low = m & ~KEY_LAYER;
@@ -210,10 +159,7 @@ __global__ void __launch_bounds__(256) k_plot_disc(const Src s, int64_t n, const
             }
         }
         if (gy == P.hline_py) rgb = P.hline_rgb;
-        uint8_t *o = rast + (((size_t)panel * G.H + gy) * G.W + gx) * 3;
-        o[0] = (uint8_t)(rgb >> 16);
-        o[1] = (uint8_t)(rgb >> 8);
-        o[2] = (uint8_t)rgb;
+        plot_store_rgb(rast + (((size_t)panel * G.H + gy) * G.W + gx) * 3, rgb);
     }
 }
 
@@ -239,40 +185,10 @@ __global__ void __launch_bounds__(256) k_plot_heat(const double *__restrict__ ht
 
 // Device memory: ctx->plot_work (key image, rasters, partials) and ctx->plot_cols (host columns in chunks), the context's grow-only buffers.
 
-// host columns travel in chunks of PLOT_CHUNK rows through one device buffer of constant size: statistics pass, then centre pass, per chunk
-struct HostCols {
-    const double *x, *y, *srp;
-    const uint8_t *layer, *panel;
-};
-constexpr int64_t PLOT_CHUNK = 1 << 20;   // 26 MiB of columns
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t chunk_bytes(int64_t n) {
-    const int64_t m = std::min<int64_t>(n, PLOT_CHUNK);
-    return round256((size_t)m * 8) * 3 + round256((size_t)m) * 2;
-}
-// rows [i0, i0 + m) into ctx->plot_cols (reserved by the caller), queued on the context's stream behind the kernels that read the last chunk
-int upload_chunk(ldw_ctx *c, const HostCols &h, int64_t n, int64_t i0, int64_t m, ColSrc &out) {
-    const int64_t m0 = std::min<int64_t>(n, PLOT_CHUNK);
-    const size_t nd = round256((size_t)m0 * 8), nb = round256((size_t)m0);
-    uint8_t *p = c->plot_cols.as<uint8_t>();
-    out = ColSrc{nullptr, nullptr, nullptr, nullptr, nullptr};
-    LDW_HIP(hipMemcpyAsync(p, h.x + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(p + nd, h.y + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-    out.x = (const double *)p;
-    out.y = (const double *)(p + nd);
-    if (h.srp) {
-        LDW_HIP(hipMemcpyAsync(p + 2 * nd, h.srp + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-        out.srp = (const double *)(p + 2 * nd);
-    }
-    if (h.layer) {
-        LDW_HIP(hipMemcpyAsync(p + 3 * nd, h.layer + i0, (size_t)m, hipMemcpyHostToDevice, c->stream));
-        out.layer = p + 3 * nd;
-    }
-    if (h.panel) {
-        LDW_HIP(hipMemcpyAsync(p + 3 * nd + nb, h.panel + i0, (size_t)m, hipMemcpyHostToDevice, c->stream));
-        out.panel = p + 3 * nd + nb;
-    }
-    return LDW_OK;
+// host columns (PlotFeed: x, y, srp, layer, panel): statistics pass, then centre pass, per chunk
+using HostCols = PlotFeed<5>;
+ColSrc chunk_src(const void *const *d) {
+    return ColSrc{(const double *)d[0], (const double *)d[1], (const double *)d[2], (const uint8_t *)d[3], (const uint8_t *)d[4]};
 }
 
 struct PlotStats {
@@ -282,8 +198,6 @@ struct PlotStats {
 
 constexpr size_t PLOT_CONST_BYTES = (size_t)PLOT_MAX_BLOCKS * PLOT_NPART * 8 + 1024;   // statistics partials + the cluster marks
 static_assert(PLOT_CONST_BYTES % 256 == 0, "the carved plot_work keeps its byte count");
-
-int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, PLOT_MAX_BLOCKS)); }
 
 int check_opts(const ldw_plot_opts *o, const char *who, int &D) {
     LDW_REQUIRE(o, LDW_ERR_ARG, "%s: null options", who);
@@ -299,15 +213,16 @@ template <class Src>
 int stats_accum(ldw_ctx *c, const Src &s, int64_t m, int n_panels, double *d_part, double *v) {
     const int grid = grid_for(m);
     LDW_LAUNCH(k_plot_stats<Src>, dim3(grid), dim3(256), 0, c->stream, s, m, n_panels, d_part);
-    std::vector<double> part((size_t)grid * PLOT_NPART);
-    LDW_HIP(hipMemcpyAsync(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < grid; ++b)
-        for (int k = 0; k < PLOT_NPART; ++k) {
-            const double q = part[(size_t)b * PLOT_NPART + k];
-            v[k] = k >= 6 ? v[k] + q : ((k & 1) ? std::max(v[k], q) : std::min(v[k], q));
-        }
-    return LDW_OK;
+    return plot_partials_merge<3, 4>(c, d_part, grid, v);
+}
+
+// one launch of the centre pass over rows row0 .. row0 + m - 1 of a table of n_total
+template <class Src, int KEY>
+void centre_launch(ldw_ctx *c, const Src &s, int64_t m, int64_t row0, int64_t n_total, int pre, const PlotGeom &G, unsigned long long *d_keys) {
+    if (pre)
+        hipLaunchKernelGGL((k_plot_centre<Src, KEY, 1>), dim3(grid_for(m)), dim3(256), 0, c->stream, s, m, row0, n_total, G, d_keys);
+    else
+        hipLaunchKernelGGL((k_plot_centre<Src, KEY, 0>), dim3(grid_for(m)), dim3(256), 0, c->stream, s, m, row0, n_total, G, d_keys);
 }
 
 // hc != NULL: the rows are host columns, fed in chunks (s is then only the colour pass's view)
@@ -316,12 +231,7 @@ int plot_stats(ldw_ctx *c, const Src &s, const HostCols *hc, int64_t n, int n_pa
     if (n > 0) {
         double v[PLOT_NPART] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY, 0, 0, 0, 0};
         if (hc) {
-            for (int64_t i0 = 0; i0 < n; i0 += PLOT_CHUNK) {
-                const int64_t m = std::min<int64_t>(PLOT_CHUNK, n - i0);
-                ColSrc cs;
-                if (int rc = upload_chunk(c, *hc, n, i0, m, cs)) return rc;
-                if (int rc = stats_accum(c, cs, m, n_panels, d_part, v)) return rc;
-            }
+            if (int rc = hc->each_chunk(c, n, [&](const void *const *d, int64_t, int64_t m) { return stats_accum(c, chunk_src(d), m, n_panels, d_part, v); })) return rc;
         } else if (int rc = stats_accum(c, s, n, n_panels, d_part, v)) {
             return rc;
         }
@@ -352,19 +262,9 @@ template <class Src>
 int plot_raster(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int64_t n, const ldw_plot_opts *o, int D, int n_panels, int W, int H, const double xlim[2], const double ylim[2],
                 int nxt, const int32_t *xt, int nyt, const int32_t *yt, const PlotStats &st, unsigned long long *d_keys, uint8_t *d_rast, hipEvent_t *ev) {
     const PlotGeom G{xlim[0], xlim[1], ylim[0], ylim[1], W, H, n_panels};
-    PlotPaint P;
-    memset(&P, 0, sizeof(P));
-    P.D = D;
-    P.h = D / 2;
-    for (int dy = -P.h; dy <= P.h; ++dy) {
-        int w = 0;
-        while (4 * ((w + 1) * (w + 1) + dy * dy) <= D * D) ++w;
-        P.hw[dy + P.h] = (int8_t)w;
-    }
-    P.nx = nxt;
-    P.ny = nyt;
-    for (int k = 0; k < nxt; ++k) P.xt[k] = xt[k];
-    for (int k = 0; k < nyt; ++k) P.yt[k] = yt[k];
+    PlotPaint P{};
+    P.disc = PlotDisc::make(D);
+    P.ticks = PlotTicks::make(nxt, xt, nyt, yt);
     P.lo = st.lo;
     P.hi = st.hi;
     P.hline_py = o->has_hline ? H - 1 - plot_pixel(o->hline_y, ylim[0], ylim[1], H) : -1;
@@ -377,41 +277,25 @@ int plot_raster(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int6
     LDW_HIP(hipMemsetAsync(d_keys, 0, pixels * 8, c->stream));
     if (ev) LDW_HIP(hipEventRecord(ev[1], c->stream));
     const int pre = (o->flags & LDW_PLOT_NO_PRECHECK) ? 0 : 1;
-    const dim3 dgrid((W + PLOT_TX - 1) / PLOT_TX, (H + PLOT_TY - 1) / PLOT_TY, n_panels);
-    const size_t lds = (size_t)(PLOT_TX + 2 * P.h) * (PLOT_TY + 2 * P.h) * 8;
-    int rc_up = LDW_OK;
-    auto run = [&](auto ordered_tag) {
-        constexpr int ORD = decltype(ordered_tag)::value;
+    const dim3 dgrid((W + PLOT_T - 1) / PLOT_T, (H + PLOT_T - 1) / PLOT_T, n_panels);
+    auto run = [&](auto key_tag) -> int {
+        constexpr int KEY = decltype(key_tag)::value;
         if (n > 0 && hc) {
-            for (int64_t i0 = 0; i0 < n && rc_up == LDW_OK; i0 += PLOT_CHUNK) {
-                const int64_t m = std::min<int64_t>(PLOT_CHUNK, n - i0);
-                ColSrc cs;
-                rc_up = upload_chunk(c, *hc, n, i0, m, cs);
-                if (rc_up != LDW_OK) break;
-                if (pre)
-                    hipLaunchKernelGGL((k_plot_centre<ColSrc, ORD, 1>), dim3(grid_for(m)), dim3(256), 0, c->stream, cs, m, i0, n, G, d_keys);
-                else
-                    hipLaunchKernelGGL((k_plot_centre<ColSrc, ORD, 0>), dim3(grid_for(m)), dim3(256), 0, c->stream, cs, m, i0, n, G, d_keys);
-            }
+            if (int rc = hc->each_chunk(c, n, [&](const void *const *d, int64_t i0, int64_t m) {
+                    centre_launch<ColSrc, KEY>(c, chunk_src(d), m, i0, n, pre, G, d_keys);
+                    return (int)LDW_OK;
+                }))
+                return rc;
         } else if (n > 0) {
-            if (pre)
-                hipLaunchKernelGGL((k_plot_centre<Src, ORD, 1>), dim3(grid_for(n)), dim3(256), 0, c->stream, s, n, (int64_t)0, n, G, d_keys);
-            else
-                hipLaunchKernelGGL((k_plot_centre<Src, ORD, 0>), dim3(grid_for(n)), dim3(256), 0, c->stream, s, n, (int64_t)0, n, G, d_keys);
+            centre_launch<Src, KEY>(c, s, n, 0, n, pre, G, d_keys);
         }
-        if (ev) (void)hipEventRecord(ev[2], c->stream);
-        hipLaunchKernelGGL((k_plot_disc<Src, ORD>), dgrid, dim3(256), lds, c->stream, s, n, G, P, d_keys, d_rast);
-        if (ev) (void)hipEventRecord(ev[3], c->stream);
-    };
-    return [&]() {
-        if (o->ordered)
-            run(std::integral_constant<int, 1>());
-        else
-            run(std::integral_constant<int, 0>());
-        if (rc_up != LDW_OK) return rc_up;
+        if (ev) LDW_HIP(hipEventRecord(ev[2], c->stream));
+        hipLaunchKernelGGL((k_plot_disc<Src, KEY == KEY_FIRST_ROW>), dgrid, dim3(256), plot_tile_lds(P.disc), c->stream, s, n, G, P, d_keys, d_rast);
+        if (ev) LDW_HIP(hipEventRecord(ev[3], c->stream));
         LDW_HIP(hipGetLastError());
         return LDW_OK;
-    }();
+    };
+    return o->ordered ? run(std::integral_constant<int, KEY_FIRST_ROW>()) : run(std::integral_constant<int, KEY_SRP>());
 }
 
 template <class Src>
@@ -430,35 +314,26 @@ int plot_panels(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int6
     auto d_part = cv.take<double>(PLOT_CONST_BYTES / 8);
     if (int rc = cv.reserve(c->plot_work)) return rc;
     if (scratch_out) *scratch_out = (int64_t)cv.bytes;
-    hipEvent_t ev[6] = {};
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() {
-            for (int k = 0; k < 6; ++k)
-                if (e[k]) (void)hipEventDestroy(e[k]);
-        }
-    } guard{ev};
-    if (ms_out)
-        for (int k = 0; k < 6; ++k) LDW_HIP(hipEventCreate(&ev[k]));
+    PlotEvents<2> ev_stats;   // round the statistics pass
+    PlotEvents<4> ev;         // round the clear, the centre pass, the disc pass
+    if (ms_out) {
+        LDW_HIP(ev_stats.create());
+        LDW_HIP(ev.create());
+    }
     PlotStats st;
-    if (ms_out) LDW_HIP(hipEventRecord(ev[4], c->stream));
+    if (ms_out) LDW_HIP(hipEventRecord(ev_stats.e[0], c->stream));
     if (int rc = plot_stats(c, s, hc, n, n_panels, o, d_part, st, who)) return rc;
-    if (ms_out) LDW_HIP(hipEventRecord(ev[5], c->stream));
+    if (ms_out) LDW_HIP(hipEventRecord(ev_stats.e[1], c->stream));
     double xlim[2], ylim[2], tick[LDW_PLOT_MAX_TICKS];
     int32_t xt[LDW_PLOT_MAX_TICKS], yt[LDW_PLOT_MAX_TICKS], nxt = 0, nyt = 0;
     LDW_REQUIRE(plot_axis(st.xr[0], st.xr[1], W, 0, xlim, tick, xt, &nxt) == LDW_OK && plot_axis(st.yr[0], st.yr[1], H, 1, ylim, tick, yt, &nyt) == LDW_OK,
                 LDW_ERR_ARG, "%s: the data ranges are not finite intervals", who);
-    if (int rc = plot_raster(c, s, hc, has_srp, n, o, D, n_panels, W, H, xlim, ylim, nxt, xt, nyt, yt, st, d_keys, d_rast, ms_out ? ev : nullptr)) return rc;
+    if (int rc = plot_raster(c, s, hc, has_srp, n, o, D, n_panels, W, H, xlim, ylim, nxt, xt, nyt, yt, st, d_keys, d_rast, ms_out ? ev.e : nullptr)) return rc;
     LDW_HIP(hipMemcpyAsync(rgb_out, d_rast, pixels * 3, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     if (ms_out) {
-        float f = 0;
-        LDW_HIP(hipEventElapsedTime(&f, ev[4], ev[5]));
-        ms_out[0] = f;
-        for (int k = 0; k < 3; ++k) {
-            LDW_HIP(hipEventElapsedTime(&f, ev[k], ev[k + 1]));
-            ms_out[k + 1] = f;
-        }
+        LDW_HIP(ev_stats.elapsed(ms_out));
+        LDW_HIP(ev.elapsed(ms_out + 1));
     }
     if (stats_out) {
         const double v[8] = {st.xr[0], st.xr[1], st.yr[0], st.yr[1], st.lo, st.hi, (double)st.kept, (double)st.dropped};
@@ -469,15 +344,9 @@ int plot_panels(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int6
 
 int emit_figure(const ldw_plot_layout &lay, int kind, const std::vector<uint8_t> &rasters, const int32_t *panel_label, const char *title, bool cb_valid,
                 double cb_lo, double cb_hi, const char *png_path, uint8_t *rgb_out) {
-    std::vector<uint8_t> own;
-    uint8_t *canvas = rgb_out;
-    if (!canvas) {
-        own.resize((size_t)lay.width * lay.height * 3);
-        canvas = own.data();
-    }
-    plot_frame(canvas, lay, kind, rasters.data(), panel_label, title, cb_valid, cb_lo, cb_hi);
-    if (png_path) return ldw_png_write(png_path, canvas, lay.width, lay.height, -1, nullptr);
-    return LDW_OK;
+    PlotCanvas canvas(rgb_out, lay.width, lay.height);
+    plot_frame(canvas.rgb, lay, kind, rasters.data(), panel_label, title, cb_valid, cb_lo, cb_hi);
+    return canvas.finish(png_path);
 }
 
 // the whole figure: statistics -> layout -> rasters -> frame -> PNG / canvas
@@ -522,9 +391,9 @@ struct Cols {
              int ordered) {
         src = ColSrc{x, y, srp, layer, panel};
         if (on_device || n == 0) return LDW_OK;
-        host = HostCols{x, y, srp, layer, panel};
+        host = HostCols{{x, y, srp, layer, panel}, {8, 8, 8, 1, 1}};
         hc = &host;
-        const size_t cb = chunk_bytes(n);
+        const size_t cb = host.chunk_bytes(n);
         const bool whole_srp = ordered && srp;
         if (int rc = c->plot_cols.reserve(cb + (whole_srp ? (size_t)n * 8 : 0))) return rc;
         src = ColSrc{nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -561,6 +430,14 @@ int heat_figure(ldw_ctx *c, const double *d_htm, int32_t B, const char *title, c
 }
 
 }  // namespace
+
+int plot_stats_accum(ldw_ctx *c, const ColSrc &s, int64_t m, int n_panels, double *d_part, double *v) { return stats_accum(c, s, m, n_panels, d_part, v); }
+
+int plot_centre_classes(ldw_ctx *c, const ColSrc &s, int64_t m, int64_t row0, const PlotGeom &G, unsigned long long *d_keys) {
+    LDW_LAUNCH((k_plot_centre<ColSrc, KEY_CLASS, 1>), dim3(grid_for(m)), dim3(256), 0, c->stream, s, m, row0, (int64_t)0, G, d_keys);
+    return LDW_OK;
+}
+
 }  // namespace ldw
 
 using namespace ldw;

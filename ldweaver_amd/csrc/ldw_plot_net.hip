@@ -1,10 +1,9 @@
 // The edges of the network plot on the device (include/ldweaver_amd.h 12): translucent capsules — a segment with a width — blended
 // in list order over a white canvas.
 //
-// Rule.  The endpoints and the pixels are integer points (the centre of pixel (x, y) is the point (x, y)).  With p = pixel - end 0 and d = end 1 -
-// end 0, the squared distance D2 from the pixel to the segment is |p|^2 where p.d <= 0, |p - d|^2 where p.d >= |d|^2, and (p x d)^2 / |d|^2 between;
-// the pixel is covered iff 4 D2 <= w^2, evaluated in int64 as 4 (p x d)^2 <= w^2 |d|^2 in the interior.  Coordinates are bounded by NET_COORD_* and
-// w by NET_MAX_W, so |p x d| < 2^30 and every product stays below 2^62.  A covered pixel takes c = (c (255 - a) + col a + 127) / 255 per channel.
+// Rule.  The endpoints and the pixels are integer points (the centre of pixel (x, y) is the point (x, y)); a pixel is covered iff its squared
+// distance D2 to the segment satisfies 4 D2 <= w^2 (plot_capsule_covers, ldw_plot_prim.h: exact in int64 for coordinates inside the window and
+// w <= NET_MAX_W).  A covered pixel takes c = (c (255 - a) + col a + 127) / 255 per channel.
 //
 // Kernels.  k_net_boxes: the tiles (32 x 32 pixels) that a capsule's bounding box, inflated by ceil(w / 2) and clipped at the canvas, meets.
 // k_net_bin: one thread per tile walks the boxes IN LIST ORDER (staged through LDS 256 at a time), first counting, then — behind rocPRIM's exclusive
@@ -15,15 +14,13 @@
 #include <algorithm>
 #include <vector>
 
-#include "ldw_dev.h"
-#include "ldw_work.h"
-#include "ldw_plot.h"
+#include "ldw_plot_prim.h"
 
 namespace ldw {
 namespace {
 
-constexpr int NET_T = 32;
-constexpr int NET_MAX_DIM = 8192, NET_COORD_LO = -8192, NET_COORD_HI = 16383, NET_MAX_W = 1024;
+constexpr int NET_T = PLOT_T;
+constexpr int NET_MAX_DIM = 8192, NET_MAX_W = 1024;
 constexpr int64_t NET_MAX_CAPS = 1 << 17;   // k_net_bin tests every capsule against every tile, twice: 8192 edges of 16 segments is what that serves
 
 struct TileBox {
@@ -77,18 +74,6 @@ __global__ __launch_bounds__(256) void k_net_bin(const TileBox *__restrict__ box
     if (!FILL && tile < ntiles) cnt[tile] = k;
 }
 
-__device__ __forceinline__ bool net_covers(const ldw_capsule &c, int x, int y) {
-    const int64_t px = x - c.x0, py = y - c.y0, dx = c.x1 - c.x0, dy = c.y1 - c.y0;
-    const int64_t w2 = (int64_t)c.w * c.w, dd = dx * dx + dy * dy, t = px * dx + py * dy;
-    if (t <= 0) return 4 * (px * px + py * py) <= w2;
-    if (t >= dd) {
-        const int64_t qx = px - dx, qy = py - dy;
-        return 4 * (qx * qx + qy * qy) <= w2;
-    }
-    const int64_t cr = px * dy - py * dx;
-    return 4 * cr * cr <= w2 * dd;
-}
-
 __global__ __launch_bounds__(256) void k_net_shade(const ldw_capsule *__restrict__ caps, const uint32_t *__restrict__ off, const uint32_t *__restrict__ list, int W, int H,
                                                    uint8_t *__restrict__ rast) {
     const int tile = blockIdx.y * gridDim.x + blockIdx.x;
@@ -101,9 +86,10 @@ __global__ __launch_bounds__(256) void k_net_shade(const ldw_capsule *__restrict
     for (uint32_t k = lo; k < hi; ++k) {
         const ldw_capsule c = caps[list[k]];
         const int cr = (int)(c.rgb >> 16 & 0xff), cg = (int)(c.rgb >> 8 & 0xff), cb = (int)(c.rgb & 0xff), a = c.alpha;
+        const int64_t w2 = (int64_t)c.w * c.w;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            if (net_covers(c, x, y0 + 8 * q)) {
+            if (plot_capsule_covers(c.x0, c.y0, c.x1, c.y1, w2, x, y0 + 8 * q)) {
                 r[q] = (r[q] * (255 - a) + cr * a + 127) / 255;
                 g[q] = (g[q] * (255 - a) + cg * a + 127) / 255;
                 b[q] = (b[q] * (255 - a) + cb * a + 127) / 255;
@@ -128,8 +114,7 @@ int check_capsules(const ldw_capsule *caps, int64_t n, int W, int H, const char 
     LDW_REQUIRE(n >= 0 && n <= NET_MAX_CAPS && (n == 0 || caps), LDW_ERR_ARG, "%s: %lld capsules (0..%lld), or a null list", who, (long long)n, (long long)NET_MAX_CAPS);
     for (int64_t i = 0; i < n; ++i) {
         const ldw_capsule &c = caps[i];
-        const int lo = std::min(std::min(c.x0, c.y0), std::min(c.x1, c.y1)), hi = std::max(std::max(c.x0, c.y0), std::max(c.x1, c.y1));
-        LDW_REQUIRE(lo >= NET_COORD_LO && hi <= NET_COORD_HI, LDW_ERR_ARG, "%s: capsule %lld has a coordinate outside %d..%d", who, (long long)i, NET_COORD_LO, NET_COORD_HI);
+        if (int rc = plot_check_window(c, (long long)i, "capsule", who)) return rc;
         LDW_REQUIRE(c.w >= 1 && c.w <= NET_MAX_W, LDW_ERR_ARG, "%s: capsule %lld has width %d outside 1..%d", who, (long long)i, c.w, NET_MAX_W);
         LDW_REQUIRE(c.alpha >= 1 && c.alpha <= 255 && c.rgb <= 0xFFFFFFu, LDW_ERR_ARG, "%s: capsule %lld has alpha %d outside 1..255 or a colour beyond 0xFFFFFF", who, (long long)i,
                     c.alpha);
@@ -208,16 +193,10 @@ int ldw_plot_network(ldw_ctx *c, const ldw_capsule *caps, int64_t n_caps, int32_
     for (int k = 0; k < n_nodes; ++k) LDW_REQUIRE(node_names[k] != nullptr, LDW_ERR_ARG, "ldw_plot_network: node %d has no name", k);
     if (int rc = check_capsules(caps, n_caps, W, H, "ldw_plot_network")) return rc;
     if (int rc = check_gpu(c)) return rc;
-    std::vector<uint8_t> own;
-    uint8_t *canvas = rgb_out;
-    if (!canvas) {
-        own.resize((size_t)W * H * 3);
-        canvas = own.data();
-    }
-    if (int rc = net_raster(c, caps, n_caps, W, H, canvas, nullptr, "ldw_plot_network")) return rc;
-    plot_net_overlay(canvas, W, H, node_xy, node_names, n_nodes, title, legend_value, legend_rgb, n_legend, text_scale, boxes_out);
-    if (png_path) return ldw_png_write(png_path, canvas, W, H, -1, nullptr);
-    return LDW_OK;
+    PlotCanvas canvas(rgb_out, W, H);
+    if (int rc = net_raster(c, caps, n_caps, W, H, canvas.rgb, nullptr, "ldw_plot_network")) return rc;
+    plot_net_overlay(canvas.rgb, W, H, node_xy, node_names, n_nodes, title, legend_value, legend_rgb, n_legend, text_scale, boxes_out);
+    return canvas.finish(png_path);
 }
 
 int ldw_debug_plot_capsules(ldw_ctx *c, const ldw_capsule *caps, int64_t n_caps, int32_t W, int32_t H, uint8_t *rgb_out, double *ms_out) {

@@ -16,14 +16,12 @@
 #include <algorithm>
 #include <vector>
 
-#include "ldw_dev.h"
-#include "ldw_work.h"
-#include "ldw_plot.h"
+#include "ldw_plot_prim.h"
 
 namespace ldw {
 namespace {
 
-constexpr int TNG_COORD_LO = -8192, TNG_COORD_HI = 16383, TNG_BLOCKS = 2048;
+constexpr int TNG_BLOCKS = 2048;
 constexpr int64_t TNG_MAX_RECTS = 1 << 16;
 
 // the last b in [lo, n) with off[b] <= t, given off[lo] <= t < off[n]
@@ -68,11 +66,7 @@ __global__ __launch_bounds__(256) void k_tng_paint(const ldw_rect *__restrict__ 
         size_t pix;
         const int b = rect_pixel(rects, off, n, W, H, t, lane, &pix);
         if (owner[pix] != (uint32_t)b + 1) continue;
-        const uint32_t rgb = rects[b].rgb;
-        uint8_t *o = rast + pix * 3;
-        o[0] = (uint8_t)(rgb >> 16);
-        o[1] = (uint8_t)(rgb >> 8);
-        o[2] = (uint8_t)rgb;
+        plot_store_rgb(rast + pix * 3, rects[b].rgb);
     }
 }
 
@@ -80,8 +74,7 @@ int check_rects(const ldw_rect *rects, int64_t n, const char *who) {
     LDW_REQUIRE(n >= 0 && n <= TNG_MAX_RECTS && (n == 0 || rects), LDW_ERR_ARG, "%s: %lld rectangles (0..%lld), or a null list", who, (long long)n, (long long)TNG_MAX_RECTS);
     for (int64_t i = 0; i < n; ++i) {
         const ldw_rect &r = rects[i];
-        const int lo = std::min(std::min(r.x0, r.y0), std::min(r.x1, r.y1)), hi = std::max(std::max(r.x0, r.y0), std::max(r.x1, r.y1));
-        LDW_REQUIRE(lo >= TNG_COORD_LO && hi <= TNG_COORD_HI, LDW_ERR_ARG, "%s: rectangle %lld has a coordinate outside %d..%d", who, (long long)i, TNG_COORD_LO, TNG_COORD_HI);
+        if (int rc = plot_check_window(r, (long long)i, "rectangle", who)) return rc;
         LDW_REQUIRE(r.x1 >= r.x0 && r.y1 >= r.y0, LDW_ERR_ARG, "%s: rectangle %lld has x1 < x0 or y1 < y0", who, (long long)i);
         LDW_REQUIRE(r.rgb <= 0xFFFFFFu, LDW_ERR_ARG, "%s: rectangle %lld has a colour beyond 0xFFFFFF", who, (long long)i);
     }
@@ -142,16 +135,10 @@ int ldw_plot_tanglegram(ldw_ctx *c, const ldw_capsule *caps, int64_t n_caps, con
     if (int rc = check_capsules(caps, n_caps, W, H, "ldw_plot_tanglegram")) return rc;
     if (int rc = check_rects(rects, n_rects, "ldw_plot_tanglegram")) return rc;
     if (int rc = check_gpu(c)) return rc;
-    std::vector<uint8_t> own;
-    uint8_t *canvas = rgb_out;
-    if (!canvas) {
-        own.resize((size_t)W * H * 3);
-        canvas = own.data();
-    }
-    if (int rc = tng_raster(c, caps, n_caps, rects, n_rects, W, H, canvas, nullptr, "ldw_plot_tanglegram")) return rc;
-    plot_tng_overlay(canvas, W, H, label_xy, labels, n_labels, title, text_scale, boxes_out);
-    if (png_path) return ldw_png_write(png_path, canvas, W, H, -1, nullptr);
-    return LDW_OK;
+    PlotCanvas canvas(rgb_out, W, H);
+    if (int rc = tng_raster(c, caps, n_caps, rects, n_rects, W, H, canvas.rgb, nullptr, "ldw_plot_tanglegram")) return rc;
+    plot_tng_overlay(canvas.rgb, W, H, label_xy, labels, n_labels, title, text_scale, boxes_out);
+    return canvas.finish(png_path);
 }
 
 int ldw_debug_plot_marks(ldw_ctx *c, const ldw_capsule *caps, int64_t n_caps, const ldw_rect *rects, int64_t n_rects, int32_t W, int32_t H, uint8_t *rgb_out, double *ms_out) {

@@ -22,9 +22,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ldw_dev.h"
-#include "ldw_work.h"
-#include "ldw_plot.h"
+#include "ldw_plot_prim.h"
 
 namespace ldw {
 namespace {
@@ -193,16 +191,9 @@ int tree_raster(ldw_ctx *c, int W, int H, const int32_t *panel, const ldw_bar *b
     auto d_line = cv.take<uint8_t>((int64_t)R * maxw * 3);
     auto d_canvas = cv.take<uint8_t>((int64_t)W * H * 3);
     if (int rc = cv.reserve(c->plot_work)) return rc;
-    hipEvent_t ev[5] = {};
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() {
-            for (int k = 0; k < 5; ++k)
-                if (e[k]) (void)hipEventDestroy(e[k]);
-        }
-    } guard{ev};
-    if (ms_out)
-        for (auto &e : ev) LDW_HIP(hipEventCreate(&e));
+    PlotEvents<5> events;
+    if (ms_out) LDW_HIP(events.create());
+    hipEvent_t *ev = events.e;
     hipStream_t st = c->stream;
     if (n > 0) LDW_HIP(hipMemcpyAsync(d_bars, bars, (size_t)n * sizeof(ldw_bar), hipMemcpyHostToDevice, st));
     if (R > 0) {
@@ -233,12 +224,7 @@ int tree_raster(ldw_ctx *c, int W, int H, const int32_t *panel, const ldw_bar *b
     if (ms_out) LDW_HIP(hipEventRecord(ev[4], st));
     LDW_HIP(hipMemcpyAsync(rgb_out, d_canvas, (size_t)W * H * 3, hipMemcpyDeviceToHost, st));
     LDW_HIP(hipStreamSynchronize(st));
-    if (ms_out)
-        for (int k = 0; k < 4; ++k) {
-            float f = 0;
-            LDW_HIP(hipEventElapsedTime(&f, ev[k], ev[k + 1]));
-            ms_out[k] = f;
-        }
+    if (ms_out) LDW_HIP(events.elapsed(ms_out));
     return LDW_OK;
 }
 
@@ -266,16 +252,10 @@ int ldw_plot_tree(ldw_ctx *c, int32_t W, int32_t H, const int32_t *panel, const 
     LDW_REQUIRE(entries == 0 || (legend_label && legend_rgb), LDW_ERR_ARG, "ldw_plot_tree: null legend entries");
     for (int64_t k = 0; k < entries; ++k) LDW_REQUIRE(legend_label[k] != nullptr, LDW_ERR_ARG, "ldw_plot_tree: legend entry %lld has no label", (long long)k);
     if (int rc = check_gpu(c)) return rc;
-    std::vector<uint8_t> own;
-    uint8_t *canvas = rgb_out;
-    if (!canvas) {
-        own.resize((size_t)W * H * 3);
-        canvas = own.data();
-    }
-    if (int rc = tree_raster(c, W, H, panel, bars, n_bars, bar_rgb, levels, n_tips, palette, band_rect, n_bands, canvas, nullptr, "ldw_plot_tree")) return rc;
-    plot_tree_overlay(canvas, W, H, band_rect, band_label, n_bands, title, legend_title, legend_n, legend_label, legend_rgb, legend_xy, text_scale, boxes_out);
-    if (png_path) return ldw_png_write(png_path, canvas, W, H, -1, nullptr);
-    return LDW_OK;
+    PlotCanvas canvas(rgb_out, W, H);
+    if (int rc = tree_raster(c, W, H, panel, bars, n_bars, bar_rgb, levels, n_tips, palette, band_rect, n_bands, canvas.rgb, nullptr, "ldw_plot_tree")) return rc;
+    plot_tree_overlay(canvas.rgb, W, H, band_rect, band_label, n_bands, title, legend_title, legend_n, legend_label, legend_rgb, legend_xy, text_scale, boxes_out);
+    return canvas.finish(png_path);
 }
 
 int ldw_debug_plot_tree(ldw_ctx *c, int32_t W, int32_t H, const int32_t *panel, const ldw_bar *bars, int64_t n_bars, uint32_t bar_rgb, const uint8_t *levels,

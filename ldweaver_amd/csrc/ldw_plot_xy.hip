@@ -1,16 +1,16 @@
 // The "xy" figures on the device (include/ldweaver_amd.h 12): c<i>_fit.png — black points under a red polyline — and
 // CDS_clustering.png — points coloured by class, drawn in row order.
 //
-// Points.  ggplot draws geom_point in data order, so a pixel shows the class of the LARGEST row whose disc covers it.  k_xy_centre takes the
-// maximum of the key (row + 1) << 8 | cls per CENTRE pixel (one 64-bit atomicMax per kept row), k_xy_paint the maximum of the key image over
-// the disc of offsets round every output pixel (read through an LDS tile with a halo of D / 2) — the structure of k_plot_centre / k_plot_disc
-// (ldw_plot.hip).  The colour is class_rgb[key & 0xFF]: no column is read by row.  Both maxima are order independent.
+// Points.  ggplot draws geom_point in data order, so a pixel shows the class of the LARGEST row whose disc covers it.  The scatter's statistics
+// and centre passes (ldw_plot.hip) run over the columns with the class in the panel slot: the centre pass takes the maximum of the key
+// (row + 1) << 8 | cls per CENTRE pixel, k_xy_paint the maximum of the key image over the disc round every output pixel (ldw_plot_prim.h).  The
+// colour is class_rgb[key & 0xFF]: no column is read by row.  Both maxima are order independent.
 //
 // Line.  k_xy_segments turns the vertices into pixel segments, one thread per vertex pair: entry i is the segment between the centre pixels
 // of vertices i and i + 1 where both are finite, the single pixel of vertex i where it is finite and neither neighbour is, and nothing
 // otherwise.  The line is opaque and of one colour, so a pixel needs to know only WHETHER a segment covers it: k_xy_paint's block walks the
 // entries 256 at a time, keeps in LDS those whose box (inflated by ceil(w / 2)) meets its 32 x 32 tile, and every pixel tests the kept ones by
-// the network plot's exact rule 4 D2 <= w^2 in 64-bit integers (ldw_plot_net.hip).  A covered pixel takes line_rgb over whatever the points left.
+// the capsule rule 4 D2 <= w^2 in 64-bit integers (plot_capsule_covers).  A covered pixel takes line_rgb over whatever the points left.
 //
 // Bounds: a kept row's and a finite vertex's pixel lie in [0, W) x [0, H) by the clamps of plot_pixel (both lie inside the axis range, which is
 // taken over both); the paint pass reads the key image only at in-panel coordinates (0 outside) and writes one RGB triple per in-panel pixel;
@@ -19,93 +19,33 @@
 #include <cmath>
 #include <vector>
 
-#include "ldw_dev.h"
-#include "ldw_work.h"
-#include "ldw_plot.h"
+#include "ldw_plot_prim.h"
 
 #pragma clang fp contract(off)
 
 namespace ldw {
 namespace {
 
-constexpr int XY_T = 32, XY_NPART = 7, XY_MAX_BLOCKS = 1024, XY_MAX_DIM = 8192, XY_MAX_LINE_W = 1024;
-constexpr int64_t XY_CHUNK = 1 << 20, XY_MAX_VERTS = 1 << 17;
-
-struct XYCols {
-    const double *x, *y;
-    const uint8_t *cls;   // NULL: class 0
-};
+constexpr int XY_MAX_DIM = 8192, XY_MAX_LINE_W = 1024;
+constexpr int64_t XY_MAX_VERTS = 1 << 17;
 
 struct XYSeg {
     int32_t x0, y0, x1, y1;   // x0 < 0: no entry
 };
 
-struct XYGeom {
-    double x0, x1, y0, y1;
-    int W, H;
-};
-
 struct XYPaint {
-    int D, h;
-    int8_t hw[LDW_PLOT_MAX_D];   // hw[dy + h] = largest dx with 4 (dx^2 + dy^2) <= D^2
-    int nx, ny, xt[LDW_PLOT_MAX_TICKS], yt[LDW_PLOT_MAX_TICKS];
+    PlotDisc disc;
+    PlotTicks ticks;
     uint32_t class_rgb[LDW_PLOT_MAX_CLASSES], line_rgb;
     int line_w;
 };
-
-// ---- statistics: x / y range of the kept rows, rows kept, rows dropped, a class out of range; [block][XY_NPART] partials --------------------------
-__global__ void __launch_bounds__(256) k_xy_stats(const XYCols s, int64_t n, int n_classes, double *__restrict__ part) {
-    double v[XY_NPART] = {INFINITY, -INFINITY, INFINITY, -INFINITY, 0, 0, 0};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double x = s.x[i], y = s.y[i];
-        if (s.cls && (int)s.cls[i] >= n_classes) v[6] = 1;
-        if (!(isfinite(x) && isfinite(y))) {
-            v[5] += 1;
-            continue;
-        }
-        v[4] += 1;
-        v[0] = fmin(v[0], x);
-        v[1] = fmax(v[1], x);
-        v[2] = fmin(v[2], y);
-        v[3] = fmax(v[3], y);
-    }
-    __shared__ double sh[256];
-    for (int k = 0; k < XY_NPART; ++k) {
-        sh[threadIdx.x] = v[k];
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if ((int)threadIdx.x < w) {
-                const double p = sh[threadIdx.x], q = sh[threadIdx.x + w];
-                sh[threadIdx.x] = k >= 4 ? p + q : ((k & 1) ? fmax(p, q) : fmin(p, q));   // (counts below 2^53: exact)
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) part[(size_t)blockIdx.x * XY_NPART + k] = sh[0];
-        __syncthreads();
-    }
-}
-
-// ---- centre pass: one atomicMax per kept row; rows row0 .. row0 + n - 1 of the table ------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_xy_centre(const XYCols s, int64_t n, int64_t row0, int n_classes, const XYGeom G, unsigned long long *__restrict__ img) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double x = s.x[i], y = s.y[i];
-        const int cls = s.cls ? (int)s.cls[i] : 0;
-        if (!(isfinite(x) && isfinite(y)) || cls >= n_classes) continue;
-        const int px = plot_pixel(x, G.x0, G.x1, G.W), py = G.H - 1 - plot_pixel(y, G.y0, G.y1, G.H);
-        const size_t at = (size_t)py * G.W + px;
-        const unsigned long long key = ((unsigned long long)(row0 + i + 1) << 8) | (unsigned long long)cls;
-        // the image only grows: a stale read is never larger than the current value, so the test can only fail to skip (see k_plot_centre)
-        if (img[at] >= key) continue;
-        atomicMax(&img[at], key);
-    }
-}
 
 // ---- vertices to pixel segments: thread i looks at vertices i - 1, i, i + 1 ------------------------------------------------------------------------------
 __device__ __forceinline__ bool xy_finite(const double *vx, const double *vy, int64_t i, int64_t n) {
     return i >= 0 && i < n && isfinite(vx[i]) && isfinite(vy[i]);
 }
 
-__global__ void __launch_bounds__(256) k_xy_segments(const double *__restrict__ vx, const double *__restrict__ vy, int64_t n, const XYGeom G, XYSeg *__restrict__ seg) {
+__global__ void __launch_bounds__(256) k_xy_segments(const double *__restrict__ vx, const double *__restrict__ vy, int64_t n, const PlotGeom G, XYSeg *__restrict__ seg) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     XYSeg s{-1, -1, -1, -1};
@@ -120,31 +60,15 @@ __global__ void __launch_bounds__(256) k_xy_segments(const double *__restrict__ 
     seg[i] = s;
 }
 
-__device__ __forceinline__ bool xy_covers(const XYSeg &c, int64_t w2, int x, int y) {   // net_covers of ldw_plot_net.hip
-    const int64_t px = x - c.x0, py = y - c.y0, dx = c.x1 - c.x0, dy = c.y1 - c.y0;
-    const int64_t dd = dx * dx + dy * dy, t = px * dx + py * dy;
-    if (t <= 0) return 4 * (px * px + py * py) <= w2;
-    if (t >= dd) {
-        const int64_t qx = px - dx, qy = py - dy;
-        return 4 * (qx * qx + qy * qy) <= w2;
-    }
-    const int64_t cr = px * dy - py * dx;
-    return 4 * cr * cr <= w2 * dd;
-}
-
 // ---- paint: one block per 32 x 32 tile, one thread per pixel (four rows each): disc maximum -> class colour, then the line over it -------------------------
-__global__ void __launch_bounds__(256) k_xy_paint(const XYGeom G, const XYPaint P, const unsigned long long *__restrict__ img, const XYSeg *__restrict__ seg,
+__global__ void __launch_bounds__(256) k_xy_paint(const PlotGeom G, const XYPaint P, const unsigned long long *__restrict__ img, const XYSeg *__restrict__ seg,
                                                   int64_t n_seg, uint8_t *__restrict__ rast) {
     extern __shared__ unsigned long long tile[];
     __shared__ XYSeg hit[256];
     __shared__ int n_hit;
-    const int h = P.h, tw = XY_T + 2 * h, th = XY_T + 2 * h;
-    const int bx = blockIdx.x * XY_T, by = blockIdx.y * XY_T;
-    for (int t = threadIdx.x; t < tw * th; t += 256) {
-        const int gx = bx - h + t % tw, gy = by - h + t / tw;
-        tile[t] = (gx >= 0 && gx < G.W && gy >= 0 && gy < G.H) ? img[(size_t)gy * G.W + gx] : 0ull;   // discs are clipped at the panel
-    }
-    const int lx = threadIdx.x % XY_T, ly0 = threadIdx.x / XY_T;
+    const int bx = blockIdx.x * PLOT_T, by = blockIdx.y * PLOT_T;
+    plot_tile_load(tile, img, G.W, G.H, bx, by, P.disc.h);
+    const int lx = threadIdx.x % PLOT_T, ly0 = threadIdx.x / PLOT_T;
     bool line[4] = {false, false, false, false};
     const int r = (P.line_w + 1) / 2;
     const int64_t w2 = (int64_t)P.line_w * P.line_w;
@@ -154,7 +78,7 @@ __global__ void __launch_bounds__(256) k_xy_paint(const XYGeom G, const XYPaint 
         __syncthreads();
         if (base + threadIdx.x < n_seg) {
             const XYSeg c = seg[base + threadIdx.x];
-            if (c.x0 >= 0 && max(c.x0, c.x1) + r >= bx && min(c.x0, c.x1) - r < bx + XY_T && max(c.y0, c.y1) + r >= by && min(c.y0, c.y1) - r < by + XY_T)
+            if (c.x0 >= 0 && max(c.x0, c.x1) + r >= bx && min(c.x0, c.x1) - r < bx + PLOT_T && max(c.y0, c.y1) + r >= by && min(c.y0, c.y1) - r < by + PLOT_T)
                 hit[atomicAdd(&n_hit, 1)] = c;   // (any order: coverage is an OR)
         }
         __syncthreads();
@@ -162,7 +86,7 @@ __global__ void __launch_bounds__(256) k_xy_paint(const XYGeom G, const XYPaint 
         for (int j = 0; j < m; ++j) {
             const XYSeg c = hit[j];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) line[q] = line[q] || xy_covers(c, w2, bx + lx, by + ly0 + 8 * q);
+            for (int q = 0; q < 4; ++q) line[q] = line[q] || plot_capsule_covers(c.x0, c.y0, c.x1, c.y1, w2, bx + lx, by + ly0 + 8 * q);
         }
     }
     __syncthreads();   // (the tile, when there are no segments)
@@ -174,35 +98,18 @@ __global__ void __launch_bounds__(256) k_xy_paint(const XYGeom G, const XYPaint 
         if (line[q]) {
             rgb = P.line_rgb;
         } else {
-            unsigned long long m = 0;
-            for (int dy = -h; dy <= h; ++dy) {
-                const int w = P.hw[dy + h];
-                const unsigned long long *rowp = tile + (ly + h + dy) * tw + lx + h;
-                for (int dx = -w; dx <= w; ++dx) m = max(m, rowp[dx]);
-            }
-            if (m == 0) {
-                bool grid = false;
-                for (int k = 0; k < P.nx; ++k) grid |= P.xt[k] == gx;
-                for (int k = 0; k < P.ny; ++k) grid |= P.yt[k] == gy;
-                rgb = grid ? PLOT_GRID : PLOT_BG;
-            } else {
-                rgb = P.class_rgb[(int)(m & 0xFF)];   // (cls < n_classes <= LDW_PLOT_MAX_CLASSES by the centre pass)
-            }
+            const unsigned long long m = plot_disc_max(tile, P.disc, lx, ly);
+            rgb = m == 0 ? P.ticks.grid_or_background(gx, gy) : P.class_rgb[(int)(m & 0xFF)];   // (cls < n_classes <= LDW_PLOT_MAX_CLASSES by the centre pass)
         }
-        uint8_t *o = rast + ((size_t)gy * G.W + gx) * 3;
-        o[0] = (uint8_t)(rgb >> 16);
-        o[1] = (uint8_t)(rgb >> 8);
-        o[2] = (uint8_t)rgb;
+        plot_store_rgb(rast + ((size_t)gy * G.W + gx) * 3, rgb);
     }
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------------
 
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, XY_MAX_BLOCKS)); }
-
 struct XYArgs {
-    XYCols cols;   // as given
+    ColSrc cols;        // x, y and, in the panel slot, the class (NULL: class 0), as given
+    PlotFeed<3> feed;   // the same three as host columns
     int64_t n;
     int on_device;
     const double *line_x, *line_y;   // host
@@ -227,7 +134,8 @@ int check_args(const double *x, const double *y, const uint8_t *cls, int64_t n, 
         LDW_REQUIRE(o->class_rgb[k] <= 0xFFFFFFu, LDW_ERR_ARG, "%s: the colour of class %d lies beyond 0xFFFFFF", who, k);
     LDW_REQUIRE(n_line >= 0 && n_line <= XY_MAX_VERTS && (n_line == 0 || (line_x && line_y)), LDW_ERR_ARG, "%s: %lld line vertices (0..%lld), or null vertex arrays", who,
                 (long long)n_line, (long long)XY_MAX_VERTS);
-    a.cols = XYCols{x, y, cls};
+    a.cols = ColSrc{x, y, nullptr, nullptr, cls};
+    a.feed = PlotFeed<3>{{x, y, cls}, {8, 8, 1}};
     a.n = n;
     a.on_device = on_device;
     a.line_x = line_x;
@@ -238,18 +146,13 @@ int check_args(const double *x, const double *y, const uint8_t *cls, int64_t n, 
     return LDW_OK;
 }
 
-// rows [i0, i0 + m) of host columns into ctx->plot_cols (reserved by the caller), queued on the context's stream behind the kernels that read the last chunk
-int upload_chunk(ldw_ctx *c, const XYCols &h, int64_t n, int64_t i0, int64_t m, XYCols &out) {
-    const size_t nd = round256((size_t)std::min<int64_t>(n, XY_CHUNK) * 8);
-    uint8_t *p = c->plot_cols.as<uint8_t>();
-    LDW_HIP(hipMemcpyAsync(p, h.x + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(p + nd, h.y + i0, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-    out = XYCols{(const double *)p, (const double *)(p + nd), nullptr};
-    if (h.cls) {
-        LDW_HIP(hipMemcpyAsync(p + 2 * nd, h.cls + i0, (size_t)m, hipMemcpyHostToDevice, c->stream));
-        out.cls = p + 2 * nd;
-    }
-    return LDW_OK;
+// f(columns on the device, first row, rows): for every chunk of host columns, or once for device columns where they lie
+template <class F> int each_rows(ldw_ctx *c, const XYArgs &a, F f) {
+    if (a.n == 0) return LDW_OK;
+    if (a.on_device) return f(a.cols, (int64_t)0, a.n);
+    return a.feed.each_chunk(c, a.n, [&](const void *const *d, int64_t i0, int64_t m) {
+        return f(ColSrc{(const double *)d[0], (const double *)d[1], nullptr, nullptr, (const uint8_t *)d[2]}, i0, m);
+    });
 }
 
 struct XYStats {
@@ -271,47 +174,24 @@ int reserve_work(ldw_ctx *c, const XYArgs &a, int W, int H, XYWork &w) {
     Carve cv;
     auto keys = cv.take<unsigned long long>((int64_t)pixels);
     auto rast = cv.take<uint8_t>((int64_t)pixels * 3);
-    auto part = cv.take<double>((int64_t)XY_MAX_BLOCKS * XY_NPART);
+    auto part = cv.take<double>((int64_t)PLOT_MAX_BLOCKS * PLOT_NPART);
     auto vx = cv.take<double>(a.n_line);
     auto vy = cv.take<double>(a.n_line);
     auto seg = cv.take<XYSeg>(a.n_line);
     if (int rc = cv.reserve(c->plot_work)) return rc;
     w = XYWork{keys, rast, part, vx, vy, seg, cv.bytes};
     if (!a.on_device && a.n > 0)
-        if (int rc = c->plot_cols.reserve(round256((size_t)std::min<int64_t>(a.n, XY_CHUNK) * 8) * 2 + round256((size_t)std::min<int64_t>(a.n, XY_CHUNK)))) return rc;
-    return LDW_OK;
-}
-
-int stats_accum(ldw_ctx *c, const XYCols &s, int64_t m, int n_classes, double *d_part, double *v) {
-    const int grid = grid_for(m);
-    LDW_LAUNCH(k_xy_stats, dim3(grid), dim3(256), 0, c->stream, s, m, n_classes, d_part);
-    std::vector<double> part((size_t)grid * XY_NPART);
-    LDW_HIP(hipMemcpyAsync(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < grid; ++b)
-        for (int k = 0; k < XY_NPART; ++k) {
-            const double q = part[(size_t)b * XY_NPART + k];
-            v[k] = k >= 4 ? v[k] + q : ((k & 1) ? std::max(v[k], q) : std::min(v[k], q));
-        }
+        if (int rc = c->plot_cols.reserve(a.feed.chunk_bytes(a.n))) return rc;
     return LDW_OK;
 }
 
 // ranges of the kept rows and the finite line vertices; refuses a class out of range
 int xy_stats(ldw_ctx *c, const XYArgs &a, const XYWork &w, XYStats &st, const char *who) {
-    double v[XY_NPART] = {INFINITY, -INFINITY, INFINITY, -INFINITY, 0, 0, 0};
-    if (a.n > 0 && !a.on_device) {
-        for (int64_t i0 = 0; i0 < a.n; i0 += XY_CHUNK) {
-            const int64_t m = std::min<int64_t>(XY_CHUNK, a.n - i0);
-            XYCols cs;
-            if (int rc = upload_chunk(c, a.cols, a.n, i0, m, cs)) return rc;
-            if (int rc = stats_accum(c, cs, m, a.n_classes, w.part, v)) return rc;
-        }
-    } else if (a.n > 0) {
-        if (int rc = stats_accum(c, a.cols, a.n, a.n_classes, w.part, v)) return rc;
-    }
-    LDW_REQUIRE(v[6] == 0, LDW_ERR_ARG, "%s: a class lies outside 0..%d", who, a.n_classes - 1);
-    st.kept = (int64_t)v[4];
-    st.dropped = (int64_t)v[5];
+    double v[PLOT_NPART] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY, 0, 0, 0, 0};   // (plot_stats_accum)
+    if (int rc = each_rows(c, a, [&](const ColSrc &s, int64_t, int64_t m) { return plot_stats_accum(c, s, m, a.n_classes, w.part, v); })) return rc;
+    LDW_REQUIRE(v[8] == 0, LDW_ERR_ARG, "%s: a class lies outside 0..%d", who, a.n_classes - 1);
+    st.kept = (int64_t)v[6];
+    st.dropped = (int64_t)v[7];
     for (int64_t i = 0; i < a.n_line; ++i) {
         const double x = a.line_x[i], y = a.line_y[i];
         if (!(std::isfinite(x) && std::isfinite(y))) continue;
@@ -332,44 +212,24 @@ int xy_stats(ldw_ctx *c, const XYArgs &a, const XYWork &w, XYStats &st, const ch
 // key image -> raster of one panel of W x H pixels, left on the device in w.rast; ev (may be NULL): 4 events round the clear, the centre pass, the paint pass
 int xy_raster(ldw_ctx *c, const XYArgs &a, const XYWork &w, int W, int H, const double xlim[2], const double ylim[2], int nxt, const int32_t *xt, int nyt,
               const int32_t *yt, hipEvent_t *ev) {
-    const XYGeom G{xlim[0], xlim[1], ylim[0], ylim[1], W, H};
-    XYPaint P;
-    memset(&P, 0, sizeof(P));
-    P.D = a.D;
-    P.h = a.D / 2;
-    for (int dy = -P.h; dy <= P.h; ++dy) {
-        int hw = 0;
-        while (4 * ((hw + 1) * (hw + 1) + dy * dy) <= a.D * a.D) ++hw;
-        P.hw[dy + P.h] = (int8_t)hw;
-    }
-    P.nx = nxt;
-    P.ny = nyt;
-    for (int k = 0; k < nxt; ++k) P.xt[k] = xt[k];
-    for (int k = 0; k < nyt; ++k) P.yt[k] = yt[k];
+    const PlotGeom G{xlim[0], xlim[1], ylim[0], ylim[1], W, H, a.n_classes};
+    XYPaint P{};
+    P.disc = PlotDisc::make(a.D);
+    P.ticks = PlotTicks::make(nxt, xt, nyt, yt);
     for (int k = 0; k < a.n_classes; ++k) P.class_rgb[k] = a.o->class_rgb[k];
     P.line_rgb = a.o->line_rgb;
     P.line_w = a.line_w;
     if (ev) LDW_HIP(hipEventRecord(ev[0], c->stream));
     LDW_HIP(hipMemsetAsync(w.keys, 0, (size_t)W * H * 8, c->stream));
     if (ev) LDW_HIP(hipEventRecord(ev[1], c->stream));
-    if (a.n > 0 && !a.on_device) {
-        for (int64_t i0 = 0; i0 < a.n; i0 += XY_CHUNK) {
-            const int64_t m = std::min<int64_t>(XY_CHUNK, a.n - i0);
-            XYCols cs;
-            if (int rc = upload_chunk(c, a.cols, a.n, i0, m, cs)) return rc;
-            LDW_LAUNCH(k_xy_centre, dim3(grid_for(m)), dim3(256), 0, c->stream, cs, m, i0, a.n_classes, G, w.keys);
-        }
-    } else if (a.n > 0) {
-        LDW_LAUNCH(k_xy_centre, dim3(grid_for(a.n)), dim3(256), 0, c->stream, a.cols, a.n, (int64_t)0, a.n_classes, G, w.keys);
-    }
+    if (int rc = each_rows(c, a, [&](const ColSrc &s, int64_t i0, int64_t m) { return plot_centre_classes(c, s, m, i0, G, w.keys); })) return rc;
     if (a.n_line > 0) {
         LDW_HIP(hipMemcpyAsync(w.vx, a.line_x, (size_t)a.n_line * 8, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemcpyAsync(w.vy, a.line_y, (size_t)a.n_line * 8, hipMemcpyHostToDevice, c->stream));
         LDW_LAUNCH(k_xy_segments, dim3((unsigned)((a.n_line + 255) / 256)), dim3(256), 0, c->stream, (const double *)w.vx, (const double *)w.vy, a.n_line, G, w.seg);
     }
     if (ev) LDW_HIP(hipEventRecord(ev[2], c->stream));
-    const size_t lds = (size_t)(XY_T + 2 * P.h) * (XY_T + 2 * P.h) * 8;
-    LDW_LAUNCH(k_xy_paint, dim3((W + XY_T - 1) / XY_T, (H + XY_T - 1) / XY_T), dim3(256), lds, c->stream, G, P, (const unsigned long long *)w.keys,
+    LDW_LAUNCH(k_xy_paint, dim3((W + PLOT_T - 1) / PLOT_T, (H + PLOT_T - 1) / PLOT_T), dim3(256), plot_tile_lds(P.disc), c->stream, G, P, (const unsigned long long *)w.keys,
                (const XYSeg *)w.seg, a.n_line, w.rast);
     if (ev) LDW_HIP(hipEventRecord(ev[3], c->stream));
     return LDW_OK;
@@ -399,18 +259,13 @@ int ldw_plot_xy(ldw_ctx *c, const double *x, const double *y, const uint8_t *cls
     if (int rc = xy_stats(c, a, w, st, "ldw_plot_xy")) return rc;
     if (int rc = ldw_plot_xy_layout_get(opts->kind, 1, st.xr[0], st.xr[1], st.yr[0], st.yr[1], &lay)) return rc;
     if (int rc = xy_raster(c, a, w, W, H, lay.xlim, lay.ylim, lay.n_xticks, lay.xtick_px, lay.n_yticks, lay.ytick_px, nullptr)) return rc;
-    std::vector<uint8_t> raster((size_t)W * H * 3), own;
+    std::vector<uint8_t> raster((size_t)W * H * 3);
     LDW_HIP(hipMemcpyAsync(raster.data(), w.rast, raster.size(), hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     if (dropped_out) *dropped_out = st.dropped;
-    uint8_t *canvas = rgb_out;
-    if (!canvas) {
-        own.resize((size_t)lay.width * lay.height * 3);
-        canvas = own.data();
-    }
-    plot_xy_frame(canvas, lay, opts->kind, raster.data(), title, xlab, ylab, opts->class_rgb, opts->n_classes);
-    if (png_path) return ldw_png_write(png_path, canvas, lay.width, lay.height, -1, nullptr);
-    return LDW_OK;
+    PlotCanvas canvas(rgb_out, lay.width, lay.height);
+    plot_xy_frame(canvas.rgb, lay, opts->kind, raster.data(), title, xlab, ylab, opts->class_rgb, opts->n_classes);
+    return canvas.finish(png_path);
 }
 
 int ldw_debug_plot_xy_panel(ldw_ctx *c, const double *x, const double *y, const uint8_t *cls, int64_t n, int on_device, const double *line_x,
@@ -425,12 +280,16 @@ int ldw_debug_plot_xy_panel(ldw_ctx *c, const double *x, const double *y, const 
     if (int rc = check_gpu(c)) return rc;
     XYWork w;
     if (int rc = reserve_work(c, a, W, H, w)) return rc;
-    PlotEvents<6> ev;
-    if (ms_out) LDW_HIP(ev.create());
+    PlotEvents<2> ev_stats;   // round the statistics pass
+    PlotEvents<4> ev;         // round the clear, the centre pass, the paint pass
+    if (ms_out) {
+        LDW_HIP(ev_stats.create());
+        LDW_HIP(ev.create());
+    }
     XYStats st;
-    if (ms_out) LDW_HIP(hipEventRecord(ev.e[4], c->stream));
+    if (ms_out) LDW_HIP(hipEventRecord(ev_stats.e[0], c->stream));
     if (int rc = xy_stats(c, a, w, st, who)) return rc;
-    if (ms_out) LDW_HIP(hipEventRecord(ev.e[5], c->stream));
+    if (ms_out) LDW_HIP(hipEventRecord(ev_stats.e[1], c->stream));
     double xlim[2], ylim[2], tick[LDW_PLOT_MAX_TICKS];
     int32_t xt[LDW_PLOT_MAX_TICKS], yt[LDW_PLOT_MAX_TICKS], nxt = 0, nyt = 0;
     LDW_REQUIRE(plot_axis(st.xr[0], st.xr[1], W, 0, xlim, tick, xt, &nxt) == LDW_OK && plot_axis(st.yr[0], st.yr[1], H, 1, ylim, tick, yt, &nyt) == LDW_OK, LDW_ERR_ARG,
@@ -439,13 +298,8 @@ int ldw_debug_plot_xy_panel(ldw_ctx *c, const double *x, const double *y, const 
     LDW_HIP(hipMemcpyAsync(rgb_out, w.rast, (size_t)W * H * 3, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     if (ms_out) {
-        float f = 0;
-        LDW_HIP(hipEventElapsedTime(&f, ev.e[4], ev.e[5]));
-        ms_out[0] = f;
-        for (int k = 0; k < 3; ++k) {
-            LDW_HIP(hipEventElapsedTime(&f, ev.e[k], ev.e[k + 1]));
-            ms_out[k + 1] = f;
-        }
+        LDW_HIP(ev_stats.elapsed(ms_out));
+        LDW_HIP(ev.elapsed(ms_out + 1));
     }
     if (stats_out) {
         const double v[6] = {st.xr[0], st.xr[1], st.yr[0], st.yr[1], (double)st.kept, (double)st.dropped};

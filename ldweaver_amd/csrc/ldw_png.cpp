@@ -418,6 +418,16 @@ int ldw_plot_ticks(double lo, double hi, int npx, int flip, double lim_out[2], d
     return LDW_OK;
 }
 
+// the tail of a layout: the data ranges are finite intervals, then both axes of the panel
+static int layout_axes(ldw_plot_layout &L, double x_min, double x_max, double y_min, double y_max, const char *who) {
+    LDW_REQUIRE(std::isfinite(x_min) && std::isfinite(x_max) && x_min <= x_max && std::isfinite(y_min) && std::isfinite(y_max) && y_min <= y_max,
+                LDW_ERR_ARG, "%s: the data ranges are not finite intervals", who);
+    LDW_REQUIRE(plot_axis(x_min, x_max, L.panel_w, 0, L.xlim, L.xtick, L.xtick_px, &L.n_xticks) == LDW_OK &&
+                    plot_axis(y_min, y_max, L.panel_h, 1, L.ylim, L.ytick, L.ytick_px, &L.n_yticks) == LDW_OK,
+                LDW_ERR_ARG, "%s: the axis range of the data is not finite", who);
+    return LDW_OK;
+}
+
 int ldw_plot_layout_get(int kind, int n_panels, double x_min, double x_max, double y_min, double y_max, ldw_plot_layout *out) {
     LDW_REQUIRE(out, LDW_ERR_ARG, "ldw_plot_layout_get: null output");
     LDW_REQUIRE(kind >= LDW_PLOT_SR_CLUST && kind <= LDW_PLOT_LDMAP, LDW_ERR_ARG, "ldw_plot_layout_get: unknown figure kind %d", kind);
@@ -436,8 +446,6 @@ int ldw_plot_layout_get(int kind, int n_panels, double x_min, double x_max, doub
         L.panel[0][2] = L.panel[0][3] = 4600;
         return LDW_OK;
     }
-    LDW_REQUIRE(std::isfinite(x_min) && std::isfinite(x_max) && x_min <= x_max && std::isfinite(y_min) && std::isfinite(y_max) && y_min <= y_max,
-                LDW_ERR_ARG, "ldw_plot_layout_get: the data ranges are not finite intervals");
     static const int R[11] = {0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3}, Cc[11] = {0, 1, 2, 3, 2, 3, 3, 3, 3, 3, 4};   // ggplot2::wrap_dims
     L.width = kind == LDW_PLOT_LR ? 4800 : 2200;
     L.height = 1200;
@@ -469,18 +477,13 @@ int ldw_plot_layout_get(int kind, int n_panels, double x_min, double x_max, doub
         L.cbar[0] = L.width - right + 50;
         L.cbar[1] = (L.height - 400) / 2;
     }
-    LDW_REQUIRE(plot_axis(x_min, x_max, L.panel_w, 0, L.xlim, L.xtick, L.xtick_px, &L.n_xticks) == LDW_OK &&
-                    plot_axis(y_min, y_max, L.panel_h, 1, L.ylim, L.ytick, L.ytick_px, &L.n_yticks) == LDW_OK,
-                LDW_ERR_ARG, "ldw_plot_layout_get: the axis range of the data is not finite");
-    return LDW_OK;
+    return layout_axes(L, x_min, x_max, y_min, y_max, "ldw_plot_layout_get");
 }
 
 int ldw_plot_xy_layout_get(int kind, int n_panels, double x_min, double x_max, double y_min, double y_max, ldw_plot_layout *out) {
     LDW_REQUIRE(out, LDW_ERR_ARG, "ldw_plot_xy_layout_get: null output");
     LDW_REQUIRE(kind == LDW_PLOT_FIT || kind == LDW_PLOT_CDS, LDW_ERR_ARG, "ldw_plot_xy_layout_get: figure kind %d is no xy figure", kind);
     LDW_REQUIRE(n_panels == 1, LDW_ERR_ARG, "ldw_plot_xy_layout_get: %d panels (an xy figure has one)", n_panels);
-    LDW_REQUIRE(std::isfinite(x_min) && std::isfinite(x_max) && x_min <= x_max && std::isfinite(y_min) && std::isfinite(y_max) && y_min <= y_max,
-                LDW_ERR_ARG, "ldw_plot_xy_layout_get: the data ranges are not finite intervals");
     ldw_plot_layout &L = *out;
     memset(&L, 0, sizeof(L));
     L.n_panels = L.rows = L.cols = 1;
@@ -493,10 +496,7 @@ int ldw_plot_xy_layout_get(int kind, int n_panels, double x_min, double x_max, d
     L.panel[0][1] = top;
     L.panel[0][2] = L.panel_w;
     L.panel[0][3] = L.panel_h;
-    LDW_REQUIRE(plot_axis(x_min, x_max, L.panel_w, 0, L.xlim, L.xtick, L.xtick_px, &L.n_xticks) == LDW_OK &&
-                    plot_axis(y_min, y_max, L.panel_h, 1, L.ylim, L.ytick, L.ytick_px, &L.n_yticks) == LDW_OK,
-                LDW_ERR_ARG, "ldw_plot_xy_layout_get: the axis range of the data is not finite");
-    return LDW_OK;
+    return layout_axes(L, x_min, x_max, y_min, y_max, "ldw_plot_xy_layout_get");
 }
 
 int ldw_png_write(const char *path, const uint8_t *rgb, int32_t width, int32_t height, int level, int64_t *bytes_out) {

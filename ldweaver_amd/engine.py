@@ -688,6 +688,12 @@ class Engine:
         return dict(total_ms=v[0], read_ms=v[1], copy_ms=v[2], line_ms=v[3], grep_ms=v[4], chunks=int(v[5]), bytes=int(v[6]), kept=int(v[7]))
 
     # -- the network plot (include/ldweaver_amd.h 12) --------------------------------
+    @staticmethod
+    def _c_strings(seq):
+        """The labels of a figure, encoded, and the ``char *`` array over them (one entry at least; the list keeps the bytes alive)."""
+        names = [x.encode("utf-8", "replace") if isinstance(x, str) else bytes(x) for x in seq]
+        return names, (C.c_char_p * max(len(names), 1))(*names)
+
     CAPSULE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("w", "<i4"), ("rgb", "<u4"), ("alpha", "<i4")])
 
     def plot_capsules(self, caps, W: int, H: int, timings: bool = False):
@@ -702,8 +708,7 @@ class Engine:
         """The network figure (ldw_plot_network).  Returns (canvas uint8 [H, W, 3] or None, boxes int32 [nodes + 2, 4])."""
         caps = np.ascontiguousarray(caps, dtype=self.CAPSULE)
         xy = np.ascontiguousarray(node_xy, dtype=np.int32).reshape(-1, 2)
-        names = [x.encode("utf-8", "replace") if isinstance(x, str) else bytes(x) for x in node_names]
-        arr = (C.c_char_p * max(len(names), 1))(*names)
+        names, arr = self._c_strings(node_names)
         lv = np.ascontiguousarray(legend_value, dtype=np.int32)
         lc = np.ascontiguousarray(legend_rgb, dtype=np.uint32)
         boxes = np.zeros((len(names) + 2, 4), dtype=np.int32)
@@ -734,10 +739,9 @@ class Engine:
         caps = np.ascontiguousarray(caps, dtype=self.CAPSULE)
         rects = np.ascontiguousarray(rects, dtype=self.RECT)
         xy = np.ascontiguousarray(label_xy, dtype=np.int32).reshape(-1, 2)
-        names = [x.encode("utf-8", "replace") if isinstance(x, str) else bytes(x) for x in labels]
+        names, arr = self._c_strings(labels)
         if len(names) != len(xy):
             raise ValueError(f"{len(names)} labels for {len(xy)} anchors")
-        arr = (C.c_char_p * max(len(names), 1))(*names)
         boxes = np.zeros((len(names) + 1, 4), dtype=np.int32)
         canvas = np.empty((int(H), int(W), 3), dtype=np.uint8) if want_canvas else None
         L.check(L.lib().ldw_plot_tanglegram(self._ctx, L.ptr(caps) if len(caps) else None, len(caps), L.ptr(rects) if len(rects) else None, len(rects), int(W),
@@ -777,28 +781,22 @@ class Engine:
         None, boxes int32 [bands + 3, 4]: the band labels, the title, the two legends)."""
         keep, args = self._tree_args(W, H, panel, bars, bar_rgb, levels, palette, band_rect)
         R = args[-1]
-
-        def enc(s):
-            return s.encode("utf-8", "replace") if isinstance(s, str) else bytes(s)
-
-        labels = [enc(s) for s in (band_labels if band_labels is not None else [""] * R)]
+        labels, lab_arr = self._c_strings(band_labels if band_labels is not None else [""] * R)
         if len(labels) != R:
             raise ValueError(f"{len(labels)} band labels for {R} bands")
-        lab_arr = (C.c_char_p * max(R, 1))(*labels)
         legends = list(legends) + [("", [], [], (0, 0))] * (2 - len(legends))
         if len(legends) != 2:
             raise ValueError("at most two legends")
-        lt = (C.c_char_p * 2)(*[enc(g[0]) for g in legends])
+        _, lt = self._c_strings([g[0] for g in legends])
         ln = np.asarray([len(g[1]) for g in legends], dtype=np.int32)
-        entries = [enc(s) for g in legends for s in g[1]]
-        le = (C.c_char_p * max(len(entries), 1))(*entries)
+        entries, le = self._c_strings([s for g in legends for s in g[1]])
         lc = np.ascontiguousarray([int(v) for g in legends for v in g[2]], dtype=np.uint32)
         if len(lc) != len(entries):
             raise ValueError("a legend needs one colour per label")
         lxy = np.ascontiguousarray([v for g in legends for v in g[3]], dtype=np.int32).reshape(4)
         boxes = np.zeros((R + 3, 4), dtype=np.int32)
         canvas = np.empty((int(H), int(W), 3), dtype=np.uint8) if want_canvas else None
-        L.check(L.lib().ldw_plot_tree(self._ctx, *args, C.cast(lab_arr, C.c_void_p) if R else None, enc(title or ""), C.cast(lt, C.c_void_p), L.ptr(ln),
+        L.check(L.lib().ldw_plot_tree(self._ctx, *args, C.cast(lab_arr, C.c_void_p) if R else None, self._c_strings([title or ""])[0][0], C.cast(lt, C.c_void_p), L.ptr(ln),
                                       C.cast(le, C.c_void_p) if entries else None, L.ptr(lc) if entries else None, L.ptr(lxy), int(text_scale),
                                       os.fsencode(png_path) if png_path is not None else None, L.ptr(canvas), L.ptr(boxes)))
         return canvas, boxes

@@ -81,11 +81,16 @@ def plot_opts(kind: int, D: int = 11, ordered: bool = False, layer_rgb=(GREY, 0)
     return o
 
 
-def _columns(x, y, srp, layer, panel):
-    """The five columns as C-contiguous arrays of the C ABI's types: numpy (host) or torch tensors on the GPU (device)."""
-    dev = hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
+SCATTER_COLS = (("x", "float64"), ("y", "float64"), ("srp", "float64"), ("layer", "uint8"), ("panel", "uint8"))
+XY_COLS = (("x", "float64"), ("y", "float64"), ("cls", "uint8"))
+
+
+def _columns(spec, *arrays):
+    """The columns ``arrays`` (None: not given) of the (name, dtype) list ``spec`` as C-contiguous arrays of the C ABI's types: numpy (host) or
+    torch tensors on the GPU (device), as the first one is.  Returns (columns, rows, on the device)."""
+    dev = hasattr(arrays[0], "data_ptr") and bool(getattr(arrays[0], "is_cuda", False))
     cols = []
-    for a, dt in ((x, "float64"), (y, "float64"), (srp, "float64"), (layer, "uint8"), (panel, "uint8")):
+    for a, (_, dt) in zip(arrays, spec):
         if a is None:
             cols.append(None)
         elif dev:
@@ -105,7 +110,7 @@ def _columns(x, y, srp, layer, panel):
 def render_scatter(eng, x, y, srp=None, layer=None, panel=None, *, opts: L.PlotOpts, n_panels: int = 1, labels=None, path=None,
                    want_canvas: bool = False):
     """One scatter figure (ldw_plot_scatter).  Returns (canvas or None, rows dropped)."""
-    cols, n, dev = _columns(x, y, srp, layer, panel)
+    cols, n, dev = _columns(SCATTER_COLS, x, y, srp, layer, panel)
     W, H = CANVAS[opts.kind]
     canvas = np.zeros((H, W, 3), dtype=np.uint8) if want_canvas else None
     lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32)
@@ -131,7 +136,7 @@ def render_links(eng, which: int, *, opts: L.PlotOpts, use_aracne: bool = True, 
 
 def debug_panels(eng, x, y, srp=None, layer=None, panel=None, *, opts: L.PlotOpts, n_panels: int = 1, W: int, H: int, timing: bool = False):
     """The rasters without the frame (ldw_debug_plot_panels): (rgb (n_panels, H, W, 3), stats dict, scratch bytes, ms or None)."""
-    cols, n, dev = _columns(x, y, srp, layer, panel)
+    cols, n, dev = _columns(SCATTER_COLS, x, y, srp, layer, panel)
     out = np.zeros((n_panels, H, W, 3), dtype=np.uint8)
     st, ms, scratch = np.zeros(8), np.zeros(4), C.c_int64(0)
     L.check(L.lib().ldw_debug_plot_panels(eng._ctx, *[L.ptr(c) for c in cols], n, int(dev), C.byref(opts), int(n_panels), int(W), int(H),
@@ -149,23 +154,8 @@ def xy_opts(kind: int, D: int = 11, class_rgb=(0,), line_w: int = 5, line_rgb: i
 
 
 def _xy_columns(x, y, cls, line):
-    """x, y, cls as arrays of the C ABI's types (numpy: host; torch tensors on the GPU: device) and the line's vertices as host arrays."""
-    dev = hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
-    cols = []
-    for a, dt in ((x, "float64"), (y, "float64"), (cls, "uint8")):
-        if a is None:
-            cols.append(None)
-        elif dev:
-            import torch
-            cols.append(a.to(getattr(torch, dt)).contiguous())
-        else:
-            cols.append(np.ascontiguousarray(a, dtype=dt))
-    if dev:
-        import torch
-        torch.cuda.current_stream().synchronize()   # the library reads the columns on the engine's stream
-    n = len(cols[0])
-    if any(c is not None and len(c) != n for c in cols):
-        raise ValueError("the columns differ in length")
+    """x, y, cls through ``_columns`` and the line's vertices as host arrays."""
+    cols, n, dev = _columns(XY_COLS, x, y, cls)
     lx, ly = (None, None) if line is None else (np.ascontiguousarray(line[0], dtype=np.float64), np.ascontiguousarray(line[1], dtype=np.float64))
     if lx is not None and len(lx) != len(ly):
         raise ValueError("the line's vertex arrays differ in length")
@@ -239,11 +229,7 @@ def cds_cluster_plot(cds_var, path, *, engine=None) -> str:
 
 def render_heatmap(eng, htm, path, title=None):
     """LD_plot.png of a B x B map in [0, 1] (ldw_plot_heatmap)."""
-    dev = hasattr(htm, "data_ptr") and bool(getattr(htm, "is_cuda", False))
-    h = htm.contiguous() if dev else np.ascontiguousarray(htm, dtype=np.float64)
-    if dev:
-        import torch
-        torch.cuda.current_stream().synchronize()
+    (h,), _, dev = _columns((("htm", "float64"),), htm)
     if h.ndim != 2 or h.shape[0] != h.shape[1]:
         raise ValueError("the map must be square")
     L.check(L.lib().ldw_plot_heatmap(eng._ctx, L.ptr(h), int(h.shape[0]), int(dev), None if title is None else str(title).encode(),
