@@ -145,6 +145,11 @@ int ldw_overflow_report(ldw_ctx *ctx, int64_t out[4]);
  * had to grow where it is used, or that ldw_ctx_reserve had not made —, out[1..5] bytes held now, summed over the pipeline slots, by the unit
  * lists, the per-block SNP constants, the pair lists, the row bins / flags and the maybe list's extracts. */
 int ldw_slot_report(ldw_ctx *ctx, int64_t out[6]);
+/* What the library holds on the GPU side, process-wide (all devices, all contexts): out[0] device blocks held by live buffers, out[1] released
+ * device blocks waiting on the free list (ldw_host_trim empties it), out[2] pinned host blocks, out[3] events, out[4] streams the library
+ * created and has not destroyed (a stream handed in by ldw_ctx_set_stream is never counted).  A context's share of out[0], out[2], out[3] and
+ * out[4] is gone after ldw_ctx_destroy: tests/test_ctx_lifecycle_gpu.py compares the counts around whole jobs. */
+int ldw_resource_report(int64_t out[5]);
 
 /* ---- inspection and test hooks (BOUNDS.md; tests/test_bounds.py brute-forces every bound of the default path through them;
  *      ldweaver_amd/csrc/ldw_debug.hip) ------------------------------------------------------------------------------------------- */

@@ -195,6 +195,7 @@ _SIGS_DEBUG = {
     "ldw_span_report": (C.c_int, [_p, _p]),
     "ldw_overflow_report": (C.c_int, [_p, _p]),
     "ldw_slot_report": (C.c_int, [_p, _p]),
+    "ldw_resource_report": (C.c_int, [_p]),
     "ldw_snp_bounds": (C.c_int, [_p, _p, C.c_int64]),
     "ldw_debug_violations": (C.c_int, [_p, _p]),
     "ldw_debug_tab11": (C.c_int, [_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),

@@ -200,6 +200,7 @@ hipError_t dev_alloc(void **out, size_t want, size_t &cap_out) {
 }
 }  // namespace
 
+OwnCounts g_own;
 size_t device_pool_trim() { return pool_flush(); }
 // the per-SNP state counts into ctx->counts ([L][5] int32) on the context's stream; no copy, no synchronisation (ldw_state_counts, ldw_hamming_weights)
 int launch_state_counts(ldw_ctx *c);
@@ -211,13 +212,10 @@ DrainedScope::~DrainedScope() { g_owner_drained = false; }
 
 int DevBuf::reserve(size_t bytes) {
     if (bytes <= cap && p) return LDW_OK;
-    if (p) {
-        pool_give(p, cap);
-        p = nullptr;
-        cap = 0;
-    }
+    release();
     size_t want = bytes < 256 ? 256 : bytes, got = 0;
     LDW_HIP(dev_alloc(&p, want, got));
+    ++g_own.dev;
     cap = got;
     return LDW_OK;
 }
@@ -238,47 +236,27 @@ int DevBuf::reserve_keep(size_t bytes, size_t used, hipStream_t s) {
         }
     }
     if (p && used) {
-        LDW_HIP(hipMemcpyAsync(np, p, used, hipMemcpyDeviceToDevice, s));
-        LDW_HIP(hipStreamSynchronize(s));
+        hipError_t e = hipMemcpyAsync(np, p, used, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            pool_give(np, got);
+            return hip_fail(e, "DevBuf::reserve_keep: copy of the kept bytes", __FILE__, __LINE__);
+        }
     }
-    if (p) pool_give(p, cap);
+    release();
+    ++g_own.dev;
     p = np;
     cap = got;
     return LDW_OK;
 }
 
 void DevBuf::release() {
-    if (p) pool_give(p, cap);
+    if (p) {
+        pool_give(p, cap);
+        --g_own.dev;
+    }
     p = nullptr;
     cap = 0;
-}
-
-int PinnedPair::reserve(size_t bytes, const char *who) {
-    if (bytes <= cap) return LDW_OK;
-    release();
-    for (auto &q : p)
-        if (hipHostMalloc(&q, bytes, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();   // (the error is sticky; the slot may hold anything)
-            q = nullptr;
-            release();
-            set_error("%s: hipHostMalloc of %zu bytes failed", who, bytes);
-            return LDW_ERR_HIP;
-        }
-    cap = bytes;
-    return LDW_OK;
-}
-
-int64_t PinnedPair::release() {
-    int64_t n = 0;
-    for (auto &q : p) {
-        if (q) {
-            (void)hipHostFree(q);
-            n += (int64_t)cap;
-        }
-        q = nullptr;
-    }
-    cap = 0;
-    return n;
 }
 
 int check_gpu(ldw_ctx *ctx) {
@@ -542,27 +520,29 @@ int ldw_ctx_create(int device, ldw_ctx **out) {
         set_error("ldw_ctx_create: device %d is %s; kernels are built for gfx950 only", device, prop.gcnArchName);
         return LDW_ERR_NOGPU;
     }
-    ldw_ctx *c = new ldw_ctx();
+    // a half-built context is not handed out: every failing return below destroys it (and takes it off the live count); *out stays null, the error text is the failure's
+    struct Destroy {
+        void operator()(ldw_ctx *h) const {
+            const std::string msg = ldw_last_error();
+            ldw_ctx_destroy(h);
+            ldw::set_error("%s", msg.c_str());
+        }
+    };
+    std::unique_ptr<ldw_ctx, Destroy> guard(new ldw_ctx());
+    ldw_ctx *c = guard.get();
     ldw::ctx_count(+1);
     c->device = device;
     c->prune = getenv("LDW_NO_PRUNE") == nullptr;
-    LDW_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    c->own_stream = true;
-    for (auto &e : c->ev) LDW_HIP(hipEventCreate(&e));
+    LDW_HIP(c->stream.ensure(hipStreamNonBlocking));
+    for (auto &e : c->ev) LDW_HIP(e.ensure());
     // r04: the two extra streams of the all-pairs loop (hipStreamCreate: 12 ms each on this box), its events and pinned pick records are made
     // WITH the context, and the code objects of the pass's kernels (loaded at the first launch of a kernel of each translation unit
     // otherwise) by a side thread that starts with it — not inside the first pass of the job.  Joined by the entry points (join_prepare).
     static const bool no_prep = getenv("LDW_NO_PREPARE") != nullptr;
     if (!no_prep) {
         // (the streams here, synchronously: a side thread inside hipStreamCreate slowed the caller's upload of the alignment from 9.5 to 17 ms)
-        if (int rc = ldw::ensure_streams(c)) {   // (a half-built context is not handed out — destroyed here, *out stays null)
-            const std::string msg = ldw_last_error();
-            ldw_ctx_destroy(c);
-            *out = nullptr;
-            ldw::set_error("%s", msg.c_str());
-            return rc;
-        }
-        c->prep_thread = new std::thread([c] {
+        if (int rc = ldw::ensure_streams(c)) return rc;
+        c->prep_thread = std::thread([c] {
             int rc = LDW_OK;
             if (hipSetDevice(c->device) != hipSuccess) rc = LDW_ERR_HIP;
             if (rc == LDW_OK) {
@@ -576,7 +556,7 @@ int ldw_ctx_create(int device, ldw_ctx **out) {
             c->prep_rc = rc;
         });
     }
-    *out = c;
+    *out = guard.release();
     return LDW_OK;
 }
 
@@ -587,11 +567,7 @@ int ldw_ctx_create(int device, ldw_ctx **out) {
 int ldw_ctx_reserve(ldw_ctx *c, int64_t L, int64_t N, int64_t max_blk_sz) {
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(L > 0 && N > 0 && max_blk_sz > 0, LDW_ERR_ARG, "ldw_ctx_reserve: L, N and max_blk_sz must be positive");
-    if (c->prep_thread2) {   // an earlier reservation: finish it first
-        if (c->prep_thread2->joinable()) c->prep_thread2->join();
-        delete c->prep_thread2;
-        c->prep_thread2 = nullptr;
-    }
+    if (c->prep_thread2.joinable()) c->prep_thread2.join();   // an earlier reservation: finish it first
     static const bool no_prep = getenv("LDW_NO_PREPARE") != nullptr;
     if (no_prep) return LDW_OK;
     const int64_t blk = std::min<int64_t>(L, max_blk_sz);
@@ -601,21 +577,13 @@ int ldw_ctx_reserve(ldw_ctx *c, int64_t L, int64_t N, int64_t max_blk_sz) {
     const int64_t nt = blk * nseg, rows_f = blk * 5 / 4 + 512, rows_t = nt * 5 / 4 + 512;
     const size_t stage = (size_t)((blk + nt) * 12 + (rows_f + rows_t) * 9 + nt * 52 + (blk + 64) * 16 + 3 * (rows_t / 128 + 1) * (rows_f / 64 + 1) + 65536);   // (r06: + the band's tile list, at most 2 bytes per tile of the mask)
     const int64_t Npad = (N + ldw::KSTEP - 1) / ldw::KSTEP * ldw::KSTEP;
-    c->prep_thread2 = new std::thread([c, stage, Npad, blk, nseg] {
+    c->prep_thread2 = std::thread([c, stage, Npad, blk, nseg] {
         int rc = LDW_OK;
         if (hipSetDevice(c->device) != hipSuccess) rc = LDW_ERR_HIP;
         if (rc == LDW_OK) rc = ldw::reserve_slot_buffers(c, Npad, blk, nseg);
         for (int k = 0; k < LDW_NSLOT && rc == LDW_OK; ++k) {
-            if (c->pin_cap[k] >= stage) continue;
-            if (c->pin[k]) (void)hipHostFree(c->pin[k]);
-            c->pin[k] = nullptr;
-            c->pin_cap[k] = 0;
-            if (hipHostMalloc(&c->pin[k], stage * 2, hipHostMallocDefault) != hipSuccess) {
-                ldw::set_error("ldw_ctx_reserve: hipHostMalloc of %zu bytes failed", stage * 2);
-                rc = LDW_ERR_HIP;
-                break;
-            }
-            c->pin_cap[k] = stage * 2;
+            if (c->pin[k].cap >= stage) continue;
+            if ((rc = c->pin[k].reserve(stage * 2, "ldw_ctx_reserve")) != LDW_OK) break;
             if (c->dstage[k].reserve(stage * 2) != LDW_OK) rc = LDW_ERR_HIP;
         }
         if (rc != LDW_OK) c->prep_err2 = ldw_last_error();
@@ -630,63 +598,16 @@ int ldw_ctx_destroy(ldw_ctx *c) {
     (void)ldw::join_prepare(c);
     (void)ldw_tsv_join(c);
     (void)ldw_lr_stream_end(c, nullptr, nullptr, nullptr);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->gemm_stream) (void)hipStreamSynchronize(c->gemm_stream);
-    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    if (c->lr_st) (void)hipStreamSynchronize(c->lr_st);
+    for (hipStream_t s : {(hipStream_t)c->stream, (hipStream_t)c->gemm_stream, (hipStream_t)c->copy_stream, (hipStream_t)c->lr_st})
+        if (s) (void)hipStreamSynchronize(s);
     {
-    ldw::DrainedScope drained;   // every stream that could touch this context's blocks is idle: no device-wide synchronisation per released block
-    ldw::fasta_release(c);
-    ldw::out_release(c);
-    ldw::grep_release(c);
-    ldw::tsv_release(c);
-    ldw::DevBuf *bufs[] = {&c->srm_tmp, &c->chars, &c->states, &c->digits, &c->vfixed, &c->r, &c->uqe, &c->POS, &c->paint, &c->Mbits, &c->row0,
-                           &c->slot_meta, &c->slot_pfix, &c->apx_skip, &c->snp_sup, &c->counts, &c->pfix_state, &c->G, &c->MIblk, &c->rowlist_f, &c->rowlist_t,
-                           &c->idx_f, &c->idx_t, &c->lrow_f, &c->lrow_t, &c->perm_f, &c->perm_t, &c->scr_units, &c->epi_rest, &c->slot_pfix_hi, &c->glo, &c->lo_rows, &c->packs, &c->colcnt,
-                           &c->cand_key2, &c->cand_val2, &c->sel_bitmap, &c->sel_chunks, &c->sel_prefix, &c->scratch, &c->small, &c->sr_a, &c->sr_b,
-                           &c->sr_mi, &c->lr_a, &c->lr_b, &c->lr_mi, &c->srm_pack, &c->srm_key, &c->srm_pack2, &c->srm_key2, &c->srm_pay, &c->srm_pay2, &c->srm_off,
-                           &c->srm_q, &c->srm_n, &c->srm_md, &c->srm_part, &c->srm_shape, &c->srm_cnt, &c->red_row, &c->red_meta,
-                           &c->red_srp, &c->pool_a, &c->pool_b, &c->pool_mi, &c->ar_key, &c->ar_val, &c->ar_key2, &c->ar_val2,
-                           &c->ar_off, &c->ar_flags, &c->seq_perm, &c->dig_a, &c->dig_b, &c->apx_shift, &c->slot_papx, &c->pop_segs, &c->pop_wbeg, &c->pop_vpos,
-                           &c->pair_sums, &c->tab11[0], &c->tab11[1], &c->G2, &c->G3, &c->miss_key, &c->miss_val, &c->srd_lower, &c->srd_cur, &c->srd_out, &c->srd_seg, &c->pos_ord.order, &c->pos_ord.srt, &c->pos_ord.slot,
-                           &c->cds_keep, &c->cds_work, &c->annot_keep, &c->annot_work, &c->plot_work, &c->plot_cols};
-    for (auto *b : bufs) b->release();
-    for (int k = 0; k < LDW_NSLOT; ++k)
-        for (ldw::DevBuf *b : {&c->panel[k][0], &c->panel[k][1], &c->Gapx[k], &c->pairs[k], &c->apx_mini[k], &c->apx_units[k], &c->apx_packs[k], &c->apx_bins[k], &c->apx_clean[k],
-                               &c->hist[k], &c->cand_key[k], &c->cand_val[k]})
-            b->release();
-    for (auto &e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < LDW_NSLOT; ++k) {
-        c->dstage[k].release();
-        if (c->pin[k]) (void)hipHostFree(c->pin[k]);
-        if (c->ev_up[k]) (void)hipEventDestroy(c->ev_up[k]);
-        if (c->ev_done[k]) (void)hipEventDestroy(c->ev_done[k]);
+        ldw::DrainedScope drained;   // every stream that could touch this context's blocks is idle: no device-wide synchronisation per released block
+        ldw::fasta_release(c);
+        ldw::out_release(c);
+        ldw::grep_release(c);
+        ldw::tsv_release(c);
+        delete c;
     }
-    c->dstage[LDW_NSLOT].release();   // (the staging of a span segment redone on its own)
-    }
-    if (c->pin[LDW_NSLOT]) (void)hipHostFree(c->pin[LDW_NSLOT]);
-    for (int k = 0; k < LDW_NSLOT; ++k) {
-        if (c->pin_pick[k]) (void)hipHostFree(c->pin_pick[k]);
-        if (c->ev_pick[k]) (void)hipEventDestroy(c->ev_pick[k]);
-    }
-    if (c->pin_fetch) (void)hipHostFree(c->pin_fetch);
-    if (c->pin_lrc) (void)hipHostFree(c->pin_lrc);
-    if (c->ev_lrc) (void)hipEventDestroy(c->ev_lrc);
-    for (auto &e : c->ev_probe)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->ev_pool) (void)hipEventDestroy(e);
-    for (auto &e : c->lr_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->lr_counts) (void)hipHostFree(c->lr_counts);
-    if (c->lr_pin) (void)hipHostFree(c->lr_pin);
-    if (c->lr_st) (void)hipStreamDestroy(c->lr_st);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->gemm_stream) (void)hipStreamDestroy(c->gemm_stream);
-    for (auto &e : c->ev_gemm)
-        if (e) (void)hipEventDestroy(e);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
     ldw::ctx_count(-1);
     return LDW_OK;
 }
@@ -694,14 +615,25 @@ int ldw_ctx_destroy(ldw_ctx *c) {
 int ldw_ctx_set_stream(ldw_ctx *c, void *s) {
     if (int rc = check_gpu(c)) return rc;
     LDW_HIP(hipStreamSynchronize(c->stream));
-    if (c->own_stream && c->stream) LDW_HIP(hipStreamDestroy(c->stream));
     if (s) {
-        c->stream = (hipStream_t)s;
-        c->own_stream = false;
+        c->stream.adopt((hipStream_t)s);
     } else {
-        LDW_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        c->own_stream = true;
+        c->stream.destroy();
+        LDW_HIP(c->stream.ensure(hipStreamNonBlocking));
     }
+    return LDW_OK;
+}
+
+int ldw_resource_report(int64_t out[5]) {
+    LDW_REQUIRE(out, LDW_ERR_ARG, "ldw_resource_report: null argument");
+    out[0] = ldw::g_own.dev;
+    {
+        std::lock_guard<std::mutex> lk(ldw::g_pool_mtx);
+        out[1] = (int64_t)ldw::g_pool.size();
+    }
+    out[2] = ldw::g_own.pinned;
+    out[3] = ldw::g_own.events;
+    out[4] = ldw::g_own.streams;
     return LDW_OK;
 }
 
@@ -1247,37 +1179,37 @@ __global__ __launch_bounds__(256) void k_snp_sup(int64_t L, const uint32_t *__re
     for (int k = 0; k < 4; ++k) sup[a * 4 + k] = out[k];
 }
 
+// dst (int64 [L][5]) = the fixed-point marginals of the per-sequence weights w [Npad] by slot (h_slot_meta), shifted right by `shift`; synchronous
+static int slot_marginals(ldw_ctx *c, const std::vector<int64_t> &w, int shift, ldw::DevBuf &dst, const char *what) {
+    const int64_t L = c->L, Npad = c->Npad;
+    ldw::DevBuf d_w, d_p, d_cnt;
+    if (int rc = d_w.reserve((size_t)Npad * 8)) return rc;
+    if (int rc = d_p.reserve((size_t)L * 40)) return rc;
+    if (int rc = d_cnt.reserve((size_t)L * 20)) return rc;
+    if (int rc = dst.reserve((size_t)L * 40)) return rc;
+    hipError_t he = hipMemcpyAsync(d_w.p, w.data(), (size_t)Npad * 8, hipMemcpyHostToDevice, c->stream);
+    hipLaunchKernelGGL(k_counts_marginals, dim3((unsigned)((L + 3) / 4)), dim3(256), 0, c->stream, c->states.as<uint8_t>(), L, Npad, d_w.as<int64_t>(),
+                       d_cnt.as<int32_t>(), d_p.as<int64_t>());
+    std::vector<int64_t> by_state((size_t)L * 5), by_slot((size_t)L * 5, 0);
+    if (he == hipSuccess) he = hipMemcpyAsync(by_state.data(), d_p.p, (size_t)L * 40, hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    if (he != hipSuccess) return ldw::hip_fail(he, what, __FILE__, __LINE__);
+    for (int64_t a = 0; a < L; ++a) {
+        const uint32_t m = c->h_slot_meta[a];
+        const int n = (int)(m & 7);
+        for (int i = 0; i <= n; ++i) by_slot[a * 5 + i] = by_state[a * 5 + ((m >> (8 + 3 * i)) & 7)] >> shift;
+    }
+    LDW_HIP(hipMemcpyAsync(dst.p, by_slot.data(), (size_t)L * 40, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    return LDW_OK;
+}
+
 // Marginals of the high-limb weights, by slot, for the screen of the MIXED-precision path — made when a block first takes that path (r04: the
 // default path never does, and building them eagerly cost 2.5 ms of every job's ldw_set_snp_meta).
 int ensure_hi_marginals(ldw_ctx *c) {
     if (c->hi_ready || c->nlimbs != 5) return LDW_OK;
-    const int64_t L = c->L, Npad = c->Npad;
-    const std::vector<uint32_t> &meta = c->h_slot_meta;
-    LDW_REQUIRE((int64_t)meta.size() == L, LDW_ERR_STATE, "ensure_hi_marginals: the row map has not been built");
-    {
-        ldw::DevBuf d_vhi, d_phi, d_cnt2;
-        int rc = LDW_OK;
-        if ((rc = d_vhi.reserve((size_t)Npad * 8)) || (rc = d_phi.reserve((size_t)L * 40)) || (rc = d_cnt2.reserve((size_t)L * 20)) ||
-            (rc = c->slot_pfix_hi.reserve((size_t)L * 40))) {
-            d_vhi.release(); d_phi.release(); d_cnt2.release();
-            return rc;
-        }
-        hipError_t he = hipMemcpyAsync(d_vhi.p, c->h_vfixed_hi.data(), (size_t)Npad * 8, hipMemcpyHostToDevice, c->stream);
-        hipLaunchKernelGGL(k_counts_marginals, dim3((unsigned)((L + 3) / 4)), dim3(256), 0, c->stream, c->states.as<uint8_t>(), L, Npad,
-                           d_vhi.as<int64_t>(), d_cnt2.as<int32_t>(), d_phi.as<int64_t>());
-        std::vector<int64_t> phs((size_t)L * 5), sph((size_t)L * 5, 0);
-        if (he == hipSuccess) he = hipMemcpyAsync(phs.data(), d_phi.p, (size_t)L * 40, hipMemcpyDeviceToHost, c->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-        d_vhi.release(); d_phi.release(); d_cnt2.release();
-        if (he != hipSuccess) return ldw::hip_fail(he, "high-limb marginals", __FILE__, __LINE__);
-        for (int64_t a = 0; a < L; ++a) {
-            const uint32_t m = meta[a];
-            const int n = (int)(m & 7);
-            for (int i = 0; i <= n; ++i) sph[a * 5 + i] = phs[a * 5 + ((m >> (8 + 3 * i)) & 7)];
-        }
-        LDW_HIP(hipMemcpyAsync(c->slot_pfix_hi.p, sph.data(), (size_t)L * 40, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipStreamSynchronize(c->stream));
-    }
+    LDW_REQUIRE((int64_t)c->h_slot_meta.size() == c->L, LDW_ERR_STATE, "ensure_hi_marginals: the row map has not been built");
+    if (int rc = slot_marginals(c, c->h_vfixed_hi, 0, c->slot_pfix_hi, "high-limb marginals")) return rc;
     c->hi_ready = true;
     return LDW_OK;
 }
@@ -1366,28 +1298,7 @@ int ensure_rows(ldw_ctx *c) {
     LDW_HIP(hipMemcpyAsync(c->slot_pfix.p, spf.data(), (size_t)L * 40, hipMemcpyHostToDevice, c->stream));
     c->hi_ready = false;   // (the high-limb marginals of the mixed-precision path are made when a block first takes that path: ensure_hi_marginals)
     if (c->apx_ok) {   // marginals of the approximate weights V' = a b 2^e by slot, in the accumulators' final unit 2^e_last (floor)
-        ldw::DevBuf d_v, d_p, d_cnt2;
-        int rc = LDW_OK;
-        if ((rc = d_v.reserve((size_t)Npad * 8)) || (rc = d_p.reserve((size_t)L * 40)) || (rc = d_cnt2.reserve((size_t)L * 20)) ||
-            (rc = c->slot_papx.reserve((size_t)L * 40))) {
-            d_v.release(); d_p.release(); d_cnt2.release();
-            return rc;
-        }
-        hipError_t he = hipMemcpyAsync(d_v.p, c->h_vapx.data(), (size_t)Npad * 8, hipMemcpyHostToDevice, c->stream);
-        hipLaunchKernelGGL(k_counts_marginals, dim3((unsigned)((L + 3) / 4)), dim3(256), 0, c->stream, c->states.as<uint8_t>(), L, Npad,
-                           d_v.as<int64_t>(), d_cnt2.as<int32_t>(), d_p.as<int64_t>());
-        std::vector<int64_t> pas((size_t)L * 5), spa((size_t)L * 5, 0);
-        if (he == hipSuccess) he = hipMemcpyAsync(pas.data(), d_p.p, (size_t)L * 40, hipMemcpyDeviceToHost, c->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-        d_v.release(); d_p.release(); d_cnt2.release();
-        if (he != hipSuccess) return ldw::hip_fail(he, "approximate-weight marginals", __FILE__, __LINE__);
-        for (int64_t a = 0; a < L; ++a) {
-            const uint32_t m = meta[a];
-            const int n = (int)(m & 7);
-            for (int i = 0; i <= n; ++i) spa[a * 5 + i] = pas[a * 5 + ((m >> (8 + 3 * i)) & 7)] >> c->apx_e_last;
-        }
-        LDW_HIP(hipMemcpyAsync(c->slot_papx.p, spa.data(), (size_t)L * 40, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipStreamSynchronize(c->stream));
+        if (int rc = slot_marginals(c, c->h_vapx, c->apx_e_last, c->slot_papx, "approximate-weight marginals")) return rc;
     }
     // rows R .. R+TILE-1 stay zero: tile padding of the row lists points at row R
     LDW_HIP(hipMemsetAsync(c->Mbits.as<uint64_t>() + (size_t)R * c->KW, 0, (size_t)TILE * c->KW * 8, c->stream));

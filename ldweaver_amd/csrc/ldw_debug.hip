@@ -173,39 +173,31 @@ int ldw_debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t
     std::copy(rows_t, rows_t + nrt, rl.begin());
     std::copy(rows_f, rows_f + nrf, rl.begin() + RTpad);
     DevBuf d_rl, d_pt, d_pf, d_G;
-    int rc = LDW_OK;
-    if ((rc = d_rl.reserve(rl.size() * 4)) || (rc = d_pt.reserve((size_t)M2 * RTpad * 32)) || (rc = d_pf.reserve((size_t)M2 * RFpad * 32)) ||
-        (rc = d_G.reserve((size_t)RTpad * RFpad * 4))) {
-        d_rl.release(); d_pt.release(); d_pf.release(); d_G.release();
-        return rc;
-    }
-    auto body = [&]() -> int {
-        LDW_HIP(hipMemcpyAsync(d_rl.p, rl.data(), rl.size() * 4, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemsetAsync(d_G.p, 0xFF, (size_t)RTpad * RFpad * 4, c->stream));   // (every entry must be WRITTEN by the kernel)
-        if (int r2 = launch_pack_panel(c, d_rl.as<int32_t>() + RTpad, RFpad, d_pf.as<uint64_t>(), c->stream, d_rl.as<int32_t>(), RTpad, d_pt.as<uint64_t>())) return r2;
-        ApxGemmArgs P;
-        memset(&P, 0, sizeof(P));
-        P.panel_t = d_pt.as<uint64_t>();
-        P.panel_f = d_pf.as<uint64_t>();
-        P.RTpad = RTpad;
-        P.RFpad = RFpad;
-        P.M2 = M2;
-        P.dig_a = c->dig_a.as<uint8_t>();
-        P.dig_b = c->dig_b.as<uint8_t>();
-        P.shift = c->apx_shift.as<int32_t>();
-        P.G = d_G.as<int32_t>();
-        P.fine = c->apx_fine ? 1 : 0;
-        if (int r2 = launch_gemm_apx(c, P, c->stream)) return r2;
-        std::vector<int32_t> h((size_t)RTpad * RFpad);
-        LDW_HIP(hipMemcpyAsync(h.data(), d_G.p, h.size() * 4, hipMemcpyDeviceToHost, c->stream));
-        LDW_HIP(hipStreamSynchronize(c->stream));
-        for (int t = 0; t < nrt; ++t) memcpy(out + (size_t)t * nrf, h.data() + (size_t)t * RFpad, (size_t)nrf * 4);
-        return LDW_OK;
-    };
-    rc = body();
-    (void)hipStreamSynchronize(c->stream);
-    d_rl.release(); d_pt.release(); d_pf.release(); d_G.release();
-    return rc;
+    if (int rc = d_rl.reserve(rl.size() * 4)) return rc;
+    if (int rc = d_pt.reserve((size_t)M2 * RTpad * 32)) return rc;
+    if (int rc = d_pf.reserve((size_t)M2 * RFpad * 32)) return rc;
+    if (int rc = d_G.reserve((size_t)RTpad * RFpad * 4)) return rc;
+    LDW_HIP(hipMemcpyAsync(d_rl.p, rl.data(), rl.size() * 4, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemsetAsync(d_G.p, 0xFF, (size_t)RTpad * RFpad * 4, c->stream));   // (every entry must be WRITTEN by the kernel)
+    if (int r2 = launch_pack_panel(c, d_rl.as<int32_t>() + RTpad, RFpad, d_pf.as<uint64_t>(), c->stream, d_rl.as<int32_t>(), RTpad, d_pt.as<uint64_t>())) return r2;
+    ApxGemmArgs P;
+    memset(&P, 0, sizeof(P));
+    P.panel_t = d_pt.as<uint64_t>();
+    P.panel_f = d_pf.as<uint64_t>();
+    P.RTpad = RTpad;
+    P.RFpad = RFpad;
+    P.M2 = M2;
+    P.dig_a = c->dig_a.as<uint8_t>();
+    P.dig_b = c->dig_b.as<uint8_t>();
+    P.shift = c->apx_shift.as<int32_t>();
+    P.G = d_G.as<int32_t>();
+    P.fine = c->apx_fine ? 1 : 0;
+    if (int r2 = launch_gemm_apx(c, P, c->stream)) return r2;
+    std::vector<int32_t> h((size_t)RTpad * RFpad);
+    LDW_HIP(hipMemcpyAsync(h.data(), d_G.p, h.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    for (int t = 0; t < nrt; ++t) memcpy(out + (size_t)t * nrf, h.data() + (size_t)t * RFpad, (size_t)nrf * 4);
+    return LDW_OK;
 }
 
 int ldw_debug_screen_bound(ldw_ctx *c, int kind, int na, int nb, int64_t n, const int64_t *g, const int64_t *pa, const int64_t *pb, const float *pX, const float *pY,
@@ -232,43 +224,42 @@ int ldw_debug_screen_bound(ldw_ctx *c, int kind, int na, int nb, int64_t n, cons
                  o_m = o_rr + al(sz_r), o_o = o_m + al(sz_m), o_o64 = o_o + al(sz_o), total = o_o64 + al(sz_o64);
     if (int rc = B.reserve(total)) return rc;
     char *base = B.as<char>();
-    auto body = [&]() -> int {
-        LDW_HIP(hipMemcpyAsync(base + o_g, g, sz_g, hipMemcpyHostToDevice, c->stream));
-        if (apx) LDW_HIP(hipMemcpyAsync(base + o_g32, g32.data(), sz_g32, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(base + o_pa, pa, sz_p, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(base + o_pb, pb, sz_p, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(base + o_pX, pX, sz_f, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(base + o_pY, pY, sz_f, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(base + o_rr, rr, sz_r, hipMemcpyHostToDevice, c->stream));
-        if (masks) LDW_HIP(hipMemcpyAsync(base + o_m, masks, sz_m, hipMemcpyHostToDevice, c->stream));
-        EpiArgs A;
-        memset(&A, 0, sizeof(A));
-        A.neff = params[5];
-        A.scale = std::ldexp(1.0, -(int)params[0]);
-        A.quirk = LDW_QUIRK_INTENDED;
-        A.E.apx = apx ? 1 : 0;
-        A.E.apx_EG = (float)params[6];
-        A.E.apx_dfac = (float)params[7];
-        A.E.apx_s1 = (float)params[8];
-        A.E.apx_c1 = (float)params[9];
-        A.E.apx_W = params[10];
-        A.E.apx_unit = params[11];
-        A.E.apx_MU = (float)params[18];
-        A.E.scr_shift = apx ? 0 : (int)params[13];
-        A.E.scr_scale = (float)(apx ? params[12] : params[14]);
-        DbgArrays D;
-        D.g = reinterpret_cast<const int64_t *>(base + o_g);
-        D.g32 = reinterpret_cast<const int32_t *>(base + o_g32);
-        D.pa = reinterpret_cast<const int64_t *>(base + o_pa);
-        D.pb = reinterpret_cast<const int64_t *>(base + o_pb);
-        D.pX = reinterpret_cast<const float *>(base + o_pX);
-        D.pY = reinterpret_cast<const float *>(base + o_pY);
-        D.rr = reinterpret_cast<const double *>(base + o_rr);
-        D.mk = reinterpret_cast<const uint32_t *>(base + o_m);
-        D.out = reinterpret_cast<float *>(base + o_o);
-        D.out64 = reinterpret_cast<double *>(base + o_o64);
-        D.n = n;
-        const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+    LDW_HIP(hipMemcpyAsync(base + o_g, g, sz_g, hipMemcpyHostToDevice, c->stream));
+    if (apx) LDW_HIP(hipMemcpyAsync(base + o_g32, g32.data(), sz_g32, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(base + o_pa, pa, sz_p, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(base + o_pb, pb, sz_p, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(base + o_pX, pX, sz_f, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(base + o_pY, pY, sz_f, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(base + o_rr, rr, sz_r, hipMemcpyHostToDevice, c->stream));
+    if (masks) LDW_HIP(hipMemcpyAsync(base + o_m, masks, sz_m, hipMemcpyHostToDevice, c->stream));
+    EpiArgs A;
+    memset(&A, 0, sizeof(A));
+    A.neff = params[5];
+    A.scale = std::ldexp(1.0, -(int)params[0]);
+    A.quirk = LDW_QUIRK_INTENDED;
+    A.E.apx = apx ? 1 : 0;
+    A.E.apx_EG = (float)params[6];
+    A.E.apx_dfac = (float)params[7];
+    A.E.apx_s1 = (float)params[8];
+    A.E.apx_c1 = (float)params[9];
+    A.E.apx_W = params[10];
+    A.E.apx_unit = params[11];
+    A.E.apx_MU = (float)params[18];
+    A.E.scr_shift = apx ? 0 : (int)params[13];
+    A.E.scr_scale = (float)(apx ? params[12] : params[14]);
+    DbgArrays D;
+    D.g = reinterpret_cast<const int64_t *>(base + o_g);
+    D.g32 = reinterpret_cast<const int32_t *>(base + o_g32);
+    D.pa = reinterpret_cast<const int64_t *>(base + o_pa);
+    D.pb = reinterpret_cast<const int64_t *>(base + o_pb);
+    D.pX = reinterpret_cast<const float *>(base + o_pX);
+    D.pY = reinterpret_cast<const float *>(base + o_pY);
+    D.rr = reinterpret_cast<const double *>(base + o_rr);
+    D.mk = reinterpret_cast<const uint32_t *>(base + o_m);
+    D.out = reinterpret_cast<float *>(base + o_o);
+    D.out64 = reinterpret_cast<double *>(base + o_o64);
+    D.n = n;
+    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
 #define LDW_DBG_FULL(K)                                                                                   \
     {                                                                                                     \
         if (na == 1 && nb == 1) hipLaunchKernelGGL((k_dbg_full<1, 1, K>), grid, blk, 0, c->stream, A, D); \
@@ -276,22 +267,17 @@ int ldw_debug_screen_bound(ldw_ctx *c, int kind, int na, int nb, int64_t n, cons
         else if (nb == 1) hipLaunchKernelGGL((k_dbg_full<2, 1, K>), grid, blk, 0, c->stream, A, D);       \
         else hipLaunchKernelGGL((k_dbg_full<2, 2, K>), grid, blk, 0, c->stream, A, D);                    \
     }
-        if (kind == 0) LDW_DBG_FULL(0)
-        else if (kind == 2) LDW_DBG_FULL(2)
-        else if (kind == 4) LDW_DBG_FULL(4)
-        else if (kind == 1) hipLaunchKernelGGL(k_dbg_generic<true>, grid, blk, 0, c->stream, A, D);
-        else hipLaunchKernelGGL(k_dbg_generic<false>, grid, blk, 0, c->stream, A, D);
+    if (kind == 0) LDW_DBG_FULL(0)
+    else if (kind == 2) LDW_DBG_FULL(2)
+    else if (kind == 4) LDW_DBG_FULL(4)
+    else if (kind == 1) hipLaunchKernelGGL(k_dbg_generic<true>, grid, blk, 0, c->stream, A, D);
+    else hipLaunchKernelGGL(k_dbg_generic<false>, grid, blk, 0, c->stream, A, D);
 #undef LDW_DBG_FULL
-        LDW_HIP(hipGetLastError());
-        if (kind == 4) LDW_HIP(hipMemcpyAsync(out64, base + o_o64, sz_o64, hipMemcpyDeviceToHost, c->stream));
-        else LDW_HIP(hipMemcpyAsync(out, base + o_o, sz_o, hipMemcpyDeviceToHost, c->stream));
-        LDW_HIP(hipStreamSynchronize(c->stream));
-        return LDW_OK;
-    };
-    const int rc = body();
-    (void)hipStreamSynchronize(c->stream);
-    B.release();
-    return rc;
+    LDW_HIP(hipGetLastError());
+    if (kind == 4) LDW_HIP(hipMemcpyAsync(out64, base + o_o64, sz_o64, hipMemcpyDeviceToHost, c->stream));
+    else LDW_HIP(hipMemcpyAsync(out, base + o_o, sz_o, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    return LDW_OK;
 }
 
 }  // extern "C"

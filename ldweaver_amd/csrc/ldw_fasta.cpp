@@ -208,7 +208,7 @@ struct FastaScan {
     bool kept = false;
     PinnedPair pin;                    // pinned chunks [rows][Lp]
     DevBuf dchunk[2];                  // their device images
-    hipEvent_t ev[2] = {nullptr, nullptr};   // recorded after the copy of a chunk out of pin[k] (and the kernel behind it)
+    Event ev[2];                       // recorded after the copy of a chunk out of pin[k] (and the kernel behind it)
     bool ev_live[2] = {false, false};
 };
 
@@ -228,18 +228,7 @@ static int64_t free_chunks(FastaScan *f) {
     return n;
 }
 
-void fasta_release(ldw_ctx *c) {
-    auto *f = static_cast<FastaScan *>(c->fasta);
-    if (!f) return;
-    (void)hipStreamSynchronize(c->stream);
-    free_chunks(f);
-    f->counts.release();
-    f->packed.release();
-    for (auto &e : f->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete f;
-    c->fasta = nullptr;
-}
+void fasta_release(ldw_ctx *c) { release_state<FastaScan>(c, c->fasta); }
 
 int64_t fasta_trim(ldw_ctx *c) {
     auto *f = static_cast<FastaScan *>(c->fasta);
@@ -251,8 +240,7 @@ int64_t fasta_trim(ldw_ctx *c) {
 
 // two pinned chunks of `bytes` each and their device images; events once
 static int ensure_chunks(FastaScan *f, size_t bytes) {
-    for (auto &e : f->ev)
-        if (!e) LDW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto &e : f->ev) LDW_HIP(e.ensure(hipEventDisableTiming));
     if (int rc = f->pin.reserve(bytes, "ldw_fasta")) return rc;
     for (int k = 0; k < 2; ++k)
         if (int rc = f->dchunk[k].reserve(bytes)) return rc;
@@ -267,7 +255,7 @@ static int wait_chunk(FastaScan *f, int k) {
 }
 
 static int upload_chunk(ldw_ctx *c, FastaScan *f, int k, int64_t rows) {
-    LDW_HIP(hipMemcpyAsync(f->dchunk[k].p, f->pin.p[k], (size_t)(rows * f->Lp), hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(f->dchunk[k].p, f->pin.b[k], (size_t)(rows * f->Lp), hipMemcpyHostToDevice, c->stream));
     return LDW_OK;
 }
 
@@ -279,7 +267,7 @@ static int chunk_done(ldw_ctx *c, FastaScan *f, int k) {
 
 // the row r of pin[k]: its padding bytes L .. Lp are zeroed (the kernels read whole 16-byte groups)
 static inline char *pin_row(FastaScan *f, int k, int64_t r) {
-    char *row = static_cast<char *>(f->pin.p[k]) + r * f->Lp;
+    char *row = f->pin.b[k].as<char>() + r * f->Lp;
     if (f->Lp > f->L) memset(row + f->L, 0, (size_t)(f->Lp - f->L));
     return row;
 }

@@ -190,9 +190,11 @@ __global__ void k_shared_i32(const int64_t *__restrict__ G, int ld, const int32_
 
 }  // namespace ldw
 
+struct HamBufs {   // the working memory of one call (hamming_impl releases it)
+    ldw::DevBuf info, Hb, T, dig, um, Gh, rl, scnt, dhdw, tmp;
+};
 // tile0 < 0: the whole matrix -> hdw_out (and shared_out); else the strip of 128-sequence row tiles [tile0, tile1) -> counts_out
-static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *shared_out, int tile0, int tile1, int64_t *counts_out) {
-    if (int rc = check_gpu(c)) return rc;
+static int hamming_run(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *shared_out, int tile0, int tile1, int64_t *counts_out, HamBufs &bufs) {
     const auto wall0 = std::chrono::steady_clock::now();
     static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
     double t_last = 0;
@@ -209,31 +211,18 @@ static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sh
     const int Rp = (int)Npad;  // sequences padded to the GEMM tile (Npad is a multiple of 128)
     LDW_REQUIRE(!strip || (tile0 < tile1 && tile1 <= Rp / ldw::TILE), LDW_ERR_ARG, "ldw_hamming_counts: tile range %d..%d outside 0..%d", tile0,
                 tile1, Rp / ldw::TILE);
-    ldw::DevBuf info, Hb, T, dig, um, Gh, rl, scnt, dhdw, tmp;
+    auto &[info, Hb, T, dig, um, Gh, rl, scnt, dhdw, tmp] = bufs;
     int rc = LDW_OK;
-    auto done = [&](int code) {
-        // (the stream has been drained on every path that reaches this with work queued; a failed launch has queued nothing behind it)
-        const bool drained = hipStreamSynchronize(c->stream) == hipSuccess;
-        if (drained) {
-            ldw::DrainedScope quiet;   // no device-wide synchronisation per released block (other contexts of the device may be in the middle of a pass)
-            for (ldw::DevBuf *b : {&info, &Hb, &T, &dig, &um, &Gh, &rl, &scnt, &dhdw, &tmp}) b->release();
-        } else {
-            for (ldw::DevBuf *b : {&info, &Hb, &T, &dig, &um, &Gh, &rl, &scnt, &dhdw, &tmp}) b->release();
-        }
-        return code;
-    };
     hipError_t he;
-#define HC(x) do { he = (x); if (he != hipSuccess) return done(ldw::hip_fail(he, #x, __FILE__, __LINE__)); } while (0)
-    HC(hipEventRecord(c->ev[0], c->stream));
+    LDW_HIP(hipEventRecord(c->ev[0], c->stream));
     // per-SNP state counts -> which state is dropped, which columns exist: on the device (k_ham_ncols, a prefix sum, k_ham_fill); the host learns the column
     // count alone (one 4-byte copy) to size the bit matrices
     LDW_REQUIRE(L < (1ll << 27), LDW_ERR_ARG, "ldw_hamming_weights: too many SNPs");
-    auto done2 = [&](int code) { return done(code); };
-    if ((rc = ldw::launch_state_counts(c))) return done(rc);
+    if ((rc = ldw::launch_state_counts(c))) return rc;
     size_t scan_bytes = 0;
-    HC(ldw::prim_scan_bytes<int32_t>((size_t)L + 1, c->stream, &scan_bytes));
+    LDW_HIP(ldw::prim_scan_bytes<int32_t>((size_t)L + 1, c->stream, &scan_bytes));
     const size_t o_off = ((size_t)(L + 1) * 4 + 255) / 256 * 256, o_scan = 2 * o_off;
-    if ((rc = tmp.reserve(o_scan + scan_bytes + 256))) return done(rc);
+    if ((rc = tmp.reserve(o_scan + scan_bytes + 256))) return rc;
     int32_t *d_ncol = tmp.as<int32_t>(), *d_off = reinterpret_cast<int32_t *>(tmp.as<char>() + o_off);
     hipLaunchKernelGGL(k_ham_ncols, dim3((unsigned)((L + 1 + 255) / 256)), dim3(256), 0, c->stream, c->counts.as<int32_t>(), L, d_ncol);
     he = hipGetLastError();
@@ -241,7 +230,7 @@ static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sh
     int32_t kr32 = 0;
     if (he == hipSuccess) he = hipMemcpyAsync(&kr32, d_off + L, 4, hipMemcpyDeviceToHost, c->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-    if (he != hipSuccess) return done2(ldw::hip_fail(he, "column count of the Hamming GEMM", __FILE__, __LINE__));
+    if (he != hipSuccess) return ldw::hip_fail(he, "column count of the Hamming GEMM", __FILE__, __LINE__);
     lap("column count on the host");
     const int64_t KR = (int64_t)kr32;
     int64_t KWr = (KR + 63) / 64;
@@ -251,45 +240,45 @@ static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sh
         (rc = T.reserve((size_t)Rp * KWr * 8)) || (rc = dig.reserve((size_t)Kpad)) || (rc = um.reserve((size_t)KWr * 8)) ||
         (rc = Gh.reserve((size_t)Rp * Rp * 8)) || (rc = rl.reserve((size_t)Rp * 4)) || (rc = scnt.reserve((size_t)Rp * 4)) ||
         (rc = dhdw.reserve((size_t)N * 8)))
-        return done2(rc);
+        return rc;
     lap("device buffers");
     he = hipMemsetAsync(dig.p, 0, (size_t)Kpad, c->stream);
     if (he == hipSuccess) he = hipMemsetAsync(um.p, 0, (size_t)KWr * 8, c->stream);
-    if (he != hipSuccess) return done2(ldw::hip_fail(he, "zeroing the column weights", __FILE__, __LINE__));
+    if (he != hipSuccess) return ldw::hip_fail(he, "zeroing the column weights", __FILE__, __LINE__);
     if (KR > 0) {
         hipLaunchKernelGGL(k_ham_fill, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, c->stream, c->counts.as<int32_t>(), L, d_off, info.as<int32_t>(), dig.as<int8_t>(),
                            um.as<unsigned long long>());
         he = hipGetLastError();
-        if (he != hipSuccess) return done2(ldw::hip_fail(he, "k_ham_fill", __FILE__, __LINE__));
+        if (he != hipSuccess) return ldw::hip_fail(he, "k_ham_fill", __FILE__, __LINE__);
     }
     std::vector<int32_t> rowlist((size_t)Rp);
     for (int i = 0; i < Rp; ++i) rowlist[i] = i;
-    HC(hipMemcpyAsync(rl.p, rowlist.data(), (size_t)Rp * 4, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(rl.p, rowlist.data(), (size_t)Rp * 4, hipMemcpyHostToDevice, c->stream));
     lap("uploads queued");
-    HC(hipEventRecord(c->ev[4], c->stream));   // (r06: the kernels in front of the GEMM bracketed on their own — ev[0] also sees the host work above)
+    LDW_HIP(hipEventRecord(c->ev[4], c->stream));   // (r06: the kernels in front of the GEMM bracketed on their own — ev[0] also sees the host work above)
     if (KR > 0) {
         if (KR * KW >= ((int64_t)1 << 39)) {
             ldw::set_error("ldw_hamming_weights: %lld columns x %lld words exceed the launch grid", (long long)KR, (long long)KW);
-            return done(LDW_ERR_SIZE);
+            return LDW_ERR_SIZE;
         }
         hipLaunchKernelGGL(k_hamming_cols, dim3((unsigned)((KR * KW + 255) / 256)), dim3(256), 0, c->stream, c->states.as<uint8_t>(), Npad, info.as<int32_t>(),
                            KW, KR, Hb.as<uint64_t>());
-        HC(hipGetLastError());
+        LDW_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_bits_transpose, dim3((unsigned)((KWr + 3) / 4), (unsigned)KW), dim3(256), 0, c->stream, Hb.as<uint64_t>(), KR, KW,
                        T.as<uint64_t>(), KWr);
-    HC(hipGetLastError());
+    LDW_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_seq_minor_count, dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, c->stream, T.as<uint64_t>(), um.as<uint64_t>(),
                        (int64_t)Rp, KWr, scnt.as<int32_t>());
-    HC(hipGetLastError());
-    HC(hipEventRecord(c->ev[2], c->stream));
+    LDW_HIP(hipGetLastError());
+    LDW_HIP(hipEventRecord(c->ev[2], c->stream));
     if ((rc = launch_gemm_bits(c, T.as<uint64_t>(), KWr, rl.as<int32_t>(), Rp, rl.as<int32_t>(), Rp, Gh.as<int64_t>(), 1, dig.as<int8_t>(), 1,
                                nullptr, strip ? tile0 : 0, strip ? tile1 : -1)))
-        return done(rc);
-    HC(hipEventRecord(c->ev[1], c->stream));
+        return rc;
+    LDW_HIP(hipEventRecord(c->ev[1], c->stream));
     if (strip) {
         ldw::DevBuf dcnt;
-        if ((rc = dcnt.reserve((size_t)N * 4))) return done(rc);
+        if ((rc = dcnt.reserve((size_t)N * 4))) return rc;
         const int64_t t0 = (int64_t)tile0 * ldw::TILE, t1 = std::min<int64_t>((int64_t)tile1 * ldw::TILE, N);
         std::vector<int32_t> hcnt((size_t)N, 0);
         he = hipMemsetAsync(dcnt.p, 0, (size_t)N * 4, c->stream);
@@ -300,35 +289,33 @@ static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sh
         }
         if (he == hipSuccess) he = hipMemcpyAsync(hcnt.data(), dcnt.p, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream);
         if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-        dcnt.release();
-        if (he != hipSuccess) return done(ldw::hip_fail(he, "strip counts", __FILE__, __LINE__));
+        if (he != hipSuccess) return ldw::hip_fail(he, "strip counts", __FILE__, __LINE__);
         for (int64_t i = 0; i < N; ++i) counts_out[i] = hcnt[(size_t)i];
-        return done(LDW_OK);
+        return LDW_OK;
     }
     hipLaunchKernelGGL(k_hdw, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, Gh.as<int64_t>(), Rp, scnt.as<int32_t>(), N, L,
                        (int)thresh, dhdw.as<double>());
-    HC(hipGetLastError());
-    HC(hipEventRecord(c->ev[3], c->stream));
-    HC(hipMemcpyAsync(hdw_out, dhdw.p, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipGetLastError());
+    LDW_HIP(hipEventRecord(c->ev[3], c->stream));
+    LDW_HIP(hipMemcpyAsync(hdw_out, dhdw.p, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
     if (shared_out) {
         ldw::DevBuf s32;
-        if ((rc = s32.reserve((size_t)N * N * 4))) return done(rc);
+        if ((rc = s32.reserve((size_t)N * N * 4))) return rc;
         dim3 g2((unsigned)((N + 255) / 256), (unsigned)N);
         hipLaunchKernelGGL(k_shared_i32, g2, dim3(256), 0, c->stream, Gh.as<int64_t>(), Rp, scnt.as<int32_t>(), N, L, s32.as<int32_t>());
         he = hipMemcpyAsync(shared_out, s32.p, (size_t)N * N * 4, hipMemcpyDeviceToHost, c->stream);
         if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-        s32.release();
-        if (he != hipSuccess) return done(ldw::hip_fail(he, "shared copy", __FILE__, __LINE__));
+        if (he != hipSuccess) return ldw::hip_fail(he, "shared copy", __FILE__, __LINE__);
     }
     lap("kernels queued");
-    HC(hipStreamSynchronize(c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
     lap("stream drained");
     float t = 0, tg = 0;
-    HC(hipEventElapsedTime(&t, c->ev[0], c->ev[1]));
-    HC(hipEventElapsedTime(&tg, c->ev[2], c->ev[1]));
+    LDW_HIP(hipEventElapsedTime(&t, c->ev[0], c->ev[1]));
+    LDW_HIP(hipEventElapsedTime(&tg, c->ev[2], c->ev[1]));
     float tp = 0, tpre = 0;
-    HC(hipEventElapsedTime(&tp, c->ev[1], c->ev[3]));
-    HC(hipEventElapsedTime(&tpre, c->ev[4], c->ev[2]));
+    LDW_HIP(hipEventElapsedTime(&tp, c->ev[1], c->ev[3]));
+    LDW_HIP(hipEventElapsedTime(&tpre, c->ev[4], c->ev[2]));
     c->last_ms[0] = tg;          // the GEMM alone
     c->last_ms[1] = tp;          // r06: the N x N neighbour count (k_hdw)
     c->last_ms[2] = 0;
@@ -344,8 +331,20 @@ static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sh
     c->ham_stat[5] = (double)KR * (double)Npad + 2.0 * (double)KR * (double)KW * 8.0 + 2.0 * (double)Rp * (double)KWr * 8.0;
     c->ham_stat[6] = (double)N * (double)N * 8.0 + (double)N * 8.0;
     c->ham_stat[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-#undef HC
-    return done(LDW_OK);
+    return LDW_OK;
+}
+
+static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *shared_out, int tile0, int tile1, int64_t *counts_out) {
+    if (int rc = check_gpu(c)) return rc;
+    HamBufs bufs;
+    const int rc = hamming_run(c, thresh, hdw_out, shared_out, tile0, tile1, counts_out, bufs);
+    // this context's stream alone touched the blocks: once it is idle they go without a device-wide synchronisation each (other contexts of the
+    // device may be in the middle of a pass).  A failed launch has queued nothing behind it.
+    if (hipStreamSynchronize(c->stream) == hipSuccess) {
+        ldw::DrainedScope quiet;
+        bufs = HamBufs();
+    }
+    return rc;
 }
 
 extern "C" int ldw_hamming_weights(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *shared_out) {

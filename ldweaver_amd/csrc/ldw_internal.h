@@ -12,6 +12,7 @@
 
 #include "../../include/ldweaver_amd.h"
 #include "../../include/ldweaver_amd_debug.h"
+#include "ldw_own.h"   // DevBuf, PinnedBuf, PinnedPair, Event, Stream: what a context holds on the GPU, each freed by its destructor
 
 // Pipeline slots of the all-pairs loop: the block-wide kernels (GEMM stream) may run LDW_NSLOT - 1 blocks ahead of the block whose
 // lists the main stream is evaluating; every per-block buffer exists once per slot (block b uses slot b % LDW_NSLOT).
@@ -38,24 +39,6 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
         }                              \
     } while (0)
 
-// grow-only device buffer
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes);  // returns LDW_OK / error; contents NOT preserved on growth
-    int reserve_keep(size_t bytes, size_t used, hipStream_t s);  // preserves the first `used` bytes
-    void release();
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-// two pinned host buffers of one size, grow-only: the double buffer of a streaming stage (FASTA feeder, alignment writer, text-file pass)
-struct PinnedPair {
-    void *p[2] = {nullptr, nullptr};
-    size_t cap = 0;                               // bytes of each
-    int reserve(size_t bytes, const char *who);   // contents NOT preserved on growth; LDW_ERR_HIP "<who>: hipHostMalloc of <bytes> bytes failed" leaves no buffer
-    int64_t release();                            // bytes freed; nothing may still be copying to or from the buffers
-};
-
 constexpr int TILE = 128;     // GEMM block tile (rows on both sides)
 constexpr int KSTEP = 128;    // bytes of K (sequences) per pipeline stage
 constexpr int NBINS = 4096;   // level-1 histogram bins of the lr quantile search
@@ -72,11 +55,15 @@ struct BlockTrace {
 
 }  // namespace ldw
 
+// Every GPU resource below is an owning member (ldw_own.h): `delete` gives all of it back, in reverse order of declaration, so the streams
+// come first and go last.  ldw_ctx_destroy drains them before it deletes.
 struct ldw_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = true;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ldw::Stream stream;              // the main stream: the library's own, or the caller's (ldw_ctx_set_stream: adopted, never destroyed here)
+    ldw::Stream copy_stream, gemm_stream;   // pipelined block staging (ensure_streams): host prep of block i+1 overlaps the GPU work of block i
+    ldw::Stream lr_st;               // the streaming lr_links.tsv writer's (ensure_streams)
+    bool streams_ready = false;      // ensure_streams has made everything it makes
+    ldw::Event ev[6];
     double last_ms[4] = {0, 0, 0, 0};
     int engine = LDW_ENGINE_MFMA;
 
@@ -240,15 +227,12 @@ struct ldw_ctx {
 
     // ---- short-range model and ARACNE on the device-resident sr table (ldw_srp.hip) ----
     void *lr_stream = nullptr;   // r05: lr_links.tsv appended while the pass runs (ldw_tsv.cpp: LrStream), if ldw_lr_stream_begin opened one
-    // its device-side resources, made once with the context's other streams (hipStreamCreate is a 12-ms call: not inside a job's pass)
-    hipStream_t lr_st = nullptr;
-    hipEvent_t lr_ev[64] = {};
-    int64_t *lr_counts = nullptr;   // pinned [64]
-    void *lr_pin = nullptr;         // pinned staging of a batch of rows (a, b, MI); grows on demand
-    size_t lr_pin_cap = 0;
+    // its device-side resources (with lr_st), made once with the context's other streams (hipStreamCreate is a 12-ms call: not inside a job's pass)
+    ldw::Event lr_ev[64];
+    ldw::PinnedBuf lr_counts;    // int64 [64]
+    ldw::PinnedBuf lr_pin;       // pinned staging of a batch of rows (a, b, MI); grows on demand
     void *tsv_async = nullptr;   // r04: the asynchronous link-table writer, if one is running (ldw_tsv.cpp: TsvAsync)
-    void *pin_fetch = nullptr;   // r04: pinned host arena the tsv writer fetches a link table into (see ldw_write_links_tsv)
-    size_t pin_fetch_cap = 0;
+    ldw::PinnedBuf pin_fetch;    // r04: pinned host arena the tsv writer fetches a link table into (see ldw_write_links_tsv)
     ldw::DevBuf srm_pack, srm_key, srm_pack2, srm_key2, srm_pay, srm_pay2, srm_off, srm_q, srm_n, srm_md, srm_part, srm_shape, srm_cnt, srm_tmp;
     ldw::DevBuf srd_lower, srd_cur, srd_out, srd_seg;   // r05, the model over ranks (ldw_sr_tail_extract ...): per-group bounds, cursors, the extracted rows, block segments
     double ham_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ldw_hamming_stats: columns, padded K, stage times and algorithmic bytes of the last ldw_hamming_weights
@@ -262,25 +246,23 @@ struct ldw_ctx {
     int srm_S = 0, srm_nclust = 0;   // geometry of the last ldw_sr_len_quantiles call
     double srm_sr_dist = 0;
 
-    // ---- pipelined block staging: host prep of block i+1 overlaps the GPU work of block i ----
-    hipStream_t copy_stream = nullptr, gemm_stream = nullptr;
-    hipEvent_t ev_gemm[LDW_NSLOT] = {};
+    // ---- pipelined block staging ----
+    ldw::Event ev_gemm[LDW_NSLOT];
     bool overlap = true;                 // GEMM of block b+1 on its own stream beside the epilogue/selection of block b
-    void *pin[LDW_NSLOT + 1] = {};   // pinned host staging, one packed buffer per slot (+ 1: a span segment that is redone on its own)
-    size_t pin_cap[LDW_NSLOT + 1] = {};
+    ldw::PinnedBuf pin[LDW_NSLOT + 1];   // pinned host staging, one packed buffer per slot (+ 1: a span segment that is redone on its own)
     ldw::DevBuf dstage[LDW_NSLOT + 1];               // device image of the packed buffer
-    hipEvent_t ev_up[LDW_NSLOT] = {}, ev_done[LDW_NSLOT] = {};
+    ldw::Event ev_up[LDW_NSLOT], ev_done[LDW_NSLOT];
     bool done_recorded[LDW_NSLOT] = {};
     bool up_recorded[LDW_NSLOT] = {};    // ev_up[slot] has been recorded at least once
-    void *pin_pick[LDW_NSLOT] = {};   // pinned landing zone of the per-block PickOut, one per slot
-    hipEvent_t ev_pick[LDW_NSLOT] = {};
-    hipEvent_t ev_probe[2] = {};      // one per cold-start probe of a pass: the calling thread waits for the probe it needs, not for the stream
-    void *pin_lrc = nullptr;             // pinned copy of the running long-range row count
-    hipEvent_t ev_lrc = nullptr;
+    ldw::PinnedBuf pin_pick[LDW_NSLOT];   // pinned landing zone of the per-block PickOut, one per slot
+    ldw::Event ev_pick[LDW_NSLOT];
+    ldw::Event ev_probe[2];           // one per cold-start probe of a pass: the calling thread waits for the probe it needs, not for the stream
+    ldw::PinnedBuf pin_lrc;              // pinned copy of the running long-range row count
+    ldw::Event ev_lrc;
     bool lrc_recorded = false;
     bool spec_seen[2] = {false, false};  // a block of this kind (off-diagonal, diagonal) has set its own guess
     bool spec_probed[2] = {false, false};   // the kind's current guess came from a cold-start probe of the kind itself
-    std::vector<hipEvent_t> ev_pool;     // 4 timing events per block
+    std::vector<ldw::Event> ev_pool;     // 4 timing events per block
     int spec_hist[2][6] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};   // the last true buckets per kind (adaptive margin of the guess)
     int spec_hist_n[2] = {0, 0};
     bool spec_small[2] = {false, false};   // the kind's blocks keep few rows (< 5000): noisier thresholds, wider margins
@@ -293,7 +275,7 @@ struct ldw_ctx {
     // ldw_ctx_reserve (r04): what a job's FIRST pass otherwise pays inside its timed loop — two hipStreamCreate (12 ms each on this box), the
     // pinned staging buffers (hipHostMalloc: 0.2 ms per MB), the lazy load of the code objects of the pass's kernels — done by a side thread
     // while the caller uploads the alignment and runs the Hamming GEMM.  Joined by every entry point that uses what it prepares.
-    std::thread *prep_thread = nullptr, *prep_thread2 = nullptr;   // started by ldw_ctx_create (streams, code objects) / ldw_ctx_reserve (staging buffers)
+    std::thread prep_thread, prep_thread2;   // started by ldw_ctx_create (streams, code objects) / ldw_ctx_reserve (staging buffers)
     int prep_rc = 0, prep_rc2 = 0;
     std::string prep_err, prep_err2;
 };
@@ -337,6 +319,13 @@ void warm_post();
 // ldw_post.hip: the graph node of every SNP for consumers that work on positions (LD map, ARACNE): *slot = null and *n_nodes = L when POS
 // ascends strictly, else the device array ctx->pos_ord.slot (SNPs sharing a position share a node) and the number of distinct positions
 int pos_slots(ldw_ctx *ctx, const int32_t **slot, int64_t *n_nodes);
+// a sub-state of the context (ctx->fasta, out, tsv, grep: a struct of owning members behind a void *) goes, once the main stream is idle
+template <class T> void release_state(ldw_ctx *ctx, void *&state) {
+    if (!state) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    delete static_cast<T *>(state);
+    state = nullptr;
+}
 void out_release(ldw_ctx *ctx);      // ldw_out.hip: the alignment writer's staging (ldw_ctx_destroy)
 int64_t out_trim(ldw_ctx *ctx);      // ... its pinned buffers and device image only (ldw_host_trim); bytes released
 }  // namespace ldw

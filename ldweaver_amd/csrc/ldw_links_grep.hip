@@ -208,8 +208,8 @@ __global__ void k_grep_init(GrepResult *res) {
 
 struct GrepState {
     DevBuf tables, work;                 // the needle tables and the result word; a chunk's records and mask words
-    GrepResult *pin_res = nullptr;       // pinned twin of the result word
-    hipEvent_t ev[2] = {};               // before k_tsv_starts, after the search kernel
+    PinnedBuf pin_res;                   // GrepResult: pinned twin of the result word
+    Event ev[2];                         // before k_tsv_starts, after the search kernel
     // the last result (host)
     int nw = 0;
     std::vector<int64_t> row;
@@ -232,18 +232,7 @@ const char *const GREP_NAMES[GREP_NUM + GREP_STR] = {"pos1", "pos2", "len", "ARA
 }  // namespace
 
 namespace ldw {
-void grep_release(ldw_ctx *c) {
-    auto *g = static_cast<GrepState *>(c->grep);
-    if (!g) return;
-    (void)hipStreamSynchronize(c->stream);
-    g->tables.release();
-    g->work.release();
-    if (g->pin_res) (void)hipHostFree(g->pin_res);
-    for (auto &e : g->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete g;
-    c->grep = nullptr;
-}
+void grep_release(ldw_ctx *c) { release_state<GrepState>(c, c->grep); }
 
 int64_t grep_trim(ldw_ctx *c) {
     auto *g = static_cast<GrepState *>(c->grep);
@@ -296,9 +285,8 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
     const int nw = (n_needles + 63) / 64;
     g->nw = nw;
     const auto t_begin = std::chrono::steady_clock::now();
-    for (auto &e : g->ev)
-        if (!e) LDW_HIP(hipEventCreate(&e));
-    if (!g->pin_res) LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->pin_res), sizeof(GrepResult), hipHostMallocDefault));
+    for (auto &e : g->ev) LDW_HIP(e.ensure());
+    if (int rc = g->pin_res.reserve(sizeof(GrepResult), "ldw_links_grep")) return rc;
 
     // the needles by first byte (a stable order inside a bucket: the caller's)
     const int32_t blob_bytes = needle_off[n_needles];
@@ -383,14 +371,14 @@ int ldw_links_grep(ldw_ctx *c, const char *path, const uint8_t *needles, const i
         if (searched) {
             LDW_HIP(hipEventSynchronize(g->ev[1]));
             if (hipEventElapsedTime(&fms, g->ev[0], g->ev[1]) == hipSuccess) g->ms[4] += fms;
-            GrepResult r = *g->pin_res;
+            GrepResult r = *g->pin_res.as<GrepResult>();
             if (r.bad == ~0ull && r.kept > rec_cap) {   // more rows kept than the first guess holds: once more with room for every row
                 LDW_HIP(hipEventRecord(g->ev[0], c->stream));
                 if (int rc2 = search(cut, skip, nrows, nrows)) return rc2;
                 LDW_HIP(hipEventRecord(g->ev[1], c->stream));
                 LDW_HIP(hipEventSynchronize(g->ev[1]));
                 if (hipEventElapsedTime(&fms, g->ev[0], g->ev[1]) == hipSuccess) g->ms[4] += fms;
-                r = *g->pin_res;
+                r = *g->pin_res.as<GrepResult>();
             }
             if (r.bad != ~0ull) {
                 bad_row = rows_seen + (int64_t)(r.bad >> 16);

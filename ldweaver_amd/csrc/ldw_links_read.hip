@@ -231,16 +231,16 @@ struct TsvState {
     // what a pass over a text file borrows (TsvPass)
     PinnedPair pin;                      // pinned chunk buffers: TSV_FRONT '\n', the data, TSV_TAIL '\n'
     DevBuf img, cnt, off, starts, scan_tmp;
-    uint32_t *pin_rows = nullptr;        // pinned: the line count of the chunk in flight
-    hipEvent_t pass_ev[3] = {};          // before / after a chunk's copy, after its line count
+    PinnedBuf pin_rows;                  // uint32: the line count of the chunk in flight
+    Event pass_ev[3];                    // before / after a chunk's copy, after its line count
     // the reader's own
-    TsvResult *pin_res = nullptr;        // pinned twin of res, one per chunk buffer
+    PinnedBuf pin_res;                   // TsvResult [2]: pinned twin of res, one per chunk buffer
     DevBuf slow, res, patch;
     DevBuf cols;                         // double [ncols][stride], column-major: the parsed table
     int64_t rows = 0, stride = 0;
     int ncols = 0;
     int64_t grows = 0;                   // times the columns were moved to a larger buffer (since the context was made)
-    hipEvent_t ev[2][2] = {};            // per chunk buffer: before / after the parse kernel
+    Event ev[2][2];                      // per chunk buffer: before / after the parse kernel
     std::string path;                    // of the last read, for the line numbers of ldw_links_load's refusals
     int variant = 0;                     // 0: rows parsed from cached global loads, 1: from an LDS-staged tile
     double ms[8] = {};                   // last read: total, read (host), copy, line kernels, parse kernel, slow-cell patch, chunks, bytes
@@ -267,8 +267,7 @@ int grow_columns(ldw_ctx *c, TsvState *t, int64_t rows) {
         LDW_HIP(hipMemcpy2DAsync(nb.p, (size_t)stride * 8, t->cols.p, (size_t)t->stride * 8, (size_t)t->rows * 8, (size_t)t->ncols, hipMemcpyDeviceToDevice, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
     }
-    t->cols.release();
-    t->cols = nb;
+    t->cols = std::move(nb);
     t->stride = stride;
     ++t->grows;
     return LDW_OK;
@@ -277,32 +276,15 @@ int grow_columns(ldw_ctx *c, TsvState *t, int64_t rows) {
 }  // namespace
 
 namespace ldw {
-void tsv_release(ldw_ctx *c) {
-    auto *t = static_cast<TsvState *>(c->tsv);
-    if (!t) return;
-    (void)hipStreamSynchronize(c->stream);
-    t->pin.release();
-    if (t->pin_rows) (void)hipHostFree(t->pin_rows);
-    if (t->pin_res) (void)hipHostFree(t->pin_res);
-    for (DevBuf *b : {&t->img, &t->cnt, &t->off, &t->starts, &t->slow, &t->res, &t->patch, &t->scan_tmp, &t->cols, &t->keep, &t->koff, &t->idx1, &t->idx2, &t->bad})
-        b->release();
-    for (auto &e : t->pass_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &row : t->ev)
-        for (auto &e : row)
-            if (e) (void)hipEventDestroy(e);
-    delete t;
-    c->tsv = nullptr;
-}
+void tsv_release(ldw_ctx *c) { release_state<TsvState>(c, c->tsv); }
 
 // ---- TsvPass, the stream half (the host half: ldw_links_read_host.cpp) --------------------------------------------------------------------------
 
 int TsvPass::attach(ldw_ctx *c) {
     ctx_ = c;
     TsvState *t = tsv_state(c);
-    for (auto &e : t->pass_ev)
-        if (!e) LDW_HIP(hipEventCreate(&e));
-    if (!t->pin_rows) LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->pin_rows), 4, hipHostMallocDefault));
+    for (auto &e : t->pass_ev) LDW_HIP(e.ensure());
+    if (int rc = t->pin_rows.reserve(4, "ldw_tsv_read")) return rc;
     const size_t buf_bytes = (size_t)buffer_bytes();
     if (int rc = t->pin.reserve(buf_bytes, "ldw_tsv_read")) return rc;   // (the pair is the reader's, whoever asks)
     if (int rc = t->img.reserve(buf_bytes)) return rc;
@@ -313,7 +295,7 @@ int TsvPass::attach(ldw_ctx *c) {
     LDW_HIP(prim_scan_bytes<uint32_t>((size_t)max_blocks + 1, c->stream, &scan_bytes));
     if (int rc = t->scan_tmp.reserve(scan_bytes)) return rc;
     d_text_ = t->img.as<uint8_t>() + TSV_FRONT;
-    use(t->pin.p[0], t->pin.p[1]);
+    use(t->pin.b[0], t->pin.b[1]);
     return LDW_OK;
 }
 
@@ -341,7 +323,7 @@ int TsvPass::wait(uint32_t *rows) {
     float f = 0;
     if (hipEventElapsedTime(&f, t->pass_ev[0], t->pass_ev[1]) == hipSuccess) copy_ms += f;
     if (hipEventElapsedTime(&f, t->pass_ev[1], t->pass_ev[2]) == hipSuccess) line_ms += f;
-    *rows = *t->pin_rows;
+    *rows = *t->pin_rows.as<uint32_t>();
     return LDW_OK;
 }
 
@@ -387,9 +369,8 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
     memset(t->ms, 0, sizeof(t->ms));
     const auto t_begin = std::chrono::steady_clock::now();
     for (auto &row : t->ev)
-        for (auto &e : row)
-            if (!e) LDW_HIP(hipEventCreate(&e));
-    if (!t->pin_res) LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->pin_res), 2 * sizeof(TsvResult), hipHostMallocDefault));
+        for (auto &e : row) LDW_HIP(e.ensure());
+    if (int rc = t->pin_res.reserve(2 * sizeof(TsvResult), "ldw_tsv_read")) return rc;
     if (int rc = t->res.reserve(sizeof(TsvResult))) return rc;
     if (int rc = pass.attach(c)) return rc;
 
@@ -410,7 +391,7 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
         k.queued = false;
         hipError_t e = hipEventSynchronize(t->ev[b][1]);
         if (e != hipSuccess) return hip_fail(e, "ldw_tsv_read: chunk", __FILE__, __LINE__);
-        const TsvResult r = t->pin_res[b];
+        const TsvResult r = t->pin_res.as<TsvResult>()[b];
         float f = 0;
         if (hipEventElapsedTime(&f, t->ev[b][0], t->ev[b][1]) == hipSuccess) t->ms[4] += f;
         if (r.bad != ~0ull) {
@@ -461,7 +442,7 @@ int ldw_tsv_read(ldw_ctx *c, const char *path, int sep, int32_t ncols, int64_t c
         else
             LDW_LAUNCH(k_tsv_parse<false>, grid, dim3(TSV_BLOCK), 0, c->stream, pass.d_text(), (uint32_t)pass.cut(), d_starts, nrows, (int)ncols, (uint8_t)sep,
                        t->cols.as<double>(), t->stride, t->rows, d_res, t->slow.as<uint2>());
-        LDW_HIP(hipMemcpyAsync(&t->pin_res[b], d_res, sizeof(TsvResult), hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipMemcpyAsync(t->pin_res.as<TsvResult>() + b, d_res, sizeof(TsvResult), hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipEventRecord(t->ev[b][1], c->stream));
         ch[b].row0 = t->rows;
         ch[b].queued = true;

@@ -63,34 +63,33 @@ namespace {
 }  // namespace
 
 namespace ldw {
+// Every creation is an idempotent ensure, and "ready" is set after the last one: a call that failed half-way is simply repeated.
 int ensure_streams(ldw_ctx *c) {
-    if (!c->copy_stream) {
-        LDW_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        for (int k = 0; k < LDW_NSLOT; ++k) {
-            LDW_HIP(hipEventCreateWithFlags(&c->ev_up[k], hipEventDisableTiming));
-            LDW_HIP(hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming));
-        }
-        for (int k = 0; k < LDW_NSLOT; ++k) {
-            LDW_HIP(hipEventCreateWithFlags(&c->ev_pick[k], hipEventDisableTiming));
-            LDW_HIP(hipHostMalloc(&c->pin_pick[k], (size_t)LDW_SPAN_MAX * PICK_STRIDE + 64, hipHostMallocDefault));
-        }
-        LDW_HIP(hipEventCreateWithFlags(&c->ev_lrc, hipEventDisableTiming));
-        for (auto &e : c->ev_probe) LDW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        LDW_HIP(hipHostMalloc(&c->pin_lrc, 64, hipHostMallocDefault));
-        {   // the block-wide kernels (GEMM, screens) fill the chip; the tail of the previous block on the main stream is a chain of
-            // small latency-bound kernels that should be dispatched as soon as they are ready: lowest priority for this stream
-            int lo_p = 0, hi_p = 0;
-            LDW_HIP(hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
-            LDW_HIP(hipStreamCreateWithPriority(&c->gemm_stream, hipStreamNonBlocking, lo_p));
-        }
-        for (int k = 0; k < LDW_NSLOT; ++k) LDW_HIP(hipEventCreateWithFlags(&c->ev_gemm[k], hipEventDisableTiming));
-        // r05: what the streaming lr_links.tsv writer needs on the device side (ldw_lr_stream_begin): made here, not inside a job
-        LDW_HIP(hipStreamCreateWithFlags(&c->lr_st, hipStreamNonBlocking));
-        for (auto &e : c->lr_ev) LDW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        LDW_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->lr_counts), sizeof(int64_t) * 64, hipHostMallocDefault));
-        c->lr_pin_cap = (size_t)32 << 20;   // (2 M rows: a batch of eight items of a C4 pass is 0.2-0.6 M)
-        LDW_HIP(hipHostMalloc(&c->lr_pin, c->lr_pin_cap, hipHostMallocDefault));
+    if (c->streams_ready) return LDW_OK;
+    const unsigned quiet = hipEventDisableTiming;
+    LDW_HIP(c->copy_stream.ensure(hipStreamNonBlocking));
+    for (int k = 0; k < LDW_NSLOT; ++k) {
+        LDW_HIP(c->ev_up[k].ensure(quiet));
+        LDW_HIP(c->ev_done[k].ensure(quiet));
+        LDW_HIP(c->ev_pick[k].ensure(quiet));
+        LDW_HIP(c->ev_gemm[k].ensure(quiet));
+        if (int rc = c->pin_pick[k].reserve((size_t)LDW_SPAN_MAX * PICK_STRIDE + 64, "ensure_streams")) return rc;
     }
+    LDW_HIP(c->ev_lrc.ensure(quiet));
+    for (auto &e : c->ev_probe) LDW_HIP(e.ensure(quiet));
+    if (int rc = c->pin_lrc.reserve(64, "ensure_streams")) return rc;
+    {   // the block-wide kernels (GEMM, screens) fill the chip; the tail of the previous block on the main stream is a chain of
+        // small latency-bound kernels that should be dispatched as soon as they are ready: lowest priority for this stream
+        int lo_p = 0, hi_p = 0;
+        LDW_HIP(hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
+        LDW_HIP(c->gemm_stream.ensure(hipStreamNonBlocking, lo_p));
+    }
+    // r05: what the streaming lr_links.tsv writer needs on the device side (ldw_lr_stream_begin): made here, not inside a job
+    LDW_HIP(c->lr_st.ensure(hipStreamNonBlocking));
+    for (auto &e : c->lr_ev) LDW_HIP(e.ensure(quiet));
+    if (int rc = c->lr_counts.reserve(sizeof(int64_t) * 64, "ensure_streams")) return rc;
+    if (int rc = c->lr_pin.reserve((size_t)32 << 20, "ensure_streams")) return rc;   // (2 M rows: a batch of eight items of a C4 pass is 0.2-0.6 M)
+    c->streams_ready = true;
     return LDW_OK;
 }
 
@@ -98,11 +97,8 @@ int join_prepare(ldw_ctx *c) {
     if (!c) return LDW_OK;
     int rc = LDW_OK;
     for (int which = 0; which < 2; ++which) {
-        std::thread *&t = which == 0 ? c->prep_thread : c->prep_thread2;
-        if (!t) continue;
-        if (t->joinable()) t->join();
-        delete t;
-        t = nullptr;
+        std::thread &t = which == 0 ? c->prep_thread : c->prep_thread2;
+        if (t.joinable()) t.join();
         int &trc = which == 0 ? c->prep_rc : c->prep_rc2;
         if (trc != LDW_OK && rc == LDW_OK) {
             rc = trc;
@@ -183,14 +179,9 @@ int ldw_joint_tables(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, i
     std::vector<int8_t> ones((size_t)c->Npad, 1);
     ldw::DevBuf d_ones, d_out, d_cmarg;
     int rc = LDW_OK;
-    auto cleanup = [&]() { d_ones.release(); d_out.release(); d_cmarg.release(); };
-    if ((rc = d_ones.reserve((size_t)c->Npad)) || (rc = d_out.reserve((size_t)CH * 25 * 8)) ||
-        (rc = d_cmarg.reserve((size_t)c->L * 40))) {
-        cleanup();
-        return rc;
-    }
+    if ((rc = d_ones.reserve((size_t)c->Npad)) || (rc = d_out.reserve((size_t)CH * 25 * 8)) || (rc = d_cmarg.reserve((size_t)c->L * 40))) return rc;
     hipError_t he = hipMemcpyAsync(d_ones.p, ones.data(), ones.size(), hipMemcpyHostToDevice, c->stream);
-    if (he != hipSuccess) { cleanup(); return ldw::hip_fail(he, "memcpy ones", __FILE__, __LINE__); }
+    if (he != hipSuccess) return ldw::hip_fail(he, "memcpy ones", __FILE__, __LINE__);
     hipLaunchKernelGGL(k_slot_counts, dim3((unsigned)((c->L + 255) / 256)), dim3(256), 0, c->stream,
                        c->counts.as<int32_t>(), c->slot_meta.as<uint32_t>(), c->L, d_cmarg.as<int64_t>());
     for (int64_t p0 = 0; p0 < np && rc == LDW_OK; p0 += CH) {
@@ -221,7 +212,6 @@ int ldw_joint_tables(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, i
             if (he != hipSuccess) rc = ldw::hip_fail(he, "joint tables copy", __FILE__, __LINE__);
         }
     }
-    cleanup();
     return rc;
 }
 
@@ -247,9 +237,9 @@ int ldw_links_begin(ldw_ctx *c, int64_t nblocks_capacity) {
     LDW_HIP(hipEventRecord(c->ev_up[0], c->stream));
     LDW_HIP(hipStreamWaitEvent(c->gemm_stream, c->ev_up[0], 0));
     while ((int64_t)c->ev_pool.size() < nblocks_capacity * EVB) {
-        hipEvent_t e;
-        LDW_HIP(hipEventCreate(&e));
-        c->ev_pool.push_back(e);
+        ldw::Event e;
+        LDW_HIP(e.ensure());
+        c->ev_pool.push_back(std::move(e));
     }
     for (int k = 0; k < LDW_NSLOT; ++k) c->done_recorded[k] = false;
     c->early_sr = false;
@@ -328,7 +318,7 @@ int ldw_links_end(ldw_ctx *c) {
         c->stats[b].n_sr = si[b * 3 + 2];
         c->stats[b].disc_thresh = sd[b];
         float t01 = 0, t12 = 0, t23 = 0;
-        hipEvent_t *ev = &c->ev_pool[(size_t)b * EVB];
+        const hipEvent_t *ev = handles(&c->ev_pool[(size_t)b * EVB]);
         if (b < (int64_t)c->ev_valid.size() && !c->ev_valid[(size_t)b]) continue;   // a later segment of a span: its time is in the span's first block
         LDW_HIP(hipEventElapsedTime(&t01, ev[0], ev[1]));
         LDW_HIP(hipEventElapsedTime(&t12, ev[c->engine == LDW_ENGINE_MFMA ? 4 : 1], ev[2]));
@@ -671,7 +661,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
             const int64_t npairs = diag ? (int64_t)fi.size() * ((int64_t)fi.size() - 1) / 2 : (int64_t)fi.size() * (int64_t)ti.size();
             if (npairs < PROBE_MIN_PAIRS) continue;
             // (a staging buffer that has to grow for the second sample is reallocated: the first sample's upload must have left it)
-            if (n_probe > 0 && c->pin_cap[LDW_NSLOT] < pin_base + 2 * probes[0].hb.total + 65536) LDW_HIP(hipStreamSynchronize(c->stream));
+            if (n_probe > 0 && c->pin[LDW_NSLOT].cap < pin_base + 2 * probes[0].hb.total + 65536) LDW_HIP(hipStreamSynchronize(c->stream));
             if (int rc = probe_enqueue(c, fi.data(), (int64_t)fi.size(), ti.data(), (int64_t)ti.size(), p, sl, kind, n_probe, pin_base, probes[n_probe])) return rc;
             pin_base = (pin_base + probes[n_probe].hb.total + 255) / 256 * 256;
             ++n_probe;
@@ -852,17 +842,7 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
     // made this 12 ms for C4's 55 blocks), and the block pairs whose ranges lie further apart than sr_dist on the circle — 35 of the 55 — are
     // recognised from their four end positions (POS ascends) without building their columns.
     ldw::DevBuf dcols[2];
-    hipEvent_t done[2] = {nullptr, nullptr};
-    struct Rel {
-        ldw::DevBuf *b;
-        hipEvent_t *e;
-        ~Rel() {
-            for (int k = 0; k < 2; ++k) {
-                b[k].release();
-                if (e[k]) (void)hipEventDestroy(e[k]);
-            }
-        }
-    } rel{dcols, done};
+    ldw::Event done[2];
     const std::vector<int32_t> &P = c->h_POS;
     int64_t n_filled = 0;
     for (int64_t b = 0; b < nblocks; ++b) {
@@ -886,7 +866,7 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
         if (int rc = build_cols(c, fi.data(), nf, ti.data(), nt, diag, sr_dist, cols, n_blk)) return rc;
         if (n_blk > 0 && a_out && b_out) {
             LDW_REQUIRE(base + n_blk <= capacity, LDW_ERR_SIZE, "ldw_sr_pairs_fill: capacity %lld < %lld rows", (long long)capacity, (long long)(base + n_blk));
-            if (!done[k]) LDW_HIP(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+            LDW_HIP(done[k].ensure(hipEventDisableTiming));
             if (int rc = dcols[k].reserve(cols.size() * sizeof(ColInfo))) return rc;
             LDW_HIP(hipMemcpyAsync(dcols[k].p, cols.data(), cols.size() * sizeof(ColInfo), hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(k_sr_fill, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, c->stream, dcols[k].as<ColInfo>(), (int)nf, (int)nt, fs - 1, ts - 1, diag ? 1 : 0, base,
@@ -927,7 +907,6 @@ int ldw_debug_tab11(ldw_ctx *c, double W, double lo, double delta, double eta, d
     hipError_t he = hipGetLastError();
     if (he == hipSuccess) he = hipMemcpyAsync(out, t.p, (size_t)NB * NB * 8, hipMemcpyDeviceToHost, c->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-    t.release();
     if (he != hipSuccess) return ldw::hip_fail(he, "ldw_debug_tab11", __FILE__, __LINE__);
     *cbin_out = (double)cbin;
     return LDW_OK;

@@ -337,7 +337,7 @@ void bind_packs(EpiArgs &A, const PacksLayout &K, bool hi) {
     A.rowpack_hi = hi ? K.rp_hi : K.rp;
 }
 int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RFpad, int RTpad, int quirk, EmitArgs E,
-                    hipEvent_t *ev, int which, ldw::DevBuf *Gb, hipStream_t gstream, unsigned long long *ghist,
+                    const hipEvent_t *ev, int which, ldw::DevBuf *Gb, hipStream_t gstream, unsigned long long *ghist,
                     const LoHost *mixed = nullptr) {
     ldw::DevBuf &Gbuf = Gb ? *Gb : c->G;
     if (!gstream) gstream = c->stream;
@@ -474,7 +474,7 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
 // Events: ev[0] / ev[1] around the packing + approximate GEMM, ev[5] after the screens and the band GEMM (gs); ev[4] / ev[2]
 // around phase 2.
 // ------------------------------------------------------------------------------------------------
-int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RFpad, int RTpad, int quirk, EmitArgs E, hipEvent_t *ev, int phase,
+int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RFpad, int RTpad, int quirk, EmitArgs E, const hipEvent_t *ev, int phase,
                      hipStream_t gs, unsigned long long *ghist, const LoHost *lo_h, void *zero_hist = nullptr, void *zero_pick = nullptr,
                      size_t zero_pick_bytes = 0) {
     const int s = lo_h->slot;
@@ -858,7 +858,7 @@ int run_block_mi(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t 
     E.write_dense = 1;
     E.spec_B = -1;
     // a symmetric block (same list on both sides) may be asked for in full: the GEMM then computes every tile
-    return launch_block_mi(c, D, nf, nt, SF.Rpad, ST.Rpad, quirk, E, c->ev, 3, nullptr, nullptr, c->hist[0].as<unsigned long long>());
+    return launch_block_mi(c, D, nf, nt, SF.Rpad, ST.Rpad, quirk, E, handles(c->ev), 3, nullptr, nullptr, c->hist[0].as<unsigned long long>());
 }
 
 int ensure_links_capacity(ldw_ctx *c, int64_t sr_rows, int64_t lr_rows) {

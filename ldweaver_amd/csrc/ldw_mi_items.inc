@@ -436,16 +436,10 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     if (band_listed) im.array<&DevPtrs::band_list>(W.bandl.data(), W.bandl.size());
     hb.total = im.bytes;
     const int ps = pin_slot >= 0 ? pin_slot : slot;
-    if (c->pin_cap[ps] < stage_base + hb.total) {
-        void *np = nullptr;
-        LDW_HIP(hipHostMalloc(&np, (stage_base + hb.total) * 2, hipHostMallocDefault));
-        if (c->pin[ps] && stage_base) memcpy(np, c->pin[ps], stage_base);   // (the images in front of it: the first cold-start probe's)
-        if (c->pin[ps]) LDW_HIP(hipHostFree(c->pin[ps]));
-        c->pin[ps] = np;
-        c->pin_cap[ps] = (stage_base + hb.total) * 2;
-    }
+    if (c->pin[ps].cap < stage_base + hb.total)   // (kept: the images in front of it, the first cold-start probe's)
+        if (int rc = c->pin[ps].reserve_keep((stage_base + hb.total) * 2, stage_base)) return rc;
     tp[6] = pnow();
-    char *b = static_cast<char *>(c->pin[ps]) + stage_base;
+    char *b = c->pin[ps].as<char>() + stage_base;
     im.copy_to(b);
     build_perm(c, to_idx, nt, reinterpret_cast<int32_t *>(b + at_perm_t), W.ord_t);
     if (prep_timing && blk_no < 12)
@@ -604,7 +598,7 @@ int submit_a(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayou
     hipStream_t gs = c->overlap ? c->gemm_stream : c->stream;   // overlap off: the stages of all blocks run back to back
     LDW_HIP(hipStreamWaitEvent(gs, c->ev_up[s], 0));
     if (c->done_recorded[s]) LDW_HIP(hipStreamWaitEvent(gs, c->ev_done[s], 0));
-    hipEvent_t *ev = &c->ev_pool[(size_t)hb.blk_no * EVB];
+    const hipEvent_t *ev = handles(&c->ev_pool[(size_t)hb.blk_no * EVB]);
     const bool do_lr = !p->sr_only;
     // (a span: one guess serves every reference block, and the next guess only arrives after all of them.  No wider margin is needed: at C5
     // (800 kept rows per block, the noisiest thresholds) 3 of 1275 blocks miss per pass, as many as block by block)
@@ -682,7 +676,7 @@ int submit_generic(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
     const int s = hb.slot;
     const bool do_lr = !p->sr_only;
     LDW_HIP(hipStreamWaitEvent(c->stream, c->ev_up[s], 0));
-    hipEvent_t *ev = &c->ev_pool[(size_t)hb.blk_no * EVB];
+    const hipEvent_t *ev = handles(&c->ev_pool[(size_t)hb.blk_no * EVB]);
     EmitArgs E0;
     memset(&E0, 0, sizeof(E0));
     E0.write_dense = 1;
@@ -768,7 +762,7 @@ int submit_b(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayou
     if (int rc = make_emit_args(c, hb, p, sl, (hb.mixed || hb.apx) ? (do_lr ? hb.guess : -1) : (do_lr ? c->spec_B_next[hb.diag ? 1 : 0] : -1)))   // (the bit-plane histogram engine shares the epilogue: it speculates like the MFMA engine)
         return rc;
     if (!hb.apx) LDW_HIP(hipMemsetAsync(sl.pick[s], 0, sizeof(ldw::PickOut), c->stream));
-    hipEvent_t *ev = &c->ev_pool[(size_t)hb.blk_no * EVB];
+    const hipEvent_t *ev = handles(&c->ev_pool[(size_t)hb.blk_no * EVB]);
     if (hb.apx) {
         hb.lo.span = hb.span;
         hb.lo.sseg = hb.sseg;
@@ -957,7 +951,7 @@ int finish_block(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallL
     const int s = hb.slot;
     // ---- the one host round trip of the block: the candidate count sizes the sorts ----
     LDW_HIP(hipEventSynchronize(c->ev_pick[s]));
-    ldw::PickOut *hp = static_cast<ldw::PickOut *>(c->pin_pick[s]);
+    ldw::PickOut *hp = c->pin_pick[s].as<ldw::PickOut>();
     bool missed = false;
     if (do_lr && hb.spec_B >= 0 && hp->n > 0 && !hp->spec_ok) {
         // the bucket guess was above the true bucket: redo the epilogue non-speculatively (the short-range rows are
@@ -1022,7 +1016,7 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
     }
     LDW_HIP(hipEventSynchronize(c->ev_pick[s]));
     ldw::PickOut picks[LDW_SPAN_MAX];
-    for (int k = 0; k < hb.span; ++k) memcpy(&picks[k], static_cast<const char *>(c->pin_pick[s]) + (size_t)k * PICK_STRIDE, sizeof(ldw::PickOut));
+    for (int k = 0; k < hb.span; ++k) memcpy(&picks[k], c->pin_pick[s].as<char>() + (size_t)k * PICK_STRIDE, sizeof(ldw::PickOut));
     if (int rc = read_lr_count(c)) return rc;   // (all EARLIER blocks; within the span: upper bounds add up)
     {
         static const bool trace_on = getenv("LDW_BLOCK_TRACE") != nullptr;
@@ -1157,7 +1151,7 @@ int probe_enqueue(ldw_ctx *c, const int32_t *fi, int64_t nf, const int32_t *ti, 
         if (which > 0) LDW_HIP(hipStreamSynchronize(c->stream));
         if (int rc = c->dstage[PS].reserve(which == 0 ? 2 * hb.total + 65536 + 256 : pin_base + hb.total)) return rc;
     }
-    LDW_HIP(hipMemcpyAsync(c->dstage[PS].as<char>() + pin_base, static_cast<const char *>(c->pin[PS]) + pin_base, hb.total, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->dstage[PS].as<char>() + pin_base, c->pin[PS].as<char>() + pin_base, hb.total, hipMemcpyHostToDevice, c->stream));
     fill_dev_ptrs(c, hb);
     if (int rc = c->hist[which].reserve((size_t)NBINS * 8)) return rc;
     if (int rc = make_emit_args(c, hb, &q, sl, -1)) return rc;
@@ -1166,7 +1160,7 @@ int probe_enqueue(ldw_ctx *c, const int32_t *fi, int64_t nf, const int32_t *ti, 
     LDW_HIP(hipMemsetAsync(sl.pick[which], 0, sizeof(ldw::PickOut), c->stream));
     // (in the CALLER's reading of RXY: under quirk Q1 the scrambled RXY — r of two other SNPs — lifts 3-state x 3-state pairs into the tail of an
     // off-diagonal block; a sample evaluated with the intended RXY sat 15 buckets = 7.5 % below the block's own threshold)
-    if (int rc = launch_block_mi(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, hb.E, c->ev, 3, &gx(c, which), nullptr, c->hist[which].as<unsigned long long>()))
+    if (int rc = launch_block_mi(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, hb.E, handles(c->ev), 3, &gx(c, which), nullptr, c->hist[which].as<unsigned long long>()))
         return rc;
     hipLaunchKernelGGL(k_pick_bucket, dim3(1), dim3(256), 0, c->stream, c->hist[which].as<unsigned long long>(), p->lr_retain_links, p->lr_links_approx, -1,
                        (long long)hb.n_lr_total, sl.pick[which], (const unsigned int *)nullptr, 0u);
@@ -1180,7 +1174,7 @@ int probe_enqueue(ldw_ctx *c, const int32_t *fi, int64_t nf, const int32_t *ti, 
 // after hipEventSynchronize(c->ev_probe[P.which])
 void probe_collect(ldw_ctx *c, const Probe &P) {
     if (!P.queued) return;
-    const ldw::PickOut *hp = static_cast<const ldw::PickOut *>(c->pin_pick[P.which]);
+    const ldw::PickOut *hp = c->pin_pick[P.which].as<ldw::PickOut>();
     if (hp->n > 0 && hp->B_true < NBINS) {
         const int g = hp->B_true - PROBE_MARGIN;
         c->spec_B_next[P.kind] = g > 0 ? g : 0;

@@ -177,21 +177,13 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
     // three columns (also what unsorted positions, a fractional genome length and SR-only passes do).
     const bool sr_mi_only = !rows_stay && c0->pos_sorted && c0->g == std::floor(c0->g) && !p->sr_only && p->keep_sr && getenv("LDW_MULTI_SR_FULL_ROWS") == nullptr;
     ldw::DevBuf nA[2], nB[2], nM[2];
-    auto fail = [&](int rc) {
-        for (int w = 0; w < 2; ++w) {
-            nA[w].release();
-            nB[w].release();
-            nM[w].release();
-        }
-        return rc;
-    };
     for (int w = rows_stay ? 1 : 0; w < 2; ++w) {
         const size_t n = (size_t)std::max<int64_t>(tot[w], 1);
-        if (int rc = nA[w].reserve(n * 4)) return fail(rc);
-        if (int rc = nB[w].reserve(n * 4)) return fail(rc);
-        if (int rc = nM[w].reserve(n * 8)) return fail(rc);
+        if (int rc = nA[w].reserve(n * 4)) return rc;
+        if (int rc = nB[w].reserve(n * 4)) return rc;
+        if (int rc = nM[w].reserve(n * 8)) return rc;
     }
-    if (hipStreamSynchronize(c0->stream) != hipSuccess) return fail(LDW_ERR_HIP);   // (the fresh buffers are visible to every queue before a peer writes into them)
+    if (hipStreamSynchronize(c0->stream) != hipSuccess) return LDW_ERR_HIP;   // (the fresh buffers are visible to every queue before a peer writes into them)
     std::vector<int64_t> src_off((size_t)n_ctx * 2, 0);
     int64_t dst_off[2] = {0, 0};
     hipError_t he = hipSuccess;
@@ -238,7 +230,7 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
         }
     }
     (void)hipSetDevice(c0->device);
-    if (rc != LDW_OK) return fail(rc);
+    if (rc != LDW_OK) return rc;
     // ---- 5) ctx[0] adopts the assembled tables (its own share's buffers are released) and the per-block records of ALL blocks
     if (!rows_stay) {
         std::swap(c0->sr_a, nA[0]);
@@ -248,7 +240,7 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
     std::swap(c0->lr_a, nA[1]);
     std::swap(c0->lr_b, nB[1]);
     std::swap(c0->lr_mi, nM[1]);
-    fail(LDW_OK);
+    for (ldw::DevBuf *b : {&nA[0], &nB[0], &nM[0], &nA[1], &nB[1], &nM[1]}) b->release();   // (here, inside ms_out[1], not at the return)
     if (!rows_stay) c0->n_sr = tot[0];   // (rows_stay: ctx[0] keeps the short-range rows of its own share, like every other context)
     c0->n_lr = tot[1];
     c0->n_red = c0->n_pool = 0;
@@ -414,10 +406,6 @@ int ldw_sr_len_quantiles_multi(ldw_ctx **ctx, int n_ctx, int nclust, double sr_d
     int64_t others = 0;
     for (int k = 1; k < n_ctx; ++k) others += tn[(size_t)k];
     ldw::DevBuf stage;   // the other contexts' candidates on context 0's device
-    struct Rel {
-        ldw::DevBuf &b;
-        ~Rel() { b.release(); }
-    } rel{stage};
     LDW_HIP(hipSetDevice(c0->device));
     if (int rc = stage.reserve((size_t)std::max<int64_t>(others, 1) * 8)) return rc;
     LDW_HIP(hipStreamSynchronize(c0->stream));   // (the fresh buffer is visible to every queue before a peer writes into it)

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void k_states_to_text(const uint8_t *__restric
 struct OutState {
     PinnedPair pin;
     DevBuf img, rec_off, name_off, names, idx;
-    hipEvent_t ev[2][3] = {};   // per pinned buffer: before the kernels, after them, after the copy
+    Event ev[2][3];   // per pinned buffer: before the kernels, after them, after the copy
 };
 
 OutState *out_state(ldw_ctx *c) {
@@ -107,7 +107,7 @@ OutState *out_state(ldw_ctx *c) {
 int make_events(OutState *o) {
     for (auto &row : o->ev)
         for (auto &e : row)
-            if (!e) LDW_HIP(hipEventCreate(&e));
+            LDW_HIP(e.ensure());
     return LDW_OK;
 }
 
@@ -128,18 +128,7 @@ int write_all(int fd, const char *p, size_t n, const char *path) {
 }  // namespace
 
 namespace ldw {
-void out_release(ldw_ctx *c) {
-    auto *o = static_cast<OutState *>(c->out);
-    if (!o) return;
-    (void)hipStreamSynchronize(c->stream);
-    o->pin.release();
-    for (DevBuf *b : {&o->img, &o->rec_off, &o->name_off, &o->names, &o->idx}) b->release();
-    for (auto &row : o->ev)
-        for (auto &e : row)
-            if (e) (void)hipEventDestroy(e);
-    delete o;
-    c->out = nullptr;
-}
+void out_release(ldw_ctx *c) { release_state<OutState>(c, c->out); }
 
 int64_t out_trim(ldw_ctx *c) {
     auto *o = static_cast<OutState *>(c->out);
@@ -236,7 +225,7 @@ int ldw_write_alignment(ldw_ctx *c, const char *path, int append, int format, co
         }
         const int64_t bytes = rec_off[(size_t)cuts[(size_t)i + 1]] - rec_off[(size_t)cuts[(size_t)i]];
         const auto w0 = std::chrono::steady_clock::now();
-        if (int r = write_all(fd, static_cast<const char *>(o->pin.p[b]), (size_t)bytes, path)) return r;
+        if (int r = write_all(fd, o->pin.b[b].as<char>(), (size_t)bytes, path)) return r;
         t_write += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
         total += bytes;
         return LDW_OK;
@@ -260,7 +249,7 @@ int ldw_write_alignment(ldw_ctx *c, const char *path, int append, int format, co
         }
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(o->ev[b][1], c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(o->pin.p[b], o->img.p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(o->pin.b[b], o->img.p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipEventRecord(o->ev[b][2], c->stream);
         if (e != hipSuccess) {
             rc = hip_fail(e, "ldw_write_alignment: chunk", __FILE__, __LINE__);

@@ -6,6 +6,7 @@
 
 #include "../../include/ldweaver_amd.h"
 #include "ldw_carve.h"
+#include "ldw_own.h"
 
 namespace ldw {
 
@@ -59,14 +60,10 @@ void plot_net_overlay(uint8_t *canvas, int W, int H, const int32_t *node_xy, con
 
 // N hip events of a timed render: created on demand, destroyed with the object
 template <int N> struct PlotEvents {
-    hipEvent_t e[N] = {};
-    ~PlotEvents() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
+    Event e[N];
     hipError_t create() {
-        for (hipEvent_t &x : e)
-            if (hipError_t rc = hipEventCreate(&x)) return rc;
+        for (Event &x : e)
+            if (hipError_t rc = x.ensure()) return rc;
         return hipSuccess;
     }
     // ms[k] = the time from event k to event k + 1 (all recorded, the stream idle)
@@ -82,7 +79,7 @@ template <int N> struct PlotEvents {
 
 // ldw_plot_net.hip, shared with the tanglegram (ldw_plot_tng.hip): the capsule checks, and the capsule raster left on the device (see there)
 int check_capsules(const ldw_capsule *caps, int64_t n, int W, int H, const char *who);
-int net_raster_device(ldw_ctx *c, Carve &cv, const ldw_capsule *caps, int64_t n, int W, int H, uint8_t **d_rast_out, hipEvent_t *ev, const char *who);
+int net_raster_device(ldw_ctx *c, Carve &cv, const ldw_capsule *caps, int64_t n, int W, int H, uint8_t **d_rast_out, const Event *ev, const char *who);
 
 // the tanglegram's labels (read upwards from their anchors label_xy[2 k], label_xy[2 k + 1]) and title over the device canvas[H][W][3]
 // (ldw_plot_tng.hip); boxes (may be NULL): (n_labels + 1) x 4

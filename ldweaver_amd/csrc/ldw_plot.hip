@@ -260,7 +260,7 @@ int plot_stats(ldw_ctx *c, const Src &s, const HostCols *hc, int64_t n, int n_pa
 // key image + rasters of n_panels panels of W x H pixels; ev (may be NULL): 4 events recorded after the clear, the centre pass, the disc pass
 template <class Src>
 int plot_raster(ldw_ctx *c, const Src &s, const HostCols *hc, bool has_srp, int64_t n, const ldw_plot_opts *o, int D, int n_panels, int W, int H, const double xlim[2], const double ylim[2],
-                int nxt, const int32_t *xt, int nyt, const int32_t *yt, const PlotStats &st, unsigned long long *d_keys, uint8_t *d_rast, hipEvent_t *ev) {
+                int nxt, const int32_t *xt, int nyt, const int32_t *yt, const PlotStats &st, unsigned long long *d_keys, uint8_t *d_rast, const Event *ev) {
     const PlotGeom G{xlim[0], xlim[1], ylim[0], ylim[1], W, H, n_panels};
     PlotPaint P{};
     P.disc = PlotDisc::make(D);

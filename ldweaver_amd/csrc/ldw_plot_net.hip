@@ -125,7 +125,7 @@ int check_capsules(const ldw_capsule *caps, int64_t n, int W, int H, const char 
 // The raster of the capsules, left ON THE DEVICE: *d_rast_out[H][W][3] inside ctx->plot_work, valid until that buffer's next use; the work is queued on the
 // context's stream and not waited for.  cv: arrays the caller took for itself beforehand — they are carved from the same buffer, behind which this call
 // puts its own, and are bound when it returns.  ev (may be NULL, 3 created events): recorded before the binning, between binning and shading, after it.
-int net_raster_device(ldw_ctx *c, Carve &cv, const ldw_capsule *caps, int64_t n, int W, int H, uint8_t **d_rast_out, hipEvent_t *ev, const char *who) {
+int net_raster_device(ldw_ctx *c, Carve &cv, const ldw_capsule *caps, int64_t n, int W, int H, uint8_t **d_rast_out, const Event *ev, const char *who) {
     if (int rc = check_capsules(caps, n, W, H, who)) return rc;
     const int ntx = (W + NET_T - 1) / NET_T, nty = (H + NET_T - 1) / NET_T, ntiles = ntx * nty;
     size_t scan_bytes = 0;

@@ -193,7 +193,7 @@ int tree_raster(ldw_ctx *c, int W, int H, const int32_t *panel, const ldw_bar *b
     if (int rc = cv.reserve(c->plot_work)) return rc;
     PlotEvents<5> events;
     if (ms_out) LDW_HIP(events.create());
-    hipEvent_t *ev = events.e;
+    const Event *ev = events.e;
     hipStream_t st = c->stream;
     if (n > 0) LDW_HIP(hipMemcpyAsync(d_bars, bars, (size_t)n * sizeof(ldw_bar), hipMemcpyHostToDevice, st));
     if (R > 0) {

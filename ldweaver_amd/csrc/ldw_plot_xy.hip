@@ -211,7 +211,7 @@ int xy_stats(ldw_ctx *c, const XYArgs &a, const XYWork &w, XYStats &st, const ch
 
 // key image -> raster of one panel of W x H pixels, left on the device in w.rast; ev (may be NULL): 4 events round the clear, the centre pass, the paint pass
 int xy_raster(ldw_ctx *c, const XYArgs &a, const XYWork &w, int W, int H, const double xlim[2], const double ylim[2], int nxt, const int32_t *xt, int nyt,
-              const int32_t *yt, hipEvent_t *ev) {
+              const int32_t *yt, const Event *ev) {
     const PlotGeom G{xlim[0], xlim[1], ylim[0], ylim[1], W, H, a.n_classes};
     XYPaint P{};
     P.disc = PlotDisc::make(a.D);

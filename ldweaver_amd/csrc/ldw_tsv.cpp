@@ -484,22 +484,10 @@ static int links_tsv_prepare(ldw_ctx *c, int which, const char *path, int append
     // mmap'ed, so delete[] is munmap) stalls the process's NEXT GPU call by ~20 ms — the driver quiesces the queues to drop the registration
     // and restores them a moment later; the short-range model's first stream synchronisation after lr_links.tsv paid it in every job.
     const size_t fetch_bytes = (size_t)n * 16;
-    if (fetch_bytes <= ((size_t)2 << 30)) {
-        if (c->pin_fetch_cap < fetch_bytes) {
-            if (c->pin_fetch) (void)hipHostFree(c->pin_fetch);
-            c->pin_fetch = nullptr;
-            c->pin_fetch_cap = 0;
-            const size_t want = fetch_bytes + fetch_bytes / 8 + 4096;
-            if (hipHostMalloc(&c->pin_fetch, want, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                c->pin_fetch = nullptr;
-            } else {
-                c->pin_fetch_cap = want;
-            }
-        }
-    }
-    if (c->pin_fetch && c->pin_fetch_cap >= fetch_bytes) {
-        J.mi = static_cast<double *>(c->pin_fetch);
+    if (fetch_bytes <= ((size_t)2 << 30) && c->pin_fetch.cap < fetch_bytes)
+        (void)c->pin_fetch.reserve(fetch_bytes + fetch_bytes / 8 + 4096, "link table fetch");   // (on failure: the pageable arrays below)
+    if (c->pin_fetch.cap >= fetch_bytes) {
+        J.mi = c->pin_fetch.as<double>();
         J.a = reinterpret_cast<int32_t *>(J.mi + n);
         J.b = J.a + n;
     } else {   // (tables beyond 2 GB, or no pinned memory to be had: pageable arrays)
@@ -529,7 +517,7 @@ struct LrStream {
     std::mutex mu;
     std::condition_variable cv;
     hipStream_t st = nullptr;           // the context's lr_st / lr_ev / lr_counts (ensure_streams)
-    hipEvent_t *ev = nullptr;
+    const ldw::Event *ev = nullptr;
     int64_t *counts = nullptr;          // pinned [RING]
     int64_t pushed = 0, consumed = 0;   // ring entries handed over / fully written
     bool busy = false, closing = false;
@@ -552,20 +540,12 @@ static void lr_stream_batch(LrStream *S, int64_t hi) {
     const int64_t lo = S->rows, n = hi - lo;
     if (n <= 0 || S->rc != LDW_OK) return;
     const size_t need = (size_t)n * 16;
-    if (c->lr_pin_cap < need) {
-        if (c->lr_pin) (void)hipHostFree(c->lr_pin);
-        c->lr_pin = nullptr;
-        c->lr_pin_cap = 0;
-        const size_t want = std::max<size_t>(need + need / 2, (size_t)8 << 20);
-        if (hipHostMalloc(&c->lr_pin, want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            S->rc = LDW_ERR_HIP;
-            S->err = "lr stream: no pinned staging memory";
-            return;
-        }
-        c->lr_pin_cap = want;
+    if (c->lr_pin.cap < need && c->lr_pin.reserve(std::max<size_t>(need + need / 2, (size_t)8 << 20), "lr stream") != LDW_OK) {
+        S->rc = LDW_ERR_HIP;
+        S->err = "lr stream: no pinned staging memory";
+        return;
     }
-    double *mi = static_cast<double *>(c->lr_pin);
+    double *mi = c->lr_pin.as<double>();
     int32_t *a = reinterpret_cast<int32_t *>(mi + n), *b = a + n;
     // (the table's buffers cannot move under this copy: a growth of the long-range table drains the stream first — ensure_links_capacity)
     hipError_t e = hipMemcpyAsync(a, c->lr_a.as<int32_t>() + lo, (size_t)n * 4, hipMemcpyDeviceToHost, S->st);
@@ -799,10 +779,7 @@ int ldw_host_trim(ldw_ctx *c, int64_t *bytes_out) {
         n += ldw::grep_trim(c);    // the annotated-link search's chunk records and the host copy of its last result (ldw_links_grep.hip)
         if (c->lr_stream == nullptr && c->pin_fetch) {
             (void)hipSetDevice(c->device);
-            (void)hipHostFree(c->pin_fetch);
-            n += (int64_t)c->pin_fetch_cap;
-            c->pin_fetch = nullptr;
-            c->pin_fetch_cap = 0;
+            n += c->pin_fetch.release();
         }
     }
     if (bytes_out) *bytes_out = n;
@@ -828,7 +805,7 @@ int ldw_lr_stream_begin(ldw_ctx *c, const char *path, int append, int nthreads) 
     if (int rc = ldw::ensure_streams(c)) return rc;   // (made with the context unless LDW_NO_PREPARE: the writer's stream, event ring, pinned counters)
     S->st = c->lr_st;
     S->ev = c->lr_ev;
-    S->counts = c->lr_counts;
+    S->counts = c->lr_counts.as<int64_t>();
     LrStream *raw = S.release();
     raw->th = std::thread(lr_stream_main, raw);
     c->lr_stream = raw;
