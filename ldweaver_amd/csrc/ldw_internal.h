@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <string>
 #include <atomic>
 #include <memory>
@@ -53,6 +54,46 @@ struct BlockTrace {
     long long n_cand = 0;
 };
 
+
+// The short-range model's device buffers (ldw_srp.hip) and the geometry of the last ldw_sr_len_quantiles call, which every later entry point of
+// the model runs on.  Other units borrow some of the buffers as working memory between the model's calls: ldw_post.hip cnt and q,
+// ldw_mi.hip seg and out, ldw_multi.cpp out.
+struct SrModel {
+    DevBuf pack, key, pack2, key2, pay, pay2, off, q, n, md, part, shape, cnt, tmp;
+    DevBuf lower, cur, out, seg;   // the model over ranks (ldw_sr_tail_extract ...): per-group bounds, cursors, the extracted rows, block segments
+    int S = 0, nclust = 0;         // set by ldw_sr_len_quantiles before anything launches
+    double sr_dist = 0;
+    bool same_geometry(int nclust_, int32_t S_) const { return nclust_ == nclust && S_ == S; }
+};
+
+// The links kept by ldw_sr_pvalues (rows of the short-range table) or ldw_lr_tukey (rows of the long-range one), the ARACNE pool that goes
+// with them, and the ARACNE flags.  Whatever replaces a link table empties the kept set and the pool and drops the flags: invalidate(), called
+// by ldw_links_import, ldw_links_load, ldw_set_positions, ldw_mi_all_pairs_multi's adoption of the assembled tables and, before it counts,
+// ldw_sr_pvalues.  ldw_lr_tukey borrows ar_val, ar_val2 and ar_flags as working memory: it drops the flags when it starts (drop_flags) and
+// adopts its counts when it is done; ldw_sr_reduced_import adopts likewise; ldw_sr_pool_build resets n_pool alone.
+struct KeptLinks {
+    DevBuf row, meta, srp;                 // int64 row of the table, uint32 clust_c | first_cluster << 8 | dup << 16, double srp_max
+    DevBuf pool_a, pool_b, pool_mi;
+    DevBuf ar_key, ar_val, ar_key2, ar_val2, ar_off, ar_flags;
+    int64_t n_red = 0, n_pool = 0;
+    bool from_lr = false;    // row indexes the long-range table (ldw_lr_tukey) instead of the short-range one
+    bool ar_valid = false;   // ar_flags holds the ARACNE flags of the CURRENT kept links: set by ldw_aracne_device alone
+    void drop_flags() { ar_valid = false; }
+    void invalidate() { n_red = n_pool = 0, drop_flags(); }
+    void adopt(int64_t n_red_, int64_t n_pool_, bool from_lr_) { n_red = n_red_, n_pool = n_pool_, from_lr = from_lr_, drop_flags(); }   // a new kept set and pool are in the buffers
+    int reserve_red(size_t rows) {
+        if (int rc = row.reserve(rows * 8)) return rc;
+        if (int rc = meta.reserve(rows * 4)) return rc;
+        return srp.reserve(rows * 8);
+    }
+    int reserve_pool(size_t rows) {
+        if (int rc = pool_a.reserve(rows * 4)) return rc;
+        if (int rc = pool_b.reserve(rows * 4)) return rc;
+        return pool_mi.reserve(rows * 8);
+    }
+    int64_t red_capacity() const { return (int64_t)std::min(row.cap / 8, std::min(meta.cap / 4, srp.cap / 8)); }
+    int64_t pool_capacity() const { return (int64_t)std::min(pool_a.cap / 4, std::min(pool_b.cap / 4, pool_mi.cap / 8)); }
+};
 }  // namespace ldw
 
 // Every GPU resource below is an owning member (ldw_own.h): `delete` gives all of it back, in reverse order of declaration, so the streams
@@ -233,18 +274,11 @@ struct ldw_ctx {
     ldw::PinnedBuf lr_pin;       // pinned staging of a batch of rows (a, b, MI); grows on demand
     void *tsv_async = nullptr;   // r04: the asynchronous link-table writer, if one is running (ldw_tsv.cpp: TsvAsync)
     ldw::PinnedBuf pin_fetch;    // r04: pinned host arena the tsv writer fetches a link table into (see ldw_write_links_tsv)
-    ldw::DevBuf srm_pack, srm_key, srm_pack2, srm_key2, srm_pay, srm_pay2, srm_off, srm_q, srm_n, srm_md, srm_part, srm_shape, srm_cnt, srm_tmp;
-    ldw::DevBuf srd_lower, srd_cur, srd_out, srd_seg;   // r05, the model over ranks (ldw_sr_tail_extract ...): per-group bounds, cursors, the extracted rows, block segments
+    ldw::SrModel srm;            // the short-range model's buffers and the geometry of the last quantile call
     double ham_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ldw_hamming_stats: columns, padded K, stage times and algorithmic bytes of the last ldw_hamming_weights
     double gemm_stat[6] = {0, 0, 0, 0, 0, 0};   // ldw_gemm_stats: launches and executed int8 ops of the block-wide GEMMs
-    ldw::DevBuf red_row, red_meta, red_srp, pool_a, pool_b, pool_mi, ar_key, ar_val, ar_key2, ar_val2, ar_off, ar_flags;
-    int64_t n_red = 0, n_pool = 0;
-    bool red_from_lr = false;    // red_row indexes the long-range table (ldw_lr_tukey) instead of the short-range one
-    bool ar_valid = false;       // ar_flags holds the ARACNE flags of the CURRENT kept links: set by ldw_aracne_device, cleared wherever the kept set changes
-                                 // or ar_flags is borrowed as working memory (ldw_lr_tukey)
+    ldw::KeptLinks kept;         // the kept links, their ARACNE pool and flags
     ldw::DevBuf plot_work, plot_cols;   // the plots (ldw_plot.hip): key image + rasters + partials; device copy of a chunk of host columns
-    int srm_S = 0, srm_nclust = 0;   // geometry of the last ldw_sr_len_quantiles call
-    double srm_sr_dist = 0;
 
     // ---- pipelined block staging ----
     ldw::Event ev_gemm[LDW_NSLOT];

@@ -548,8 +548,7 @@ int ldw_set_positions(ldw_ctx *c, const int32_t *POS, int64_t L, double g) {
     c->sr_total = c->sr_share_rows = -1;
     c->sr_total_dist = -1;
     c->n_sr = c->n_lr = 0;
-    c->n_red = c->n_pool = 0;
-    c->ar_valid = false;
+    c->kept.invalidate();
     c->stats.clear();
     c->multi_owner.clear();
     return LDW_OK;
@@ -624,8 +623,7 @@ int ldw_links_load(ldw_ctx *c, int which, int32_t pos1_col, int32_t pos2_col, in
         LDW_HIP(hipStreamSynchronize(c->stream));
     }
     (which == 0 ? c->n_sr : c->n_lr) = kept;
-    c->n_red = c->n_pool = 0;   // as ldw_links_import leaves the context: whatever was derived from the old table is stale
-    c->ar_valid = false;
+    c->kept.invalidate();   // as ldw_links_import leaves the context: whatever was derived from the old table is stale
     c->stats.clear();
     c->multi_owner.clear();
     if (n_out) *n_out = kept;

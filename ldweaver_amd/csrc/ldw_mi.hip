@@ -809,9 +809,9 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
         auto d_cu = cv.take<int32_t>(ncols), d_cl = cv.take<int32_t>(ncols);
         auto d_rows = cv.take<int64_t>((int64_t)nb), d_base = cv.take<int64_t>((int64_t)nb + 1);
         auto d_bad = cv.take<int>(2);
-        if (int rc = cv.reserve(c->srd_seg)) return rc;
-        if (int rc = c->srd_out.reserve((size_t)ncols * sizeof(ColInfo))) return rc;
-        ColInfo *d_cols = c->srd_out.as<ColInfo>();
+        if (int rc = cv.reserve(c->srm.seg)) return rc;
+        if (int rc = c->srm.out.reserve((size_t)ncols * sizeof(ColInfo))) return rc;
+        ColInfo *d_cols = c->srm.out.as<ColInfo>();
         LDW_HIP(hipMemcpyAsync(d_blk, hb.data(), nb * sizeof(SrBlkDev), hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemsetAsync(d_bad, 0, 8, c->stream));
         hipLaunchKernelGGL(k_cols_dev, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, c->stream, c->POS.as<int32_t>(), c->g, sr_dist, d_blk, (int)nb, ncols, d_cols, d_cu,
@@ -1044,8 +1044,7 @@ int ldw_links_import(ldw_ctx *c, int which, const int32_t *a, const int32_t *b, 
         LDW_HIP(hipStreamSynchronize(c->stream));
     }
     (which == 0 ? c->n_sr : c->n_lr) = n;
-    c->n_red = c->n_pool = 0;   // whatever was derived from the old table is stale:
-    c->ar_valid = false;
+    c->kept.invalidate();   // whatever was derived from the old table is stale:
     c->stats.clear();           // the per-block records of the pass that made it (ldw_block_stats answers LDW_ERR_ARG until the next pass) ...
     c->multi_owner.clear();     // ... and the deal of an in-process pass whose shares these rows replace
     return LDW_OK;

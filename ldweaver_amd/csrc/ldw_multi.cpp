@@ -243,8 +243,7 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
     for (ldw::DevBuf *b : {&nA[0], &nB[0], &nM[0], &nA[1], &nB[1], &nM[1]}) b->release();   // (here, inside ms_out[1], not at the return)
     if (!rows_stay) c0->n_sr = tot[0];   // (rows_stay: ctx[0] keeps the short-range rows of its own share, like every other context)
     c0->n_lr = tot[1];
-    c0->n_red = c0->n_pool = 0;
-    c0->ar_valid = false;
+    c0->kept.invalidate();
     c0->stats = stats;                    // the records of ALL blocks, in the caller's order (ldw_block_stats)
     if (rows_stay) c0->multi_owner = owner;
     if (ms_out) ms_out[1] = now_ms() - t_1;
@@ -398,8 +397,8 @@ int ldw_sr_len_quantiles_multi(ldw_ctx **ctx, int n_ctx, int nclust, double sr_d
             if (int r = ldw_sr_tail_extract(ctx[k], nclust, S, lower.data(), tcnt[(size_t)k].data(), nullptr, 0, 0, &n)) return r;
             tn[(size_t)k] = n;
             if (n == 0) return (int)LDW_OK;
-            if (int r = ctx[k]->srd_out.reserve((size_t)n * 8)) return r;
-            return ldw_sr_tail_extract(ctx[k], nclust, S, lower.data(), tcnt[(size_t)k].data(), ctx[k]->srd_out.as<double>(), n, 1, &n);
+            if (int r = ctx[k]->srm.out.reserve((size_t)n * 8)) return r;
+            return ldw_sr_tail_extract(ctx[k], nclust, S, lower.data(), tcnt[(size_t)k].data(), ctx[k]->srm.out.as<double>(), n, 1, &n);
         }))
         return rc;
     ldw_ctx *c0 = ctx[0];
@@ -414,7 +413,7 @@ int ldw_sr_len_quantiles_multi(ldw_ctx **ctx, int n_ctx, int nclust, double sr_d
     {
         int64_t off = 0;
         hipError_t he = hipSuccess;
-        pm[0] = c0->srd_out.as<double>();
+        pm[0] = c0->srm.out.as<double>();
         pc[0] = tcnt[0].data();
         for (int k = 1; k < n_ctx && he == hipSuccess; ++k) {
             pm[(size_t)k] = stage.as<double>() + off;
@@ -424,7 +423,7 @@ int ldw_sr_len_quantiles_multi(ldw_ctx **ctx, int n_ctx, int nclust, double sr_d
                 he = hipErrorInvalidDevice;
                 break;
             }
-            he = copy_rows(stage.as<double>() + off, c0, ctx[k]->srd_out.p, ctx[k], (size_t)tn[(size_t)k] * 8);
+            he = copy_rows(stage.as<double>() + off, c0, ctx[k]->srm.out.p, ctx[k], (size_t)tn[(size_t)k] * 8);
             off += tn[(size_t)k];
         }
         for (int k = 1; k < n_ctx; ++k)   // every source's copy has landed

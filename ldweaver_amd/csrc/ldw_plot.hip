@@ -483,21 +483,21 @@ int ldw_plot_links(ldw_ctx *c, int which, int use_aracne, const ldw_plot_opts *o
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(c->POS.p != nullptr, LDW_ERR_STATE, "ldw_plot_links: no SNP meta data (ldw_set_snp_meta)");
     LDW_REQUIRE(c->g > 0, LDW_ERR_STATE, "ldw_plot_links: the genome length is not known (ldw_set_positions with g = 0): len cannot be taken from the positions");
-    LDW_REQUIRE((which == 1) == c->red_from_lr, LDW_ERR_STATE, "ldw_plot_links: the kept links are those of the %s table", c->red_from_lr ? "long-range" : "short-range");
-    const int64_t n = c->n_red;
-    LDW_REQUIRE(!use_aracne || n == 0 || (c->ar_valid && c->ar_flags.cap >= (size_t)n), LDW_ERR_STATE,
+    LDW_REQUIRE((which == 1) == c->kept.from_lr, LDW_ERR_STATE, "ldw_plot_links: the kept links are those of the %s table", c->kept.from_lr ? "long-range" : "short-range");
+    const int64_t n = c->kept.n_red;
+    LDW_REQUIRE(!use_aracne || n == 0 || (c->kept.ar_valid && c->kept.ar_flags.cap >= (size_t)n), LDW_ERR_STATE,
                 "ldw_plot_links: ldw_aracne_device has not run for the kept links (use_aracne = 0 draws every link as direct)");
     CtxSrc s;
     memset(&s, 0, sizeof(s));
-    s.row = c->red_row.as<int64_t>();
+    s.row = c->kept.row.as<int64_t>();
     s.a = (which ? c->lr_a : c->sr_a).as<int32_t>();
     s.b = (which ? c->lr_b : c->sr_b).as<int32_t>();
     s.mi = (which ? c->lr_mi : c->sr_mi).as<double>();
     s.POS = c->POS.as<int32_t>();
     s.g = c->g;
-    s.srp = which ? nullptr : c->red_srp.as<double>();
-    s.meta = which ? nullptr : c->red_meta.as<uint32_t>();
-    s.flags = use_aracne && n > 0 ? c->ar_flags.as<uint8_t>() : nullptr;
+    s.srp = which ? nullptr : c->kept.srp.as<double>();
+    s.meta = which ? nullptr : c->kept.meta.as<uint32_t>();
+    s.flags = use_aracne && n > 0 ? c->kept.ar_flags.as<uint8_t>() : nullptr;
     int n_panels = 1;
     int32_t labels[LDW_PLOT_MAX_PANELS] = {1};
     if (opts->kind == LDW_PLOT_SR_CLUST && n > 0) {

@@ -258,34 +258,34 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
         LDW_REQUIRE(sr_a[i] >= 0 && sr_a[i] < c->L && sr_b[i] >= 0 && sr_b[i] < c->L, LDW_ERR_ARG,
                     "ldw_lr_tukey: short-range row %lld has SNP indices (%d, %d) outside 0..%lld (a position that is not in POS?)", (long long)i, sr_a[i], sr_b[i],
                     (long long)c->L - 1);
-    c->ar_valid = false;   // the kept set changes, and ar_flags is working memory below
+    c->kept.drop_flags();   // the kept set changes, and ar_flags is working memory below
     if (ns > 0) {
-        if (int rc = c->ar_val.reserve((size_t)ns * 4)) return rc;
-        if (int rc = c->ar_val2.reserve((size_t)ns * 4)) return rc;
-        if (int rc = c->ar_flags.reserve((size_t)ns * 8)) return rc;
-        LDW_HIP(hipMemcpyAsync(c->ar_val.p, sr_a, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(c->ar_val2.p, sr_b, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(c->ar_flags.p, sr_mi, (size_t)ns * 8, hipMemcpyHostToDevice, c->stream));
+        if (int rc = c->kept.ar_val.reserve((size_t)ns * 4)) return rc;
+        if (int rc = c->kept.ar_val2.reserve((size_t)ns * 4)) return rc;
+        if (int rc = c->kept.ar_flags.reserve((size_t)ns * 8)) return rc;
+        LDW_HIP(hipMemcpyAsync(c->kept.ar_val.p, sr_a, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
+        LDW_HIP(hipMemcpyAsync(c->kept.ar_val2.p, sr_b, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
+        LDW_HIP(hipMemcpyAsync(c->kept.ar_flags.p, sr_mi, (size_t)ns * 8, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));   // pageable sources
     }
-    const int32_t *d_sa = c->ar_val.as<int32_t>(), *d_sb = c->ar_val2.as<int32_t>();
-    const double *d_smi = c->ar_flags.as<double>();
+    const int32_t *d_sa = c->kept.ar_val.as<int32_t>(), *d_sb = c->kept.ar_val2.as<int32_t>();
+    const double *d_smi = c->kept.ar_flags.as<double>();
     LDW_REQUIRE(n > 0, LDW_ERR_STATE, "ldw_lr_tukey: the long-range table is empty");
     LDW_REQUIRE(n < 2147483647LL, LDW_ERR_SIZE, "ldw_lr_tukey: too many long-range links");
     // ---- sorted MI keys -> order statistics ----
-    if (int rc = c->ar_key.reserve((size_t)n * 8)) return rc;
-    if (int rc = c->ar_key2.reserve((size_t)n * 8)) return rc;
-    LDW_LAUNCH(k_mi_keys, grid_of(n), dim3(256), 0, c->stream, c->lr_mi.as<double>(), n, c->ar_key.as<uint64_t>());
+    if (int rc = c->kept.ar_key.reserve((size_t)n * 8)) return rc;
+    if (int rc = c->kept.ar_key2.reserve((size_t)n * 8)) return rc;
+    LDW_LAUNCH(k_mi_keys, grid_of(n), dim3(256), 0, c->stream, c->lr_mi.as<double>(), n, c->kept.ar_key.as<uint64_t>());
     size_t tb = 0;
     LDW_HIP(prim_sort_keys_bytes<uint64_t>((size_t)n, 0, 64, c->stream, &tb));
     if (int rc = c->scratch.reserve(tb)) return rc;
     tb = c->scratch.cap;
-    LDW_HIP(prim_sort_keys(c->scratch.p, tb, c->ar_key.as<uint64_t>(), c->ar_key2.as<uint64_t>(), (int)n, 0, 64, c->stream));
+    LDW_HIP(prim_sort_keys(c->scratch.p, tb, c->kept.ar_key.as<uint64_t>(), c->kept.ar_key2.as<uint64_t>(), (int)n, 0, 64, c->stream));
     auto order_stats = [&](double p, double &q) -> int {
         const Q7 r = q7_ranks(n, p);
         uint64_t k[2];
-        LDW_HIP(hipMemcpyAsync(&k[0], c->ar_key2.as<uint64_t>() + (r.lo - 1), 8, hipMemcpyDeviceToHost, c->stream));
-        LDW_HIP(hipMemcpyAsync(&k[1], c->ar_key2.as<uint64_t>() + (r.hi - 1), 8, hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipMemcpyAsync(&k[0], c->kept.ar_key2.as<uint64_t>() + (r.lo - 1), 8, hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipMemcpyAsync(&k[1], c->kept.ar_key2.as<uint64_t>() + (r.hi - 1), 8, hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
         q = q7_value(r, key_f64(k[0]), key_f64(k[1]));
         return LDW_OK;
@@ -299,8 +299,8 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     double thr[2] = {q3 + 1.5 * iqr, q3 + 3.0 * iqr};
     // ---- rows above min(thresholds): count per 256-row segment, prefix, ordered select ----
     const int64_t nseg_l = (n + 255) / 256, nseg_s = (ns + 255) / 256;
-    if (int rc = c->ar_off.reserve((size_t)(nseg_l + nseg_s + 2) * 8 * 2)) return rc;
-    int64_t *cnt_l = c->ar_off.as<int64_t>(), *off_l = cnt_l + nseg_l + 1, *cnt_s = off_l + nseg_l + 1, *off_s = cnt_s + nseg_s + 1;
+    if (int rc = c->kept.ar_off.reserve((size_t)(nseg_l + nseg_s + 2) * 8 * 2)) return rc;
+    int64_t *cnt_l = c->kept.ar_off.as<int64_t>(), *off_l = cnt_l + nseg_l + 1, *cnt_s = off_l + nseg_l + 1, *off_s = cnt_s + nseg_s + 1;
     auto count_pass = [&](double t, int64_t &n_red, int64_t &n_srp) -> int {
         LDW_LAUNCH(k_count_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->lr_mi.as<double>(), n, t, cnt_l);
         if (ns > 0) LDW_LAUNCH(k_count_gt, dim3((unsigned)nseg_s), dim3(256), 0, c->stream, d_smi, ns, t, cnt_s);
@@ -337,21 +337,17 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     }
     const double tmin = std::min(thr[0], thr[1]);
     const int64_t n_pool = n_red + n_srp;
-    if (int rc = c->red_row.reserve((size_t)std::max<int64_t>(n_red, 1) * 8)) return rc;
-    if (int rc = c->pool_a.reserve((size_t)std::max<int64_t>(n_pool, 1) * 4)) return rc;
-    if (int rc = c->pool_b.reserve((size_t)std::max<int64_t>(n_pool, 1) * 4)) return rc;
-    if (int rc = c->pool_mi.reserve((size_t)std::max<int64_t>(n_pool, 1) * 8)) return rc;
+    if (int rc = c->kept.row.reserve((size_t)std::max<int64_t>(n_red, 1) * 8)) return rc;
+    if (int rc = c->kept.reserve_pool((size_t)std::max<int64_t>(n_pool, 1))) return rc;
     LDW_LAUNCH(k_select_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(),
-                       c->lr_mi.as<double>(), n, tmin, off_l, (int64_t)0, c->red_row.as<int64_t>(), c->pool_a.as<int32_t>(),
-                       c->pool_b.as<int32_t>(), c->pool_mi.as<double>());
+                       c->lr_mi.as<double>(), n, tmin, off_l, (int64_t)0, c->kept.row.as<int64_t>(), c->kept.pool_a.as<int32_t>(),
+                       c->kept.pool_b.as<int32_t>(), c->kept.pool_mi.as<double>());
     if (ns > 0)
         LDW_LAUNCH(k_select_gt, dim3((unsigned)nseg_s), dim3(256), 0, c->stream, d_sa, d_sb,
-                           d_smi, ns, tmin, off_s, n_red, (int64_t *)nullptr, c->pool_a.as<int32_t>(),
-                           c->pool_b.as<int32_t>(), c->pool_mi.as<double>());
+                           d_smi, ns, tmin, off_s, n_red, (int64_t *)nullptr, c->kept.pool_a.as<int32_t>(),
+                           c->kept.pool_b.as<int32_t>(), c->kept.pool_mi.as<double>());
     LDW_HIP(hipStreamSynchronize(c->stream));
-    c->n_red = n_red;
-    c->n_pool = n_pool;
-    c->red_from_lr = true;
+    c->kept.adopt(n_red, n_pool, true);
     thresholds_out[0] = thr[0];
     thresholds_out[1] = thr[1];
     *fallback_out = fallback;
@@ -380,8 +376,8 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
     int64_t n_nodes = 0;
     if (int rc = pos_slots(c, &d_slot, &n_nodes)) return rc;
     // ---- pos_vec: which SNPs occur in a link, and their rank ----
-    if (int rc = c->srm_cnt.reserve((size_t)(n_nodes + 1) * 4 * 2)) return rc;
-    int32_t *used = c->srm_cnt.as<int32_t>(), *rank = used + n_nodes + 1;
+    if (int rc = c->srm.cnt.reserve((size_t)(n_nodes + 1) * 4 * 2)) return rc;
+    int32_t *used = c->srm.cnt.as<int32_t>(), *rank = used + n_nodes + 1;
     LDW_HIP(hipMemsetAsync(used, 0, (size_t)(n_nodes + 1) * 4, c->stream));
     const int32_t *POS = c->POS.as<int32_t>();
     if (nl > 0) LDW_LAUNCH(k_mark_used, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), nl, POS, from, to, windowed, used, d_slot);
@@ -407,9 +403,9 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
     LDW_REQUIRE(capacity < 0 || capacity >= (int64_t)B * B, LDW_ERR_SIZE, "ldw_ldmap: capacity %lld < %lld", (long long)capacity, (long long)B * B);
     const int64_t nb = (int64_t)B * B;
     const int rgrid = (int)std::min<int64_t>((nb + 255) / 256, 1024);
-    if (int rc = c->srm_q.reserve((size_t)nb * 32 + (size_t)rgrid * 16)) return rc;
+    if (int rc = c->srm.q.reserve((size_t)nb * 32 + (size_t)rgrid * 16)) return rc;
     // red: what went past the fixed-point accumulators (k_ldmap_add); acc_lo / acc_hi: their two words
-    double *red = c->srm_q.as<double>(), *htm = red + 3 * nb, *mm = htm + nb;
+    double *red = c->srm.q.as<double>(), *htm = red + 3 * nb, *mm = htm + nb;
     unsigned long long *acc_lo = reinterpret_cast<unsigned long long *>(red + nb), *acc_hi = acc_lo + nb;
     LDW_HIP(hipMemsetAsync(red, 0, (size_t)nb * 24, c->stream));
     if (nl > 0) LDW_LAUNCH(k_ldmap_add, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>(), nl, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);

@@ -6,9 +6,11 @@
 // numerical steps in between — the log-log least-squares fit (:428) and the two-parameter beta MLE (:452) — stay
 // with the caller (they are O(sr_dist) and O(1)); the library offers the data reductions either side of them:
 //
-//   ldw_sr_len_quantiles : rows -> (len, cluster, cluster) tags; two stable radix sorts (MI, then len); one
-//                          workgroup per len counts the members of every cluster and picks the two order
-//                          statistics quantile type 7 interpolates between           (:417-424)
+//   ldw_sr_len_quantiles : per (cluster, len) the two order statistics quantile type 7 interpolates between (:417-424).  Up to
+//                          SEL_MAXCL clusters (the default path): ONE stable radix sort by len, its keys and {MI key, cluster tags}
+//                          payload read straight from the table, then a radix select per len (k_sr_select).  More clusters, or
+//                          LDW_SR_QUANT_SORT: rows -> (len, cluster, cluster) tags, two stable radix sorts (MI, then len), one
+//                          workgroup per len counts the members of every cluster and picks the two ranks (k_sr_quant)
 //   ldw_sr_excess_stats  : diff = MI - mean_dist[len] (positional index, quirk Q5); n, sum x, sum x^2,
 //                          sum log x, sum log(1-x) of the positive excesses per cluster — the sufficient
 //                          statistics of the beta likelihood, reduced in a fixed order      (:444-452)
@@ -17,6 +19,10 @@
 //                          MI >= min(MI kept) (:489-490)
 //   ldw_aracne_device    : CSR adjacency of the pool by one radix sort; one wave per link to check intersects the
 //                          two sorted neighbour lists
+//
+// Every kernel that streams the table takes it as one SrRowsView and reads a row through row_tag; which clusters a row is a member of, and
+// its excess over a cluster's fitted decay, are stated once (RowTag::member, member_excess).  Sections: the row and its clusters, quantiles,
+// excess statistics, p-values and pool, ARACNE, the model over ranks, import.
 //
 // HBM-bound integer/byte work apart from the log/continued-fraction arithmetic of the p-values.
 #include <algorithm>
@@ -36,42 +42,83 @@ namespace ldw {
 constexpr int SRM_MAXCL = 255;   // cluster ids 1..255 fit the 8-bit tags
 constexpr int SRM_GRID = 2048;   // fixed grid of the row-streaming kernels (deterministic reduction order)
 
+// ------------------------------------------------------------------------------------------------
+// the row of the table and the clusters it is a member of
+// ------------------------------------------------------------------------------------------------
+// The short-range table with what places a row on the genome and in its clusters: built by sr_rows(c), taken by value by every kernel that
+// streams the rows.  (The members are no-alias like the separate kernel parameters they replace; nothing here is written by those kernels.)
+struct SrRowsView {
+    const int32_t *__restrict__ sa, *__restrict__ sb;   // from side (pos2), to side (pos1)
+    const double *__restrict__ smi;
+    const int32_t *__restrict__ POS, *__restrict__ paint;
+    int64_t n;
+    double g, sr_dist;
+};
+
 struct RowTag {
     int len;      // integer len, 0 = not in (0, sr_dist)
     int c1, c2;   // clust1 (to side, pos1), clust2 (from side, pos2)
+    // A row is a member of the cluster of its to-side SNP and, when that differs, of its from-side SNP's too (R/computePairwiseMI.R:411-414):
+    // the cluster of side s (0: to side, then 1: from side), 0 for the second side of a row whose two clusters coincide.
+    __host__ __device__ bool cross() const { return c2 != c1; }
+    __host__ __device__ int member(int s) const { return s == 0 ? c1 : (cross() ? c2 : 0); }
+    // len << 16 | clust1 << 8 | clust2: the tag k_sr_quant and k_sr_select read
+    __host__ __device__ uint32_t pack() const { return ((uint32_t)len << 16) | ((uint32_t)c1 << 8) | (uint32_t)c2; }
 };
 
-__device__ __forceinline__ RowTag row_tag(int32_t a, int32_t b, const int32_t *__restrict__ POS,
-                                          const int32_t *__restrict__ paint, double g, double sr_dist) {
-    RowTag t;
-    const int64_t gi = (int64_t)g;
-    if ((double)gi == g && gi > 0) {
-        // integral genome length (the rule: ldw_sr_len_quantiles requires it): POS are integers, so circ_len's 0.5 g - |d - 0.5 g| is min(d, g - d)
-        // exactly — no fp64 division per row (r04: k_sr_stats / k_sr_pval stream 2.25e9 rows at C5)
-        int64_t d = ((int64_t)POS[b] - (int64_t)POS[a]) % gi;
-        if (d < 0) d += gi;
-        const int64_t len = d < gi - d ? d : gi - d;
-        t.len = (len > 0 && (double)len < sr_dist) ? (int)len : 0;
-    } else {
-        const double len = circ_len((double)POS[b], (double)POS[a], g);
-        t.len = (len > 0.0 && len < sr_dist) ? (int)len : 0;
+// len between SNPs a and b on a genome of integral length gi: POS are integers, so circ_len's 0.5 g - |d - 0.5 g| is min(d, g - d) exactly — no
+// fp64 division per row (r04: k_sr_stats / k_sr_pval stream 2.25e9 rows at C5)
+__host__ __device__ __forceinline__ int row_len(const SrRowsView &v, int32_t a, int32_t b, int64_t gi) {
+    int64_t d = ((int64_t)v.POS[b] - (int64_t)v.POS[a]) % gi;
+    if (d < 0) d += gi;
+    const int64_t len = d < gi - d ? d : gi - d;
+    return (len > 0 && (double)len < v.sr_dist) ? (int)len : 0;
+}
+__host__ __device__ __forceinline__ RowTag row_clusters(const SrRowsView &v, int32_t a, int32_t b) { return RowTag{0, v.paint[b], v.paint[a]}; }
+
+__device__ __forceinline__ RowTag row_tag(const SrRowsView &v, int32_t a, int32_t b) {
+    RowTag t = row_clusters(v, a, b);
+    const int64_t gi = (int64_t)v.g;
+    if ((double)gi == v.g && gi > 0) {
+        t.len = row_len(v, a, b, gi);
+    } else {   // (ldw_sr_len_quantiles requires an integral genome length; a later ldw_set_snp_meta may bring any)
+        const double len = circ_len((double)v.POS[b], (double)v.POS[a], v.g);
+        t.len = (len > 0.0 && len < v.sr_dist) ? (int)len : 0;
     }
-    t.c1 = paint[b];
-    t.c2 = paint[a];
     return t;
+}
+__device__ __forceinline__ RowTag row_tag(const SrRowsView &v, int64_t i) { return row_tag(v, v.sa[i], v.sb[i]); }
+
+// excess of a link over cluster c's fitted decay; NaN when the link has no valid len or the table has no entry
+__device__ __forceinline__ double excess(double mi, int len, int c, const double *__restrict__ md, int S) {
+    if (len <= 0 || c < 1) return __builtin_nan("");
+    return mi - md[(int64_t)(c - 1) * S + (len - 1)];
+}
+// ... over the decay of the cluster of its side s; NaN (never > 0) where the row is no member through that side.  A row contributes to a
+// cluster where this is positive (R/computePairwiseMI.R:444-486); sides are visited to side, then from side everywhere.
+__device__ __forceinline__ double member_excess(const RowTag &t, int s, double mi, const double *__restrict__ md, int S) {
+    return excess(mi, t.len, t.member(s), md, S);
+}
+
+// the context's short-range table on the geometry of the last ldw_sr_len_quantiles call
+static SrRowsView sr_rows(const ldw_ctx *c) {
+    return SrRowsView{c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->n_sr, c->g, c->srm.sr_dist};
+}
+
+static int sr_ready(ldw_ctx *c, const char *who) {
+    if (int rc = check_gpu(c)) return rc;
+    LDW_REQUIRE(c->have_meta, LDW_ERR_STATE, "%s: ldw_set_snp_meta has not been called", who);
+    LDW_REQUIRE(!c->pos_only, LDW_ERR_STATE, "%s: the context holds positions only (ldw_set_positions): the short-range model needs the paint of ldw_set_snp_meta", who);
+    return LDW_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
 // quantiles per (cluster, len)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sr_tag(const int32_t *__restrict__ sa, const int32_t *__restrict__ sb,
-                                                const double *__restrict__ smi, int64_t n, const int32_t *__restrict__ POS,
-                                                const int32_t *__restrict__ paint, double g, double sr_dist,
-                                                uint32_t *__restrict__ pack, uint64_t *__restrict__ key) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const RowTag t = row_tag(sa[i], sb[i], POS, paint, g, sr_dist);
-        pack[i] = ((uint32_t)t.len << 16) | ((uint32_t)t.c1 << 8) | (uint32_t)t.c2;
-        key[i] = f64_key(smi[i]);
+__global__ __launch_bounds__(256) void k_sr_tag(const SrRowsView v, uint32_t *__restrict__ pack, uint64_t *__restrict__ key) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < v.n; i += (int64_t)gridDim.x * 256) {
+        pack[i] = row_tag(v, i).pack();
+        key[i] = f64_key(v.smi[i]);
     }
 }
 
@@ -204,29 +251,17 @@ __global__ __launch_bounds__(256) void k_sr_quant(const SrPay *__restrict__ pay,
 // ------------------------------------------------------------------------------------------------
 constexpr int SEL_MAXCL = 4, SEL_BITS = 11, SEL_BINS = 1 << SEL_BITS, SEL_CAP = 512;
 
-struct SrRowsView {
-    const int32_t *sa, *sb;
-    const double *smi;
-    const int32_t *POS, *paint;
-    double g, sr_dist;
-};
-// (the sort evaluates both functors once per row and pass: the key needs the two positions only — in integers: POS and g are integers, so
-// circ_len's 0.5 g - |d - 0.5 g| is min(d, g - d) exactly — the payload the two cluster ids only)
+// (the sort evaluates both functors once per row and pass: the key needs the two positions only — in integers, row_len — the payload the MI
+// and the two cluster ids only)
 struct SrLenOf {
     SrRowsView v;
-    __host__ __device__ uint16_t operator()(int64_t i) const {
-        const int64_t gi = (int64_t)v.g;
-        int64_t d = ((int64_t)v.POS[v.sb[i]] - (int64_t)v.POS[v.sa[i]]) % gi;
-        if (d < 0) d += gi;
-        const int64_t len = d < gi - d ? d : gi - d;
-        return (len > 0 && (double)len < v.sr_dist) ? (uint16_t)len : (uint16_t)0;
-    }
+    __host__ __device__ uint16_t operator()(int64_t i) const { return (uint16_t)row_len(v, v.sa[i], v.sb[i], (int64_t)v.g); }
 };
 struct SrPayOf {
     SrRowsView v;
     __host__ __device__ SrPay operator()(int64_t i) const {
         const uint64_t k = f64_key(v.smi[i]);
-        return SrPay{(uint32_t)k, (uint32_t)(k >> 32), ((uint32_t)v.paint[v.sb[i]] << 8) | (uint32_t)v.paint[v.sa[i]]};
+        return SrPay{(uint32_t)k, (uint32_t)(k >> 32), row_clusters(v, v.sa[i], v.sb[i]).pack()};
     }
 };
 
@@ -438,6 +473,83 @@ __global__ __launch_bounds__(SEL_NT) void k_sr_select(const SrPay *__restrict__ 
     }
 }
 
+// Buffers of the select path.  (r04, tried and dropped: reserving them on a side thread while the MI pass runs, with and without touching the
+// new memory there.  The first quantile step of a context costs ~20 ms more than a later one (2.4 GB of fresh device memory at C4), but the
+// wait only moved — from hipMalloc to the first sort — and the memset took 5 ms from the MI pass: tools/quant_cold_probe.py, tools/job_profile.py --cold.)
+static size_t srm_sort_temp_bytes(int64_t n) {
+    const SrRowsView V{};   // (only sizes the sort: never read)
+    auto kin = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SrLenOf{V});
+    auto vin = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SrPayOf{V});
+    size_t tb = 0;
+    if (rocprim::radix_sort_pairs(nullptr, tb, kin, (uint16_t *)nullptr, vin, (SrPay *)nullptr, (size_t)n, 0u, 16u, (hipStream_t)0) != hipSuccess) return 0;
+    return tb;
+}
+static int srm_reserve_select(ldw_ctx *c, int64_t n) {
+    if (int rc = c->srm.pack2.reserve((size_t)n * 2 + 64)) return rc;
+    if (int rc = c->srm.pay.reserve((size_t)n * sizeof(SrPay))) return rc;
+    return c->srm.tmp.reserve(srm_sort_temp_bytes(n) + 256);
+}
+
+// The two-sort path from tagged rows on: c->srm.pack[i] = len << 16 | clust1 << 8 | clust2, c->srm.key[i] = key of MI, n rows (k_sr_tag, or the
+// candidates of all ranks: k_tail_unpack).  Two stable LSD sorts, both over the FULL width of their key type: by MI (u64 keys, tags as values), then
+// by len (u16 keys, {MI key, tag} as values) -> ordered by (len, MI).  rocPRIM 7.2's merge-sort path mis-sorts u32 keys on a partial bit range at
+// mid sizes (reproduced standalone through the hipCUB interface), so no begin_bit/end_bit tricks here.  q: host, 2 * nclust * S (NaN-filled by
+// the caller: uploaded first); gtot / viol_out: see k_sr_quant.
+static int quant_reserve_sorts(ldw_ctx *c, int64_t n, int32_t S, size_t cells) {
+    if (int rc = c->srm.pack.reserve((size_t)n * 4)) return rc;
+    if (int rc = c->srm.pack2.reserve((size_t)n * 4)) return rc;
+    if (int rc = c->srm.key.reserve((size_t)n * 8)) return rc;
+    if (int rc = c->srm.key2.reserve((size_t)n * 8)) return rc;
+    if (int rc = c->srm.off.reserve((size_t)(S + 2) * 8)) return rc;
+    if (int rc = c->srm.q.reserve(cells * 16)) return rc;
+    if (int rc = c->srm.n.reserve(cells * 8 + 64)) return rc;
+    if (int rc = c->srm.pay.reserve((size_t)n * sizeof(SrPay))) return rc;
+    return c->srm.pay2.reserve((size_t)n * sizeof(SrPay));
+}
+static int quant_two_sorts(ldw_ctx *c, int64_t n, int32_t S, int nclust, double prob, const int64_t *d_gtot, std::vector<double> &q, int64_t *n_out,
+                           unsigned int *viol_out) {
+    const size_t cells = (size_t)nclust * S;
+    uint32_t *pack = c->srm.pack.as<uint32_t>(), *pack2 = c->srm.pack2.as<uint32_t>();
+    uint64_t *key = c->srm.key.as<uint64_t>(), *key2 = c->srm.key2.as<uint64_t>();
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, 65536);
+    uint16_t *len16 = reinterpret_cast<uint16_t *>(pack), *len16b = len16 + n;   // pack is free after the first sort
+    SrPay *pay = c->srm.pay.as<SrPay>(), *pay2 = c->srm.pay2.as<SrPay>();
+    size_t t1 = 0, t2 = 0;
+    LDW_HIP((prim_sort_pairs_bytes<uint64_t, uint32_t>((size_t)n, 0, 64, c->stream, &t1)));
+    LDW_HIP((prim_sort_pairs_bytes<uint16_t, SrPay>((size_t)n, 0, 16, c->stream, &t2)));
+    if (int rc = c->scratch.reserve(std::max(t1, t2))) return rc;
+    size_t tb = c->scratch.cap;
+    LDW_HIP(prim_sort_pairs(c->scratch.p, tb, key, key2, pack, pack2, n, 0, 64, c->stream));
+    LDW_LAUNCH(k_sr_split, dim3(grid), dim3(256), 0, c->stream, pack2, key2, n, len16, pay);
+    tb = c->scratch.cap;
+    LDW_HIP(prim_sort_pairs(c->scratch.p, tb, len16, len16b, pay, pay2, n, 0, 16, c->stream));
+    LDW_LAUNCH(k_sr_seg_offsets, dim3((S + 2 + 255) / 256), dim3(256), 0, c->stream, len16b, n, S, c->srm.off.as<int64_t>());
+    LDW_HIP(hipMemcpyAsync(c->srm.q.p, q.data(), cells * 16, hipMemcpyHostToDevice, c->stream));
+    unsigned int *d_viol = reinterpret_cast<unsigned int *>(c->srm.n.as<char>() + cells * 8);   // (the 64 spare bytes behind the counts)
+    if (viol_out) LDW_HIP(hipMemsetAsync(d_viol, 0, 4, c->stream));
+    LDW_LAUNCH(k_sr_quant, dim3(S), dim3(256), 0, c->stream, pay2, c->srm.off.as<int64_t>(), S, nclust, prob,
+                       c->srm.q.as<double>(), c->srm.n.as<int64_t>(), d_gtot, viol_out ? d_viol : (unsigned int *)nullptr);
+    LDW_HIP(hipMemcpyAsync(q.data(), c->srm.q.p, cells * 16, hipMemcpyDeviceToHost, c->stream));
+    if (n_out) LDW_HIP(hipMemcpyAsync(n_out, c->srm.n.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    if (viol_out) LDW_HIP(hipMemcpyAsync(viol_out, d_viol, 4, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    return LDW_OK;
+}
+
+static void split_q(const std::vector<double> &q, size_t cells, double *q_lo_out, double *q_hi_out) {   // q[2 k], q[2 k + 1] of cell k
+    for (size_t k = 0; k < cells; ++k) {
+        q_lo_out[k] = q[2 * k];
+        q_hi_out[k] = q[2 * k + 1];
+    }
+}
+
+// host wall time of the steps of ldw_sr_len_quantiles (LDW_HOST_TIMING)
+struct HostClock {
+    using Point = std::chrono::steady_clock::time_point;
+    static Point now() { return std::chrono::steady_clock::now(); }
+    static double ms(Point a, Point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+};
+
 // ------------------------------------------------------------------------------------------------
 // positive excesses over the fitted decay: sufficient statistics of the beta likelihood
 // ------------------------------------------------------------------------------------------------
@@ -445,12 +557,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-// excess of a link over cluster c's fitted decay; NaN when the link has no valid len or the table has no entry
-__device__ __forceinline__ double excess(double mi, int len, int c, const double *__restrict__ md, int S) {
-    if (len <= 0 || c < 1) return __builtin_nan("");
-    return mi - md[(int64_t)(c - 1) * S + (len - 1)];
 }
 
 // The rows of one workgroup.  seg == null: the table cut into gridDim.x contiguous strips.  r05, seg != null: segment blockIdx.x / strips of the table
@@ -475,28 +581,25 @@ __device__ __forceinline__ void strip_of(int64_t n, const int64_t *__restrict__ 
 // still a fixed order, bit-identical from run to run.  k_sr_stats peels the clusters of every wave of 64 rows and reduces five doubles across
 // the wave each time (and evaluates both logarithms for all 64 lanes): 33 ms for the 2.25e9 rows of C5.
 template <int NC>
-__global__ __launch_bounds__(256) void k_sr_stats_small(const int32_t *__restrict__ sa, const int32_t *__restrict__ sb,
-                                                        const double *__restrict__ smi, int64_t n, const int32_t *__restrict__ POS,
-                                                        const int32_t *__restrict__ paint, double g, double sr_dist,
-                                                        const double *__restrict__ md, int S, int nclust, double *__restrict__ part,
+__global__ __launch_bounds__(256) void k_sr_stats_small(const SrRowsView v, const double *__restrict__ md, int S, int nclust, double *__restrict__ part,
                                                         const int64_t *__restrict__ seg, int strips) {
     __shared__ double red[4][NC][5];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int64_t beg, end;
-    strip_of(n, seg, strips, beg, end);
+    strip_of(v.n, seg, strips, beg, end);
     double a[NC][5];
 #pragma unroll
     for (int c = 0; c < NC; ++c)
 #pragma unroll
         for (int k = 0; k < 5; ++k) a[c][k] = 0.0;
     for (int64_t i = beg + tid; i < end; i += 256) {
-        const RowTag t = row_tag(sa[i], sb[i], POS, paint, g, sr_dist);
-        const double mi = smi[i];
+        const RowTag t = row_tag(v, i);
+        const double mi = v.smi[i];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const int c = s == 0 ? t.c1 : (t.c2 != t.c1 ? t.c2 : 0);
-            const double x = c ? excess(mi, t.len, c, md, S) : 0.0;
-            if (c && x > 0) {   // (few rows lie above the fitted decay: the logarithms run for those lanes only)
+            const int c = t.member(s);
+            const double x = member_excess(t, s, mi, md, S);
+            if (x > 0) {   // (few rows lie above the fitted decay: the logarithms run for those lanes only)
                 const double lx = log(x), l1x = log1p(-x);
 #pragma unroll
                 for (int cc = 0; cc < NC; ++cc)
@@ -514,8 +617,8 @@ __global__ __launch_bounds__(256) void k_sr_stats_small(const int32_t *__restric
     for (int c = 0; c < NC; ++c)
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
-            const double v = wave_sum(a[c][k]);   // (xor butterfly: the same tree on every run)
-            if (lane == 0) red[wv][c][k] = v;
+            const double w = wave_sum(a[c][k]);   // (xor butterfly: the same tree on every run)
+            if (lane == 0) red[wv][c][k] = w;
         }
     __syncthreads();
     for (int k = tid; k < nclust * 5; k += 256) {
@@ -525,35 +628,28 @@ __global__ __launch_bounds__(256) void k_sr_stats_small(const int32_t *__restric
 }
 
 // part[(blockIdx.x * nclust + c) * 5 + k]
-__global__ __launch_bounds__(256) void k_sr_stats(const int32_t *__restrict__ sa, const int32_t *__restrict__ sb,
-                                                  const double *__restrict__ smi, int64_t n, const int32_t *__restrict__ POS,
-                                                  const int32_t *__restrict__ paint, double g, double sr_dist,
-                                                  const double *__restrict__ md, int S, int nclust,
-                                                  double *__restrict__ part, const int64_t *__restrict__ seg, int strips) {
+__global__ __launch_bounds__(256) void k_sr_stats(const SrRowsView v, const double *__restrict__ md, int S, int nclust, double *__restrict__ part,
+                                                  const int64_t *__restrict__ seg, int strips) {
     extern __shared__ double acc[];   // [4 waves][nclust][5]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     for (int k = tid; k < 4 * nclust * 5; k += 256) acc[k] = 0.0;
     __syncthreads();
     double *mine = acc + (int64_t)wv * nclust * 5;
     int64_t beg, end;
-    strip_of(n, seg, strips, beg, end);
+    strip_of(v.n, seg, strips, beg, end);
     for (int64_t base = beg; base < end; base += 256) {
         const int64_t i = base + tid;
         int cs[2] = {0, 0};
         double ds[2] = {0, 0};
         if (i < end) {
-            const RowTag t = row_tag(sa[i], sb[i], POS, paint, g, sr_dist);
-            const double mi = smi[i];
-            const double d1 = excess(mi, t.len, t.c1, md, S);
-            if (d1 > 0) {
-                cs[0] = t.c1;
-                ds[0] = d1;
-            }
-            if (t.c2 != t.c1) {
-                const double d2 = excess(mi, t.len, t.c2, md, S);
-                if (d2 > 0) {
-                    cs[1] = t.c2;
-                    ds[1] = d2;
+            const RowTag t = row_tag(v, i);
+            const double mi = v.smi[i];
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const double d = member_excess(t, s, mi, md, S);
+                if (d > 0) {
+                    cs[s] = t.member(s);
+                    ds[s] = d;
                 }
             }
         }
@@ -584,6 +680,33 @@ __global__ __launch_bounds__(256) void k_sr_stats(const int32_t *__restrict__ sa
     __syncthreads();
     for (int k = tid; k < nclust * 5; k += 256)
         part[(int64_t)blockIdx.x * nclust * 5 + k] = ((acc[k] + acc[nclust * 5 + k]) + acc[2 * nclust * 5 + k]) + acc[3 * nclust * 5 + k];
+}
+
+// the fitted decay of the model's clusters onto the device; the caller's nclust / S must be those of the last ldw_sr_len_quantiles call
+static int upload_md(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, const char *who) {
+    LDW_REQUIRE(c->srm.same_geometry(nclust, S), LDW_ERR_STATE, "%s: nclust/S differ from the last ldw_sr_len_quantiles call", who);
+    LDW_REQUIRE(mean_dist, LDW_ERR_ARG, "%s: null mean_dist", who);
+    if (int rc = c->srm.md.reserve((size_t)nclust * S * 8)) return rc;
+    LDW_HIP(hipMemcpyAsync(c->srm.md.p, mean_dist, (size_t)nclust * S * 8, hipMemcpyHostToDevice, c->stream));
+    return LDW_OK;
+}
+
+// One statistics kernel over `grid` workgroups (strips of the table, or of the device segments `seg`: strip_of) and its partial sums on the
+// host, part[(workgroup * nclust + c) * 5 + k]: the caller adds them up in its own fixed order.  After upload_md.
+static int launch_sr_stats(ldw_ctx *c, const SrRowsView &v, int grid, const int64_t *seg, int strips, std::vector<double> &part) {
+    const int nclust = c->srm.nclust;
+    const int32_t S = c->srm.S;
+    const size_t pbytes = (size_t)grid * nclust * 5 * 8;
+    if (int rc = c->srm.part.reserve(pbytes)) return rc;
+    if (nclust <= 4 && getenv("LDW_SR_STATS_PEEL") == nullptr)
+        LDW_LAUNCH(k_sr_stats_small<4>, dim3(grid), dim3(256), 0, c->stream, v, c->srm.md.as<double>(), S, nclust, c->srm.part.as<double>(), seg, strips);
+    else
+        LDW_LAUNCH(k_sr_stats, dim3(grid), dim3(256), (size_t)4 * nclust * 5 * 8, c->stream, v, c->srm.md.as<double>(), S, nclust, c->srm.part.as<double>(), seg,
+                   strips);
+    part.resize((size_t)grid * nclust * 5);
+    LDW_HIP(hipMemcpyAsync(part.data(), c->srm.part.p, pbytes, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));
+    return LDW_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -655,85 +778,103 @@ __global__ void k_sr_dstar(const double *__restrict__ shape, int nclust, double 
     dstar[c] = lo * 0.999999;   // (lo: the tail there is still <= the cut-off)
 }
 
-// MODE 0: count reduced rows and min MI key; MODE 1: also write them.  meta = clust_c | first_cluster << 8 | dup << 16
-template <int MODE>
-__global__ __launch_bounds__(256) void k_sr_pval(const int32_t *__restrict__ sa, const int32_t *__restrict__ sb,
-                                                 const double *__restrict__ smi, int64_t n, const int32_t *__restrict__ POS,
-                                                 const int32_t *__restrict__ paint, double g, double sr_dist,
-                                                 const double *__restrict__ md, int S, const double *__restrict__ shape,
-                                                 double cutoff, SrCounters *__restrict__ ctr, int64_t *__restrict__ red_row,
-                                                 uint32_t *__restrict__ red_meta, double *__restrict__ red_srp, int64_t cap,
-                                                 const double *__restrict__ dstar) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const RowTag t = row_tag(sa[i], sb[i], POS, paint, g, sr_dist);
-        const double mi = smi[i];
-        const double d1 = excess(mi, t.len, t.c1, md, S);
-        const bool v1 = d1 > 0;
+// Appends the rows whose largest tail over their clusters exceeds the cut-off (the first `cap` of them: ctr->n_red counts all) and keeps the
+// smallest MI key among them.  meta = clust_c | first_cluster << 8 | dup << 16
+__global__ __launch_bounds__(256) void k_sr_pval(const SrRowsView v, const double *__restrict__ md, int S, const double *__restrict__ shape, double cutoff,
+                                                 SrCounters *__restrict__ ctr, int64_t *__restrict__ red_row, uint32_t *__restrict__ red_meta,
+                                                 double *__restrict__ red_srp, int64_t cap, const double *__restrict__ dstar) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < v.n; i += (int64_t)gridDim.x * 256) {
+        const RowTag t = row_tag(v, i);
+        const double mi = v.smi[i];
+        const double d[2] = {member_excess(t, 0, mi, md, S), member_excess(t, 1, mi, md, S)};
         if (dstar) {   // (a row is kept only if the tail of one of its clusters exceeds the cut-off: neither excess reaches its cluster's crossing -> dropped)
-            bool may = v1 && d1 >= dstar[t.c1 - 1];
-            if (!may && t.c2 != t.c1) {
-                const double d2 = excess(mi, t.len, t.c2, md, S);
-                may = d2 > 0 && d2 >= dstar[t.c2 - 1];
-            }
+            bool may = false;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) may = may || (d[k] > 0 && d[k] >= dstar[t.member(k) - 1]);
             if (!may) continue;
         }
         double s = 0.0;
-        int cc = 0, first = 0;
-        if (v1) {
-            const double *sh = shape + (int64_t)(t.c1 - 1) * 3;
-            s = neg_log_beta_sf(d1, sh[0], sh[1], sh[2]);
-            cc = first = t.c1;
-        }
-        const bool dup = t.c2 != t.c1;
-        if (dup) {
-            const double d2 = excess(mi, t.len, t.c2, md, S);
-            if (d2 > 0) {
-                const double *sh = shape + (int64_t)(t.c2 - 1) * 3;
-                const double s2 = neg_log_beta_sf(d2, sh[0], sh[1], sh[2]);
-                // which.max over the rows of the group in cluster order: ties go to the smaller cluster id
-                if (!v1 || s2 > s || (s2 == s && t.c2 < cc)) {
-                    s = s2;
-                    cc = t.c2;
-                }
-                first = (!v1 || t.c2 < first) ? t.c2 : first;
+        int cc = 0, first = 0;   // first: the smaller member with a positive excess
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (!(d[k] > 0)) continue;
+            const int c = t.member(k);
+            const double *sh = shape + (int64_t)(c - 1) * 3;
+            const double sk = neg_log_beta_sf(d[k], sh[0], sh[1], sh[2]);
+            // which.max over the rows of the group in cluster order: ties go to the smaller cluster id
+            if (!cc || sk > s || (sk == s && c < cc)) {
+                s = sk;
+                cc = c;
             }
+            first = (!first || c < first) ? c : first;
         }
         if (cc && s > cutoff) {
             const unsigned long long slot = atomicAdd(&ctr->n_red, 1ull);
             atomicMin(&ctr->min_key, (unsigned long long)f64_key(mi));
-            if (MODE == 1 && (int64_t)slot < cap) {
+            if ((int64_t)slot < cap) {
                 red_row[slot] = i;
-                red_meta[slot] = (uint32_t)cc | ((uint32_t)first << 8) | ((uint32_t)dup << 16);
+                red_meta[slot] = (uint32_t)cc | ((uint32_t)first << 8) | ((uint32_t)t.cross() << 16);
                 red_srp[slot] = s;
             }
         }
     }
 }
 
-// ARACNE pool: rows of the merged table (positive excess in some cluster) with MI >= min(MI kept)
-template <int MODE>
-__global__ __launch_bounds__(256) void k_sr_pool(const int32_t *__restrict__ sa, const int32_t *__restrict__ sb,
-                                                 const double *__restrict__ smi, int64_t n, const int32_t *__restrict__ POS,
-                                                 const int32_t *__restrict__ paint, double g, double sr_dist,
-                                                 const double *__restrict__ md, int S, SrCounters *__restrict__ ctr,
-                                                 int32_t *__restrict__ pa, int32_t *__restrict__ pb, double *__restrict__ pmi,
-                                                 int64_t cap) {
+// ARACNE pool: rows of the merged table (positive excess in some cluster) with MI >= min(MI kept); the first `cap` are written, all counted
+__global__ __launch_bounds__(256) void k_sr_pool(const SrRowsView v, const double *__restrict__ md, int S, SrCounters *__restrict__ ctr,
+                                                 int32_t *__restrict__ pa, int32_t *__restrict__ pb, double *__restrict__ pmi, int64_t cap) {
     const uint64_t kmin = ctr->min_key;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double mi = smi[i];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < v.n; i += (int64_t)gridDim.x * 256) {
+        const double mi = v.smi[i];
         if (f64_key(mi) < kmin) continue;
-        const int32_t a = sa[i], b = sb[i];
-        const RowTag t = row_tag(a, b, POS, paint, g, sr_dist);
-        bool v = excess(mi, t.len, t.c1, md, S) > 0;
-        if (!v && t.c2 != t.c1) v = excess(mi, t.len, t.c2, md, S) > 0;
-        if (!v) continue;
+        const int32_t a = v.sa[i], b = v.sb[i];
+        const RowTag t = row_tag(v, a, b);
+        if (!(member_excess(t, 0, mi, md, S) > 0 || member_excess(t, 1, mi, md, S) > 0)) continue;
         const unsigned long long slot = atomicAdd(&ctr->n_pool, 1ull);
-        if (MODE == 1 && (int64_t)slot < cap) {
+        if ((int64_t)slot < cap) {
             pa[slot] = a;
             pb[slot] = b;
             pmi[slot] = mi;
         }
     }
+}
+
+__global__ void k_red_gather(const int64_t *__restrict__ row, int64_t n, const int32_t *__restrict__ sa, const int32_t *__restrict__ sb,
+                             const double *__restrict__ smi, int32_t *__restrict__ a, int32_t *__restrict__ b, double *__restrict__ mi) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t r = row[i];
+    a[i] = sa[r];
+    b[i] = sb[r];
+    mi[i] = smi[r];
+}
+
+// ARACNE pool of the context's short-range table: rows with a positive excess in some cluster and MI key >= min_key (R/computePairwiseMI.R:489-490);
+// needs the fitted decay on the device (upload_md) and the geometry of the last ldw_sr_len_quantiles call.  Sets c->kept.n_pool.
+static int build_pool(ldw_ctx *c, unsigned long long min_key) {
+    const int64_t n = c->n_sr;
+    KeptLinks &K = c->kept;
+    K.n_pool = 0;
+    if (n == 0) return LDW_OK;
+    if (int rc = c->srm.cnt.reserve(sizeof(SrCounters))) return rc;
+    SrCounters *d = c->srm.cnt.as<SrCounters>();
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, 16384);
+    if (int rc = K.reserve_pool((size_t)std::min<int64_t>(n, (int64_t)1 << 22))) return rc;   // (the row floor: ldw_sr_pvalues)
+    for (int pass = 0; pass < 2; ++pass) {
+        const int64_t cap = K.pool_capacity();
+        SrCounters h2 = {0, 0, min_key};
+        LDW_HIP(hipMemcpyAsync(d, &h2, sizeof(h2), hipMemcpyHostToDevice, c->stream));
+        LDW_LAUNCH(k_sr_pool, dim3(grid), dim3(256), 0, c->stream, sr_rows(c), c->srm.md.as<double>(), c->srm.S, d, K.pool_a.as<int32_t>(), K.pool_b.as<int32_t>(),
+                   K.pool_mi.as<double>(), cap);
+        SrCounters got;
+        LDW_HIP(hipMemcpyAsync(&got, d, sizeof(got), hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipStreamSynchronize(c->stream));
+        K.n_pool = (int64_t)got.n_pool;
+        if (K.n_pool <= cap) break;
+        LDW_REQUIRE(pass == 0, LDW_ERR_STATE, "short-range pool changed size between passes");
+        if (int rc = K.reserve_pool((size_t)K.n_pool)) return rc;
+    }
+    return LDW_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -804,32 +945,6 @@ __global__ __launch_bounds__(256) void k_ar_check(const int64_t *__restrict__ re
     if (lane == 0) flags[w] = any ? 0 : 1;
 }
 
-__global__ void k_red_gather(const int64_t *__restrict__ row, int64_t n, const int32_t *__restrict__ sa, const int32_t *__restrict__ sb,
-                             const double *__restrict__ smi, int32_t *__restrict__ a, int32_t *__restrict__ b, double *__restrict__ mi) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t r = row[i];
-    a[i] = sa[r];
-    b[i] = sb[r];
-    mi[i] = smi[r];
-}
-
-// Buffers of the select path.  (r04, tried and dropped: reserving them on a side thread while the MI pass runs, with and without touching the
-// new memory there.  The first quantile step of a context costs ~20 ms more than a later one (2.4 GB of fresh device memory at C4), but the
-// wait only moved — from hipMalloc to the first sort — and the memset took 5 ms from the MI pass: tools/quant_cold_probe.py, tools/job_profile.py --cold.)
-static size_t srm_sort_temp_bytes(int64_t n) {
-    const SrRowsView V{nullptr, nullptr, nullptr, nullptr, nullptr, 1.0, 1.0};
-    auto kin = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SrLenOf{V});
-    auto vin = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SrPayOf{V});
-    size_t tb = 0;
-    if (rocprim::radix_sort_pairs(nullptr, tb, kin, (uint16_t *)nullptr, vin, (SrPay *)nullptr, (size_t)n, 0u, 16u, (hipStream_t)0) != hipSuccess) return 0;
-    return tb;
-}
-static int srm_reserve_select(ldw_ctx *c, int64_t n) {
-    if (int rc = c->srm_pack2.reserve((size_t)n * 2 + 64)) return rc;
-    if (int rc = c->srm_pay.reserve((size_t)n * sizeof(SrPay))) return rc;
-    return c->srm_tmp.reserve(srm_sort_temp_bytes(n) + 256);
-}
 // ------------------------------------------------------------------------------------------------
 // r05: the short-range model with the rows LEFT on the rank that computed them (docs/HISTORY.md 7b).  What travels instead of the table:
 // per (cluster, len) group the rows at or above a bound that is known to lie below the group's order statistics (k_sr_tail: ~7 % of the MI
@@ -839,17 +954,15 @@ static int srm_reserve_select(ldw_ctx *c, int64_t n) {
 // whose two SNPs lie in different clusters is a member of both groups (R/computePairwiseMI.R:411-414) and is listed in each.
 // MODE 0: cur[g] += members passing; MODE 1: out[cur[g]++] = MI (cur preset to the groups' first output positions).  NaN bound: nothing passes.
 template <int MODE>
-__global__ __launch_bounds__(256) void k_sr_tail(const int32_t *__restrict__ sa, const int32_t *__restrict__ sb, const double *__restrict__ smi,
-                                                 int64_t n, const int32_t *__restrict__ POS, const int32_t *__restrict__ paint, double g,
-                                                 double sr_dist, const double *__restrict__ lower, int S, int nclust,
-                                                 unsigned long long *__restrict__ cur, double *__restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const RowTag t = row_tag(sa[i], sb[i], POS, paint, g, sr_dist);
+__global__ __launch_bounds__(256) void k_sr_tail(const SrRowsView v, const double *__restrict__ lower, int S, int nclust, unsigned long long *__restrict__ cur,
+                                                 double *__restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < v.n; i += (int64_t)gridDim.x * 256) {
+        const RowTag t = row_tag(v, i);
         if (t.len <= 0 || t.len > S) continue;
-        const double mi = smi[i];
+        const double mi = v.smi[i];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const int c = s == 0 ? t.c1 : (t.c2 != t.c1 ? t.c2 : 0);
+            const int c = t.member(s);
             if (c < 1 || c > nclust) continue;
             if (!(mi >= lower[(int64_t)(c - 1) * S + (t.len - 1)])) continue;
             const unsigned long long pos = atomicAdd(&cur[(int64_t)(t.len - 1) * nclust + (c - 1)], 1ull);
@@ -880,62 +993,11 @@ __global__ void k_iota64(int64_t *__restrict__ p, int64_t n) {
     if (i < n) p[i] = i;
 }
 
-// The two-sort path from tagged rows on: c->srm_pack[i] = len << 16 | clust1 << 8 | clust2, c->srm_key[i] = key of MI, n rows (k_sr_tag, or the
-// candidates of all ranks: k_tail_unpack).  Two stable LSD sorts, both over the FULL width of their key type: by MI (u64 keys, tags as values), then
-// by len (u16 keys, {MI key, tag} as values) -> ordered by (len, MI).  rocPRIM 7.2's merge-sort path mis-sorts u32 keys on a partial bit range at
-// mid sizes (reproduced standalone through the hipCUB interface), so no begin_bit/end_bit tricks here.  q: host, 2 * nclust * S (NaN-filled by
-// the caller: uploaded first); gtot / viol_out: see k_sr_quant.
-static int quant_reserve_sorts(ldw_ctx *c, int64_t n, int32_t S, size_t cells) {
-    if (int rc = c->srm_pack.reserve((size_t)n * 4)) return rc;
-    if (int rc = c->srm_pack2.reserve((size_t)n * 4)) return rc;
-    if (int rc = c->srm_key.reserve((size_t)n * 8)) return rc;
-    if (int rc = c->srm_key2.reserve((size_t)n * 8)) return rc;
-    if (int rc = c->srm_off.reserve((size_t)(S + 2) * 8)) return rc;
-    if (int rc = c->srm_q.reserve(cells * 16)) return rc;
-    if (int rc = c->srm_n.reserve(cells * 8 + 64)) return rc;
-    if (int rc = c->srm_pay.reserve((size_t)n * sizeof(SrPay))) return rc;
-    return c->srm_pay2.reserve((size_t)n * sizeof(SrPay));
-}
-static int quant_two_sorts(ldw_ctx *c, int64_t n, int32_t S, int nclust, double prob, const int64_t *d_gtot, std::vector<double> &q, int64_t *n_out,
-                           unsigned int *viol_out) {
-    const size_t cells = (size_t)nclust * S;
-    uint32_t *pack = c->srm_pack.as<uint32_t>(), *pack2 = c->srm_pack2.as<uint32_t>();
-    uint64_t *key = c->srm_key.as<uint64_t>(), *key2 = c->srm_key2.as<uint64_t>();
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, 65536);
-    uint16_t *len16 = reinterpret_cast<uint16_t *>(pack), *len16b = len16 + n;   // pack is free after the first sort
-    SrPay *pay = c->srm_pay.as<SrPay>(), *pay2 = c->srm_pay2.as<SrPay>();
-    size_t t1 = 0, t2 = 0;
-    LDW_HIP((prim_sort_pairs_bytes<uint64_t, uint32_t>((size_t)n, 0, 64, c->stream, &t1)));
-    LDW_HIP((prim_sort_pairs_bytes<uint16_t, SrPay>((size_t)n, 0, 16, c->stream, &t2)));
-    if (int rc = c->scratch.reserve(std::max(t1, t2))) return rc;
-    size_t tb = c->scratch.cap;
-    LDW_HIP(prim_sort_pairs(c->scratch.p, tb, key, key2, pack, pack2, n, 0, 64, c->stream));
-    LDW_LAUNCH(k_sr_split, dim3(grid), dim3(256), 0, c->stream, pack2, key2, n, len16, pay);
-    tb = c->scratch.cap;
-    LDW_HIP(prim_sort_pairs(c->scratch.p, tb, len16, len16b, pay, pay2, n, 0, 16, c->stream));
-    LDW_LAUNCH(k_sr_seg_offsets, dim3((S + 2 + 255) / 256), dim3(256), 0, c->stream, len16b, n, S, c->srm_off.as<int64_t>());
-    LDW_HIP(hipMemcpyAsync(c->srm_q.p, q.data(), cells * 16, hipMemcpyHostToDevice, c->stream));
-    unsigned int *d_viol = reinterpret_cast<unsigned int *>(c->srm_n.as<char>() + cells * 8);   // (the 64 spare bytes behind the counts)
-    if (viol_out) LDW_HIP(hipMemsetAsync(d_viol, 0, 4, c->stream));
-    LDW_LAUNCH(k_sr_quant, dim3(S), dim3(256), 0, c->stream, pay2, c->srm_off.as<int64_t>(), S, nclust, prob,
-                       c->srm_q.as<double>(), c->srm_n.as<int64_t>(), d_gtot, viol_out ? d_viol : (unsigned int *)nullptr);
-    LDW_HIP(hipMemcpyAsync(q.data(), c->srm_q.p, cells * 16, hipMemcpyDeviceToHost, c->stream));
-    if (n_out) LDW_HIP(hipMemcpyAsync(n_out, c->srm_n.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
-    if (viol_out) LDW_HIP(hipMemcpyAsync(viol_out, d_viol, 4, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipStreamSynchronize(c->stream));
-    return LDW_OK;
-}
-static int sr_ready(ldw_ctx *c, const char *who) {
-    if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->have_meta, LDW_ERR_STATE, "%s: ldw_set_snp_meta has not been called", who);
-    LDW_REQUIRE(!c->pos_only, LDW_ERR_STATE, "%s: the context holds positions only (ldw_set_positions): the short-range model needs the paint of ldw_set_snp_meta", who);
-    return LDW_OK;
-}
-
 }  // namespace ldw
 
 extern "C" {
 
+// ---- quantiles
 int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, int32_t S, double *q_lo_out, double *q_hi_out,
                          int64_t *n_out) {
     if (int rc = sr_ready(c, "ldw_sr_len_quantiles")) return rc;
@@ -953,9 +1015,9 @@ int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, in
     // (POS may be in any order and may repeat: every row's len is computed from its two positions, rows with len outside
     // (0, sr_dist) are left out exactly as R/computePairwiseMI.R:414 does)
     const int64_t n = c->n_sr;
-    c->srm_S = S;
-    c->srm_nclust = nclust;
-    c->srm_sr_dist = sr_dist;
+    c->srm.S = S;
+    c->srm.nclust = nclust;
+    c->srm.sr_dist = sr_dist;
     const size_t cells = (size_t)nclust * S;
     std::vector<double> q(cells * 2, std::nan(""));
     if (n == 0) {
@@ -966,8 +1028,8 @@ int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, in
         return LDW_OK;
     }
     static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto now = HostClock::now;
+    const auto ms = HostClock::ms;
     const auto t_0 = now();
     const bool force_sort = getenv("LDW_SR_QUANT_SORT") != nullptr;   // (A/B and tests: the two-sort path for any nclust; read per call)
     if (nclust <= SEL_MAXCL && n < (int64_t)0xFFFFFFFFll && !force_sort) {
@@ -987,17 +1049,17 @@ int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, in
             tmp_cap = c->Gapx[2].cap;
         } else {
             if (int rc = srm_reserve_select(c, n)) return rc;
-            mem[0] = c->srm_pack2.p;
-            mem[1] = c->srm_pay.p;
-            mem[2] = c->srm_tmp.p;
-            tmp_cap = c->srm_tmp.cap;
+            mem[0] = c->srm.pack2.p;
+            mem[1] = c->srm.pay.p;
+            mem[2] = c->srm.tmp.p;
+            tmp_cap = c->srm.tmp.cap;
         }
         const auto t_b = now();
-        if (int rc = c->srm_off.reserve((size_t)(S + 2) * 8)) return rc;
-        if (int rc = c->srm_q.reserve(cells * 16)) return rc;
-        if (int rc = c->srm_n.reserve(cells * 8)) return rc;
+        if (int rc = c->srm.off.reserve((size_t)(S + 2) * 8)) return rc;
+        if (int rc = c->srm.q.reserve(cells * 16)) return rc;
+        if (int rc = c->srm.n.reserve(cells * 8)) return rc;
         if (host_timing) fprintf(stderr, "[ldw] sr quantiles: temp query %.2f ms, gemm stream sync / reserve %.2f, small reserves %.2f\n", ms(t_0, t_a), ms(t_a, t_b), ms(t_b, now()));
-        const SrRowsView V{c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, sr_dist};
+        const SrRowsView V = sr_rows(c);
         auto kin = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SrLenOf{V});
         auto vin = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SrPayOf{V});
         uint16_t *len_sorted = static_cast<uint16_t *>(mem[0]);
@@ -1013,74 +1075,25 @@ int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, in
             fprintf(stderr, "[ldw] sr quantiles%s: reserve %.2f ms (scratch %.1f MB), stream drain %.2f, sort enqueue %.2f + wait %.2f\n", borrow ? " (memory borrowed from the pass)" : "", ms(t_0, t_1), (double)tb / 1e6,
                     ms(t_1, t_1b), ms(t_1b, t_2), ms(t_2, now()));
         }
-        LDW_LAUNCH(k_sr_seg_offsets, dim3((S + 2 + 255) / 256), dim3(256), 0, c->stream, len_sorted, n, S, c->srm_off.as<int64_t>());
-        LDW_HIP(hipMemcpyAsync(c->srm_q.p, q.data(), cells * 16, hipMemcpyHostToDevice, c->stream));
-        LDW_LAUNCH(k_sr_select, dim3(S), dim3(SEL_NT), 0, c->stream, pay_sorted, c->srm_off.as<int64_t>(), S, nclust, prob, c->srm_q.as<double>(),
-                           c->srm_n.as<int64_t>());
-        LDW_HIP(hipMemcpyAsync(q.data(), c->srm_q.p, cells * 16, hipMemcpyDeviceToHost, c->stream));
-        LDW_HIP(hipMemcpyAsync(n_out, c->srm_n.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
+        LDW_LAUNCH(k_sr_seg_offsets, dim3((S + 2 + 255) / 256), dim3(256), 0, c->stream, len_sorted, n, S, c->srm.off.as<int64_t>());
+        LDW_HIP(hipMemcpyAsync(c->srm.q.p, q.data(), cells * 16, hipMemcpyHostToDevice, c->stream));
+        LDW_LAUNCH(k_sr_select, dim3(S), dim3(SEL_NT), 0, c->stream, pay_sorted, c->srm.off.as<int64_t>(), S, nclust, prob, c->srm.q.as<double>(),
+                           c->srm.n.as<int64_t>());
+        LDW_HIP(hipMemcpyAsync(q.data(), c->srm.q.p, cells * 16, hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipMemcpyAsync(n_out, c->srm.n.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
-        for (size_t k = 0; k < cells; ++k) {
-            q_lo_out[k] = q[2 * k];
-            q_hi_out[k] = q[2 * k + 1];
-        }
+        split_q(q, cells, q_lo_out, q_hi_out);
         return LDW_OK;
     }
     if (int rc = quant_reserve_sorts(c, n, S, cells)) return rc;
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 65536);
-    LDW_LAUNCH(k_sr_tag, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(),
-                       c->sr_mi.as<double>(), n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, sr_dist, c->srm_pack.as<uint32_t>(), c->srm_key.as<uint64_t>());
+    LDW_LAUNCH(k_sr_tag, dim3(grid), dim3(256), 0, c->stream, sr_rows(c), c->srm.pack.as<uint32_t>(), c->srm.key.as<uint64_t>());
     if (int rc = quant_two_sorts(c, n, S, nclust, prob, nullptr, q, n_out, nullptr)) return rc;
-    for (size_t k = 0; k < cells; ++k) {
-        q_lo_out[k] = q[2 * k];
-        q_hi_out[k] = q[2 * k + 1];
-    }
+    split_q(q, cells, q_lo_out, q_hi_out);
     return LDW_OK;
 }
 
-// ARACNE pool of the context's short-range table: rows with a positive excess in some cluster and MI key >= min_key (R/computePairwiseMI.R:489-490);
-// needs the fitted decay on the device (upload_md) and the geometry of the last ldw_sr_len_quantiles call.  Sets c->n_pool.
-static int build_pool(ldw_ctx *c, unsigned long long min_key) {
-    const int64_t n = c->n_sr;
-    c->n_pool = 0;
-    if (n == 0) return LDW_OK;
-    if (int rc = c->srm_cnt.reserve(sizeof(SrCounters))) return rc;
-    SrCounters *d = c->srm_cnt.as<SrCounters>();
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, 16384);
-    {
-        const size_t floor_rows = (size_t)std::min<int64_t>(n, (int64_t)1 << 22);
-        if (int rc = c->pool_a.reserve(floor_rows * 4)) return rc;
-        if (int rc = c->pool_b.reserve(floor_rows * 4)) return rc;
-        if (int rc = c->pool_mi.reserve(floor_rows * 8)) return rc;
-    }
-    for (int pass = 0; pass < 2; ++pass) {
-        const int64_t cap = std::min<int64_t>((int64_t)(c->pool_a.cap / 4), std::min<int64_t>((int64_t)(c->pool_b.cap / 4), (int64_t)(c->pool_mi.cap / 8)));
-        SrCounters h2 = {0, 0, min_key};
-        LDW_HIP(hipMemcpyAsync(d, &h2, sizeof(h2), hipMemcpyHostToDevice, c->stream));
-        LDW_LAUNCH(k_sr_pool<1>, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n,
-                           c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist, c->srm_md.as<double>(), c->srm_S, d, c->pool_a.as<int32_t>(),
-                           c->pool_b.as<int32_t>(), c->pool_mi.as<double>(), cap);
-        SrCounters got;
-        LDW_HIP(hipMemcpyAsync(&got, d, sizeof(got), hipMemcpyDeviceToHost, c->stream));
-        LDW_HIP(hipStreamSynchronize(c->stream));
-        c->n_pool = (int64_t)got.n_pool;
-        if (c->n_pool <= cap) break;
-        LDW_REQUIRE(pass == 0, LDW_ERR_STATE, "short-range pool changed size between passes");
-        if (int rc = c->pool_a.reserve((size_t)c->n_pool * 4)) return rc;
-        if (int rc = c->pool_b.reserve((size_t)c->n_pool * 4)) return rc;
-        if (int rc = c->pool_mi.reserve((size_t)c->n_pool * 8)) return rc;
-    }
-    return LDW_OK;
-}
-
-static int upload_md(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, const char *who) {
-    LDW_REQUIRE(nclust == c->srm_nclust && S == c->srm_S, LDW_ERR_STATE, "%s: nclust/S differ from the last ldw_sr_len_quantiles call", who);
-    LDW_REQUIRE(mean_dist, LDW_ERR_ARG, "%s: null mean_dist", who);
-    if (int rc = c->srm_md.reserve((size_t)nclust * S * 8)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->srm_md.p, mean_dist, (size_t)nclust * S * 8, hipMemcpyHostToDevice, c->stream));
-    return LDW_OK;
-}
-
+// ---- excess statistics
 int ldw_sr_excess_stats(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, double *stats_out) {
     if (int rc = sr_ready(c, "ldw_sr_excess_stats")) return rc;
     if (int rc = upload_md(c, nclust, S, mean_dist, "ldw_sr_excess_stats")) return rc;
@@ -1089,24 +1102,50 @@ int ldw_sr_excess_stats(ldw_ctx *c, int nclust, int32_t S, const double *mean_di
     for (int k = 0; k < nclust * 5; ++k) stats_out[k] = 0.0;
     if (n == 0) return LDW_OK;
     const int grid = (int)std::min<int64_t>((n + 255) / 256, SRM_GRID);
-    const size_t pbytes = (size_t)grid * nclust * 5 * 8;
-    if (int rc = c->srm_part.reserve(pbytes)) return rc;
-    if (nclust <= 4 && getenv("LDW_SR_STATS_PEEL") == nullptr)
-        LDW_LAUNCH(k_sr_stats_small<4>, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n,
-                           c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist, c->srm_md.as<double>(), S, nclust, c->srm_part.as<double>(),
-                           (const int64_t *)nullptr, 0);
-    else
-        LDW_LAUNCH(k_sr_stats, dim3(grid), dim3(256), (size_t)4 * nclust * 5 * 8, c->stream, c->sr_a.as<int32_t>(),
-                       c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g,
-                       c->srm_sr_dist, c->srm_md.as<double>(), S, nclust, c->srm_part.as<double>(), (const int64_t *)nullptr, 0);
-    std::vector<double> part((size_t)grid * nclust * 5);
-    LDW_HIP(hipMemcpyAsync(part.data(), c->srm_part.p, pbytes, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipStreamSynchronize(c->stream));
+    std::vector<double> part;
+    if (int rc = launch_sr_stats(c, sr_rows(c), grid, nullptr, 0, part)) return rc;
     for (int b = 0; b < grid; ++b)   // fixed order: the result does not depend on scheduling
         for (int k = 0; k < nclust * 5; ++k) stats_out[k] += part[(size_t)b * nclust * 5 + k];
     return LDW_OK;
 }
 
+// r05: the same sums per reference block of the table (rows_per_block in table order): a block's sums are a function of its rows alone
+int ldw_sr_excess_stats_blocks(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, int64_t nblocks, const int64_t *rows_per_block,
+                               double *stats_out) {
+    if (int rc = sr_ready(c, "ldw_sr_excess_stats_blocks")) return rc;
+    if (int rc = upload_md(c, nclust, S, mean_dist, "ldw_sr_excess_stats_blocks")) return rc;
+    LDW_REQUIRE(nblocks >= 0 && (nblocks == 0 || (rows_per_block && stats_out)), LDW_ERR_ARG, "ldw_sr_excess_stats_blocks: null argument");
+    constexpr int STRIPS = 64;   // strips per block: fixed, so that a block's sums do not depend on which rank holds it
+    std::vector<int64_t> seg, which;
+    int64_t run = 0;
+    for (int64_t b = 0; b < nblocks; ++b) {
+        LDW_REQUIRE(rows_per_block[b] >= 0, LDW_ERR_ARG, "ldw_sr_excess_stats_blocks: negative row count");
+        if (rows_per_block[b] > 0) {
+            seg.push_back(run);
+            seg.push_back(run + rows_per_block[b]);
+            which.push_back(b);
+        }
+        run += rows_per_block[b];
+    }
+    LDW_REQUIRE(run == c->n_sr, LDW_ERR_ARG, "ldw_sr_excess_stats_blocks: the blocks hold %lld rows, the short-range table %lld", (long long)run, (long long)c->n_sr);
+    const size_t per = (size_t)nclust * 5;
+    for (size_t k = 0; k < (size_t)nblocks * per; ++k) stats_out[k] = 0.0;
+    const int64_t nb = (int64_t)which.size();
+    if (nb == 0) return LDW_OK;
+    LDW_REQUIRE(nb * STRIPS < (int64_t)1 << 30, LDW_ERR_SIZE, "ldw_sr_excess_stats_blocks: too many blocks");
+    if (int rc = c->srm.seg.reserve(seg.size() * 8)) return rc;
+    LDW_HIP(hipMemcpyAsync(c->srm.seg.p, seg.data(), seg.size() * 8, hipMemcpyHostToDevice, c->stream));
+    std::vector<double> part;
+    if (int rc = launch_sr_stats(c, sr_rows(c), (int)(nb * STRIPS), c->srm.seg.as<int64_t>(), STRIPS, part)) return rc;
+    for (int64_t k = 0; k < nb; ++k) {   // strips in order: fixed
+        double *o = stats_out + (size_t)which[(size_t)k] * per;
+        for (int j = 0; j < STRIPS; ++j)
+            for (size_t t = 0; t < per; ++t) o[t] += part[((size_t)k * STRIPS + (size_t)j) * per + t];
+    }
+    return LDW_OK;
+}
+
+// ---- p-values and pool
 int ldw_sr_pvalues(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, const double *shape, double srp_cutoff,
                    int64_t *n_red_out, int64_t *n_pool_out, double *min_mi_out) {
     if (int rc = sr_ready(c, "ldw_sr_pvalues")) return rc;
@@ -1116,89 +1155,75 @@ int ldw_sr_pvalues(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, c
         LDW_REQUIRE(shape[3 * k] > 0 && shape[3 * k + 1] > 0 && std::isfinite(shape[3 * k + 2]), LDW_ERR_ARG,
                     "ldw_sr_pvalues: cluster %d has an invalid beta shape", k + 1);
     const int64_t n = c->n_sr;
-    c->n_red = c->n_pool = 0;
-    c->red_from_lr = false;
-    c->ar_valid = false;
+    KeptLinks &K = c->kept;
+    K.invalidate();
+    K.from_lr = false;
     *n_red_out = 0;
     if (n_pool_out) *n_pool_out = 0;
     if (min_mi_out) *min_mi_out = std::nan("");
     if (n == 0) return LDW_OK;
-    if (int rc = c->srm_shape.reserve((size_t)nclust * 32)) return rc;
-    if (int rc = c->srm_cnt.reserve(sizeof(SrCounters))) return rc;
-    LDW_HIP(hipMemcpyAsync(c->srm_shape.p, shape, (size_t)nclust * 24, hipMemcpyHostToDevice, c->stream));
+    if (int rc = c->srm.shape.reserve((size_t)nclust * 32)) return rc;
+    if (int rc = c->srm.cnt.reserve(sizeof(SrCounters))) return rc;
+    LDW_HIP(hipMemcpyAsync(c->srm.shape.p, shape, (size_t)nclust * 24, hipMemcpyHostToDevice, c->stream));
     SrCounters h = {0, 0, ~0ull};
-    SrCounters *d = c->srm_cnt.as<SrCounters>();
+    SrCounters *d = c->srm.cnt.as<SrCounters>();
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 16384);
-    const int32_t *sa = c->sr_a.as<int32_t>(), *sb = c->sr_b.as<int32_t>();
-    const double *smi = c->sr_mi.as<double>();
-    const int32_t *POS = c->POS.as<int32_t>(), *paint = c->paint.as<int32_t>();
     // pass 1 writes into whatever capacity is there; a second pass runs only if it was too small.  r04: a floor of 4 M rows (144 MB in all)
     // under both outputs, so that the FIRST job of a context does not pay the two kernels twice (C5: 1.5 M rows kept of 2.25e9, 50 ms per pass)
-    {
-        const size_t floor_rows = (size_t)std::min<int64_t>(n, (int64_t)1 << 22);
-        if (int rc = c->red_row.reserve(floor_rows * 8)) return rc;
-        if (int rc = c->red_meta.reserve(floor_rows * 4)) return rc;
-        if (int rc = c->red_srp.reserve(floor_rows * 8)) return rc;
-        if (int rc = c->pool_a.reserve(floor_rows * 4)) return rc;
-        if (int rc = c->pool_b.reserve(floor_rows * 4)) return rc;
-        if (int rc = c->pool_mi.reserve(floor_rows * 8)) return rc;
-    }
-    // (srm_shape: 3 doubles per cluster, the crossings behind them)
+    const size_t floor_rows = (size_t)std::min<int64_t>(n, (int64_t)1 << 22);
+    if (int rc = K.reserve_red(floor_rows)) return rc;
+    if (int rc = K.reserve_pool(floor_rows)) return rc;
+    // (srm.shape: 3 doubles per cluster, the crossings behind them)
     double *d_dstar = nullptr;
     if (getenv("LDW_SR_PVAL_ALL") == nullptr) {
-        d_dstar = c->srm_shape.as<double>() + (size_t)nclust * 3;
-        LDW_LAUNCH(k_sr_dstar, dim3((nclust + 63) / 64), dim3(64), 0, c->stream, c->srm_shape.as<double>(), nclust, srp_cutoff, d_dstar);
+        d_dstar = c->srm.shape.as<double>() + (size_t)nclust * 3;
+        LDW_LAUNCH(k_sr_dstar, dim3((nclust + 63) / 64), dim3(64), 0, c->stream, c->srm.shape.as<double>(), nclust, srp_cutoff, d_dstar);
     }
     for (int pass = 0; pass < 2; ++pass) {
-        const int64_t cap = (int64_t)(c->red_row.cap / 8);
+        const int64_t cap = K.red_capacity();
         LDW_HIP(hipMemcpyAsync(d, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-        LDW_LAUNCH(k_sr_pval<1>, dim3(grid), dim3(256), 0, c->stream, sa, sb, smi, n, POS, paint, c->g, c->srm_sr_dist,
-                           c->srm_md.as<double>(), S, c->srm_shape.as<double>(), srp_cutoff, d, c->red_row.as<int64_t>(),
-                           c->red_meta.as<uint32_t>(), c->red_srp.as<double>(),
-                           std::min<int64_t>(cap, std::min<int64_t>((int64_t)(c->red_meta.cap / 4), (int64_t)(c->red_srp.cap / 8))), d_dstar);
+        LDW_LAUNCH(k_sr_pval, dim3(grid), dim3(256), 0, c->stream, sr_rows(c), c->srm.md.as<double>(), S, c->srm.shape.as<double>(), srp_cutoff, d,
+                   K.row.as<int64_t>(), K.meta.as<uint32_t>(), K.srp.as<double>(), cap, d_dstar);
         SrCounters got;
         LDW_HIP(hipMemcpyAsync(&got, d, sizeof(got), hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
-        c->n_red = (int64_t)got.n_red;
+        K.n_red = (int64_t)got.n_red;
         h.min_key = got.min_key;
-        const int64_t have = std::min<int64_t>(cap, std::min<int64_t>((int64_t)(c->red_meta.cap / 4), (int64_t)(c->red_srp.cap / 8)));
-        if (c->n_red <= have) break;
+        if (K.n_red <= cap) break;
         LDW_REQUIRE(pass == 0, LDW_ERR_STATE, "ldw_sr_pvalues: reduced set changed size between passes");
-        if (int rc = c->red_row.reserve((size_t)c->n_red * 8)) return rc;
-        if (int rc = c->red_meta.reserve((size_t)c->n_red * 4)) return rc;
-        if (int rc = c->red_srp.reserve((size_t)c->n_red * 8)) return rc;
+        if (int rc = K.reserve_red((size_t)K.n_red)) return rc;
         h.min_key = ~0ull;
     }
-    *n_red_out = c->n_red;
-    if (c->n_red == 0) return LDW_OK;
+    *n_red_out = K.n_red;
+    if (K.n_red == 0) return LDW_OK;
     if (min_mi_out) *min_mi_out = key_f64(h.min_key);
     if (!n_pool_out) return LDW_OK;
     if (int rc = build_pool(c, h.min_key)) return rc;
-    *n_pool_out = c->n_pool;
+    *n_pool_out = K.n_pool;
     return LDW_OK;
 }
 
 int ldw_sr_reduced_fetch(ldw_ctx *c, int64_t capacity, int64_t *row_out, int32_t *a_out, int32_t *b_out, double *MI_out,
                          int32_t *clust_c_out, int32_t *first_clust_out, uint8_t *dup_out, double *srp_out) {
     if (int rc = check_gpu(c)) return rc;
-    const int64_t n = c->n_red;
+    const int64_t n = c->kept.n_red;
     LDW_REQUIRE(capacity >= n, LDW_ERR_SIZE, "ldw_sr_reduced_fetch: capacity %lld < %lld rows", (long long)capacity, (long long)n);
     if (n == 0) return LDW_OK;
     LDW_REQUIRE(row_out && a_out && b_out && MI_out && clust_c_out && first_clust_out && dup_out && srp_out, LDW_ERR_ARG,
                 "ldw_sr_reduced_fetch: null output");
-    LDW_REQUIRE(!c->red_from_lr, LDW_ERR_STATE, "ldw_sr_reduced_fetch: the reduced set is the long-range one (ldw_lr_tukey ran last)");
+    LDW_REQUIRE(!c->kept.from_lr, LDW_ERR_STATE, "ldw_sr_reduced_fetch: the reduced set is the long-range one (ldw_lr_tukey ran last)");
     std::vector<uint32_t> meta((size_t)n);
     if (int rc = c->scratch.reserve((size_t)n * 16)) return rc;
     double *gmi = c->scratch.as<double>();
     int32_t *ga = reinterpret_cast<int32_t *>(gmi + n), *gb = ga + n;
-    LDW_LAUNCH(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), n,
+    LDW_LAUNCH(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->kept.row.as<int64_t>(), n,
                        c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), ga, gb, gmi);
     LDW_HIP(hipMemcpyAsync(a_out, ga, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(b_out, gb, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(MI_out, gmi, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipMemcpyAsync(row_out, c->red_row.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipMemcpyAsync(meta.data(), c->red_meta.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipMemcpyAsync(srp_out, c->red_srp.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(row_out, c->kept.row.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(meta.data(), c->kept.meta.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(srp_out, c->kept.srp.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < n; ++i) {
         clust_c_out[i] = (int32_t)(meta[i] & 0xFF);
@@ -1210,13 +1235,13 @@ int ldw_sr_reduced_fetch(ldw_ctx *c, int64_t capacity, int64_t *row_out, int32_t
 
 int ldw_sr_pool_fetch(ldw_ctx *c, int64_t capacity, int32_t *a_out, int32_t *b_out, double *MI_out) {
     if (int rc = check_gpu(c)) return rc;
-    const int64_t n = c->n_pool;
+    const int64_t n = c->kept.n_pool;
     LDW_REQUIRE(capacity >= n, LDW_ERR_SIZE, "ldw_sr_pool_fetch: capacity %lld < %lld rows", (long long)capacity, (long long)n);
     if (n == 0) return LDW_OK;
     LDW_REQUIRE(a_out && b_out && MI_out, LDW_ERR_ARG, "ldw_sr_pool_fetch: null output");
-    LDW_HIP(hipMemcpyAsync(a_out, c->pool_a.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipMemcpyAsync(b_out, c->pool_b.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipMemcpyAsync(MI_out, c->pool_mi.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(a_out, c->kept.pool_a.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(b_out, c->kept.pool_b.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(MI_out, c->kept.pool_mi.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     return LDW_OK;
 }
@@ -1224,27 +1249,40 @@ int ldw_sr_pool_fetch(ldw_ctx *c, int64_t capacity, int32_t *a_out, int32_t *b_o
 // rows of the long-range table kept by ldw_lr_tukey, in table order
 int ldw_lr_reduced_fetch(ldw_ctx *c, int64_t capacity, int64_t *row_out, int32_t *a_out, int32_t *b_out, double *MI_out) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->red_from_lr, LDW_ERR_STATE, "ldw_lr_reduced_fetch: call ldw_lr_tukey first");
-    const int64_t n = c->n_red;
+    LDW_REQUIRE(c->kept.from_lr, LDW_ERR_STATE, "ldw_lr_reduced_fetch: call ldw_lr_tukey first");
+    const int64_t n = c->kept.n_red;
     LDW_REQUIRE(capacity >= n, LDW_ERR_SIZE, "ldw_lr_reduced_fetch: capacity %lld < %lld rows", (long long)capacity, (long long)n);
     if (n == 0) return LDW_OK;
     LDW_REQUIRE(row_out && a_out && b_out && MI_out, LDW_ERR_ARG, "ldw_lr_reduced_fetch: null output");
     if (int rc = c->scratch.reserve((size_t)n * 16)) return rc;
     double *gmi = c->scratch.as<double>();
     int32_t *ga = reinterpret_cast<int32_t *>(gmi + n), *gb = ga + n;
-    LDW_LAUNCH(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), n,
+    LDW_LAUNCH(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->kept.row.as<int64_t>(), n,
                        c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>(), ga, gb, gmi);
     LDW_HIP(hipMemcpyAsync(a_out, ga, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(b_out, gb, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(MI_out, gmi, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipMemcpyAsync(row_out, c->red_row.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(row_out, c->kept.row.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     return LDW_OK;
 }
 
+int ldw_sr_pool_build(ldw_ctx *c, double min_mi, int64_t *n_pool_out) {
+    if (int rc = sr_ready(c, "ldw_sr_pool_build")) return rc;
+    LDW_REQUIRE(n_pool_out, LDW_ERR_ARG, "ldw_sr_pool_build: null output");
+    LDW_REQUIRE(c->srm.S > 0 && c->srm.md.p, LDW_ERR_STATE, "ldw_sr_pool_build: call ldw_sr_pvalues first (the fitted decay is not on the device)");
+    *n_pool_out = 0;
+    c->kept.n_pool = 0;
+    if (std::isnan(min_mi)) return LDW_OK;   // nothing was kept anywhere: no pool
+    if (int rc = build_pool(c, (unsigned long long)f64_key(min_mi))) return rc;
+    *n_pool_out = c->kept.n_pool;
+    return LDW_OK;
+}
+
+// ---- ARACNE
 int ldw_aracne_device(ldw_ctx *c, int64_t capacity, uint8_t *flags_out) {
     if (int rc = check_gpu(c)) return rc;
-    const int64_t nr = c->n_red, np = c->n_pool;
+    const int64_t nr = c->kept.n_red, np = c->kept.n_pool;
     LDW_REQUIRE(capacity >= nr, LDW_ERR_SIZE, "ldw_aracne_device: capacity %lld < %lld links", (long long)capacity, (long long)nr);
     if (nr == 0) return LDW_OK;
     LDW_REQUIRE(flags_out, LDW_ERR_ARG, "ldw_aracne_device: null output");
@@ -1254,31 +1292,31 @@ int ldw_aracne_device(ldw_ctx *c, int64_t capacity, uint8_t *flags_out) {
     const int32_t *d_slot = nullptr;
     int64_t n_nodes = 0;
     if (int rc = pos_slots(c, &d_slot, &n_nodes)) return rc;
-    if (int rc = c->ar_key.reserve((size_t)n2 * 8)) return rc;
-    if (int rc = c->ar_key2.reserve((size_t)n2 * 8)) return rc;
-    if (int rc = c->ar_val.reserve((size_t)n2 * 8)) return rc;
-    if (int rc = c->ar_val2.reserve((size_t)n2 * 8)) return rc;
-    if (int rc = c->ar_off.reserve((size_t)(n_nodes + 2) * 8)) return rc;
-    if (int rc = c->ar_flags.reserve((size_t)nr)) return rc;
-    LDW_LAUNCH(k_ar_edges, grid_of(np), dim3(256), 0, c->stream, c->pool_a.as<int32_t>(), c->pool_b.as<int32_t>(),
-                       c->pool_mi.as<double>(), np, c->ar_key.as<uint64_t>(), c->ar_val.as<double>(), d_slot);
+    if (int rc = c->kept.ar_key.reserve((size_t)n2 * 8)) return rc;
+    if (int rc = c->kept.ar_key2.reserve((size_t)n2 * 8)) return rc;
+    if (int rc = c->kept.ar_val.reserve((size_t)n2 * 8)) return rc;
+    if (int rc = c->kept.ar_val2.reserve((size_t)n2 * 8)) return rc;
+    if (int rc = c->kept.ar_off.reserve((size_t)(n_nodes + 2) * 8)) return rc;
+    if (int rc = c->kept.ar_flags.reserve((size_t)nr)) return rc;
+    LDW_LAUNCH(k_ar_edges, grid_of(np), dim3(256), 0, c->stream, c->kept.pool_a.as<int32_t>(), c->kept.pool_b.as<int32_t>(),
+                       c->kept.pool_mi.as<double>(), np, c->kept.ar_key.as<uint64_t>(), c->kept.ar_val.as<double>(), d_slot);
     size_t tb = 0;
     LDW_HIP((prim_sort_pairs_bytes<uint64_t, double>((size_t)n2, 0, 64, c->stream, &tb)));
     if (int rc = c->scratch.reserve(tb)) return rc;
     tb = c->scratch.cap;
-    LDW_HIP(prim_sort_pairs(c->scratch.p, tb, c->ar_key.as<uint64_t>(), c->ar_key2.as<uint64_t>(),
-                                               c->ar_val.as<double>(), c->ar_val2.as<double>(), n2, 0, 64, c->stream));
-    LDW_LAUNCH(k_ar_offsets, dim3((unsigned)((n_nodes + 1 + 255) / 256)), dim3(256), 0, c->stream, c->ar_key2.as<uint64_t>(), n2, n_nodes,
-                       c->ar_off.as<int64_t>());
+    LDW_HIP(prim_sort_pairs(c->scratch.p, tb, c->kept.ar_key.as<uint64_t>(), c->kept.ar_key2.as<uint64_t>(),
+                                               c->kept.ar_val.as<double>(), c->kept.ar_val2.as<double>(), n2, 0, 64, c->stream));
+    LDW_LAUNCH(k_ar_offsets, dim3((unsigned)((n_nodes + 1 + 255) / 256)), dim3(256), 0, c->stream, c->kept.ar_key2.as<uint64_t>(), n2, n_nodes,
+                       c->kept.ar_off.as<int64_t>());
     // the links to check are rows of the short-range table (after ldw_sr_pvalues) or of the long-range one (after ldw_lr_tukey)
-    const int32_t *ta = (c->red_from_lr ? c->lr_a : c->sr_a).as<int32_t>(), *tb2 = (c->red_from_lr ? c->lr_b : c->sr_b).as<int32_t>();
-    const double *tmi = (c->red_from_lr ? c->lr_mi : c->sr_mi).as<double>();
-    LDW_LAUNCH(k_ar_check, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), nr,
-                       ta, tb2, tmi, c->ar_key2.as<uint64_t>(),
-                       c->ar_val2.as<double>(), c->ar_off.as<int64_t>(), c->ar_flags.as<uint8_t>(), d_slot);
-    LDW_HIP(hipMemcpyAsync(flags_out, c->ar_flags.p, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+    const int32_t *ta = (c->kept.from_lr ? c->lr_a : c->sr_a).as<int32_t>(), *tb2 = (c->kept.from_lr ? c->lr_b : c->sr_b).as<int32_t>();
+    const double *tmi = (c->kept.from_lr ? c->lr_mi : c->sr_mi).as<double>();
+    LDW_LAUNCH(k_ar_check, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, c->stream, c->kept.row.as<int64_t>(), nr,
+                       ta, tb2, tmi, c->kept.ar_key2.as<uint64_t>(),
+                       c->kept.ar_val2.as<double>(), c->kept.ar_off.as<int64_t>(), c->kept.ar_flags.as<uint8_t>(), d_slot);
+    LDW_HIP(hipMemcpyAsync(flags_out, c->kept.ar_flags.p, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
-    c->ar_valid = true;   // (ldw_plot_links may read the flags where they lie)
+    c->kept.ar_valid = true;   // (ldw_plot_links may read the flags where they lie)
     return LDW_OK;
 }
 
@@ -1287,23 +1325,21 @@ int ldw_aracne_device(ldw_ctx *c, int64_t capacity, uint8_t *flags_out) {
 int ldw_sr_tail_extract(ldw_ctx *c, int nclust, int32_t S, const double *lower, int64_t *cnt_out, double *mi_out, int64_t capacity, int on_device,
                         int64_t *n_out) {
     if (int rc = sr_ready(c, "ldw_sr_tail_extract")) return rc;
-    LDW_REQUIRE(nclust == c->srm_nclust && S == c->srm_S && nclust >= 1 && S >= 1, LDW_ERR_STATE,
+    LDW_REQUIRE(c->srm.same_geometry(nclust, S) && nclust >= 1 && S >= 1, LDW_ERR_STATE,
                 "ldw_sr_tail_extract: nclust/S differ from the last ldw_sr_len_quantiles call");
     LDW_REQUIRE(lower && cnt_out && n_out, LDW_ERR_ARG, "ldw_sr_tail_extract: null argument");
     const int64_t n = c->n_sr, G = (int64_t)nclust * S;
     *n_out = 0;
     for (int64_t k = 0; k < G; ++k) cnt_out[k] = 0;
     if (n == 0) return LDW_OK;
-    if (int rc = c->srd_lower.reserve((size_t)G * 8)) return rc;
-    if (int rc = c->srd_cur.reserve((size_t)G * 8)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->srd_lower.p, lower, (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemsetAsync(c->srd_cur.p, 0, (size_t)G * 8, c->stream));
+    if (int rc = c->srm.lower.reserve((size_t)G * 8)) return rc;
+    if (int rc = c->srm.cur.reserve((size_t)G * 8)) return rc;
+    LDW_HIP(hipMemcpyAsync(c->srm.lower.p, lower, (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemsetAsync(c->srm.cur.p, 0, (size_t)G * 8, c->stream));
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 16384);
-    const int32_t *sa = c->sr_a.as<int32_t>(), *sb = c->sr_b.as<int32_t>();
-    const double *smi = c->sr_mi.as<double>();
-    LDW_LAUNCH(k_sr_tail<0>, dim3(grid), dim3(256), 0, c->stream, sa, sb, smi, n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist,
-                       c->srd_lower.as<double>(), S, nclust, c->srd_cur.as<unsigned long long>(), (double *)nullptr);
-    LDW_HIP(hipMemcpyAsync(cnt_out, c->srd_cur.p, (size_t)G * 8, hipMemcpyDeviceToHost, c->stream));
+    const SrRowsView v = sr_rows(c);
+    LDW_LAUNCH(k_sr_tail<0>, dim3(grid), dim3(256), 0, c->stream, v, c->srm.lower.as<double>(), S, nclust, c->srm.cur.as<unsigned long long>(), (double *)nullptr);
+    LDW_HIP(hipMemcpyAsync(cnt_out, c->srm.cur.p, (size_t)G * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     int64_t total = 0;
     for (int64_t k = 0; k < G; ++k) total += cnt_out[k];
@@ -1316,14 +1352,13 @@ int ldw_sr_tail_extract(ldw_ctx *c, int nclust, int32_t S, const double *lower, 
         first[(size_t)k] = run;
         run += cnt_out[k];
     }
-    LDW_HIP(hipMemcpyAsync(c->srd_cur.p, first.data(), (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->srm.cur.p, first.data(), (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
     double *d_out = mi_out;
     if (!on_device) {
-        if (int rc = c->srd_out.reserve((size_t)total * 8)) return rc;
-        d_out = c->srd_out.as<double>();
+        if (int rc = c->srm.out.reserve((size_t)total * 8)) return rc;
+        d_out = c->srm.out.as<double>();
     }
-    LDW_LAUNCH(k_sr_tail<1>, dim3(grid), dim3(256), 0, c->stream, sa, sb, smi, n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist,
-                       c->srd_lower.as<double>(), S, nclust, c->srd_cur.as<unsigned long long>(), d_out);
+    LDW_LAUNCH(k_sr_tail<1>, dim3(grid), dim3(256), 0, c->stream, v, c->srm.lower.as<double>(), S, nclust, c->srm.cur.as<unsigned long long>(), d_out);
     if (!on_device) LDW_HIP(hipMemcpyAsync(mi_out, d_out, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));   // (`first` is read by the copy above)
     return LDW_OK;
@@ -1356,11 +1391,11 @@ int ldw_sr_quantiles_merge(ldw_ctx *c, int nclust, int32_t S, double prob, int n
     } else {
         LDW_REQUIRE(m < (int64_t)0x7FFFFFFFll * 4, LDW_ERR_SIZE, "ldw_sr_quantiles_merge: too many candidates");
         if (int rc = quant_reserve_sorts(c, m, S, cells)) return rc;
-        if (int rc = c->srd_lower.reserve((size_t)G * 8)) return rc;
-        if (int rc = c->srd_seg.reserve((size_t)n_src * (size_t)(G + 1) * 8)) return rc;
+        if (int rc = c->srm.lower.reserve((size_t)G * 8)) return rc;
+        if (int rc = c->srm.seg.reserve((size_t)n_src * (size_t)(G + 1) * 8)) return rc;
         if (!on_device)
-            if (int rc = c->srd_out.reserve((size_t)m * 8)) return rc;
-        LDW_HIP(hipMemcpyAsync(c->srd_lower.p, n_total, (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+            if (int rc = c->srm.out.reserve((size_t)m * 8)) return rc;
+        LDW_HIP(hipMemcpyAsync(c->srm.lower.p, n_total, (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
         std::vector<int64_t> goff((size_t)n_src * (size_t)(G + 1));
         int64_t base = 0;
         for (int r = 0; r < n_src; ++r) {
@@ -1369,89 +1404,26 @@ int ldw_sr_quantiles_merge(ldw_ctx *c, int nclust, int32_t S, double prob, int n
             for (int64_t k = 0; k < G; ++k) go[k + 1] = go[k] + cnt_src[r][k];
             const int64_t mr = m_src[(size_t)r];
             if (mr == 0) continue;
-            int64_t *d_go = c->srd_seg.as<int64_t>() + (size_t)r * (size_t)(G + 1);
+            int64_t *d_go = c->srm.seg.as<int64_t>() + (size_t)r * (size_t)(G + 1);
             LDW_HIP(hipMemcpyAsync(d_go, go, (size_t)(G + 1) * 8, hipMemcpyHostToDevice, c->stream));
             const double *d_mi = mi_src[r];
             if (!on_device) {
-                LDW_HIP(hipMemcpyAsync(c->srd_out.as<double>() + base, mi_src[r], (size_t)mr * 8, hipMemcpyHostToDevice, c->stream));
-                d_mi = c->srd_out.as<double>() + base;
+                LDW_HIP(hipMemcpyAsync(c->srm.out.as<double>() + base, mi_src[r], (size_t)mr * 8, hipMemcpyHostToDevice, c->stream));
+                d_mi = c->srm.out.as<double>() + base;
             }
             LDW_LAUNCH(k_tail_unpack, dim3((unsigned)std::min<int64_t>((mr + 255) / 256, 16384)), dim3(256), 0, c->stream, d_mi, mr, d_go, (int)G, nclust,
-                               base, c->srm_pack.as<uint32_t>(), c->srm_key.as<uint64_t>());
+                               base, c->srm.pack.as<uint32_t>(), c->srm.key.as<uint64_t>());
             base += mr;
         }
-        if (int rc = quant_two_sorts(c, m, S, nclust, prob, c->srd_lower.as<int64_t>(), q, nullptr, &viol)) return rc;   // (synchronises: goff may go)
+        if (int rc = quant_two_sorts(c, m, S, nclust, prob, c->srm.lower.as<int64_t>(), q, nullptr, &viol)) return rc;   // (synchronises: goff may go)
     }
-    for (size_t k = 0; k < cells; ++k) {
-        q_lo_out[k] = q[2 * k];
-        q_hi_out[k] = q[2 * k + 1];
-    }
+    split_q(q, cells, q_lo_out, q_hi_out);
     if (violations_out) *violations_out = (int64_t)viol;
     LDW_REQUIRE(viol == 0 || violations_out, LDW_ERR_STATE, "ldw_sr_quantiles_merge: %u groups whose order statistic lies below the candidates sent", viol);
     return LDW_OK;
 }
 
-int ldw_sr_excess_stats_blocks(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, int64_t nblocks, const int64_t *rows_per_block,
-                               double *stats_out) {
-    if (int rc = sr_ready(c, "ldw_sr_excess_stats_blocks")) return rc;
-    if (int rc = upload_md(c, nclust, S, mean_dist, "ldw_sr_excess_stats_blocks")) return rc;
-    LDW_REQUIRE(nblocks >= 0 && (nblocks == 0 || (rows_per_block && stats_out)), LDW_ERR_ARG, "ldw_sr_excess_stats_blocks: null argument");
-    constexpr int STRIPS = 64;   // strips per block: fixed, so that a block's sums do not depend on which rank holds it
-    std::vector<int64_t> seg;
-    std::vector<int64_t> which;
-    int64_t run = 0;
-    for (int64_t b = 0; b < nblocks; ++b) {
-        LDW_REQUIRE(rows_per_block[b] >= 0, LDW_ERR_ARG, "ldw_sr_excess_stats_blocks: negative row count");
-        if (rows_per_block[b] > 0) {
-            seg.push_back(run);
-            seg.push_back(run + rows_per_block[b]);
-            which.push_back(b);
-        }
-        run += rows_per_block[b];
-    }
-    LDW_REQUIRE(run == c->n_sr, LDW_ERR_ARG, "ldw_sr_excess_stats_blocks: the blocks hold %lld rows, the short-range table %lld", (long long)run, (long long)c->n_sr);
-    const size_t per = (size_t)nclust * 5;
-    for (size_t k = 0; k < (size_t)nblocks * per; ++k) stats_out[k] = 0.0;
-    const int64_t nb = (int64_t)which.size();
-    if (nb == 0) return LDW_OK;
-    LDW_REQUIRE(nb * STRIPS < (int64_t)1 << 30, LDW_ERR_SIZE, "ldw_sr_excess_stats_blocks: too many blocks");
-    const int grid = (int)(nb * STRIPS);
-    const size_t pbytes = (size_t)grid * per * 8;
-    if (int rc = c->srm_part.reserve(pbytes)) return rc;
-    if (int rc = c->srd_seg.reserve(seg.size() * 8)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->srd_seg.p, seg.data(), seg.size() * 8, hipMemcpyHostToDevice, c->stream));
-    const int64_t n = c->n_sr;
-    if (nclust <= 4 && getenv("LDW_SR_STATS_PEEL") == nullptr)
-        LDW_LAUNCH(k_sr_stats_small<4>, dim3(grid), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), n,
-                           c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist, c->srm_md.as<double>(), S, nclust, c->srm_part.as<double>(),
-                           c->srd_seg.as<int64_t>(), STRIPS);
-    else
-        LDW_LAUNCH(k_sr_stats, dim3(grid), dim3(256), (size_t)4 * nclust * 5 * 8, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(),
-                           c->sr_mi.as<double>(), n, c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->g, c->srm_sr_dist, c->srm_md.as<double>(), S, nclust,
-                           c->srm_part.as<double>(), c->srd_seg.as<int64_t>(), STRIPS);
-    std::vector<double> part((size_t)grid * per);
-    LDW_HIP(hipMemcpyAsync(part.data(), c->srm_part.p, pbytes, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipStreamSynchronize(c->stream));
-    for (int64_t k = 0; k < nb; ++k) {   // strips in order: fixed
-        double *o = stats_out + (size_t)which[(size_t)k] * per;
-        for (int j = 0; j < STRIPS; ++j)
-            for (size_t t = 0; t < per; ++t) o[t] += part[((size_t)k * STRIPS + (size_t)j) * per + t];
-    }
-    return LDW_OK;
-}
-
-int ldw_sr_pool_build(ldw_ctx *c, double min_mi, int64_t *n_pool_out) {
-    if (int rc = sr_ready(c, "ldw_sr_pool_build")) return rc;
-    LDW_REQUIRE(n_pool_out, LDW_ERR_ARG, "ldw_sr_pool_build: null output");
-    LDW_REQUIRE(c->srm_S > 0 && c->srm_md.p, LDW_ERR_STATE, "ldw_sr_pool_build: call ldw_sr_pvalues first (the fitted decay is not on the device)");
-    *n_pool_out = 0;
-    c->n_pool = 0;
-    if (std::isnan(min_mi)) return LDW_OK;   // nothing was kept anywhere: no pool
-    if (int rc = build_pool(c, (unsigned long long)f64_key(min_mi))) return rc;
-    *n_pool_out = c->n_pool;
-    return LDW_OK;
-}
-
+// ---- import
 int ldw_sr_reduced_import(ldw_ctx *c, int64_t n_red, const int32_t *a, const int32_t *b, const double *MI, int64_t n_pool, const int32_t *pool_a,
                           const int32_t *pool_b, const double *pool_MI) {
     return ldw::reduced_import_full(c, n_red, a, b, MI, nullptr, nullptr, n_pool, pool_a, pool_b, pool_MI);
@@ -1471,30 +1443,24 @@ int reduced_import_full(ldw_ctx *c, int64_t n_red, const int32_t *a, const int32
         LDW_REQUIRE(pool_a[i] >= 0 && pool_a[i] < c->L && pool_b[i] >= 0 && pool_b[i] < c->L, LDW_ERR_ARG,
                     "ldw_sr_reduced_import: pool link %lld has a SNP index outside 0..L-1", (long long)i);
     if (int rc = ldw_links_import(c, 0, a, b, MI, n_red, 0)) return rc;   // the kept links ARE the short-range table now (rows 0..n_red-1)
-    c->red_from_lr = false;
+    c->kept.from_lr = false;
     const size_t nr = (size_t)std::max<int64_t>(n_red, 1), np = (size_t)std::max<int64_t>(n_pool, 1);
-    if (int rc = c->red_row.reserve(nr * 8)) return rc;
-    if (int rc = c->red_meta.reserve(nr * 4)) return rc;
-    if (int rc = c->red_srp.reserve(nr * 8)) return rc;
-    if (int rc = c->pool_a.reserve(np * 4)) return rc;
-    if (int rc = c->pool_b.reserve(np * 4)) return rc;
-    if (int rc = c->pool_mi.reserve(np * 8)) return rc;
-    if (meta && n_red > 0) LDW_HIP(hipMemcpyAsync(c->red_meta.p, meta, (size_t)n_red * 4, hipMemcpyHostToDevice, c->stream));
-    else LDW_HIP(hipMemsetAsync(c->red_meta.p, 0, nr * 4, c->stream));
-    if (srp && n_red > 0) LDW_HIP(hipMemcpyAsync(c->red_srp.p, srp, (size_t)n_red * 8, hipMemcpyHostToDevice, c->stream));
-    else LDW_HIP(hipMemsetAsync(c->red_srp.p, 0, nr * 8, c->stream));
+    if (int rc = c->kept.reserve_red(nr)) return rc;
+    if (int rc = c->kept.reserve_pool(np)) return rc;
+    if (meta && n_red > 0) LDW_HIP(hipMemcpyAsync(c->kept.meta.p, meta, (size_t)n_red * 4, hipMemcpyHostToDevice, c->stream));
+    else LDW_HIP(hipMemsetAsync(c->kept.meta.p, 0, nr * 4, c->stream));
+    if (srp && n_red > 0) LDW_HIP(hipMemcpyAsync(c->kept.srp.p, srp, (size_t)n_red * 8, hipMemcpyHostToDevice, c->stream));
+    else LDW_HIP(hipMemsetAsync(c->kept.srp.p, 0, nr * 8, c->stream));
     if (n_red > 0) {
-        LDW_LAUNCH(k_iota64, dim3((unsigned)((n_red + 255) / 256)), dim3(256), 0, c->stream, c->red_row.as<int64_t>(), n_red);
+        LDW_LAUNCH(k_iota64, dim3((unsigned)((n_red + 255) / 256)), dim3(256), 0, c->stream, c->kept.row.as<int64_t>(), n_red);
     }
     if (n_pool > 0) {
-        LDW_HIP(hipMemcpyAsync(c->pool_a.p, pool_a, (size_t)n_pool * 4, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(c->pool_b.p, pool_b, (size_t)n_pool * 4, hipMemcpyHostToDevice, c->stream));
-        LDW_HIP(hipMemcpyAsync(c->pool_mi.p, pool_MI, (size_t)n_pool * 8, hipMemcpyHostToDevice, c->stream));
+        LDW_HIP(hipMemcpyAsync(c->kept.pool_a.p, pool_a, (size_t)n_pool * 4, hipMemcpyHostToDevice, c->stream));
+        LDW_HIP(hipMemcpyAsync(c->kept.pool_b.p, pool_b, (size_t)n_pool * 4, hipMemcpyHostToDevice, c->stream));
+        LDW_HIP(hipMemcpyAsync(c->kept.pool_mi.p, pool_MI, (size_t)n_pool * 8, hipMemcpyHostToDevice, c->stream));
     }
     LDW_HIP(hipStreamSynchronize(c->stream));
-    c->n_red = n_red;
-    c->n_pool = n_pool;
-    c->ar_valid = false;
+    c->kept.adopt(n_red, n_pool, false);
     return LDW_OK;
 }
 

@@ -723,6 +723,31 @@ def test_stats_blocks_with_empty_and_one_row_blocks(engine):
 
 
 @pytest.mark.gpu
+def test_stats_blocks_through_the_peeling_kernel_at_a_small_cluster_count(engine):
+    """ldw_sr_excess_stats_blocks at nclust <= 4 under LDW_SR_STATS_PEEL: the peeling k_sr_stats over segments cut into strips, where
+    k_sr_stats_small is the default.  Blocks of 0, 1 and 70 rows (fewer rows than strips x 2: empty strips), each block against numpy."""
+    rng = np.random.default_rng(12)
+    L, nclust = 400, 3
+    POS = np.sort(rng.choice(np.arange(1, 3000), L, replace=False))
+    paint = rng.integers(1, nclust + 1, L).astype(np.int32)
+    a, b, mi = _decay_table(rng, POS, paint, 30_000, 200.0, float(G), w=40)
+    md = _md(nclust, 199, 150, level=0.03)
+    blocks = np.array([0, 1, 5000, 0, 70, len(a) - 5071])
+    _place(engine, POS, paint, a, b, mi)
+    engine.sr_len_quantiles(nclust, 200.0, 0.95)
+    parts = _with_env("LDW_SR_STATS_PEEL", lambda: engine.sr_excess_stats_blocks(md, blocks))
+    assert parts.shape == (len(blocks), nclust, 5) and (paint[a] != paint[b]).sum() > 1000
+    ends = np.cumsum(blocks)
+    for k in range(len(blocks)):
+        s = slice(ends[k] - blocks[k], ends[k])
+        if blocks[k] == 0:
+            assert (parts[k] == 0).all()
+        else:
+            _stats_match(parts[k], a[s], b[s], mi[s], POS, paint, G, 200.0, md)
+    _stats_match(parts.sum(axis=0), a, b, mi, POS, paint, G, 200.0, md)
+
+
+@pytest.mark.gpu
 def test_past_the_row_floor_and_the_grid_stride():
     """About 5 M kept rows and pool rows on a fresh engine: more than the 2^22-row floor of ldw_sr_pvalues' outputs (the second pass runs)
     and than 16384 x 256 (k_sr_pval / k_sr_pool stride round), and than 2048 x 256 (k_sr_stats' strips hold several rows per lane)."""
