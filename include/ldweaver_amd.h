@@ -718,6 +718,19 @@ int ldw_plot_tree(ldw_ctx *ctx, int32_t W, int32_t H, const int32_t *panel, cons
                   const char *const *legend_title, const int32_t *legend_n, const char *const *legend_label, const uint32_t *legend_rgb,
                   const int32_t *legend_xy, int32_t text_scale, const char *png_path, uint8_t *rgb_out, int32_t *boxes_out);
 
+/* ---- (16) a neighbour-joining tree built on the device — the tree view_tree otherwise reads from a file -----------------------------------
+ * Nodes 0 .. n-1 are the tips, node n + s is made by join s (s = 0 .. n-4) and node 2n-3 is the root, on which the last three nodes hang: the tree is
+ * unrooted with a trifurcation.  dist NULL: the resident alignment, d(i, j) = the number of SNPs at which sequences i and j differ under the five-state
+ * rule (L - shared of ldw_hamming_weights), and n must be its number of sequences.  Otherwise dist is a HOST n x n fp64 matrix, checked on the device
+ * before any join runs: finite, symmetric bit for bit, zero diagonal; its row sums start as r_i = d(0, i) + d(1, i) + ... in that order.  Every join is
+ * IEEE fp64 without fused multiply-adds, operation by operation as DESIGN.md 26 states it, ties between equal Q going to the smallest (smaller node id,
+ * larger node id): the result is a function of the matrix alone.  parent_out[2n-2]: the parent of every node, -1 at the root; length_out[2n-2]: the branch
+ * to the parent, raw (it may be negative), in the matrix's unit — differing SNP columns for the alignment; 0 at the root.
+ * LDW_ERR_STATE: dist NULL and no alignment resident.  LDW_ERR_ARG: n < 3, n not the alignment's sequence count, a bad matrix, a null output.  The call
+ * holds n x n x 8 bytes of device memory (beside the Hamming stage's, released before the joins) and gives it back; the alignment, the weights, the SNP
+ * metadata and the link tables of the context stay as they are. */
+int ldw_nj_tree(ldw_ctx *ctx, const double *dist, int64_t n, int32_t *parent_out, double *length_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

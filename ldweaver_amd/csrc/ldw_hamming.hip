@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "ldw_internal.h"
+#include "ldw_hamming.h"
 #include "ldw_prim.h"
 
 using namespace ldw;
@@ -144,13 +145,6 @@ __global__ __launch_bounds__(256) void k_seq_minor_count(const uint64_t *__restr
     if (lane == 0) cnt[i] = c;
 }
 
-// shared(i, j) from the lower-triangular G (element (t, f) with t <= f is always inside a computed tile)
-__device__ __forceinline__ int64_t shared_ij(const int64_t *__restrict__ G, int ld, const int32_t *__restrict__ cnt, int64_t L,
-                                             int64_t i, int64_t j) {
-    const int64_t t = i < j ? i : j, f = i < j ? j : i;
-    return L - cnt[i] - cnt[j] + G[t * ld + f];
-}
-
 __global__ __launch_bounds__(256) void k_hdw(const int64_t *__restrict__ G, int ld, const int32_t *__restrict__ cnt, int64_t N,
                                              int64_t L, int thresh, double *__restrict__ hdw) {
     const int lane = threadIdx.x & 63;
@@ -190,27 +184,14 @@ __global__ void k_shared_i32(const int64_t *__restrict__ G, int ld, const int32_
 
 }  // namespace ldw
 
-struct HamBufs {   // the working memory of one call (hamming_impl releases it)
-    ldw::DevBuf info, Hb, T, dig, um, Gh, rl, scnt, dhdw, tmp;
-};
-// tile0 < 0: the whole matrix -> hdw_out (and shared_out); else the strip of 128-sequence row tiles [tile0, tile1) -> counts_out
-static int hamming_run(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *shared_out, int tile0, int tile1, int64_t *counts_out, HamBufs &bufs) {
-    const auto wall0 = std::chrono::steady_clock::now();
-    static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
-    double t_last = 0;
-    auto lap = [&](const char *what) {
-        if (!host_timing) return;
-        const double t = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-        fprintf(stderr, "[ldw host] hamming: %-28s %7.3f ms (+%.3f)\n", what, t, t - t_last);
-        t_last = t;
-    };
-    LDW_REQUIRE(ldw::have_alignment(c), LDW_ERR_STATE, "ldw_hamming_weights: set the alignment first");
+using ldw::HamBufs;
+
+// The stage up to its GEMM (ldw_hamming.h): what ldw_hamming_weights / _counts and ldw_nj_tree have in common.
+int ldw::hamming_gram(ldw_ctx *c, HamBufs &bufs, int tile0, int tile1, HamClock &clk, HamShape *shape) {
+    auto lap = [&](const char *what) { clk.lap(what); };
     const bool strip = tile0 >= 0;
-    LDW_REQUIRE(strip ? counts_out != nullptr : hdw_out != nullptr, LDW_ERR_ARG, "ldw_hamming_weights: output is null");
-    const int64_t L = c->L, N = c->N, Npad = c->Npad, KW = c->KW;
+    const int64_t L = c->L, Npad = c->Npad, KW = c->KW;
     const int Rp = (int)Npad;  // sequences padded to the GEMM tile (Npad is a multiple of 128)
-    LDW_REQUIRE(!strip || (tile0 < tile1 && tile1 <= Rp / ldw::TILE), LDW_ERR_ARG, "ldw_hamming_counts: tile range %d..%d outside 0..%d", tile0,
-                tile1, Rp / ldw::TILE);
     auto &[info, Hb, T, dig, um, Gh, rl, scnt, dhdw, tmp] = bufs;
     int rc = LDW_OK;
     hipError_t he;
@@ -238,8 +219,7 @@ static int hamming_run(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sha
     const int64_t Kpad = KWr * 64;
     if ((rc = info.reserve((size_t)std::max<int64_t>(KR, 1) * 4)) || (rc = Hb.reserve((size_t)std::max<int64_t>(KR, 1) * KW * 8)) ||
         (rc = T.reserve((size_t)Rp * KWr * 8)) || (rc = dig.reserve((size_t)Kpad)) || (rc = um.reserve((size_t)KWr * 8)) ||
-        (rc = Gh.reserve((size_t)Rp * Rp * 8)) || (rc = rl.reserve((size_t)Rp * 4)) || (rc = scnt.reserve((size_t)Rp * 4)) ||
-        (rc = dhdw.reserve((size_t)N * 8)))
+        (rc = Gh.reserve((size_t)Rp * Rp * 8)) || (rc = rl.reserve((size_t)Rp * 4)) || (rc = scnt.reserve((size_t)Rp * 4)))
         return rc;
     lap("device buffers");
     he = hipMemsetAsync(dig.p, 0, (size_t)Kpad, c->stream);
@@ -276,6 +256,28 @@ static int hamming_run(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sha
                                nullptr, strip ? tile0 : 0, strip ? tile1 : -1)))
         return rc;
     LDW_HIP(hipEventRecord(c->ev[1], c->stream));
+    if (shape) shape->KR = KR, shape->KWr = KWr, shape->Kpad = Kpad;
+    return LDW_OK;
+}
+
+// tile0 < 0: the whole matrix -> hdw_out (and shared_out); else the strip of 128-sequence row tiles [tile0, tile1) -> counts_out
+static int hamming_run(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *shared_out, int tile0, int tile1, int64_t *counts_out, HamBufs &bufs) {
+    ldw::HamClock clk;
+    auto lap = [&](const char *what) { clk.lap(what); };
+    LDW_REQUIRE(ldw::have_alignment(c), LDW_ERR_STATE, "ldw_hamming_weights: set the alignment first");
+    const bool strip = tile0 >= 0;
+    LDW_REQUIRE(strip ? counts_out != nullptr : hdw_out != nullptr, LDW_ERR_ARG, "ldw_hamming_weights: output is null");
+    const int64_t L = c->L, N = c->N, Npad = c->Npad;
+    const int Rp = (int)Npad;  // sequences padded to the GEMM tile (Npad is a multiple of 128)
+    LDW_REQUIRE(!strip || (tile0 < tile1 && tile1 <= Rp / ldw::TILE), LDW_ERR_ARG, "ldw_hamming_counts: tile range %d..%d outside 0..%d", tile0,
+                tile1, Rp / ldw::TILE);
+    auto &[info, Hb, T, dig, um, Gh, rl, scnt, dhdw, tmp] = bufs;
+    int rc = LDW_OK;
+    hipError_t he;
+    ldw::HamShape shape;
+    if ((rc = ldw::hamming_gram(c, bufs, tile0, tile1, clk, &shape))) return rc;
+    if ((rc = dhdw.reserve((size_t)N * 8))) return rc;
+    const int64_t KR = shape.KR, KWr = shape.KWr, Kpad = shape.Kpad, KW = c->KW;
     if (strip) {
         ldw::DevBuf dcnt;
         if ((rc = dcnt.reserve((size_t)N * 4))) return rc;
@@ -330,7 +332,7 @@ static int hamming_run(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sha
     c->ham_stat[4] = (double)tp;
     c->ham_stat[5] = (double)KR * (double)Npad + 2.0 * (double)KR * (double)KW * 8.0 + 2.0 * (double)Rp * (double)KWr * 8.0;
     c->ham_stat[6] = (double)N * (double)N * 8.0 + (double)N * 8.0;
-    c->ham_stat[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    c->ham_stat[7] = clk.ms();
     return LDW_OK;
 }
 

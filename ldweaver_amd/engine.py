@@ -472,6 +472,24 @@ class Engine:
         L.check(L.lib().ldw_hamming_weights(self._ctx, int(thresh), L.ptr(hdw), L.ptr(shared)))
         return (hdw, shared) if want_shared else hdw
 
+    def nj_tree(self, dist=None):
+        """The neighbour-joining tree (ldw_nj_tree) of the resident alignment's Hamming distances, or of ``dist``: a symmetric (n, n)
+        float64 matrix with a zero diagonal.  Returns (parent int32 [2n - 2], length float64 [2n - 2]): nodes 0 .. n-1 are the tips, node n + s is made
+        by join s, node 2n - 3 is the root (parent -1) with the last three nodes on it; lengths are raw and may be negative.  ``last_timing()`` afterwards, from
+        the library's events: ``gemm_ms`` the joins, ``epilogue_ms`` what ran in front of them (upload and checks, or the Hamming GEMM and the fill),
+        ``select_ms`` the launches per join, ``total_ms`` the first two together."""
+        if dist is None:
+            d, n = None, int(self.N)
+        else:
+            d = L.as_c(dist, np.float64)
+            if d.ndim != 2 or d.shape[0] != d.shape[1]:
+                raise ValueError(f"dist must be a square matrix, not {d.shape}")
+            n = int(d.shape[0])
+        m = max(2 * n - 2, 1)
+        parent, length = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float64)
+        L.check(L.lib().ldw_nj_tree(self._ctx, L.ptr(d), n, L.ptr(parent), L.ptr(length)))
+        return parent, length
+
     def hamming_counts(self, thresh: int, tile0: int, tile1: int) -> np.ndarray:
         """Contribution of the strip of 128-sequence row tiles [tile0, tile1) to the neighbour counts n_j (all j)."""
         out = np.zeros(self.N, dtype=np.int64)

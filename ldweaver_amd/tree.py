@@ -5,7 +5,10 @@ The selection of links, SNP columns, FASTA rows and metadata rows is the referen
 needs neither ape nor phytools: ``read_newick`` parses iteratively, ``midpoint_root`` finds the root by two sweeps in O(tips) where
 ``phytools::midpoint.root`` builds the matrix of all tip-to-tip distances, ``ladderize`` orders the children.  The picture is ours too: the tree as
 bars in 1/16 pixel and the bands as area-weighted means of their tips' colours, rendered on the device (``Engine.plot_tree``, include/ldweaver_amd.h
-15); the host draws the band labels, the title and the two legends."""
+15); the host draws the band labels, the title and the two legends.
+
+Without a tree file the tree is built here: ``nj_tree`` joins neighbours on the device (``Engine.nj_tree``) over the Hamming distances of
+the alignment the engine holds, or over a distance matrix; ``write_newick`` writes any ``Tree`` so that ``read_newick`` returns it bit for bit."""
 from __future__ import annotations
 
 import math
@@ -204,6 +207,122 @@ def read_newick(path) -> Tree:
     any depth parses.  Malformed text raises ValueError naming the byte offset; so do fewer than two tips and a repeated tip label."""
     with open(path, "rb") as fh:
         return parse_newick(fh.read())
+
+
+_NEEDS_QUOTES = re.compile(r"[()\[\],:;' \t\r\n]")
+
+
+def _newick_label(s: str) -> str:
+    """A label as ``parse_newick`` reads it back: plain when it holds none of ``()[],:;'`` and no white space, else 'quoted' with '' for a quote."""
+    if not s:
+        raise ValueError("write_newick: an empty tip label cannot be read back")
+    return "'" + s.replace("'", "''") + "'" if _NEEDS_QUOTES.search(s) else s
+
+
+def write_newick(tree: Tree, path=None) -> str:
+    """The tree as one line of Newick text, returned and, with ``path``, written there: children in their order, every branch length as
+    ``repr(float)`` (the shortest text that reads back as the same double), tip labels quoted where they need it, no internal labels, no length at
+    the root.  ``read_newick`` of the result has the same parent array, labels and lengths."""
+    ptr, idx, ln = tree.child_ptr.tolist(), tree.child_idx.tolist(), tree.length.tolist()
+    lab = {int(v): _newick_label(str(tree.tip_label[t])) for t, v in enumerate(tree.tip_node.tolist())}
+    parts, stack = [], [(0, 0)]
+    while stack:
+        v, k = stack.pop()
+        nk = ptr[v + 1] - ptr[v]
+        if k < nk:                              # open the node or go on to its next child
+            parts.append("(" if k == 0 else ",")
+            stack.append((v, k + 1))
+            stack.append((idx[ptr[v] + k], 0))
+            continue
+        parts.append(")" if nk else lab[v])
+        if v:
+            parts.append(":" + repr(float(ln[v])))
+    text = "".join(parts) + ";\n"
+    if path is not None:
+        with open(path, "wb") as fh:
+            fh.write(text.encode("utf-8", "surrogateescape"))
+    return text
+
+
+# ---- neighbour joining (DESIGN.md 26) ------------------------------------------------------------------------------------------------------------------
+
+def nj_clamp(parent: np.ndarray, length: np.ndarray) -> np.ndarray:
+    """The lengths of ``Engine.nj_tree`` without negative branches: where one branch of a join is negative it becomes 0 and its sibling gets the sum
+    of the two, which is d_ab (la + lb: to the last bit where the lengths are dyadic, else within one rounding); a negative branch at the root
+    becomes 0.  Returns a copy."""
+    out = np.array(length, dtype=np.float64)
+    n = (len(parent) + 2) // 2
+    kids = {}
+    for v in range(2 * n - 3):
+        kids.setdefault(int(parent[v]), []).append(v)
+    for u in range(n, 2 * n - 3):
+        a, b = kids[u]
+        la, lb = float(out[a]), float(out[b])
+        if la < 0:
+            out[a], out[b] = 0.0, la + lb
+        elif lb < 0:
+            out[a], out[b] = la + lb, 0.0
+    for v in kids[2 * n - 3]:
+        if out[v] < 0:
+            out[v] = 0.0
+    return out
+
+
+def nj_tree(snp_dat=None, *, dist=None, labels=None, engine=None, alignment_resident=False, clamp_negative=True, per_site=False) -> Tree:
+    """The neighbour-joining tree, built on the device, of ``snp_dat``'s sequences under the Hamming distance of the five-state rule (the number of
+    SNP columns at which two sequences differ: what ``estimate_Hamming_distance_weights`` thresholds), or of ``dist``, a symmetric (n, n) float64
+    matrix with a zero diagonal.  ``engine`` with ``alignment_resident=True``: the engine already holds the alignment (``snp_dat`` may then be None).
+    Tips are labelled ``labels``, else ``snp_dat.seq_names``, else 1 .. n, in sequence order.  The tree is unrooted: its root is the trifurcation of
+    the last three nodes, children in ascending node id (a join's: smaller id, larger id); ``midpoint_root`` roots it.  ``clamp_negative``: see
+    ``nj_clamp`` (``midpoint_root`` rejects negative branches).  ``per_site`` divides the lengths by the number of SNP columns.  Needs a GPU."""
+    from .engine import Engine
+    if dist is not None and (snp_dat is not None or alignment_resident):
+        raise ValueError("nj_tree: pass either dist or an alignment")
+    if dist is None and snp_dat is None and not alignment_resident:
+        raise ValueError("nj_tree: nothing to build a tree of: pass snp_dat, dist, or an engine with alignment_resident=True")
+    if alignment_resident and engine is None:
+        raise ValueError("alignment_resident=True needs the engine that holds the alignment")
+    if dist is not None and per_site:
+        raise ValueError("nj_tree: per_site needs an alignment")
+    own = engine is None
+    eng = Engine(0) if own else engine
+    try:
+        if dist is not None:
+            parent, length = eng.nj_tree(dist)
+        else:
+            if not alignment_resident:
+                if snp_dat.states is None:
+                    raise ValueError("snp_dat.states is None (the alignment stayed on the device): pass its engine with alignment_resident=True")
+                eng.set_alignment(snp_dat.states)
+            parent, length = eng.nj_tree()
+            n_snp = eng.L
+    finally:
+        if own:
+            eng.close()
+    if labels is None:
+        names = list(getattr(snp_dat, "seq_names", None) or [])
+        labels = names if 2 * len(names) - 2 == len(parent) else None
+    if per_site:
+        length = length / float(n_snp)
+    return tree_from_joins(parent, length, labels, clamp_negative)
+
+
+def tree_from_joins(parent, length, labels=None, clamp_negative=True) -> Tree:
+    """The ``Tree`` of ``Engine.nj_tree``'s (parent, length): the root is node 2n - 3, the children of every node in ascending node id, the tips
+    labelled ``labels`` (default 1 .. n) in node order."""
+    parent, length = np.asarray(parent), np.asarray(length, dtype=np.float64)
+    n = (len(parent) + 2) // 2
+    labels = [str(k + 1) for k in range(n)] if labels is None else [str(x) for x in labels]
+    if len(labels) != n:
+        raise ValueError(f"{len(labels)} labels for {n} tips")
+    if clamp_negative:
+        length = nj_clamp(parent, length)
+    root = 2 * n - 3
+    kids = [[] for _ in range(2 * n - 2)]
+    for v in range(root):
+        kids[int(parent[v])].append(v)
+    ln = length.tolist()
+    return _build(root, lambda v: kids[v], lambda v: ln[v], lambda v: v if v < n else -1, labels)
 
 
 # ---- rooting and ordering ---------------------------------------------------------------------------------------------------------------------------
@@ -630,7 +749,7 @@ def tree_layout(tree: Tree, width: int, height: int, n_metadata: int = 0, n_alle
 
 # ---- view_tree ------------------------------------------------------------------------------------------------------------------------------------------------
 
-def view_tree(tree_path, perform_midpoint_rooting=True, metadata_df=None, fasta_path=None, pos_file_path=None, links_df=None, lr_tophits_path=None,
+def view_tree(tree_path=None, perform_midpoint_rooting=True, metadata_df=None, fasta_path=None, pos_file_path=None, links_df=None, lr_tophits_path=None,
               lr_annotated_links_path=None, sr_tophits_path=None, sr_annotated_links_path=None, ntop_links=10, from_=None, to=None, offset_metadata=None,
               offset_alleles=None, width_metadata=None, width_alleles=None, plot_save_path=None, plot_height=20, plot_width=15, *, engine=None,
               want_canvas=False, dpi=300):
@@ -638,13 +757,27 @@ def view_tree(tree_path, perform_midpoint_rooting=True, metadata_df=None, fasta_
     either way.  Returns a dict: ``tree`` (rooted and ladderized), ``tip_order``, ``pos_plot`` (the allele columns), ``metadata_columns``, ``alleles``
     / ``metadata`` (levels uint8 [bands, tips in figure order] and their values), ``layout`` (``tree_layout``), ``boxes`` (what the host drew: band
     labels, title, two legends), ``png`` (the path written, or None) and ``canvas`` (uint8 [H, W, 3]: with ``want_canvas`` or without a path, when no
-    file is written).  The figure needs a GPU."""
+    file is written).  The figure needs a GPU.
+
+    Without ``tree_path`` the tree is built from the sequences of ``fasta_path``: encoded by the five-state rule, joined by ``nj_tree`` on an engine of
+    its own (the caller's keeps its alignment), the tips named as the FASTA names them, in file order; the figure's title is then ``NJ (Hamming)``."""
     if fasta_path is None or pos_file_path is None:
         raise ValueError("fasta_path and pos_file_path must be provided")
     W, H = _half_up(float(plot_width) * dpi), _half_up(float(plot_height) * dpi)
     if not (1 <= W <= MAX_CANVAS and 1 <= H <= MAX_CANVAS):
         raise ValueError(f"the canvas of {W} x {H} pixels (plot_width x dpi by plot_height x dpi) must lie in 1..{MAX_CANVAS} either way")
-    tree = read_newick(os.path.realpath(tree_path))          # :64-65
+    if tree_path is None:
+        from .snpdat import SnpDat, encode_chars, read_fasta
+        names, seq = read_fasta(fasta_path)
+        states = np.ascontiguousarray(encode_chars(seq).T)
+        tree = nj_tree(SnpDat(states=states, POS=np.arange(states.shape[0], dtype=np.int32), g=None, uqe=None, r=None, seq_names=names), labels=names)
+        # through its Newick text, so that the figure is the one ``view_tree`` draws of the written tree: a file numbers its tips in its own
+        # order, and midpoint rooting breaks its ties by tip number
+        tree = parse_newick(write_newick(tree).encode("utf-8", "surrogateescape"))
+        title = "NJ (Hamming)"
+    else:
+        tree = read_newick(os.path.realpath(tree_path))      # :64-65
+        title = os.path.basename(str(tree_path))
     if perform_midpoint_rooting:
         tree = midpoint_root(tree)
     sel = tree_selection(tree.tip_label, metadata_df, fasta_path, pos_file_path, links_df, lr_tophits_path, lr_annotated_links_path, sr_tophits_path,
@@ -668,7 +801,7 @@ def view_tree(tree_path, perform_midpoint_rooting=True, metadata_df=None, fasta_
     eng = Engine(0) if own else engine
     need_canvas = want_canvas or plot_save_path is None
     try:
-        canvas, boxes = eng.plot_tree(W, H, lay["panel"], lay["bars"], TREE_RGB, levels, palette, lay["bands"], labels, os.path.basename(str(tree_path)),
+        canvas, boxes = eng.plot_tree(W, H, lay["panel"], lay["bars"], TREE_RGB, levels, palette, lay["bands"], labels, title,
                                       [(t, l, c, xy) for (t, l, c), xy in zip(legends, lay["legend_xy"])], lay["text_scale"], png_path=plot_save_path,
                                       want_canvas=need_canvas)
     finally:
