@@ -3,7 +3,6 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,252 +12,9 @@
 #include "ldw_dev.h"
 #include "ldw_fasta.h"
 #include "ldw_links_read.h"
+#include "ldw_slots.h"
 
-// ------------------------------------------------------------------------------------------------
-// error plumbing
-// ------------------------------------------------------------------------------------------------
 namespace ldw {
-static thread_local char g_err[1024] = "";
-
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-int hip_fail(hipError_t e, const char *what, const char *file, int line) {
-    set_error("HIP error %d (%s) at %s:%d: %s", (int)e, hipGetErrorString(e), file, line, what);
-    return LDW_ERR_HIP;
-}
-
-// ---- r05: released device blocks are kept for the next taker (process-wide, per device).  tools/scratch/realloc_probe.cpp: device memory the runtime has to fetch from the driver
-// costs up to 40 ms per GB on this stack (4 x 12 GB: 1.9 s, fresh or right after freeing the same amount; under ~16 GB the runtime re-uses what it just freed), so an engine created after
-// another one was destroyed — every test, every job of a long session — waited about a second for the 13-19 GB its context reserves.  Blocks of >= 64 MB go to a free list on release and are
-// handed out again best-fit (at most a quarter larger than asked for); LDW_DEVPOOL_GB (default 48, 0: off) caps what is kept; a failing hipMalloc flushes the list and tries again;
-// ldw_host_trim gives everything back.  A block is given up only after the device has drained (what hipFree does implicitly), so its next owner cannot meet the last one's kernels.
-namespace {
-struct PoolBlock {
-    void *p;
-    size_t cap;
-    int dev;
-};
-std::mutex g_pool_mtx;
-std::vector<PoolBlock> g_pool;
-size_t g_pool_bytes = 0;
-constexpr size_t POOL_MIN = (size_t)64 << 20;
-size_t pool_limit() {
-    static const size_t v = [] {
-        const char *e = getenv("LDW_DEVPOOL_GB");
-        const double gb = e ? atof(e) : 48.0;
-        return gb > 0 ? (size_t)(gb * 1073741824.0) : (size_t)0;
-    }();
-    return v;
-}
-void *pool_take(size_t want, size_t &cap_out) {
-    if (want < POOL_MIN || pool_limit() == 0) return nullptr;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_pool_mtx);
-    size_t best = (size_t)-1;
-    for (size_t i = 0; i < g_pool.size(); ++i)
-        if (g_pool[i].dev == dev && g_pool[i].cap >= want && g_pool[i].cap <= want + want / 4 && (best == (size_t)-1 || g_pool[i].cap < g_pool[best].cap)) best = i;
-    if (best == (size_t)-1) return nullptr;
-    void *p = g_pool[best].p;
-    cap_out = g_pool[best].cap;
-    g_pool_bytes -= cap_out;
-    g_pool[best] = g_pool.back();
-    g_pool.pop_back();
-    return p;
-}
-// r06: a caller that has drained every stream that could touch its blocks (ldw_ctx_destroy: the context's own streams) says so for the
-// duration of its releases, and the device-wide synchronisation — which stalls OTHER contexts of the device in the middle of their passes — is skipped
-thread_local bool g_owner_drained = false;
-std::atomic<int> g_live_ctx{0};
-size_t pool_idle_limit() {   // what the free list may keep once the process holds no context at all (LDW_DEVPOOL_IDLE_GB, default 24; the live cap is LDW_DEVPOOL_GB)
-    static const size_t v = [] {
-        const char *e = getenv("LDW_DEVPOOL_IDLE_GB");
-        const double gb = e ? atof(e) : 24.0;
-        return gb > 0 ? (size_t)(gb * 1073741824.0) : (size_t)0;
-    }();
-    return v;
-}
-// a block goes back to the runtime: large ones zero-filled first (the runtime may hand the same memory to the next hipMalloc without clearing it;
-// the pages are mapped, so this runs at HBM speed), so that whatever dev_alloc gets from the runtime reads as zero
-void pool_free_zeroed(void *p, size_t cap) {
-    if (cap >= POOL_MIN && hipMemsetAsync(p, 0, cap, nullptr) != hipSuccess) (void)hipGetLastError();
-    (void)hipFree(p);   // (waits for the fill)
-}
-void pool_give(void *p, size_t cap) {
-    if (!p) return;
-    if (cap >= POOL_MIN && pool_limit() > 0) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, p) == hipSuccess) {
-            int cur = 0;
-            (void)hipGetDevice(&cur);
-            if (cur != at.device) (void)hipSetDevice(at.device);
-            const bool drained = g_owner_drained || hipDeviceSynchronize() == hipSuccess;   // (the releasing context's kernels are done with it: what hipFree waits for as well)
-            if (cur != at.device) (void)hipSetDevice(cur);
-            if (drained) {
-                std::lock_guard<std::mutex> lk(g_pool_mtx);
-                if (g_pool_bytes + cap <= pool_limit()) {
-                    g_pool.push_back(PoolBlock{p, cap, at.device});
-                    g_pool_bytes += cap;
-                    return;
-                }
-            }
-        }
-        (void)hipGetLastError();
-    }
-    pool_free_zeroed(p, cap);
-}
-// keep: bytes the list may hold afterwards (0: give everything back); the largest blocks go first
-size_t pool_flush(size_t keep = 0) {
-    std::vector<PoolBlock> all;
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mtx);
-        if (keep == 0) {
-            all.swap(g_pool);
-            g_pool_bytes = 0;
-        } else {
-            std::sort(g_pool.begin(), g_pool.end(), [](const PoolBlock &x, const PoolBlock &y) { return x.cap < y.cap; });
-            while (g_pool_bytes > keep && !g_pool.empty()) {
-                all.push_back(g_pool.back());
-                g_pool_bytes -= g_pool.back().cap;
-                g_pool.pop_back();
-            }
-        }
-    }
-    size_t n = 0;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (const PoolBlock &b : all) {
-        (void)hipSetDevice(b.dev);
-        pool_free_zeroed(b.p, b.cap);
-        n += b.cap;
-    }
-    if (!all.empty()) (void)hipSetDevice(cur);
-    return n;
-}
-// a block of at least `want` bytes: from the free list, else from the runtime (a second try after giving the free list back)
-// LDW_POISON_ALLOC=1 (debugging aid, any build): every block handed out is filled with 0xA5 first — fresh device memory happens to be zero on this stack, a block from
-// the free list (or from the runtime's own cache) is not, and code that reads what it never wrote must not depend on the difference (tools/fuzz_paths.py found one such read)
-bool poison_on() {
-    static const bool on = getenv("LDW_POISON_ALLOC") != nullptr;
-    return on;
-}
-// LDW_POISON_ALLOC=1: bytes 0xA5 (an index read from it is wild: the kernel faults).  LDW_POISON_ALLOC=2: int32 words of 1 — indices stay in range, flags
-// read "set", floats are denormals: a read-before-write shows as a wrong RESULT instead of a fault (the gentler first probe)
-void poison_fill(void *p, size_t bytes) {
-    static const int mode = getenv("LDW_POISON_ALLOC") ? atoi(getenv("LDW_POISON_ALLOC")) : 0;
-    if (mode == 2) (void)hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), 1, bytes / 4);
-    else if (mode == 3) (void)hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), 0x00000A5A, bytes / 4);   // a second in-range pattern: index 2650, flags set, float denormal
-    else (void)hipMemset(p, 0xA5, bytes);
-    (void)hipDeviceSynchronize();
-}
-hipError_t dev_alloc(void **out, size_t want, size_t &cap_out) {
-    if (void *p = pool_take(want, cap_out)) {
-        // a block from the free list holds its last owner's data; memory that comes from the driver is zero, and the engine has always been handed zeroed
-        // blocks (nothing else was ever observed on this stack): keep it so — LDW_POISON_ALLOC (below) found kernels that read index arrays before writing
-        // them, which zeroes make harmless and another buffer's contents would not.  The pages are mapped already: the fill runs at HBM speed (7 ms for 20 GB).
-        hipError_t e = hipMemsetAsync(p, 0, cap_out, nullptr);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (the library's streams do not synchronise with the null stream; only the fill has to be done — no device-wide wait)
-        if (e == hipSuccess && poison_on()) poison_fill(p, cap_out);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(p);
-        } else {
-            *out = p;
-            return hipSuccess;
-        }
-    }
-    hipError_t e = hipMalloc(out, want);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (pool_flush() > 0) e = hipMalloc(out, want);
-    }
-    cap_out = want;
-    // r06 — "a fresh DevBuf reads as zero" as an invariant with a reason per source, instead of an accident of the stack:
-    //   * from the free list: zero-filled above (mapped pages: HBM speed);
-    //   * small blocks (< 64 MB, never pooled: the runtime caches and re-uses them DIRTY): zero-filled here, microseconds;
-    //   * large blocks from the runtime: either fresh from the driver — the kernel driver clears VRAM it hands to a process — or a block this library
-    //     gave back with hipFree, and those are zero-filled BEFORE they are freed (pool_free_zeroed).  Filling them here as well was measured: it maps
-    //     every page of the 13-19 GB a context reserves (0.37 s on a job's first Hamming call against 6 ms: profiles/r06_alloc_zero_fill.txt).
-    // It is NOT what makes stale data harmless: a DevBuf kept across problems holds the last problem's bytes; tools/fuzz_paths.py and tests/test_bounds.py
-    // run ~500 problems one after the other on one context for that, LDW_POISON_ALLOC=2 / 3 fill every block with in-range garbage instead of zeroes.
-    if (e == hipSuccess && want < POOL_MIN) {
-        e = hipMemsetAsync(*out, 0, want, nullptr);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(*out);
-            *out = nullptr;
-        }
-    }
-    if (e == hipSuccess && poison_on()) poison_fill(*out, want);
-    return e;
-}
-}  // namespace
-
-OwnCounts g_own;
-size_t device_pool_trim() { return pool_flush(); }
-// the per-SNP state counts into ctx->counts ([L][5] int32) on the context's stream; no copy, no synchronisation (ldw_state_counts, ldw_hamming_weights)
-int launch_state_counts(ldw_ctx *c);
-void ctx_count(int d) {
-    if (g_live_ctx.fetch_add(d) + d <= 0 && d < 0) (void)pool_flush(pool_idle_limit() ? pool_idle_limit() : 0);   // the last context of the process has gone
-}
-DrainedScope::DrainedScope() { g_owner_drained = true; }
-DrainedScope::~DrainedScope() { g_owner_drained = false; }
-
-int DevBuf::reserve(size_t bytes) {
-    if (bytes <= cap && p) return LDW_OK;
-    release();
-    size_t want = bytes < 256 ? 256 : bytes, got = 0;
-    LDW_HIP(dev_alloc(&p, want, got));
-    ++g_own.dev;
-    cap = got;
-    return LDW_OK;
-}
-
-int DevBuf::reserve_keep(size_t bytes, size_t used, hipStream_t s) {
-    if (bytes <= cap && p) return LDW_OK;
-    size_t want = bytes < 256 ? 256 : bytes;
-    if (want < cap + cap / 2) want = cap + cap / 2;  // geometric growth for the link tables
-    void *np = nullptr;
-    size_t got = 0;
-    {
-        hipError_t e = dev_alloc(&np, want, got);
-        if (e != hipSuccess) {
-            size_t fr = 0, tot = 0;
-            (void)hipMemGetInfo(&fr, &tot);
-            set_error("hipMalloc of %zu bytes failed (%s); %zu of %zu bytes free on the device", want, hipGetErrorString(e), fr, tot);
-            return LDW_ERR_HIP;
-        }
-    }
-    if (p && used) {
-        hipError_t e = hipMemcpyAsync(np, p, used, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            pool_give(np, got);
-            return hip_fail(e, "DevBuf::reserve_keep: copy of the kept bytes", __FILE__, __LINE__);
-        }
-    }
-    release();
-    ++g_own.dev;
-    p = np;
-    cap = got;
-    return LDW_OK;
-}
-
-void DevBuf::release() {
-    if (p) {
-        pool_give(p, cap);
-        --g_own.dev;
-    }
-    p = nullptr;
-    cap = 0;
-}
-
 int check_gpu(ldw_ctx *ctx) {
     LDW_REQUIRE(ctx != nullptr, LDW_ERR_ARG, "null context");
     LDW_HIP(hipSetDevice(ctx->device));
@@ -461,9 +217,9 @@ __global__ void k_fast_hadamard(double *__restrict__ MI, const double *__restric
 
 int launch_state_counts(ldw_ctx *c) {
     LDW_REQUIRE(ldw::have_alignment(c), LDW_ERR_STATE, "state counts: no alignment resident");
-    if (int rc = c->counts.reserve((size_t)c->L * 5 * 4)) return rc;
+    if (int rc = c->rows.counts.reserve((size_t)c->L * 5 * 4)) return rc;
     hipLaunchKernelGGL(k_counts_marginals, dim3((unsigned)((c->L + 3) / 4)), dim3(256), 0, c->stream, c->states.as<uint8_t>(), c->L, c->Npad, (const int64_t *)nullptr,
-                       c->counts.as<int32_t>(), (int64_t *)nullptr);
+                       c->rows.counts.as<int32_t>(), (int64_t *)nullptr);
     LDW_HIP(hipGetLastError());
     return LDW_OK;
 }
@@ -494,8 +250,6 @@ int launch_fasta_encode_rows(bool packed, const uint8_t *src, int64_t stride, in
 extern "C" {
 
 int ldw_version(void) { return 100; }
-
-const char *ldw_last_error(void) { return ldw::g_err; }
 
 int ldw_build_info(void) { return 0; }
 
@@ -532,7 +286,7 @@ int ldw_ctx_create(int device, ldw_ctx **out) {
     ldw_ctx *c = guard.get();
     ldw::ctx_count(+1);
     c->device = device;
-    c->prune = getenv("LDW_NO_PRUNE") == nullptr;
+    c->knobs.prune = getenv("LDW_NO_PRUNE") == nullptr;
     LDW_HIP(c->stream.ensure(hipStreamNonBlocking));
     for (auto &e : c->ev) LDW_HIP(e.ensure());
     // r04: the two extra streams of the all-pairs loop (hipStreamCreate: 12 ms each on this box), its events and pinned pick records are made
@@ -572,7 +326,7 @@ int ldw_ctx_reserve(ldw_ctx *c, int64_t L, int64_t N, int64_t max_blk_sz) {
     if (no_prep) return LDW_OK;
     const int64_t blk = std::min<int64_t>(L, max_blk_sz);
     const int64_t nblk = (L + blk - 1) / blk;
-    const int64_t nseg = std::max<int64_t>(1, std::min<int64_t>(c->span_on ? c->span_max : 1, nblk - 2));
+    const int64_t nseg = std::max<int64_t>(1, std::min<int64_t>(c->knobs.span_on ? c->knobs.span_max : 1, nblk - 2));
     // the packed staging image of a span (prep_block): index, row and permutation lists of both sides, 48 bytes of intervals per to-side SNP
     const int64_t nt = blk * nseg, rows_f = blk * 5 / 4 + 512, rows_t = nt * 5 / 4 + 512;
     const size_t stage = (size_t)((blk + nt) * 12 + (rows_f + rows_t) * 9 + nt * 52 + (blk + 64) * 16 + 3 * (rows_t / 128 + 1) * (rows_f / 64 + 1) + 65536);   // (r06: + the band's tile list, at most 2 bytes per tile of the mask)
@@ -624,19 +378,6 @@ int ldw_ctx_set_stream(ldw_ctx *c, void *s) {
     return LDW_OK;
 }
 
-int ldw_resource_report(int64_t out[5]) {
-    LDW_REQUIRE(out, LDW_ERR_ARG, "ldw_resource_report: null argument");
-    out[0] = ldw::g_own.dev;
-    {
-        std::lock_guard<std::mutex> lk(ldw::g_pool_mtx);
-        out[1] = (int64_t)ldw::g_pool.size();
-    }
-    out[2] = ldw::g_own.pinned;
-    out[3] = ldw::g_own.events;
-    out[4] = ldw::g_own.streams;
-    return LDW_OK;
-}
-
 int ldw_ctx_sync(ldw_ctx *c) {
     if (int rc = check_gpu(c)) return rc;
     LDW_HIP(hipStreamSynchronize(c->stream));
@@ -649,71 +390,56 @@ int ldw_ctx_last_timing(ldw_ctx *c, double ms_out[4]) {
     return LDW_OK;
 }
 
-int ldw_ctx_counters2(ldw_ctx *c, int64_t out[8]) {
-    LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_ctx_counters2: null argument");
-    out[0] = c->spec_misses;
-    out[1] = 0;   // (the removed fused kernel's blocks)
-    out[2] = c->blocks_run;
-    out[3] = c->screen_violations;
-    out[4] = c->mixed_blocks;
-    out[5] = c->apx_blocks;
-    out[6] = c->apx_units_listed;
-    out[7] = c->apx_pairs_listed;
+// ---- reports and switches: the entries that only read PassCounters or write Knobs (one needing a type of the MI unit stays in ldw_mi.hip) ----
+// the first n of the eight pass counters (ldw_ctx_counters: 4, ldw_ctx_counters2: all)
+static int ctx_counters(ldw_ctx *c, int64_t *out, int n, const char *who) {
+    LDW_REQUIRE(c && out, LDW_ERR_ARG, "%s: null argument", who);
+    const ldw::PassCounters &k = c->cnt;
+    const int64_t all[8] = {k.spec_misses, 0 /* (the removed fused kernel's blocks) */, k.blocks_run, k.screen_violations, k.mixed_blocks, k.apx_blocks, k.apx_units_listed, k.apx_pairs_listed};
+    std::copy(all, all + n, out);
     return LDW_OK;
 }
-
-int ldw_ctx_counters(ldw_ctx *c, int64_t out[4]) {
-    LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_ctx_counters: null argument");
-    out[0] = c->spec_misses;
-    out[1] = 0;   // (the removed fused kernel's blocks)
-    out[2] = c->blocks_run;
-    out[3] = c->screen_violations;
-    return LDW_OK;
-}
+int ldw_ctx_counters2(ldw_ctx *c, int64_t out[8]) { return ctx_counters(c, out, 8, "ldw_ctx_counters2"); }
+int ldw_ctx_counters(ldw_ctx *c, int64_t out[4]) { return ctx_counters(c, out, 4, "ldw_ctx_counters"); }
 
 int ldw_reset_speculation(ldw_ctx *c) {
     LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
-    c->spec_B_next[0] = c->spec_B_next[1] = -1;
-    c->spec_seen[0] = c->spec_seen[1] = false;
-    c->spec_probed[0] = c->spec_probed[1] = false;
-    c->spec_hist_n[0] = c->spec_hist_n[1] = 0;
-    c->tab11_lo[0] = c->tab11_lo[1] = 0;
-    c->maybe_off = false;
+    c->spec.reset();
     return LDW_OK;
 }
 
 int ldw_path_report(ldw_ctx *c, int64_t out[8], char *gate, int capacity) {
     LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_path_report: null argument");
-    out[0] = c->apx_blocks;
-    out[1] = c->mixed_blocks;
-    out[2] = c->blocks_run - c->apx_blocks - c->mixed_blocks + c->spec_misses + c->generic_blocks;   // (blocks in generic POS order always take the plain path)
+    out[0] = c->cnt.apx_blocks;
+    out[1] = c->cnt.mixed_blocks;
+    out[2] = c->cnt.blocks_run - c->cnt.apx_blocks - c->cnt.mixed_blocks + c->cnt.spec_misses + c->cnt.generic_blocks;   // (blocks in generic POS order always take the plain path)
     out[3] = 0;   // (the removed fused kernel's blocks)
-    out[4] = c->spec_misses;
-    out[5] = c->probe_blocks;
-    out[6] = c->apx_pairs_listed;
-    out[7] = c->apx_units_listed;
-    if (gate && capacity > 0) snprintf(gate, (size_t)capacity, "%s", c->have_weights ? c->apx_gate.c_str() : "weights not set");
+    out[4] = c->cnt.spec_misses;
+    out[5] = c->cnt.probe_blocks;
+    out[6] = c->cnt.apx_pairs_listed;
+    out[7] = c->cnt.apx_units_listed;
+    if (gate && capacity > 0) snprintf(gate, (size_t)capacity, "%s", c->apx.gate(c->wts.have_weights));
     return LDW_OK;
 }
 
 int ldw_pair_form_report(ldw_ctx *c, int64_t out[5]) {
     LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_pair_form_report: null argument");
-    for (int i = 0; i < 5; ++i) out[i] = c->form_launches[i];
+    for (int i = 0; i < 5; ++i) out[i] = c->cnt.form_launches[i];
     return LDW_OK;
 }
 
 int ldw_set_prune(ldw_ctx *c, int on) {
     LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
-    c->prune = on != 0;
+    c->knobs.prune = on != 0;
     return LDW_OK;
 }
 
 int ldw_prune_report(ldw_ctx *c, int64_t out[4]) {
     LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_prune_report: null argument");
-    out[0] = c->sorted_blocks;
-    out[1] = c->apx_waves_skipped;
-    out[2] = c->apx_waves_total;
-    out[3] = c->prune ? 1 : 0;
+    out[0] = c->cnt.sorted_blocks;
+    out[1] = c->cnt.apx_waves_skipped;
+    out[2] = c->cnt.apx_waves_total;
+    out[3] = c->knobs.prune ? 1 : 0;
     return LDW_OK;
 }
 
@@ -722,39 +448,39 @@ int ldw_snp_bounds(ldw_ctx *c, double *out, int64_t capacity) {
     LDW_REQUIRE(out, LDW_ERR_ARG, "ldw_snp_bounds: null argument");
     if (int rc = ldw::ensure_rows(c)) return rc;
     LDW_REQUIRE(capacity >= 4 * c->L, LDW_ERR_ARG, "ldw_snp_bounds: capacity %lld < 4 L = %lld", (long long)capacity, (long long)(4 * c->L));
-    LDW_HIP(hipMemcpyAsync(out, c->snp_sup.p, (size_t)c->L * 32, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(out, c->rows.snp_sup.p, (size_t)c->L * 32, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     return LDW_OK;
 }
 
 int ldw_set_select(ldw_ctx *c, int mode) {
     LDW_REQUIRE(c && (mode == 0 || mode == 1), LDW_ERR_ARG, "ldw_set_select: mode must be 0 (auto) or 1 (radix sorts)");
-    c->select_mode = mode;
+    c->knobs.select_mode = mode;
     return LDW_OK;
 }
 
 int ldw_set_path(ldw_ctx *c, int mode) {
     LDW_REQUIRE(c && mode >= 0 && mode <= 2, LDW_ERR_ARG, "ldw_set_path: mode must be 0 (auto), 1 (limb GEMM paths) or 2 (approximate GEMM path)");
-    c->path_mode = mode;
+    c->knobs.path_mode = mode;
     return LDW_OK;
 }
 
 int ldw_apx_info(ldw_ctx *c, double out[6]) {
     LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_apx_info: null argument");
-    out[0] = c->apx_ok ? 1.0 : 0.0;
-    out[1] = c->apx_delta;
-    out[2] = (double)c->n_classes;
-    out[3] = (double)c->n_pop_segs;
-    out[4] = (double)c->apx_transitions;
-    out[5] = (double)c->apx_e_last;
+    out[0] = c->apx.apx_ok ? 1.0 : 0.0;
+    out[1] = c->apx.apx_delta;
+    out[2] = (double)c->apx.n_classes;
+    out[3] = (double)c->apx.n_pop_segs;
+    out[4] = (double)c->apx.apx_transitions;
+    out[5] = (double)c->apx.apx_e_last;
     return LDW_OK;
 }
 
 int ldw_gemm_stats(ldw_ctx *c, double out[6], int reset) {
     LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_gemm_stats: null argument");
     for (int k = 0; k < 6; ++k) {
-        out[k] = c->gemm_stat[k];
-        if (reset) c->gemm_stat[k] = 0;
+        out[k] = c->cnt.gemm_stat[k];
+        if (reset) c->cnt.gemm_stat[k] = 0;
     }
     return LDW_OK;
 }
@@ -764,7 +490,57 @@ int ldw_set_engine(ldw_ctx *c, int engine) {
     LDW_REQUIRE(engine == LDW_ENGINE_MFMA || engine == LDW_ENGINE_HIST || engine == LDW_ENGINE_HIST_STATES, LDW_ERR_ARG, "unknown engine %d", engine);
     LDW_REQUIRE(engine != LDW_ENGINE_HIST_STATES, LDW_ERR_STATE,
                 "LDW_ENGINE_HIST_STATES: the byte-state histogram kernel (formerly the LDW_EXPERIMENTS build's) was measured ~200x slower and has been removed");
-    c->engine = engine;
+    c->knobs.engine = engine;
+    return LDW_OK;
+}
+
+int ldw_overflow_report(ldw_ctx *c, int64_t out[4]) {
+    LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_overflow_report: null argument");
+    out[0] = c->cnt.pair_list_overflows;
+    out[1] = c->cnt.maybe_overflows;
+    out[2] = c->spec.maybe_off ? 1 : 0;
+    out[3] = c->cnt.maybe_entries;
+    return LDW_OK;
+}
+
+int ldw_span_report(ldw_ctx *c, int64_t out[4]) {
+    LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_span_report: null argument");
+    out[0] = c->cnt.span_items;
+    out[1] = c->cnt.span_blocks;
+    out[2] = c->cnt.span_fallbacks;
+    out[3] = c->knobs.span_on ? 1 : 0;
+    return LDW_OK;
+}
+
+int ldw_set_span(ldw_ctx *c, int on, int max_blocks) {
+    LDW_REQUIRE(c && (max_blocks == 0 || (max_blocks >= 2 && max_blocks <= LDW_SPAN_MAX)), LDW_ERR_ARG, "ldw_set_span: max_blocks must be 0 or 2..%d", LDW_SPAN_MAX);
+    LDW_REQUIRE(!(on & 6), LDW_ERR_STATE, "ldw_set_span: corner spans / split diagonal blocks (bits 1, 2; formerly the LDW_EXPERIMENTS build's) were measured slower and have been removed");
+    c->knobs.span_on = on != 0;
+    if (max_blocks) c->knobs.span_max = max_blocks;
+    return LDW_OK;
+}
+
+int ldw_set_overlap(ldw_ctx *c, int on) {
+    LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
+    c->knobs.overlap = on != 0;
+    return LDW_OK;
+}
+
+int ldw_set_screen(ldw_ctx *c, int mode) {
+    LDW_REQUIRE(c && mode >= 0 && mode <= 2, LDW_ERR_ARG, "ldw_set_screen: mode must be 0, 1 or 2");
+    c->knobs.screen = mode;
+    return LDW_OK;
+}
+
+int ldw_set_mixed(ldw_ctx *c, int on) {
+    LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
+    c->knobs.mixed = on != 0;
+    return LDW_OK;
+}
+
+int ldw_set_fused(ldw_ctx *c, int on) {
+    LDW_REQUIRE(!on, LDW_ERR_STATE, "ldw_set_fused(1): the fused GEMM + epilogue kernel (formerly the LDW_EXPERIMENTS build's) was measured slower and has been removed");
+    LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
     return LDW_OK;
 }
 
@@ -833,10 +609,7 @@ int ldw::set_dims(ldw_ctx *c, int64_t L, int64_t N) {
     c->N = N;
     c->Npad = (N + KSTEP - 1) / KSTEP * KSTEP;
     c->KW = c->Npad / 64;
-    c->rows_ready = false;
-    c->have_weights = false;
-    c->have_meta = false;
-    c->pos_only = false;
+    c->new_shape();
     return c->states.reserve((size_t)L * c->Npad);
 }
 }
@@ -874,7 +647,7 @@ int ldw_state_counts(ldw_ctx *c, int32_t *counts_out) {
     LDW_REQUIRE(counts_out && ldw::have_alignment(c), LDW_ERR_STATE, "ldw_state_counts: no alignment resident");
     if (int rc = ldw::launch_state_counts(c)) return rc;
     // stored [L][5] row-major == 5 x L column-major (ACGTN_table layout)
-    LDW_HIP(hipMemcpyAsync(counts_out, c->counts.p, (size_t)c->L * 20, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(counts_out, c->rows.counts.p, (size_t)c->L * 20, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     return LDW_OK;
 }
@@ -940,8 +713,8 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
         if (int rc = join_prepare(c)) return rc;
         LDW_HIP(hipDeviceSynchronize());
         std::vector<ldw::DevBuf *> g;
-        if (mask & 1) g.insert(g.end(), {&c->dig_a, &c->dig_b, &c->apx_shift, &c->seq_perm, &c->digits, &c->vfixed});
-        if (mask & 2) g.insert(g.end(), {&c->pop_segs, &c->pop_wbeg, &c->pop_vpos, &c->slot_papx});
+        if (mask & 1) g.insert(g.end(), {&c->apx.dig_a, &c->apx.dig_b, &c->apx.apx_shift, &c->wts.seq_perm, &c->wts.digits, &c->wts.vfixed});
+        if (mask & 2) g.insert(g.end(), {&c->apx.pop_segs, &c->apx.pop_wbeg, &c->apx.pop_vpos, &c->rows.slot_papx});
         if (mask & 4)
             for (int k = 0; k < LDW_NSLOT; ++k) g.insert(g.end(), {&c->panel[k][0], &c->panel[k][1], &c->Gapx[k]});
         if (mask & 8)
@@ -953,10 +726,10 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
                 if (mask & (64 << q)) g.push_back(one[q]);
         }
         if (mask & 16)
-            g.insert(g.end(), {&c->Mbits, &c->row0, &c->slot_meta, &c->slot_pfix, &c->slot_pfix_hi, &c->counts, &c->pfix_state, &c->snp_sup, &c->packs, &c->glo, &c->lo_rows});
+            g.insert(g.end(), {&c->rows.Mbits, &c->rows.row0, &c->rows.slot_meta, &c->rows.slot_pfix, &c->rows.slot_pfix_hi, &c->rows.counts, &c->rows.pfix_state, &c->rows.snp_sup, &c->packs, &c->glo, &c->lo_rows});
         if (mask & 32) {
             g.insert(g.end(), {&c->G, &c->G2, &c->G3, &c->MIblk, &c->rowlist_f, &c->rowlist_t, &c->idx_f, &c->idx_t, &c->lrow_f, &c->lrow_t, &c->perm_f, &c->perm_t, &c->scr_units, &c->epi_rest, &c->colcnt,
-                               &c->cand_key2, &c->cand_val2, &c->sel_bitmap, &c->sel_chunks, &c->sel_prefix, &c->scratch, &c->small, &c->pair_sums, &c->tab11[0], &c->tab11[1], &c->miss_key,
+                               &c->cand_key2, &c->cand_val2, &c->sel_bitmap, &c->sel_chunks, &c->sel_prefix, &c->scratch, &c->small, &c->pair_sums, &c->spec.tab11[0], &c->spec.tab11[1], &c->miss_key,
                                &c->miss_val});
             for (int k = 0; k < LDW_NSLOT; ++k) g.insert(g.end(), {&c->hist[k], &c->cand_key[k], &c->cand_val[k], &c->dstage[k]});
         }
@@ -985,15 +758,15 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
     bool unit = true;  // all weights exactly 1 (unweighted counts): F = 0 is exact with one limb
     for (int64_t s = 0; s < N; ++s) unit = unit && (v[s] == 1.0);
     if (unit) F = 0;
-    c->nlimbs = nlimbs;
-    c->frac_bits = F;
-    c->neff = (double)neff;
-    c->h_vfixed.assign((size_t)c->Npad, 0);
+    c->wts.nlimbs = nlimbs;
+    c->wts.frac_bits = F;
+    c->wts.neff = (double)neff;
+    c->wts.h_vfixed.assign((size_t)c->Npad, 0);
     std::vector<int8_t> dseq((size_t)nlimbs * c->Npad, 0);   // digits by sequence
     int64_t total = 0;
     for (int64_t s = 0; s < N; ++s) {
         int64_t V = (int64_t)std::llround(std::ldexp(v[s], F));
-        c->h_vfixed[s] = V;
+        c->wts.h_vfixed[s] = V;
         total += V;
         int64_t rem = V;
         for (int j = 0; j < nlimbs; ++j) {
@@ -1003,21 +776,21 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
         }
         LDW_REQUIRE(rem == 0, LDW_ERR_ARG, "ldw_set_weights: internal: weight %g does not fit %d limbs at F=%d", v[s], nlimbs, F);
     }
-    c->total_fixed = total;
+    c->wts.total_fixed = total;
     // Mixed-precision path (5 limbs only): the block-wide GEMM carries the 3 high limbs, V = V_hi * 2^16 + V_lo.
     // lo_abs_sum = sum |V_lo| 2^-F bounds what the low limbs can add to any joint sum.
-    c->h_vfixed_hi.assign((size_t)c->Npad, 0);
-    c->total_fixed_hi = 0;
-    c->lo_abs_sum = 0;
+    c->wts.h_vfixed_hi.assign((size_t)c->Npad, 0);
+    c->wts.total_fixed_hi = 0;
+    c->wts.lo_abs_sum = 0;
     if (nlimbs == 5) {
         long double lo_abs = 0;
         for (int64_t s = 0; s < N; ++s) {
             const int64_t lo = (int64_t)dseq[s] + 256 * (int64_t)dseq[(size_t)c->Npad + s];
-            c->h_vfixed_hi[s] = (c->h_vfixed[s] - lo) / 65536;   // exact: the remainder is what limbs 2..4 encode
-            c->total_fixed_hi += c->h_vfixed_hi[s];
+            c->wts.h_vfixed_hi[s] = (c->wts.h_vfixed[s] - lo) / 65536;   // exact: the remainder is what limbs 2..4 encode
+            c->wts.total_fixed_hi += c->wts.h_vfixed_hi[s];
             lo_abs += (long double)(lo < 0 ? -lo : lo);
         }
-        c->lo_abs_sum = (double)(lo_abs * (long double)std::ldexp(1.0, -F));
+        c->wts.lo_abs_sum = (double)(lo_abs * (long double)std::ldexp(1.0, -F));
     }
     // Position order of the bit rows: ascending weight (ties by sequence), padding last.  A sum over sequences does not
     // care about their order; this one makes the sequences of one weight CLASS contiguous (class-wise popcounts of the
@@ -1025,40 +798,24 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
     {
         std::vector<int32_t> order((size_t)N);
         for (int64_t s = 0; s < N; ++s) order[(size_t)s] = (int32_t)s;
-        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return c->h_vfixed[x] < c->h_vfixed[y]; });
-        c->h_seq_perm.assign((size_t)c->Npad, -1);
-        for (int64_t q = 0; q < N; ++q) c->h_seq_perm[(size_t)q] = order[(size_t)q];
+        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return c->wts.h_vfixed[x] < c->wts.h_vfixed[y]; });
+        c->wts.h_seq_perm.assign((size_t)c->Npad, -1);
+        for (int64_t q = 0; q < N; ++q) c->wts.h_seq_perm[(size_t)q] = order[(size_t)q];
     }
     std::vector<int8_t> dig((size_t)nlimbs * c->Npad, 0);   // digits by position
     for (int j = 0; j < nlimbs; ++j)
-        for (int64_t q = 0; q < N; ++q) dig[(size_t)j * c->Npad + q] = dseq[(size_t)j * c->Npad + c->h_seq_perm[(size_t)q]];
-    if (int rc = c->seq_perm.reserve((size_t)c->Npad * 4)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->seq_perm.p, c->h_seq_perm.data(), (size_t)c->Npad * 4, hipMemcpyHostToDevice, c->stream));
+        for (int64_t q = 0; q < N; ++q) dig[(size_t)j * c->Npad + q] = dseq[(size_t)j * c->Npad + c->wts.h_seq_perm[(size_t)q]];
+    if (int rc = c->wts.seq_perm.reserve((size_t)c->Npad * 4)) return rc;
+    LDW_HIP(hipMemcpyAsync(c->wts.seq_perm.p, c->wts.h_seq_perm.data(), (size_t)c->Npad * 4, hipMemcpyHostToDevice, c->stream));
     if (int rc = prepare_apx_weights(c)) return rc;
-    if (int rc = c->digits.reserve(dig.size())) return rc;
-    if (int rc = c->vfixed.reserve((size_t)c->Npad * 8)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->digits.p, dig.data(), dig.size(), hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(c->vfixed.p, c->h_vfixed.data(), (size_t)c->Npad * 8, hipMemcpyHostToDevice, c->stream));
+    if (int rc = c->wts.digits.reserve(dig.size())) return rc;
+    if (int rc = c->wts.vfixed.reserve((size_t)c->Npad * 8)) return rc;
+    LDW_HIP(hipMemcpyAsync(c->wts.digits.p, dig.data(), dig.size(), hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->wts.vfixed.p, c->wts.h_vfixed.data(), (size_t)c->Npad * 8, hipMemcpyHostToDevice, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
-    c->have_weights = true;
-    c->rows_ready = false;
-    c->tab11_lo[0] = c->tab11_lo[1] = 0;   // the threshold tables belong to the old weights
+    c->new_weights();
     return LDW_OK;
 }
-
-}  // extern "C"
-
-// the host copy of new positions and what is known of their order; the order built from the old ones (ldw::pos_order) is dropped
-void ldw::set_pos_meta(ldw_ctx *c, const int32_t *POS, int64_t L) {
-    c->h_POS.assign(POS, POS + L);
-    c->pos_sorted = true;
-    for (int64_t i = 1; i < L && c->pos_sorted; ++i) c->pos_sorted = POS[i] >= POS[i - 1];
-    c->pos_strict = c->pos_sorted;
-    for (int64_t i = 1; i < L && c->pos_strict; ++i) c->pos_strict = POS[i] > POS[i - 1];
-    c->pos_ord.n_slots = 0;
-}
-
-extern "C" {
 
 int ldw_set_snp_meta(ldw_ctx *c, const double *r, const uint8_t *uqe, const int32_t *POS, const int32_t *paint, double g) {
     if (int rc = check_gpu(c)) return rc;
@@ -1068,40 +825,36 @@ int ldw_set_snp_meta(ldw_ctx *c, const double *r, const uint8_t *uqe, const int3
     LDW_REQUIRE(g > 0, LDW_ERR_ARG, "ldw_set_snp_meta: genome length g must be positive (snp.dat$g)");
     const int64_t L = c->L;
     for (int64_t i = 0; i < L * 5; ++i) LDW_REQUIRE(uqe[i] <= 1, LDW_ERR_ARG, "ldw_set_snp_meta: uqe must be 0/1");
-    if (int rc = c->r.reserve((size_t)L * 8)) return rc;
-    if (int rc = c->uqe.reserve((size_t)L * 5)) return rc;
-    if (int rc = c->POS.reserve((size_t)L * 4)) return rc;
-    if (int rc = c->paint.reserve((size_t)L * 4)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->r.p, r, (size_t)L * 8, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(c->uqe.p, uqe, (size_t)L * 5, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(c->POS.p, POS, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
-    if (paint) LDW_HIP(hipMemcpyAsync(c->paint.p, paint, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
-    else LDW_HIP(hipMemsetAsync(c->paint.p, 0, (size_t)L * 4, c->stream));
+    if (int rc = c->meta.r.reserve((size_t)L * 8)) return rc;
+    if (int rc = c->meta.uqe.reserve((size_t)L * 5)) return rc;
+    if (int rc = c->meta.POS.reserve((size_t)L * 4)) return rc;
+    if (int rc = c->meta.paint.reserve((size_t)L * 4)) return rc;
+    LDW_HIP(hipMemcpyAsync(c->meta.r.p, r, (size_t)L * 8, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->meta.uqe.p, uqe, (size_t)L * 5, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->meta.POS.p, POS, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
+    if (paint) LDW_HIP(hipMemcpyAsync(c->meta.paint.p, paint, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
+    else LDW_HIP(hipMemsetAsync(c->meta.paint.p, 0, (size_t)L * 4, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
-    c->h_r.assign(r, r + L);
-    c->r_min = r[0];
-    for (int64_t i = 1; i < L; ++i) c->r_min = r[i] < c->r_min ? r[i] : c->r_min;
-    ldw::set_pos_meta(c, POS, L);
-    if (paint) c->h_paint.assign(paint, paint + L);
-    else c->h_paint.assign((size_t)L, 0);
-    c->paint_min = c->paint_max = 0;
+    c->meta.h_r.assign(r, r + L);
+    c->meta.r_min = r[0];
+    for (int64_t i = 1; i < L; ++i) c->meta.r_min = r[i] < c->meta.r_min ? r[i] : c->meta.r_min;
+    c->meta.set_positions(POS, L);
+    if (paint) c->meta.h_paint.assign(paint, paint + L);
+    else c->meta.h_paint.assign((size_t)L, 0);
+    c->meta.paint_min = c->meta.paint_max = 0;
     if (paint) {
-        c->paint_min = c->paint_max = paint[0];
+        c->meta.paint_min = c->meta.paint_max = paint[0];
         for (int64_t i = 1; i < L; ++i) {
-            c->paint_min = paint[i] < c->paint_min ? paint[i] : c->paint_min;
-            c->paint_max = paint[i] > c->paint_max ? paint[i] : c->paint_max;
+            c->meta.paint_min = paint[i] < c->meta.paint_min ? paint[i] : c->meta.paint_min;
+            c->meta.paint_max = paint[i] > c->meta.paint_max ? paint[i] : c->meta.paint_max;
         }
     }
-    c->g = g;
-    c->have_meta = true;
-    c->rows_ready = false;
-    c->sr_total = -1;
-    c->sr_total_dist = -1;
-    c->sr_share_rows = -1;
+    c->meta.g = g;
+    c->new_meta();
     // r04: with the alignment and the weights in place the row map (indicator rows, marginals, per-SNP bounds: ensure_rows, ~9 ms at C4) is
     // built HERE — it belongs to handing over the data — instead of lazily inside the first block loop; a later ldw_set_weights
     // invalidates it again and the next pass rebuilds it
-    if (c->L > 0 && c->have_weights) return ldw::ensure_rows(c);
+    if (c->L > 0 && c->wts.have_weights) return ldw::ensure_rows(c);
     return LDW_OK;
 }
 
@@ -1195,7 +948,7 @@ static int slot_marginals(ldw_ctx *c, const std::vector<int64_t> &w, int shift, 
     if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
     if (he != hipSuccess) return ldw::hip_fail(he, what, __FILE__, __LINE__);
     for (int64_t a = 0; a < L; ++a) {
-        const uint32_t m = c->h_slot_meta[a];
+        const uint32_t m = c->rows.h_slot_meta[a];
         const int n = (int)(m & 7);
         for (int i = 0; i <= n; ++i) by_slot[a * 5 + i] = by_state[a * 5 + ((m >> (8 + 3 * i)) & 7)] >> shift;
     }
@@ -1207,51 +960,50 @@ static int slot_marginals(ldw_ctx *c, const std::vector<int64_t> &w, int shift, 
 // Marginals of the high-limb weights, by slot, for the screen of the MIXED-precision path — made when a block first takes that path (r04: the
 // default path never does, and building them eagerly cost 2.5 ms of every job's ldw_set_snp_meta).
 int ensure_hi_marginals(ldw_ctx *c) {
-    if (c->hi_ready || c->nlimbs != 5) return LDW_OK;
-    LDW_REQUIRE((int64_t)c->h_slot_meta.size() == c->L, LDW_ERR_STATE, "ensure_hi_marginals: the row map has not been built");
-    if (int rc = slot_marginals(c, c->h_vfixed_hi, 0, c->slot_pfix_hi, "high-limb marginals")) return rc;
-    c->hi_ready = true;
+    if (c->rows.hi_ready || c->wts.nlimbs != 5) return LDW_OK;
+    LDW_REQUIRE((int64_t)c->rows.h_slot_meta.size() == c->L, LDW_ERR_STATE, "ensure_hi_marginals: the row map has not been built");
+    if (int rc = slot_marginals(c, c->wts.h_vfixed_hi, 0, c->rows.slot_pfix_hi, "high-limb marginals")) return rc;
+    c->rows.hi_ready = true;
     return LDW_OK;
 }
 
 int ensure_rows(ldw_ctx *c) {
-    if (c->rows_ready) return LDW_OK;
-    static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
-    const auto t_rows0 = std::chrono::steady_clock::now();
+    if (c->rows.rows_ready) return LDW_OK;
+    const auto t_rows0 = HostClock::now();
     auto lap = [&](const char *what) {
-        if (!host_timing) return;
+        if (!host_timing()) return;
         (void)hipStreamSynchronize(c->stream);
-        fprintf(stderr, "[ldw] ensure_rows: %.2f ms at %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_rows0).count(), what);
+        fprintf(stderr, "[ldw] ensure_rows: %.2f ms at %s\n", HostClock::ms(t_rows0, HostClock::now()), what);
     };
-    LDW_REQUIRE(ldw::have_alignment(c) && c->have_weights && c->have_meta, LDW_ERR_STATE,
+    LDW_REQUIRE(ldw::have_alignment(c) && c->wts.have_weights && c->meta.have_meta, LDW_ERR_STATE,
                 "MI needs the alignment, the weights and the SNP meta data to be set first");
     const int64_t L = c->L, Npad = c->Npad;
-    if (int rc = c->counts.reserve((size_t)L * 20)) return rc;
-    if (int rc = c->slot_pfix.reserve((size_t)L * 40)) return rc;
-    if (int rc = c->pfix_state.reserve((size_t)L * 40)) return rc;
-    int64_t *d_pfix_state = c->pfix_state.as<int64_t>();  // [L][5] by state
+    if (int rc = c->rows.counts.reserve((size_t)L * 20)) return rc;
+    if (int rc = c->rows.slot_pfix.reserve((size_t)L * 40)) return rc;
+    if (int rc = c->rows.pfix_state.reserve((size_t)L * 40)) return rc;
+    int64_t *d_pfix_state = c->rows.pfix_state.as<int64_t>();  // [L][5] by state
     hipLaunchKernelGGL(k_counts_marginals, dim3((unsigned)((L + 3) / 4)), dim3(256), 0, c->stream,
-                       c->states.as<uint8_t>(), L, Npad, c->vfixed.as<int64_t>(), c->counts.as<int32_t>(), d_pfix_state);
+                       c->states.as<uint8_t>(), L, Npad, c->wts.vfixed.as<int64_t>(), c->rows.counts.as<int32_t>(), d_pfix_state);
     LDW_HIP(hipGetLastError());
-    c->h_counts.resize((size_t)L * 5);
+    c->rows.h_counts.resize((size_t)L * 5);
     std::vector<int64_t> pfs((size_t)L * 5);
     std::vector<uint8_t> uqe((size_t)L * 5);
-    LDW_HIP(hipMemcpyAsync(c->h_counts.data(), c->counts.p, (size_t)L * 20, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->rows.h_counts.data(), c->rows.counts.p, (size_t)L * 20, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(pfs.data(), d_pfix_state, (size_t)L * 40, hipMemcpyDeviceToHost, c->stream));
-    LDW_HIP(hipMemcpyAsync(uqe.data(), c->uqe.p, (size_t)L * 5, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipMemcpyAsync(uqe.data(), c->meta.uqe.p, (size_t)L * 5, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     lap("counts + exact marginals fetched");
 
     // Slots of SNP a: one per state that is present (count > 0) or flagged in uqe.  The most frequent
     // present state is the "drop" slot: it gets no indicator row, its joint cells follow from the
     // marginals by exact integer subtraction.  Rows are the remaining slots in increasing state order.
-    c->h_row0.assign((size_t)L + 1, 0);
+    c->rows.h_row0.assign((size_t)L + 1, 0);
     std::vector<uint32_t> meta((size_t)L);
     std::vector<int64_t> spf((size_t)L * 5, 0);
     std::vector<int32_t> rowinfo;
     rowinfo.reserve((size_t)L * 2);
     for (int64_t a = 0; a < L; ++a) {
-        const int32_t *cnt = &c->h_counts[a * 5];
+        const int32_t *cnt = &c->rows.h_counts[a * 5];
         int drop = -1;
         for (int x = 0; x < 5; ++x)
             if (cnt[x] > 0 && (drop < 0 || cnt[x] > cnt[drop])) drop = x;
@@ -1273,52 +1025,46 @@ int ensure_rows(ldw_ctx *c) {
         spf[a * 5 + nrows] = pfs[a * 5 + drop];
         m |= (uint32_t)nrows;
         meta[a] = m;
-        c->h_row0[a + 1] = c->h_row0[a] + nrows;
+        c->rows.h_row0[a + 1] = c->rows.h_row0[a] + nrows;
     }
-    c->R = c->h_row0[L];
-    c->h_slot_meta = meta;
-    c->h_minor_w.assign((size_t)L, INT64_MAX);   // order key of the tile pruning (prep_block): rows with a table bin first, by weight
+    c->rows.R = c->rows.h_row0[L];
+    c->rows.h_slot_meta = meta;
+    c->rows.h_minor_w.assign((size_t)L, INT64_MAX);   // order key of the tile pruning (prep_block): rows with a table bin first, by weight
     for (int64_t a = 0; a < L; ++a)
-        if ((meta[a] & 7u) == 1u && ((meta[a] >> 3) & 3u) == 3u && c->h_r[(size_t)a] == 2.0) c->h_minor_w[(size_t)a] = spf[a * 5];
-    c->order_cache.clear();
-    c->h_span_bad.assign((size_t)L + 1, 0);
+        if ((meta[a] & 7u) == 1u && ((meta[a] >> 3) & 3u) == 3u && c->meta.h_r[(size_t)a] == 2.0) c->rows.h_minor_w[(size_t)a] = spf[a * 5];
+    c->rows.h_span_bad.assign((size_t)L + 1, 0);
     for (int64_t a = 0; a < L; ++a) {
         const int n = (int)(meta[a] & 7u);
         const bool bad = n == 0 || ((n == 1 || n == 2) && (((meta[a] >> 3) & ((2u << n) - 1u)) != ((2u << n) - 1u)));
-        c->h_span_bad[(size_t)a + 1] = c->h_span_bad[(size_t)a] + (bad ? 1 : 0);
+        c->rows.h_span_bad[(size_t)a + 1] = c->rows.h_span_bad[(size_t)a] + (bad ? 1 : 0);
     }
-    const int64_t R = c->R;
+    const int64_t R = c->rows.R;
     lap("slot maps built on the host");
-    if (int rc = c->row0.reserve((size_t)(L + 1) * 4)) return rc;
-    if (int rc = c->slot_meta.reserve((size_t)L * 4)) return rc;
-    if (int rc = c->Mbits.reserve((size_t)(R + TILE) * c->KW * 8)) return rc;
+    if (int rc = c->rows.row0.reserve((size_t)(L + 1) * 4)) return rc;
+    if (int rc = c->rows.slot_meta.reserve((size_t)L * 4)) return rc;
+    if (int rc = c->rows.Mbits.reserve((size_t)(R + TILE) * c->KW * 8)) return rc;
     if (int rc = c->small.reserve((size_t)(R + 1) * 4)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->row0.p, c->h_row0.data(), (size_t)(L + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(c->slot_meta.p, meta.data(), (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(c->slot_pfix.p, spf.data(), (size_t)L * 40, hipMemcpyHostToDevice, c->stream));
-    c->hi_ready = false;   // (the high-limb marginals of the mixed-precision path are made when a block first takes that path: ensure_hi_marginals)
-    if (c->apx_ok) {   // marginals of the approximate weights V' = a b 2^e by slot, in the accumulators' final unit 2^e_last (floor)
-        if (int rc = slot_marginals(c, c->h_vapx, c->apx_e_last, c->slot_papx, "approximate-weight marginals")) return rc;
+    LDW_HIP(hipMemcpyAsync(c->rows.row0.p, c->rows.h_row0.data(), (size_t)(L + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->rows.slot_meta.p, meta.data(), (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->rows.slot_pfix.p, spf.data(), (size_t)L * 40, hipMemcpyHostToDevice, c->stream));
+    if (c->apx.apx_ok) {   // marginals of the approximate weights V' = a b 2^e by slot, in the accumulators' final unit 2^e_last (floor)
+        if (int rc = slot_marginals(c, c->apx.h_vapx, c->apx.apx_e_last, c->rows.slot_papx, "approximate-weight marginals")) return rc;
     }
     // rows R .. R+TILE-1 stay zero: tile padding of the row lists points at row R
-    LDW_HIP(hipMemsetAsync(c->Mbits.as<uint64_t>() + (size_t)R * c->KW, 0, (size_t)TILE * c->KW * 8, c->stream));
+    LDW_HIP(hipMemsetAsync(c->rows.Mbits.as<uint64_t>() + (size_t)R * c->KW, 0, (size_t)TILE * c->KW * 8, c->stream));
     lap("approximate marginals");
     if (R > 0) {
         LDW_HIP(hipMemcpyAsync(c->small.p, rowinfo.data(), (size_t)R * 4, hipMemcpyHostToDevice, c->stream));
         LDW_REQUIRE(R < 2147483647LL, LDW_ERR_ARG, "too many indicator rows");
         if (int rc = fill_rows_bits(c, c->small.as<int32_t>(), R)) return rc;
     }
-    if (int rc = c->snp_sup.reserve((size_t)L * 32)) return rc;
-    hipLaunchKernelGGL(k_snp_sup, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, c->stream, L, c->slot_meta.as<uint32_t>(), c->slot_pfix.as<int64_t>(),
-                       c->r.as<double>(), std::ldexp(1.0, -c->frac_bits), c->neff, c->r_min, c->snp_sup.as<double>());
+    if (int rc = c->rows.snp_sup.reserve((size_t)L * 32)) return rc;
+    hipLaunchKernelGGL(k_snp_sup, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, c->stream, L, c->rows.slot_meta.as<uint32_t>(), c->rows.slot_pfix.as<int64_t>(),
+                       c->meta.r.as<double>(), std::ldexp(1.0, -c->wts.frac_bits), c->wts.neff, c->meta.r_min, c->rows.snp_sup.as<double>());
     LDW_HIP(hipGetLastError());
     LDW_HIP(hipStreamSynchronize(c->stream));
     lap("bit rows + per-SNP bounds");
-    c->rows_ready = true;
-    c->spec_B_next[0] = c->spec_B_next[1] = -1;   // bucket guesses of an earlier alignment / weighting say nothing about this one
-    c->spec_seen[0] = c->spec_seen[1] = false;
-    c->spec_probed[0] = c->spec_probed[1] = false;
-    c->spec_hist_n[0] = c->spec_hist_n[1] = 0;
+    c->rows_rebuilt();
     return LDW_OK;
 }
 

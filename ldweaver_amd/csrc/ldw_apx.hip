@@ -49,9 +49,9 @@ int prepare_apx_weights(ldw_ctx *c) {
     static const ProdTable PT;
     const int64_t N = c->N, Npad = c->Npad;
     const int M2 = (int)(Npad / 128);
-    c->apx_ok = false;
+    c->apx.apx_ok = false;
     std::vector<int64_t> Vp((size_t)Npad, 0);
-    for (int64_t p = 0; p < N; ++p) Vp[(size_t)p] = c->h_vfixed[(size_t)c->h_seq_perm[(size_t)p]];
+    for (int64_t p = 0; p < N; ++p) Vp[(size_t)p] = c->wts.h_vfixed[(size_t)c->wts.h_seq_perm[(size_t)p]];
     // block exponents, one per MFMA k-step of 32 consecutive positions (r03; r02 had one per macro step of 128, which put weights
     // 1/128 .. 1 of an alignment with N distinct weights under ONE exponent: delta 6e-3, path off): smallest non-decreasing e(k)
     // with ceil(Vmax(k) / 2^e) <= APX_PROD_CAP.  Products of two 7-bit digits are dense up to ~12000 (worst relative half-gap
@@ -68,7 +68,7 @@ int prepare_apx_weights(ldw_ctx *c) {
         std::fill(sh.begin(), sh.end(), 0);
         std::fill(da.begin(), da.end(), 0);
         std::fill(db.begin(), db.end(), 0);
-        c->h_vapx.assign((size_t)Npad, 0);
+        c->apx.h_vapx.assign((size_t)Npad, 0);
         int e_prev = 0;
         transitions = 0;
         for (int k0 = 0; k0 < S4; k0 += gran) {
@@ -92,23 +92,23 @@ int prepare_apx_weights(ldw_ctx *c) {
             da[(size_t)p] = PT.a[k];
             db[(size_t)p] = PT.b[k];
             const int64_t Va = (int64_t)PT.val[k] << e;
-            c->h_vapx[(size_t)c->h_seq_perm[(size_t)p]] = Va;
+            c->apx.h_vapx[(size_t)c->wts.h_seq_perm[(size_t)p]] = Va;
             delta = std::max(delta, std::fabs((double)(Va - V)) / (double)V);
         }
     };
     assign(4);
-    c->apx_fine = false;
+    c->apx.apx_fine = false;
     if (delta > 1.5e-3) {
         assign(1);
-        c->apx_fine = true;
+        c->apx.apx_fine = true;
     }
-    c->apx_delta = delta;
-    c->apx_e_last = S4 > 0 ? em[(size_t)S4 - 1] : 0;
-    c->apx_transitions = transitions;
+    c->apx.apx_delta = delta;
+    c->apx.apx_e_last = S4 > 0 ? em[(size_t)S4 - 1] : 0;
+    c->apx.apx_transitions = transitions;
     // units of 2^e_last a GEMM entry can have lost to the truncations: < 1 unit of 2^e(m) at every transition into macro step m
-    c->apx_lost_units = 0;
+    c->apx.apx_lost_units = 0;
     for (int k = 1; k < S4; ++k)
-        if (sh[(size_t)k] > 0) c->apx_lost_units += std::ldexp(1.0, em[(size_t)k] - c->apx_e_last);
+        if (sh[(size_t)k] > 0) c->apx.apx_lost_units += std::ldexp(1.0, em[(size_t)k] - c->apx.apx_e_last);
     // weight classes = runs of equal V along the positions; segments = (32-bit word, class) intersections
     std::vector<PopSeg> segs;
     std::vector<int32_t> wbeg((size_t)(Npad / 32) + 1, 0);
@@ -134,40 +134,40 @@ int prepare_apx_weights(ldw_ctx *c) {
         for (auto &s : per_word[w]) segs.push_back(s);
     }
     wbeg[per_word.size()] = (int32_t)segs.size();
-    c->n_pop_segs = (int)segs.size();
-    c->n_classes = n_classes;
+    c->apx.n_pop_segs = (int)segs.size();
+    c->apx.n_classes = n_classes;
     if (segs.empty()) segs.push_back(PopSeg{0, 0, 0});
-    if (int rc = c->dig_a.reserve((size_t)Npad)) return rc;
-    if (int rc = c->dig_b.reserve((size_t)Npad)) return rc;
-    if (int rc = c->apx_shift.reserve((size_t)std::max(S4, 4) * 4)) return rc;
-    if (int rc = c->pop_segs.reserve(segs.size() * sizeof(PopSeg))) return rc;
-    if (int rc = c->pop_wbeg.reserve(wbeg.size() * 4)) return rc;
+    if (int rc = c->apx.dig_a.reserve((size_t)Npad)) return rc;
+    if (int rc = c->apx.dig_b.reserve((size_t)Npad)) return rc;
+    if (int rc = c->apx.apx_shift.reserve((size_t)std::max(S4, 4) * 4)) return rc;
+    if (int rc = c->apx.pop_segs.reserve(segs.size() * sizeof(PopSeg))) return rc;
+    if (int rc = c->apx.pop_wbeg.reserve(wbeg.size() * 4)) return rc;
     {   // r05: the fixed-point weight of every POSITION (0 in the padding) for the bit-walking pair sums of weightings with many classes (k_pair_sums_bits)
         std::vector<int64_t> vpos((size_t)Npad, 0);
         for (int64_t q = 0; q < N; ++q) vpos[(size_t)q] = Vp[(size_t)q];
-        if (int rc = c->pop_vpos.reserve((size_t)Npad * 8)) return rc;
-        LDW_HIP(hipMemcpyAsync(c->pop_vpos.p, vpos.data(), (size_t)Npad * 8, hipMemcpyHostToDevice, c->stream));
+        if (int rc = c->apx.pop_vpos.reserve((size_t)Npad * 8)) return rc;
+        LDW_HIP(hipMemcpyAsync(c->apx.pop_vpos.p, vpos.data(), (size_t)Npad * 8, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));   // (vpos is on this frame)
     }
-    LDW_HIP(hipMemcpyAsync(c->dig_a.p, da.data(), (size_t)Npad, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(c->dig_b.p, db.data(), (size_t)Npad, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(c->apx_shift.p, sh.data(), (size_t)S4 * 4, hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(c->pop_segs.p, segs.data(), segs.size() * sizeof(PopSeg), hipMemcpyHostToDevice, c->stream));
-    LDW_HIP(hipMemcpyAsync(c->pop_wbeg.p, wbeg.data(), wbeg.size() * 4, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->apx.dig_a.p, da.data(), (size_t)Npad, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->apx.dig_b.p, db.data(), (size_t)Npad, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->apx.apx_shift.p, sh.data(), (size_t)S4 * 4, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->apx.pop_segs.p, segs.data(), segs.size() * sizeof(PopSeg), hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(c->apx.pop_wbeg.p, wbeg.data(), wbeg.size() * 4, hipMemcpyHostToDevice, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     // The path pays when the approximation is tight enough for the screen to dismiss almost everything (its margin grows with
     // delta); the digit arrays of the GEMM must fit in LDS.  Any weights qualify: with many distinct values the popcount sums of
     // the listed pairs walk more segments per word, which is still cheap for the few pairs that are listed.
     // (r03 also required the popcount segment tables of k_pair_sums to fit 60 000 B of LDS, which switched the path off for ~3700 and more
     // distinct weights; the kernel now reads larger tables from global memory)
-    c->apx_ok = delta <= 4e-3 && Npad <= 30720 && M2 > 0;
+    c->apx.apx_ok = delta <= 4e-3 && Npad <= 30720 && M2 > 0;
     {
         char why[160];
-        if (c->apx_ok) snprintf(why, sizeof(why), c->apx_fine ? "ok (block exponents per 32 positions)" : "ok");
+        if (c->apx.apx_ok) snprintf(why, sizeof(why), c->apx.apx_fine ? "ok (block exponents per 32 positions)" : "ok");
         else if (!(delta <= 4e-3)) snprintf(why, sizeof(why), "delta %.3g > 4e-03 (dual-digit weights too coarse)", delta);
         else if (Npad > 30720) snprintf(why, sizeof(why), "Npad %lld > 30720 (digit arrays exceed the GEMM's LDS)", (long long)Npad);
         else snprintf(why, sizeof(why), "no macro step (Npad %lld)", (long long)Npad);
-        c->apx_gate = why;
+        c->apx.apx_gate = why;
     }
     return LDW_OK;
 }
@@ -221,8 +221,8 @@ __global__ __launch_bounds__(256) void k_pack_panel(const uint64_t *__restrict__
 
 int launch_pack_panel(ldw_ctx *c, const int32_t *rowlist, int Rpad, uint64_t *panel, hipStream_t st, const int32_t *rowlist2, int Rpad2, uint64_t *panel2) {
     const int rmax = (rowlist2 && Rpad2 > Rpad) ? Rpad2 : Rpad;
-    hipLaunchKernelGGL(k_pack_panel, dim3((unsigned)((rmax + 63) / 64), rowlist2 ? 2u : 1u), dim3(256), 0, st, c->Mbits.as<uint64_t>(), c->KW, rowlist, Rpad,
-                       (int)(c->KW / 2), panel, c->apx_fine ? 1 : 0, rowlist2, Rpad2, panel2);
+    hipLaunchKernelGGL(k_pack_panel, dim3((unsigned)((rmax + 63) / 64), rowlist2 ? 2u : 1u), dim3(256), 0, st, c->rows.Mbits.as<uint64_t>(), c->KW, rowlist, Rpad,
+                       (int)(c->KW / 2), panel, c->apx.apx_fine ? 1 : 0, rowlist2, Rpad2, panel2);
     LDW_HIP(hipGetLastError());
     return LDW_OK;
 }
@@ -607,12 +607,12 @@ int launch_gemm_apx(ldw_ctx *c, const ApxGemmArgs &P, hipStream_t st) {
             if (!P.lower_only) waves += ntx;
             else for (int tx = 0; tx < ntx; ++tx) waves += (tx * TWd + TWd - 1 < ty * TH) ? 0 : 1;
         }
-        c->gemm_stat[0] += 1;
-        if (P.fuse) c->gemm_stat[5] += 1;
-        c->gemm_stat[1] += 2.0 * (double)waves * TH * TWd * ((double)P.M2 * 128.0);
+        c->cnt.gemm_stat[0] += 1;
+        if (P.fuse) c->cnt.gemm_stat[5] += 1;
+        c->cnt.gemm_stat[1] += 2.0 * (double)waves * TH * TWd * ((double)P.M2 * 128.0);
         if (P.fuse && P.skip_ctr) {   // the tiles the kernel prunes are taken off again when the counter is read (ldw_gemm_stats, ldw_links_end)
             c->apx_ops_per_wave = 2.0 * TH * TWd * ((double)P.M2 * 128.0);
-            c->apx_waves_total += waves;
+            c->cnt.apx_waves_total += waves;
         }
     }
     return LDW_OK;
@@ -988,14 +988,14 @@ __global__ __launch_bounds__(256) void k_pair_mi(PairArgs P) {
 int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, int64_t *sums, hipStream_t st) {
     PairArgs P;
     memset(&P, 0, sizeof(P));
-    P.Mbits = c->Mbits.as<uint64_t>();
+    P.Mbits = c->rows.Mbits.as<uint64_t>();
     P.KW = c->KW;
     P.nwords = (int)(c->KW * 2);
-    P.nseg = c->n_pop_segs;
-    P.segs = c->pop_segs.as<PopSeg>();
-    P.wbeg = c->pop_wbeg.as<int32_t>();
-    P.row0 = c->row0.as<int32_t>();
-    P.zero_row = (int32_t)c->R;
+    P.nseg = c->apx.n_pop_segs;
+    P.segs = c->apx.pop_segs.as<PopSeg>();
+    P.wbeg = c->apx.pop_wbeg.as<int32_t>();
+    P.row0 = c->rows.row0.as<int32_t>();
+    P.zero_row = (int32_t)c->rows.R;
     P.sums = sums;
     P.A = A;
     P.ghist = ghist;
@@ -1011,22 +1011,22 @@ int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, 
     // (which form: the class-wise one costs a popcount per SEGMENT — 1.3 segments per word with C4's 57 clonal classes —, the bit walk an LDS read per
     // co-occurring position; from ~8 segments per word on, i.e. weightings whose classes are a few sequences each, the bits are fewer than the segments)
     const bool many_classes = !P.seg_in_lds || P.nseg >= 8 * P.nwords;
-    if (many_classes && !bits_off && lds_bits <= 160 * 1024 && c->pop_vpos.p) {
+    if (many_classes && !bits_off && lds_bits <= 160 * 1024 && c->apx.pop_vpos.p) {
         if (lds_bits > 64 * 1024 && !c->pair_bits_attr) {
             LDW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_sums_bits<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             LDW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_sums_bits<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             c->pair_bits_attr = true;
         }
-        hipLaunchKernelGGL(k_pair_sums_bits<false>, dim3(256, PAIR_SHARDS, 4), dim3(256), lds_bits, st, P, c->pop_vpos.as<int64_t>(), stride);
-        hipLaunchKernelGGL(k_pair_sums_bits<true>, dim3(256, PAIR_SHARDS, 1), dim3(256), lds_bits, st, P, c->pop_vpos.as<int64_t>(), stride);
-        c->form_launches[lds_bits > 64 * 1024 ? 1 : 0] += 2;
+        hipLaunchKernelGGL(k_pair_sums_bits<false>, dim3(256, PAIR_SHARDS, 4), dim3(256), lds_bits, st, P, c->apx.pop_vpos.as<int64_t>(), stride);
+        hipLaunchKernelGGL(k_pair_sums_bits<true>, dim3(256, PAIR_SHARDS, 1), dim3(256), lds_bits, st, P, c->apx.pop_vpos.as<int64_t>(), stride);
+        c->cnt.form_launches[lds_bits > 64 * 1024 ? 1 : 0] += 2;
     } else {
         // (grid: r06 — 512 / 1024 workgroups per list instead of 256: 67 -> 61 and 34 -> 23 us per launch; 128 / 64 / 32: 96 / 150 / 236 us.  A 1-D grid whose
         // waves share the pairs of all lists evenly was built too: no better (64 / 42 us) — the long launches are not a matter of balance.  LDW_PAIR_GRID: A/B)
         static const unsigned gx_env = [] { const char *e = getenv("LDW_PAIR_GRID"); return e ? (unsigned)atoi(e) : 0u; }();
         hipLaunchKernelGGL(k_pair_sums<false>, dim3(gx_env ? gx_env : 512u, PAIR_SHARDS, 4), dim3(256), lds, st, P);
         hipLaunchKernelGGL(k_pair_sums<true>, dim3(gx_env ? gx_env : 1024u, PAIR_SHARDS, 1), dim3(256), lds, st, P);
-        c->form_launches[P.seg_in_lds ? 2 : 3] += 2;
+        c->cnt.form_launches[P.seg_in_lds ? 2 : 3] += 2;
     }
     hipLaunchKernelGGL(k_pair_mi, dim3(64, PAIR_SHARDS, PAIR_PATHS), dim3(256), 0, st, P);
     LDW_HIP(hipGetLastError());

@@ -197,7 +197,7 @@ int ldw_cds_variation(ldw_ctx *c, const int32_t *POS, int64_t L, const char *ref
         LDW_HIP(hipMemcpyAsync(d_se + ncds, cds_end, (size_t)ncds * 4, hipMemcpyHostToDevice, c->stream));
     }
     if (int rc = sort_positions(c, POS, L, end_bit, d_pos, d_iota, spos, sidx, tmp, sort_bytes)) return rc;
-    LDW_LAUNCH(k_cds_snp, grid_of(L), dim3(256), 0, c->stream, c->counts.as<int32_t>(), d_pos, d_ref, L, d_sv, d_alt, d_rc);
+    LDW_LAUNCH(k_cds_snp, grid_of(L), dim3(256), 0, c->stream, c->rows.counts.as<int32_t>(), d_pos, d_ref, L, d_sv, d_alt, d_rc);
     LDW_LAUNCH(k_cds_gather, grid_of(L + 1), dim3(256), 0, c->stream, sidx, d_sv, L, d_vs);
     LDW_HIP((prim_exclusive_sum<int64_t>(tmp, scan_bytes, d_vs, d_P, (size_t)L + 1, c->stream)));
     if (ncds > 0) {

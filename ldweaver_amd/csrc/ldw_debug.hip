@@ -109,16 +109,16 @@ extern "C" {
 int ldw_debug_apx_params(ldw_ctx *c, double out[20], int64_t *vfixed_out, int64_t *vapx_out, int64_t capacity) {
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(out, LDW_ERR_ARG, "ldw_debug_apx_params: null output");
-    LDW_REQUIRE(c->have_weights, LDW_ERR_STATE, "ldw_debug_apx_params: no weights (ldw_set_weights)");
+    LDW_REQUIRE(c->wts.have_weights, LDW_ERR_STATE, "ldw_debug_apx_params: no weights (ldw_set_weights)");
     EmitArgs E;
     memset(&E, 0, sizeof(E));
     apx_screen_params(c, E);
-    out[0] = c->frac_bits;
-    out[1] = c->apx_e_last;
-    out[2] = c->apx_delta;
-    out[3] = c->apx_lost_units;
-    out[4] = (double)c->total_fixed;
-    out[5] = c->neff;
+    out[0] = c->wts.frac_bits;
+    out[1] = c->apx.apx_e_last;
+    out[2] = c->apx.apx_delta;
+    out[3] = c->apx.apx_lost_units;
+    out[4] = (double)c->wts.total_fixed;
+    out[5] = c->wts.neff;
     out[6] = E.apx_EG;
     out[7] = E.apx_dfac;
     out[8] = E.apx_s1;
@@ -128,24 +128,24 @@ int ldw_debug_apx_params(ldw_ctx *c, double out[20], int64_t *vfixed_out, int64_
     out[12] = E.scr_scale;
     {   // the exact-limb screen reads the top 31 bits of a sum (make_emit_args, all limbs in the block-wide GEMM)
         int bits = 0;
-        while (bits < 62 && (c->total_fixed >> bits) != 0) ++bits;
+        while (bits < 62 && (c->wts.total_fixed >> bits) != 0) ++bits;
         const int shift = bits > 31 ? bits - 31 : 0;
         out[13] = shift;
-        out[14] = std::ldexp(1.0, shift - c->frac_bits);
+        out[14] = std::ldexp(1.0, shift - c->wts.frac_bits);
     }
-    out[15] = (c->apx_ok ? 1 : 0) | (c->apx_fine ? 2 : 0);
-    out[16] = c->lo_abs_sum;   // mixed-precision path: sum_s |V_lo,s| 2^-F and the margin it adds to the screen (lo_bound, ldw_mi_items.inc)
+    out[15] = (c->apx.apx_ok ? 1 : 0) | (c->apx.apx_fine ? 2 : 0);
+    out[16] = c->wts.lo_abs_sum;   // mixed-precision path: sum_s |V_lo,s| 2^-F and the margin it adds to the screen (lo_bound, ldw_mi_items.inc)
     {
-        const double den = c->neff > 1.0 ? c->neff : 1.0;
-        out[17] = c->lo_abs_sum * (2.0 * std::log(den + 12.5) + 3.0) / den;
+        const double den = c->wts.neff > 1.0 ? c->wts.neff : 1.0;
+        out[17] = c->wts.lo_abs_sum * (2.0 * std::log(den + 12.5) + 3.0) / den;
     }
     out[18] = E.apx_MU;
-    out[19] = c->nlimbs;
+    out[19] = c->wts.nlimbs;
     if (vfixed_out || vapx_out) {
         LDW_REQUIRE(capacity >= c->N, LDW_ERR_SIZE, "ldw_debug_apx_params: capacity %lld < N %lld", (long long)capacity, (long long)c->N);
         for (int64_t s = 0; s < c->N; ++s) {
-            if (vfixed_out) vfixed_out[s] = c->h_vfixed[(size_t)s];
-            if (vapx_out) vapx_out[s] = (size_t)s < c->h_vapx.size() ? c->h_vapx[(size_t)s] : 0;
+            if (vfixed_out) vfixed_out[s] = c->wts.h_vfixed[(size_t)s];
+            if (vapx_out) vapx_out[s] = (size_t)s < c->apx.h_vapx.size() ? c->apx.h_vapx[(size_t)s] : 0;
         }
     }
     return LDW_OK;
@@ -155,8 +155,8 @@ int ldw_debug_rows(ldw_ctx *c, int32_t *row0_out, uint32_t *slot_meta_out, int64
     if (int rc = check_gpu(c)) return rc;
     if (int rc = ensure_rows(c)) return rc;
     LDW_REQUIRE(row0_out && slot_meta_out && capacity >= c->L + 1, LDW_ERR_ARG, "ldw_debug_rows: need L + 1 = %lld entries", (long long)c->L + 1);
-    memcpy(row0_out, c->h_row0.data(), (size_t)(c->L + 1) * 4);
-    memcpy(slot_meta_out, c->h_slot_meta.data(), (size_t)c->L * 4);
+    memcpy(row0_out, c->rows.h_row0.data(), (size_t)(c->L + 1) * 4);
+    memcpy(slot_meta_out, c->rows.h_slot_meta.data(), (size_t)c->L * 4);
     return LDW_OK;
 }
 
@@ -165,11 +165,11 @@ int ldw_debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t
     if (int rc = join_prepare(c)) return rc;
     if (int rc = ensure_rows(c)) return rc;
     LDW_REQUIRE(rows_t && rows_f && out && nrt > 0 && nrf > 0 && nrt <= 8192 && nrf <= 8192, LDW_ERR_ARG, "ldw_debug_apx_gemm: bad argument");
-    LDW_REQUIRE(c->apx_ok, LDW_ERR_STATE, "ldw_debug_apx_gemm: the weights do not allow the approximate path (%s)", c->apx_gate.c_str());
-    for (int k = 0; k < nrt; ++k) LDW_REQUIRE(rows_t[k] >= 0 && rows_t[k] <= c->R, LDW_ERR_ARG, "ldw_debug_apx_gemm: to-side row %d = %d outside 0..R", k, rows_t[k]);
-    for (int k = 0; k < nrf; ++k) LDW_REQUIRE(rows_f[k] >= 0 && rows_f[k] <= c->R, LDW_ERR_ARG, "ldw_debug_apx_gemm: from-side row %d = %d outside 0..R", k, rows_f[k]);
+    LDW_REQUIRE(c->apx.apx_ok, LDW_ERR_STATE, "ldw_debug_apx_gemm: the weights do not allow the approximate path (%s)", c->apx.apx_gate.c_str());
+    for (int k = 0; k < nrt; ++k) LDW_REQUIRE(rows_t[k] >= 0 && rows_t[k] <= c->rows.R, LDW_ERR_ARG, "ldw_debug_apx_gemm: to-side row %d = %d outside 0..R", k, rows_t[k]);
+    for (int k = 0; k < nrf; ++k) LDW_REQUIRE(rows_f[k] >= 0 && rows_f[k] <= c->rows.R, LDW_ERR_ARG, "ldw_debug_apx_gemm: from-side row %d = %d outside 0..R", k, rows_f[k]);
     const int RTpad = (nrt + APX_TW - 1) / APX_TW * APX_TW, RFpad = (nrf + APX_TW - 1) / APX_TW * APX_TW, M2 = (int)(c->KW / 2);
-    std::vector<int32_t> rl((size_t)RTpad + RFpad, (int32_t)c->R);   // padding -> the all-zero row R
+    std::vector<int32_t> rl((size_t)RTpad + RFpad, (int32_t)c->rows.R);   // padding -> the all-zero row R
     std::copy(rows_t, rows_t + nrt, rl.begin());
     std::copy(rows_f, rows_f + nrf, rl.begin() + RTpad);
     DevBuf d_rl, d_pt, d_pf, d_G;
@@ -187,11 +187,11 @@ int ldw_debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t
     P.RTpad = RTpad;
     P.RFpad = RFpad;
     P.M2 = M2;
-    P.dig_a = c->dig_a.as<uint8_t>();
-    P.dig_b = c->dig_b.as<uint8_t>();
-    P.shift = c->apx_shift.as<int32_t>();
+    P.dig_a = c->apx.dig_a.as<uint8_t>();
+    P.dig_b = c->apx.dig_b.as<uint8_t>();
+    P.shift = c->apx.apx_shift.as<int32_t>();
     P.G = d_G.as<int32_t>();
-    P.fine = c->apx_fine ? 1 : 0;
+    P.fine = c->apx.apx_fine ? 1 : 0;
     if (int r2 = launch_gemm_apx(c, P, c->stream)) return r2;
     std::vector<int32_t> h((size_t)RTpad * RFpad);
     LDW_HIP(hipMemcpyAsync(h.data(), d_G.p, h.size() * 4, hipMemcpyDeviceToHost, c->stream));

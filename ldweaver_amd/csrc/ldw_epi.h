@@ -129,18 +129,18 @@ struct EmitArgs {
 // weights and the units lost to truncation.  One place for the engine (make_emit_args, ldw_mi_items.inc) and the test hook (ldw_debug_apx_params):
 // BOUNDS.md 3 states what each constant has to cover.
 inline void apx_screen_params(const ldw_ctx *c, EmitArgs &E) {
-    const double den = c->neff > 1.0 ? c->neff : 1.0;
+    const double den = c->wts.neff > 1.0 ? c->wts.neff : 1.0;
     E.apx = 1;
-    E.apx_EG = (float)(c->apx_lost_units * 1.001);
-    E.apx_dfac = (float)(1.01 * c->apx_delta / (1.0 - c->apx_delta));
-    E.apx_unit = std::ldexp(1.0, c->apx_e_last - c->frac_bits);
-    E.apx_s1 = (float)(E.apx_unit * (2.0 * std::log(den + 12.5) + 2.1) / (1.0 - c->apx_delta) * 1.01);
+    E.apx_EG = (float)(c->apx.apx_lost_units * 1.001);
+    E.apx_dfac = (float)(1.01 * c->apx.apx_delta / (1.0 - c->apx.apx_delta));
+    E.apx_unit = std::ldexp(1.0, c->apx.apx_e_last - c->wts.frac_bits);
+    E.apx_s1 = (float)(E.apx_unit * (2.0 * std::log(den + 12.5) + 2.1) / (1.0 - c->apx.apx_delta) * 1.01);
     E.apx_c1 = 0.02f;
-    E.apx_W = std::ldexp((double)c->total_fixed, -c->frac_bits);
+    E.apx_W = std::ldexp((double)c->wts.total_fixed, -c->wts.frac_bits);
     E.scr_shift = 0;
-    E.scr_scale = (float)std::ldexp(1.0, c->apx_e_last - c->frac_bits);
+    E.scr_scale = (float)std::ldexp(1.0, c->apx.apx_e_last - c->wts.frac_bits);
     E.scr_eps = 2e-4f;   // SCREEN_EPS (below)
-    E.apx_MU = c->apx_e_last == 0 ? 0.0f : 1.0f;
+    E.apx_MU = c->apx.apx_e_last == 0 ? 0.0f : 1.0f;
 }
 
 // H16: the LDS histogram holds two 16-bit counters per word (bucket b in half b & 1 of word b >> 1) — for a workgroup that sees at most 65 535

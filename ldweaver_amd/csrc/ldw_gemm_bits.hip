@@ -201,7 +201,7 @@ int launch_gemm_bits(ldw_ctx *ctx, const uint64_t *Mbits, int64_t KW, const int3
     if (tile_list) {   // (the mask's tiles as a list: tile = by << 16 | bx, tiles above the diagonal of a lower_only launch already left out)
         LDW_REQUIRE(n_tile_list >= 0 && by0 == 0 && RFpad / TILE_F4 < 65536 && RTpad / TILE < 65536, LDW_ERR_ARG, "launch_gemm_bits: bad tile list");
         if (n_tile_list == 0) {
-            ctx->gemm_stat[4] += 1;
+            ctx->cnt.gemm_stat[4] += 1;
             return LDW_OK;
         }
         grid = dim3((unsigned)n_tile_list, 1);
@@ -234,20 +234,20 @@ int launch_gemm_bits(ldw_ctx *ctx, const uint64_t *Mbits, int64_t KW, const int3
             if (!lower_only) tiles += nbx;
             else for (int bx = 0; bx < nbx; ++bx) tiles += (bx * TILE_F4 + TILE_F4 - 1 < by * TILE) ? 0 : 1;
         }
-        ctx->gemm_stat[2] += 1;
-        ctx->gemm_stat[3] += 2.0 * (double)tiles * TILE * TILE_F4 * (double)Kpad * nlimbs;
+        ctx->cnt.gemm_stat[2] += 1;
+        ctx->cnt.gemm_stat[3] += 2.0 * (double)tiles * TILE * TILE_F4 * (double)Kpad * nlimbs;
     } else {
-        ctx->gemm_stat[4] += 1;
+        ctx->cnt.gemm_stat[4] += 1;
     }
     return LDW_OK;
 }
 
 int fill_rows_bits(ldw_ctx *c, const int32_t *d_rowinfo, int64_t R) {
-    LDW_REQUIRE(c->seq_perm.p && (int64_t)c->h_seq_perm.size() == c->Npad, LDW_ERR_STATE, "fill_rows_bits: no sequence order (set the weights first)");
+    LDW_REQUIRE(c->wts.seq_perm.p && (int64_t)c->wts.h_seq_perm.size() == c->Npad, LDW_ERR_STATE, "fill_rows_bits: no sequence order (set the weights first)");
     const int use_lds = c->Npad <= 61440 ? 1 : 0;   // the default dynamic-LDS limit is 64 KB
     hipLaunchKernelGGL(k_fill_rows_bits, dim3((unsigned)R), dim3(256), use_lds ? (size_t)c->Npad : 0, c->stream, c->states.as<uint8_t>(), c->Npad,
-                       d_rowinfo, c->KW, c->seq_perm.as<int32_t>(), use_lds, c->Mbits.as<uint64_t>());
-    if (!use_lds) ++c->form_launches[4];
+                       d_rowinfo, c->KW, c->wts.seq_perm.as<int32_t>(), use_lds, c->rows.Mbits.as<uint64_t>());
+    if (!use_lds) ++c->cnt.form_launches[4];
     LDW_HIP(hipGetLastError());
     return LDW_OK;
 }

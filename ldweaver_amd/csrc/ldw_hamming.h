@@ -15,12 +15,11 @@ struct HamBufs {   // the working memory of one call (the caller releases it onc
 
 // LDW_HOST_TIMING: the host's wall clock since the call began, one line per lap
 struct HamClock {
-    const std::chrono::steady_clock::time_point wall0 = std::chrono::steady_clock::now();
+    const HostClock::Point wall0 = HostClock::now();
     double t_last = 0;
-    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count(); }
+    double ms() const { return HostClock::ms(wall0, HostClock::now()); }
     void lap(const char *what) {
-        static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
-        if (!host_timing) return;
+        if (!ldw::host_timing()) return;
         const double t = ms();
         fprintf(stderr, "[ldw host] hamming: %-28s %7.3f ms (+%.3f)\n", what, t, t - t_last);
         t_last = t;

@@ -205,7 +205,7 @@ int ldw::hamming_gram(ldw_ctx *c, HamBufs &bufs, int tile0, int tile1, HamClock 
     const size_t o_off = ((size_t)(L + 1) * 4 + 255) / 256 * 256, o_scan = 2 * o_off;
     if ((rc = tmp.reserve(o_scan + scan_bytes + 256))) return rc;
     int32_t *d_ncol = tmp.as<int32_t>(), *d_off = reinterpret_cast<int32_t *>(tmp.as<char>() + o_off);
-    hipLaunchKernelGGL(k_ham_ncols, dim3((unsigned)((L + 1 + 255) / 256)), dim3(256), 0, c->stream, c->counts.as<int32_t>(), L, d_ncol);
+    hipLaunchKernelGGL(k_ham_ncols, dim3((unsigned)((L + 1 + 255) / 256)), dim3(256), 0, c->stream, c->rows.counts.as<int32_t>(), L, d_ncol);
     he = hipGetLastError();
     if (he == hipSuccess) he = ldw::prim_exclusive_sum<int32_t>(tmp.as<char>() + o_scan, scan_bytes, d_ncol, d_off, (size_t)L + 1, c->stream);
     int32_t kr32 = 0;
@@ -226,7 +226,7 @@ int ldw::hamming_gram(ldw_ctx *c, HamBufs &bufs, int tile0, int tile1, HamClock 
     if (he == hipSuccess) he = hipMemsetAsync(um.p, 0, (size_t)KWr * 8, c->stream);
     if (he != hipSuccess) return ldw::hip_fail(he, "zeroing the column weights", __FILE__, __LINE__);
     if (KR > 0) {
-        hipLaunchKernelGGL(k_ham_fill, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, c->stream, c->counts.as<int32_t>(), L, d_off, info.as<int32_t>(), dig.as<int8_t>(),
+        hipLaunchKernelGGL(k_ham_fill, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, c->stream, c->rows.counts.as<int32_t>(), L, d_off, info.as<int32_t>(), dig.as<int8_t>(),
                            um.as<unsigned long long>());
         he = hipGetLastError();
         if (he != hipSuccess) return ldw::hip_fail(he, "k_ham_fill", __FILE__, __LINE__);

@@ -137,18 +137,18 @@ __global__ __launch_bounds__(256) void k_cooc_popc(CoocArgs P) {
 int launch_cooc_popc(ldw_ctx *c, const int32_t *rowlist_t, int RTpad, const int32_t *rowlist_f, int RFpad, int64_t *G, int lower_only, hipStream_t st) {
     LDW_REQUIRE(RTpad % PC_T == 0 && RFpad % PC_T == 0, LDW_ERR_ARG, "launch_cooc_popc: row lists must be padded to %d", PC_T);
     LDW_REQUIRE(c->N <= 65535, LDW_ERR_ARG, "the popcount engine's 32-bit limb sums hold at most 65535 sequences (%lld)", (long long)c->N);
-    LDW_REQUIRE(c->nlimbs <= 6, LDW_ERR_ARG, "the popcount engine folds weights of at most 48 bits (nlimbs <= 6)");
-    LDW_REQUIRE(c->pop_segs.p && c->pop_wbeg.p, LDW_ERR_STATE, "weights not set (no popcount segments)");
+    LDW_REQUIRE(c->wts.nlimbs <= 6, LDW_ERR_ARG, "the popcount engine folds weights of at most 48 bits (nlimbs <= 6)");
+    LDW_REQUIRE(c->apx.pop_segs.p && c->apx.pop_wbeg.p, LDW_ERR_STATE, "weights not set (no popcount segments)");
     CoocArgs P;
-    P.Mbits = c->Mbits.as<uint64_t>();
+    P.Mbits = c->rows.Mbits.as<uint64_t>();
     P.KW = c->KW;
     P.rowlist_t = rowlist_t;
     P.rowlist_f = rowlist_f;
     P.RTpad = RTpad;
     P.RFpad = RFpad;
     P.nwords = (int)((c->N + 31) / 32);
-    P.segs = c->pop_segs.as<PopSegH>();
-    P.wbeg = c->pop_wbeg.as<int32_t>();
+    P.segs = c->apx.pop_segs.as<PopSegH>();
+    P.wbeg = c->apx.pop_wbeg.as<int32_t>();
     P.G = G;
     P.lower_only = lower_only;
     dim3 grid((unsigned)(RFpad / PC_T), (unsigned)(RTpad / PC_T));

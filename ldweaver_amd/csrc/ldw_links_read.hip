@@ -528,29 +528,21 @@ int ldw_set_positions(ldw_ctx *c, const int32_t *POS, int64_t L, double g) {
     if (int rc = ldw_tsv_join(c)) return rc;   // (a pending asynchronous table reads the positions this call replaces)
     LDW_REQUIRE(POS != nullptr && L > 0 && L < ((int64_t)1 << 27), LDW_ERR_ARG, "ldw_set_positions: null positions or L = %lld outside 1..2^27", (long long)L);
     LDW_REQUIRE(g >= 0 && !std::isnan(g), LDW_ERR_ARG, "ldw_set_positions: genome length g must be positive, or 0 when it is not known");
-    LDW_REQUIRE(c->blk_capacity == 0 && c->lr_stream == nullptr, LDW_ERR_STATE, "ldw_set_positions: a link pass or an lr_links stream is still open");
+    LDW_REQUIRE(c->links.blk_capacity == 0 && c->lr_stream == nullptr, LDW_ERR_STATE, "ldw_set_positions: a link pass or an lr_links stream is still open");
     LDW_HIP(hipStreamSynchronize(c->stream));
-    if (int rc = c->POS.reserve((size_t)L * 4)) return rc;
-    LDW_HIP(hipMemcpyAsync(c->POS.p, POS, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
+    if (int rc = c->meta.POS.reserve((size_t)L * 4)) return rc;
+    LDW_HIP(hipMemcpyAsync(c->meta.POS.p, POS, (size_t)L * 4, hipMemcpyHostToDevice, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     // what an alignment would have brought is gone: states, weights, r, uqe and paint; the tables index the old SNPs
     c->L = L;
     c->N = c->Npad = c->KW = 0;
-    c->pos_only = true;
-    c->have_weights = false;
-    c->rows_ready = false;
-    c->h_r.clear();
-    c->h_paint.clear();
-    c->paint_min = c->paint_max = 0;
-    set_pos_meta(c, POS, L);
-    c->g = g;
-    c->have_meta = true;
-    c->sr_total = c->sr_share_rows = -1;
-    c->sr_total_dist = -1;
-    c->n_sr = c->n_lr = 0;
-    c->kept.invalidate();
-    c->stats.clear();
-    c->multi_owner.clear();
+    c->positions_only();
+    c->meta.h_r.clear();
+    c->meta.h_paint.clear();
+    c->meta.paint_min = c->meta.paint_max = 0;
+    c->meta.set_positions(POS, L);
+    c->meta.g = g;
+    c->meta.mark_set(true);
     return LDW_OK;
 }
 
@@ -565,20 +557,20 @@ int ldw_links_load(ldw_ctx *c, int which, int32_t pos1_col, int32_t pos2_col, in
     const int nc = t->ncols;
     LDW_REQUIRE(pos1_col >= 0 && pos1_col < nc && pos2_col >= 0 && pos2_col < nc && mi_col >= 0 && mi_col < nc && min_len_col >= -1 && min_len_col < nc, LDW_ERR_ARG,
                 "ldw_links_load: a column index lies outside the %d columns read (min_len_col: -1 for none)", nc);
-    LDW_REQUIRE(c->have_meta && c->POS.p && (int64_t)c->h_POS.size() == c->L, LDW_ERR_STATE, "ldw_links_load: no positions (ldw_set_snp_meta or ldw_set_positions)");
-    LDW_REQUIRE(c->blk_capacity == 0, LDW_ERR_STATE, "ldw_links_load: a link pass is still open (ldw_links_end)");
+    LDW_REQUIRE(c->meta.have_meta && c->meta.POS.p && (int64_t)c->meta.h_POS.size() == c->L, LDW_ERR_STATE, "ldw_links_load: no positions (ldw_set_snp_meta or ldw_set_positions)");
+    LDW_REQUIRE(c->links.blk_capacity == 0, LDW_ERR_STATE, "ldw_links_load: a link pass is still open (ldw_links_end)");
     const int64_t n = t->rows, L = c->L;
     LDW_REQUIRE(n < 2147483647LL, LDW_ERR_SIZE, "ldw_links_load: too many rows");
     if (c->gemm_stream) LDW_HIP(hipStreamSynchronize(c->gemm_stream));
-    DevBuf &A = which == 0 ? c->sr_a : c->lr_a, &B = which == 0 ? c->sr_b : c->lr_b, &M = which == 0 ? c->sr_mi : c->lr_mi;
+    DevBuf &A = which == 0 ? c->links.sr_a : c->links.lr_a, &B = which == 0 ? c->links.sr_b : c->links.lr_b, &M = which == 0 ? c->links.sr_mi : c->links.lr_mi;
     int64_t kept = 0;
     if (n > 0) {
         // the positions in ascending order: POS itself, or the context's sorted copy with the SNP of every entry (the first SNP of a position first)
-        const int32_t *d_srt = c->POS.as<int32_t>(), *d_order = nullptr;
-        if (!c->pos_sorted) {
+        const int32_t *d_srt = c->meta.POS.as<int32_t>(), *d_order = nullptr;
+        if (!c->meta.pos_sorted) {
             if (int rc = pos_order(c)) return rc;
-            d_srt = c->pos_ord.srt.as<int32_t>();
-            d_order = c->pos_ord.order.as<int32_t>();
+            d_srt = c->meta.pos_ord.srt.as<int32_t>();
+            d_order = c->meta.pos_ord.order.as<int32_t>();
         }
         if (int rc = t->keep.reserve((size_t)(n + 1) * 4)) return rc;
         if (int rc = t->koff.reserve((size_t)(n + 1) * 4)) return rc;
@@ -622,10 +614,8 @@ int ldw_links_load(ldw_ctx *c, int which, int32_t pos1_col, int32_t pos2_col, in
                            cols + (int64_t)mi_col * t->stride, n, A.as<int32_t>(), B.as<int32_t>(), M.as<double>());
         LDW_HIP(hipStreamSynchronize(c->stream));
     }
-    (which == 0 ? c->n_sr : c->n_lr) = kept;
-    c->kept.invalidate();   // as ldw_links_import leaves the context: whatever was derived from the old table is stale
-    c->stats.clear();
-    c->multi_owner.clear();
+    (which == 0 ? c->links.n_sr : c->links.n_lr) = kept;
+    c->links.replaced(c->kept);   // as ldw_links_import leaves the context
     if (n_out) *n_out = kept;
     return LDW_OK;
 }

@@ -174,7 +174,7 @@ int ldw_joint_tables(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, i
     LDW_REQUIRE(pair_a && pair_b && np > 0, LDW_ERR_ARG, "ldw_joint_tables: bad argument");
     if (int rc = join_prepare(c)) return rc;   // (ldw_ctx_reserve's side thread sizes c->G's neighbours gx(c, s) — no entry point touches them beside it)
     if (int rc = ensure_rows(c)) return rc;
-    if (frac_bits_out) *frac_bits_out = c->frac_bits;
+    if (frac_bits_out) *frac_bits_out = c->wts.frac_bits;
     const int64_t CH = 1024;
     std::vector<int8_t> ones((size_t)c->Npad, 1);
     ldw::DevBuf d_ones, d_out, d_cmarg;
@@ -183,7 +183,7 @@ int ldw_joint_tables(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, i
     hipError_t he = hipMemcpyAsync(d_ones.p, ones.data(), ones.size(), hipMemcpyHostToDevice, c->stream);
     if (he != hipSuccess) return ldw::hip_fail(he, "memcpy ones", __FILE__, __LINE__);
     hipLaunchKernelGGL(k_slot_counts, dim3((unsigned)((c->L + 255) / 256)), dim3(256), 0, c->stream,
-                       c->counts.as<int32_t>(), c->slot_meta.as<uint32_t>(), c->L, d_cmarg.as<int64_t>());
+                       c->rows.counts.as<int32_t>(), c->rows.slot_meta.as<uint32_t>(), c->L, d_cmarg.as<int64_t>());
     for (int64_t p0 = 0; p0 < np && rc == LDW_OK; p0 += CH) {
         const int64_t n = std::min(CH, np - p0);
         SideLists SF, ST;
@@ -200,13 +200,13 @@ int ldw_joint_tables(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, i
         for (int pass = 0; pass < 2 && rc == LDW_OK; ++pass) {
             int64_t *host_out = pass == 0 ? counts_out : fixed_out;
             if (!host_out) continue;
-            rc = launch_gemm_bits(c, c->Mbits.as<uint64_t>(), c->KW, c->rowlist_t.as<int32_t>(), RTpad, c->rowlist_f.as<int32_t>(), RFpad, c->G.as<int64_t>(),
-                                  pass == 0 ? 1 : c->nlimbs, pass == 0 ? d_ones.as<int8_t>() : c->digits.as<int8_t>(), 0);
+            rc = launch_gemm_bits(c, c->rows.Mbits.as<uint64_t>(), c->KW, c->rowlist_t.as<int32_t>(), RTpad, c->rowlist_f.as<int32_t>(), RFpad, c->G.as<int64_t>(),
+                                  pass == 0 ? 1 : c->wts.nlimbs, pass == 0 ? d_ones.as<int8_t>() : c->wts.digits.as<int8_t>(), 0);
             if (rc) break;
             hipLaunchKernelGGL(k_tables, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->G.as<int64_t>(), RFpad,
                                c->idx_f.as<int32_t>(), c->lrow_f.as<int32_t>(), c->idx_t.as<int32_t>(),
-                               c->lrow_t.as<int32_t>(), (int)n, c->slot_meta.as<uint32_t>(),
-                               pass == 0 ? d_cmarg.as<int64_t>() : c->slot_pfix.as<int64_t>(), d_out.as<int64_t>());
+                               c->lrow_t.as<int32_t>(), (int)n, c->rows.slot_meta.as<uint32_t>(),
+                               pass == 0 ? d_cmarg.as<int64_t>() : c->rows.slot_pfix.as<int64_t>(), d_out.as<int64_t>());
             he = hipMemcpyAsync(host_out + p0 * 25, d_out.p, (size_t)n * 25 * 8, hipMemcpyDeviceToHost, c->stream);
             if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
             if (he != hipSuccess) rc = ldw::hip_fail(he, "joint tables copy", __FILE__, __LINE__);
@@ -219,14 +219,14 @@ int ldw_links_begin(ldw_ctx *c, int64_t nblocks_capacity) {
     if (int rc = check_gpu(c)) return rc;
     if (int rc = join_prepare(c)) return rc;
     LDW_REQUIRE(nblocks_capacity > 0, LDW_ERR_ARG, "ldw_links_begin: capacity must be positive");
-    if (c->blk_capacity != 0) {
+    if (c->links.blk_capacity != 0) {
         // the previous pass never reached ldw_links_end (an error return in the middle of ldw_mi_all_pairs / ldw_mi_block_links): kernels of
         // the aborted pass may still be queued on the three streams and read the index lists, staging images and per-slot buffers
         // that this pass is about to overwrite
         if (c->gemm_stream) LDW_HIP(hipStreamSynchronize(c->gemm_stream));
         if (c->copy_stream) LDW_HIP(hipStreamSynchronize(c->copy_stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
-        c->blk_capacity = 0;
+        c->links.blk_capacity = 0;
     }
     if (int rc = ensure_rows(c)) return rc;  // uses ctx->small for staging; link bookkeeping takes it over below
     const size_t need = 64 + (size_t)LDW_NSLOT * LDW_SPAN_MAX * PICK_STRIDE + (size_t)nblocks_capacity * 32 + 64;
@@ -245,23 +245,20 @@ int ldw_links_begin(ldw_ctx *c, int64_t nblocks_capacity) {
     c->early_sr = false;
     c->ev_valid.assign((size_t)nblocks_capacity, 1);
     c->lrc_recorded = false;
-    c->n_sr = 0;
-    c->n_lr = 0;
-    c->stats.clear();
-    c->multi_owner.clear();   // (a deal of ldw_mi_all_pairs_multi(.., LDW_MI_SR_ROWS_STAY) describes the tables of THAT pass only: ADVICE r05)
+    c->links.new_pass();
     c->trace.clear();
-    c->blk_capacity = nblocks_capacity;
-    c->blk_cursor = 0;
+    c->links.blk_capacity = nblocks_capacity;
+    c->links.blk_cursor = 0;
     for (int i = 0; i < 4; ++i) c->last_ms[i] = 0;
     return LDW_OK;
 }
 
 static int links_check(ldw_ctx *c, const ldw_mi_params *p) {
-    LDW_REQUIRE(c->blk_capacity > 0 && c->blk_cursor < c->blk_capacity, LDW_ERR_STATE,
+    LDW_REQUIRE(c->links.blk_capacity > 0 && c->links.blk_cursor < c->links.blk_capacity, LDW_ERR_STATE,
                 "call ldw_links_begin with enough capacity first");
     LDW_REQUIRE(p->sr_only || p->lr_links_approx > 0, LDW_ERR_ARG, "lr_links_approx must be positive");
     LDW_REQUIRE(p->quirk_mode == LDW_QUIRK_REFERENCE || p->quirk_mode == LDW_QUIRK_INTENDED, LDW_ERR_ARG, "bad quirk mode");
-    LDW_REQUIRE(c->have_meta, LDW_ERR_STATE, "SNP meta data (POS, g) not set");
+    LDW_REQUIRE(c->meta.have_meta, LDW_ERR_STATE, "SNP meta data (POS, g) not set");
     return LDW_OK;
 }
 
@@ -273,20 +270,20 @@ int ldw_mi_block_links(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const in
     SmallLayout sl;
     links_layout(c, sl);
     HostBlock hb;
-    if (int rc = prep_block(c, from_idx, nf, to_idx, nt, p, (int)(c->blk_cursor % LDW_NSLOT), c->blk_cursor, hb)) return rc;
+    if (int rc = prep_block(c, from_idx, nf, to_idx, nt, p, (int)(c->links.blk_cursor % LDW_NSLOT), c->links.blk_cursor, hb)) return rc;
     if (int rc = submit_a(c, hb, p, sl)) return rc;
     if (int rc = submit_b(c, hb, p, sl)) return rc;
     if (int rc = finish_block(c, hb, p, sl)) return rc;
-    ++c->blk_cursor;
+    ++c->links.blk_cursor;
     return LDW_OK;
 }
 
 int ldw_links_end(ldw_ctx *c) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->blk_capacity > 0, LDW_ERR_STATE, "ldw_links_end without ldw_links_begin");
+    LDW_REQUIRE(c->links.blk_capacity > 0, LDW_ERR_STATE, "ldw_links_end without ldw_links_begin");
     SmallLayout sl;
     links_layout(c, sl);
-    const int64_t nb = c->blk_cursor;
+    const int64_t nb = c->links.blk_cursor;
     int64_t h_lr = 0;
     std::vector<int64_t> si((size_t)nb * 3 + 1);
     std::vector<double> sd((size_t)nb + 1);
@@ -304,25 +301,25 @@ int ldw_links_end(ldw_ctx *c) {
         LDW_HIP(hipMemcpyAsync(sd.data(), sl.stats_d, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
     }
     LDW_HIP(hipStreamSynchronize(c->stream));
-    c->n_lr = h_lr;
-    c->screen_violations += h_viol;
-    c->apx_units_listed += h_apx[0];
-    c->apx_pairs_listed += h_apx[1];
-    c->maybe_entries += h_apx[2];
-    c->apx_waves_skipped += (int64_t)h_skip;
-    c->gemm_stat[1] -= (double)h_skip * c->apx_ops_per_wave;
-    c->stats.resize((size_t)nb);
+    c->links.n_lr = h_lr;
+    c->cnt.screen_violations += h_viol;
+    c->cnt.apx_units_listed += h_apx[0];
+    c->cnt.apx_pairs_listed += h_apx[1];
+    c->cnt.maybe_entries += h_apx[2];
+    c->cnt.apx_waves_skipped += (int64_t)h_skip;
+    c->cnt.gemm_stat[1] -= (double)h_skip * c->apx_ops_per_wave;
+    c->links.stats.resize((size_t)nb);
     for (int64_t b = 0; b < nb; ++b) {
-        c->stats[b].n_lr_total = si[b * 3 + 0];
-        c->stats[b].n_lr_kept = si[b * 3 + 1];
-        c->stats[b].n_sr = si[b * 3 + 2];
-        c->stats[b].disc_thresh = sd[b];
+        c->links.stats[b].n_lr_total = si[b * 3 + 0];
+        c->links.stats[b].n_lr_kept = si[b * 3 + 1];
+        c->links.stats[b].n_sr = si[b * 3 + 2];
+        c->links.stats[b].disc_thresh = sd[b];
         float t01 = 0, t12 = 0, t23 = 0;
         const hipEvent_t *ev = handles(&c->ev_pool[(size_t)b * EVB]);
         if (b < (int64_t)c->ev_valid.size() && !c->ev_valid[(size_t)b]) continue;   // a later segment of a span: its time is in the span's first block
         LDW_HIP(hipEventElapsedTime(&t01, ev[0], ev[1]));
-        LDW_HIP(hipEventElapsedTime(&t12, ev[c->engine == LDW_ENGINE_MFMA ? 4 : 1], ev[2]));
-        if (c->engine == LDW_ENGINE_MFMA) {   // the screens of the approximate path run behind the GEMM on its stream
+        LDW_HIP(hipEventElapsedTime(&t12, ev[c->knobs.engine == LDW_ENGINE_MFMA ? 4 : 1], ev[2]));
+        if (c->knobs.engine == LDW_ENGINE_MFMA) {   // the screens of the approximate path run behind the GEMM on its stream
             float t15 = 0;
             if (hipEventElapsedTime(&t15, ev[1], ev[5]) == hipSuccess) t12 += t15;
             else (void)hipGetLastError();   // (an event this block never recorded: the failed query must not surface at the next launch check)
@@ -340,10 +337,10 @@ int ldw_links_end(ldw_ctx *c) {
             while (pb >= 0 && pb < (int64_t)c->ev_valid.size() && !c->ev_valid[(size_t)pb]) --pb;   // (the previous block that recorded events: a span's first)
             if (pb >= 0 && hipEventElapsedTime(&span, c->ev_pool[(size_t)pb * EVB + 3], ev[3]) != hipSuccess) (void)hipGetLastError();   // selection end of the item before -> selection end of b
             fprintf(stderr, "[ldw block %3lld] %s path %d guess %4d true %4d%s cand %8lld kept %7lld  gemm %.3f epi %.3f sel %.3f  span %.3f ms\n", (long long)b,
-                    tr.diag ? "diag" : "off ", tr.path, tr.guess, tr.B_true, tr.missed ? " MISS" : "", tr.n_cand, (long long)c->stats[b].n_lr_kept, t01, t12, t23, span);
+                    tr.diag ? "diag" : "off ", tr.path, tr.guess, tr.B_true, tr.missed ? " MISS" : "", tr.n_cand, (long long)c->links.stats[b].n_lr_kept, t01, t12, t23, span);
         }
     }
-    c->blk_capacity = 0;
+    c->links.blk_capacity = 0;
     return LDW_OK;
 }
 
@@ -357,20 +354,20 @@ static bool span_candidate(const ldw_ctx *c, const int32_t *b, const ldw_mi_para
     if (!(fs >= 1 && fe >= fs && ts > fe && te >= ts && te <= c->L)) return false;
     const int64_t nf = fe - fs + 1, nt = te - ts + 1;
     if (nf != nt || nf < 2048) return false;
-    if ((int64_t)c->h_span_bad.size() != c->L + 1) return false;
-    if (c->h_span_bad[(size_t)fe] - c->h_span_bad[(size_t)fs - 1] != 0 || c->h_span_bad[(size_t)te] - c->h_span_bad[(size_t)ts - 1] != 0) return false;
-    if (!(2 * p->sr_dist < c->g)) return false;
-    const std::vector<int32_t> &P = c->h_POS;
+    if ((int64_t)c->rows.h_span_bad.size() != c->L + 1) return false;
+    if (c->rows.h_span_bad[(size_t)fe] - c->rows.h_span_bad[(size_t)fs - 1] != 0 || c->rows.h_span_bad[(size_t)te] - c->rows.h_span_bad[(size_t)ts - 1] != 0) return false;
+    if (!(2 * p->sr_dist < c->meta.g)) return false;
+    const std::vector<int32_t> &P = c->meta.h_POS;
     const double pf_min = P[(size_t)fs - 1], pf_max = P[(size_t)fe - 1], pt_min = P[(size_t)ts - 1], pt_max = P[(size_t)te - 1];
-    return pt_min - pf_max > p->sr_dist && pf_min + c->g - pt_max > p->sr_dist;
+    return pt_min - pf_max > p->sr_dist && pf_min + c->meta.g - pt_max > p->sr_dist;
 }
 // what the whole pass must offer (checked once, when the pass is planned: a positive guess for off-diagonal blocks exists, or — guess_expected —
 // the cold-start probe of the pass is about to sample one)
 static bool spans_possible(const ldw_ctx *c, const ldw_mi_params *p, bool guess_expected) {
     static const bool env_off = getenv("LDW_NO_SPAN") != nullptr;
-    return c->span_on && !env_off && c->span_max >= 2 && c->prune && c->engine == LDW_ENGINE_MFMA && c->apx_ok && c->path_mode != 1 && c->screen == 1 &&
-           !p->sr_only && speculation_pays(c, p) && c->pos_sorted && (c->spec_B_next[0] > 0 || guess_expected) &&
-           (p->quirk_mode != LDW_QUIRK_REFERENCE || c->r_min >= 2.0);
+    return c->knobs.span_on && !env_off && c->knobs.span_max >= 2 && c->knobs.prune && c->knobs.engine == LDW_ENGINE_MFMA && c->apx.apx_ok && c->knobs.path_mode != 1 && c->knobs.screen == 1 &&
+           !p->sr_only && speculation_pays(c, p) && c->meta.pos_sorted && (c->spec.spec_B_next[0] > 0 || guess_expected) &&
+           (p->quirk_mode != LDW_QUIRK_REFERENCE || c->meta.r_min >= 2.0);
 }
 struct WorkItem {
     int64_t b0;
@@ -381,7 +378,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(blocks && p && nblocks > 0, LDW_ERR_ARG, "ldw_mi_all_pairs: bad argument");
     LDW_REQUIRE(reset, LDW_ERR_ARG, "ldw_mi_all_pairs: appending to earlier calls is not supported (reset must be 1)");
-    static const bool host_timing0 = getenv("LDW_HOST_TIMING") != nullptr;
+    const bool host_timing = ldw::host_timing();
     auto now0 = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_enter = now0();
     if (int rc = join_prepare(c)) return rc;
@@ -413,7 +410,6 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
     // stream evaluates.
     constexpr int RING = 8;
     HostBlock hb[RING];
-    static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
     double th[5] = {0, 0, 0, 0, 0};
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     // The plan: items in block order, made BEFORE the helpers start and before the cold-start probes are queued, so that the list building of
@@ -422,9 +418,9 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
     // plan ASSUMES the off-diagonal probe below will deliver one (it is known here whether that probe will be attempted).  A probe that then
     // yields no guess costs time, never a row: the spans planned on it fall back as any span whose guess has gone does (submit_a: span_alone).
     static const bool probe_on = getenv("LDW_NO_PROBE") == nullptr;
-    const bool probes_wanted = probe_on && !p->sr_only && c->pos_sorted && speculation_pays(c, p);
+    const bool probes_wanted = probe_on && !p->sr_only && c->meta.pos_sorted && speculation_pays(c, p);
     bool probe_expected = false;   // an off-diagonal guess is missing and the first off-diagonal block is large enough to be sampled
-    if (probes_wanted && c->spec_B_next[0] < 0)
+    if (probes_wanted && c->spec.spec_B_next[0] < 0)
         for (int64_t b = 0; b < nblocks; ++b) {
             if (blocks[b * 4 + 0] == blocks[b * 4 + 2] && blocks[b * 4 + 1] == blocks[b * 4 + 3]) continue;
             probe_expected = (int64_t)(blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1) * (int64_t)(blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1) >= PROBE_MIN_PAIRS;
@@ -440,7 +436,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
                 const int64_t nf = blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1;
                 int64_t nt_tot = blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1;
                 static const int env_max = [] { const char *e = getenv("LDW_SPAN_MAX"); return e ? atoi(e) : 0; }();   // (A/B measurements)
-                const int nmax = std::min<int>(env_max >= 1 ? env_max : c->span_max, LDW_SPAN_MAX);
+                const int nmax = std::min<int>(env_max >= 1 ? env_max : c->knobs.span_max, LDW_SPAN_MAX);
                 while (n < nmax && b + n < nblocks && span_candidate(c, blocks + (b + n) * 4, p) && blocks[(b + n) * 4 + 0] == blocks[b * 4 + 0] &&
                        blocks[(b + n) * 4 + 1] == blocks[b * 4 + 1] && blocks[(b + n) * 4 + 2] > blocks[(b + n - 1) * 4 + 3]) {
                     const int64_t nt_k = blocks[(b + n) * 4 + 3] - blocks[(b + n) * 4 + 2] + 1;
@@ -560,15 +556,15 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
         }
     } joiner{sh, helpers, n_helpers};
     // (the helpers are at work: the table sizing below runs beside the list building of the first items, which is what the GPU waits for)
-    if (p->keep_sr && c->pos_sorted && 2 * p->sr_dist < c->g) {
+    if (p->keep_sr && c->meta.pos_sorted && 2 * p->sr_dist < c->meta.g) {
         // Size the short-range table ONCE: geometric growth re-copies up to a gigabyte and synchronises both streams every time (ten times in
         // the first pass of C4), and would double-buffer tens of GB at C5.  The blocks of a pass hold every unordered SNP pair at most once,
         // so the number of pairs within sr_dist on the circle bounds the rows: POS ascends — a two-pointer walk, O(L) (r03 ran build_cols
         // over every block for this, 0.2 ms each, and only for passes of more than 200 blocks).
         const int64_t Ls = c->L;
-        const std::vector<int32_t> &P = c->h_POS;
+        const std::vector<int32_t> &P = c->meta.h_POS;
         int64_t total_sr = 0, hi = 0, wlo = 0;
-        if (c->sr_total_dist == p->sr_dist && c->sr_total >= 0) total_sr = c->sr_total;   // (the walk is 1 ms at L = 100k: once per positions and sr_dist)
+        if (c->sizing.sr_total_dist == p->sr_dist && c->sizing.sr_total >= 0) total_sr = c->sizing.sr_total;   // (the walk is 1 ms at L = 100k: once per positions and sr_dist)
         else {
         for (int64_t a = 0; a < Ls; ++a) {
             if (hi < a + 1) hi = a + 1;
@@ -576,13 +572,13 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
             total_sr += hi - a - 1;                                   // partners ahead of a, directly
         }
         for (int64_t a = 0; a < Ls; ++a) {   // partners across the origin: b before a with P[b] + g - P[a] <= sr_dist (the limit ascends with a)
-            const double lim = p->sr_dist - c->g + (double)P[(size_t)a];
+            const double lim = p->sr_dist - c->meta.g + (double)P[(size_t)a];
             if (lim < (double)P[0]) continue;
             while (wlo < Ls && (double)P[(size_t)wlo] <= lim) ++wlo;
             total_sr += std::min<int64_t>(wlo, a);
         }
-        c->sr_total = total_sr;
-        c->sr_total_dist = p->sr_dist;
+        c->sizing.sr_total = total_sr;
+        c->sizing.sr_total_dist = p->sr_dist;
         }
         // r05: a SHARE of the block list (a rank or context of a multi-GPU job: under three quarters of the pair space) is sized for the rows of ITS blocks — the band
         // enumerator counts them on the device in well under a millisecond (ldw_sr_pairs_fill without outputs; cached per block list) — instead of the whole alignment's:
@@ -595,13 +591,12 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
                 share_pairs += (double)(blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1) * (double)(blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1);
                 for (int q = 0; q < 4; ++q) key = (key ^ (uint64_t)(uint32_t)blocks[b * 4 + q]) * 1099511628211ull;
             }
-            if (share_pairs < 0.375 * (double)Ls * (double)Ls && c->g == std::floor(c->g)) {
-                if (c->sr_share_rows >= 0 && c->sr_share_key == key) want_sr = std::min(total_sr, c->sr_share_rows);
+            if (share_pairs < 0.375 * (double)Ls * (double)Ls && c->meta.g == std::floor(c->meta.g)) {
+                if (c->sizing.sr_share_rows >= 0 && c->sizing.sr_share_key == key) want_sr = std::min(total_sr, c->sizing.sr_share_rows);
                 else {
                     int64_t n_share = 0;
                     if (ldw_sr_pairs_fill(c, blocks, nblocks, p->sr_dist, nullptr, nullptr, 0, &n_share) == LDW_OK && n_share <= total_sr) {
-                        c->sr_share_key = key;
-                        c->sr_share_rows = n_share;
+                        c->sizing.learn_share(key, n_share);
                         want_sr = n_share;
                     }
                 }
@@ -619,7 +614,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
         for (int64_t b = 0; b < nblocks; ++b) tot_pairs += (double)(blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1) * (double)(blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1);
         const double want = std::min(tot_pairs, std::max(0.0, p->lr_retain_links) * 1.25 + (double)(4 << 20));
         if (want < 4e9)
-            if (int rc = ensure_links_capacity(c, c->n_sr, (int64_t)want)) return rc;
+            if (int rc = ensure_links_capacity(c, c->links.n_sr, (int64_t)want)) return rc;
     }
     const double t_sized = now0();
     // blocks until item k is prepared (true) — or, with wait = false, says whether it is
@@ -643,7 +638,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
         sh.cv.notify_all();
         return LDW_OK;
     };
-    const int64_t ahead = c->overlap ? LDW_NSLOT - 1 : 1;
+    const int64_t ahead = c->knobs.overlap ? LDW_NSLOT - 1 : 1;
     // (the helpers are already building the first items' lists while the probes run)
     // cold start: a sampled guess for each block kind that has none yet (probe_kind_guess), taken from the first block of the kind
     Probe probes[2];
@@ -656,7 +651,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
             const int kind = diag ? 1 : 0;
             if (done_kind[kind]) continue;
             done_kind[kind] = true;
-            if (c->spec_B_next[kind] >= 0) continue;
+            if (c->spec.spec_B_next[kind] >= 0) continue;
             if (int rc = fill(b)) return rc;
             const int64_t npairs = diag ? (int64_t)fi.size() * ((int64_t)fi.size() - 1) / 2 : (int64_t)fi.size() * (int64_t)ti.size();
             if (npairs < PROBE_MIN_PAIRS) continue;
@@ -691,7 +686,7 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
     const double t_probed = now0();
     if (int rc = submit_next()) return rc;
     const double t_planned = now0();
-    if (host_timing0)
+    if (host_timing)
         fprintf(stderr, "[ldw host us] waiting for the side threads %.0f  links_begin (row map if stale, bookkeeping) %.0f  table sizing + plan + helper start %.0f  cold-start probes queued %.0f  first upload + wait for its probe %.0f  first item submitted %.0f\n",
                 t_joined - t_enter, t_begun - t_joined, t_sized - t_begun, t_queued - t_sized, t_probed - t_queued, t_planned - t_probed);
     int fail_rc = LDW_OK;
@@ -742,8 +737,8 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
             sh.n_done = b + 1;
         }
         sh.cv.notify_all();
-        c->blk_cursor += items[(size_t)b].nseg;
-        lr_stream_push(c, c->stream, sl.lr_count, c->blk_cursor);   // (no-op without ldw_lr_stream_begin: the rows of this item may go to lr_links.tsv now)
+        c->links.blk_cursor += items[(size_t)b].nseg;
+        lr_stream_push(c, c->stream, sl.lr_count, c->links.blk_cursor);   // (no-op without ldw_lr_stream_begin: the rows of this item may go to lr_links.tsv now)
         if (n_sub <= b + 1 && b + 1 < nitems) {                          // overlap off / no guess yet: one item after the other
             int rc = LDW_OK;
             prepped(b + 1, true, rc);
@@ -762,8 +757,8 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
                 if (!(bb == b_fail && b_fail_submitted))
                     if (submit_b(c, h, p, sl) != LDW_OK) break;
                 if (finish_block(c, h, p, sl) != LDW_OK) break;
-                c->blk_cursor += items[(size_t)bb].nseg;
-                lr_stream_push(c, c->stream, sl.lr_count, c->blk_cursor);
+                c->links.blk_cursor += items[(size_t)bb].nseg;
+                lr_stream_push(c, c->stream, sl.lr_count, c->links.blk_cursor);
             }
         }
         set_error("%s", fail_msg.c_str());
@@ -782,22 +777,22 @@ int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const l
 int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double sr_dist, int32_t *a_out, int32_t *b_out, int64_t capacity, int64_t *n_out) {
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(blocks && nblocks > 0 && n_out && sr_dist >= 0, LDW_ERR_ARG, "ldw_sr_pairs_fill: bad argument");
-    LDW_REQUIRE(c->have_meta && c->pos_sorted, LDW_ERR_STATE, "ldw_sr_pairs_fill: needs SNP positions in ascending order (ldw_set_snp_meta)");
+    LDW_REQUIRE(c->meta.have_meta && c->meta.pos_sorted, LDW_ERR_STATE, "ldw_sr_pairs_fill: needs SNP positions in ascending order (ldw_set_snp_meta)");
     *n_out = 0;
     // r05: everything on the device (k_cols_dev ... k_sr_fill_all) — the host loop below built the intervals of C4's 20 band blocks in 17 ms, which a
     // multi-GPU job's rank 0 paid after every gather.  Integral genome length (every len is then an exact integer on host and device alike); a column
     // whose interval check fails (none on ascending positions) sends the call down the host path, as does LDW_SR_PAIRS_HOST=1 (A/B, tests).
-    if (c->g == std::floor(c->g) && getenv("LDW_SR_PAIRS_HOST") == nullptr) {
+    if (c->meta.g == std::floor(c->meta.g) && getenv("LDW_SR_PAIRS_HOST") == nullptr) {
         std::vector<SrBlkDev> hb;
         int64_t ncols = 0;
-        const std::vector<int32_t> &Ph = c->h_POS;
+        const std::vector<int32_t> &Ph = c->meta.h_POS;
         for (int64_t b = 0; b < nblocks; ++b) {
             const int32_t fs = blocks[b * 4 + 0], fe = blocks[b * 4 + 1], ts = blocks[b * 4 + 2], te = blocks[b * 4 + 3];
             LDW_REQUIRE(fs >= 1 && fe >= fs && fe <= c->L && ts >= 1 && te >= ts && te <= c->L, LDW_ERR_ARG, "block %lld = (%d,%d,%d,%d) outside 1..%lld", (long long)b, fs, fe,
                         ts, te, (long long)c->L);
-            if (ts > fe && 2 * sr_dist < c->g) {   // (as below: ranges further apart than sr_dist directly and across the origin)
+            if (ts > fe && 2 * sr_dist < c->meta.g) {   // (as below: ranges further apart than sr_dist directly and across the origin)
                 const double pf_min = Ph[(size_t)fs - 1], pf_max = Ph[(size_t)fe - 1], pt_min = Ph[(size_t)ts - 1], pt_max = Ph[(size_t)te - 1];
-                if (pt_min - pf_max > sr_dist && pf_min + c->g - pt_max > sr_dist) continue;
+                if (pt_min - pf_max > sr_dist && pf_min + c->meta.g - pt_max > sr_dist) continue;
             }
             hb.push_back(SrBlkDev{fs - 1, fe - fs + 1, ts - 1, te - ts + 1, (fs == ts && fe == te) ? 1 : 0, 0, ncols});
             ncols += te - ts + 1;
@@ -814,7 +809,7 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
         ColInfo *d_cols = c->srm.out.as<ColInfo>();
         LDW_HIP(hipMemcpyAsync(d_blk, hb.data(), nb * sizeof(SrBlkDev), hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemsetAsync(d_bad, 0, 8, c->stream));
-        hipLaunchKernelGGL(k_cols_dev, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, c->stream, c->POS.as<int32_t>(), c->g, sr_dist, d_blk, (int)nb, ncols, d_cols, d_cu,
+        hipLaunchKernelGGL(k_cols_dev, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, c->stream, c->meta.POS.as<int32_t>(), c->meta.g, sr_dist, d_blk, (int)nb, ncols, d_cols, d_cu,
                            d_cl, d_bad);
         hipLaunchKernelGGL(k_cols_scan, dim3((unsigned)nb), dim3(256), 0, c->stream, d_blk, d_cols, d_cu, d_cl, d_rows);
         hipLaunchKernelGGL(k_blk_bases, dim3(1), dim3(64), 0, c->stream, d_rows, (int)nb, d_base);
@@ -843,15 +838,15 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
     // recognised from their four end positions (POS ascends) without building their columns.
     ldw::DevBuf dcols[2];
     ldw::Event done[2];
-    const std::vector<int32_t> &P = c->h_POS;
+    const std::vector<int32_t> &P = c->meta.h_POS;
     int64_t n_filled = 0;
     for (int64_t b = 0; b < nblocks; ++b) {
         const int32_t fs = blocks[b * 4 + 0], fe = blocks[b * 4 + 1], ts = blocks[b * 4 + 2], te = blocks[b * 4 + 3];
         LDW_REQUIRE(fs >= 1 && fe >= fs && fe <= c->L && ts >= 1 && te >= ts && te <= c->L, LDW_ERR_ARG, "block %lld = (%d,%d,%d,%d) outside 1..%lld", (long long)b, fs, fe,
                     ts, te, (long long)c->L);
-        if (ts > fe && 2 * sr_dist < c->g) {   // disjoint ranges, to side after the from side: no pair within sr_dist directly or across the origin?
+        if (ts > fe && 2 * sr_dist < c->meta.g) {   // disjoint ranges, to side after the from side: no pair within sr_dist directly or across the origin?
             const double pf_min = P[(size_t)fs - 1], pf_max = P[(size_t)fe - 1], pt_min = P[(size_t)ts - 1], pt_max = P[(size_t)te - 1];
-            if (pt_min - pf_max > sr_dist && pf_min + c->g - pt_max > sr_dist) continue;
+            if (pt_min - pf_max > sr_dist && pf_min + c->meta.g - pt_max > sr_dist) continue;
         }
         const int64_t nf = fe - fs + 1, nt = te - ts + 1;
         fi.resize((size_t)nf);
@@ -912,19 +907,11 @@ int ldw_debug_tab11(ldw_ctx *c, double W, double lo, double delta, double eta, d
     return LDW_OK;
 }
 
-int ldw_set_span(ldw_ctx *c, int on, int max_blocks) {
-    LDW_REQUIRE(c && (max_blocks == 0 || (max_blocks >= 2 && max_blocks <= LDW_SPAN_MAX)), LDW_ERR_ARG, "ldw_set_span: max_blocks must be 0 or 2..%d", LDW_SPAN_MAX);
-    LDW_REQUIRE(!(on & 6), LDW_ERR_STATE, "ldw_set_span: corner spans / split diagonal blocks (bits 1, 2; formerly the LDW_EXPERIMENTS build's) were measured slower and have been removed");
-    c->span_on = on != 0;
-    if (max_blocks) c->span_max = max_blocks;
-    return LDW_OK;
-}
-
 int ldw_slot_report(ldw_ctx *c, int64_t out[6]) {
     LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_slot_report: null argument");
     if (int rc = join_prepare(c)) return rc;   // (ldw_ctx_reserve's side thread may still be sizing the buffers)
     for (int k = 1; k < 6; ++k) out[k] = 0;
-    out[0] = c->slot_grown;
+    out[0] = c->cnt.slot_grown;
     for (int s = 0; s < LDW_NSLOT; ++s) {
         out[1] += (int64_t)c->apx_units[s].cap;
         out[2] += (int64_t)c->apx_packs[s].cap;
@@ -935,57 +922,15 @@ int ldw_slot_report(ldw_ctx *c, int64_t out[6]) {
     return LDW_OK;
 }
 
-int ldw_overflow_report(ldw_ctx *c, int64_t out[4]) {
-    LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_overflow_report: null argument");
-    out[0] = c->pair_list_overflows;
-    out[1] = c->maybe_overflows;
-    out[2] = c->maybe_off ? 1 : 0;
-    out[3] = c->maybe_entries;
-    return LDW_OK;
-}
-
-int ldw_span_report(ldw_ctx *c, int64_t out[4]) {
-    LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_span_report: null argument");
-    out[0] = c->span_items;
-    out[1] = c->span_blocks;
-    out[2] = c->span_fallbacks;
-    out[3] = c->span_on ? 1 : 0;
-    return LDW_OK;
-}
-
 int ldw_set_pair_cap(uint32_t cap) {
     LDW_REQUIRE(cap == 0 || (cap >= 16 && cap <= (1u << 22)), LDW_ERR_ARG, "ldw_set_pair_cap: 0 or 16..2^22");
     g_pair_cap_override.store(cap);
     return LDW_OK;
 }
 
-int ldw_set_overlap(ldw_ctx *c, int on) {
-    LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
-    c->overlap = on != 0;
-    return LDW_OK;
-}
-
-int ldw_set_screen(ldw_ctx *c, int mode) {
-    LDW_REQUIRE(c && mode >= 0 && mode <= 2, LDW_ERR_ARG, "ldw_set_screen: mode must be 0, 1 or 2");
-    c->screen = mode;
-    return LDW_OK;
-}
-
-int ldw_set_mixed(ldw_ctx *c, int on) {
-    LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
-    c->mixed = on != 0;
-    return LDW_OK;
-}
-
-int ldw_set_fused(ldw_ctx *c, int on) {
-    LDW_REQUIRE(!on, LDW_ERR_STATE, "ldw_set_fused(1): the fused GEMM + epilogue kernel (formerly the LDW_EXPERIMENTS build's) was measured slower and has been removed");
-    LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
-    return LDW_OK;
-}
-
 int ldw_links_count(ldw_ctx *c, int which, int64_t *n_out) {
     LDW_REQUIRE(c && n_out && (which == 0 || which == 1), LDW_ERR_ARG, "ldw_links_count: bad argument");
-    *n_out = which == 0 ? c->n_sr : c->n_lr;
+    *n_out = which == 0 ? c->links.n_sr : c->links.n_lr;
     return LDW_OK;
 }
 
@@ -993,12 +938,12 @@ int ldw_links_device_ptrs(ldw_ctx *c, int which, const int32_t **a_out, const in
     if (int rc = check_gpu(c)) return rc;
     if (int rc = join_prepare(c)) return rc;
     LDW_REQUIRE((which == 0 || which == 1) && a_out && b_out && MI_out && n_out, LDW_ERR_ARG, "ldw_links_device_ptrs: bad argument");
-    LDW_REQUIRE(c->blk_capacity == 0, LDW_ERR_STATE, "ldw_links_device_ptrs: a link pass is still open (ldw_links_end)");
+    LDW_REQUIRE(c->links.blk_capacity == 0, LDW_ERR_STATE, "ldw_links_device_ptrs: a link pass is still open (ldw_links_end)");
     LDW_HIP(hipStreamSynchronize(c->stream));
-    *a_out = (which == 0 ? c->sr_a : c->lr_a).as<int32_t>();
-    *b_out = (which == 0 ? c->sr_b : c->lr_b).as<int32_t>();
-    *MI_out = (which == 0 ? c->sr_mi : c->lr_mi).as<double>();
-    *n_out = which == 0 ? c->n_sr : c->n_lr;
+    *a_out = (which == 0 ? c->links.sr_a : c->links.lr_a).as<int32_t>();
+    *b_out = (which == 0 ? c->links.sr_b : c->links.lr_b).as<int32_t>();
+    *MI_out = (which == 0 ? c->links.sr_mi : c->links.lr_mi).as<double>();
+    *n_out = which == 0 ? c->links.n_sr : c->links.n_lr;
     return LDW_OK;
 }
 
@@ -1012,12 +957,12 @@ int ldw_links_fetch(ldw_ctx *c, int which, int32_t *a_out, int32_t *b_out, doubl
                     int on_device) {
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(which == 0 || which == 1, LDW_ERR_ARG, "ldw_links_fetch: which must be 0 (sr) or 1 (lr)");
-    const int64_t n = which == 0 ? c->n_sr : c->n_lr;
+    const int64_t n = which == 0 ? c->links.n_sr : c->links.n_lr;
     LDW_REQUIRE(capacity >= n, LDW_ERR_SIZE, "ldw_links_fetch: capacity %lld < %lld rows", (long long)capacity, (long long)n);
     if (n == 0) return LDW_OK;
     LDW_REQUIRE(a_out && b_out && MI_out, LDW_ERR_ARG, "ldw_links_fetch: null output");
     const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    ldw::DevBuf &A = which == 0 ? c->sr_a : c->lr_a, &B = which == 0 ? c->sr_b : c->lr_b, &M = which == 0 ? c->sr_mi : c->lr_mi;
+    ldw::DevBuf &A = which == 0 ? c->links.sr_a : c->links.lr_a, &B = which == 0 ? c->links.sr_b : c->links.lr_b, &M = which == 0 ? c->links.sr_mi : c->links.lr_mi;
     LDW_HIP(hipMemcpyAsync(a_out, A.p, (size_t)n * 4, k, c->stream));
     LDW_HIP(hipMemcpyAsync(b_out, B.p, (size_t)n * 4, k, c->stream));
     LDW_HIP(hipMemcpyAsync(MI_out, M.p, (size_t)n * 8, k, c->stream));
@@ -1030,9 +975,9 @@ int ldw_links_import(ldw_ctx *c, int which, const int32_t *a, const int32_t *b, 
     if (int rc = join_prepare(c)) return rc;
     LDW_REQUIRE(which == 0 || which == 1, LDW_ERR_ARG, "ldw_links_import: which must be 0 (sr) or 1 (lr)");
     LDW_REQUIRE(n >= 0 && (n == 0 || (a && b && MI)), LDW_ERR_ARG, "ldw_links_import: bad argument");
-    LDW_REQUIRE(c->blk_capacity == 0, LDW_ERR_STATE, "ldw_links_import: a link pass is still open (ldw_links_end)");
+    LDW_REQUIRE(c->links.blk_capacity == 0, LDW_ERR_STATE, "ldw_links_import: a link pass is still open (ldw_links_end)");
     if (c->gemm_stream) LDW_HIP(hipStreamSynchronize(c->gemm_stream));
-    ldw::DevBuf &A = which == 0 ? c->sr_a : c->lr_a, &B = which == 0 ? c->sr_b : c->lr_b, &M = which == 0 ? c->sr_mi : c->lr_mi;
+    ldw::DevBuf &A = which == 0 ? c->links.sr_a : c->links.lr_a, &B = which == 0 ? c->links.sr_b : c->links.lr_b, &M = which == 0 ? c->links.sr_mi : c->links.lr_mi;
     if (int rc = A.reserve((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
     if (int rc = B.reserve((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
     if (int rc = M.reserve((size_t)std::max<int64_t>(n, 1) * 8)) return rc;
@@ -1043,23 +988,21 @@ int ldw_links_import(ldw_ctx *c, int which, const int32_t *a, const int32_t *b, 
         LDW_HIP(hipMemcpyAsync(M.p, MI, (size_t)n * 8, k, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
     }
-    (which == 0 ? c->n_sr : c->n_lr) = n;
-    c->kept.invalidate();   // whatever was derived from the old table is stale:
-    c->stats.clear();           // the per-block records of the pass that made it (ldw_block_stats answers LDW_ERR_ARG until the next pass) ...
-    c->multi_owner.clear();     // ... and the deal of an in-process pass whose shares these rows replace
+    (which == 0 ? c->links.n_sr : c->links.n_lr) = n;
+    c->links.replaced(c->kept);
     return LDW_OK;
 }
 
 int ldw_block_stats(ldw_ctx *c, int64_t nblocks, int64_t *n_lr_total, int64_t *n_lr_kept, int64_t *n_sr,
                     double *disc_thresh) {
     LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
-    LDW_REQUIRE((int64_t)c->stats.size() == nblocks, LDW_ERR_ARG, "ldw_block_stats: last call processed %lld blocks, not %lld",
-                (long long)c->stats.size(), (long long)nblocks);
+    LDW_REQUIRE((int64_t)c->links.stats.size() == nblocks, LDW_ERR_ARG, "ldw_block_stats: last call processed %lld blocks, not %lld",
+                (long long)c->links.stats.size(), (long long)nblocks);
     for (int64_t b = 0; b < nblocks; ++b) {
-        if (n_lr_total) n_lr_total[b] = c->stats[b].n_lr_total;
-        if (n_lr_kept) n_lr_kept[b] = c->stats[b].n_lr_kept;
-        if (n_sr) n_sr[b] = c->stats[b].n_sr;
-        if (disc_thresh) disc_thresh[b] = c->stats[b].disc_thresh;
+        if (n_lr_total) n_lr_total[b] = c->links.stats[b].n_lr_total;
+        if (n_lr_kept) n_lr_kept[b] = c->links.stats[b].n_lr_kept;
+        if (n_sr) n_sr[b] = c->links.stats[b].n_sr;
+        if (disc_thresh) disc_thresh[b] = c->links.stats[b].disc_thresh;
     }
     return LDW_OK;
 }

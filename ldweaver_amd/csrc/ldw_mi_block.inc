@@ -26,7 +26,7 @@ int build_side(ldw_ctx *c, const int32_t *idx, int64_t n, SideLists &S, const st
     S.rowlist.clear();
     S.pos.clear();
     S.cls.clear();
-    const int32_t zero_row = (int32_t)c->R;   // rows R .. R+TILE-1 of Mbits are zero
+    const int32_t zero_row = (int32_t)c->rows.R;   // rows R .. R+TILE-1 of Mbits are zero
     for (int64_t k = 0; k < n; ++k)
         LDW_REQUIRE(idx[k] >= 0 && idx[k] < c->L, LDW_ERR_ARG, "SNP index %d out of range 0..%lld", idx[k], (long long)c->L - 1);
     for (int cl : {1, 2, 4}) {
@@ -35,12 +35,12 @@ int build_side(ldw_ctx *c, const int32_t *idx, int64_t n, SideLists &S, const st
         for (int64_t kk = 0; kk < cnt; ++kk) {
             const int64_t k = ordered ? (int64_t)(*order1)[(size_t)kk] : kk;
             const int32_t a = idx[k];
-            const int nr = c->h_row0[a + 1] - c->h_row0[a];
+            const int nr = c->rows.h_row0[a + 1] - c->rows.h_row0[a];
             const int mine = nr <= 1 ? 1 : (nr == 2 ? 2 : 4);
             if (mine != cl) continue;
             S.lrow[k] = (int32_t)S.rowlist.size();
             for (int q = 0; q < cl; ++q) {
-                S.rowlist.push_back(q < nr ? c->h_row0[a] + q : zero_row);
+                S.rowlist.push_back(q < nr ? c->rows.h_row0[a] + q : zero_row);
                 S.pos.push_back(q == 0 ? (int32_t)k : -1);
             }
         }
@@ -66,18 +66,18 @@ int build_side(ldw_ctx *c, const int32_t *idx, int64_t n, SideLists &S, const st
 // (circ_len <= sr_dist); a column that fails the check is rebuilt by scanning.
 int build_cols(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *to_idx, int64_t nt, bool diag, double sr_dist,
                std::vector<ColInfo> &cols, int64_t &n_sr_blk) {
-    const double g = c->g;
+    const double g = c->meta.g;
     std::vector<double> pf((size_t)nf);
     for (int64_t a = 0; a < nf; ++a) {
-        pf[a] = (double)c->h_POS[from_idx[a]];
+        pf[a] = (double)c->meta.h_POS[from_idx[a]];
         LDW_REQUIRE(a == 0 || pf[a] >= pf[a - 1], LDW_ERR_ARG, "from-side SNP list must be ascending in POS (position %lld)", (long long)a);
     }
     cols.resize((size_t)nt);
     {   // quick reject: when the two position ranges are farther apart than sr_dist both directly and around the
         // origin, no pair of the block is short-range (true for most off-diagonal blocks)
-        double pt_min = (double)c->h_POS[to_idx[0]], pt_max = pt_min;
+        double pt_min = (double)c->meta.h_POS[to_idx[0]], pt_max = pt_min;
         for (int64_t b = 1; b < nt; ++b) {
-            const double v = (double)c->h_POS[to_idx[b]];
+            const double v = (double)c->meta.h_POS[to_idx[b]];
             pt_min = v < pt_min ? v : pt_min;
             pt_max = v > pt_max ? v : pt_max;
         }
@@ -101,7 +101,7 @@ int build_cols(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
     int64_t hint[4] = {0, 0, 0, 0};
     double p_prev = 0;
     for (int64_t b = 0; b < nt; ++b) {
-        const double p1 = (double)c->h_POS[to_idx[b]];
+        const double p1 = (double)c->meta.h_POS[to_idx[b]];
         const bool fwd = b > 0 && p1 >= p_prev;
         p_prev = p1;
         auto lower = [&](int64_t &h, double v) -> int64_t {   // first index with pf >= v
@@ -228,11 +228,11 @@ void fill_epi_args(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RFp
     A.lrow_t = D.lrow_t;
     A.nf = (int)nf;
     A.nt = (int)nt;
-    A.slot_meta = c->slot_meta.as<uint32_t>();
-    A.slot_pfix = c->slot_pfix.as<int64_t>();
-    A.r = c->r.as<double>();
-    A.neff = c->neff;
-    A.scale = std::ldexp(1.0, -c->frac_bits);
+    A.slot_meta = c->rows.slot_meta.as<uint32_t>();
+    A.slot_pfix = c->rows.slot_pfix.as<int64_t>();
+    A.r = c->meta.r.as<double>();
+    A.neff = c->wts.neff;
+    A.scale = std::ldexp(1.0, -c->wts.frac_bits);
     A.quirk = quirk;
     A.gen_t0 = D.gen_t0;
     A.gen_q0 = D.gen_q0;
@@ -242,7 +242,7 @@ void fill_epi_args(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RFp
     A.pl_pairs = nullptr;
     A.pl_n = nullptr;
     A.pl_cap = 0;
-    A.row0 = c->row0.as<int32_t>();
+    A.row0 = c->rows.row0.as<int32_t>();
     A.tab11 = nullptr;
     A.clean = nullptr;
     A.clean_stride = 0;
@@ -286,10 +286,10 @@ inline uint32_t maybe_cap_for(int64_t RTpad, int64_t RFpad) {
 // a block (or a span's segment) redone because a list overflowed (PickOut::over): counted, and a maybe list that overflowed — impossible at its
 // worst-case capacity, so only under LDW_MAYBE_CAP — is switched off for the rest of the pass instead of overflowing item after item
 inline void note_overflow(ldw_ctx *c, int over) {
-    if (over & 1) ++c->pair_list_overflows;
+    if (over & 1) ++c->cnt.pair_list_overflows;
     if (over & 2) {
-        ++c->maybe_overflows;
-        c->maybe_off = true;
+        ++c->cnt.maybe_overflows;
+        c->spec.maybe_off = true;
     }
 }
 // The run-time RXY read mode (rxy_read_mode, ldw_epi.h) as a template argument: f(std::integral_constant<int, RM>).  SPAN = false leaves mode 3 out:
@@ -345,8 +345,8 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
         if (int rc = Gbuf.reserve((size_t)RFpad * RTpad * 8)) return rc;
         LDW_HIP(hipEventRecord(ev[0], gstream));
         // mixed-precision path: the block-wide GEMM carries the high limbs only
-        if (int rc = launch_gemm_bits(c, c->Mbits.as<uint64_t>(), c->KW, D.rl_t, RTpad, D.rl_f, RFpad, Gbuf.as<int64_t>(),
-                                      mixed ? HI_LIMBS : c->nlimbs, c->digits.as<int8_t>() + (mixed ? (int64_t)LO_LIMBS * c->KW * 64 : 0),
+        if (int rc = launch_gemm_bits(c, c->rows.Mbits.as<uint64_t>(), c->KW, D.rl_t, RTpad, D.rl_f, RFpad, Gbuf.as<int64_t>(),
+                                      mixed ? HI_LIMBS : c->wts.nlimbs, c->wts.digits.as<int8_t>() + (mixed ? (int64_t)LO_LIMBS * c->KW * 64 : 0),
                                       E.lower_only, gstream))
             return rc;
         LDW_HIP(hipEventRecord(ev[1], gstream));
@@ -362,10 +362,10 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
     if (!epilogue_only) {
         if (int rc = Gbuf.reserve((size_t)RFpad * RTpad * 8)) return rc;
         LDW_HIP(hipEventRecord(ev[0], c->stream));
-        if (c->engine == LDW_ENGINE_HIST) {   // the histogram formulation on bit planes: class-wise popcounts instead of the MFMA GEMM
+        if (c->knobs.engine == LDW_ENGINE_HIST) {   // the histogram formulation on bit planes: class-wise popcounts instead of the MFMA GEMM
             if (int rc = launch_cooc_popc(c, D.rl_t, RTpad, D.rl_f, RFpad, Gbuf.as<int64_t>(), E.lower_only, c->stream)) return rc;
-        } else if (int rc = launch_gemm_bits(c, c->Mbits.as<uint64_t>(), c->KW, D.rl_t, RTpad, D.rl_f, RFpad, Gbuf.as<int64_t>(), c->nlimbs,
-                                             c->digits.as<int8_t>(), E.lower_only, c->stream))
+        } else if (int rc = launch_gemm_bits(c, c->rows.Mbits.as<uint64_t>(), c->KW, D.rl_t, RTpad, D.rl_f, RFpad, Gbuf.as<int64_t>(), c->wts.nlimbs,
+                                             c->wts.digits.as<int8_t>(), E.lower_only, c->stream))
             return rc;
         LDW_HIP(hipEventRecord(ev[1], c->stream));
     }
@@ -396,7 +396,7 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
             lo.cnt = U.tile_cnt();
             lo.tl = U.tl;
             lo.glo = c->glo.as<int32_t>();
-            lo.slot_pfix_hi = c->slot_pfix_hi.as<int64_t>();
+            lo.slot_pfix_hi = c->rows.slot_pfix_hi.as<int64_t>();
             lo.hi_shift = 8 * LO_LIMBS;
         }
         {   // per-block SNP constants in epilogue order (A.lo is final by now: the high-limb marginals are reachable)
@@ -416,16 +416,16 @@ int launch_block_mi(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int RF
         LDW_HIP(hipGetLastError());
         if (mixed) {   // low limbs of the listed units
             LoGemmArgs P;
-            P.Mbits = c->Mbits.as<uint64_t>();
+            P.Mbits = c->rows.Mbits.as<uint64_t>();
             P.KW = c->KW;
             P.Kpad = c->KW * 64;
-            P.digits_lo = c->digits.as<int8_t>();
+            P.digits_lo = c->wts.digits.as<int8_t>();
             P.perm_f = D.perm;
             P.idx_f = D.idx_f;
             P.perm_t = D.perm_t;
             P.idx_t = D.idx_t;
-            P.row0 = c->row0.as<int32_t>();
-            P.zero_row = (int32_t)c->R;
+            P.row0 = c->rows.row0.as<int32_t>();
+            P.zero_row = (int32_t)c->rows.R;
             P.nf = (int32_t)nf;
             P.nt = (int32_t)nt;
             P.tf_list = D.tf_list;
@@ -494,7 +494,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     PairsLayout PL(pl_cap, maybe_cap);
     auto place = [c, phase](Carve &cv, ldw::DevBuf &b) {
         if (phase == 1) {
-            c->slot_grown += cv.bytes > b.cap || !b.p ? 1 : 0;
+            c->cnt.slot_grown += cv.bytes > b.cap || !b.p ? 1 : 0;
             return cv.reserve(b);
         }
         cv.bind(b);
@@ -537,25 +537,25 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
             // on ONE stream, so the rebuild cannot overtake a reader.
             const int kd = lo_h->diag ? 1 : 0;
             const double lo_blk = E.spec_lo - (double)E.scr_eps;
-            if (!(c->tab11_lo[kd] > 0) || lo_blk < c->tab11_lo[kd] || lo_blk > 1.05 * c->tab11_lo[kd]) {
+            if (!(c->spec.tab11_lo[kd] > 0) || lo_blk < c->spec.tab11_lo[kd] || lo_blk > 1.05 * c->spec.tab11_lo[kd]) {
                 constexpr int NBINS_T = 64;
-                if (int rc = c->tab11[kd].reserve((size_t)4 * NBINS_T * NBINS_T * 8)) return rc;   // a ring of four tables
-                c->tab11_cur[kd] = (c->tab11_cur[kd] + 1) & 3;   // (items in flight — at most the two before this one — keep the tables they were screened for)
-                const double W = std::ldexp((double)c->total_fixed, -c->frac_bits);
-                c->tab11_lo[kd] = 0.98 * lo_blk;   // buckets are 0.5 % wide: the next blocks of the kind may guess four buckets lower (six higher) without a rebuild (73 us)
-                c->tab11_c = (float)(NBINS_T / std::sqrt(W + 1.0));
-                c->tab11_nb = NBINS_T;
-                const double sprime = std::ldexp(1.0, c->apx_e_last - c->frac_bits);
-                hipLaunchKernelGGL(k_build_tab11, dim3(NBINS_T * NBINS_T * 32 / 256), dim3(256), 0, gs, W, c->tab11_lo[kd], c->apx_delta * 1.001,
-                                   (c->apx_lost_units + 1.0) * sprime, sprime, NBINS_T, c->tab11_c, c->tab11[kd].as<int2>() + (size_t)c->tab11_cur[kd] * NBINS_T * NBINS_T);
+                if (int rc = c->spec.tab11[kd].reserve((size_t)4 * NBINS_T * NBINS_T * 8)) return rc;   // a ring of four tables
+                c->spec.tab11_cur[kd] = (c->spec.tab11_cur[kd] + 1) & 3;   // (items in flight — at most the two before this one — keep the tables they were screened for)
+                const double W = std::ldexp((double)c->wts.total_fixed, -c->wts.frac_bits);
+                c->spec.tab11_lo[kd] = 0.98 * lo_blk;   // buckets are 0.5 % wide: the next blocks of the kind may guess four buckets lower (six higher) without a rebuild (73 us)
+                c->spec.tab11_c = (float)(NBINS_T / std::sqrt(W + 1.0));
+                c->spec.tab11_nb = NBINS_T;
+                const double sprime = std::ldexp(1.0, c->apx.apx_e_last - c->wts.frac_bits);
+                hipLaunchKernelGGL(k_build_tab11, dim3(NBINS_T * NBINS_T * 32 / 256), dim3(256), 0, gs, W, c->spec.tab11_lo[kd], c->apx.apx_delta * 1.001,
+                                   (c->apx.apx_lost_units + 1.0) * sprime, sprime, NBINS_T, c->spec.tab11_c, c->spec.tab11[kd].as<int2>() + (size_t)c->spec.tab11_cur[kd] * NBINS_T * NBINS_T);
                 LDW_HIP(hipGetLastError());
-                ++c->tab11_builds;
+                ++c->cnt.tab11_builds;
             }
         }
     }
     EpiArgs A;
     fill_epi_args(c, D, nf, nt, RFpad, quirk, E, reinterpret_cast<const int64_t *>(c->Gapx[s].p), A);
-    A.lo.slot_pfix_hi = c->slot_papx.as<int64_t>();   // the screen derives its cells from the marginals of the approximate weights
+    A.lo.slot_pfix_hi = c->rows.slot_papx.as<int64_t>();   // the screen derives its cells from the marginals of the approximate weights
     if (lo_h->span) {
         LDW_REQUIRE(E.scr_mode == 1 && E.do_lr && !E.any_sr && !lo_h->band_full && lo_h->fuse_ok && lo_h->sseg, LDW_ERR_STATE, "a span needs long-range-only blocks and pair lists");
         A.span = lo_h->span;
@@ -565,28 +565,28 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     // (the table is built for RXY = 1, the floor of the reference's scrambled RXY = r r' / 4 as long as no SNP has r < 2)
     if (phase == 1 || !lo_h->tab_set) {
         lo_h->tab_p = nullptr;
-        if (E.do_lr && c->tab11[kd_tab].p && c->tab11_lo[kd_tab] > 0 && E.spec_lo - (double)E.scr_eps >= c->tab11_lo[kd_tab] &&
-            (quirk != LDW_QUIRK_REFERENCE || c->r_min >= 2.0))
-            lo_h->tab_p = c->tab11[kd_tab].as<int2>() + (size_t)c->tab11_cur[kd_tab] * 64 * 64;
+        if (E.do_lr && c->spec.tab11[kd_tab].p && c->spec.tab11_lo[kd_tab] > 0 && E.spec_lo - (double)E.scr_eps >= c->spec.tab11_lo[kd_tab] &&
+            (quirk != LDW_QUIRK_REFERENCE || c->meta.r_min >= 2.0))
+            lo_h->tab_p = c->spec.tab11[kd_tab].as<int2>() + (size_t)c->spec.tab11_cur[kd_tab] * 64 * 64;
         lo_h->tab_set = true;
     }
     if (lo_h->tab_p) {   // (phase 2: the table of phase 1, whatever later items have built since)
         A.tab11 = lo_h->tab_p;
-        A.tab_nb = c->tab11_nb;
-        A.tab_c = c->tab11_c;
+        A.tab_nb = c->spec.tab11_nb;
+        A.tab_c = c->spec.tab11_c;
     }
     // long-range-only blocks: the GEMM applies the table itself and neither stores nor lets the screen read the regions that pass
-    const bool fuse = lo_h->fuse_ok && A.tab11 && A.tab_nb == 64 && (use_pairs || c->screen == 2) && E.do_lr && (!E.any_sr || (D.band_mask && !lo_h->band_full)) && RFpad % 64 == 0 &&   // (verify mode: the clean regions' units are listed as dismissed and checked in fp64)
+    const bool fuse = lo_h->fuse_ok && A.tab11 && A.tab_nb == 64 && (use_pairs || c->knobs.screen == 2) && E.do_lr && (!E.any_sr || (D.band_mask && !lo_h->band_full)) && RFpad % 64 == 0 &&   // (verify mode: the clean regions' units are listed as dismissed and checked in fp64)
                       2048 + (size_t)(c->KW / 2) * 256 + 64 * 64 * 8 + 1024 <= 65536;   // (the table shares the GEMM's LDS with the digit arrays)
     // pruning flags by row and by epilogue slot
-    const bool wide_prune = c->prune && c->snp_sup.p && E.do_lr && (use_pairs || c->screen == 2);
+    const bool wide_prune = c->knobs.prune && c->rows.snp_sup.p && E.do_lr && (use_pairs || c->knobs.screen == 2);
     uint8_t *sflag_f = nullptr, *sflag_t = nullptr, *rflag_f = nullptr, *rflag_t = nullptr;
     if (wide_prune) {
         sflag_f = B.sflag_f;
         sflag_t = B.sflag_t;
         rflag_f = B.rflag_f;
         rflag_t = B.rflag_t;
-        A.snp_sup = c->snp_sup.as<double>();
+        A.snp_sup = c->rows.snp_sup.as<double>();
         A.sflag_f = sflag_f;
         A.sflag_t = sflag_t;
     }
@@ -605,7 +605,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     // (only where the K loop is long enough to carry the epilogue's extra work — the mask of the failing entries is built for every eligible
     // region: at N = 616 the GEMM's launch went from 0.091 to 0.107 ms and the pass from 19.4 to 20.1 ms with it, at N = 5000 the launch does
     // not move and the pass gains 0.3-0.4 ms; building the mask only in failing regions was slower at both sizes)
-    const bool use_maybe = maybe_on && !c->maybe_off && fuse && use_pairs && c->screen == 1 && !E.lower_only && c->KW >= 32;
+    const bool use_maybe = maybe_on && !c->spec.maybe_off && fuse && use_pairs && c->knobs.screen == 1 && !E.lower_only && c->KW >= 32;
     unsigned int *maybe_n = nullptr;
     ApxMaybe *maybe_list = nullptr;
     MiniCol *mini_c = nullptr;
@@ -662,15 +662,15 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
             P.RTpad = RTpad;
             P.RFpad = RFpad;
             P.M2 = (int)(c->KW / 2);
-            P.dig_a = c->dig_a.as<uint8_t>();
-            P.dig_b = c->dig_b.as<uint8_t>();
-            P.shift = c->apx_shift.as<int32_t>();
-            P.fine = c->apx_fine ? 1 : 0;
+            P.dig_a = c->apx.dig_a.as<uint8_t>();
+            P.dig_b = c->apx.dig_b.as<uint8_t>();
+            P.shift = c->apx.apx_shift.as<int32_t>();
+            P.fine = c->apx.apx_fine ? 1 : 0;
             P.G = c->Gapx[s].as<int32_t>();
             P.lower_only = E.lower_only;
             if (fuse) {
                 P.fuse = 1;
-                P.skip_ctr = (c->prune && lo_h->ordered) ? c->apx_skip.as<unsigned long long>() : nullptr;   // (list order: a tile spans every bin)
+                P.skip_ctr = (c->knobs.prune && lo_h->ordered) ? c->apx_skip.as<unsigned long long>() : nullptr;   // (list order: a tile spans every bin)
                 if (P.skip_ctr) {
                     P.tile_list = B.tile_list;
                     P.n_live = B.n_live;
@@ -724,7 +724,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
             LDW_HIP(hipGetLastError());
         }
         if (band_early && need_exact)
-            if (int rc = launch_gemm_bits(c, c->Mbits.as<uint64_t>(), c->KW, D.rl_t, RTpad, D.rl_f, RFpad, Gx.as<int64_t>(), c->nlimbs, c->digits.as<int8_t>(),
+            if (int rc = launch_gemm_bits(c, c->rows.Mbits.as<uint64_t>(), c->KW, D.rl_t, RTpad, D.rl_f, RFpad, Gx.as<int64_t>(), c->wts.nlimbs, c->wts.digits.as<int8_t>(),
                                           E.lower_only, gs, 0, -1, band, band ? D.band_list : nullptr, D.n_band))
                 return rc;
         if (use_maybe && E.do_lr) {
@@ -746,7 +746,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
     launch_screen_generic<true>(A, D, (int)egrid.x, U, s2);
     LDW_HIP(hipGetLastError());
     if (need_exact && !band_early)
-        if (int rc = launch_gemm_bits(c, c->Mbits.as<uint64_t>(), c->KW, D.rl_t, RTpad, D.rl_f, RFpad, Gx.as<int64_t>(), c->nlimbs, c->digits.as<int8_t>(),
+        if (int rc = launch_gemm_bits(c, c->rows.Mbits.as<uint64_t>(), c->KW, D.rl_t, RTpad, D.rl_f, RFpad, Gx.as<int64_t>(), c->wts.nlimbs, c->wts.digits.as<int8_t>(),
                                       E.lower_only, s2, 0, -1, band, band ? D.band_list : nullptr, D.n_band))
             return rc;
     if (use_pairs) {
@@ -776,7 +776,7 @@ void build_perm_tiles(ldw_ctx *c, const int32_t *from_idx, int64_t nf, std::vect
         if (want == 1 && order1) perm.insert(perm.end(), order1->begin(), order1->end());   // (every one-row SNP, in row order: build_side)
         else
             for (int64_t k = 0; k < nf; ++k)
-                if (c->h_row0[from_idx[k] + 1] - c->h_row0[from_idx[k]] == want) perm.push_back((int32_t)k);
+                if (c->rows.h_row0[from_idx[k] + 1] - c->rows.h_row0[from_idx[k]] == want) perm.push_back((int32_t)k);
         if (want != 3)   // 3 and 4 rows share the generic code anyway
             while (perm.size() % 64) perm.push_back(-1);
     }
@@ -791,7 +791,7 @@ void build_perm(ldw_ctx *c, const int32_t *from_idx, int64_t nf, int32_t *perm, 
             continue;
         }
         for (int64_t k = 0; k < nf; ++k)
-            if (c->h_row0[from_idx[k] + 1] - c->h_row0[from_idx[k]] == want) perm[w++] = (int32_t)k;
+            if (c->rows.h_row0[from_idx[k] + 1] - c->rows.h_row0[from_idx[k]] == want) perm[w++] = (int32_t)k;
     }
 }
 
@@ -801,21 +801,21 @@ void build_perm(ldw_ctx *c, const int32_t *from_idx, int64_t nf, int32_t *perm, 
 // valid whatever another thread adds; a full cache (256 lists) computes into the caller's own vector instead.
 const std::vector<int32_t> *minor_weight_order(ldw_ctx *c, const int32_t *idx, int64_t n, std::vector<int32_t> &own) {
     {
-        std::lock_guard<std::mutex> lk(c->order_mtx);
-        for (auto &pe : c->order_cache)
+        std::lock_guard<std::mutex> lk(c->rows.order_mtx);
+        for (auto &pe : c->rows.order_cache)
             if ((int64_t)pe->idx.size() == n && pe->idx[0] == idx[0] && memcmp(pe->idx.data(), idx, (size_t)n * 4) == 0) return &pe->order;
     }
     std::vector<std::pair<int64_t, int32_t>> key;
     key.reserve((size_t)n);
     for (int64_t k = 0; k < n; ++k)
-        if (c->h_row0[idx[k] + 1] - c->h_row0[idx[k]] == 1) key.emplace_back(c->h_minor_w[(size_t)idx[k]], (int32_t)k);
+        if (c->rows.h_row0[idx[k] + 1] - c->rows.h_row0[idx[k]] == 1) key.emplace_back(c->rows.h_minor_w[(size_t)idx[k]], (int32_t)k);
     std::sort(key.begin(), key.end());
     own.resize(key.size());
     for (size_t i = 0; i < key.size(); ++i) own[i] = key[i].second;
-    std::lock_guard<std::mutex> lk(c->order_mtx);
-    if (c->order_cache.size() >= 256) return &own;
-    c->order_cache.emplace_back(new ldw_ctx::OrderCache());
-    auto &e = *c->order_cache.back();
+    std::lock_guard<std::mutex> lk(c->rows.order_mtx);
+    if (c->rows.order_cache.size() >= 256) return &own;
+    c->rows.order_cache.emplace_back(new ldw::OrderCache());
+    auto &e = *c->rows.order_cache.back();
     e.idx.assign(idx, idx + n);
     e.order = own;
     return &e.order;
@@ -864,17 +864,17 @@ int run_block_mi(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t 
 int ensure_links_capacity(ldw_ctx *c, int64_t sr_rows, int64_t lr_rows) {
     // a reallocation (rare: the all-pairs driver sizes the table up front) waits for the GEMM stream and is complete before
     // anything else is queued
-    const bool grow_sr = (size_t)sr_rows * 8 > c->sr_mi.cap || (size_t)sr_rows * 4 > c->sr_a.cap || (size_t)sr_rows * 4 > c->sr_b.cap;
+    const bool grow_sr = (size_t)sr_rows * 8 > c->links.sr_mi.cap || (size_t)sr_rows * 4 > c->links.sr_a.cap || (size_t)sr_rows * 4 > c->links.sr_b.cap;
     if (grow_sr && c->gemm_stream) LDW_HIP(hipStreamSynchronize(c->gemm_stream));
-    if (int rc = c->sr_a.reserve_keep((size_t)sr_rows * 4, (size_t)c->n_sr * 4, c->stream)) return rc;
-    if (int rc = c->sr_b.reserve_keep((size_t)sr_rows * 4, (size_t)c->n_sr * 4, c->stream)) return rc;
-    if (int rc = c->sr_mi.reserve_keep((size_t)sr_rows * 8, (size_t)c->n_sr * 8, c->stream)) return rc;
+    if (int rc = c->links.sr_a.reserve_keep((size_t)sr_rows * 4, (size_t)c->links.n_sr * 4, c->stream)) return rc;
+    if (int rc = c->links.sr_b.reserve_keep((size_t)sr_rows * 4, (size_t)c->links.n_sr * 4, c->stream)) return rc;
+    if (int rc = c->links.sr_mi.reserve_keep((size_t)sr_rows * 8, (size_t)c->links.n_sr * 8, c->stream)) return rc;
     if (grow_sr) LDW_HIP(hipStreamSynchronize(c->stream));
-    if (c->lr_stream && ((size_t)lr_rows * 8 > c->lr_mi.cap || (size_t)lr_rows * 4 > c->lr_a.cap || (size_t)lr_rows * 4 > c->lr_b.cap))
+    if (c->lr_stream && ((size_t)lr_rows * 8 > c->links.lr_mi.cap || (size_t)lr_rows * 4 > c->links.lr_a.cap || (size_t)lr_rows * 4 > c->links.lr_b.cap))
         lr_stream_drain(c);   // (the writer thread reads these buffers on its own stream: everything handed over is on disk before they move)
-    if (int rc = c->lr_a.reserve_keep((size_t)lr_rows * 4, (size_t)c->n_lr * 4, c->stream)) return rc;
-    if (int rc = c->lr_b.reserve_keep((size_t)lr_rows * 4, (size_t)c->n_lr * 4, c->stream)) return rc;
-    if (int rc = c->lr_mi.reserve_keep((size_t)lr_rows * 8, (size_t)c->n_lr * 8, c->stream)) return rc;
+    if (int rc = c->links.lr_a.reserve_keep((size_t)lr_rows * 4, (size_t)c->links.n_lr * 4, c->stream)) return rc;
+    if (int rc = c->links.lr_b.reserve_keep((size_t)lr_rows * 4, (size_t)c->links.n_lr * 4, c->stream)) return rc;
+    if (int rc = c->links.lr_mi.reserve_keep((size_t)lr_rows * 8, (size_t)c->links.n_lr * 8, c->stream)) return rc;
     return LDW_OK;
 }
 
@@ -894,6 +894,6 @@ void links_layout(ldw_ctx *c, SmallLayout &sl) {
     // (every slot has room for the pick records of a span's segments: segment k of slot s at sl.pick[s] + k * PICK_STRIDE bytes)
     for (int k = 0; k < LDW_NSLOT; ++k) sl.pick[k] = reinterpret_cast<ldw::PickOut *>(base + 64 + (size_t)k * LDW_SPAN_MAX * PICK_STRIDE);
     sl.stats_i = reinterpret_cast<int64_t *>(base + 64 + (size_t)LDW_NSLOT * LDW_SPAN_MAX * PICK_STRIDE);
-    sl.stats_d = reinterpret_cast<double *>(sl.stats_i + c->blk_capacity * 3);
+    sl.stats_d = reinterpret_cast<double *>(sl.stats_i + c->links.blk_capacity * 3);
 }
 

@@ -78,7 +78,7 @@ struct SpanPlan {
 // 5 %.  Above 0.7 % every block takes the plain path (5-limb GEMM, fp64 MI of every pair, full histogram), cold start included.
 // Only the automatic choice is gated: ldw_set_path(1 | 2) is honoured as given.
 static inline bool speculation_pays(const ldw_ctx *c, const ldw_mi_params *p) {
-    if (c->path_mode != 0) return true;
+    if (c->knobs.path_mode != 0) return true;
     return !(p->lr_links_approx > 0.0) || p->lr_retain_links < 0.007 * p->lr_links_approx;
 }
 
@@ -118,7 +118,7 @@ int PrepWork::intervals(const ldw_mi_params *p, const SpanPlan *sp) {
     const int64_t blk_no = hb.blk_no;
     auto ascending = [&](const int32_t *idx, int64_t n) {
         for (int64_t k = 1; k < n; ++k)
-            if (c->h_POS[idx[k]] < c->h_POS[idx[k - 1]]) return false;
+            if (c->meta.h_POS[idx[k]] < c->meta.h_POS[idx[k - 1]]) return false;
         return true;
     };
     hb.generic = !ascending(from_idx, nf) || !ascending(to_idx, nt);
@@ -175,10 +175,10 @@ int PrepWork::intervals(const ldw_mi_params *p, const SpanPlan *sp) {
 // of tiles the exact GEMM covers needs their partners contiguous — behind the ordered rest.  Diagonal blocks stay as they are:
 // every SNP has short-range partners there.
 int PrepWork::row_order(const SpanPlan *sp) {
-    if (c->prune && !hb.generic && !hb.diag && c->engine == LDW_ENGINE_MFMA && c->apx_ok) {
+    if (c->knobs.prune && !hb.generic && !hb.diag && c->knobs.engine == LDW_ENGINE_MFMA && c->apx.apx_ok) {
         bool rowless = false;
-        for (int64_t k = 0; k < nf && !rowless; ++k) rowless = c->h_row0[from_idx[k] + 1] == c->h_row0[from_idx[k]];
-        for (int64_t k = 0; k < nt && !rowless; ++k) rowless = c->h_row0[to_idx[k] + 1] == c->h_row0[to_idx[k]];
+        for (int64_t k = 0; k < nf && !rowless; ++k) rowless = c->rows.h_row0[from_idx[k] + 1] == c->rows.h_row0[from_idx[k]];
+        for (int64_t k = 0; k < nt && !rowless; ++k) rowless = c->rows.h_row0[to_idx[k] + 1] == c->rows.h_row0[to_idx[k]];
         if (!rowless) {
             ord_f = minor_weight_order(c, from_idx, nf, ord_f_full);
             ord_t = minor_weight_order(c, to_idx, nt, ord_t_full);
@@ -205,14 +205,14 @@ int PrepWork::row_order(const SpanPlan *sp) {
                     for (int32_t k : sorted)
                         if (!corner[(size_t)k]) out.push_back(k);
                     for (int64_t k = 0; k < n; ++k)
-                        if (corner[(size_t)k] && c->h_row0[idx[k] + 1] - c->h_row0[idx[k]] == 1) out.push_back((int32_t)k);
+                        if (corner[(size_t)k] && c->rows.h_row0[idx[k] + 1] - c->rows.h_row0[idx[k]] == 1) out.push_back((int32_t)k);
                 };
                 rest_then_corner(*ord_f, in_f, from_idx, nf, ord_f_own);
                 rest_then_corner(*ord_t, in_t, to_idx, nt, ord_t_own);
                 ord_f = &ord_f_own;
                 ord_t = &ord_t_own;
             }
-            c->sorted_blocks += sp ? sp->nseg : 1;
+            c->cnt.sorted_blocks += sp ? sp->nseg : 1;
         }
     }
     LDW_REQUIRE(!sp || (ord_f && ord_t), LDW_ERR_STATE, "span at block %lld cannot be ordered", (long long)hb.blk_no);
@@ -225,7 +225,7 @@ void PrepWork::tiles(int slot) {
     {   // where the SNPs with 1 or 2 indicator rows end in either order
         int64_t n12f = 0, n1 = 0, n2 = 0;
         for (int64_t k = 0; k < nf; ++k) {
-            const int nr = c->h_row0[from_idx[k] + 1] - c->h_row0[from_idx[k]];
+            const int nr = c->rows.h_row0[from_idx[k] + 1] - c->rows.h_row0[from_idx[k]];
             n1 += nr == 1;
             n2 += nr == 2;
         }
@@ -233,7 +233,7 @@ void PrepWork::tiles(int slot) {
         hb.D.gen_t0 = (int)n12f;
         int64_t q12 = 0;
         for (int64_t k = 0; k < nt; ++k) {
-            const int nr = c->h_row0[to_idx[k] + 1] - c->h_row0[to_idx[k]];
+            const int nr = c->rows.h_row0[to_idx[k] + 1] - c->rows.h_row0[to_idx[k]];
             q12 += nr == 1 || nr == 2;
         }
         hb.D.gen_q0 = (int)q12;
@@ -244,7 +244,7 @@ void PrepWork::tiles(int slot) {
     {
         LoHost &lo = hb.lo;
         lo = LoHost();
-        for (int64_t k = 0; k < nt; ++k) ++lo.n_lc[lo_class(c->h_row0[to_idx[k] + 1] - c->h_row0[to_idx[k]])];
+        for (int64_t k = 0; k < nt; ++k) ++lo.n_lc[lo_class(c->rows.h_row0[to_idx[k] + 1] - c->rows.h_row0[to_idx[k]])];
         int32_t uo = 0, rb = 0;
         for (int lc = 0; lc < 3; ++lc) {
             lo.uoff[lc] = uo;
@@ -257,7 +257,7 @@ void PrepWork::tiles(int slot) {
         for (size_t t = 0; t < pf.size(); ++t) {
             if (pf[t] < 0) continue;
             const int32_t a = from_idx[pf[t]];
-            const int cls = 1 << lo_class(c->h_row0[a + 1] - c->h_row0[a]);
+            const int cls = 1 << lo_class(c->rows.h_row0[a + 1] - c->rows.h_row0[a]);
             if (cls > cmax[t / 64]) cmax[t / 64] = cls;
         }
         int64_t tb = 0;
@@ -288,21 +288,21 @@ void PrepWork::band_mask() {
     bool no_rowless = true;   // no SNP without an indicator row: a one-row SNP's row-list position is its slot (ApxGemmArgs::fuse)
     {
         const int ntx = hb.RFpad / 64;
-        auto cls_of = [&](int32_t snp) { const int nr = c->h_row0[snp + 1] - c->h_row0[snp]; return nr <= 1 ? 0 : (nr == 2 ? 1 : 2); };
+        auto cls_of = [&](int32_t snp) { const int nr = c->rows.h_row0[snp + 1] - c->rows.h_row0[snp]; return nr <= 1 ? 0 : (nr == 2 ? 1 : 2); };
         std::vector<int32_t> pre[3];
         int32_t base[3] = {0, 0, 0};
         for (int k = 0; k < 3; ++k) pre[k].assign((size_t)nf + 1, 0);
         for (int64_t a = 0; a < nf; ++a) {
             const int k = cls_of(from_idx[a]);
             for (int q = 0; q < 3; ++q) pre[q][(size_t)a + 1] = pre[q][(size_t)a] + (q == k ? 1 : 0);
-            const uint32_t m = c->h_slot_meta[(size_t)from_idx[a]];
+            const uint32_t m = c->rows.h_slot_meta[(size_t)from_idx[a]];
             const int n = (int)(m & 7);
             if ((n == 1 || n == 2) && (((m >> 3) & ((2u << n) - 1u)) != ((2u << n) - 1u))) hb.lo.band_full = 1;
             if (n == 0) hb.lo.band_full = 1;   // SNPs without a row sit among the one-row SNPs in the row list but last in the tiles
             if (n == 0) no_rowless = false;
         }
         for (int64_t b2 = 0; b2 < nt; ++b2) {
-            const uint32_t m = c->h_slot_meta[(size_t)to_idx[b2]];
+            const uint32_t m = c->rows.h_slot_meta[(size_t)to_idx[b2]];
             const int n = (int)(m & 7);
             if (n == 0) no_rowless = false;
             if ((n == 1 || n == 2) && (((m >> 3) & ((2u << n) - 1u)) != ((2u << n) - 1u))) hb.lo.band_full = 1;
@@ -387,7 +387,7 @@ int prep_block(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
         LDW_REQUIRE(from_idx[k] >= 0 && from_idx[k] < c->L, LDW_ERR_ARG, "SNP index %d out of range", from_idx[k]);
     for (int64_t k = 0; k < nt; ++k)
         LDW_REQUIRE(to_idx[k] >= 0 && to_idx[k] < c->L, LDW_ERR_ARG, "SNP index %d out of range", to_idx[k]);
-    static const bool prep_timing = getenv("LDW_HOST_TIMING") != nullptr;
+    const bool prep_timing = ldw::host_timing();
     auto pnow = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tp[8] = {pnow(), 0, 0, 0, 0, 0, 0, 0};
     hb = HostBlock();
@@ -464,8 +464,8 @@ int launch_gather(ldw_ctx *c, const HostBlock &hb, const EmitArgs &E, const Smal
 // subtraction from the high-limb marginals — misses exactly the low limbs of ITS sequences, so sum_cells |dp| <= lo_abs_sum;
 // dMI <= (1/den) sum_cells |dp| (|ln(pxy den / d)| + 1) with 0.5 <= pxy <= den, 0.25 <= d <= den^2, den >= neff.
 double lo_bound(const ldw_ctx *c) {
-    const double den = c->neff > 1.0 ? c->neff : 1.0;
-    return c->lo_abs_sum * (2.0 * std::log(den + 12.5) + 3.0) / den;
+    const double den = c->wts.neff > 1.0 ? c->wts.neff : 1.0;
+    return c->wts.lo_abs_sum * (2.0 * std::log(den + 12.5) + 3.0) / den;
 }
 
 // what the emission of a block's pairs needs (short-range table, candidate list of this slot)
@@ -479,10 +479,10 @@ int make_emit_args(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
     E.lower_only = hb.diag ? 1 : 0;
     E.keep_sr = p->keep_sr ? 1 : 0;
     E.do_lr = do_lr ? 1 : 0;
-    E.sr_base = c->early_sr ? hb.sr_base : c->n_sr;   // (early_sr: the rows were assigned when the item was submitted)
-    E.sr_a = c->sr_a.as<int32_t>();
-    E.sr_b = c->sr_b.as<int32_t>();
-    E.sr_mi = c->sr_mi.as<double>();
+    E.sr_base = c->early_sr ? hb.sr_base : c->links.n_sr;   // (early_sr: the rows were assigned when the item was submitted)
+    E.sr_a = c->links.sr_a.as<int32_t>();
+    E.sr_b = c->links.sr_b.as<int32_t>();
+    E.sr_mi = c->links.sr_mi.as<double>();
     // Long-range candidates: with a bucket guess from an earlier block the epilogue appends them itself and the
     // dense MI block is neither written nor re-read; without one (first block, histogram engine) the dense block
     // is written and k_lr_gather collects them once the true bucket is known.
@@ -525,14 +525,14 @@ int make_emit_args(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
         E.cval = c->miss_val.as<uint64_t>();
     }
     // fp32 screen: only where a pair can be dismissed at all (speculative mode with a positive lower edge)
-    E.scr_mode = (hb.spec_B > 0 || !do_lr) && !E.write_dense && (!do_lr || speculation_pays(c, p)) ? c->screen : 0;   // (no screen where nearly every unit would be listed)
+    E.scr_mode = (hb.spec_B > 0 || !do_lr) && !E.write_dense && (!do_lr || speculation_pays(c, p)) ? c->knobs.screen : 0;   // (no screen where nearly every unit would be listed)
     // the screen reads the top 31 bits of a joint sum; in the mixed-precision path the sums are those of the high-limb
     // weights (units of 2^(16 - F)) and the margin also covers what the low limbs can add (lo_bound)
-    const int64_t tot = hb.mixed ? c->total_fixed_hi : c->total_fixed;
+    const int64_t tot = hb.mixed ? c->wts.total_fixed_hi : c->wts.total_fixed;
     int bits = 0;
     while (bits < 62 && (tot >> bits) != 0) ++bits;
     E.scr_shift = bits > 31 ? bits - 31 : 0;
-    E.scr_scale = (float)std::ldexp(1.0, E.scr_shift - c->frac_bits + (hb.mixed ? 8 * LO_LIMBS : 0));
+    E.scr_scale = (float)std::ldexp(1.0, E.scr_shift - c->wts.frac_bits + (hb.mixed ? 8 * LO_LIMBS : 0));
     E.scr_eps = SCREEN_EPS + (hb.mixed ? (float)lo_bound(c) : 0.0f);
     if (hb.apx) {
         apx_screen_params(c, E);   // (ldw_epi.h: shared with the test hook ldw_debug_apx_params, so that the brute-force tests price the engine's own constants)
@@ -557,7 +557,7 @@ int launch_pick(ldw_ctx *c, const HostBlock &hb, const ldw_mi_params *p, const S
         return LDW_OK;
     }
     if (!p->sr_only) {
-        const bool pl = hb.apx && c->screen == 1;
+        const bool pl = hb.apx && c->knobs.screen == 1;
         hipLaunchKernelGGL(k_pick_bucket, dim3(1), dim3(256), 0, st, c->hist[s].as<unsigned long long>(), p->lr_retain_links,
                            p->lr_links_approx, hb.spec_B, (long long)hb.n_lr_total, sl.pick[s],
                            pl ? pl_hdr : nullptr, pair_cap_for(hb.nf, hb.nt));
@@ -594,55 +594,55 @@ int submit_a(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayou
     const int s = hb.slot;
     if (int rc = submit_upload(c, hb)) return rc;
     hb.submitted = true;
-    if (c->engine != LDW_ENGINE_MFMA || hb.generic) return LDW_OK;
-    hipStream_t gs = c->overlap ? c->gemm_stream : c->stream;   // overlap off: the stages of all blocks run back to back
+    if (c->knobs.engine != LDW_ENGINE_MFMA || hb.generic) return LDW_OK;
+    hipStream_t gs = c->knobs.overlap ? c->gemm_stream : c->stream;   // overlap off: the stages of all blocks run back to back
     LDW_HIP(hipStreamWaitEvent(gs, c->ev_up[s], 0));
     if (c->done_recorded[s]) LDW_HIP(hipStreamWaitEvent(gs, c->ev_done[s], 0));
     const hipEvent_t *ev = handles(&c->ev_pool[(size_t)hb.blk_no * EVB]);
     const bool do_lr = !p->sr_only;
     // (a span: one guess serves every reference block, and the next guess only arrives after all of them.  No wider margin is needed: at C5
     // (800 kept rows per block, the noisiest thresholds) 3 of 1275 blocks miss per pass, as many as block by block)
-    const int guess = do_lr ? ((speculation_pays(c, p) && !hb.force_plain) ? c->spec_B_next[hb.diag ? 1 : 0] : -1) : 0;
+    const int guess = do_lr ? ((speculation_pays(c, p) && !hb.force_plain) ? c->spec.spec_B_next[hb.diag ? 1 : 0] : -1) : 0;
     if ((int64_t)c->ev_valid.size() < hb.blk_no + std::max(1, hb.span)) c->ev_valid.resize((size_t)(hb.blk_no + std::max(1, hb.span)), 1);
     c->ev_valid[(size_t)hb.blk_no] = 1;
     for (int k = 1; k < hb.span; ++k) c->ev_valid[(size_t)hb.blk_no + k] = 0;   // (the span's stage events are its first block's; a segment that runs alone records its own)
     if (c->early_sr) {   // this pass assigns short-range rows in SUBMIT order (= block order)
         const int64_t sr_add = p->keep_sr ? hb.n_sr_blk : 0;
-        if (int rc = ensure_links_capacity(c, c->n_sr + sr_add, c->n_lr)) return rc;
-        hb.sr_base = c->n_sr;
-        c->n_sr += sr_add;
+        if (int rc = ensure_links_capacity(c, c->links.n_sr + sr_add, c->links.n_lr)) return rc;
+        hb.sr_base = c->links.n_sr;
+        c->links.n_sr += sr_add;
     }
     if (hb.span) {
         // a span runs the approximate path or not at all: should the state it was planned on have gone (no positive guess any more),
         // its reference blocks take the ordinary chain one after the other (finish_span)
-        const bool can = c->path_mode != 1 && c->apx_ok && c->screen == 1 && do_lr && guess > 0;
+        const bool can = c->knobs.path_mode != 1 && c->apx.apx_ok && c->knobs.screen == 1 && do_lr && guess > 0;
         if (!can) {
             hb.span_alone = true;
             return LDW_OK;
         }
     }
-    c->blocks_run += hb.span ? hb.span : 1;
+    c->cnt.blocks_run += hb.span ? hb.span : 1;
     hb.guess = guess;
     // mixed precision: with a bucket guess the block will run the screen, which only needs the high limbs; the low
     // limbs follow for the listed units only.  The guess is frozen here because the GEMM commits to it.
-    hb.mixed = c->mixed && c->screen && c->nlimbs == HI_LIMBS + LO_LIMBS && do_lr && guess > 0 && lo_bound(c) < 1e-3 &&
+    hb.mixed = c->knobs.mixed && c->knobs.screen && c->wts.nlimbs == HI_LIMBS + LO_LIMBS && do_lr && guess > 0 && lo_bound(c) < 1e-3 &&
                c->N <= 60000;   // the low-limb sums are int32: |sum| <= N * 2^15
     // approximate GEMM + class-wise popcounts: any block that takes the screen path (a bucket guess exists, or the pass
     // is SR-only and needs no MI to screen at all)
-    hb.apx = c->path_mode != 1 && c->apx_ok && c->screen && (do_lr ? guess > 0 : true) && hb.nt < (1 << 29);
-    LDW_REQUIRE(c->path_mode != 2 || hb.apx || (do_lr && guess <= 0), LDW_ERR_STATE,
-                "ldw_set_path(2): the approximate path is not available (delta %.3g, %d weight classes, %lld sequences, screen %d)", c->apx_delta,
-                c->n_classes, (long long)c->N, c->screen);
+    hb.apx = c->knobs.path_mode != 1 && c->apx.apx_ok && c->knobs.screen && (do_lr ? guess > 0 : true) && hb.nt < (1 << 29);
+    LDW_REQUIRE(c->knobs.path_mode != 2 || hb.apx || (do_lr && guess <= 0), LDW_ERR_STATE,
+                "ldw_set_path(2): the approximate path is not available (delta %.3g, %d weight classes, %lld sequences, screen %d)", c->apx.apx_delta,
+                c->apx.n_classes, (long long)c->N, c->knobs.screen);
     if (hb.apx) {
         hb.mixed = false;
         hb.lo.apx = 1;
-        c->apx_blocks += hb.span ? hb.span : 1;
+        c->cnt.apx_blocks += hb.span ? hb.span : 1;
     }
     if (hb.span) {
-        ++c->span_items;
-        c->span_blocks += hb.span;
+        ++c->cnt.span_items;
+        c->cnt.span_blocks += hb.span;
     }
-    if (hb.mixed) ++c->mixed_blocks;
+    if (hb.mixed) ++c->cnt.mixed_blocks;
     if (hb.apx) {
         // phase 1 of the approximate path: panels, GEMM, SNP constants and the screens, all beside the previous block's tail.
         // The emission constants of phase 2 (table pointers, row base) are refreshed in submit_b.
@@ -698,8 +698,8 @@ int submit_generic(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
     S.do_lr = do_lr ? 1 : 0;
     S.idx_f = hb.D.idx_f;
     S.idx_t = hb.D.idx_t;
-    S.POS = c->POS.as<int32_t>();
-    S.g = c->g;
+    S.POS = c->meta.POS.as<int32_t>();
+    S.g = c->meta.g;
     S.sr_dist = p->sr_dist;
     int32_t *cnt_u = c->colcnt.as<int32_t>(), *cnt_l = cnt_u + hb.nt;
     int64_t *off_u = reinterpret_cast<int64_t *>(c->colcnt.as<char>() + (((size_t)hb.nt * 8 + 15) / 16 * 16)), *off_l = off_u + hb.nt;
@@ -723,15 +723,15 @@ int submit_generic(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
     hb.n_sr_blk = nu + nl;
     hb.n_lr_total = (hb.diag ? hb.nf * (hb.nf - 1) / 2 : hb.nf * hb.nt - std::min(hb.nf, hb.nt)) - hb.n_sr_blk;
     const int64_t sr_add = p->keep_sr ? hb.n_sr_blk : 0;
-    if (int rc = ensure_links_capacity(c, c->n_sr + sr_add, c->n_lr)) return rc;
+    if (int rc = ensure_links_capacity(c, c->links.n_sr + sr_add, c->links.n_lr)) return rc;
     if (sr_add > 0) {
         LDW_HIP(hipMemcpyAsync(off_u, ho.data(), (size_t)hb.nt * 16, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_gen_emit_sr, dim3(gridc), dim3(256), 0, c->stream, S, off_u, off_l, (int64_t)c->n_sr, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(),
-                           c->sr_mi.as<double>());
+        hipLaunchKernelGGL(k_gen_emit_sr, dim3(gridc), dim3(256), 0, c->stream, S, off_u, off_l, (int64_t)c->links.n_sr, c->links.sr_a.as<int32_t>(), c->links.sr_b.as<int32_t>(),
+                           c->links.sr_mi.as<double>());
         LDW_HIP(hipGetLastError());
         LDW_HIP(hipStreamSynchronize(c->stream));   // (ho is a host vector: the copy must be done before it goes away)
     }
-    c->n_sr += sr_add;
+    c->links.n_sr += sr_add;
     hb.spec_B = -1;
     if (do_lr) {
         const size_t cap = (size_t)hb.nf * hb.nt;
@@ -744,7 +744,7 @@ int submit_generic(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const Smal
     LDW_HIP(hipEventRecord(ev[2], c->stream));
     LDW_HIP(hipMemcpyAsync(c->pin_pick[s], sl.pick[s], sizeof(ldw::PickOut), hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipEventRecord(c->ev_pick[s], c->stream));
-    ++c->generic_blocks;
+    ++c->cnt.generic_blocks;
     return LDW_OK;
 }
 
@@ -753,13 +753,13 @@ int submit_b(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayou
     if (hb.generic) return submit_generic(c, hb, p, sl);
     const int s = hb.slot;
     LDW_HIP(hipStreamWaitEvent(c->stream, c->ev_up[s], 0));
-    if (c->engine == LDW_ENGINE_MFMA) LDW_HIP(hipStreamWaitEvent(c->stream, c->ev_gemm[s], 0));
+    if (c->knobs.engine == LDW_ENGINE_MFMA) LDW_HIP(hipStreamWaitEvent(c->stream, c->ev_gemm[s], 0));
     const bool do_lr = !p->sr_only;
     const int64_t sr_add = (p->keep_sr && !c->early_sr) ? hb.n_sr_blk : 0;   // (early_sr: assigned in submit_a)
-    if (int rc = ensure_links_capacity(c, c->n_sr + sr_add, c->n_lr)) return rc;
+    if (int rc = ensure_links_capacity(c, c->links.n_sr + sr_add, c->links.n_lr)) return rc;
     if (int rc = c->hist[s].reserve((size_t)NBINS * 8)) return rc;
     if (!hb.apx) LDW_HIP(hipMemsetAsync(c->hist[s].p, 0, (size_t)NBINS * 8, c->stream));   // (the approximate path zeroed both in its first phase: k_zero4)
-    if (int rc = make_emit_args(c, hb, p, sl, (hb.mixed || hb.apx) ? (do_lr ? hb.guess : -1) : (do_lr ? c->spec_B_next[hb.diag ? 1 : 0] : -1)))   // (the bit-plane histogram engine shares the epilogue: it speculates like the MFMA engine)
+    if (int rc = make_emit_args(c, hb, p, sl, (hb.mixed || hb.apx) ? (do_lr ? hb.guess : -1) : (do_lr ? c->spec.spec_B_next[hb.diag ? 1 : 0] : -1)))   // (the bit-plane histogram engine shares the epilogue: it speculates like the MFMA engine)
         return rc;
     if (!hb.apx) LDW_HIP(hipMemsetAsync(sl.pick[s], 0, sizeof(ldw::PickOut), c->stream));
     const hipEvent_t *ev = handles(&c->ev_pool[(size_t)hb.blk_no * EVB]);
@@ -768,10 +768,10 @@ int submit_b(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLayou
         hb.lo.sseg = hb.sseg;
         if (int rc = launch_block_apx(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, hb.E, ev, 2, nullptr, c->hist[s].as<unsigned long long>(), &hb.lo))
             return rc;
-    } else if (int rc = launch_block_mi(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, hb.E, ev, c->engine == LDW_ENGINE_MFMA ? 2 : 3,
+    } else if (int rc = launch_block_mi(c, hb.D, hb.nf, hb.nt, hb.RFpad, hb.RTpad, p->quirk_mode, hb.E, ev, c->knobs.engine == LDW_ENGINE_MFMA ? 2 : 3,
                                         &gx(c, s), nullptr, c->hist[s].as<unsigned long long>(), hb.mixed ? &hb.lo : nullptr))
         return rc;
-    c->n_sr += sr_add;
+    c->links.n_sr += sr_add;
     if (int rc = launch_pick(c, hb, p, sl, c->stream)) return rc;
     if (do_lr && hb.spec_B < 0)
         if (int rc = launch_gather(c, hb, hb.E, sl)) return rc;
@@ -789,29 +789,29 @@ void update_guess(ldw_ctx *c, bool diag, const ldw::PickOut *hp, bool missed) {
     // the margin follows what the thresholds of this kind have actually done: the spread of the last six of them plus two
     // buckets, between 4 and 10 (every bucket below the true one costs ~3000 more candidates on the C4 shape; a miss costs a
     // full non-speculative pass of the block, after which the history starts over)
-    int &hn = c->spec_hist_n[kind];
+    int &hn = c->spec.spec_hist_n[kind];
     if (missed) hn = 0;
-    c->spec_hist[kind][hn % 6] = hp->B_true;
+    c->spec.spec_hist[kind][hn % 6] = hp->B_true;
     ++hn;
     int margin = 10;
     if (hn >= 3) {
         int lo = hp->B_true, hi = hp->B_true;
         for (int k = 0; k < (hn < 6 ? hn : 6); ++k) {
-            lo = c->spec_hist[kind][k] < lo ? c->spec_hist[kind][k] : lo;
-            hi = c->spec_hist[kind][k] > hi ? c->spec_hist[kind][k] : hi;
+            lo = c->spec.spec_hist[kind][k] < lo ? c->spec.spec_hist[kind][k] : lo;
+            hi = c->spec.spec_hist[kind][k] > hi ? c->spec.spec_hist[kind][k] : hi;
         }
         // few kept rows per block (many blocks: C5 keeps ~800 per block) make the threshold itself noisier
         const bool small = hp->n * (1.0 - hp->prob) < 5000.0;
-        c->spec_small[kind] = small;
+        c->spec.spec_small[kind] = small;
         margin = hi - lo + (small ? 4 : 2);
         const int mmin = small ? 6 : 4;
         margin = margin < mmin ? mmin : (margin > 10 ? 10 : margin);
     }
-    c->spec_B_next[kind] = hp->B_true - margin > 0 ? hp->B_true - margin : 0;
-    c->spec_seen[kind] = true;
-    if (!c->spec_seen[other] && !c->spec_probed[other]) {   // (a probed guess of the other kind is better than one derived from this kind)
+    c->spec.spec_B_next[kind] = hp->B_true - margin > 0 ? hp->B_true - margin : 0;
+    c->spec.spec_seen[kind] = true;
+    if (!c->spec.spec_seen[other] && !c->spec.spec_probed[other]) {   // (a probed guess of the other kind is better than one derived from this kind)
         const int g = diag ? hp->B_true - 10 : hp->B_true - 16 - 2 * 10;
-        c->spec_B_next[other] = g > 0 ? g : 0;
+        c->spec.spec_B_next[other] = g > 0 ? g : 0;
     }
 }
 
@@ -861,9 +861,9 @@ int select_rows(ldw_ctx *c, const SelIn &S, bool do_lr, const SmallLayout &sl) {
     static const bool sel_fast_on = getenv("LDW_NO_FAST_SELECT") == nullptr;
     const long long n_words = (long long)((2 * sel_space + 31) / 32) + 1, n_chunks = (long long)((2 * sel_space + SEL_CHUNK_BITS - 1) / SEL_CHUNK_BITS) + 1;
     const long long n_super_ll = (n_chunks + SEL_SUPER - 1) / SEL_SUPER;
-    if (do_lr && m > 0 && sel_fast_on && c->select_mode == 0 && m <= SEL_MAX && n_super_ll <= SEL_MAX_SUPER) {
+    if (do_lr && m > 0 && sel_fast_on && c->knobs.select_mode == 0 && m <= SEL_MAX && n_super_ll <= SEL_MAX_SUPER) {
         // the common case: radix select + bitmap ranks, four small launches, no sort (k_sel_thresh)
-        if (int rc = ensure_links_capacity(c, c->n_sr, c->n_lr + m)) return rc;
+        if (int rc = ensure_links_capacity(c, c->links.n_sr, c->links.n_lr + m)) return rc;
         const int n_super = (int)n_super_ll;
         if (int rc = reserve_sel_scratch(c, (size_t)n_words * 4, (size_t)n_chunks * 4, (size_t)SEL_MAX_SUPER * 4)) return rc;
         uint32_t *bm = c->sel_bitmap.as<uint32_t>(), *cc = c->sel_chunks.as<uint32_t>(), *sc = c->sel_prefix.as<uint32_t>();
@@ -871,13 +871,13 @@ int select_rows(ldw_ctx *c, const SelIn &S, bool do_lr, const SmallLayout &sl) {
         hipLaunchKernelGGL(k_sel_thresh, dim3(1), dim3(1024), 0, c->stream, ck, S.pick);
         hipLaunchKernelGGL(k_sel_mark, dim3(gridm), dim3(256), 0, c->stream, ck, cv, S.pick, sel_space, bm, cc, sc);
         hipLaunchKernelGGL(k_sel_scatter, dim3(gridm), dim3(256), 0, c->stream, ck, cv, S.pick, sel_space, bm, cc, sc, n_super, S.idx_f, S.idx_t, (int)S.nf,
-                           sl.lr_count, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>());
+                           sl.lr_count, c->links.lr_a.as<int32_t>(), c->links.lr_b.as<int32_t>(), c->links.lr_mi.as<double>());
         hipLaunchKernelGGL(k_sel_clear, dim3(gridm), dim3(256), 0, c->stream, ck, cv, S.pick, sel_space, bm, cc, sc);
         LDW_HIP(hipGetLastError());
-        c->n_lr += m;  // upper bound; the exact value is *lr_count
+        c->links.n_lr += m;  // upper bound; the exact value is *lr_count
     } else if (do_lr && m > 0) {
         LDW_REQUIRE(m < 2147483647LL, LDW_ERR_SIZE, "too many quantile candidates (%lld)", (long long)m);
-        if (int rc = ensure_links_capacity(c, c->n_sr, c->n_lr + m)) return rc;
+        if (int rc = ensure_links_capacity(c, c->links.n_sr, c->links.n_lr + m)) return rc;
         if (int rc = c->cand_key2.reserve((size_t)m * 8)) return rc;
         if (int rc = c->cand_val2.reserve((size_t)m * 8)) return rc;
         size_t tmp_bytes = 0;
@@ -895,9 +895,9 @@ int select_rows(ldw_ctx *c, const SelIn &S, bool do_lr, const SmallLayout &sl) {
                                                    c->cand_val2.as<uint64_t>(), (int)m, 0, 64, c->stream));
         hipLaunchKernelGGL(k_lr_append, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream,
                            c->cand_key2.as<uint64_t>(), c->cand_val2.as<uint64_t>(), S.pick, S.idx_f, S.idx_t, (int)S.nf,
-                           sl.lr_count, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>());
+                           sl.lr_count, c->links.lr_a.as<int32_t>(), c->links.lr_b.as<int32_t>(), c->links.lr_mi.as<double>());
         LDW_HIP(hipGetLastError());
-        c->n_lr += m;  // upper bound; the exact value is *lr_count
+        c->links.n_lr += m;  // upper bound; the exact value is *lr_count
     } else if (do_lr) {
         hipLaunchKernelGGL(k_lr_thresh, dim3(1), dim3(64), 0, c->stream, ck, S.pick);
         LDW_HIP(hipGetLastError());
@@ -912,7 +912,7 @@ int select_rows(ldw_ctx *c, const SelIn &S, bool do_lr, const SmallLayout &sl) {
 int read_lr_count(ldw_ctx *c) {
     if (!c->lrc_recorded) return LDW_OK;
     LDW_HIP(hipEventSynchronize(c->ev_lrc));
-    memcpy(&c->n_lr, c->pin_lrc, 8);
+    memcpy(&c->links.n_lr, c->pin_lrc, 8);
     return LDW_OK;
 }
 int queue_lr_count(ldw_ctx *c, const SmallLayout &sl) {
@@ -974,7 +974,7 @@ int finish_block(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallL
         if (int rc = launch_gather(c, hb, E, sl)) return rc;
         LDW_HIP(hipMemcpyAsync(c->pin_pick[s], sl.pick[s], sizeof(ldw::PickOut), hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));
-        ++c->spec_misses;
+        ++c->cnt.spec_misses;
         note_overflow(c, hp->over);
         missed = true;
     }
@@ -1037,7 +1037,7 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
     }
     // the common case — every guess held, every candidate set fits the sort-free selection — takes ONE launch per stage for all segments
     static const bool sel_fast_on = getenv("LDW_NO_FAST_SELECT") == nullptr;
-    bool batched = sel_fast_on && c->select_mode == 0;
+    bool batched = sel_fast_on && c->knobs.select_mode == 0;
     long long m_max = 0, m_sum = 0;
     for (int k = 0; k < hb.span && batched; ++k) {
         const ldw::PickOut *hp = &picks[k];
@@ -1066,7 +1066,7 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
             S.n_super[k] = (int)((n_chunks + SEL_SUPER - 1) / SEL_SUPER);
         }
         if (int rc = reserve_sel_scratch(c, w_off * 4, c_off * 4, (size_t)LDW_SPAN_MAX * SEL_MAX_SUPER * 4)) return rc;
-        if (int rc = ensure_links_capacity(c, c->n_sr, c->n_lr + m_sum)) return rc;
+        if (int rc = ensure_links_capacity(c, c->links.n_sr, c->links.n_lr + m_sum)) return rc;
         for (int k = 0; k < hb.span; ++k) {
             const ldw::PickOut *hp = &picks[k];
             note_block(c, hb, k, hp, true, false);
@@ -1083,18 +1083,18 @@ int finish_span(ldw_ctx *c, HostBlock &hb, const ldw_mi_params *p, const SmallLa
         hipLaunchKernelGGL(k_sel_thresh_span, dim3(1, (unsigned)hb.span), dim3(1024), 0, c->stream, S);
         hipLaunchKernelGGL(k_sel_mark_span, dim3(gridm, (unsigned)hb.span), dim3(256), 0, c->stream, S);
         hipLaunchKernelGGL(k_sel_scatter_span, dim3(gridm, (unsigned)hb.span), dim3(256), 0, c->stream, S, hb.D.idx_f, (int)hb.nf,
-                           sl.lr_count, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>());
+                           sl.lr_count, c->links.lr_a.as<int32_t>(), c->links.lr_b.as<int32_t>(), c->links.lr_mi.as<double>());
         hipLaunchKernelGGL(k_sel_clear_span, dim3(gridm, (unsigned)hb.span), dim3(256), 0, c->stream, S);
         hipLaunchKernelGGL(k_span_done, dim3(1), dim3(64), 0, c->stream, S, DA, sl.lr_count, sl.stats_i + hb.blk_no * 3, sl.stats_d + hb.blk_no);
         LDW_HIP(hipGetLastError());
-        c->n_lr += m_sum;   // upper bound; the exact value is *lr_count
+        c->links.n_lr += m_sum;   // upper bound; the exact value is *lr_count
     }
     for (int k = 0; k < hb.span && !batched; ++k) {
         const ldw::PickOut *hp = &picks[k];
         const bool missed = hp->n > 0 && !hp->spec_ok;
         if (missed) {
-            ++c->spec_misses;
-            ++c->span_fallbacks;
+            ++c->cnt.spec_misses;
+            ++c->cnt.span_fallbacks;
             note_overflow(c, hp->over);
             // (the redo reads the exact row count of everything before it: the selections of the span's earlier segments are queued, not counted yet)
             if (int rc = queue_lr_count(c, sl)) return rc;
@@ -1177,22 +1177,22 @@ void probe_collect(ldw_ctx *c, const Probe &P) {
     const ldw::PickOut *hp = c->pin_pick[P.which].as<ldw::PickOut>();
     if (hp->n > 0 && hp->B_true < NBINS) {
         const int g = hp->B_true - PROBE_MARGIN;
-        c->spec_B_next[P.kind] = g > 0 ? g : 0;
-        c->spec_hist_n[P.kind] = 0;
-        c->spec_probed[P.kind] = true;
-        ++c->probe_blocks;
+        c->spec.spec_B_next[P.kind] = g > 0 ? g : 0;
+        c->spec.spec_hist_n[P.kind] = 0;
+        c->spec.spec_probed[P.kind] = true;
+        ++c->cnt.probe_blocks;
         static const bool trace_on = getenv("LDW_BLOCK_TRACE") != nullptr;
         if (trace_on) fprintf(stderr, "[ldw probe] kind %d: sample %lld x %lld, %lld long-range pairs, bucket %d -> guess %d\n", P.kind, (long long)P.hb.nf, (long long)P.hb.nt,
-                              (long long)P.hb.n_lr_total, hp->B_true, c->spec_B_next[P.kind]);
+                              (long long)P.hb.n_lr_total, hp->B_true, c->spec.spec_B_next[P.kind]);
     }
 }
 
 // whether the next block can be submitted before the current one is finished
 bool can_submit_early(ldw_ctx *c, const HostBlock &hb, const ldw_mi_params *p) {
-    if (!c->overlap) return false;
+    if (!c->knobs.overlap) return false;
     if (!p->sr_only && !speculation_pays(c, p)) return true;   // (plain blocks need no guess)
     // no bucket guess for this kind of block yet (the first blocks of a cold pass): the block in flight is about to provide one —
     // submitted now, this block would take the non-speculative path (full 5-limb GEMM, fp64 for every pair: ~4 ms more)
-    return !(c->engine == LDW_ENGINE_MFMA && !p->sr_only && c->screen && c->spec_B_next[hb.diag ? 1 : 0] < 0);
+    return !(c->knobs.engine == LDW_ENGINE_MFMA && !p->sr_only && c->knobs.screen && c->spec.spec_B_next[hb.diag ? 1 : 0] < 0);
 }
 

@@ -68,7 +68,7 @@ int ldw_deal_blocks(const int32_t *blocks, int64_t nblocks, int n_ranks, int32_t
 }
 
 int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int64_t nblocks, const ldw_mi_params *p, int32_t *owner_out, double *ms_out) {
-    if (ctx && n_ctx >= 1 && ctx[0]) ctx[0]->multi_owner.clear();   // whatever this call returns, the deal of an EARLIER call no longer describes ctx[0]
+    if (ctx && n_ctx >= 1 && ctx[0]) ctx[0]->links.drop_deal();   // whatever this call returns, the deal of an EARLIER call no longer describes ctx[0]
     LDW_REQUIRE(ctx && n_ctx >= 1 && n_ctx <= 64 && blocks && p && nblocks > 0, LDW_ERR_ARG, "ldw_mi_all_pairs_multi: bad argument");
     for (int k = 0; k < n_ctx; ++k) {
         LDW_REQUIRE(ctx[k], LDW_ERR_ARG, "ldw_mi_all_pairs_multi: context %d is null", k);
@@ -76,8 +76,8 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
         LDW_REQUIRE(ctx[k]->L == ctx[0]->L && ctx[k]->N == ctx[0]->N && ctx[k]->L > 0, LDW_ERR_STATE,
                     "ldw_mi_all_pairs_multi: context %d holds a %lld x %lld alignment, context 0 %lld x %lld (every context needs the same alignment, weights and SNP meta data)",
                     k, (long long)ctx[k]->L, (long long)ctx[k]->N, (long long)ctx[0]->L, (long long)ctx[0]->N);
-        LDW_REQUIRE(ctx[k]->have_weights && ctx[k]->have_meta, LDW_ERR_STATE, "ldw_mi_all_pairs_multi: context %d has no weights or SNP meta data", k);
-        LDW_REQUIRE(ctx[k]->neff == ctx[0]->neff && ctx[k]->g == ctx[0]->g && ctx[k]->h_POS == ctx[0]->h_POS, LDW_ERR_STATE,
+        LDW_REQUIRE(ctx[k]->wts.have_weights && ctx[k]->meta.have_meta, LDW_ERR_STATE, "ldw_mi_all_pairs_multi: context %d has no weights or SNP meta data", k);
+        LDW_REQUIRE(ctx[k]->wts.neff == ctx[0]->wts.neff && ctx[k]->meta.g == ctx[0]->meta.g && ctx[k]->meta.h_POS == ctx[0]->meta.h_POS, LDW_ERR_STATE,
                     "ldw_mi_all_pairs_multi: context %d differs from context 0 in its weights, genome length or positions", k);
     }
     const double t_0 = now_ms();
@@ -132,7 +132,7 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
         ms_out[1] = 0;           // the gather (below)
         for (int k = 0; k < n_ctx && k < 8; ++k) ms_out[2 + k] = W[(size_t)k].ms;
     }
-    c0->multi_owner.clear();
+    c0->links.drop_deal();
     if (n_ctx == 1) return LDW_OK;
     const bool rows_stay = (p->flags & LDW_MI_SR_ROWS_STAY) != 0 && p->keep_sr;   // r05: only the long-range table is assembled; (7c) runs the model over the contexts
     // ---- 4) the gather: rows of block b lie at the running offset of its owner's table; their place in ctx[0]'s assembled table is the
@@ -140,9 +140,9 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
     std::vector<ldw::BlockStat> stats((size_t)nblocks);
     for (int k = 0; k < n_ctx; ++k) {
         const Worker &w = W[(size_t)k];
-        LDW_REQUIRE(w.ids.empty() || ctx[k]->stats.size() == w.ids.size(), LDW_ERR_STATE, "ldw_mi_all_pairs_multi: context %d reports %lld blocks, ran %lld", k,
-                    (long long)ctx[k]->stats.size(), (long long)w.ids.size());
-        for (size_t i = 0; i < w.ids.size(); ++i) stats[(size_t)w.ids[i]] = ctx[k]->stats[i];
+        LDW_REQUIRE(w.ids.empty() || ctx[k]->links.stats.size() == w.ids.size(), LDW_ERR_STATE, "ldw_mi_all_pairs_multi: context %d reports %lld blocks, ran %lld", k,
+                    (long long)ctx[k]->links.stats.size(), (long long)w.ids.size());
+        for (size_t i = 0; i < w.ids.size(); ++i) stats[(size_t)w.ids[i]] = ctx[k]->links.stats[i];
     }
     int64_t tot[2] = {0, 0};
     for (int64_t b = 0; b < nblocks; ++b) {
@@ -156,8 +156,8 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
             l += stats[(size_t)id].n_lr_kept;
         }
         if (W[(size_t)k].ids.empty()) continue;
-        LDW_REQUIRE(s == ctx[k]->n_sr && l == ctx[k]->n_lr, LDW_ERR_STATE, "ldw_mi_all_pairs_multi: context %d holds %lld / %lld rows, its blocks report %lld / %lld", k,
-                    (long long)ctx[k]->n_sr, (long long)ctx[k]->n_lr, (long long)s, (long long)l);
+        LDW_REQUIRE(s == ctx[k]->links.n_sr && l == ctx[k]->links.n_lr, LDW_ERR_STATE, "ldw_mi_all_pairs_multi: context %d holds %lld / %lld rows, its blocks report %lld / %lld", k,
+                    (long long)ctx[k]->links.n_sr, (long long)ctx[k]->links.n_lr, (long long)s, (long long)l);
     }
     // peer access towards GPU 0 (a context on another device writes into ctx[0]'s memory); already-enabled is fine, unavailable falls back to
     // the runtime's staged copy
@@ -175,7 +175,7 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
     // xGMI — what the RCCL gather of dist.py does.  The DEFAULT since the enumerator builds its intervals on the device (r05: 0.8 ms for C4's
     // 9e7 rows; its host loop took 12-19 ms, which made this the option, LDW_MULTI_SR_MI_ONLY, earlier in the round); LDW_MULTI_SR_FULL_ROWS=1 sends all
     // three columns (also what unsorted positions, a fractional genome length and SR-only passes do).
-    const bool sr_mi_only = !rows_stay && c0->pos_sorted && c0->g == std::floor(c0->g) && !p->sr_only && p->keep_sr && getenv("LDW_MULTI_SR_FULL_ROWS") == nullptr;
+    const bool sr_mi_only = !rows_stay && c0->meta.pos_sorted && c0->meta.g == std::floor(c0->meta.g) && !p->sr_only && p->keep_sr && getenv("LDW_MULTI_SR_FULL_ROWS") == nullptr;
     ldw::DevBuf nA[2], nB[2], nM[2];
     for (int w = rows_stay ? 1 : 0; w < 2; ++w) {
         const size_t n = (size_t)std::max<int64_t>(tot[w], 1);
@@ -203,7 +203,7 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
         }
         for (int w = rows_stay ? 1 : 0; w < 2 && he == hipSuccess; ++w) {
             const int64_t so = src_off[(size_t)k * 2 + w], d = dst_off[w], n = rows[w];
-            const ldw::DevBuf &sa = w == 0 ? ck->sr_a : ck->lr_a, &sb = w == 0 ? ck->sr_b : ck->lr_b, &sm = w == 0 ? ck->sr_mi : ck->lr_mi;
+            const ldw::DevBuf &sa = w == 0 ? ck->links.sr_a : ck->links.lr_a, &sb = w == 0 ? ck->links.sr_b : ck->links.lr_b, &sm = w == 0 ? ck->links.sr_mi : ck->links.lr_mi;
             if (!(w == 0 && sr_mi_only)) {
                 he = copy_rows(nA[w].as<int32_t>() + d, c0, sa.as<int32_t>() + so, ck, (size_t)n * 4);
                 if (he == hipSuccess) he = copy_rows(nB[w].as<int32_t>() + d, c0, sb.as<int32_t>() + so, ck, (size_t)n * 4);
@@ -233,19 +233,19 @@ int ldw_mi_all_pairs_multi(ldw_ctx **ctx, int n_ctx, const int32_t *blocks, int6
     if (rc != LDW_OK) return rc;
     // ---- 5) ctx[0] adopts the assembled tables (its own share's buffers are released) and the per-block records of ALL blocks
     if (!rows_stay) {
-        std::swap(c0->sr_a, nA[0]);
-        std::swap(c0->sr_b, nB[0]);
-        std::swap(c0->sr_mi, nM[0]);
+        std::swap(c0->links.sr_a, nA[0]);
+        std::swap(c0->links.sr_b, nB[0]);
+        std::swap(c0->links.sr_mi, nM[0]);
     }
-    std::swap(c0->lr_a, nA[1]);
-    std::swap(c0->lr_b, nB[1]);
-    std::swap(c0->lr_mi, nM[1]);
+    std::swap(c0->links.lr_a, nA[1]);
+    std::swap(c0->links.lr_b, nB[1]);
+    std::swap(c0->links.lr_mi, nM[1]);
     for (ldw::DevBuf *b : {&nA[0], &nB[0], &nM[0], &nA[1], &nB[1], &nM[1]}) b->release();   // (here, inside ms_out[1], not at the return)
-    if (!rows_stay) c0->n_sr = tot[0];   // (rows_stay: ctx[0] keeps the short-range rows of its own share, like every other context)
-    c0->n_lr = tot[1];
-    c0->kept.invalidate();
-    c0->stats = stats;                    // the records of ALL blocks, in the caller's order (ldw_block_stats)
-    if (rows_stay) c0->multi_owner = owner;
+    if (!rows_stay) c0->links.n_sr = tot[0];   // (rows_stay: ctx[0] keeps the short-range rows of its own share, like every other context)
+    c0->links.n_lr = tot[1];
+    c0->links.replaced(c0->kept);
+    c0->links.stats = stats;                    // the records of ALL blocks, in the caller's order (ldw_block_stats)
+    if (rows_stay) c0->links.multi_owner = owner;
     if (ms_out) ms_out[1] = now_ms() - t_1;
     return LDW_OK;
 }
@@ -341,22 +341,22 @@ int shares_of(ldw_ctx **ctx, int n_ctx, const char *who, bool &spread, std::vect
     LDW_REQUIRE(ctx && n_ctx >= 1 && n_ctx <= 64 && ctx[0], LDW_ERR_ARG, "%s: bad argument", who);
     for (int k = 0; k < n_ctx; ++k) LDW_REQUIRE(ctx[k], LDW_ERR_ARG, "%s: context %d is null", who, k);
     const ldw_ctx *c0 = ctx[0];
-    spread = n_ctx > 1 && !c0->multi_owner.empty();
+    spread = n_ctx > 1 && !c0->links.multi_owner.empty();
     mine.assign((size_t)n_ctx, {});
     rows.assign((size_t)n_ctx, {});
     if (!spread) return LDW_OK;
-    LDW_REQUIRE(c0->multi_owner.size() == c0->stats.size(), LDW_ERR_STATE, "%s: context 0 is not the context 0 of the last ldw_mi_all_pairs_multi call", who);
-    for (size_t b = 0; b < c0->multi_owner.size(); ++b) {
-        const int k = c0->multi_owner[b];
+    LDW_REQUIRE(c0->links.multi_owner.size() == c0->links.stats.size(), LDW_ERR_STATE, "%s: context 0 is not the context 0 of the last ldw_mi_all_pairs_multi call", who);
+    for (size_t b = 0; b < c0->links.multi_owner.size(); ++b) {
+        const int k = c0->links.multi_owner[b];
         LDW_REQUIRE(k >= 0 && k < n_ctx, LDW_ERR_STATE, "%s: block %lld belongs to context %d, %d contexts given", who, (long long)b, k, n_ctx);
         mine[(size_t)k].push_back((int64_t)b);
-        rows[(size_t)k].push_back(c0->stats[b].n_sr);
+        rows[(size_t)k].push_back(c0->links.stats[b].n_sr);
     }
     for (int k = 0; k < n_ctx; ++k) {
         int64_t s = 0;
         for (int64_t r : rows[(size_t)k]) s += r;
-        LDW_REQUIRE(s == ctx[k]->n_sr, LDW_ERR_STATE, "%s: context %d holds %lld short-range rows, its blocks of the last ldw_mi_all_pairs_multi call %lld", who, k,
-                    (long long)ctx[k]->n_sr, (long long)s);
+        LDW_REQUIRE(s == ctx[k]->links.n_sr, LDW_ERR_STATE, "%s: context %d holds %lld short-range rows, its blocks of the last ldw_mi_all_pairs_multi call %lld", who, k,
+                    (long long)ctx[k]->links.n_sr, (long long)s);
     }
     return LDW_OK;
 }
@@ -450,11 +450,11 @@ int ldw_sr_excess_stats_multi(ldw_ctx **ctx, int n_ctx, int nclust, int32_t S, c
         ldw_ctx *c = ctx[0];
         int64_t s = 0;
         std::vector<int64_t> r;
-        for (const auto &st : c->stats) {
+        for (const auto &st : c->links.stats) {
             r.push_back(st.n_sr);
             s += st.n_sr;
         }
-        if (r.empty() || s != c->n_sr) return ldw_sr_excess_stats(c, nclust, S, mean_dist, stats_out);
+        if (r.empty() || s != c->links.n_sr) return ldw_sr_excess_stats(c, nclust, S, mean_dist, stats_out);
         std::vector<double> part(r.size() * per);
         if (int rc = ldw_sr_excess_stats_blocks(c, nclust, S, mean_dist, (int64_t)r.size(), r.data(), part.data())) return rc;
         for (size_t t = 0; t < per; ++t) stats_out[t] = 0.0;
@@ -462,7 +462,7 @@ int ldw_sr_excess_stats_multi(ldw_ctx **ctx, int n_ctx, int nclust, int32_t S, c
             for (size_t t = 0; t < per; ++t) stats_out[t] += part[b * per + t];
         return LDW_OK;
     }
-    const size_t nb = ctx[0]->stats.size();
+    const size_t nb = ctx[0]->links.stats.size();
     std::vector<std::vector<double>> part((size_t)n_ctx);
     if (int rc = for_each_ctx(ctx, n_ctx, "ldw_sr_excess_stats_multi", [&](int k) {
             part[(size_t)k].assign(std::max<size_t>(rows[(size_t)k].size(), 1) * per, 0.0);
@@ -518,9 +518,9 @@ int ldw_sr_pvalues_multi(ldw_ctx **ctx, int n_ctx, int nclust, int32_t S, const 
         }))
         return rc;
     // 3) rows of a context's table -> rows of the job's table (make_blocks order); all kept links in that order
-    const size_t nb = ctx[0]->stats.size();
+    const size_t nb = ctx[0]->links.stats.size();
     std::vector<int64_t> goff(nb + 1, 0);
-    for (size_t b = 0; b < nb; ++b) goff[b + 1] = goff[b] + ctx[0]->stats[b].n_sr;
+    for (size_t b = 0; b < nb; ++b) goff[b + 1] = goff[b] + ctx[0]->links.stats[b].n_sr;
     int64_t n_red = 0, n_pool = 0;
     for (int k = 0; k < n_ctx; ++k) {
         n_red += nr[(size_t)k];
@@ -567,7 +567,7 @@ int ldw_sr_pvalues_multi(ldw_ctx **ctx, int n_ctx, int nclust, int32_t S, const 
     // 4) context 0 adopts them: ldw_sr_reduced_fetch / ldw_sr_pool_fetch / ldw_aracne_device follow as after ldw_sr_pvalues
     LDW_HIP(hipSetDevice(ctx[0]->device));
     if (int rc = ldw::reduced_import_full(ctx[0], n_red, A.data(), B.data(), M.data(), META.data(), SRP.data(), n_pool, PA.data(), PB.data(), PM.data())) return rc;
-    ctx[0]->multi_owner.clear();   // (its short-range table is the kept set now: the shares are gone)
+    ctx[0]->links.drop_deal();   // (its short-range table is the kept set now: the shares are gone)
     *n_red_out = n_red;
     *n_pool_out = n_pool;
     if (min_mi_out) *min_mi_out = gmin;

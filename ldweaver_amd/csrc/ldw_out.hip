@@ -187,7 +187,7 @@ int ldw_write_alignment(ldw_ctx *c, const char *path, int append, int format, co
     // the file (truncated or appended to) before any device work: an unwritable path is an argument error
     const int fd = open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0666);
     LDW_REQUIRE(fd >= 0, LDW_ERR_ARG, "cannot open %s: %s", path, strerror(errno));
-    const bool timing = getenv("LDW_HOST_TIMING") != nullptr;
+    const bool timing = getenv("LDW_HOST_TIMING") != nullptr;   // (read per call, unlike ldw::host_timing(): a caller may switch it on for one file)
     int rc = LDW_OK;
     OutState *o = out_state(c);
     do {

@@ -14,13 +14,13 @@ namespace ldw {
 
 void set_error(const char *fmt, ...);
 
-// process-wide (ldw_api.hip): device blocks held by DevBufs, pinned host blocks, events, streams the library created
+// process-wide (ldw_alloc.cpp): device blocks held by DevBufs, pinned host blocks, events, streams the library created
 struct OwnCounts {
     std::atomic<int64_t> dev{0}, pinned{0}, events{0}, streams{0};
 };
 extern OwnCounts g_own;
 
-// grow-only device buffer; the blocks come from and go back to the pool of ldw_api.hip
+// grow-only device buffer; the blocks come from and go back to the pool of ldw_alloc.cpp
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;

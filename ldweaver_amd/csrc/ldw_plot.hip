@@ -481,8 +481,8 @@ int ldw_plot_links(ldw_ctx *c, int which, int use_aracne, const ldw_plot_opts *o
                 opts->kind, which);
     LDW_REQUIRE(png_path || rgb_out, LDW_ERR_ARG, "ldw_plot_links: neither a path nor a canvas to write to");
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->POS.p != nullptr, LDW_ERR_STATE, "ldw_plot_links: no SNP meta data (ldw_set_snp_meta)");
-    LDW_REQUIRE(c->g > 0, LDW_ERR_STATE, "ldw_plot_links: the genome length is not known (ldw_set_positions with g = 0): len cannot be taken from the positions");
+    LDW_REQUIRE(c->meta.POS.p != nullptr, LDW_ERR_STATE, "ldw_plot_links: no SNP meta data (ldw_set_snp_meta)");
+    LDW_REQUIRE(c->meta.g > 0, LDW_ERR_STATE, "ldw_plot_links: the genome length is not known (ldw_set_positions with g = 0): len cannot be taken from the positions");
     LDW_REQUIRE((which == 1) == c->kept.from_lr, LDW_ERR_STATE, "ldw_plot_links: the kept links are those of the %s table", c->kept.from_lr ? "long-range" : "short-range");
     const int64_t n = c->kept.n_red;
     LDW_REQUIRE(!use_aracne || n == 0 || (c->kept.ar_valid && c->kept.ar_flags.cap >= (size_t)n), LDW_ERR_STATE,
@@ -490,11 +490,11 @@ int ldw_plot_links(ldw_ctx *c, int which, int use_aracne, const ldw_plot_opts *o
     CtxSrc s;
     memset(&s, 0, sizeof(s));
     s.row = c->kept.row.as<int64_t>();
-    s.a = (which ? c->lr_a : c->sr_a).as<int32_t>();
-    s.b = (which ? c->lr_b : c->sr_b).as<int32_t>();
-    s.mi = (which ? c->lr_mi : c->sr_mi).as<double>();
-    s.POS = c->POS.as<int32_t>();
-    s.g = c->g;
+    s.a = (which ? c->links.lr_a : c->links.sr_a).as<int32_t>();
+    s.b = (which ? c->links.lr_b : c->links.sr_b).as<int32_t>();
+    s.mi = (which ? c->links.lr_mi : c->links.sr_mi).as<double>();
+    s.POS = c->meta.POS.as<int32_t>();
+    s.g = c->meta.g;
     s.srp = which ? nullptr : c->kept.srp.as<double>();
     s.meta = which ? nullptr : c->kept.meta.as<uint32_t>();
     s.flags = use_aracne && n > 0 ? c->kept.ar_flags.as<uint8_t>() : nullptr;

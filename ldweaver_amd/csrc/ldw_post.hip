@@ -169,21 +169,21 @@ __global__ __launch_bounds__(256) void k_ldmap_rescale(double *__restrict__ red,
 // the first SNP of a position is the first of its run) and a running rank over the distinct positions (the graph nodes of the LD map and ARACNE, which
 // like the reference work on positions: SNPs sharing one are one node).  What the order of POS makes trivial is not built.
 int pos_order(ldw_ctx *c) {
-    auto &po = c->pos_ord;
-    if (c->pos_strict || po.n_slots > 0) return LDW_OK;
+    auto &po = c->meta.pos_ord;
+    if (c->meta.pos_strict || po.n_slots > 0) return LDW_OK;
     const size_t L = (size_t)c->L;
     std::vector<int32_t> ord(L), srt(L), slot(L);
     for (size_t i = 0; i < L; ++i) ord[i] = (int32_t)i;
-    std::stable_sort(ord.begin(), ord.end(), [&](int32_t u, int32_t v) { return c->h_POS[(size_t)u] < c->h_POS[(size_t)v]; });
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t u, int32_t v) { return c->meta.h_POS[(size_t)u] < c->meta.h_POS[(size_t)v]; });
     int32_t k = -1;
     for (size_t i = 0; i < L; ++i) {
-        srt[i] = c->h_POS[(size_t)ord[i]];
+        srt[i] = c->meta.h_POS[(size_t)ord[i]];
         if (i == 0 || srt[i] != srt[i - 1]) ++k;
         slot[(size_t)ord[i]] = k;
     }
     if (int rc = po.slot.reserve(L * 4)) return rc;
     LDW_HIP(hipMemcpyAsync(po.slot.p, slot.data(), L * 4, hipMemcpyHostToDevice, c->stream));
-    if (!c->pos_sorted) {
+    if (!c->meta.pos_sorted) {
         if (int rc = po.srt.reserve(L * 4)) return rc;
         if (int rc = po.order.reserve(L * 4)) return rc;
         LDW_HIP(hipMemcpyAsync(po.srt.p, srt.data(), L * 4, hipMemcpyHostToDevice, c->stream));
@@ -196,8 +196,8 @@ int pos_order(ldw_ctx *c) {
 
 int pos_slots(ldw_ctx *c, const int32_t **slot, int64_t *n_nodes) {
     if (int rc = pos_order(c)) return rc;
-    *slot = c->pos_strict ? nullptr : c->pos_ord.slot.as<int32_t>();
-    *n_nodes = c->pos_strict ? c->L : c->pos_ord.n_slots;
+    *slot = c->meta.pos_strict ? nullptr : c->meta.pos_ord.slot.as<int32_t>();
+    *n_nodes = c->meta.pos_strict ? c->L : c->meta.pos_ord.n_slots;
     return LDW_OK;
 }
 
@@ -215,8 +215,8 @@ int sort_positions(ldw_ctx *c, const int32_t *POS, int64_t L, unsigned end_bit, 
 
 static int links_ready(ldw_ctx *c, const char *who) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->have_meta, LDW_ERR_STATE, "%s: ldw_set_snp_meta has not been called", who);
-    LDW_REQUIRE(c->blk_capacity == 0, LDW_ERR_STATE, "%s: a link pass is still open (ldw_links_end)", who);
+    LDW_REQUIRE(c->meta.have_meta, LDW_ERR_STATE, "%s: ldw_set_snp_meta has not been called", who);
+    LDW_REQUIRE(c->links.blk_capacity == 0, LDW_ERR_STATE, "%s: a link pass is still open (ldw_links_end)", who);
     return LDW_OK;
 }
 
@@ -253,7 +253,7 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     LDW_REQUIRE(n_sr_rows >= 0 && (n_sr_rows == 0 || (sr_a && sr_b && sr_mi)), LDW_ERR_ARG, "ldw_lr_tukey: bad short-range table");
     // the short-range part of the ARACNE pool is what sr_links.tsv holds — the REDUCED set perform_MI_computation returned
     // (srp_max > srp_cutoff, R/computePairwiseMI.R:122,140), not the engine's raw short-range table: the caller hands it in
-    const int64_t n = c->n_lr, ns = n_sr_rows;
+    const int64_t n = c->links.n_lr, ns = n_sr_rows;
     for (int64_t i = 0; i < ns; ++i)   // host arrays: an index outside the alignment (an NA from R's match() is INT_MIN) must not reach the device
         LDW_REQUIRE(sr_a[i] >= 0 && sr_a[i] < c->L && sr_b[i] >= 0 && sr_b[i] < c->L, LDW_ERR_ARG,
                     "ldw_lr_tukey: short-range row %lld has SNP indices (%d, %d) outside 0..%lld (a position that is not in POS?)", (long long)i, sr_a[i], sr_b[i],
@@ -275,7 +275,7 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     // ---- sorted MI keys -> order statistics ----
     if (int rc = c->kept.ar_key.reserve((size_t)n * 8)) return rc;
     if (int rc = c->kept.ar_key2.reserve((size_t)n * 8)) return rc;
-    LDW_LAUNCH(k_mi_keys, grid_of(n), dim3(256), 0, c->stream, c->lr_mi.as<double>(), n, c->kept.ar_key.as<uint64_t>());
+    LDW_LAUNCH(k_mi_keys, grid_of(n), dim3(256), 0, c->stream, c->links.lr_mi.as<double>(), n, c->kept.ar_key.as<uint64_t>());
     size_t tb = 0;
     LDW_HIP(prim_sort_keys_bytes<uint64_t>((size_t)n, 0, 64, c->stream, &tb));
     if (int rc = c->scratch.reserve(tb)) return rc;
@@ -302,7 +302,7 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     if (int rc = c->kept.ar_off.reserve((size_t)(nseg_l + nseg_s + 2) * 8 * 2)) return rc;
     int64_t *cnt_l = c->kept.ar_off.as<int64_t>(), *off_l = cnt_l + nseg_l + 1, *cnt_s = off_l + nseg_l + 1, *off_s = cnt_s + nseg_s + 1;
     auto count_pass = [&](double t, int64_t &n_red, int64_t &n_srp) -> int {
-        LDW_LAUNCH(k_count_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->lr_mi.as<double>(), n, t, cnt_l);
+        LDW_LAUNCH(k_count_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->links.lr_mi.as<double>(), n, t, cnt_l);
         if (ns > 0) LDW_LAUNCH(k_count_gt, dim3((unsigned)nseg_s), dim3(256), 0, c->stream, d_smi, ns, t, cnt_s);
         size_t sb = 0;
         LDW_HIP(prim_scan_bytes<int64_t>((size_t)nseg_l, c->stream, &sb));
@@ -339,8 +339,8 @@ int ldw_lr_tukey(ldw_ctx *c, int64_t min_links, const int32_t *sr_a, const int32
     const int64_t n_pool = n_red + n_srp;
     if (int rc = c->kept.row.reserve((size_t)std::max<int64_t>(n_red, 1) * 8)) return rc;
     if (int rc = c->kept.reserve_pool((size_t)std::max<int64_t>(n_pool, 1))) return rc;
-    LDW_LAUNCH(k_select_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(),
-                       c->lr_mi.as<double>(), n, tmin, off_l, (int64_t)0, c->kept.row.as<int64_t>(), c->kept.pool_a.as<int32_t>(),
+    LDW_LAUNCH(k_select_gt, dim3((unsigned)nseg_l), dim3(256), 0, c->stream, c->links.lr_a.as<int32_t>(), c->links.lr_b.as<int32_t>(),
+                       c->links.lr_mi.as<double>(), n, tmin, off_l, (int64_t)0, c->kept.row.as<int64_t>(), c->kept.pool_a.as<int32_t>(),
                        c->kept.pool_b.as<int32_t>(), c->kept.pool_mi.as<double>());
     if (ns > 0)
         LDW_LAUNCH(k_select_gt, dim3((unsigned)nseg_s), dim3(256), 0, c->stream, d_sa, d_sb,
@@ -368,7 +368,7 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
     const int windowed = (from != 0 || to != 0) ? 1 : 0;
     LDW_REQUIRE(!windowed || (to > from && from >= 0), LDW_ERR_ARG, "ldw_ldmap: <to> must be greater than <from> and both positive");
     LDW_REQUIRE(reducer >= 0, LDW_ERR_ARG, "ldw_ldmap: reducer must be >= 0 (0 = default)");
-    const int64_t nl = c->n_lr, ns = c->n_sr;
+    const int64_t nl = c->links.n_lr, ns = c->links.n_sr;
     LDW_REQUIRE(nl + ns > 0, LDW_ERR_STATE, "ldw_ldmap: no links");
     // r05: the rank of a position in pos_vec is its rank among the sorted distinct positions.  With POS strictly ascending (what the reference's parser
     // emits) that is the SNP order; otherwise (any order, repeated positions) through a slot per SNP (ldw::pos_slots).
@@ -379,9 +379,9 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
     if (int rc = c->srm.cnt.reserve((size_t)(n_nodes + 1) * 4 * 2)) return rc;
     int32_t *used = c->srm.cnt.as<int32_t>(), *rank = used + n_nodes + 1;
     LDW_HIP(hipMemsetAsync(used, 0, (size_t)(n_nodes + 1) * 4, c->stream));
-    const int32_t *POS = c->POS.as<int32_t>();
-    if (nl > 0) LDW_LAUNCH(k_mark_used, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), nl, POS, from, to, windowed, used, d_slot);
-    if (ns > 0) LDW_LAUNCH(k_mark_used, grid_of(ns), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), ns, POS, from, to, windowed, used, d_slot);
+    const int32_t *POS = c->meta.POS.as<int32_t>();
+    if (nl > 0) LDW_LAUNCH(k_mark_used, grid_of(nl), dim3(256), 0, c->stream, c->links.lr_a.as<int32_t>(), c->links.lr_b.as<int32_t>(), nl, POS, from, to, windowed, used, d_slot);
+    if (ns > 0) LDW_LAUNCH(k_mark_used, grid_of(ns), dim3(256), 0, c->stream, c->links.sr_a.as<int32_t>(), c->links.sr_b.as<int32_t>(), ns, POS, from, to, windowed, used, d_slot);
     size_t sb = 0;
     LDW_HIP(prim_scan_bytes<int32_t>((size_t)n_nodes + 1, c->stream, &sb));
     if (int rc = c->scratch.reserve(sb)) return rc;
@@ -408,8 +408,8 @@ int ldmap_device(ldw_ctx *c, int32_t reducer, int32_t from, int32_t to, int64_t 
     double *red = c->srm.q.as<double>(), *htm = red + 3 * nb, *mm = htm + nb;
     unsigned long long *acc_lo = reinterpret_cast<unsigned long long *>(red + nb), *acc_hi = acc_lo + nb;
     LDW_HIP(hipMemsetAsync(red, 0, (size_t)nb * 24, c->stream));
-    if (nl > 0) LDW_LAUNCH(k_ldmap_add, grid_of(nl), dim3(256), 0, c->stream, c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>(), nl, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
-    if (ns > 0) LDW_LAUNCH(k_ldmap_add, grid_of(ns), dim3(256), 0, c->stream, c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), ns, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
+    if (nl > 0) LDW_LAUNCH(k_ldmap_add, grid_of(nl), dim3(256), 0, c->stream, c->links.lr_a.as<int32_t>(), c->links.lr_b.as<int32_t>(), c->links.lr_mi.as<double>(), nl, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
+    if (ns > 0) LDW_LAUNCH(k_ldmap_add, grid_of(ns), dim3(256), 0, c->stream, c->links.sr_a.as<int32_t>(), c->links.sr_b.as<int32_t>(), c->links.sr_mi.as<double>(), ns, POS, from, to, windowed, used, rank, r, B, red, acc_lo, acc_hi, d_slot);
     LDW_LAUNCH(k_ldmap_log, dim3(rgrid), dim3(256), 0, c->stream, red, acc_lo, acc_hi, (int)B, 1.0 / ((double)r * (double)r), htm, mm);
     std::vector<double> hmm((size_t)rgrid * 2);
     LDW_HIP(hipMemcpyAsync(hmm.data(), mm, hmm.size() * 8, hipMemcpyDeviceToHost, c->stream));

@@ -102,13 +102,13 @@ __device__ __forceinline__ double member_excess(const RowTag &t, int s, double m
 
 // the context's short-range table on the geometry of the last ldw_sr_len_quantiles call
 static SrRowsView sr_rows(const ldw_ctx *c) {
-    return SrRowsView{c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), c->POS.as<int32_t>(), c->paint.as<int32_t>(), c->n_sr, c->g, c->srm.sr_dist};
+    return SrRowsView{c->links.sr_a.as<int32_t>(), c->links.sr_b.as<int32_t>(), c->links.sr_mi.as<double>(), c->meta.POS.as<int32_t>(), c->meta.paint.as<int32_t>(), c->links.n_sr, c->meta.g, c->srm.sr_dist};
 }
 
 static int sr_ready(ldw_ctx *c, const char *who) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(c->have_meta, LDW_ERR_STATE, "%s: ldw_set_snp_meta has not been called", who);
-    LDW_REQUIRE(!c->pos_only, LDW_ERR_STATE, "%s: the context holds positions only (ldw_set_positions): the short-range model needs the paint of ldw_set_snp_meta", who);
+    LDW_REQUIRE(c->meta.have_meta, LDW_ERR_STATE, "%s: ldw_set_snp_meta has not been called", who);
+    LDW_REQUIRE(!c->meta.pos_only, LDW_ERR_STATE, "%s: the context holds positions only (ldw_set_positions): the short-range model needs the paint of ldw_set_snp_meta", who);
     return LDW_OK;
 }
 
@@ -543,13 +543,6 @@ static void split_q(const std::vector<double> &q, size_t cells, double *q_lo_out
     }
 }
 
-// host wall time of the steps of ldw_sr_len_quantiles (LDW_HOST_TIMING)
-struct HostClock {
-    using Point = std::chrono::steady_clock::time_point;
-    static Point now() { return std::chrono::steady_clock::now(); }
-    static double ms(Point a, Point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
-};
-
 // ------------------------------------------------------------------------------------------------
 // positive excesses over the fitted decay: sufficient statistics of the beta likelihood
 // ------------------------------------------------------------------------------------------------
@@ -852,7 +845,7 @@ __global__ void k_red_gather(const int64_t *__restrict__ row, int64_t n, const i
 // ARACNE pool of the context's short-range table: rows with a positive excess in some cluster and MI key >= min_key (R/computePairwiseMI.R:489-490);
 // needs the fitted decay on the device (upload_md) and the geometry of the last ldw_sr_len_quantiles call.  Sets c->kept.n_pool.
 static int build_pool(ldw_ctx *c, unsigned long long min_key) {
-    const int64_t n = c->n_sr;
+    const int64_t n = c->links.n_sr;
     KeptLinks &K = c->kept;
     K.n_pool = 0;
     if (n == 0) return LDW_OK;
@@ -1007,14 +1000,14 @@ int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, in
     LDW_REQUIRE(prob >= 0 && prob <= 1, LDW_ERR_ARG, "ldw_sr_len_quantiles: prob outside [0,1]");
     LDW_REQUIRE(S == (int32_t)std::ceil(sr_dist) - 1, LDW_ERR_ARG, "ldw_sr_len_quantiles: S must be ceil(sr_dist)-1 = %d",
                 (int)std::ceil(sr_dist) - 1);
-    LDW_REQUIRE(c->g == std::floor(c->g), LDW_ERR_ARG, "ldw_sr_len_quantiles: the genome length must be an integer");
+    LDW_REQUIRE(c->meta.g == std::floor(c->meta.g), LDW_ERR_ARG, "ldw_sr_len_quantiles: the genome length must be an integer");
     LDW_REQUIRE(q_lo_out && q_hi_out && n_out, LDW_ERR_ARG, "ldw_sr_len_quantiles: null output");
-    LDW_REQUIRE(c->paint_min >= 1 && c->paint_max <= nclust, LDW_ERR_ARG,
-                "ldw_sr_len_quantiles: cds_var$paint must lie in 1..nclust (found %d..%d, nclust %d)", (int)c->paint_min,
-                (int)c->paint_max, nclust);
+    LDW_REQUIRE(c->meta.paint_min >= 1 && c->meta.paint_max <= nclust, LDW_ERR_ARG,
+                "ldw_sr_len_quantiles: cds_var$paint must lie in 1..nclust (found %d..%d, nclust %d)", (int)c->meta.paint_min,
+                (int)c->meta.paint_max, nclust);
     // (POS may be in any order and may repeat: every row's len is computed from its two positions, rows with len outside
     // (0, sr_dist) are left out exactly as R/computePairwiseMI.R:414 does)
-    const int64_t n = c->n_sr;
+    const int64_t n = c->links.n_sr;
     c->srm.S = S;
     c->srm.nclust = nclust;
     c->srm.sr_dist = sr_dist;
@@ -1027,7 +1020,7 @@ int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, in
         }
         return LDW_OK;
     }
-    static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
+    const bool host_timing = ldw::host_timing();   // (host wall time of the steps below)
     const auto now = HostClock::now;
     const auto ms = HostClock::ms;
     const auto t_0 = now();
@@ -1041,7 +1034,7 @@ int ldw_sr_len_quantiles(ldw_ctx *c, int nclust, double sr_dist, double prob, in
         const size_t need[3] = {(size_t)n * 2 + 64, (size_t)n * sizeof(SrPay), srm_sort_temp_bytes(n) + 256};
         void *mem[3];
         size_t tmp_cap;
-        const bool borrow = LDW_NSLOT >= 3 && c->blk_capacity == 0 /* (no link pass open: its slots are really idle) */ && c->Gapx[0].cap >= need[0] && c->Gapx[1].cap >= need[1] && c->Gapx[2].cap >= need[2];
+        const bool borrow = LDW_NSLOT >= 3 && c->links.blk_capacity == 0 /* (no link pass open: its slots are really idle) */ && c->Gapx[0].cap >= need[0] && c->Gapx[1].cap >= need[1] && c->Gapx[2].cap >= need[2];
         const auto t_a = now();
         if (borrow) {
             if (c->gemm_stream) LDW_HIP(hipStreamSynchronize(c->gemm_stream));   // (idle already; the G' blocks belong to that stream's kernels)
@@ -1098,7 +1091,7 @@ int ldw_sr_excess_stats(ldw_ctx *c, int nclust, int32_t S, const double *mean_di
     if (int rc = sr_ready(c, "ldw_sr_excess_stats")) return rc;
     if (int rc = upload_md(c, nclust, S, mean_dist, "ldw_sr_excess_stats")) return rc;
     LDW_REQUIRE(stats_out, LDW_ERR_ARG, "ldw_sr_excess_stats: null output");
-    const int64_t n = c->n_sr;
+    const int64_t n = c->links.n_sr;
     for (int k = 0; k < nclust * 5; ++k) stats_out[k] = 0.0;
     if (n == 0) return LDW_OK;
     const int grid = (int)std::min<int64_t>((n + 255) / 256, SRM_GRID);
@@ -1127,7 +1120,7 @@ int ldw_sr_excess_stats_blocks(ldw_ctx *c, int nclust, int32_t S, const double *
         }
         run += rows_per_block[b];
     }
-    LDW_REQUIRE(run == c->n_sr, LDW_ERR_ARG, "ldw_sr_excess_stats_blocks: the blocks hold %lld rows, the short-range table %lld", (long long)run, (long long)c->n_sr);
+    LDW_REQUIRE(run == c->links.n_sr, LDW_ERR_ARG, "ldw_sr_excess_stats_blocks: the blocks hold %lld rows, the short-range table %lld", (long long)run, (long long)c->links.n_sr);
     const size_t per = (size_t)nclust * 5;
     for (size_t k = 0; k < (size_t)nblocks * per; ++k) stats_out[k] = 0.0;
     const int64_t nb = (int64_t)which.size();
@@ -1154,7 +1147,7 @@ int ldw_sr_pvalues(ldw_ctx *c, int nclust, int32_t S, const double *mean_dist, c
     for (int k = 0; k < nclust; ++k)
         LDW_REQUIRE(shape[3 * k] > 0 && shape[3 * k + 1] > 0 && std::isfinite(shape[3 * k + 2]), LDW_ERR_ARG,
                     "ldw_sr_pvalues: cluster %d has an invalid beta shape", k + 1);
-    const int64_t n = c->n_sr;
+    const int64_t n = c->links.n_sr;
     KeptLinks &K = c->kept;
     K.invalidate();
     K.from_lr = false;
@@ -1217,7 +1210,7 @@ int ldw_sr_reduced_fetch(ldw_ctx *c, int64_t capacity, int64_t *row_out, int32_t
     double *gmi = c->scratch.as<double>();
     int32_t *ga = reinterpret_cast<int32_t *>(gmi + n), *gb = ga + n;
     LDW_LAUNCH(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->kept.row.as<int64_t>(), n,
-                       c->sr_a.as<int32_t>(), c->sr_b.as<int32_t>(), c->sr_mi.as<double>(), ga, gb, gmi);
+                       c->links.sr_a.as<int32_t>(), c->links.sr_b.as<int32_t>(), c->links.sr_mi.as<double>(), ga, gb, gmi);
     LDW_HIP(hipMemcpyAsync(a_out, ga, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(b_out, gb, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(MI_out, gmi, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1258,7 +1251,7 @@ int ldw_lr_reduced_fetch(ldw_ctx *c, int64_t capacity, int64_t *row_out, int32_t
     double *gmi = c->scratch.as<double>();
     int32_t *ga = reinterpret_cast<int32_t *>(gmi + n), *gb = ga + n;
     LDW_LAUNCH(k_red_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->kept.row.as<int64_t>(), n,
-                       c->lr_a.as<int32_t>(), c->lr_b.as<int32_t>(), c->lr_mi.as<double>(), ga, gb, gmi);
+                       c->links.lr_a.as<int32_t>(), c->links.lr_b.as<int32_t>(), c->links.lr_mi.as<double>(), ga, gb, gmi);
     LDW_HIP(hipMemcpyAsync(a_out, ga, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(b_out, gb, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(MI_out, gmi, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1309,8 +1302,8 @@ int ldw_aracne_device(ldw_ctx *c, int64_t capacity, uint8_t *flags_out) {
     LDW_LAUNCH(k_ar_offsets, dim3((unsigned)((n_nodes + 1 + 255) / 256)), dim3(256), 0, c->stream, c->kept.ar_key2.as<uint64_t>(), n2, n_nodes,
                        c->kept.ar_off.as<int64_t>());
     // the links to check are rows of the short-range table (after ldw_sr_pvalues) or of the long-range one (after ldw_lr_tukey)
-    const int32_t *ta = (c->kept.from_lr ? c->lr_a : c->sr_a).as<int32_t>(), *tb2 = (c->kept.from_lr ? c->lr_b : c->sr_b).as<int32_t>();
-    const double *tmi = (c->kept.from_lr ? c->lr_mi : c->sr_mi).as<double>();
+    const int32_t *ta = (c->kept.from_lr ? c->links.lr_a : c->links.sr_a).as<int32_t>(), *tb2 = (c->kept.from_lr ? c->links.lr_b : c->links.sr_b).as<int32_t>();
+    const double *tmi = (c->kept.from_lr ? c->links.lr_mi : c->links.sr_mi).as<double>();
     LDW_LAUNCH(k_ar_check, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, c->stream, c->kept.row.as<int64_t>(), nr,
                        ta, tb2, tmi, c->kept.ar_key2.as<uint64_t>(),
                        c->kept.ar_val2.as<double>(), c->kept.ar_off.as<int64_t>(), c->kept.ar_flags.as<uint8_t>(), d_slot);
@@ -1328,7 +1321,7 @@ int ldw_sr_tail_extract(ldw_ctx *c, int nclust, int32_t S, const double *lower, 
     LDW_REQUIRE(c->srm.same_geometry(nclust, S) && nclust >= 1 && S >= 1, LDW_ERR_STATE,
                 "ldw_sr_tail_extract: nclust/S differ from the last ldw_sr_len_quantiles call");
     LDW_REQUIRE(lower && cnt_out && n_out, LDW_ERR_ARG, "ldw_sr_tail_extract: null argument");
-    const int64_t n = c->n_sr, G = (int64_t)nclust * S;
+    const int64_t n = c->links.n_sr, G = (int64_t)nclust * S;
     *n_out = 0;
     for (int64_t k = 0; k < G; ++k) cnt_out[k] = 0;
     if (n == 0) return LDW_OK;

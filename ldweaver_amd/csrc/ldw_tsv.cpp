@@ -299,7 +299,7 @@ int write_rows(const char *path, int append, int64_t nrows, const std::vector<Co
         int64_t round_open = -1;   // the last round whose offsets are known
         int64_t next_off = base;
         bool failed = false;
-        static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
+        const bool host_timing = ldw::host_timing();
         std::vector<double> t_fmt((size_t)nt, 0.0), t_wait((size_t)nt, 0.0), t_wr((size_t)nt, 0.0);
         auto worker = [&](int t) {
             bufs[(size_t)t].reset(new PoolBlock((size_t)chunk * row_max));   // (uninitialised; first touched by the thread that fills it)
@@ -465,7 +465,7 @@ struct LinksTsvJob {
 static int links_tsv_prepare(ldw_ctx *c, int which, const char *path, int append, int nthreads, LinksTsvJob &J) {
     if (int rc = ldw::check_gpu(c)) return rc;
     LDW_REQUIRE(path && (which == 0 || which == 1), LDW_ERR_ARG, "ldw_write_links_tsv: bad argument");
-    LDW_REQUIRE(c->have_meta && (int64_t)c->h_POS.size() == c->L && (int64_t)c->h_paint.size() == c->L, LDW_ERR_STATE,
+    LDW_REQUIRE(c->meta.have_meta && (int64_t)c->meta.h_POS.size() == c->L && (int64_t)c->meta.h_paint.size() == c->L, LDW_ERR_STATE,
                 "ldw_write_links_tsv: SNP meta data (POS, paint, g) not set");
     int64_t n = 0;
     if (int rc = ldw_links_count(c, which, &n)) return rc;
@@ -473,9 +473,9 @@ static int links_tsv_prepare(ldw_ctx *c, int which, const char *path, int append
     J.path = path;
     J.append = append;
     J.nthreads = nthreads;
-    J.g = c->g;
-    J.POS = c->h_POS.data();
-    J.paint = c->h_paint.data();
+    J.g = c->meta.g;
+    J.POS = c->meta.h_POS.data();
+    J.paint = c->meta.h_paint.data();
     if (n == 0) return LDW_OK;   // the reference writes nothing for an empty frame (R/computePairwiseMI.R:360)
     // (uninitialised arrays: a std::vector would clear 48 bytes per row on the calling thread before anything is written)
     // The table itself (a, b, MI: 16 bytes per row) is fetched into a PINNED arena that stays with the context.  r04, measured
@@ -548,9 +548,9 @@ static void lr_stream_batch(LrStream *S, int64_t hi) {
     double *mi = c->lr_pin.as<double>();
     int32_t *a = reinterpret_cast<int32_t *>(mi + n), *b = a + n;
     // (the table's buffers cannot move under this copy: a growth of the long-range table drains the stream first — ensure_links_capacity)
-    hipError_t e = hipMemcpyAsync(a, c->lr_a.as<int32_t>() + lo, (size_t)n * 4, hipMemcpyDeviceToHost, S->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b, c->lr_b.as<int32_t>() + lo, (size_t)n * 4, hipMemcpyDeviceToHost, S->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(mi, c->lr_mi.as<double>() + lo, (size_t)n * 8, hipMemcpyDeviceToHost, S->st);
+    hipError_t e = hipMemcpyAsync(a, c->links.lr_a.as<int32_t>() + lo, (size_t)n * 4, hipMemcpyDeviceToHost, S->st);
+    if (e == hipSuccess) e = hipMemcpyAsync(b, c->links.lr_b.as<int32_t>() + lo, (size_t)n * 4, hipMemcpyDeviceToHost, S->st);
+    if (e == hipSuccess) e = hipMemcpyAsync(mi, c->links.lr_mi.as<double>() + lo, (size_t)n * 8, hipMemcpyDeviceToHost, S->st);
     if (e == hipSuccess) e = hipStreamSynchronize(S->st);
     if (e != hipSuccess) {
         S->rc = LDW_ERR_HIP;
@@ -559,7 +559,7 @@ static void lr_stream_batch(LrStream *S, int64_t hi) {
     }
     int64_t wrote = 0;
     // (while the pass runs: few threads — the submitting thread and its helpers need the host more; once the stream is closing the pass is over)
-    const int rc = write_link_rows(S->path.c_str(), S->first_batch ? S->append : 1, S->closing_seen ? 0 : S->nthreads, n, a, b, mi, c->h_POS.data(), c->h_paint.data(), c->g, &wrote);
+    const int rc = write_link_rows(S->path.c_str(), S->first_batch ? S->append : 1, S->closing_seen ? 0 : S->nthreads, n, a, b, mi, c->meta.h_POS.data(), c->meta.h_paint.data(), c->meta.g, &wrote);
     S->first_batch = false;
     if (rc != LDW_OK) {
         S->rc = rc;
@@ -652,7 +652,7 @@ static int write_link_rows(const char *path, int append, int nthreads, int64_t n
                            const int32_t *paint, double g, int64_t *bytes_out) {
     if (bytes_out) *bytes_out = 0;
     if (n == 0) return LDW_OK;
-    static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
+    const bool host_timing = ldw::host_timing();
     const auto t_1 = std::chrono::steady_clock::now();
     PoolBlock derived((size_t)n * 32);   // pos1, pos2 (int32), clust1, clust2, len (double)
     LDW_REQUIRE(derived.p != nullptr, LDW_ERR_ARG, "ldw_write_links_tsv: out of host memory");
@@ -697,7 +697,7 @@ static int write_link_rows(const char *path, int append, int nthreads, int64_t n
 static int links_tsv_finish(LinksTsvJob &J, int64_t *bytes_out) {
     if (bytes_out) *bytes_out = 0;
     if (J.n == 0) return LDW_OK;
-    static const bool host_timing = getenv("LDW_HOST_TIMING") != nullptr;
+    const bool host_timing = ldw::host_timing();
     if (host_timing) fprintf(stderr, "[ldw] links tsv: fetch %.2f ms\n", J.fetch_ms);
     const int rc = write_link_rows(J.path.c_str(), J.append, J.nthreads, J.n, J.a, J.b, J.mi, J.POS, J.paint, J.g, bytes_out);
     J.derived.reset();
@@ -770,7 +770,7 @@ int ldw_host_trim(ldw_ctx *c, int64_t *bytes_out) {
     // pinned fetch arena (up to 2 GB x 1.125) until the context dies.  They are kept on purpose WHILE jobs run (an munmap next to GPU work
     // stalls the process's next GPU call by ~20 ms: docs/HISTORY.md 8); this gives them back between jobs, when the caller says so.
     int64_t n = (int64_t)host_pool().trim();
-    n += (int64_t)ldw::device_pool_trim();   // r05: + the released DEVICE blocks kept for the next context (ldw_api.hip)
+    n += (int64_t)ldw::device_pool_trim();   // r05: + the released DEVICE blocks kept for the next context (ldw_alloc.cpp)
     if (c) {
         if (int rc = tsv_async_join(c, nullptr, nullptr)) return rc;
         n += ldw::fasta_trim(c);   // the FASTA feeder's pinned chunk buffers
@@ -790,7 +790,7 @@ int ldw_lr_stream_begin(ldw_ctx *c, const char *path, int append, int nthreads) 
     if (int rc = ldw::check_gpu(c)) return rc;
     LDW_REQUIRE(path != nullptr, LDW_ERR_ARG, "ldw_lr_stream_begin: null path");
     LDW_REQUIRE(c->lr_stream == nullptr, LDW_ERR_STATE, "ldw_lr_stream_begin: a stream is already open (ldw_lr_stream_end)");
-    LDW_REQUIRE(c->have_meta && (int64_t)c->h_POS.size() == c->L && (int64_t)c->h_paint.size() == c->L, LDW_ERR_STATE,
+    LDW_REQUIRE(c->meta.have_meta && (int64_t)c->meta.h_POS.size() == c->L && (int64_t)c->meta.h_paint.size() == c->L, LDW_ERR_STATE,
                 "ldw_lr_stream_begin: SNP meta data (POS, paint, g) not set");
     if (!append) {   // (truncate now: a pass that keeps no long-range row writes nothing, like the reference — :360 — but must not leave an old file behind)
         const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);

@@ -20,7 +20,7 @@ inline dim3 grid_of(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std:
     } while (0)
 
 // ldw_post.hip.  The ascending order of the context's positions, built on first use after they change (one stable sort of h_POS: SNPs of one
-// position stay in index order) and kept on the device in ctx->pos_ord: slot / n_slots unless POS ascends strictly, srt / order unless it ascends.
+// position stay in index order) and kept on the device in ctx->meta.pos_ord: slot / n_slots unless POS ascends strictly, srt / order unless it ascends.
 int pos_order(ldw_ctx *ctx);
 // The caller's POS (host, L entries, any order) ascending on the device, into arrays the caller carved: spos[k] = the k-th smallest position over
 // key bits [0, end_bit), sidx[k] = its SNP (equal positions in index order).  d_pos takes POS as given, iota is working memory, tmp holds

@@ -1549,7 +1549,7 @@ def test_full_size_properties(engine, Ls, N):
 
 
 def test_link_tables_regrow_mid_call(synth):
-    """DevBuf::reserve_keep (ldw_api.hip) under load: a FRESH context whose link tables start empty takes blocks one by one
+    """DevBuf::reserve_keep (ldw_alloc.cpp) under load: a FRESH context whose link tables start empty takes blocks one by one
     (ldw_mi_block_links sizes the tables per block, so the short-range and long-range tables are reallocated — and their rows
     copied — several times while earlier blocks' rows are already in them), then a larger all-pairs call after a smaller one
     (stale row counts from the previous call).  Tables must equal those of the driver that sizes the short-range table up front."""
