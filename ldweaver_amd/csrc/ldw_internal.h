@@ -297,6 +297,7 @@ struct HostClock {
     using Point = std::chrono::steady_clock::time_point;
     static Point now() { return std::chrono::steady_clock::now(); }
     static double ms(Point a, Point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+    static double us(Point a, Point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
 };
 }  // namespace ldw
 

@@ -39,10 +39,8 @@
 #define LDW_SCREEN_WAVES 6   // waves per SIMD the screen is compiled for (80 VGPRs; 5: 96)
 #endif
 #include "ldw_epi.h"
-#include <condition_variable>
-#include <mutex>
+#include "ldw_pass_plan.h"
 #include <future>
-#include <thread>
 
 #include "ldw_apx.h"
 
@@ -60,6 +58,7 @@ namespace ldw {
 namespace {
 #include "ldw_mi_block.inc"
 #include "ldw_mi_items.inc"
+#include "ldw_mi_pass.inc"
 }  // namespace
 
 namespace ldw {
@@ -344,433 +343,50 @@ int ldw_links_end(ldw_ctx *c) {
     return LDW_OK;
 }
 
-// ---- spans (r04): which blocks of the list may share a launch sequence ----
-// A block can be part of a span when its to side lies strictly AFTER its from side (make_blocks order: i < j), it is square, far enough
-// from its from side that no pair is short-range (POS ascends over the alignment: the test of build_cols on the four end positions), and
-// neither side holds a SNP the fused table test cannot place (no indicator row, or unflagged slots: h_span_bad).
-// Corner blocks (a few short-range pairs at the facing ends) stay items of their own: docs/HISTORY.md 6b.
-static bool span_candidate(const ldw_ctx *c, const int32_t *b, const ldw_mi_params *p) {
-    const int64_t fs = b[0], fe = b[1], ts = b[2], te = b[3];
-    if (!(fs >= 1 && fe >= fs && ts > fe && te >= ts && te <= c->L)) return false;
-    const int64_t nf = fe - fs + 1, nt = te - ts + 1;
-    if (nf != nt || nf < 2048) return false;
-    if ((int64_t)c->rows.h_span_bad.size() != c->L + 1) return false;
-    if (c->rows.h_span_bad[(size_t)fe] - c->rows.h_span_bad[(size_t)fs - 1] != 0 || c->rows.h_span_bad[(size_t)te] - c->rows.h_span_bad[(size_t)ts - 1] != 0) return false;
-    if (!(2 * p->sr_dist < c->meta.g)) return false;
-    const std::vector<int32_t> &P = c->meta.h_POS;
-    const double pf_min = P[(size_t)fs - 1], pf_max = P[(size_t)fe - 1], pt_min = P[(size_t)ts - 1], pt_max = P[(size_t)te - 1];
-    return pt_min - pf_max > p->sr_dist && pf_min + c->meta.g - pt_max > p->sr_dist;
-}
-// what the whole pass must offer (checked once, when the pass is planned: a positive guess for off-diagonal blocks exists, or — guess_expected —
-// the cold-start probe of the pass is about to sample one)
-static bool spans_possible(const ldw_ctx *c, const ldw_mi_params *p, bool guess_expected) {
-    static const bool env_off = getenv("LDW_NO_SPAN") != nullptr;
-    return c->knobs.span_on && !env_off && c->knobs.span_max >= 2 && c->knobs.prune && c->knobs.engine == LDW_ENGINE_MFMA && c->apx.apx_ok && c->knobs.path_mode != 1 && c->knobs.screen == 1 &&
-           !p->sr_only && speculation_pays(c, p) && c->meta.pos_sorted && (c->spec.spec_B_next[0] > 0 || guess_expected) &&
-           (p->quirk_mode != LDW_QUIRK_REFERENCE || c->meta.r_min >= 2.0);
-}
-struct WorkItem {
-    int64_t b0;
-    int nseg;           // 1: an ordinary block
-};
-
+// A pass over a block list: the plan, the helpers, the table sizing, the probes and the item loop are ldw_mi_pass.inc's (and ldw_pass_plan.h's).
 int ldw_mi_all_pairs(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, const ldw_mi_params *p, int reset) {
     if (int rc = check_gpu(c)) return rc;
     LDW_REQUIRE(blocks && p && nblocks > 0, LDW_ERR_ARG, "ldw_mi_all_pairs: bad argument");
     LDW_REQUIRE(reset, LDW_ERR_ARG, "ldw_mi_all_pairs: appending to earlier calls is not supported (reset must be 1)");
     const bool host_timing = ldw::host_timing();
-    auto now0 = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_enter = now0();
+    using Clock = HostClock;
+    const Clock::Point t_enter = Clock::now();
     if (int rc = join_prepare(c)) return rc;
-    const double t_joined = now0();
+    const Clock::Point t_joined = Clock::now();
     if (int rc = ldw_links_begin(c, nblocks)) return rc;
     if (int rc = links_check(c, p)) return rc;
-    const double t_begun = now0();
+    const Clock::Point t_begun = Clock::now();
     SmallLayout sl;
     links_layout(c, sl);
-    std::vector<int32_t> fi, ti;
-    auto fill = [&](int64_t b) -> int {
-        const int32_t fs = blocks[b * 4 + 0], fe = blocks[b * 4 + 1], ts = blocks[b * 4 + 2], te = blocks[b * 4 + 3];
-        LDW_REQUIRE(fs >= 1 && fe >= fs && fe <= c->L && ts >= 1 && te >= ts && te <= c->L, LDW_ERR_ARG,
-                    "block %lld = (%d,%d,%d,%d) outside 1..%lld", (long long)b, fs, fe, ts, te, (long long)c->L);
-        fi.resize((size_t)(fe - fs + 1));
-        ti.resize((size_t)(te - ts + 1));
-        for (int32_t k = fs; k <= fe; ++k) fi[k - fs] = k - 1;
-        for (int32_t k = ts; k <= te; ++k) ti[k - ts] = k - 1;
-        return LDW_OK;
-    };
-    // Software pipeline, three ITEMS deep on the host (an item = one block, or a span of consecutive long-range-only blocks of one block
-    // row: r04): item i's epilogue chain is submitted (main stream), then at once the block-wide pass of item i+1 (GEMM stream; prepared
-    // earlier), and only then the host waits for item i's pick(s).
-    // r03: the lists of an item are built by a HELPER THREAD that runs ahead of the submitting thread (prep_block is pure host work into the
-    // slot's pinned staging buffer: 0.45 ms per 10k x 10k block — once the GPU side of a block had come down to 0.5 ms it was the loop's
-    // critical path).  Hand-over through counters under one mutex: item k may be prepared once item k - RING is finished (its ring entry
-    // is free) and item k - LDW_NSLOT has been submitted (the slot's staging buffer then belongs to an upload the helper waits for: ev_up).
-    // The plan is complete before the helpers start (below); the GEMM stream runs up to LDW_NSLOT - 1 = 2 items ahead of the item the main
-    // stream evaluates.
-    constexpr int RING = 8;
-    HostBlock hb[RING];
-    double th[5] = {0, 0, 0, 0, 0};
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    // The plan: items in block order, made BEFORE the helpers start and before the cold-start probes are queued, so that the list building of
-    // the first span (~3 ms for eight blocks, against 1.3 ms of GPU work in the diagonal block in front of it) runs beside the probes and
-    // the first item instead of after them.  Whether spans may form depends on a positive guess for off-diagonal blocks: on a cold pass the
-    // plan ASSUMES the off-diagonal probe below will deliver one (it is known here whether that probe will be attempted).  A probe that then
-    // yields no guess costs time, never a row: the spans planned on it fall back as any span whose guess has gone does (submit_a: span_alone).
-    static const bool probe_on = getenv("LDW_NO_PROBE") == nullptr;
-    const bool probes_wanted = probe_on && !p->sr_only && c->meta.pos_sorted && speculation_pays(c, p);
-    bool probe_expected = false;   // an off-diagonal guess is missing and the first off-diagonal block is large enough to be sampled
-    if (probes_wanted && c->spec.spec_B_next[0] < 0)
-        for (int64_t b = 0; b < nblocks; ++b) {
-            if (blocks[b * 4 + 0] == blocks[b * 4 + 2] && blocks[b * 4 + 1] == blocks[b * 4 + 3]) continue;
-            probe_expected = (int64_t)(blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1) * (int64_t)(blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1) >= PROBE_MIN_PAIRS;
-            break;
-        }
-    std::vector<WorkItem> items;
-    {   // consecutive candidates of one block row, to sides ascending, form a span (at most span_max blocks,
-        // nf x nt below the 32-bit index limit of the unit lists, the int32 block below ~6 GB)
-        const bool spans = spans_possible(c, p, probe_expected);
-        for (int64_t b = 0; b < nblocks;) {
-            int n = 1;
-            if (spans && span_candidate(c, blocks + b * 4, p)) {
-                const int64_t nf = blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1;
-                int64_t nt_tot = blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1;
-                static const int env_max = [] { const char *e = getenv("LDW_SPAN_MAX"); return e ? atoi(e) : 0; }();   // (A/B measurements)
-                const int nmax = std::min<int>(env_max >= 1 ? env_max : c->knobs.span_max, LDW_SPAN_MAX);
-                while (n < nmax && b + n < nblocks && span_candidate(c, blocks + (b + n) * 4, p) && blocks[(b + n) * 4 + 0] == blocks[b * 4 + 0] &&
-                       blocks[(b + n) * 4 + 1] == blocks[b * 4 + 1] && blocks[(b + n) * 4 + 2] > blocks[(b + n - 1) * 4 + 3]) {
-                    const int64_t nt_k = blocks[(b + n) * 4 + 3] - blocks[(b + n) * 4 + 2] + 1;
-                    if (nf * (nt_tot + nt_k) >= 1500000000LL || (nt_tot + nt_k) > 900000) break;
-                    nt_tot += nt_k;
-                    ++n;
-                }
-            }
-            items.push_back(WorkItem{b, n});
-            b += n;
-        }
-        c->early_sr = spans;
-    }
-    const int64_t nitems = (int64_t)items.size();
-    struct Shared {
-        std::mutex m;
-        std::condition_variable cv;
-        int64_t n_sub = 0, n_done = 0, next = 0;   // next: the item the next free helper takes
-        std::vector<uint8_t> prepped;               // per item (helpers finish out of order)
-        int rc = LDW_OK;
-        int64_t bad = INT64_MAX;             // the first item whose preparation failed (items before it are still good: r05)
-        bool stop = false;
-        std::string err;
-    } sh;
-    sh.prepped.assign((size_t)nblocks + 1, 0);
-    // r04: TWO helpers (a span of eight blocks took ~3 ms of list building, a diagonal block in front of it gives the
-    // GPU 1.3 ms of work: one helper left the GEMM stream waiting).  Each takes the next item; items k, k+1, k+2 use different slots.
-    // Now one helper per slot: with the whole plan known at the start, the first three items — the diagonal block, the corner block next
-    // to it and the first span (1.2, 0.9 and 2 ms of list building) — are prepared side by side, where the span used to start behind the
-    // corner block and the GEMM stream stood idle for 0.4-0.9 ms in front of it (profiles/cold_start_timeline.txt).
-    auto worker = [&]() {
-        (void)hipSetDevice(c->device);
-        std::vector<int32_t> wfi, wti;   // this helper's own index lists
-        for (;;) {
-            WorkItem it{0, 0};
-            int64_t k = 0;
-            {
-                std::unique_lock<std::mutex> lk(sh.m);
-                sh.cv.wait(lk, [&] {
-                    if (sh.stop || sh.next >= nitems) return true;   // (nothing left: leave)
-                    return sh.next < sh.n_done + RING && sh.next < sh.n_sub + LDW_NSLOT;
-                });
-                if (sh.stop || sh.next >= nitems) return;
-                k = sh.next++;
-                it = items[(size_t)k];
-            }
-            int rc = LDW_OK;
-            try {   // (prep_block allocates a dozen std::vectors: an exception on this thread must come back as an error code, not std::terminate)
-                const int32_t fs = blocks[it.b0 * 4 + 0], fe = blocks[it.b0 * 4 + 1];
-                bool ok = fs >= 1 && fe >= fs && fe <= c->L;
-                SpanPlan spn;
-                wti.clear();
-                for (int q = 0; q < it.nseg && ok; ++q) {
-                    const int32_t ts = blocks[(it.b0 + q) * 4 + 2], te = blocks[(it.b0 + q) * 4 + 3];
-                    ok = ts >= 1 && te >= ts && te <= c->L;
-                    if (!ok) break;
-                    spn.start[q] = (int32_t)wti.size();
-                    spn.nt[q] = te - ts + 1;
-                    for (int32_t x = ts; x <= te; ++x) wti.push_back(x - 1);
-                }
-                spn.nseg = it.nseg;
-                if (!ok) {
-                    set_error("block %lld = (%d,%d,%d,%d) outside 1..%lld", (long long)it.b0, fs, fe, blocks[it.b0 * 4 + 2], blocks[it.b0 * 4 + 3], (long long)c->L);
-                    rc = LDW_ERR_ARG;
-                } else {
-                    wfi.resize((size_t)(fe - fs + 1));
-                    for (int32_t q = fs; q <= fe; ++q) wfi[q - fs] = q - 1;
-                    const int slot = (int)(k % LDW_NSLOT);
-                    if (c->up_recorded[slot] && hipEventSynchronize(c->ev_up[slot]) != hipSuccess) {   // the staging buffer of this slot has been uploaded
-                        set_error("prep: hipEventSynchronize failed");
-                        rc = LDW_ERR_HIP;
-                    }
-                    HostBlock &h = hb[k % RING];
-                    if (rc == LDW_OK) rc = prep_block(c, wfi.data(), (int64_t)wfi.size(), wti.data(), (int64_t)wti.size(), p, slot, it.b0, h, it.nseg > 1 ? &spn : nullptr);
-                    if (rc == LDW_OK && it.nseg > 1) {
-                        h.span_from = wfi;
-                        h.span_to = wti;
-                    }
-                }
-            } catch (const std::exception &e) {
-                set_error("preparing block %lld: %s", (long long)it.b0, e.what());
-                rc = LDW_ERR_HIP;
-            } catch (...) {
-                set_error("preparing block %lld: unknown exception", (long long)it.b0);
-                rc = LDW_ERR_HIP;
-            }
-            std::lock_guard<std::mutex> lk(sh.m);
-            if (rc != LDW_OK) {
-                if (sh.rc == LDW_OK || k < sh.bad) {
-                    sh.rc = rc;
-                    sh.err = ldw_last_error();
-                }
-                sh.bad = std::min(sh.bad, k);
-                sh.stop = true;
-            } else {
-                sh.prepped[(size_t)k] = 1;
-            }
-            sh.cv.notify_all();
-            if (rc != LDW_OK) return;
-        }
-    };
-    constexpr int n_helpers = LDW_NSLOT;
-    std::thread helpers[n_helpers];
-    for (int i = 0; i < n_helpers; ++i) helpers[i] = std::thread(worker);
-    struct Joiner {   // every way out of this function stops and joins the helpers
-        Shared &sh;
-        std::thread *t;
-        int n;
-        ~Joiner() {
-            {
-                std::lock_guard<std::mutex> lk(sh.m);
-                sh.stop = true;
-            }
-            sh.cv.notify_all();
-            for (int i = 0; i < n; ++i)
-                if (t[i].joinable()) t[i].join();
-        }
-    } joiner{sh, helpers, n_helpers};
-    // (the helpers are at work: the table sizing below runs beside the list building of the first items, which is what the GPU waits for)
-    if (p->keep_sr && c->meta.pos_sorted && 2 * p->sr_dist < c->meta.g) {
-        // Size the short-range table ONCE: geometric growth re-copies up to a gigabyte and synchronises both streams every time (ten times in
-        // the first pass of C4), and would double-buffer tens of GB at C5.  The blocks of a pass hold every unordered SNP pair at most once,
-        // so the number of pairs within sr_dist on the circle bounds the rows: POS ascends — a two-pointer walk, O(L) (r03 ran build_cols
-        // over every block for this, 0.2 ms each, and only for passes of more than 200 blocks).
-        const int64_t Ls = c->L;
-        const std::vector<int32_t> &P = c->meta.h_POS;
-        int64_t total_sr = 0, hi = 0, wlo = 0;
-        if (c->sizing.sr_total_dist == p->sr_dist && c->sizing.sr_total >= 0) total_sr = c->sizing.sr_total;   // (the walk is 1 ms at L = 100k: once per positions and sr_dist)
-        else {
-        for (int64_t a = 0; a < Ls; ++a) {
-            if (hi < a + 1) hi = a + 1;
-            while (hi < Ls && (double)P[(size_t)hi] - (double)P[(size_t)a] <= p->sr_dist) ++hi;
-            total_sr += hi - a - 1;                                   // partners ahead of a, directly
-        }
-        for (int64_t a = 0; a < Ls; ++a) {   // partners across the origin: b before a with P[b] + g - P[a] <= sr_dist (the limit ascends with a)
-            const double lim = p->sr_dist - c->meta.g + (double)P[(size_t)a];
-            if (lim < (double)P[0]) continue;
-            while (wlo < Ls && (double)P[(size_t)wlo] <= lim) ++wlo;
-            total_sr += std::min<int64_t>(wlo, a);
-        }
-        c->sizing.sr_total = total_sr;
-        c->sizing.sr_total_dist = p->sr_dist;
-        }
-        // r05: a SHARE of the block list (a rank or context of a multi-GPU job: under three quarters of the pair space) is sized for the rows of ITS blocks — the band
-        // enumerator counts them on the device in well under a millisecond (ldw_sr_pairs_fill without outputs; cached per block list) — instead of the whole alignment's:
-        // at config 5 that is 4.5 instead of 36 GB per rank of eight.  Whatever this under-estimates still grows where it is used (ensure_links_capacity per item).
-        int64_t want_sr = total_sr;
-        {
-            double share_pairs = 0;
-            uint64_t key = 1469598103934665603ull ^ (uint64_t)(int64_t)(p->sr_dist * 16.0);
-            for (int64_t b = 0; b < nblocks; ++b) {
-                share_pairs += (double)(blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1) * (double)(blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1);
-                for (int q = 0; q < 4; ++q) key = (key ^ (uint64_t)(uint32_t)blocks[b * 4 + q]) * 1099511628211ull;
-            }
-            if (share_pairs < 0.375 * (double)Ls * (double)Ls && c->meta.g == std::floor(c->meta.g)) {
-                if (c->sizing.sr_share_rows >= 0 && c->sizing.sr_share_key == key) want_sr = std::min(total_sr, c->sizing.sr_share_rows);
-                else {
-                    int64_t n_share = 0;
-                    if (ldw_sr_pairs_fill(c, blocks, nblocks, p->sr_dist, nullptr, nullptr, 0, &n_share) == LDW_OK && n_share <= total_sr) {
-                        c->sizing.learn_share(key, n_share);
-                        want_sr = n_share;
-                    }
-                }
-            }
-        }
-        if (int rc = ensure_links_capacity(c, want_sr + 1024, 0)) return rc;
-    }
-    if (!p->sr_only) {
-        // r05: the long-range table sized ONCE as well.  The per-block filter keeps about lr_retain_links rows in all (R/computePairwiseMI.R:347-358:
-        // prob = 1 - lr_retain_links / lr_links_approx), and what a selection needs beyond the rows kept so far is its own candidate count (<= 2^20 on
-        // the sort-free path): 1.25 lr_retain_links + 4 M rows, at most the pass's pairs.  A fresh context grew the table nine times in its first
-        // pass — each time a stream synchronisation, and with lr_links.tsv streaming (ldw_lr_stream_begin) a wait for the writer thread on top
-        // (tools/lr_stream_probe.py: first pass 72-88 ms against 41).  Whatever this under-estimates still grows where it is used.
-        double tot_pairs = 0;
-        for (int64_t b = 0; b < nblocks; ++b) tot_pairs += (double)(blocks[b * 4 + 1] - blocks[b * 4 + 0] + 1) * (double)(blocks[b * 4 + 3] - blocks[b * 4 + 2] + 1);
-        const double want = std::min(tot_pairs, std::max(0.0, p->lr_retain_links) * 1.25 + (double)(4 << 20));
-        if (want < 4e9)
-            if (int rc = ensure_links_capacity(c, c->links.n_sr, (int64_t)want)) return rc;
-    }
-    const double t_sized = now0();
-    // blocks until item k is prepared (true) — or, with wait = false, says whether it is
-    auto prepped = [&](int64_t k, bool wait, int &rc) -> bool {
-        std::unique_lock<std::mutex> lk(sh.m);
-        // (a failure of a LATER item does not concern this one: the helpers take the items in order, so every item before the failed one is
-        // prepared or being prepared — the pass runs on to the failed item itself, like the reference's loop: R/computePairwiseMI.R:103-116)
-        if (wait) sh.cv.wait(lk, [&] { return (sh.rc != LDW_OK && k >= sh.bad) || sh.prepped[(size_t)k] != 0; });
-        rc = (sh.rc != LDW_OK && k >= sh.bad) ? sh.rc : LDW_OK;
-        if (rc != LDW_OK) set_error("%s", sh.err.c_str());
-        return sh.prepped[(size_t)k] != 0;
-    };
-    int64_t n_sub = 0;   // items [0, n_sub) have been submitted to the GEMM stream
-    auto submit_next = [&]() -> int {
-        if (int rc = submit_a(c, hb[n_sub % RING], p, sl)) return rc;
-        ++n_sub;
-        {
-            std::lock_guard<std::mutex> lk(sh.m);
-            sh.n_sub = n_sub;
-        }
-        sh.cv.notify_all();
-        return LDW_OK;
-    };
-    const int64_t ahead = c->knobs.overlap ? LDW_NSLOT - 1 : 1;
-    // (the helpers are already building the first items' lists while the probes run)
-    // cold start: a sampled guess for each block kind that has none yet (probe_kind_guess), taken from the first block of the kind
-    Probe probes[2];
-    int n_probe = 0;
-    if (probes_wanted) {
-        bool done_kind[2] = {false, false};
-        size_t pin_base = 0;
-        for (int64_t b = 0; b < nblocks && !(done_kind[0] && done_kind[1]); ++b) {
-            const bool diag = blocks[b * 4 + 0] == blocks[b * 4 + 2] && blocks[b * 4 + 1] == blocks[b * 4 + 3];
-            const int kind = diag ? 1 : 0;
-            if (done_kind[kind]) continue;
-            done_kind[kind] = true;
-            if (c->spec.spec_B_next[kind] >= 0) continue;
-            if (int rc = fill(b)) return rc;
-            const int64_t npairs = diag ? (int64_t)fi.size() * ((int64_t)fi.size() - 1) / 2 : (int64_t)fi.size() * (int64_t)ti.size();
-            if (npairs < PROBE_MIN_PAIRS) continue;
-            // (a staging buffer that has to grow for the second sample is reallocated: the first sample's upload must have left it)
-            if (n_probe > 0 && c->pin[LDW_NSLOT].cap < pin_base + 2 * probes[0].hb.total + 65536) LDW_HIP(hipStreamSynchronize(c->stream));
-            if (int rc = probe_enqueue(c, fi.data(), (int64_t)fi.size(), ti.data(), (int64_t)ti.size(), p, sl, kind, n_probe, pin_base, probes[n_probe])) return rc;
-            pin_base = (pin_base + probes[n_probe].hb.total + 255) / 256 * 256;
-            ++n_probe;
-        }
-    }
-    const double t_queued = now0();
-    // The first item's lists go up while the probes run (the upload needs no guess).  Then the host waits for the probes that item needs — the
-    // one that ran on slot 0's buffers, the one of the item's own kind — and NOT for a second probe of the other kind: that one finishes on
-    // the main stream beside the item's block-wide pass and is collected behind the item's second phase, before anything else is submitted.
-    int deferred = -1;   // the probe still to collect
-    {
-        int rc = LDW_OK;
-        prepped(0, true, rc);
-        if (rc) return rc;
-        if ((rc = submit_upload(c, hb[0]))) return rc;
-        const int kind0 = hb[0].diag ? 1 : 0;
-        for (int k = 0; k < n_probe; ++k) {
-            if (!probes[k].queued) continue;
-            if (probes[k].which != 0 && probes[k].kind != kind0) {
-                deferred = k;
-                continue;
-            }
-            LDW_HIP(hipEventSynchronize(c->ev_probe[probes[k].which]));
-            probe_collect(c, probes[k]);
-        }
-    }
-    const double t_probed = now0();
-    if (int rc = submit_next()) return rc;
-    const double t_planned = now0();
+    const PassPlan plan = plan_pass(c, blocks, nblocks, p);
+    ItemLoop loop(c, blocks, p, sl, plan.items);   // (every return below joins the helpers: ~ItemLoop)
+    c->early_sr = plan.spans;                      // read by the helpers: stored before the first one starts
+    loop.start_helpers();
+    if (int rc = size_link_tables(c, blocks, nblocks, p)) return rc;
+    const Clock::Point t_sized = Clock::now();
+    Probes probes;
+    if (plan.probes_wanted)
+        if (int rc = queue_probes(c, blocks, nblocks, p, sl, probes)) return rc;
+    const Clock::Point t_queued = Clock::now();
+    // The first item's lists go up while the probes run (the upload needs no guess); then the host waits for the probes that item needs.
+    if (int rc = loop.wait_prepared(0)) return rc;
+    if (int rc = submit_upload(c, loop.hb[0])) return rc;
+    if (int rc = collect_probes_for(c, loop.hb[0], probes)) return rc;
+    const Clock::Point t_probed = Clock::now();
+    if (int rc = loop.submit_next()) return rc;
+    const Clock::Point t_planned = Clock::now();
     if (host_timing)
         fprintf(stderr, "[ldw host us] waiting for the side threads %.0f  links_begin (row map if stale, bookkeeping) %.0f  table sizing + plan + helper start %.0f  cold-start probes queued %.0f  first upload + wait for its probe %.0f  first item submitted %.0f\n",
-                t_joined - t_enter, t_begun - t_joined, t_sized - t_begun, t_queued - t_sized, t_probed - t_queued, t_planned - t_probed);
-    int fail_rc = LDW_OK;
-    std::string fail_msg;
-    int64_t b_fail = -1;          // the item the loop was at when it failed
-    bool b_fail_submitted = false, b_fail_finished = false;
-    auto failed = [&](int rc, int64_t b, bool sub_b, bool fin) {
-        fail_rc = rc;
-        fail_msg = ldw_last_error();
-        b_fail = b;
-        b_fail_submitted = sub_b;
-        b_fail_finished = fin;
-    };
-    for (int64_t b = 0; b < nitems && fail_rc == LDW_OK; ++b) {
-        HostBlock &cur = hb[b % RING];
-        double t0 = now();
-        if (int rc = submit_b(c, cur, p, sl)) { failed(rc, b, false, false); break; }   // epilogue + pick of item b (main stream)
-        th[0] += now() - t0;
-        if (deferred >= 0) {   // (b == 0) the probe of the other kind ran in front of this second phase: its guess is there before any item of its kind is submitted
-            if (hipEventSynchronize(c->ev_probe[probes[deferred].which]) != hipSuccess) {
-                set_error("cold-start probe: hipEventSynchronize failed");
-                failed(LDW_ERR_HIP, b, true, false);
-                break;
-            }
-            probe_collect(c, probes[deferred]);
-            deferred = -1;
-        }
-        t0 = now();
-        // items b+1 .. b+ahead (GEMM stream) run beside them: b+1 is waited for, the ones after it are taken if they are ready
-        while (n_sub < nitems && n_sub <= b + ahead) {
-            int rc = LDW_OK;
-            const double tw = now();
-            const bool ready = prepped(n_sub, n_sub == b + 1, rc);
-            th[1] += now() - tw;
-            if (rc) { failed(rc, b, true, false); break; }
-            if (!ready || !can_submit_early(c, hb[n_sub % RING], p)) break;
-            if ((rc = submit_next())) { failed(rc, b, true, false); break; }
-        }
-        if (fail_rc != LDW_OK) break;
-        th[2] += now() - t0;
-        t0 = now();
-        // (tried: the second phase of block b+1 queued HERE, before the host waits for block b's pick, so that the main stream has work during the
-        // round trip — block b's selection then runs behind it, its slot is released later, and the pass got slower: 43.0 against 40.2 ms)
-        if (int rc = finish_block(c, cur, p, sl)) { failed(rc, b, true, false); break; }   // round trip + selection of item b
-        th[3] += now() - t0;
-        {
-            std::lock_guard<std::mutex> lk(sh.m);
-            sh.n_done = b + 1;
-        }
-        sh.cv.notify_all();
-        c->links.blk_cursor += items[(size_t)b].nseg;
-        lr_stream_push(c, c->stream, sl.lr_count, c->links.blk_cursor);   // (no-op without ldw_lr_stream_begin: the rows of this item may go to lr_links.tsv now)
-        if (n_sub <= b + 1 && b + 1 < nitems) {                          // overlap off / no guess yet: one item after the other
-            int rc = LDW_OK;
-            prepped(b + 1, true, rc);
-            if (rc) { failed(rc, b, true, true); break; }
-            if ((rc = submit_next())) { failed(rc, b, true, true); break; }
-        }
-    }
-    if (fail_rc != LDW_OK) {
-        // r05: with lr_links.tsv streaming, the items that were submitted before the failure are run to their end, so that the file holds
-        // the rows of EVERY block in front of the failed one — what the reference's loop has appended when it stops at a block (:362).
-        // Best effort: a second failure in here is ignored, the first one is reported.
-        if (c->lr_stream && b_fail >= 0) {
-            for (int64_t bb = b_fail; bb < n_sub; ++bb) {
-                HostBlock &h = hb[bb % RING];
-                if (bb == b_fail && b_fail_finished) continue;
-                if (!(bb == b_fail && b_fail_submitted))
-                    if (submit_b(c, h, p, sl) != LDW_OK) break;
-                if (finish_block(c, h, p, sl) != LDW_OK) break;
-                c->links.blk_cursor += items[(size_t)bb].nseg;
-                lr_stream_push(c, c->stream, sl.lr_count, c->links.blk_cursor);
-            }
-        }
-        set_error("%s", fail_msg.c_str());
-        return fail_rc;
-    }
-    const double t_loop = now0();
+                Clock::us(t_enter, t_joined), Clock::us(t_joined, t_begun), Clock::us(t_begun, t_sized), Clock::us(t_sized, t_queued), Clock::us(t_queued, t_probed), Clock::us(t_probed, t_planned));
+    if (loop.run(probes) != LDW_OK) return loop.drain_after_failure();
+    const Clock::Point t_loop = Clock::now();
     const int rc_end = ldw_links_end(c);
-    if (host_timing)
-        fprintf(stderr, "[ldw host us] item loop %.0f  links_end %.0f  whole call %.0f\n", t_loop - t_planned, now0() - t_loop, now0() - t_enter);
-    if (host_timing)
-        fprintf(stderr, "[ldw host us/item] submit_b %.1f  wait for the helper's prep %.1f  submit_a (incl. that wait) %.1f  finish (incl. wait) %.1f  items %lld (blocks %lld)\n", th[0] / nitems, th[1] / nitems,
-                th[2] / nitems, th[3] / nitems, (long long)nitems, (long long)nblocks);
+    if (host_timing) {
+        const double n = (double)loop.nitems;
+        fprintf(stderr, "[ldw host us] item loop %.0f  links_end %.0f  whole call %.0f\n", Clock::us(t_planned, t_loop), Clock::us(t_loop, Clock::now()), Clock::us(t_enter, Clock::now()));
+        fprintf(stderr, "[ldw host us/item] submit_b %.1f  wait for the helper's prep %.1f  submit_a (incl. that wait) %.1f  finish (incl. wait) %.1f  items %lld (blocks %lld)\n", loop.th[0] / n, loop.th[1] / n,
+                loop.th[2] / n, loop.th[3] / n, (long long)loop.nitems, (long long)nblocks);
+    }
     return rc_end;
 }
 
@@ -788,8 +404,7 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
         const std::vector<int32_t> &Ph = c->meta.h_POS;
         for (int64_t b = 0; b < nblocks; ++b) {
             const int32_t fs = blocks[b * 4 + 0], fe = blocks[b * 4 + 1], ts = blocks[b * 4 + 2], te = blocks[b * 4 + 3];
-            LDW_REQUIRE(fs >= 1 && fe >= fs && fe <= c->L && ts >= 1 && te >= ts && te <= c->L, LDW_ERR_ARG, "block %lld = (%d,%d,%d,%d) outside 1..%lld", (long long)b, fs, fe,
-                        ts, te, (long long)c->L);
+            if (int rc = check_block(c, blocks, b)) return rc;
             if (ts > fe && 2 * sr_dist < c->meta.g) {   // (as below: ranges further apart than sr_dist directly and across the origin)
                 const double pf_min = Ph[(size_t)fs - 1], pf_max = Ph[(size_t)fe - 1], pt_min = Ph[(size_t)ts - 1], pt_max = Ph[(size_t)te - 1];
                 if (pt_min - pf_max > sr_dist && pf_min + c->meta.g - pt_max > sr_dist) continue;
@@ -842,8 +457,7 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
     int64_t n_filled = 0;
     for (int64_t b = 0; b < nblocks; ++b) {
         const int32_t fs = blocks[b * 4 + 0], fe = blocks[b * 4 + 1], ts = blocks[b * 4 + 2], te = blocks[b * 4 + 3];
-        LDW_REQUIRE(fs >= 1 && fe >= fs && fe <= c->L && ts >= 1 && te >= ts && te <= c->L, LDW_ERR_ARG, "block %lld = (%d,%d,%d,%d) outside 1..%lld", (long long)b, fs, fe,
-                    ts, te, (long long)c->L);
+        if (int rc = check_block(c, blocks, b)) return rc;
         if (ts > fe && 2 * sr_dist < c->meta.g) {   // disjoint ranges, to side after the from side: no pair within sr_dist directly or across the origin?
             const double pf_min = P[(size_t)fs - 1], pf_max = P[(size_t)fe - 1], pt_min = P[(size_t)ts - 1], pt_max = P[(size_t)te - 1];
             if (pt_min - pf_max > sr_dist && pf_min + c->meta.g - pt_max > sr_dist) continue;

@@ -13,7 +13,7 @@ The constants the cases sit on, restated as plain numbers (a change there: revis
   NBINS = 4096             ldw_internal.h: buckets of the level-1 histogram; mi_bucket (ldw_epi.h) is restated in ``_bucket``
   margin 10                ldw_mi_items.inc, update_guess: the guess a block leaves while fewer than three thresholds of its kind are known
   0.007                    ldw_mi_items.inc, speculation_pays: blocks speculate when lr_retain_links < 0.007 lr_links_approx
-  2048, square             ldw_mi.hip, span_candidate: what a block must be to join a span
+  2048, square             ldw_pass_plan.h, span_candidate: what a block must be to join a span
 
 Not reachable through the public surface (see the cases): span segments of different nt and a span segment that keeps no row (span_candidate
 takes square blocks of at least 2048 SNPs without one short-range pair, and `>=` keeps the maximum of every non-empty block); the guess of a
@@ -447,7 +447,7 @@ def test_speculation_guess_too_high_too_low_and_exact(engine, clones):
 # ------------------------------------------------------------------------------------------------
 # 8: spans
 # ------------------------------------------------------------------------------------------------
-S = 2048       # ldw_mi.hip, span_candidate: the smallest (square) block a span takes
+S = 2048       # ldw_pass_plan.h, span_candidate: the smallest (square) block a span takes
 
 
 @pytest.fixture(scope="module")

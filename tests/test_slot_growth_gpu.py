@@ -55,7 +55,7 @@ def _same(x, y, what):
             assert np.array_equal(a, b), (what, which)
 
 
-# (Ls, N, B, a span can form).  A block joins a span only from 2048 SNPs a side on (span_candidate, ldw_mi.hip): the blocks of 500 exercise the growth
+# (Ls, N, B, a span can form).  A block joins a span only from 2048 SNPs a side on (span_candidate, ldw_pass_plan.h): the blocks of 500 exercise the growth
 # of every buffer of ordinary items, the blocks of 2048 that of a span's.
 @pytest.mark.parametrize("Ls,N,B,spans", [(1500, 2100, 500, False), (6144, 2100, 2048, True)])
 def test_slot_buffers_grow_where_they_are_used(Ls, N, B, spans):
