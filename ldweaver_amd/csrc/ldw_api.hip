@@ -286,6 +286,7 @@ int ldw_ctx_create(int device, ldw_ctx **out) {
     ldw_ctx *c = guard.get();
     ldw::ctx_count(+1);
     c->device = device;
+    c->n_cu = prop.multiProcessorCount;
     c->knobs.prune = getenv("LDW_NO_PRUNE") == nullptr;
     LDW_HIP(c->stream.ensure(hipStreamNonBlocking));
     for (auto &e : c->ev) LDW_HIP(e.ensure());

@@ -49,9 +49,13 @@ struct ApxGemmArgs {
     // before the K loop; lane 0 counts it in *skip_ctr.  Null: every tile is computed.
     unsigned long long *skip_ctr;
     // with skip_ctr: k_apx_live_tiles writes the numbers of the wave tiles that have to be computed to tile_list (ty * ntx + tx, ntx =
-    // RFpad / 64) and their count to *n_live (zeroed by the caller); the GEMM then runs over that list, four tiles per workgroup
+    // RFpad / 64) and their count to *n_live (zeroed by the caller); the GEMM then runs over that list, four waves per workgroup (grid_wgs)
     uint32_t *tile_list;
     unsigned int *n_live;
+    // Host side only, with tile_list: workgroups of the list launch.  Wave w of the 4 grid_wgs waves walks the tiles w, w + 4 grid_wgs, ... of the
+    // list (apx_run_grid gives the default path's).  0: the worst case, (tiles + 3) / 4 — a wave then has at most one tile and the workgroups
+    // beyond the list leave at once, which is the launch as it was before the runs (LDW_NO_APX_RUNS=1).
+    int grid_wgs;
     // the same for the wider tables: pruning flags (PF_*, ldw_epi.h) of every ROW of the two row lists, 0 for padding rows.  A tile
     // whose to-rows are all of one kind and dead versus the (one) kind of its from-rows, or the other way round, is not computed.
     const uint8_t *rflag_t, *rflag_f;
@@ -68,6 +72,9 @@ int launch_pack_panel(ldw_ctx *c, const int32_t *rowlist, int Rpad, uint64_t *pa
                       uint64_t *panel2 = nullptr);
 int launch_apx_live_tiles(ldw_ctx *c, const ApxGemmArgs &P, hipStream_t st);   // P.skip_ctr set: before launch_gemm_apx, same stream
 int launch_gemm_apx(ldw_ctx *c, const ApxGemmArgs &P, hipStream_t st);
+// ApxGemmArgs::grid_wgs of the default path for a block of RTpad x RFpad rows: APX_RUNS_R workgroups per resident slot (two slots per CU of the
+// context's device) or what LDW_APX_GRID_WGS asks for, never more than the worst case; 0 under LDW_NO_APX_RUNS=1.  Both read per call.
+int apx_run_grid(const ldw_ctx *c, int RTpad, int RFpad);
 // the pair lists of A (filled by the approximate screen): exact sums, fp64 MI, emission
 int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, int64_t *sums, hipStream_t st);
 

@@ -237,6 +237,8 @@ int launch_pack_panel(ldw_ctx *c, const int32_t *rowlist, int Rpad, uint64_t *pa
 // consecutive 16-B pieces: coalesced), one macro step ahead; LDS only holds the 0xFF expansion table and the two digit
 // arrays.  Per MFMA k-step (32 positions) a lane expands 16 bits of each of its MT + NT rows through the table (2 look-ups
 // each) and masks them with the 16 digits of its lane half: 6 (MT + NT) VALU + 2 (MT + NT) ds_read_b64 for MT NT MFMAs.
+// r07: on the list launch a wave computes a RUN of tiles (ApxGemmArgs::grid_wgs): the workgroup stages LDS once, takes its one barrier, and every
+// wave loops tile by tile on its own, the next tile's first panel pieces requested before the epilogue of the current one.
 // ------------------------------------------------------------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -464,30 +466,45 @@ __global__ __launch_bounds__(256, WPS) void gemm_apx_kernel(ApxGemmArgs P) {
     uint8_t *sA = smem + APX_LUT_BYTES, *sB = sA + (size_t)P.M2 * 128;       // digits by position
     int2 *s_tab = reinterpret_cast<int2 *>(sB + (size_t)P.M2 * 128);  // threshold table (P.fuse)
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int TH = 32 * MT, TWd = 32 * NT;
-    int ty = 2 * blockIdx.y + (wave >> 1), tx = 2 * blockIdx.x + (wave & 1);
-    bool outside;
+    const int ntx = P.RFpad / TWd;
+    // The wave's run of tiles: entries k, k + step, ... < k_end of the live-tile list, or (2-D launch) the one tile of its place in the grid.
+    // t: the tile's number ty * ntx + tx, -1: the wave has none.  All wave-uniform: they live in scalar registers.
+    unsigned int k = 0, k_end = 0, step = 1;
+    int t;
     if (P.tile_list) {
-        // tile pruning (k_apx_live_tiles): the grid is 1-D over the list of the tiles that are left, four per workgroup; it is sized for
-        // the worst case, so the workgroups beyond the list leave at once, before anything is staged
-        const unsigned int n_live = *P.n_live;
+        // tile pruning (k_apx_live_tiles): the grid is 1-D over the list of the tiles that are left, four waves per workgroup; the workgroups
+        // beyond the list (the worst-case grid, a short list) leave at once, before anything is staged
+        const unsigned int n_live = *P.n_live, nw = gridDim.x * 4u, w = blockIdx.x * 4u + (unsigned int)wave;
         if (blockIdx.x * 4u >= n_live) return;
-        const unsigned int k = blockIdx.x * 4u + (unsigned int)wave;
-        outside = k >= n_live;
-        const int t = outside ? 0 : (int)P.tile_list[k];
-        const int ntx = P.RFpad / TWd;
-        ty = t / ntx;
-        tx = t - ty * ntx;
+#ifdef LDW_APX_RUNS_CONTIG   // measurement only (same results): a run of consecutive entries per wave instead of every nw-th
+        const unsigned int base = n_live / nw, rem = n_live % nw;
+        k = w * base + (w < rem ? w : rem);
+        k_end = k + base + (w < rem ? 1u : 0u);
+#else
+        // every nw-th entry: the waves in flight cover ONE window of the list that moves along it, as the dispatch order of the one-tile launch
+        // does — neighbouring waves share their to-rows, the window's panel rows stay in L2
+        k = w;
+        k_end = n_live;
+        step = nw;
+#endif
+        t = k < k_end ? (int)P.tile_list[k] : -1;
     } else {
-        outside = ty * TH >= P.RTpad || tx * TWd >= P.RFpad || (P.lower_only && tx * TWd + TWd - 1 < ty * TH);
+        auto outside = [&](int ty, int tx) { return ty * TH >= P.RTpad || tx * TWd >= P.RFpad || (P.lower_only && tx * TWd + TWd - 1 < ty * TH); };
+        const int ty0 = 2 * (int)blockIdx.y, tx0 = 2 * (int)blockIdx.x;
+        // (a diagonal block: the workgroups wholly above the diagonal — about half the grid — leave before they stage anything)
+        if (outside(ty0, tx0) && outside(ty0, tx0 + 1) && outside(ty0 + 1, tx0) && outside(ty0 + 1, tx0 + 1)) return;
+        const int ty = ty0 + (wave >> 1), tx = tx0 + (wave & 1);
+        t = outside(ty, tx) ? -1 : ty * ntx + tx;
     }
+    // staged ONCE per workgroup, whatever the length of its waves' runs
     if (P.fuse)
         for (int i = tid; i < P.tab_nb * P.tab_nb; i += 256) s_tab[i] = P.tab[i];
     {
         uint64_t e = 0;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) e |= ((tid >> k) & 1) ? (0xFFull << (8 * k)) : 0ull;
+        for (int k8 = 0; k8 < 8; ++k8) e |= ((tid >> k8) & 1) ? (0xFFull << (8 * k8)) : 0ull;
         lutFF[tid] = e;
         const int n16 = P.M2 * 8;   // 16-byte pieces per digit array
         for (int i = tid; i < n16; i += 256) {
@@ -495,22 +512,35 @@ __global__ __launch_bounds__(256, WPS) void gemm_apx_kernel(ApxGemmArgs P) {
             reinterpret_cast<uint4 *>(sB)[i] = reinterpret_cast<const uint4 *>(P.dig_b)[i];
         }
     }
-    __syncthreads();
-    if (outside) return;
+    __syncthreads();   // the only barrier: none inside the tile loop
+    if (t < 0) return;
     const int frow = lane & 31, fh = lane >> 5;
     const int64_t sta = (int64_t)P.RTpad * 2, stb = (int64_t)P.RFpad * 2;
-    {
-        const apx_u32x4 *pa[MT], *pb[NT];   // (pieces of the scaled panel: k_pack_panel)
+    // Pieces of the scaled panel (k_pack_panel).  ONE pointer per side — the lane's piece of the tile's first row at macro step 0; the MFMA tile 32 i is
+    // an immediate offset (32 rows of 2 pieces of 16 bytes) — so that the next tile's addressing costs the epilogue four registers, not twelve.
+    // (A wave-uniform base with a 32-bit lane offset would cost none: hipcc 7.2's register allocator crashes on it under the iterative-ilp scheduler.)
+    const uint8_t *base_t, *base_f;
+    const unsigned int lane_off = (unsigned int)(frow * 2 + fh) * 16u;
+    auto piece = [&](const uint8_t *base, int64_t macro_step_bytes, int i) {
+        return *reinterpret_cast<const apx_u32x4 *>(base + macro_step_bytes + 1024 * i);
+    };
+    apx_u32x4 wa[MT], wb[NT], na[MT], nb[NT];
+    // tile (ty, tx): its place in the panels and the request for its first pieces
+    auto open_tile = [&](int ty, int tx) {
+        base_t = reinterpret_cast<const uint8_t *>(P.panel_t) + (int64_t)ty * TH * 32 + lane_off;
+        base_f = reinterpret_cast<const uint8_t *>(P.panel_f) + (int64_t)tx * TWd * 32 + lane_off;
 #pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int rt = ty * TH + 32 * i + frow;
-            pa[i] = reinterpret_cast<const apx_u32x4 *>(P.panel_t) + ((int64_t)rt * 2 + fh);
-        }
+        for (int i = 0; i < MT; ++i) na[i] = piece(base_t, 0, i);
 #pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int rf = tx * TWd + 32 * i + frow;
-            pb[i] = reinterpret_cast<const apx_u32x4 *>(P.panel_f) + ((int64_t)rf * 2 + fh);
-        }
+        for (int i = 0; i < NT; ++i) nb[i] = piece(base_f, 0, i);
+    };
+    const uint8_t *lut_bytes = smem;
+    int ty = t / ntx, tx = t - ty * ntx;
+    open_tile(ty, tx);
+    for (;;) {
+        // the next tile of the run, asked for now and looked at after the K loop
+        k += step;
+        const int t_next = k < k_end ? (int)P.tile_list[k] : -1;
         v16i acc[MT][NT];
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -518,12 +548,6 @@ __global__ __launch_bounds__(256, WPS) void gemm_apx_kernel(ApxGemmArgs P) {
             for (int j = 0; j < NT; ++j)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
-        apx_u32x4 wa[MT], wb[NT], na[MT], nb[NT];
-        const uint8_t *lut_bytes = smem;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) na[i] = pa[i][0];
-#pragma unroll
-        for (int i = 0; i < NT; ++i) nb[i] = pb[i][0];
         for (int m = 0; m < P.M2; ++m) {
 #pragma unroll
             for (int i = 0; i < MT; ++i) wa[i] = na[i];
@@ -531,15 +555,19 @@ __global__ __launch_bounds__(256, WPS) void gemm_apx_kernel(ApxGemmArgs P) {
             for (int i = 0; i < NT; ++i) wb[i] = nb[i];
             if (m + 1 < P.M2) {
 #pragma unroll
-                for (int i = 0; i < MT; ++i) na[i] = pa[i][(int64_t)(m + 1) * sta];
+                for (int i = 0; i < MT; ++i) na[i] = piece(base_t, (int64_t)(m + 1) * sta * 16, i);
 #pragma unroll
-                for (int i = 0; i < NT; ++i) nb[i] = pb[i][(int64_t)(m + 1) * stb];
+                for (int i = 0; i < NT; ++i) nb[i] = piece(base_f, (int64_t)(m + 1) * stb * 16, i);
             }
             // FINE: one block exponent per k-step; k-step kk = positions 128 m + 32 kk .. + 31 (k_pack_panel interleaves the panel words
             // accordingly), lane half fh holds 16 of them.  Coarse (the weights' dynamic range within 128 positions is small: clonal
             // data): one exponent per macro step, k-step kk = bits 16 kk of the plain words 0 and 1 — 4 % faster (0.517 vs 0.538 ms).
-            const int4 sh4 = reinterpret_cast<const int4 *>(P.shift)[m];   // (wave-uniform: one scalar load per macro step)
-            const int shk[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
+            // (wave-uniform: one scalar load per macro step.  Read through the constant address space — nothing writes the shifts while the kernel runs —
+            // because the stores of the previous tile's epilogue now precede the load, and a load they might alias becomes a VECTOR load with a wait
+            // for everything in flight, the next step's panel pieces included: +6 % on the kernel)
+            typedef const __attribute__((address_space(4))) v4i *shift_ptr;
+            const v4i sh4 = ((shift_ptr)(uintptr_t)P.shift)[m];
+            const int shk[4] = {sh4[0], sh4[1], sh4[2], sh4[3]};
             const uint8_t *dA = sA + m * 128 + fh * (FINE ? 16 : 64), *dB = sB + m * 128 + fh * (FINE ? 16 : 64);
             auto kstep = [&](auto KKc) {
                 constexpr int kk = decltype(KKc)::value;
@@ -569,7 +597,17 @@ __global__ __launch_bounds__(256, WPS) void gemm_apx_kernel(ApxGemmArgs P) {
             kstep(std::integral_constant<int, 2>{});
             kstep(std::integral_constant<int, 3>{});
         }
-        apx_gemm_epilogue<MT, NT>(P, acc, ty, tx, lane, s_tab, reinterpret_cast<uint8_t *>(s_tab + 64 * 64) + wave * 256);
+        // the first pieces of the next tile are on their way while the epilogue tests and stores this one (na / nb are free after the last macro step)
+        const int ty_next = t_next / ntx, tx_next = t_next - ty_next * ntx;
+        if (t_next >= 0) open_tile(ty_next, tx_next);
+        // (the empty statement makes the offset a value of THIS pass of the loop: the epilogue's sixteen LDS addresses are then made here, per tile, as
+        // before; hoisted out of the tile loop they lived through the K loop and two registers spilled)
+        int bt_off = wave * 256;
+        asm volatile("" : "+s"(bt_off));
+        apx_gemm_epilogue<MT, NT>(P, acc, ty, tx, lane, s_tab, reinterpret_cast<uint8_t *>(s_tab + 64 * 64) + bt_off);
+        if (t_next < 0) break;
+        ty = ty_next;
+        tx = tx_next;
     }
 }
 
@@ -587,9 +625,11 @@ int launch_gemm_apx(ldw_ctx *c, const ApxGemmArgs &P, hipStream_t st) {
     const size_t lds = APX_LUT_BYTES + (size_t)P.M2 * 256 + (P.fuse ? (size_t)P.tab_nb * P.tab_nb * 8 + 1024 : 0);
     LDW_REQUIRE(lds <= 65536, LDW_ERR_ARG, "launch_gemm_apx: %d positions do not fit the LDS digit arrays", P.M2 * 128);
     LDW_REQUIRE(!P.fuse || (P.tab_nb == 64 && P.bin_t && P.bin_f && P.tab && P.clean), LDW_ERR_ARG, "launch_gemm_apx: bad table arguments");
-    if (P.skip_ctr) {
-        LDW_REQUIRE(P.fuse && P.tile_list && P.n_live && P.RFpad % 64 == 0, LDW_ERR_ARG, "launch_gemm_apx: bad pruning arguments");
-        const int tiles = (P.RTpad / (32 * APX_MT)) * (P.RFpad / 64), g = (tiles + 3) / 4;   // (the list is made by launch_apx_live_tiles)
+    LDW_REQUIRE(!P.skip_ctr || (P.fuse && P.tile_list), LDW_ERR_ARG, "launch_gemm_apx: bad pruning arguments");
+    if (P.tile_list) {   // (the list is made by launch_apx_live_tiles, or by the caller: ldw_debug_apx_gemm_list)
+        LDW_REQUIRE(P.n_live && P.RFpad % 64 == 0 && P.grid_wgs >= 0, LDW_ERR_ARG, "launch_gemm_apx: bad tile list arguments");
+        const int tiles = (P.RTpad / (32 * APX_MT)) * (P.RFpad / 64), worst = (tiles + 3) / 4;
+        const int g = P.grid_wgs > 0 ? P.grid_wgs : worst;
         if (P.fine) hipLaunchKernelGGL((gemm_apx_kernel<APX_MT, 2, true, APX_WPS>), dim3((unsigned)g), dim3(256), lds, st, P);
         else hipLaunchKernelGGL((gemm_apx_kernel<APX_MT, 2, false, APX_WPS>), dim3((unsigned)g), dim3(256), lds, st, P);
     } else {
@@ -616,6 +656,20 @@ int launch_gemm_apx(ldw_ctx *c, const ApxGemmArgs &P, hipStream_t st) {
         }
     }
     return LDW_OK;
+}
+
+// Workgroups per resident slot of the list launch (two slots per CU: APX_WPS waves per SIMD).  1 would be fully persistent: fewest turnovers, but the
+// main stream's short kernels get onto a CU only where a GEMM workgroup retires.  Chosen by the overlapped pass's time: profiles/r07_apx_tile_runs.txt.
+constexpr int APX_RUNS_R = 8;
+
+int apx_run_grid(const ldw_ctx *c, int RTpad, int RFpad) {
+    if (getenv("LDW_NO_APX_RUNS") != nullptr) return 0;   // (read per call: the tests switch it)
+    if (const char *e = getenv("LDW_APX_GRID_WGS")) {
+        const int k = atoi(e);
+        if (k > 0) return k;
+    }
+    const int worst = ((RTpad / (32 * APX_MT)) * (RFpad / 64) + 3) / 4;
+    return std::max(1, std::min(worst, APX_RUNS_R * APX_WPS * std::max(c->n_cu, 1)));
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -160,7 +160,19 @@ int ldw_debug_rows(ldw_ctx *c, int32_t *row0_out, uint32_t *slot_meta_out, int64
     return LDW_OK;
 }
 
+// grid_wgs < 0: the 2-D launch (ldw_debug_apx_gemm); > 0: the list launch over a list of every tile that holds an entry of `out`, with that grid
+static int debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int grid_wgs, int32_t *out);
+
 int ldw_debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int32_t *out) {
+    return debug_apx_gemm(c, rows_t, nrt, rows_f, nrf, -1, out);
+}
+
+int ldw_debug_apx_gemm_list(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int grid_wgs, int32_t *out) {
+    LDW_REQUIRE(grid_wgs > 0 && grid_wgs <= 65536, LDW_ERR_ARG, "ldw_debug_apx_gemm_list: grid of %d workgroups outside 1..65536", grid_wgs);
+    return debug_apx_gemm(c, rows_t, nrt, rows_f, nrf, grid_wgs, out);
+}
+
+static int debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int grid_wgs, int32_t *out) {
     if (int rc = check_gpu(c)) return rc;
     if (int rc = join_prepare(c)) return rc;
     if (int rc = ensure_rows(c)) return rc;
@@ -172,7 +184,16 @@ int ldw_debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t
     std::vector<int32_t> rl((size_t)RTpad + RFpad, (int32_t)c->rows.R);   // padding -> the all-zero row R
     std::copy(rows_t, rows_t + nrt, rl.begin());
     std::copy(rows_f, rows_f + nrf, rl.begin() + RTpad);
-    DevBuf d_rl, d_pt, d_pf, d_G;
+    DevBuf d_rl, d_pt, d_pf, d_G, d_list;
+    std::vector<uint32_t> list(1, 0u);   // [0] the count, then the tiles (128 to-rows x 64 from-rows) that hold a row of the caller's
+    if (grid_wgs > 0) {
+        const int ntx = RFpad / 64;
+        for (int ty = 0; ty * 128 < nrt; ++ty)
+            for (int tx = 0; tx * 64 < nrf; ++tx) list.push_back((uint32_t)(ty * ntx + tx));
+        list[0] = (uint32_t)(list.size() - 1);
+        if (int rc = d_list.reserve(list.size() * 4)) return rc;
+        LDW_HIP(hipMemcpyAsync(d_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
     if (int rc = d_rl.reserve(rl.size() * 4)) return rc;
     if (int rc = d_pt.reserve((size_t)M2 * RTpad * 32)) return rc;
     if (int rc = d_pf.reserve((size_t)M2 * RFpad * 32)) return rc;
@@ -192,6 +213,11 @@ int ldw_debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t
     P.shift = c->apx.apx_shift.as<int32_t>();
     P.G = d_G.as<int32_t>();
     P.fine = c->apx.apx_fine ? 1 : 0;
+    if (grid_wgs > 0) {   // (no table fusion: every listed tile is stored)
+        P.n_live = d_list.as<unsigned int>();
+        P.tile_list = d_list.as<uint32_t>() + 1;
+        P.grid_wgs = grid_wgs;
+    }
     if (int r2 = launch_gemm_apx(c, P, c->stream)) return r2;
     std::vector<int32_t> h((size_t)RTpad * RFpad);
     LDW_HIP(hipMemcpyAsync(h.data(), d_G.p, h.size() * 4, hipMemcpyDeviceToHost, c->stream));

@@ -305,6 +305,7 @@ struct HostClock {
 // come first and go last.  ldw_ctx_destroy drains them before it deletes.
 struct ldw_ctx {
     int device = 0;
+    int n_cu = 0;                    // compute units of the device (hipDeviceProp_t::multiProcessorCount): sizes the approximate GEMM's list launch
     ldw::Stream stream;              // the main stream: the library's own, or the caller's (ldw_ctx_set_stream: adopted, never destroyed here)
     ldw::Stream copy_stream, gemm_stream;   // pipelined block staging (ensure_streams): host prep of block i+1 overlaps the GPU work of block i
     ldw::Stream lr_st;               // the streaming lr_links.tsv writer's (ensure_streams)

@@ -674,6 +674,7 @@ int launch_block_apx(ldw_ctx *c, const DevPtrs &D, int64_t nf, int64_t nt, int R
                 if (P.skip_ctr) {
                     P.tile_list = B.tile_list;
                     P.n_live = B.n_live;
+                    P.grid_wgs = apx_run_grid(c, RTpad, RFpad);   // every wave walks a run of the list
                     P.rflag_t = rflag_t;
                     P.rflag_f = rflag_f;
                 }

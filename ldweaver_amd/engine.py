@@ -199,12 +199,16 @@ class Engine:
         L.check(L.lib().ldw_debug_rows(self._ctx, L.ptr(row0), L.ptr(meta), self.L + 1))
         return row0, meta
 
-    def debug_apx_gemm(self, rows_t, rows_f):
-        """gemm_apx_kernel over the given indicator rows: int32 [len(rows_t), len(rows_f)] sums of the dual-digit weights in units of 2^e_last."""
+    def debug_apx_gemm(self, rows_t, rows_f, grid_wgs: int | None = None):
+        """gemm_apx_kernel over the given indicator rows: int32 [len(rows_t), len(rows_f)] sums of the dual-digit weights in units of 2^e_last.
+        grid_wgs: through the kernel's list launch with that many workgroups (ldw_debug_apx_gemm_list) instead of the 2-D launch."""
         rt = np.ascontiguousarray(rows_t, dtype=np.int32)
         rf = np.ascontiguousarray(rows_f, dtype=np.int32)
         out = np.zeros((len(rt), len(rf)), dtype=np.int32)
-        L.check(L.lib().ldw_debug_apx_gemm(self._ctx, L.ptr(rt), len(rt), L.ptr(rf), len(rf), L.ptr(out)))
+        if grid_wgs is None:
+            L.check(L.lib().ldw_debug_apx_gemm(self._ctx, L.ptr(rt), len(rt), L.ptr(rf), len(rf), L.ptr(out)))
+        else:
+            L.check(L.lib().ldw_debug_apx_gemm_list(self._ctx, L.ptr(rt), len(rt), L.ptr(rf), len(rf), int(grid_wgs), L.ptr(out)))
         return out
 
     def debug_screen_bound(self, kind: int, na: int, nb: int, g, pa, pb, pX, pY, rr, params, masks=None):
