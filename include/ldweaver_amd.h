@@ -731,6 +731,24 @@ int ldw_plot_tree(ldw_ctx *ctx, int32_t W, int32_t H, const int32_t *panel, cons
  * metadata and the link tables of the context stay as they are. */
 int ldw_nj_tree(ldw_ctx *ctx, const double *dist, int64_t n, int32_t *parent_out, double *length_out);
 
+/* Bootstrap support of that tree.  mult[B][L] (HOST, a row per replicate): how often replicate b holds SNP column a of the resident
+ * alignment, 0 <= mult <= 63 and every row's sum < 2^27 — L draws with replacement for the bootstrap proper, 0 / 1 for a jackknife, any other weighting.
+ * Replicate b's distance is d_b(i, j) = the sum of mult[b][a] over the columns a at which sequences i and j differ (five-state rule), its tree the tree
+ * ldw_nj_tree would build of that matrix, bit for bit.  parent_out / length_out [2n-2]: the tree of the alignment itself, exactly ldw_nj_tree's.
+ * support_out[2n-2]: for a join node u = n .. 2n-4 (the n - 3 internal edges of the unrooted tree) the number of replicates whose tree has a join node
+ * that splits the tips into the same two sets as u does; -1 at the tips and at the root.  rep_parent_out [B][2n-2] and rep_length_out [B][2n-2] (each
+ * may be NULL): the replicates' trees, for tests and for callers who build a consensus of their own.  Splits are compared on the device by a pair of
+ * 64-bit sums of per-tip keys: two different splits are taken for one with probability at most B (n-3)^2 2^-128.
+ * The replicates' trees are joined R side by side (R = min(B, 16, 4 GiB / 8 n^2), at least 1; LDW_NJ_BATCH=k in the environment, read at every call,
+ * forces R = k: a test hook); no result depends on R.  Nothing is read back between the joins.  ldw_ctx_last_timing afterwards, summed over the
+ * replicates: [0] joins, [1] multiplicities + digits + GEMMs + fills, [2] split sums + look-ups, [3] their sum.
+ * Refused before any join, the context staying usable — LDW_ERR_STATE: no alignment resident.  LDW_ERR_ARG: n not the alignment's sequence count,
+ * n < 3, B < 1, mult or one of the three first outputs NULL, a multiplicity outside 0..63, a row sum >= 2^27.  The call holds the Hamming stage's
+ * working memory, R n x n x 8 bytes and, with a replicate output, B (2n-2) x 12 bytes on the device and gives them back; the alignment, the weights,
+ * the SNP metadata and the link tables of the context stay as they are. */
+int ldw_nj_bootstrap(ldw_ctx *ctx, const int32_t *mult, int64_t B, int64_t n, int32_t *parent_out, double *length_out, int32_t *support_out,
+                     int32_t *rep_parent_out, double *rep_length_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

@@ -15,7 +15,7 @@ _EXPORTS = {
     "create_tanglegram": "tanglegram",
     "LDWeaver": "driver", "cleanup": "driver",
     "view_tree": "tree", "read_newick": "tree", "midpoint_root": "tree", "ladderize": "tree",
-    "nj_tree": "tree", "write_newick": "tree",
+    "nj_tree": "tree", "write_newick": "tree", "bootstrap_multiplicities": "tree",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -494,6 +494,24 @@ class Engine:
         L.check(L.lib().ldw_nj_tree(self._ctx, L.ptr(d), n, L.ptr(parent), L.ptr(length)))
         return parent, length
 
+    def nj_bootstrap(self, mult, want_trees=False):
+        """Bootstrap support of ``nj_tree()`` (ldw_nj_bootstrap).  ``mult``: int32 (B, L), a row per replicate, how often the replicate holds
+        each SNP column of the resident alignment (0..63; ``tree.bootstrap_multiplicities`` draws them).  Returns (parent, length, support): the tree of
+        ``nj_tree()`` and, int32 [2n - 2], for every join node n .. 2n-4 the number of replicates whose tree has the same split of the tips, -1 at the tips
+        and the root; with ``want_trees`` also (rep_parent int32 (B, 2n - 2), rep_length float64 (B, 2n - 2)), the replicates' trees.  ``last_timing()``
+        afterwards, summed over the replicates: ``gemm_ms`` the joins, ``epilogue_ms`` digits + GEMMs + fills, ``select_ms`` split sums + look-ups."""
+        m = L.as_c(mult, np.int32)
+        if m.ndim != 2 or m.shape[1] != self.L:
+            raise ValueError(f"mult must be (replicates, {self.L} SNP columns), not {m.shape}")
+        B, n = int(m.shape[0]), int(self.N)
+        w = max(2 * n - 2, 1)
+        parent, length, support = np.empty(w, dtype=np.int32), np.empty(w, dtype=np.float64), np.empty(w, dtype=np.int32)
+        rp = np.empty((B, w), dtype=np.int32) if want_trees else None
+        rl = np.empty((B, w), dtype=np.float64) if want_trees else None
+        # (an empty array has no address to hand over: the library then answers as it does for a null pointer, after its own checks of the state)
+        L.check(L.lib().ldw_nj_bootstrap(self._ctx, L.ptr(m) if m.size else None, B, n, L.ptr(parent), L.ptr(length), L.ptr(support), L.ptr(rp), L.ptr(rl)))
+        return (parent, length, support, rp, rl) if want_trees else (parent, length, support)
+
     def hamming_counts(self, thresh: int, tile0: int, tile1: int) -> np.ndarray:
         """Contribution of the strip of 128-sequence row tiles [tile0, tile1) to the neighbour counts n_j (all j)."""
         out = np.zeros(self.N, dtype=np.int64)

@@ -37,6 +37,8 @@ class Tree:
     tip_node: np.ndarray    # int32 [tips]: the node of every tip
     child_ptr: np.ndarray   # int32 [nodes + 1]: the children of v are child_idx[child_ptr[v] : child_ptr[v + 1]], in order
     child_idx: np.ndarray   # int32 [nodes - 1]
+    support: np.ndarray = None   # int32 [nodes], or None: how many bootstrap replicates have the branch to the parent; -1 where there is no count
+    n_replicates: int = None     # the replicates ``support`` counts, where the tree knows (a Newick file does not say)
 
     @property
     def n_nodes(self) -> int:
@@ -63,9 +65,10 @@ class Tree:
         return d
 
 
-def _build(root, kids, elen, tip_of, tip_label) -> Tree:
+def _build(root, kids, elen, tip_of, tip_label, esup=None, n_replicates=None) -> Tree:
     """The Tree of the rooted structure ``kids`` (node -> its children in order; any hashable ids), ``elen(child)`` the length of the branch above a
-    child, ``tip_of`` node -> tip index (absent or -1: internal): renumbered depth-first without recursion."""
+    child, ``tip_of`` node -> tip index (absent or -1: internal): renumbered depth-first without recursion.  ``esup(child)``, where given: the support
+    of that branch (-1: none)."""
     order, parent = [], []
     stack = [(root, -1)]
     while stack:
@@ -77,10 +80,13 @@ def _build(root, kids, elen, tip_of, tip_label) -> Tree:
             stack.append((u, me))
     n = len(order)
     length = np.zeros(n, dtype=np.float64)
+    support = None if esup is None else np.full(n, -1, dtype=np.int32)
     tip_node = np.full(len(tip_label), -1, dtype=np.int32)
     for me, v in enumerate(order):
         if me:
             length[me] = elen(v)
+            if esup is not None:
+                support[me] = esup(v)
         t = tip_of(v)
         if t >= 0:
             tip_node[t] = me
@@ -89,7 +95,7 @@ def _build(root, kids, elen, tip_of, tip_label) -> Tree:
     ptr = np.zeros(n + 1, dtype=np.int32)
     ptr[1:] = np.cumsum(cnt)
     idx = (np.argsort(par[1:], kind="stable") + 1).astype(np.int32) if n > 1 else np.zeros(0, dtype=np.int32)   # ascending node = the order given
-    return Tree(par, length, list(tip_label), tip_node, ptr, idx)
+    return Tree(par, length, list(tip_label), tip_node, ptr, idx, support, n_replicates if support is not None else None)
 
 
 # ---- Newick ---------------------------------------------------------------------------------------------------------------------------------------
@@ -142,6 +148,7 @@ def parse_newick(data: bytes) -> Tree:
         return 0.0, i
 
     parent, length, labels, is_tip = [], [], [], []
+    support = {}                                # internal node -> the plain non-negative integer it is labelled with
     stack, expect, i = [], True, 0
     while True:
         i = skip(i)
@@ -174,7 +181,10 @@ def parse_newick(data: bytes) -> Tree:
             if not stack:
                 raise ValueError(f"Newick: ')' without '(' at byte {i}")
             node = stack.pop()
-            _, j = label(i + 1)                 # internal labels are read and ignored
+            k = skip(i + 1)
+            lab, j = label(k)                   # an internal label is a support count where it is a plain integer, else read and ignored
+            if node and lab.isdigit() and data[k] != 0x27 and int(lab) < 2 ** 31:
+                support[node] = int(lab)
             length[node], i = branch(j)
         elif c == 0x3B:                         # ;
             if stack:
@@ -198,13 +208,19 @@ def parse_newick(data: bytes) -> Tree:
     ptr = np.zeros(n_nodes + 1, dtype=np.int32)
     ptr[1:] = np.cumsum(cnt)
     idx = (np.argsort(par[1:], kind="stable") + 1).astype(np.int32)
-    return Tree(par, ln, tip_label, np.asarray(tips, dtype=np.int32), ptr, idx)
+    sup = None
+    if support:
+        sup = np.full(n_nodes, -1, dtype=np.int32)
+        sup[list(support)] = list(support.values())
+    return Tree(par, ln, tip_label, np.asarray(tips, dtype=np.int32), ptr, idx, sup)
 
 
 def read_newick(path) -> Tree:
     """The first tree of a Newick file: nested parentheses, multifurcations, unquoted labels, 'quoted labels' with '' for a quote, ``:length`` in
-    decimal or exponent form (missing: 0.0), ``[comments]`` skipped, internal labels read and ignored, a closing ``;``.  Iterative: a caterpillar of
-    any depth parses.  Malformed text raises ValueError naming the byte offset; so do fewer than two tips and a repeated tip label."""
+    decimal or exponent form (missing: 0.0), ``[comments]`` skipped, a closing ``;``.  An internal label that is a plain non-negative integer (unquoted,
+    below 2^31, not at the root) is the support of the branch above its node and goes into ``support`` (-1 elsewhere; None when the file has no such
+    label); any other internal label is read and ignored.  Iterative: a caterpillar of any depth parses.  Malformed text raises ValueError naming the
+    byte offset; so do fewer than two tips and a repeated tip label."""
     with open(path, "rb") as fh:
         return parse_newick(fh.read())
 
@@ -221,9 +237,11 @@ def _newick_label(s: str) -> str:
 
 def write_newick(tree: Tree, path=None) -> str:
     """The tree as one line of Newick text, returned and, with ``path``, written there: children in their order, every branch length as
-    ``repr(float)`` (the shortest text that reads back as the same double), tip labels quoted where they need it, no internal labels, no length at
-    the root.  ``read_newick`` of the result has the same parent array, labels and lengths."""
+    ``repr(float)`` (the shortest text that reads back as the same double), tip labels quoted where they need it, no length at the root.  Internal
+    nodes are labelled with their support where the tree has one that is >= 0, as in ``)87:0.25``, and not otherwise.  ``read_newick`` of the result has
+    the same parent array, labels, lengths and support (a support array without a single count reads back as None)."""
     ptr, idx, ln = tree.child_ptr.tolist(), tree.child_idx.tolist(), tree.length.tolist()
+    sup = None if tree.support is None else tree.support.tolist()
     lab = {int(v): _newick_label(str(tree.tip_label[t])) for t, v in enumerate(tree.tip_node.tolist())}
     parts, stack = [], [(0, 0)]
     while stack:
@@ -236,6 +254,8 @@ def write_newick(tree: Tree, path=None) -> str:
             continue
         parts.append(")" if nk else lab[v])
         if v:
+            if nk and sup is not None and sup[v] >= 0:
+                parts.append(str(sup[v]))
             parts.append(":" + repr(float(ln[v])))
     text = "".join(parts) + ";\n"
     if path is not None:
@@ -268,14 +288,38 @@ def nj_clamp(parent: np.ndarray, length: np.ndarray) -> np.ndarray:
     return out
 
 
-def nj_tree(snp_dat=None, *, dist=None, labels=None, engine=None, alignment_resident=False, clamp_negative=True, per_site=False) -> Tree:
+def bootstrap_multiplicities(L: int, B: int, seed: int = 0) -> np.ndarray:
+    """The column multiplicities of B Felsenstein bootstrap replicates of an alignment of L SNP columns, int32 (B, L), every row adding up to L:
+    ``rng = np.random.default_rng(seed)`` and then, replicate after replicate, ``np.bincount(rng.integers(0, L, size=L), minlength=L)``."""
+    L, B = int(L), int(B)
+    if L < 1 or B < 0:
+        raise ValueError(f"bootstrap_multiplicities: {L} columns, {B} replicates")
+    rng = np.random.default_rng(seed)
+    out = np.zeros((B, L), dtype=np.int32)
+    for b in range(B):
+        out[b] = np.bincount(rng.integers(0, L, size=L), minlength=L)
+    return out
+
+
+def nj_tree(snp_dat=None, *, dist=None, labels=None, engine=None, alignment_resident=False, clamp_negative=True, per_site=False, bootstrap=0, seed=0,
+            multiplicities=None) -> Tree:
     """The neighbour-joining tree, built on the device, of ``snp_dat``'s sequences under the Hamming distance of the five-state rule (the number of
     SNP columns at which two sequences differ: what ``estimate_Hamming_distance_weights`` thresholds), or of ``dist``, a symmetric (n, n) float64
     matrix with a zero diagonal.  ``engine`` with ``alignment_resident=True``: the engine already holds the alignment (``snp_dat`` may then be None).
     Tips are labelled ``labels``, else ``snp_dat.seq_names``, else 1 .. n, in sequence order.  The tree is unrooted: its root is the trifurcation of
     the last three nodes, children in ascending node id (a join's: smaller id, larger id); ``midpoint_root`` roots it.  ``clamp_negative``: see
-    ``nj_clamp`` (``midpoint_root`` rejects negative branches).  ``per_site`` divides the lengths by the number of SNP columns.  Needs a GPU."""
+    ``nj_clamp`` (``midpoint_root`` rejects negative branches).  ``per_site`` divides the lengths by the number of SNP columns.  Needs a GPU.
+
+    ``bootstrap=B`` (B > 0) adds bootstrap support, computed on the device (``Engine.nj_bootstrap``): B replicates drawn by
+    ``bootstrap_multiplicities(L, B, seed)``, or the rows of ``multiplicities``, an int (B, L) array of column multiplicities 0..63 of your own.  The
+    tree then has ``support`` — per node the number of replicates whose tree has the branch above it, -1 at the tips and the root — and
+    ``n_replicates``.  A matrix has no columns to resample: with ``dist`` either argument raises ValueError."""
     from .engine import Engine
+    if bootstrap < 0:
+        raise ValueError("nj_tree: bootstrap must be >= 0")
+    want_support = bootstrap > 0 or multiplicities is not None
+    if dist is not None and want_support:
+        raise ValueError("nj_tree: bootstrap support needs an alignment: a distance matrix has no columns to resample")
     if dist is not None and (snp_dat is not None or alignment_resident):
         raise ValueError("nj_tree: pass either dist or an alignment")
     if dist is None and snp_dat is None and not alignment_resident:
@@ -286,6 +330,7 @@ def nj_tree(snp_dat=None, *, dist=None, labels=None, engine=None, alignment_resi
         raise ValueError("nj_tree: per_site needs an alignment")
     own = engine is None
     eng = Engine(0) if own else engine
+    support, n_rep = None, None
     try:
         if dist is not None:
             parent, length = eng.nj_tree(dist)
@@ -294,8 +339,15 @@ def nj_tree(snp_dat=None, *, dist=None, labels=None, engine=None, alignment_resi
                 if snp_dat.states is None:
                     raise ValueError("snp_dat.states is None (the alignment stayed on the device): pass its engine with alignment_resident=True")
                 eng.set_alignment(snp_dat.states)
-            parent, length = eng.nj_tree()
             n_snp = eng.L
+            if want_support:
+                mult = bootstrap_multiplicities(n_snp, bootstrap, seed) if multiplicities is None else np.asarray(multiplicities)
+                if mult.ndim != 2 or (bootstrap and mult.shape[0] != bootstrap):
+                    raise ValueError(f"nj_tree: multiplicities of shape {mult.shape} for bootstrap = {bootstrap}")
+                parent, length, support = eng.nj_bootstrap(mult)
+                n_rep = int(mult.shape[0])
+            else:
+                parent, length = eng.nj_tree()
     finally:
         if own:
             eng.close()
@@ -304,12 +356,12 @@ def nj_tree(snp_dat=None, *, dist=None, labels=None, engine=None, alignment_resi
         labels = names if 2 * len(names) - 2 == len(parent) else None
     if per_site:
         length = length / float(n_snp)
-    return tree_from_joins(parent, length, labels, clamp_negative)
+    return tree_from_joins(parent, length, labels, clamp_negative, support, n_rep)
 
 
-def tree_from_joins(parent, length, labels=None, clamp_negative=True) -> Tree:
+def tree_from_joins(parent, length, labels=None, clamp_negative=True, support=None, n_replicates=None) -> Tree:
     """The ``Tree`` of ``Engine.nj_tree``'s (parent, length): the root is node 2n - 3, the children of every node in ascending node id, the tips
-    labelled ``labels`` (default 1 .. n) in node order."""
+    labelled ``labels`` (default 1 .. n) in node order.  ``support``, where given, is ``Engine.nj_bootstrap``'s, per node of the joins."""
     parent, length = np.asarray(parent), np.asarray(length, dtype=np.float64)
     n = (len(parent) + 2) // 2
     labels = [str(k + 1) for k in range(n)] if labels is None else [str(x) for x in labels]
@@ -322,7 +374,8 @@ def tree_from_joins(parent, length, labels=None, clamp_negative=True) -> Tree:
     for v in range(root):
         kids[int(parent[v])].append(v)
     ln = length.tolist()
-    return _build(root, lambda v: kids[v], lambda v: ln[v], lambda v: v if v < n else -1, labels)
+    sup = None if support is None else np.asarray(support).tolist()
+    return _build(root, lambda v: kids[v], lambda v: ln[v], lambda v: v if v < n else -1, labels, None if sup is None else (lambda v: sup[v]), n_replicates)
 
 
 # ---- rooting and ordering ---------------------------------------------------------------------------------------------------------------------------
@@ -355,7 +408,8 @@ def midpoint_root(tree: Tree) -> Tree:
     """The tree rooted half way between its two most distant tips, in O(nodes): a = the tip farthest from tip 0, b = the tip farthest from a (ties:
     the lowest tip index of the file); the root lies on the path from a to b at half their distance from a.  Where that point is a node, the node
     becomes the root; otherwise its branch is split.  An old root left with two branches is removed and their lengths are added.  A node that
-    changes direction gets its old parent as its last child.  Negative lengths and a tree whose lengths are all zero raise ValueError."""
+    changes direction gets its old parent as its last child.  Negative lengths and a tree whose lengths are all zero raise ValueError.  ``support``
+    stays with its branch: both halves of a split branch keep the branch's, and the one branch made of the removed old root's two takes the larger."""
     ln = tree.length
     if np.any(ln[1:] < 0) or np.any(~np.isfinite(ln[1:])):
         raise ValueError("midpoint_root: the tree has a negative or non-finite branch length")
@@ -404,24 +458,34 @@ def midpoint_root(tree: Tree) -> Tree:
             return len_c if split[0] in (v, u) else len_p
         return lnl[v] if par[v] == u else lnl[u]
 
-    kids, up, stack = {}, {new_root: (-1, 0.0)}, [new_root]
+    supl = None if tree.support is None else tree.support.tolist()
+
+    def esup(v, u):                              # support belongs to the branch, whichever way it now points; both halves of the split branch keep it
+        if supl is None:
+            return -1
+        if split and n_old in (v, u):
+            return supl[split[0]]
+        return supl[v] if par[v] == u else supl[u]
+
+    kids, up, stack = {}, {new_root: (-1, 0.0, -1)}, [new_root]
     while stack:
         v = stack.pop()
         kids[v] = [u for u in nbrs(v) if u != up[v][0]]
         for u in kids[v]:
-            up[u] = (v, edge(v, u))
+            up[u] = (v, edge(v, u), esup(v, u))
             stack.append(u)
     old = 0
     if old != new_root and len(kids[old]) <= 1:  # the old root is left with two branches (or, a root of one child, with one): it goes
-        q, l_up = up[old]
+        q, l_up, s_up = up[old]
         if kids[old]:
             only = kids[old][0]
-            up[only] = (q, up[only][1] + l_up)
+            up[only] = (q, up[only][1] + l_up, max(up[only][2], s_up))   # one branch of the two: the larger support
             kids[q] = [only if x == old else x for x in kids[q]]
         else:
             kids[q] = [x for x in kids[q] if x != old]
     tip_of = {int(v): t for t, v in enumerate(tips.tolist())}
-    return _build(new_root, lambda v: kids[v], lambda v: up[v][1], lambda v: tip_of.get(v, -1), tree.tip_label)
+    return _build(new_root, lambda v: kids[v], lambda v: up[v][1], lambda v: tip_of.get(v, -1), tree.tip_label,
+                  None if supl is None else (lambda v: up[v][2]), tree.n_replicates)
 
 
 def ladderize(tree: Tree) -> Tree:
@@ -435,7 +499,9 @@ def ladderize(tree: Tree) -> Tree:
         c[par[v]] += c[v]
     tip_of = {int(v): t for t, v in enumerate(tree.tip_node.tolist())}
     lnl = tree.length.tolist()
-    return _build(0, lambda v: sorted(tree.children(v).tolist(), key=lambda u: c[u]), lambda v: lnl[v], lambda v: tip_of.get(v, -1), tree.tip_label)
+    supl = None if tree.support is None else tree.support.tolist()
+    return _build(0, lambda v: sorted(tree.children(v).tolist(), key=lambda u: c[u]), lambda v: lnl[v], lambda v: tip_of.get(v, -1), tree.tip_label,
+                  None if supl is None else (lambda v: supl[v]), tree.n_replicates)
 
 
 # ---- the reference's selection (R/preptrees.R:67-179) ---------------------------------------------------------------------------------------------------
@@ -650,7 +716,7 @@ def _text_width(s: str, sc: int) -> int:
 
 
 def tree_layout(tree: Tree, width: int, height: int, n_metadata: int = 0, n_alleles: int = 0, offset_metadata=None, offset_alleles=None, width_metadata=None,
-                width_alleles=None, band_labels=(), legends=(), thickness: int = 16) -> dict:
+                width_alleles=None, band_labels=(), legends=(), thickness: int = 16, support_min=None, n_replicates=None) -> dict:
     """Every rectangle of the figure (x, y, w, h in canvas pixels) and the bars of the tree.  Root at the top.  The margins: 20 text-scale pixels on top
     (the title), 4 below; left, room for the longest band label (at least width / 20); right, room for the widest legend (at least width / 10).  The tree
     panel is T pixels high, T = floor(available height / (1 + E)), E the larger lower end of the two groups of bands: the offsets and widths are
@@ -660,7 +726,10 @@ def tree_layout(tree: Tree, width: int, height: int, n_metadata: int = 0, n_alle
     groups raise ValueError.  Tip slot i of N (figure order) spans [i, i + 1) PW / N of the panel; a tip's x is the middle of its slot, a node's the
     midpoint of its first and last child; y = 0.5 + depth / max depth (T - 1) pixels; both rounded half up to 1/16 pixel.  Bars (1/16 pixel, relative
     to the panel): per branch [x - t/2, x + t/2) x [y parent, y), per internal node the connector [x first - t/2, x last + t/2) x [y - t/2, y + t/2).
-    Returns a dict: canvas, panel, bands (metadata then alleles), legend_xy, text_scale, bars, tip_order, node_x / node_y (1/16 pixel)."""
+    With ``support_min`` and ``n_replicates`` and a tree that has ``support``, every internal node whose support is >= support_min x n_replicates is
+    marked by a knob: a square of side 3 t centred on the node, one more bar each, appended after the bars above in node order.
+    Returns a dict: canvas, panel, bands (metadata then alleles), legend_xy, text_scale, bars, tip_order, node_x / node_y (1/16 pixel), support_nodes
+    (int32: the marked nodes)."""
     K = n_alleles
     if width_metadata is None:
         width_metadata = K / 200.0      # :183-186
@@ -738,13 +807,20 @@ def tree_layout(tree: Tree, width: int, height: int, n_metadata: int = 0, n_alle
             bars.append((X[v] - h0, Y[par[v]], X[v] + h1, Y[v]))
         if ptr[v + 1] > ptr[v]:
             bars.append((X[idx[ptr[v]]] - h0, Y[v] - h0, X[idx[ptr[v + 1] - 1]] + h1, Y[v] + h1))
+    marked = []
+    if tree.support is not None and support_min is not None and n_replicates:
+        need, sup = float(support_min) * float(n_replicates), tree.support.tolist()
+        marked = [v for v in range(n_nodes) if ptr[v + 1] > ptr[v] and sup[v] >= 0 and sup[v] >= need]
+        k0, k1 = (3 * thickness) // 2, 3 * thickness - (3 * thickness) // 2
+        bars += [(X[v] - k0, Y[v] - k0, X[v] + k1, Y[v] + k1) for v in marked]
     from .engine import Engine
     barr = np.zeros(len(bars), dtype=Engine.BAR)
     if bars:
         b = np.asarray(bars, dtype=np.int32)
         barr["x0"], barr["y0"], barr["x1"], barr["y1"] = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
     return dict(canvas=(W, H), panel=(left, top, PW, T), bands=np.asarray(bands, dtype=np.int32).reshape(-1, 4), legend_xy=legend_xy, text_scale=sc,
-                bars=barr, tip_order=order, node_x=np.asarray(X, dtype=np.int32), node_y=np.asarray(Y, dtype=np.int32))
+                bars=barr, tip_order=order, node_x=np.asarray(X, dtype=np.int32), node_y=np.asarray(Y, dtype=np.int32),
+                support_nodes=np.asarray(marked, dtype=np.int32))
 
 
 # ---- view_tree ------------------------------------------------------------------------------------------------------------------------------------------------
@@ -752,7 +828,7 @@ def tree_layout(tree: Tree, width: int, height: int, n_metadata: int = 0, n_alle
 def view_tree(tree_path=None, perform_midpoint_rooting=True, metadata_df=None, fasta_path=None, pos_file_path=None, links_df=None, lr_tophits_path=None,
               lr_annotated_links_path=None, sr_tophits_path=None, sr_annotated_links_path=None, ntop_links=10, from_=None, to=None, offset_metadata=None,
               offset_alleles=None, width_metadata=None, width_alleles=None, plot_save_path=None, plot_height=20, plot_width=15, *, engine=None,
-              want_canvas=False, dpi=300):
+              want_canvas=False, dpi=300, bootstrap=0, seed=0, support_min=0.7):
     """``view_tree`` (R/preptrees.R:45-215; ``from`` is spelled ``from_``).  The canvas has plot_width dpi x plot_height dpi pixels, at most 8192
     either way.  Returns a dict: ``tree`` (rooted and ladderized), ``tip_order``, ``pos_plot`` (the allele columns), ``metadata_columns``, ``alleles``
     / ``metadata`` (levels uint8 [bands, tips in figure order] and their values), ``layout`` (``tree_layout``), ``boxes`` (what the host drew: band
@@ -760,9 +836,15 @@ def view_tree(tree_path=None, perform_midpoint_rooting=True, metadata_df=None, f
     file is written).  The figure needs a GPU.
 
     Without ``tree_path`` the tree is built from the sequences of ``fasta_path``: encoded by the five-state rule, joined by ``nj_tree`` on an engine of
-    its own (the caller's keeps its alignment), the tips named as the FASTA names them, in file order; the figure's title is then ``NJ (Hamming)``."""
+    its own (the caller's keeps its alignment), the tips named as the FASTA names them, in file order; the figure's title is then ``NJ (Hamming)``.
+
+    ``bootstrap=B`` (B > 0): the built tree gets the support of B bootstrap replicates (``nj_tree(bootstrap=B, seed=seed)``), the title becomes
+    ``NJ (Hamming), B = <B>`` and every internal node whose support is >= ``support_min`` x B is marked by a square knob (``tree_layout``;
+    ``layout["support_nodes"]``).  With ``tree_path``, B is the number of replicates the file's integer internal labels count: the same marks."""
     if fasta_path is None or pos_file_path is None:
         raise ValueError("fasta_path and pos_file_path must be provided")
+    if bootstrap < 0:
+        raise ValueError("bootstrap must be >= 0")
     W, H = _half_up(float(plot_width) * dpi), _half_up(float(plot_height) * dpi)
     if not (1 <= W <= MAX_CANVAS and 1 <= H <= MAX_CANVAS):
         raise ValueError(f"the canvas of {W} x {H} pixels (plot_width x dpi by plot_height x dpi) must lie in 1..{MAX_CANVAS} either way")
@@ -770,14 +852,17 @@ def view_tree(tree_path=None, perform_midpoint_rooting=True, metadata_df=None, f
         from .snpdat import SnpDat, encode_chars, read_fasta
         names, seq = read_fasta(fasta_path)
         states = np.ascontiguousarray(encode_chars(seq).T)
-        tree = nj_tree(SnpDat(states=states, POS=np.arange(states.shape[0], dtype=np.int32), g=None, uqe=None, r=None, seq_names=names), labels=names)
+        tree = nj_tree(SnpDat(states=states, POS=np.arange(states.shape[0], dtype=np.int32), g=None, uqe=None, r=None, seq_names=names), labels=names,
+                       bootstrap=bootstrap, seed=seed)
         # through its Newick text, so that the figure is the one ``view_tree`` draws of the written tree: a file numbers its tips in its own
         # order, and midpoint rooting breaks its ties by tip number
         tree = parse_newick(write_newick(tree).encode("utf-8", "surrogateescape"))
-        title = "NJ (Hamming)"
+        title = f"NJ (Hamming), B = {bootstrap}" if bootstrap else "NJ (Hamming)"
     else:
         tree = read_newick(os.path.realpath(tree_path))      # :64-65
         title = os.path.basename(str(tree_path))
+    if bootstrap and tree.support is not None:
+        tree.n_replicates = int(bootstrap)                   # (Newick text carries the counts, not what they are counts of)
     if perform_midpoint_rooting:
         tree = midpoint_root(tree)
     sel = tree_selection(tree.tip_label, metadata_df, fasta_path, pos_file_path, links_df, lr_tophits_path, lr_annotated_links_path, sr_tophits_path,
@@ -793,7 +878,8 @@ def view_tree(tree_path=None, perform_midpoint_rooting=True, metadata_df=None, f
     md_missing, al_missing = bool(np.any(md_lev == MISSING_LEVEL)), False
     legends = [("Metadata", [str(v) for v in md_vals] + (["NA"] if md_missing else []), [int(v) for v in md_pal[:len(md_vals)]] + ([MISSING_RGB] if md_missing else [])),
                ("Alleles", [chr(v) for v in al_vals], [int(v) for v in al_pal[:len(al_vals)]])]
-    lay = tree_layout(tree, W, H, len(meta_names), len(cols), offset_metadata, offset_alleles, width_metadata, width_alleles, labels, legends)
+    lay = tree_layout(tree, W, H, len(meta_names), len(cols), offset_metadata, offset_alleles, width_metadata, width_alleles, labels, legends,
+                      support_min=support_min if bootstrap else None, n_replicates=bootstrap or None)
     levels = np.concatenate([md_lev, al_lev], axis=0)
     palette = np.stack([md_pal] * len(md_lev) + [al_pal] * len(al_lev)) if len(levels) else np.zeros((0, 256), dtype=np.uint32)
     from .engine import Engine
