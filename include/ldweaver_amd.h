@@ -33,6 +33,14 @@
  *   write caller device memory synchronise before they return, except ldw_acgtn2num_dev and
  *   ldw_fast_hadamard(on_device != 0), which only queue their kernel on the context's stream (ldw_ctx_sync
  *   waits for it).  A context must not be used from two threads at once.
+ *   The caller's stream may be of any kind: non-blocking or blocking (default flags), of any priority, torch's current
+ *   stream or not.  Work the caller has queued on it in front of a call needs no wait: the call's kernels and copies are
+ *   ordered behind it by the stream.  The helper streams (block staging, the block-wide GEMMs, the streaming tsv writer)
+ *   and the side threads stay the context's own whatever its main stream is; the helper streams are ordered against the
+ *   main stream by events, never through the null stream.  Several contexts may run on the same caller's stream: their
+ *   work is serialised on it in the order of the calls, results do not change (also under ldw_mi_all_pairs_multi).
+ *   A stream handed in is never destroyed by the library and works on after the context has gone.
+ *   (tests/test_caller_stream_gpu.py pins all of this.)
  *
  * Device memory handed out
  *   Device views handed out by ldw_links_device_ptrs and ldw_sr_tail_extract(on_device = 1) stay valid only
@@ -80,8 +88,14 @@ int ldw_ctx_destroy(ldw_ctx *ctx);
  * at most max_blk_sz SNPs, on a side thread of the context.  Call it right after the alignment upload.  The entry points that use
  * these buffers wait for the thread; without this call they are made on first use.  Results do not depend on it. */
 int ldw_ctx_reserve(ldw_ctx *ctx, int64_t L, int64_t N, int64_t max_blk_sz);
-/* run everything on an externally owned hipStream_t (e.g. torch's current stream); NULL = own stream.  The context's current stream is
- * synchronised first. */
+/* run everything on an externally owned hipStream_t (e.g. torch's current stream); NULL = own stream.  The context's current main
+ * stream and its helper streams are synchronised first, so everything the context has queued is done before the stream changes; the
+ * helper streams stay the context's own and the side threads of ldw_ctx_create / ldw_ctx_reserve are not waited for (they touch no
+ * stream).  The call is therefore allowed between any two calls on the context: right after ldw_ctx_create, between the stages of a
+ * job, between ldw_links_begin and ldw_links_end, and while ldw_lr_stream_begin or ldw_write_links_tsv_begin is open — tables and
+ * files are the same as without it.  Adopting a stream destroys the context's own main stream (one stream fewer in
+ * ldw_resource_report), NULL makes one again; the stream handed in is never destroyed, and the same one may be given to several
+ * contexts (see "Streams and synchronisation"). */
 int ldw_ctx_set_stream(ldw_ctx *ctx, void *hip_stream);
 /* waits for the work queued on the context's stream */
 int ldw_ctx_sync(ldw_ctx *ctx);

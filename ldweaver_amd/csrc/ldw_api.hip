@@ -369,7 +369,15 @@ int ldw_ctx_destroy(ldw_ctx *c) {
 
 int ldw_ctx_set_stream(ldw_ctx *c, void *s) {
     if (int rc = check_gpu(c)) return rc;
+    // Everything the context has queued is done before its main stream changes: the old main stream, then the helper streams, which stay the
+    // context's own whatever the main stream is (idle between calls; inside an open link pass they may hold work that waits for the old main
+    // stream's events).  What the new stream runs is then ordered behind all of it by this host-side wait alone, so the stream may change
+    // between any two calls, also between ldw_links_begin and ldw_links_end or while a tsv writer is open: the streaming writer waits for
+    // events and copies on its own stream, the asynchronous one holds a host copy.  The side threads of ldw_ctx_create / ldw_ctx_reserve load
+    // code objects and size buffers; they never touch a stream of the context and are not joined here.
     LDW_HIP(hipStreamSynchronize(c->stream));
+    for (hipStream_t h : {(hipStream_t)c->gemm_stream, (hipStream_t)c->copy_stream, (hipStream_t)c->lr_st})
+        if (h) LDW_HIP(hipStreamSynchronize(h));
     if (s) {
         c->stream.adopt((hipStream_t)s);
     } else {

@@ -69,7 +69,8 @@ class Engine:
         self.close()
 
     def set_stream(self, stream):
-        """stream: a raw hipStream_t value (int), e.g. torch.cuda.current_stream().cuda_stream; None/0 = own stream."""
+        """stream: a raw hipStream_t value (int), e.g. torch.cuda.current_stream().cuda_stream; None/0 = own stream.  Any kind of stream, between
+        any two calls (ldw_ctx_set_stream waits for everything the context has queued); the stream is never destroyed by the engine."""
         L.check(L.lib().ldw_ctx_set_stream(self._ctx, C.c_void_p(int(stream) if stream else 0)))
 
     def sync(self):
