@@ -763,6 +763,36 @@ int ldw_nj_tree(ldw_ctx *ctx, const double *dist, int64_t n, int32_t *parent_out
 int ldw_nj_bootstrap(ldw_ctx *ctx, const int32_t *mult, int64_t B, int64_t n, int32_t *parent_out, double *length_out, int32_t *support_out,
                      int32_t *rep_parent_out, double *rep_length_out);
 
+/* ---- (17) maximum parsimony on a given tree: what a SNP, and a pair of SNPs, does along the branches ---------------------------------------
+ * The tree: parent[nodes] (HOST), parent[0] = -1 and 0 <= parent[v] < v otherwise — the numbering of the Python Tree; a node may have any number of
+ * children, one included.  tip_seq[nodes] (HOST): for a node without children the 0-based sequence of the resident alignment it stands for, -1 for a node
+ * with children; the tree may hold a subset of the sequences in any order, none of them twice.
+ * A node's set is a mask of the states 0..4 (A, C, G, T, N).  Tips: under gap_mode 0 a tip in state N gets the set {A, C, G, T}, a wildcard that costs
+ * nothing, any other tip {s}; under gap_mode 1 every tip gets {s} and N is a fifth state.  Up pass (Hartigan's rule; Fitch's for two children), v from
+ * nodes-1 down to 0: for a node with children, c(s) = the children whose set holds s, K = max c, set(v) = {s : c(s) = K}, score += arity(v) - K.  Down pass:
+ * state(0) = the lowest state of set(0); for v = 1 .. nodes-1, state(v) = state(parent(v)) where set(v) holds it, else the lowest state of set(v); branch v
+ * changes where state(v) != state(parent(v)).  The changes of a SNP number its score, which is the least number any reconstruction needs.
+ * ldw_tree_parsimony: for every SNP of the alignment, score_out[L] and min_changes_out[L] = the distinct states at the tree's tips minus one, floored at 0
+ * (N not counted under gap_mode 0); homoplasy = score - min_changes.
+ * SNPs are processed in chunks whose node sets (nodes bytes per SNP) stay within 1 GiB; LDW_PARS_CHUNK=k in the environment, read at every call, forces
+ * chunks of k SNPs: a test hook, no result depends on it.  ldw_ctx_last_timing afterwards: [0] the passes, [1] the gathers of the tips' states, [2] what
+ * follows them (copies, transposes, pairs), [3] their sum.
+ * Refused on the host before anything is launched, the context staying usable — LDW_ERR_STATE: no alignment resident.  LDW_ERR_ARG: nodes < 2 or fewer than
+ * two tips; parent[0] != -1 or a parent[v] outside [0, v); a childless node whose tip_seq is outside [0, N) or names a sequence another tip names; a node
+ * with children whose tip_seq is not -1; gap_mode other than 0 or 1; a SNP index outside [0, L); k or K < 1; a null pointer.  The message names the node or
+ * the index.  Every call takes its working memory and gives it back; the alignment, the weights, the SNP metadata and the link tables stay as they are. */
+int ldw_tree_parsimony(ldw_ctx *ctx, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, int32_t *score_out,
+                       int32_t *min_changes_out);
+/* The reconstruction itself: node_state_out[k][nodes] (HOST), row i the state 0..4 of every node for SNP snp_idx[i] (HOST, 0-based, any order, repeats
+ * allowed: equal rows). */
+int ldw_tree_states(ldw_ctx *ctx, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, const int32_t *snp_idx, int64_t k,
+                    uint8_t *node_state_out);
+/* Pairs of SNPs (pair_a[K], pair_b[K], HOST; a == b and repeated pairs allowed): changes_a_out[K] and changes_b_out[K] the branches on which each SNP
+ * changes (= its score), co_out[K] the branches v >= 1 on which both do.  Only the distinct SNPs named go through the passes; each leaves a bitmap of
+ * its changed branches (nodes / 8 bytes per distinct SNP, held for the call) and a pair is the popcount of the AND of two. */
+int ldw_tree_cochanges(ldw_ctx *ctx, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, const int32_t *pair_a,
+                       const int32_t *pair_b, int64_t K, int32_t *changes_a_out, int32_t *changes_b_out, int32_t *co_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

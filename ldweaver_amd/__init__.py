@@ -16,6 +16,8 @@ _EXPORTS = {
     "LDWeaver": "driver", "cleanup": "driver",
     "view_tree": "tree", "read_newick": "tree", "midpoint_root": "tree", "ladderize": "tree",
     "nj_tree": "tree", "write_newick": "tree", "bootstrap_multiplicities": "tree",
+    "snp_parsimony": "parsimony", "link_cochanges": "parsimony", "ancestral_states": "parsimony", "tip_sequences": "parsimony",
+    "cochange_pvalue": "parsimony",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -513,6 +513,45 @@ class Engine:
         L.check(L.lib().ldw_nj_bootstrap(self._ctx, L.ptr(m) if m.size else None, B, n, L.ptr(parent), L.ptr(length), L.ptr(support), L.ptr(rp), L.ptr(rl)))
         return (parent, length, support, rp, rl) if want_trees else (parent, length, support)
 
+    # -- parsimony on a tree -------------------------------------
+    @staticmethod
+    def _pars_tree(parent, tip_seq):
+        p, t = L.as_c(parent, np.int32).ravel(), L.as_c(tip_seq, np.int32).ravel()
+        if len(p) != len(t):
+            raise ValueError(f"parent has {len(p)} nodes but tip_seq {len(t)}")
+        return p, t, (L.ptr(p) if len(p) else None), (L.ptr(t) if len(t) else None)
+
+    def tree_parsimony(self, parent, tip_seq, gap_mode: int = 0):
+        """Maximum parsimony of every SNP of the resident alignment on the tree ``parent`` (int32 [nodes], -1 at node 0, ``parent[v] < v``) whose
+        childless nodes stand for the sequences ``tip_seq`` (int32 [nodes], -1 at the other nodes): ldw_tree_parsimony.  ``gap_mode`` 0: a tip in state
+        N is a wildcard; 1: N is a fifth state.  Returns (score int32 [L], min_changes int32 [L])."""
+        p, t, pp, tp = self._pars_tree(parent, tip_seq)
+        score, mn = np.empty(max(self.L, 1), dtype=np.int32), np.empty(max(self.L, 1), dtype=np.int32)
+        L.check(L.lib().ldw_tree_parsimony(self._ctx, pp, tp, len(p), int(gap_mode), L.ptr(score), L.ptr(mn)))
+        return score[:self.L], mn[:self.L]
+
+    def tree_states(self, parent, tip_seq, snp_idx, gap_mode: int = 0) -> np.ndarray:
+        """The most-parsimonious reconstruction DESIGN.md 28 states, for the SNPs ``snp_idx`` (0-based, any order, repeats allowed): uint8
+        (len(snp_idx), nodes), the state 0..4 of every node (ldw_tree_states)."""
+        p, t, pp, tp = self._pars_tree(parent, tip_seq)
+        idx = L.as_c(snp_idx, np.int32).ravel()
+        out = np.empty((len(idx), len(p)), dtype=np.uint8)
+        L.check(L.lib().ldw_tree_states(self._ctx, pp, tp, len(p), int(gap_mode), L.ptr(idx) if len(idx) else None, len(idx), L.ptr(out) if out.size else None))
+        return out
+
+    def tree_cochanges(self, parent, tip_seq, pair_a, pair_b, gap_mode: int = 0):
+        """For every pair of SNPs (``pair_a[i]``, ``pair_b[i]``): (changes_a, changes_b, co_changes), int32 each — the branches on which each SNP
+        changes under that reconstruction, and those on which both do (ldw_tree_cochanges)."""
+        p, t, pp, tp = self._pars_tree(parent, tip_seq)
+        a, b = L.as_c(pair_a, np.int32).ravel(), L.as_c(pair_b, np.int32).ravel()
+        if len(a) != len(b):
+            raise ValueError(f"{len(a)} first SNPs but {len(b)} second SNPs")
+        K = len(a)
+        ca, cb, co = (np.empty(max(K, 1), dtype=np.int32) for _ in range(3))
+        L.check(L.lib().ldw_tree_cochanges(self._ctx, pp, tp, len(p), int(gap_mode), L.ptr(a) if K else None, L.ptr(b) if K else None, K, L.ptr(ca), L.ptr(cb),
+                                           L.ptr(co)))
+        return ca[:K], cb[:K], co[:K]
+
     def hamming_counts(self, thresh: int, tile0: int, tile1: int) -> np.ndarray:
         """Contribution of the strip of 128-sequence row tiles [tile0, tile1) to the neighbour counts n_j (all j)."""
         out = np.zeros(self.N, dtype=np.int64)
