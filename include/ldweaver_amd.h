@@ -793,6 +793,42 @@ int ldw_tree_states(ldw_ctx *ctx, const int32_t *parent, const int32_t *tip_seq,
 int ldw_tree_cochanges(ldw_ctx *ctx, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, const int32_t *pair_a,
                        const int32_t *pair_b, int64_t K, int32_t *changes_a_out, int32_t *changes_b_out, int32_t *co_out);
 
+/* ---- (18) the lineage check for links: clusters of the sequences, and the MI of listed SNP pairs inside them --------------------------------
+ * ldw_seq_clusters: single-linkage clusters of the sequences of the resident alignment.  Sequences i and j are neighbours at threshold t iff
+ * L - shared(i, j) < t, the predicate of ldw_hamming_weights (strict, in differing SNP columns under the five-state rule); a cluster is a connected
+ * component of that graph.  thresh[n_thresh] (HOST, 1..16 of them, each >= 0) are served from ONE Hamming GEMM.  labels_out[n_thresh][N] (HOST): clusters
+ * are numbered 0, 1, ... in the order of their smallest member, so a row is a function of the alignment and t alone; n_clusters_out[n_thresh].  t = 0 gives
+ * N singletons, t = 1 joins identical sequences, t > L gives one cluster; a larger t only merges clusters.  The components are found by rounds of hooking
+ * onto roots and pointer jumping over a bit adjacency matrix; the host reads one word back per round.  ldw_ctx_last_timing afterwards: [0] the rounds,
+ * [1] the GEMM and whatever else ran in front of them, [2] the rounds taken (of the threshold that took most), [3] the sum of [0] and [1].
+ * LDW_ERR_STATE: no alignment resident.  LDW_ERR_ARG: n_thresh outside 1..16, a negative threshold, a null pointer.  The call runs on the context's stream,
+ * takes the Hamming stage's working memory and N x Npad / 8 bytes per threshold and gives them back; the alignment, the weights, the SNP metadata and the
+ * link tables stay as they are. */
+int ldw_seq_clusters(ldw_ctx *ctx, const int32_t *thresh, int32_t n_thresh, int32_t *labels_out, int32_t *n_clusters_out);
+/* ldw_links_stratified: per cluster of a partition of the sequences, the joint tables and the weighted MI of the SNP pairs (pair_a[i], pair_b[i]), i < K
+ * (HOST, 0-based; a == b and repeated pairs allowed).  labels[N] (HOST): the cluster 0 .. C-1 of every sequence, or -1 for a sequence left out of
+ * everything; a cluster without a member is legal: its tables, MI and flags are 0.  Needs the alignment and the weights (ldw_set_weights), not the SNP
+ * metadata; the weights are the resident ones, not re-estimated per cluster.  For cluster c and pair (a, b):
+ *   counts[X][Y]  the members of c in state X at a and Y at b; fixed[X][Y] the sum of their V_s = round(fl(sqrt w_s)^2 2^F), F in *frac_bits_out as with
+ *                 ldw_joint_tables; both exact.  counts_out / fixed_out [K][C][25] (HOST) may both be NULL.
+ *   present_a[X]  the count marginal of X is positive; r_a the number of present states (N counts as one); likewise b.
+ *   poly_out[K][C]  bit 0: r_a > 1, bit 1: r_b > 1.
+ *   neff_out[C]   the fp64 of the long-double sum of the weights hdw[s] of the members in sequence order (the rule of ldw_set_weights' neff).
+ *   mi_out[K][C]  the sum over the cells whose two states are present, X outer and Y inner, in fp64, of
+ *                     (pxy / den) log(pxy / (pX pY + r_a r_b / 4 + r_a pX / 2 + r_b pY / 2) den),
+ *                 pxy = fixed[X][Y] / 2^F + 1/2, pX = (sum over Y of fixed[X][Y]) / 2^F, pY likewise, den = neff_c + r_a r_b / 2: the reference's formula
+ *                 with the intended RXY on the members alone.  Finite for every cluster with a member; where both SNPs are monomorphic in c the sum is
+ *                 log 1 and 0 is returned outright.
+ *   mi_all_out[K] the same over all labelled sequences (the tables summed over the clusters, neff summed over the labelled sequences in sequence order).
+ * The cell order is fixed and every sum is an integer: equal inputs give equal bits whatever the chunking or the numbering of the clusters.  Pairs go in
+ * chunks whose working memory stays within 1 GiB; LDW_LIN_CHUNK=k in the environment, read at every call, forces chunks of k pairs: a test hook.
+ * ldw_ctx_last_timing afterwards: [0] the pairs, [1] the bit rows of the chunks' SNPs, [2] the copies out, [3] their sum.
+ * Refused on the host before anything is launched, the context staying usable — LDW_ERR_STATE: no alignment or no weights resident.  LDW_ERR_ARG: K < 1;
+ * C outside 1..65536; a label outside [-1, C); every label -1; a SNP index outside [0, L); a null pointer among the required ones.  The message names the
+ * index. */
+int ldw_links_stratified(ldw_ctx *ctx, const int32_t *pair_a, const int32_t *pair_b, int64_t K, const int32_t *labels, int32_t C, double *mi_out,
+                         double *mi_all_out, uint8_t *poly_out, double *neff_out, int64_t *counts_out, int64_t *fixed_out, int *frac_bits_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

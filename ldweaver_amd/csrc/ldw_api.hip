@@ -770,6 +770,7 @@ int ldw_set_weights(ldw_ctx *c, const double *hdw, int64_t N, int nlimbs) {
     c->wts.nlimbs = nlimbs;
     c->wts.frac_bits = F;
     c->wts.neff = (double)neff;
+    c->wts.h_hdw.assign(hdw, hdw + N);
     c->wts.h_vfixed.assign((size_t)c->Npad, 0);
     std::vector<int8_t> dseq((size_t)nlimbs * c->Npad, 0);   // digits by sequence
     int64_t total = 0;

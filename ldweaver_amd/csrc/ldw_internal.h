@@ -108,6 +108,7 @@ struct Weights {
     DevBuf digits;              // int8 [nlimbs][Npad] balanced base-256 digits of V_s
     DevBuf vfixed;              // int64 [Npad] quantised weights V_s (0 in the padding)
     std::vector<int64_t> h_vfixed;
+    std::vector<double> h_hdw;  // [N] the weights as given (ldw_links_stratified sums them per cluster, by the rule of neff)
     // mixed-precision path (nlimbs == 5): V = V_hi * 2^16 + V_lo, V_hi = limbs 2..4
     std::vector<int64_t> h_vfixed_hi;
     int64_t total_fixed_hi = 0;
@@ -460,6 +461,12 @@ template <class T> void release_state(ldw_ctx *ctx, void *&state) {
     (void)hipStreamSynchronize(ctx->stream);
     delete static_cast<T *>(state);
     state = nullptr;
+}
+// n items of host memory into a device buffer grown to hold them, queued on the main stream (the source stays valid until the stream has passed the copy)
+template <class T> int upload(ldw_ctx *ctx, DevBuf &b, const T *src, size_t n) {
+    if (int rc = b.reserve(std::max<size_t>(n, 1) * sizeof(T))) return rc;
+    if (n) LDW_HIP(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return LDW_OK;
 }
 void out_release(ldw_ctx *ctx);      // ldw_out.hip: the alignment writer's staging (ldw_ctx_destroy)
 int64_t out_trim(ldw_ctx *ctx);      // ... its pinned buffers and device image only (ldw_host_trim); bytes released

@@ -244,12 +244,6 @@ int64_t pars_chunk(int64_t nodes, int64_t total) {
     return std::min<int64_t>(std::min<int64_t>(C, PARS_MAX_CHUNK), total);
 }
 
-template <class T> int pars_upload(ldw_ctx *c, ldw::DevBuf &b, const T *src, size_t n) {
-    if (int rc = b.reserve(std::max<size_t>(n, 1) * sizeof(T))) return rc;
-    if (n) LDW_HIP(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    return LDW_OK;
-}
-
 // What the three entry points share: the tree on the device, then chunk after chunk of `total` SNP slots (slot j is SNP snp[j], or SNP j where snp is null)
 // the tips, the up pass and, with `down`, the down pass; after_chunk(first slot, count) queues what the caller wants of the chunk's sets before the next
 // chunk overwrites them.  ldw_ctx_last_timing: [0] the passes, [1] the gathers, [2] whatever after_chunk and the caller queued behind, [3] their sum.
@@ -268,11 +262,11 @@ struct ParsRun {
         if ((rc = b.sets.reserve((size_t)t.nodes * (size_t)Cpad)) || (rc = b.seen.reserve((size_t)Cpad)) ||
             (want_score && ((rc = b.score.reserve((size_t)Cpad * 4)) || (rc = b.minch.reserve((size_t)Cpad * 4)))))
             return rc;
-        if ((rc = pars_upload(c, b.child_ptr, t.child_ptr.data(), t.child_ptr.size())) || (rc = pars_upload(c, b.child_idx, t.child_idx.data(), t.child_idx.size())) ||
-            (rc = pars_upload(c, b.tip_seq, t.tip_seq.data(), t.tip_seq.size())) || (rc = pars_upload(c, b.tip_node, t.tip_node.data(), t.tip_node.size())))
+        if ((rc = ldw::upload(c, b.child_ptr, t.child_ptr.data(), t.child_ptr.size())) || (rc = ldw::upload(c, b.child_idx, t.child_idx.data(), t.child_idx.size())) ||
+            (rc = ldw::upload(c, b.tip_seq, t.tip_seq.data(), t.tip_seq.size())) || (rc = ldw::upload(c, b.tip_node, t.tip_node.data(), t.tip_node.size())))
             return rc;
-        if (down && (rc = pars_upload(c, b.parent, parent, (size_t)t.nodes))) return rc;
-        if (snp && (rc = pars_upload(c, b.snp, snp, (size_t)total))) return rc;
+        if (down && (rc = ldw::upload(c, b.parent, parent, (size_t)t.nodes))) return rc;
+        if (snp && (rc = ldw::upload(c, b.snp, snp, (size_t)total))) return rc;
         const int64_t n_chunks = (total + C - 1) / C;
         ev.resize((size_t)n_chunks * 3 + 1);
         for (ldw::Event &e : ev) LDW_HIP(e.ensure());
@@ -405,8 +399,8 @@ int cochanges_run(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int
     for (int64_t i = 0; i < K; ++i) sa[(size_t)i] = pars_slot(d, pair_a[i]), sb[(size_t)i] = pars_slot(d, pair_b[i]);
     ParsRun run{c, b, t, gap_mode};
     int rc = LDW_OK;
-    if ((rc = run.start(parent, D, d.data(), false, true)) || (rc = b.bits.reserve((size_t)words * (size_t)D * 4)) || (rc = pars_upload(c, b.slot_a, sa.data(), sa.size())) ||
-        (rc = pars_upload(c, b.slot_b, sb.data(), sb.size())) || (rc = b.ca.reserve((size_t)K * 4)) || (rc = b.cb.reserve((size_t)K * 4)) ||
+    if ((rc = run.start(parent, D, d.data(), false, true)) || (rc = b.bits.reserve((size_t)words * (size_t)D * 4)) || (rc = ldw::upload(c, b.slot_a, sa.data(), sa.size())) ||
+        (rc = ldw::upload(c, b.slot_b, sb.data(), sb.size())) || (rc = b.ca.reserve((size_t)K * 4)) || (rc = b.cb.reserve((size_t)K * 4)) ||
         (rc = b.co.reserve((size_t)K * 4)))
         return rc;
     if ((rc = run.chunks(D, true, false, true, b.bits.as<uint32_t>(), D, [](int64_t, int64_t) { return (int)LDW_OK; }))) return rc;

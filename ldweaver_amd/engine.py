@@ -552,6 +552,48 @@ class Engine:
                                            L.ptr(co)))
         return ca[:K], cb[:K], co[:K]
 
+    # -- the lineage check ---------------------------------------
+    def seq_clusters(self, thresh):
+        """Single-linkage clusters of the resident alignment's sequences (ldw_seq_clusters): i and j are neighbours iff they differ in fewer than
+        ``thresh`` SNP columns.  ``thresh``: an int, or up to 16 of them served from one Hamming GEMM.  Returns (labels, n_clusters): int32 [N] and an
+        int for one threshold, int32 (n_thresh, N) and int32 [n_thresh] for a sequence; clusters are numbered in the order of their smallest member.
+        ``last_timing()`` afterwards: ``gemm_ms`` the rounds, ``epilogue_ms`` what ran in front of them, ``select_ms`` the rounds taken."""
+        one = np.ndim(thresh) == 0
+        th = L.as_c(np.atleast_1d(thresh), np.int32).ravel()
+        labels = np.empty((max(len(th), 1), max(self.N, 1)), dtype=np.int32)
+        n = np.empty(max(len(th), 1), dtype=np.int32)
+        L.check(L.lib().ldw_seq_clusters(self._ctx, L.ptr(th) if len(th) else None, len(th), L.ptr(labels), L.ptr(n)))
+        labels, n = labels[:len(th), :self.N], n[:len(th)]
+        return (labels[0], int(n[0])) if one else (labels, n)
+
+    def links_stratified(self, pair_a, pair_b, labels, C=None, want_tables=False):
+        """Per cluster of ``labels`` (int [N]: 0 .. C-1, or -1 for a sequence left out; ``C`` defaults to max(labels) + 1) the weighted MI of the SNP
+        pairs (``pair_a[i]``, ``pair_b[i]``) over the cluster's members alone, under the resident weights (ldw_links_stratified).  Returns a dict:
+        ``mi`` float64 (K, C), ``mi_all`` float64 [K] (over all labelled sequences), ``poly`` uint8 (K, C) (bit 0: the first SNP is polymorphic in the
+        cluster, bit 1: the second), ``neff`` float64 [C], ``frac_bits``; with ``want_tables`` also ``counts`` and ``fixed``, int64 (K, C, 5, 5)."""
+        import ctypes as ct         # (the argument C, the number of clusters as the C ABI names it, hides the module's alias here)
+        a, b = L.as_c(pair_a, np.int32).ravel(), L.as_c(pair_b, np.int32).ravel()
+        if len(a) != len(b):
+            raise ValueError(f"{len(a)} first SNPs but {len(b)} second SNPs")
+        lab = L.as_c(labels, np.int32).ravel()
+        if len(lab) != self.N:
+            raise ValueError(f"labels has {len(lab)} entries, the alignment {self.N} sequences")
+        if C is None:
+            C = int(lab.max()) + 1 if len(lab) else 0
+        K, C = len(a), int(C)
+        shape = (max(K, 1), max(min(C, 65536), 1))
+        mi, mi_all, poly = np.empty(shape), np.empty(shape[0]), np.empty(shape, dtype=np.uint8)
+        neff = np.empty(shape[1])
+        cnt = np.empty(shape + (5, 5), dtype=np.int64) if want_tables else None
+        fix = np.empty(shape + (5, 5), dtype=np.int64) if want_tables else None
+        fb = ct.c_int(0)
+        L.check(L.lib().ldw_links_stratified(self._ctx, L.ptr(a) if K else None, L.ptr(b) if K else None, K, L.ptr(lab) if len(lab) else None, C, L.ptr(mi),
+                                             L.ptr(mi_all), L.ptr(poly), L.ptr(neff), L.ptr(cnt), L.ptr(fix), ct.byref(fb)))
+        out = dict(mi=mi, mi_all=mi_all, poly=poly, neff=neff, frac_bits=fb.value)
+        if want_tables:
+            out.update(counts=cnt, fixed=fix)
+        return out
+
     def hamming_counts(self, thresh: int, tile0: int, tile1: int) -> np.ndarray:
         """Contribution of the strip of 128-sequence row tiles [tile0, tile1) to the neighbour counts n_j (all j)."""
         out = np.zeros(self.N, dtype=np.int64)
