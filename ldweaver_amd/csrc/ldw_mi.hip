@@ -398,10 +398,20 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
     // r05: everything on the device (k_cols_dev ... k_sr_fill_all) — the host loop below built the intervals of C4's 20 band blocks in 17 ms, which a
     // multi-GPU job's rank 0 paid after every gather.  Integral genome length (every len is then an exact integer on host and device alike); a column
     // whose interval check fails (none on ascending positions) sends the call down the host path, as does LDW_SR_PAIRS_HOST=1 (A/B, tests).
-    if (c->meta.g == std::floor(c->meta.g) && getenv("LDW_SR_PAIRS_HOST") == nullptr) {
+    // A block whose positions do not lie within one turn of the circle (within_one_turn, ldw_pass_plan.h) raises `bad` before anything is launched: the
+    // windows of k_cols_dev are not exact there and its boundary checks do not see it; build_cols scans such a block with the predicate.
+    const std::vector<int32_t> &Ph = c->meta.h_POS;
+    auto block_in_one_turn = [&](int32_t fs, int32_t fe, int32_t ts, int32_t te) {   // (POS ascends: a side's ends are its extremes)
+        return within_one_turn((double)std::min(Ph[(size_t)fs - 1], Ph[(size_t)ts - 1]), (double)std::max(Ph[(size_t)fe - 1], Ph[(size_t)te - 1]), c->meta.g);
+    };
+    bool bad_turn = false;
+    for (int64_t b = 0; b < nblocks && !bad_turn; ++b) {
+        if (int rc = check_block(c, blocks, b)) return rc;
+        bad_turn = !block_in_one_turn(blocks[b * 4 + 0], blocks[b * 4 + 1], blocks[b * 4 + 2], blocks[b * 4 + 3]);
+    }
+    if (!bad_turn && c->meta.g == std::floor(c->meta.g) && getenv("LDW_SR_PAIRS_HOST") == nullptr) {
         std::vector<SrBlkDev> hb;
         int64_t ncols = 0;
-        const std::vector<int32_t> &Ph = c->meta.h_POS;
         for (int64_t b = 0; b < nblocks; ++b) {
             const int32_t fs = blocks[b * 4 + 0], fe = blocks[b * 4 + 1], ts = blocks[b * 4 + 2], te = blocks[b * 4 + 3];
             if (int rc = check_block(c, blocks, b)) return rc;
@@ -458,7 +468,7 @@ int ldw_sr_pairs_fill(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, double
     for (int64_t b = 0; b < nblocks; ++b) {
         const int32_t fs = blocks[b * 4 + 0], fe = blocks[b * 4 + 1], ts = blocks[b * 4 + 2], te = blocks[b * 4 + 3];
         if (int rc = check_block(c, blocks, b)) return rc;
-        if (ts > fe && 2 * sr_dist < c->meta.g) {   // disjoint ranges, to side after the from side: no pair within sr_dist directly or across the origin?
+        if (ts > fe && 2 * sr_dist < c->meta.g && block_in_one_turn(fs, fe, ts, te)) {   // disjoint ranges, to side after the from side: no pair within sr_dist directly or across the origin?
             const double pf_min = P[(size_t)fs - 1], pf_max = P[(size_t)fe - 1], pt_min = P[(size_t)ts - 1], pt_max = P[(size_t)te - 1];
             if (pt_min - pf_max > sr_dist && pf_min + c->meta.g - pt_max > sr_dist) continue;
         }

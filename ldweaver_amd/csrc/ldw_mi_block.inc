@@ -62,8 +62,12 @@ int build_side(ldw_ctx *c, const int32_t *idx, int64_t n, SideLists &S, const st
 
 // Short-range intervals of every to-side SNP (host, O(nt log nf)); returns the block's short-range row count.
 // Requires the from-side list to be ascending in POS (true for contiguous blocks and for the order-preserving
-// subsets of SR-only mode).  Every interval boundary is verified with the exact predicate of the reference
-// (circ_len <= sr_dist); a column that fails the check is rebuilt by scanning.
+// subsets of SR-only mode).  The intervals come from three position windows, which are exact when the positions
+// of both sides lie within one turn of the circle (within_one_turn, ldw_pass_plan.h); the predicate of the
+// reference (circ_len <= sr_dist) is then evaluated at the interval boundaries only, as a guard on the window
+// arithmetic — it proves nothing about the inside of an interval — and a column that fails it is rebuilt by
+// scanning.  A block whose positions do NOT lie within one turn (positions beyond g: a window can then begin
+// and end on partners and hold non-partners inside) builds every column by that scan and takes no quick reject.
 int build_cols(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *to_idx, int64_t nt, bool diag, double sr_dist,
                std::vector<ColInfo> &cols, int64_t &n_sr_blk) {
     const double g = c->meta.g;
@@ -73,6 +77,7 @@ int build_cols(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
         LDW_REQUIRE(a == 0 || pf[a] >= pf[a - 1], LDW_ERR_ARG, "from-side SNP list must be ascending in POS (position %lld)", (long long)a);
     }
     cols.resize((size_t)nt);
+    bool one_turn = true;
     {   // quick reject: when the two position ranges are farther apart than sr_dist both directly and around the
         // origin, no pair of the block is short-range (true for most off-diagonal blocks)
         double pt_min = (double)c->meta.h_POS[to_idx[0]], pt_max = pt_min;
@@ -84,7 +89,8 @@ int build_cols(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
         const double pf_min = pf.front(), pf_max = pf.back();
         const bool apart = (pt_min - pf_max > sr_dist && pf_min + g - pt_max > sr_dist) ||
                            (pf_min - pt_max > sr_dist && pt_min + g - pf_max > sr_dist);
-        if (apart && 2 * sr_dist < g) {
+        one_turn = within_one_turn(std::min(pf_min, pt_min), std::max(pf_max, pt_max), g);
+        if (one_turn && apart && 2 * sr_dist < g) {
             ColInfo z;
             memset(&z, 0, sizeof(z));
             std::fill(cols.begin(), cols.end(), z);
@@ -133,13 +139,13 @@ int build_cols(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *t
             if (n > 0 && iv[k][0] <= m[n - 1][1]) m[n - 1][1] = std::max(m[n - 1][1], iv[k][1]);
             else { m[n][0] = iv[k][0]; m[n][1] = iv[k][1]; ++n; }
         }
-        bool ok = true;
+        bool ok = one_turn;
         for (int k = 0; k < n && ok; ++k) {
             ok = P(m[k][0]) && P(m[k][1] - 1);
             if (ok && m[k][0] > 0) ok = !P(m[k][0] - 1);
             if (ok && m[k][1] < nf) ok = !P(m[k][1]);
         }
-        if (n == 0 && nf > 0) ok = !P(0) && !P(nf - 1);
+        if (ok && n == 0 && nf > 0) ok = !P(0) && !P(nf - 1);
         if (!ok) {  // rebuild from the exact predicate
             n = 0;
             int64_t a = 0;

@@ -62,6 +62,15 @@ inline bool probe_expected(const int32_t *blocks, int64_t nblocks, int64_t min_p
 }
 
 // ------------------------------------------------------------------------------------------------
+// One turn of the circle.  Every shortcut of the short/long-range split that works on POSITION WINDOWS or on a block's end positions (build_cols'
+// three windows and its quick reject, k_cols_dev, span_candidate, the rejects of ldw_sr_pairs_fill) assumes that the positions of the block's two
+// sides lie within one turn: all in [0, g] and less than g apart.  The difference of two such positions lies in (-g, g), where "within sr_dist
+// on the circle" IS the union of the three windows.  The reference accepts any positions (its %% folds them), and ldw_set_snp_meta does not
+// bound POS by g: a block outside this condition takes the predicate itself, pair by pair, everywhere.
+// ------------------------------------------------------------------------------------------------
+inline bool within_one_turn(double p_min, double p_max, double g) { return p_min >= 0 && p_max <= g && p_max - p_min < g; }
+
+// ------------------------------------------------------------------------------------------------
 // spans (r04): which blocks of the list may share a launch sequence
 // ------------------------------------------------------------------------------------------------
 // A block can be part of a span when its to side lies strictly AFTER its from side (make_blocks order: i < j), it is square, far enough
@@ -84,6 +93,7 @@ inline bool span_candidate(const SpanView &v, const int32_t *b) {
     if (!(2 * v.sr_dist < v.g)) return false;
     const std::vector<int32_t> &P = v.POS;
     const double pf_min = P[(size_t)fs - 1], pf_max = P[(size_t)fe - 1], pt_min = P[(size_t)ts - 1], pt_max = P[(size_t)te - 1];
+    if (!within_one_turn(pf_min, pt_max, v.g)) return false;   // (POS ascends and ts > fe: the block's smallest and largest position)
     return pt_min - pf_max > v.sr_dist && pf_min + v.g - pt_max > v.sr_dist;
 }
 

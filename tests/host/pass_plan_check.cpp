@@ -135,6 +135,23 @@ static void check_plan() {
         CHECK(total_pairs(bl, 3) == 4000.0 * 4000.0 * 2 + 4000.0 * 100.0, "total_pairs");
         CHECK(block_list_key(bl, 3, 20000.0) != block_list_key(bl, 2, 20000.0) && block_list_key(bl, 3, 20000.0) != block_list_key(bl, 3, 20000.5), "block_list_key");
     }
+    {   // span_candidate at its geometric boundary: five blocks of 2048 SNPs one apart.  The nearest pair of (1, 3) is 2049 apart; (1, 5) closes the circle at g - 10239
+        const int32_t L = 5 * B;
+        std::vector<int32_t> POS((size_t)L), bad((size_t)L + 1, 0);
+        for (int32_t i = 0; i < L; ++i) POS[(size_t)i] = i + 1;
+        const int32_t b13[] = {1, B, 2 * B + 1, 3 * B}, b15[] = {1, B, 4 * B + 1, 5 * B}, b12[] = {1, B, B + 1, 2 * B};
+        const auto cand = [&](const int32_t *b, double g, double sr) { return span_candidate(SpanView{L, g, POS, bad, sr}, b); };
+        CHECK(cand(b13, 12288, 2048) && !cand(b13, 12288, 2049) && !cand(b12, 12288, 2048), "a pair at len == sr_dist keeps its block out of spans");
+        CHECK(cand(b15, 12288, 2048) && !cand(b15, 12287, 2048) && cand(b15, 12287, 2047.5), "the same across the origin");
+        CHECK(!cand(b13, 4096, 2048) && !cand(b13, 4097, 2048), "2 sr_dist >= g, and a genome shorter than the block's extent");
+        // positions outside [0, g] or g and more apart: no block is a candidate, whatever its four end positions say
+        CHECK(!within_one_turn(0, 10, 10) && within_one_turn(0, 9.5, 10) && within_one_turn(1, 10, 10) &&!within_one_turn(0, 11, 10) && !within_one_turn(-1, 5, 10) && !within_one_turn(0, 10, 9.5),
+              "within_one_turn: all in [0, g], less than g apart");
+        std::vector<int32_t> far(POS);
+        for (int32_t &p : far) p += 20000;
+        CHECK(cand(b13, 12288, 2048) && !span_candidate(SpanView{L, 12288, far, bad, 2048}, b13) && span_candidate(SpanView{L, 32288, far, bad, 2048}, b13),
+              "positions beyond g: no span");
+    }
     printf("plan: done\n");
 }
 
