@@ -829,6 +829,37 @@ int ldw_seq_clusters(ldw_ctx *ctx, const int32_t *thresh, int32_t n_thresh, int3
 int ldw_links_stratified(ldw_ctx *ctx, const int32_t *pair_a, const int32_t *pair_b, int64_t K, const int32_t *labels, int32_t C, double *mi_out,
                          double *mi_all_out, uint8_t *poly_out, double *neff_out, int64_t *counts_out, int64_t *fixed_out, int *frac_bits_out);
 
+/* ---- (19) permutation p-values for links, within lineages -------------------------------------------------------------------------------
+ * ldw_links_permuted: for the SNP pairs (pair_a[i], pair_b[i]), i < K, labels[N] and C exactly as ldw_links_stratified takes them (HOST), the weighted MI
+ * over all labelled sequences and its null distribution under B permutations of SNP b's states among the sequences of every cluster.  Needs the alignment
+ * and the weights resident.
+ *   P            the number of sequences with labels >= 0 (*p_out).  order0[P]: those sequences sorted by (label, sequence index).
+ *   order_r[P]   for replicate r in [0, B): the same sequences stably sorted by the 56-bit key (label << 40) | h(seed, r, s); equal keys keep ascending
+ *                sequence index.  With all arithmetic mod 2^64:
+ *                    z = seed + 0x9E3779B97F4A7C15 (r + 1) + 0xD1B54A32D192ED03 (s + 1)
+ *                    z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) 0x94D049BB133111EB;  z ^= z >> 31;  h = z >> 24.
+ *                A replicate is thus a permutation within every cluster and a function of (labels, seed, r) alone.
+ *   fixed_r[X][Y]  the sum over p of V[order0[p]] wherever states[a][order0[p]] == X and states[b][order_r[p]] == Y (states above 4 count as 4, N);
+ *                counts_r the same with 1 in place of V.  The weight stays with the sequence and with SNP a: only b's states move.
+ *   mi_r         the formula of (18) on that one table over all labelled sequences: neff is mi_all's (the long-double sum of hdw over the labelled sequences
+ *                in sequence order), r_a and r_b come from the count marginals, "both monomorphic" returns 0 outright.  It is evaluated by the same device
+ *                function as mi_all, so equal integer tables give equal bits.
+ * Outputs (HOST): mi_obs_out[K] = mi_r under the identity order (order0), bit-equal to ldw_links_stratified's mi_all_out for the same inputs; n_ge_out[K]
+ * (int32) the replicates with mi_r >= mi_obs, an fp64 compare on the device's own values; null_max_out[K] the largest mi_r; and, each of which may be NULL,
+ * null_out[K][B] (fp64) every mi_r, fixed_out[K][B][25] (int64) every fixed_r, order_out[B][P] (int32) every order_r; *frac_bits_out as with
+ * ldw_links_stratified.  Replicates go in batches of at most 256 — one stable radix sort per batch — sized so that keys, values and sort storage stay within
+ * 1 GiB; pairs go in chunks whose per-batch values and tables stay within 1 GiB.  No result depends on either: counts are integers, maxima are maxima.
+ * Test hooks in the environment, read at every call: LDW_PERM_BATCH=k forces batches of k replicates (k <= 256), LDW_PERM_CHUNK=k chunks of k pairs,
+ * LDW_PERM_LDS=m the kernel form m (0: weights and both state arrays in LDS, 1: the state arrays, 2: none) or the next one that fits.
+ * ldw_ctx_last_timing afterwards: [0] the pair kernel (with the counts), [1] keys and sorts, [2] the copies out, [3] their sum.
+ * Refused on the host before anything is launched, the context staying usable — LDW_ERR_STATE: no alignment or no weights resident.  LDW_ERR_ARG: K < 1;
+ * B outside 1..2^24; C outside 1..65536; a label outside [-1, C); every label -1; a SNP index outside [0, L); a null pointer among the required ones.  The
+ * message names the index.  The call takes its working memory (besides the above, 28 bytes per pair) and gives it back; the alignment, the weights, the SNP
+ * metadata and the link tables stay as they are. */
+int ldw_links_permuted(ldw_ctx *ctx, const int32_t *pair_a, const int32_t *pair_b, int64_t K, const int32_t *labels, int32_t C, int32_t B, uint64_t seed,
+                       double *mi_obs_out, int32_t *n_ge_out, double *null_max_out, double *null_out, int64_t *fixed_out, int32_t *order_out, int64_t *p_out,
+                       int *frac_bits_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

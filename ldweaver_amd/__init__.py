@@ -18,7 +18,7 @@ _EXPORTS = {
     "nj_tree": "tree", "write_newick": "tree", "bootstrap_multiplicities": "tree",
     "snp_parsimony": "parsimony", "link_cochanges": "parsimony", "ancestral_states": "parsimony", "tip_sequences": "parsimony",
     "cochange_pvalue": "parsimony",
-    "sequence_clusters": "lineage", "link_lineage_mi": "lineage",
+    "sequence_clusters": "lineage", "link_lineage_mi": "lineage", "link_permutation_test": "lineage",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -163,6 +163,7 @@ _SIGS_API = {
     "ldw_tree_cochanges": (C.c_int, [_p, _p, _p, _i64, C.c_int32, _p, _p, _i64, _p, _p, _p]),
     "ldw_seq_clusters": (C.c_int, [_p, _p, C.c_int32, _p, _p]),
     "ldw_links_stratified": (C.c_int, [_p, _p, _p, _i64, _p, C.c_int32, _p, _p, _p, _p, _p, _p, C.POINTER(C.c_int)]),
+    "ldw_links_permuted": (C.c_int, [_p, _p, _p, _i64, _p, C.c_int32, C.c_int32, C.c_uint64, _p, _p, _p, _p, _p, _p, C.POINTER(_i64), C.POINTER(C.c_int)]),
     "ldw_tsv_probe": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ldw_tsv_read": (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int32, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_uint32)]),
     "ldw_tsv_columns": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_i64), C.POINTER(C.c_int32), C.POINTER(_i64)]),

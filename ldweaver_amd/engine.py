@@ -594,6 +594,46 @@ class Engine:
             out.update(counts=cnt, fixed=fix)
         return out
 
+    # -- the permutation test -------------------------------------
+    def links_permuted(self, pair_a, pair_b, labels, n_perm, seed=0, C=None, want_null=False, want_tables=False, want_orders=False):
+        """The weighted MI of the SNP pairs (``pair_a[i]``, ``pair_b[i]``) over the labelled sequences and its null distribution under ``n_perm``
+        permutations of the second SNP's states among the sequences of every cluster of ``labels`` (as ``links_stratified`` takes them; ``C`` defaults
+        to max(labels) + 1), under the resident weights (ldw_links_permuted).  Returns a dict: ``mi_obs`` float64 [K] (bit-equal to
+        ``links_stratified(...)["mi_all"]``), ``n_ge`` int32 [K] (replicates whose MI reaches the observed one), ``null_max`` float64 [K], ``P`` (the
+        labelled sequences), ``n_perm``, ``frac_bits``; with ``want_null`` also ``null`` float64 (K, n_perm), with ``want_tables`` ``fixed`` int64
+        (K, n_perm, 5, 5), with ``want_orders`` ``orders`` int32 (n_perm, P).  A replicate is a function of (labels, seed, its number) alone."""
+        import ctypes as ct         # (the argument C, the number of clusters as the C ABI names it, hides the module's alias here)
+        a, b = L.as_c(pair_a, np.int32).ravel(), L.as_c(pair_b, np.int32).ravel()
+        if len(a) != len(b):
+            raise ValueError(f"{len(a)} first SNPs but {len(b)} second SNPs")
+        lab = L.as_c(labels, np.int32).ravel()
+        if len(lab) != self.N:
+            raise ValueError(f"labels has {len(lab)} entries, the alignment {self.N} sequences")
+        if C is None:
+            C = int(lab.max()) + 1 if len(lab) else 0
+        K, C, B = len(a), int(C), int(n_perm)
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed {seed} is not an unsigned 64-bit integer")
+        if not -(1 << 31) <= B < 1 << 31:
+            raise ValueError(f"n_perm {B} is out of range")
+        rows, reps, n_lab = max(K, 1), max(min(B, 1 << 24), 1), max(int((lab >= 0).sum()), 1)
+        mi_obs, n_ge, null_max = np.empty(rows), np.empty(rows, dtype=np.int32), np.empty(rows)
+        null = np.empty((rows, reps)) if want_null else None
+        fix = np.empty((rows, reps, 5, 5), dtype=np.int64) if want_tables else None
+        orders = np.empty((reps, n_lab), dtype=np.int32) if want_orders else None
+        p_out, fb = ct.c_int64(0), ct.c_int(0)
+        L.check(L.lib().ldw_links_permuted(self._ctx, L.ptr(a) if K else None, L.ptr(b) if K else None, K, L.ptr(lab) if len(lab) else None, C, B, seed,
+                                           L.ptr(mi_obs), L.ptr(n_ge), L.ptr(null_max), L.ptr(null), L.ptr(fix), L.ptr(orders), ct.byref(p_out), ct.byref(fb)))
+        out = dict(mi_obs=mi_obs, n_ge=n_ge, null_max=null_max, P=int(p_out.value), n_perm=B, frac_bits=fb.value)
+        if want_null:
+            out["null"] = null
+        if want_tables:
+            out["fixed"] = fix
+        if want_orders:
+            out["orders"] = orders
+        return out
+
     def hamming_counts(self, thresh: int, tile0: int, tile1: int) -> np.ndarray:
         """Contribution of the strip of 128-sequence row tiles [tile0, tile1) to the neighbour counts n_j (all j)."""
         out = np.zeros(self.N, dtype=np.int64)

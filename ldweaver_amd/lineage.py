@@ -1,7 +1,9 @@
 """The lineage check for links: does an association hold inside the lineages, or only between them?  ``sequence_clusters`` cuts the
 sequences into single-linkage clusters of the Hamming distances (``Engine.seq_clusters``); ``link_lineage_mi`` evaluates the weighted MI of every link
 inside each cluster (``Engine.links_stratified``) and appends the summary: a pair of lineage markers has a large MI over the whole sample and none
-within any lineage, an epistatic pair keeps its MI within them.  Both run on the device over the alignment the engine holds."""
+within any lineage, an epistatic pair keeps its MI within them.  ``link_permutation_test`` gives every link a p-value for its MI from
+permutations of one SNP's states among the sequences of each cluster (``Engine.links_permuted``).  All run on the device over the alignment the engine
+holds."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -101,6 +103,20 @@ def lineage_summary(mi, mi_all, poly, neff) -> dict:
     return dict(mi_within=within, within_frac=frac, n_poly=(np.asarray(poly) == 3).sum(axis=1).astype(np.int64), top_cluster=top, top_share=share)
 
 
+def permutation_columns(mi_obs, n_ge, null_max, n_perm) -> dict:
+    """The columns ``link_permutation_test`` appends: ``mi_all`` the observed MI, ``perm_ge`` the replicates whose MI reaches it, ``perm_p`` =
+    (1 + perm_ge) / (1 + n_perm) — the observed arrangement counts as one of the permutations, so no p is 0 —, ``null_max`` the largest replicate MI
+    and ``n_perm``."""
+    n_perm = int(n_perm)
+    if n_perm < 1:
+        raise ValueError(f"n_perm must be at least 1, got {n_perm}")
+    ge = np.asarray(n_ge, dtype=np.int64)
+    if ge.size and (ge.min() < 0 or ge.max() > n_perm):
+        raise ValueError("a count of replicates lies outside 0 .. n_perm")
+    return dict(mi_all=np.asarray(mi_obs, dtype=np.float64), perm_ge=ge, perm_p=(1.0 + ge) / (1.0 + n_perm),
+                null_max=np.asarray(null_max, dtype=np.float64), n_perm=np.full(len(ge), n_perm, dtype=np.int64))
+
+
 def sequence_clusters(snp_dat=None, *, threshold=0.1, snps=None, min_size: int = 1, small: str = "drop", engine=None, alignment_resident: bool = False):
     """Single-linkage clusters of the sequences: i and j are neighbours iff they differ in fewer than ``thresh`` SNP columns, ``thresh`` =
     ``int(L * threshold)`` — the rule of the Hamming weights — or the absolute ``snps``.  Either may be a list (up to 16 values, served from one Hamming
@@ -163,6 +179,50 @@ def link_lineage_mi(links, clusters, snp_dat=None, *, hdw=None, threshold: float
     if out_path is not None:
         _write_frame(df, out_path)
     return (df, res["mi"]) if per_cluster else df
+
+
+def link_permutation_test(links, clusters=None, snp_dat=None, *, n_perm: int = 1000, seed: int = 0, hdw=None, threshold: float = 0.1, engine=None,
+                          alignment_resident: bool = False, return_null: bool = False, out_path=None):
+    """``links`` — as ``link_lineage_mi`` takes them — with five columns appended, rows and order unchanged (``permutation_columns``): ``mi_all``,
+    ``perm_ge``, ``perm_p``, ``null_max`` and ``n_perm``.  Each of the ``n_perm`` replicates permutes the second SNP's states among the sequences of
+    every cluster and re-evaluates the weighted MI over all labelled sequences, so population structure that the clusters capture is in the null: a
+    pair of lineage markers keeps its table in every replicate (p = 1), a pair coupled inside the lineages gets a small p.  ``clusters``: as for
+    ``link_lineage_mi``; None means one cluster, the unrestricted test.  The weights are ``hdw``, or the Hamming weights at ``threshold``; they stay
+    with the sequences.  A replicate is a function of (clusters, ``seed``, its number) alone.  ``return_null=True`` returns (frame, the (K, n_perm)
+    matrix of the replicates' MI).  ``out_path``, ``engine`` / ``alignment_resident`` as for ``link_lineage_mi``.  Needs a GPU."""
+    import os
+    from .parsimony import _engine_for, _names, _snp_index
+    n_perm = int(n_perm)
+    if not 1 <= n_perm <= 1 << 24:
+        raise ValueError(f"n_perm must lie in 1 .. 2^24, got {n_perm}")
+    if isinstance(links, (str, bytes, os.PathLike)):
+        from .output import read_TopHits
+        links = read_TopHits(links)
+    df = links.copy()
+    a, b = _snp_index(snp_dat, df["pos1"], "link_permutation_test"), _snp_index(snp_dat, df["pos2"], "link_permutation_test")
+    eng, own = _engine_for(snp_dat, engine, alignment_resident, "link_permutation_test")
+    try:
+        if clusters is None:
+            labels, C = np.zeros(eng.N, dtype=np.int32), 1
+        else:
+            labels, C = cluster_labels(clusters, _names(snp_dat, eng.N))
+        if len(labels) != eng.N:
+            raise ValueError(f"{len(labels)} cluster labels for {eng.N} sequences")
+        if C < 1:
+            raise ValueError("link_permutation_test: no sequence has a cluster")
+        eng.set_weights(eng.hamming_weights(int(eng.L * float(threshold))) if hdw is None else hdw)
+        if len(df):
+            res = eng.links_permuted(a, b, labels, n_perm, seed=seed, C=C, want_null=return_null)
+        else:
+            res = dict(mi_obs=np.zeros(0), n_ge=np.zeros(0, dtype=np.int32), null_max=np.zeros(0), null=np.zeros((0, n_perm)))
+    finally:
+        if own:
+            eng.close()
+    for name, col in permutation_columns(res["mi_obs"], res["n_ge"], res["null_max"], n_perm).items():
+        df[name] = col
+    if out_path is not None:
+        _write_frame(df, out_path)
+    return (df, res["null"]) if return_null else df
 
 
 def _write_frame(df, path):
