@@ -124,10 +124,14 @@ int ldw_path_report(ldw_ctx *ctx, int64_t out[8], char *gate, int capacity);
 /* Kernel launches by form since the context was created, so that a test can tell which form of a size-dependent stage ran (results do not
  * depend on the form): the exact pair sums of the approximate path's listed pairs, two launches per block, out[0] walking the set bits against
  * a per-position weight table within the default 64 KB of LDS (k_pair_sums_bits), out[1] the same with the 160-KB dynamic-LDS attribute
- * (more than 8 192 padded sequences), out[2] class-wise popcounts with the segment tables in LDS (k_pair_sums), out[3] the same with the tables
- * in global memory (many weight classes beyond the bit walk's 160 KB, or LDW_NO_PAIR_BITS set); out[4] launches of the bit-row fill that
+ * (more than 8 192 padded sequences), out[2] class-wise popcounts with the segment tables in LDS (k_pair_sums_q, or k_pair_sums under
+ * LDW_PAIR_WAVE=1), out[3] the same with the tables in global memory (k_pair_sums: many weight classes beyond the bit walk's 160 KB, or LDW_NO_PAIR_BITS set); out[4] launches of the bit-row fill that
  * reads the states from global memory instead of staging a row in LDS (more than 61 440 padded sequences). */
 int ldw_pair_form_report(ldw_ctx *ctx, int64_t out[5]);
+/* Launches of the class-wise pair sums (out[2] + out[3] above) by kernel since the context was created: out[0] the kernel with a quarter-wave
+ * per pair and persistent waves (the default where the segment tables fit LDS), out[1] the kernel with a wave per pair (tables in global
+ * memory, or LDW_PAIR_WAVE=1, read per call).  Both give the same sums. */
+int ldw_pair_kernel_report(ldw_ctx *ctx, int64_t out[2]);
 /* tile pruning (ldw_set_prune): out[0] blocks whose rows were ordered, out[1] wave tiles pruned, out[2] wave tiles of the GEMMs that
  * could prune (both since the context was created; pruned tiles are not counted as executed work by ldw_gemm_stats), out[3] = on. */
 int ldw_prune_report(ldw_ctx *ctx, int64_t out[4]);

@@ -199,6 +199,7 @@ _SIGS_DEBUG = {
     "ldw_reset_speculation": (C.c_int, [_p]),
     "ldw_path_report": (C.c_int, [_p, _p, C.c_char_p, C.c_int]),
     "ldw_pair_form_report": (C.c_int, [_p, _p]),
+    "ldw_pair_kernel_report": (C.c_int, [_p, _p]),
     "ldw_prune_report": (C.c_int, [_p, _p]),
     "ldw_span_report": (C.c_int, [_p, _p]),
     "ldw_overflow_report": (C.c_int, [_p, _p]),

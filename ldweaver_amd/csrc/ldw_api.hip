@@ -437,6 +437,12 @@ int ldw_pair_form_report(ldw_ctx *c, int64_t out[5]) {
     return LDW_OK;
 }
 
+int ldw_pair_kernel_report(ldw_ctx *c, int64_t out[2]) {
+    LDW_REQUIRE(c && out, LDW_ERR_ARG, "ldw_pair_kernel_report: null argument");
+    for (int i = 0; i < 2; ++i) out[i] = c->cnt.pair_kernel_launches[i];
+    return LDW_OK;
+}
+
 int ldw_set_prune(ldw_ctx *c, int on) {
     LDW_REQUIRE(c, LDW_ERR_ARG, "null context");
     c->knobs.prune = on != 0;

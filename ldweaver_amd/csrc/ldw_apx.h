@@ -9,9 +9,11 @@
 // single limb: the pass that took 3 (mixed precision) or 5 limbs takes 1.
 //
 // What the screen lists gets EXACT joint sums.  Long-range candidates (one pair in a few thousand) are listed PAIR by pair and
-// need no GEMM at all: sum_s V_s x_s y_s = sum over 32-bit words and weight classes of V_class popcount(x & y & class mask), one
-// wave per pair, lane = word (k_pair_sums), then the fp64 MI (k_pair_mi).  Units that hold a short-range pair are listed
-// whole — the short-range band is dense — and evaluated from the exact 5-limb GEMM of just the tiles the band touches.
+// need no GEMM at all: sum_s V_s x_s y_s = sum over 32-bit words and weight classes of V_class popcount(x & y & class mask), a
+// quarter-wave per pair, four pairs per persistent wave, a lane holding two words of every 32 (k_pair_sums_q; k_pair_sums, a wave per
+// pair with lane = word, where the segment tables do not fit LDS or LDW_PAIR_WAVE=1), then the fp64 MI (k_pair_mi).  Units that hold a
+// short-range pair are listed whole — the short-range band is dense — and evaluated from the exact 5-limb GEMM of just the tiles the
+// band touches.
 #pragma once
 #include "ldw_internal.h"
 #include "ldw_epi.h"

@@ -2,7 +2,7 @@
 //   prepare_apx_weights  host: dual digits a, b and block exponents of the weights, popcount segments of the weight classes
 //   k_pack_panel         per block side: bit rows of the row list, transposed to [macro step][row][2 words]
 //   gemm_apx_kernel      one int8 MFMA pass, both operands masked digits -> int32 approximate joint sums (screen input)
-//   k_pair_sums / k_pair_mi  exact joint sums of the listed candidate pairs by class-wise popcounts, fp64 MI, emission
+//   k_pair_sums_q (k_pair_sums, k_pair_sums_bits) / k_pair_mi  exact joint sums of the listed candidate pairs by class-wise popcounts, fp64 MI, emission
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -674,11 +674,14 @@ int apx_run_grid(const ldw_ctx *c, int RTpad, int RFpad) {
 
 // ------------------------------------------------------------------------------------------------
 // The long-range candidates listed pair by pair (units without a short-range pair), in two kernels:
+//   k_pair_sums_q<CA, CB>  a QUARTER-WAVE per pair (the 16 lanes of a DPP row), four pairs per wave, persistent waves: the default where
+//                        the segment tables fit LDS (its own comment below; r08).  The same sums as:
 //   k_pair_sums<CA, CB>  one WAVE per pair, lane = 32-bit word of the bit rows (coalesced 256-B reads of the pair's CA + CB rows
 //                        from the row-major bit matrix).  sum_s V_s x_s y_s = sum_words sum_segments V_class popcount(x & y & mask):
 //                        every lane multiplies the popcounts of ITS words by the class weight at once (one 64-bit multiply-add
 //                        per segment) and a wave reduction adds the lanes up: no per-class flush, no serial walk over the row.
 //                        The CA * CB exact sums of pair i of list `sub` go to sums[(sub * cap + i) * 16 + j * 4 + i].
+//                        Runs where the tables stay in global memory, and under LDW_PAIR_WAVE=1 (the reference of the tests).
 //   k_pair_mi<NA, NB>    one LANE per pair: the sums -> fp64 MI -> emission (candidate list + histogram).
 // One pair in a few thousand gets here.
 // ------------------------------------------------------------------------------------------------
@@ -831,6 +834,259 @@ __global__ __launch_bounds__(256) void k_pair_sums(PairArgs P) {
             case 1: pair_sums_body<2, 1>(P, 1, s_wbeg, s_segs); break;
             case 2: pair_sums_body<1, 2>(P, 2, s_wbeg, s_segs); break;
             default: pair_sums_body<2, 2>(P, 3, s_wbeg, s_segs); break;
+        }
+    }
+}
+
+// r08: the same class-wise sums with a QUARTER-WAVE per pair and persistent waves (the default where the segment tables fit LDS; LDW_PAIR_WAVE=1
+// launches the kernels above instead).  The 16 lanes of a DPP row own one pair, a wave works on four pairs at once.  Lane l of a row holds the words
+// 32 k + 2 l, 32 k + 2 l + 1 of every row of its pair (one dwordx2 per row and step: a row of lanes reads 128 contiguous bytes), words past nwords
+// read as zero.  The segments of those words are the same for every pair and stay in registers for PQ_KQ steps (160 words: 5 120 sequences), two per
+// word; a word with more goes through the table in LDS, and so do the words of longer rows.  A workgroup stages the tables once, takes its one
+// barrier, and its waves then walk the eight shards of their path as one index space (a prefix over the clamped counts) in strides of the whole
+// grid, so a short shard idles nobody.  The loads of a wave's next four pairs (whose list entries were asked for one turn earlier still) are issued
+// before the arithmetic of the current four.  The sixteen partial sums of a row are added with four DPP steps (two quad_perm, row_half_mirror,
+// row_mirror), carry included; lane 0 of the row stores them where k_pair_mi reads them.  Same int64 terms in another order: the same sums.
+constexpr int PQ_KQ = 5, PQ_KS = 2;
+constexpr int PQ_WGS_PER_CU = 2;   // workgroups per CU and path (LDW_PAIR_GRID: A/B; profiles/r08_pair_sums_quarter.txt)
+
+template <int CTRL>
+__device__ __forceinline__ int64_t dpp_add64(int64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)((uint64_t)v >> 32), CTRL, 0xF, 0xF, false);
+    return v + (int64_t)(((uint64_t)hi << 32) | (uint64_t)lo);
+}
+// the sum over the 16 lanes of a DPP row, in every lane of it (all 64 lanes active)
+__device__ __forceinline__ int64_t row16_sum(int64_t v) {
+    v = dpp_add64<0xB1>(v);    // quad_perm [1, 0, 3, 2]
+    v = dpp_add64<0x4E>(v);    // quad_perm [2, 3, 0, 1]
+    v = dpp_add64<0x141>(v);   // row_half_mirror
+    v = dpp_add64<0x140>(v);   // row_mirror
+    return v;
+}
+
+template <int CA, int CB, bool PREF>
+__device__ __forceinline__ void pair_sums_q_body(const PairArgs &P, int path, const int32_t *s_wbeg, const PopSeg *s_segs) {
+    constexpr bool GENB = CA == 4 && CB == 4;
+    constexpr int KQ = PQ_KQ, KS = PQ_KS;
+    const EpiArgs &A = P.A;
+    const int lane = threadIdx.x & 63, l = lane & 15, grp = lane >> 4;
+    // the eight shards of the path as one index space
+    unsigned int pre[PAIR_SHARDS + 1];
+    pre[0] = 0u;
+#pragma unroll
+    for (int s = 0; s < PAIR_SHARDS; ++s) {
+        const unsigned int n = A.pl_n[path * PAIR_SHARDS + s];
+        pre[s + 1] = pre[s] + (n > A.pl_cap ? A.pl_cap : n);
+    }
+    const unsigned int total = pre[PAIR_SHARDS];
+    const unsigned int nwv = gridDim.x * 4u;
+    unsigned int t = blockIdx.x * 4u + (threadIdx.x >> 6);   // four pairs 4 t .. 4 t + 3 per turn of a wave
+    if (4u * t >= total) return;
+    const PairEnt *lists = A.pl_pairs + (int64_t)path * PAIR_SHARDS * A.pl_cap;
+    auto locate = [&](unsigned int p, int &shard, unsigned int &idx) {
+        shard = 0;
+        unsigned int base = 0u;
+#pragma unroll
+        for (int s = 1; s < PAIR_SHARDS; ++s)
+            if (p >= pre[s]) shard = s, base = pre[s];
+        idx = p - base;
+    };
+    // (ra, rb) of this row's pair of turn tt; (0, 0) — no rows — behind the end of the lists
+    auto load_ent = [&](unsigned int tt) -> uint2 {
+        const unsigned int p = 4u * tt + (unsigned int)grp;
+        if (p >= total) return make_uint2(0u, 0u);
+        int shard;
+        unsigned int idx;
+        locate(p, shard, idx);
+        const PairEnt *e = lists + (int64_t)shard * A.pl_cap + idx;
+        return make_uint2(e->ra, e->rb);
+    };
+    auto row_ptr = [&](uint32_t r, int i) -> const uint2 * {
+        const int r0 = (int)(r & 0x1FFFFFFFu), n = (int)(r >> 29);
+        return reinterpret_cast<const uint2 *>(P.Mbits + (int64_t)(i < n ? r0 + i : P.zero_row) * P.KW);
+    };
+    auto issue_rows = [&](uint2 e, uint2 (&f)[KQ][CA], uint2 (&tt)[KQ][CB]) {
+        const int na = (int)(e.x >> 29), nb = (int)(e.y >> 29);
+#pragma unroll
+        for (int i = 0; i < CA; ++i) {
+            const uint2 *fr = row_ptr(e.x, i);
+#pragma unroll
+            for (int k = 0; k < KQ; ++k) f[k][i] = (32 * k + 2 * l < P.nwords && (!GENB || i < na)) ? fr[16 * k + l] : make_uint2(0u, 0u);
+        }
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+            const uint2 *tr = row_ptr(e.y, j);
+#pragma unroll
+            for (int k = 0; k < KQ; ++k) tt[k][j] = (32 * k + 2 * l < P.nwords && (!GENB || j < nb)) ? tr[16 * k + l] : make_uint2(0u, 0u);
+        }
+    };
+    // the segments of THIS lane's words (the same in the four rows of the wave)
+    uint32_t smask[KQ][2][KS];
+    int64_t sV[KQ][2][KS];
+    uint32_t more = 0u;
+#pragma unroll
+    for (int k = 0; k < KQ; ++k)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int w = 32 * k + 2 * l + h;
+            int s0 = 0, s1 = 0;
+            if (w < P.nwords) {
+                s0 = s_wbeg[w] & 0x7FFFFFFF;
+                s1 = s_wbeg[w + 1] & 0x7FFFFFFF;
+            }
+            const bool mr = s1 - s0 > KS;
+            if (mr) more |= 1u << (2 * k + h);
+#pragma unroll
+            for (int q = 0; q < KS; ++q) {
+                const bool on = s0 + q < s1 && !mr;
+                smask[k][h][q] = on ? s_segs[s0 + q].mask : 0u;
+                sV[k][h][q] = on ? s_segs[s0 + q].V : 0;
+            }
+        }
+    uint2 e_cur = load_ent(t);
+    uint2 f[KQ][CA], tt[KQ][CB];
+    issue_rows(e_cur, f, tt);
+    unsigned int tn = t + nwv;
+    uint2 e_nx = load_ent(tn);
+    for (;;) {
+        const bool has_nx = 4u * tn < total;   // wave-uniform
+        uint2 fn[KQ][CA], tnx[KQ][CB];
+        uint2 e_nx2 = make_uint2(0u, 0u);
+        if (PREF && has_nx) {
+            issue_rows(e_nx, fn, tnx);
+            e_nx2 = load_ent(tn + nwv);
+        }
+        const int na = (int)(e_cur.x >> 29), nb = (int)(e_cur.y >> 29);
+        // the predicated list: rows differ in (na, nb); an absent row was not loaded and adds zero, the loops stop at the wave's largest
+        int namax = CA, nbmax = CB;
+        if constexpr (GENB) {
+            namax = 1 + (__ballot(na >= 2) != 0ull) + (__ballot(na >= 3) != 0ull) + (__ballot(na >= 4) != 0ull);
+            nbmax = 1 + (__ballot(nb >= 2) != 0ull) + (__ballot(nb >= 3) != 0ull) + (__ballot(nb >= 4) != 0ull);
+        }
+        int64_t s[CB][CA];
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+#pragma unroll
+            for (int i = 0; i < CA; ++i) s[j][i] = 0;
+#pragma unroll
+        for (int k = 0; k < KQ; ++k) {
+            if (32 * k >= P.nwords) break;   // (uniform)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                uint32_t fw[CA], tw[CB];
+#pragma unroll
+                for (int i = 0; i < CA; ++i) fw[i] = h ? f[k][i].y : f[k][i].x;
+#pragma unroll
+                for (int j = 0; j < CB; ++j) tw[j] = h ? tt[k][j].y : tt[k][j].x;
+#pragma unroll
+                for (int q = 0; q < KS; ++q)
+#pragma unroll
+                    for (int j = 0; j < CB; ++j)
+#pragma unroll
+                        for (int i = 0; i < CA; ++i)
+                            if (!GENB || (i < namax && j < nbmax)) s[j][i] += (int64_t)((uint64_t)__popc(fw[i] & tw[j] & smask[k][h][q]) * (uint64_t)sV[k][h][q]);
+                if ((more >> (2 * k + h)) & 1u) {   // more than KS segments in this lane's word (its registers hold none of them)
+                    const int w = 32 * k + 2 * l + h;
+                    const int s0 = s_wbeg[w] & 0x7FFFFFFF, s1 = s_wbeg[w + 1] & 0x7FFFFFFF;
+                    for (int sg = s0; sg < s1; ++sg) {
+                        const PopSeg seg = s_segs[sg];
+#pragma unroll
+                        for (int j = 0; j < CB; ++j)
+#pragma unroll
+                            for (int i = 0; i < CA; ++i)
+                                if (!GENB || (i < namax && j < nbmax)) s[j][i] += (int64_t)((uint64_t)__popc(fw[i] & tw[j] & seg.mask) * (uint64_t)seg.V);
+                    }
+                }
+            }
+        }
+        if (32 * KQ < P.nwords) {   // longer rows: the rest through the table (absent rows: the row of zeros)
+            const uint2 *fr[CA], *tr[CB];
+#pragma unroll
+            for (int i = 0; i < CA; ++i) fr[i] = row_ptr(e_cur.x, i);
+#pragma unroll
+            for (int j = 0; j < CB; ++j) tr[j] = row_ptr(e_cur.y, j);
+            for (int w2 = 16 * KQ + l; 2 * w2 < P.nwords; w2 += 16) {
+                uint2 f2[CA], t2[CB];
+#pragma unroll
+                for (int i = 0; i < CA; ++i) f2[i] = fr[i][w2];
+#pragma unroll
+                for (int j = 0; j < CB; ++j) t2[j] = tr[j][w2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int w = 2 * w2 + h;
+                    const int s0 = s_wbeg[w] & 0x7FFFFFFF, s1 = s_wbeg[w + 1] & 0x7FFFFFFF;
+                    for (int sg = s0; sg < s1; ++sg) {
+                        const PopSeg seg = s_segs[sg];
+#pragma unroll
+                        for (int j = 0; j < CB; ++j)
+#pragma unroll
+                            for (int i = 0; i < CA; ++i)
+                                if (!GENB || (i < namax && j < nbmax))
+                                    s[j][i] += (int64_t)((uint64_t)__popc((h ? f2[i].y : f2[i].x) & (h ? t2[j].y : t2[j].x) & seg.mask) * (uint64_t)seg.V);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+#pragma unroll
+            for (int i = 0; i < CA; ++i)
+                if (!GENB || (i < namax && j < nbmax)) s[j][i] = row16_sum(s[j][i]);
+        const unsigned int p = 4u * t + (unsigned int)grp;
+        if (l == 0 && p < total) {
+            int shard;
+            unsigned int idx;
+            locate(p, shard, idx);
+            int64_t *o = P.sums + ((int64_t)(path * PAIR_SHARDS + shard) * A.pl_cap + idx) * 16;
+#pragma unroll
+            for (int j = 0; j < CB; ++j)
+#pragma unroll
+                for (int i = 0; i < CA; ++i) o[j * 4 + i] = s[j][i];
+        }
+        if (!has_nx) break;
+        t = tn;
+        tn += nwv;
+        e_cur = e_nx;
+        if constexpr (PREF) {
+#pragma unroll
+            for (int k = 0; k < KQ; ++k) {
+#pragma unroll
+                for (int i = 0; i < CA; ++i) f[k][i] = fn[k][i];
+#pragma unroll
+                for (int j = 0; j < CB; ++j) tt[k][j] = tnx[k][j];
+            }
+            e_nx = e_nx2;
+        } else {
+            issue_rows(e_cur, f, tt);
+            e_nx = load_ent(tn);
+        }
+    }
+}
+
+template <bool GEN>
+__global__ __launch_bounds__(256) void k_pair_sums_q(PairArgs P) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t pop_smem[];
+    int32_t *s_wbeg = reinterpret_cast<int32_t *>(pop_smem);
+    PopSeg *s_segs = reinterpret_cast<PopSeg *>(pop_smem + (((size_t)P.nwords + 4) * 4 + 15) / 16 * 16);
+    const int path = GEN ? 4 : (int)blockIdx.z;
+    unsigned int total = 0u;
+    for (int s = 0; s < PAIR_SHARDS; ++s) {
+        const unsigned int n = P.A.pl_n[path * PAIR_SHARDS + s];
+        total += n > P.A.pl_cap ? P.A.pl_cap : n;
+    }
+    if (blockIdx.x * 16u >= total) return;   // nothing for this workgroup
+    for (int i = threadIdx.x; i < P.nwords + 1; i += 256) s_wbeg[i] = P.wbeg[i];
+    for (int i = threadIdx.x; i < P.nseg; i += 256) s_segs[i] = P.segs[i];
+    __syncthreads();
+    if constexpr (GEN) {
+        pair_sums_q_body<4, 4, false>(P, 4, s_wbeg, s_segs);
+    } else {
+        switch (path) {
+            case 0: pair_sums_q_body<1, 1, true>(P, 0, s_wbeg, s_segs); break;
+            case 1: pair_sums_q_body<2, 1, true>(P, 1, s_wbeg, s_segs); break;
+            case 2: pair_sums_q_body<1, 2, true>(P, 2, s_wbeg, s_segs); break;
+            default: pair_sums_q_body<2, 2, true>(P, 3, s_wbeg, s_segs); break;
         }
     }
 }
@@ -1053,7 +1309,7 @@ int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, 
     P.sums = sums;
     P.A = A;
     P.ghist = ghist;
-    // 1024 waves per list stride over its pairs (one wave per pair), then one lane per pair for the fp64 value
+    // the exact sums of every list (a quarter-wave per pair, or one of the wave-per-pair forms below), then one lane per pair for the fp64 value
     size_t lds = (((size_t)P.nwords + 4) * 4 + 15) / 16 * 16 + (size_t)P.nseg * sizeof(PopSeg);
     P.seg_in_lds = lds <= 60000 ? 1 : 0;
     if (!P.seg_in_lds) lds = 0;
@@ -1074,7 +1330,17 @@ int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, 
         hipLaunchKernelGGL(k_pair_sums_bits<false>, dim3(256, PAIR_SHARDS, 4), dim3(256), lds_bits, st, P, c->apx.pop_vpos.as<int64_t>(), stride);
         hipLaunchKernelGGL(k_pair_sums_bits<true>, dim3(256, PAIR_SHARDS, 1), dim3(256), lds_bits, st, P, c->apx.pop_vpos.as<int64_t>(), stride);
         c->cnt.form_launches[lds_bits > 64 * 1024 ? 1 : 0] += 2;
+    } else if (const char *wv = getenv("LDW_PAIR_WAVE"); P.seg_in_lds && !(wv && atoi(wv) != 0)) {   // (read per call: the tests run both kernels)
+        // r08: a quarter-wave per pair, persistent waves: LDW_PAIR_GRID (or PQ_WGS_PER_CU) workgroups per CU for every path; those beyond a
+        // path's pairs leave before staging
+        static const unsigned per_cu_env = [] { const char *e = getenv("LDW_PAIR_GRID"); return e ? (unsigned)atoi(e) : 0u; }();
+        const unsigned gx = (per_cu_env ? per_cu_env : (unsigned)PQ_WGS_PER_CU) * (unsigned)std::max(c->n_cu, 1);
+        hipLaunchKernelGGL(k_pair_sums_q<false>, dim3(gx, 1, 4), dim3(256), lds, st, P);
+        hipLaunchKernelGGL(k_pair_sums_q<true>, dim3(gx, 1, 1), dim3(256), lds, st, P);
+        c->cnt.form_launches[2] += 2;
+        c->cnt.pair_kernel_launches[0] += 2;
     } else {
+        c->cnt.pair_kernel_launches[1] += 2;
         // (grid: r06 — 512 / 1024 workgroups per list instead of 256: 67 -> 61 and 34 -> 23 us per launch; 128 / 64 / 32: 96 / 150 / 236 us.  A 1-D grid whose
         // waves share the pairs of all lists evenly was built too: no better (64 / 42 us) — the long launches are not a matter of balance.  LDW_PAIR_GRID: A/B)
         static const unsigned gx_env = [] { const char *e = getenv("LDW_PAIR_GRID"); return e ? (unsigned)atoi(e) : 0u; }();

@@ -261,6 +261,8 @@ struct PassCounters {
     // launches by form (ldw_pair_form_report): [0] k_pair_sums_bits within the default 64 KB of LDS, [1] k_pair_sums_bits with the 160-KB attribute,
     // [2] k_pair_sums with its segment tables in LDS, [3] k_pair_sums with them in global memory, [4] k_fill_rows_bits in its global-memory form
     int64_t form_launches[5] = {0, 0, 0, 0, 0};
+    // launches of the class-wise pair sums by kernel (ldw_pair_kernel_report): [0] a quarter-wave per pair (k_pair_sums_q), [1] a wave per pair (k_pair_sums)
+    int64_t pair_kernel_launches[2] = {0, 0};
     int64_t apx_waves_skipped = 0, apx_waves_total = 0;
     int64_t tab11_builds = 0;
     int64_t slot_grown = 0;              // reallocations of a slot buffer where it is used (launch_block_apx; ldw_slot_report out[0])

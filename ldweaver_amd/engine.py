@@ -120,6 +120,13 @@ class Engine:
         L.check(L.lib().ldw_pair_form_report(self._ctx, L.ptr(v)))
         return dict(bits_lds64=int(v[0]), bits_lds160=int(v[1]), classwise_lds=int(v[2]), classwise_global=int(v[3]), fill_rows_global=int(v[4]))
 
+    def pair_kernel_report(self):
+        """Launches of the class-wise pair sums by kernel since the context was created (ldw_pair_kernel_report): a quarter-wave per pair
+        (the default), a wave per pair (LDW_PAIR_WAVE=1, or segment tables in global memory)."""
+        v = np.zeros(2, dtype=np.int64)
+        L.check(L.lib().ldw_pair_kernel_report(self._ctx, L.ptr(v)))
+        return dict(quarter_wave=int(v[0]), wave=int(v[1]))
+
     def set_prune(self, on: bool):
         """Tile pruning of the approximate path (default on): rows ordered by minor-state weight, rare x rare tiles never computed."""
         L.check(L.lib().ldw_set_prune(self._ctx, int(bool(on))))
