@@ -183,6 +183,19 @@ int ldw_debug_tab11(ldw_ctx *ctx, double W, double lo, double delta, double eta,
  * ldw_debug_apx_gemm_list: the same contract and the same values through the kernel's LIST launch (the default path's, without its table test): a list of every
  *   wave tile (128 to-rows x 64 from-rows) that holds an entry of out, walked by grid_wgs workgroups (1..65536) of four waves — wave w takes the tiles w, w + 4 grid_wgs,
  *   ... of the list; workgroups beyond the list leave at once.
+ * ldw_debug_pair_sums: the exact joint sums of caller-made pair lists, by the sum kernels alone (no MI, no emission) and through the launch code of the default path.
+ *   The lists are those of the approximate screen: 5 paths x 8 shards, list = path * 8 + shard, paths 0..3 for SNP pairs of (1,1), (2,1), (1,2), (2,2) indicator rows
+ *   (from side, to side), path 4 for any 1..4 x 1..4.  counts[40] = entries of every list (a count above cap is clamped by the kernels, as after an overflow);
+ *   snp_a / snp_b[40][cap] = the SNPs of the entries (from side, to side), read up to min(count, cap) per list.  form: 0 = what the default path would launch, 1 = a
+ *   quarter-wave per pair (k_pair_sums_q), 2 / 3 = a wave per pair with the segment tables in LDS / in global memory (k_pair_sums), 4 = the bit walk
+ *   (k_pair_sums_bits); *form_out (may be NULL) = the form that ran.  grid_wgs: 0 = the default path's grid, else (1..65536) gridDim.x of both launches — the whole
+ *   grid of a path for form 1 (wave w of the 4 grid_wgs waves takes the groups of four pairs w, w + 4 grid_wgs, ... of the path's eight shards walked as one index
+ *   space), workgroups per list for the others.  sums_out[40][cap][16] int64: entry j * 4 + i of a pair = sum over the sequences of the fixed-point weight where
+ *   SNP a is in the state of its row i and SNP b in that of its row j; paths 0..3 write the rows x rows entries k_pair_mi reads, path 4 all sixteen (0 for an absent
+ *   row).  The buffer is filled with bytes LDW_DEBUG_PAIR_SUMS_FILL before the launches: every int64 the kernels did not write still holds that pattern.
+ *   LDW_ERR_STATE: no weights set, or a forced form cannot run (forms 1, 2: the segment tables exceed 60 000 B of LDS; form 4: the per-position table exceeds
+ *   160 KB); LDW_ERR_ARG: cap outside 1..65536, an SNP outside 0..L-1, row counts that are not the list's.  Nothing is launched then, and no launch counter
+ *   (ldw_pair_form_report, ldw_pair_kernel_report) ever moves.  tests/test_pair_sums_fn_gpu.py compares every form with the integer sums of numpy.
  * ldw_debug_screen_bound: the engine's own device functions on n caller-made joint tables (arrays by case: g[16] = sums of the indicator rows, g[j * 4 + i] = slot i of the
  *   from-side SNP x slot j of the to-side SNP; pa / pb[5] integer marginals by slot; pX / pY[5] weighted marginals; rr[3] = r_a, r_b, RXY; masks[2] = slot meta of both SNPs,
  *   kinds 1 / 3 only; params = the 20 numbers of ldw_debug_apx_params, which the caller may alter).  kind 0: full_cells_screen<na, nb, APX> — the approximate path's upper
@@ -192,6 +205,9 @@ int ldw_debug_apx_params(ldw_ctx *ctx, double out[20], int64_t *vfixed_out, int6
 int ldw_debug_rows(ldw_ctx *ctx, int32_t *row0_out, uint32_t *slot_meta_out, int64_t capacity);
 int ldw_debug_apx_gemm(ldw_ctx *ctx, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int32_t *out);
 int ldw_debug_apx_gemm_list(ldw_ctx *ctx, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int grid_wgs, int32_t *out);
+#define LDW_DEBUG_PAIR_SUMS_FILL 0xA5 /* every byte of sums_out the kernels did not write */
+int ldw_debug_pair_sums(ldw_ctx *ctx, int form, int grid_wgs, uint32_t cap, const uint32_t *counts, const int32_t *snp_a, const int32_t *snp_b, int64_t *sums_out,
+                        int *form_out);
 int ldw_debug_screen_bound(ldw_ctx *ctx, int kind, int na, int nb, int64_t n, const int64_t *g, const int64_t *pa, const int64_t *pb, const float *pX, const float *pY,
                            const double *rr, const uint32_t *masks, const double params[20], float *out, double *out64);
 

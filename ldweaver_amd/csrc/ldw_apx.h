@@ -77,7 +77,18 @@ int launch_gemm_apx(ldw_ctx *c, const ApxGemmArgs &P, hipStream_t st);
 // ApxGemmArgs::grid_wgs of the default path for a block of RTpad x RFpad rows: APX_RUNS_R workgroups per resident slot (two slots per CU of the
 // context's device) or what LDW_APX_GRID_WGS asks for, never more than the worst case; 0 under LDW_NO_APX_RUNS=1.  Both read per call.
 int apx_run_grid(const ldw_ctx *c, int RTpad, int RFpad);
-// the pair lists of A (filled by the approximate screen): exact sums, fp64 MI, emission
+// The forms of the exact pair sums (the numbers of ldw_debug_pair_sums): a quarter-wave per pair (k_pair_sums_q), a wave per pair with the segment
+// tables in LDS / in global memory (k_pair_sums), the bit walk (k_pair_sums_bits).
+enum PairForm : int { PAIR_FORM_AUTO = 0, PAIR_FORM_QUARTER = 1, PAIR_FORM_WAVE_LDS = 2, PAIR_FORM_WAVE_GLOBAL = 3, PAIR_FORM_BITS = 4 };
+struct PairSumsRan {
+    int form = 0;          // the form that was launched (1..4)
+    bool lds160 = false;   // the bit walk with the 160-KB dynamic-LDS attribute
+};
+// The sums alone, sums[(list * A.pl_cap + i) * 16 + j * 4 + i'] of the lists A.pl_pairs / A.pl_n / A.pl_cap (nothing else of A is read): form
+// PAIR_FORM_AUTO = the product's choice, else that form or LDW_ERR_STATE where it cannot run; grid_wgs 0 = the product's grid, else gridDim.x of
+// both launches (the quarter-wave kernel: the whole grid of a path; the others: workgroups per list).  Counts nothing.
+int launch_pair_sums(ldw_ctx *c, const EpiArgs &A, int64_t *sums, hipStream_t st, int form, int grid_wgs, PairSumsRan *ran);
+// the pair lists of A (filled by the approximate screen): exact sums (launch_pair_sums(.., PAIR_FORM_AUTO, 0)), fp64 MI, emission
 int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, int64_t *sums, hipStream_t st);
 
 }  // namespace ldw

@@ -1295,7 +1295,7 @@ __global__ __launch_bounds__(256) void k_pair_mi(PairArgs P) {
         atomicAdd(&P.ghist[hb0 + threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
 }
 
-int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, int64_t *sums, hipStream_t st) {
+static PairArgs make_pair_args(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, int64_t *sums) {
     PairArgs P;
     memset(&P, 0, sizeof(P));
     P.Mbits = c->rows.Mbits.as<uint64_t>();
@@ -1309,45 +1309,83 @@ int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, 
     P.sums = sums;
     P.A = A;
     P.ghist = ghist;
-    // the exact sums of every list (a quarter-wave per pair, or one of the wave-per-pair forms below), then one lane per pair for the fp64 value
+    return P;
+}
+
+// The exact sums of every list: chooses the form (PAIR_FORM_*; form 0) or takes the caller's (ldw_debug_pair_sums; LDW_ERR_STATE where that form cannot
+// run, before anything is launched) and launches its two kernels.  grid_wgs 0: the product's grid; else gridDim.x of both launches.
+int launch_pair_sums(ldw_ctx *c, const EpiArgs &A, int64_t *sums, hipStream_t st, int form, int grid_wgs, PairSumsRan *ran) {
+    PairArgs P = make_pair_args(c, A, nullptr, sums);
     size_t lds = (((size_t)P.nwords + 4) * 4 + 15) / 16 * 16 + (size_t)P.nseg * sizeof(PopSeg);
-    P.seg_in_lds = lds <= 60000 ? 1 : 0;
-    if (!P.seg_in_lds) lds = 0;
+    const bool fits = lds <= 60000;
     // r05: many weight classes (the segment tables do not fit LDS) -> walk the set bits against a per-position weight table in LDS instead, as long as
     // THAT fits (256 B per word of a row: 40 KB at N = 5120, 80 KB at 10 240; beyond 160 KB — N > 20 480 — the class-wise kernel reads its tables from global memory)
     const int stride = (P.nwords + 31) / 32 * 32;
     const size_t lds_bits = (size_t)32 * stride * 8;
-    const bool bits_off = getenv("LDW_NO_PAIR_BITS") != nullptr;   // (read per call: A/B, and the test runs both forms)
-    // (which form: the class-wise one costs a popcount per SEGMENT — 1.3 segments per word with C4's 57 clonal classes —, the bit walk an LDS read per
-    // co-occurring position; from ~8 segments per word on, i.e. weightings whose classes are a few sequences each, the bits are fewer than the segments)
-    const bool many_classes = !P.seg_in_lds || P.nseg >= 8 * P.nwords;
-    if (many_classes && !bits_off && lds_bits <= 160 * 1024 && c->apx.pop_vpos.p) {
+    const bool bits_can = lds_bits <= 160 * 1024 && c->apx.pop_vpos.p;
+    if (form == PAIR_FORM_AUTO) {
+        const bool bits_off = getenv("LDW_NO_PAIR_BITS") != nullptr;   // (read per call: A/B, and the test runs both forms)
+        // (which form: the class-wise one costs a popcount per SEGMENT — 1.3 segments per word with C4's 57 clonal classes —, the bit walk an LDS read per
+        // co-occurring position; from ~8 segments per word on, i.e. weightings whose classes are a few sequences each, the bits are fewer than the segments)
+        const bool many_classes = !fits || P.nseg >= 8 * P.nwords;
+        const char *wv = getenv("LDW_PAIR_WAVE");   // (read per call: the tests run both kernels)
+        if (many_classes && !bits_off && bits_can) form = PAIR_FORM_BITS;
+        else if (fits && !(wv && atoi(wv) != 0)) form = PAIR_FORM_QUARTER;
+        else form = fits ? PAIR_FORM_WAVE_LDS : PAIR_FORM_WAVE_GLOBAL;
+    } else {
+        LDW_REQUIRE(form >= PAIR_FORM_QUARTER && form <= PAIR_FORM_BITS, LDW_ERR_ARG, "pair sums: form %d outside 0..4", form);
+        LDW_REQUIRE(fits || (form != PAIR_FORM_QUARTER && form != PAIR_FORM_WAVE_LDS), LDW_ERR_STATE,
+                    "pair sums: form %d needs the popcount segment tables in LDS (%zu B > 60000 B)", form, lds);
+        LDW_REQUIRE(form != PAIR_FORM_BITS || bits_can, LDW_ERR_STATE, "pair sums: the bit walk needs a per-position weight table of at most 160 KB of LDS (%zu B)",
+                    lds_bits);
+    }
+    P.seg_in_lds = (fits && form != PAIR_FORM_WAVE_GLOBAL) ? 1 : 0;
+    if (!P.seg_in_lds) lds = 0;
+    const unsigned gforce = grid_wgs > 0 ? (unsigned)grid_wgs : 0u;
+    if (form == PAIR_FORM_BITS) {
         if (lds_bits > 64 * 1024 && !c->pair_bits_attr) {
             LDW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_sums_bits<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             LDW_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_sums_bits<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             c->pair_bits_attr = true;
         }
-        hipLaunchKernelGGL(k_pair_sums_bits<false>, dim3(256, PAIR_SHARDS, 4), dim3(256), lds_bits, st, P, c->apx.pop_vpos.as<int64_t>(), stride);
-        hipLaunchKernelGGL(k_pair_sums_bits<true>, dim3(256, PAIR_SHARDS, 1), dim3(256), lds_bits, st, P, c->apx.pop_vpos.as<int64_t>(), stride);
-        c->cnt.form_launches[lds_bits > 64 * 1024 ? 1 : 0] += 2;
-    } else if (const char *wv = getenv("LDW_PAIR_WAVE"); P.seg_in_lds && !(wv && atoi(wv) != 0)) {   // (read per call: the tests run both kernels)
+        const unsigned gx = gforce ? gforce : 256u;
+        hipLaunchKernelGGL(k_pair_sums_bits<false>, dim3(gx, PAIR_SHARDS, 4), dim3(256), lds_bits, st, P, c->apx.pop_vpos.as<int64_t>(), stride);
+        hipLaunchKernelGGL(k_pair_sums_bits<true>, dim3(gx, PAIR_SHARDS, 1), dim3(256), lds_bits, st, P, c->apx.pop_vpos.as<int64_t>(), stride);
+    } else if (form == PAIR_FORM_QUARTER) {
         // r08: a quarter-wave per pair, persistent waves: LDW_PAIR_GRID (or PQ_WGS_PER_CU) workgroups per CU for every path; those beyond a
-        // path's pairs leave before staging
+        // path's pairs leave before staging.  LDW_PAIR_GRID_WGS (read per call: the tests force turns on small lists) sets the whole grid of a path.
         static const unsigned per_cu_env = [] { const char *e = getenv("LDW_PAIR_GRID"); return e ? (unsigned)atoi(e) : 0u; }();
-        const unsigned gx = (per_cu_env ? per_cu_env : (unsigned)PQ_WGS_PER_CU) * (unsigned)std::max(c->n_cu, 1);
+        unsigned gx = (per_cu_env ? per_cu_env : (unsigned)PQ_WGS_PER_CU) * (unsigned)std::max(c->n_cu, 1);
+        if (const char *e = getenv("LDW_PAIR_GRID_WGS")) {
+            const int k = atoi(e);
+            if (k > 0 && k <= 65536) gx = (unsigned)k;
+        }
+        if (gforce) gx = gforce;
         hipLaunchKernelGGL(k_pair_sums_q<false>, dim3(gx, 1, 4), dim3(256), lds, st, P);
         hipLaunchKernelGGL(k_pair_sums_q<true>, dim3(gx, 1, 1), dim3(256), lds, st, P);
-        c->cnt.form_launches[2] += 2;
-        c->cnt.pair_kernel_launches[0] += 2;
     } else {
-        c->cnt.pair_kernel_launches[1] += 2;
         // (grid: r06 — 512 / 1024 workgroups per list instead of 256: 67 -> 61 and 34 -> 23 us per launch; 128 / 64 / 32: 96 / 150 / 236 us.  A 1-D grid whose
         // waves share the pairs of all lists evenly was built too: no better (64 / 42 us) — the long launches are not a matter of balance.  LDW_PAIR_GRID: A/B)
         static const unsigned gx_env = [] { const char *e = getenv("LDW_PAIR_GRID"); return e ? (unsigned)atoi(e) : 0u; }();
-        hipLaunchKernelGGL(k_pair_sums<false>, dim3(gx_env ? gx_env : 512u, PAIR_SHARDS, 4), dim3(256), lds, st, P);
-        hipLaunchKernelGGL(k_pair_sums<true>, dim3(gx_env ? gx_env : 1024u, PAIR_SHARDS, 1), dim3(256), lds, st, P);
-        c->cnt.form_launches[P.seg_in_lds ? 2 : 3] += 2;
+        hipLaunchKernelGGL(k_pair_sums<false>, dim3(gforce ? gforce : gx_env ? gx_env : 512u, PAIR_SHARDS, 4), dim3(256), lds, st, P);
+        hipLaunchKernelGGL(k_pair_sums<true>, dim3(gforce ? gforce : gx_env ? gx_env : 1024u, PAIR_SHARDS, 1), dim3(256), lds, st, P);
     }
+    ran->form = form;
+    ran->lds160 = form == PAIR_FORM_BITS && lds_bits > 64 * 1024;
+    return LDW_OK;
+}
+
+int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, int64_t *sums, hipStream_t st) {
+    // the exact sums of every list (a quarter-wave per pair, or one of the wave-per-pair forms), then one lane per pair for the fp64 value
+    PairSumsRan ran;
+    if (int rc = launch_pair_sums(c, A, sums, st, PAIR_FORM_AUTO, 0, &ran)) return rc;
+    switch (ran.form) {
+        case PAIR_FORM_BITS: c->cnt.form_launches[ran.lds160 ? 1 : 0] += 2; break;
+        case PAIR_FORM_QUARTER: c->cnt.form_launches[2] += 2, c->cnt.pair_kernel_launches[0] += 2; break;
+        case PAIR_FORM_WAVE_LDS: c->cnt.form_launches[2] += 2, c->cnt.pair_kernel_launches[1] += 2; break;
+        default: c->cnt.form_launches[3] += 2, c->cnt.pair_kernel_launches[1] += 2; break;
+    }
+    const PairArgs P = make_pair_args(c, A, ghist, sums);
     hipLaunchKernelGGL(k_pair_mi, dim3(64, PAIR_SHARDS, PAIR_PATHS), dim3(256), 0, st, P);
     LDW_HIP(hipGetLastError());
     return LDW_OK;

@@ -4,6 +4,7 @@
 //   ldw_debug_apx_params    the dual-digit weights V' of the current weighting and every constant the approximate screen's bound is built from
 //   ldw_debug_rows          SNP -> indicator rows (which state each row stands for)
 //   ldw_debug_apx_gemm      gemm_apx_kernel on caller-chosen rows: the int32 sums G' (truncation bound apx_lost_units)
+//   ldw_debug_pair_sums     the exact sums of caller-made pair lists through launch_pair_sums (every form, a forced grid), without k_pair_mi
 //   ldw_debug_screen_bound  full_cells_screen / pair_screen_generic (fp32; APX and exact-limb forms) and full_cells_mi (fp64) on caller-made tables
 // Nothing here is on the product path; the kernels are the product's own device functions (ldw_epi.h), instantiated once more.
 #include <algorithm>
@@ -224,6 +225,59 @@ static int debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int3
     LDW_HIP(hipStreamSynchronize(c->stream));
     for (int t = 0; t < nrt; ++t) memcpy(out + (size_t)t * nrf, h.data() + (size_t)t * RFpad, (size_t)nrf * 4);
     return LDW_OK;
+}
+
+int ldw_debug_pair_sums(ldw_ctx *c, int form, int grid_wgs, uint32_t cap, const uint32_t *counts, const int32_t *snp_a, const int32_t *snp_b, int64_t *sums_out,
+                        int *form_out) {
+    if (int rc = check_gpu(c)) return rc;
+    if (int rc = join_prepare(c)) return rc;
+    LDW_REQUIRE(counts && snp_a && snp_b && sums_out, LDW_ERR_ARG, "ldw_debug_pair_sums: null argument");
+    LDW_REQUIRE(cap >= 1 && cap <= 65536, LDW_ERR_ARG, "ldw_debug_pair_sums: list capacity %u outside 1..65536", cap);
+    LDW_REQUIRE(form >= 0 && form <= 4, LDW_ERR_ARG, "ldw_debug_pair_sums: form %d outside 0..4", form);
+    LDW_REQUIRE(grid_wgs >= 0 && grid_wgs <= 65536, LDW_ERR_ARG, "ldw_debug_pair_sums: grid of %d workgroups outside 0..65536", grid_wgs);
+    LDW_REQUIRE(c->wts.have_weights && c->apx.pop_segs.p && c->apx.pop_wbeg.p, LDW_ERR_STATE, "ldw_debug_pair_sums: the weight tables of the approximate path are not prepared (ldw_set_weights)");
+    if (int rc = ensure_rows(c)) return rc;
+    constexpr int NL = PAIR_PATHS * PAIR_SHARDS;
+    static const int path_na[4] = {1, 2, 1, 2}, path_nb[4] = {1, 1, 2, 2};
+    // the entries as flush_pairs (ldw_mi_screen.inc) writes them: first bit row | row count << 29 of both SNPs
+    std::vector<PairEnt> ents((size_t)NL * cap, PairEnt{0u, 0u, 0u, 0u});
+    for (int sub = 0; sub < NL; ++sub) {
+        const int path = sub / PAIR_SHARDS;
+        const uint32_t n = std::min(counts[sub], cap);
+        for (uint32_t k = 0; k < n; ++k) {
+            const size_t at = (size_t)sub * cap + k;
+            const int64_t a = snp_a[at], b = snp_b[at];
+            LDW_REQUIRE(a >= 0 && a < c->L && b >= 0 && b < c->L, LDW_ERR_ARG, "ldw_debug_pair_sums: list %d entry %u: SNPs (%lld, %lld) outside 0..L-1", sub, k, (long long)a,
+                        (long long)b);
+            const int32_t r0a = c->rows.h_row0[(size_t)a], r0b = c->rows.h_row0[(size_t)b];
+            const int na = c->rows.h_row0[(size_t)a + 1] - r0a, nb = c->rows.h_row0[(size_t)b + 1] - r0b;
+            if (path < 4) LDW_REQUIRE(na == path_na[path] && nb == path_nb[path], LDW_ERR_ARG, "ldw_debug_pair_sums: list %d entry %u: %d x %d rows in the list of %d x %d", sub, k, na, nb, path_na[path], path_nb[path]);
+            else LDW_REQUIRE(na >= 1 && na <= 4 && nb >= 1 && nb <= 4, LDW_ERR_ARG, "ldw_debug_pair_sums: list %d entry %u: %d x %d rows outside 1..4", sub, k, na, nb);
+            ents[at] = PairEnt{k, k, (uint32_t)r0a | ((uint32_t)na << 29), (uint32_t)r0b | ((uint32_t)nb << 29)};
+        }
+    }
+    const size_t n_sums = (size_t)NL * cap * 16;
+    DevBuf d_n, d_ents, d_sums;
+    if (int rc = d_n.reserve(NL * 4)) return rc;
+    if (int rc = d_ents.reserve(ents.size() * sizeof(PairEnt))) return rc;
+    if (int rc = d_sums.reserve(n_sums * 8)) return rc;
+    LDW_HIP(hipMemcpyAsync(d_n.p, counts, NL * 4, hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemcpyAsync(d_ents.p, ents.data(), ents.size() * sizeof(PairEnt), hipMemcpyHostToDevice, c->stream));
+    LDW_HIP(hipMemsetAsync(d_sums.p, LDW_DEBUG_PAIR_SUMS_FILL, n_sums * 8, c->stream));   // (a store outside the entries k_pair_mi reads shows)
+    EpiArgs A;
+    memset(&A, 0, sizeof(A));
+    A.pl_n = d_n.as<unsigned int>();
+    A.pl_pairs = d_ents.as<PairEnt>();
+    A.pl_cap = cap;
+    PairSumsRan ran;
+    const int rc = launch_pair_sums(c, A, d_sums.as<int64_t>(), c->stream, form, grid_wgs, &ran);
+    if (rc == LDW_OK) {
+        LDW_HIP(hipGetLastError());
+        LDW_HIP(hipMemcpyAsync(sums_out, d_sums.p, n_sums * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    LDW_HIP(hipStreamSynchronize(c->stream));   // (the uploads read this frame)
+    if (rc == LDW_OK && form_out) *form_out = ran.form;
+    return rc;
 }
 
 int ldw_debug_screen_bound(ldw_ctx *c, int kind, int na, int nb, int64_t n, const int64_t *g, const int64_t *pa, const int64_t *pb, const float *pX, const float *pY,

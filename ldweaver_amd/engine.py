@@ -219,6 +219,26 @@ class Engine:
             L.check(L.lib().ldw_debug_apx_gemm_list(self._ctx, L.ptr(rt), len(rt), L.ptr(rf), len(rf), int(grid_wgs), L.ptr(out)))
         return out
 
+    PAIR_PATHS, PAIR_SHARDS = 5, 8
+    PAIR_FORMS = ("auto", "quarter_wave", "wave_lds", "wave_global", "bits")
+    PAIR_SUMS_FILL = int(np.frombuffer(bytes([0xA5] * 8), dtype=np.int64)[0])
+
+    def debug_pair_sums(self, counts, snp_a, snp_b, form: int = 0, grid_wgs: int = 0):
+        """The exact joint sums of caller-made pair lists by the sum kernels alone (ldw_debug_pair_sums): counts[40] entries per list (list = path * 8 +
+        shard; a count above the capacity is clamped by the kernels), snp_a / snp_b [40, cap] the SNPs of the entries.  form: an index of PAIR_FORMS
+        (0: what the default path would launch), grid_wgs: gridDim.x of both launches (0: the default path's).  Returns (sums int64 [40, cap, 16], the
+        form that ran); whatever the kernels did not write holds PAIR_SUMS_FILL."""
+        nl = self.PAIR_PATHS * self.PAIR_SHARDS
+        cnt = np.ascontiguousarray(counts, dtype=np.uint32).reshape(nl)
+        a = np.ascontiguousarray(snp_a, dtype=np.int32)
+        b = np.ascontiguousarray(snp_b, dtype=np.int32)
+        assert a.shape == b.shape and a.size % nl == 0, (a.shape, b.shape)
+        cap = a.size // nl
+        out = np.zeros((nl, cap, 16), dtype=np.int64)
+        ran = C.c_int(0)
+        L.check(L.lib().ldw_debug_pair_sums(self._ctx, int(form), int(grid_wgs), cap, L.ptr(cnt), L.ptr(a), L.ptr(b), L.ptr(out), C.byref(ran)))
+        return out, int(ran.value)
+
     def debug_screen_bound(self, kind: int, na: int, nb: int, g, pa, pb, pX, pY, rr, params, masks=None):
         """The engine's screen / evaluation device functions on caller-made joint tables (ldw_debug_screen_bound): kind 0 / 1 the approximate path's upper
         bounds (straight-line / predicated), 2 / 3 the fp32 MI of the exact-limb screens, 4 the fp64 value the engine emits."""

@@ -7,7 +7,10 @@ approximate path and listed pairs.
 
 Shapes.  Sequence counts at the word edges of a 16-lane row (a lane holds the 32-bit words 32 k + 2 l, 32 k + 2 l + 1 of a bit row): N = 33
 (Npad 128: four words, two lanes of sixteen busy), 513, 1 000 (32 words: one step), 2 049 (Npad 2 176: 68 words, the third step holds two
-lanes) and 5 000 (160 words: all five steps whose segments stay in registers).  L = 2 000 SNPs in blocks of 600: diagonal blocks and single
+lanes), 5 000 (160 words: all five steps whose segments stay in registers) and 5 121 (164 words: the first step through the table, two lanes
+busy).  At 513 and 5 121 a fourth and a fifth way run the quarter-wave kernel under LDW_PAIR_GRID_WGS=1 and =3, a whole grid of one and three
+workgroups per path: a block's few thousand pairs then take dozens of turns of the persistent waves, where the default grid takes one or two (as
+functions, against integer sums: tests/test_pair_sums_fn_gpu.py).  L = 2 000 SNPs in blocks of 600: diagonal blocks and single
 off-diagonal blocks, square and ragged (spans need blocks of 2 048 SNPs and more: tests/test_gpu_parity.py runs them on the default path).
 SNPs with one, two and three minor states at high frequency are planted by clonal group (so that they are in LD with each other over any
 distance), and lr_retain_links is 0.65 % of the long-range pairs (a pass speculates up to 0.7 %), so pairs of every shape — the four
@@ -32,15 +35,15 @@ SR_DIST = 20000.0
 LR_FRAC = 0.0065         # of the long-range pairs: just below the 0.7 % up to which a pass speculates at all
 
 
-def _alignment(N, seed):
+def _alignment(N, seed, Ls=LS, device="cuda"):
     """synth_alignment plus planted multi-state SNPs: every 3rd SNP gets a second minor state in the sequences of every 3rd clonal group,
     every 7th SNP a second and a third one (groups 1 and 2 of 4), every 13th a fourth (state 4) as well.  Group membership is the same for
     every planted SNP, so they are in LD with each other at any distance."""
-    syn = synth_alignment(LS, N, seed=seed, device="cuda", as_numpy=False)
+    syn = synth_alignment(Ls, N, seed=seed, device=device, as_numpy=False)
     st = syn["states"]
     rs = np.random.default_rng(seed + 1)
     grp = torch.as_tensor(rs.integers(0, 12, N), device=st.device)
-    rows = torch.arange(LS, device=st.device)
+    rows = torch.arange(Ls, device=st.device)
     base = st[:, :1]                                   # column 0 holds every SNP's major allele (synth_alignment)
 
     def other(k):                                      # a base k steps from the major one
@@ -73,15 +76,19 @@ def _hand_weights(N):
     return np.random.default_rng(N).permutation(w)
 
 
-def _run(syn, hdw, env, plain, pair_cap=0):
-    """A fresh engine: one cold and one warm pass.  Returns per pass (sr table, lr table, block_stats) and the reports' deltas."""
+def _run(syn, hdw, env, plain, pair_cap=0, grid=0):
+    """A fresh engine: one cold and one warm pass.  Returns per pass (sr table, lr table, block_stats) and the reports' deltas.
+    grid: LDW_PAIR_GRID_WGS, the whole grid of a path of the quarter-wave kernel (read per call)."""
     blocks = MIH.make_blocks(LS, BLK)
     approx = MIH.lr_links_approx(syn["POS"], float(syn["g"]), SR_DIST)
     out = []
     old = os.environ.pop("LDW_PAIR_WAVE", None)
+    assert "LDW_PAIR_GRID_WGS" not in os.environ
     try:
         if env:
             os.environ["LDW_PAIR_WAVE"] = "1"
+        if grid:
+            os.environ["LDW_PAIR_GRID_WGS"] = str(grid)
         Engine.set_pair_cap(pair_cap)
         with Engine(0) as eng:
             eng.set_engine(L.ENGINE_MFMA)
@@ -108,6 +115,7 @@ def _run(syn, hdw, env, plain, pair_cap=0):
     finally:
         Engine.set_pair_cap(0)
         os.environ.pop("LDW_PAIR_WAVE", None)
+        os.environ.pop("LDW_PAIR_GRID_WGS", None)
         if old is not None:
             os.environ["LDW_PAIR_WAVE"] = old
     return out, rep
@@ -121,7 +129,7 @@ def _same(x, y, what):
         assert np.array_equal(x[2][k], y[2][k]), (what, k)
 
 
-def _three_ways(syn, hdw, pair_cap=0):
+def _three_ways(syn, hdw, pair_cap=0, grids=()):
     plain, rp = _run(syn, hdw, env=False, plain=True)
     quarter, rq = _run(syn, hdw, env=False, plain=False, pair_cap=pair_cap)
     wave, rw = _run(syn, hdw, env=True, plain=False, pair_cap=pair_cap)
@@ -143,14 +151,31 @@ def _three_ways(syn, hdw, pair_cap=0):
     for k, tag in enumerate(("cold", "warm")):
         _same(plain[k], quarter[k], ("quarter-wave", tag))
         _same(plain[k], wave[k], ("wave per pair", tag))
+    # a fourth and a fifth way: the quarter-wave kernel with a whole grid of `grid` workgroups per path, 16 pairs per workgroup and turn.  Five paths
+    # share a block's pairs, so 10 x 16 x grid pairs per block put 32 x grid and more into some path of some block: every wave of it turns twice and more
+    for grid in grids:
+        forced, rf = _run(syn, hdw, env=False, plain=False, pair_cap=pair_cap, grid=grid)
+        per_block = rf["path"]["pairs_listed"] / rf["path"]["apx_blocks"]
+        print(f"grid {grid}:", rf["path"], rf["kern"], f"{per_block:.0f} pairs per block = {per_block / (16 * grid):.1f} turns of the grid")
+        assert rf["kern"]["quarter_wave"] > 0 and rf["kern"]["wave"] == 0, rf
+        assert rf["form"]["classwise_lds"] == rf["kern"]["quarter_wave"] and rf["form"]["bits_lds64"] == 0 and rf["form"]["classwise_global"] == 0, rf
+        assert rf["path"]["apx_gate"].startswith("ok") and rf["path"]["apx_blocks"] > 0 and rf["cnt"]["screen_violations"] == 0, rf
+        assert per_block >= 10 * 16 * grid, (grid, rf["path"])
+        # (a wrong sum can hide behind the fall-back: a block whose candidates miss the guessed bucket is redone on the plain path and the tables
+        # come out right.  The grid changes no value, so it changes no block's fate either)
+        for k in ("spec_misses", "plain_blocks", "pairs_listed", "units_listed"):
+            assert rf["path"][k] == rq["path"][k], (grid, k, rf["path"], rq["path"])
+        for k, tag in enumerate(("cold", "warm")):
+            _same(plain[k], forced[k], (f"quarter-wave, grid of {grid}", tag))
     return rq, rw
 
 
-@pytest.mark.parametrize("N", [33, 513, 1000, 2049, 5000])
+@pytest.mark.parametrize("N", [33, 513, 1000, 2049, 5000, 5121])
 def test_quarter_wave_sums_at_the_word_edges_of_a_row(N):
-    """Hamming weights (a few clonal classes) at sequence counts around the word edges of a 16-lane row."""
+    """Hamming weights (a few clonal classes) at sequence counts around the word edges of a 16-lane row; at 513 and 5 121 (164 words: the first
+    step past the registers, two lanes busy) also under whole grids of one and three workgroups, where the persistent waves turn several times."""
     syn = _alignment(N, 100 + N)
-    rq, rw = _three_ways(syn, None)
+    rq, rw = _three_ways(syn, None, grids=(1, 3) if N in (513, 5121) else ())
     assert rq["over"]["pair_list"] == 0 and rw["over"]["pair_list"] == 0, (rq, rw)
 
 
