@@ -183,6 +183,33 @@ int ldw_debug_tab11(ldw_ctx *ctx, double W, double lo, double delta, double eta,
  * ldw_debug_apx_gemm_list: the same contract and the same values through the kernel's LIST launch (the default path's, without its table test): a list of every
  *   wave tile (128 to-rows x 64 from-rows) that holds an entry of out, walked by grid_wgs workgroups (1..65536) of four waves — wave w takes the tiles w, w + 4 grid_wgs,
  *   ... of the list; workgroups beyond the list leave at once.
+ * ldw_debug_limb_gemm: the exact co-occurrence GEMMs as functions: launch_gemm_bits (engine 0: gemm_bits_kernel<J>) or launch_cooc_popc (engine 1: k_cooc_popc), unchanged, over
+ *   caller-given indicator rows of the context's current bit rows and weights.  rows_t[nrt] / rows_f[nrf] (1..8192 each): row indices 0..R, R = the all-zero padding row; both
+ *   lists are padded to multiples of 128 with R (RTpad, RFpad).  Engine 0: the launch gets the digit limbs limb0 .. limb0 + nlimbs - 1 of the weights (digits + limb0 * Kpad, as
+ *   the mixed path asks for its three high limbs), nlimbs in 1..6 (six run as 3 + 3: the second launch shifts by 24 bits and accumulates), limb0 >= 0 and limb0 + nlimbs <= the
+ *   limb count of ldw_set_weights; lower_only: the launch of a diagonal block (tiles of 128 to-rows x 64 from-rows with bx * 64 + 63 < by * 128 are left out); by0, by1: the strip
+ *   of tile rows by0 <= by < by1 (by1 < 0: all RTpad / 128); tile_mask (may be NULL): [RTpad / 128][RFpad / 64] bytes, 0 = the tile is left out; tile_list (may be NULL) with
+ *   n_tile_list entries by << 16 | bx (by < RTpad / 128, bx < RFpad / 64; at most 65 536): a 1-D launch over exactly these tiles, whatever lower_only and the mask say — the engine
+ *   passes the mask with the list, so both may be given; n_tile_list = 0 is a legal launch of nothing (LDW_OK); a list needs by0 = 0.  Engine 1 takes limb0 = 0, all the limbs,
+ *   no mask, no list and no strip; its lower_only rule is on tiles of 64 x 64 rows (tx * 64 + 63 < ty * 64 is left out).  out[nrt][nrf] int64:
+ *   out[t][f] = sum over the sequences s of V_part(s) [row t has s][row f has s],  V_part = sum_j d_(limb0 + j) 256^j  over the balanced base-256 digits d of the fixed-point weight.
+ *   The device buffer is filled with bytes LDW_DEBUG_LIMB_GEMM_FILL before the launch: every int64 no kernel wrote still holds that pattern.
+ *   LDW_ERR_STATE: no weights set (engine 1: no popcount segments); LDW_ERR_ARG: engine outside 0..1, a row outside 0..R, nrt / nrf outside 1..8192, nlimbs outside 1..6, limbs
+ *   beyond the context's, by0 >= by1 or a strip outside the tile rows, a list with by0 != 0, more than 65 536 entries or a tile outside the grid, n_tile_list != 0 without a list.
+ *   Nothing is launched then and out is not written; the counters of ldw_gemm_stats never move, refused or not.  tests/test_limb_gemm_fn_gpu.py compares every stored integer
+ *   with the integer sums of numpy.
+ * ldw_debug_lo_units: the gathered low-limb GEMM of the mixed path (launch_gemm_lo_units: gemm_lo_units_kernel) on caller-made unit lists.  from_snps[64 * ntiles] (ntiles in
+ *   1..4096): the from-side SNPs in epilogue order, tile t = entries 64 t .. 64 t + 63, -1 = a padding lane; to_snps[nt] (nt in 1..1 048 576): any SNPs 0..L-1, repeats allowed:
+ *   column slot q stands for to_snps[q].  counts[ntiles][3]: listed units per (tile, row-slot class lc = 0, 1, 2 for SNPs of <= 1, 2, >= 3 indicator rows); slots[]: the listed
+ *   column slots of every (tile, lc) one list behind the other, tiles outermost (sum of counts entries).  A slot listed under lc must hold a SNP of that class, and a (tile, lc)
+ *   lists at most as many units as to_snps holds SNPs of the class (the capacity of its rows).  The geometry is made by lo_layout (csrc/ldw_lo_geom.h), the function prep_block
+ *   lays a block out with: geom_out[8] = rowbase[3], uoff[3], RTlo, (tile, fs) pairs of the launch; cmax_out[ntiles] = 1, 2, 4: slots per from-side SNP of the tile;
+ *   tile_base_out[ntiles]: first int of the tile's block in glo; *glo_total_out: ints of glo.  glo_out == NULL: the geometry alone, nothing is launched.  Else glo_out[glo_capacity],
+ *   glo_capacity >= glo total: the raw buffer, filled with bytes LDW_DEBUG_LO_UNITS_FILL before the launch.  For unit k of (tile, lc) — column slot q = its k-th listed slot — row j
+ *   of SNP to_snps[q] and slot i of the SNP in lane ln of the tile, the int32 at tile_base[tile] + (rowbase[lc] + (k << lc) + j) * 64 cmax + ln * cmax + i is
+ *   sum_s (d_0(s) + 256 d_1(s)) [to row has s][from row has s]; absent rows, absent slots and padding lanes give 0; the rows of a chunk of 128 beyond the last listed unit are
+ *   written as 0; chunks no list reaches keep the fill.  Needs weights of at least two limbs (LDW_ERR_STATE) and at most 65 535 (tile, fs) pairs; LDW_ERR_ARG for SNPs, slots or
+ *   counts outside these bounds and for a buffer above 2^28 ints; nothing is launched then.
  * ldw_debug_pair_sums: the exact joint sums of caller-made pair lists, by the sum kernels alone (no MI, no emission) and through the launch code of the default path.
  *   The lists are those of the approximate screen: 5 paths x 8 shards, list = path * 8 + shard, paths 0..3 for SNP pairs of (1,1), (2,1), (1,2), (2,2) indicator rows
  *   (from side, to side), path 4 for any 1..4 x 1..4.  counts[40] = entries of every list (a count above cap is clamped by the kernels, as after an overflow);
@@ -205,6 +232,12 @@ int ldw_debug_apx_params(ldw_ctx *ctx, double out[20], int64_t *vfixed_out, int6
 int ldw_debug_rows(ldw_ctx *ctx, int32_t *row0_out, uint32_t *slot_meta_out, int64_t capacity);
 int ldw_debug_apx_gemm(ldw_ctx *ctx, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int32_t *out);
 int ldw_debug_apx_gemm_list(ldw_ctx *ctx, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int grid_wgs, int32_t *out);
+#define LDW_DEBUG_LIMB_GEMM_FILL 0xA5 /* every byte of out no kernel wrote */
+int ldw_debug_limb_gemm(ldw_ctx *ctx, int engine, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int limb0, int nlimbs, int lower_only, int by0, int by1,
+                        const uint8_t *tile_mask, const uint32_t *tile_list, int n_tile_list, int64_t *out);
+#define LDW_DEBUG_LO_UNITS_FILL 0xA5 /* every byte of glo_out the kernel did not write */
+int ldw_debug_lo_units(ldw_ctx *ctx, const int32_t *from_snps, int ntiles, const int32_t *to_snps, int nt, const uint32_t *counts, const int32_t *slots, int32_t geom_out[8],
+                       int32_t *cmax_out, int64_t *tile_base_out, int64_t *glo_total_out, int32_t *glo_out, int64_t glo_capacity);
 #define LDW_DEBUG_PAIR_SUMS_FILL 0xA5 /* every byte of sums_out the kernels did not write */
 int ldw_debug_pair_sums(ldw_ctx *ctx, int form, int grid_wgs, uint32_t cap, const uint32_t *counts, const int32_t *snp_a, const int32_t *snp_b, int64_t *sums_out,
                         int *form_out);

@@ -4,6 +4,8 @@
 //   ldw_debug_apx_params    the dual-digit weights V' of the current weighting and every constant the approximate screen's bound is built from
 //   ldw_debug_rows          SNP -> indicator rows (which state each row stands for)
 //   ldw_debug_apx_gemm      gemm_apx_kernel on caller-chosen rows: the int32 sums G' (truncation bound apx_lost_units)
+//   ldw_debug_limb_gemm     launch_gemm_bits / launch_cooc_popc on caller-chosen rows, limbs, strips, masks and tile lists: the exact int64 sums, every entry the launch left alone
+//   ldw_debug_lo_units      launch_gemm_lo_units on caller-made unit lists, laid out by lo_layout (ldw_lo_geom.h) as prep_block lays out a block: the raw low-limb buffer
 //   ldw_debug_pair_sums     the exact sums of caller-made pair lists through launch_pair_sums (every form, a forced grid), without k_pair_mi
 //   ldw_debug_screen_bound  full_cells_screen / pair_screen_generic (fp32; APX and exact-limb forms) and full_cells_mi (fp64) on caller-made tables
 // Nothing here is on the product path; the kernels are the product's own device functions (ldw_epi.h), instantiated once more.
@@ -14,6 +16,7 @@
 
 #include "ldw_apx.h"
 #include "ldw_dev.h"
+#include "ldw_gemm_tile.h"
 
 using namespace ldw;
 
@@ -225,6 +228,171 @@ static int debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int3
     LDW_HIP(hipStreamSynchronize(c->stream));
     for (int t = 0; t < nrt; ++t) memcpy(out + (size_t)t * nrf, h.data() + (size_t)t * RFpad, (size_t)nrf * 4);
     return LDW_OK;
+}
+
+int ldw_debug_limb_gemm(ldw_ctx *c, int engine, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int limb0, int nlimbs, int lower_only, int by0, int by1,
+                        const uint8_t *tile_mask, const uint32_t *tile_list, int n_tile_list, int64_t *out) {
+    if (int rc = check_gpu(c)) return rc;
+    if (int rc = join_prepare(c)) return rc;
+    LDW_REQUIRE(engine == 0 || engine == 1, LDW_ERR_ARG, "ldw_debug_limb_gemm: engine %d outside 0..1", engine);
+    LDW_REQUIRE(rows_t && rows_f && out && nrt > 0 && nrf > 0 && nrt <= 8192 && nrf <= 8192, LDW_ERR_ARG, "ldw_debug_limb_gemm: bad argument");
+    LDW_REQUIRE(c->wts.have_weights && c->wts.digits.p, LDW_ERR_STATE, "ldw_debug_limb_gemm: no weights (ldw_set_weights)");
+    if (int rc = ensure_rows(c)) return rc;
+    for (int k = 0; k < nrt; ++k) LDW_REQUIRE(rows_t[k] >= 0 && rows_t[k] <= c->rows.R, LDW_ERR_ARG, "ldw_debug_limb_gemm: to-side row %d = %d outside 0..R", k, rows_t[k]);
+    for (int k = 0; k < nrf; ++k) LDW_REQUIRE(rows_f[k] >= 0 && rows_f[k] <= c->rows.R, LDW_ERR_ARG, "ldw_debug_limb_gemm: from-side row %d = %d outside 0..R", k, rows_f[k]);
+    const int RTpad = (nrt + TILE - 1) / TILE * TILE, RFpad = (nrf + TILE - 1) / TILE * TILE, nby = RTpad / TILE, nbx = RFpad / TILE_F4;
+    // everything the launch code would refuse, and what it trusts (the tiles of a list), before anything is queued
+    LDW_REQUIRE(nlimbs >= 1 && nlimbs <= 6, LDW_ERR_ARG, "ldw_debug_limb_gemm: nlimbs %d outside 1..6", nlimbs);
+    LDW_REQUIRE(limb0 >= 0 && limb0 + nlimbs <= c->wts.nlimbs, LDW_ERR_ARG, "ldw_debug_limb_gemm: limbs %d..%d beyond the %d of the weights", limb0, limb0 + nlimbs - 1, c->wts.nlimbs);
+    const int by_end = by1 < 0 ? nby : by1;
+    LDW_REQUIRE(by0 >= 0 && by0 < by_end && by_end <= nby, LDW_ERR_ARG, "ldw_debug_limb_gemm: bad tile-row range %d..%d of %d", by0, by1, nby);
+    LDW_REQUIRE(tile_list || n_tile_list == 0, LDW_ERR_ARG, "ldw_debug_limb_gemm: %d listed tiles without a list", n_tile_list);
+    if (tile_list) {
+        LDW_REQUIRE(n_tile_list >= 0 && n_tile_list <= 65536 && by0 == 0, LDW_ERR_ARG, "ldw_debug_limb_gemm: bad tile list (%d entries, by0 %d)", n_tile_list, by0);
+        for (int k = 0; k < n_tile_list; ++k)
+            LDW_REQUIRE((int)(tile_list[k] >> 16) < nby && (int)(tile_list[k] & 0xFFFFu) < nbx, LDW_ERR_ARG, "ldw_debug_limb_gemm: listed tile %d = (%u, %u) outside the %d x %d grid", k,
+                        tile_list[k] >> 16, tile_list[k] & 0xFFFFu, nby, nbx);
+    }
+    if (engine == 1) {
+        LDW_REQUIRE(limb0 == 0 && nlimbs == c->wts.nlimbs && !tile_mask && !tile_list && by0 == 0 && by_end == nby, LDW_ERR_ARG,
+                    "ldw_debug_limb_gemm: the popcount engine takes all limbs, no mask, no list and no strip");
+        LDW_REQUIRE(c->N <= 65535, LDW_ERR_ARG, "ldw_debug_limb_gemm: the popcount engine holds at most 65535 sequences (%lld)", (long long)c->N);
+        LDW_REQUIRE(c->apx.pop_segs.p && c->apx.pop_wbeg.p, LDW_ERR_STATE, "ldw_debug_limb_gemm: no popcount segments (ldw_set_weights)");
+    }
+    std::vector<int32_t> rl((size_t)RTpad + RFpad, (int32_t)c->rows.R);   // padding -> the all-zero row R
+    std::copy(rows_t, rows_t + nrt, rl.begin());
+    std::copy(rows_f, rows_f + nrf, rl.begin() + RTpad);
+    const size_t n_out = (size_t)RTpad * RFpad, n_mask = (size_t)nby * nbx;
+    DevBuf d_rl, d_G, d_mask, d_list;
+    if (int rc = d_rl.reserve(rl.size() * 4)) return rc;
+    if (int rc = d_G.reserve(n_out * 8)) return rc;
+    LDW_HIP(hipMemcpyAsync(d_rl.p, rl.data(), rl.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (tile_mask) {
+        if (int rc = d_mask.reserve(n_mask)) return rc;
+        LDW_HIP(hipMemcpyAsync(d_mask.p, tile_mask, n_mask, hipMemcpyHostToDevice, c->stream));
+    }
+    if (tile_list) {
+        if (int rc = d_list.reserve((size_t)std::max(1, n_tile_list) * 4)) return rc;
+        if (n_tile_list > 0) LDW_HIP(hipMemcpyAsync(d_list.p, tile_list, (size_t)n_tile_list * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    LDW_HIP(hipMemsetAsync(d_G.p, LDW_DEBUG_LIMB_GEMM_FILL, n_out * 8, c->stream));   // (an entry no kernel wrote shows)
+    double stat[6];
+    memcpy(stat, c->cnt.gemm_stat, sizeof(stat));   // the hook is no block-wide GEMM of a pass: ldw_gemm_stats does not see it
+    int rc;
+    if (engine == 1) rc = launch_cooc_popc(c, d_rl.as<int32_t>(), RTpad, d_rl.as<int32_t>() + RTpad, RFpad, d_G.as<int64_t>(), lower_only, c->stream);
+    else
+        rc = launch_gemm_bits(c, c->rows.Mbits.as<uint64_t>(), c->KW, d_rl.as<int32_t>(), RTpad, d_rl.as<int32_t>() + RTpad, RFpad, d_G.as<int64_t>(), nlimbs,
+                              c->wts.digits.as<int8_t>() + (int64_t)limb0 * c->KW * 64, lower_only, c->stream, by0, by1, tile_mask ? d_mask.as<uint8_t>() : nullptr,
+                              tile_list ? d_list.as<uint32_t>() : nullptr, n_tile_list);
+    memcpy(c->cnt.gemm_stat, stat, sizeof(stat));
+    std::vector<int64_t> h;
+    if (rc == LDW_OK) {
+        h.resize(n_out);
+        LDW_HIP(hipMemcpyAsync(h.data(), d_G.p, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    LDW_HIP(hipStreamSynchronize(c->stream));   // (the uploads read this frame)
+    if (rc != LDW_OK) return rc;
+    for (int t = 0; t < nrt; ++t) memcpy(out + (size_t)t * nrf, h.data() + (size_t)t * RFpad, (size_t)nrf * 8);
+    return LDW_OK;
+}
+
+int ldw_debug_lo_units(ldw_ctx *c, const int32_t *from_snps, int ntiles, const int32_t *to_snps, int nt, const uint32_t *counts, const int32_t *slots, int32_t geom_out[8],
+                       int32_t *cmax_out, int64_t *tile_base_out, int64_t *glo_total_out, int32_t *glo_out, int64_t glo_capacity) {
+    if (int rc = check_gpu(c)) return rc;
+    if (int rc = join_prepare(c)) return rc;
+    LDW_REQUIRE(from_snps && to_snps && counts && slots && geom_out && cmax_out && tile_base_out && glo_total_out, LDW_ERR_ARG, "ldw_debug_lo_units: null argument");
+    LDW_REQUIRE(ntiles >= 1 && ntiles <= 4096 && nt >= 1 && nt <= (1 << 20), LDW_ERR_ARG, "ldw_debug_lo_units: %d from-tiles (1..4096) or %d to-side SNPs (1..1048576)", ntiles, nt);
+    LDW_REQUIRE(c->wts.have_weights && c->wts.digits.p, LDW_ERR_STATE, "ldw_debug_lo_units: no weights (ldw_set_weights)");
+    LDW_REQUIRE(c->wts.nlimbs >= 2, LDW_ERR_STATE, "ldw_debug_lo_units: the weights have %d limb, the low-limb GEMM reads two", c->wts.nlimbs);
+    if (int rc = ensure_rows(c)) return rc;
+    const std::vector<int32_t> &row0 = c->rows.h_row0;
+    for (int k = 0; k < 64 * ntiles; ++k) LDW_REQUIRE(from_snps[k] >= -1 && from_snps[k] < c->L, LDW_ERR_ARG, "ldw_debug_lo_units: from-side lane %d = %d outside -1..L-1", k, from_snps[k]);
+    for (int k = 0; k < nt; ++k) LDW_REQUIRE(to_snps[k] >= 0 && to_snps[k] < c->L, LDW_ERR_ARG, "ldw_debug_lo_units: to-side SNP %d = %d outside 0..L-1", k, to_snps[k]);
+    auto rows_of = [&](int32_t snp) { return (int)(row0[(size_t)snp + 1] - row0[(size_t)snp]); };
+    std::vector<int32_t> cmax, tf;
+    std::vector<int64_t> tbase;
+    const LoLayout g = lo_layout(
+        nt, [&](int64_t k) { return rows_of(to_snps[k]); }, (size_t)64 * ntiles, [&](size_t t) { return from_snps[t] < 0 ? -1 : rows_of(from_snps[t]); }, cmax, tbase, tf);
+    LDW_REQUIRE(g.n_tf > 0 && g.n_tf <= 65535 && g.glo_total > 0 && g.glo_total <= ((int64_t)1 << 28), LDW_ERR_ARG, "ldw_debug_lo_units: %d (tile, fs) pairs or %lld ints of sums beyond the hook's limits",
+                g.n_tf, (long long)g.glo_total);
+    // the unit lists as k_mi_screen leaves them: tl[tile * nt + uoff[lc] + k] = the column slot
+    std::vector<uint32_t> tl((size_t)ntiles * nt, 0u), cnt((size_t)ntiles * 3);
+    size_t at = 0;
+    for (int t = 0; t < ntiles; ++t)
+        for (int lc = 0; lc < 3; ++lc) {
+            const uint32_t n = counts[t * 3 + lc];
+            LDW_REQUIRE(n <= (uint32_t)g.n_lc[lc], LDW_ERR_ARG, "ldw_debug_lo_units: tile %d lists %u units of class %d, the to side holds %d", t, n, lc, g.n_lc[lc]);
+            cnt[(size_t)t * 3 + lc] = n;
+            for (uint32_t k = 0; k < n; ++k, ++at) {
+                const int32_t q = slots[at];
+                LDW_REQUIRE(q >= 0 && q < nt && lo_class(rows_of(to_snps[q])) == lc, LDW_ERR_ARG, "ldw_debug_lo_units: tile %d class %d unit %u: slot %d outside 0..nt-1 or of another class", t, lc,
+                            k, q);
+                tl[(size_t)t * nt + g.uoff[lc] + k] = (uint32_t)q;
+            }
+        }
+    for (int k = 0; k < 3; ++k) {
+        geom_out[k] = g.rowbase[k];
+        geom_out[3 + k] = g.uoff[k];
+    }
+    geom_out[6] = g.RTlo;
+    geom_out[7] = g.n_tf;
+    std::copy(cmax.begin(), cmax.end(), cmax_out);
+    std::copy(tbase.begin(), tbase.end(), tile_base_out);
+    *glo_total_out = g.glo_total;
+    if (!glo_out) return LDW_OK;
+    LDW_REQUIRE(glo_capacity >= g.glo_total, LDW_ERR_SIZE, "ldw_debug_lo_units: capacity %lld < %lld ints", (long long)glo_capacity, (long long)g.glo_total);
+    std::vector<int32_t> idx_f((size_t)c->L), perm_t((size_t)nt);   // from side: the lanes name their SNPs; to side: slot q is entry q
+    for (int64_t k = 0; k < c->L; ++k) idx_f[(size_t)k] = (int32_t)k;
+    for (int k = 0; k < nt; ++k) perm_t[(size_t)k] = k;
+    DevBuf d_pf, d_if, d_pt, d_it, d_cmax, d_tb, d_tf, d_cnt, d_tl, d_glo;
+    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> int {
+        if (int rc = b.reserve(bytes)) return rc;
+        LDW_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+        return LDW_OK;
+    };
+    if (int rc = up(d_pf, from_snps, (size_t)64 * ntiles * 4)) return rc;
+    if (int rc = up(d_if, idx_f.data(), idx_f.size() * 4)) return rc;
+    if (int rc = up(d_pt, perm_t.data(), perm_t.size() * 4)) return rc;
+    if (int rc = up(d_it, to_snps, (size_t)nt * 4)) return rc;
+    if (int rc = up(d_cmax, cmax.data(), cmax.size() * 4)) return rc;
+    if (int rc = up(d_tb, tbase.data(), tbase.size() * 8)) return rc;
+    if (int rc = up(d_tf, tf.data(), tf.size() * 4)) return rc;
+    if (int rc = up(d_cnt, cnt.data(), cnt.size() * 4)) return rc;
+    if (int rc = up(d_tl, tl.data(), tl.size() * 4)) return rc;
+    if (int rc = d_glo.reserve((size_t)g.glo_total * 4 + 64)) return rc;
+    LDW_HIP(hipMemsetAsync(d_glo.p, LDW_DEBUG_LO_UNITS_FILL, (size_t)g.glo_total * 4, c->stream));
+    LoGemmArgs P;
+    memset(&P, 0, sizeof(P));
+    P.Mbits = c->rows.Mbits.as<uint64_t>();
+    P.KW = c->KW;
+    P.Kpad = c->KW * 64;
+    P.digits_lo = c->wts.digits.as<int8_t>();
+    P.perm_f = d_pf.as<int32_t>();
+    P.idx_f = d_if.as<int32_t>();
+    P.perm_t = d_pt.as<int32_t>();
+    P.idx_t = d_it.as<int32_t>();
+    P.row0 = c->rows.row0.as<int32_t>();
+    P.zero_row = (int32_t)c->rows.R;
+    P.nf = 64 * ntiles;
+    P.nt = nt;
+    P.tf_list = d_tf.as<int32_t>();
+    for (int k = 0; k < 3; ++k) {
+        P.lo.n_lc[k] = g.n_lc[k];
+        P.lo.uoff[k] = g.uoff[k];
+        P.lo.rowbase[k] = g.rowbase[k];
+    }
+    P.lo.RTlo = g.RTlo;
+    P.lo.ntiles = g.ntiles;
+    P.lo.on = 1;
+    P.lo.cmax_f = d_cmax.as<int32_t>();
+    P.lo.tile_base = d_tb.as<int64_t>();
+    P.lo.cnt = d_cnt.as<unsigned int>();
+    P.lo.tl = d_tl.as<uint32_t>();
+    P.lo.glo = d_glo.as<int32_t>();
+    const int rc = launch_gemm_lo_units(c, P, g.n_tf, c->stream);
+    if (rc == LDW_OK) LDW_HIP(hipMemcpyAsync(glo_out, d_glo.p, (size_t)g.glo_total * 4, hipMemcpyDeviceToHost, c->stream));
+    LDW_HIP(hipStreamSynchronize(c->stream));   // (the uploads read this frame)
+    return rc;
 }
 
 int ldw_debug_pair_sums(ldw_ctx *c, int form, int grid_wgs, uint32_t cap, const uint32_t *counts, const int32_t *snp_a, const int32_t *snp_b, int64_t *sums_out,

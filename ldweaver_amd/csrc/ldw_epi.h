@@ -5,7 +5,8 @@
 #include "ldw_internal.h"
 #include "ldw_dev.h"
 #include "ldw_log.h"
-#include "ldw_slots.h"   // the records of the per-slot buffers (ColInfo, ColMeta, RowPack, PairEnt, ...) and the buffers' layouts
+#include "ldw_lo_geom.h"
+#include "ldw_slots.h"  // the records of the per-slot buffers (ColInfo, ColMeta, RowPack, PairEnt, ...) and the buffers' layouts
 
 namespace ldw {
 
@@ -230,7 +231,8 @@ struct LoGeom {
     const int64_t *slot_pfix_hi;       // [L][5] marginals of the high-limb weights by slot
     int hi_shift;                      // G holds sums of V_hi = (V - V_lo) / 2^hi_shift
 };
-__host__ __device__ __forceinline__ int lo_class(int nrows) { return nrows <= 1 ? 0 : (nrows == 2 ? 1 : 2); }
+// (lo_class and the host arithmetic of this geometry: ldw_lo_geom.h)
+static_assert(LO_CHUNK_ROWS == TILE, "a chunk of low-limb rows is one to-side tile of the K loop");
 
 // r04: a SPAN = several reference blocks that share their from side (one block row of make_blocks: R/computePairwiseMI.R:147-165), run as ONE
 // launch sequence over the concatenated to side.  Everything per-SNP and per-row is as for a single block; what belongs to the REFERENCE

@@ -239,45 +239,27 @@ void PrepWork::tiles(int slot) {
         hb.D.gen_q0 = (int)q12;
     }
     // mixed-precision path: row-slot classes of the to side, widest class per from-tile, low-limb block offsets
-    cmax.assign((size_t)hb.D.nf_tiles, 1);
-    tbase.assign(cmax.size(), 0);
+    // (lo_layout, ldw_lo_geom.h: cmax, tbase and tf — last tiles first — come with it)
     {
+        const std::vector<int32_t> &row0 = c->rows.h_row0;
+        const LoLayout g = lo_layout(
+            nt, [&](int64_t k) { return (int)(row0[to_idx[k] + 1] - row0[to_idx[k]]); }, pf.size(),
+            [&](size_t t) { return pf[t] < 0 ? -1 : (int)(row0[from_idx[pf[t]] + 1] - row0[from_idx[pf[t]]]); }, cmax, tbase, tf);
         LoHost &lo = hb.lo;
         lo = LoHost();
-        for (int64_t k = 0; k < nt; ++k) ++lo.n_lc[lo_class(c->rows.h_row0[to_idx[k] + 1] - c->rows.h_row0[to_idx[k]])];
-        int32_t uo = 0, rb = 0;
         for (int lc = 0; lc < 3; ++lc) {
-            lo.uoff[lc] = uo;
-            lo.rowbase[lc] = rb;
-            uo += lo.n_lc[lc];
-            rb += (int32_t)((((int64_t)lo.n_lc[lc] << lc) + TILE - 1) / TILE * TILE);
+            lo.n_lc[lc] = g.n_lc[lc];
+            lo.uoff[lc] = g.uoff[lc];
+            lo.rowbase[lc] = g.rowbase[lc];
+            lo.n_tiles_cf[lc] = g.n_tiles_cf[lc];
         }
-        lo.RTlo = rb;
-        lo.ntiles = (int32_t)cmax.size();
-        for (size_t t = 0; t < pf.size(); ++t) {
-            if (pf[t] < 0) continue;
-            const int32_t a = from_idx[pf[t]];
-            const int cls = 1 << lo_class(c->rows.h_row0[a + 1] - c->rows.h_row0[a]);
-            if (cls > cmax[t / 64]) cmax[t / 64] = cls;
-        }
-        int64_t tb = 0;
-        for (size_t t = 0; t < cmax.size(); ++t) {
-            tbase[t] = tb;
-            tb += (int64_t)lo.RTlo * 64 * cmax[t];
-            ++lo.n_tiles_cf[cmax[t] == 1 ? 0 : (cmax[t] == 2 ? 1 : 2)];
-        }
+        lo.RTlo = g.RTlo;
+        lo.ntiles = g.ntiles;
+        lo.n_tf = g.n_tf;
+        lo.glo_total = g.glo_total;
         lo.slot = slot;
         lo.diag = hb.diag ? 1 : 0;
-        lo.glo_total = tb;
     }
-    // last tiles first: the tile of the SNPs with >= 3 minor states (generic code, every unit listed, cmax 4) is the
-    // critical path of the gathered GEMM and must not start last
-    for (size_t t = cmax.size(); t-- > 0;)
-        for (int fs = 0; fs < cmax[t]; ++fs) {
-            tf.push_back((int32_t)t);
-            tf.push_back(fs);
-        }
-    hb.lo.n_tf = (int32_t)(tf.size() / 2);
 }
 
 // approximate path: tiles of the exact GEMM (128 to-side x 64 from-side rows) that hold a short-range pair.  POS ascends along

@@ -219,6 +219,61 @@ class Engine:
             L.check(L.lib().ldw_debug_apx_gemm_list(self._ctx, L.ptr(rt), len(rt), L.ptr(rf), len(rf), int(grid_wgs), L.ptr(out)))
         return out
 
+    LIMB_GEMM_FILL = int(np.frombuffer(bytes([0xA5] * 8), dtype=np.int64)[0])
+    LO_UNITS_FILL = int(np.frombuffer(bytes([0xA5] * 4), dtype=np.int32)[0])
+
+    def debug_limb_gemm(self, rows_t, rows_f, engine: int = 0, limb0: int = 0, nlimbs: int | None = None, lower_only: bool = False, by0: int = 0, by1: int = -1,
+                        tile_mask=None, tile_list=None, out=None):
+        """The exact co-occurrence GEMMs over the given indicator rows (ldw_debug_limb_gemm): engine 0 = gemm_bits_kernel with the weight limbs limb0 ..
+        limb0 + nlimbs - 1 (None: all from limb0 up), engine 1 = k_cooc_popc.  lower_only, the strip by0..by1 of tile rows, tile_mask [RTpad / 128, RFpad / 64]
+        and tile_list (by << 16 | bx; an empty list launches nothing) are handed to the launch as they are.  Returns int64 [len(rows_t), len(rows_f)]; whatever
+        no kernel wrote holds LIMB_GEMM_FILL.  out: an array to write into (a refused call leaves it untouched)."""
+        rt = np.ascontiguousarray(rows_t, dtype=np.int32)
+        rf = np.ascontiguousarray(rows_f, dtype=np.int32)
+        if nlimbs is None:
+            nlimbs = int(self.debug_apx_params(want_weights=False)[0][19]) - int(limb0)
+        if out is None:
+            out = np.zeros((len(rt), len(rf)), dtype=np.int64)
+        assert out.dtype == np.int64 and out.shape == (len(rt), len(rf)) and out.flags.c_contiguous
+        mask = None if tile_mask is None else np.ascontiguousarray(tile_mask, dtype=np.uint8)
+        if mask is not None:
+            assert mask.shape == (-(-len(rt) // 128), 2 * -(-len(rf) // 128)), mask.shape
+        tl = None if tile_list is None else np.ascontiguousarray(tile_list, dtype=np.uint32).reshape(-1)
+        n_tl = 0 if tl is None else len(tl)
+        if tl is not None and n_tl == 0:
+            tl = np.zeros(1, dtype=np.uint32)      # (a non-null list of no entries)
+        L.check(L.lib().ldw_debug_limb_gemm(self._ctx, int(engine), L.ptr(rt), len(rt), L.ptr(rf), len(rf), int(limb0), int(nlimbs), int(bool(lower_only)), int(by0), int(by1),
+                                            L.ptr(mask), L.ptr(tl), n_tl, L.ptr(out)))
+        return out
+
+    def debug_lo_units(self, from_snps, to_snps, lists, launch: bool = True):
+        """The gathered low-limb GEMM on caller-made unit lists (ldw_debug_lo_units).  from_snps[64 * ntiles]: the SNPs of the from-tiles' lanes (-1: a padding
+        lane); to_snps[nt]: the SNP of every column slot; lists[tile][lc]: the listed column slots of row-slot class lc (0, 1, 2).  Returns a dict: glo (the raw
+        int32 buffer, None with launch = False; what the kernel did not write holds LO_UNITS_FILL), tile_base, cmax, rowbase, uoff, RTlo, n_tf."""
+        fs = np.ascontiguousarray(from_snps, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(to_snps, dtype=np.int32).reshape(-1)
+        assert len(fs) % 64 == 0 and len(fs) > 0
+        ntiles = len(fs) // 64
+        assert len(lists) == ntiles and all(len(x) == 3 for x in lists)
+        counts = np.array([[len(x[lc]) for lc in range(3)] for x in lists], dtype=np.uint32)
+        flat = [np.asarray(x[lc], dtype=np.int32).reshape(-1) for x in lists for lc in range(3)]
+        slots = np.ascontiguousarray(np.concatenate(flat + [np.zeros(1, dtype=np.int32)]))
+        geom = np.zeros(8, dtype=np.int32)
+        cmax = np.zeros(ntiles, dtype=np.int32)
+        tbase = np.zeros(ntiles, dtype=np.int64)
+        total = C.c_int64(0)
+
+        def call(glo, cap):
+            L.check(L.lib().ldw_debug_lo_units(self._ctx, L.ptr(fs), ntiles, L.ptr(ts), len(ts), L.ptr(counts), L.ptr(slots), L.ptr(geom), L.ptr(cmax), L.ptr(tbase),
+                                               C.byref(total), L.ptr(glo), cap))
+
+        call(None, 0)
+        glo = None
+        if launch:
+            glo = np.zeros(int(total.value), dtype=np.int32)
+            call(glo, len(glo))
+        return dict(glo=glo, tile_base=tbase, cmax=cmax, rowbase=geom[0:3].copy(), uoff=geom[3:6].copy(), RTlo=int(geom[6]), n_tf=int(geom[7]), glo_total=int(total.value))
+
     PAIR_PATHS, PAIR_SHARDS = 5, 8
     PAIR_FORMS = ("auto", "quarter_wave", "wave_lds", "wave_global", "bits")
     PAIR_SUMS_FILL = int(np.frombuffer(bytes([0xA5] * 8), dtype=np.int64)[0])
