@@ -122,13 +122,13 @@ int ldw_reset_speculation(ldw_ctx *ctx);
  * ("delta 5.1e-03 > 4e-03", "Npad 40960 > 30720", "popcount segment tables 70000 B > 60000 B of LDS", "weights not set"). */
 int ldw_path_report(ldw_ctx *ctx, int64_t out[8], char *gate, int capacity);
 /* Kernel launches by form since the context was created, so that a test can tell which form of a size-dependent stage ran (results do not
- * depend on the form): the exact pair sums of the approximate path's listed pairs, two launches per block, out[0] walking the set bits against
+ * depend on the form): the exact pair sums of the approximate path's listed pairs (ldw_pairs.hip; the form is choose_pair_form's, ldw_pairs.h), two launches per block, out[0] walking the set bits against
  * a per-position weight table within the default 64 KB of LDS (k_pair_sums_bits), out[1] the same with the 160-KB dynamic-LDS attribute
  * (more than 8 192 padded sequences), out[2] class-wise popcounts with the segment tables in LDS (k_pair_sums_q, or k_pair_sums under
  * LDW_PAIR_WAVE=1), out[3] the same with the tables in global memory (k_pair_sums: many weight classes beyond the bit walk's 160 KB, or LDW_NO_PAIR_BITS set); out[4] launches of the bit-row fill that
  * reads the states from global memory instead of staging a row in LDS (more than 61 440 padded sequences). */
 int ldw_pair_form_report(ldw_ctx *ctx, int64_t out[5]);
-/* Launches of the class-wise pair sums (out[2] + out[3] above) by kernel since the context was created: out[0] the kernel with a quarter-wave
+/* Launches of the class-wise pair sums (out[2] + out[3] above; kernels of ldw_pairs.hip) by kernel since the context was created: out[0] the kernel with a quarter-wave
  * per pair and persistent waves (the default where the segment tables fit LDS), out[1] the kernel with a wave per pair (tables in global
  * memory, or LDW_PAIR_WAVE=1, read per call).  Both give the same sums. */
 int ldw_pair_kernel_report(ldw_ctx *ctx, int64_t out[2]);
@@ -210,7 +210,7 @@ int ldw_debug_tab11(ldw_ctx *ctx, double W, double lo, double delta, double eta,
  *   sum_s (d_0(s) + 256 d_1(s)) [to row has s][from row has s]; absent rows, absent slots and padding lanes give 0; the rows of a chunk of 128 beyond the last listed unit are
  *   written as 0; chunks no list reaches keep the fill.  Needs weights of at least two limbs (LDW_ERR_STATE) and at most 65 535 (tile, fs) pairs; LDW_ERR_ARG for SNPs, slots or
  *   counts outside these bounds and for a buffer above 2^28 ints; nothing is launched then.
- * ldw_debug_pair_sums: the exact joint sums of caller-made pair lists, by the sum kernels alone (no MI, no emission) and through the launch code of the default path.
+ * ldw_debug_pair_sums: the exact joint sums of caller-made pair lists, by the sum kernels alone (no MI, no emission) and through the launch code of the default path (launch_pair_sums, ldw_pairs.hip).
  *   The lists are those of the approximate screen: 5 paths x 8 shards, list = path * 8 + shard, paths 0..3 for SNP pairs of (1,1), (2,1), (1,2), (2,2) indicator rows
  *   (from side, to side), path 4 for any 1..4 x 1..4.  counts[40] = entries of every list (a count above cap is clamped by the kernels, as after an overflow);
  *   snp_a / snp_b[40][cap] = the SNPs of the entries (from side, to side), read up to min(count, cap) per list.  form: 0 = what the default path would launch, 1 = a

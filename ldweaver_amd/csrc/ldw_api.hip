@@ -303,6 +303,7 @@ int ldw_ctx_create(int device, ldw_ctx **out) {
             if (rc == LDW_OK) {
                 ldw::warm_mi();
                 ldw::warm_apx();
+                ldw::warm_pairs();
                 ldw::warm_gemm_bits();
                 ldw::warm_srp();
                 ldw::warm_post();

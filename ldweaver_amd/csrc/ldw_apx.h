@@ -8,24 +8,13 @@
 // masked by a digit (to side: a, from side: b) ONE int8 MFMA pass carries ~12 bits of every weight instead of the 8 of a
 // single limb: the pass that took 3 (mixed precision) or 5 limbs takes 1.
 //
-// What the screen lists gets EXACT joint sums.  Long-range candidates (one pair in a few thousand) are listed PAIR by pair and
-// need no GEMM at all: sum_s V_s x_s y_s = sum over 32-bit words and weight classes of V_class popcount(x & y & class mask), a
-// quarter-wave per pair, four pairs per persistent wave, a lane holding two words of every 32 (k_pair_sums_q; k_pair_sums, a wave per
-// pair with lane = word, where the segment tables do not fit LDS or LDW_PAIR_WAVE=1), then the fp64 MI (k_pair_mi).  Units that hold a
-// short-range pair are listed whole — the short-range band is dense — and evaluated from the exact 5-limb GEMM of just the tiles the
-// band touches.
+// What the screen lists gets EXACT joint sums: the long-range candidates pair by pair (ldw_pairs.h), the units that hold a short-range pair
+// whole — the short-range band is dense — from the exact 5-limb GEMM of just the tiles the band touches.
 #pragma once
 #include "ldw_internal.h"
 #include "ldw_epi.h"
 
 namespace ldw {
-
-// one (32-bit word, weight class) intersection of the position axis
-struct PopSeg {
-    uint32_t mask;    // bits of the word that belong to the class
-    uint32_t flush;   // 1: last segment of its class: fold the class count into the 64-bit sums with weight V
-    int64_t V;        // fixed-point weight of the class
-};
 
 constexpr int APX_TW = 128;      // rows per side of one wave tile of the approximate GEMM (4 x 4 MFMA tiles of 32 x 32)
 struct ApxGemmArgs {
@@ -77,18 +66,4 @@ int launch_gemm_apx(ldw_ctx *c, const ApxGemmArgs &P, hipStream_t st);
 // ApxGemmArgs::grid_wgs of the default path for a block of RTpad x RFpad rows: APX_RUNS_R workgroups per resident slot (two slots per CU of the
 // context's device) or what LDW_APX_GRID_WGS asks for, never more than the worst case; 0 under LDW_NO_APX_RUNS=1.  Both read per call.
 int apx_run_grid(const ldw_ctx *c, int RTpad, int RFpad);
-// The forms of the exact pair sums (the numbers of ldw_debug_pair_sums): a quarter-wave per pair (k_pair_sums_q), a wave per pair with the segment
-// tables in LDS / in global memory (k_pair_sums), the bit walk (k_pair_sums_bits).
-enum PairForm : int { PAIR_FORM_AUTO = 0, PAIR_FORM_QUARTER = 1, PAIR_FORM_WAVE_LDS = 2, PAIR_FORM_WAVE_GLOBAL = 3, PAIR_FORM_BITS = 4 };
-struct PairSumsRan {
-    int form = 0;          // the form that was launched (1..4)
-    bool lds160 = false;   // the bit walk with the 160-KB dynamic-LDS attribute
-};
-// The sums alone, sums[(list * A.pl_cap + i) * 16 + j * 4 + i'] of the lists A.pl_pairs / A.pl_n / A.pl_cap (nothing else of A is read): form
-// PAIR_FORM_AUTO = the product's choice, else that form or LDW_ERR_STATE where it cannot run; grid_wgs 0 = the product's grid, else gridDim.x of
-// both launches (the quarter-wave kernel: the whole grid of a path; the others: workgroups per list).  Counts nothing.
-int launch_pair_sums(ldw_ctx *c, const EpiArgs &A, int64_t *sums, hipStream_t st, int form, int grid_wgs, PairSumsRan *ran);
-// the pair lists of A (filled by the approximate screen): exact sums (launch_pair_sums(.., PAIR_FORM_AUTO, 0)), fp64 MI, emission
-int launch_pairs_exact(ldw_ctx *c, const EpiArgs &A, unsigned long long *ghist, int64_t *sums, hipStream_t st);
-
 }  // namespace ldw

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ldw_apx.h"
+#include "ldw_pairs.h"
 #include "ldw_dev.h"
 #include "ldw_gemm_tile.h"
 

@@ -692,7 +692,7 @@ __device__ __forceinline__ double pair_mi_full(const EpiArgs &A, const RowSide &
 }
 
 // ------------------------------------------------------------------------------------------------
-// pieces shared by the screen / epilogue / unit kernels (ldw_mi.hip, ldw_apx.hip): all of them walk a block in the same
+// pieces shared by the screen / epilogue / unit kernels (ldw_mi.hip, ldw_apx.hip, ldw_pairs.hip): all of them walk a block in the same
 // units, one unit = the 64 from-side SNPs of a wave (perm_f order) x one to-side SNP (perm_t order); both orders group
 // equal slot counts.
 // ------------------------------------------------------------------------------------------------

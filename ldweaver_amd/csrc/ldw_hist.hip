@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "ldw_internal.h"
+#include "ldw_pairs.h"   // PopSeg
 
 using namespace ldw;
 
@@ -26,17 +27,12 @@ namespace ldw {
 // one coalesced line), the segment records are wave-uniform (scalar loads).  Diagonal blocks skip the tiles above the diagonal.
 // Bound: VALU issue (2 ops per row pair and word + 3 per row pair and class).
 // ------------------------------------------------------------------------------------------------
-struct PopSegH {      // == ldw::PopSeg of ldw_apx.h (kept local: this file shares no header with the approximate path)
-    uint32_t mask, flush;
-    int64_t V;
-};
-
 struct CoocArgs {
     const uint64_t *Mbits;
     int64_t KW;                  // 64-bit words per bit row
     const int32_t *rowlist_t, *rowlist_f;
     int RTpad, RFpad, nwords;    // nwords: 32-bit words that hold sequences (<= 2 KW)
-    const PopSegH *segs;
+    const PopSeg *segs;
     const int32_t *wbeg;         // [nwords + 1] first segment of every word (bit 31: flag of another kernel, masked off)
     int64_t *G;
     int lower_only;
@@ -92,7 +88,7 @@ __global__ __launch_bounds__(256) void k_cooc_popc(CoocArgs P) {
                 for (int j = 0; j < 4; ++j) xy[i][j] = x[i] & y[j];
             const int sg0 = P.wbeg[w0 + w] & 0x7FFFFFFF, sg1 = P.wbeg[w0 + w + 1] & 0x7FFFFFFF;   // wave-uniform
             for (int sg = sg0; sg < sg1; ++sg) {
-                const PopSegH seg = P.segs[sg];
+                const PopSeg seg = P.segs[sg];
                 if (seg.mask == 0xFFFFFFFFu) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
@@ -147,7 +143,7 @@ int launch_cooc_popc(ldw_ctx *c, const int32_t *rowlist_t, int RTpad, const int3
     P.RTpad = RTpad;
     P.RFpad = RFpad;
     P.nwords = (int)((c->N + 31) / 32);
-    P.segs = c->apx.pop_segs.as<PopSegH>();
+    P.segs = c->apx.pop_segs.as<PopSeg>();
     P.wbeg = c->apx.pop_wbeg.as<int32_t>();
     P.G = G;
     P.lower_only = lower_only;

@@ -135,7 +135,7 @@ struct ApxWeights {
     double apx_lost_units = 0;         // what that adds up to in units of 2^apx_e_last (< 2: the exponents ascend)
     double apx_delta = 0;              // max_p |V'_p - V_p| / V_p
     std::vector<int64_t> h_vapx;       // [Npad] by SEQUENCE: V'_s = a b 2^e (exact integer)
-    DevBuf pop_segs, pop_wbeg;         // popcount segments (PopSeg) and first segment of every 32-bit word (+1)
+    DevBuf pop_segs, pop_wbeg;         // popcount segments (PopSeg, ldw_pairs.h) and first segment of every 32-bit word (+1)
     DevBuf pop_vpos;                   // r05: int64 [Npad] fixed-point weight by POSITION (k_pair_sums_bits: weightings with many classes)
     int n_pop_segs = 0, n_classes = 0;
     const char *gate(bool have_weights) const { return have_weights ? apx_gate.c_str() : "weights not set"; }
@@ -433,7 +433,7 @@ int launch_gemm_bits(ldw_ctx *ctx, const uint64_t *Mbits, int64_t KW, const int3
 int launch_cooc_popc(ldw_ctx *ctx, const int32_t *rowlist_t, int RTpad, const int32_t *rowlist_f, int RFpad, int64_t *G, int lower_only,
                      hipStream_t stream = nullptr);
 int fill_rows_bits(ldw_ctx *ctx, const int32_t *d_rowinfo, int64_t R);
-int prepare_apx_weights(ldw_ctx *ctx);   // ldw_apx.hip: dual digits, exponents, popcount segments from h_vfixed / h_seq_perm
+int prepare_apx_weights(ldw_ctx *ctx);   // ldw_apx.hip: dual digits, exponents and the popcount segment tables (ldw_pairs.h) from h_vfixed / h_seq_perm
 int check_gpu(ldw_ctx *ctx);
 inline bool have_alignment(const ldw_ctx *ctx) { return ctx->L > 0 && !ctx->meta.pos_only; }   // (ldw_set_positions sets L without one)
 int ensure_hi_marginals(ldw_ctx *ctx);   // slot_pfix_hi on demand (mixed-precision path)
@@ -444,6 +444,7 @@ int reserve_slot_buffers(ldw_ctx *ctx, int64_t Npad, int64_t blk, int64_t nseg);
 int ensure_streams(ldw_ctx *ctx);    // the copy / GEMM streams, per-slot events and pinned pick records of the all-pairs loop (once per context)
 void warm_mi();                      // lazy code-object loads of the translation units whose kernels a pass launches (hipFuncGetAttributes)
 void warm_apx();
+void warm_pairs();
 void warm_gemm_bits();
 void ctx_count(int d);               // ldw_alloc.cpp: live contexts of the process (the last one to go trims the device free list to its idle cap)
 struct DrainedScope { DrainedScope(); ~DrainedScope(); };   // releases inside: the caller has drained every stream that could touch the blocks

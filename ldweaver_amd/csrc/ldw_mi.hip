@@ -43,6 +43,7 @@
 #include <future>
 
 #include "ldw_apx.h"
+#include "ldw_pairs.h"
 
 using namespace ldw;
 

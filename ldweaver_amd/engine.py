@@ -114,7 +114,7 @@ class Engine:
                     probe_blocks=int(v[5]), pairs_listed=int(v[6]), units_listed=int(v[7]), apx_gate=buf.value.decode())
 
     def form_report(self):
-        """Kernel launches by form since the context was created (ldw_pair_form_report): the exact pair sums of the listed pairs walking set bits
+        """Kernel launches by form since the context was created (ldw_pair_form_report): the exact pair sums of the listed pairs (ldw_pairs.hip) walking set bits
         within 64 KB of LDS / with the 160-KB attribute, class-wise with LDS / global segment tables, and bit-row fills from global memory."""
         v = np.zeros(5, dtype=np.int64)
         L.check(L.lib().ldw_pair_form_report(self._ctx, L.ptr(v)))
@@ -279,7 +279,7 @@ class Engine:
     PAIR_SUMS_FILL = int(np.frombuffer(bytes([0xA5] * 8), dtype=np.int64)[0])
 
     def debug_pair_sums(self, counts, snp_a, snp_b, form: int = 0, grid_wgs: int = 0):
-        """The exact joint sums of caller-made pair lists by the sum kernels alone (ldw_debug_pair_sums): counts[40] entries per list (list = path * 8 +
+        """The exact joint sums of caller-made pair lists by the sum kernels of ldw_pairs.hip alone (ldw_debug_pair_sums): counts[40] entries per list (list = path * 8 +
         shard; a count above the capacity is clamped by the kernels), snp_a / snp_b [40, cap] the SNPs of the entries.  form: an index of PAIR_FORMS
         (0: what the default path would launch), grid_wgs: gridDim.x of both launches (0: the default path's).  Returns (sums int64 [40, cap, 16], the
         form that ran); whatever the kernels did not write holds PAIR_SUMS_FILL."""

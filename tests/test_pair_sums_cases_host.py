@@ -1,6 +1,6 @@
 """The case table of tests/test_pair_sums_fn_gpu.py meets the conditions it was made for (no GPU).
 
-From the mapping in k_pair_sums_q's comment (ldw_apx.hip): the eight shards of a path are one index space (the clamped counts one after the other), a group
+From the mapping in k_pair_sums_q's comment (ldw_pairs.hip): the eight shards of a path are one index space (the clamped counts one after the other), a group
 is four consecutive pairs of it — one per 16-lane row of a wave —, and wave w of g workgroups takes the groups w, w + 4 g, ...  These are conditions on the
 inputs, not measurements."""
 import itertools

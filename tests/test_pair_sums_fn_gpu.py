@@ -1,7 +1,7 @@
 """The exact pair-sum kernels as functions (ldw_debug_pair_sums), against plain integer sums, over turns, shards and row lengths.
 
 Every long-range MI of the default path is computed from the sums of k_pair_sums_q (a quarter-wave per pair, persistent waves), k_pair_sums (a wave per
-pair, segment tables in LDS or in global memory) or k_pair_sums_bits (the bit walk), all in ldw_apx.hip.  End to end they are only reached through whole
+pair, segment tables in LDS or in global memory) or k_pair_sums_bits (the bit walk), all in ldw_pairs.hip.  End to end they are only reached through whole
 passes, where a block's lists fill one turn of the persistent grid, at most two.  Here the hook runs the sum kernels alone, through the launch code of the
 default path, on caller-made lists and with a forced grid, and the whole sums buffer is compared with == :
 

@@ -1,4 +1,4 @@
-"""The exact sums of the listed long-range candidates, a quarter-wave per pair (k_pair_sums_q, ldw_apx.hip), at the edges of its mapping.
+"""The exact sums of the listed long-range candidates, a quarter-wave per pair (k_pair_sums_q, ldw_pairs.hip), at the edges of its mapping.
 
 Every case runs one small alignment three ways on fresh engines — the default path (the quarter-wave kernel), the default path with
 LDW_PAIR_WAVE=1 (the wave-per-pair kernels) and the plain path — each cold (after reset_speculation) and warm, and compares the short-range

@@ -2,7 +2,7 @@
 both sides of its switch, up to 70 000 sequences.
 
 The forms and where they flip:
-  - exact pair sums of the approximate path's listed pairs (launch_pairs_exact, ldw_apx.hip): the bit walk against a per-position weight table
+  - exact pair sums of the approximate path's listed pairs (launch_pairs_exact, ldw_pairs.hip): the bit walk against a per-position weight table
     in LDS (k_pair_sums_bits) within the default 64 KB up to Npad 8 192, with the 160-KB dynamic-LDS attribute up to Npad 20 480, beyond that
     the class-wise popcounts (k_pair_sums) with their segment tables in global memory; few weight classes take k_pair_sums with LDS tables;
   - the approximate path itself up to Npad 30 720 (prepare_apx_weights);
