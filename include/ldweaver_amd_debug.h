@@ -183,6 +183,24 @@ int ldw_debug_tab11(ldw_ctx *ctx, double W, double lo, double delta, double eta,
  * ldw_debug_apx_gemm_list: the same contract and the same values through the kernel's LIST launch (the default path's, without its table test): a list of every
  *   wave tile (128 to-rows x 64 from-rows) that holds an entry of out, walked by grid_wgs workgroups (1..65536) of four waves — wave w takes the tiles w, w + 4 grid_wgs,
  *   ... of the list; workgroups beyond the list leave at once.
+ * ldw_debug_apx_gemm_fused: the approximate GEMM as the default path launches it — FUSED with the threshold-table test of its epilogue (clean-region flags, maybe list) and,
+ *   with prune != 0, behind the live-tile pass (tile-pruning rules (a) and (b)) — through the product's own launch code, unchanged: launch_pack_panel, launch_apx_live_tiles,
+ *   launch_gemm_apx with fuse = 1, on caller-made inputs.  rows_t[nrt] / rows_f[nrf] (1..8192 each): as for ldw_debug_apx_gemm, padded with R to multiples of 128 (RTpad, RFpad).
+ *   bin_t[nrt] / bin_f[nrf]: the table bin 0..63 of every row, or 255 (no bin); padding rows get 255, as k_build_packs leaves them.  rflag_t[nrt] / rflag_f[nrf] (both or neither
+ *   NULL): the pruning flags of every row (kind 2 or 3 in bits 0-1, 4 = dead versus kind 2, 8 = dead versus kind 3), read by the live-tile pass only; padding rows get 0.
+ *   tab[64 * 64 * 2]: int32 (Lq, Hq) of entry [bin_t][bin_f], the caller's own (a sum n' with Lq < n' < Hq passes).  sr_mask (may be NULL): [RTpad / 128][RFpad / 64] bytes, != 0 =
+ *   the tile is never table-tested.  lower_only: a diagonal block's launch (tiles with tx * 64 + 63 < ty * 128 are no part of it).  prune = 0: the 2-D launch; prune != 0: the
+ *   live-tile pass, then the list launch with grid_wgs workgroups (1..65536; 0 = apx_run_grid's; without prune grid_wgs must be 0).  maybe_cap: -1 = no maybe list, else its
+ *   capacity 1..1 048 576.  Every output is the raw device buffer, filled with bytes LDW_DEBUG_APX_FUSED_FILL before the launches — the clean flags too, which the product zeroes:
+ *   what no kernel wrote still holds the pattern.  G_out[RTpad][RFpad] int32: the stored regions (32 to-rows x 64 from-rows each); clean_out[RTpad / 32][RFpad / 64]: the region
+ *   flags; tiles_out[(RTpad / 128) * (RFpad / 64)] (prune only, else may be NULL): the live-tile list, ty * (RFpad / 64) + tx; maybe_out[maybe_cap][3] (may be NULL without a list):
+ *   (to-row position, from-row position, n') of the entries handed over; counts_out[4]: live tiles, tiles the live-tile pass counted as pruned (a counter of the hook's own), the
+ *   final count of the maybe list (it counts beyond the capacity), and the bytes written behind the list's capacity (a guard of 64 entries on the device: 0).  A live tile's region with no row or column of bin 255 and no mask is flagged 1 and not stored when every
+ *   entry passes, or when a maybe list is given and at most LDW_DEBUG_APX_MAYBE_MAX entries fail (those go to the list); every other region of a live tile is flagged 0 and stored.
+ *   LDW_ERR_STATE: the weights do not allow the approximate path; LDW_ERR_ARG: a row outside 0..R, a bin in 64..254, counts outside 1..8192, grid_wgs != 0 without prune or outside
+ *   0..65536, maybe_cap outside -1, 1..1 048 576, the flags of one side only.  Nothing is launched then and no output is written; the counters of ldw_gemm_stats and ldw_prune_report
+ *   never move, refused or not.  tests/test_apx_fused_gpu.py compares every flag, stored integer, list entry and count with the plain-loop model of tests/apx_fused_ref.py;
+ *   tests/apx_fused_cases.py makes the cases and tests/test_apx_fused_cases_host.py checks without a GPU that they hold the situations they were made for.
  * ldw_debug_limb_gemm: the exact co-occurrence GEMMs as functions: launch_gemm_bits (engine 0: gemm_bits_kernel<J>) or launch_cooc_popc (engine 1: k_cooc_popc), unchanged, over
  *   caller-given indicator rows of the context's current bit rows and weights.  rows_t[nrt] / rows_f[nrf] (1..8192 each): row indices 0..R, R = the all-zero padding row; both
  *   lists are padded to multiples of 128 with R (RTpad, RFpad).  Engine 0: the launch gets the digit limbs limb0 .. limb0 + nlimbs - 1 of the weights (digits + limb0 * Kpad, as
@@ -232,6 +250,11 @@ int ldw_debug_apx_params(ldw_ctx *ctx, double out[20], int64_t *vfixed_out, int6
 int ldw_debug_rows(ldw_ctx *ctx, int32_t *row0_out, uint32_t *slot_meta_out, int64_t capacity);
 int ldw_debug_apx_gemm(ldw_ctx *ctx, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int32_t *out);
 int ldw_debug_apx_gemm_list(ldw_ctx *ctx, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int grid_wgs, int32_t *out);
+#define LDW_DEBUG_APX_FUSED_FILL 0xA5 /* every byte of G_out, clean_out, tiles_out and maybe_out no kernel wrote */
+#define LDW_DEBUG_APX_MAYBE_MAX 96    /* the build's APX_MAYBE_MAX: most failing entries of a region that go to the maybe list */
+int ldw_debug_apx_gemm_fused(ldw_ctx *ctx, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, const uint8_t *bin_t, const uint8_t *bin_f, const uint8_t *rflag_t,
+                             const uint8_t *rflag_f, const int32_t *tab, const uint8_t *sr_mask, int lower_only, int prune, int grid_wgs, int maybe_cap, int32_t *G_out,
+                             uint8_t *clean_out, uint32_t *tiles_out, int32_t *maybe_out, int64_t counts_out[4]);
 #define LDW_DEBUG_LIMB_GEMM_FILL 0xA5 /* every byte of out no kernel wrote */
 int ldw_debug_limb_gemm(ldw_ctx *ctx, int engine, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, int limb0, int nlimbs, int lower_only, int by0, int by1,
                         const uint8_t *tile_mask, const uint32_t *tile_list, int n_tile_list, int64_t *out);

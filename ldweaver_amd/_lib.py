@@ -212,6 +212,7 @@ _SIGS_DEBUG = {
     "ldw_debug_rows": (C.c_int, [_p, _p, _p, _i64]),
     "ldw_debug_apx_gemm": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p]),
     "ldw_debug_apx_gemm_list": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, C.c_int, _p]),
+    "ldw_debug_apx_gemm_fused": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]),
     "ldw_debug_limb_gemm": (C.c_int, [_p, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, C.c_int, _p]),
     "ldw_debug_lo_units": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p, _p, _p, _p, _p, C.POINTER(C.c_int64), _p, C.c_int64]),
     "ldw_debug_pair_sums": (C.c_int, [_p, C.c_int, C.c_int, C.c_uint32, _p, _p, _p, _p, C.POINTER(C.c_int)]),

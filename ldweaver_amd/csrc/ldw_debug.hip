@@ -4,6 +4,8 @@
 //   ldw_debug_apx_params    the dual-digit weights V' of the current weighting and every constant the approximate screen's bound is built from
 //   ldw_debug_rows          SNP -> indicator rows (which state each row stands for)
 //   ldw_debug_apx_gemm      gemm_apx_kernel on caller-chosen rows: the int32 sums G' (truncation bound apx_lost_units)
+//   ldw_debug_apx_gemm_fused  the FUSED launches of the default path (launch_pack_panel, launch_apx_live_tiles, launch_gemm_apx with P.fuse = 1) on caller-made rows, bins,
+//                           row flags, threshold table and band mask: the raw G', clean flags, live-tile list, maybe list and counters, each over a fill pattern
 //   ldw_debug_limb_gemm     launch_gemm_bits / launch_cooc_popc on caller-chosen rows, limbs, strips, masks and tile lists: the exact int64 sums, every entry the launch left alone
 //   ldw_debug_lo_units      launch_gemm_lo_units on caller-made unit lists, laid out by lo_layout (ldw_lo_geom.h) as prep_block lays out a block: the raw low-limb buffer
 //   ldw_debug_pair_sums     the exact sums of caller-made pair lists through launch_pair_sums (every form, a forced grid), without k_pair_mi
@@ -228,6 +230,139 @@ static int debug_apx_gemm(ldw_ctx *c, const int32_t *rows_t, int nrt, const int3
     LDW_HIP(hipMemcpyAsync(h.data(), d_G.p, h.size() * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     for (int t = 0; t < nrt; ++t) memcpy(out + (size_t)t * nrf, h.data() + (size_t)t * RFpad, (size_t)nrf * 4);
+    return LDW_OK;
+}
+
+static_assert(LDW_DEBUG_APX_MAYBE_MAX == APX_MAYBE_MAX, "ldweaver_amd_debug.h documents the build's APX_MAYBE_MAX");
+static_assert(sizeof(ApxMaybe) == 12, "maybe_out is [maybe_cap][3] 32-bit words");
+
+int ldw_debug_apx_gemm_fused(ldw_ctx *c, const int32_t *rows_t, int nrt, const int32_t *rows_f, int nrf, const uint8_t *bin_t, const uint8_t *bin_f, const uint8_t *rflag_t,
+                             const uint8_t *rflag_f, const int32_t *tab, const uint8_t *sr_mask, int lower_only, int prune, int grid_wgs, int maybe_cap, int32_t *G_out,
+                             uint8_t *clean_out, uint32_t *tiles_out, int32_t *maybe_out, int64_t counts_out[4]) {
+    if (int rc = check_gpu(c)) return rc;
+    if (int rc = join_prepare(c)) return rc;
+    if (int rc = ensure_rows(c)) return rc;
+    LDW_REQUIRE(rows_t && rows_f && bin_t && bin_f && tab && G_out && clean_out && counts_out && nrt > 0 && nrf > 0 && nrt <= 8192 && nrf <= 8192, LDW_ERR_ARG,
+                "ldw_debug_apx_gemm_fused: bad argument");
+    LDW_REQUIRE(c->apx.apx_ok, LDW_ERR_STATE, "ldw_debug_apx_gemm_fused: the weights do not allow the approximate path (%s)", c->apx.apx_gate.c_str());
+    LDW_REQUIRE((rflag_t == nullptr) == (rflag_f == nullptr), LDW_ERR_ARG, "ldw_debug_apx_gemm_fused: the row flags of one side only");
+    LDW_REQUIRE(prune ? (grid_wgs >= 0 && grid_wgs <= 65536) : grid_wgs == 0, LDW_ERR_ARG, "ldw_debug_apx_gemm_fused: grid of %d workgroups (prune %d: 0%s)", grid_wgs, prune,
+                prune ? "..65536" : " only");
+    LDW_REQUIRE(maybe_cap == -1 || (maybe_cap >= 1 && maybe_cap <= (1 << 20)), LDW_ERR_ARG, "ldw_debug_apx_gemm_fused: maybe list capacity %d outside -1, 1..1048576", maybe_cap);
+    LDW_REQUIRE((!prune || tiles_out) && (maybe_cap < 0 || maybe_out), LDW_ERR_ARG, "ldw_debug_apx_gemm_fused: no room for the tile list or the maybe list");
+    for (int k = 0; k < nrt; ++k) {
+        LDW_REQUIRE(rows_t[k] >= 0 && rows_t[k] <= c->rows.R, LDW_ERR_ARG, "ldw_debug_apx_gemm_fused: to-side row %d = %d outside 0..R", k, rows_t[k]);
+        LDW_REQUIRE(bin_t[k] < 64 || bin_t[k] == 255, LDW_ERR_ARG, "ldw_debug_apx_gemm_fused: to-side bin %d = %d", k, bin_t[k]);
+    }
+    for (int k = 0; k < nrf; ++k) {
+        LDW_REQUIRE(rows_f[k] >= 0 && rows_f[k] <= c->rows.R, LDW_ERR_ARG, "ldw_debug_apx_gemm_fused: from-side row %d = %d outside 0..R", k, rows_f[k]);
+        LDW_REQUIRE(bin_f[k] < 64 || bin_f[k] == 255, LDW_ERR_ARG, "ldw_debug_apx_gemm_fused: from-side bin %d = %d", k, bin_f[k]);
+    }
+    const int RTpad = (nrt + APX_TW - 1) / APX_TW * APX_TW, RFpad = (nrf + APX_TW - 1) / APX_TW * APX_TW, M2 = (int)(c->KW / 2);
+    const size_t n_G = (size_t)RTpad * RFpad, n_clean = (size_t)(RTpad / 32) * (RFpad / 64), n_tiles = (size_t)(RTpad / 128) * (RFpad / 64);
+    // the row lists, bins and flags as prep_block / k_build_packs leave them: padding -> the all-zero row R, no bin, no flag
+    std::vector<int32_t> rl((size_t)RTpad + RFpad, (int32_t)c->rows.R);
+    std::vector<uint8_t> bins((size_t)RTpad + RFpad, (uint8_t)255), flags((size_t)RTpad + RFpad, (uint8_t)0);
+    std::copy(rows_t, rows_t + nrt, rl.begin());
+    std::copy(rows_f, rows_f + nrf, rl.begin() + RTpad);
+    std::copy(bin_t, bin_t + nrt, bins.begin());
+    std::copy(bin_f, bin_f + nrf, bins.begin() + RTpad);
+    if (rflag_t) {
+        std::copy(rflag_t, rflag_t + nrt, flags.begin());
+        std::copy(rflag_f, rflag_f + nrf, flags.begin() + RTpad);
+    }
+    DevBuf d_rl, d_pt, d_pf, d_G, d_bins, d_flags, d_tab, d_mask, d_clean, d_list, d_ctr, d_maybe;
+    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> int {
+        if (int rc = b.reserve(bytes)) return rc;
+        LDW_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+        return LDW_OK;
+    };
+    auto filled = [&](DevBuf &b, size_t bytes) -> int {
+        if (int rc = b.reserve(bytes)) return rc;
+        LDW_HIP(hipMemsetAsync(b.p, LDW_DEBUG_APX_FUSED_FILL, bytes, c->stream));
+        return LDW_OK;
+    };
+    if (int rc = up(d_rl, rl.data(), rl.size() * 4)) return rc;
+    if (int rc = up(d_bins, bins.data(), bins.size())) return rc;
+    if (int rc = up(d_flags, flags.data(), flags.size())) return rc;
+    if (int rc = up(d_tab, tab, (size_t)64 * 64 * 8)) return rc;
+    if (sr_mask)
+        if (int rc = up(d_mask, sr_mask, n_tiles)) return rc;
+    if (int rc = d_pt.reserve((size_t)M2 * RTpad * 32)) return rc;
+    if (int rc = d_pf.reserve((size_t)M2 * RFpad * 32)) return rc;
+    if (int rc = filled(d_G, n_G * 4)) return rc;
+    if (int rc = filled(d_clean, n_clean)) return rc;
+    if (int rc = filled(d_list, n_tiles * 4)) return rc;
+    constexpr int MAYBE_GUARD = 64;   // entries behind the capacity: they must keep the fill (counts_out[3])
+    if (maybe_cap > 0)
+        if (int rc = filled(d_maybe, ((size_t)maybe_cap + MAYBE_GUARD) * sizeof(ApxMaybe))) return rc;
+    // the three counters the launches add to, zeroed as the product zeroes them: [0] skipped tiles (64 bits), [2] live tiles, [3] maybe entries
+    if (int rc = d_ctr.reserve(64)) return rc;
+    LDW_HIP(hipMemsetAsync(d_ctr.p, 0, 64, c->stream));
+    if (int r2 = launch_pack_panel(c, d_rl.as<int32_t>() + RTpad, RFpad, d_pf.as<uint64_t>(), c->stream, d_rl.as<int32_t>(), RTpad, d_pt.as<uint64_t>())) return r2;
+    ApxGemmArgs P;
+    memset(&P, 0, sizeof(P));
+    P.panel_t = d_pt.as<uint64_t>();
+    P.panel_f = d_pf.as<uint64_t>();
+    P.RTpad = RTpad;
+    P.RFpad = RFpad;
+    P.M2 = M2;
+    P.dig_a = c->apx.dig_a.as<uint8_t>();
+    P.dig_b = c->apx.dig_b.as<uint8_t>();
+    P.shift = c->apx.apx_shift.as<int32_t>();
+    P.fine = c->apx.apx_fine ? 1 : 0;
+    P.G = d_G.as<int32_t>();
+    P.lower_only = lower_only ? 1 : 0;
+    P.fuse = 1;
+    if (prune) {   // (as the block's launch chain fills them, ldw_mi_block.inc: the row flags go with the live-tile pass only)
+        P.skip_ctr = d_ctr.as<unsigned long long>();
+        P.tile_list = d_list.as<uint32_t>();
+        P.n_live = d_ctr.as<unsigned int>() + 2;
+        P.grid_wgs = grid_wgs > 0 ? grid_wgs : apx_run_grid(c, RTpad, RFpad);
+        if (rflag_t) {
+            P.rflag_t = d_flags.as<uint8_t>();
+            P.rflag_f = d_flags.as<uint8_t>() + RTpad;
+        }
+    }
+    P.bin_t = d_bins.as<uint8_t>();
+    P.bin_f = d_bins.as<uint8_t>() + RTpad;
+    P.tab = d_tab.as<int2>();
+    P.tab_nb = 64;
+    P.clean = d_clean.as<uint8_t>();
+    P.sr_mask = sr_mask ? d_mask.as<uint8_t>() : nullptr;
+    if (maybe_cap > 0) {
+        P.maybe = d_maybe.as<ApxMaybe>();
+        P.maybe_n = d_ctr.as<unsigned int>() + 3;
+        P.maybe_cap = (unsigned int)maybe_cap;
+    }
+    // the hook is no block of a pass: what the launch code adds to the context's counters is taken off again (ldw_gemm_stats, ldw_prune_report)
+    double stat[6];
+    memcpy(stat, c->cnt.gemm_stat, sizeof(stat));
+    const int64_t waves_total = c->cnt.apx_waves_total;
+    const double ops_per_wave = c->apx_ops_per_wave;
+    int rc = prune ? launch_apx_live_tiles(c, P, c->stream) : LDW_OK;
+    if (rc == LDW_OK) rc = launch_gemm_apx(c, P, c->stream);
+    memcpy(c->cnt.gemm_stat, stat, sizeof(stat));
+    c->cnt.apx_waves_total = waves_total;
+    c->apx_ops_per_wave = ops_per_wave;
+    uint32_t ctr[4] = {0u, 0u, 0u, 0u};
+    std::vector<uint8_t> guard(maybe_cap > 0 ? MAYBE_GUARD * sizeof(ApxMaybe) : 0, (uint8_t)LDW_DEBUG_APX_FUSED_FILL);
+    if (rc == LDW_OK) {
+        LDW_HIP(hipMemcpyAsync(G_out, d_G.p, n_G * 4, hipMemcpyDeviceToHost, c->stream));
+        LDW_HIP(hipMemcpyAsync(clean_out, d_clean.p, n_clean, hipMemcpyDeviceToHost, c->stream));
+        if (tiles_out) LDW_HIP(hipMemcpyAsync(tiles_out, d_list.p, n_tiles * 4, hipMemcpyDeviceToHost, c->stream));
+        if (maybe_cap > 0) {
+            LDW_HIP(hipMemcpyAsync(maybe_out, d_maybe.p, (size_t)maybe_cap * sizeof(ApxMaybe), hipMemcpyDeviceToHost, c->stream));
+            LDW_HIP(hipMemcpyAsync(guard.data(), d_maybe.as<ApxMaybe>() + maybe_cap, guard.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        LDW_HIP(hipMemcpyAsync(ctr, d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+    }
+    LDW_HIP(hipStreamSynchronize(c->stream));   // (the uploads read this frame)
+    if (rc != LDW_OK) return rc;
+    counts_out[0] = ctr[2];
+    counts_out[1] = (int64_t)(((uint64_t)ctr[1] << 32) | ctr[0]);
+    counts_out[2] = ctr[3];
+    counts_out[3] = (int64_t)std::count_if(guard.begin(), guard.end(), [](uint8_t b) { return b != (uint8_t)LDW_DEBUG_APX_FUSED_FILL; });
     return LDW_OK;
 }
 

@@ -219,6 +219,40 @@ class Engine:
             L.check(L.lib().ldw_debug_apx_gemm_list(self._ctx, L.ptr(rt), len(rt), L.ptr(rf), len(rf), int(grid_wgs), L.ptr(out)))
         return out
 
+    APX_FUSED_FILL = 0xA5                                                             # LDW_DEBUG_APX_FUSED_FILL: every byte no kernel wrote
+    APX_FUSED_FILL32 = int(np.frombuffer(bytes([0xA5] * 4), dtype=np.int32)[0])
+    APX_MAYBE_MAX = 96                                                                # LDW_DEBUG_APX_MAYBE_MAX (the library's build asserts it)
+
+    def debug_apx_gemm_fused(self, rows_t, rows_f, bin_t, bin_f, tab, rflag_t=None, rflag_f=None, sr_mask=None, lower_only: bool = False, prune: bool = False,
+                             grid_wgs: int = 0, maybe_cap: int = -1, out=None):
+        """The fused launches of the approximate GEMM on caller-made inputs (ldw_debug_apx_gemm_fused): the table test of the epilogue and, with prune, the
+        live-tile pass in front of the list launch (grid_wgs workgroups, 0: the default path's grid).  bin_t / bin_f: a table bin 0..63 or 255 per row;
+        rflag_t / rflag_f: pruning flags per row (both or neither); tab: int32 [64, 64, 2] (Lq, Hq); sr_mask: uint8 [RTpad / 128, RFpad / 64]; maybe_cap: -1 =
+        no maybe list.  Returns a dict of the raw buffers — G int32 [RTpad, RFpad], clean uint8 [RTpad / 32, RFpad / 64], tiles uint32 [tiles], maybe int32
+        [max(maybe_cap, 0), 3] — whatever no kernel wrote holds APX_FUSED_FILL bytes, and n_live, pruned, maybe_n, beyond_cap (bytes written behind the maybe list's capacity: 0).  out: a dict of such arrays to write
+        into (a refused call leaves them untouched)."""
+        rt = np.ascontiguousarray(rows_t, dtype=np.int32)
+        rf = np.ascontiguousarray(rows_f, dtype=np.int32)
+        bt = np.ascontiguousarray(bin_t, dtype=np.uint8)
+        bf = np.ascontiguousarray(bin_f, dtype=np.uint8)
+        assert bt.shape == rt.shape and bf.shape == rf.shape
+        ft = None if rflag_t is None else np.ascontiguousarray(rflag_t, dtype=np.uint8)
+        ff = None if rflag_f is None else np.ascontiguousarray(rflag_f, dtype=np.uint8)
+        assert (ft is None or ft.shape == rt.shape) and (ff is None or ff.shape == rf.shape)
+        tb = np.ascontiguousarray(tab, dtype=np.int32)
+        assert tb.shape == (64, 64, 2), tb.shape
+        RTpad, RFpad = -(-len(rt) // 128) * 128, -(-len(rf) // 128) * 128
+        mask = None if sr_mask is None else np.ascontiguousarray(sr_mask, dtype=np.uint8)
+        assert mask is None or mask.shape == (RTpad // 128, RFpad // 64), mask.shape
+        if out is None:
+            out = dict(G=np.zeros((RTpad, RFpad), dtype=np.int32), clean=np.zeros((RTpad // 32, RFpad // 64), dtype=np.uint8),
+                       tiles=np.zeros((RTpad // 128) * (RFpad // 64), dtype=np.uint32), maybe=np.zeros((max(int(maybe_cap), 0), 3), dtype=np.int32))
+        counts = np.zeros(4, dtype=np.int64)
+        L.check(L.lib().ldw_debug_apx_gemm_fused(self._ctx, L.ptr(rt), len(rt), L.ptr(rf), len(rf), L.ptr(bt), L.ptr(bf), L.ptr(ft), L.ptr(ff), L.ptr(tb), L.ptr(mask),
+                                                 int(bool(lower_only)), int(bool(prune)), int(grid_wgs), int(maybe_cap), L.ptr(out["G"]), L.ptr(out["clean"]),
+                                                 L.ptr(out["tiles"]), L.ptr(out["maybe"]) if out["maybe"].size else None, L.ptr(counts)))
+        return dict(out, n_live=int(counts[0]), pruned=int(counts[1]), maybe_n=int(counts[2]), beyond_cap=int(counts[3]))
+
     LIMB_GEMM_FILL = int(np.frombuffer(bytes([0xA5] * 8), dtype=np.int64)[0])
     LO_UNITS_FILL = int(np.frombuffer(bytes([0xA5] * 4), dtype=np.int32)[0])
 
