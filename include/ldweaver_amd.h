@@ -860,6 +860,29 @@ int ldw_links_permuted(ldw_ctx *ctx, const int32_t *pair_a, const int32_t *pair_
                        double *mi_obs_out, int32_t *n_ge_out, double *null_max_out, double *null_out, int64_t *fixed_out, int32_t *order_out, int64_t *p_out,
                        int *frac_bits_out);
 
+/* ---- (20) LD decay: a histogram, circular distance bin x MI bucket, of EVERY SNP pair of a block list ------------------------------------
+ * ldw_mi_profile needs the alignment, the weights and the SNP meta data, as ldw_mi_all_pairs does (LDW_ERR_STATE without them, and for a context that holds
+ * positions only, ldw_set_positions).
+ *   blocks[nblocks][4]  (from_s, from_e, to_s, to_e), 1-based inclusive, as make_blocks emits them (HOST).  A block is diagonal (both ranges equal) or its
+ *                ranges are disjoint; any other overlap is LDW_ERR_ARG.
+ *   the pairs    of a diagonal block: the local pairs a_loc > b_loc; of any other block: every (a_loc, b_loc) with a_loc != b_loc — the reference drops the
+ *                local diagonal there (R/computePairwiseMI.R:306-310), and so does this.  The total is the sum of n_sr + n_lr_total of ldw_block_stats
+ *                after ldw_mi_all_pairs over the same blocks.
+ *   the value    of a pair: what ldw_mi_block stores at [a_loc + b_loc * nf] for the block under the same quirk_mode (quirk Q1 makes it depend on the
+ *                block's geometry, which is why the blocks are an input).
+ *   distance bin len = 0.5 g - |(POS[to] - POS[from]) mod g - 0.5 g|, the len column of the link tables.  cuts[n_cut] (HOST): finite, non-negative, strictly
+ *                ascending, 0 <= n_cut <= 1023 (LDW_ERR_ARG otherwise).  The bin of a pair is the number of cuts strictly below len: bins are
+ *                (c_(k-1), c_k], n_cut + 1 of them, and a cut equal to sr_dist separates the pass's short range (len <= sr_dist) from its long range.
+ *   MI bin       mi_bucket(mi) >> mi_shift, mi_shift in 0..6, NB = 4096 >> mi_shift bins.  mi_bucket is the long-range selection's rule, taken from the IEEE
+ *                bits of the value: 0 for negatives, +-0 and values below 2^-20; else ((bits >> 45) - ((1023 - 20) << 7)), at most 4095: 128 buckets per
+ *                octave, lower edge of bucket B >= 1 the double with bits (B + ((1023 - 20) << 7)) << 45.
+ * Outputs (HOST): hist_out[n_cut + 1][NB] counts; max_out[n_cut + 1] (may be NULL) the largest value of every distance bin, the device's own bits, NaN for
+ * a bin without a pair; *npairs_out the number of pairs.  Integer adds and a maximum: nothing depends on the order of evaluation.
+ * The link tables and the ldw_block_stats of an earlier pass stay as they were.  ldw_ctx_last_timing afterwards: [0] the blocks' GEMM + epilogue, [1] the
+ * histogram kernels, [2] 0, [3] their sum.  The call runs on the context's stream and returns when the outputs are written. */
+int ldw_mi_profile(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int quirk_mode, const double *cuts, int32_t n_cut, int32_t mi_shift,
+                   uint64_t *hist_out, double *max_out, int64_t *npairs_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

@@ -267,6 +267,21 @@ int ldw_debug_pair_sums(ldw_ctx *ctx, int form, int grid_wgs, uint32_t cap, cons
 int ldw_debug_screen_bound(ldw_ctx *ctx, int kind, int na, int nb, int64_t n, const int64_t *g, const int64_t *pa, const int64_t *pb, const float *pX, const float *pY,
                            const double *rr, const uint32_t *masks, const double params[20], float *out, double *out64);
 
+/* ---- LD decay (ldweaver_amd.h 20) --------------------------------------------------------------------------------------------------------------------------
+ * ldw_debug_profile_hist: the histogram kernel of ldw_mi_profile (k_decay_hist) as a function, on caller-made values; needs no alignment.  mi[nf * nt]
+ *   (HOST, column-major: the pair (a_loc, b_loc) at a_loc + b_loc * nf; no NaN), pos_f[nf] / pos_t[nt] the positions of the two sides, g > 0 the genome
+ *   length, diag = 1 (nf == nt): the pairs a_loc > b_loc, diag = 0: the pairs a_loc != b_loc; cuts, n_cut, mi_shift and the three outputs as ldw_mi_profile.
+ *   The kernel works in patches of 64 rows x 256 columns; a patch bounds its distance bins lo..hi from the extreme positions of its rows and columns and
+ *   counts in LDS when (hi - lo + 1) * NB <= 8192 counters fit (route A), else by wave-aggregated global adds (route B).  route: 0 = every patch chooses,
+ *   1 = route A, LDW_ERR_ARG (outputs undefined) when a patch does not fit, 2 = route B for every patch.  All give the same bytes.  stats_out (may be NULL,
+ *   3 values): patches with a pair, patches that took route B, pairs found outside their patch's bound (added one by one; 0 for integral g).
+ *   LDW_ERR_ARG: nf, nt outside 1..1 000 000, diag with nf != nt, g not positive, route outside 0..2, cuts or mi_shift as ldw_mi_profile refuses them.
+ * ldw_decay_report: out[0..2] the same three counts summed over the last ldw_mi_profile of the context, out[3] its blocks. */
+int ldw_debug_profile_hist(ldw_ctx *ctx, const double *mi, int64_t nf, int64_t nt, const int32_t *pos_f, const int32_t *pos_t, double g, int diag,
+                           const double *cuts, int32_t n_cut, int32_t mi_shift, int route, uint64_t *hist_out, double *max_out, int64_t *npairs_out,
+                           int64_t *stats_out);
+int ldw_decay_report(ldw_ctx *ctx, int64_t out[4]);
+
 /* ---- the plots (ldweaver_amd.h 12) ------------------------------------------------------------------------------------------------ */
 /* The rasters of ldw_plot_scatter without the frame, for panels of W x H pixels each (any size >= 1): rgb_out[n_panels][H][W][3] (host).  Grid
  * lines lie at the ticks of ldw_plot_ticks for the data range and W / H.  stats_out (may be NULL, 8 doubles): x min, x max, y min, y max of

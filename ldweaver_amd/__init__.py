@@ -18,6 +18,7 @@ _EXPORTS = {
     "nj_tree": "tree", "write_newick": "tree", "bootstrap_multiplicities": "tree",
     "snp_parsimony": "parsimony", "link_cochanges": "parsimony", "ancestral_states": "parsimony", "tip_sequences": "parsimony",
     "cochange_pvalue": "parsimony",
+    "ld_decay": "decay", "LDDecay": "decay", "default_cuts": "decay",
     "sequence_clusters": "lineage", "link_lineage_mi": "lineage", "link_permutation_test": "lineage",
 }
 __all__ = sorted(_EXPORTS)

@@ -393,6 +393,7 @@ struct ldw_ctx {
     ldw::PinnedBuf lr_pin;       // pinned staging of a batch of rows (a, b, MI); grows on demand
     void *tsv_async = nullptr;   // r04: the asynchronous link-table writer, if one is running (ldw_tsv.cpp: TsvAsync)
     ldw::PinnedBuf pin_fetch;    // r04: pinned host arena the tsv writer fetches a link table into (see ldw_write_links_tsv)
+    int64_t decay_stat[4] = {0, 0, 0, 0};            // ldw_decay_report: patches, route-B patches, pairs outside their patch's bound and blocks of the last ldw_mi_profile
     double ham_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ldw_hamming_stats: columns, padded K, stage times and algorithmic bytes of the last ldw_hamming_weights
     ldw::DevBuf plot_work, plot_cols;   // the plots (ldw_plot.hip): key image + rasters + partials; device copy of a chunk of host columns
 
@@ -437,6 +438,9 @@ int prepare_apx_weights(ldw_ctx *ctx);   // ldw_apx.hip: dual digits, exponents 
 int check_gpu(ldw_ctx *ctx);
 inline bool have_alignment(const ldw_ctx *ctx) { return ctx->L > 0 && !ctx->meta.pos_only; }   // (ldw_set_positions sets L without one)
 int ensure_hi_marginals(ldw_ctx *ctx);   // slot_pfix_hi on demand (mixed-precision path)
+// ldw_mi.hip: run_block_mi without link tables, as ldw_mi_block runs it: the dense MI of one block into ctx->MIblk [nf * nt] column-major; the block's index
+// lists stay in ctx->idx_f / idx_t, its stage events are ctx->ev[0..2] (ldw_decay.hip)
+int block_mi_dense(ldw_ctx *ctx, const int32_t *from_idx, int64_t nf, const int32_t *to_idx, int64_t nt, int quirk);
 void lr_stream_push(ldw_ctx *ctx, hipStream_t s, const int64_t *d_lr_count, int64_t blocks_done);   // ldw_tsv.cpp: no-ops without an open stream
 void lr_stream_drain(ldw_ctx *ctx);
 int join_prepare(ldw_ctx *ctx);      // waits for the side thread of ldw_ctx_reserve (no-op without one); its error, if any, becomes the caller's

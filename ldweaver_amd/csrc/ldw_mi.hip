@@ -137,6 +137,12 @@ int reserve_slot_buffers(ldw_ctx *c, int64_t Npad, int64_t blk, int64_t nseg) {
     return LDW_OK;
 }
 
+int block_mi_dense(ldw_ctx *c, const int32_t *from_idx, int64_t nf, const int32_t *to_idx, int64_t nt, int quirk) {
+    EmitArgs E;
+    memset(&E, 0, sizeof(E));
+    return run_block_mi(c, from_idx, nf, to_idx, nt, quirk, E);
+}
+
 void warm_mi() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_zero4));

@@ -328,6 +328,52 @@ class Engine:
         L.check(L.lib().ldw_debug_pair_sums(self._ctx, int(form), int(grid_wgs), cap, L.ptr(cnt), L.ptr(a), L.ptr(b), L.ptr(out), C.byref(ran)))
         return out, int(ran.value)
 
+    # -- LD decay ---------------------------------------------------
+    @staticmethod
+    def _decay_cuts(cuts):
+        cu = np.zeros(0) if cuts is None else L.as_c(cuts, np.float64).ravel()
+        return cu, min(len(cu), 1 << 20)
+
+    def mi_profile(self, blocks, cuts, mi_shift: int = 3, quirk=L.QUIRK_REFERENCE):
+        """The histogram, circular distance bin x MI bucket, of EVERY SNP pair of ``blocks`` ((nb, 4) rows as make_blocks emits them), with the largest MI of
+        every distance bin (ldw_mi_profile).  ``cuts``: ascending distances; bin k holds the pairs with cuts[k-1] < len <= cuts[k].  Returns a dict: ``hist``
+        uint64 (len(cuts) + 1, 4096 >> mi_shift), ``max`` float64 (NaN for an empty bin), ``n_pairs``.  The link tables stay as they are."""
+        bl = L.as_c(blocks, np.int32).reshape(-1, 4)
+        cu, n_cut = self._decay_cuts(cuts)
+        nb = 4096 >> mi_shift if 0 <= int(mi_shift) <= 6 else 1
+        hist = np.zeros((min(n_cut, 1023) + 1, nb), dtype=np.uint64)
+        mx = np.full(hist.shape[0], np.nan)
+        n = C.c_int64(0)
+        L.check(L.lib().ldw_mi_profile(self._ctx, L.ptr(bl), len(bl), int(quirk), L.ptr(cu) if n_cut else None, n_cut, int(mi_shift), L.ptr(hist), L.ptr(mx),
+                                       C.byref(n)))
+        return dict(hist=hist, max=mx, n_pairs=int(n.value))
+
+    def decay_report(self):
+        """Of the last mi_profile (ldw_decay_report): patches of the histogram kernel, those that took route B, pairs outside their patch's bound, blocks."""
+        v = np.zeros(4, dtype=np.int64)
+        L.check(L.lib().ldw_decay_report(self._ctx, L.ptr(v)))
+        return dict(patches=int(v[0]), route_b=int(v[1]), outside=int(v[2]), blocks=int(v[3]))
+
+    def debug_profile_hist(self, mi, pos_f, pos_t, g, diag, cuts, mi_shift: int = 3, route: int = 0):
+        """The histogram kernel of mi_profile on caller-made values (ldw_debug_profile_hist): ``mi`` (nf, nt) (stored column-major for the call), the positions
+        of the two sides, the genome length, ``diag`` (pairs a > b of a square block) or not (pairs a != b).  route 0: every patch chooses, 1: the LDS window
+        (LdwError LDW_ERR_ARG where it does not fit), 2: wave-aggregated global adds.  Returns the dict of mi_profile plus ``stats`` (patches, route-B patches,
+        pairs outside their patch's bound)."""
+        m = np.asarray(mi, dtype=np.float64)
+        assert m.ndim == 2, m.shape
+        nf, nt = m.shape
+        mf = np.asfortranarray(m)
+        pf, pt = L.as_c(pos_f, np.int32).ravel(), L.as_c(pos_t, np.int32).ravel()
+        assert len(pf) == nf and len(pt) == nt, (len(pf), len(pt), m.shape)
+        cu, n_cut = self._decay_cuts(cuts)
+        nb = 4096 >> mi_shift if 0 <= int(mi_shift) <= 6 else 1
+        hist = np.zeros((min(n_cut, 1023) + 1, nb), dtype=np.uint64)
+        mx = np.full(hist.shape[0], np.nan)
+        n, st = C.c_int64(0), np.zeros(3, dtype=np.int64)
+        L.check(L.lib().ldw_debug_profile_hist(self._ctx, L.ptr(mf), nf, nt, L.ptr(pf), L.ptr(pt), float(g), int(bool(diag)), L.ptr(cu) if n_cut else None, n_cut,
+                                               int(mi_shift), int(route), L.ptr(hist), L.ptr(mx), C.byref(n), L.ptr(st)))
+        return dict(hist=hist, max=mx, n_pairs=int(n.value), stats=st)
+
     def debug_screen_bound(self, kind: int, na: int, nb: int, g, pa, pb, pX, pY, rr, params, masks=None):
         """The engine's screen / evaluation device functions on caller-made joint tables (ldw_debug_screen_bound): kind 0 / 1 the approximate path's upper
         bounds (straight-line / predicated), 2 / 3 the fp32 MI of the exact-limb screens, 4 the fp64 value the engine emits."""

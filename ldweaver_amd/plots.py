@@ -212,6 +212,26 @@ def fit_plot(fit_data_i, i: int, path, *, engine=None) -> str:
     return str(path)
 
 
+DECAY_LABELS = ("Basepair separation (upper edge of the bin)", "MI quantile")
+
+
+def ld_decay_plot(decay, path, q: float = 0.95, *, engine=None) -> str:
+    """The LD-decay curve of ``decay`` (``decay.LDDecay``): the q-quantile of the MI (its lo) of every distance bin that holds a pair against the bin's
+    upper edge as black points, and the background level (``decay.background(q)``; left out when no bin lies at or beyond g / 4) as a red line across,
+    in the layout of the fit figures (PLOT_FIT).  Returns the path."""
+    qlo, _ = decay.quantile(q)
+    keep = np.isfinite(qlo)
+    x, y = np.asarray(decay.len_hi, dtype=np.float64)[keep], qlo[keep]
+    try:
+        bg = decay.background(q)[0]
+        line = (np.array([x.min(), x.max()]), np.array([bg, bg])) if len(x) else None
+    except ValueError:
+        line = None
+    _with_engine(engine, lambda eng: render_xy(eng, x, y, None, line, opts=xy_opts(L.PLOT_FIT), title=f"LD decay (q = {q:g})", xlab=DECAY_LABELS[0],
+                                               ylab=DECAY_LABELS[1], path=path))
+    return str(path)
+
+
 def cds_cluster_plot(cds_var, path, *, engine=None) -> str:
     """``CDS_clustering.png`` (R/estimateCDSDiversity.R:212-220): ``var_estimate`` against ``cds_start``, coloured by the cluster
     ``km_clst_ord`` in ggplot's default hues, in row order.  Returns the path."""
