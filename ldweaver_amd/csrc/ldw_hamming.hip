@@ -336,21 +336,8 @@ static int hamming_run(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *sha
     return LDW_OK;
 }
 
-static int hamming_impl(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *shared_out, int tile0, int tile1, int64_t *counts_out) {
-    if (int rc = check_gpu(c)) return rc;
-    HamBufs bufs;
-    const int rc = hamming_run(c, thresh, hdw_out, shared_out, tile0, tile1, counts_out, bufs);
-    // this context's stream alone touched the blocks: once it is idle they go without a device-wide synchronisation each (other contexts of the
-    // device may be in the middle of a pass).  A failed launch has queued nothing behind it.
-    if (hipStreamSynchronize(c->stream) == hipSuccess) {
-        ldw::DrainedScope quiet;
-        bufs = HamBufs();
-    }
-    return rc;
-}
-
 extern "C" int ldw_hamming_weights(ldw_ctx *c, int32_t thresh, double *hdw_out, int32_t *shared_out) {
-    return hamming_impl(c, thresh, hdw_out, shared_out, -1, -1, nullptr);
+    return ldw::scoped_call<HamBufs>(c, [&](HamBufs &b) { return hamming_run(c, thresh, hdw_out, shared_out, -1, -1, nullptr, b); });
 }
 
 extern "C" int ldw_hamming_stats(ldw_ctx *c, double out[8]) {
@@ -361,5 +348,5 @@ extern "C" int ldw_hamming_stats(ldw_ctx *c, double out[8]) {
 
 extern "C" int ldw_hamming_counts(ldw_ctx *c, int32_t thresh, int32_t tile0, int32_t tile1, int64_t *counts_out) {
     LDW_REQUIRE(tile0 >= 0, LDW_ERR_ARG, "ldw_hamming_counts: tile0 must be >= 0");
-    return hamming_impl(c, thresh, nullptr, nullptr, tile0, tile1, counts_out);
+    return ldw::scoped_call<HamBufs>(c, [&](HamBufs &b) { return hamming_run(c, thresh, nullptr, nullptr, tile0, tile1, counts_out, b); });
 }

@@ -475,6 +475,41 @@ template <class T> int upload(ldw_ctx *ctx, DevBuf &b, const T *src, size_t n) {
     if (n) LDW_HIP(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     return LDW_OK;
 }
+// The frame of an entry point that works in buffers of its own (a struct of DevBufs) rather than the context's: run(bufs), then the buffers go.
+// This context's stream alone touched the blocks: once it is idle they go without a device-wide synchronisation each (other contexts of the
+// device may be in the middle of a pass).  A failed launch has queued nothing behind it; a stream that does not drain leaves them to the destructors.
+template <class Bufs, class Run> int scoped_call(ldw_ctx *ctx, Run run) {
+    if (int rc = check_gpu(ctx)) return rc;
+    Bufs bufs;
+    const int rc = run(bufs);
+    if (hipStreamSynchronize(ctx->stream) == hipSuccess) {
+        DrainedScope quiet;
+        bufs = Bufs();
+    }
+    return rc;
+}
+// The events a chunked call records on its stream, one after the other, and the time between them once the stream has drained
+struct Laps {
+    std::vector<Event> ev;
+    int mark(hipStream_t s) {   // one more event, recorded
+        ev.emplace_back();
+        LDW_HIP(ev.back().ensure());
+        LDW_HIP(hipEventRecord(ev.back(), s));
+        return LDW_OK;
+    }
+    // ms[k % period] += the time from event k to event k + 1.  group > 0: the events come in groups of that many, k counts within its group, and
+    // the time from the last event of a group to the first of the next is nobody's
+    int sums(int period, double *ms, int group = 0) const {
+        for (size_t k = 0; k + 1 < ev.size(); ++k) {
+            const size_t in = group ? k % (size_t)group : k;
+            float x = 0;
+            if (group && in + 1 == (size_t)group) continue;
+            LDW_HIP(hipEventElapsedTime(&x, ev[k], ev[k + 1]));
+            ms[in % (size_t)period] += x;
+        }
+        return LDW_OK;
+    }
+};
 void out_release(ldw_ctx *ctx);      // ldw_out.hip: the alignment writer's staging (ldw_ctx_destroy)
 int64_t out_trim(ldw_ctx *ctx);      // ... its pinned buffers and device image only (ldw_host_trim); bytes released
 }  // namespace ldw

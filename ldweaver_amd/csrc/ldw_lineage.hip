@@ -30,6 +30,7 @@
 #include "ldw_hamming.h"
 #include "ldw_lin_table.h"   // LinTable, lin_eval, lin_zero, lin_add, lin_reduce: shared with ldw_perm.hip
 #include "ldw_prim.h"
+#include "ldw_seq_plan.h"   // LIN_SMALL, build_lin_plan, LabelSet, DistinctSlots: the host side of ldw_links_stratified
 
 using namespace ldw;
 
@@ -37,7 +38,6 @@ namespace ldw {
 
 constexpr int CLU_MAX_THRESH = 16;
 constexpr int64_t CLU_ADJ_BYTES = (int64_t)2 << 30;   // the adjacency bits of the thresholds served by one read of G stay within this
-constexpr int LIN_SMALL = 16;                         // a cluster of at most this many pieces is walked by one lane
 constexpr int64_t LIN_BUDGET = (int64_t)1 << 30;      // bytes of working memory a chunk of pairs may take
 constexpr int LIN_MAX_CLUSTERS = 65536;
 
@@ -233,8 +233,6 @@ __global__ __launch_bounds__(256) void k_lin_pairs(const uint64_t *__restrict__ 
 
 namespace {
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 struct CluBufs {   // the working memory of one ldw_seq_clusters call
     ldw::HamBufs ham;
     ldw::DevBuf adj, f, changed, root, rank, label, scan;
@@ -261,10 +259,8 @@ int clusters_run(ldw_ctx *c, const int32_t *thresh, int32_t n_thresh, int32_t *l
     const unsigned rows4 = (unsigned)ceil_div(N, 4), rows256 = (unsigned)ceil_div(N, 256);
     int32_t *f = b.f.as<int32_t>();
     uint32_t *changed = b.changed.as<uint32_t>();
-    std::vector<ldw::Event> ev((size_t)2 * ceil_div(n_thresh, per_read));
-    for (ldw::Event &e : ev) LDW_HIP(e.ensure());
+    ldw::Laps laps;   // a pair of events per read of G, around its rounds
     int rounds_max = 0;
-    size_t e = 0;
     for (int g0 = 0; g0 < n_thresh; g0 += per_read) {
         const int ng = std::min<int>(per_read, n_thresh - g0);
         ldw::CluThresh th{};
@@ -279,7 +275,7 @@ int clusters_run(ldw_ctx *c, const int32_t *thresh, int32_t n_thresh, int32_t *l
             ldw::DrainedScope quiet;
             b.ham = ldw::HamBufs();
         }
-        LDW_HIP(hipEventRecord(ev[e++], c->stream));
+        if ((rc = laps.mark(c->stream))) return rc;
         uint32_t active = ng == 32 ? 0xFFFFFFFFu : ((1u << ng) - 1u);
         for (int round = 1; active; ++round) {
             LDW_HIP(hipMemsetAsync(changed, 0, 4, c->stream));
@@ -293,7 +289,7 @@ int clusters_run(ldw_ctx *c, const int32_t *thresh, int32_t n_thresh, int32_t *l
             rounds_max = std::max(rounds_max, round);
             LDW_REQUIRE(round <= N + 1, LDW_ERR_HIP, "%s: internal: the rounds do not end", who);
         }
-        LDW_HIP(hipEventRecord(ev[e++], c->stream));
+        if ((rc = laps.mark(c->stream))) return rc;
         for (int g = 0; g < ng; ++g) {
             const int32_t *fg = f + (int64_t)g * N;
             hipLaunchKernelGGL(k_clu_roots, dim3((unsigned)ceil_div(N + 1, 256)), dim3(256), 0, c->stream, N, fg, b.root.as<int32_t>());
@@ -307,13 +303,10 @@ int clusters_run(ldw_ctx *c, const int32_t *thresh, int32_t n_thresh, int32_t *l
         }
     }
     // the rounds' time: between each read's pair of events; what ran in front: ev[0] (hamming_gram's) to the first event, and between the reads
-    float t_rounds = 0, t_total = 0;
-    for (size_t q = 0; q + 1 < ev.size(); q += 2) {
-        float x = 0;
-        LDW_HIP(hipEventElapsedTime(&x, ev[q], ev[q + 1]));
-        t_rounds += x;
-    }
-    LDW_HIP(hipEventElapsedTime(&t_total, c->ev[0], ev.back()));
+    double t_rounds = 0;
+    float t_total = 0;
+    if ((rc = laps.sums(1, &t_rounds, 2))) return rc;
+    LDW_HIP(hipEventElapsedTime(&t_total, c->ev[0], laps.ev.back()));
     c->last_ms[0] = t_rounds;
     c->last_ms[1] = (double)t_total - t_rounds;   // the Hamming GEMM, the adjacency bits (and, between two reads of G, the labels of the first)
     c->last_ms[2] = (double)rounds_max;           // rounds of the threshold that took most
@@ -337,75 +330,35 @@ int stratified_run(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int
     LDW_REQUIRE(K < (1ll << 31), LDW_ERR_ARG, "%s: too many pairs", who);
     LDW_REQUIRE(C >= 1 && C <= LIN_MAX_CLUSTERS, LDW_ERR_ARG, "%s: C = %d clusters (1..%d)", who, (int)C, LIN_MAX_CLUSTERS);
     const int64_t N = c->N, L = c->L;
-    int64_t P = 0;
-    for (int64_t s = 0; s < N; ++s) {
-        LDW_REQUIRE(labels[s] >= -1 && labels[s] < C, LDW_ERR_ARG, "%s: labels[%lld] = %d (-1, or a cluster 0..%d)", who, (long long)s, (int)labels[s], (int)(C - 1));
-        P += labels[s] >= 0;
-    }
+    const ldw::LabelSet ls = ldw::LabelSet::scan(labels, N, C);
+    LDW_REQUIRE(ls.bad < 0, LDW_ERR_ARG, "%s: labels[%lld] = %d (-1, or a cluster 0..%d)", who, (long long)ls.bad, (int)labels[ls.bad], (int)(C - 1));
+    const int64_t P = ls.P;
     LDW_REQUIRE(P >= 1, LDW_ERR_ARG, "%s: every label is -1: no sequence to count", who);
-    for (int64_t i = 0; i < K; ++i) {
-        LDW_REQUIRE(pair_a[i] >= 0 && pair_a[i] < L, LDW_ERR_ARG, "%s: pair_a[%lld] = %d (the alignment has SNPs 0..%lld)", who, (long long)i, (int)pair_a[i], (long long)(L - 1));
-        LDW_REQUIRE(pair_b[i] >= 0 && pair_b[i] < L, LDW_ERR_ARG, "%s: pair_b[%lld] = %d (the alignment has SNPs 0..%lld)", who, (long long)i, (int)pair_b[i], (long long)(L - 1));
-    }
+    int64_t bad_k = -1;
+    const int32_t *bad = ldw::first_bad_pair(pair_a, pair_b, K, L, &bad_k);
+    LDW_REQUIRE(!bad, LDW_ERR_ARG, "%s: %s[%lld] = %d (the alignment has SNPs 0..%lld)", who, bad == pair_a ? "pair_a" : "pair_b", (long long)bad_k, (int)bad[bad_k], (long long)(L - 1));
     const std::vector<int64_t> &V = c->wts.h_vfixed;
     const std::vector<double> &hdw = c->wts.h_hdw;
     const bool want_tables = counts_out != nullptr;
 
-    // ---- the order of the labelled sequences, the pieces, the clusters' ranges and sums ----
-    std::vector<int32_t> perm;
-    perm.reserve((size_t)P);
-    for (int64_t s = 0; s < N; ++s)
-        if (labels[s] >= 0) perm.push_back((int32_t)s);
-    std::sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) {
-        if (labels[x] != labels[y]) return labels[x] < labels[y];
-        if (V[(size_t)x] != V[(size_t)y]) return V[(size_t)x] < V[(size_t)y];
-        return x < y;
-    });
+    // ---- the order of the labelled sequences, the pieces, the clusters' ranges, the jobs (ldw_seq_plan.h) and the clusters' sums ----
+    const ldw::LinPlan plan = ldw::build_lin_plan(labels, V.data(), N, C, P);
     const int64_t W = ceil_div(P, 64);
-    std::vector<int32_t> pc_word;
-    std::vector<uint64_t> pc_mask;
-    std::vector<int64_t> pc_v, clu_piece((size_t)C + 1, 0);
-    for (int64_t p = 0; p < P;) {   // a piece: the positions of one word that share label and V
-        const int32_t s = perm[(size_t)p];
-        int64_t q = p + 1;
-        while (q < P && (q >> 6) == (p >> 6) && labels[perm[(size_t)q]] == labels[s] && V[(size_t)perm[(size_t)q]] == V[(size_t)s]) ++q;
-        const int n = (int)(q - p);
-        pc_word.push_back((int32_t)(p >> 6));
-        pc_mask.push_back((n == 64 ? ~0ull : ((1ull << n) - 1ull)) << (p & 63));
-        pc_v.push_back(V[(size_t)s]);
-        ++clu_piece[(size_t)labels[s] + 1];
-        p = q;
-    }
-    for (int32_t k = 0; k < C; ++k) clu_piece[(size_t)k + 1] += clu_piece[(size_t)k];
-    std::vector<long double> sums((size_t)C + 1, 0.0L);   // per cluster and, last, over all labelled sequences, each in sequence order
-    for (int64_t s = 0; s < N; ++s)
-        if (labels[s] >= 0) sums[(size_t)labels[s]] += (long double)hdw[(size_t)s], sums[(size_t)C] += (long double)hdw[(size_t)s];
+    const int32_t n_jobs = (int32_t)plan.job_first.size();
     std::vector<double> neff((size_t)C + 1);
-    for (size_t k = 0; k <= (size_t)C; ++k) neff[k] = (double)sums[k];
-    // the jobs: every large cluster on its own, the small ones 64 to a job; a cluster without a member is in neither
-    std::vector<int32_t> job_first, job_count, small;
-    for (int32_t k = 0; k < C; ++k) {
-        const int64_t n = clu_piece[(size_t)k + 1] - clu_piece[(size_t)k];
-        if (n > LIN_SMALL) job_first.push_back(k), job_count.push_back(0);
-        else if (n > 0) small.push_back(k);
-    }
-    for (size_t s0 = 0; s0 < small.size(); s0 += 64) job_first.push_back((int32_t)s0), job_count.push_back((int32_t)std::min<size_t>(64, small.size() - s0));
-    const int32_t n_jobs = (int32_t)job_first.size();
+    ldw::LabelSet::neff(labels, hdw.data(), N, C, neff.data());
 
     // ---- pairs per chunk: the rows of its distinct SNPs (2 k at most, and never more than L) and k rows of every output within the budget ----
     const int64_t row_bytes = 5 * W * 8 + 2 * 4, out_bytes = (int64_t)C * (8 + 1 + (want_tables ? 400 : 0)) + 8 + 2 * 4;
     int64_t chunk = L * row_bytes <= LIN_BUDGET / 2 ? (LIN_BUDGET - L * row_bytes) / out_bytes : LIN_BUDGET / (2 * row_bytes + out_bytes);
-    chunk = std::max<int64_t>(1, chunk);
-    if (const char *e = getenv("LDW_LIN_CHUNK")) {
-        const long long k = atoll(e);
-        if (k >= 1) chunk = k;
-    }
+    chunk = ldw::budget_or_env(std::max<int64_t>(1, chunk), "LDW_LIN_CHUNK");
     chunk = std::min<int64_t>(std::min<int64_t>(chunk, K), (int64_t)1 << 24);
     int rc = LDW_OK;
-    if ((rc = ldw::upload(c, b.perm, perm.data(), perm.size())) || (rc = ldw::upload(c, b.pc_word, pc_word.data(), pc_word.size())) ||
-        (rc = ldw::upload(c, b.pc_mask, pc_mask.data(), pc_mask.size())) || (rc = ldw::upload(c, b.pc_v, pc_v.data(), pc_v.size())) ||
-        (rc = ldw::upload(c, b.clu_piece, clu_piece.data(), clu_piece.size())) || (rc = ldw::upload(c, b.job_first, job_first.data(), job_first.size())) ||
-        (rc = ldw::upload(c, b.job_count, job_count.data(), job_count.size())) || (rc = ldw::upload(c, b.small, small.data(), small.size())) ||
+    if ((rc = ldw::upload(c, b.perm, plan.perm.data(), plan.perm.size())) || (rc = ldw::upload(c, b.pc_word, plan.pc_word.data(), plan.pc_word.size())) ||
+        (rc = ldw::upload(c, b.pc_mask, plan.pc_mask.data(), plan.pc_mask.size())) || (rc = ldw::upload(c, b.pc_v, plan.pc_v.data(), plan.pc_v.size())) ||
+        (rc = ldw::upload(c, b.clu_piece, plan.clu_piece.data(), plan.clu_piece.size())) ||
+        (rc = ldw::upload(c, b.job_first, plan.job_first.data(), plan.job_first.size())) ||
+        (rc = ldw::upload(c, b.job_count, plan.job_count.data(), plan.job_count.size())) || (rc = ldw::upload(c, b.small, plan.small.data(), plan.small.size())) ||
         (rc = ldw::upload(c, b.neff, neff.data(), neff.size())))
         return rc;
     const size_t rows = (size_t)chunk * (size_t)C, d_max = (size_t)std::min<int64_t>(2 * chunk, L);
@@ -414,34 +367,26 @@ int stratified_run(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int
         (rc = b.poly.reserve(rows)) || (rc = b.mi_all.reserve((size_t)chunk * 8)) ||
         (want_tables && ((rc = b.tab_cnt.reserve(rows * 25 * 8)) || (rc = b.tab_fix.reserve(rows * 25 * 8)))))
         return rc;
-    const int64_t n_chunks = ceil_div(K, chunk);
-    std::vector<ldw::Event> ev((size_t)n_chunks * 3 + 1);
-    for (ldw::Event &e : ev) LDW_HIP(e.ensure());
+    ldw::Laps laps;   // three events per chunk and one behind the last
     const double scale = std::ldexp(1.0, -c->wts.frac_bits);
-    std::vector<int32_t> d, sa, sb;
-    size_t e = 0;
+    ldw::DistinctSlots ds;
+    std::vector<int32_t> sa, sb;
     for (int64_t k0 = 0; k0 < K; k0 += chunk) {
         const int64_t k = std::min<int64_t>(chunk, K - k0);
-        d.assign(pair_a + k0, pair_a + k0 + k);   // the distinct SNPs of the chunk in ascending order (as ldw_tree_cochanges finds them)
-        d.insert(d.end(), pair_b + k0, pair_b + k0 + k);
-        std::sort(d.begin(), d.end());
-        d.erase(std::unique(d.begin(), d.end()), d.end());
+        ds.assign(pair_a + k0, k, pair_b + k0, k);   // the distinct SNPs of the chunk
         sa.resize((size_t)k), sb.resize((size_t)k);
-        for (int64_t i = 0; i < k; ++i) {
-            sa[(size_t)i] = (int32_t)(std::lower_bound(d.begin(), d.end(), pair_a[k0 + i]) - d.begin());
-            sb[(size_t)i] = (int32_t)(std::lower_bound(d.begin(), d.end(), pair_b[k0 + i]) - d.begin());
-        }
-        const int64_t D = (int64_t)d.size();
+        for (int64_t i = 0; i < k; ++i) sa[(size_t)i] = ds.slot(pair_a[k0 + i]), sb[(size_t)i] = ds.slot(pair_b[k0 + i]);
+        const int64_t D = (int64_t)ds.d.size();
         const size_t out_rows = (size_t)k * (size_t)C;
-        LDW_HIP(hipEventRecord(ev[e++], c->stream));
-        LDW_HIP(hipMemcpyAsync(b.snp.p, d.data(), (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        if ((rc = laps.mark(c->stream))) return rc;
+        LDW_HIP(hipMemcpyAsync(b.snp.p, ds.d.data(), (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemcpyAsync(b.slot_a.p, sa.data(), (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemcpyAsync(b.slot_b.p, sb.data(), (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
         LDW_HIP(hipMemsetAsync(b.seen.p, 0, (size_t)D * 4, c->stream));
         hipLaunchKernelGGL(k_lin_bits, dim3((unsigned)D, (unsigned)ceil_div(W, 4)), dim3(256), 0, c->stream, c->states.as<uint8_t>(), c->Npad, b.snp.as<int32_t>(),
                            b.perm.as<int32_t>(), P, W, b.bits.as<uint64_t>(), b.seen.as<uint32_t>());
         LDW_HIP(hipGetLastError());
-        LDW_HIP(hipEventRecord(ev[e++], c->stream));
+        if ((rc = laps.mark(c->stream))) return rc;
         LDW_HIP(hipMemsetAsync(b.mi.p, 0, out_rows * 8, c->stream));   // (a cluster without a member: 0 everywhere)
         LDW_HIP(hipMemsetAsync(b.poly.p, 0, out_rows, c->stream));
         if (want_tables) {
@@ -453,7 +398,7 @@ int stratified_run(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int
                            b.pc_word.as<int32_t>(), b.pc_mask.as<uint64_t>(), b.pc_v.as<int64_t>(), b.neff.as<double>(), scale, b.mi.as<double>(), b.poly.as<uint8_t>(),
                            b.mi_all.as<double>(), want_tables ? b.tab_cnt.as<int64_t>() : (int64_t *)nullptr, want_tables ? b.tab_fix.as<int64_t>() : (int64_t *)nullptr);
         LDW_HIP(hipGetLastError());
-        LDW_HIP(hipEventRecord(ev[e++], c->stream));
+        if ((rc = laps.mark(c->stream))) return rc;
         LDW_HIP(hipMemcpyAsync(mi_out + k0 * C, b.mi.p, out_rows * 8, hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipMemcpyAsync(poly_out + k0 * C, b.poly.p, out_rows, hipMemcpyDeviceToHost, c->stream));
         LDW_HIP(hipMemcpyAsync(mi_all_out + k0, b.mi_all.p, (size_t)k * 8, hipMemcpyDeviceToHost, c->stream));
@@ -461,18 +406,14 @@ int stratified_run(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int
             LDW_HIP(hipMemcpyAsync(counts_out + k0 * C * 25, b.tab_cnt.p, out_rows * 25 * 8, hipMemcpyDeviceToHost, c->stream));
             LDW_HIP(hipMemcpyAsync(fixed_out + k0 * C * 25, b.tab_fix.p, out_rows * 25 * 8, hipMemcpyDeviceToHost, c->stream));
         }
-        LDW_HIP(hipStreamSynchronize(c->stream));   // (d, sa and sb are filled again for the next chunk)
+        LDW_HIP(hipStreamSynchronize(c->stream));   // (ds, sa and sb are filled again for the next chunk)
     }
-    LDW_HIP(hipEventRecord(ev[e], c->stream));
+    if ((rc = laps.mark(c->stream))) return rc;
     LDW_HIP(hipStreamSynchronize(c->stream));
     for (int32_t k = 0; k < C; ++k) neff_out[k] = neff[(size_t)k];
     *frac_bits_out = c->wts.frac_bits;
     double ms[3] = {0, 0, 0};
-    for (size_t q = 0; q + 1 < ev.size(); ++q) {
-        float x = 0;
-        LDW_HIP(hipEventElapsedTime(&x, ev[q], ev[q + 1]));
-        ms[q % 3] += x;
-    }
+    if ((rc = laps.sums(3, ms))) return rc;
     c->last_ms[0] = ms[1];   // k_lin_pairs (with the zeroing of its outputs)
     c->last_ms[1] = ms[0];   // the chunk's uploads and k_lin_bits
     c->last_ms[2] = ms[2];   // the copies out
@@ -480,27 +421,15 @@ int stratified_run(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int
     return LDW_OK;
 }
 
-// as ldw_nj_tree: this context's stream alone touched the blocks
-template <class Bufs, class Run> int lin_call(ldw_ctx *c, Run run) {
-    if (int rc = check_gpu(c)) return rc;
-    Bufs bufs;
-    const int rc = run(bufs);
-    if (hipStreamSynchronize(c->stream) == hipSuccess) {
-        ldw::DrainedScope quiet;
-        bufs = Bufs();
-    }
-    return rc;
-}
-
 }  // namespace
 
 extern "C" int ldw_seq_clusters(ldw_ctx *c, const int32_t *thresh, int32_t n_thresh, int32_t *labels_out, int32_t *n_clusters_out) {
-    return lin_call<CluBufs>(c, [&](CluBufs &b) { return clusters_run(c, thresh, n_thresh, labels_out, n_clusters_out, b); });
+    return ldw::scoped_call<CluBufs>(c, [&](CluBufs &b) { return clusters_run(c, thresh, n_thresh, labels_out, n_clusters_out, b); });
 }
 
 extern "C" int ldw_links_stratified(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int64_t K, const int32_t *labels, int32_t C, double *mi_out,
                                     double *mi_all_out, uint8_t *poly_out, double *neff_out, int64_t *counts_out, int64_t *fixed_out, int *frac_bits_out) {
-    return lin_call<LinBufs>(c, [&](LinBufs &b) {
+    return ldw::scoped_call<LinBufs>(c, [&](LinBufs &b) {
         return stratified_run(c, pair_a, pair_b, K, labels, C, mi_out, mi_all_out, poly_out, neff_out, counts_out, fixed_out, frac_bits_out, b);
     });
 }

@@ -18,6 +18,7 @@
 
 #include "ldw_internal.h"
 #include "ldw_hamming.h"
+#include "ldw_seq_plan.h"
 
 using namespace ldw;
 
@@ -474,15 +475,7 @@ static int nj_run(ldw_ctx *c, const double *dist, int64_t n, int32_t *parent_out
 }
 
 extern "C" int ldw_nj_tree(ldw_ctx *c, const double *dist, int64_t n, int32_t *parent_out, double *length_out) {
-    if (int rc = check_gpu(c)) return rc;
-    NjBufs bufs;
-    const int rc = nj_run(c, dist, n, parent_out, length_out, bufs);
-    // as hamming_impl: this context's stream alone touched the blocks
-    if (hipStreamSynchronize(c->stream) == hipSuccess) {
-        ldw::DrainedScope quiet;
-        bufs = NjBufs();
-    }
-    return rc;
+    return ldw::scoped_call<NjBufs>(c, [&](NjBufs &b) { return nj_run(c, dist, n, parent_out, length_out, b); });
 }
 
 // ---- bootstrap support ----------------------------------------------------------------------------------------------------------------------------------
@@ -499,12 +492,7 @@ struct NjBootBufs {   // the working memory of one call: the single tree's, the 
 
 // the batch size R of this call: LDW_NJ_BATCH=k forces k (a test hook, read at every call); never more than B
 static int64_t nj_batch_size(int64_t B, int64_t N) {
-    int64_t R = std::min<int64_t>(NJ_BATCH_CAP, std::max<int64_t>(1, NJ_BATCH_BYTES / (8 * N * N)));
-    if (const char *e = getenv("LDW_NJ_BATCH")) {
-        const long long k = atoll(e);
-        if (k >= 1) R = k;
-    }
-    return std::min<int64_t>(R, B);
+    return std::min<int64_t>(ldw::budget_or_env(std::min<int64_t>(NJ_BATCH_CAP, std::max<int64_t>(1, NJ_BATCH_BYTES / (8 * N * N))), "LDW_NJ_BATCH"), B);
 }
 
 static int nj_boot_run(ldw_ctx *c, const int32_t *mult, int64_t B, int64_t n, int32_t *parent_out, double *length_out, int32_t *support_out,
@@ -573,13 +561,12 @@ static int nj_boot_run(ldw_ctx *c, const int32_t *mult, int64_t B, int64_t n, in
     // the replicates, R at a time: digits, GEMM and fill one after the other into G (the stream orders them), then the joins of all R, their sums, the look-up
     const NjBatch strides{N * N, N, sP};
     const int64_t n_batches = (B + R - 1) / R;
-    std::vector<ldw::Event> ev((size_t)n_batches * 4);
-    for (ldw::Event &e : ev) LDW_HIP(e.ensure());
+    ldw::Laps laps;   // four events per batch: the three intervals between them count, what lies between two batches does not
     for (int64_t q = 0; q < n_batches; ++q) {
         const int64_t b0 = q * R, nb = std::min<int64_t>(R, B - b0);
         int32_t *bpar = parent + (1 + (keep ? b0 : 0)) * sP;
         double *blen = length + (1 + (keep ? b0 : 0)) * sP;
-        LDW_HIP(hipEventRecord(ev[4 * q], c->stream));
+        if ((rc = laps.mark(c->stream))) return rc;
         LDW_HIP(hipMemcpyAsync(b.mult.p, mult + b0 * L, (size_t)nb * L * 4, hipMemcpyHostToDevice, c->stream));
         for (int64_t k = 0; k < nb; ++k) {
             hipLaunchKernelGGL(k_boot_digits, dim3((unsigned)((shape.Kpad + NJ_THREADS - 1) / NJ_THREADS)), dim3(NJ_THREADS), 0, c->stream, t.ham.dig.as<int8_t>(),
@@ -590,11 +577,11 @@ static int nj_boot_run(ldw_ctx *c, const int32_t *mult, int64_t B, int64_t n, in
             hipLaunchKernelGGL(k_boot_fill, dim3((unsigned)N), dim3(NJ_THREADS), 0, c->stream, G, ldg, N, D + k * N * N, r + k * N, id + k * N);
             LDW_HIP(hipGetLastError());
         }
-        LDW_HIP(hipEventRecord(ev[4 * q + 1], c->stream));
+        if ((rc = laps.mark(c->stream))) return rc;
         // (a batch of one takes the single tree's kernels: the same bodies, and 6.2 ms instead of 7.8 for a launch-bound tree of 616 tips)
         if ((rc = nb == 1 ? nj_queue_tree(c, N, D, r, id, part, join, bpar, blen) : nj_queue_trees(c, N, (int)nb, strides, D, r, id, part, join, bpar, blen)))
             return rc;
-        LDW_HIP(hipEventRecord(ev[4 * q + 2], c->stream));
+        if ((rc = laps.mark(c->stream))) return rc;
         if (M > 0) {
             LDW_HIP(hipMemsetAsync(h, 0, (size_t)nb * 2 * sP * 8, c->stream));
             hipLaunchKernelGGL(k_boot_hash, dim3(tip_grid, (unsigned)nb), dim3(NJ_THREADS), 0, c->stream, bpar, sP, N, h);
@@ -602,7 +589,7 @@ static int nj_boot_run(ldw_ctx *c, const int32_t *mult, int64_t B, int64_t n, in
                                sorted, node, support);
             LDW_HIP(hipGetLastError());
         }
-        LDW_HIP(hipEventRecord(ev[4 * q + 3], c->stream));
+        if ((rc = laps.mark(c->stream))) return rc;
     }
     LDW_HIP(hipMemcpyAsync(parent_out, parent, (size_t)sP * 4, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipMemcpyAsync(length_out, length, (size_t)sP * 8, hipMemcpyDeviceToHost, c->stream));
@@ -611,12 +598,7 @@ static int nj_boot_run(ldw_ctx *c, const int32_t *mult, int64_t B, int64_t n, in
     if (rep_length_out) LDW_HIP(hipMemcpyAsync(rep_length_out, length + sP, (size_t)B * sP * 8, hipMemcpyDeviceToHost, c->stream));
     LDW_HIP(hipStreamSynchronize(c->stream));
     double ms[3] = {0, 0, 0};
-    for (int64_t q = 0; q < n_batches; ++q)
-        for (int k = 0; k < 3; ++k) {
-            float x = 0;
-            LDW_HIP(hipEventElapsedTime(&x, ev[4 * q + k], ev[4 * q + k + 1]));
-            ms[k] += x;
-        }
+    if ((rc = laps.sums(3, ms, 4))) return rc;
     c->last_ms[0] = ms[1];                     // the replicates' joins and roots
     c->last_ms[1] = ms[0];                     // their multiplicities, digits, GEMMs and fills
     c->last_ms[2] = ms[2];                     // their sums and look-ups
@@ -626,12 +608,6 @@ static int nj_boot_run(ldw_ctx *c, const int32_t *mult, int64_t B, int64_t n, in
 
 extern "C" int ldw_nj_bootstrap(ldw_ctx *c, const int32_t *mult, int64_t B, int64_t n, int32_t *parent_out, double *length_out, int32_t *support_out,
                                 int32_t *rep_parent_out, double *rep_length_out) {
-    if (int rc = check_gpu(c)) return rc;
-    NjBootBufs bufs;
-    const int rc = nj_boot_run(c, mult, B, n, parent_out, length_out, support_out, rep_parent_out, rep_length_out, bufs);
-    if (hipStreamSynchronize(c->stream) == hipSuccess) {
-        ldw::DrainedScope quiet;
-        bufs = NjBootBufs();
-    }
-    return rc;
+    return ldw::scoped_call<NjBootBufs>(
+        c, [&](NjBootBufs &b) { return nj_boot_run(c, mult, B, n, parent_out, length_out, support_out, rep_parent_out, rep_length_out, b); });
 }

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ldw_internal.h"
+#include "ldw_seq_plan.h"
 
 using namespace ldw;
 
@@ -232,15 +233,9 @@ int pars_check_tree(const ldw_ctx *c, const char *who, const int32_t *parent, co
     return LDW_OK;
 }
 
-int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
 // SNPs of a chunk: what PARS_BUDGET bytes of sets hold, LDW_PARS_CHUNK=k forces k (a test hook, read at every call); never more than `total`
 int64_t pars_chunk(int64_t nodes, int64_t total) {
-    int64_t C = std::max<int64_t>(PARS_TILE, PARS_BUDGET / nodes / PARS_TILE * PARS_TILE);
-    if (const char *e = getenv("LDW_PARS_CHUNK")) {
-        const long long k = atoll(e);
-        if (k >= 1) C = k;
-    }
+    const int64_t C = ldw::budget_or_env(std::max<int64_t>(PARS_TILE, PARS_BUDGET / nodes / PARS_TILE * PARS_TILE), "LDW_PARS_CHUNK");
     return std::min<int64_t>(std::min<int64_t>(C, PARS_MAX_CHUNK), total);
 }
 
@@ -253,8 +248,7 @@ struct ParsRun {
     const ParsTree &t;
     int32_t gap_mode;
     int64_t C = 0, Cpad = 0, stride4 = 0;
-    std::vector<ldw::Event> ev;
-    double ms[3] = {0, 0, 0};
+    ldw::Laps laps;   // three events per chunk and one behind the last
 
     int start(const int32_t *parent, int64_t total, const int32_t *snp, bool want_score, bool down) {
         C = pars_chunk(t.nodes, total), Cpad = round_up(C, PARS_TILE), stride4 = Cpad / 4;
@@ -267,24 +261,20 @@ struct ParsRun {
             return rc;
         if (down && (rc = ldw::upload(c, b.parent, parent, (size_t)t.nodes))) return rc;
         if (snp && (rc = ldw::upload(c, b.snp, snp, (size_t)total))) return rc;
-        const int64_t n_chunks = (total + C - 1) / C;
-        ev.resize((size_t)n_chunks * 3 + 1);
-        for (ldw::Event &e : ev) LDW_HIP(e.ensure());
         return LDW_OK;
     }
 
     template <class After> int chunks(int64_t total, bool have_snp, bool want_score, bool down, uint32_t *bits, int64_t bit_stride, After after_chunk) {
         uint32_t *sets = b.sets.as<uint32_t>(), *seen = b.seen.as<uint32_t>();
-        size_t e = 0;
         for (int64_t j0 = 0; j0 < total; j0 += C) {
             const int64_t count = std::min<int64_t>(C, total - j0);
-            LDW_HIP(hipEventRecord(ev[e++], c->stream));
+            if (int rc = laps.mark(c->stream)) return rc;
             LDW_HIP(hipMemsetAsync(seen, 0, (size_t)Cpad, c->stream));
             hipLaunchKernelGGL(k_pars_tips, dim3((unsigned)((t.tips + PARS_TIPS - 1) / PARS_TIPS), (unsigned)(Cpad / PARS_TILE)), dim3(256), 0, c->stream,
                                c->states.as<uint8_t>(), c->Npad, b.tip_seq.as<int32_t>(), b.tip_node.as<int32_t>(), t.tips,
                                have_snp ? b.snp.as<int32_t>() + j0 : (const int32_t *)nullptr, j0, count, gap_mode, sets, stride4, seen);
             LDW_HIP(hipGetLastError());
-            LDW_HIP(hipEventRecord(ev[e++], c->stream));
+            if (int rc = laps.mark(c->stream)) return rc;
             hipLaunchKernelGGL(k_pars_up, dim3((unsigned)(stride4 / PARS_WAVE)), dim3(PARS_WAVE), 0, c->stream, sets, stride4, t.nodes, b.child_ptr.as<int32_t>(),
                                b.child_idx.as<int32_t>(), seen, want_score ? b.score.as<int32_t>() : (int32_t *)nullptr,
                                want_score ? b.minch.as<int32_t>() : (int32_t *)nullptr);
@@ -292,20 +282,16 @@ struct ParsRun {
                 hipLaunchKernelGGL(k_pars_down, dim3((unsigned)(stride4 / PARS_WAVE)), dim3(PARS_WAVE), 0, c->stream, sets, stride4, t.nodes, b.parent.as<int32_t>(),
                                    bits, bit_stride, j0, count);
             LDW_HIP(hipGetLastError());
-            LDW_HIP(hipEventRecord(ev[e++], c->stream));
+            if (int rc = laps.mark(c->stream)) return rc;
             if (int rc = after_chunk(j0, count)) return rc;
         }
-        LDW_HIP(hipEventRecord(ev[e], c->stream));
-        return LDW_OK;
+        return laps.mark(c->stream);
     }
 
     // after the stream has drained
     int finish() {
-        for (size_t k = 0; k + 1 < ev.size(); ++k) {
-            float x = 0;
-            LDW_HIP(hipEventElapsedTime(&x, ev[k], ev[k + 1]));
-            ms[k % 3] += x;
-        }
+        double ms[3] = {0, 0, 0};
+        if (int rc = laps.sums(3, ms)) return rc;
         c->last_ms[0] = ms[1];   // the passes
         c->last_ms[1] = ms[0];   // the gathers
         c->last_ms[2] = ms[2];   // what followed a chunk: the copies out, the transposes, the pairs
@@ -315,9 +301,8 @@ struct ParsRun {
 };
 
 int pars_check_snps(const ldw_ctx *c, const char *who, const char *what, const int32_t *idx, int64_t n) {
-    for (int64_t k = 0; k < n; ++k)
-        LDW_REQUIRE(idx[k] >= 0 && idx[k] < c->L, LDW_ERR_ARG, "%s: %s[%lld] = %d (the alignment has SNPs 0..%lld)", who, what, (long long)k, (int)idx[k],
-                    (long long)(c->L - 1));
+    const int64_t k = ldw::first_bad_index(idx, n, c->L);
+    LDW_REQUIRE(k < 0, LDW_ERR_ARG, "%s: %s[%lld] = %d (the alignment has SNPs 0..%lld)", who, what, (long long)k, (int)idx[k], (long long)(c->L - 1));
     return LDW_OK;
 }
 
@@ -339,16 +324,6 @@ int parsimony_run(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int
     return run.finish();
 }
 
-// the distinct SNPs of a list in ascending order
-std::vector<int32_t> pars_distinct(const int32_t *a, int64_t na, const int32_t *b, int64_t nb) {
-    std::vector<int32_t> d(a, a + na);
-    if (b) d.insert(d.end(), b, b + nb);
-    std::sort(d.begin(), d.end());
-    d.erase(std::unique(d.begin(), d.end()), d.end());
-    return d;
-}
-int32_t pars_slot(const std::vector<int32_t> &d, int32_t snp) { return (int32_t)(std::lower_bound(d.begin(), d.end(), snp) - d.begin()); }
-
 int states_run(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, const int32_t *snp_idx, int64_t k, uint8_t *out,
                ParsBufs &b) {
     const char *who = "ldw_tree_states";
@@ -359,10 +334,10 @@ int states_run(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int64_
     ParsTree t;
     if (int rc = pars_check_tree(c, who, parent, tip_seq, nodes, gap_mode, t)) return rc;
     if (int rc = pars_check_snps(c, who, "snp_idx", snp_idx, k)) return rc;
-    const std::vector<int32_t> d = pars_distinct(snp_idx, k, nullptr, 0);
-    const int64_t D = (int64_t)d.size();
+    const ldw::DistinctSlots ds(snp_idx, k, nullptr, 0);
+    const int64_t D = (int64_t)ds.d.size();
     ParsRun run{c, b, t, gap_mode};
-    if (int rc = run.start(parent, D, d.data(), false, true)) return rc;
+    if (int rc = run.start(parent, D, ds.d.data(), false, true)) return rc;
     if (int rc = b.state.reserve((size_t)run.C * (size_t)nodes)) return rc;
     std::vector<uint8_t> rows((size_t)run.C * (size_t)nodes);
     if (int rc = run.chunks(D, true, false, true, nullptr, 0, [&](int64_t j0, int64_t count) {
@@ -372,7 +347,7 @@ int states_run(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int64_
             LDW_HIP(hipMemcpyAsync(rows.data(), b.state.p, (size_t)count * (size_t)nodes, hipMemcpyDeviceToHost, c->stream));
             LDW_HIP(hipStreamSynchronize(c->stream));
             for (int64_t i = 0; i < k; ++i) {   // a SNP listed twice gets its row twice
-                const int64_t s = pars_slot(d, snp_idx[i]);
+                const int64_t s = ds.slot(snp_idx[i]);
                 if (s >= j0 && s < j0 + count) memcpy(out + i * nodes, rows.data() + (s - j0) * nodes, (size_t)nodes);
             }
             return (int)LDW_OK;
@@ -393,13 +368,13 @@ int cochanges_run(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int
     if (int rc = pars_check_tree(c, who, parent, tip_seq, nodes, gap_mode, t)) return rc;
     if (int rc = pars_check_snps(c, who, "pair_a", pair_a, K)) return rc;
     if (int rc = pars_check_snps(c, who, "pair_b", pair_b, K)) return rc;
-    const std::vector<int32_t> d = pars_distinct(pair_a, K, pair_b, K);
-    const int64_t D = (int64_t)d.size(), words = (nodes + 31) / 32;
+    const ldw::DistinctSlots ds(pair_a, K, pair_b, K);
+    const int64_t D = (int64_t)ds.d.size(), words = (nodes + 31) / 32;
     std::vector<int32_t> sa((size_t)K), sb((size_t)K);
-    for (int64_t i = 0; i < K; ++i) sa[(size_t)i] = pars_slot(d, pair_a[i]), sb[(size_t)i] = pars_slot(d, pair_b[i]);
+    for (int64_t i = 0; i < K; ++i) sa[(size_t)i] = ds.slot(pair_a[i]), sb[(size_t)i] = ds.slot(pair_b[i]);
     ParsRun run{c, b, t, gap_mode};
     int rc = LDW_OK;
-    if ((rc = run.start(parent, D, d.data(), false, true)) || (rc = b.bits.reserve((size_t)words * (size_t)D * 4)) || (rc = ldw::upload(c, b.slot_a, sa.data(), sa.size())) ||
+    if ((rc = run.start(parent, D, ds.d.data(), false, true)) || (rc = b.bits.reserve((size_t)words * (size_t)D * 4)) || (rc = ldw::upload(c, b.slot_a, sa.data(), sa.size())) ||
         (rc = ldw::upload(c, b.slot_b, sb.data(), sb.size())) || (rc = b.ca.reserve((size_t)K * 4)) || (rc = b.cb.reserve((size_t)K * 4)) ||
         (rc = b.co.reserve((size_t)K * 4)))
         return rc;
@@ -415,36 +390,24 @@ int cochanges_run(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int
     LDW_HIP(hipStreamSynchronize(c->stream));
     if ((rc = run.finish())) return rc;
     float pairs_ms = 0;
-    LDW_HIP(hipEventElapsedTime(&pairs_ms, run.ev.back(), c->ev[0]));
+    LDW_HIP(hipEventElapsedTime(&pairs_ms, run.laps.ev.back(), c->ev[0]));
     c->last_ms[2] += pairs_ms, c->last_ms[3] += pairs_ms;
     return LDW_OK;
-}
-
-// as ldw_nj_tree: this context's stream alone touched the blocks
-template <class Run> int pars_call(ldw_ctx *c, Run run) {
-    if (int rc = check_gpu(c)) return rc;
-    ParsBufs bufs;
-    const int rc = run(bufs);
-    if (hipStreamSynchronize(c->stream) == hipSuccess) {
-        ldw::DrainedScope quiet;
-        bufs = ParsBufs();
-    }
-    return rc;
 }
 
 }  // namespace
 
 extern "C" int ldw_tree_parsimony(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, int32_t *score_out,
                                   int32_t *min_changes_out) {
-    return pars_call(c, [&](ParsBufs &b) { return parsimony_run(c, parent, tip_seq, nodes, gap_mode, score_out, min_changes_out, b); });
+    return ldw::scoped_call<ParsBufs>(c, [&](ParsBufs &b) { return parsimony_run(c, parent, tip_seq, nodes, gap_mode, score_out, min_changes_out, b); });
 }
 
 extern "C" int ldw_tree_states(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, const int32_t *snp_idx, int64_t k,
                                uint8_t *node_state_out) {
-    return pars_call(c, [&](ParsBufs &b) { return states_run(c, parent, tip_seq, nodes, gap_mode, snp_idx, k, node_state_out, b); });
+    return ldw::scoped_call<ParsBufs>(c, [&](ParsBufs &b) { return states_run(c, parent, tip_seq, nodes, gap_mode, snp_idx, k, node_state_out, b); });
 }
 
 extern "C" int ldw_tree_cochanges(ldw_ctx *c, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, const int32_t *pair_a,
                                   const int32_t *pair_b, int64_t K, int32_t *changes_a_out, int32_t *changes_b_out, int32_t *co_out) {
-    return pars_call(c, [&](ParsBufs &b) { return cochanges_run(c, parent, tip_seq, nodes, gap_mode, pair_a, pair_b, K, changes_a_out, changes_b_out, co_out, b); });
+    return ldw::scoped_call<ParsBufs>(c, [&](ParsBufs &b) { return cochanges_run(c, parent, tip_seq, nodes, gap_mode, pair_a, pair_b, K, changes_a_out, changes_b_out, co_out, b); });
 }

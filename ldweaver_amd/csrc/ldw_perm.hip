@@ -24,6 +24,7 @@
 #include "ldw_internal.h"
 #include "ldw_lin_table.h"
 #include "ldw_prim.h"
+#include "ldw_seq_plan.h"   // LabelSet, perm_order0, budget_or_env: the host side of ldw_links_permuted
 
 using namespace ldw;
 
@@ -227,13 +228,6 @@ __global__ __launch_bounds__(256) void k_perm_init(int64_t K, int32_t *__restric
 
 namespace {
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-long long env_int(const char *name) {
-    const char *e = getenv(name);
-    return e ? atoll(e) : -1;
-}
-
 struct PermBufs {   // the working memory of one ldw_links_permuted call
     ldw::DevBuf order0, labels, v0, pair_a, pair_b, key, key2, val, val2, sort, obs, n_ge, mx, mi, fix;
 };
@@ -276,46 +270,29 @@ int permuted_run(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int64
     LDW_REQUIRE(B >= 1 && B <= PERM_MAX_REPLICATES, LDW_ERR_ARG, "%s: B = %d replicates (1..%d)", who, (int)B, PERM_MAX_REPLICATES);
     LDW_REQUIRE(C >= 1 && C <= PERM_MAX_CLUSTERS, LDW_ERR_ARG, "%s: C = %d clusters (1..%d)", who, (int)C, PERM_MAX_CLUSTERS);
     const int64_t N = c->N, L = c->L, Npad = c->Npad;
-    int64_t P = 0;
-    for (int64_t s = 0; s < N; ++s) {
-        LDW_REQUIRE(labels[s] >= -1 && labels[s] < C, LDW_ERR_ARG, "%s: labels[%lld] = %d (-1, or a cluster 0..%d)", who, (long long)s, (int)labels[s], (int)(C - 1));
-        P += labels[s] >= 0;
-    }
+    const ldw::LabelSet ls = ldw::LabelSet::scan(labels, N, C);
+    LDW_REQUIRE(ls.bad < 0, LDW_ERR_ARG, "%s: labels[%lld] = %d (-1, or a cluster 0..%d)", who, (long long)ls.bad, (int)labels[ls.bad], (int)(C - 1));
+    const int64_t P = ls.P;
     LDW_REQUIRE(P >= 1, LDW_ERR_ARG, "%s: every label is -1: no sequence to permute", who);
-    for (int64_t i = 0; i < K; ++i) {
-        LDW_REQUIRE(pair_a[i] >= 0 && pair_a[i] < L, LDW_ERR_ARG, "%s: pair_a[%lld] = %d (the alignment has SNPs 0..%lld)", who, (long long)i, (int)pair_a[i], (long long)(L - 1));
-        LDW_REQUIRE(pair_b[i] >= 0 && pair_b[i] < L, LDW_ERR_ARG, "%s: pair_b[%lld] = %d (the alignment has SNPs 0..%lld)", who, (long long)i, (int)pair_b[i], (long long)(L - 1));
-    }
+    int64_t bad_k = -1;
+    const int32_t *bad = ldw::first_bad_pair(pair_a, pair_b, K, L, &bad_k);
+    LDW_REQUIRE(!bad, LDW_ERR_ARG, "%s: %s[%lld] = %d (the alignment has SNPs 0..%lld)", who, bad == pair_a ? "pair_a" : "pair_b", (long long)bad_k, (int)bad[bad_k], (long long)(L - 1));
     const std::vector<int64_t> &V = c->wts.h_vfixed;
     const std::vector<double> &hdw = c->wts.h_hdw;
 
-    // ---- order0: the labelled sequences by (label, sequence), a counting sort; the weights in that order; neff as mi_all has it ----
-    std::vector<int64_t> first((size_t)C + 1, 0);
-    for (int64_t s = 0; s < N; ++s)
-        if (labels[s] >= 0) ++first[(size_t)labels[s] + 1];
-    for (int32_t k = 0; k < C; ++k) first[(size_t)k + 1] += first[(size_t)k];
-    std::vector<int32_t> order0((size_t)P);
-    std::vector<int64_t> v0((size_t)P);
-    long double sum = 0.0L;
-    for (int64_t s = 0; s < N; ++s)
-        if (labels[s] >= 0) {
-            const int64_t p = first[(size_t)labels[s]]++;
-            order0[(size_t)p] = (int32_t)s;
-            v0[(size_t)p] = V[(size_t)s];
-            sum += (long double)hdw[(size_t)s];
-        }
+    // ---- order0: the labelled sequences by (label, sequence) and the weights in that order (ldw_seq_plan.h); neff as mi_all has it ----
+    const ldw::PermOrder po = ldw::perm_order0(labels, V.data(), N, C);
+    std::vector<double> neff((size_t)C + 1);
+    ldw::LabelSet::neff(labels, hdw.data(), N, C, neff.data());
     PermLaunch pl;
     pl.P = P;
-    pl.neff = (double)sum;
+    pl.neff = neff[(size_t)C];
     pl.scale = std::ldexp(1.0, -c->wts.frac_bits);
 
     // ---- what goes to LDS.  LDW_PERM_LDS=m in the environment asks for mode m or, where that does not fit, the next that does: a test hook ----
     const int64_t lds_states = PERM_LDS_HEAD + Npad + ceil_div(P, 16) * 16;
     pl.mode = P * 8 + lds_states <= PERM_LDS_WITH_V ? 0 : lds_states <= PERM_LDS_MAX ? 1 : 2;
-    {
-        const long long m = env_int("LDW_PERM_LDS");
-        if (m >= 0 && m <= 2) pl.mode = std::max(pl.mode, (int)m);
-    }
+    if (const long long m = ldw::env_int("LDW_PERM_LDS"); m >= 0 && m <= 2) pl.mode = std::max(pl.mode, (int)m);   // (the hook's own rule: only the read is shared)
     pl.lds = pl.mode == 0 ? (size_t)(P * 8 + lds_states) : pl.mode == 1 ? (size_t)lds_states : (size_t)PERM_LDS_HEAD;
     if (pl.lds > 64 * 1024) {   // past what a kernel gets without asking
         const void *fn = pl.mode == 0 ? reinterpret_cast<const void *>(k_perm_pairs<0>) : reinterpret_cast<const void *>(k_perm_pairs<1>);
@@ -323,14 +300,14 @@ int permuted_run(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int64
     }
 
     // ---- replicates per batch: keys and values twice over and the sort's storage within the budget.  LDW_PERM_BATCH=k forces k: a test hook ----
-    const long long forced = env_int("LDW_PERM_BATCH");
-    int64_t R = forced >= 1 ? forced : std::max<int64_t>(1, PERM_BUDGET / (P * 40));
+    const bool forced = ldw::env_int("LDW_PERM_BATCH") >= 1;
+    int64_t R = ldw::budget_or_env(std::max<int64_t>(1, PERM_BUDGET / (P * 40)), "LDW_PERM_BATCH");
     R = std::min<int64_t>(std::min<int64_t>(R, PERM_MAX_BATCH), B);
     const unsigned end_bit = 56 + 8;
     size_t sort_bytes = 0;
     for (;;) {   // (the sort's storage is known only once asked for: halve R while it does not fit)
         LDW_HIP((ldw::prim_sort_pairs_bytes<uint64_t, int32_t>((size_t)(R * P), 0, end_bit, c->stream, &sort_bytes)));
-        if (R == 1 || forced >= 1 || (int64_t)sort_bytes + R * P * 24 <= PERM_BUDGET) break;
+        if (R == 1 || forced || (int64_t)sort_bytes + R * P * 24 <= PERM_BUDGET) break;
         R /= 2;
     }
     const int64_t R_tail = B % R;
@@ -339,22 +316,17 @@ int permuted_run(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int64
 
     // ---- pairs per chunk: a chunk's (pairs, R) values and, on request, tables within the budget.  LDW_PERM_CHUNK=k forces k: a test hook ----
     const int64_t cell_bytes = 8 + (fixed_out ? 200 : 0);
-    int64_t chunk = std::max<int64_t>(1, PERM_BUDGET / (R * cell_bytes));
-    {
-        const long long k = env_int("LDW_PERM_CHUNK");
-        if (k >= 1) chunk = k;
-    }
-    chunk = std::min<int64_t>(chunk, K);
+    const int64_t chunk = std::min<int64_t>(ldw::budget_or_env(std::max<int64_t>(1, PERM_BUDGET / (R * cell_bytes)), "LDW_PERM_CHUNK"), K);
 
     int rc = LDW_OK;
     const size_t items = (size_t)(R * P);
-    if ((rc = ldw::upload(c, b.order0, order0.data(), order0.size())) || (rc = ldw::upload(c, b.v0, v0.data(), v0.size())) ||
+    if ((rc = ldw::upload(c, b.order0, po.order0.data(), po.order0.size())) || (rc = ldw::upload(c, b.v0, po.v0.data(), po.v0.size())) ||
         (rc = ldw::upload(c, b.labels, labels, (size_t)N)) || (rc = ldw::upload(c, b.pair_a, pair_a, (size_t)K)) || (rc = ldw::upload(c, b.pair_b, pair_b, (size_t)K)) ||
         (rc = b.key.reserve(items * 8)) || (rc = b.key2.reserve(items * 8)) || (rc = b.val.reserve(items * 4)) || (rc = b.val2.reserve(items * 4)) ||
         (rc = b.sort.reserve(std::max(sort_bytes, sort_bytes_tail) + 256)) || (rc = b.obs.reserve((size_t)K * 8)) || (rc = b.n_ge.reserve((size_t)K * 4)) ||
         (rc = b.mx.reserve((size_t)K * 8)) || (rc = b.mi.reserve((size_t)(chunk * R) * 8)) || (fixed_out && (rc = b.fix.reserve((size_t)(chunk * R) * 200))))
         return rc;
-    ldw::Event ev[4];
+    ldw::Event ev[4];   // (no ldw::Laps: every step is timed as soon as its synchronisation returns, and the (batch, chunk) steps have no useful bound)
     for (ldw::Event &e : ev) LDW_HIP(e.ensure());
     double ms[3] = {0, 0, 0};   // the pair kernel (with the counts), keys and sorts, copies out
     auto lap = [&](int slot, int from) -> int {   // the time between ev[from] and ev[from + 1], once the stream has passed both
@@ -427,12 +399,7 @@ int permuted_run(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int64
 extern "C" int ldw_links_permuted(ldw_ctx *c, const int32_t *pair_a, const int32_t *pair_b, int64_t K, const int32_t *labels, int32_t C, int32_t B, uint64_t seed,
                                   double *mi_obs_out, int32_t *n_ge_out, double *null_max_out, double *null_out, int64_t *fixed_out, int32_t *order_out, int64_t *p_out,
                                   int *frac_bits_out) {
-    if (int rc = check_gpu(c)) return rc;   // as ldw_links_stratified: this context's stream alone touched the blocks
-    PermBufs bufs;
-    const int rc = permuted_run(c, pair_a, pair_b, K, labels, C, B, seed, mi_obs_out, n_ge_out, null_max_out, null_out, fixed_out, order_out, p_out, frac_bits_out, bufs);
-    if (hipStreamSynchronize(c->stream) == hipSuccess) {
-        ldw::DrainedScope quiet;
-        bufs = PermBufs();
-    }
-    return rc;
+    return ldw::scoped_call<PermBufs>(c, [&](PermBufs &b) {
+        return permuted_run(c, pair_a, pair_b, K, labels, C, B, seed, mi_obs_out, n_ge_out, null_max_out, null_out, fixed_out, order_out, p_out, frac_bits_out, b);
+    });
 }

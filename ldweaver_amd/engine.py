@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+from ctypes import byref, c_int, c_int64   # (by name: methods whose argument C is a number of clusters cannot reach the alias)
 import errno
 import os
 
@@ -683,6 +684,25 @@ class Engine:
             raise ValueError(f"parent has {len(p)} nodes but tip_seq {len(t)}")
         return p, t, (L.ptr(p) if len(p) else None), (L.ptr(t) if len(t) else None)
 
+    @staticmethod
+    def _pairs(pair_a, pair_b):
+        """The two SNP lists of K pairs as the C ABI takes them: (a, b, their pointers (None for no pairs), K)."""
+        a, b = L.as_c(pair_a, np.int32).ravel(), L.as_c(pair_b, np.int32).ravel()
+        if len(a) != len(b):
+            raise ValueError(f"{len(a)} first SNPs but {len(b)} second SNPs")
+        K = len(a)
+        return a, b, (L.ptr(a) if K else None), (L.ptr(b) if K else None), K
+
+    def _pairs_labels(self, pair_a, pair_b, labels, n_clusters):
+        """``_pairs`` and the cluster labels of the N sequences: (..., K, lab, its pointer, C), C defaulting to max(labels) + 1."""
+        pairs = self._pairs(pair_a, pair_b)
+        lab = L.as_c(labels, np.int32).ravel()
+        if len(lab) != self.N:
+            raise ValueError(f"labels has {len(lab)} entries, the alignment {self.N} sequences")
+        if n_clusters is None:
+            n_clusters = int(lab.max()) + 1 if len(lab) else 0
+        return pairs + (lab, (L.ptr(lab) if len(lab) else None), int(n_clusters))
+
     def tree_parsimony(self, parent, tip_seq, gap_mode: int = 0):
         """Maximum parsimony of every SNP of the resident alignment on the tree ``parent`` (int32 [nodes], -1 at node 0, ``parent[v] < v``) whose
         childless nodes stand for the sequences ``tip_seq`` (int32 [nodes], -1 at the other nodes): ldw_tree_parsimony.  ``gap_mode`` 0: a tip in state
@@ -705,13 +725,9 @@ class Engine:
         """For every pair of SNPs (``pair_a[i]``, ``pair_b[i]``): (changes_a, changes_b, co_changes), int32 each — the branches on which each SNP
         changes under that reconstruction, and those on which both do (ldw_tree_cochanges)."""
         p, t, pp, tp = self._pars_tree(parent, tip_seq)
-        a, b = L.as_c(pair_a, np.int32).ravel(), L.as_c(pair_b, np.int32).ravel()
-        if len(a) != len(b):
-            raise ValueError(f"{len(a)} first SNPs but {len(b)} second SNPs")
-        K = len(a)
+        a, b, pa, pb, K = self._pairs(pair_a, pair_b)
         ca, cb, co = (np.empty(max(K, 1), dtype=np.int32) for _ in range(3))
-        L.check(L.lib().ldw_tree_cochanges(self._ctx, pp, tp, len(p), int(gap_mode), L.ptr(a) if K else None, L.ptr(b) if K else None, K, L.ptr(ca), L.ptr(cb),
-                                           L.ptr(co)))
+        L.check(L.lib().ldw_tree_cochanges(self._ctx, pp, tp, len(p), int(gap_mode), pa, pb, K, L.ptr(ca), L.ptr(cb), L.ptr(co)))
         return ca[:K], cb[:K], co[:K]
 
     # -- the lineage check (DESIGN.md 29) ---------------------------------------
@@ -733,24 +749,14 @@ class Engine:
         pairs (``pair_a[i]``, ``pair_b[i]``) over the cluster's members alone, under the resident weights (ldw_links_stratified).  Returns a dict:
         ``mi`` float64 (K, C), ``mi_all`` float64 [K] (over all labelled sequences), ``poly`` uint8 (K, C) (bit 0: the first SNP is polymorphic in the
         cluster, bit 1: the second), ``neff`` float64 [C], ``frac_bits``; with ``want_tables`` also ``counts`` and ``fixed``, int64 (K, C, 5, 5)."""
-        import ctypes as ct         # (the argument C, the number of clusters as the C ABI names it, hides the module's alias here)
-        a, b = L.as_c(pair_a, np.int32).ravel(), L.as_c(pair_b, np.int32).ravel()
-        if len(a) != len(b):
-            raise ValueError(f"{len(a)} first SNPs but {len(b)} second SNPs")
-        lab = L.as_c(labels, np.int32).ravel()
-        if len(lab) != self.N:
-            raise ValueError(f"labels has {len(lab)} entries, the alignment {self.N} sequences")
-        if C is None:
-            C = int(lab.max()) + 1 if len(lab) else 0
-        K, C = len(a), int(C)
+        a, b, pa, pb, K, lab, plab, C = self._pairs_labels(pair_a, pair_b, labels, C)
         shape = (max(K, 1), max(min(C, 65536), 1))
         mi, mi_all, poly = np.empty(shape), np.empty(shape[0]), np.empty(shape, dtype=np.uint8)
         neff = np.empty(shape[1])
         cnt = np.empty(shape + (5, 5), dtype=np.int64) if want_tables else None
         fix = np.empty(shape + (5, 5), dtype=np.int64) if want_tables else None
-        fb = ct.c_int(0)
-        L.check(L.lib().ldw_links_stratified(self._ctx, L.ptr(a) if K else None, L.ptr(b) if K else None, K, L.ptr(lab) if len(lab) else None, C, L.ptr(mi),
-                                             L.ptr(mi_all), L.ptr(poly), L.ptr(neff), L.ptr(cnt), L.ptr(fix), ct.byref(fb)))
+        fb = c_int(0)
+        L.check(L.lib().ldw_links_stratified(self._ctx, pa, pb, K, plab, C, L.ptr(mi), L.ptr(mi_all), L.ptr(poly), L.ptr(neff), L.ptr(cnt), L.ptr(fix), byref(fb)))
         out = dict(mi=mi, mi_all=mi_all, poly=poly, neff=neff, frac_bits=fb.value)
         if want_tables:
             out.update(counts=cnt, fixed=fix)
@@ -764,16 +770,8 @@ class Engine:
         ``links_stratified(...)["mi_all"]``), ``n_ge`` int32 [K] (replicates whose MI reaches the observed one), ``null_max`` float64 [K], ``P`` (the
         labelled sequences), ``n_perm``, ``frac_bits``; with ``want_null`` also ``null`` float64 (K, n_perm), with ``want_tables`` ``fixed`` int64
         (K, n_perm, 5, 5), with ``want_orders`` ``orders`` int32 (n_perm, P).  A replicate is a function of (labels, seed, its number) alone."""
-        import ctypes as ct         # (the argument C, the number of clusters as the C ABI names it, hides the module's alias here)
-        a, b = L.as_c(pair_a, np.int32).ravel(), L.as_c(pair_b, np.int32).ravel()
-        if len(a) != len(b):
-            raise ValueError(f"{len(a)} first SNPs but {len(b)} second SNPs")
-        lab = L.as_c(labels, np.int32).ravel()
-        if len(lab) != self.N:
-            raise ValueError(f"labels has {len(lab)} entries, the alignment {self.N} sequences")
-        if C is None:
-            C = int(lab.max()) + 1 if len(lab) else 0
-        K, C, B = len(a), int(C), int(n_perm)
+        a, b, pa, pb, K, lab, plab, C = self._pairs_labels(pair_a, pair_b, labels, C)
+        B = int(n_perm)
         seed = int(seed)
         if not 0 <= seed < 1 << 64:
             raise ValueError(f"seed {seed} is not an unsigned 64-bit integer")
@@ -784,9 +782,9 @@ class Engine:
         null = np.empty((rows, reps)) if want_null else None
         fix = np.empty((rows, reps, 5, 5), dtype=np.int64) if want_tables else None
         orders = np.empty((reps, n_lab), dtype=np.int32) if want_orders else None
-        p_out, fb = ct.c_int64(0), ct.c_int(0)
-        L.check(L.lib().ldw_links_permuted(self._ctx, L.ptr(a) if K else None, L.ptr(b) if K else None, K, L.ptr(lab) if len(lab) else None, C, B, seed,
-                                           L.ptr(mi_obs), L.ptr(n_ge), L.ptr(null_max), L.ptr(null), L.ptr(fix), L.ptr(orders), ct.byref(p_out), ct.byref(fb)))
+        p_out, fb = c_int64(0), c_int(0)
+        L.check(L.lib().ldw_links_permuted(self._ctx, pa, pb, K, plab, C, B, seed, L.ptr(mi_obs), L.ptr(n_ge), L.ptr(null_max), L.ptr(null), L.ptr(fix),
+                                           L.ptr(orders), byref(p_out), byref(fb)))
         out = dict(mi_obs=mi_obs, n_ge=n_ge, null_max=null_max, P=int(p_out.value), n_perm=B, frac_bits=fb.value)
         if want_null:
             out["null"] = null
