@@ -883,6 +883,26 @@ int ldw_links_permuted(ldw_ctx *ctx, const int32_t *pair_a, const int32_t *pair_
 int ldw_mi_profile(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int quirk_mode, const double *cuts, int32_t n_cut, int32_t mi_shift,
                    uint64_t *hist_out, double *max_out, int64_t *npairs_out);
 
+/* ---- (21) per-SNP MI summary over EVERY SNP pair of a block list: the background of each SNP, in two distance classes ---------------------
+ * ldw_mi_snp_summary requires and refuses what ldw_mi_profile does (20): the alignment, the weights and the SNP meta data; blocks diagonal or disjoint.
+ *   the pairs    exactly those of ldw_mi_profile over the same blocks, with the same values under the same quirk_mode.
+ *   the class    of a pair: c = 0 (short range) if len = 0.5 g - |(POS[to] - POS[from]) mod g - 0.5 g| <= sr_dist, else c = 1 (long range): the pass's own
+ *                split.  sr_dist is non-negative and not NaN (LDW_ERR_ARG otherwise); +inf makes every pair short range.
+ *   contribution every pair contributes to BOTH of its SNPs, the from-SNP and the to-SNP.  Per SNP i and class c (outputs [2][L], class-major, HOST):
+ *     n_out      the number of partners.
+ *     sumq_out   the sum of q(mi) = llrint(mi * 2^40) over the partners: the product is an exact scaling, the rounding is to nearest, ties to even.  A value
+ *                that is not finite or has |mi| >= 2^22 adds 0 and is counted (ldw_snp_summary_report).  |q| < 2^62; with MI <= ln 5 (|q| < 2^41) and at
+ *                most 2^21 partners the sum stays below 2^62.  The mean MI of SNP i with its partners of class c is sumq / n / 2^40.
+ *     max_out    (may be NULL) the largest value in the order of the IEEE bits (-0 below +0), the device's own bits; NaN where n == 0.
+ *     nge_out    (may be NULL) the number of partners with mi >= thr[c], an fp64 comparison: +inf counts no finite value, a NaN value never counts.
+ *   npairs_out[2] the pairs of each class: sum_i n[c][i] == 2 npairs[c]; npairs[0] / npairs[1] equal the sums of n_sr / n_lr_total of ldw_block_stats after
+ *                ldw_mi_all_pairs with the same sr_dist over the same blocks.
+ * Integer adds and a maximum: nothing depends on the order of evaluation.  The link tables and the ldw_block_stats of an earlier pass stay as they were.
+ * ldw_ctx_last_timing afterwards: [0] the blocks' GEMM + epilogue, [1] the summary kernels, [2] 0, [3] their sum.  The call runs on the context's stream
+ * and returns when the outputs are written. */
+int ldw_mi_snp_summary(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int quirk_mode, double sr_dist, const double *thr, int64_t *n_out,
+                       int64_t *sumq_out, double *max_out, int64_t *nge_out, int64_t *npairs_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

@@ -282,6 +282,22 @@ int ldw_debug_profile_hist(ldw_ctx *ctx, const double *mi, int64_t nf, int64_t n
                            int64_t *stats_out);
 int ldw_decay_report(ldw_ctx *ctx, int64_t out[4]);
 
+/* ---- per-SNP MI summary (ldweaver_amd.h 21) ------------------------------------------------------------------------------------------------------------------
+ * ldw_debug_snp_summary: the kernel of ldw_mi_snp_summary (k_snp_summary) as a function, on caller-made values; needs no alignment.  mi, nf, nt, pos_f, pos_t,
+ *   g and diag as ldw_debug_profile_hist (mi may hold any double, NaN included); sr_dist and thr[2] as ldw_mi_snp_summary.  The two sides come out apart:
+ *   n_f / sumq_f / max_f / nge_f [2][nf] what the pairs add to their from-SNPs (the rows), n_t / sumq_t / max_t / nge_t [2][nt] what they add to their to-SNPs
+ *   (the columns); max_* and nge_* may be NULL.  npairs_out[2] the pairs of each class.
+ *   The kernel works in patches of 64 rows x 256 columns; a patch bounds its distances from the extreme positions of its rows and columns.  route: 0 = a patch
+ *   the bound puts in one class carries one set of accumulators (route 1), any other both (route 2); 1 = route 1, LDW_ERR_ARG (outputs undefined) when the
+ *   bound does not put a patch in one class; 2 = route 2 for every patch.  All give the same integers.  stats_out (may be NULL, 4 values): patches
+ *   visited (every patch but a diagonal block's patches that lie wholly on or above the diagonal; a visited patch may hold no pair), patches on route 2, pairs whose own class is not their route-1 patch's (added one by one), values q refused (once per pair).
+ *   LDW_ERR_ARG: nf, nt outside 1..1 000 000, diag with nf != nt, g not positive, route outside 0..2, sr_dist negative or NaN.
+ * ldw_snp_summary_report: out[0..3] the same four counts summed over the last ldw_mi_snp_summary of the context, out[4] its blocks. */
+int ldw_debug_snp_summary(ldw_ctx *ctx, const double *mi, int64_t nf, int64_t nt, const int32_t *pos_f, const int32_t *pos_t, double g, int diag, double sr_dist,
+                          const double *thr, int route, int64_t *n_f, int64_t *sumq_f, double *max_f, int64_t *nge_f, int64_t *n_t, int64_t *sumq_t, double *max_t,
+                          int64_t *nge_t, int64_t *npairs_out, int64_t *stats_out);
+int ldw_snp_summary_report(ldw_ctx *ctx, int64_t out[5]);
+
 /* ---- the plots (ldweaver_amd.h 12) ------------------------------------------------------------------------------------------------ */
 /* The rasters of ldw_plot_scatter without the frame, for panels of W x H pixels each (any size >= 1): rgb_out[n_panels][H][W][3] (host).  Grid
  * lines lie at the ticks of ldw_plot_ticks for the data range and W / H.  stats_out (may be NULL, 8 doubles): x min, x max, y min, y max of

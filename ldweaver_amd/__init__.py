@@ -19,6 +19,7 @@ _EXPORTS = {
     "snp_parsimony": "parsimony", "link_cochanges": "parsimony", "ancestral_states": "parsimony", "tip_sequences": "parsimony",
     "cochange_pvalue": "parsimony",
     "ld_decay": "decay", "LDDecay": "decay", "default_cuts": "decay",
+    "snp_background": "background", "SnpBackground": "background", "link_apc": "background",
     "sequence_clusters": "lineage", "link_lineage_mi": "lineage", "link_permutation_test": "lineage",
 }
 __all__ = sorted(_EXPORTS)

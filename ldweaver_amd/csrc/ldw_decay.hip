@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "ldw_internal.h"
@@ -267,29 +268,24 @@ static int decay_end(ldw_ctx *c, const DecayRun &R, uint64_t *hist_out, double *
 
 static int64_t decay_pairs(int64_t nf, int64_t nt, bool diag) { return diag ? nf * (nf - 1) / 2 : nf * nt - std::min(nf, nt); }
 
-}  // namespace ldw
-
-extern "C" {
-
-int ldw_mi_profile(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, int quirk_mode, const double *cuts, int32_t n_cut, int32_t mi_shift, uint64_t *hist_out,
-                   double *max_out, int64_t *npairs_out) {
+// ---- the block walk of ldw_mi_profile and ldw_mi_snp_summary (ldw_internal.h) ----
+int pair_blocks_check(ldw_ctx *c, const char *who, const int32_t *blocks, int64_t nblocks, int quirk_mode, bool outputs_ok, const std::function<int()> &own_check) {
     if (int rc = check_gpu(c)) return rc;
-    LDW_REQUIRE(blocks && nblocks > 0 && hist_out && npairs_out, LDW_ERR_ARG, "ldw_mi_profile: bad argument");
-    LDW_REQUIRE(quirk_mode == LDW_QUIRK_REFERENCE || quirk_mode == LDW_QUIRK_INTENDED, LDW_ERR_ARG, "bad quirk mode");
-    LDW_REQUIRE(have_alignment(c) && c->wts.have_weights && c->meta.have_meta, LDW_ERR_STATE,
-                "ldw_mi_profile needs the alignment, the weights and the SNP meta data to be set first");
-    if (int rc = decay_check(cuts, n_cut, mi_shift, "ldw_mi_profile")) return rc;
+    LDW_REQUIRE(blocks && nblocks > 0 && outputs_ok, LDW_ERR_ARG, "%s: bad argument", who);
+    LDW_REQUIRE(quirk_mode == LDW_QUIRK_REFERENCE || quirk_mode == LDW_QUIRK_INTENDED, LDW_ERR_ARG, "%s: bad quirk mode", who);
+    LDW_REQUIRE(have_alignment(c) && c->wts.have_weights && c->meta.have_meta, LDW_ERR_STATE, "%s needs the alignment, the weights and the SNP meta data to be set first", who);
+    if (int rc = own_check()) return rc;   // (the caller's own arguments are judged before the blocks, as ldw_mi_profile always did)
     for (int64_t b = 0; b < nblocks; ++b) {
         const int32_t fs = blocks[b * 4 + 0], fe = blocks[b * 4 + 1], ts = blocks[b * 4 + 2], te = blocks[b * 4 + 3];
-        LDW_REQUIRE(fs >= 1 && fs <= fe && fe <= c->L && ts >= 1 && ts <= te && te <= c->L, LDW_ERR_ARG, "ldw_mi_profile: block %lld (%d..%d x %d..%d) outside 1..%lld",
-                    (long long)b, fs, fe, ts, te, (long long)c->L);
-        LDW_REQUIRE((fs == ts && fe == te) || fe < ts || te < fs, LDW_ERR_ARG, "ldw_mi_profile: the ranges of block %lld (%d..%d x %d..%d) overlap without being equal",
-                    (long long)b, fs, fe, ts, te);
+        LDW_REQUIRE(fs >= 1 && fs <= fe && fe <= c->L && ts >= 1 && ts <= te && te <= c->L, LDW_ERR_ARG, "%s: block %lld (%d..%d x %d..%d) outside 1..%lld", who, (long long)b,
+                    fs, fe, ts, te, (long long)c->L);
+        LDW_REQUIRE((fs == ts && fe == te) || fe < ts || te < fs, LDW_ERR_ARG, "%s: the ranges of block %lld (%d..%d x %d..%d) overlap without being equal", who, (long long)b,
+                    fs, fe, ts, te);
     }
-    DecayRun R;
-    if (int rc = decay_begin(c, R, cuts, n_cut, mi_shift)) return rc;
-    double ms_mi = 0, ms_hist = 0;
-    int64_t npairs = 0;
+    return LDW_OK;
+}
+
+int pair_blocks_walk(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, int quirk_mode, PairBlockWalk &W, const std::function<int(int64_t, int64_t, bool)> &consumer) {
     std::vector<int32_t> fi, ti;
     for (int64_t b = 0; b < nblocks; ++b) {
         const int32_t fs = blocks[b * 4 + 0], fe = blocks[b * 4 + 1], ts = blocks[b * 4 + 2], te = blocks[b * 4 + 3];
@@ -300,23 +296,41 @@ int ldw_mi_profile(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, int quirk
         for (int64_t k = 0; k < nt; ++k) ti[(size_t)k] = ts - 1 + (int32_t)k;
         if (int rc = block_mi_dense(c, fi.data(), nf, ti.data(), nt, quirk_mode)) return rc;   // (leaves the block's index lists in ctx->idx_f / idx_t)
         LDW_HIP(hipEventRecord(c->ev[3], c->stream));
-        if (int rc = decay_launch(c, R, c->MIblk.as<double>(), nf, nt, c->meta.POS.as<int32_t>(), c->idx_f.as<int32_t>(), c->meta.POS.as<int32_t>(), c->idx_t.as<int32_t>(),
-                                  c->meta.g, diag ? 1 : 0, 0))
-            return rc;
+        if (int rc = consumer(nf, nt, diag)) return rc;
         LDW_HIP(hipEventRecord(c->ev[4], c->stream));
         LDW_HIP(hipStreamSynchronize(c->stream));   // (the next block's staging overwrites the lists and the events)
         float t01 = 0, t12 = 0, t34 = 0;
         LDW_HIP(hipEventElapsedTime(&t01, c->ev[0], c->ev[1]));
         LDW_HIP(hipEventElapsedTime(&t12, c->ev[1], c->ev[2]));
         LDW_HIP(hipEventElapsedTime(&t34, c->ev[3], c->ev[4]));
-        ms_mi += (double)t01 + t12, ms_hist += t34;
-        npairs += decay_pairs(nf, nt, diag);
+        W.ms_mi += (double)t01 + t12, W.ms_consumer += t34;
+        W.npairs += decay_pairs(nf, nt, diag);
     }
+    return LDW_OK;
+}
+
+}  // namespace ldw
+
+extern "C" {
+
+int ldw_mi_profile(ldw_ctx *c, const int32_t *blocks, int64_t nblocks, int quirk_mode, const double *cuts, int32_t n_cut, int32_t mi_shift, uint64_t *hist_out,
+                   double *max_out, int64_t *npairs_out) {
+    if (int rc = pair_blocks_check(c, "ldw_mi_profile", blocks, nblocks, quirk_mode, hist_out && npairs_out,
+                                   [&] { return decay_check(cuts, n_cut, mi_shift, "ldw_mi_profile"); }))
+        return rc;
+    DecayRun R;
+    if (int rc = decay_begin(c, R, cuts, n_cut, mi_shift)) return rc;
+    PairBlockWalk W;
+    if (int rc = pair_blocks_walk(c, blocks, nblocks, quirk_mode, W, [&](int64_t nf, int64_t nt, bool diag) {
+            return decay_launch(c, R, c->MIblk.as<double>(), nf, nt, c->meta.POS.as<int32_t>(), c->idx_f.as<int32_t>(), c->meta.POS.as<int32_t>(), c->idx_t.as<int32_t>(),
+                                c->meta.g, diag ? 1 : 0, 0);
+        }))
+        return rc;
     unsigned long long st[4];
     if (int rc = decay_end(c, R, hist_out, max_out, st)) return rc;
-    *npairs_out = npairs;
+    *npairs_out = W.npairs;
     c->decay_stat[0] = (int64_t)st[0], c->decay_stat[1] = (int64_t)st[1], c->decay_stat[2] = (int64_t)st[2], c->decay_stat[3] = nblocks;
-    c->last_ms[0] = ms_mi, c->last_ms[1] = ms_hist, c->last_ms[2] = 0, c->last_ms[3] = ms_mi + ms_hist;
+    c->last_ms[0] = W.ms_mi, c->last_ms[1] = W.ms_consumer, c->last_ms[2] = 0, c->last_ms[3] = W.ms_mi + W.ms_consumer;
     return LDW_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <string>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -394,6 +395,7 @@ struct ldw_ctx {
     void *tsv_async = nullptr;   // r04: the asynchronous link-table writer, if one is running (ldw_tsv.cpp: TsvAsync)
     ldw::PinnedBuf pin_fetch;    // r04: pinned host arena the tsv writer fetches a link table into (see ldw_write_links_tsv)
     int64_t decay_stat[4] = {0, 0, 0, 0};            // ldw_decay_report: patches, route-B patches, pairs outside their patch's bound and blocks of the last ldw_mi_profile
+    int64_t snpsum_stat[5] = {0, 0, 0, 0, 0};        // ldw_snp_summary_report: patches, general-route patches, pairs off their patch's class, values q refused and blocks of the last ldw_mi_snp_summary
     double ham_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ldw_hamming_stats: columns, padded K, stage times and algorithmic bytes of the last ldw_hamming_weights
     ldw::DevBuf plot_work, plot_cols;   // the plots (ldw_plot.hip): key image + rasters + partials; device copy of a chunk of host columns
 
@@ -441,6 +443,15 @@ int ensure_hi_marginals(ldw_ctx *ctx);   // slot_pfix_hi on demand (mixed-precis
 // ldw_mi.hip: run_block_mi without link tables, as ldw_mi_block runs it: the dense MI of one block into ctx->MIblk [nf * nt] column-major; the block's index
 // lists stay in ctx->idx_f / idx_t, its stage events are ctx->ev[0..2] (ldw_decay.hip)
 int block_mi_dense(ldw_ctx *ctx, const int32_t *from_idx, int64_t nf, const int32_t *to_idx, int64_t nt, int quirk);
+// ldw_decay.hip: what ldw_mi_profile and ldw_mi_snp_summary share.  pair_blocks_check: the requirements of both entries (a GPU, the arguments, the quirk mode, the
+// resident alignment, weights and meta data, then own_check() for the caller's own arguments, then every block diagonal or disjoint), refused under the caller's name.  pair_blocks_walk: per block the dense MI
+// (block_mi_dense), consumer(nf, nt, diag) launched behind it on the context's stream, the synchronisation, and the event times and pair count added to W.
+struct PairBlockWalk {
+    double ms_mi = 0, ms_consumer = 0;   // the blocks' GEMM + epilogue; the consumer's kernels
+    int64_t npairs = 0;
+};
+int pair_blocks_check(ldw_ctx *ctx, const char *who, const int32_t *blocks, int64_t nblocks, int quirk_mode, bool outputs_ok, const std::function<int()> &own_check);
+int pair_blocks_walk(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int quirk_mode, PairBlockWalk &W, const std::function<int(int64_t, int64_t, bool)> &consumer);
 void lr_stream_push(ldw_ctx *ctx, hipStream_t s, const int64_t *d_lr_count, int64_t blocks_done);   // ldw_tsv.cpp: no-ops without an open stream
 void lr_stream_drain(ldw_ctx *ctx);
 int join_prepare(ldw_ctx *ctx);      // waits for the side thread of ldw_ctx_reserve (no-op without one); its error, if any, becomes the caller's

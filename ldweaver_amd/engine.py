@@ -375,6 +375,48 @@ class Engine:
                                                int(mi_shift), int(route), L.ptr(hist), L.ptr(mx), C.byref(n), L.ptr(st)))
         return dict(hist=hist, max=mx, n_pairs=int(n.value), stats=st)
 
+    # -- per-SNP MI summary -----------------------------------------
+    def mi_snp_summary(self, blocks, sr_dist, thr=(np.inf, np.inf), quirk=L.QUIRK_REFERENCE):
+        """Per SNP and distance class (0: len <= sr_dist, 1: beyond) over EVERY SNP pair of ``blocks`` (ldw_mi_snp_summary), each pair adding to both of its
+        SNPs: ``n`` the partners, ``sumq`` the sum of llrint(mi 2^40), ``max`` the largest MI (NaN where n == 0), ``nge`` the partners with mi >= thr[class] —
+        each (2, L) — and ``npairs`` (2,) the pairs of each class.  The link tables stay as they are."""
+        bl = L.as_c(blocks, np.int32).reshape(-1, 4)
+        th = L.as_c(thr, np.float64).reshape(2)
+        n, sumq, nge = (np.zeros((2, self.L), dtype=np.int64) for _ in range(3))
+        mx = np.full((2, self.L), np.nan)
+        npairs = np.zeros(2, dtype=np.int64)
+        L.check(L.lib().ldw_mi_snp_summary(self._ctx, L.ptr(bl), len(bl), int(quirk), float(sr_dist), L.ptr(th), L.ptr(n), L.ptr(sumq), L.ptr(mx), L.ptr(nge),
+                                           L.ptr(npairs)))
+        return dict(n=n, sumq=sumq, max=mx, nge=nge, npairs=npairs)
+
+    def snp_summary_report(self):
+        """Of the last mi_snp_summary (ldw_snp_summary_report): patches the summary kernel visited, those on the general route, pairs off their patch's class,
+        values the fixed point refused, blocks."""
+        v = np.zeros(5, dtype=np.int64)
+        L.check(L.lib().ldw_snp_summary_report(self._ctx, L.ptr(v)))
+        return dict(patches=int(v[0]), general=int(v[1]), off_class=int(v[2]), refused=int(v[3]), blocks=int(v[4]))
+
+    def debug_snp_summary(self, mi, pos_f, pos_t, g, diag, sr_dist, thr=(np.inf, np.inf), route: int = 0):
+        """The kernel of mi_snp_summary on caller-made values (ldw_debug_snp_summary): ``mi`` (nf, nt) (stored column-major for the call), the positions of
+        the two sides, the genome length, ``diag`` (pairs a > b of a square block) or not (pairs a != b).  route 0: every patch chooses, 1: single class
+        (LdwError LDW_ERR_ARG where the bound does not say), 2: both classes carried.  Returns ``rows`` and ``cols``, each a dict of n, sumq, max, nge with
+        shapes (2, nf) and (2, nt) — what the pairs add to their from-SNPs and to their to-SNPs —, ``npairs`` (2,) and ``stats`` (patches visited, general-route
+        patches, pairs off their patch's class, values refused)."""
+        m = np.asarray(mi, dtype=np.float64)
+        assert m.ndim == 2, m.shape
+        nf, nt = m.shape
+        mf = np.asfortranarray(m)
+        pf, pt = L.as_c(pos_f, np.int32).ravel(), L.as_c(pos_t, np.int32).ravel()
+        assert len(pf) == nf and len(pt) == nt, (len(pf), len(pt), m.shape)
+        th = L.as_c(thr, np.float64).reshape(2)
+        side = lambda k: dict(n=np.zeros((2, k), dtype=np.int64), sumq=np.zeros((2, k), dtype=np.int64), max=np.full((2, k), np.nan),
+                              nge=np.zeros((2, k), dtype=np.int64))
+        rows, cols = side(nf), side(nt)
+        npairs, st = np.zeros(2, dtype=np.int64), np.zeros(4, dtype=np.int64)
+        L.check(L.lib().ldw_debug_snp_summary(self._ctx, L.ptr(mf), nf, nt, L.ptr(pf), L.ptr(pt), float(g), int(bool(diag)), float(sr_dist), L.ptr(th), int(route),
+                                              *[L.ptr(s[k]) for s in (rows, cols) for k in ("n", "sumq", "max", "nge")], L.ptr(npairs), L.ptr(st)))
+        return dict(rows=rows, cols=cols, npairs=npairs, stats=st)
+
     def debug_screen_bound(self, kind: int, na: int, nb: int, g, pa, pb, pX, pY, rr, params, masks=None):
         """The engine's screen / evaluation device functions on caller-made joint tables (ldw_debug_screen_bound): kind 0 / 1 the approximate path's upper
         bounds (straight-line / predicated), 2 / 3 the fp32 MI of the exact-limb screens, 4 the fp64 value the engine emits."""

@@ -232,6 +232,21 @@ def ld_decay_plot(decay, path, q: float = 0.95, *, engine=None) -> str:
     return str(path)
 
 
+BACKGROUND_LABELS = ("Genomic position", "Mean long-range MI")
+
+
+def snp_background_plot(background, path, *, engine=None) -> str:
+    """Of ``background`` (``background.SnpBackground``): the mean long-range MI of every SNP that has a long-range partner against its position as black
+    points, and the overall long-range mean as a red line across, in the layout of the fit figures (PLOT_FIT).  Returns the path."""
+    y = background.mean("lr")
+    keep = np.isfinite(y)
+    x, y = np.asarray(background.POS, dtype=np.float64)[keep], y[keep]
+    line = (np.array([x.min(), x.max()]), np.full(2, background.overall_mean("lr"))) if len(x) else None
+    _with_engine(engine, lambda eng: render_xy(eng, x, y, None, line, opts=xy_opts(L.PLOT_FIT), title="MI background", xlab=BACKGROUND_LABELS[0],
+                                               ylab=BACKGROUND_LABELS[1], path=path))
+    return str(path)
+
+
 def cds_cluster_plot(cds_var, path, *, engine=None) -> str:
     """``CDS_clustering.png`` (R/estimateCDSDiversity.R:212-220): ``var_estimate`` against ``cds_start``, coloured by the cluster
     ``km_clst_ord`` in ggplot's default hues, in row order.  Returns the path."""
