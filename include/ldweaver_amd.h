@@ -903,6 +903,37 @@ int ldw_mi_profile(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int qui
 int ldw_mi_snp_summary(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int quirk_mode, double sr_dist, const double *thr, int64_t *n_out,
                        int64_t *sumq_out, double *max_out, int64_t *nge_out, int64_t *npairs_out);
 
+/* ---- (22) selection by a corrected score over EVERY SNP pair of a block list, with each SNP's best partner ----------------------------------
+ * ldw_mi_score_scan and ldw_mi_score_links require and refuse what ldw_mi_profile does (20): the alignment, the weights and the SNP meta data; blocks
+ * diagonal or disjoint.  Blocks, pair set and values are exactly those of (20) and (21) under the same quirk_mode.
+ *   the score    of the pair of the global SNPs (A, B): s = mi - w[A] * w[B], two IEEE fp64 operations, the product and then the difference, never one
+ *                fused multiply-add (csrc/ldw_score.h states it once for the device and the host).  The product is commutative: s does not depend on which
+ *                SNP is the from-SNP.  w[L] (HOST) must be finite: LDW_ERR_ARG otherwise, the message naming the index.  The average product correction is
+ *                w = mean / sqrt(overall mean); the entries do not know that: any rank-one correction is a w.  A pair whose MI is NaN has a NaN score.
+ *   the class mask cls_mask = 1: the pairs with len <= sr_dist (short range), 2: the pairs beyond (long range), 3: both; len, sr_dist and the class of a pair
+ *                as in (21).  LDW_ERR_ARG for any other mask, for a negative or NaN sr_dist.  Pairs outside the mask take no part in anything below.
+ * ldw_mi_score_scan — outputs (HOST):
+ *   hist_out[4096]  hist_out[B] counts the pairs with mi_bucket(s) == B, the long-range selection's rule as (20) states it (0 for negatives, +-0 and values
+ *                below 2^-20).  A NaN score is in no bucket.
+ *   best_out[L]  the largest score of SNP i over its partners in the order of the IEEE bits (-0 below +0), the device's own bits; NaN where there is none.
+ *                Every pair contributes to both of its SNPs; a NaN score is never a best.
+ *   *npairs_out  the pairs inside the mask: the sum of hist_out plus the NaN scores of ldw_score_select_report.
+ * ldw_mi_score_links — every pair inside the mask with s >= thr (an fp64 comparison: a NaN score is never listed) is listed once as a_out / b_out (the
+ *   from-SNP and the to-SNP, global and 0-based), mi_out and score_out (the device's own bits), in no stated order.  *count_out is the exact number of such
+ *   pairs whatever cap is; where it exceeds cap the call returns LDW_ERR_SIZE with *count_out written and the lists undefined; nothing is written past
+ *   cap entries.  cap = 0 with null lists is a pure count.
+ *   partner_out[L] (int32, may be NULL; needs best_in[L], LDW_ERR_ARG otherwise): the smallest global index j among i's partners inside the mask whose score
+ *                has the key of best_in[i] (equal IEEE bits); -1 where best_in[i] is NaN or no partner matches.  With best_in = best_out of a scan with the
+ *                same arguments it names each SNP's best partner.  A 32-bit integer minimum: nothing depends on the order of evaluation.
+ * Integer adds, maxima of an ordered key and integer minima only.  The link tables and the ldw_block_stats of an earlier pass stay as they were.
+ * ldw_ctx_last_timing afterwards: [0] the blocks' GEMM + epilogue, [1] the scan or links kernels, [2] 0, [3] their sum.  Both calls run on the context's
+ * stream and return when the outputs are written. */
+int ldw_mi_score_scan(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int quirk_mode, double sr_dist, int cls_mask, const double *w, uint64_t *hist_out,
+                      double *best_out, int64_t *npairs_out);
+int ldw_mi_score_links(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int quirk_mode, double sr_dist, int cls_mask, const double *w, double thr,
+                       const double *best_in, int64_t cap, int32_t *a_out, int32_t *b_out, double *mi_out, double *score_out, int64_t *count_out,
+                       int32_t *partner_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

@@ -298,6 +298,26 @@ int ldw_debug_snp_summary(ldw_ctx *ctx, const double *mi, int64_t nf, int64_t nt
                           int64_t *nge_t, int64_t *npairs_out, int64_t *stats_out);
 int ldw_snp_summary_report(ldw_ctx *ctx, int64_t out[5]);
 
+/* ---- selection by a corrected score (ldweaver_amd.h 22) ------------------------------------------------------------------------------------------------------
+ * ldw_debug_score_scan / ldw_debug_score_links: the kernels of ldw_mi_score_scan (k_score_scan) and ldw_mi_score_links (k_score_links) as functions, on
+ *   caller-made values; they need no alignment.  mi, nf, nt, pos_f, pos_t, g and diag as ldw_debug_snp_summary (mi may hold any double); sr_dist and cls_mask
+ *   as (22); w_f[nf] / w_t[nt] the weights of the two sides, finite.  The two sides come out apart.
+ *   scan: hist_out[4096], best_f[nf] / best_t[nt] the largest score of every row / column (NaN: none), *npairs_out the pairs inside the mask.
+ *   links: id_f[nf] / id_t[nt] the global ids of the two sides, 0..2^31 - 2, in any order (the scan needs none); thr, cap, the four lists (a_out from id_f,
+ *   b_out from id_t) and *count_out as (22); best_f / best_t (both or neither) and partner_f[nf] / partner_t[nt] (both or neither, they need the bests): per
+ *   row the smallest id_t among its partners whose score has the key of best_f, per column the smallest id_f likewise; -1: none.
+ *   stats_out (may be NULL, 2 values): patches visited (every patch but a diagonal block's patches that lie wholly on or above the diagonal), NaN scores.
+ *   LDW_ERR_ARG: nf, nt outside 1..1 000 000, diag with nf != nt, g not positive, what (22) refuses, an id outside its range.
+ * ldw_score_select_report: out[0..1] the same two counts summed over the last ldw_mi_score_scan or ldw_mi_score_links of the context, out[2] its blocks. */
+int ldw_debug_score_scan(ldw_ctx *ctx, const double *mi, int64_t nf, int64_t nt, const int32_t *pos_f, const int32_t *pos_t, double g, int diag, double sr_dist,
+                         int cls_mask, const double *w_f, const double *w_t, uint64_t *hist_out, double *best_f, double *best_t, int64_t *npairs_out,
+                         int64_t *stats_out);
+int ldw_debug_score_links(ldw_ctx *ctx, const double *mi, int64_t nf, int64_t nt, const int32_t *pos_f, const int32_t *pos_t, double g, int diag, double sr_dist,
+                          int cls_mask, const int32_t *id_f, const int32_t *id_t, const double *w_f, const double *w_t, double thr, const double *best_f,
+                          const double *best_t, int64_t cap, int32_t *a_out, int32_t *b_out, double *mi_out, double *score_out, int64_t *count_out,
+                          int32_t *partner_f, int32_t *partner_t, int64_t *stats_out);
+int ldw_score_select_report(ldw_ctx *ctx, int64_t out[3]);
+
 /* ---- the plots (ldweaver_amd.h 12) ------------------------------------------------------------------------------------------------ */
 /* The rasters of ldw_plot_scatter without the frame, for panels of W x H pixels each (any size >= 1): rgb_out[n_panels][H][W][3] (host).  Grid
  * lines lie at the ticks of ldw_plot_ticks for the data range and W / H.  stats_out (may be NULL, 8 doubles): x min, x max, y min, y max of

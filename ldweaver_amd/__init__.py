@@ -20,6 +20,7 @@ _EXPORTS = {
     "cochange_pvalue": "parsimony",
     "ld_decay": "decay", "LDDecay": "decay", "default_cuts": "decay",
     "snp_background": "background", "SnpBackground": "background", "link_apc": "background",
+    "apc_links": "background", "pick_threshold": "background",
     "sequence_clusters": "lineage", "link_lineage_mi": "lineage", "link_permutation_test": "lineage",
 }
 __all__ = sorted(_EXPORTS)

@@ -1,7 +1,8 @@
 """The MI background of every SNP (include/ldweaver_amd.h 21): per SNP and distance class the number of partners, the exact sum of their MI
 in 40-bit fixed point, the largest MI and the partners above a threshold, over EVERY SNP pair of an alignment — the values the pass computes and drops —
 and the average product correction of links that follows from it.  The integers are taken on the device (``Engine.mi_snp_summary``); everything in
-``SnpBackground`` and ``link_apc`` is a pure host function of them."""
+``SnpBackground`` and ``link_apc`` is a pure host function of them.  ``apc_links`` (include/ldweaver_amd.h 22) selects links by the corrected
+score over every pair instead of re-ranking a list that raw MI selected, and names every SNP's best partner by that score."""
 from __future__ import annotations
 
 import warnings
@@ -12,7 +13,7 @@ import pandas as pd
 
 from . import _lib as L
 
-__all__ = ["snp_background", "SnpBackground", "link_apc"]
+__all__ = ["snp_background", "SnpBackground", "link_apc", "apc_links", "apc_weights", "pick_threshold"]
 
 FRAC = 40                         # fraction bits of sumq (csrc/ldw_snpsum.h SNPSUM_FRAC)
 WHICH = ("sr", "lr", "all")
@@ -112,6 +113,103 @@ def snp_background(snp_dat, hdw=None, *, sr_dist=20000, thr=(np.inf, np.inf), ma
         if own:
             eng.close()
     return bg
+
+
+CLS_MASK = {"sr": 1, "lr": 2, "all": 3}     # ldw_mi_score_scan's class mask of ``which``
+NBINS = 4096
+BUCKET_OFF = (1023 - 20) << 7              # csrc/ldw_epi.h: bucket B >= 1 starts at the double with bits (B + BUCKET_OFF) << 45
+CAP_LIMIT = 1 << 26
+
+
+def pick_threshold(hist, top: int):
+    """The threshold of ``apc_links`` from the scan's histogram, a pure function: with cum(B) the pairs in the buckets >= B, B* is the largest B >= 1 with
+    cum(B) >= top, else 1.  Returns (thr, cap): thr the lower edge of bucket B*, the double with bits (B* + ((1023 - 20) << 7)) << 45, and cap = cum(B*).
+    Bucket edges are monotone in the value, so exactly cap pairs have a score >= thr.  Bucket 0 is never taken: scores below 2^-20 are never listed."""
+    h = np.asarray(hist).astype(np.uint64).astype(object)                      # Python integers: no wrap-around
+    if h.shape != (NBINS,):
+        raise ValueError(f"pick_threshold: the histogram has shape {h.shape}, not ({NBINS},)")
+    cum = np.cumsum(h[::-1])[::-1]
+    reach = [B for B in range(1, NBINS) if cum[B] >= top]
+    B = max(reach) if reach else 1
+    thr = float(np.array([(B + BUCKET_OFF) << 45], dtype=np.int64).view(np.float64)[0])
+    return thr, int(cum[B])
+
+
+def apc_weights(background: "SnpBackground", which: str = "lr") -> np.ndarray:
+    """The per-SNP vector of the average product correction: w = mean(which) / sqrt(overall_mean(which)), so that w[a] w[b] = mean(a) mean(b) / overall.
+    0 where the mean is NaN (such a SNP has no pair in the class).  ValueError when the overall mean is not positive."""
+    overall = background.overall_mean(which)
+    if not overall > 0:
+        raise ValueError(f"apc_weights: the overall mean MI of class {which!r} is {overall}: the correction needs a positive one")
+    m = background.mean(which)
+    return np.where(np.isnan(m), 0.0, m / np.sqrt(overall))
+
+
+def apc_links(snp_dat, hdw=None, *, background: "SnpBackground | None" = None, top: int = 1000, which: str = "lr", sr_dist=20000, max_blk_sz: int = 10000,
+              threshold: float = 0.1, quirk_mode: int = L.QUIRK_REFERENCE, engine=None, alignment_resident: bool = False, out_path=None):
+    """The ``top`` links of class ``which`` by the APC-corrected score mi_apc = MI - w[a] w[b], selected over EVERY SNP pair — not re-ranked from a list
+    selected by raw MI, as ``link_apc`` does — and every SNP's best partner by that score.  ``background=None`` runs ``snp_background`` first, on the same
+    engine.  The flow: ``Engine.mi_score_scan`` (histogram of the score, best score per SNP), ``pick_threshold``, ``Engine.mi_score_links`` with that
+    threshold, capacity and the scan's best scores; the host sorts by score descending, ties by (a, b) ascending, and trims to ``top``.  Scores below 2^-20
+    are never listed (bucket 0 of the histogram holds them together with the negatives), so fewer than ``top`` rows may come back; a threshold bucket that
+    holds more than 2^26 pairs raises ValueError: ask for a smaller ``top``.
+    Returns (links, partners): ``links`` with pos1 (the to-SNP), pos2 (the from-SNP), len, MI, bg1, bg2 (the background means of the two), apc = w w and
+    mi_apc, the device's score; ``partners`` one row per SNP: pos, best (its largest score, NaN without a partner in the class), partner_pos (NaN where
+    none), partner_snp (-1 where none).  ``out_path``: ``links`` as tsv, header first.  Nothing here changes a link table."""
+    from . import rcompat
+    from .engine import Engine, write_table_tsv
+    from .mi import make_blocks
+    if which not in CLS_MASK:
+        raise ValueError(f"which must be one of {WHICH}, got {which!r}")
+    own = engine is None
+    eng = engine or Engine(0)
+    try:
+        if background is None:
+            background = snp_background(snp_dat, hdw, sr_dist=sr_dist, max_blk_sz=max_blk_sz, threshold=threshold, quirk_mode=quirk_mode, engine=eng,
+                                        alignment_resident=alignment_resident)
+        else:
+            if snp_dat.g is None:
+                raise ValueError("snp.dat$g is NULL: set the genome length first (R/BacGWES.R:338-345)")
+            if not alignment_resident:
+                eng.set_alignment(snp_dat.states)
+            if hdw is None:
+                hdw = eng.hamming_weights(int(snp_dat.nsnp * threshold))
+            eng.set_weights(hdw)
+            eng.set_snp_meta(snp_dat.r, snp_dat.uqe, snp_dat.POS, None, float(snp_dat.g))
+        w = apc_weights(background, which)
+        if len(w) != snp_dat.nsnp:
+            raise ValueError(f"apc_links: the background has {len(w)} SNPs, snp_dat {snp_dat.nsnp}")
+        blocks, mask = make_blocks(snp_dat.nsnp, int(max_blk_sz)), CLS_MASK[which]
+        scan = eng.mi_score_scan(blocks, float(sr_dist), mask, w, quirk=quirk_mode)
+        thr, cap = pick_threshold(scan["hist"], int(top))
+        if cap > CAP_LIMIT:
+            raise ValueError(f"apc_links: {cap} pairs share the threshold bucket of top = {top} (more than 2^26): ask for a smaller top")
+        got = eng.mi_score_links(blocks, float(sr_dist), mask, w, thr, cap, best_in=scan["best"], quirk=quirk_mode)
+        assert got["count"] == cap, (got["count"], cap)                       # bucket edges are monotone in the value
+    finally:
+        if own:
+            eng.close()
+    POS = np.asarray(snp_dat.POS)
+    if cap:
+        a, b, mi, sc = (got[k] for k in ("a", "b", "mi", "score"))
+        order = np.lexsort((b, a, -sc))[:max(int(top), 0)]
+        a, b, mi, sc = a[order], b[order], mi[order], sc[order]
+    else:
+        a = b = np.zeros(0, dtype=np.int32)
+        mi = sc = np.zeros(0)
+    m = background.mean(which)
+    pos1, pos2 = POS[b].astype(np.float64), POS[a].astype(np.float64)
+    links = pd.DataFrame({"pos1": pos1, "pos2": pos2, "len": rcompat.circ_len(pos1, pos2, float(snp_dat.g)), "MI": mi, "bg1": m[b], "bg2": m[a],
+                          "apc": w[a] * w[b], "mi_apc": sc})
+    ps = got["partner"].astype(np.int64)
+    partners = pd.DataFrame({"pos": POS, "best": scan["best"], "partner_pos": np.where(ps >= 0, POS[np.maximum(ps, 0)].astype(np.float64), np.nan),
+                             "partner_snp": ps})
+    partners.attrs["cap"], partners.attrs["thr"] = cap, thr
+    if out_path is not None:
+        with open(out_path, "w") as f:
+            f.write("\t".join(links.columns) + "\n")
+        write_table_tsv(out_path, [links[c].to_numpy() for c in links.columns], append=True)
+    return links, partners
 
 
 def _mi_column(df):

@@ -396,6 +396,7 @@ struct ldw_ctx {
     ldw::PinnedBuf pin_fetch;    // r04: pinned host arena the tsv writer fetches a link table into (see ldw_write_links_tsv)
     int64_t decay_stat[4] = {0, 0, 0, 0};            // ldw_decay_report: patches, route-B patches, pairs outside their patch's bound and blocks of the last ldw_mi_profile
     int64_t snpsum_stat[5] = {0, 0, 0, 0, 0};        // ldw_snp_summary_report: patches, general-route patches, pairs off their patch's class, values q refused and blocks of the last ldw_mi_snp_summary
+    int64_t scoresel_stat[3] = {0, 0, 0};            // ldw_score_select_report: patches visited, NaN scores and blocks of the last ldw_mi_score_scan or ldw_mi_score_links
     double ham_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ldw_hamming_stats: columns, padded K, stage times and algorithmic bytes of the last ldw_hamming_weights
     ldw::DevBuf plot_work, plot_cols;   // the plots (ldw_plot.hip): key image + rasters + partials; device copy of a chunk of host columns
 
@@ -443,7 +444,7 @@ int ensure_hi_marginals(ldw_ctx *ctx);   // slot_pfix_hi on demand (mixed-precis
 // ldw_mi.hip: run_block_mi without link tables, as ldw_mi_block runs it: the dense MI of one block into ctx->MIblk [nf * nt] column-major; the block's index
 // lists stay in ctx->idx_f / idx_t, its stage events are ctx->ev[0..2] (ldw_decay.hip)
 int block_mi_dense(ldw_ctx *ctx, const int32_t *from_idx, int64_t nf, const int32_t *to_idx, int64_t nt, int quirk);
-// ldw_decay.hip: what ldw_mi_profile and ldw_mi_snp_summary share.  pair_blocks_check: the requirements of both entries (a GPU, the arguments, the quirk mode, the
+// ldw_decay.hip: what ldw_mi_profile, ldw_mi_snp_summary and the two entries of ldw_scoresel.hip share.  pair_blocks_check: the requirements of both entries (a GPU, the arguments, the quirk mode, the
 // resident alignment, weights and meta data, then own_check() for the caller's own arguments, then every block diagonal or disjoint), refused under the caller's name.  pair_blocks_walk: per block the dense MI
 // (block_mi_dense), consumer(nf, nt, diag) launched behind it on the context's stream, the synchronisation, and the event times and pair count added to W.
 struct PairBlockWalk {

@@ -417,6 +417,94 @@ class Engine:
                                               *[L.ptr(s[k]) for s in (rows, cols) for k in ("n", "sumq", "max", "nge")], L.ptr(npairs), L.ptr(st)))
         return dict(rows=rows, cols=cols, npairs=npairs, stats=st)
 
+    # -- selection by a corrected score -----------------------------
+    def mi_score_scan(self, blocks, sr_dist, cls_mask, w, quirk=L.QUIRK_REFERENCE):
+        """Over EVERY SNP pair of ``blocks`` inside the class mask (1: len <= sr_dist, 2: beyond, 3: both), with the score s = mi - w[a] w[b]
+        (ldw_mi_score_scan): ``hist`` uint64 (4096,) the pairs per ``mi_bucket(s)``, ``best`` float64 (L,) the largest score of every SNP over its partners (NaN
+        where none) and ``npairs`` the pairs inside the mask.  ``w`` (L,) must be finite.  The link tables stay as they are."""
+        bl = L.as_c(blocks, np.int32).reshape(-1, 4)
+        wv = L.as_c(w, np.float64).reshape(self.L)
+        hist, best, n = np.zeros(4096, dtype=np.uint64), np.full(self.L, np.nan), C.c_int64(0)
+        L.check(L.lib().ldw_mi_score_scan(self._ctx, L.ptr(bl), len(bl), int(quirk), float(sr_dist), int(cls_mask), L.ptr(wv), L.ptr(hist), L.ptr(best), C.byref(n)))
+        return dict(hist=hist, best=best, npairs=int(n.value))
+
+    @staticmethod
+    def _link_lists(cap):
+        cap = int(cap)
+        return (np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap), np.zeros(cap)) if cap > 0 else (None, None, None, None)
+
+    def mi_score_links(self, blocks, sr_dist, cls_mask, w, thr, cap: int = 0, best_in=None, quirk=L.QUIRK_REFERENCE):
+        """The pairs of ``mi_score_scan``'s pair set with s >= ``thr`` (ldw_mi_score_links): ``a`` / ``b`` the from-SNP and the to-SNP (global, 0-based), ``mi``,
+        ``score``, in no stated order, and ``count``, exact whatever ``cap`` is.  ``cap`` = 0 only counts; a count above ``cap`` raises LdwError LDW_ERR_SIZE,
+        which carries the count as ``.count``.  With ``best_in`` (L,) — the ``best`` of a scan with the same arguments — ``partner`` int32 (L,) is the smallest
+        partner of every SNP whose score has the bits of best_in, -1 where there is none."""
+        bl = L.as_c(blocks, np.int32).reshape(-1, 4)
+        wv = L.as_c(w, np.float64).reshape(self.L)
+        a, b, mi, sc = self._link_lists(cap)
+        bi = None if best_in is None else L.as_c(best_in, np.float64).reshape(self.L)
+        partner = None if bi is None else np.full(self.L, -1, dtype=np.int32)
+        n = C.c_int64(0)
+        try:
+            L.check(L.lib().ldw_mi_score_links(self._ctx, L.ptr(bl), len(bl), int(quirk), float(sr_dist), int(cls_mask), L.ptr(wv), float(thr), L.ptr(bi), max(int(cap), 0),
+                                               L.ptr(a), L.ptr(b), L.ptr(mi), L.ptr(sc), C.byref(n), L.ptr(partner)))
+        except L.LdwError as e:
+            e.count = int(n.value)
+            raise
+        k = int(n.value)
+        cut = (lambda x: None if x is None else x[:k])
+        return dict(a=cut(a), b=cut(b), mi=cut(mi), score=cut(sc), count=k, partner=partner)
+
+    def score_select_report(self):
+        """Of the last mi_score_scan or mi_score_links (ldw_score_select_report): patches the kernel visited, NaN scores, blocks."""
+        v = np.zeros(3, dtype=np.int64)
+        L.check(L.lib().ldw_score_select_report(self._ctx, L.ptr(v)))
+        return dict(patches=int(v[0]), nan_scores=int(v[1]), blocks=int(v[2]))
+
+    @staticmethod
+    def _debug_block(mi, pos_f, pos_t, w_f, w_t):
+        m = np.asarray(mi, dtype=np.float64)
+        assert m.ndim == 2, m.shape
+        nf, nt = m.shape
+        pf, pt = L.as_c(pos_f, np.int32).ravel(), L.as_c(pos_t, np.int32).ravel()
+        wf, wt = L.as_c(w_f, np.float64).ravel(), L.as_c(w_t, np.float64).ravel()
+        assert len(pf) == nf == len(wf) and len(pt) == nt == len(wt), (len(pf), len(pt), len(wf), len(wt), m.shape)
+        return np.asfortranarray(m), nf, nt, pf, pt, wf, wt
+
+    def debug_score_scan(self, mi, pos_f, pos_t, g, diag, sr_dist, cls_mask, w_f, w_t):
+        """The kernel of mi_score_scan on caller-made values (ldw_debug_score_scan): ``mi`` (nf, nt) (stored column-major for the call), the positions and the
+        weights of the two sides, the genome length, ``diag`` (pairs a > b of a square block) or not (pairs a != b).  Returns ``hist``, ``best_f`` (nf,) and
+        ``best_t`` (nt,) — the two sides apart —, ``npairs`` and ``stats`` (patches visited, NaN scores)."""
+        mf, nf, nt, pf, pt, wf, wt = self._debug_block(mi, pos_f, pos_t, w_f, w_t)
+        hist, bf, bt = np.zeros(4096, dtype=np.uint64), np.full(nf, np.nan), np.full(nt, np.nan)
+        n, st = C.c_int64(0), np.zeros(2, dtype=np.int64)
+        L.check(L.lib().ldw_debug_score_scan(self._ctx, L.ptr(mf), nf, nt, L.ptr(pf), L.ptr(pt), float(g), int(bool(diag)), float(sr_dist), int(cls_mask), L.ptr(wf),
+                                             L.ptr(wt), L.ptr(hist), L.ptr(bf), L.ptr(bt), C.byref(n), L.ptr(st)))
+        return dict(hist=hist, best_f=bf, best_t=bt, npairs=int(n.value), stats=st)
+
+    def debug_score_links(self, mi, pos_f, pos_t, g, diag, sr_dist, cls_mask, id_f, id_t, w_f, w_t, thr, cap: int = 0, best_f=None, best_t=None):
+        """The kernel of mi_score_links on caller-made values (ldw_debug_score_links), as debug_score_scan; ``id_f`` / ``id_t`` the global ids of the two sides.
+        Returns the dict of mi_score_links with ``partner_f`` (nf,) and ``partner_t`` (nt,) in place of ``partner`` (None without ``best_f`` / ``best_t``) and
+        ``stats`` (patches visited, NaN scores)."""
+        mf, nf, nt, pf, pt, wf, wt = self._debug_block(mi, pos_f, pos_t, w_f, w_t)
+        idf, idt = L.as_c(id_f, np.int32).ravel(), L.as_c(id_t, np.int32).ravel()
+        assert len(idf) == nf and len(idt) == nt and (best_f is None) == (best_t is None), (len(idf), len(idt))
+        a, b, mo, sc = self._link_lists(cap)
+        bf = None if best_f is None else L.as_c(best_f, np.float64).reshape(nf)
+        bt = None if best_t is None else L.as_c(best_t, np.float64).reshape(nt)
+        prf = None if bf is None else np.full(nf, -1, dtype=np.int32)
+        prt = None if bt is None else np.full(nt, -1, dtype=np.int32)
+        n, st = C.c_int64(0), np.zeros(2, dtype=np.int64)
+        try:
+            L.check(L.lib().ldw_debug_score_links(self._ctx, L.ptr(mf), nf, nt, L.ptr(pf), L.ptr(pt), float(g), int(bool(diag)), float(sr_dist), int(cls_mask), L.ptr(idf),
+                                                  L.ptr(idt), L.ptr(wf), L.ptr(wt), float(thr), L.ptr(bf), L.ptr(bt), max(int(cap), 0), L.ptr(a), L.ptr(b), L.ptr(mo),
+                                                  L.ptr(sc), C.byref(n), L.ptr(prf), L.ptr(prt), L.ptr(st)))
+        except L.LdwError as e:
+            e.count = int(n.value)
+            raise
+        k = int(n.value)
+        cut = (lambda x: None if x is None else x[:k])
+        return dict(a=cut(a), b=cut(b), mi=cut(mo), score=cut(sc), count=k, partner_f=prf, partner_t=prt, stats=st)
+
     def debug_screen_bound(self, kind: int, na: int, nb: int, g, pa, pb, pX, pY, rr, params, masks=None):
         """The engine's screen / evaluation device functions on caller-made joint tables (ldw_debug_screen_bound): kind 0 / 1 the approximate path's upper
         bounds (straight-line / predicated), 2 / 3 the fp32 MI of the exact-limb screens, 4 the fp64 value the engine emits."""
