@@ -934,6 +934,44 @@ int ldw_mi_score_links(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int
                        const double *best_in, int64_t cap, int32_t *a_out, int32_t *b_out, double *mi_out, double *score_out, int64_t *count_out,
                        int32_t *partner_out);
 
+/* ---- (23) the co-change scan: the branches of a tree on which two SNPs both change, over EVERY pair of the SNPs that change often enough -----
+ * parent, tip_seq, nodes and gap_mode exactly as (17) takes and refuses them; further nodes <= 2^21, which keeps the products below inside int64.
+ * B = nodes - 1 is the number of branches.  changes[i] is SNP i's parsimony score (17): the popcount of its bitmap of changed branches.
+ *   eligible     SNP i is eligible when changes[i] >= min_changes (min_changes >= 1).  M is their number; they are taken in ascending SNP index.
+ *   the pair set P: the unordered pairs i < j of eligible SNPs; where min_len >= 0 only those with circ_len(POS[j], POS[i], g) > min_len, the len column of the
+ *                link tables (0.5 g - |(POS[j] - POS[i]) mod g - 0.5 g|), closed below as the pass's sr_dist is.  min_len < 0: no distance is computed and
+ *                neither SNP meta data nor positions are needed.  NaN is refused.
+ *   qualifying   co = popcount(bits_i & bits_j), the branches on which both change (ldw_tree_cochanges' co_out).  A pair of P qualifies when
+ *                co * B >= min_lift * changes[i] * changes[j], an int64 comparison: co is at least min_lift times what two independent branch sets would
+ *                share.  min_lift is an integer in [0, 2^20]; 0 qualifies every pair of P.
+ * ldw_tree_cochange_scan — outputs (HOST):
+ *   changes_out[L]  the score of every SNP.
+ *   hist_out[1024]  the qualifying pairs per min(co, 1023).
+ *   best_out[L]  (int32) the largest co of SNP i over its qualifying partners; -1 where there are none, ineligible SNPs included.
+ *   nge_out[L]   (int64) the qualifying partners of SNP i with co >= min_co (min_co >= 0).
+ *   npairs_out[2]  |P| and the number of qualifying pairs; the second equals the sum of hist_out.
+ *   Every pair adds to both of its SNPs.
+ * ldw_tree_cochange_links — every qualifying pair with co >= min_co is listed once as a_out < b_out (global, 0-based) and co_out, in no stated order.
+ *   *count_out is the exact number of such pairs whatever cap is; where it exceeds cap the call returns LDW_ERR_SIZE with *count_out written and the lists
+ *   undefined; nothing is written past cap entries.  cap = 0 with null lists is a pure count: the contract of ldw_mi_score_links (22).
+ *   partner_out[L] (int32, may be NULL; needs best_in[L], LDW_ERR_ARG otherwise): the smallest j among i's qualifying partners whose co == best_in[i]; -1
+ *                where best_in[i] < 0, where nothing matches and for an ineligible SNP.  With best_in = best_out of a scan with the same arguments it names
+ *                each SNP's best partner.
+ * Integer adds, integer maxima and integer minima only: nothing depends on the order of evaluation, on the chunks of the passes (LDW_PARS_CHUNK) or on the
+ * bands the pair kernel is launched in (at most 65 535 tile rows each; LDW_COSCAN_ROWS=k in the environment, read at every call, forces bands of k tile
+ * rows: a test hook).  M of 0 or 1 is legal: zero pairs, best all -1.  ldw_ctx_last_timing afterwards: [0] the pair kernels, [1] the parsimony passes and
+ * gathers, [2] the copies out, [3] their sum.
+ * Refused on the host before anything is launched, the context staying usable — LDW_ERR_STATE: no alignment resident, or min_len >= 0 without positions
+ * (ldw_set_snp_meta).  LDW_ERR_ARG: whatever (17) refuses; nodes > 2^21; min_changes < 1; min_co < 0; min_lift outside [0, 2^20]; min_len NaN; partner_out
+ * without best_in; a null required pointer.  Both calls run on the context's stream, take their working memory (the scores' node sets as (17), then
+ * ceil(nodes / 32) x 4 bytes per eligible SNP for the bitmaps) and give it back; the alignment, the weights, the SNP metadata and the link tables stay as
+ * they are. */
+int ldw_tree_cochange_scan(ldw_ctx *ctx, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, int32_t min_changes, int32_t min_co,
+                           int64_t min_lift, double min_len, int32_t *changes_out, uint64_t *hist_out, int32_t *best_out, int64_t *nge_out, int64_t *npairs_out);
+int ldw_tree_cochange_links(ldw_ctx *ctx, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, int32_t min_changes, int32_t min_co,
+                            int64_t min_lift, double min_len, const int32_t *best_in, int64_t cap, int32_t *a_out, int32_t *b_out, int32_t *co_out,
+                            int64_t *count_out, int32_t *partner_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

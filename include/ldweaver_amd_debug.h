@@ -318,6 +318,22 @@ int ldw_debug_score_links(ldw_ctx *ctx, const double *mi, int64_t nf, int64_t nt
                           int32_t *partner_f, int32_t *partner_t, int64_t *stats_out);
 int ldw_score_select_report(ldw_ctx *ctx, int64_t out[3]);
 
+/* ---- the co-change scan (ldweaver_amd.h 23) ------------------------------------------------------------------------------------------------------------------
+ * ldw_debug_cochange_scan / ldw_debug_cochange_links: the pair kernel of ldw_tree_cochange_scan and ldw_tree_cochange_links (k_coscan) as functions, on
+ *   caller-made bitmaps; they need no alignment and no tree, and run the launch code of the two entries (bands, LDW_COSCAN_ROWS, initialisation).  All from the
+ *   HOST: bits[words][M] (word w of slot s at bits[w M + s]; any bits, words 1..2^16), M in 0..2^24 slots standing for the eligible SNPs; changes[M] what the
+ *   lift test multiplies (0..2^21 - 1; the entries do not require the popcount of the row); idx[M] the global SNP of every slot, strictly ascending, 0..2^31 - 2;
+ *   pos[M] and g (needed where min_len >= 0); B in 1..2^21 - 1; min_co, min_lift, min_len as (23).  The pair set, the qualifying pairs and every output are
+ *   those of (23) over the M slots: hist_out[1024], best_out[M], nge_out[M], npairs_out[2]; best_in[M], cap, the three lists (global SNPs from idx), *count_out
+ *   and partner_out[M] (a global SNP, or -1).  LDW_ERR_ARG: what (23) refuses of the thresholds and of the lists, a size or a value outside the ranges above,
+ *   idx not ascending, a null pointer among those M > 0 needs. */
+int ldw_debug_cochange_scan(ldw_ctx *ctx, const uint32_t *bits, int64_t words, int64_t M, const int32_t *changes, const int32_t *idx, const int32_t *pos, double g,
+                            int64_t B, int32_t min_co, int64_t min_lift, double min_len, uint64_t *hist_out, int32_t *best_out, int64_t *nge_out,
+                            int64_t *npairs_out);
+int ldw_debug_cochange_links(ldw_ctx *ctx, const uint32_t *bits, int64_t words, int64_t M, const int32_t *changes, const int32_t *idx, const int32_t *pos, double g,
+                             int64_t B, int32_t min_co, int64_t min_lift, double min_len, const int32_t *best_in, int64_t cap, int32_t *a_out, int32_t *b_out,
+                             int32_t *co_out, int64_t *count_out, int32_t *partner_out);
+
 /* ---- the plots (ldweaver_amd.h 12) ------------------------------------------------------------------------------------------------ */
 /* The rasters of ldw_plot_scatter without the frame, for panels of W x H pixels each (any size >= 1): rgb_out[n_panels][H][W][3] (host).  Grid
  * lines lie at the ticks of ldw_plot_ticks for the data range and W / H.  stats_out (may be NULL, 8 doubles): x min, x max, y min, y max of

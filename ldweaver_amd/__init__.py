@@ -17,7 +17,7 @@ _EXPORTS = {
     "view_tree": "tree", "read_newick": "tree", "midpoint_root": "tree", "ladderize": "tree",
     "nj_tree": "tree", "write_newick": "tree", "bootstrap_multiplicities": "tree",
     "snp_parsimony": "parsimony", "link_cochanges": "parsimony", "ancestral_states": "parsimony", "tip_sequences": "parsimony",
-    "cochange_pvalue": "parsimony",
+    "cochange_pvalue": "parsimony", "cochange_scan": "parsimony", "CochangeScan": "parsimony", "pick_min_co": "parsimony",
     "ld_decay": "decay", "LDDecay": "decay", "default_cuts": "decay",
     "snp_background": "background", "SnpBackground": "background", "link_apc": "background",
     "apc_links": "background", "pick_threshold": "background",

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ldw_internal.h"
+#include "ldw_pars.h"
 #include "ldw_seq_plan.h"
 
 using namespace ldw;
@@ -179,20 +180,7 @@ __global__ __launch_bounds__(256) void k_pars_pairs(const uint32_t *__restrict__
 
 }  // namespace ldw
 
-namespace {
-
-// the tree as the kernels read it, checked: nothing here touches the device
-struct ParsTree {
-    int64_t nodes = 0, tips = 0;
-    std::vector<int32_t> child_ptr, child_idx;   // CSR: the children of v in ascending order
-    std::vector<int32_t> tip_seq, tip_node;      // the tips in ascending order of their sequence
-};
-
-struct ParsBufs {   // the working memory of one call (the entry points release it)
-    ldw::DevBuf sets, seen, score, minch, parent, child_ptr, child_idx, tip_seq, tip_node, snp, bits, state, slot_a, slot_b, ca, cb, co;
-};
-
-int pars_check_tree(const ldw_ctx *c, const char *who, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, ParsTree &t) {
+int ldw::pars_check_tree(const ldw_ctx *c, const char *who, const int32_t *parent, const int32_t *tip_seq, int64_t nodes, int32_t gap_mode, ParsTree &t) {
     LDW_REQUIRE(parent && tip_seq, LDW_ERR_ARG, "%s: parent or tip_seq is null", who);
     LDW_REQUIRE(gap_mode == 0 || gap_mode == 1, LDW_ERR_ARG, "%s: gap_mode %d (0: N is missing, 1: N is a state)", who, (int)gap_mode);
     LDW_REQUIRE(nodes >= 2, LDW_ERR_ARG, "%s: %lld nodes (a tree needs at least 2)", who, (long long)nodes);
@@ -233,72 +221,67 @@ int pars_check_tree(const ldw_ctx *c, const char *who, const int32_t *parent, co
     return LDW_OK;
 }
 
+namespace {
+
 // SNPs of a chunk: what PARS_BUDGET bytes of sets hold, LDW_PARS_CHUNK=k forces k (a test hook, read at every call); never more than `total`
 int64_t pars_chunk(int64_t nodes, int64_t total) {
     const int64_t C = ldw::budget_or_env(std::max<int64_t>(PARS_TILE, PARS_BUDGET / nodes / PARS_TILE * PARS_TILE), "LDW_PARS_CHUNK");
     return std::min<int64_t>(std::min<int64_t>(C, PARS_MAX_CHUNK), total);
 }
 
-// What the three entry points share: the tree on the device, then chunk after chunk of `total` SNP slots (slot j is SNP snp[j], or SNP j where snp is null)
-// the tips, the up pass and, with `down`, the down pass; after_chunk(first slot, count) queues what the caller wants of the chunk's sets before the next
-// chunk overwrites them.  ldw_ctx_last_timing: [0] the passes, [1] the gathers, [2] whatever after_chunk and the caller queued behind, [3] their sum.
-struct ParsRun {
-    ldw_ctx *c;
-    ParsBufs &b;
-    const ParsTree &t;
-    int32_t gap_mode;
-    int64_t C = 0, Cpad = 0, stride4 = 0;
-    ldw::Laps laps;   // three events per chunk and one behind the last
+}  // namespace
 
-    int start(const int32_t *parent, int64_t total, const int32_t *snp, bool want_score, bool down) {
-        C = pars_chunk(t.nodes, total), Cpad = round_up(C, PARS_TILE), stride4 = Cpad / 4;
-        int rc = LDW_OK;
-        if ((rc = b.sets.reserve((size_t)t.nodes * (size_t)Cpad)) || (rc = b.seen.reserve((size_t)Cpad)) ||
-            (want_score && ((rc = b.score.reserve((size_t)Cpad * 4)) || (rc = b.minch.reserve((size_t)Cpad * 4)))))
-            return rc;
-        if ((rc = ldw::upload(c, b.child_ptr, t.child_ptr.data(), t.child_ptr.size())) || (rc = ldw::upload(c, b.child_idx, t.child_idx.data(), t.child_idx.size())) ||
-            (rc = ldw::upload(c, b.tip_seq, t.tip_seq.data(), t.tip_seq.size())) || (rc = ldw::upload(c, b.tip_node, t.tip_node.data(), t.tip_node.size())))
-            return rc;
-        if (down && (rc = ldw::upload(c, b.parent, parent, (size_t)t.nodes))) return rc;
-        if (snp && (rc = ldw::upload(c, b.snp, snp, (size_t)total))) return rc;
-        return LDW_OK;
-    }
+// ParsRun (ldw_pars.h)
+int ldw::ParsRun::start(const int32_t *parent, int64_t total, const int32_t *snp, bool want_score, bool down) {
+    C = pars_chunk(t.nodes, total), Cpad = round_up(C, PARS_TILE), stride4 = Cpad / 4;
+    int rc = LDW_OK;
+    if ((rc = b.sets.reserve((size_t)t.nodes * (size_t)Cpad)) || (rc = b.seen.reserve((size_t)Cpad)) ||
+        (want_score && ((rc = b.score.reserve((size_t)Cpad * 4)) || (rc = b.minch.reserve((size_t)Cpad * 4)))))
+        return rc;
+    if ((rc = ldw::upload(c, b.child_ptr, t.child_ptr.data(), t.child_ptr.size())) || (rc = ldw::upload(c, b.child_idx, t.child_idx.data(), t.child_idx.size())) ||
+        (rc = ldw::upload(c, b.tip_seq, t.tip_seq.data(), t.tip_seq.size())) || (rc = ldw::upload(c, b.tip_node, t.tip_node.data(), t.tip_node.size())))
+        return rc;
+    if (down && (rc = ldw::upload(c, b.parent, parent, (size_t)t.nodes))) return rc;
+    if (snp && (rc = ldw::upload(c, b.snp, snp, (size_t)total))) return rc;
+    return LDW_OK;
+}
 
-    template <class After> int chunks(int64_t total, bool have_snp, bool want_score, bool down, uint32_t *bits, int64_t bit_stride, After after_chunk) {
-        uint32_t *sets = b.sets.as<uint32_t>(), *seen = b.seen.as<uint32_t>();
-        for (int64_t j0 = 0; j0 < total; j0 += C) {
-            const int64_t count = std::min<int64_t>(C, total - j0);
-            if (int rc = laps.mark(c->stream)) return rc;
-            LDW_HIP(hipMemsetAsync(seen, 0, (size_t)Cpad, c->stream));
-            hipLaunchKernelGGL(k_pars_tips, dim3((unsigned)((t.tips + PARS_TIPS - 1) / PARS_TIPS), (unsigned)(Cpad / PARS_TILE)), dim3(256), 0, c->stream,
-                               c->states.as<uint8_t>(), c->Npad, b.tip_seq.as<int32_t>(), b.tip_node.as<int32_t>(), t.tips,
-                               have_snp ? b.snp.as<int32_t>() + j0 : (const int32_t *)nullptr, j0, count, gap_mode, sets, stride4, seen);
-            LDW_HIP(hipGetLastError());
-            if (int rc = laps.mark(c->stream)) return rc;
-            hipLaunchKernelGGL(k_pars_up, dim3((unsigned)(stride4 / PARS_WAVE)), dim3(PARS_WAVE), 0, c->stream, sets, stride4, t.nodes, b.child_ptr.as<int32_t>(),
-                               b.child_idx.as<int32_t>(), seen, want_score ? b.score.as<int32_t>() : (int32_t *)nullptr,
-                               want_score ? b.minch.as<int32_t>() : (int32_t *)nullptr);
-            if (down)
-                hipLaunchKernelGGL(k_pars_down, dim3((unsigned)(stride4 / PARS_WAVE)), dim3(PARS_WAVE), 0, c->stream, sets, stride4, t.nodes, b.parent.as<int32_t>(),
-                                   bits, bit_stride, j0, count);
-            LDW_HIP(hipGetLastError());
-            if (int rc = laps.mark(c->stream)) return rc;
-            if (int rc = after_chunk(j0, count)) return rc;
-        }
-        return laps.mark(c->stream);
+int ldw::ParsRun::chunks(int64_t total, bool have_snp, bool want_score, bool down, uint32_t *bits, int64_t bit_stride, const std::function<int(int64_t, int64_t)> &after_chunk) {
+    uint32_t *sets = b.sets.as<uint32_t>(), *seen = b.seen.as<uint32_t>();
+    for (int64_t j0 = 0; j0 < total; j0 += C) {
+        const int64_t count = std::min<int64_t>(C, total - j0);
+        if (int rc = laps.mark(c->stream)) return rc;
+        LDW_HIP(hipMemsetAsync(seen, 0, (size_t)Cpad, c->stream));
+        hipLaunchKernelGGL(k_pars_tips, dim3((unsigned)((t.tips + PARS_TIPS - 1) / PARS_TIPS), (unsigned)(Cpad / PARS_TILE)), dim3(256), 0, c->stream,
+                           c->states.as<uint8_t>(), c->Npad, b.tip_seq.as<int32_t>(), b.tip_node.as<int32_t>(), t.tips,
+                           have_snp ? b.snp.as<int32_t>() + j0 : (const int32_t *)nullptr, j0, count, gap_mode, sets, stride4, seen);
+        LDW_HIP(hipGetLastError());
+        if (int rc = laps.mark(c->stream)) return rc;
+        hipLaunchKernelGGL(k_pars_up, dim3((unsigned)(stride4 / PARS_WAVE)), dim3(PARS_WAVE), 0, c->stream, sets, stride4, t.nodes, b.child_ptr.as<int32_t>(),
+                           b.child_idx.as<int32_t>(), seen, want_score ? b.score.as<int32_t>() : (int32_t *)nullptr,
+                           want_score ? b.minch.as<int32_t>() : (int32_t *)nullptr);
+        if (down)
+            hipLaunchKernelGGL(k_pars_down, dim3((unsigned)(stride4 / PARS_WAVE)), dim3(PARS_WAVE), 0, c->stream, sets, stride4, t.nodes, b.parent.as<int32_t>(),
+                               bits, bit_stride, j0, count);
+        LDW_HIP(hipGetLastError());
+        if (int rc = laps.mark(c->stream)) return rc;
+        if (int rc = after_chunk(j0, count)) return rc;
     }
+    return laps.mark(c->stream);
+}
 
-    // after the stream has drained
-    int finish() {
-        double ms[3] = {0, 0, 0};
-        if (int rc = laps.sums(3, ms)) return rc;
-        c->last_ms[0] = ms[1];   // the passes
-        c->last_ms[1] = ms[0];   // the gathers
-        c->last_ms[2] = ms[2];   // what followed a chunk: the copies out, the transposes, the pairs
-        c->last_ms[3] = ms[0] + ms[1] + ms[2];
-        return LDW_OK;
-    }
-};
+// after the stream has drained
+int ldw::ParsRun::finish() {
+    double ms[3] = {0, 0, 0};
+    if (int rc = lap_sums(ms)) return rc;
+    c->last_ms[0] = ms[1];   // the passes
+    c->last_ms[1] = ms[0];   // the gathers
+    c->last_ms[2] = ms[2];   // what followed a chunk: the copies out, the transposes, the pairs
+    c->last_ms[3] = ms[0] + ms[1] + ms[2];
+    return LDW_OK;
+}
+
+namespace {
 
 int pars_check_snps(const ldw_ctx *c, const char *who, const char *what, const int32_t *idx, int64_t n) {
     const int64_t k = ldw::first_bad_index(idx, n, c->L);

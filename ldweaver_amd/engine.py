@@ -860,6 +860,88 @@ class Engine:
         L.check(L.lib().ldw_tree_cochanges(self._ctx, pp, tp, len(p), int(gap_mode), pa, pb, K, L.ptr(ca), L.ptr(cb), L.ptr(co)))
         return ca[:K], cb[:K], co[:K]
 
+    # -- the co-change scan ---------------------------------------
+    def tree_cochange_scan(self, parent, tip_seq, gap_mode: int = 0, min_changes: int = 2, min_co: int = 2, min_lift: int = 0, min_len: float = -1.0):
+        """Over EVERY pair i < j of the SNPs that change on at least ``min_changes`` branches of the tree (ldw_tree_cochange_scan), co the branches on which
+        both change: a pair qualifies when co (nodes - 1) >= ``min_lift`` changes[i] changes[j]; with ``min_len`` >= 0 only pairs whose circular distance
+        exceeds it take part (needs the SNP meta data).  Returns a dict: ``changes`` int32 (L,) the score of every SNP, ``hist`` uint64 (1024,) the qualifying
+        pairs per min(co, 1023), ``best`` int32 (L,) the largest co of every SNP over its qualifying partners (-1: none), ``nge`` int64 (L,) its qualifying
+        partners with co >= ``min_co``, ``npairs`` the pairs of the pair set and ``n_qualifying``."""
+        p, t, pp, tp = self._pars_tree(parent, tip_seq)
+        n = max(self.L, 1)
+        changes, best, nge = np.zeros(n, dtype=np.int32), np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.int64)
+        hist, npairs = np.zeros(1024, dtype=np.uint64), np.zeros(2, dtype=np.int64)
+        L.check(L.lib().ldw_tree_cochange_scan(self._ctx, pp, tp, len(p), int(gap_mode), int(min_changes), int(min_co), int(min_lift), float(min_len), L.ptr(changes),
+                                               L.ptr(hist), L.ptr(best), L.ptr(nge), L.ptr(npairs)))
+        return dict(changes=changes[:self.L], hist=hist, best=best[:self.L], nge=nge[:self.L], npairs=int(npairs[0]), n_qualifying=int(npairs[1]))
+
+    @staticmethod
+    def _cochange_lists(cap):
+        cap = int(cap)
+        return tuple(np.zeros(cap, dtype=np.int32) for _ in range(3)) if cap > 0 else (None, None, None)
+
+    def tree_cochange_links(self, parent, tip_seq, gap_mode: int = 0, min_changes: int = 2, min_co: int = 2, min_lift: int = 0, min_len: float = -1.0, cap: int = 0,
+                            best_in=None):
+        """The qualifying pairs of ``tree_cochange_scan`` with co >= ``min_co`` (ldw_tree_cochange_links): ``a`` < ``b`` (global, 0-based) and ``co``, in no
+        stated order, and ``count``, exact whatever ``cap`` is.  ``cap`` = 0 only counts; a count above ``cap`` raises LdwError LDW_ERR_SIZE, which carries
+        the count as ``.count``.  With ``best_in`` (L,) — the ``best`` of a scan with the same arguments — ``partner`` int32 (L,) is the smallest partner of
+        every SNP among its qualifying ones with co == best_in, -1 where there is none."""
+        p, t, pp, tp = self._pars_tree(parent, tip_seq)
+        a, b, co = self._cochange_lists(cap)
+        bi = None if best_in is None else L.as_c(best_in, np.int32).reshape(self.L)
+        partner = None if bi is None else np.full(max(self.L, 1), -1, dtype=np.int32)
+        n = C.c_int64(0)
+        try:
+            L.check(L.lib().ldw_tree_cochange_links(self._ctx, pp, tp, len(p), int(gap_mode), int(min_changes), int(min_co), int(min_lift), float(min_len), L.ptr(bi),
+                                                    max(int(cap), 0), L.ptr(a), L.ptr(b), L.ptr(co), C.byref(n), L.ptr(partner)))
+        except L.LdwError as e:
+            e.count = int(n.value)
+            raise
+        k = int(n.value)
+        cut = (lambda x: None if x is None else x[:k])
+        return dict(a=cut(a), b=cut(b), co=cut(co), count=k, partner=None if partner is None else partner[:self.L])
+
+    @staticmethod
+    def _cochange_slots(bits, changes, idx, pos):
+        w = L.as_c(bits, np.uint32)
+        assert w.ndim == 2, w.shape
+        words, M = w.shape
+        ch, ix = L.as_c(changes, np.int32).ravel(), L.as_c(idx, np.int32).ravel()
+        ps = None if pos is None else L.as_c(pos, np.int32).ravel()
+        assert len(ch) == M == len(ix) and (ps is None or len(ps) == M), (w.shape, len(ch), len(ix))
+        return w, words, M, ch, ix, ps
+
+    def debug_cochange_scan(self, bits, changes, idx, B, min_co: int = 0, min_lift: int = 0, min_len: float = -1.0, pos=None, g: float = 0.0):
+        """The pair kernel of tree_cochange_scan on caller-made bitmaps (ldw_debug_cochange_scan): ``bits`` uint32 (words, M), ``changes`` (M,), ``idx`` (M,)
+        the ascending global SNP of every slot, ``B`` the branches; ``pos`` (M,) and ``g`` where ``min_len`` >= 0.  Returns ``hist``, ``best`` (M,), ``nge``
+        (M,), ``npairs`` and ``n_qualifying`` over the M slots."""
+        w, words, M, ch, ix, ps = self._cochange_slots(bits, changes, idx, pos)
+        hist, npairs = np.zeros(1024, dtype=np.uint64), np.zeros(2, dtype=np.int64)
+        best, nge = np.full(max(M, 1), -1, dtype=np.int32), np.zeros(max(M, 1), dtype=np.int64)
+        L.check(L.lib().ldw_debug_cochange_scan(self._ctx, L.ptr(w), words, M, L.ptr(ch), L.ptr(ix), L.ptr(ps), float(g), int(B), int(min_co), int(min_lift), float(min_len),
+                                                L.ptr(hist), L.ptr(best), L.ptr(nge), L.ptr(npairs)))
+        return dict(hist=hist, best=best[:M], nge=nge[:M], npairs=int(npairs[0]), n_qualifying=int(npairs[1]))
+
+    def debug_cochange_links(self, bits, changes, idx, B, min_co: int = 0, min_lift: int = 0, min_len: float = -1.0, pos=None, g: float = 0.0, cap: int = 0, best_in=None):
+        """The pair kernel of tree_cochange_links on caller-made bitmaps (ldw_debug_cochange_links), as debug_cochange_scan: the dict of tree_cochange_links
+        over the M slots (``a`` / ``b`` and ``partner`` are global SNPs from ``idx``)."""
+        w, words, M, ch, ix, ps = self._cochange_slots(bits, changes, idx, pos)
+        a, b, co = self._cochange_lists(cap)
+        bi = partner = None
+        if best_in is not None:          # (one entry at least: an empty array has no pointer to give)
+            bi, partner = np.full(max(M, 1), -1, dtype=np.int32), np.full(max(M, 1), -1, dtype=np.int32)
+            bi[:M] = L.as_c(best_in, np.int32).reshape(M)
+        n = C.c_int64(0)
+        try:
+            L.check(L.lib().ldw_debug_cochange_links(self._ctx, L.ptr(w), words, M, L.ptr(ch), L.ptr(ix), L.ptr(ps), float(g), int(B), int(min_co), int(min_lift),
+                                                     float(min_len), L.ptr(bi), max(int(cap), 0), L.ptr(a), L.ptr(b), L.ptr(co), C.byref(n), L.ptr(partner)))
+        except L.LdwError as e:
+            e.count = int(n.value)
+            raise
+        k = int(n.value)
+        cut = (lambda x: None if x is None else x[:k])
+        return dict(a=cut(a), b=cut(b), co=cut(co), count=k, partner=None if partner is None else partner[:M])
+
     # -- the lineage check (DESIGN.md 29) ---------------------------------------
     def seq_clusters(self, thresh):
         """Single-linkage clusters of the resident alignment's sequences (ldw_seq_clusters): i and j are neighbours iff they differ in fewer than
