@@ -972,6 +972,40 @@ int ldw_tree_cochange_links(ldw_ctx *ctx, const int32_t *parent, const int32_t *
                             int64_t min_lift, double min_len, const int32_t *best_in, int64_t cap, int32_t *a_out, int32_t *b_out, int32_t *co_out,
                             int64_t *count_out, int32_t *partner_out);
 
+/* ---- (24) segment x segment map over EVERY SNP pair of a block list, with each cell's best pair ----------------------------------------------
+ * ldw_mi_segment_map and ldw_mi_segment_best require and refuse what ldw_mi_profile does (20): the alignment, the weights and the SNP meta data; blocks
+ * diagonal or disjoint.  Blocks, pair set and per-pair values are exactly those of (20)-(22) under the same quirk_mode.
+ *   segments     seg[L] (HOST) labels the SNPs: seg[i] in -1..S-1, S in 1..8192 (LDW_ERR_ARG otherwise, the message naming the first bad index).  A pair with
+ *                either SNP at -1 takes part in nothing.  The ids need not be contiguous runs or ascend along the genome: equal ids far apart are one segment.
+ *   class mask   sr_dist and cls_mask exactly as (22); pairs outside the mask take part in nothing.
+ *   the value    of the pair of the global SNPs (A, B): v = mi when w == NULL, else v = mi - w[A] * w[B], the score of (22) (csrc/ldw_score.h); w[L] (HOST) must
+ *                be finite (LDW_ERR_ARG, the message naming the index).
+ *   the cell     of a pair is (min(seg[A], seg[B]), max(seg[A], seg[B])): a pair counts once, whichever SNP is the from-SNP.  Every matrix is row-major [S][S];
+ *                only cells with row <= column are written, the rest stay 0 (NaN in max_out).
+ * ldw_mi_segment_map — per cell (HOST):
+ *   n_out        the number of pairs.
+ *   nge_out      (may be NULL) the pairs with v >= thr, an fp64 comparison: a NaN value never counts, thr = +inf counts nothing.
+ *   sum_lo_out, sum_hi_out  (both or neither) the sum of q(v) = llrint(v * 2^40), the product and the rounding of (21), in two words so that no cell can overflow:
+ *                sum_lo = sum of (q & (2^24 - 1)), sum_hi = sum of (q >> 24) (an arithmetic shift); the exact sum is sum_hi * 2^24 + sum_lo
+ *                (csrc/ldw_segmap.h).  A value that is not finite or has |v| >= 4 adds 0 to both words and is counted (ldw_segment_map_report); it still counts
+ *                in n, nge and max.  With |q| <= 2^42 both words stay below 2^63 for any cell of fewer than 2^39 pairs; a block list of 2^39 pairs or more is
+ *                LDW_ERR_SIZE.  The mean value of a cell is (sum_hi * 2^24 + sum_lo) / n / 2^40.
+ *   max_out      (may be NULL) the largest value in the order of the IEEE bits (-0 below +0), the device's own bits; NaN where n == 0.  A NaN value is never a
+ *                maximum (a cell of NaN values only has NaN).
+ *   *npairs_out  the pairs inside the mask with both segments >= 0: the sum of n_out.
+ * ldw_mi_segment_best — pair_out[S * S] (uint64): per cell the smallest ((uint64)min(A, B) << 32) | max(A, B) over the cell's pairs inside the mask whose value
+ *   has the key of max_in[cell] (equal IEEE bits); all-ones where max_in[cell] is NaN or nothing matches.  With max_in = max_out of a map call with the same
+ *   arguments it names the pair behind each maximum.  A 64-bit integer minimum.
+ * Integer adds, maxima of an ordered key and integer minima only: nothing depends on the order of evaluation, and there is no floating-point atomic.  Device
+ * memory: 40 S^2 bytes for the map (16 S^2 for the best pairs) plus the per-SNP vectors, one working buffer that the call takes and gives back.  The link
+ * tables and the ldw_block_stats of an earlier pass stay as they were.  ldw_ctx_last_timing afterwards: [0] the blocks' GEMM + epilogue, [1] this entry's
+ * kernels, [2] 0, [3] their sum.  Both calls run on the context's stream and return when the outputs are written. */
+int ldw_mi_segment_map(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int quirk_mode, const int32_t *seg, int32_t S, double sr_dist, int cls_mask,
+                       const double *w, double thr, int64_t *n_out, int64_t *nge_out, int64_t *sum_lo_out, int64_t *sum_hi_out, double *max_out,
+                       int64_t *npairs_out);
+int ldw_mi_segment_best(ldw_ctx *ctx, const int32_t *blocks, int64_t nblocks, int quirk_mode, const int32_t *seg, int32_t S, double sr_dist, int cls_mask,
+                        const double *w, const double *max_in, uint64_t *pair_out);
+
 /* ---- small native helpers kept for finest-grain A/B parity (host memory) -------------------- */
 /* .compareToRow src/computeMI.cpp:25-41: ret[j] = any(x[j,] in y); x is nr x nc column-major */
 int ldw_compare_to_row(const double *x, int64_t nr, int64_t nc, const double *y, int64_t ny, uint8_t *ret);

@@ -334,6 +334,28 @@ int ldw_debug_cochange_links(ldw_ctx *ctx, const uint32_t *bits, int64_t words, 
                              int64_t B, int32_t min_co, int64_t min_lift, double min_len, const int32_t *best_in, int64_t cap, int32_t *a_out, int32_t *b_out,
                              int32_t *co_out, int64_t *count_out, int32_t *partner_out);
 
+/* ---- the segment map (ldweaver_amd.h 24) ---------------------------------------------------------------------------------------------------------------------
+ * ldw_debug_segment_map / ldw_debug_segment_best: the kernels of ldw_mi_segment_map and ldw_mi_segment_best (k_segment) as functions, on caller-made values;
+ *   they need no alignment.  mi, nf, nt, pos_f, pos_t, g and diag as ldw_debug_snp_summary (mi may hold any double); seg_f[nf] / seg_t[nt] the segments of the
+ *   two sides, S, sr_dist, cls_mask and thr as (24); w_f[nf] / w_t[nt] the weights of the two sides, finite, both or neither.  The outputs are those of (24).
+ *   best: id_f[nf] / id_t[nt] the global ids of the two sides, 0..2^31 - 2, in any order; max_in[S * S] and pair_out[S * S] as (24), packed from the ids.
+ *   The kernel works in patches of 64 rows x 256 columns and cuts the segment ids of a patch's rows and columns into runs.  route: 0 = a patch of at most 8
+ *   row runs and 16 column runs keeps a window of cells in LDS (route 1), any other adds per pair, the lanes of a cell combined (route 2); 1 = route 1,
+ *   LDW_ERR_ARG (outputs undefined) when a patch does not fit; 2 = route 2 for every patch.  All give the same bytes.  stats_out (may be NULL, 4 values): patches
+ *   visited (every patch but a diagonal block's patches that lie wholly on or above the diagonal), patches on route 2, values q refused (map only; NaN
+ *   included), NaN values.
+ *   LDW_ERR_ARG: nf, nt outside 1..1 000 000, diag with nf != nt, g not positive, route outside 0..2, one of w_f / w_t alone, what (24) refuses, an id outside
+ *   its range.
+ * ldw_segment_map_report: out[0..3] the same four counts summed over the last ldw_mi_segment_map or ldw_mi_segment_best of the context, out[4] its blocks. */
+int ldw_debug_segment_map(ldw_ctx *ctx, const double *mi, int64_t nf, int64_t nt, const int32_t *pos_f, const int32_t *pos_t, double g, int diag,
+                          const int32_t *seg_f, const int32_t *seg_t, int32_t S, double sr_dist, int cls_mask, const double *w_f, const double *w_t, double thr,
+                          int route, int64_t *n_out, int64_t *nge_out, int64_t *sum_lo_out, int64_t *sum_hi_out, double *max_out, int64_t *npairs_out,
+                          int64_t *stats_out);
+int ldw_debug_segment_best(ldw_ctx *ctx, const double *mi, int64_t nf, int64_t nt, const int32_t *pos_f, const int32_t *pos_t, double g, int diag,
+                           const int32_t *seg_f, const int32_t *seg_t, int32_t S, double sr_dist, int cls_mask, const int32_t *id_f, const int32_t *id_t,
+                           const double *w_f, const double *w_t, const double *max_in, int route, uint64_t *pair_out, int64_t *stats_out);
+int ldw_segment_map_report(ldw_ctx *ctx, int64_t out[5]);
+
 /* ---- the plots (ldweaver_amd.h 12) ------------------------------------------------------------------------------------------------ */
 /* The rasters of ldw_plot_scatter without the frame, for panels of W x H pixels each (any size >= 1): rgb_out[n_panels][H][W][3] (host).  Grid
  * lines lie at the ticks of ldw_plot_ticks for the data range and W / H.  stats_out (may be NULL, 8 doubles): x min, x max, y min, y max of

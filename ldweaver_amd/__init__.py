@@ -21,6 +21,7 @@ _EXPORTS = {
     "ld_decay": "decay", "LDDecay": "decay", "default_cuts": "decay",
     "snp_background": "background", "SnpBackground": "background", "link_apc": "background",
     "apc_links": "background", "pick_threshold": "background",
+    "gene_map": "genemap", "GeneMap": "genemap", "segments_from_features": "genemap", "segments_from_annotation": "genemap", "segments_equal": "genemap",
     "sequence_clusters": "lineage", "link_lineage_mi": "lineage", "link_permutation_test": "lineage",
 }
 __all__ = sorted(_EXPORTS)

@@ -170,6 +170,8 @@ _SIGS_API = {
     "ldw_mi_score_links": (C.c_int, [_p, _p, _i64, C.c_int, C.c_double, C.c_int, _p, C.c_double, _p, _i64, _p, _p, _p, _p, C.POINTER(_i64), _p]),
     "ldw_tree_cochange_scan": (C.c_int, [_p, _p, _p, _i64, C.c_int32, C.c_int32, C.c_int32, _i64, C.c_double, _p, _p, _p, _p, _p]),
     "ldw_tree_cochange_links": (C.c_int, [_p, _p, _p, _i64, C.c_int32, C.c_int32, C.c_int32, _i64, C.c_double, _p, _i64, _p, _p, _p, C.POINTER(_i64), _p]),
+    "ldw_mi_segment_map": (C.c_int, [_p, _p, _i64, C.c_int, _p, C.c_int32, C.c_double, C.c_int, _p, C.c_double, _p, _p, _p, _p, _p, C.POINTER(_i64)]),
+    "ldw_mi_segment_best": (C.c_int, [_p, _p, _i64, C.c_int, _p, C.c_int32, C.c_double, C.c_int, _p, _p, _p]),
     "ldw_tsv_probe": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ldw_tsv_read": (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int32, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_uint32)]),
     "ldw_tsv_columns": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_i64), C.POINTER(C.c_int32), C.POINTER(_i64)]),
@@ -231,6 +233,10 @@ _SIGS_DEBUG = {
     "ldw_debug_score_links": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_double, C.c_int, C.c_double, C.c_int, _p, _p, _p, _p, C.c_double, _p, _p, _i64, _p, _p, _p, _p,
                                         C.POINTER(_i64), _p, _p, _p]),
     "ldw_score_select_report": (C.c_int, [_p, _p]),
+    "ldw_debug_segment_map": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_double, C.c_int, _p, _p, C.c_int32, C.c_double, C.c_int, _p, _p, C.c_double, C.c_int, _p, _p, _p, _p, _p,
+                                        C.POINTER(_i64), _p]),
+    "ldw_debug_segment_best": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_double, C.c_int, _p, _p, C.c_int32, C.c_double, C.c_int, _p, _p, _p, _p, _p, C.c_int, _p, _p]),
+    "ldw_segment_map_report": (C.c_int, [_p, _p]),
     "ldw_debug_cochange_scan": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, C.c_double, _i64, C.c_int32, _i64, C.c_double, _p, _p, _p, _p]),
     "ldw_debug_cochange_links": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, C.c_double, _i64, C.c_int32, _i64, C.c_double, _p, _i64, _p, _p, _p, C.POINTER(_i64), _p]),
     "ldw_debug_plot_panels": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, C.c_int, _p, C.c_int, C.c_int32, C.c_int32, _p, _p, C.POINTER(_i64), _p]),

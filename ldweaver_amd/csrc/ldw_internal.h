@@ -397,6 +397,7 @@ struct ldw_ctx {
     int64_t decay_stat[4] = {0, 0, 0, 0};            // ldw_decay_report: patches, route-B patches, pairs outside their patch's bound and blocks of the last ldw_mi_profile
     int64_t snpsum_stat[5] = {0, 0, 0, 0, 0};        // ldw_snp_summary_report: patches, general-route patches, pairs off their patch's class, values q refused and blocks of the last ldw_mi_snp_summary
     int64_t scoresel_stat[3] = {0, 0, 0};            // ldw_score_select_report: patches visited, NaN scores and blocks of the last ldw_mi_score_scan or ldw_mi_score_links
+    int64_t segmap_stat[5] = {0, 0, 0, 0, 0};        // ldw_segment_map_report: patches visited, patches on route 2, values q refused, NaN values and blocks of the last ldw_mi_segment_map or ldw_mi_segment_best
     double ham_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ldw_hamming_stats: columns, padded K, stage times and algorithmic bytes of the last ldw_hamming_weights
     ldw::DevBuf plot_work, plot_cols;   // the plots (ldw_plot.hip): key image + rasters + partials; device copy of a chunk of host columns
 

@@ -505,6 +505,97 @@ class Engine:
         cut = (lambda x: None if x is None else x[:k])
         return dict(a=cut(a), b=cut(b), mi=cut(mo), score=cut(sc), count=k, partner_f=prf, partner_t=prt, stats=st)
 
+    # -- the segment map --------------------------------------------
+    @staticmethod
+    def _segmap_side(S):
+        return int(S) if 1 <= int(S) <= 8192 else 1      # (an S the library refuses: any shape will do)
+
+    @staticmethod
+    def _segmap_outputs(S):
+        S = Engine._segmap_side(S)
+        n, nge, lo, hi = (np.zeros((S, S), dtype=np.int64) for _ in range(4))
+        return n, nge, lo, hi, np.full((S, S), np.nan)
+
+    def _segmap_vectors(self, seg, w):
+        sg = L.as_c(seg, np.int32).ravel()
+        wv = None if w is None else L.as_c(w, np.float64).ravel()
+        if self.L and (len(sg) != self.L or (wv is not None and len(wv) != self.L)):      # (without an alignment the library refuses the call itself)
+            raise ValueError(f"seg and w take one entry per SNP ({self.L}), got {len(sg)}" + ("" if wv is None else f" and {len(wv)}"))
+        return sg, wv
+
+    def mi_segment_map(self, blocks, seg, S, sr_dist, cls_mask, w=None, thr=np.inf, quirk=L.QUIRK_REFERENCE):
+        """Over EVERY SNP pair of ``blocks`` inside the class mask (1: len <= sr_dist, 2: beyond, 3: both), per cell (min(seg[a], seg[b]), max(seg[a], seg[b]))
+        of the value v = mi, or mi - w[a] w[b] with ``w`` (ldw_mi_segment_map): ``n`` the pairs, ``nge`` the pairs with v >= thr, ``sum_lo`` / ``sum_hi`` the
+        two words of the sum of llrint(v 2^40) (the exact sum is sum_hi 2^24 + sum_lo), each int64 (S, S), ``max`` float64 (S, S) the largest value (NaN where
+        n == 0) and ``npairs``.  ``seg`` (L,) in -1..S-1; a pair with a SNP at -1 takes no part.  Only cells with row <= column are written.  The link tables
+        stay as they are."""
+        bl = L.as_c(blocks, np.int32).reshape(-1, 4)
+        sg, wv = self._segmap_vectors(seg, w)
+        n, nge, lo, hi, mx = self._segmap_outputs(S)
+        npairs = C.c_int64(0)
+        L.check(L.lib().ldw_mi_segment_map(self._ctx, L.ptr(bl), len(bl), int(quirk), L.ptr(sg), int(S), float(sr_dist), int(cls_mask), L.ptr(wv), float(thr), L.ptr(n),
+                                           L.ptr(nge), L.ptr(lo), L.ptr(hi), L.ptr(mx), C.byref(npairs)))
+        return dict(n=n, nge=nge, sum_lo=lo, sum_hi=hi, max=mx, npairs=int(npairs.value))
+
+    def mi_segment_best(self, blocks, seg, S, sr_dist, cls_mask, max_in, w=None, quirk=L.QUIRK_REFERENCE):
+        """Per cell of ``mi_segment_map``'s pair set the smallest packed pair (min(a, b) << 32 | max(a, b), uint64 (S, S)) whose value has the bits of
+        ``max_in`` (S, S) (ldw_mi_segment_best); all-ones where max_in is NaN or nothing matches.  With ``max_in`` the ``max`` of a map call with the same
+        arguments it names the pair behind each maximum."""
+        bl = L.as_c(blocks, np.int32).reshape(-1, 4)
+        sg, wv = self._segmap_vectors(seg, w)
+        S_ = self._segmap_side(S)
+        mi_ = L.as_c(max_in, np.float64).reshape(S_, S_)
+        pair = np.full((S_, S_), np.uint64(0xFFFFFFFFFFFFFFFF), dtype=np.uint64)
+        L.check(L.lib().ldw_mi_segment_best(self._ctx, L.ptr(bl), len(bl), int(quirk), L.ptr(sg), int(S), float(sr_dist), int(cls_mask), L.ptr(wv), L.ptr(mi_), L.ptr(pair)))
+        return pair
+
+    def segment_map_report(self):
+        """Of the last mi_segment_map or mi_segment_best (ldw_segment_map_report): patches the kernel visited, those on route 2, values the fixed point
+        refused, NaN values, blocks."""
+        v = np.zeros(5, dtype=np.int64)
+        L.check(L.lib().ldw_segment_map_report(self._ctx, L.ptr(v)))
+        return dict(patches=int(v[0]), general=int(v[1]), refused=int(v[2]), nan_values=int(v[3]), blocks=int(v[4]))
+
+    @staticmethod
+    def _segmap_block(mi, pos_f, pos_t, seg_f, seg_t, w_f, w_t):
+        m = np.asarray(mi, dtype=np.float64)
+        assert m.ndim == 2, m.shape
+        nf, nt = m.shape
+        pf, pt = L.as_c(pos_f, np.int32).ravel(), L.as_c(pos_t, np.int32).ravel()
+        sf, st = L.as_c(seg_f, np.int32).ravel(), L.as_c(seg_t, np.int32).ravel()
+        wf = None if w_f is None else L.as_c(w_f, np.float64).ravel()
+        wt = None if w_t is None else L.as_c(w_t, np.float64).ravel()
+        assert len(pf) == nf == len(sf) and len(pt) == nt == len(st), (len(pf), len(pt), len(sf), len(st), m.shape)
+        assert (wf is None or len(wf) == nf) and (wt is None or len(wt) == nt)
+        return np.asfortranarray(m), nf, nt, pf, pt, sf, st, wf, wt
+
+    def debug_segment_map(self, mi, pos_f, pos_t, g, diag, seg_f, seg_t, S, sr_dist, cls_mask, w_f=None, w_t=None, thr=np.inf, route: int = 0):
+        """The kernel of mi_segment_map on caller-made values (ldw_debug_segment_map): ``mi`` (nf, nt) (stored column-major for the call), the positions and
+        the segments of the two sides, the genome length, ``diag`` (pairs a > b of a square block) or not (pairs a != b); the weights of the two sides both or
+        neither.  route 0: every patch chooses, 1: the LDS window of runs (LdwError LDW_ERR_ARG where a patch does not fit), 2: per-pair global operations.
+        Returns the dict of mi_segment_map plus ``stats`` (patches visited, route-2 patches, values refused, NaN values)."""
+        mf, nf, nt, pf, pt, sf, st, wf, wt = self._segmap_block(mi, pos_f, pos_t, seg_f, seg_t, w_f, w_t)
+        n, nge, lo, hi, mx = self._segmap_outputs(S)
+        npairs, stats = C.c_int64(0), np.zeros(4, dtype=np.int64)
+        L.check(L.lib().ldw_debug_segment_map(self._ctx, L.ptr(mf), nf, nt, L.ptr(pf), L.ptr(pt), float(g), int(bool(diag)), L.ptr(sf), L.ptr(st), int(S), float(sr_dist),
+                                              int(cls_mask), L.ptr(wf), L.ptr(wt), float(thr), int(route), L.ptr(n), L.ptr(nge), L.ptr(lo), L.ptr(hi), L.ptr(mx),
+                                              C.byref(npairs), L.ptr(stats)))
+        return dict(n=n, nge=nge, sum_lo=lo, sum_hi=hi, max=mx, npairs=int(npairs.value), stats=stats)
+
+    def debug_segment_best(self, mi, pos_f, pos_t, g, diag, seg_f, seg_t, S, sr_dist, cls_mask, id_f, id_t, max_in, w_f=None, w_t=None, route: int = 0):
+        """The kernel of mi_segment_best on caller-made values (ldw_debug_segment_best), as debug_segment_map; ``id_f`` / ``id_t`` the global ids of the two
+        sides.  Returns ``pair`` uint64 (S, S) and ``stats``."""
+        mf, nf, nt, pf, pt, sf, st, wf, wt = self._segmap_block(mi, pos_f, pos_t, seg_f, seg_t, w_f, w_t)
+        idf, idt = L.as_c(id_f, np.int32).ravel(), L.as_c(id_t, np.int32).ravel()
+        assert len(idf) == nf and len(idt) == nt, (len(idf), len(idt))
+        S_ = self._segmap_side(S)
+        mi_ = L.as_c(max_in, np.float64).reshape(S_, S_)
+        pair = np.full((S_, S_), np.uint64(0xFFFFFFFFFFFFFFFF), dtype=np.uint64)
+        stats = np.zeros(4, dtype=np.int64)
+        L.check(L.lib().ldw_debug_segment_best(self._ctx, L.ptr(mf), nf, nt, L.ptr(pf), L.ptr(pt), float(g), int(bool(diag)), L.ptr(sf), L.ptr(st), int(S), float(sr_dist),
+                                               int(cls_mask), L.ptr(idf), L.ptr(idt), L.ptr(wf), L.ptr(wt), L.ptr(mi_), int(route), L.ptr(pair), L.ptr(stats)))
+        return dict(pair=pair, stats=stats)
+
     def debug_screen_bound(self, kind: int, na: int, nb: int, g, pa, pb, pX, pY, rr, params, masks=None):
         """The engine's screen / evaluation device functions on caller-made joint tables (ldw_debug_screen_bound): kind 0 / 1 the approximate path's upper
         bounds (straight-line / predicated), 2 / 3 the fp32 MI of the exact-limb screens, 4 the fp64 value the engine emits."""

@@ -271,6 +271,30 @@ def render_heatmap(eng, htm, path, title=None):
                                      os.fsencode(path), None))
 
 
+GENE_MAP_BY = ("frac", "max", "mean")
+
+
+def gene_map_matrix(gm, by: str = "frac") -> np.ndarray:
+    """What ``gene_map_plot`` draws, a pure host function: ``gm.symmetric(by)`` divided by its largest finite value, clipped to [0, 1]; a cell without a
+    pair, a non-finite value and everything when no value is positive become 0."""
+    if by not in GENE_MAP_BY:
+        raise ValueError(f"by must be one of {GENE_MAP_BY}, got {by!r}")
+    m = np.asarray(gm.symmetric(by), dtype=np.float64)
+    fin = np.isfinite(m)
+    top = m[fin].max() if fin.any() else 0.0
+    if not top > 0:
+        return np.zeros_like(m)
+    return np.clip(np.where(fin, m, 0.0) / top, 0.0, 1.0)
+
+
+def gene_map_plot(gm, path, by: str = "frac", *, engine=None) -> str:
+    """Of ``gm`` (``genemap.GeneMap``): the symmetrised segment x segment matrix ``by`` (frac, max or mean), rescaled to [0, 1] by its finite maximum
+    (``gene_map_matrix``), as the heat map of ``LD_plot.png`` (ldw_plot_heatmap): segment 0 at the bottom left.  Returns the path."""
+    h = gene_map_matrix(gm, by)
+    _with_engine(engine, lambda eng: render_heatmap(eng, h, path, title=f"Gene map ({by})"))
+    return str(path)
+
+
 # ---- the readers of R/io_functions.R:32-66 ---------------------------------------------------------------------------------------------------
 
 def read_ShortRangeLinks(sr_links_path, reader: str = "pandas"):
